@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- the AGMV hot path on MI355X: frames/s encode+decode, and the HBM roofline of the
-dominant kernel, next to the reference CPU path timed on the same box.
+dominant kernel; with --full, the reference CPU path timed on the same box beside it.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5] [--frames T] [--backend nccl|gloo]
-                  [--no-cpu-baseline] [--no-normal-heavy] [--no-secondary]
+                  [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-normal-heavy] [--no-secondary]]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
               --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,6 +17,20 @@ Workload (BASELINE.json configs):
                 (512 colours) -- the configuration the roofline target is quoted on
   c2            212 source frames 320x240 -> the 156 encoded frames of AGMV_EncodeAGMV/OPT_III (light PDIFS)
   c5            1280x720 clip (use --frames; 8192 frames need ~70 GB of HBM per GPU)
+A plain run sets up, warms up, times the K steps and prints the result line (plus --dump-outputs).  --full adds, after
+the timed region, the legs that take runs of their own: the CPU baseline (the reference's CPU path on a sample of the
+same clip, checked against the GPU's bitstreams and pixels), k_encode on NORMAL-heavy content, and the 320x240 lines.
+
+--dump-outputs DIR: after the timed steps, what the last step handed back (rank 0's), as float .npy files (under 64 MB):
+  sizes, nentered              float64 [T]    bitstream bytes per frame, blocks the decoder reached per frame
+  frame_index                  float64 [k]    the frames dumped whole: 0, T-1, then seeded picks while the budget lasts
+  bitstreams                   float32 [k, L] those frames' bitstream bytes, zero past each frame's size
+  decoded                      float32 [k, H, W, 3]  their decoded pixels as R, G, B
+  decoded_sample               float32 [S, 3] R, G, B at S seeded positions over the whole batch (decoded_sample_index:
+                                              float64 [S], frame * W * H + pixel)
+  bitstream_sample             float32 [S]    bytes at S seeded positions inside the frames' bitstreams
+The inputs are synthetic and fixed by the arguments, so two builds can be compared output for output.
+
 Multi-GPU: weak scaling by default -- every rank encodes+decodes its own T-frame clip (frames r*T .. r*T+T-1 of one
 long clip), value = N*T*K / max-over-ranks time.  --scaling strong: ONE T-frame clip (configs 4 and 5) is split over the
 ranks by GOP range (libagmv_amd.shard.gop_ranges), value = T*K / max-over-ranks time.  Either way the only collectives are
@@ -44,20 +58,28 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="c3", choices=["c3", "c2", "c5"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the CPU baseline, the NORMAL-heavy k_encode run and the 320x240 lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32/float64, under 64 MB)")
     ap.add_argument("--no-normal-heavy", action="store_true",
-                    help="skip the k_encode run on a NORMAL-heavy variant of the clip (roofline_normal_heavy; it runs AFTER the timed region -- "
-                         "use this switch for a profile that should hold the headline launches only)")
+                    help="with --full: skip the k_encode run on a NORMAL-heavy variant of the clip (roofline_normal_heavy; it runs AFTER the timed region)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the 320x240 lines (secondary.c2: the 156 encoded frames of config 2; secondary.c2_large: 8192 frames), "
+                    help="with --full: skip the 320x240 lines (secondary.c2: the 156 encoded frames of config 2; secondary.c2_large: 8192 frames), "
                          "which also run after the timed region")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo lets several ranks share ONE card to rehearse the multi-rank path)")
     ap.add_argument("--frames", type=int, default=0, help="frames per GPU (default: the workload's)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank its own clip of --frames frames; strong: ONE clip of --frames frames split over the ranks by GOP range")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames of the CPU baseline sample")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def workload(args):
@@ -72,12 +94,24 @@ def workload(args):
 
 
 def host_lib():
-    from libagmv_amd import build
-    build.build()
-    L = C.CDLL(os.path.join(ROOT, "libagmv_amd", "libagmv.so"))
+    """libagmv.so as build() left it.  The benchmark builds nothing: it may run in a tree it cannot write."""
+    path = os.path.join(ROOT, "libagmv_amd", "libagmv.so")
+    if not os.path.exists(path):
+        raise SystemExit("bench: %s is missing: run __graft_entry__.build() (or python -m libagmv_amd.build) first" % path)
+    L = C.CDLL(path)
     L.AGMV_BuildPalette.restype = None
     L.AGMV_BuildPalette.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.agmv_lzss_mem.restype = C.c_ulong
+    L.agmv_lzss_mem.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
     return L
+
+
+def lzss(L, data):
+    """libagmv.so's exact LZSS of one bitstream: (compressed bytes, csize)"""
+    src = np.concatenate([np.ascontiguousarray(data, np.uint8), np.zeros(8, np.uint8)])
+    out = np.zeros(2 * len(data) + 64, np.uint8)
+    cs = int(L.agmv_lzss_mem(src.ctypes.data, len(data), out.ctypes.data))
+    return out[:cs].copy(), cs
 
 
 def cpu_baseline(wl, p0, p1, frames_np, gpu_bits, gpu_pix=None, gpu_decode=None):
@@ -110,7 +144,7 @@ def cpu_baseline(wl, p0, p1, frames_np, gpu_bits, gpu_pix=None, gpu_decode=None)
     dec_kind = kind
     if kind == "reference":
         import tempfile
-        import hostlib as HL
+        HL = host_lib()
         L = O.ref()
         a = L.refshim_create(W, H, O.OPT_III, O.LZSS, np.ascontiguousarray(p0, np.uint32), np.ascontiguousarray(p1, np.uint32))
         tmp = os.path.join(tempfile.mkdtemp(prefix="agmv_bench_"), "sample.agmv")
@@ -118,7 +152,7 @@ def cpu_baseline(wl, p0, p1, frames_np, gpu_bits, gpu_pix=None, gpu_decode=None)
         L.refshim_destroy(a)
         with open(tmp, "ab") as fh:
             for k, b in enumerate(bits):
-                comp, cs = HL.lzss(b)
+                comp, cs = lzss(HL, b)
                 fh.write(b"AGFC" + np.array([k + 1, len(b), cs], "<u4").tobytes() + comp.tobytes() + b"\xff" * 8)
         err = C.c_int(0)
         w_, h_, n_, v_ = (C.c_uint32(0) for _ in range(4))
@@ -272,6 +306,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     hip.check()
+    if args.dump_outputs and rank == 0:                       # before the --full legs, which re-use out / sizes
+        dump_outputs(args.dump_outputs, torch, out, sizes, dec, nent)
 
     # ------------------------------------------------------------------ results
     usz = sizes.cpu().numpy().astype(np.int64)
@@ -353,7 +389,7 @@ def main():
             res["final_gather_ms"] = round(gather_ms, 3)
         if gather_err is not None:
             res["final_gather_error"] = gather_err
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             n_cpu = args.cpu_frames or (8 if npx > 500000 else 32)
             n_cpu = min(n_cpu, n_enc)
             f_np = frames[:n_cpu].cpu().numpy().view(np.uint32)
@@ -369,9 +405,9 @@ def main():
                 torch.cuda.synchronize()
                 return px.cpu().numpy().view(np.uint32).reshape(len(bits_list), -1)
             res["cpu_baseline"] = cpu_baseline(wl, p0, p1, list(f_np), gpu_bits, gpu_pix, gpu_decode)
-        if not args.no_normal_heavy and world == 1 and npx > 500000 and args.scaling == "weak":     # (after the timed region: it re-uses the bitstream slab)
+        if args.full and not args.no_normal_heavy and world == 1 and npx > 500000 and args.scaling == "weak":     # (after the timed region: it re-uses the bitstream slab)
             res["roofline_normal_heavy"] = normal_heavy_leg(torch, hip, frames, W, H, first_fc, out, sizes)
-        if not args.no_secondary and world == 1 and args.workload == "c3" and args.scaling == "weak":
+        if args.full and not args.no_secondary and world == 1 and args.workload == "c3" and args.scaling == "weak":
             del dec
             res["secondary"] = secondary_legs(torch, local_rank, dev)
         print(json.dumps(res))
@@ -382,6 +418,52 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     hip.close()
+
+
+DUMP_BUDGET = 63_000_000        # bytes of .npy payload --dump-outputs writes at most (the limit is 64 MB)
+DUMP_SAMPLE = 1 << 18           # seeded positions of decoded_sample / bitstream_sample
+
+
+def dump_outputs(dirname, torch, out, sizes, dec, nent, seed=20240601):
+    """the last timed step's bitstreams (out, sizes), decoder block counts (nent) and pixels (dec), as float arrays: whole
+    frames 0 and T-1 and seeded picks while DUMP_BUDGET lasts, plus fixed seeded samples over the whole batch"""
+    os.makedirs(dirname, exist_ok=True)
+    n, H, W = dec.shape
+    npx = W * H
+    usz = sizes.cpu().numpy().astype(np.int64)
+    rng = np.random.default_rng(seed)
+    rgb = lambda v: torch.stack([(v >> 16) & 255, (v >> 8) & 255, v & 255], dim=-1).float()
+
+    arrays = {"sizes": usz.astype(np.float64), "nentered": nent.cpu().numpy().astype(np.float64)}
+    s = min(DUMP_SAMPLE, n * npx)
+    pidx = np.sort(rng.integers(0, n * npx, size=s))
+    arrays["decoded_sample_index"] = pidx.astype(np.float64)
+    arrays["decoded_sample"] = rgb(dec.reshape(-1)[torch.from_numpy(pidx).to(dec.device)]).cpu().numpy()
+    bf = np.flatnonzero(usz > 0)[rng.integers(0, int((usz > 0).sum()), size=s)]   # (frame, byte) inside each frame's size:
+    bb = np.floor(rng.random(s) * usz[bf]).astype(np.int64)                        # the bytes behind it are never written
+    arrays["bitstream_sample"] = out.reshape(-1)[torch.from_numpy(bf * out.stride(0) + bb).to(out.device)].float().cpu().numpy()
+
+    used = sum(a.nbytes for a in arrays.values())
+    order = [0] + ([n - 1] if n > 1 else []) + [int(f) + 1 for f in rng.permutation(max(0, n - 2))]
+    pick, maxlen = [], 0
+    for f in order:
+        L = max(maxlen, int(usz[f]))
+        if used + (len(pick) + 1) * (npx * 3 * 4 + L * 4) + 8 * (len(pick) + 1) > DUMP_BUDGET:
+            break
+        pick.append(f)
+        maxlen = L
+    pick.sort()
+    arrays["frame_index"] = np.array(pick, np.float64)
+    bits = np.zeros((len(pick), maxlen), np.float32)
+    dec_frames = np.zeros((len(pick), H, W, 3), np.float32)
+    for k, f in enumerate(pick):
+        bits[k, :usz[f]] = out[f, :usz[f]].cpu().numpy()
+        dec_frames[k] = rgb(dec[f]).cpu().numpy()
+    arrays["bitstreams"] = bits
+    arrays["decoded"] = dec_frames
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def normal_heavy_leg(torch, hip, frames, W, H, first_fc, out, sizes, n=256):
