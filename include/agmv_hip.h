@@ -166,8 +166,13 @@ int agmv_hip_decode_bitstreams_dev(agmv_hip_ctx* ctx, const uint8_t* d_bits, siz
 /* After agmv_hip_decode_frames_dev / agmv_hip_parse_decode_frames_dev / agmv_hip_decode_bitstreams_dev: 1 when a pixel of that batch derives from d_prev_frame / d_prev_iframe (a block the
    bitstream did not rewrite before it was read: stale tail after `escape`, COPY in the first GOP, a FILL / NORMAL block cut
    off by bpos -- reference src/agmv_decode.c:229-232, :268-271, :277-285, :310-314), 0 when the batch is a function of its
-   own bitstreams alone, negative on error.  What a GOP-sharded decode needs to know before it trusts a range decoded from
-   the fresh state (never 1 for a stream the encoder emits).  Synchronises the stream. */
+   own bitstreams alone, negative on error.  Exact: tracked per pixel over the whole batch (a batch that starts inside a GOP
+   also depends through a COPY in its first I-frame, which reads d_prev_iframe), so 1 means some output pixel changes with
+   the prior state.  What a GOP-sharded decode needs to know before it trusts a range decoded from the fresh state.  Never 1 for a
+   stream the encoder emits that starts at a GOP boundary, with one exception: at width 4 (one block per row) a FILL as the
+   last block of the first frame stores the block's own pixel (3,0) of d_prev_frame (the reference's x-1 wraps, :264-266).
+   A decode_bitstreams call cut into parts (more than 65532 frames) reports its dependence on the caller's state, i.e. that
+   of its first part: later parts continue from the output of the part before them.  Synchronises the stream. */
 int agmv_hip_decode_prior_dependent(agmv_hip_ctx* ctx, uint32_t w, uint32_t h, void* stream);
 /* host-memory convenience: parse on the GPU, reconstruct, copy back (synchronous) */
 int agmv_hip_decode_frames(agmv_hip_ctx* ctx, const uint8_t* h_bits, size_t bits_stride,

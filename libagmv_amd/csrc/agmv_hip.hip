@@ -102,6 +102,7 @@ struct agmv_hip_ctx {
 	size_t ient_cap;                // in entries
 	uint32_t* d_dirty;              // decode: bitmap of block positions needing the fix-up
 	size_t dirty_cap;               // in words
+	bool dep_split;                 // the last decode call was cut into parts: its prior dependence is part 0's, saved behind the bitmap
 	int enc_grid;                   // resident workgroups for the persistent encode kernel
 	int n_cu;
 	uint32_t* d_parse_ws;           // parser workspace: cum | centry | summ
@@ -1742,11 +1743,12 @@ struct DecArgs {
 
 // one 4x4 block of D2 (512 colours, src/agmv_decode.c:234-319) or D3 (256 colours, :335-396).
 // `cur` is the block's img_data, `icol` the block's iframe->img_data.  fill_written reports a
-// FILL that stored pixels (the caller applies the last-block quirk, :264-266).
+// FILL that stored pixels (the caller applies the last-block quirk, :264-266).  stale / istale: bit k set when pixel k of
+// cur / icol still derives from the state before the GOP (per pixel: a NORMAL block cut off by bpos stores a prefix).
 template <bool M512, class Src>
 __device__ __forceinline__ void decode_block(const Src& src, uint32_t bitpos, const uint32_t bpos,
                                              const uint32_t* pal, uint32_t (&cur)[16], const uint32_t (&icol)[16],
-                                             bool istale, bool& stale, bool& fill_written)
+                                             uint32_t istale, uint32_t& stale, bool& fill_written)
 {
 	fill_written = false;
 	uint32_t byte = src(bitpos++);
@@ -1768,7 +1770,7 @@ __device__ __forceinline__ void decode_block(const Src& src, uint32_t bitpos, co
 		if (!(bitpos > bpos)) {
 #pragma unroll
 			for (int k = 0; k < 16; k++) cur[k] = color;
-			stale = false;
+			stale = 0;
 			fill_written = true;
 		}
 	} else if (byte == COPY_FLAG) {                            // no over-run check, :281-290
@@ -1777,7 +1779,6 @@ __device__ __forceinline__ void decode_block(const Src& src, uint32_t bitpos, co
 		stale = istale;
 	} else {
 		bool dead = false;                                     // once a row broke, nothing more is stored
-		uint32_t nwritten = 0;
 #pragma unroll
 		for (int j = 0; j < 4; j++) {
 			bool rowbreak = false;
@@ -1793,12 +1794,11 @@ __device__ __forceinline__ void decode_block(const Src& src, uint32_t bitpos, co
 						color = pal[idx];
 					}
 					if (bitpos > bpos || invalid) { invalid = false; rowbreak = true; dead = true; }
-					else { cur[j * 4 + i] = color; nwritten++; }
+					else { cur[j * 4 + i] = color; stale &= ~(1u << (j * 4 + i)); }
 				}
 			}
 		}
 		(void)dead;
-		if (nwritten == 16) stale = false;
 	}
 }
 
@@ -1811,7 +1811,7 @@ __device__ __forceinline__ void decode_block(const Src& src, uint32_t bitpos, co
 template <bool M512>
 __device__ __forceinline__ void decode_block_staged(const StagedSrc& src, uint32_t off, const uint32_t bpos,
                                                     const uint32_t* pal, uint32_t (&cur)[16], const uint32_t (&icol)[16],
-                                                    bool istale, bool& stale, bool& fill_written)
+                                                    uint32_t istale, uint32_t& stale, bool& fill_written)
 {
 	typedef const __attribute__((address_space(3))) uint8_t* lds8;
 	typedef const __attribute__((address_space(3))) uint32_t* lds32;
@@ -1850,7 +1850,7 @@ __device__ __forceinline__ void decode_block_staged(const StagedSrc& src, uint32
 			if (!(end > bpos)) {
 #pragma unroll
 				for (int k = 0; k < 16; k++) cur[k] = color;
-				stale = false;
+				stale = 0;
 				fill_written = true;
 			}
 			slow = false;
@@ -1871,7 +1871,7 @@ __device__ __forceinline__ void decode_block_staged(const StagedSrc& src, uint32
 			if (off + 1u + pos <= bpos) {                      // every code ends inside the stream: all 16 pixels are stored
 #pragma unroll
 				for (int k = 0; k < 16; k++) cur[k] = pal[ci[k]];
-				stale = false;
+				stale = 0;
 				slow = false;
 			}
 		}
@@ -1953,8 +1953,8 @@ __global__ __launch_bounds__(DEC_T, DEC_WPE) void k_decode(DecArgs A)
 	uint32_t off[4], ne[4], bp[4];
 	uint32_t r_lo[4], r_len[4];
 	uint32_t cur[16], icol[16];
-	bool stale, istale;
-	// stale / istale: the block's img_data / iframe->img_data still derive from the state before this GOP.  For the first
+	uint32_t stale, istale;
+	// stale / istale (a bit per pixel): the block's img_data / iframe->img_data still derive from the state before this GOP.  For the first
 	// GOP of the batch that state is the caller's (prev / prev_iframe) and the pixels are right as they are; what the
 	// flags then tell is whether the batch DEPENDS on the state handed in (reported through agmv_hip_decode_prior_dependent).
 	auto load_prior = [&]() {
@@ -1973,7 +1973,7 @@ __global__ __launch_bounds__(DEC_T, DEC_WPE) void k_decode(DecArgs A)
 #pragma unroll
 			for (int k = 0; k < 16; k++) { cur[k] = 0; icol[k] = 0; }
 		}
-		stale = true; istale = true;
+		stale = 0xFFFFu; istale = 0xFFFFu;
 	};
 	uint32_t st[4][DEC_SR];                                    // the byte windows on their way from global memory to LDS
 	// The first DEC_T dwords of every window go out as unconditional buffer loads (a lane beyond the window is out of range: 0,
@@ -2152,7 +2152,7 @@ __global__ __launch_bounds__(DEC_T, DEC_WPE) void k_decode(DecArgs A)
 	load_prior();                                              // (only the first GOP of a batch reads anything here: kept out of the prologue, whose registers hold the byte windows)
 	__syncthreads();                                           // the last wait on global loads in this kernel
 
-	bool anystale = false, needfix = false;
+	bool anystale = false, needfix = false, depstale = false;
 #pragma unroll
 	for (int i = 0; i < 4; i++) {
 		if (i >= nf) break;
@@ -2160,28 +2160,28 @@ __global__ __launch_bounds__(DEC_T, DEC_WPE) void k_decode(DecArgs A)
 		bool fill_written = false;
 		const bool entered = valid && blk < ne[i];
 		const uint32_t own3 = cur[3];                          // the block's pixel (3,0) and staleness before this frame
-		const bool stale0 = stale;
+		const uint32_t stale0 = stale;
 		if (entered) {
 			StagedSrc src{(const __attribute__((address_space(3))) uint8_t*)s_bytes[i], r_lo[i], r_len[i], A.bits + (size_t)f * A.stride, (uint32_t)A.stride};
 			decode_block_staged<M512>(src, off[i], bp[i], s_pal, cur, icol, istale, stale, fill_written);
 		}
 		if (has_last) {                                        // img_data[(x-1)+(y+1)*w] of the block to the left
 			s_nb[tid] = cur[7];
-			s_nbstale[tid] = stale ? 1u : 0u;
+			s_nbstale[tid] = (stale >> 7) & 1u;
 			lds_barrier();
 			if (is_last && fill_written) {
 				if (A.bw == 1) {                                   // one block per row: the reference's 64-bit (x-1) wraps to the
 #pragma unroll                                                     // block's own pixel (3,0), not yet written in this frame
 					for (int k = 0; k < 16; k++) cur[k] = own3;
-					stale = stale0;
+					stale = ((stale0 >> 3) & 1u) ? 0xFFFFu : 0u;
 				} else if (tid > 0) {
 					uint32_t c = s_nb[tid - 1];
 #pragma unroll
 					for (int k = 0; k < 16; k++) cur[k] = c;
-					stale = s_nbstale[tid - 1] != 0;
+					stale = s_nbstale[tid - 1] ? 0xFFFFu : 0u;
 				} else {
-					stale = true; needfix = true;             // neighbour lives in another tile: fix-up (the pixels here are NOT final)
-				}
+					stale = 0xFFFFu; needfix = true;          // neighbour lives in another tile: fix-up (the pixels here are NOT final,
+				}                                              // and k_fixup tells whether they depend on the batch's prior state)
 			}
 			lds_barrier();
 		}
@@ -2190,7 +2190,8 @@ __global__ __launch_bounds__(DEC_T, DEC_WPE) void k_decode(DecArgs A)
 			for (int k = 0; k < 16; k++) icol[k] = cur[k];
 			istale = stale;
 		}
-		anystale |= stale;
+		anystale |= stale != 0;
+		if (!needfix) depstale |= stale != 0;
 		if (valid) store_block(A.out + (size_t)f * npx, poff, A.w, cur);
 	}
 	if (valid && (anystale || needfix)) {
@@ -2198,7 +2199,7 @@ __global__ __launch_bounds__(DEC_T, DEC_WPE) void k_decode(DecArgs A)
 			atomicOr(A.dirty + (blk >> 5), 1u << (blk & 31u));
 			A.dirty[(A.nblk + 31) >> 5] = 1u;                   // "anything to repair" word behind the bitmap
 		}
-		if (group == 0 && anystale) A.dirty[((A.nblk + 31) >> 5) + 1] = 1u;   // the batch depends on the decoder state before it
+		if (group == 0 && depstale) A.dirty[((A.nblk + 31) >> 5) + 1] = 1u;   // the batch depends on the decoder state before it
 	}
 }
 
@@ -2208,6 +2209,9 @@ __global__ __launch_bounds__(DEC_T, DEC_WPE) void k_decode(DecArgs A)
 // 64 bitmap bits are clear exits at once, the others replay ALL frames in order for their flagged positions from the true
 // pre-batch state and overwrite the output.  The wave that holds block nblk-1 also replays block nblk-2 (flagged or not:
 // a replay from the true state writes the true pixels), in the lane below when both sit in one wave, else in lane 1.
+// The replay follows, pixel by pixel, what still derives from the pre-batch state, which k_decode cannot tell beyond the
+// batch's first GOP (a batch that starts inside a GOP hands the caller's I-frame snapshot on to a COPY in its first
+// I-frame) nor for a last block whose left neighbour sits in another tile: every block it leaves to this kernel is replayed.
 template <bool M512, bool BM>
 __global__ __launch_bounds__(64) void k_fixup(DecArgs A)
 {
@@ -2246,26 +2250,34 @@ __global__ __launch_bounds__(64) void k_fixup(DecArgs A)
 #pragma unroll
 		for (int k = 0; k < 16; k++) icol[k] = 0;
 	}
+	uint32_t stale = 0xFFFFu, istale = 0xFFFFu;                // per pixel, as in k_decode
+	bool dep = false;
 	for (uint32_t f = 0; f < A.n_frames; f++) {
-		bool stale = false, fill_written = false;
-		const uint32_t own3 = cur[3];
+		bool fill_written = false;
+		const uint32_t own3 = cur[3], own3s = (stale >> 3) & 1u;
 		if (active && blk < A.nentered[f]) {
 			ByteSrc src{A.bits + (size_t)f * A.stride, (uint32_t)A.stride};
 			const uint32_t o = BM ? bm_offset_of(A.vm, A.kb, A.maxR, A.bpos[f], f, blk) : A.offsets[(size_t)f * A.nblk + blk];
-			decode_block<M512>(src, o, A.bpos[f], s_pal, cur, icol, false, stale, fill_written);
+			decode_block<M512>(src, o, A.bpos[f], s_pal, cur, icol, istale, stale, fill_written);
 		}
-		const uint32_t left = (uint32_t)__builtin_amdgcn_readlane((int)cur[7], nb_lane < 0 ? 0 : nb_lane);   // img_data[(x-1)+(y+1)*w] of the left neighbour
+		const int nbl = nb_lane < 0 ? 0 : nb_lane;
+		const uint32_t left = (uint32_t)__builtin_amdgcn_readlane((int)cur[7], nbl);   // img_data[(x-1)+(y+1)*w] of the left neighbour
+		const uint32_t lefts = ((uint32_t)__builtin_amdgcn_readlane((int)stale, nbl) >> 7) & 1u;
 		if (is_last && fill_written) {
 			const uint32_t c = A.bw == 1 ? own3 : left;            // one block per row: see k_decode
 #pragma unroll
 			for (int k = 0; k < 16; k++) cur[k] = c;
+			stale = (A.bw == 1 ? own3s : lefts) ? 0xFFFFu : 0u;
 		}
 		if (((A.first_fc + f) & 3u) == 0) {
 #pragma unroll
 			for (int k = 0; k < 16; k++) icol[k] = cur[k];
+			istale = stale;
 		}
 		if (active) store_block(A.out + (size_t)f * npx, poff, A.w, cur);
+		if (active && stale) dep = true;
 	}
+	if (dep) A.dirty[nwords + 1] = 1u;                         // the batch depends on the decoder state before it
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -2907,6 +2919,9 @@ static int parse_launch(agmv_hip_ctx* c, const uint8_t* d_bits, size_t stride, c
 	const dim3 grid(gx, gy);
 	if (robust_only) {                                         // debugging aid: every frame through the robust kernels (bitmap form)
 		if (bitmap) CK(hipMemsetAsync(A.tidx, 0xFF, (size_t)n_frames * (tpfd + 1) * 4, s));   // TIDX_NONE (otherwise k_fp_finish's job; nbad: k_fp_walk's)
+		// k_parse_chunks clears the entry bitmap words up to a frame's last chunk, k_fp_tiles / k_decode read up to the end of
+		// its last region: without k_fp_walk (which writes every word of a region) the words in between are cleared here
+		if (bitmap) CK(hipMemsetAsync(A.vm, 0, (size_t)n_frames * maxR * FOWN * 8, s));
 		CK(hipMemsetD32Async((hipDeviceptr_t)A.fstate, (int)FS_BAD, n_frames, s));
 		CK(hipMemsetD32Async((hipDeviceptr_t)A.nbad, (int)n_frames, 1, s));
 	} else {
@@ -2993,13 +3008,14 @@ static int decode_prepare(agmv_hip_ctx* c, DecArgs& A, const uint8_t* d_bits, si
 	A.first_fc = first_fc; A.phase = first_fc & 3u;
 	A.n_groups = (n_frames + A.phase + 3) / 4;
 	size_t nwords = (A.nblk + 31) / 32 + 2;                    // bitmap + the "anything to repair" word + the "depends on the prior state" word
-	if (nwords > c->dirty_cap) {
+	if (nwords + 1 > c->dirty_cap) {                           // (+ part 0's "depends" word of a call cut into parts: written, never cleared)
 		if (c->d_dirty) CK(hipFree(c->d_dirty));
 		c->d_dirty = nullptr; c->dirty_cap = 0;
-		CK(hipMalloc(&c->d_dirty, nwords * 4));
-		c->dirty_cap = nwords;
+		CK(hipMalloc(&c->d_dirty, (nwords + 1) * 4));
+		c->dirty_cap = nwords + 1;
 	}
 	A.dirty = c->d_dirty;
+	c->dep_split = false;
 	if (ndirty_out) *ndirty_out = (uint32_t)nwords;
 	else CK(hipMemsetAsync(c->d_dirty, 0, nwords * 4, s));
 	return 0;
@@ -3146,8 +3162,13 @@ extern "C" int agmv_hip_decode_bitstreams_dev(agmv_hip_ctx* c, const uint8_t* d_
 		if (decode_launch(c, A, 0, A.n_groups, s)) return -1;
 		if (fixup_launch(c, A, s)) return -1;
 		ev_mark(c, 5, s);
+		if (f0 == 0 && f1 < n_frames) {                        // later parts depend on the parts before them, not on the caller:
+			const size_t dw = (A.nblk + 31) / 32 + 1;          // the call's prior dependence is part 0's (the next k_fp_tiles clears it)
+			CK(hipMemcpyAsync(c->d_dirty + dw + 1, c->d_dirty + dw, 4, hipMemcpyDeviceToDevice, s));
+		}
 		f0 = f1;
 	}
+	c->dep_split = n_frames > PART;
 	ev_mark(c, 7, s);
 	return 0;
 }
@@ -3159,7 +3180,7 @@ extern "C" int agmv_hip_decode_prior_dependent(agmv_hip_ctx* c, uint32_t w, uint
 	const size_t nblk = (size_t)(w / 4) * (h / 4);
 	uint32_t v = 0;
 	CK(hipStreamSynchronize((hipStream_t)stream));
-	CK(hipMemcpy(&v, c->d_dirty + (nblk + 31) / 32 + 1, 4, hipMemcpyDeviceToHost));
+	CK(hipMemcpy(&v, c->d_dirty + (nblk + 31) / 32 + (c->dep_split ? 2 : 1), 4, hipMemcpyDeviceToHost));
 	return v ? 1 : 0;
 }
 

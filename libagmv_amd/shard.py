@@ -7,7 +7,7 @@ the rank that runs the host LZ stage and writes the container in frame order (RC
 "nccl" backend, gloo in the CPU tests).  Each peer sends over its own direct link to the root, so this is
 a plain gather (sizes first, then the variable-length payloads), not a ring.
 
-Decode shards the same way.  A GOP is self-contained for every stream the encoder can emit; only a stream that
+Decode shards the same way.  A GOP is self-contained for every stream the encoder can emit wider than 4 pixels; only a stream that
 raises the reference's `escape` (blocks the bitstream does not reach keep the previous frame's pixels, reference
 src/agmv_decode.c:229-232) or carries a COPY block in an I-frame (reads the snapshot of the previous GOP, :277-285)
 makes a range depend on the decoder state before it.  decode_sharded() decodes every range in parallel from the fresh
@@ -154,7 +154,7 @@ def _block_end(row, start, bpos, mode512):
     return flag, pos
 
 
-def range_depends_on_prior_state(bits, bpos, offsets, nentered, nblk, mode512=True, first_is_iframe=True):
+def range_depends_on_prior_state(bits, bpos, offsets, nentered, nblk, mode512=True, first_is_iframe=True, w=None):
     """True when the pixels of a range may depend on img_data / iframe_data from before its first frame.  (Host-side form for
     callers that hold the parser's outputs; a GPU decode reports the same fact itself, AgmvHip.decode_depends_on_prior().)
     bits [n, stride] uint8, bpos [n], offsets [n, nblk] (byte position at which each block is ENTERED, i.e. before the
@@ -163,7 +163,11 @@ def range_depends_on_prior_state(bits, bpos, offsets, nentered, nblk, mode512=Tr
       (b) a COPY block in the range's first frame reads the snapshot taken before the range.  A block is decoded under the
           first flag-valued byte at or after its entry position, so that byte is what is classified;
       (c) a block that runs past bpos is not (FILL, :268-271) or not completely (NORMAL, per-pixel check :310-314 /
-          :386-392) stored.  Inside a frame that ends the frame (case a); as the LAST block it has to be looked at itself.
+          :386-392) stored.  Inside a frame that ends the frame (case a); as the LAST block it has to be looked at itself;
+      (d) with one block per row (frame width w == 4) a FILL as the last block stores the block's own pixel (3,0) as it was
+          before the frame (the reference's x-1 wraps, :264-266): in the range's first frame, the state before the range.
+          This needs the width: a caller that decodes frames 4 pixels wide must pass w.  w=None takes the frame to be
+          wider unless it is a single block (nblk == 1, so w == 4).
     Everything else a frame writes is a function of its own bitstream and of frames inside the range."""
     n = int(nentered.numel())
     if n == 0:
@@ -193,13 +197,15 @@ def range_depends_on_prior_state(bits, bpos, offsets, nentered, nblk, mode512=Tr
         flag, end = _block_end(rows[f], int(off[f, nblk - 1]), int(bp[f]), mode512)
         if flag is None or (flag != COPY_FLAG and end > int(bp[f])):
             return True
+        if f == 0 and flag == FILL_FLAG and (w == 4 or (w is None and nblk == 1)):   # (d)
+            return True
     return False
 
 
 def decode_sharded(dist, decode_range, n_frames, first_frame_count=0, prev=None, prev_iframe=None):
     """Bit-exact GOP-sharded decode.  decode_range(lo, hi, prev, prev_iframe) decodes frames [lo, hi) of the clip from
     the given prior state (None = fresh decoder) and returns (pixels [hi-lo, H, W] int32, depends: bool) where
-    `depends` is range_depends_on_prior_state() of that range.  Returns this rank's (lo, hi, pixels).
+    `depends` is range_depends_on_prior_state() of that range (with w=W) or AgmvHip.decode_depends_on_prior().  Returns this rank's (lo, hi, pixels).
     Hand-off: after the parallel pass the `depends` flags are all-gathered; for each dependent rank r (in rank order)
     the nearest non-empty rank before it sends its final frame and its I-frame snapshot, and r decodes again."""
     world, rank = dist.get_world_size(), dist.get_rank()

@@ -238,6 +238,28 @@ class OracleDecoder:
             return pix, padded, offs, n_ent.value
         return pix
 
+    def set_state(self, prev=None, prev_iframe=None, frame_count=0, bitstream=None):
+        """start from a given decoder state instead of the fresh one: img_data = `prev`, iframe->img_data = `prev_iframe`
+        (w*h pixels each, None = zeroed), the frame_count of the NEXT frame, and optionally the bytes of the persistent
+        bitstream buffer (None leaves it as it is; its stale bytes are read on over-run)"""
+        n = self.w * self.h
+        img = np.ctypeslib.as_array(self.s.img, (n,))
+        ifr = np.ctypeslib.as_array(self.s.iframe, (n,))
+        img[:] = 0 if prev is None else np.ascontiguousarray(prev, np.uint32).reshape(-1)
+        ifr[:] = 0 if prev_iframe is None else np.ascontiguousarray(prev_iframe, np.uint32).reshape(-1)
+        self.s.frame_count = int(frame_count)
+        if bitstream is not None:
+            buf = np.ctypeslib.as_array(self.s.bitstream, (self.s.bitstream_cap,))
+            b = np.ascontiguousarray(bitstream, np.uint8).reshape(-1)
+            assert len(b) == len(buf), "bitstream buffer holds %d bytes" % len(buf)
+            buf[:] = b
+
+    def state(self):
+        """(img_data, iframe->img_data, frame_count, persistent bitstream buffer) -- copies"""
+        n = self.w * self.h
+        return (np.ctypeslib.as_array(self.s.img, (n,)).copy(), np.ctypeslib.as_array(self.s.iframe, (n,)).copy(),
+                int(self.s.frame_count), np.ctypeslib.as_array(self.s.bitstream, (self.s.bitstream_cap,)).copy())
+
     def close(self):
         if self.p:
             self.L.orc_decoder_free(self.p)
