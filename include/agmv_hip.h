@@ -104,7 +104,8 @@ int agmv_hip_within2_count(agmv_hip_ctx* ctx, const uint32_t a[16], const uint32
 /* Notes on a context:
  *  - device memory: 512 MiB of address space for the colour -> entry table (32 MiB of it populated, see
  *    k_lut_build in agmv_hip.hip), plus per-batch work areas grown on demand (look-back status 8 B per tile and
- *    frame, parser workspace <= 15 % of the bitstream slab);
+ *    frame, parser workspace <= 15 % of the bitstream slab; LZSS: about 29 bytes per position of the largest chunk of a
+ *    batch, at most 2^24 positions, ~460 MiB);
  *  - the encode entry points of ONE context share its look-back status and control words: a second encode is
  *    ordered behind the first (on another stream it waits for it through an event); use one context per
  *    concurrent encoder;
@@ -194,6 +195,27 @@ int agmv_hip_pack_frames_dev(agmv_hip_ctx* ctx, const uint8_t* d_slab, size_t st
                              uint32_t n_frames, uint8_t* d_msg, unsigned long long* d_offsets, void* stream);
 int agmv_hip_unpack_frames_dev(agmv_hip_ctx* ctx, const uint8_t* d_msg, const uint32_t* d_sizes, uint32_t n_frames,
                                uint8_t* d_slab, size_t stride, unsigned long long* d_offsets, void* stream);
+
+/* -- LZSS stage of the encoder (AGMV_LZSS + the csize handling of AGMV_EncodeFrame, reference src/agmv_encode.c:106-177,
+ * :567-585, :622-624; AGMV_FlushWriteBits src/agmv_utils.c:106-112) ------------------------------------------------
+ * agmv_hip_lzss_max_csize: bytes a payload row must hold for a pre-LZ bitstream of n bytes (ceil(9n/8) all-literal, plus
+ *                          one byte for the float rounding of csize).
+ * agmv_hip_lzss_frames_dev: row f = d_bits + f*bits_stride, d_sizes[f] bytes (as agmv_hip_encode_frames_dev leaves them);
+ *                          d_out + f*out_stride receives exactly the csize payload bytes the reference's file holds for that
+ *                          frame (the partial last byte when the float csize counts it, its unused high bits 0; bytes of
+ *                          the row behind csize are left as they are), d_csize[f] its csize field.  Sizes may differ and
+ *                          be 0; each must be < 2^24 and out_stride >= agmv_hip_lzss_max_csize of it.  Bit-exact with the
+ *                          reference (longest match <= 15 in the 65535-byte window, earliest start among equals).
+ *                          Asynchronous on `stream` except that it synchronises the stream once, before its kernels, to
+ *                          read d_sizes (they decide how the batch is cut into chunks).  Calls on one context share its LZ
+ *                          work areas: they must not overlap.  The payload rows of a batch travel to the host as one
+ *                          message through agmv_hip_pack_frames_dev with d_csize as the sizes.
+ * agmv_hip_lzss_frames:     the same from/to host memory (synchronous). */
+size_t agmv_hip_lzss_max_csize(size_t n);
+int agmv_hip_lzss_frames_dev(agmv_hip_ctx* ctx, const uint8_t* d_bits, size_t bits_stride, const uint32_t* d_sizes,
+                             uint32_t n_frames, uint8_t* d_out, size_t out_stride, uint32_t* d_csize, void* stream);
+int agmv_hip_lzss_frames(agmv_hip_ctx* ctx, const uint8_t* h_bits, size_t bits_stride, const uint32_t* h_sizes,
+                         uint32_t n_frames, uint8_t* h_out, size_t out_stride, uint32_t* h_csize);
 
 /* -- helpers on the caller side of the path -------------------------------------------------*/
 /* canonical synthetic clip agmv_synth_v1: frames t0..t0+n-1 into d_pix */

@@ -84,11 +84,11 @@ def build(force=False, verbose=False):
 
 
 def _build(force=False, verbose=False):
-    hip_src = os.path.join(CSRC, "agmv_hip.hip")
+    hip_srcs = [os.path.join(CSRC, "agmv_hip.hip"), os.path.join(CSRC, "agmv_lz_hip.hip")]
     hdrs = glob.glob(os.path.join(ROOT, "include", "*.h"))
     hip_so = os.path.join(HERE, "libagmv_hip.so")
-    if force or _stale(hip_so, [hip_src] + hdrs):
-        _compile([HIPCC, "--offload-arch=" + ARCH, "-O3", "-fPIC", "-shared", "-std=c++17", hip_src, "-o", hip_so], hip_so, verbose, no_scratch=True)
+    if force or _stale(hip_so, hip_srcs + hdrs):
+        _compile([HIPCC, "--offload-arch=" + ARCH, "-O3", "-fPIC", "-shared", "-std=c++17"] + hip_srcs + ["-o", hip_so], hip_so, verbose, no_scratch=True)
     c_srcs = sorted(glob.glob(os.path.join(CSRC, "*.c")))
     if c_srcs:
         host_so = os.path.join(HERE, "libagmv.so")

@@ -16,6 +16,7 @@
 //   k_fixup         sequential repair of blocks whose value depends on an earlier GOP
 //                   (stale tail after `escape`, src/agmv_decode.c:229-232; last-block FILL
 //                   quirk :264-266)
+// The encoder's LZSS stage (AGMV_LZSS, src/agmv_encode.c:106-177) is in agmv_lz_hip.hip.
 // Integer/byte work only: no MFMA. The bound is HBM (4 B/px in, usize out).
 #include <hip/hip_runtime.h>
 
@@ -129,7 +130,14 @@ struct agmv_hip_ctx {
 	hipStream_t aux_stream;         // decode pipeline: the parser's stream (the reconstruction runs on the caller's)
 	hipEvent_t ev_fork;             // ... caller's stream -> parser's stream
 	hipEvent_t ev_slice[DEC_MAX_SLICES];   // ... slice parsed
+	void* lz_ws;                    // agmv_hip_lzss_frames_dev: work areas (agmv_lz_hip.hip)
 };
+
+// for agmv_lz_hip.hip, the LZSS stage: the error text, the context's slot for its work areas, the device
+int agmv_hip_internal_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); return -1; }
+void** agmv_hip_internal_lz_slot(agmv_hip_ctx* c) { return &c->lz_ws; }
+int agmv_hip_internal_device(agmv_hip_ctx* c) { return c->device; }
+void agmv_hip_internal_lz_free(void* p);
 
 extern "C" size_t agmv_hip_max_usize(uint32_t w, uint32_t h, int mode512)
 {
@@ -2499,6 +2507,7 @@ extern "C" void agmv_hip_destroy(agmv_hip_ctx* c)
 	if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
 	for (int i = 0; i < DEC_MAX_SLICES; i++) if (c->ev_slice[i]) (void)hipEventDestroy(c->ev_slice[i]);
 	if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
+	agmv_hip_internal_lz_free(c->lz_ws);
 	free(c);
 }
 

@@ -161,6 +161,7 @@ static u32 lzss_run(const u8* d, int n, sink* s)
 	gq q[16];
 	unsigned char isq[16];
 	int k, L, i = 0, ins = 0, outbits = 0;
+	u32 csize;
 	memset(isq, 0, sizeof(isq));
 	for (k = 0; k < LZ_NQ; k++) { gq_init(&q[LZ_Q[k]], LZ_Q[k]); isq[LZ_Q[k]] = 1; }
 	while (i < n) {
@@ -197,7 +198,11 @@ static u32 lzss_run(const u8* d, int n, sink* s)
 		}
 	}
 	for (k = 0; k < LZ_NQ; k++) gq_free(&q[LZ_Q[k]]);
-	return (u32)((float)outbits / 8.0f);                   /* csize is computed in float, :176 */
+	csize = (u32)((float)outbits / 8.0f);                  /* csize is computed in float, :176 */
+	/* above 2^24 bits the float can round up to floor(outbits/8) + 1: the reference's file then keeps the partial last byte
+	   AGMV_FlushWriteBits wrote (unused high bits 0, src/agmv_utils.c:106-112), so the memory sink stores it too */
+	if (!s->f && s->bits && csize > s->n) s->out[s->n] = (u8)s->buf;
+	return csize;
 }
 
 /* ---- LZ77 (reference src/agmv_encode.c:179-238): 4-byte tokens {u16 distance, u8 length, u8 next}.
@@ -268,7 +273,7 @@ u32 AGMV_LZ77(FILE* file, AGMV_BITSTREAM* in)
 
 /* memory forms used by the batch drivers: returns the bytes the reference leaves in the file for the
    payload, i.e. exactly csize bytes (the flushed partial byte is overwritten by the 0xFF guard,
-   reference src/agmv_encode.c:579-585,622-624).  `out` needs 2*n+16 (LZSS) / 4*n+16 (LZ77) bytes. */
+   reference src/agmv_encode.c:579-585,622-624, unless csize counts it: LZSS above 2^24 bits, see lzss_run).  `out` needs 2*n+16 (LZSS) / 4*n+16 (LZ77) bytes. */
 u32 agmv_lzss_mem(const u8* in, size_t n, u8* out)
 {
 	sink s;

@@ -161,6 +161,7 @@ typedef struct ebatch {
 	size_t* boff;
 	lzjob* jobs;
 	u8* comp; size_t comp_cap;
+	uint32_t* csizes;                      /* pinned [cap]: AGMV_LZ_DEVICE, the csize of each frame */
 } ebatch;
 
 typedef struct eworker {
@@ -172,6 +173,8 @@ typedef struct eworker {
 	uint32_t *d_frames, *d_sizes, *d_tmp[2];
 	uint8_t* d_out;
 	uint16_t* d_ient;
+	uint8_t* d_lz;                         /* AGMV_LZ_DEVICE: payload rows [cap][lz_stride] and their csize */
+	uint32_t* d_csize;
 } eworker;
 
 struct agmv_seq {
@@ -179,8 +182,9 @@ struct agmv_seq {
 	FILE* file;
 	const char *dir, *base;
 	int scale_w, scale_h, audio_chunks, mode512, lz77, use_b;
+	int lz_dev;                            /* AGMV_LZ_DEVICE=1 and LZSS: the LZ stage runs on the GPU workers */
 	uint32_t w, h;
-	size_t npx, per, stride;
+	size_t npx, per, stride, lz_stride;
 	unsigned cap, nslots, nworkers;
 	ebatch* slot;
 	eworker* wk;
@@ -277,6 +281,31 @@ static void* eworker_main(void* p)
 		                               wk->stream) ||
 		    agmv_hip_memcpy_async(wk->ctx, b->sizes, wk->d_sizes, 4 * (size_t)b->n, 1, wk->stream) || agmv_hip_check(wk->ctx, wk->stream))
 			seq_die(s, "batch encode");
+		if (s->lz_dev) {                                   /* LZSS on the GPU: the payloads travel instead of the bitstreams */
+			const double tl0 = now_s();
+			if (agmv_hip_lzss_frames_dev(wk->ctx, wk->d_out, s->stride, wk->d_sizes, b->n, wk->d_lz, s->lz_stride, wk->d_csize, wk->stream) ||
+			    agmv_hip_memcpy_async(wk->ctx, b->csizes, wk->d_csize, 4 * (size_t)b->n, 1, wk->stream) || agmv_hip_stream_sync(wk->ctx, wk->stream))
+				seq_die(s, "batch LZSS");
+			for (k = 0; k < b->n; k++) { b->boff[k] = total; total += (size_t)b->csizes[k]; }
+			if (total + 16 > b->h_bits_cap) {
+				agmv_hip_host_free(b->h_bits);
+				b->h_bits_cap = total + total / 4 + 4096;
+				b->h_bits = (u8*)agmv_hip_host_alloc(b->h_bits_cap);
+				if (!b->h_bits) seq_die(s, "pinned allocation");
+			}
+			for (k = 0; k < b->n; k++)
+				if (b->csizes[k] && agmv_hip_memcpy_async(wk->ctx, b->h_bits + b->boff[k], wk->d_lz + (size_t)k * s->lz_stride, b->csizes[k], 1, wk->stream))
+					seq_die(s, "payload download");
+			if (agmv_hip_stream_sync(wk->ctx, wk->stream)) seq_die(s, "payload download");
+			for (k = 0; k < b->n; k++) { b->jobs[k].out = b->h_bits + b->boff[k]; b->jobs[k].csize = b->csizes[k]; }
+			pthread_mutex_lock(&s->mu);
+			s->t_gpu += now_s() - tw0;
+			s->t_lz += now_s() - tl0;
+			b->bits_ready = 1;
+			pthread_cond_broadcast(&s->cv);
+			pthread_mutex_unlock(&s->mu);
+			continue;
+		}
 		for (k = 0; k < b->n; k++) { b->boff[k] = total; total += (size_t)b->sizes[k] + 1; }
 		if (total + 16 > b->h_bits_cap) {
 			agmv_hip_host_free(b->h_bits);
@@ -303,6 +332,12 @@ static void prepare_batch(agmv_seq* s, ebatch* b)
 {
 	size_t need = 0, coff = 0;
 	unsigned k;
+	if (s->lz_dev) {                                       /* the GPU worker left the payloads (LZSS reads nothing past the end) */
+		pthread_mutex_lock(&s->mu);
+		b->lz_left = 0;
+		pthread_mutex_unlock(&s->mu);
+		return;
+	}
 	for (k = 0; k < b->n; k++) need += (size_t)b->sizes[k] * (s->lz77 ? 4 : 2) + 64;
 	if (need > b->comp_cap) { free(b->comp); b->comp_cap = need + need / 4; b->comp = (u8*)xmalloc(b->comp_cap); }
 	for (k = 0; k < b->n; k++) {
@@ -424,6 +459,11 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const char* dir, const char* base, 
 	s->audio_chunks = audio_chunks; s->mode512 = mode512; s->lz77 = lz77; s->use_b = use_interp;
 	s->w = (uint32_t)AGMV_GetWidth(a); s->h = (uint32_t)AGMV_GetHeight(a);
 	s->npx = (size_t)s->w * s->h; s->per = s->npx * (use_interp ? 2 : 1); s->stride = agmv_hip_max_usize(s->w, s->h, 1);
+	{	/* AGMV_LZ_DEVICE=1: LZSS on the GPU (opt-in; LZ77 stays on the host with its look past the end) */
+		const char* lv = getenv("AGMV_LZ_DEVICE");
+		s->lz_dev = !lz77 && lv && atoi(lv) != 0;
+		s->lz_stride = (agmv_hip_lzss_max_csize(s->stride) + 255) & ~(size_t)255;
+	}
 	s->cap = (cap + 3u) & ~3u;
 	s->nworkers = devices * 2;
 	s->nslots = s->nworkers + 2;
@@ -442,7 +482,8 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const char* dir, const char* base, 
 		b->jobs = (lzjob*)xcalloc(s->cap, sizeof(lzjob));
 		b->h_pix = (uint32_t*)agmv_hip_host_alloc(s->per * 4 * s->cap);
 		b->sizes = (uint32_t*)agmv_hip_host_alloc(4 * (size_t)s->cap + 64);
-		if (!b->h_pix || !b->sizes) agmv_die("pinned allocation");
+		b->csizes = (uint32_t*)agmv_hip_host_alloc(4 * (size_t)s->cap + 64);
+		if (!b->h_pix || !b->sizes || !b->csizes) agmv_die("pinned allocation");
 	}
 	t1 = now_s();
 	TRACE("seq_open: pool + %u pinned slots of %.1f MB in %.3f s\n", s->nslots, s->per * 4.0 * s->cap / 1e6, t1 - t0);
@@ -460,7 +501,10 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const char* dir, const char* base, 
 		wk->d_ient = (uint16_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 2);
 		wk->d_tmp[0] = use_interp ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 4) : NULL;
 		wk->d_tmp[1] = use_interp ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 4) : NULL;
-		if (!wk->stream || !wk->d_frames || !wk->d_out || !wk->d_sizes || !wk->d_ient || (use_interp && (!wk->d_tmp[0] || !wk->d_tmp[1])))
+		wk->d_lz = s->lz_dev ? (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->lz_stride * s->cap) : NULL;
+		wk->d_csize = s->lz_dev ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, 4 * (size_t)s->cap) : NULL;
+		if (!wk->stream || !wk->d_frames || !wk->d_out || !wk->d_sizes || !wk->d_ient || (use_interp && (!wk->d_tmp[0] || !wk->d_tmp[1])) ||
+		    (s->lz_dev && (!wk->d_lz || !wk->d_csize)))
 			agmv_die("device allocation");
 		if (pthread_create(&wk->th, NULL, eworker_main, wk)) agmv_die("cannot start a GPU worker thread");
 	}
@@ -490,14 +534,15 @@ u32 agmv_seq_close(agmv_seq* s)
 	pthread_mutex_unlock(&s->mu);
 	seq_progress(s, 0, 1);
 	TRACE("pipeline: %u frames in %u batches, %.3f s from open to last chunk written; summed over the threads: BMP parse %.3f s, GPU workers "
-	      "(upload + kernels + download) %.3f s, LZ %.3f s, chunk writes %.3f s\n", (unsigned)s->frames_written, s->nsubmitted, now_s() - s->t_open,
-	      s->t_load, s->t_gpu, s->t_lz, s->t_write);
+	      "(upload + kernels + download) %.3f s, LZ (%s) %.3f s, chunk writes %.3f s\n", (unsigned)s->frames_written, s->nsubmitted, now_s() - s->t_open,
+	      s->t_load, s->t_gpu, s->lz_dev ? "device" : "host", s->t_lz, s->t_write);
 	t0 = now_s();
 	for (i = 0; i < s->nworkers; i++) {
 		eworker* wk = &s->wk[i];
 		pthread_join(wk->th, NULL);
 		agmv_hip_free_on(wk->ctx, wk->d_frames); agmv_hip_free_on(wk->ctx, wk->d_out); agmv_hip_free_on(wk->ctx, wk->d_sizes);
 		agmv_hip_free_on(wk->ctx, wk->d_ient); agmv_hip_free_on(wk->ctx, wk->d_tmp[0]); agmv_hip_free_on(wk->ctx, wk->d_tmp[1]);
+		agmv_hip_free_on(wk->ctx, wk->d_lz); agmv_hip_free_on(wk->ctx, wk->d_csize);
 		agmv_hip_stream_destroy(wk->ctx, wk->stream);
 		agmv_hip_destroy(wk->ctx);
 	}
@@ -505,7 +550,7 @@ u32 agmv_seq_close(agmv_seq* s)
 	for (i = 0; i < s->nslots; i++) {
 		ebatch* b = &s->slot[i];
 		free(b->srcA); free(b->srcB); free(b->boff); free(b->jobs); free(b->comp);
-		agmv_hip_host_free(b->h_pix); agmv_hip_host_free(b->sizes); agmv_hip_host_free(b->h_bits);
+		agmv_hip_host_free(b->h_pix); agmv_hip_host_free(b->sizes); agmv_hip_host_free(b->csizes); agmv_hip_host_free(b->h_bits);
 	}
 	written = s->frames_written;
 	TRACE("seq_close: teardown %.3f s\n", now_s() - t0);

@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "agmv_hip_stream_create", "agmv_hip_stream_destroy", "agmv_hip_stream_sync", "agmv_hip_host_alloc",
     "agmv_hip_host_free", "agmv_hip_malloc_on", "agmv_hip_free_on", "agmv_hip_memcpy_async",
     "agmv_hip_memset_async", "agmv_hip_ctx_device",
+    "agmv_hip_lzss_max_csize", "agmv_hip_lzss_frames_dev", "agmv_hip_lzss_frames",
 ]
 
 
@@ -91,6 +92,13 @@ def load_library(path=None):
         L.agmv_hip_unpack_frames_dev.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp]
         L.agmv_hip_unpack_frames_dev.restype = C.c_int
     L.agmv_hip_parse_fallback_frames.restype = C.c_int
+    if path is None or hasattr(L, "agmv_hip_lzss_frames_dev"):      # (older builds under tools/variants/ lack it)
+        L.agmv_hip_lzss_max_csize.restype = sz
+        L.agmv_hip_lzss_max_csize.argtypes = [sz]
+        L.agmv_hip_lzss_frames_dev.argtypes = [vp, vp, sz, vp, u32, vp, sz, vp, vp]
+        L.agmv_hip_lzss_frames_dev.restype = C.c_int
+        L.agmv_hip_lzss_frames.argtypes = [vp, vp, sz, vp, u32, vp, sz, vp]
+        L.agmv_hip_lzss_frames.restype = C.c_int
     L.agmv_hip_decode_prior_dependent.restype = C.c_int
     L.agmv_hip_synth_dev.argtypes = [vp, vp, u32, u32, u32, u32, C.c_uint64, vp]
     L.agmv_hip_interp_dev.argtypes = [vp, vp, vp, vp, sz, vp]
@@ -253,6 +261,39 @@ class AgmvHip:
             self._ck(self.L.agmv_hip_unpack_frames_dev(self.ctx, packed.data_ptr(), sizes.data_ptr(), n, out.data_ptr(), out.stride(0),
                                                        offs.data_ptr(), self._stream()))
         return out
+
+    def lzss_max_csize(self, n):
+        """bytes a payload row must hold for a pre-LZ bitstream of n bytes"""
+        return int(self.L.agmv_hip_lzss_max_csize(int(n)))
+
+    def lzss_frames_dev(self, bits, sizes, n_frames, out=None, csize=None):
+        """LZSS stage of AGMV_EncodeFrame on the GPU: bits u8 [n, stride] (rows of pre-LZ bitstreams), sizes int32 [n].
+        Returns (out u8 [n, out_stride], csize int32 [n]); row f holds the csize[f] payload bytes the reference's file holds.
+        Reads the sizes once (synchronises torch's current stream)."""
+        import torch
+        if out is None:
+            out = torch.empty((n_frames, self.lzss_max_csize(bits.stride(0))), dtype=torch.uint8, device=bits.device)
+        if csize is None:
+            csize = torch.empty(n_frames, dtype=torch.int32, device=bits.device)
+        self._ck(self.L.agmv_hip_lzss_frames_dev(self.ctx, bits.data_ptr(), bits.stride(0), sizes.data_ptr(), n_frames,
+                                                 out.data_ptr(), out.stride(0), csize.data_ptr(), self._stream()))
+        return out, csize
+
+    def lzss_frames(self, streams):
+        """host form: a list of u8 arrays (pre-LZ bitstreams) -> list of payloads (csize bytes each)"""
+        streams = [np.ascontiguousarray(x, np.uint8) for x in streams]
+        n = len(streams)
+        sizes = np.array([len(x) for x in streams], np.uint32)
+        stride = max([1] + [len(x) for x in streams])
+        ostride = self.lzss_max_csize(stride)
+        bits = np.zeros((max(n, 1), stride), np.uint8)
+        for i, x in enumerate(streams):
+            bits[i, :len(x)] = x
+        out = np.zeros((max(n, 1), ostride), np.uint8)
+        cs = np.zeros(max(n, 1), np.uint32)
+        self._ck(self.L.agmv_hip_lzss_frames(self.ctx, _np_ptr(bits), stride, _np_ptr(sizes), n, _np_ptr(out), ostride,
+                                             _np_ptr(cs)))
+        return [out[i, :cs[i]].copy() for i in range(n)]
 
     def parse_fallback_frames(self):
         """frames of the last parse that went to the robust kernels (a statistic)"""
