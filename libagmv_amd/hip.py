@@ -124,6 +124,21 @@ def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+# the C-ABI sees a pointer and a row stride: a tensor of another dtype or layout would be read as other bytes, without an error
+def _check_rows(name, t, n):
+    import torch
+    if not (t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] >= n):
+        raise ValueError("%s: a CUDA uint8 tensor [>= %d, stride] with unit inner stride is needed, got %s %s strides %s on %s"
+                         % (name, n, t.dtype, tuple(t.shape), t.stride(), t.device))
+
+
+def _check_vec(name, t, n):
+    import torch
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= n):
+        raise ValueError("%s: a contiguous CUDA int32 tensor of >= %d entries is needed, got %s %s strides %s on %s"
+                         % (name, n, t.dtype, tuple(t.shape), t.stride(), t.device))
+
+
 class AgmvHip:
     """One context = one GPU + one palette.  Device-resident calls take torch CUDA tensors
     (uint8 / int16 / int32 storage: torch has no unsigned 16/32-bit arithmetic types, the bytes
@@ -271,10 +286,14 @@ class AgmvHip:
         Returns (out u8 [n, out_stride], csize int32 [n]); row f holds the csize[f] payload bytes the reference's file holds.
         Reads the sizes once (synchronises torch's current stream)."""
         import torch
+        _check_rows("bits", bits, n_frames)
+        _check_vec("sizes", sizes, n_frames)
         if out is None:
             out = torch.empty((n_frames, self.lzss_max_csize(bits.stride(0))), dtype=torch.uint8, device=bits.device)
         if csize is None:
             csize = torch.empty(n_frames, dtype=torch.int32, device=bits.device)
+        _check_rows("out", out, n_frames)
+        _check_vec("csize", csize, n_frames)
         self._ck(self.L.agmv_hip_lzss_frames_dev(self.ctx, bits.data_ptr(), bits.stride(0), sizes.data_ptr(), n_frames,
                                                  out.data_ptr(), out.stride(0), csize.data_ptr(), self._stream()))
         return out, csize

@@ -1,7 +1,6 @@
 """The LZSS stage on the GPU (agmv_hip_lzss_frames_dev / AgmvHip.lzss_frames_dev) against the brute-force restatement
 (orc_lzss_compress), the host stage (agmv_lzss_mem) and the closed form of an all-literal stream.  Payloads are the
 csize bytes the reference's file holds for a frame."""
-import ctypes as C
 import os
 import time
 
@@ -10,7 +9,7 @@ import pytest
 
 import hostlib as H
 import lzss_cases as Z
-import oracles as O
+from lzss_cases import gpu_batch, orc
 
 pytestmark = pytest.mark.gpu
 
@@ -23,37 +22,6 @@ def hip():
     h = AgmvHip(0)
     yield h
     h.close()
-
-
-def orc(x):
-    """the brute-force payload: csize bytes of the flushed stream, zero-padded"""
-    x = np.ascontiguousarray(x, np.uint8)
-    out = np.zeros(4 * len(x) + 64, np.uint8)
-    cs = C.c_uint32()
-    n = O.oracle().orc_lzss_compress(np.concatenate([x, np.zeros(8, np.uint8)]), len(x), out, C.byref(cs))
-    p = np.zeros(cs.value, np.uint8)
-    p[:min(n, cs.value)] = out[:min(n, cs.value)]
-    return p
-
-
-def gpu_batch(hip, streams, stride_extra=0, out_extra=0):
-    """one batched device call; rows at a stride larger than needed"""
-    import torch
-    n = len(streams)
-    stride = max([1] + [len(x) for x in streams]) + stride_extra
-    bits = np.zeros((n, stride), np.uint8)
-    for i, x in enumerate(streams):
-        bits[i, :len(x)] = x
-    sizes = np.array([len(x) for x in streams], np.int32)
-    ostride = hip.lzss_max_csize(stride) + out_extra
-    d_bits = torch.from_numpy(bits).cuda()
-    d_sizes = torch.from_numpy(sizes).cuda()
-    out = torch.full((n, ostride), 0xA5, dtype=torch.uint8, device="cuda")
-    out, cs = hip.lzss_frames_dev(d_bits, d_sizes, n, out=out)
-    torch.cuda.synchronize()
-    out = out.cpu().numpy()
-    cs = cs.cpu().numpy().view(np.uint32)
-    return [out[i, :cs[i]].copy() for i in range(n)]
 
 
 def small_cases():
