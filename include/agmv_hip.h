@@ -217,6 +217,51 @@ int agmv_hip_lzss_frames_dev(agmv_hip_ctx* ctx, const uint8_t* d_bits, size_t bi
 int agmv_hip_lzss_frames(agmv_hip_ctx* ctx, const uint8_t* h_bits, size_t bits_stride, const uint32_t* h_sizes,
                          uint32_t n_frames, uint8_t* h_out, size_t out_stride, uint32_t* h_csize);
 
+/* -- LZ stage of the decoder (the LZSS / LZ77 decompression of AGMV_DecodeFrameChunk with its bit reader, reference
+ * src/agmv_decode.c:160-222, src/agmv_utils.c:32-57; the persistent buffer agmv->bitstream->data it decompresses into) --
+ * agmv_hip_lz_decode_frames_dev: version 1 or 2 is LZSS, any other value LZ77.  Frame f's payload starts at
+ *                          d_src + d_off[f]; d_avail[f] bytes of it exist (reads past them return 0 and are not counted;
+ *                          nothing past min(avail, csize + 3) is read), d_usize[f] / d_csize[f] are the chunk header's
+ *                          fields.  Rows may overlap (a reader runs on into the guard and the next chunk header).  Row f of
+ *                          d_bits (stride bits_stride >= cap) receives data[0, bpos) as agmv_lz_decode_mem writes it into a
+ *                          buffer of cap bytes (lim = cap - 16), d_bpos[f] bpos and d_used[f] the payload bytes the reader
+ *                          fetched, capped at avail (they decide where the next chunk is found).  Nothing else is written.
+ *                          Asynchronous on `stream` except that it synchronises the stream once, before its kernels, to read
+ *                          avail / usize / csize (they decide how the batch is cut into chunks); nothing else waits for
+ *                          the device (the per-call tables go up from pinned staging).  cap < 2^31.
+ * agmv_hip_lz_decode_frames_sized_dev: the same with h_avail / h_usize / h_csize in host memory (read before the call
+ *                          returns): no stream synchronisation at all.  What a driver that has parsed the chunk headers
+ *                          itself uses.
+ * agmv_hip_lz_decode_commit_dev: the host driver's loop over the reference's ONE persistent buffer (d_persist, cap bytes) for
+ *                          the first n_frames rows, in frame order: row f's bytes [bpos, bpos + 16), clipped to bits_stride
+ *                          and to cap, become the buffer's, then the buffer's [0, min(bpos, cap)) become row f's.  The rows
+ *                          are then what agmv_hip_decode_bitstreams_dev reads with d_bpos.  A separate call because only the
+ *                          frames before a batch cut may reach the buffer.  Asynchronous on `stream`.
+ * agmv_hip_lz_decode_fallback_frames: frames of the last agmv_hip_lz_decode_frames_dev call that the position-parallel path
+ *                          left to the serial kernel (a match with offset > pos followed by further tokens, or LZ77 output
+ *                          past usize + 256: damaged or crafted streams).  A statistic: the outputs are the same either way.
+ *                          Synchronises the stream.
+ * agmv_hip_lz_decode_frames: both from/to host memory, synchronous: h_src (src_len bytes), h_off[f] + min(avail, csize + 3)
+ *                          <= src_len; rows h_bits [n_frames][bits_stride] are updated in place (bytes behind bpos + 16 keep
+ *                          their content); h_persist (cap bytes, may be NULL = zeroed and not returned) is the buffer
+ *                          before the call and receives it after.
+ * Calls on one context share its LZ-decode work areas: they must not overlap. */
+int agmv_hip_lz_decode_frames_dev(agmv_hip_ctx* ctx, int version, const uint8_t* d_src, const unsigned long long* d_off,
+                                  const uint32_t* d_avail, const uint32_t* d_usize, const uint32_t* d_csize, uint32_t n_frames,
+                                  uint8_t* d_bits, size_t bits_stride, size_t cap, uint32_t* d_bpos, uint32_t* d_used,
+                                  void* stream);
+int agmv_hip_lz_decode_frames_sized_dev(agmv_hip_ctx* ctx, int version, const uint8_t* d_src, const unsigned long long* d_off,
+                                        const uint32_t* h_avail, const uint32_t* h_usize, const uint32_t* h_csize,
+                                        uint32_t n_frames, uint8_t* d_bits, size_t bits_stride, size_t cap, uint32_t* d_bpos,
+                                        uint32_t* d_used, void* stream);
+int agmv_hip_lz_decode_commit_dev(agmv_hip_ctx* ctx, uint8_t* d_bits, size_t bits_stride, const uint32_t* d_bpos,
+                                  uint32_t n_frames, uint8_t* d_persist, size_t cap, void* stream);
+int agmv_hip_lz_decode_fallback_frames(agmv_hip_ctx* ctx, void* stream);
+int agmv_hip_lz_decode_frames(agmv_hip_ctx* ctx, int version, const uint8_t* h_src, size_t src_len,
+                              const unsigned long long* h_off, const uint32_t* h_avail, const uint32_t* h_usize,
+                              const uint32_t* h_csize, uint32_t n_frames, uint8_t* h_bits, size_t bits_stride, size_t cap,
+                              uint32_t* h_bpos, uint32_t* h_used, uint8_t* h_persist);
+
 /* -- helpers on the caller side of the path -------------------------------------------------*/
 /* canonical synthetic clip agmv_synth_v1: frames t0..t0+n-1 into d_pix */
 int agmv_hip_synth_dev(agmv_hip_ctx* ctx, uint32_t* d_pix, uint32_t w, uint32_t h, uint32_t t0,
@@ -246,6 +291,12 @@ int agmv_hip_check(agmv_hip_ctx* ctx, void* stream);
 void* agmv_hip_stream_create(agmv_hip_ctx* ctx);
 void  agmv_hip_stream_destroy(agmv_hip_ctx* ctx, void* stream);
 int   agmv_hip_stream_sync(agmv_hip_ctx* ctx, void* stream);
+/* events order work across streams without a host synchronisation: agmv_hip_stream_wait_event makes later work on `stream`
+   wait for the work before agmv_hip_event_record on the other stream (the sequence decoder hands its LZ stage's rows over so) */
+void* agmv_hip_event_create(agmv_hip_ctx* ctx);
+void  agmv_hip_event_destroy(agmv_hip_ctx* ctx, void* ev);
+int   agmv_hip_event_record(agmv_hip_ctx* ctx, void* ev, void* stream);
+int   agmv_hip_stream_wait_event(agmv_hip_ctx* ctx, void* stream, void* ev);
 void* agmv_hip_host_alloc(size_t bytes);
 void  agmv_hip_host_free(void* h);
 void* agmv_hip_malloc_on(agmv_hip_ctx* ctx, size_t bytes);

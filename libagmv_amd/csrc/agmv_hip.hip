@@ -131,6 +131,7 @@ struct agmv_hip_ctx {
 	hipEvent_t ev_fork;             // ... caller's stream -> parser's stream
 	hipEvent_t ev_slice[DEC_MAX_SLICES];   // ... slice parsed
 	void* lz_ws;                    // agmv_hip_lzss_frames_dev: work areas (agmv_lz_hip.hip)
+	void* lzd_ws;                   // agmv_hip_lz_decode_*: work areas (agmv_lz_decode_hip.hip)
 };
 
 // for agmv_lz_hip.hip, the LZSS stage: the error text, the context's slot for its work areas, the device
@@ -138,6 +139,9 @@ int agmv_hip_internal_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%
 void** agmv_hip_internal_lz_slot(agmv_hip_ctx* c) { return &c->lz_ws; }
 int agmv_hip_internal_device(agmv_hip_ctx* c) { return c->device; }
 void agmv_hip_internal_lz_free(void* p);
+// ... and for agmv_lz_decode_hip.hip, the LZ stage of the decoder
+void** agmv_hip_internal_lzd_slot(agmv_hip_ctx* c) { return &c->lzd_ws; }
+void agmv_hip_internal_lzd_free(void* p);
 
 extern "C" size_t agmv_hip_max_usize(uint32_t w, uint32_t h, int mode512)
 {
@@ -2508,6 +2512,7 @@ extern "C" void agmv_hip_destroy(agmv_hip_ctx* c)
 	for (int i = 0; i < DEC_MAX_SLICES; i++) if (c->ev_slice[i]) (void)hipEventDestroy(c->ev_slice[i]);
 	if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
 	agmv_hip_internal_lz_free(c->lz_ws);
+	agmv_hip_internal_lzd_free(c->lzd_ws);
 	free(c);
 }
 
@@ -3360,6 +3365,31 @@ extern "C" int agmv_hip_stream_sync(agmv_hip_ctx* c, void* stream)
 {
 	if (need_ctx(c, false)) return -1;
 	CK(hipStreamSynchronize((hipStream_t)stream));
+	return 0;
+}
+extern "C" void* agmv_hip_event_create(agmv_hip_ctx* c)
+{
+	if (need_ctx(c, false)) return nullptr;
+	hipEvent_t e = nullptr;
+	if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { snprintf(g_err, sizeof(g_err), "agmv_hip: hipEventCreate failed"); return nullptr; }
+	return (void*)e;
+}
+extern "C" void agmv_hip_event_destroy(agmv_hip_ctx* c, void* ev)
+{
+	if (!c || !ev) return;
+	(void)hipSetDevice(c->device);
+	(void)hipEventDestroy((hipEvent_t)ev);
+}
+extern "C" int agmv_hip_event_record(agmv_hip_ctx* c, void* ev, void* stream)
+{
+	if (need_ctx(c, false)) return -1;
+	CK(hipEventRecord((hipEvent_t)ev, (hipStream_t)stream));
+	return 0;
+}
+extern "C" int agmv_hip_stream_wait_event(agmv_hip_ctx* c, void* stream, void* ev)
+{
+	if (need_ctx(c, false)) return -1;
+	CK(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)ev, 0));
 	return 0;
 }
 extern "C" void* agmv_hip_host_alloc(size_t bytes)

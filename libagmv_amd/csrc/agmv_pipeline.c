@@ -647,8 +647,11 @@ void agmv_histogram_frames(agmv_hip_ctx* ctx, const char* dir, const char* base,
 typedef struct dbatch {
 	unsigned n;
 	uint32_t first;                        /* frame_count of its first frame */
-	u8* h_slab;                            /* pinned [cap][stride] */
+	u8* h_slab;                            /* pinned [cap][stride] (host LZ stage) */
 	uint32_t *h_bpos, *h_out;              /* pinned [cap], [cap][npx] */
+	uint8_t* d_slab;                       /* AGMV_LZ_DECODE_DEVICE: the batch's rows [cap][stride] on the device, their bpos, and */
+	uint32_t* d_bpos;
+	void* ready;                           /* the event behind their commit on the LZ stage's stream */
 	unsigned long name0;                   /* quick_export_<name0 + k>.bmp */
 	int filled, decoded;
 	unsigned saves_left;
@@ -700,7 +703,12 @@ static void* dworker_main(void* p)
 		while (!(id < d->nfilled) && !d->closing) pthread_cond_wait(&d->cv, &d->mu);
 		if (id >= d->nfilled) { pthread_mutex_unlock(&d->mu); break; }
 		pthread_mutex_unlock(&d->mu);
-		if (agmv_hip_memcpy_async(d->ctx, d->d_bits, b->h_slab, d->stride * b->n, 0, d->stream) ||
+		if (b->d_slab) {                       /* the LZ stage left the rows on the device: wait for their commit, on the device */
+			if (agmv_hip_stream_wait_event(d->ctx, d->stream, b->ready) ||
+			    agmv_hip_decode_bitstreams_dev(d->ctx, b->d_slab, d->stride, b->d_bpos, b->n, d->w, d->h, b->first, d->d_nent, out, prev,
+			                                   have_state ? d->d_iframe : NULL, d->stream))
+				goto fail;
+		} else if (agmv_hip_memcpy_async(d->ctx, d->d_bits, b->h_slab, d->stride * b->n, 0, d->stream) ||
 		    agmv_hip_memcpy_async(d->ctx, d->d_bpos, b->h_bpos, 4 * (size_t)b->n, 0, d->stream) ||
 		    agmv_hip_decode_bitstreams_dev(d->ctx, d->d_bits, d->stride, d->d_bpos, b->n, d->w, d->h, b->first, d->d_nent, out, prev,
 		                                   have_state ? d->d_iframe : NULL, d->stream))
@@ -770,6 +778,109 @@ static size_t behind_chunk(const u8* file, size_t len, size_t c, size_t used, in
 	return pos;
 }
 
+/* AGMV_LZ_DECODE_DEVICE=1: the LZ stage of a batch on the GPU (agmv_hip_lz_decode_frames_dev + agmv_hip_lz_decode_commit_dev),
+   on a context and stream of its own (the worker thread owns the decoder's context), into the device rows of the batch's
+   slot.  The persistent buffer stays on the device, zero-initialised like `persist`. */
+typedef struct dlz {
+	agmv_hip_ctx* ctx;
+	void* stream;
+	u8* h_stage;                           /* pinned: the file range that holds a batch's rows ... */
+	uint8_t* d_src; size_t src_cap;        /* ... and its device copy, src_cap bytes each */
+	uint8_t* d_persist;
+	size_t* chunk;                         /* [cap] where each chunk was assumed */
+	unsigned long long *h_off, *d_off;     /* pinned / device [cap] */
+	uint32_t *h_avail, *h_usize, *h_csize, *h_used;              /* pinned [cap] each */
+	uint32_t* d_used;                      /* device [cap] */
+	unsigned batches;
+	double secs;
+} dlz;
+
+static int dlz_open(dlz* z, agmv_hip_ctx* ctx, unsigned cap_frames, size_t cap)
+{
+	const size_t n = cap_frames;
+	memset(z, 0, sizeof(*z));
+	z->ctx = agmv_hip_create(agmv_hip_ctx_device(ctx));
+	if (!z->ctx) return -1;
+	z->stream = agmv_hip_stream_create(z->ctx);
+	z->d_persist = (uint8_t*)agmv_hip_malloc_on(z->ctx, cap);
+	z->chunk = (size_t*)calloc(n, sizeof(size_t));
+	z->h_off = (unsigned long long*)agmv_hip_host_alloc(8 * n);
+	z->d_off = (unsigned long long*)agmv_hip_malloc_on(z->ctx, 8 * n);
+	z->h_avail = (uint32_t*)agmv_hip_host_alloc(4 * 4 * n);
+	z->d_used = (uint32_t*)agmv_hip_malloc_on(z->ctx, 4 * n);
+	if (!z->stream || !z->d_persist || !z->chunk || !z->h_off || !z->d_off || !z->h_avail || !z->d_used) return -1;
+	z->h_usize = z->h_avail + n; z->h_csize = z->h_usize + n; z->h_used = z->h_csize + n;
+	return agmv_hip_memset_async(z->ctx, z->d_persist, 0, cap, z->stream) || agmv_hip_stream_sync(z->ctx, z->stream) ? -1 : 0;
+}
+
+static void dlz_close(dlz* z)
+{
+	if (!z->ctx) return;
+	agmv_hip_host_free(z->h_stage); agmv_hip_host_free(z->h_off); agmv_hip_host_free(z->h_avail);
+	agmv_hip_free_on(z->ctx, z->d_src); agmv_hip_free_on(z->ctx, z->d_persist); agmv_hip_free_on(z->ctx, z->d_off);
+	agmv_hip_free_on(z->ctx, z->d_used);
+	agmv_hip_stream_destroy(z->ctx, z->stream);
+	agmv_hip_destroy(z->ctx);
+	free(z->chunk);
+}
+
+/* locate up to `want` chunks from *pos (every reader assumed to stop right behind its payload), upload the file range that
+   holds their rows in one copy, decompress them into b's device rows, read back used (the one synchronisation a batch
+   needs), cut the batch at the first chunk that is not where it was assumed, commit the frames before the cut to the
+   persistent buffer and record b->ready behind the commit: the worker's stream waits for that event, not the host.
+   Returns the frames of the batch (0: none left), negative on error. */
+static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, const u8* file, size_t len, size_t* pos, unsigned want, int ver,
+                     int has_audio, size_t cap)
+{
+	const double t0 = now_s();
+	unsigned n = 0, k;
+	size_t spos = *pos, lo = 0, hi = 0;
+	while (n < want) {
+		const size_t c = scan_fourcc(file, len, spos, "AGFC");
+		size_t avail, r;
+		uint32_t cs;
+		if (c + 16 > len) break;
+		z->chunk[n] = c;
+		z->h_usize[n] = file[c + 8] | file[c + 9] << 8 | file[c + 10] << 16 | (uint32_t)file[c + 11] << 24;
+		z->h_csize[n] = cs = file[c + 12] | file[c + 13] << 8 | file[c + 14] << 16 | (uint32_t)file[c + 15] << 24;
+		avail = len - (c + 16);
+		z->h_avail[n] = avail > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)avail;
+		r = (size_t)cs + 3 < avail ? (size_t)cs + 3 : avail;       /* the most a reader fetches */
+		if (!n) lo = c + 16;
+		if (c + 16 + r > hi) hi = c + 16 + r;
+		spos = behind_chunk(file, len, c, cs < avail ? cs : avail, has_audio);
+		n++;
+	}
+	if (!n) return 0;
+	for (k = 0; k < n; k++) z->h_off[k] = z->chunk[k] + 16 - lo;
+	if (hi - lo + 1 > z->src_cap) {
+		agmv_hip_host_free(z->h_stage); agmv_hip_free_on(z->ctx, z->d_src);
+		z->src_cap = (hi - lo + 1) * 5 / 4 + 4096;
+		z->h_stage = (u8*)agmv_hip_host_alloc(z->src_cap);
+		z->d_src = (uint8_t*)agmv_hip_malloc_on(z->ctx, z->src_cap);
+		if (!z->h_stage || !z->d_src) { z->src_cap = 0; return -1; }
+	}
+	memcpy(z->h_stage, file + lo, hi - lo);
+	/* (the staging and h_off of the batch before are free again: the read of its `used` waited for its uploads) */
+	if (agmv_hip_memcpy_async(z->ctx, z->d_src, z->h_stage, hi - lo, 0, z->stream) ||
+	    agmv_hip_memcpy_async(z->ctx, z->d_off, z->h_off, 8 * (size_t)n, 0, z->stream) ||
+	    agmv_hip_lz_decode_frames_sized_dev(z->ctx, ver, z->d_src, z->d_off, z->h_avail, z->h_usize, z->h_csize, n, b->d_slab, d->stride,
+	                                        cap, b->d_bpos, z->d_used, z->stream) ||
+	    agmv_hip_memcpy_async(z->ctx, z->h_used, z->d_used, 4 * (size_t)n, 1, z->stream) ||
+	    agmv_hip_stream_sync(z->ctx, z->stream))
+		return -1;
+	for (k = 0; k < n; k++) {                              /* in order: true position of the next chunk */
+		*pos = behind_chunk(file, len, z->chunk[k], z->h_used[k], has_audio);
+		if (k + 1 < n && scan_fourcc(file, len, *pos, "AGFC") != z->chunk[k + 1]) { n = k + 1; break; }   /* the rest was decompressed from the wrong place */
+	}
+	if (agmv_hip_lz_decode_commit_dev(z->ctx, b->d_slab, d->stride, b->d_bpos, n, z->d_persist, cap, z->stream) ||
+	    agmv_hip_event_record(z->ctx, b->ready, z->stream))
+		return -1;
+	z->batches++;
+	z->secs += now_s() - t0;
+	return (int)n;
+}
+
 /* the frame loop of AGMV_DecodeAGMV / AGMV_DecodeVideo on a file image: `pos` = first byte behind the header.
    The LZ stage of a batch runs on the pool, one frame per task.  Where frame k+1's chunk is depends on how many payload
    bytes the bit reader of frame k consumed (it runs past csize into the guard, src/agmv_decode.c:171-198), so the chunks of
@@ -782,12 +893,16 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
                        int has_audio, unsigned cap_frames, unsigned threads, unsigned long* export_count)
 {
 	dpipe d;
+	dlz z;
+	const char* lzv = getenv("AGMV_LZ_DECODE_DEVICE");     /* opt-in: the LZ stage on the GPU (read when a decode starts) */
+	const int lz_dev = lzv && atoi(lzv) == 1;
 	const size_t npx = (size_t)w * h, cap = npx * 33 / 16 + 4096;
 	u8* persist = (u8*)calloc(cap, 1);                     /* the reference's ONE decompression buffer, zero-initialised */
 	uint32_t done = 0;
 	unsigned id = 0, i;
 	int rc = NO_ERR;
 	memset(&d, 0, sizeof(d));
+	memset(&z, 0, sizeof(z));
 	d.ctx = ctx; d.w = w; d.h = h; d.npx = npx; d.stride = (cap + 255) & ~(size_t)255;
 	d.cap = cap_frames; d.nslots = 3;
 	pthread_mutex_init(&d.mu, NULL);
@@ -795,18 +910,27 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	d.slot = (dbatch*)calloc(d.nslots, sizeof(dbatch));
 	if (!d.slot) { d.nslots = 0; rc = MEMORY_CORRUPTION_ERR; goto out; }
 	d.stream = agmv_hip_stream_create(ctx);
-	d.d_bits = (uint8_t*)agmv_hip_malloc_on(ctx, d.stride * d.cap);
-	d.d_bpos = (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
+	d.d_bits = lz_dev ? NULL : (uint8_t*)agmv_hip_malloc_on(ctx, d.stride * d.cap);      /* (the host LZ stage's upload slab) */
+	d.d_bpos = lz_dev ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
 	d.d_nent = (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
 	d.d_out[0] = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
 	d.d_out[1] = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
 	d.d_iframe = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4);
-	if (!persist || !d.stream || !d.d_bits || !d.d_bpos || !d.d_nent || !d.d_out[0] || !d.d_out[1] || !d.d_iframe) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+	if (!persist || !d.stream || (!lz_dev && (!d.d_bits || !d.d_bpos)) || !d.d_nent || !d.d_out[0] || !d.d_out[1] || !d.d_iframe) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+	if (lz_dev && dlz_open(&z, ctx, d.cap, cap)) { rc = MEMORY_CORRUPTION_ERR; goto out; }
 	for (i = 0; i < d.nslots; i++) {
-		d.slot[i].h_slab = (u8*)agmv_hip_host_alloc(d.stride * d.cap);
-		d.slot[i].h_bpos = (uint32_t*)agmv_hip_host_alloc(4 * (size_t)d.cap + 64);
+		if (lz_dev) {                                          /* the rows live on the device only */
+			d.slot[i].d_slab = (uint8_t*)agmv_hip_malloc_on(ctx, d.stride * d.cap);
+			d.slot[i].d_bpos = (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
+			d.slot[i].ready = agmv_hip_event_create(ctx);
+			if (!d.slot[i].d_slab || !d.slot[i].d_bpos || !d.slot[i].ready) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+		} else {
+			d.slot[i].h_slab = (u8*)agmv_hip_host_alloc(d.stride * d.cap);
+			d.slot[i].h_bpos = (uint32_t*)agmv_hip_host_alloc(4 * (size_t)d.cap + 64);
+			if (!d.slot[i].h_slab || !d.slot[i].h_bpos) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+		}
 		d.slot[i].h_out = (uint32_t*)agmv_hip_host_alloc(npx * 4 * d.cap);
-		if (!d.slot[i].h_slab || !d.slot[i].h_bpos || !d.slot[i].h_out) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+		if (!d.slot[i].h_out) { rc = MEMORY_CORRUPTION_ERR; goto out; }
 	}
 	d.pool = agmv_pool_start(threads);
 	if (pthread_create(&d.th, NULL, dworker_main, &d)) {       /* no worker: nothing to join, nothing would ever consume a batch */
@@ -821,7 +945,15 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 		while (b->filled && !d.failed) pthread_cond_wait(&d.cv, &d.mu);      /* the slot's frames of batch id - nslots are all exported */
 		pthread_mutex_unlock(&d.mu);
 		if (d.failed) break;
-		{
+		if (lz_dev) {
+			const int got = dlz_batch(&z, &d, b, file, len, &pos, d.cap < nframes - done ? d.cap : nframes - done, ver, has_audio, cap);
+			if (got < 0) {
+				fprintf(stderr, "libagmv(amd): batch LZ stage: %s (the AGMV hot path runs on the GPU only -- no CPU fallback)\n", agmv_hip_last_error());
+				rc = MEMORY_CORRUPTION_ERR;
+				break;
+			}
+			n = (unsigned)got;
+		} else {
 			unlz* jobs = (unlz*)calloc(d.cap, sizeof(unlz));
 			unsigned left, k;
 			size_t spos = pos;
@@ -874,8 +1006,13 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	pthread_mutex_unlock(&d.mu);
 	agmv_pool_stop(d.pool);
 	if (d.failed) rc = MEMORY_CORRUPTION_ERR;
+	if (lz_dev) TRACE("decode: LZ stage device, %u frames in %u batches, %.3f s\n", (unsigned)done, z.batches, z.secs);
 out:
-	for (i = 0; i < d.nslots; i++) { agmv_hip_host_free(d.slot[i].h_slab); agmv_hip_host_free(d.slot[i].h_bpos); agmv_hip_host_free(d.slot[i].h_out); }
+	for (i = 0; i < d.nslots; i++) {
+		agmv_hip_host_free(d.slot[i].h_slab); agmv_hip_host_free(d.slot[i].h_bpos); agmv_hip_host_free(d.slot[i].h_out);
+		agmv_hip_free_on(ctx, d.slot[i].d_slab); agmv_hip_free_on(ctx, d.slot[i].d_bpos); agmv_hip_event_destroy(ctx, d.slot[i].ready);
+	}
+	dlz_close(&z);
 	agmv_hip_free_on(ctx, d.d_bits); agmv_hip_free_on(ctx, d.d_bpos); agmv_hip_free_on(ctx, d.d_nent);
 	agmv_hip_free_on(ctx, d.d_out[0]); agmv_hip_free_on(ctx, d.d_out[1]); agmv_hip_free_on(ctx, d.d_iframe);
 	agmv_hip_stream_destroy(ctx, d.stream);

@@ -25,6 +25,9 @@ ABI_SYMBOLS = [
     "agmv_hip_host_free", "agmv_hip_malloc_on", "agmv_hip_free_on", "agmv_hip_memcpy_async",
     "agmv_hip_memset_async", "agmv_hip_ctx_device",
     "agmv_hip_lzss_max_csize", "agmv_hip_lzss_frames_dev", "agmv_hip_lzss_frames",
+    "agmv_hip_lz_decode_frames_dev", "agmv_hip_lz_decode_commit_dev", "agmv_hip_lz_decode_fallback_frames",
+    "agmv_hip_lz_decode_frames", "agmv_hip_lz_decode_frames_sized_dev",
+    "agmv_hip_event_create", "agmv_hip_event_destroy", "agmv_hip_event_record", "agmv_hip_stream_wait_event",
 ]
 
 
@@ -99,6 +102,17 @@ def load_library(path=None):
         L.agmv_hip_lzss_frames_dev.restype = C.c_int
         L.agmv_hip_lzss_frames.argtypes = [vp, vp, sz, vp, u32, vp, sz, vp]
         L.agmv_hip_lzss_frames.restype = C.c_int
+    if path is None or hasattr(L, "agmv_hip_lz_decode_frames_dev"):
+        L.agmv_hip_lz_decode_frames_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, u32, vp, sz, sz, vp, vp, vp]
+        L.agmv_hip_lz_decode_frames_dev.restype = C.c_int
+        L.agmv_hip_lz_decode_frames_sized_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, u32, vp, sz, sz, vp, vp, vp]
+        L.agmv_hip_lz_decode_frames_sized_dev.restype = C.c_int
+        L.agmv_hip_lz_decode_commit_dev.argtypes = [vp, vp, sz, vp, u32, vp, sz, vp]
+        L.agmv_hip_lz_decode_commit_dev.restype = C.c_int
+        L.agmv_hip_lz_decode_fallback_frames.argtypes = [vp, vp]
+        L.agmv_hip_lz_decode_fallback_frames.restype = C.c_int
+        L.agmv_hip_lz_decode_frames.argtypes = [vp, C.c_int, vp, sz, vp, vp, vp, vp, u32, vp, sz, sz, vp, vp, vp]
+        L.agmv_hip_lz_decode_frames.restype = C.c_int
     L.agmv_hip_decode_prior_dependent.restype = C.c_int
     L.agmv_hip_synth_dev.argtypes = [vp, vp, u32, u32, u32, u32, C.c_uint64, vp]
     L.agmv_hip_interp_dev.argtypes = [vp, vp, vp, vp, sz, vp]
@@ -313,6 +327,97 @@ class AgmvHip:
         self._ck(self.L.agmv_hip_lzss_frames(self.ctx, _np_ptr(bits), stride, _np_ptr(sizes), n, _np_ptr(out), ostride,
                                              _np_ptr(cs)))
         return [out[i, :cs[i]].copy() for i in range(n)]
+
+    def lz_decode_frames_dev(self, version, src, off, avail, usize, csize, n_frames, cap, bits=None, bpos=None, used=None):
+        """LZ stage of AGMV_DecodeFrameChunk on the GPU: frame f's payload is src[off[f]:] (u8 [N], off int64 [n]) with
+        avail[f] bytes that exist and the chunk's usize[f] / csize[f] (int32 [n]).  Version 1 or 2 is LZSS, any other LZ77.
+        Returns (bits u8 [n, stride >= cap], bpos int32 [n], used int32 [n]); row f holds data[0, bpos) of a buffer of cap
+        bytes.  Reads avail / usize / csize once (synchronises torch's current stream); given as host numpy arrays instead,
+        they go to agmv_hip_lz_decode_frames_sized_dev, which does not synchronise."""
+        import torch
+        if not (src.is_cuda and src.dtype == torch.uint8 and src.dim() == 1 and src.is_contiguous()):
+            raise ValueError("src: a contiguous 1-D CUDA uint8 tensor is needed, got %s %s on %s" % (src.dtype, tuple(src.shape), src.device))
+        if not (off.is_cuda and off.dtype == torch.int64 and off.is_contiguous() and off.numel() >= n_frames):
+            raise ValueError("off: a contiguous CUDA int64 tensor of >= %d entries is needed, got %s %s on %s"
+                             % (n_frames, off.dtype, tuple(off.shape), off.device))
+        host = [isinstance(t, np.ndarray) for t in (avail, usize, csize)]
+        if any(host) and not all(host):
+            raise ValueError("avail, usize, csize: all CUDA int32 tensors or all host arrays")
+        if all(host):
+            sizes = [np.ascontiguousarray(np.asarray(t).astype(np.uint32)) for t in (avail, usize, csize)]
+            if any(t.ndim != 1 or t.size < n_frames for t in sizes):
+                raise ValueError("avail, usize, csize: 1-D host arrays of >= %d entries are needed" % n_frames)
+        else:
+            for name, t in (("avail", avail), ("usize", usize), ("csize", csize)):
+                _check_vec(name, t, n_frames)
+        if bits is None:
+            bits = torch.zeros((n_frames, max(int(cap), 1)), dtype=torch.uint8, device=src.device)
+        if bpos is None:
+            bpos = torch.empty(n_frames, dtype=torch.int32, device=src.device)
+        if used is None:
+            used = torch.empty(n_frames, dtype=torch.int32, device=src.device)
+        _check_rows("bits", bits, n_frames)
+        _check_vec("bpos", bpos, n_frames)
+        _check_vec("used", used, n_frames)
+        if int(cap) > bits.stride(0):
+            raise ValueError("cap %d exceeds the row stride %d of bits" % (cap, bits.stride(0)))
+        if all(host):
+            self._ck(self.L.agmv_hip_lz_decode_frames_sized_dev(self.ctx, int(version), src.data_ptr(), off.data_ptr(), _np_ptr(sizes[0]),
+                                                                _np_ptr(sizes[1]), _np_ptr(sizes[2]), n_frames, bits.data_ptr(),
+                                                                bits.stride(0), int(cap), bpos.data_ptr(), used.data_ptr(), self._stream()))
+        else:
+            self._ck(self.L.agmv_hip_lz_decode_frames_dev(self.ctx, int(version), src.data_ptr(), off.data_ptr(), avail.data_ptr(),
+                                                          usize.data_ptr(), csize.data_ptr(), n_frames, bits.data_ptr(), bits.stride(0),
+                                                          int(cap), bpos.data_ptr(), used.data_ptr(), self._stream()))
+        return bits, bpos, used
+
+    def lz_decode_commit_dev(self, bits, bpos, n_frames, persist):
+        """the reference's persistent buffer over the first n_frames rows, in frame order: each row's 16 bytes behind bpos
+        come from the buffer, then the buffer takes the row's [0, bpos).  persist: u8 [cap], updated in place."""
+        import torch
+        _check_rows("bits", bits, n_frames)
+        _check_vec("bpos", bpos, n_frames)
+        if not (persist.is_cuda and persist.dtype == torch.uint8 and persist.dim() == 1 and persist.is_contiguous()):
+            raise ValueError("persist: a contiguous 1-D CUDA uint8 tensor is needed, got %s %s on %s"
+                             % (persist.dtype, tuple(persist.shape), persist.device))
+        self._ck(self.L.agmv_hip_lz_decode_commit_dev(self.ctx, bits.data_ptr(), bits.stride(0), bpos.data_ptr(), n_frames,
+                                                      persist.data_ptr(), persist.numel(), self._stream()))
+        return bits, persist
+
+    def lz_decode_fallback_frames(self):
+        """frames of the last lz_decode_frames_dev call that went to the serial kernel (a statistic)"""
+        rc = self.L.agmv_hip_lz_decode_fallback_frames(self.ctx, self._stream())
+        if rc < 0:
+            raise RuntimeError(self.L.agmv_hip_last_error().decode())
+        return rc
+
+    def lz_decode_frames(self, version, payloads, usizes, csizes, cap, persist=None):
+        """host form of lz_decode_frames_dev + lz_decode_commit_dev: payloads is a list of u8 arrays (every byte that
+        exists behind each chunk header).  Returns (rows u8 [n, cap], bpos, used, persist u8 [cap]); row f holds
+        data[0, bpos) and the 16 bytes behind it from the persistent buffer (zero-initialised when persist is None)."""
+        payloads = [np.ascontiguousarray(x, np.uint8) for x in payloads]
+        n = len(payloads)
+        if len(usizes) != n or len(csizes) != n:
+            raise ValueError("payloads, usizes and csizes must have the same length")
+        cap = int(cap)
+        lens = np.array([len(x) for x in payloads], np.uint64)
+        off = np.zeros(max(n, 1), np.uint64)
+        if n:
+            off[1:n] = np.cumsum(lens)[:-1]
+        src = np.concatenate(payloads + [np.zeros(1, np.uint8)])
+        avail = lens.astype(np.uint32) if n else np.zeros(1, np.uint32)
+        us = np.ascontiguousarray(np.asarray(usizes, np.uint64).astype(np.uint32)) if n else np.zeros(1, np.uint32)
+        cs = np.ascontiguousarray(np.asarray(csizes, np.uint64).astype(np.uint32)) if n else np.zeros(1, np.uint32)
+        rows = np.zeros((max(n, 1), max(cap, 1)), np.uint8)
+        per = np.zeros(max(cap, 1), np.uint8) if persist is None else np.array(persist, np.uint8, copy=True)
+        if per.size < cap:
+            raise ValueError("persist: %d bytes, cap is %d" % (per.size, cap))
+        bpos = np.zeros(max(n, 1), np.uint32)
+        used = np.zeros(max(n, 1), np.uint32)
+        self._ck(self.L.agmv_hip_lz_decode_frames(self.ctx, int(version), _np_ptr(src), src.size - 1, _np_ptr(off), _np_ptr(avail),
+                                                  _np_ptr(us), _np_ptr(cs), n, _np_ptr(rows), rows.shape[1], cap,
+                                                  _np_ptr(bpos), _np_ptr(used), _np_ptr(per)))
+        return rows[:n], bpos[:n], used[:n], per[:cap]
 
     def parse_fallback_frames(self):
         """frames of the last parse that went to the robust kernels (a statistic)"""
