@@ -105,7 +105,8 @@ int agmv_hip_within2_count(agmv_hip_ctx* ctx, const uint32_t a[16], const uint32
  *  - device memory: 512 MiB of address space for the colour -> entry table (32 MiB of it populated, see
  *    k_lut_build in agmv_hip.hip), plus per-batch work areas grown on demand (look-back status 8 B per tile and
  *    frame, parser workspace <= 15 % of the bitstream slab; LZSS: about 29 bytes per position of the largest chunk of a
- *    batch, at most 2^24 positions, ~460 MiB);
+ *    batch, at most 2^24 positions, ~460 MiB; LZ77: 5 bytes per input byte of the largest chunk of a batch, at most
+ *    2^26 bytes, 320 MiB);
  *  - the encode entry points of ONE context share its look-back status and control words: a second encode is
  *    ordered behind the first (on another stream it waits for it through an event); use one context per
  *    concurrent encoder;
@@ -216,6 +217,40 @@ int agmv_hip_lzss_frames_dev(agmv_hip_ctx* ctx, const uint8_t* d_bits, size_t bi
                              uint32_t n_frames, uint8_t* d_out, size_t out_stride, uint32_t* d_csize, void* stream);
 int agmv_hip_lzss_frames(agmv_hip_ctx* ctx, const uint8_t* h_bits, size_t bits_stride, const uint32_t* h_sizes,
                          uint32_t n_frames, uint8_t* h_out, size_t out_stride, uint32_t* h_csize);
+
+/* -- LZ77 stage of the encoder (AGMV_LZ77, reference src/agmv_encode.c:179-238; its csize :236; the byte behind the stream
+ * that a match running to the end emits, :222, read from the reference's one persistent bitstream buffer) ---------------
+ * agmv_hip_lz77_max_csize: bytes a payload row must hold for a pre-LZ bitstream of n bytes: 4 * n, every byte a token.
+ * agmv_hip_lz77_peek_dev:  the persistent buffer over the n_frames rows, in frame order (reference :222 with the buffer
+ *                          AGMV_EncodeFrame fills, src/agmv_encode.c:561-566): d_peek[f] = size_f < persist_len ?
+ *                          buffer[size_f] : 0, then buffer[0, min(size_f, persist_len)) = row f.  d_persist (persist_len
+ *                          bytes) is updated in place and carries over to the next batch.  Asynchronous on `stream`.
+ * agmv_hip_lz77_frames_dev: rows and sizes as for agmv_hip_lzss_frames_dev.  d_out + f*out_stride receives the 4-byte
+ *                          tokens {dist lo, dist hi, len, next} of the reference's greedy parse (longest match <= 255 in
+ *                          the 65535-byte window, earliest start among equals, one equal byte is a match), d_csize[f] =
+ *                          4 * tokens (reference :236).  The token of a match that ends exactly at size_f takes `next`
+ *                          from d_peek[f] (NULL = zeros); a row is never read past its size.  Sizes may differ and be 0;
+ *                          each must be < 2^24 and out_stride >= agmv_hip_lz77_max_csize of it, else an error return.
+ *                          Bytes of a row behind csize are left as they are.  Asynchronous on `stream` except that it
+ *                          synchronises the stream once, before its kernels, to read d_sizes.  Calls on one context share
+ *                          its LZ77 work areas: they must not overlap.
+ *                          Memory: the work areas hold 5 bytes per input byte of a chunk of frames (a chunk is at most
+ *                          2^26 bytes of input: 320 MiB), grown on demand and kept by the context.
+ * agmv_hip_lz77_frames:    peek + compress from/to host memory (synchronous).  h_persist (persist_len bytes) is the buffer
+ *                          before the call and receives it after; NULL = zeroed and not returned.
+ * agmv_hip_lz77_reparsed_segments: segments of the last agmv_hip_lz77_frames_dev call whose speculative parse did not
+ *                          start on the true token chain and were parsed again from their true entry.  A statistic, like
+ *                          agmv_hip_parse_fallback_frames: the outputs are the same either way.  Synchronises the stream. */
+size_t agmv_hip_lz77_max_csize(size_t n);
+int agmv_hip_lz77_peek_dev(agmv_hip_ctx* ctx, const uint8_t* d_bits, size_t bits_stride, const uint32_t* d_sizes,
+                           uint32_t n_frames, uint8_t* d_persist, size_t persist_len, uint8_t* d_peek, void* stream);
+int agmv_hip_lz77_frames_dev(agmv_hip_ctx* ctx, const uint8_t* d_bits, size_t bits_stride, const uint32_t* d_sizes,
+                             uint32_t n_frames, const uint8_t* d_peek, uint8_t* d_out, size_t out_stride, uint32_t* d_csize,
+                             void* stream);
+int agmv_hip_lz77_frames(agmv_hip_ctx* ctx, const uint8_t* h_bits, size_t bits_stride, const uint32_t* h_sizes,
+                         uint32_t n_frames, uint8_t* h_persist, size_t persist_len, uint8_t* h_out, size_t out_stride,
+                         uint32_t* h_csize);
+int agmv_hip_lz77_reparsed_segments(agmv_hip_ctx* ctx, void* stream);
 
 /* -- LZ stage of the decoder (the LZSS / LZ77 decompression of AGMV_DecodeFrameChunk with its bit reader, reference
  * src/agmv_decode.c:160-222, src/agmv_utils.c:32-57; the persistent buffer agmv->bitstream->data it decompresses into) --

@@ -132,6 +132,7 @@ struct agmv_hip_ctx {
 	hipEvent_t ev_slice[DEC_MAX_SLICES];   // ... slice parsed
 	void* lz_ws;                    // agmv_hip_lzss_frames_dev: work areas (agmv_lz_hip.hip)
 	void* lzd_ws;                   // agmv_hip_lz_decode_*: work areas (agmv_lz_decode_hip.hip)
+	void* lz77_ws;                  // agmv_hip_lz77_*: work areas (agmv_lz77_hip.hip)
 };
 
 // for agmv_lz_hip.hip, the LZSS stage: the error text, the context's slot for its work areas, the device
@@ -142,6 +143,8 @@ void agmv_hip_internal_lz_free(void* p);
 // ... and for agmv_lz_decode_hip.hip, the LZ stage of the decoder
 void** agmv_hip_internal_lzd_slot(agmv_hip_ctx* c) { return &c->lzd_ws; }
 void agmv_hip_internal_lzd_free(void* p);
+void** agmv_hip_internal_lz77_slot(agmv_hip_ctx* c) { return &c->lz77_ws; }
+void agmv_hip_internal_lz77_free(void* p);
 
 extern "C" size_t agmv_hip_max_usize(uint32_t w, uint32_t h, int mode512)
 {
@@ -2513,6 +2516,7 @@ extern "C" void agmv_hip_destroy(agmv_hip_ctx* c)
 	if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
 	agmv_hip_internal_lz_free(c->lz_ws);
 	agmv_hip_internal_lzd_free(c->lzd_ws);
+	agmv_hip_internal_lz77_free(c->lz77_ws);
 	free(c);
 }
 

@@ -175,6 +175,8 @@ typedef struct eworker {
 	uint16_t* d_ient;
 	uint8_t* d_lz;                         /* AGMV_LZ_DEVICE: payload rows [cap][lz_stride] and their csize */
 	uint32_t* d_csize;
+	size_t lz77_stride;                    /* AGMV_LZ77_DEVICE: stride of the rows d_lz holds now (grown on demand) */
+	uint8_t* d_peek;                       /* AGMV_LZ77_DEVICE: [cap] the byte behind each stream */
 } eworker;
 
 struct agmv_seq {
@@ -183,6 +185,9 @@ struct agmv_seq {
 	const char *dir, *base;
 	int scale_w, scale_h, audio_chunks, mode512, lz77, use_b;
 	int lz_dev;                            /* AGMV_LZ_DEVICE=1 and LZSS: the LZ stage runs on the GPU workers */
+	int lz77_dev;                          /* AGMV_LZ77_DEVICE=1, LZ77 and one device: the LZ stage runs on the GPU workers */
+	uint8_t* d_persist;                    /* AGMV_LZ77_DEVICE: `persist` on the device (persist_len bytes, zero-initialised) */
+	unsigned peek_turn;                    /* AGMV_LZ77_DEVICE: the batch whose peek call comes next (under mu) */
 	uint32_t w, h;
 	size_t npx, per, stride, lz_stride;
 	unsigned cap, nslots, nworkers;
@@ -238,6 +243,24 @@ static void lz_task(void* p)
 	free(za);
 }
 
+/* AGMV_LZ77_DEVICE: payload rows for batch b, whose sizes are on the host: 4 bytes per byte of the largest stream (the
+   worst case, 4 * stride, is 17.5 MB per 1080p frame), grown on demand.  Returns the stride of the rows. */
+static size_t lz77_rows(eworker* wk, const ebatch* b)
+{
+	agmv_seq* s = wk->s;
+	size_t top = 0, need;
+	unsigned k;
+	for (k = 0; k < b->n; k++) if (b->sizes[k] > top) top = b->sizes[k];
+	need = (agmv_hip_lz77_max_csize(top) + 256) & ~(size_t)255;
+	if (need > wk->lz77_stride) {
+		agmv_hip_free_on(wk->ctx, wk->d_lz);
+		wk->lz77_stride = (need + need / 4 + 255) & ~(size_t)255;
+		wk->d_lz = (uint8_t*)agmv_hip_malloc_on(wk->ctx, wk->lz77_stride * s->cap);
+		if (!wk->d_lz) seq_die(s, "device allocation");
+	}
+	return wk->lz77_stride;
+}
+
 /* one GPU worker: its batches are id = idx, idx + nworkers, ... in order */
 static void* eworker_main(void* p)
 {
@@ -281,11 +304,27 @@ static void* eworker_main(void* p)
 		                               wk->stream) ||
 		    agmv_hip_memcpy_async(wk->ctx, b->sizes, wk->d_sizes, 4 * (size_t)b->n, 1, wk->stream) || agmv_hip_check(wk->ctx, wk->stream))
 			seq_die(s, "batch encode");
-		if (s->lz_dev) {                                   /* LZSS on the GPU: the payloads travel instead of the bitstreams */
+		if (s->lz_dev || s->lz77_dev) {                    /* LZ on the GPU: the payloads travel instead of the bitstreams */
 			const double tl0 = now_s();
-			if (agmv_hip_lzss_frames_dev(wk->ctx, wk->d_out, s->stride, wk->d_sizes, b->n, wk->d_lz, s->lz_stride, wk->d_csize, wk->stream) ||
+			const size_t lz_stride = s->lz77_dev ? lz77_rows(wk, b) : s->lz_stride;
+			if (s->lz77_dev) {
+				/* the persistent buffer is shared by the two workers and has to see the batches in order: the peek calls take
+				   turns, and the turn is passed on once this one's writes are complete on the device */
+				pthread_mutex_lock(&s->mu);
+				while (s->peek_turn != id) pthread_cond_wait(&s->cv, &s->mu);
+				pthread_mutex_unlock(&s->mu);
+				if (agmv_hip_lz77_peek_dev(wk->ctx, wk->d_out, s->stride, wk->d_sizes, b->n, s->d_persist, s->persist_len, wk->d_peek, wk->stream) ||
+				    agmv_hip_stream_sync(wk->ctx, wk->stream))
+					seq_die(s, "batch LZ77 peek");
+				pthread_mutex_lock(&s->mu);
+				s->peek_turn = id + 1;
+				pthread_cond_broadcast(&s->cv);
+				pthread_mutex_unlock(&s->mu);
+			}
+			if ((s->lz77_dev ? agmv_hip_lz77_frames_dev(wk->ctx, wk->d_out, s->stride, wk->d_sizes, b->n, wk->d_peek, wk->d_lz, lz_stride, wk->d_csize, wk->stream)
+			                 : agmv_hip_lzss_frames_dev(wk->ctx, wk->d_out, s->stride, wk->d_sizes, b->n, wk->d_lz, lz_stride, wk->d_csize, wk->stream)) ||
 			    agmv_hip_memcpy_async(wk->ctx, b->csizes, wk->d_csize, 4 * (size_t)b->n, 1, wk->stream) || agmv_hip_stream_sync(wk->ctx, wk->stream))
-				seq_die(s, "batch LZSS");
+				seq_die(s, s->lz77_dev ? "batch LZ77" : "batch LZSS");
 			for (k = 0; k < b->n; k++) { b->boff[k] = total; total += (size_t)b->csizes[k]; }
 			if (total + 16 > b->h_bits_cap) {
 				agmv_hip_host_free(b->h_bits);
@@ -294,7 +333,7 @@ static void* eworker_main(void* p)
 				if (!b->h_bits) seq_die(s, "pinned allocation");
 			}
 			for (k = 0; k < b->n; k++)
-				if (b->csizes[k] && agmv_hip_memcpy_async(wk->ctx, b->h_bits + b->boff[k], wk->d_lz + (size_t)k * s->lz_stride, b->csizes[k], 1, wk->stream))
+				if (b->csizes[k] && agmv_hip_memcpy_async(wk->ctx, b->h_bits + b->boff[k], wk->d_lz + (size_t)k * lz_stride, b->csizes[k], 1, wk->stream))
 					seq_die(s, "payload download");
 			if (agmv_hip_stream_sync(wk->ctx, wk->stream)) seq_die(s, "payload download");
 			for (k = 0; k < b->n; k++) { b->jobs[k].out = b->h_bits + b->boff[k]; b->jobs[k].csize = b->csizes[k]; }
@@ -332,7 +371,7 @@ static void prepare_batch(agmv_seq* s, ebatch* b)
 {
 	size_t need = 0, coff = 0;
 	unsigned k;
-	if (s->lz_dev) {                                       /* the GPU worker left the payloads (LZSS reads nothing past the end) */
+	if (s->lz_dev || s->lz77_dev) {                        /* the GPU worker left the payloads (LZ77 with the byte past the end from d_persist) */
 		pthread_mutex_lock(&s->mu);
 		b->lz_left = 0;
 		pthread_mutex_unlock(&s->mu);
@@ -464,6 +503,11 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const char* dir, const char* base, 
 		s->lz_dev = !lz77 && lv && atoi(lv) != 0;
 		s->lz_stride = (agmv_hip_lzss_max_csize(s->stride) + 255) & ~(size_t)255;
 	}
+	{	/* AGMV_LZ77_DEVICE=1: LZ77 on the GPU (opt-in).  The persistent buffer behind the streams then lives on ONE device, so
+		   with more than one device the stage stays on the host pool. */
+		const char* lv = getenv("AGMV_LZ77_DEVICE");
+		s->lz77_dev = lz77 && devices == 1 && lv && atoi(lv) != 0;
+	}
 	s->cap = (cap + 3u) & ~3u;
 	s->nworkers = devices * 2;
 	s->nslots = s->nworkers + 2;
@@ -502,9 +546,15 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const char* dir, const char* base, 
 		wk->d_tmp[0] = use_interp ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 4) : NULL;
 		wk->d_tmp[1] = use_interp ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 4) : NULL;
 		wk->d_lz = s->lz_dev ? (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->lz_stride * s->cap) : NULL;
-		wk->d_csize = s->lz_dev ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, 4 * (size_t)s->cap) : NULL;
+		wk->d_csize = s->lz_dev || s->lz77_dev ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, 4 * (size_t)s->cap) : NULL;
+		wk->d_peek = s->lz77_dev ? (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->cap) : NULL;
+		if (s->lz77_dev && i == 0) {
+			s->d_persist = (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->persist_len);
+			if (!s->d_persist || agmv_hip_memset_async(wk->ctx, s->d_persist, 0, s->persist_len, wk->stream) || agmv_hip_stream_sync(wk->ctx, wk->stream))
+				agmv_die("device allocation");
+		}
 		if (!wk->stream || !wk->d_frames || !wk->d_out || !wk->d_sizes || !wk->d_ient || (use_interp && (!wk->d_tmp[0] || !wk->d_tmp[1])) ||
-		    (s->lz_dev && (!wk->d_lz || !wk->d_csize)))
+		    (s->lz_dev && (!wk->d_lz || !wk->d_csize)) || (s->lz77_dev && (!wk->d_peek || !wk->d_csize)))
 			agmv_die("device allocation");
 		if (pthread_create(&wk->th, NULL, eworker_main, wk)) agmv_die("cannot start a GPU worker thread");
 	}
@@ -535,14 +585,15 @@ u32 agmv_seq_close(agmv_seq* s)
 	seq_progress(s, 0, 1);
 	TRACE("pipeline: %u frames in %u batches, %.3f s from open to last chunk written; summed over the threads: BMP parse %.3f s, GPU workers "
 	      "(upload + kernels + download) %.3f s, LZ (%s) %.3f s, chunk writes %.3f s\n", (unsigned)s->frames_written, s->nsubmitted, now_s() - s->t_open,
-	      s->t_load, s->t_gpu, s->lz_dev ? "device" : "host", s->t_lz, s->t_write);
+	      s->t_load, s->t_gpu, s->lz_dev || s->lz77_dev ? "device" : "host", s->t_lz, s->t_write);
 	t0 = now_s();
 	for (i = 0; i < s->nworkers; i++) {
 		eworker* wk = &s->wk[i];
 		pthread_join(wk->th, NULL);
 		agmv_hip_free_on(wk->ctx, wk->d_frames); agmv_hip_free_on(wk->ctx, wk->d_out); agmv_hip_free_on(wk->ctx, wk->d_sizes);
 		agmv_hip_free_on(wk->ctx, wk->d_ient); agmv_hip_free_on(wk->ctx, wk->d_tmp[0]); agmv_hip_free_on(wk->ctx, wk->d_tmp[1]);
-		agmv_hip_free_on(wk->ctx, wk->d_lz); agmv_hip_free_on(wk->ctx, wk->d_csize);
+		agmv_hip_free_on(wk->ctx, wk->d_lz); agmv_hip_free_on(wk->ctx, wk->d_csize); agmv_hip_free_on(wk->ctx, wk->d_peek);
+		if (i == s->nworkers - 1) agmv_hip_free_on(wk->ctx, s->d_persist);       /* (every worker has been joined) */
 		agmv_hip_stream_destroy(wk->ctx, wk->stream);
 		agmv_hip_destroy(wk->ctx);
 	}

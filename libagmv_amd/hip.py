@@ -25,6 +25,8 @@ ABI_SYMBOLS = [
     "agmv_hip_host_free", "agmv_hip_malloc_on", "agmv_hip_free_on", "agmv_hip_memcpy_async",
     "agmv_hip_memset_async", "agmv_hip_ctx_device",
     "agmv_hip_lzss_max_csize", "agmv_hip_lzss_frames_dev", "agmv_hip_lzss_frames",
+    "agmv_hip_lz77_max_csize", "agmv_hip_lz77_peek_dev", "agmv_hip_lz77_frames_dev", "agmv_hip_lz77_frames",
+    "agmv_hip_lz77_reparsed_segments",
     "agmv_hip_lz_decode_frames_dev", "agmv_hip_lz_decode_commit_dev", "agmv_hip_lz_decode_fallback_frames",
     "agmv_hip_lz_decode_frames", "agmv_hip_lz_decode_frames_sized_dev",
     "agmv_hip_event_create", "agmv_hip_event_destroy", "agmv_hip_event_record", "agmv_hip_stream_wait_event",
@@ -102,6 +104,17 @@ def load_library(path=None):
         L.agmv_hip_lzss_frames_dev.restype = C.c_int
         L.agmv_hip_lzss_frames.argtypes = [vp, vp, sz, vp, u32, vp, sz, vp]
         L.agmv_hip_lzss_frames.restype = C.c_int
+    if path is None or hasattr(L, "agmv_hip_lz77_frames_dev"):
+        L.agmv_hip_lz77_max_csize.restype = sz
+        L.agmv_hip_lz77_max_csize.argtypes = [sz]
+        L.agmv_hip_lz77_peek_dev.argtypes = [vp, vp, sz, vp, u32, vp, sz, vp, vp]
+        L.agmv_hip_lz77_peek_dev.restype = C.c_int
+        L.agmv_hip_lz77_frames_dev.argtypes = [vp, vp, sz, vp, u32, vp, vp, sz, vp, vp]
+        L.agmv_hip_lz77_frames_dev.restype = C.c_int
+        L.agmv_hip_lz77_frames.argtypes = [vp, vp, sz, vp, u32, vp, sz, vp, sz, vp]
+        L.agmv_hip_lz77_frames.restype = C.c_int
+        L.agmv_hip_lz77_reparsed_segments.argtypes = [vp, vp]
+        L.agmv_hip_lz77_reparsed_segments.restype = C.c_int
     if path is None or hasattr(L, "agmv_hip_lz_decode_frames_dev"):
         L.agmv_hip_lz_decode_frames_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, u32, vp, sz, sz, vp, vp, vp]
         L.agmv_hip_lz_decode_frames_dev.restype = C.c_int
@@ -327,6 +340,75 @@ class AgmvHip:
         self._ck(self.L.agmv_hip_lzss_frames(self.ctx, _np_ptr(bits), stride, _np_ptr(sizes), n, _np_ptr(out), ostride,
                                              _np_ptr(cs)))
         return [out[i, :cs[i]].copy() for i in range(n)]
+
+    def lz77_max_csize(self, n):
+        """bytes a payload row must hold for a pre-LZ bitstream of n bytes (4 * n)"""
+        return int(self.L.agmv_hip_lz77_max_csize(int(n)))
+
+    def lz77_peek_dev(self, bits, sizes, n_frames, persist, peek=None):
+        """the byte behind each stream in the reference's persistent bitstream buffer, in frame order: peek[f] =
+        persist[sizes[f]] (0 at or behind its end), then persist takes row f.  persist: u8 [persist_len], updated in place.
+        Returns peek u8 [n]."""
+        import torch
+        _check_rows("bits", bits, n_frames)
+        _check_vec("sizes", sizes, n_frames)
+        if not (persist.is_cuda and persist.dtype == torch.uint8 and persist.dim() == 1 and persist.is_contiguous()):
+            raise ValueError("persist: a contiguous 1-D CUDA uint8 tensor is needed, got %s %s on %s"
+                             % (persist.dtype, tuple(persist.shape), persist.device))
+        if peek is None:
+            peek = torch.empty(max(n_frames, 1), dtype=torch.uint8, device=bits.device)
+        if not (peek.is_cuda and peek.dtype == torch.uint8 and peek.is_contiguous() and peek.numel() >= n_frames):
+            raise ValueError("peek: a contiguous CUDA uint8 tensor of >= %d entries is needed" % n_frames)
+        self._ck(self.L.agmv_hip_lz77_peek_dev(self.ctx, bits.data_ptr(), bits.stride(0), sizes.data_ptr(), n_frames,
+                                               persist.data_ptr(), persist.numel(), peek.data_ptr(), self._stream()))
+        return peek
+
+    def lz77_frames_dev(self, bits, sizes, n_frames, peek=None, out=None, csize=None):
+        """LZ77 stage of AGMV_EncodeFrame on the GPU: bits u8 [n, stride] (rows of pre-LZ bitstreams), sizes int32 [n],
+        peek u8 [n] or None (zeros): the byte a match that runs to the end of its stream emits.
+        Returns (out u8 [n, out_stride], csize int32 [n]); row f holds the csize[f] payload bytes the reference's file holds.
+        Reads the sizes once (synchronises torch's current stream)."""
+        import torch
+        _check_rows("bits", bits, n_frames)
+        _check_vec("sizes", sizes, n_frames)
+        if peek is not None and not (peek.is_cuda and peek.dtype == torch.uint8 and peek.is_contiguous() and peek.numel() >= n_frames):
+            raise ValueError("peek: a contiguous CUDA uint8 tensor of >= %d entries is needed" % n_frames)
+        if out is None:
+            out = torch.empty((n_frames, max(self.lz77_max_csize(bits.stride(0)), 1)), dtype=torch.uint8, device=bits.device)
+        if csize is None:
+            csize = torch.empty(n_frames, dtype=torch.int32, device=bits.device)
+        _check_rows("out", out, n_frames)
+        _check_vec("csize", csize, n_frames)
+        self._ck(self.L.agmv_hip_lz77_frames_dev(self.ctx, bits.data_ptr(), bits.stride(0), sizes.data_ptr(), n_frames,
+                                                 peek.data_ptr() if peek is not None else None, out.data_ptr(), out.stride(0),
+                                                 csize.data_ptr(), self._stream()))
+        return out, csize
+
+    def lz77_frames(self, streams, persist=None):
+        """host form of lz77_peek_dev + lz77_frames_dev: a list of u8 arrays (pre-LZ bitstreams) -> list of payloads (csize
+        bytes each).  persist: the persistent buffer before the call (u8 array, updated in place), None = none (peek 0)."""
+        streams = [np.ascontiguousarray(x, np.uint8) for x in streams]
+        n = len(streams)
+        sizes = np.array([len(x) for x in streams], np.uint32)
+        stride = max([1] + [len(x) for x in streams])
+        ostride = self.lz77_max_csize(stride)
+        bits = np.zeros((max(n, 1), stride), np.uint8)
+        for i, x in enumerate(streams):
+            bits[i, :len(x)] = x
+        out = np.zeros((max(n, 1), ostride), np.uint8)
+        cs = np.zeros(max(n, 1), np.uint32)
+        if persist is not None and not (isinstance(persist, np.ndarray) and persist.dtype == np.uint8 and persist.flags.c_contiguous):
+            raise ValueError("persist: a contiguous uint8 array is needed")
+        self._ck(self.L.agmv_hip_lz77_frames(self.ctx, _np_ptr(bits), stride, _np_ptr(sizes), n, _np_ptr(persist),
+                                             persist.size if persist is not None else 0, _np_ptr(out), ostride, _np_ptr(cs)))
+        return [out[i, :cs[i]].copy() for i in range(n)]
+
+    def lz77_reparsed_segments(self):
+        """segments of the last lz77_frames_dev call that were parsed again from their true entry (a statistic)"""
+        rc = self.L.agmv_hip_lz77_reparsed_segments(self.ctx, self._stream())
+        if rc < 0:
+            raise RuntimeError(self.L.agmv_hip_last_error().decode())
+        return rc
 
     def lz_decode_frames_dev(self, version, src, off, avail, usize, csize, n_frames, cap, bits=None, bpos=None, used=None):
         """LZ stage of AGMV_DecodeFrameChunk on the GPU: frame f's payload is src[off[f]:] (u8 [N], off int64 [n]) with

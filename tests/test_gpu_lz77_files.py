@@ -1,0 +1,107 @@
+"""File level with AGMV_LZ77_DEVICE=1 (agmv_pipeline.c: the LZ77 stage on the GPU workers, the persistent buffer behind
+the streams on the device): LZ77 files must come out byte-identical to the host stage's and to the reference's; LZSS files
+and sequences over more than one device are unaffected by the knob."""
+import hashlib
+import os
+import subprocess
+import sys
+import textwrap
+
+import pytest
+
+import hostlib as H
+import oracles as O
+import synth as S
+
+pytestmark = pytest.mark.gpu
+
+DRIVER = textwrap.dedent("""
+    import ctypes as C, sys
+    L = C.CDLL(%r)
+    L.CreateAGMV.restype = C.c_void_p; L.CreateAGMV.argtypes = [C.c_ulong] * 4
+    L.AGMV_EncodeAGMV.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ubyte] + [C.c_ulong] * 5 + [C.c_int] * 3
+    T, W, H, opt, q, comp, batch = [int(x) for x in sys.argv[1:]]
+    if hasattr(L, "AGMV_SetBatchFrames"):                            # (the compiled reference has no batches)
+        L.AGMV_SetBatchFrames.argtypes = [C.c_uint]
+        L.AGMV_SetBatchFrames(batch)
+    a = L.CreateAGMV(T, W, H, 24)
+    L.AGMV_EncodeAGMV(a, b"out.agmv", b"fr", b"f", 1, 1, T, W, H, 24, opt, q, comp)
+""")
+
+
+def encode(tmp_path, sub, so, T, W, Hh, opt, q, comp, batch, **env):
+    """the clip through the drop-in API in a child process: (bytes of the .agmv file, stderr)"""
+    fr = tmp_path / ("fr_%dx%d" % (W, Hh))
+    if not fr.exists():
+        fr.mkdir()
+        for t in range(1, T + 1):
+            H.write_bmp(str(fr / ("f%d.bmp" % t)), S.synth_frame(W, Hh, t))
+    d = tmp_path / sub
+    d.mkdir()
+    os.symlink(str(fr), str(d / "fr"))
+    e = {k: v for k, v in os.environ.items() if k not in ("AGMV_LZ77_DEVICE", "AGMV_LZ_DEVICE", "AGMV_DEVICES", "AGMV_DEVICES_OVERSUBSCRIBE")}
+    e.update(env, AGMV_TRACE="1")
+    r = subprocess.run([sys.executable, "-c", DRIVER % so, str(T), str(W), str(Hh), str(opt), str(q), str(comp), str(batch)],
+                       cwd=str(d), env=e, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=1200)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    return open(d / "out.agmv", "rb").read(), r.stderr
+
+
+def golden_case(golden, tmp_path, name, **env):
+    g = golden["files"][name]
+    assert g["driver"] == "agmv"
+    H.lib()
+    data, err = encode(tmp_path, "run", H.SO, g["T"], g["W"], g["H"], g["opt"], g["quality"], g["compression"], 8, **env)
+    assert len(data) == g["file_len"]
+    assert hashlib.sha256(data).hexdigest() == g["file_sha"], "the .agmv file differs from the reference's"
+    return err
+
+
+def test_lz77_golden_through_the_device_stage(golden, tmp_path):
+    err = golden_case(golden, tmp_path, "agmv_opt2_low_lz77_160x128", AGMV_LZ77_DEVICE="1")
+    assert b"LZ (device)" in err, err.decode()[-2000:]
+
+
+def test_lz77_golden_with_the_knob_off_stays_on_the_host(golden, tmp_path):
+    err = golden_case(golden, tmp_path, "agmv_opt2_low_lz77_160x128", AGMV_LZ77_DEVICE="0")
+    assert b"LZ (host)" in err, err.decode()[-2000:]
+
+
+def test_lzss_golden_is_unaffected_by_the_knob(golden, tmp_path):
+    err = golden_case(golden, tmp_path, "c2_agmv_opt3_low_lzss_320x240", AGMV_LZ77_DEVICE="1")
+    assert b"LZ (host)" in err, err.decode()[-2000:]
+
+
+@pytest.mark.parametrize("shape", [(320, 240, 26, 3), (640, 360, 22, 2)])
+def test_sequences_across_batches_knob_on_and_off(tmp_path, shape):
+    """batches of 4 frames: the persistent buffer crosses batches, the two workers take turns, frame sizes differ"""
+    W, Hh, T, opt = shape
+    H.lib()
+    off, err0 = encode(tmp_path, "off", H.SO, T, W, Hh, opt, 1, 2, 4)
+    on, err1 = encode(tmp_path, "on", H.SO, T, W, Hh, opt, 1, 2, 4, AGMV_LZ77_DEVICE="1")
+    assert b"LZ (host)" in err0 and b"LZ (device)" in err1, err1.decode()[-2000:]
+    assert int.from_bytes(on[4:8], "little") > 8                     # more than two batches
+    assert on == off
+
+
+def test_two_devices_keep_the_host_stage(tmp_path):
+    """AGMV_DEVICES=2: the persistent buffer would have to travel between the devices in batch order; the LZ77 stage stays
+    on the host pool and the trace says so"""
+    W, Hh, T, opt = 320, 240, 26, 3
+    H.lib()
+    one, _ = encode(tmp_path, "one", H.SO, T, W, Hh, opt, 1, 2, 4)
+    two, err = encode(tmp_path, "two", H.SO, T, W, Hh, opt, 1, 2, 4, AGMV_LZ77_DEVICE="1", AGMV_DEVICES="2",
+                      AGMV_DEVICES_OVERSUBSCRIBE="1")
+    assert b"4 GPU workers" in err and b"LZ (host)" in err and b"LZ (device)" not in err, err.decode()[-2000:]
+    assert two == one
+
+
+@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built here")
+def test_device_stage_writes_the_compiled_reference_s_file(tmp_path):
+    W, Hh, T, opt = 64, 48, 40, 2
+    H.lib()
+    ref, _ = encode(tmp_path, "ref", O.REF_SO, T, W, Hh, opt, 1, 2, 4)
+    on, err = encode(tmp_path, "on", H.SO, T, W, Hh, opt, 1, 2, 4, AGMV_LZ77_DEVICE="1")
+    assert b"LZ (device)" in err
+    assert int.from_bytes(ref[4:8], "little") > 8
+    assert on == ref
