@@ -8,11 +8,14 @@
  *            GPU worker threads (two per device, devices = AGMV_DEVICES): H2D -> PDIFS midpoint -> k_encode -> D2H of
  *              batch b, each worker on its own stream and context; batches are whole GOPs, so they are independent given
  *              the palette and go round-robin over the workers / devices (multi-GPU sharding by GOP range, no exchange)
- *            host cores: exact LZSS / LZ77 of batch b-1, one task per frame
+ *            host cores: exact LZSS / LZ77 of batch b-1, one task per frame -- or, opt-in (AGMV_LZ_DEVICE for LZSS,
+ *              AGMV_LZ77_DEVICE for LZ77 on one device), the same stage on the GPU worker's stream behind k_encode: the
+ *              payloads are downloaded instead of the bitstreams
  *            calling thread: chunks written strictly in frame order
- *   decode   calling thread: chunk scan + LZ stage into ONE persistent buffer (the stale-tail semantics need it), batch
- *            slabs in pinned memory; GPU worker: H2D -> parse -> reconstruct -> D2H with the decoder state (last frame,
- *            I-frame snapshot) kept on the device; host cores: BMP export, one task per frame
+ *   decode   calling thread: chunks located, LZ stage on the host cores into pinned batch slabs, with ONE persistent buffer
+ *            for the stale-tail semantics -- or, opt-in (AGMV_LZ_DECODE_DEVICE), on the GPU into device rows, the buffer
+ *            on the device; GPU worker: (H2D ->) parse -> reconstruct -> D2H with the decoder state (last frame, I-frame
+ *            snapshot) kept on the device; host cores: BMP export, one task per frame
  *
  * Plain C + pthreads; everything that touches the GPU goes through include/agmv_hip.h.  No CPU fallback: a GPU failure in
  * the void encoders aborts with a message, in the int-returning decoders it is returned.
@@ -36,6 +39,8 @@ static void* xcalloc(size_t n, size_t m) { void* p = calloc(n ? n : 1, m ? m : 1
 
 static int tracing(void) { static int v = -1; if (v < 0) v = getenv("AGMV_TRACE") != NULL; return v; }
 #define TRACE(...) do { if (tracing()) fprintf(stderr, "agmv trace: " __VA_ARGS__); } while (0)
+/* the opt-in knobs of the encoder are on for any non-zero integer */
+static int env_nonzero(const char* name) { const char* v = getenv(name); return v && atoi(v) != 0; }
 
 /* ------------------------------------------------------------------------------------------
  * a small task pool
@@ -112,6 +117,8 @@ void agmv_pool_stop(agmv_pool* p)
 /* ------------------------------------------------------------------------------------------
  * source frames
  * ------------------------------------------------------------------------------------------ */
+static void die_unreadable(const char* path) { fprintf(stderr, "libagmv(amd): cannot read frame %s\n", path); abort(); }
+
 void agmv_frame_path(char* out, size_t cap, const char* dir, const char* base, long idx)
 {
 	if (dir[0] != 'c' || dir[1] != 'u' || dir[2] != 'r') snprintf(out, cap, "%s/%s%ld.bmp", dir, base, idx);
@@ -127,12 +134,12 @@ void agmv_load_source(const char* dir, const char* base, long idx, int scale_w, 
 	size_t need = (size_t)w * h, have;
 	agmv_frame_path(path, sizeof(path), dir, base, idx);
 	if (!scale_w) {                                        /* straight into the caller's (pinned) buffer */
-		if (agmv_bmp_load_into(path, dst, need, &sw, &sh) != NO_ERR) { fprintf(stderr, "libagmv(amd): cannot read frame %s\n", path); abort(); }
+		if (agmv_bmp_load_into(path, dst, need, &sw, &sh) != NO_ERR) die_unreadable(path);
 		have = (size_t)sw * sh;
 		if (have < need) memset(dst + have, 0, (need - have) * 4);
 		return;
 	}
-	if (agmv_bmp_load(path, &pix, &sw, &sh) != NO_ERR) { fprintf(stderr, "libagmv(amd): cannot read frame %s\n", path); abort(); }
+	if (agmv_bmp_load(path, &pix, &sw, &sh) != NO_ERR) die_unreadable(path);
 	{
 		uint32_t nw, nh;
 		uint32_t* sc = agmv_scale_nearest(pix, sw, sh, ((float)scale_w / sw) + 0.001f, ((float)scale_h / sh) + 0.001f, &nw, &nh);
@@ -147,7 +154,7 @@ void agmv_load_source(const char* dir, const char* base, long idx, int scale_w, 
 /* ------------------------------------------------------------------------------------------
  * encode pipeline
  * ------------------------------------------------------------------------------------------ */
-typedef struct lzjob { const u8* in; uint32_t n; u8* out; u32 csize; int lz77; } lzjob;
+typedef struct lzjob { const u8* in; uint32_t n; u8* out; u32 csize; } lzjob;
 
 typedef struct ebatch {
 	unsigned id, n;
@@ -157,11 +164,11 @@ typedef struct ebatch {
 	unsigned loads_left, lz_left;
 	int loaded, bits_ready;
 	uint32_t* sizes;                       /* pinned [cap] */
-	u8* h_bits; size_t h_bits_cap;         /* pinned, frames packed back to back (+1 byte each for LZ77's look past the end) */
+	u8* h_bits; size_t h_bits_cap;         /* pinned, rows packed back to back by download_rows */
 	size_t* boff;
 	lzjob* jobs;
 	u8* comp; size_t comp_cap;
-	uint32_t* csizes;                      /* pinned [cap]: AGMV_LZ_DEVICE, the csize of each frame */
+	uint32_t* csizes;                      /* pinned [cap]: lz_dev, the csize of each frame */
 } ebatch;
 
 typedef struct eworker {
@@ -173,10 +180,10 @@ typedef struct eworker {
 	uint32_t *d_frames, *d_sizes, *d_tmp[2];
 	uint8_t* d_out;
 	uint16_t* d_ient;
-	uint8_t* d_lz;                         /* AGMV_LZ_DEVICE: payload rows [cap][lz_stride] and their csize */
+	uint8_t* d_lz;                         /* lz_dev: payload rows [cap][LZSS: lz_stride, LZ77: lz77_stride] and their csize */
 	uint32_t* d_csize;
-	size_t lz77_stride;                    /* AGMV_LZ77_DEVICE: stride of the rows d_lz holds now (grown on demand) */
-	uint8_t* d_peek;                       /* AGMV_LZ77_DEVICE: [cap] the byte behind each stream */
+	size_t lz77_stride;                    /* lz_dev, LZ77: stride of the rows d_lz holds now (grown on demand) */
+	uint8_t* d_peek;                       /* lz_dev, LZ77: [cap] the byte behind each stream */
 } eworker;
 
 struct agmv_seq {
@@ -184,10 +191,10 @@ struct agmv_seq {
 	FILE* file;
 	const char *dir, *base;
 	int scale_w, scale_h, audio_chunks, mode512, lz77, use_b;
-	int lz_dev;                            /* AGMV_LZ_DEVICE=1 and LZSS: the LZ stage runs on the GPU workers */
-	int lz77_dev;                          /* AGMV_LZ77_DEVICE=1, LZ77 and one device: the LZ stage runs on the GPU workers */
-	uint8_t* d_persist;                    /* AGMV_LZ77_DEVICE: `persist` on the device (persist_len bytes, zero-initialised) */
-	unsigned peek_turn;                    /* AGMV_LZ77_DEVICE: the batch whose peek call comes next (under mu) */
+	int lz_dev;                            /* the LZ stage runs on the GPU workers (lz77 chooses the form): AGMV_LZ_DEVICE for LZSS,
+	                                          AGMV_LZ77_DEVICE for LZ77 on one device */
+	uint8_t* d_persist;                    /* lz_dev, LZ77: `persist` on the device (persist_len bytes, zero-initialised) */
+	unsigned peek_turn;                    /* lz_dev, LZ77: the batch whose peek call comes next (under mu) */
 	uint32_t w, h;
 	size_t npx, per, stride, lz_stride;
 	unsigned cap, nslots, nworkers;
@@ -207,12 +214,6 @@ struct agmv_seq {
 
 typedef struct loadarg { agmv_seq* s; ebatch* b; unsigned k; int which; } loadarg;
 typedef struct lzarg { agmv_seq* s; ebatch* b; unsigned k; } lzarg;
-
-static void seq_die(agmv_seq* s, const char* what)
-{
-	(void)s;
-	agmv_die(what);
-}
 
 static void load_task(void* p)
 {
@@ -235,7 +236,7 @@ static void lz_task(void* p)
 	agmv_seq* s = za->s;
 	lzjob* j = &za->b->jobs[za->k];
 	const double t0 = now_s();
-	j->csize = j->lz77 ? agmv_lz77_mem(j->in, j->n, j->out) : agmv_lzss_mem(j->in, j->n, j->out);
+	j->csize = s->lz77 ? agmv_lz77_mem(j->in, j->n, j->out) : agmv_lzss_mem(j->in, j->n, j->out);
 	pthread_mutex_lock(&s->mu);
 	s->t_lz += now_s() - t0;
 	if (--za->b->lz_left == 0) pthread_cond_broadcast(&s->cv);
@@ -243,7 +244,7 @@ static void lz_task(void* p)
 	free(za);
 }
 
-/* AGMV_LZ77_DEVICE: payload rows for batch b, whose sizes are on the host: 4 bytes per byte of the largest stream (the
+/* lz_dev, LZ77: payload rows for batch b, whose sizes are on the host: 4 bytes per byte of the largest stream (the
    worst case, 4 * stride, is 17.5 MB per 1080p frame), grown on demand.  Returns the stride of the rows. */
 static size_t lz77_rows(eworker* wk, const ebatch* b)
 {
@@ -256,9 +257,57 @@ static size_t lz77_rows(eworker* wk, const ebatch* b)
 		agmv_hip_free_on(wk->ctx, wk->d_lz);
 		wk->lz77_stride = (need + need / 4 + 255) & ~(size_t)255;
 		wk->d_lz = (uint8_t*)agmv_hip_malloc_on(wk->ctx, wk->lz77_stride * s->cap);
-		if (!wk->d_lz) seq_die(s, "device allocation");
+		if (!wk->d_lz) agmv_die("device allocation");
 	}
 	return wk->lz77_stride;
+}
+
+/* the LZ stage of batch b on the worker's stream, for a sequence with lz_dev: the payload rows into wk->d_lz, their csize
+   into b->csizes (complete on return).  The one place that knows the two device forms.  Returns the stride of the rows. */
+static size_t lz_stage_dev(eworker* wk, ebatch* b)
+{
+	agmv_seq* s = wk->s;
+	const size_t lz_stride = s->lz77 ? lz77_rows(wk, b) : s->lz_stride;
+	int rc;
+	if (s->lz77) {
+		/* the persistent buffer is shared by the two workers and has to see the batches in order: the peek calls take
+		   turns, and the turn is passed on once this one's writes are complete on the device */
+		pthread_mutex_lock(&s->mu);
+		while (s->peek_turn != b->id) pthread_cond_wait(&s->cv, &s->mu);
+		pthread_mutex_unlock(&s->mu);
+		if (agmv_hip_lz77_peek_dev(wk->ctx, wk->d_out, s->stride, wk->d_sizes, b->n, s->d_persist, s->persist_len, wk->d_peek, wk->stream) ||
+		    agmv_hip_stream_sync(wk->ctx, wk->stream))
+			agmv_die("batch LZ77 peek");
+		pthread_mutex_lock(&s->mu);
+		s->peek_turn = b->id + 1;
+		pthread_cond_broadcast(&s->cv);
+		pthread_mutex_unlock(&s->mu);
+		rc = agmv_hip_lz77_frames_dev(wk->ctx, wk->d_out, s->stride, wk->d_sizes, b->n, wk->d_peek, wk->d_lz, lz_stride, wk->d_csize, wk->stream);
+	} else
+		rc = agmv_hip_lzss_frames_dev(wk->ctx, wk->d_out, s->stride, wk->d_sizes, b->n, wk->d_lz, lz_stride, wk->d_csize, wk->stream);
+	if (rc || agmv_hip_memcpy_async(wk->ctx, b->csizes, wk->d_csize, 4 * (size_t)b->n, 1, wk->stream) || agmv_hip_stream_sync(wk->ctx, wk->stream))
+		agmv_die(s->lz77 ? "batch LZ77" : "batch LZSS");
+	return lz_stride;
+}
+
+/* batch b's rows to the host, packed back to back in b->h_bits: row k is len[k] bytes at d_rows + k * row_stride and lands at
+   b->boff[k], with `pad` more bytes reserved behind it (1 for raw bitstreams headed for the host LZ stage, 0 for payloads).
+   Complete on return. */
+static void download_rows(eworker* wk, ebatch* b, const uint8_t* d_rows, size_t row_stride, const uint32_t* len, size_t pad)
+{
+	size_t total = 0;
+	unsigned k;
+	for (k = 0; k < b->n; k++) { b->boff[k] = total; total += (size_t)len[k] + pad; }
+	if (total + 16 > b->h_bits_cap) {
+		agmv_hip_host_free(b->h_bits);
+		b->h_bits_cap = total + total / 4 + 4096;
+		b->h_bits = (u8*)agmv_hip_host_alloc(b->h_bits_cap);
+		if (!b->h_bits) agmv_die("pinned allocation");
+	}
+	for (k = 0; k < b->n; k++)
+		if (len[k] && agmv_hip_memcpy_async(wk->ctx, b->h_bits + b->boff[k], d_rows + (size_t)k * row_stride, len[k], 1, wk->stream))
+			agmv_die("row download");
+	if (agmv_hip_stream_sync(wk->ctx, wk->stream)) agmv_die("row download");
 }
 
 /* one GPU worker: its batches are id = idx, idx + nworkers, ... in order */
@@ -270,7 +319,6 @@ static void* eworker_main(void* p)
 	for (id = wk->idx;; id += s->nworkers) {
 		ebatch* b;
 		unsigned k;
-		size_t total = 0;
 		pthread_mutex_lock(&s->mu);
 		while (!(id < s->nsubmitted && s->slot[id % s->nslots].id == id && s->slot[id % s->nslots].loaded) &&
 		       !(s->closing && id >= s->nsubmitted))
@@ -283,12 +331,12 @@ static void* eworker_main(void* p)
 			const uint32_t* src = b->h_pix + (size_t)k * s->per;
 			uint32_t* dst = wk->d_frames + (size_t)k * s->npx;
 			if (b->srcB[k] < 0) {
-				if (agmv_hip_memcpy_async(wk->ctx, dst, src, s->npx * 4, 0, wk->stream)) seq_die(s, "frame upload");
+				if (agmv_hip_memcpy_async(wk->ctx, dst, src, s->npx * 4, 0, wk->stream)) agmv_die("frame upload");
 			} else {                                       /* AGMV_InterpFrame on the GPU, src/agmv_utils.c:949-969 */
 				if (agmv_hip_memcpy_async(wk->ctx, wk->d_tmp[0], src, s->npx * 4, 0, wk->stream) ||
 				    agmv_hip_memcpy_async(wk->ctx, wk->d_tmp[1], src + s->npx, s->npx * 4, 0, wk->stream) ||
 				    agmv_hip_interp_dev(wk->ctx, dst, wk->d_tmp[0], wk->d_tmp[1], s->npx, wk->stream))
-					seq_die(s, "frame upload / interp");
+					agmv_die("frame upload / interp");
 			}
 		}
 		if (b->first_fc & 3u) {                            /* the batch completes a GOP the caller began: its I-frame entries */
@@ -297,67 +345,22 @@ static void* eworker_main(void* p)
 			for (i = 0; i < s->npx; i++) e[i] = (uint16_t)((s->a->iframe_entries[i].pal_num & 1u) << 8 | s->a->iframe_entries[i].index);
 			if (agmv_hip_stream_sync(wk->ctx, wk->stream) || agmv_hip_memcpy_async(wk->ctx, wk->d_ient, e, s->npx * 2, 0, wk->stream) ||
 			    agmv_hip_stream_sync(wk->ctx, wk->stream))
-				seq_die(s, "entry plane upload");
+				agmv_die("entry plane upload");
 			free(e);
 		}
 		if (agmv_hip_encode_frames_dev(wk->ctx, wk->d_frames, b->n, s->w, s->h, b->first_fc, wk->d_out, s->stride, wk->d_sizes, wk->d_ient,
 		                               wk->stream) ||
 		    agmv_hip_memcpy_async(wk->ctx, b->sizes, wk->d_sizes, 4 * (size_t)b->n, 1, wk->stream) || agmv_hip_check(wk->ctx, wk->stream))
-			seq_die(s, "batch encode");
-		if (s->lz_dev || s->lz77_dev) {                    /* LZ on the GPU: the payloads travel instead of the bitstreams */
-			const double tl0 = now_s();
-			const size_t lz_stride = s->lz77_dev ? lz77_rows(wk, b) : s->lz_stride;
-			if (s->lz77_dev) {
-				/* the persistent buffer is shared by the two workers and has to see the batches in order: the peek calls take
-				   turns, and the turn is passed on once this one's writes are complete on the device */
-				pthread_mutex_lock(&s->mu);
-				while (s->peek_turn != id) pthread_cond_wait(&s->cv, &s->mu);
-				pthread_mutex_unlock(&s->mu);
-				if (agmv_hip_lz77_peek_dev(wk->ctx, wk->d_out, s->stride, wk->d_sizes, b->n, s->d_persist, s->persist_len, wk->d_peek, wk->stream) ||
-				    agmv_hip_stream_sync(wk->ctx, wk->stream))
-					seq_die(s, "batch LZ77 peek");
-				pthread_mutex_lock(&s->mu);
-				s->peek_turn = id + 1;
-				pthread_cond_broadcast(&s->cv);
-				pthread_mutex_unlock(&s->mu);
-			}
-			if ((s->lz77_dev ? agmv_hip_lz77_frames_dev(wk->ctx, wk->d_out, s->stride, wk->d_sizes, b->n, wk->d_peek, wk->d_lz, lz_stride, wk->d_csize, wk->stream)
-			                 : agmv_hip_lzss_frames_dev(wk->ctx, wk->d_out, s->stride, wk->d_sizes, b->n, wk->d_lz, lz_stride, wk->d_csize, wk->stream)) ||
-			    agmv_hip_memcpy_async(wk->ctx, b->csizes, wk->d_csize, 4 * (size_t)b->n, 1, wk->stream) || agmv_hip_stream_sync(wk->ctx, wk->stream))
-				seq_die(s, s->lz77_dev ? "batch LZ77" : "batch LZSS");
-			for (k = 0; k < b->n; k++) { b->boff[k] = total; total += (size_t)b->csizes[k]; }
-			if (total + 16 > b->h_bits_cap) {
-				agmv_hip_host_free(b->h_bits);
-				b->h_bits_cap = total + total / 4 + 4096;
-				b->h_bits = (u8*)agmv_hip_host_alloc(b->h_bits_cap);
-				if (!b->h_bits) seq_die(s, "pinned allocation");
-			}
-			for (k = 0; k < b->n; k++)
-				if (b->csizes[k] && agmv_hip_memcpy_async(wk->ctx, b->h_bits + b->boff[k], wk->d_lz + (size_t)k * lz_stride, b->csizes[k], 1, wk->stream))
-					seq_die(s, "payload download");
-			if (agmv_hip_stream_sync(wk->ctx, wk->stream)) seq_die(s, "payload download");
+			agmv_die("batch encode");
+		const double tl0 = now_s();                        /* (the LZ slot of the trace when the stage runs here) */
+		if (s->lz_dev) {                                   /* LZ on the GPU: the payloads travel instead of the bitstreams */
+			const size_t lz_stride = lz_stage_dev(wk, b);
+			download_rows(wk, b, wk->d_lz, lz_stride, b->csizes, 0);
 			for (k = 0; k < b->n; k++) { b->jobs[k].out = b->h_bits + b->boff[k]; b->jobs[k].csize = b->csizes[k]; }
-			pthread_mutex_lock(&s->mu);
-			s->t_gpu += now_s() - tw0;
-			s->t_lz += now_s() - tl0;
-			b->bits_ready = 1;
-			pthread_cond_broadcast(&s->cv);
-			pthread_mutex_unlock(&s->mu);
-			continue;
-		}
-		for (k = 0; k < b->n; k++) { b->boff[k] = total; total += (size_t)b->sizes[k] + 1; }
-		if (total + 16 > b->h_bits_cap) {
-			agmv_hip_host_free(b->h_bits);
-			b->h_bits_cap = total + total / 4 + 4096;
-			b->h_bits = (u8*)agmv_hip_host_alloc(b->h_bits_cap);
-			if (!b->h_bits) seq_die(s, "pinned allocation");
-		}
-		for (k = 0; k < b->n; k++)
-			if (agmv_hip_memcpy_async(wk->ctx, b->h_bits + b->boff[k], wk->d_out + (size_t)k * s->stride, b->sizes[k], 1, wk->stream))
-				seq_die(s, "bitstream download");
-		if (agmv_hip_stream_sync(wk->ctx, wk->stream)) seq_die(s, "bitstream download");
+		} else download_rows(wk, b, wk->d_out, s->stride, b->sizes, 1);      /* (+1: prepare_batch sets the byte behind each stream) */
 		pthread_mutex_lock(&s->mu);
 		s->t_gpu += now_s() - tw0;
+		if (s->lz_dev) s->t_lz += now_s() - tl0;
 		b->bits_ready = 1;
 		pthread_cond_broadcast(&s->cv);
 		pthread_mutex_unlock(&s->mu);
@@ -371,12 +374,7 @@ static void prepare_batch(agmv_seq* s, ebatch* b)
 {
 	size_t need = 0, coff = 0;
 	unsigned k;
-	if (s->lz_dev || s->lz77_dev) {                        /* the GPU worker left the payloads (LZ77 with the byte past the end from d_persist) */
-		pthread_mutex_lock(&s->mu);
-		b->lz_left = 0;
-		pthread_mutex_unlock(&s->mu);
-		return;
-	}
+	if (s->lz_dev) return;     /* the GPU worker left the payloads (LZ77 with the byte past the end from d_persist); lz_left is 0 since begin_batch */
 	for (k = 0; k < b->n; k++) need += (size_t)b->sizes[k] * (s->lz77 ? 4 : 2) + 64;
 	if (need > b->comp_cap) { free(b->comp); b->comp_cap = need + need / 4; b->comp = (u8*)xmalloc(b->comp_cap); }
 	for (k = 0; k < b->n; k++) {
@@ -384,7 +382,7 @@ static void prepare_batch(agmv_seq* s, ebatch* b)
 		const size_t n = b->sizes[k];
 		raw[n] = n < s->persist_len ? s->persist[n] : 0;
 		memcpy(s->persist, raw, n < s->persist_len ? n : s->persist_len);
-		b->jobs[k].in = raw; b->jobs[k].n = (uint32_t)n; b->jobs[k].out = b->comp + coff; b->jobs[k].lz77 = s->lz77;
+		b->jobs[k].in = raw; b->jobs[k].n = (uint32_t)n; b->jobs[k].out = b->comp + coff;
 		coff += n * (s->lz77 ? 4 : 2) + 64;
 	}
 	pthread_mutex_lock(&s->mu);
@@ -491,23 +489,16 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const char* dir, const char* base, 
 	if (devices < 1) devices = 1;
 	{	/* AGMV_DEVICES_OVERSUBSCRIBE=1: more "devices" than cards -- worker pair d runs on card d % ndev.  The round-robin of
 		   batches over devices, the in-order chunk writer and the per-device tables are then exercised on a one-GPU box. */
-		const char* ov = getenv("AGMV_DEVICES_OVERSUBSCRIBE");
-		if (devices > ndev && !(ov && atoi(ov) != 0)) devices = ndev;
+		if (devices > ndev && !env_nonzero("AGMV_DEVICES_OVERSUBSCRIBE")) devices = ndev;
 	}
 	s->a = a; s->file = file; s->dir = dir; s->base = base; s->scale_w = scale_w; s->scale_h = scale_h;
 	s->audio_chunks = audio_chunks; s->mode512 = mode512; s->lz77 = lz77; s->use_b = use_interp;
 	s->w = (uint32_t)AGMV_GetWidth(a); s->h = (uint32_t)AGMV_GetHeight(a);
 	s->npx = (size_t)s->w * s->h; s->per = s->npx * (use_interp ? 2 : 1); s->stride = agmv_hip_max_usize(s->w, s->h, 1);
-	{	/* AGMV_LZ_DEVICE=1: LZSS on the GPU (opt-in; LZ77 stays on the host with its look past the end) */
-		const char* lv = getenv("AGMV_LZ_DEVICE");
-		s->lz_dev = !lz77 && lv && atoi(lv) != 0;
-		s->lz_stride = (agmv_hip_lzss_max_csize(s->stride) + 255) & ~(size_t)255;
-	}
-	{	/* AGMV_LZ77_DEVICE=1: LZ77 on the GPU (opt-in).  The persistent buffer behind the streams then lives on ONE device, so
-		   with more than one device the stage stays on the host pool. */
-		const char* lv = getenv("AGMV_LZ77_DEVICE");
-		s->lz77_dev = lz77 && devices == 1 && lv && atoi(lv) != 0;
-	}
+	/* the LZ stage on the GPU workers, opt-in: AGMV_LZ_DEVICE acts on LZSS sequences only, AGMV_LZ77_DEVICE on LZ77 ones.  LZ77's
+	   persistent buffer behind the streams then lives on ONE device, so with more than one device its stage stays on the host pool. */
+	s->lz_dev = lz77 ? devices == 1 && env_nonzero("AGMV_LZ77_DEVICE") : env_nonzero("AGMV_LZ_DEVICE");
+	s->lz_stride = (agmv_hip_lzss_max_csize(s->stride) + 255) & ~(size_t)255;
 	s->cap = (cap + 3u) & ~3u;
 	s->nworkers = devices * 2;
 	s->nslots = s->nworkers + 2;
@@ -545,16 +536,16 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const char* dir, const char* base, 
 		wk->d_ient = (uint16_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 2);
 		wk->d_tmp[0] = use_interp ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 4) : NULL;
 		wk->d_tmp[1] = use_interp ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 4) : NULL;
-		wk->d_lz = s->lz_dev ? (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->lz_stride * s->cap) : NULL;
-		wk->d_csize = s->lz_dev || s->lz77_dev ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, 4 * (size_t)s->cap) : NULL;
-		wk->d_peek = s->lz77_dev ? (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->cap) : NULL;
-		if (s->lz77_dev && i == 0) {
+		wk->d_lz = s->lz_dev && !lz77 ? (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->lz_stride * s->cap) : NULL;   /* (LZ77: lz77_rows) */
+		wk->d_csize = s->lz_dev ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, 4 * (size_t)s->cap) : NULL;
+		wk->d_peek = s->lz_dev && lz77 ? (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->cap) : NULL;
+		if (s->lz_dev && lz77 && i == 0) {
 			s->d_persist = (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->persist_len);
 			if (!s->d_persist || agmv_hip_memset_async(wk->ctx, s->d_persist, 0, s->persist_len, wk->stream) || agmv_hip_stream_sync(wk->ctx, wk->stream))
 				agmv_die("device allocation");
 		}
 		if (!wk->stream || !wk->d_frames || !wk->d_out || !wk->d_sizes || !wk->d_ient || (use_interp && (!wk->d_tmp[0] || !wk->d_tmp[1])) ||
-		    (s->lz_dev && (!wk->d_lz || !wk->d_csize)) || (s->lz77_dev && (!wk->d_peek || !wk->d_csize)))
+		    (s->lz_dev && (!wk->d_csize || (lz77 ? !wk->d_peek : !wk->d_lz))))
 			agmv_die("device allocation");
 		if (pthread_create(&wk->th, NULL, eworker_main, wk)) agmv_die("cannot start a GPU worker thread");
 	}
@@ -585,7 +576,7 @@ u32 agmv_seq_close(agmv_seq* s)
 	seq_progress(s, 0, 1);
 	TRACE("pipeline: %u frames in %u batches, %.3f s from open to last chunk written; summed over the threads: BMP parse %.3f s, GPU workers "
 	      "(upload + kernels + download) %.3f s, LZ (%s) %.3f s, chunk writes %.3f s\n", (unsigned)s->frames_written, s->nsubmitted, now_s() - s->t_open,
-	      s->t_load, s->t_gpu, s->lz_dev || s->lz77_dev ? "device" : "host", s->t_lz, s->t_write);
+	      s->t_load, s->t_gpu, s->lz_dev ? "device" : "host", s->t_lz, s->t_write);
 	t0 = now_s();
 	for (i = 0; i < s->nworkers; i++) {
 		eworker* wk = &s->wk[i];
@@ -628,7 +619,7 @@ static void hist_load_task(void* p)
 	hframe* f = &c->fr[ha->i];
 	char path[4096];
 	agmv_frame_path(path, sizeof(path), c->dir, c->base, (long)(c->start + ha->i));
-	if (agmv_bmp_load_into(path, c->ring[ha->i % c->window], c->ring_px, &f->w, &f->h) != NO_ERR) { fprintf(stderr, "libagmv(amd): cannot read frame %s\n", path); abort(); }
+	if (agmv_bmp_load_into(path, c->ring[ha->i % c->window], c->ring_px, &f->w, &f->h) != NO_ERR) die_unreadable(path);
 	pthread_mutex_lock(&c->mu);
 	f->done = 1;
 	pthread_cond_broadcast(&c->cv);
@@ -748,6 +739,8 @@ static void* dworker_main(void* p)
 		dbatch* b = &d->slot[id % d->nslots];
 		uint32_t* out = d->d_out[id & 1];
 		const uint32_t* prev = have_state ? d->d_out[(id - 1) & 1] + (size_t)(prev_n - 1) * d->npx : NULL;
+		const uint8_t* bits = b->d_slab ? b->d_slab : d->d_bits;
+		const uint32_t* bpos = b->d_slab ? b->d_bpos : d->d_bpos;
 		unsigned k;
 		int last_i = -1;
 		pthread_mutex_lock(&d->mu);
@@ -755,13 +748,11 @@ static void* dworker_main(void* p)
 		if (id >= d->nfilled) { pthread_mutex_unlock(&d->mu); break; }
 		pthread_mutex_unlock(&d->mu);
 		if (b->d_slab) {                       /* the LZ stage left the rows on the device: wait for their commit, on the device */
-			if (agmv_hip_stream_wait_event(d->ctx, d->stream, b->ready) ||
-			    agmv_hip_decode_bitstreams_dev(d->ctx, b->d_slab, d->stride, b->d_bpos, b->n, d->w, d->h, b->first, d->d_nent, out, prev,
-			                                   have_state ? d->d_iframe : NULL, d->stream))
-				goto fail;
+			if (agmv_hip_stream_wait_event(d->ctx, d->stream, b->ready)) goto fail;
 		} else if (agmv_hip_memcpy_async(d->ctx, d->d_bits, b->h_slab, d->stride * b->n, 0, d->stream) ||
-		    agmv_hip_memcpy_async(d->ctx, d->d_bpos, b->h_bpos, 4 * (size_t)b->n, 0, d->stream) ||
-		    agmv_hip_decode_bitstreams_dev(d->ctx, d->d_bits, d->stride, d->d_bpos, b->n, d->w, d->h, b->first, d->d_nent, out, prev,
+		           agmv_hip_memcpy_async(d->ctx, d->d_bpos, b->h_bpos, 4 * (size_t)b->n, 0, d->stream))
+			goto fail;
+		if (agmv_hip_decode_bitstreams_dev(d->ctx, bits, d->stride, bpos, b->n, d->w, d->h, b->first, d->d_nent, out, prev,
 		                                   have_state ? d->d_iframe : NULL, d->stream))
 			goto fail;
 		/* decoder state for the next batch stays on the device: img_data = the last frame (read in place from this batch's
@@ -803,19 +794,7 @@ static size_t scan_fourcc(const u8* d, size_t len, size_t pos, const char* cc)
 	return len;
 }
 
-/* the LZ stage of one frame on a pool thread: straight into the frame's row of the batch slab (the decoder copies only
-   from bytes it has written itself, src < bpos, so the row's old content does not matter) */
-typedef struct unlz { dpipe* d; int ver; const u8* payload; size_t avail, cap, used, chunk; uint32_t usize, csize, bpos; u8* row; unsigned* left; } unlz;
-
-static void unlz_task(void* p)
-{
-	unlz* j = (unlz*)p;
-	dpipe* d = j->d;
-	j->bpos = agmv_lz_decode_mem(j->ver, j->payload, j->avail, j->usize, j->csize, j->row, j->cap, &j->used);
-	pthread_mutex_lock(&d->mu);
-	if (--*j->left == 0) pthread_cond_broadcast(&d->cv);
-	pthread_mutex_unlock(&d->mu);
-}
+static uint32_t le32(const u8* p) { return p[0] | p[1] << 8 | p[2] << 16 | (uint32_t)p[3] << 24; }
 
 /* where the reference's reader stands behind a frame chunk at c whose LZ stage consumed `used` payload bytes (audio: AGMV_FindNextAudioChunk
    + skip, out of scope) */
@@ -824,9 +803,55 @@ static size_t behind_chunk(const u8* file, size_t len, size_t c, size_t used, in
 	size_t pos = c + 16 + used;
 	if (has_audio) {
 		size_t ac = scan_fourcc(file, len, pos, "AGAC");
-		if (ac + 8 <= len) pos = ac + 8 + (file[ac + 4] | file[ac + 5] << 8 | file[ac + 6] << 16 | (size_t)file[ac + 7] << 24);
+		if (ac + 8 <= len) pos = ac + 8 + le32(file + ac + 4);
 	}
 	return pos;
+}
+
+/* Where frame k+1's chunk is depends on how many payload bytes the bit reader of frame k consumed (it runs past csize into
+   the guard, src/agmv_decode.c:171-198).  So the chunks of a batch are first located as if every reader stopped right
+   behind its payload (locate_chunks), the LZ stage decompresses them all at once and reports what each reader consumed,
+   and the true positions are then checked in order (cut_batch): at the first chunk that was not where it was assumed the
+   batch is cut, and the next one starts from the true position.  A chunk: its "AGFC" at `at`, its header fields, `avail` bytes
+   of file behind its 16-byte header, and the `used` payload bytes that its LZ stage reports. */
+typedef struct dchunk { size_t at; uint32_t usize, csize; size_t avail, used; } dchunk;
+
+static unsigned locate_chunks(const u8* file, size_t len, size_t pos, int has_audio, dchunk* c, unsigned want)
+{
+	unsigned n;
+	for (n = 0; n < want; n++) {
+		const size_t at = scan_fourcc(file, len, pos, "AGFC");
+		if (at + 16 > len) break;
+		c[n].at = at; c[n].usize = le32(file + at + 8); c[n].csize = le32(file + at + 12); c[n].avail = len - (at + 16);
+		pos = behind_chunk(file, len, at, c[n].csize < c[n].avail ? c[n].csize : c[n].avail, has_audio);
+	}
+	return n;
+}
+
+/* *pos = the true position behind the last chunk that was where it was assumed; returns the frames up to and including it
+   (the rest was decompressed from the wrong place) */
+static unsigned cut_batch(const u8* file, size_t len, int has_audio, const dchunk* c, unsigned n, size_t* pos)
+{
+	unsigned k;
+	for (k = 0; k < n; k++) {
+		*pos = behind_chunk(file, len, c[k].at, c[k].used, has_audio);
+		if (k + 1 < n && scan_fourcc(file, len, *pos, "AGFC") != c[k + 1].at) return k + 1;
+	}
+	return n;
+}
+
+/* the host LZ stage of one frame on a pool thread: straight into the frame's row of the batch slab (the decoder copies only
+   from bytes it has written itself, src < bpos, so the row's old content does not matter) */
+typedef struct unlz { dpipe* d; int ver; const u8* payload; dchunk* c; size_t cap; uint32_t bpos; u8* row; unsigned* left; } unlz;
+
+static void unlz_task(void* p)
+{
+	unlz* j = (unlz*)p;
+	dpipe* d = j->d;
+	j->bpos = agmv_lz_decode_mem(j->ver, j->payload, j->c->avail, j->c->usize, j->c->csize, j->row, j->cap, &j->c->used);
+	pthread_mutex_lock(&d->mu);
+	if (--*j->left == 0) pthread_cond_broadcast(&d->cv);
+	pthread_mutex_unlock(&d->mu);
 }
 
 /* AGMV_LZ_DECODE_DEVICE=1: the LZ stage of a batch on the GPU (agmv_hip_lz_decode_frames_dev + agmv_hip_lz_decode_commit_dev),
@@ -838,7 +863,6 @@ typedef struct dlz {
 	u8* h_stage;                           /* pinned: the file range that holds a batch's rows ... */
 	uint8_t* d_src; size_t src_cap;        /* ... and its device copy, src_cap bytes each */
 	uint8_t* d_persist;
-	size_t* chunk;                         /* [cap] where each chunk was assumed */
 	unsigned long long *h_off, *d_off;     /* pinned / device [cap] */
 	uint32_t *h_avail, *h_usize, *h_csize, *h_used;              /* pinned [cap] each */
 	uint32_t* d_used;                      /* device [cap] */
@@ -854,12 +878,11 @@ static int dlz_open(dlz* z, agmv_hip_ctx* ctx, unsigned cap_frames, size_t cap)
 	if (!z->ctx) return -1;
 	z->stream = agmv_hip_stream_create(z->ctx);
 	z->d_persist = (uint8_t*)agmv_hip_malloc_on(z->ctx, cap);
-	z->chunk = (size_t*)calloc(n, sizeof(size_t));
 	z->h_off = (unsigned long long*)agmv_hip_host_alloc(8 * n);
 	z->d_off = (unsigned long long*)agmv_hip_malloc_on(z->ctx, 8 * n);
 	z->h_avail = (uint32_t*)agmv_hip_host_alloc(4 * 4 * n);
 	z->d_used = (uint32_t*)agmv_hip_malloc_on(z->ctx, 4 * n);
-	if (!z->stream || !z->d_persist || !z->chunk || !z->h_off || !z->d_off || !z->h_avail || !z->d_used) return -1;
+	if (!z->stream || !z->d_persist || !z->h_off || !z->d_off || !z->h_avail || !z->d_used) return -1;
 	z->h_usize = z->h_avail + n; z->h_csize = z->h_usize + n; z->h_used = z->h_csize + n;
 	return agmv_hip_memset_async(z->ctx, z->d_persist, 0, cap, z->stream) || agmv_hip_stream_sync(z->ctx, z->stream) ? -1 : 0;
 }
@@ -872,38 +895,27 @@ static void dlz_close(dlz* z)
 	agmv_hip_free_on(z->ctx, z->d_used);
 	agmv_hip_stream_destroy(z->ctx, z->stream);
 	agmv_hip_destroy(z->ctx);
-	free(z->chunk);
 }
 
-/* locate up to `want` chunks from *pos (every reader assumed to stop right behind its payload), upload the file range that
-   holds their rows in one copy, decompress them into b's device rows, read back used (the one synchronisation a batch
-   needs), cut the batch at the first chunk that is not where it was assumed, commit the frames before the cut to the
-   persistent buffer and record b->ready behind the commit: the worker's stream waits for that event, not the host.
+/* locate up to `want` chunks from *pos, upload the file range that holds their rows in one copy, decompress them into b's
+   device rows, read back used (the one synchronisation a batch needs), cut the batch, commit the frames before the cut to
+   the persistent buffer and record b->ready behind the commit: the worker's stream waits for that event, not the host.
    Returns the frames of the batch (0: none left), negative on error. */
-static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, const u8* file, size_t len, size_t* pos, unsigned want, int ver,
+static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, dchunk* c, const u8* file, size_t len, size_t* pos, unsigned want, int ver,
                      int has_audio, size_t cap)
 {
 	const double t0 = now_s();
-	unsigned n = 0, k;
-	size_t spos = *pos, lo = 0, hi = 0;
-	while (n < want) {
-		const size_t c = scan_fourcc(file, len, spos, "AGFC");
-		size_t avail, r;
-		uint32_t cs;
-		if (c + 16 > len) break;
-		z->chunk[n] = c;
-		z->h_usize[n] = file[c + 8] | file[c + 9] << 8 | file[c + 10] << 16 | (uint32_t)file[c + 11] << 24;
-		z->h_csize[n] = cs = file[c + 12] | file[c + 13] << 8 | file[c + 14] << 16 | (uint32_t)file[c + 15] << 24;
-		avail = len - (c + 16);
-		z->h_avail[n] = avail > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)avail;
-		r = (size_t)cs + 3 < avail ? (size_t)cs + 3 : avail;       /* the most a reader fetches */
-		if (!n) lo = c + 16;
-		if (c + 16 + r > hi) hi = c + 16 + r;
-		spos = behind_chunk(file, len, c, cs < avail ? cs : avail, has_audio);
-		n++;
-	}
+	unsigned n = locate_chunks(file, len, *pos, has_audio, c, want), k;
+	size_t lo, hi = 0;
 	if (!n) return 0;
-	for (k = 0; k < n; k++) z->h_off[k] = z->chunk[k] + 16 - lo;
+	lo = c[0].at + 16;
+	for (k = 0; k < n; k++) {
+		const size_t r = (size_t)c[k].csize + 3 < c[k].avail ? (size_t)c[k].csize + 3 : c[k].avail;       /* the most a reader fetches */
+		if (c[k].at + 16 + r > hi) hi = c[k].at + 16 + r;
+		z->h_off[k] = c[k].at + 16 - lo;
+		z->h_avail[k] = c[k].avail > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)c[k].avail;
+		z->h_usize[k] = c[k].usize; z->h_csize[k] = c[k].csize;
+	}
 	if (hi - lo + 1 > z->src_cap) {
 		agmv_hip_host_free(z->h_stage); agmv_hip_free_on(z->ctx, z->d_src);
 		z->src_cap = (hi - lo + 1) * 5 / 4 + 4096;
@@ -920,10 +932,8 @@ static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, const u8* file, size_t l
 	    agmv_hip_memcpy_async(z->ctx, z->h_used, z->d_used, 4 * (size_t)n, 1, z->stream) ||
 	    agmv_hip_stream_sync(z->ctx, z->stream))
 		return -1;
-	for (k = 0; k < n; k++) {                              /* in order: true position of the next chunk */
-		*pos = behind_chunk(file, len, z->chunk[k], z->h_used[k], has_audio);
-		if (k + 1 < n && scan_fourcc(file, len, *pos, "AGFC") != z->chunk[k + 1]) { n = k + 1; break; }   /* the rest was decompressed from the wrong place */
-	}
+	for (k = 0; k < n; k++) c[k].used = z->h_used[k];
+	n = cut_batch(file, len, has_audio, c, n, pos);
 	if (agmv_hip_lz_decode_commit_dev(z->ctx, b->d_slab, d->stride, b->d_bpos, n, z->d_persist, cap, z->stream) ||
 	    agmv_hip_event_record(z->ctx, b->ready, z->stream))
 		return -1;
@@ -933,12 +943,9 @@ static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, const u8* file, size_t l
 }
 
 /* the frame loop of AGMV_DecodeAGMV / AGMV_DecodeVideo on a file image: `pos` = first byte behind the header.
-   The LZ stage of a batch runs on the pool, one frame per task.  Where frame k+1's chunk is depends on how many payload
-   bytes the bit reader of frame k consumed (it runs past csize into the guard, src/agmv_decode.c:171-198), so the chunks of
-   a batch are first located as if every reader stopped right behind its payload, and after the frames have been
-   decompressed the true positions are checked in order: at the first chunk that was not where it was assumed the batch
-   is cut and the next one starts from the true position.  The bytes behind bpos that the block parser may read on an
-   over-run are those of the reference's ONE persistent buffer: they are taken from `persist` in frame order, which then
+   The LZ stage of a batch (between locate_chunks and cut_batch) runs on the pool, one frame per task, or with
+   AGMV_LZ_DECODE_DEVICE=1 on the GPU (dlz_batch).  The bytes behind bpos that the block parser may read on an over-run are
+   those of the reference's ONE persistent buffer: the host stage takes them from `persist` in frame order, which then
    receives the frame. */
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
                        int has_audio, unsigned cap_frames, unsigned threads, unsigned long* export_count)
@@ -949,6 +956,8 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	const int lz_dev = lzv && atoi(lzv) == 1;
 	const size_t npx = (size_t)w * h, cap = npx * 33 / 16 + 4096;
 	u8* persist = (u8*)calloc(cap, 1);                     /* the reference's ONE decompression buffer, zero-initialised */
+	dchunk* chunks = (dchunk*)calloc(cap_frames, sizeof(dchunk));           /* the chunks of a batch, and the host LZ stage's jobs */
+	unlz* jobs = lz_dev ? NULL : (unlz*)calloc(cap_frames, sizeof(unlz));
 	uint32_t done = 0;
 	unsigned id = 0, i;
 	int rc = NO_ERR;
@@ -967,7 +976,7 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	d.d_out[0] = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
 	d.d_out[1] = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
 	d.d_iframe = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4);
-	if (!persist || !d.stream || (!lz_dev && (!d.d_bits || !d.d_bpos)) || !d.d_nent || !d.d_out[0] || !d.d_out[1] || !d.d_iframe) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+	if (!persist || !chunks || (!lz_dev && !jobs) || !d.stream || (!lz_dev && (!d.d_bits || !d.d_bpos)) || !d.d_nent || !d.d_out[0] || !d.d_out[1] || !d.d_iframe) { rc = MEMORY_CORRUPTION_ERR; goto out; }
 	if (lz_dev && dlz_open(&z, ctx, d.cap, cap)) { rc = MEMORY_CORRUPTION_ERR; goto out; }
 	for (i = 0; i < d.nslots; i++) {
 		if (lz_dev) {                                          /* the rows live on the device only */
@@ -991,13 +1000,14 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	}
 	while (done < nframes) {
 		dbatch* b = &d.slot[id % d.nslots];
-		unsigned n = 0;
+		const unsigned want = d.cap < nframes - done ? d.cap : nframes - done;
+		unsigned n;
 		pthread_mutex_lock(&d.mu);
 		while (b->filled && !d.failed) pthread_cond_wait(&d.cv, &d.mu);      /* the slot's frames of batch id - nslots are all exported */
 		pthread_mutex_unlock(&d.mu);
 		if (d.failed) break;
 		if (lz_dev) {
-			const int got = dlz_batch(&z, &d, b, file, len, &pos, d.cap < nframes - done ? d.cap : nframes - done, ver, has_audio, cap);
+			const int got = dlz_batch(&z, &d, b, chunks, file, len, &pos, want, ver, has_audio, cap);
 			if (got < 0) {
 				fprintf(stderr, "libagmv(amd): batch LZ stage: %s (the AGMV hot path runs on the GPU only -- no CPU fallback)\n", agmv_hip_last_error());
 				rc = MEMORY_CORRUPTION_ERR;
@@ -1005,37 +1015,25 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 			}
 			n = (unsigned)got;
 		} else {
-			unlz* jobs = (unlz*)calloc(d.cap, sizeof(unlz));
 			unsigned left, k;
-			size_t spos = pos;
-			if (!jobs) { rc = MEMORY_CORRUPTION_ERR; break; }
-			while (n < d.cap && done + n < nframes) {          /* locate: every reader assumed to stop right behind its payload */
-				size_t c = scan_fourcc(file, len, spos, "AGFC");
-				unlz* j = &jobs[n];
-				if (c + 16 > len) break;
-				j->d = &d; j->ver = ver; j->chunk = c; j->left = &left;
-				j->usize = file[c + 8] | file[c + 9] << 8 | file[c + 10] << 16 | (uint32_t)file[c + 11] << 24;
-				j->csize = file[c + 12] | file[c + 13] << 8 | file[c + 14] << 16 | (uint32_t)file[c + 15] << 24;
-				j->payload = file + c + 16; j->avail = len - (c + 16); j->cap = cap;
-				j->row = b->h_slab + (size_t)n * d.stride;
-				spos = behind_chunk(file, len, c, j->csize < j->avail ? j->csize : j->avail, has_audio);
-				n++;
+			n = left = locate_chunks(file, len, pos, has_audio, chunks, want);
+			for (k = 0; k < n; k++) {
+				unlz* j = &jobs[k];
+				j->d = &d; j->ver = ver; j->c = &chunks[k]; j->left = &left; j->cap = cap;
+				j->payload = file + chunks[k].at + 16; j->row = b->h_slab + (size_t)k * d.stride;
+				agmv_pool_submit(d.pool, unlz_task, j);
 			}
-			left = n;
-			for (k = 0; k < n; k++) agmv_pool_submit(d.pool, unlz_task, &jobs[k]);
 			pthread_mutex_lock(&d.mu);
 			while (left) pthread_cond_wait(&d.cv, &d.mu);
 			pthread_mutex_unlock(&d.mu);
-			for (k = 0; k < n; k++) {                          /* in order: stale bytes, persistent buffer, true position of the next chunk */
+			n = cut_batch(file, len, has_audio, chunks, n, &pos);
+			for (k = 0; k < n; k++) {                          /* in order: stale bytes, persistent buffer */
 				unlz* j = &jobs[k];
 				const size_t bp = j->bpos, tail = bp + 16 < d.stride ? 16 : (bp < d.stride ? d.stride - bp : 0);
 				if (tail) memcpy(j->row + bp, persist + bp, tail);
 				memcpy(persist, j->row, bp < cap ? bp : cap);
 				b->h_bpos[k] = j->bpos;
-				pos = behind_chunk(file, len, j->chunk, j->used, has_audio);
-				if (k + 1 < n && scan_fourcc(file, len, pos, "AGFC") != jobs[k + 1].chunk) { n = k + 1; break; }   /* the rest was decompressed from the wrong place */
 			}
-			free(jobs);
 		}
 		if (!n) break;
 		b->n = n; b->first = done; b->name0 = *export_count + 1;
@@ -1067,7 +1065,7 @@ out:
 	agmv_hip_free_on(ctx, d.d_bits); agmv_hip_free_on(ctx, d.d_bpos); agmv_hip_free_on(ctx, d.d_nent);
 	agmv_hip_free_on(ctx, d.d_out[0]); agmv_hip_free_on(ctx, d.d_out[1]); agmv_hip_free_on(ctx, d.d_iframe);
 	agmv_hip_stream_destroy(ctx, d.stream);
-	free(d.slot); free(persist);
+	free(d.slot); free(persist); free(chunks); free(jobs);
 	pthread_mutex_destroy(&d.mu);
 	pthread_cond_destroy(&d.cv);
 	return rc;
