@@ -282,6 +282,28 @@ void AGMV_SynthFrame(unsigned* pix, unsigned w, unsigned h, unsigned t, unsigned
    of AGMV_QuantizeColor codes (the +1 initial count is added inside).  pal0/pal1: 256 words each. */
 void AGMV_BuildPalette(const unsigned* hist, AGMV_QUALITY quality, AGMV_OPT opt, u32 pal0[256], u32 pal1[256]);
 
+/* Sequences from and to frames in GPU memory: the .agmv files of the three BMP drivers without the BMPs.
+   d_frames is device memory of the library's own device (env AGMV_DEVICE, default 0; AGMV_DEVICES is not consulted),
+   [num_of_frames][height][width] pixels of 4 bytes, 0x00RRGGBB (bits >= 24 are ignored).
+   The library works on streams of its own: the frames must be complete when AGMV_EncodeFramesDev is called, and the decoded
+   frames are complete when AGMV_DecodeFramesDev returns.
+   AGMV_EncodeFramesDev writes, byte for byte, the file the BMP driver of the schedule writes for f1.bmp .. f<n>.bmp holding the
+   same frames: FULL = AGMV_EncodeFullAGMV, PDIFS = AGMV_EncodeAGMV (both on CreateAGMV(n, w, h, fps), frames 1 .. n),
+   ADAPTIVE = AGMV_EncodeVideo(frames 1 .. n), with its CreateAGMV(n - 1, ...), per-opt leniency and header patch.  For the GBA
+   and NDS opts width / height are the SOURCE size; GBA_GEN_AGMV.h is not written.  Returns 0, or -- before any file is
+   created -- a negative value: -1 NULL pointer or unknown enum value, -2 fewer frames than the schedule's first group reads
+   (4 light PDIFS / adaptive, 2 heavy, 1 FULL), -3 width or height that cannot be encoded (not a multiple of 4 for an opt that
+   does not scale).  A GPU failure inside the encoder aborts with a message, as in the BMP drivers.
+   AGMV_DecodeFramesDev is AGMV_DecodeAGMV with another destination: frame k of the file (0-based) lands at
+   d_frames + k * width * height.  It decodes at most cap_frames frames and returns their number, or a negative Error.
+   *info (may be NULL) receives the header's AGMV_INFO; with d_frames NULL nothing is decoded and only *info is filled, so the
+   caller can size the buffer. */
+typedef enum AGMV_SCHEDULE { AGMV_SCHEDULE_FULL = 0x1, AGMV_SCHEDULE_PDIFS = 0x2, AGMV_SCHEDULE_ADAPTIVE = 0x3 } AGMV_SCHEDULE;
+int AGMV_EncodeFramesDev(const char* filename, const unsigned* d_frames, u32 num_of_frames, u32 width, u32 height,
+                         u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression,
+                         AGMV_SCHEDULE schedule);
+int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frames, AGMV_INFO* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -308,6 +308,17 @@ int agmv_hip_interp_dev(agmv_hip_ctx* ctx, uint32_t* d_out, const uint32_t* d_f1
    (reference src/agmv_encode.c:2390-2394, src/agmv_utils.c:695-742); hist has 2^19 bins */
 int agmv_hip_histogram_dev(agmv_hip_ctx* ctx, const uint32_t* d_pix, size_t n_pixels, int quality,
                            uint32_t* d_hist, void* stream);
+/* the integer behind AGMV_CompareFrameSimilarity (reference src/agmv_utils.c:920-947) for every adjacent pair of a clip
+   d_pix[n_frames][n_pixels]: d_counts[f], f = 0 .. n_frames - 2, = number of positions p with grey(frame f, p) ==
+   grey(frame f + 1, p), grey = (R + G + B) / 3 in integers (bits >= 24 ignored).  d_counts is overwritten; any n_pixels >= 1.
+   Each frame is read once.  The ratio count / (f32)n_pixels and its comparison with the leniency stay with the caller. */
+int agmv_hip_similarity_dev(agmv_hip_ctx* ctx, const uint32_t* d_pix, uint32_t n_frames, size_t n_pixels,
+                            uint32_t* d_counts, void* stream);
+/* d_dst[f][k] = d_index[k] == 0xFFFFFFFF ? 0 : d_src[f][d_index[k]] for f < n_frames, k < n_out; source frames are
+   src_frame_pixels apart, an index >= src_frame_pixels reads as 0xFFFFFFFF.  The GBA / NDS nearest scale of the sequence
+   encoder, with the table built on the host. */
+int agmv_hip_gather_dev(agmv_hip_ctx* ctx, const uint32_t* d_src, size_t src_frame_pixels, uint32_t n_frames,
+                        const uint32_t* d_index, size_t n_out, uint32_t* d_dst, void* stream);
 
 /* optional timing: when enabled the library records HIP events on the caller's stream around its three kernel
    groups; agmv_hip_last_kernel_ms(which) returns the last launch's duration in ms (0 = k_encode, 1 = the parser

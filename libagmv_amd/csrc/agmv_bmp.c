@@ -122,17 +122,19 @@ int agmv_bmp_save(const char* path, const uint32_t* pix, uint32_t W, uint32_t H)
 	return NO_ERR;
 }
 
-/* new size = (u32)(w*sx) x (u32)(h*sy) in float; source pixel = (u32)(x * (float)(w-1)/nw) */
-uint32_t* agmv_scale_nearest(const uint32_t* pix, uint32_t w, uint32_t h, float sx, float sy, uint32_t* nw, uint32_t* nh)
+/* new size = (u32)(w*sx) x (u32)(h*sy) in float; source pixel = (u32)(x * (float)(w-1)/nw).  The scale as a table: the
+   source position of every pixel of the new image, AGMV_NO_SOURCE where the scaler writes 0.  The one statement of these
+   expressions: the BMP source and the device gather of the sequence encoder both go through it (agmv_source_index). */
+uint32_t* agmv_scale_nearest_index(uint32_t w, uint32_t h, float sx, float sy, uint32_t* nw, uint32_t* nh)
 {
 	uint32_t W2 = (uint32_t)(w * sx), H2 = (uint32_t)(h * sy), x, y;
 	float xs = (float)(w - 1) / W2, ys = (float)(h - 1) / H2;
-	uint32_t* out = (uint32_t*)malloc((size_t)W2 * H2 * sizeof(uint32_t));
-	for (y = 0; y < H2; y++)
+	uint32_t* idx = (uint32_t*)malloc(((size_t)W2 * H2 + 1) * sizeof(uint32_t));
+	for (y = 0; idx && y < H2; y++)
 		for (x = 0; x < W2; x++) {
 			uint32_t x2 = (uint32_t)(x * xs), y2 = (uint32_t)(y * ys);
-			out[(size_t)y * W2 + x] = (x2 < w && y2 < h) ? pix[(size_t)y2 * w + x2] : 0;
+			idx[(size_t)y * W2 + x] = (x2 < w && y2 < h) ? (uint32_t)((size_t)y2 * w + x2) : AGMV_NO_SOURCE;
 		}
 	*nw = W2; *nh = H2;
-	return out;
+	return idx;
 }

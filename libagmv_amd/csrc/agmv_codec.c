@@ -433,24 +433,31 @@ void AGMV_AssemblePFrameBitstream(AGMV* a, AGMV_ENTRY* e) { assemble_via_gpu(a, 
  * ------------------------------------------------------------------------------------------ */
 static int is_gba(AGMV_OPT o) { return o == AGMV_OPT_GBA_I || o == AGMV_OPT_GBA_II || o == AGMV_OPT_GBA_III; }
 
-static agmv_seq* seq_open(AGMV* a, FILE* file, const char* dir, const char* base, AGMV_OPT opt, int audio_chunks, int use_interp)
+/* the size the GBA / NDS opts scale every source frame to (0: the opt encodes the frames as they are) */
+static void scaled_size(AGMV_OPT opt, int* sw, int* sh)
+{
+	*sw = *sh = 0;
+	if (is_gba(opt)) { *sw = AGMV_GBA_W; *sh = AGMV_GBA_H; }
+	if (opt == AGMV_OPT_NDS) { *sw = AGMV_NDS_W; *sh = AGMV_NDS_H; }
+}
+
+static agmv_seq* seq_open(AGMV* a, FILE* file, const agmv_source* src, AGMV_OPT opt, int audio_chunks, int use_interp)
 {
 	uint32_t pal[512];
-	int i, sw = 0, sh = 0;
+	int i, sw, sh;
 	const int m512 = mode512_of(opt);
-	if (is_gba(opt)) { sw = AGMV_GBA_W; sh = AGMV_GBA_H; }
-	if (opt == AGMV_OPT_NDS) { sw = AGMV_NDS_W; sh = AGMV_NDS_H; }
+	scaled_size(opt, &sw, &sh);
 	for (i = 0; i < 256; i++) { pal[i] = (uint32_t)a->header.palette0[i]; pal[256 + i] = m512 ? (uint32_t)a->header.palette1[i] : 0; }
-	return agmv_seq_open(a, file, dir, base, sw, sh, m512, AGMV_GetCompression(a) != AGMV_LZSS_COMPRESSION, audio_chunks, use_interp,
+	return agmv_seq_open(a, file, src, sw, sh, m512, AGMV_GetCompression(a) != AGMV_LZSS_COMPRESSION, audio_chunks, use_interp,
 	                     batch_frames((size_t)AGMV_GetWidth(a) * AGMV_GetHeight(a)), devices(), lz_threads(), pal);
 }
 
 /* pass 1 of the palette build on the GPU (histogram), pick on the host */
-static void build_palette_from_frames(const char* dir, const char* base, u32 start, u32 end, u32 size, AGMV_QUALITY quality,
+static void build_palette_from_frames(const agmv_source* src, u32 start, u32 end, u32 size, AGMV_QUALITY quality,
                                       AGMV_OPT opt, u32* p0, u32* p1)
 {
 	uint32_t* hist = (uint32_t*)malloc(4u << 19);
-	agmv_histogram_frames(ctx(), dir, base, start, end, size, (int)quality, lz_threads(), hist);
+	agmv_histogram_frames(ctx(), src, start, end, size, (int)quality, lz_threads(), hist);
 	AGMV_BuildPalette(hist, quality, opt, p0, p1);
 	free(hist);
 }
@@ -481,8 +488,9 @@ static int heavy_pdifs(AGMV_OPT o) { return o == AGMV_OPT_I || o == AGMV_OPT_ANI
 
 static void resize_for_target(AGMV* a, AGMV_OPT opt)
 {
-	if (is_gba(opt)) { AGMV_SetWidth(a, AGMV_GBA_W); AGMV_SetHeight(a, AGMV_GBA_H); }
-	if (opt == AGMV_OPT_NDS) { AGMV_SetWidth(a, AGMV_NDS_W); AGMV_SetHeight(a, AGMV_NDS_H); }
+	int sw, sh;
+	scaled_size(opt, &sw, &sh);
+	if (sw) { AGMV_SetWidth(a, (u32)sw); AGMV_SetHeight(a, (u32)sh); }
 }
 
 static void require_bmp(u8 img_type)
@@ -493,29 +501,100 @@ static void require_bmp(u8 img_type)
 	}
 }
 
-/* reference src/agmv_encode.c:2270-3657 (BMP branch) */
-void AGMV_EncodeAGMV(AGMV* a, const char* filename, const char* dir, const char* basename, u8 img_type, u32 start_frame,
-                     u32 end_frame, u32 width, u32 height, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
-                     AGMV_COMPRESSION compression)
+/* "is the pair of source frames (x, x + 1) similar", the decision behind AGMV_EncodeVideo's frame skipping: the grey-equality
+   ratio of the two frames as the encoder sees them against the leniency (reference src/agmv_encode.c:744-790, :920-947).
+   The two sources differ only in where the count comes from. */
+typedef struct similarity {
+	f32 leniency;
+	uint32_t w, h;                         /* of the frames the encoder sees */
+	/* BMP source: the two frames are loaded and compared on the calling thread, per decision */
+	const agmv_source* src;
+	int scale_w, scale_h;
+	u32 *fa, *fb;
+	uint32_t* tmp;
+	/* device source: counts[x - first] of every adjacent pair, from one agmv_hip_similarity_dev launch over the clip */
+	uint32_t* counts;
+} similarity;
+
+static void similarity_open(similarity* m, const agmv_source* src, AGMV* a, AGMV_OPT opt)
+{
+	const size_t npx = (size_t)AGMV_GetWidth(a) * AGMV_GetHeight(a);
+	memset(m, 0, sizeof(*m));
+	m->leniency = AGMV_GetLeniency(a); m->src = src; m->w = (uint32_t)AGMV_GetWidth(a); m->h = (uint32_t)AGMV_GetHeight(a);
+	scaled_size(opt, &m->scale_w, &m->scale_h);
+	if (!src->d_frames) {
+		m->fa = (u32*)malloc(npx * sizeof(u32)); m->fb = (u32*)malloc(npx * sizeof(u32)); m->tmp = (uint32_t*)malloc(npx * 4);
+		return;
+	}
+	{	/* the whole clip at once; with a scale, of the scaled frames (the same gather the workers run) */
+		agmv_hip_ctx* c = ctx();
+		const uint32_t n = src->n_frames;
+		const uint32_t* d_clip = src->d_frames;
+		uint32_t *d_scaled = NULL, *d_index = NULL, *d_counts = (uint32_t*)agmv_hip_malloc_on(c, 4 * (size_t)n);
+		m->counts = (uint32_t*)calloc(n, 4);
+		if (!d_counts || !m->counts) agmv_die("device allocation");
+		if (m->scale_w) {
+			uint32_t* index = agmv_source_index(src->src_w, src->src_h, m->scale_w, m->scale_h, m->w, m->h);
+			d_index = (uint32_t*)agmv_hip_malloc_on(c, npx * 4);
+			d_scaled = (uint32_t*)agmv_hip_malloc_on(c, npx * 4 * n);
+			if (!d_index || !d_scaled || agmv_hip_memcpy_async(c, d_index, index, npx * 4, 0, NULL) ||
+			    agmv_hip_gather_dev(c, src->d_frames, (size_t)src->src_w * src->src_h, n, d_index, npx, d_scaled, NULL))
+				agmv_die("frame gather");
+			d_clip = d_scaled;
+			m->tmp = index;                                    /* (freed by similarity_close, behind the synchronisation below) */
+		}
+		if (agmv_hip_similarity_dev(c, d_clip, n, npx, d_counts, NULL) ||
+		    (n > 1 && agmv_hip_memcpy_async(c, m->counts, d_counts, 4 * (size_t)(n - 1), 1, NULL)) || agmv_hip_stream_sync(c, NULL))
+			agmv_die("frame similarity");
+		agmv_hip_free_on(c, d_counts); agmv_hip_free_on(c, d_scaled); agmv_hip_free_on(c, d_index);
+	}
+}
+
+static int similar(similarity* m, long x)
+{
+	const size_t npx = (size_t)m->w * m->h;
+	size_t k;
+	if (m->counts) return m->counts[x - m->src->first] / (f32)npx >= m->leniency;
+	agmv_load_source(m->src->dir, m->src->base, x, m->scale_w, m->scale_h, m->w, m->h, m->tmp); for (k = 0; k < npx; k++) m->fa[k] = m->tmp[k];
+	agmv_load_source(m->src->dir, m->src->base, x + 1, m->scale_w, m->scale_h, m->w, m->h, m->tmp); for (k = 0; k < npx; k++) m->fb[k] = m->tmp[k];
+	return AGMV_CompareFrameSimilarity(m->fa, m->fb, m->w, m->h) >= m->leniency;
+}
+
+static void similarity_close(similarity* m) { free(m->fa); free(m->fb); free(m->tmp); free(m->counts); }
+
+/* The three sequence encoders of the reference (src/agmv_encode.c:2270-3657 AGMV_EncodeAGMV = AGMV_SCHEDULE_PDIFS, :3659-4407
+   AGMV_EncodeFullAGMV = AGMV_SCHEDULE_FULL, :719-2268 AGMV_EncodeVideo = AGMV_SCHEDULE_ADAPTIVE; BMP branch) over one body:
+   they differ in which frames they push and in how they patch the header afterwards.  `src` says where the frames start_frame
+   .. end_frame are: BMP files, or device memory (AGMV_EncodeFramesDev).  Frees `a`, like the reference's drivers. */
+static void encode_sequence(AGMV* a, const char* filename, const agmv_source* src, AGMV_SCHEDULE schedule, u32 start_frame,
+                            u32 end_frame, u32 width, u32 height, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression)
 {
 	u32 p0[256], p1[256], adjusted = end_frame - start_frame, i;
 	FILE* file;
 	agmv_seq* s;
 	u32 written;
-	f32 rate;
-	(void)frames_per_second;
-	require_bmp(img_type);
 	AGMV_SetOPT(a, opt);
 	AGMV_SetCompression(a, compression);
-	AGMV_SetLeniency(a, 0);
-	/* :2296-2353: integer halves for the heavy modes, x0.75 in double (float for GBA_III) for the light ones */
-	if (heavy_pdifs(opt)) adjusted /= 2;
-	else if (opt == AGMV_OPT_GBA_III) adjusted = (u32)(adjusted * 0.75f);
-	else adjusted = (u32)(adjusted * 0.75);
+	if (schedule == AGMV_SCHEDULE_PDIFS) {
+		AGMV_SetLeniency(a, 0);
+		/* :2296-2353: integer halves for the heavy modes, x0.75 in double (float for GBA_III) for the light ones */
+		if (heavy_pdifs(opt)) adjusted /= 2;
+		else if (opt == AGMV_OPT_GBA_III) adjusted = (u32)(adjusted * 0.75f);
+		else adjusted = (u32)(adjusted * 0.75);
+	} else if (schedule == AGMV_SCHEDULE_ADAPTIVE) {
+		f32 len;
+		switch (opt) {                                        /* :744-790 */
+		case AGMV_OPT_II: len = 0.1282f; break;
+		case AGMV_OPT_GBA_I: case AGMV_OPT_GBA_II: case AGMV_OPT_GBA_III: case AGMV_OPT_NDS: len = 0.0f; break;
+		default: len = 0.2282f; break;
+		}
+		AGMV_SetLeniency(a, len);
+	}
 	resize_for_target(a, opt);
 
-	build_palette_from_frames(dir, basename, start_frame, end_frame, width * height, quality, opt, p0, p1);
-	if (a->audio_chunk) a->audio_chunk->size = (u32)(a->header.audio_size / (f32)adjusted);   /* 0 without an audio track */
+	build_palette_from_frames(src, start_frame, end_frame, width * height, quality, opt, p0, p1);
+	if (schedule == AGMV_SCHEDULE_PDIFS && a->audio_chunk) a->audio_chunk->size = (u32)(a->header.audio_size / (f32)adjusted);   /* 0 without an audio track */
+	if (schedule == AGMV_SCHEDULE_FULL && a->audio_chunk) a->audio_chunk->size = (u32)(a->header.audio_size / (f32)AGMV_GetNumberOfFrames(a));
 
 	file = fopen(filename, "wb");
 	if (!file) { fprintf(stderr, "libagmv(amd): cannot create %s\n", filename); abort(); }
@@ -523,114 +602,101 @@ void AGMV_EncodeAGMV(AGMV* a, const char* filename, const char* dir, const char*
 	AGMV_SetICP1(a, p1);
 	AGMV_EncodeHeader(file, a);
 
-	s = seq_open(a, file, dir, basename, opt, 1, 1);
-	for (i = start_frame; i <= end_frame;) {                  /* :2678, :3610-3612 */
-		/* NDS is "light" only for BMP input (:2727 vs :2810) -- BMP is the only input here */
-		if (!heavy_pdifs(opt)) { agmv_seq_push(s, i, -1); agmv_seq_push(s, i + 1, i + 2); agmv_seq_push(s, i + 3, -1); i += 4; }
-		else { agmv_seq_push(s, i, i + 1); i += 2; }
-		if (i + 4 >= end_frame) break;
-	}
-	written = agmv_seq_close(s);
+	if (schedule == AGMV_SCHEDULE_FULL) {                     /* every input frame, no PDIFS, no header patch */
+		s = seq_open(a, file, src, opt, AGMV_GetTotalAudioDuration(a) != 0, 0);
+		for (i = start_frame; i <= end_frame; i++) agmv_seq_push(s, i, -1);
+		(void)agmv_seq_close(s);
+	} else {
+		/* :2678, :3610-3612 and :719-2268: a PDIFS group per step, or -- AGMV_EncodeVideo, where the pair that decides (the two
+		   middle frames of a light group, the two frames of a heavy one) is not similar -- the one frame alone.
+		   NDS is "light" only for BMP input (:2727 vs :2810), and the frames of both sources are what BMP input gives */
+		similarity m;
+		f32 rate;
+		s = seq_open(a, file, src, opt, schedule == AGMV_SCHEDULE_PDIFS, 1);
+		if (schedule == AGMV_SCHEDULE_ADAPTIVE) similarity_open(&m, src, a, opt);
+		for (i = start_frame; i <= end_frame;) {
+			if (schedule == AGMV_SCHEDULE_ADAPTIVE && !similar(&m, heavy_pdifs(opt) ? (long)i : (long)i + 1)) { agmv_seq_push(s, i, -1); i += 1; }
+			else if (!heavy_pdifs(opt)) { agmv_seq_push(s, i, -1); agmv_seq_push(s, i + 1, i + 2); agmv_seq_push(s, i + 3, -1); i += 4; }
+			else { agmv_seq_push(s, i, i + 1); i += 2; }
+			if (i + 4 >= end_frame) break;
+		}
+		if (schedule == AGMV_SCHEDULE_ADAPTIVE) similarity_close(&m);
+		written = agmv_seq_close(s);
 
-	fseek(file, 4, SEEK_SET);                                 /* :3615-3620 */
-	AGMV_WriteLong(file, written);
-	fseek(file, 18, SEEK_SET);
-	rate = (f32)adjusted / (AGMV_GetNumberOfFrames(a) + 1);
-	AGMV_WriteLong(file, (u32)round(AGMV_GetFramesPerSecond(a) * rate));
+		fseek(file, 4, SEEK_SET);                             /* :3615-3620, :2225-2231 */
+		AGMV_WriteLong(file, written);
+		fseek(file, 18, SEEK_SET);
+		rate = schedule == AGMV_SCHEDULE_PDIFS ? (f32)adjusted / (AGMV_GetNumberOfFrames(a) + 1) : (f32)written / AGMV_GetNumberOfFrames(a);
+		AGMV_WriteLong(file, (u32)round(AGMV_GetFramesPerSecond(a) * rate));
+	}
 	fclose(file);
 	DestroyAGMV(a);                                           /* the callee frees the caller's object, :3625 */
-	if (is_gba(opt)) dump_gba_header(filename);
+	if (is_gba(opt) && !src->d_frames) dump_gba_header(filename);
 }
 
-/* reference src/agmv_encode.c:3659-4407 (BMP branch): every input frame, no PDIFS, no header patch */
+static agmv_source bmp_source(const char* dir, const char* basename, u8 img_type)
+{
+	agmv_source src;
+	require_bmp(img_type);
+	memset(&src, 0, sizeof(src));
+	src.dir = dir; src.base = basename;
+	return src;
+}
+
+void AGMV_EncodeAGMV(AGMV* a, const char* filename, const char* dir, const char* basename, u8 img_type, u32 start_frame,
+                     u32 end_frame, u32 width, u32 height, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
+                     AGMV_COMPRESSION compression)
+{
+	const agmv_source src = bmp_source(dir, basename, img_type);
+	(void)frames_per_second;
+	encode_sequence(a, filename, &src, AGMV_SCHEDULE_PDIFS, start_frame, end_frame, width, height, opt, quality, compression);
+}
+
 void AGMV_EncodeFullAGMV(AGMV* a, const char* filename, const char* dir, const char* basename, u8 img_type, u32 start_frame,
                          u32 end_frame, u32 width, u32 height, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
                          AGMV_COMPRESSION compression)
 {
-	u32 p0[256], p1[256], i;
-	FILE* file;
-	agmv_seq* s;
+	const agmv_source src = bmp_source(dir, basename, img_type);
 	(void)frames_per_second;
-	require_bmp(img_type);
-	AGMV_SetOPT(a, opt);
-	AGMV_SetCompression(a, compression);
-	resize_for_target(a, opt);
-	build_palette_from_frames(dir, basename, start_frame, end_frame, width * height, quality, opt, p0, p1);
-	if (a->audio_chunk) a->audio_chunk->size = (u32)(a->header.audio_size / (f32)AGMV_GetNumberOfFrames(a));
-	file = fopen(filename, "wb");
-	if (!file) { fprintf(stderr, "libagmv(amd): cannot create %s\n", filename); abort(); }
-	AGMV_SetICP0(a, p0);
-	AGMV_SetICP1(a, p1);
-	AGMV_EncodeHeader(file, a);
-	s = seq_open(a, file, dir, basename, opt, AGMV_GetTotalAudioDuration(a) != 0, 0);
-	for (i = start_frame; i <= end_frame; i++) agmv_seq_push(s, i, -1);
-	(void)agmv_seq_close(s);
-	fclose(file);
-	DestroyAGMV(a);
-	if (is_gba(opt)) dump_gba_header(filename);
+	encode_sequence(a, filename, &src, AGMV_SCHEDULE_FULL, start_frame, end_frame, width, height, opt, quality, compression);
 }
 
-/* reference src/agmv_encode.c:719-2268 (BMP branch): frame skipping decided per group by the grey-equality
-   ratio of the two middle (light) / first two (heavy) frames against the leniency */
 void AGMV_EncodeVideo(const char* filename, const char* dir, const char* basename, u8 img_type, u32 start_frame, u32 end_frame,
                       u32 width, u32 height, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression)
 {
-	AGMV* a = CreateAGMV(end_frame - start_frame, width, height, frames_per_second);
-	u32 p0[256], p1[256], i;
-	FILE* file;
-	agmv_seq* s;
-	u32 written;
-	int sw = 0, sh = 0;
-	uint32_t ew, eh;
-	f32 rate, len;
-	size_t npx;
-	u32 *fa, *fb;
-	uint32_t* tmp;
-	require_bmp(img_type);
-	AGMV_SetOPT(a, opt);
-	AGMV_SetCompression(a, compression);
-	switch (opt) {                                            /* :744-790 */
-	case AGMV_OPT_II: len = 0.1282f; break;
-	case AGMV_OPT_GBA_I: case AGMV_OPT_GBA_II: case AGMV_OPT_GBA_III: case AGMV_OPT_NDS: len = 0.0f; break;
-	default: len = 0.2282f; break;
-	}
-	AGMV_SetLeniency(a, len);
-	resize_for_target(a, opt);
-	build_palette_from_frames(dir, basename, start_frame, end_frame, width * height, quality, opt, p0, p1);
-	file = fopen(filename, "wb");
-	if (!file) { fprintf(stderr, "libagmv(amd): cannot create %s\n", filename); abort(); }
-	AGMV_SetICP0(a, p0);
-	AGMV_SetICP1(a, p1);
-	AGMV_EncodeHeader(file, a);
-	s = seq_open(a, file, dir, basename, opt, 0, 1);
-	if (is_gba(opt)) { sw = AGMV_GBA_W; sh = AGMV_GBA_H; }
-	if (opt == AGMV_OPT_NDS) { sw = AGMV_NDS_W; sh = AGMV_NDS_H; }
-	ew = (uint32_t)AGMV_GetWidth(a); eh = (uint32_t)AGMV_GetHeight(a);
-	npx = (size_t)ew * eh;
-	fa = (u32*)malloc(npx * sizeof(u32)); fb = (u32*)malloc(npx * sizeof(u32)); tmp = (uint32_t*)malloc(npx * 4);
-	for (i = start_frame; i <= end_frame;) {
-		long x = heavy_pdifs(opt) ? (long)i : (long)i + 1;   /* pair whose similarity decides */
-		size_t k;
-		f32 ratio;
-		agmv_load_source(dir, basename, x, sw, sh, ew, eh, tmp); for (k = 0; k < npx; k++) fa[k] = tmp[k];
-		agmv_load_source(dir, basename, x + 1, sw, sh, ew, eh, tmp); for (k = 0; k < npx; k++) fb[k] = tmp[k];
-		ratio = AGMV_CompareFrameSimilarity(fa, fb, ew, eh);
-		if (ratio >= AGMV_GetLeniency(a)) {
-			if (!heavy_pdifs(opt)) { agmv_seq_push(s, i, -1); agmv_seq_push(s, i + 1, i + 2); agmv_seq_push(s, i + 3, -1); i += 4; }
-			else { agmv_seq_push(s, i, i + 1); i += 2; }
-		} else { agmv_seq_push(s, i, -1); i += 1; }
-		if (i + 4 >= end_frame) break;
-	}
-	written = agmv_seq_close(s);
-	free(fa); free(fb); free(tmp);
-	fseek(file, 4, SEEK_SET);                                 /* :2225-2231 */
-	AGMV_WriteLong(file, written);
-	fseek(file, 18, SEEK_SET);
-	rate = (f32)written / AGMV_GetNumberOfFrames(a);
-	AGMV_WriteLong(file, (u32)round(AGMV_GetFramesPerSecond(a) * rate));
-	fclose(file);
-	DestroyAGMV(a);
-	if (is_gba(opt)) dump_gba_header(filename);
+	const agmv_source src = bmp_source(dir, basename, img_type);
+	encode_sequence(CreateAGMV(end_frame - start_frame, width, height, frames_per_second), filename, &src, AGMV_SCHEDULE_ADAPTIVE,
+	                start_frame, end_frame, width, height, opt, quality, compression);
+}
+
+/* The same three files from frames in device memory: d_frames[num_of_frames][height][width], 0x00RRGGBB, on the device of
+   this library's context.  What the BMP drivers write for f1.bmp .. f<n>.bmp holding these frames, byte for byte (for
+   AGMV_SCHEDULE_ADAPTIVE with AGMV_EncodeVideo's CreateAGMV(n - 1, ...)); GBA_GEN_AGMV.h is not written.  Returns 0, or a
+   negative value -- before any file is created -- for arguments that cannot be encoded. */
+int AGMV_EncodeFramesDev(const char* filename, const unsigned* d_frames, u32 num_of_frames, u32 width, u32 height,
+                         u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+{
+	agmv_source src;
+	int sw, sh;
+	u32 least;
+	if (!filename || !d_frames) return -1;
+	if (opt < AGMV_OPT_I || opt > AGMV_OPT_NDS || quality < AGMV_HIGH_QUALITY || quality > AGMV_LOW_QUALITY ||
+	    (compression != AGMV_LZSS_COMPRESSION && compression != AGMV_LZ77_COMPRESSION) ||
+	    (schedule != AGMV_SCHEDULE_FULL && schedule != AGMV_SCHEDULE_PDIFS && schedule != AGMV_SCHEDULE_ADAPTIVE))
+		return -1;
+	/* the first group of the schedule reads this many frames whatever the length of the clip */
+	least = schedule == AGMV_SCHEDULE_FULL ? 1 : (heavy_pdifs(opt) ? 2 : 4);
+	if (num_of_frames < least || num_of_frames > 0x7FFFFFFFul) return -2;
+	scaled_size(opt, &sw, &sh);
+	if (width == 0 || height == 0 || (unsigned long long)width * height > (1ull << 28)) return -3;
+	if (!sw && bad_geometry((uint32_t)width, (uint32_t)height)) return -3;
+	if (sw && (width < 2 || height < 2)) return -3;
+	memset(&src, 0, sizeof(src));
+	src.d_frames = (const uint32_t*)d_frames; src.src_w = (uint32_t)width; src.src_h = (uint32_t)height;
+	src.n_frames = (uint32_t)num_of_frames; src.first = 1; src.device = agmv_hip_ctx_device(ctx());
+	encode_sequence(CreateAGMV(schedule == AGMV_SCHEDULE_ADAPTIVE ? num_of_frames - 1 : num_of_frames, width, height, frames_per_second),
+	                filename, &src, schedule, 1, num_of_frames, width, height, opt, quality, compression);
+	return 0;
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -638,14 +704,16 @@ void AGMV_EncodeVideo(const char* filename, const char* dir, const char* basenam
  * frame by frame into ONE persistent buffer (so the stale-tail semantics hold), the GPU parses and
  * reconstructs whole batches, frames are exported as quick_export_<n>.bmp in the CWD.
  * ------------------------------------------------------------------------------------------ */
-static int decode_file(const char* filename, u8 img_type)
+/* d_dst NULL: AGMV_DecodeAGMV / AGMV_DecodeVideo, every frame to its BMP.  Else AGMV_DecodeFramesDev: up to cap_frames frames
+   into d_dst, their number into *decoded.  *info (may be NULL) = the header's; with info_only nothing else happens. */
+static int decode_file(const char* filename, u8 img_type, uint32_t* d_dst, u32 cap_frames, int info_only, AGMV_INFO* info, unsigned long* decoded)
 {
 	FILE* f = fopen(filename, "rb");
 	AGMV hdr_obj;
 	u8* file;
 	long flen;
 	size_t pos, got, npx;
-	uint32_t w, h;
+	uint32_t w, h, nframes;
 	unsigned cap;
 	int err, m512;
 	agmv_hip_ctx* c;
@@ -656,6 +724,8 @@ static int decode_file(const char* filename, u8 img_type)
 	memset(&hdr_obj, 0, sizeof(hdr_obj.header));
 	err = AGMV_DecodeHeader(f, &hdr_obj);
 	if (err != NO_ERR) { fclose(f); return err; }
+	if (info) *info = AGMV_GetVideoInfo(&hdr_obj);
+	if (info_only) { fclose(f); return NO_ERR; }
 	pos = (size_t)ftell(f);
 	fseek(f, 0, SEEK_END); flen = ftell(f); fseek(f, 0, SEEK_SET);
 	file = (u8*)malloc((size_t)flen + 16);
@@ -677,20 +747,32 @@ static int decode_file(const char* filename, u8 img_type)
 		g_pal_mode = m512;
 	}
 	cap = batch_frames(npx);
-	err = agmv_decode_stream(c, file, got, pos, w, h, (uint32_t)hdr_obj.header.num_of_frames, hdr_obj.header.version,
-	                         hdr_obj.header.total_audio_duration != 0, cap, lz_threads(), &g_export_count);
+	nframes = (uint32_t)hdr_obj.header.num_of_frames;
+	if (d_dst && nframes > cap_frames) nframes = (uint32_t)cap_frames;
+	err = agmv_decode_stream(c, file, got, pos, w, h, nframes, hdr_obj.header.version, hdr_obj.header.total_audio_duration != 0, cap,
+	                         lz_threads(), d_dst, d_dst ? decoded : &g_export_count);
 	free(file);
 	return err;
 }
 
-int AGMV_DecodeVideo(const char* filename, u8 img_type) { return decode_file(filename, img_type); }
+int AGMV_DecodeVideo(const char* filename, u8 img_type) { return decode_file(filename, img_type, NULL, 0, 0, NULL, NULL); }
+
+/* AGMV_DecodeAGMV with another destination: frame k of the file (0-based) at d_frames + k * width * height (4-byte 0x00RRGGBB,
+   device memory of this library's context) instead of in quick_export_<k + 1>.bmp.  At most cap_frames frames; returns the
+   number decoded or a negative Error.  With d_frames NULL nothing is decoded and only *info is filled. */
+int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frames, AGMV_INFO* info)
+{
+	unsigned long decoded = 0;
+	const int err = filename ? decode_file(filename, AGMV_IMG_BMP, (uint32_t*)d_frames, cap_frames, d_frames == NULL, info, &decoded) : FILE_NOT_FOUND_ERR;
+	return err == NO_ERR ? (int)decoded : -err;
+}
 
 /* audio export (quick_export.wav / .aiff) is out of scope of this build; the video frames are exported
    exactly like the reference does */
 int AGMV_DecodeAGMV(const char* filename, u8 img_type, AGMV_AUDIO_TYPE audio_type)
 {
 	(void)audio_type;
-	return decode_file(filename, img_type);
+	return decode_file(filename, img_type, NULL, 0, 0, NULL, NULL);
 }
 
 /* ------------------------------------------------------------------------------------------

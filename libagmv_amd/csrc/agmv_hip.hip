@@ -2381,6 +2381,85 @@ __global__ __launch_bounds__(256) void k_histogram(const uint32_t* __restrict__ 
 	}
 }
 
+// The grey-equality count behind AGMV_EncodeVideo's frame skipping, AGMV_CompareFrameSimilarity (src/agmv_utils.c:920-947):
+// counts[f] = number of positions at which frames f and f + 1 have the same grey, grey = (R + G + B) / 3 in integers (equal to
+// the reference's (u8)((r + g + b) / 3.0f) for all 766 sums).  A streaming reduction: a lane owns 8 pixel positions (two
+// 16-byte loads per frame, each coalesced over the wave) and walks them through ALL frames, keeping the greys of the frame
+// before in two registers, so every frame is read once per launch, not once per pair.  The loads of frame f + 1 are issued
+// before frame f is compared.  Per pair the lane's count goes through the wave (__shfl_xor), then one LDS atomic per wave into
+// the block's slot of the pair, and the block flushes its slots with one global atomic per pair every SIM_SEG pairs.
+#define SIM_SEG 1024
+
+__device__ __forceinline__ uint32_t sim_greys(uint4 v)        // the greys of 4 pixels, one per byte; bits >= 24 are ignored
+{
+	const uint32_t a = (((v.x >> 16) & 0xff) + ((v.x >> 8) & 0xff) + (v.x & 0xff)) / 3u;
+	const uint32_t b = (((v.y >> 16) & 0xff) + ((v.y >> 8) & 0xff) + (v.y & 0xff)) / 3u;
+	const uint32_t c = (((v.z >> 16) & 0xff) + ((v.z >> 8) & 0xff) + (v.z & 0xff)) / 3u;
+	const uint32_t d = (((v.w >> 16) & 0xff) + ((v.w >> 8) & 0xff) + (v.w & 0xff)) / 3u;
+	return a | b << 8 | c << 16 | d << 24;
+}
+
+__device__ __forceinline__ uint32_t sim_equal_bytes(uint32_t a, uint32_t b)
+{
+	const uint32_t x = a ^ b;
+	return ((x & 0xffu) == 0) + ((x & 0xff00u) == 0) + ((x & 0xff0000u) == 0) + ((x & 0xff000000u) == 0);
+}
+
+// pixels p .. p + 3 of a frame of npx pixels, 0 where there is none.  vec: npx % 4 == 0 and the clip is 16-byte aligned, so
+// every frame is, and p < npx implies p + 3 < npx
+__device__ __forceinline__ uint4 sim_load(const uint32_t* __restrict__ fr, size_t p, size_t npx, bool vec)
+{
+	if (vec) return p < npx ? *reinterpret_cast<const uint4*>(fr + p) : make_uint4(0, 0, 0, 0);
+	uint4 v;
+	v.x = p < npx ? fr[p] : 0; v.y = p + 1 < npx ? fr[p + 1] : 0; v.z = p + 2 < npx ? fr[p + 2] : 0; v.w = p + 3 < npx ? fr[p + 3] : 0;
+	return v;
+}
+
+__global__ __launch_bounds__(256) void k_similarity(const uint32_t* __restrict__ pix, uint32_t n_frames, size_t npx, int vec,
+                                                    uint32_t* __restrict__ counts)
+{
+	__shared__ uint32_t s_cnt[SIM_SEG];
+	const size_t pa = ((size_t)blockIdx.x * 512 + threadIdx.x) * 4, pb = pa + 1024;
+	// positions of this lane behind the frame's end read as 0 in every frame: they always compare equal and are taken off again
+	const uint32_t dead = (uint32_t)(pa >= npx ? 4 : (pa + 4 > npx ? pa + 4 - npx : 0)) + (uint32_t)(pb >= npx ? 4 : (pb + 4 > npx ? pb + 4 - npx : 0));
+	const uint32_t n_pairs = n_frames - 1;
+	uint32_t ga = sim_greys(sim_load(pix, pa, npx, vec)), gb = sim_greys(sim_load(pix, pb, npx, vec));
+	uint4 na = sim_load(pix + npx, pa, npx, vec), nb = sim_load(pix + npx, pb, npx, vec);
+	for (uint32_t seg = 0; seg < n_pairs; seg += SIM_SEG) {
+		const uint32_t n_seg = n_pairs - seg < SIM_SEG ? n_pairs - seg : SIM_SEG;
+		for (uint32_t k = threadIdx.x; k < n_seg; k += 256) s_cnt[k] = 0;
+		__syncthreads();
+		for (uint32_t k = 0; k < n_seg; k++) {
+			const uint32_t f = seg + k + 1;                    // the later frame of pair seg + k: its pixels are in na, nb
+			const uint4 ca = na, cb = nb;
+			if (f + 1 < n_frames) {
+				const uint32_t* nx = pix + (size_t)(f + 1) * npx;
+				na = sim_load(nx, pa, npx, vec); nb = sim_load(nx, pb, npx, vec);
+			}
+			const uint32_t ha = sim_greys(ca), hb = sim_greys(cb);
+			uint32_t c = sim_equal_bytes(ga, ha) + sim_equal_bytes(gb, hb) - dead;
+			ga = ha; gb = hb;
+			for (int d = 32; d; d >>= 1) c += __shfl_xor(c, d, 64);
+			if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt[k], c);
+		}
+		__syncthreads();
+		for (uint32_t k = threadIdx.x; k < n_seg; k += 256) if (s_cnt[k]) atomicAdd(counts + seg + k, s_cnt[k]);
+		__syncthreads();
+	}
+}
+
+// the GBA / NDS nearest scale as a gather: dst[f][k] = src[f][index[k]], 0 where the table says "no source pixel" (0xFFFFFFFF;
+// an index outside the source frame reads as that too).  The table holds every quirk of the host scaler (agmv_pipeline.c).
+__global__ __launch_bounds__(256) void k_gather(const uint32_t* __restrict__ src, size_t src_px, uint32_t n_frames,
+                                                const uint32_t* __restrict__ index, size_t n_out, uint32_t* __restrict__ dst)
+{
+	const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (k >= n_out) return;
+	const uint32_t i = index[k];
+	const bool live = i != 0xFFFFFFFFu && (size_t)i < src_px;
+	for (uint32_t f = 0; f < n_frames; f++) dst[(size_t)f * n_out + k] = live ? src[(size_t)f * src_px + i] : 0u;
+}
+
 // A spin of k_encode that ran into its bound leaves ctrl[1] != 0 and the kernel carries on with a wrong offset: the bytes of
 // the batch are not to be used.  So that a caller who skips agmv_hip_check cannot take them for good ones, every size of
 // the batch is then overwritten with 0xFFFFFFFF (no frame is that long: agmv_hip_max_usize < 2^32).
@@ -3347,6 +3426,31 @@ extern "C" int agmv_hip_histogram_dev(agmv_hip_ctx* c, const uint32_t* d_pix, si
 	size_t blocks = (n + 255) / 256;
 	if (blocks > 8192) blocks = 8192;
 	hipLaunchKernelGGL(k_histogram, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_pix, n, quality, d_hist);
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_similarity_dev(agmv_hip_ctx* c, const uint32_t* d_pix, uint32_t n_frames, size_t n_pixels, uint32_t* d_counts, void* stream)
+{
+	if (need_ctx(c, false)) return -1;
+	if (n_pixels == 0 || n_pixels > 0xFFFFFFFFu) { snprintf(g_err, sizeof(g_err), "agmv_hip: similarity needs 1 .. 2^32 - 1 pixels per frame"); return -1; }
+	if (n_frames < 2) return 0;                                // no pair
+	const size_t blocks = (n_pixels + 2047) / 2048;            // 256 lanes x 8 pixels
+	CK(hipMemsetAsync(d_counts, 0, 4 * (size_t)(n_frames - 1), (hipStream_t)stream));
+	const int vec = (n_pixels & 3) == 0 && ((uintptr_t)d_pix & 15) == 0;
+	hipLaunchKernelGGL(k_similarity, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_pix, n_frames, n_pixels, vec, d_counts);
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_gather_dev(agmv_hip_ctx* c, const uint32_t* d_src, size_t src_frame_pixels, uint32_t n_frames, const uint32_t* d_index,
+                                   size_t n_out, uint32_t* d_dst, void* stream)
+{
+	if (need_ctx(c, false)) return -1;
+	if (n_frames == 0 || n_out == 0) return 0;
+	if (n_out > ((size_t)1 << 39)) { snprintf(g_err, sizeof(g_err), "agmv_hip: gather table too long"); return -1; }
+	hipLaunchKernelGGL(k_gather, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_src, src_frame_pixels, n_frames,
+	                   d_index, n_out, d_dst);
 	CK(hipGetLastError());
 	return 0;
 }

@@ -20,8 +20,10 @@ int  agmv_bmp_load(const char* path, uint32_t** pix, uint32_t* w, uint32_t* h);
 int  agmv_bmp_load_into(const char* path, uint32_t* dst, size_t max_px, uint32_t* w, uint32_t* h);
 int  agmv_bmp_save(const char* path, const uint32_t* pix, uint32_t w, uint32_t h);
 /* AGIDL_FastScaleBMP(..., AGIDL_SCALE_NEAREST) as the GBA/NDS drivers call it (reference
-   src/agmv_encode.c:2707-2721, extern/agidl/src/agidl_imgp_scale.c:262-291) */
-uint32_t* agmv_scale_nearest(const uint32_t* pix, uint32_t w, uint32_t h, float sx, float sy, uint32_t* nw, uint32_t* nh);
+   src/agmv_encode.c:2707-2721, extern/agidl/src/agidl_imgp_scale.c:262-291), as a table: the source position of every pixel
+   of the nw x nh image, AGMV_NO_SOURCE where the scaler writes 0 */
+#define AGMV_NO_SOURCE 0xFFFFFFFFu
+uint32_t* agmv_scale_nearest_index(uint32_t w, uint32_t h, float sx, float sy, uint32_t* nw, uint32_t* nh);
 
 /* agmv_codec.c */
 void agmv_die(const char* what);

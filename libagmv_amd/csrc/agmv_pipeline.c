@@ -17,6 +17,11 @@
  *            on the device; GPU worker: (H2D ->) parse -> reconstruct -> D2H with the decoder state (last frame, I-frame
  *            snapshot) kept on the device; host cores: BMP export, one task per frame
  *
+ * Both pipelines have a second end for frames that live in GPU memory (AGMV_EncodeFramesDev / AGMV_DecodeFramesDev): a device
+ * SOURCE of the encoder (agmv_source: no BMP parse, no pinned staging, no upload -- the workers copy, gather or interpolate
+ * from the caller's clip) and a device SINK of the decoder (the worker decodes into the caller's buffer: no D2H, no BMP export).
+ * Everything between the two ends is the same code.
+ *
  * Plain C + pthreads; everything that touches the GPU goes through include/agmv_hip.h.  No CPU fallback: a GPU failure in
  * the void encoders aborts with a message, in the int-returning decoders it is returned.
  */
@@ -125,13 +130,30 @@ void agmv_frame_path(char* out, size_t cap, const char* dir, const char* base, l
 	else snprintf(out, cap, "%s%ld.bmp", base, idx);                /* "cur..." = current directory, src/agmv_encode.c:2373-2378 */
 }
 
-/* source frame `idx` as the encoder sees it: BMP -> 0x00RRGGBB, optional GBA/NDS nearest scale, then the first w*h pixels
-   read linearly (the reference reads a 121x81 scaled image as 120x80) */
+/* the GBA/NDS path from a source frame of sw x sh pixels to the w x h frame the encoder sees, as a table of w*h source
+   positions (AGMV_NO_SOURCE: the pixel is 0): the nearest scale to scale_w x scale_h as the reference asks for it, then the
+   first w*h pixels of the scaled image read linearly (the reference reads a 121x81 scaled image as 120x80) and
+   zeros behind a scaled image that is shorter.  Every quirk of the scaled source lives here: the BMP source applies the table
+   on the host, the device source hands it to agmv_hip_gather_dev. */
+uint32_t* agmv_source_index(uint32_t sw, uint32_t sh, int scale_w, int scale_h, uint32_t w, uint32_t h)
+{
+	uint32_t nw, nh;
+	uint32_t* sc = agmv_scale_nearest_index(sw, sh, ((float)scale_w / sw) + 0.001f, ((float)scale_h / sh) + 0.001f, &nw, &nh);
+	const size_t need = (size_t)w * h, have = (size_t)nw * nh;
+	uint32_t* idx = (uint32_t*)xmalloc(need * sizeof(uint32_t));
+	size_t k;
+	if (!sc) agmv_die("out of host memory");
+	for (k = 0; k < need; k++) idx[k] = k < have ? sc[k] : AGMV_NO_SOURCE;
+	free(sc);
+	return idx;
+}
+
+/* source frame `idx` as the encoder sees it: BMP -> 0x00RRGGBB, optional GBA/NDS nearest scale (agmv_source_index) */
 void agmv_load_source(const char* dir, const char* base, long idx, int scale_w, int scale_h, uint32_t w, uint32_t h, uint32_t* dst)
 {
 	char path[4096];
-	uint32_t *pix = NULL, sw = 0, sh = 0;
-	size_t need = (size_t)w * h, have;
+	uint32_t *pix = NULL, *index, sw = 0, sh = 0;
+	size_t need = (size_t)w * h, have, k;
 	agmv_frame_path(path, sizeof(path), dir, base, idx);
 	if (!scale_w) {                                        /* straight into the caller's (pinned) buffer */
 		if (agmv_bmp_load_into(path, dst, need, &sw, &sh) != NO_ERR) die_unreadable(path);
@@ -140,14 +162,9 @@ void agmv_load_source(const char* dir, const char* base, long idx, int scale_w, 
 		return;
 	}
 	if (agmv_bmp_load(path, &pix, &sw, &sh) != NO_ERR) die_unreadable(path);
-	{
-		uint32_t nw, nh;
-		uint32_t* sc = agmv_scale_nearest(pix, sw, sh, ((float)scale_w / sw) + 0.001f, ((float)scale_h / sh) + 0.001f, &nw, &nh);
-		free(pix); pix = sc; sw = nw; sh = nh;
-	}
-	have = (size_t)sw * sh;
-	memcpy(dst, pix, (have < need ? have : need) * 4);
-	if (have < need) memset(dst + have, 0, (need - have) * 4);
+	index = agmv_source_index(sw, sh, scale_w, scale_h, w, h);
+	for (k = 0; k < need; k++) dst[k] = index[k] == AGMV_NO_SOURCE ? 0 : pix[index[k]];
+	free(index);
 	free(pix);
 }
 
@@ -160,7 +177,7 @@ typedef struct ebatch {
 	unsigned id, n;
 	long *srcA, *srcB;                     /* source frame numbers; srcB < 0: plain frame, else PDIFS midpoint of A and B */
 	u32 first_fc;
-	uint32_t* h_pix;                       /* pinned: frame k at [k * per], its second source at [k * per + npx] */
+	uint32_t* h_pix;                       /* BMP source, pinned: frame k at [k * per], its second source at [k * per + npx] */
 	unsigned loads_left, lz_left;
 	int loaded, bits_ready;
 	uint32_t* sizes;                       /* pinned [cap] */
@@ -189,7 +206,8 @@ typedef struct eworker {
 struct agmv_seq {
 	AGMV* a;
 	FILE* file;
-	const char *dir, *base;
+	agmv_source src;
+	uint32_t* d_index;                     /* device source with a scale: the table of agmv_source_index on the device */
 	int scale_w, scale_h, audio_chunks, mode512, lz77, use_b;
 	int lz_dev;                            /* the LZ stage runs on the GPU workers (lz77 chooses the form): AGMV_LZ_DEVICE for LZSS,
 	                                          AGMV_LZ77_DEVICE for LZ77 on one device */
@@ -221,7 +239,7 @@ static void load_task(void* p)
 	agmv_seq* s = la->s;
 	ebatch* b = la->b;
 	const double t0 = now_s();
-	agmv_load_source(s->dir, s->base, la->which ? b->srcB[la->k] : b->srcA[la->k], s->scale_w, s->scale_h, s->w, s->h,
+	agmv_load_source(s->src.dir, s->src.base, la->which ? b->srcB[la->k] : b->srcA[la->k], s->scale_w, s->scale_h, s->w, s->h,
 	                 b->h_pix + (size_t)la->k * s->per + (la->which ? s->npx : 0));
 	pthread_mutex_lock(&s->mu);
 	s->t_load += now_s() - t0;
@@ -310,6 +328,21 @@ static void download_rows(eworker* wk, ebatch* b, const uint8_t* d_rows, size_t 
 	if (agmv_hip_stream_sync(wk->ctx, wk->stream)) agmv_die("row download");
 }
 
+/* a device source: where its frame `idx` is, and that frame as the encoder sees it into dst on the worker's stream (a copy, or
+   with a scale the gather through the table) */
+static const uint32_t* src_frame(const agmv_seq* s, long idx)
+{
+	return s->src.d_frames + (size_t)(idx - s->src.first) * s->src.src_w * s->src.src_h;
+}
+
+static int place_frame(eworker* wk, long idx, uint32_t* dst)
+{
+	agmv_seq* s = wk->s;
+	if (s->d_index)
+		return agmv_hip_gather_dev(wk->ctx, src_frame(s, idx), (size_t)s->src.src_w * s->src.src_h, 1, s->d_index, s->npx, dst, wk->stream);
+	return agmv_hip_memcpy_async(wk->ctx, dst, src_frame(s, idx), s->npx * 4, 2, wk->stream);
+}
+
 /* one GPU worker: its batches are id = idx, idx + nworkers, ... in order */
 static void* eworker_main(void* p)
 {
@@ -328,9 +361,18 @@ static void* eworker_main(void* p)
 		b = &s->slot[id % s->nslots];
 		const double tw0 = now_s();
 		for (k = 0; k < b->n; k++) {
-			const uint32_t* src = b->h_pix + (size_t)k * s->per;
+			const uint32_t* src = b->h_pix ? b->h_pix + (size_t)k * s->per : NULL;
 			uint32_t* dst = wk->d_frames + (size_t)k * s->npx;
-			if (b->srcB[k] < 0) {
+			if (s->src.d_frames) {                             /* the frames are on this device already: no upload */
+				if (b->srcB[k] < 0) {
+					if (place_frame(wk, b->srcA[k], dst)) agmv_die("frame copy");
+				} else if (s->d_index) {
+					if (place_frame(wk, b->srcA[k], wk->d_tmp[0]) || place_frame(wk, b->srcB[k], wk->d_tmp[1]) ||
+					    agmv_hip_interp_dev(wk->ctx, dst, wk->d_tmp[0], wk->d_tmp[1], s->npx, wk->stream))
+						agmv_die("frame gather / interp");
+				} else if (agmv_hip_interp_dev(wk->ctx, dst, src_frame(s, b->srcA[k]), src_frame(s, b->srcB[k]), s->npx, wk->stream))
+					agmv_die("frame interp");
+			} else if (b->srcB[k] < 0) {
 				if (agmv_hip_memcpy_async(wk->ctx, dst, src, s->npx * 4, 0, wk->stream)) agmv_die("frame upload");
 			} else {                                       /* AGMV_InterpFrame on the GPU, src/agmv_utils.c:949-969 */
 				if (agmv_hip_memcpy_async(wk->ctx, wk->d_tmp[0], src, s->npx * 4, 0, wk->stream) ||
@@ -462,12 +504,14 @@ static void submit_batch(agmv_seq* s)
 	ebatch* b = s->cur;
 	unsigned k, tasks = 0;
 	if (!b || !b->n) return;
-	for (k = 0; k < b->n; k++) tasks += b->srcB[k] < 0 ? 1 : 2;
+	if (!s->src.d_frames) for (k = 0; k < b->n; k++) tasks += b->srcB[k] < 0 ? 1 : 2;
 	pthread_mutex_lock(&s->mu);
 	b->loads_left = tasks;
+	if (!tasks) b->loaded = 1;                             /* a device source: nothing to load, the batch is the worker's at once */
 	s->nsubmitted++;
+	pthread_cond_broadcast(&s->cv);
 	pthread_mutex_unlock(&s->mu);
-	for (k = 0; k < b->n; k++) {
+	for (k = 0; tasks && k < b->n; k++) {
 		int which;
 		for (which = 0; which < (b->srcB[k] < 0 ? 1 : 2); which++) {
 			loadarg* la = (loadarg*)xmalloc(sizeof(*la));
@@ -478,7 +522,7 @@ static void submit_batch(agmv_seq* s)
 	s->cur = NULL;
 }
 
-agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const char* dir, const char* base, int scale_w, int scale_h, int mode512, int lz77,
+agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const agmv_source* src, int scale_w, int scale_h, int mode512, int lz77,
                         int audio_chunks, int use_interp, unsigned cap, unsigned devices, unsigned threads, const uint32_t pal[512])
 {
 	agmv_seq* s = (agmv_seq*)xcalloc(1, sizeof(*s));
@@ -486,12 +530,12 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const char* dir, const char* base, 
 	const double t0 = now_s();
 	double t1;
 	if (ndev < 1) agmv_die("cannot open the GPU");
-	if (devices < 1) devices = 1;
+	if (devices < 1 || src->d_frames) devices = 1;             /* a device source is encoded where it lives */
 	{	/* AGMV_DEVICES_OVERSUBSCRIBE=1: more "devices" than cards -- worker pair d runs on card d % ndev.  The round-robin of
 		   batches over devices, the in-order chunk writer and the per-device tables are then exercised on a one-GPU box. */
 		if (devices > ndev && !env_nonzero("AGMV_DEVICES_OVERSUBSCRIBE")) devices = ndev;
 	}
-	s->a = a; s->file = file; s->dir = dir; s->base = base; s->scale_w = scale_w; s->scale_h = scale_h;
+	s->a = a; s->file = file; s->src = *src; s->scale_w = scale_w; s->scale_h = scale_h;
 	s->audio_chunks = audio_chunks; s->mode512 = mode512; s->lz77 = lz77; s->use_b = use_interp;
 	s->w = (uint32_t)AGMV_GetWidth(a); s->h = (uint32_t)AGMV_GetHeight(a);
 	s->npx = (size_t)s->w * s->h; s->per = s->npx * (use_interp ? 2 : 1); s->stride = agmv_hip_max_usize(s->w, s->h, 1);
@@ -515,18 +559,18 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const char* dir, const char* base, 
 		b->srcA = (long*)xmalloc(sizeof(long) * s->cap); b->srcB = (long*)xmalloc(sizeof(long) * s->cap);
 		b->boff = (size_t*)xmalloc(sizeof(size_t) * s->cap);
 		b->jobs = (lzjob*)xcalloc(s->cap, sizeof(lzjob));
-		b->h_pix = (uint32_t*)agmv_hip_host_alloc(s->per * 4 * s->cap);
+		b->h_pix = src->d_frames ? NULL : (uint32_t*)agmv_hip_host_alloc(s->per * 4 * s->cap);
 		b->sizes = (uint32_t*)agmv_hip_host_alloc(4 * (size_t)s->cap + 64);
 		b->csizes = (uint32_t*)agmv_hip_host_alloc(4 * (size_t)s->cap + 64);
-		if (!b->h_pix || !b->sizes || !b->csizes) agmv_die("pinned allocation");
+		if ((!src->d_frames && !b->h_pix) || !b->sizes || !b->csizes) agmv_die("pinned allocation");
 	}
 	t1 = now_s();
-	TRACE("seq_open: pool + %u pinned slots of %.1f MB in %.3f s\n", s->nslots, s->per * 4.0 * s->cap / 1e6, t1 - t0);
+	TRACE("seq_open: pool + %u pinned slots of %.1f MB in %.3f s\n", s->nslots, src->d_frames ? 0.0 : s->per * 4.0 * s->cap / 1e6, t1 - t0);
 	s->wk = (eworker*)xcalloc(s->nworkers, sizeof(eworker));
 	for (i = 0; i < s->nworkers; i++) {
 		eworker* wk = &s->wk[i];
 		wk->s = s; wk->idx = i;
-		wk->ctx = agmv_hip_create((int)((i % devices) % ndev));
+		wk->ctx = agmv_hip_create(src->d_frames ? src->device : (int)((i % devices) % ndev));
 		if (!wk->ctx) agmv_die("cannot open the GPU");
 		if (agmv_hip_set_palette(wk->ctx, pal, pal + 256, mode512, NULL) || agmv_hip_sync()) agmv_die("palette upload");
 		wk->stream = agmv_hip_stream_create(wk->ctx);
@@ -536,6 +580,13 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const char* dir, const char* base, 
 		wk->d_ient = (uint16_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 2);
 		wk->d_tmp[0] = use_interp ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 4) : NULL;
 		wk->d_tmp[1] = use_interp ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 4) : NULL;
+		if (src->d_frames && scale_w && i == 0) {              /* the scale of a device source: its table, once, for all workers */
+			uint32_t* index = agmv_source_index(src->src_w, src->src_h, scale_w, scale_h, s->w, s->h);
+			s->d_index = (uint32_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 4);
+			if (!s->d_index || agmv_hip_memcpy_async(wk->ctx, s->d_index, index, s->npx * 4, 0, wk->stream) || agmv_hip_stream_sync(wk->ctx, wk->stream))
+				agmv_die("scale table upload");
+			free(index);
+		}
 		wk->d_lz = s->lz_dev && !lz77 ? (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->lz_stride * s->cap) : NULL;   /* (LZ77: lz77_rows) */
 		wk->d_csize = s->lz_dev ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, 4 * (size_t)s->cap) : NULL;
 		wk->d_peek = s->lz_dev && lz77 ? (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->cap) : NULL;
@@ -559,6 +610,9 @@ void agmv_seq_push(agmv_seq* s, long a, long b)
 {
 	if (!s->cur) begin_batch(s);
 	if (b >= 0 && !s->use_b) agmv_die("internal: midpoint frame on a sequence opened without interpolation");
+	if (s->src.d_frames && (a < s->src.first || a >= s->src.first + (long)s->src.n_frames || b >= s->src.first + (long)s->src.n_frames ||
+	                        (b >= 0 && b < s->src.first)))
+		agmv_die("internal: frame outside the device clip");
 	s->cur->srcA[s->cur->n] = a; s->cur->srcB[s->cur->n] = b;
 	if (++s->cur->n == batch_limit(s, s->cur)) submit_batch(s);
 }
@@ -584,7 +638,7 @@ u32 agmv_seq_close(agmv_seq* s)
 		agmv_hip_free_on(wk->ctx, wk->d_frames); agmv_hip_free_on(wk->ctx, wk->d_out); agmv_hip_free_on(wk->ctx, wk->d_sizes);
 		agmv_hip_free_on(wk->ctx, wk->d_ient); agmv_hip_free_on(wk->ctx, wk->d_tmp[0]); agmv_hip_free_on(wk->ctx, wk->d_tmp[1]);
 		agmv_hip_free_on(wk->ctx, wk->d_lz); agmv_hip_free_on(wk->ctx, wk->d_csize); agmv_hip_free_on(wk->ctx, wk->d_peek);
-		if (i == s->nworkers - 1) agmv_hip_free_on(wk->ctx, s->d_persist);       /* (every worker has been joined) */
+		if (i == s->nworkers - 1) { agmv_hip_free_on(wk->ctx, s->d_persist); agmv_hip_free_on(wk->ctx, s->d_index); }   /* (every worker has been joined) */
 		agmv_hip_stream_destroy(wk->ctx, wk->stream);
 		agmv_hip_destroy(wk->ctx);
 	}
@@ -627,9 +681,10 @@ static void hist_load_task(void* p)
 	free(ha);
 }
 
-void agmv_histogram_frames(agmv_hip_ctx* ctx, const char* dir, const char* base, u32 start, u32 end, u32 size, int quality,
+void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start, u32 end, u32 size, int quality,
                            unsigned threads, uint32_t* hist /* 2^19 bins */)
 {
+	const char *dir = src->dir, *base = src->base;
 	const u32 n = end >= start ? end - start + 1 : 0;
 	const double t0 = now_s();
 	uint32_t *d_hist, *d_pix;
@@ -639,6 +694,22 @@ void agmv_histogram_frames(agmv_hip_ctx* ctx, const char* dir, const char* base,
 	}
 	d_hist = (uint32_t*)agmv_hip_malloc_on(ctx, 4u << 19);
 	void* stream = agmv_hip_stream_create(ctx);
+	if (src->d_frames) {                                       /* the clip is resident: no parse, no ring, no upload */
+		const size_t fpx = (size_t)src->src_w * src->src_h, px = fpx < size ? fpx : size;
+		const uint32_t* d_first = src->d_frames + (size_t)((long)start - src->first) * fpx;
+		u32 k;
+		if ((long)start < src->first || (long)end >= src->first + (long)src->n_frames) agmv_die("internal: frame outside the device clip");
+		if (!d_hist || !stream || agmv_hip_memset_async(ctx, d_hist, 0, 4u << 19, stream)) agmv_die("histogram");
+		if (px == fpx) {                                       /* whole frames: the clip is one run of pixels */
+			if (agmv_hip_histogram_dev(ctx, d_first, (size_t)n * fpx, quality, d_hist, stream)) agmv_die("histogram");
+		} else
+			for (k = 0; k < n; k++) if (agmv_hip_histogram_dev(ctx, d_first + (size_t)k * fpx, px, quality, d_hist, stream)) agmv_die("histogram");
+		if (agmv_hip_memcpy_async(ctx, hist, d_hist, 4u << 19, 1, stream) || agmv_hip_stream_sync(ctx, stream)) agmv_die("histogram download");
+		agmv_hip_free_on(ctx, d_hist);
+		agmv_hip_stream_destroy(ctx, stream);
+		TRACE("palette pass 1: %u resident frames histogrammed in %.3f s\n", (unsigned)n, now_s() - t0);
+		return;
+	}
 	agmv_pool* pool = agmv_pool_start(threads);
 	hctx c;
 	u32 i, issued = 0;
@@ -713,6 +784,7 @@ typedef struct dpipe {
 	agmv_pool* pool;
 	pthread_t th;
 	uint8_t* d_bits; uint32_t *d_bpos, *d_nent, *d_out[2], *d_iframe;
+	uint32_t* d_dst;                       /* the sink: NULL = BMP export through d_out / h_out, else the caller's device frames */
 } dpipe;
 
 typedef struct savearg { dpipe* d; dbatch* b; unsigned k; } savearg;
@@ -737,8 +809,8 @@ static void* dworker_main(void* p)
 	int have_state = 0;
 	for (id = 0;; id++) {
 		dbatch* b = &d->slot[id % d->nslots];
-		uint32_t* out = d->d_out[id & 1];
-		const uint32_t* prev = have_state ? d->d_out[(id - 1) & 1] + (size_t)(prev_n - 1) * d->npx : NULL;
+		uint32_t* out;
+		const uint32_t* prev;
 		const uint8_t* bits = b->d_slab ? b->d_slab : d->d_bits;
 		const uint32_t* bpos = b->d_slab ? b->d_bpos : d->d_bpos;
 		unsigned k;
@@ -747,6 +819,9 @@ static void* dworker_main(void* p)
 		while (!(id < d->nfilled) && !d->closing) pthread_cond_wait(&d->cv, &d->mu);
 		if (id >= d->nfilled) { pthread_mutex_unlock(&d->mu); break; }
 		pthread_mutex_unlock(&d->mu);
+		/* with a sink the batch is decoded straight into its place, and the frame before it is the one before it there */
+		out = d->d_dst ? d->d_dst + (size_t)b->first * d->npx : d->d_out[id & 1];
+		prev = !have_state ? NULL : d->d_dst ? out - d->npx : d->d_out[(id - 1) & 1] + (size_t)(prev_n - 1) * d->npx;
 		if (b->d_slab) {                       /* the LZ stage left the rows on the device: wait for their commit, on the device */
 			if (agmv_hip_stream_wait_event(d->ctx, d->stream, b->ready)) goto fail;
 		} else if (agmv_hip_memcpy_async(d->ctx, d->d_bits, b->h_slab, d->stride * b->n, 0, d->stream) ||
@@ -760,15 +835,15 @@ static void* dworker_main(void* p)
 		for (k = 0; k < b->n; k++) if (((b->first + k) & 3u) == 0) last_i = (int)k;
 		if (!have_state && last_i < 0 && agmv_hip_memset_async(d->ctx, d->d_iframe, 0, d->npx * 4, d->stream)) goto fail;
 		if (last_i >= 0 && agmv_hip_memcpy_async(d->ctx, d->d_iframe, out + (size_t)last_i * d->npx, d->npx * 4, 2, d->stream)) goto fail;
-		if (agmv_hip_memcpy_async(d->ctx, b->h_out, out, d->npx * 4 * b->n, 1, d->stream) || agmv_hip_stream_sync(d->ctx, d->stream)) goto fail;
+		if ((!d->d_dst && agmv_hip_memcpy_async(d->ctx, b->h_out, out, d->npx * 4 * b->n, 1, d->stream)) || agmv_hip_stream_sync(d->ctx, d->stream)) goto fail;
 		have_state = 1;
 		prev_n = b->n;
 		pthread_mutex_lock(&d->mu);
-		b->decoded = 1;
-		b->saves_left = b->n;
+		if (d->d_dst) b->filled = 0;                       /* the frames are where they belong: the slot is free again */
+		else { b->decoded = 1; b->saves_left = b->n; }
 		pthread_cond_broadcast(&d->cv);
 		pthread_mutex_unlock(&d->mu);
-		for (k = 0; k < b->n; k++) {
+		for (k = 0; !d->d_dst && k < b->n; k++) {
 			savearg* sa = (savearg*)xmalloc(sizeof(*sa));
 			sa->d = d; sa->b = b; sa->k = k;
 			agmv_pool_submit(d->pool, save_task, sa);
@@ -946,9 +1021,10 @@ static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, dchunk* c, const u8* fil
    The LZ stage of a batch (between locate_chunks and cut_batch) runs on the pool, one frame per task, or with
    AGMV_LZ_DECODE_DEVICE=1 on the GPU (dlz_batch).  The bytes behind bpos that the block parser may read on an over-run are
    those of the reference's ONE persistent buffer: the host stage takes them from `persist` in frame order, which then
-   receives the frame. */
+   receives the frame.  The frames go to d_dst (device memory of ctx's device, frame k of the file at d_dst + k * w * h) or, with
+   d_dst NULL, to quick_export_<*export_count + 1 ...>.bmp; *export_count advances by the frames decoded either way. */
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
-                       int has_audio, unsigned cap_frames, unsigned threads, unsigned long* export_count)
+                       int has_audio, unsigned cap_frames, unsigned threads, uint32_t* d_dst, unsigned long* export_count)
 {
 	dpipe d;
 	dlz z;
@@ -964,7 +1040,7 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	memset(&d, 0, sizeof(d));
 	memset(&z, 0, sizeof(z));
 	d.ctx = ctx; d.w = w; d.h = h; d.npx = npx; d.stride = (cap + 255) & ~(size_t)255;
-	d.cap = cap_frames; d.nslots = 3;
+	d.cap = cap_frames; d.nslots = 3; d.d_dst = d_dst;
 	pthread_mutex_init(&d.mu, NULL);
 	pthread_cond_init(&d.cv, NULL);
 	d.slot = (dbatch*)calloc(d.nslots, sizeof(dbatch));
@@ -973,10 +1049,10 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	d.d_bits = lz_dev ? NULL : (uint8_t*)agmv_hip_malloc_on(ctx, d.stride * d.cap);      /* (the host LZ stage's upload slab) */
 	d.d_bpos = lz_dev ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
 	d.d_nent = (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
-	d.d_out[0] = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
-	d.d_out[1] = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
+	d.d_out[0] = d_dst ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
+	d.d_out[1] = d_dst ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
 	d.d_iframe = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4);
-	if (!persist || !chunks || (!lz_dev && !jobs) || !d.stream || (!lz_dev && (!d.d_bits || !d.d_bpos)) || !d.d_nent || !d.d_out[0] || !d.d_out[1] || !d.d_iframe) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+	if (!persist || !chunks || (!lz_dev && !jobs) || !d.stream || (!lz_dev && (!d.d_bits || !d.d_bpos)) || !d.d_nent || (!d_dst && (!d.d_out[0] || !d.d_out[1])) || !d.d_iframe) { rc = MEMORY_CORRUPTION_ERR; goto out; }
 	if (lz_dev && dlz_open(&z, ctx, d.cap, cap)) { rc = MEMORY_CORRUPTION_ERR; goto out; }
 	for (i = 0; i < d.nslots; i++) {
 		if (lz_dev) {                                          /* the rows live on the device only */
@@ -989,8 +1065,8 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 			d.slot[i].h_bpos = (uint32_t*)agmv_hip_host_alloc(4 * (size_t)d.cap + 64);
 			if (!d.slot[i].h_slab || !d.slot[i].h_bpos) { rc = MEMORY_CORRUPTION_ERR; goto out; }
 		}
-		d.slot[i].h_out = (uint32_t*)agmv_hip_host_alloc(npx * 4 * d.cap);
-		if (!d.slot[i].h_out) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+		d.slot[i].h_out = d_dst ? NULL : (uint32_t*)agmv_hip_host_alloc(npx * 4 * d.cap);
+		if (!d_dst && !d.slot[i].h_out) { rc = MEMORY_CORRUPTION_ERR; goto out; }
 	}
 	d.pool = agmv_pool_start(threads);
 	if (pthread_create(&d.th, NULL, dworker_main, &d)) {       /* no worker: nothing to join, nothing would ever consume a batch */

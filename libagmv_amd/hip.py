@@ -18,7 +18,7 @@ ABI_SYMBOLS = [
     "agmv_hip_encode_frames_dev", "agmv_hip_encode_frames", "agmv_hip_encode_entries_dev",
     "agmv_hip_encode_entries", "agmv_hip_nearest", "agmv_hip_within2_count", "agmv_hip_parse_frames_dev",
     "agmv_hip_decode_frames_dev", "agmv_hip_parse_decode_frames_dev", "agmv_hip_decode_bitstreams_dev", "agmv_hip_pack_frames_dev", "agmv_hip_unpack_frames_dev", "agmv_hip_parse_fallback_frames", "agmv_hip_decode_frames", "agmv_hip_decode_prior_dependent", "agmv_hip_synth_dev",
-    "agmv_hip_interp_dev", "agmv_hip_histogram_dev", "agmv_hip_check", "agmv_hip_malloc",
+    "agmv_hip_interp_dev", "agmv_hip_histogram_dev", "agmv_hip_similarity_dev", "agmv_hip_gather_dev", "agmv_hip_check", "agmv_hip_malloc",
     "agmv_hip_free", "agmv_hip_memcpy_h2d", "agmv_hip_memcpy_d2h", "agmv_hip_memset",
     "agmv_hip_sync", "agmv_hip_enable_timing", "agmv_hip_last_kernel_ms",
     "agmv_hip_stream_create", "agmv_hip_stream_destroy", "agmv_hip_stream_sync", "agmv_hip_host_alloc",
@@ -130,6 +130,10 @@ def load_library(path=None):
     L.agmv_hip_synth_dev.argtypes = [vp, vp, u32, u32, u32, u32, C.c_uint64, vp]
     L.agmv_hip_interp_dev.argtypes = [vp, vp, vp, vp, sz, vp]
     L.agmv_hip_histogram_dev.argtypes = [vp, vp, sz, C.c_int, vp, vp]
+    L.agmv_hip_similarity_dev.argtypes = [vp, vp, u32, sz, vp, vp]
+    L.agmv_hip_similarity_dev.restype = C.c_int
+    L.agmv_hip_gather_dev.argtypes = [vp, vp, sz, u32, vp, sz, vp, vp]
+    L.agmv_hip_gather_dev.restype = C.c_int
     L.agmv_hip_check.argtypes = [vp, vp]
     L.agmv_hip_enable_timing.argtypes = [vp, C.c_int]
     L.agmv_hip_enable_timing.restype = C.c_int
@@ -567,6 +571,35 @@ class AgmvHip:
         self._ck(self.L.agmv_hip_histogram_dev(self.ctx, pix.data_ptr(), pix.numel(), quality, hist.data_ptr(),
                                                self._stream()))
         return hist
+
+    def similarity_dev(self, pix, counts=None):
+        """pix: int32 CUDA tensor [n_frames, ...]; returns counts[n_frames - 1] (int32 storage) of equal-grey positions of
+        each adjacent pair.  `counts` is overwritten."""
+        import torch
+        n = pix.shape[0]
+        if not (pix.is_cuda and pix.dtype == torch.int32 and pix.is_contiguous() and n >= 1 and pix.numel() > 0):
+            raise ValueError("similarity_dev: a contiguous CUDA int32 tensor [n_frames, ...] is needed")
+        if counts is None:
+            counts = torch.empty(max(n - 1, 0), dtype=torch.int32, device=pix.device)
+        _check_vec("similarity_dev: counts", counts, n - 1)
+        self._ck(self.L.agmv_hip_similarity_dev(self.ctx, pix.data_ptr(), n, pix.numel() // n, counts.data_ptr(), self._stream()))
+        return counts
+
+    def gather_dev(self, src, index, out=None):
+        """src: int32 CUDA tensor [n_frames, src_px]; index: int32 storage of uint32 [n_out] (-1 = no source pixel);
+        returns [n_frames, n_out]"""
+        import torch
+        if not (src.is_cuda and src.dtype == torch.int32 and src.dim() == 2 and src.is_contiguous()):
+            raise ValueError("gather_dev: a contiguous CUDA int32 tensor [n_frames, src_px] is needed")
+        _check_vec("gather_dev: index", index, 1)
+        n, n_out = src.shape[0], index.numel()
+        if out is None:
+            out = torch.empty((n, n_out), dtype=torch.int32, device=src.device)
+        if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n * n_out):
+            raise ValueError("gather_dev: out must be a contiguous CUDA int32 tensor of n_frames * n_out entries")
+        self._ck(self.L.agmv_hip_gather_dev(self.ctx, src.data_ptr(), src.shape[1], n, index.data_ptr(), n_out, out.data_ptr(),
+                                            self._stream()))
+        return out
 
     # ------------------------------------------------------------------ host-buffer path
     def encode_host(self, frames, first_frame_count=0, ientries=None):
