@@ -304,6 +304,26 @@ int AGMV_EncodeFramesDev(const char* filename, const unsigned* d_frames, u32 num
                          AGMV_SCHEDULE schedule);
 int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frames, AGMV_INFO* info);
 
+/* The same two calls on clips in the layouts that video readers, models and image decoders hold.  One frame is:
+     AGMV_PIXFMT_XRGB32  [h][w] little-endian words 0x00RRGGBB; bits >= 24 ignored on input, 0 on output (the layout above)
+     AGMV_PIXFMT_RGB24   [h][w][3] bytes R, G, B
+     AGMV_PIXFMT_BGR24   [h][w][3] bytes B, G, R
+     AGMV_PIXFMT_RGBA32  [h][w][4] bytes R, G, B, A; A ignored on input, 0xFF on output
+     AGMV_PIXFMT_RGB8P   [3][h][w] bytes: plane R, plane G, plane B
+   Frames of a clip lie back to back; no alignment is asked for beyond 1 byte (4 for XRGB32).  The kernels that touch the clip
+   read and write it in that layout: no packed copy of more than one batch of frames exists on the device, and the files are
+   the same bytes whatever the layout.  AGMV_EncodeFramesFmtDev / AGMV_DecodeFramesFmtDev take, mean and return what
+   AGMV_EncodeFramesDev / AGMV_DecodeFramesDev do (which are the XRGB32 case); an unknown format is -1 before any file is
+   created and before a device is opened.  Frame k of a decoded file lands agmv_hip_pixfmt_frame_bytes(fmt, width * height)
+   * k bytes into d_frames (include/agmv_hip.h); frames behind cap_frames are not touched. */
+typedef enum AGMV_PIXFMT {
+	AGMV_PIXFMT_XRGB32 = 1, AGMV_PIXFMT_RGB24 = 2, AGMV_PIXFMT_BGR24 = 3, AGMV_PIXFMT_RGBA32 = 4, AGMV_PIXFMT_RGB8P = 5
+} AGMV_PIXFMT;
+int AGMV_EncodeFramesFmtDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 width, u32 height,
+                            u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression,
+                            AGMV_SCHEDULE schedule);
+int AGMV_DecodeFramesFmtDev(const char* filename, void* d_frames, AGMV_PIXFMT fmt, u32 cap_frames, AGMV_INFO* info);
+
 #ifdef __cplusplus
 }
 #endif

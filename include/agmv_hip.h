@@ -320,6 +320,37 @@ int agmv_hip_similarity_dev(agmv_hip_ctx* ctx, const uint32_t* d_pix, uint32_t n
 int agmv_hip_gather_dev(agmv_hip_ctx* ctx, const uint32_t* d_src, size_t src_frame_pixels, uint32_t n_frames,
                         const uint32_t* d_index, size_t n_out, uint32_t* d_dst, void* stream);
 
+/* -- clips in the caller's pixel layout ---------------------------------------------------------
+ * `fmt` is an AGMV_PIXFMT of include/agmv.h, by value: 1 XRGB32 (the 4-byte 0x00RRGGBB of every other entry point), 2 RGB24
+ * [h][w][3] bytes R,G,B, 3 BGR24 [h][w][3] bytes B,G,R, 4 RGBA32 [h][w][4] bytes R,G,B,A (A ignored on input, 0xFF on output),
+ * 5 RGB8P [3][h][w] bytes, plane R, G, B.  Frames lie back to back; the byte formats need no alignment (a clip whose frames
+ * start on 16-byte boundaries is read and written with 16-byte accesses, any other byte by byte).  With XRGB32 each function
+ * is the one it generalises, or a device-to-device copy.  An unknown format is an error return.
+ * agmv_hip_pixfmt_frame_bytes:   bytes of a frame of n_pixels (4n, 3n, 3n, 4n, 3n); 0 for an unknown format.  Host only: needs no
+ *                                context and no GPU.
+ * agmv_hip_pixels_to_xrgb_dev:   d_dst[f][k] = pixel k of frame f as 0x00RRGGBB, k < n_pixels <= frame_pixels.  Source frames
+ *                                are agmv_hip_pixfmt_frame_bytes(fmt, frame_pixels) bytes apart, planes frame_pixels bytes,
+ *                                destination rows n_pixels words.  (The plain frame of the sequence encoder's device source,
+ *                                which was a copy: agmv_hip_memcpy_async.)
+ * agmv_hip_pixels_from_xrgb_dev: the inverse for whole frames of n_pixels (bits >= 24 of the source are ignored); no byte
+ *                                outside the n_frames destination frames is written.  (The decoder's device sink.)
+ * agmv_hip_gather_fmt_dev:       agmv_hip_gather_dev reading a source in fmt: only the pixels the table names are touched.
+ * agmv_hip_histogram_fmt_dev:    agmv_hip_histogram_dev over the first n_pixels of each of n_frames frames read in fmt
+ *                                (d_hist is added to).
+ * agmv_hip_similarity_fmt_dev:   agmv_hip_similarity_dev on a clip in fmt (frames n_pixels apart): the same counts, each frame
+ *                                read once, d_counts overwritten. */
+size_t agmv_hip_pixfmt_frame_bytes(int fmt, size_t n_pixels);
+int agmv_hip_pixels_to_xrgb_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, size_t frame_pixels, uint32_t n_frames, size_t n_pixels,
+                                uint32_t* d_dst, void* stream);
+int agmv_hip_pixels_from_xrgb_dev(agmv_hip_ctx* ctx, int fmt, const uint32_t* d_src, uint32_t n_frames, size_t n_pixels, void* d_dst,
+                                  void* stream);
+int agmv_hip_gather_fmt_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, size_t src_frame_pixels, uint32_t n_frames,
+                            const uint32_t* d_index, size_t n_out, uint32_t* d_dst, void* stream);
+int agmv_hip_histogram_fmt_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, size_t frame_pixels, uint32_t n_frames, size_t n_pixels,
+                               int quality, uint32_t* d_hist, void* stream);
+int agmv_hip_similarity_fmt_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, uint32_t n_frames, size_t n_pixels, uint32_t* d_counts,
+                                void* stream);
+
 /* optional timing: when enabled the library records HIP events on the caller's stream around its three kernel
    groups; agmv_hip_last_kernel_ms(which) returns the last launch's duration in ms (0 = k_encode, 1 = the parser
    kernels, 2 = k_decode + k_fixup, 3 = the whole of agmv_hip_parse_decode_frames_dev / agmv_hip_decode_bitstreams_dev), or a negative value if

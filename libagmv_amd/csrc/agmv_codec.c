@@ -529,7 +529,7 @@ static void similarity_open(similarity* m, const agmv_source* src, AGMV* a, AGMV
 	{	/* the whole clip at once; with a scale, of the scaled frames (the same gather the workers run) */
 		agmv_hip_ctx* c = ctx();
 		const uint32_t n = src->n_frames;
-		const uint32_t* d_clip = src->d_frames;
+		const uint32_t* d_clip = NULL;                         /* the packed clip today's similarity reads, where one exists */
 		uint32_t *d_scaled = NULL, *d_index = NULL, *d_counts = (uint32_t*)agmv_hip_malloc_on(c, 4 * (size_t)n);
 		m->counts = (uint32_t*)calloc(n, 4);
 		if (!d_counts || !m->counts) agmv_die("device allocation");
@@ -538,12 +538,12 @@ static void similarity_open(similarity* m, const agmv_source* src, AGMV* a, AGMV
 			d_index = (uint32_t*)agmv_hip_malloc_on(c, npx * 4);
 			d_scaled = (uint32_t*)agmv_hip_malloc_on(c, npx * 4 * n);
 			if (!d_index || !d_scaled || agmv_hip_memcpy_async(c, d_index, index, npx * 4, 0, NULL) ||
-			    agmv_hip_gather_dev(c, src->d_frames, (size_t)src->src_w * src->src_h, n, d_index, npx, d_scaled, NULL))
+			    agmv_hip_gather_fmt_dev(c, src->fmt, src->d_frames, (size_t)src->src_w * src->src_h, n, d_index, npx, d_scaled, NULL))
 				agmv_die("frame gather");
 			d_clip = d_scaled;
 			m->tmp = index;                                    /* (freed by similarity_close, behind the synchronisation below) */
 		}
-		if (agmv_hip_similarity_dev(c, d_clip, n, npx, d_counts, NULL) ||
+		if ((d_clip ? agmv_hip_similarity_dev(c, d_clip, n, npx, d_counts, NULL) : agmv_hip_similarity_fmt_dev(c, src->fmt, src->d_frames, n, npx, d_counts, NULL)) ||
 		    (n > 1 && agmv_hip_memcpy_async(c, m->counts, d_counts, 4 * (size_t)(n - 1), 1, NULL)) || agmv_hip_stream_sync(c, NULL))
 			agmv_die("frame similarity");
 		agmv_hip_free_on(c, d_counts); agmv_hip_free_on(c, d_scaled); agmv_hip_free_on(c, d_index);
@@ -669,17 +669,17 @@ void AGMV_EncodeVideo(const char* filename, const char* dir, const char* basenam
 	                start_frame, end_frame, width, height, opt, quality, compression);
 }
 
-/* The same three files from frames in device memory: d_frames[num_of_frames][height][width], 0x00RRGGBB, on the device of
-   this library's context.  What the BMP drivers write for f1.bmp .. f<n>.bmp holding these frames, byte for byte (for
+/* The same three files from frames in device memory: num_of_frames frames of width x height pixels in the layout `fmt`, on the
+   device of this library's context.  What the BMP drivers write for f1.bmp .. f<n>.bmp holding these frames, byte for byte (for
    AGMV_SCHEDULE_ADAPTIVE with AGMV_EncodeVideo's CreateAGMV(n - 1, ...)); GBA_GEN_AGMV.h is not written.  Returns 0, or a
    negative value -- before any file is created -- for arguments that cannot be encoded. */
-int AGMV_EncodeFramesDev(const char* filename, const unsigned* d_frames, u32 num_of_frames, u32 width, u32 height,
-                         u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+int AGMV_EncodeFramesFmtDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 width, u32 height,
+                            u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
 {
 	agmv_source src;
 	int sw, sh;
 	u32 least;
-	if (!filename || !d_frames) return -1;
+	if (!filename || !d_frames || fmt < AGMV_PIXFMT_XRGB32 || fmt > AGMV_PIXFMT_RGB8P) return -1;
 	if (opt < AGMV_OPT_I || opt > AGMV_OPT_NDS || quality < AGMV_HIGH_QUALITY || quality > AGMV_LOW_QUALITY ||
 	    (compression != AGMV_LZSS_COMPRESSION && compression != AGMV_LZ77_COMPRESSION) ||
 	    (schedule != AGMV_SCHEDULE_FULL && schedule != AGMV_SCHEDULE_PDIFS && schedule != AGMV_SCHEDULE_ADAPTIVE))
@@ -692,11 +692,18 @@ int AGMV_EncodeFramesDev(const char* filename, const unsigned* d_frames, u32 num
 	if (!sw && bad_geometry((uint32_t)width, (uint32_t)height)) return -3;
 	if (sw && (width < 2 || height < 2)) return -3;
 	memset(&src, 0, sizeof(src));
-	src.d_frames = (const uint32_t*)d_frames; src.src_w = (uint32_t)width; src.src_h = (uint32_t)height;
+	src.d_frames = d_frames; src.fmt = (int)fmt; src.src_w = (uint32_t)width; src.src_h = (uint32_t)height;
 	src.n_frames = (uint32_t)num_of_frames; src.first = 1; src.device = agmv_hip_ctx_device(ctx());
 	encode_sequence(CreateAGMV(schedule == AGMV_SCHEDULE_ADAPTIVE ? num_of_frames - 1 : num_of_frames, width, height, frames_per_second),
 	                filename, &src, schedule, 1, num_of_frames, width, height, opt, quality, compression);
 	return 0;
+}
+
+int AGMV_EncodeFramesDev(const char* filename, const unsigned* d_frames, u32 num_of_frames, u32 width, u32 height,
+                         u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+{
+	return AGMV_EncodeFramesFmtDev(filename, d_frames, AGMV_PIXFMT_XRGB32, num_of_frames, width, height, frames_per_second, opt, quality, compression,
+	                               schedule);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -704,9 +711,9 @@ int AGMV_EncodeFramesDev(const char* filename, const unsigned* d_frames, u32 num
  * frame by frame into ONE persistent buffer (so the stale-tail semantics hold), the GPU parses and
  * reconstructs whole batches, frames are exported as quick_export_<n>.bmp in the CWD.
  * ------------------------------------------------------------------------------------------ */
-/* d_dst NULL: AGMV_DecodeAGMV / AGMV_DecodeVideo, every frame to its BMP.  Else AGMV_DecodeFramesDev: up to cap_frames frames
-   into d_dst, their number into *decoded.  *info (may be NULL) = the header's; with info_only nothing else happens. */
-static int decode_file(const char* filename, u8 img_type, uint32_t* d_dst, u32 cap_frames, int info_only, AGMV_INFO* info, unsigned long* decoded)
+/* d_dst NULL: AGMV_DecodeAGMV / AGMV_DecodeVideo, every frame to its BMP.  Else AGMV_DecodeFramesFmtDev: up to cap_frames frames
+   in the layout `fmt` into d_dst, their number into *decoded.  *info (may be NULL) = the header's; with info_only nothing else happens. */
+static int decode_file(const char* filename, u8 img_type, void* d_dst, int fmt, u32 cap_frames, int info_only, AGMV_INFO* info, unsigned long* decoded)
 {
 	FILE* f = fopen(filename, "rb");
 	AGMV hdr_obj;
@@ -750,21 +757,28 @@ static int decode_file(const char* filename, u8 img_type, uint32_t* d_dst, u32 c
 	nframes = (uint32_t)hdr_obj.header.num_of_frames;
 	if (d_dst && nframes > cap_frames) nframes = (uint32_t)cap_frames;
 	err = agmv_decode_stream(c, file, got, pos, w, h, nframes, hdr_obj.header.version, hdr_obj.header.total_audio_duration != 0, cap,
-	                         lz_threads(), d_dst, d_dst ? decoded : &g_export_count);
+	                         lz_threads(), d_dst, fmt, d_dst ? decoded : &g_export_count);
 	free(file);
 	return err;
 }
 
-int AGMV_DecodeVideo(const char* filename, u8 img_type) { return decode_file(filename, img_type, NULL, 0, 0, NULL, NULL); }
+int AGMV_DecodeVideo(const char* filename, u8 img_type) { return decode_file(filename, img_type, NULL, AGMV_PIXFMT_XRGB32, 0, 0, NULL, NULL); }
 
-/* AGMV_DecodeAGMV with another destination: frame k of the file (0-based) at d_frames + k * width * height (4-byte 0x00RRGGBB,
-   device memory of this library's context) instead of in quick_export_<k + 1>.bmp.  At most cap_frames frames; returns the
+/* AGMV_DecodeAGMV with another destination: frame k of the file (0-based) as the k-th frame of the layout `fmt` in d_frames
+   (device memory of this library's context) instead of in quick_export_<k + 1>.bmp.  At most cap_frames frames; returns the
    number decoded or a negative Error.  With d_frames NULL nothing is decoded and only *info is filled. */
-int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frames, AGMV_INFO* info)
+int AGMV_DecodeFramesFmtDev(const char* filename, void* d_frames, AGMV_PIXFMT fmt, u32 cap_frames, AGMV_INFO* info)
 {
 	unsigned long decoded = 0;
-	const int err = filename ? decode_file(filename, AGMV_IMG_BMP, (uint32_t*)d_frames, cap_frames, d_frames == NULL, info, &decoded) : FILE_NOT_FOUND_ERR;
+	int err;
+	if (fmt < AGMV_PIXFMT_XRGB32 || fmt > AGMV_PIXFMT_RGB8P) return -1;
+	err = filename ? decode_file(filename, AGMV_IMG_BMP, d_frames, (int)fmt, cap_frames, d_frames == NULL, info, &decoded) : FILE_NOT_FOUND_ERR;
 	return err == NO_ERR ? (int)decoded : -err;
+}
+
+int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frames, AGMV_INFO* info)
+{
+	return AGMV_DecodeFramesFmtDev(filename, d_frames, AGMV_PIXFMT_XRGB32, cap_frames, info);
 }
 
 /* audio export (quick_export.wav / .aiff) is out of scope of this build; the video frames are exported
@@ -772,7 +786,7 @@ int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frame
 int AGMV_DecodeAGMV(const char* filename, u8 img_type, AGMV_AUDIO_TYPE audio_type)
 {
 	(void)audio_type;
-	return decode_file(filename, img_type, NULL, 0, 0, NULL, NULL);
+	return decode_file(filename, img_type, NULL, AGMV_PIXFMT_XRGB32, 0, 0, NULL, NULL);
 }
 
 /* ------------------------------------------------------------------------------------------

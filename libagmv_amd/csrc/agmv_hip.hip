@@ -2460,6 +2460,260 @@ __global__ __launch_bounds__(256) void k_gather(const uint32_t* __restrict__ src
 	for (uint32_t f = 0; f < n_frames; f++) dst[(size_t)f * n_out + k] = live ? src[(size_t)f * src_px + i] : 0u;
 }
 
+// ---- clips in the caller's pixel layout (AGMV_PIXFMT of include/agmv.h: the values 2 .. 5; XRGB32 = 1 goes to the kernels above) ----
+// A frame of fpx pixels is fr[fpx][3] bytes R,G,B (RGB24) or B,G,R (BGR24), fr[fpx][4] bytes R,G,B,A (RGBA32), or three planes
+// of fpx bytes R, G, B (RGB8P).  The kernels below are HBM streams.  Where every frame (and plane) starts on a 16-byte
+// boundary a lane owns 16 consecutive pixels: three 16-byte loads (four for RGBA32), which the wave issues over one contiguous
+// 3 (4) KiB, and four 16-byte stores.  Otherwise (`wide` / `vec` 0: a clip at an odd byte offset, a frame size that is no multiple
+// of 16) and for the last partial group of 16 of a frame the same kernel goes pixel by pixel through byte loads.
+#define PF_XRGB32 1
+#define PF_RGB24 2
+#define PF_BGR24 3
+#define PF_RGBA32 4
+#define PF_RGB8P 5
+
+typedef uint32_t pf_u32x4 __attribute__((ext_vector_type(4)));
+template <int FMT> struct pf_raw { pf_u32x4 v[FMT == PF_RGBA32 ? 4 : 3]; };      // 16 pixels as they lie in memory
+
+// pixel k of a frame as 0x00RRGGBB, byte by byte (fmt is a constant in the templates)
+__device__ __forceinline__ uint32_t pf_read(int fmt, const uint8_t* __restrict__ fr, size_t fpx, size_t k)
+{
+	if (fmt == PF_RGB8P) return (uint32_t)fr[k] << 16 | (uint32_t)fr[fpx + k] << 8 | fr[2 * fpx + k];
+	const uint8_t* p = fr + (fmt == PF_RGBA32 ? 4 : 3) * k;
+	return fmt == PF_BGR24 ? (uint32_t)p[2] << 16 | (uint32_t)p[1] << 8 | p[0] : (uint32_t)p[0] << 16 | (uint32_t)p[1] << 8 | p[2];
+}
+
+__device__ __forceinline__ void pf_write(int fmt, uint8_t* __restrict__ fr, size_t fpx, size_t k, uint32_t x)
+{
+	const uint8_t r = (uint8_t)(x >> 16), g = (uint8_t)(x >> 8), b = (uint8_t)x;
+	if (fmt == PF_RGB8P) { fr[k] = r; fr[fpx + k] = g; fr[2 * fpx + k] = b; return; }
+	uint8_t* p = fr + (fmt == PF_RGBA32 ? 4 : 3) * k;
+	p[0] = fmt == PF_BGR24 ? b : r; p[1] = g; p[2] = fmt == PF_BGR24 ? r : b;
+	if (fmt == PF_RGBA32) p[3] = 0xFF;
+}
+
+// pixels p .. p + 15 of a frame whose rows of 16 pixels are 16-byte aligned; NT: the bytes are used once
+template <int FMT, bool NT> __device__ __forceinline__ pf_raw<FMT> pf_load16(const uint8_t* __restrict__ fr, size_t fpx, size_t p)
+{
+	pf_raw<FMT> r;
+#pragma unroll
+	for (int j = 0; j < (FMT == PF_RGBA32 ? 4 : 3); j++) {
+		const pf_u32x4* a = reinterpret_cast<const pf_u32x4*>(FMT == PF_RGB8P ? fr + (size_t)j * fpx + p : fr + (FMT == PF_RGBA32 ? 4 : 3) * p + 16 * j);
+		r.v[j] = NT ? __builtin_nontemporal_load(a) : *a;
+	}
+	return r;
+}
+
+// pixel i (a constant once the caller's loop is unrolled) of such a group as 0x00RRGGBB
+template <int FMT> __device__ __forceinline__ uint32_t pf_pixel(const pf_raw<FMT>& r, int i)
+{
+	if (FMT == PF_RGB8P) {
+		const int s = (i & 3) * 8;
+		return ((r.v[0][i >> 2] >> s) & 0xffu) << 16 | ((r.v[1][i >> 2] >> s) & 0xffu) << 8 | ((r.v[2][i >> 2] >> s) & 0xffu);
+	}
+	if (FMT == PF_RGBA32) {
+		const uint32_t w = r.v[i >> 2][i & 3];
+		return (w & 0xffu) << 16 | (w & 0xff00u) | ((w >> 16) & 0xffu);
+	}
+	const int o = 3 * i, w = o >> 2, s = (o & 3) * 8;                  // the pixel's three bytes start at byte o of the 48
+	uint32_t v = r.v[w >> 2][w & 3] >> s;
+	if (s > 8) v |= r.v[(w + 1) >> 2][(w + 1) & 3] << (32 - s);
+	v &= 0xffffffu;                                                  // first byte in bits 0..7: BGR24 is 0x00RRGGBB as it lies
+	return FMT == PF_BGR24 ? v : (v & 0xffu) << 16 | (v & 0xff00u) | v >> 16;
+}
+
+// the inverse: 16 pixels 0x..RRGGBB (x[j] = pixels 4j .. 4j + 3) as they lie in a frame of FMT
+template <int FMT> __device__ __forceinline__ pf_raw<FMT> pf_pack16(const pf_u32x4 x[4])
+{
+	pf_raw<FMT> r;
+#pragma unroll
+	for (int w = 0; w < (FMT == PF_RGBA32 ? 16 : 12); w++) {
+		uint32_t word = 0;
+		if (FMT == PF_RGBA32) {
+			const uint32_t c = x[w >> 2][w & 3];
+			word = ((c >> 16) & 0xffu) | (c & 0xff00u) | (c & 0xffu) << 16 | 0xff000000u;
+		} else {
+#pragma unroll
+			for (int b = 0; b < 4; b++) {
+				const int o = 4 * w + b;                                 // byte o of the 48
+				const int i = FMT == PF_RGB8P ? o & 15 : o / 3, ch = FMT == PF_RGB8P ? o >> 4 : o % 3;    // its pixel and channel (0 = first in memory)
+				const int sh = FMT == PF_BGR24 ? 8 * ch : 16 - 8 * ch;
+				word |= ((x[i >> 2][i & 3] >> sh) & 0xffu) << (8 * b);
+			}
+		}
+		r.v[w >> 2][w & 3] = word;
+	}
+	return r;
+}
+
+// d_dst[f][k] = pixel k of frame f, k < npx <= fpx.  A thread's group of 16 pixels is g; one frame takes bpf blocks.
+template <int FMT> __global__ __launch_bounds__(256) void k_pix_to_xrgb(const uint8_t* __restrict__ src, size_t fpx, size_t frame_bytes, size_t npx,
+                                                                        uint32_t bpf, int wide, uint32_t* __restrict__ dst)
+{
+	const uint32_t f = blockIdx.x / bpf;
+	const size_t g = (size_t)(blockIdx.x - f * bpf) * 256 + threadIdx.x, p = g * 16;
+	const uint8_t* fr = src + (size_t)f * frame_bytes;
+	uint32_t* out = dst + (size_t)f * npx;
+	if (wide && p + 16 <= npx) {
+		const pf_raw<FMT> r = pf_load16<FMT, true>(fr, fpx, p);
+#pragma unroll
+		for (int j = 0; j < 4; j++) {
+			pf_u32x4 o;
+#pragma unroll
+			for (int i = 0; i < 4; i++) o[i] = pf_pixel<FMT>(r, 4 * j + i);
+			*reinterpret_cast<pf_u32x4*>(out + p + 4 * j) = o;
+		}
+	} else if (wide) {                                                 // the last, partial group of the frame
+		for (int i = 0; i < 16; i++) if (p + i < npx) out[p + i] = pf_read(FMT, fr, fpx, p + i);
+	} else {                                                           // lanes on consecutive pixels: the wave's 1024, 64 at a time
+		const size_t w0 = (g & ~(size_t)63) * 16 + (threadIdx.x & 63);
+		for (int i = 0; i < 16; i++) if (w0 + 64 * i < npx) out[w0 + 64 * i] = pf_read(FMT, fr, fpx, w0 + 64 * i);
+	}
+}
+
+// d_dst frame f = src[f][0 .. npx) in FMT (whole frames of npx pixels); nothing outside those frames is written
+template <int FMT> __global__ __launch_bounds__(256) void k_pix_from_xrgb(const uint32_t* __restrict__ src, size_t npx, size_t frame_bytes, uint32_t bpf,
+                                                                          int wide, uint8_t* __restrict__ dst)
+{
+	const uint32_t f = blockIdx.x / bpf;
+	const size_t g = (size_t)(blockIdx.x - f * bpf) * 256 + threadIdx.x, p = g * 16;
+	const uint32_t* in = src + (size_t)f * npx;
+	uint8_t* fr = dst + (size_t)f * frame_bytes;
+	if (wide && p + 16 <= npx) {
+		pf_u32x4 x[4];
+#pragma unroll
+		for (int j = 0; j < 4; j++) x[j] = __builtin_nontemporal_load(reinterpret_cast<const pf_u32x4*>(in + p + 4 * j));
+		const pf_raw<FMT> r = pf_pack16<FMT>(x);
+#pragma unroll
+		for (int j = 0; j < (FMT == PF_RGBA32 ? 4 : 3); j++)
+			*reinterpret_cast<pf_u32x4*>(FMT == PF_RGB8P ? fr + (size_t)j * npx + p : fr + (FMT == PF_RGBA32 ? 4 : 3) * p + 16 * j) = r.v[j];
+	} else if (wide) {
+		for (int i = 0; i < 16; i++) if (p + i < npx) pf_write(FMT, fr, npx, p + i, in[p + i]);
+	} else {
+		const size_t w0 = (g & ~(size_t)63) * 16 + (threadIdx.x & 63);
+		for (int i = 0; i < 16; i++) if (w0 + 64 * i < npx) pf_write(FMT, fr, npx, w0 + 64 * i, in[w0 + 64 * i]);
+	}
+}
+
+// k_gather on a source in fmt: only the pixels the table names are read
+__global__ __launch_bounds__(256) void k_gather_fmt(const uint8_t* __restrict__ src, int fmt, size_t src_px, size_t frame_bytes, uint32_t n_frames,
+                                                    const uint32_t* __restrict__ index, size_t n_out, uint32_t* __restrict__ dst)
+{
+	const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (k >= n_out) return;
+	const uint32_t i = index[k];
+	const bool live = i != 0xFFFFFFFFu && (size_t)i < src_px;
+	for (uint32_t f = 0; f < n_frames; f++) dst[(size_t)f * n_out + k] = live ? pf_read(fmt, src + (size_t)f * frame_bytes, src_px, i) : 0u;
+}
+
+// the run-length atomics of k_histogram for one code per lane: each run of equal codes over the wave's live lanes (a prefix of
+// the wave) adds its length with one atomic.  Every lane of the wave calls it.
+__device__ __forceinline__ void hist_add_runs(uint32_t* __restrict__ hist, uint32_t c, bool live, int lane)
+{
+	const uint32_t prev = __shfl_up(c, 1, 64);
+	const bool leader = live && (lane == 0 || c != prev);
+	const unsigned long long lead = __ballot(leader), alive = __ballot(live);
+	if (leader) {
+		const unsigned long long rest = lane == 63 ? 0ull : lead >> (lane + 1);
+		const uint32_t end = rest ? (uint32_t)lane + 1u + (uint32_t)__builtin_ctzll(rest) : (uint32_t)__popcll(alive);
+		atomicAdd(hist + c, end - (uint32_t)lane);
+	}
+}
+
+// k_histogram over the first npx pixels of each frame of a clip in FMT.  A wave takes 1024 pixels of one frame in 16 slices of
+// 64 consecutive pixels, so that neighbouring lanes hold neighbouring pixels as in k_histogram and runs stay long.  Wide, the
+// wave's 3 (4) KiB go through LDS as they lie in memory (each lane's 16-byte loads stored at their place, the pixels of a
+// partial last group byte by byte) and a slice reads its pixels from there; byte-wise a slice reads global memory directly.
+template <int FMT> __global__ __launch_bounds__(256) void k_histogram_fmt(const uint8_t* __restrict__ src, size_t fpx, size_t frame_bytes, size_t npx,
+                                                                          uint32_t bpf, int wide, int quality, uint32_t* __restrict__ hist)
+{
+	__shared__ pf_u32x4 s_px[4][256];                              // per wave 4 KiB: 1024 pixels (RGB8P: planes 1024 bytes apart)
+	const int lane = threadIdx.x & 63;
+	const uint32_t f = blockIdx.x / bpf;
+	const size_t g = (size_t)(blockIdx.x - f * bpf) * 256 + threadIdx.x, p = g * 16;
+	const size_t w0 = (g & ~(size_t)63) * 16;                      // the wave's first pixel
+	const uint8_t* fr = src + (size_t)f * frame_bytes;
+	if (wide) {
+		uint8_t* sw = reinterpret_cast<uint8_t*>(s_px[threadIdx.x >> 6]);
+		if (p + 16 <= npx) {
+			const pf_raw<FMT> r = pf_load16<FMT, false>(fr, fpx, p);
+#pragma unroll
+			for (int j = 0; j < (FMT == PF_RGBA32 ? 4 : 3); j++)
+				*reinterpret_cast<pf_u32x4*>(FMT == PF_RGB8P ? sw + 1024 * j + 16 * lane : sw + (FMT == PF_RGBA32 ? 64 : 48) * lane + 16 * j) = r.v[j];
+		} else {
+			for (int i = 0; i < 16; i++) if (p + i < npx) pf_write(FMT, sw, 1024, 16 * lane + i, pf_read(FMT, fr, fpx, p + i));
+		}
+		__syncthreads();
+		for (int i = 0; i < 16; i++) {
+			const bool live = w0 + 64 * i + lane < npx;
+			hist_add_runs(hist, live ? quantize_color(pf_read(FMT, sw, 1024, 64 * i + lane), quality) : 0xFFFFFFFFu, live, lane);
+		}
+	} else {
+		for (int i = 0; i < 16; i++) {
+			const size_t k = w0 + 64 * i + lane;
+			const bool live = k < npx;
+			hist_add_runs(hist, live ? quantize_color(pf_read(FMT, fr, fpx, k), quality) : 0xFFFFFFFFu, live, lane);
+		}
+	}
+}
+
+// k_similarity on a clip in FMT (frames npx pixels apart): the same walk through all frames and the same slots, with 16 pixel
+// positions per lane: three (four) 16-byte loads per frame, the greys of the frame before in four registers.  vec: npx % 16 == 0
+// and the clip is 16-byte aligned.  Without it the loads are byte loads and deliver the greys at once (in v[0]).
+__device__ __forceinline__ uint32_t sim_grey(uint32_t x) { return (((x >> 16) & 0xff) + ((x >> 8) & 0xff) + (x & 0xff)) / 3u; }
+
+template <int FMT> __device__ __forceinline__ pf_raw<FMT> sim_load16(const uint8_t* __restrict__ fr, size_t p, size_t npx, bool vec)
+{
+	pf_raw<FMT> r;
+	if (vec && p < npx) return pf_load16<FMT, false>(fr, npx, p);
+#pragma unroll
+	for (int j = 0; j < (FMT == PF_RGBA32 ? 4 : 3); j++) r.v[j] = 0;
+	if (!vec) {
+#pragma unroll
+		for (int i = 0; i < 16; i++) if (p + i < npx) r.v[0][i >> 2] |= sim_grey(pf_read(FMT, fr, npx, p + i)) << (8 * (i & 3));
+	}
+	return r;
+}
+
+template <int FMT> __device__ __forceinline__ pf_u32x4 sim_greys16(const pf_raw<FMT>& r, bool vec)
+{
+	if (!vec) return r.v[0];
+	pf_u32x4 g = 0;
+#pragma unroll
+	for (int i = 0; i < 16; i++) g[i >> 2] |= sim_grey(pf_pixel<FMT>(r, i)) << (8 * (i & 3));
+	return g;
+}
+
+template <int FMT> __global__ __launch_bounds__(256) void k_similarity_fmt(const uint8_t* __restrict__ pix, uint32_t n_frames, size_t npx, size_t frame_bytes,
+                                                                           int vec, uint32_t* __restrict__ counts)
+{
+	__shared__ uint32_t s_cnt[SIM_SEG];
+	const size_t p = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
+	// positions of this lane behind the frame's end read as 0 in every frame: they always compare equal and are taken off again
+	const uint32_t dead = (uint32_t)(p >= npx ? 16 : (p + 16 > npx ? p + 16 - npx : 0));
+	const uint32_t n_pairs = n_frames - 1;
+	pf_u32x4 g = sim_greys16<FMT>(sim_load16<FMT>(pix, p, npx, vec), vec);
+	pf_raw<FMT> nx = sim_load16<FMT>(pix + frame_bytes, p, npx, vec);
+	for (uint32_t seg = 0; seg < n_pairs; seg += SIM_SEG) {
+		const uint32_t n_seg = n_pairs - seg < SIM_SEG ? n_pairs - seg : SIM_SEG;
+		for (uint32_t k = threadIdx.x; k < n_seg; k += 256) s_cnt[k] = 0;
+		__syncthreads();
+		for (uint32_t k = 0; k < n_seg; k++) {
+			const uint32_t f = seg + k + 1;                    // the later frame of pair seg + k: its pixels are in nx
+			const pf_raw<FMT> cur = nx;
+			if (f + 1 < n_frames) nx = sim_load16<FMT>(pix + (size_t)(f + 1) * frame_bytes, p, npx, vec);
+			const pf_u32x4 h = sim_greys16<FMT>(cur, vec);
+			uint32_t c = sim_equal_bytes(g[0], h[0]) + sim_equal_bytes(g[1], h[1]) + sim_equal_bytes(g[2], h[2]) + sim_equal_bytes(g[3], h[3]) - dead;
+			g = h;
+			for (int d = 32; d; d >>= 1) c += __shfl_xor(c, d, 64);
+			if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt[k], c);
+		}
+		__syncthreads();
+		for (uint32_t k = threadIdx.x; k < n_seg; k += 256) if (s_cnt[k]) atomicAdd(counts + seg + k, s_cnt[k]);
+		__syncthreads();
+	}
+}
+
 // A spin of k_encode that ran into its bound leaves ctrl[1] != 0 and the kernel carries on with a wrong offset: the bytes of
 // the batch are not to be used.  So that a caller who skips agmv_hip_check cannot take them for good ones, every size of
 // the batch is then overwritten with 0xFFFFFFFF (no frame is that long: agmv_hip_max_usize < 2^32).
@@ -3451,6 +3705,139 @@ extern "C" int agmv_hip_gather_dev(agmv_hip_ctx* c, const uint32_t* d_src, size_
 	if (n_out > ((size_t)1 << 39)) { snprintf(g_err, sizeof(g_err), "agmv_hip: gather table too long"); return -1; }
 	hipLaunchKernelGGL(k_gather, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_src, src_frame_pixels, n_frames,
 	                   d_index, n_out, d_dst);
+	CK(hipGetLastError());
+	return 0;
+}
+
+// ---- the same on clips in the caller's pixel layout ----
+extern "C" size_t agmv_hip_pixfmt_frame_bytes(int fmt, size_t n_pixels)
+{
+	switch (fmt) {
+	case PF_XRGB32: case PF_RGBA32: return 4 * n_pixels;
+	case PF_RGB24: case PF_BGR24: case PF_RGB8P: return 3 * n_pixels;
+	default: return 0;
+	}
+}
+
+static int bad_pixfmt(int fmt)
+{
+	if (fmt >= PF_XRGB32 && fmt <= PF_RGB8P) return 0;
+	snprintf(g_err, sizeof(g_err), "agmv_hip: unknown pixel format %d", fmt);
+	return -1;
+}
+
+// the grid of the kernels that give a thread 16 pixels of one frame: blocks per frame, and whether all of them fit
+static int pf_grid(size_t n_pixels, uint32_t n_frames, uint32_t* bpf, unsigned* blocks)
+{
+	const size_t per = (n_pixels + 4095) / 4096;
+	if (per * n_frames > 0x7FFFFFFFull) { snprintf(g_err, sizeof(g_err), "agmv_hip: clip too large for one launch"); return -1; }
+	*bpf = (uint32_t)per; *blocks = (unsigned)(per * n_frames);
+	return 0;
+}
+
+// every frame of the clip (planes frame_pixels apart) starts on a 16-byte boundary
+static int pf_aligned(int fmt, const void* d, size_t frame_pixels, uint32_t n_frames)
+{
+	if ((uintptr_t)d & 15) return 0;
+	if (fmt == PF_RGB8P && (frame_pixels & 15)) return 0;
+	return n_frames == 1 || (agmv_hip_pixfmt_frame_bytes(fmt, frame_pixels) & 15) == 0;
+}
+
+#define PF_LAUNCH(kernel, ...) do { switch (fmt) { \
+	case PF_RGB24: hipLaunchKernelGGL(kernel<PF_RGB24>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+	case PF_BGR24: hipLaunchKernelGGL(kernel<PF_BGR24>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+	case PF_RGBA32: hipLaunchKernelGGL(kernel<PF_RGBA32>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+	default: hipLaunchKernelGGL(kernel<PF_RGB8P>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); break; } } while (0)
+
+extern "C" int agmv_hip_pixels_to_xrgb_dev(agmv_hip_ctx* c, int fmt, const void* d_src, size_t frame_pixels, uint32_t n_frames, size_t n_pixels,
+                                           uint32_t* d_dst, void* stream)
+{
+	if (need_ctx(c, false) || bad_pixfmt(fmt)) return -1;
+	if (n_pixels > frame_pixels) { snprintf(g_err, sizeof(g_err), "agmv_hip: n_pixels %zu > frame_pixels %zu", n_pixels, frame_pixels); return -1; }
+	if (n_frames == 0 || n_pixels == 0) return 0;
+	if (fmt == PF_XRGB32) {
+		if (n_frames == 1 || n_pixels == frame_pixels) CK(hipMemcpyAsync(d_dst, d_src, (size_t)n_frames * n_pixels * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+		else CK(hipMemcpy2DAsync(d_dst, n_pixels * 4, d_src, frame_pixels * 4, n_pixels * 4, n_frames, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+		return 0;
+	}
+	uint32_t bpf; unsigned blocks;
+	if (pf_grid(n_pixels, n_frames, &bpf, &blocks)) return -1;
+	const int wide = pf_aligned(fmt, d_src, frame_pixels, n_frames) && pf_aligned(PF_XRGB32, d_dst, n_pixels, n_frames);
+	PF_LAUNCH(k_pix_to_xrgb, (const uint8_t*)d_src, frame_pixels, agmv_hip_pixfmt_frame_bytes(fmt, frame_pixels), n_pixels, bpf, wide, d_dst);
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_pixels_from_xrgb_dev(agmv_hip_ctx* c, int fmt, const uint32_t* d_src, uint32_t n_frames, size_t n_pixels, void* d_dst, void* stream)
+{
+	if (need_ctx(c, false) || bad_pixfmt(fmt)) return -1;
+	if (n_frames == 0 || n_pixels == 0) return 0;
+	if (fmt == PF_XRGB32) {
+		CK(hipMemcpyAsync(d_dst, d_src, (size_t)n_frames * n_pixels * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+		return 0;
+	}
+	uint32_t bpf; unsigned blocks;
+	if (pf_grid(n_pixels, n_frames, &bpf, &blocks)) return -1;
+	const int wide = pf_aligned(fmt, d_dst, n_pixels, n_frames) && pf_aligned(PF_XRGB32, d_src, n_pixels, n_frames);
+	PF_LAUNCH(k_pix_from_xrgb, d_src, n_pixels, agmv_hip_pixfmt_frame_bytes(fmt, n_pixels), bpf, wide, (uint8_t*)d_dst);
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_gather_fmt_dev(agmv_hip_ctx* c, int fmt, const void* d_src, size_t src_frame_pixels, uint32_t n_frames, const uint32_t* d_index,
+                                       size_t n_out, uint32_t* d_dst, void* stream)
+{
+	if (need_ctx(c, false) || bad_pixfmt(fmt)) return -1;
+	if (fmt == PF_XRGB32) return agmv_hip_gather_dev(c, (const uint32_t*)d_src, src_frame_pixels, n_frames, d_index, n_out, d_dst, stream);
+	if (n_frames == 0 || n_out == 0) return 0;
+	if (n_out > ((size_t)1 << 39)) { snprintf(g_err, sizeof(g_err), "agmv_hip: gather table too long"); return -1; }
+	hipLaunchKernelGGL(k_gather_fmt, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_src, fmt, src_frame_pixels,
+	                   agmv_hip_pixfmt_frame_bytes(fmt, src_frame_pixels), n_frames, d_index, n_out, d_dst);
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_histogram_fmt_dev(agmv_hip_ctx* c, int fmt, const void* d_src, size_t frame_pixels, uint32_t n_frames, size_t n_pixels, int quality,
+                                          uint32_t* d_hist, void* stream)
+{
+	if (need_ctx(c, false) || bad_pixfmt(fmt)) return -1;
+	if (n_pixels > frame_pixels) { snprintf(g_err, sizeof(g_err), "agmv_hip: n_pixels %zu > frame_pixels %zu", n_pixels, frame_pixels); return -1; }
+	if (n_frames == 0 || n_pixels == 0) return 0;
+	if (fmt == PF_XRGB32) {
+		const uint32_t* d_pix = (const uint32_t*)d_src;
+		if (n_pixels == frame_pixels) return agmv_hip_histogram_dev(c, d_pix, (size_t)n_frames * frame_pixels, quality, d_hist, stream);   // one run of pixels
+		for (uint32_t f = 0; f < n_frames; f++) if (agmv_hip_histogram_dev(c, d_pix + (size_t)f * frame_pixels, n_pixels, quality, d_hist, stream)) return -1;
+		return 0;
+	}
+	uint32_t bpf; unsigned blocks;
+	if (pf_grid(n_pixels, n_frames, &bpf, &blocks)) return -1;
+	const int wide = pf_aligned(fmt, d_src, frame_pixels, n_frames);
+	PF_LAUNCH(k_histogram_fmt, (const uint8_t*)d_src, frame_pixels, agmv_hip_pixfmt_frame_bytes(fmt, frame_pixels), n_pixels, bpf, wide, quality, d_hist);
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_similarity_fmt_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t n_frames, size_t n_pixels, uint32_t* d_counts, void* stream)
+{
+	if (need_ctx(c, false) || bad_pixfmt(fmt)) return -1;
+	if (fmt == PF_XRGB32) return agmv_hip_similarity_dev(c, (const uint32_t*)d_src, n_frames, n_pixels, d_counts, stream);
+	if (n_pixels == 0 || n_pixels > 0xFFFFFFFFu) { snprintf(g_err, sizeof(g_err), "agmv_hip: similarity needs 1 .. 2^32 - 1 pixels per frame"); return -1; }
+	if (n_frames < 2) return 0;                                // no pair
+	const unsigned blocks = (unsigned)((n_pixels + 4095) / 4096);    // 256 lanes x 16 pixels
+	CK(hipMemsetAsync(d_counts, 0, 4 * (size_t)(n_frames - 1), (hipStream_t)stream));
+	const int vec = (n_pixels & 15) == 0 && ((uintptr_t)d_src & 15) == 0;
+	const size_t frame_bytes = agmv_hip_pixfmt_frame_bytes(fmt, n_pixels);
+	switch (fmt) {                                             // (the grey is a sum: the two 3-byte orders are one kernel)
+	case PF_RGB24: case PF_BGR24:
+		hipLaunchKernelGGL(k_similarity_fmt<PF_RGB24>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_src, n_frames, n_pixels, frame_bytes, vec, d_counts);
+		break;
+	case PF_RGBA32:
+		hipLaunchKernelGGL(k_similarity_fmt<PF_RGBA32>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_src, n_frames, n_pixels, frame_bytes, vec, d_counts);
+		break;
+	default:
+		hipLaunchKernelGGL(k_similarity_fmt<PF_RGB8P>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_src, n_frames, n_pixels, frame_bytes, vec, d_counts);
+		break;
+	}
 	CK(hipGetLastError());
 	return 0;
 }

@@ -20,7 +20,8 @@
  * Both pipelines have a second end for frames that live in GPU memory (AGMV_EncodeFramesDev / AGMV_DecodeFramesDev): a device
  * SOURCE of the encoder (agmv_source: no BMP parse, no pinned staging, no upload -- the workers copy, gather or interpolate
  * from the caller's clip) and a device SINK of the decoder (the worker decodes into the caller's buffer: no D2H, no BMP export).
- * Everything between the two ends is the same code.
+ * Both ends carry a pixel format (AGMV_PIXFMT): the kernels that touch the caller's clip read or write it in that layout, and
+ * only the worker's batch buffers hold packed 0x00RRGGBB pixels.  Everything between the two ends is the same code.
  *
  * Plain C + pthreads; everything that touches the GPU goes through include/agmv_hip.h.  No CPU fallback: a GPU failure in
  * the void encoders aborts with a message, in the int-returning decoders it is returned.
@@ -328,19 +329,19 @@ static void download_rows(eworker* wk, ebatch* b, const uint8_t* d_rows, size_t 
 	if (agmv_hip_stream_sync(wk->ctx, wk->stream)) agmv_die("row download");
 }
 
-/* a device source: where its frame `idx` is, and that frame as the encoder sees it into dst on the worker's stream (a copy, or
-   with a scale the gather through the table) */
-static const uint32_t* src_frame(const agmv_seq* s, long idx)
+/* a device source: where its frame `idx` is, and that frame as the encoder sees it into dst on the worker's stream (converted
+   from the source's layout -- for XRGB32 a copy --, or with a scale gathered through the table) */
+static const void* src_frame(const agmv_seq* s, long idx)
 {
-	return s->src.d_frames + (size_t)(idx - s->src.first) * s->src.src_w * s->src.src_h;
+	return (const u8*)s->src.d_frames + (size_t)(idx - s->src.first) * agmv_hip_pixfmt_frame_bytes(s->src.fmt, (size_t)s->src.src_w * s->src.src_h);
 }
 
 static int place_frame(eworker* wk, long idx, uint32_t* dst)
 {
 	agmv_seq* s = wk->s;
-	if (s->d_index)
-		return agmv_hip_gather_dev(wk->ctx, src_frame(s, idx), (size_t)s->src.src_w * s->src.src_h, 1, s->d_index, s->npx, dst, wk->stream);
-	return agmv_hip_memcpy_async(wk->ctx, dst, src_frame(s, idx), s->npx * 4, 2, wk->stream);
+	const size_t fpx = (size_t)s->src.src_w * s->src.src_h;
+	if (s->d_index) return agmv_hip_gather_fmt_dev(wk->ctx, s->src.fmt, src_frame(s, idx), fpx, 1, s->d_index, s->npx, dst, wk->stream);
+	return agmv_hip_pixels_to_xrgb_dev(wk->ctx, s->src.fmt, src_frame(s, idx), fpx, 1, s->npx, dst, wk->stream);
 }
 
 /* one GPU worker: its batches are id = idx, idx + nworkers, ... in order */
@@ -366,11 +367,12 @@ static void* eworker_main(void* p)
 			if (s->src.d_frames) {                             /* the frames are on this device already: no upload */
 				if (b->srcB[k] < 0) {
 					if (place_frame(wk, b->srcA[k], dst)) agmv_die("frame copy");
-				} else if (s->d_index) {
+				} else if (s->d_index || s->src.fmt != AGMV_PIXFMT_XRGB32) {        /* the two sources as packed frames first */
 					if (place_frame(wk, b->srcA[k], wk->d_tmp[0]) || place_frame(wk, b->srcB[k], wk->d_tmp[1]) ||
 					    agmv_hip_interp_dev(wk->ctx, dst, wk->d_tmp[0], wk->d_tmp[1], s->npx, wk->stream))
 						agmv_die("frame gather / interp");
-				} else if (agmv_hip_interp_dev(wk->ctx, dst, src_frame(s, b->srcA[k]), src_frame(s, b->srcB[k]), s->npx, wk->stream))
+				} else if (agmv_hip_interp_dev(wk->ctx, dst, (const uint32_t*)src_frame(s, b->srcA[k]), (const uint32_t*)src_frame(s, b->srcB[k]), s->npx,
+				                               wk->stream))
 					agmv_die("frame interp");
 			} else if (b->srcB[k] < 0) {
 				if (agmv_hip_memcpy_async(wk->ctx, dst, src, s->npx * 4, 0, wk->stream)) agmv_die("frame upload");
@@ -696,14 +698,10 @@ void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start,
 	void* stream = agmv_hip_stream_create(ctx);
 	if (src->d_frames) {                                       /* the clip is resident: no parse, no ring, no upload */
 		const size_t fpx = (size_t)src->src_w * src->src_h, px = fpx < size ? fpx : size;
-		const uint32_t* d_first = src->d_frames + (size_t)((long)start - src->first) * fpx;
-		u32 k;
+		const u8* d_first = (const u8*)src->d_frames + (size_t)((long)start - src->first) * agmv_hip_pixfmt_frame_bytes(src->fmt, fpx);
 		if ((long)start < src->first || (long)end >= src->first + (long)src->n_frames) agmv_die("internal: frame outside the device clip");
 		if (!d_hist || !stream || agmv_hip_memset_async(ctx, d_hist, 0, 4u << 19, stream)) agmv_die("histogram");
-		if (px == fpx) {                                       /* whole frames: the clip is one run of pixels */
-			if (agmv_hip_histogram_dev(ctx, d_first, (size_t)n * fpx, quality, d_hist, stream)) agmv_die("histogram");
-		} else
-			for (k = 0; k < n; k++) if (agmv_hip_histogram_dev(ctx, d_first + (size_t)k * fpx, px, quality, d_hist, stream)) agmv_die("histogram");
+		if (agmv_hip_histogram_fmt_dev(ctx, src->fmt, d_first, fpx, n, px, quality, d_hist, stream)) agmv_die("histogram");
 		if (agmv_hip_memcpy_async(ctx, hist, d_hist, 4u << 19, 1, stream) || agmv_hip_stream_sync(ctx, stream)) agmv_die("histogram download");
 		agmv_hip_free_on(ctx, d_hist);
 		agmv_hip_stream_destroy(ctx, stream);
@@ -784,7 +782,8 @@ typedef struct dpipe {
 	agmv_pool* pool;
 	pthread_t th;
 	uint8_t* d_bits; uint32_t *d_bpos, *d_nent, *d_out[2], *d_iframe;
-	uint32_t* d_dst;                       /* the sink: NULL = BMP export through d_out / h_out, else the caller's device frames */
+	void* d_dst;                           /* the sink: NULL = BMP export through d_out / h_out, else the caller's device frames */
+	int fmt;                               /* ... in this AGMV_PIXFMT: XRGB32 is decoded in place, any other through d_out */
 } dpipe;
 
 typedef struct savearg { dpipe* d; dbatch* b; unsigned k; } savearg;
@@ -819,9 +818,11 @@ static void* dworker_main(void* p)
 		while (!(id < d->nfilled) && !d->closing) pthread_cond_wait(&d->cv, &d->mu);
 		if (id >= d->nfilled) { pthread_mutex_unlock(&d->mu); break; }
 		pthread_mutex_unlock(&d->mu);
-		/* with a sink the batch is decoded straight into its place, and the frame before it is the one before it there */
-		out = d->d_dst ? d->d_dst + (size_t)b->first * d->npx : d->d_out[id & 1];
-		prev = !have_state ? NULL : d->d_dst ? out - d->npx : d->d_out[(id - 1) & 1] + (size_t)(prev_n - 1) * d->npx;
+		/* with a packed sink the batch is decoded straight into its place, and the frame before it is the one before it there;
+		   a sink in another layout takes the batch from the double buffer, where the decoder's state stays */
+		const int direct = d->d_dst && d->fmt == AGMV_PIXFMT_XRGB32;
+		out = direct ? (uint32_t*)d->d_dst + (size_t)b->first * d->npx : d->d_out[id & 1];
+		prev = !have_state ? NULL : direct ? out - d->npx : d->d_out[(id - 1) & 1] + (size_t)(prev_n - 1) * d->npx;
 		if (b->d_slab) {                       /* the LZ stage left the rows on the device: wait for their commit, on the device */
 			if (agmv_hip_stream_wait_event(d->ctx, d->stream, b->ready)) goto fail;
 		} else if (agmv_hip_memcpy_async(d->ctx, d->d_bits, b->h_slab, d->stride * b->n, 0, d->stream) ||
@@ -835,6 +836,9 @@ static void* dworker_main(void* p)
 		for (k = 0; k < b->n; k++) if (((b->first + k) & 3u) == 0) last_i = (int)k;
 		if (!have_state && last_i < 0 && agmv_hip_memset_async(d->ctx, d->d_iframe, 0, d->npx * 4, d->stream)) goto fail;
 		if (last_i >= 0 && agmv_hip_memcpy_async(d->ctx, d->d_iframe, out + (size_t)last_i * d->npx, d->npx * 4, 2, d->stream)) goto fail;
+		if (d->d_dst && !direct &&
+		    agmv_hip_pixels_from_xrgb_dev(d->ctx, d->fmt, out, b->n, d->npx, (u8*)d->d_dst + (size_t)b->first * agmv_hip_pixfmt_frame_bytes(d->fmt, d->npx), d->stream))
+			goto fail;
 		if ((!d->d_dst && agmv_hip_memcpy_async(d->ctx, b->h_out, out, d->npx * 4 * b->n, 1, d->stream)) || agmv_hip_stream_sync(d->ctx, d->stream)) goto fail;
 		have_state = 1;
 		prev_n = b->n;
@@ -1021,11 +1025,13 @@ static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, dchunk* c, const u8* fil
    The LZ stage of a batch (between locate_chunks and cut_batch) runs on the pool, one frame per task, or with
    AGMV_LZ_DECODE_DEVICE=1 on the GPU (dlz_batch).  The bytes behind bpos that the block parser may read on an over-run are
    those of the reference's ONE persistent buffer: the host stage takes them from `persist` in frame order, which then
-   receives the frame.  The frames go to d_dst (device memory of ctx's device, frame k of the file at d_dst + k * w * h) or, with
-   d_dst NULL, to quick_export_<*export_count + 1 ...>.bmp; *export_count advances by the frames decoded either way. */
+   receives the frame.  The frames go to d_dst (device memory of ctx's device, frame k of the file as a frame of the AGMV_PIXFMT
+   `fmt` at its place there) or, with d_dst NULL, to quick_export_<*export_count + 1 ...>.bmp; *export_count advances by the
+   frames decoded either way. */
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
-                       int has_audio, unsigned cap_frames, unsigned threads, uint32_t* d_dst, unsigned long* export_count)
+                       int has_audio, unsigned cap_frames, unsigned threads, void* d_dst, int fmt, unsigned long* export_count)
 {
+	const int direct = d_dst && fmt == AGMV_PIXFMT_XRGB32;     /* decoded in place: no double buffer */
 	dpipe d;
 	dlz z;
 	const char* lzv = getenv("AGMV_LZ_DECODE_DEVICE");     /* opt-in: the LZ stage on the GPU (read when a decode starts) */
@@ -1040,7 +1046,7 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	memset(&d, 0, sizeof(d));
 	memset(&z, 0, sizeof(z));
 	d.ctx = ctx; d.w = w; d.h = h; d.npx = npx; d.stride = (cap + 255) & ~(size_t)255;
-	d.cap = cap_frames; d.nslots = 3; d.d_dst = d_dst;
+	d.cap = cap_frames; d.nslots = 3; d.d_dst = d_dst; d.fmt = fmt;
 	pthread_mutex_init(&d.mu, NULL);
 	pthread_cond_init(&d.cv, NULL);
 	d.slot = (dbatch*)calloc(d.nslots, sizeof(dbatch));
@@ -1049,10 +1055,10 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	d.d_bits = lz_dev ? NULL : (uint8_t*)agmv_hip_malloc_on(ctx, d.stride * d.cap);      /* (the host LZ stage's upload slab) */
 	d.d_bpos = lz_dev ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
 	d.d_nent = (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
-	d.d_out[0] = d_dst ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
-	d.d_out[1] = d_dst ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
+	d.d_out[0] = direct ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
+	d.d_out[1] = direct ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
 	d.d_iframe = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4);
-	if (!persist || !chunks || (!lz_dev && !jobs) || !d.stream || (!lz_dev && (!d.d_bits || !d.d_bpos)) || !d.d_nent || (!d_dst && (!d.d_out[0] || !d.d_out[1])) || !d.d_iframe) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+	if (!persist || !chunks || (!lz_dev && !jobs) || !d.stream || (!lz_dev && (!d.d_bits || !d.d_bpos)) || !d.d_nent || (!direct && (!d.d_out[0] || !d.d_out[1])) || !d.d_iframe) { rc = MEMORY_CORRUPTION_ERR; goto out; }
 	if (lz_dev && dlz_open(&z, ctx, d.cap, cap)) { rc = MEMORY_CORRUPTION_ERR; goto out; }
 	for (i = 0; i < d.nslots; i++) {
 		if (lz_dev) {                                          /* the rows live on the device only */

@@ -17,10 +17,12 @@ uint32_t* agmv_source_index(uint32_t sw, uint32_t sh, int scale_w, int scale_h, 
 void agmv_load_source(const char* dir, const char* base, long idx, int scale_w, int scale_h, uint32_t w, uint32_t h, uint32_t* dst);
 
 /* where the frames of a sequence encode come from: the numbered BMP files dir/base<idx>.bmp, or (d_frames != NULL) a clip of
-   n_frames frames of src_w x src_h 0x00RRGGBB pixels in the memory of device `device`, its first frame numbered `first` */
+   n_frames frames of src_w x src_h pixels in the layout `fmt` (an AGMV_PIXFMT) in the memory of device `device`, its first
+   frame numbered `first` */
 typedef struct agmv_source {
 	const char *dir, *base;
-	const uint32_t* d_frames;
+	const void* d_frames;
+	int fmt;
 	uint32_t src_w, src_h, n_frames;
 	long first;
 	int device;
@@ -40,7 +42,7 @@ void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start,
                            unsigned threads, uint32_t* hist);
 
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
-                       int has_audio, unsigned cap_frames, unsigned threads, uint32_t* d_dst, unsigned long* export_count);
+                       int has_audio, unsigned cap_frames, unsigned threads, void* d_dst, int fmt, unsigned long* export_count);
 
 /* agmv_codec.c */
 void agmv_write_frame_chunk(FILE* f, u32 frame_no, u32 usize, u32 csize, const u8* payload);

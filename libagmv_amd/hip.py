@@ -30,6 +30,8 @@ ABI_SYMBOLS = [
     "agmv_hip_lz_decode_frames_dev", "agmv_hip_lz_decode_commit_dev", "agmv_hip_lz_decode_fallback_frames",
     "agmv_hip_lz_decode_frames", "agmv_hip_lz_decode_frames_sized_dev",
     "agmv_hip_event_create", "agmv_hip_event_destroy", "agmv_hip_event_record", "agmv_hip_stream_wait_event",
+    "agmv_hip_pixfmt_frame_bytes", "agmv_hip_pixels_to_xrgb_dev", "agmv_hip_pixels_from_xrgb_dev", "agmv_hip_gather_fmt_dev",
+    "agmv_hip_histogram_fmt_dev", "agmv_hip_similarity_fmt_dev",
 ]
 
 
@@ -134,6 +136,17 @@ def load_library(path=None):
     L.agmv_hip_similarity_dev.restype = C.c_int
     L.agmv_hip_gather_dev.argtypes = [vp, vp, sz, u32, vp, sz, vp, vp]
     L.agmv_hip_gather_dev.restype = C.c_int
+    if path is None or hasattr(L, "agmv_hip_pixels_to_xrgb_dev"):     # (older builds under tools/variants/ lack them)
+        L.agmv_hip_pixfmt_frame_bytes.restype = sz
+        L.agmv_hip_pixfmt_frame_bytes.argtypes = [C.c_int, sz]
+        L.agmv_hip_pixels_to_xrgb_dev.argtypes = [vp, C.c_int, vp, sz, u32, sz, vp, vp]
+        L.agmv_hip_pixels_from_xrgb_dev.argtypes = [vp, C.c_int, vp, u32, sz, vp, vp]
+        L.agmv_hip_gather_fmt_dev.argtypes = [vp, C.c_int, vp, sz, u32, vp, sz, vp, vp]
+        L.agmv_hip_histogram_fmt_dev.argtypes = [vp, C.c_int, vp, sz, u32, sz, C.c_int, vp, vp]
+        L.agmv_hip_similarity_fmt_dev.argtypes = [vp, C.c_int, vp, u32, sz, vp, vp]
+        for f in (L.agmv_hip_pixels_to_xrgb_dev, L.agmv_hip_pixels_from_xrgb_dev, L.agmv_hip_gather_fmt_dev, L.agmv_hip_histogram_fmt_dev,
+                  L.agmv_hip_similarity_fmt_dev):
+            f.restype = C.c_int
     L.agmv_hip_check.argtypes = [vp, vp]
     L.agmv_hip_enable_timing.argtypes = [vp, C.c_int]
     L.agmv_hip_enable_timing.restype = C.c_int
@@ -149,6 +162,18 @@ def load_library(path=None):
         f.restype = C.c_int
     _libs[p] = L
     return L
+
+
+# AGMV_PIXFMT of include/agmv.h: name -> value
+PIXFMT = {"xrgb32": 1, "rgb24": 2, "bgr24": 3, "rgba32": 4, "rgb8p": 5}
+
+
+def pixfmt(fmt):
+    """the AGMV_PIXFMT value of a name or of a value"""
+    v = PIXFMT.get(fmt, fmt)
+    if v not in PIXFMT.values():
+        raise ValueError("fmt: one of %s is needed, got %r" % (", ".join(sorted(PIXFMT)), fmt))
+    return v
 
 
 def _np_ptr(a):
@@ -600,6 +625,80 @@ class AgmvHip:
         self._ck(self.L.agmv_hip_gather_dev(self.ctx, src.data_ptr(), src.shape[1], n, index.data_ptr(), n_out, out.data_ptr(),
                                             self._stream()))
         return out
+
+    # ------------------------------------------------------------------ clips in the caller's pixel layout
+    # A clip in a byte format is a CUDA uint8 tensor of any shape holding whole frames back to back (it may be a view at any byte
+    # offset of an allocation); packed pixels are int32 storage as everywhere else.
+    def _check_clip(self, name, fmt, t, n_bytes):
+        import torch
+        fmt = pixfmt(fmt)
+        dt = torch.int32 if fmt == 1 else torch.uint8
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() * t.element_size() >= n_bytes):
+            raise ValueError("%s: a contiguous CUDA %s tensor of >= %d bytes is needed, got %s %s on %s"
+                             % (name, dt, n_bytes, t.dtype, tuple(t.shape), t.device))
+        return fmt
+
+    def pixfmt_frame_bytes(self, fmt, n_pixels):
+        return self.L.agmv_hip_pixfmt_frame_bytes(pixfmt(fmt), n_pixels)
+
+    def pixels_to_xrgb_dev(self, fmt, src, frame_pixels, n_frames, n_pixels=None, out=None):
+        """src: clip of n_frames frames of frame_pixels in fmt -> int32 [n_frames, n_pixels] of 0x00RRGGBB (the first n_pixels of each)"""
+        import torch
+        n_pixels = frame_pixels if n_pixels is None else n_pixels
+        fmt = self._check_clip("pixels_to_xrgb_dev: src", fmt, src, n_frames * self.pixfmt_frame_bytes(fmt, frame_pixels))
+        if out is None:
+            out = torch.empty((n_frames, n_pixels), dtype=torch.int32, device=src.device)
+        _check_vec("pixels_to_xrgb_dev: out", out, n_frames * n_pixels)
+        self._ck(self.L.agmv_hip_pixels_to_xrgb_dev(self.ctx, fmt, src.data_ptr(), frame_pixels, n_frames, n_pixels, out.data_ptr(), self._stream()))
+        return out
+
+    def pixels_from_xrgb_dev(self, fmt, src, out=None):
+        """src: int32 [n_frames, n_pixels] -> the clip in fmt (uint8 [n_frames, frame bytes]; int32 [n_frames, n_pixels] for xrgb32)"""
+        import torch
+        if not (src.is_cuda and src.dtype == torch.int32 and src.dim() == 2 and src.is_contiguous()):
+            raise ValueError("pixels_from_xrgb_dev: a contiguous CUDA int32 tensor [n_frames, n_pixels] is needed")
+        n, npx = src.shape
+        fb = self.pixfmt_frame_bytes(fmt, npx)
+        if out is None:
+            out = torch.empty((n, npx), dtype=torch.int32, device=src.device) if pixfmt(fmt) == 1 else torch.empty((n, fb), dtype=torch.uint8, device=src.device)
+        fmt = self._check_clip("pixels_from_xrgb_dev: out", fmt, out, n * fb)
+        self._ck(self.L.agmv_hip_pixels_from_xrgb_dev(self.ctx, fmt, src.data_ptr(), n, npx, out.data_ptr(), self._stream()))
+        return out
+
+    def gather_fmt_dev(self, fmt, src, src_frame_pixels, n_frames, index, out=None):
+        """gather_dev on a clip of n_frames frames of src_frame_pixels in fmt; returns int32 [n_frames, n_out]"""
+        import torch
+        fmt = self._check_clip("gather_fmt_dev: src", fmt, src, n_frames * self.pixfmt_frame_bytes(fmt, src_frame_pixels))
+        _check_vec("gather_fmt_dev: index", index, 1)
+        n_out = index.numel()
+        if out is None:
+            out = torch.empty((n_frames, n_out), dtype=torch.int32, device=src.device)
+        _check_vec("gather_fmt_dev: out", out, n_frames * n_out)
+        self._ck(self.L.agmv_hip_gather_fmt_dev(self.ctx, fmt, src.data_ptr(), src_frame_pixels, n_frames, index.data_ptr(), n_out, out.data_ptr(),
+                                                self._stream()))
+        return out
+
+    def histogram_fmt_dev(self, fmt, src, frame_pixels, n_frames, n_pixels=None, quality=1, hist=None):
+        """histogram_dev over the first n_pixels of each frame of a clip in fmt; `hist` is added to"""
+        import torch
+        n_pixels = frame_pixels if n_pixels is None else n_pixels
+        fmt = self._check_clip("histogram_fmt_dev: src", fmt, src, n_frames * self.pixfmt_frame_bytes(fmt, frame_pixels))
+        if hist is None:
+            hist = torch.zeros(1 << 19, dtype=torch.int32, device=src.device)
+        _check_vec("histogram_fmt_dev: hist", hist, 1 << 19)
+        self._ck(self.L.agmv_hip_histogram_fmt_dev(self.ctx, fmt, src.data_ptr(), frame_pixels, n_frames, n_pixels, quality, hist.data_ptr(),
+                                                   self._stream()))
+        return hist
+
+    def similarity_fmt_dev(self, fmt, src, n_frames, n_pixels, counts=None):
+        """similarity_dev on a clip of n_frames frames of n_pixels in fmt; `counts` [n_frames - 1] is overwritten"""
+        import torch
+        fmt = self._check_clip("similarity_fmt_dev: src", fmt, src, n_frames * self.pixfmt_frame_bytes(fmt, n_pixels))
+        if counts is None:
+            counts = torch.empty(max(n_frames - 1, 0), dtype=torch.int32, device=src.device)
+        _check_vec("similarity_fmt_dev: counts", counts, n_frames - 1)
+        self._ck(self.L.agmv_hip_similarity_fmt_dev(self.ctx, fmt, src.data_ptr(), n_frames, n_pixels, counts.data_ptr(), self._stream()))
+        return counts
 
     # ------------------------------------------------------------------ host-buffer path
     def encode_host(self, frames, first_frame_count=0, ientries=None):
