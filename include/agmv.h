@@ -319,6 +319,36 @@ int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frame
 typedef enum AGMV_PIXFMT {
 	AGMV_PIXFMT_XRGB32 = 1, AGMV_PIXFMT_RGB24 = 2, AGMV_PIXFMT_BGR24 = 3, AGMV_PIXFMT_RGBA32 = 4, AGMV_PIXFMT_RGB8P = 5
 } AGMV_PIXFMT;
+
+/* 8-bit YUV 4:2:0, what video decoders deliver and video encoders take.  These two values continue AGMV_PIXFMT (6 stays an
+   unknown format) and are passed in the same `fmt` argument, OR-ed with the two flags below.  A frame is w x h pixels, with
+   cw = (w + 1) / 2 and ch = (h + 1) / 2 in integers; frames lie back to back, w * h + 2 * cw * ch bytes each
+   (agmv_hip_yuv_frame_bytes of include/agmv_hip.h), and no alignment is required.
+     AGMV_PIXFMT_NV12  [h][w] bytes Y, then [ch][cw][2] bytes U, V
+     AGMV_PIXFMT_I420  [h][w] bytes Y, then [ch][cw] bytes U, then [ch][cw] bytes V
+   Flags: AGMV_YUV_BT709 (default BT.601) and AGMV_YUV_FULL_RANGE (default limited range).  A flag on the formats 1 .. 5, any
+   other bit above 0xFF and any other base value is an unknown format: -1 before a file is created or a device is opened.
+
+   Reading.  Pixel (x, y) takes Y at (x, y) and U, V at (x >> 1, y >> 1): nearest chroma, no interpolation.  With
+   C = ky * (Y - yo), D = U - 128, E = V - 128 in 32-bit signed integers and >> an arithmetic shift,
+     R = clip8((C + rv * E + 128) >> 8),  G = clip8((C - gu * D - gv * E + 128) >> 8),  B = clip8((C + bu * D + 128) >> 8)
+                        ky   yo   rv   gu   gv   bu
+     BT.601 limited    298   16  409  100  208  516
+     BT.709 limited    298   16  459   55  136  541
+     BT.601 full       256    0  359   88  183  454
+     BT.709 full       256    0  403   48  120  475
+   Writing (the decoder's sink).  Y = clip8(((yr * R + yg * G + yb * B + 128) >> 8) + yo) per pixel.  For each chroma sample take
+   the pixels of its 2 x 2 block that exist (cnt = 4, 2 or 1 at odd edges), average each of R, G, B over them as
+   (sum + (cnt >> 1)) / cnt, then U = clip8(((ur * R + ug * G + ub * B + 128) >> 8) + 128), and V likewise.
+                       yr  yg  yb   yo     ur   ug   ub     vr    vg   vb
+     BT.601 limited    66 129  25   16    -38  -74  112    112   -94  -18
+     BT.709 limited    47 157  16   16    -26  -86  112    112  -102  -10
+     BT.601 full       77 150  29    0    -43  -85  128    128  -107  -21
+     BT.709 full       54 183  19    0    -29  -99  128    128  -116  -12
+   Every chroma row sums to 0, so greys stay at U = V = 128.  A YUV clip stands for the XRGB32 clip that this reading gives: the
+   palette, the adaptive schedule's decisions, the GBA / NDS scaling and the encoded file are those of that clip, byte for byte,
+   and a file decoded into a YUV sink is the XRGB32 decode with the writing rule applied. */
+enum { AGMV_PIXFMT_NV12 = 16, AGMV_PIXFMT_I420 = 17, AGMV_YUV_BT709 = 0x100, AGMV_YUV_FULL_RANGE = 0x200 };
 int AGMV_EncodeFramesFmtDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 width, u32 height,
                             u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression,
                             AGMV_SCHEDULE schedule);

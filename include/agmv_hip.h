@@ -351,6 +351,35 @@ int agmv_hip_histogram_fmt_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, si
 int agmv_hip_similarity_fmt_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, uint32_t n_frames, size_t n_pixels, uint32_t* d_counts,
                                 void* stream);
 
+/* -- clips in 8-bit YUV 4:2:0 --------------------------------------------------------------------
+ * `fmt` is AGMV_PIXFMT_NV12 (16) or AGMV_PIXFMT_I420 (17) of include/agmv.h, which defines the layouts and the arithmetic,
+ * OR-ed with AGMV_YUV_BT709 (0x100) and / or AGMV_YUV_FULL_RANGE (0x200).  The chroma of a pixel depends on its x and y, so
+ * these take the frame's w and h where the functions above take a pixel count.  Frames lie back to back, no alignment is needed
+ * (w a multiple of 16 and a clip on a 16-byte boundary are read and written in patches of 16 x 2 pixels with 16-byte accesses,
+ * anything else byte by byte).  Any other format or flag is an error return.
+ * agmv_hip_yuv_frame_bytes:    w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2); 0 for anything that is not one of the two formats.
+ *                              Host only: needs no context and no GPU.
+ * agmv_hip_yuv_to_xrgb_dev:    d_dst[f][k] = pixel k (raster order) of frame f as 0x00RRGGBB, k < n_pixels <= w * h;
+ *                              destination rows n_pixels words.
+ * agmv_hip_yuv_from_xrgb_dev:  whole frames of w * h packed pixels (bits >= 24 ignored) written as YUV; no byte outside the
+ *                              n_frames destination frames is written.  (The decoder's device sink.)
+ * agmv_hip_yuv_gather_dev:     agmv_hip_gather_dev reading a YUV source: d_index holds y * w + x (agmv_source_index); only the
+ *                              pixels the table names, and their chroma, are read.
+ * agmv_hip_yuv_histogram_dev:  agmv_hip_histogram_dev over the first n_pixels of each of n_frames frames (d_hist is added to).
+ * agmv_hip_yuv_similarity_dev: agmv_hip_similarity_dev on the clip: the same counts, each frame read once, d_counts
+ *                              overwritten. */
+size_t agmv_hip_yuv_frame_bytes(int fmt, uint32_t w, uint32_t h);
+int agmv_hip_yuv_to_xrgb_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames, size_t n_pixels,
+                             uint32_t* d_dst, void* stream);
+int agmv_hip_yuv_from_xrgb_dev(agmv_hip_ctx* ctx, int fmt, const uint32_t* d_src, uint32_t w, uint32_t h, uint32_t n_frames, void* d_dst,
+                               void* stream);
+int agmv_hip_yuv_gather_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames,
+                            const uint32_t* d_index, size_t n_out, uint32_t* d_dst, void* stream);
+int agmv_hip_yuv_histogram_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames, size_t n_pixels,
+                               int quality, uint32_t* d_hist, void* stream);
+int agmv_hip_yuv_similarity_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames,
+                                uint32_t* d_counts, void* stream);
+
 /* optional timing: when enabled the library records HIP events on the caller's stream around its three kernel
    groups; agmv_hip_last_kernel_ms(which) returns the last launch's duration in ms (0 = k_encode, 1 = the parser
    kernels, 2 = k_decode + k_fixup, 3 = the whole of agmv_hip_parse_decode_frames_dev / agmv_hip_decode_bitstreams_dev), or a negative value if

@@ -538,12 +538,15 @@ static void similarity_open(similarity* m, const agmv_source* src, AGMV* a, AGMV
 			d_index = (uint32_t*)agmv_hip_malloc_on(c, npx * 4);
 			d_scaled = (uint32_t*)agmv_hip_malloc_on(c, npx * 4 * n);
 			if (!d_index || !d_scaled || agmv_hip_memcpy_async(c, d_index, index, npx * 4, 0, NULL) ||
-			    agmv_hip_gather_fmt_dev(c, src->fmt, src->d_frames, (size_t)src->src_w * src->src_h, n, d_index, npx, d_scaled, NULL))
+			    (AGMV_FMT_IS_YUV(src->fmt) ? agmv_hip_yuv_gather_dev(c, src->fmt, src->d_frames, src->src_w, src->src_h, n, d_index, npx, d_scaled, NULL)
+			                               : agmv_hip_gather_fmt_dev(c, src->fmt, src->d_frames, (size_t)src->src_w * src->src_h, n, d_index, npx, d_scaled, NULL)))
 				agmv_die("frame gather");
 			d_clip = d_scaled;
 			m->tmp = index;                                    /* (freed by similarity_close, behind the synchronisation below) */
 		}
-		if ((d_clip ? agmv_hip_similarity_dev(c, d_clip, n, npx, d_counts, NULL) : agmv_hip_similarity_fmt_dev(c, src->fmt, src->d_frames, n, npx, d_counts, NULL)) ||
+		if ((d_clip ? agmv_hip_similarity_dev(c, d_clip, n, npx, d_counts, NULL) :
+		     AGMV_FMT_IS_YUV(src->fmt) ? agmv_hip_yuv_similarity_dev(c, src->fmt, src->d_frames, src->src_w, src->src_h, n, d_counts, NULL) :
+		                                 agmv_hip_similarity_fmt_dev(c, src->fmt, src->d_frames, n, npx, d_counts, NULL)) ||
 		    (n > 1 && agmv_hip_memcpy_async(c, m->counts, d_counts, 4 * (size_t)(n - 1), 1, NULL)) || agmv_hip_stream_sync(c, NULL))
 			agmv_die("frame similarity");
 		agmv_hip_free_on(c, d_counts); agmv_hip_free_on(c, d_scaled); agmv_hip_free_on(c, d_index);
@@ -669,6 +672,14 @@ void AGMV_EncodeVideo(const char* filename, const char* dir, const char* basenam
 	                start_frame, end_frame, width, height, opt, quality, compression);
 }
 
+/* an AGMV_PIXFMT the sequence drivers take: a byte layout without flags, or a YUV 4:2:0 layout with its two flags at most */
+static int known_pixfmt(int fmt)
+{
+	const int base = fmt & 0xFF, flags = fmt & ~0xFF;
+	if (base == AGMV_PIXFMT_NV12 || base == AGMV_PIXFMT_I420) return (flags & ~(AGMV_YUV_BT709 | AGMV_YUV_FULL_RANGE)) == 0;
+	return flags == 0 && base >= AGMV_PIXFMT_XRGB32 && base <= AGMV_PIXFMT_RGB8P;
+}
+
 /* The same three files from frames in device memory: num_of_frames frames of width x height pixels in the layout `fmt`, on the
    device of this library's context.  What the BMP drivers write for f1.bmp .. f<n>.bmp holding these frames, byte for byte (for
    AGMV_SCHEDULE_ADAPTIVE with AGMV_EncodeVideo's CreateAGMV(n - 1, ...)); GBA_GEN_AGMV.h is not written.  Returns 0, or a
@@ -679,7 +690,7 @@ int AGMV_EncodeFramesFmtDev(const char* filename, const void* d_frames, AGMV_PIX
 	agmv_source src;
 	int sw, sh;
 	u32 least;
-	if (!filename || !d_frames || fmt < AGMV_PIXFMT_XRGB32 || fmt > AGMV_PIXFMT_RGB8P) return -1;
+	if (!known_pixfmt((int)fmt) || !filename || !d_frames) return -1;
 	if (opt < AGMV_OPT_I || opt > AGMV_OPT_NDS || quality < AGMV_HIGH_QUALITY || quality > AGMV_LOW_QUALITY ||
 	    (compression != AGMV_LZSS_COMPRESSION && compression != AGMV_LZ77_COMPRESSION) ||
 	    (schedule != AGMV_SCHEDULE_FULL && schedule != AGMV_SCHEDULE_PDIFS && schedule != AGMV_SCHEDULE_ADAPTIVE))
@@ -771,7 +782,7 @@ int AGMV_DecodeFramesFmtDev(const char* filename, void* d_frames, AGMV_PIXFMT fm
 {
 	unsigned long decoded = 0;
 	int err;
-	if (fmt < AGMV_PIXFMT_XRGB32 || fmt > AGMV_PIXFMT_RGB8P) return -1;
+	if (!known_pixfmt((int)fmt)) return -1;
 	err = filename ? decode_file(filename, AGMV_IMG_BMP, d_frames, (int)fmt, cap_frames, d_frames == NULL, info, &decoded) : FILE_NOT_FOUND_ERR;
 	return err == NO_ERR ? (int)decoded : -err;
 }

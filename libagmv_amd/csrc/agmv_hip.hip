@@ -2714,6 +2714,347 @@ template <int FMT> __global__ __launch_bounds__(256) void k_similarity_fmt(const
 	}
 }
 
+// ---- clips in 8-bit YUV 4:2:0 (AGMV_PIXFMT_NV12 = 16, AGMV_PIXFMT_I420 = 17 of include/agmv.h, which holds the definition) ----
+// A frame of w x h pixels is [h][w] bytes Y, then with cw = (w + 1) / 2, ch = (h + 1) / 2 either [ch][cw][2] bytes U,V (NV12) or
+// [ch][cw] bytes U and [ch][cw] bytes V (I420).  Pixel (x, y) takes its chroma from (x >> 1, y >> 1).  The matrix is data: six
+// (reading) or ten (writing) integers the host picks from the flags in fmt; the only template axis is the layout.  The kernels are
+// HBM streams.  Wide (w a multiple of 16, every frame on a 16-byte boundary) a lane owns a patch of 16 x 2 pixels: two 16-byte
+// luma loads and the 16 chroma bytes both rows share (I420: 8 + 8), 32 pixels.  Everything else -- another w, a clip at an odd
+// offset, the odd last row, a pixel count that ends inside a patch -- goes pixel by pixel in the same kernel.
+#define PF_NV12 16
+#define PF_I420 17
+
+typedef uint32_t pf_u32x2 __attribute__((ext_vector_type(2)));
+struct yuv_rd { int ky, yo, rv, gu, gv, bu; };
+struct yuv_wr { int yr, yg, yb, yo, ur, ug, ub, vr, vg, vb; };
+struct yuv_terms { int r, g, b; };                                 // what one chroma sample adds to its (up to) 2 x 2 pixels, rounding included
+struct yuv_raw { pf_u32x4 y0, y1, c; };                            // a patch as it lies in memory; c: 8 pairs U,V (NV12), 8 U then 8 V (I420)
+
+__device__ __forceinline__ int yuv_clip8(int v) { return min(max(v, 0), 255); }
+
+__device__ __forceinline__ yuv_terms yuv_chroma(const yuv_rd& m, int u, int v)
+{
+	const int d = u - 128, e = v - 128;
+	yuv_terms t;
+	t.r = m.rv * e + 128; t.g = 128 - m.gu * d - m.gv * e; t.b = m.bu * d + 128;
+	return t;
+}
+
+__device__ __forceinline__ uint32_t yuv_pixel(const yuv_rd& m, int y, const yuv_terms& t)
+{
+	const int c = m.ky * (y - m.yo);
+	return (uint32_t)yuv_clip8((c + t.r) >> 8) << 16 | (uint32_t)yuv_clip8((c + t.g) >> 8) << 8 | (uint32_t)yuv_clip8((c + t.b) >> 8);
+}
+
+// pixel (x, y) of a frame as 0x00RRGGBB, byte by byte
+template <int FMT> __device__ __forceinline__ uint32_t yuv_read(const uint8_t* __restrict__ fr, uint32_t w, uint32_t h, uint32_t x, uint32_t y, const yuv_rd& m)
+{
+	const size_t cw = (w + 1) >> 1, ch = (h + 1) >> 1, ci = (size_t)(y >> 1) * cw + (x >> 1);
+	const uint8_t* c = fr + (size_t)w * h;
+	const int u = FMT == PF_NV12 ? c[2 * ci] : c[ci], v = FMT == PF_NV12 ? c[2 * ci + 1] : c[cw * ch + ci];
+	return yuv_pixel(m, fr[(size_t)y * w + x], yuv_chroma(m, u, v));
+}
+
+// the patch at column x0 (a multiple of 16) of rows 2 * py and (row1) 2 * py + 1, w a multiple of 16 and fr 16-byte aligned
+template <int FMT, bool NT> __device__ __forceinline__ yuv_raw yuv_load_patch(const uint8_t* __restrict__ fr, uint32_t w, uint32_t h, uint32_t x0, uint32_t py, bool row1)
+{
+	yuv_raw r;
+	const size_t cw = w >> 1, ch = (h + 1) >> 1;
+	const pf_u32x4* a = reinterpret_cast<const pf_u32x4*>(fr + (size_t)2 * py * w + x0);
+	const pf_u32x4* b = reinterpret_cast<const pf_u32x4*>(fr + ((size_t)2 * py + 1) * w + x0);
+	r.y0 = NT ? __builtin_nontemporal_load(a) : *a;
+	r.y1 = 0;
+	if (row1) r.y1 = NT ? __builtin_nontemporal_load(b) : *b;
+	if (FMT == PF_NV12) {
+		const pf_u32x4* c = reinterpret_cast<const pf_u32x4*>(fr + (size_t)w * h + (size_t)py * w + x0);
+		r.c = NT ? __builtin_nontemporal_load(c) : *c;
+	} else {
+		const pf_u32x2* u = reinterpret_cast<const pf_u32x2*>(fr + (size_t)w * h + (size_t)py * cw + (x0 >> 1));
+		const pf_u32x2* v = reinterpret_cast<const pf_u32x2*>(fr + (size_t)w * h + cw * ch + (size_t)py * cw + (x0 >> 1));
+		const pf_u32x2 uu = NT ? __builtin_nontemporal_load(u) : *u, vv = NT ? __builtin_nontemporal_load(v) : *v;
+		r.c[0] = uu[0]; r.c[1] = uu[1]; r.c[2] = vv[0]; r.c[3] = vv[1];
+	}
+	return r;
+}
+
+// chroma sample j (a constant once the caller's loop is unrolled) of a patch
+template <int FMT> __device__ __forceinline__ yuv_terms yuv_patch_chroma(const yuv_raw& r, int j, const yuv_rd& m)
+{
+	if (FMT == PF_NV12) return yuv_chroma(m, (r.c[j >> 1] >> (16 * (j & 1))) & 0xff, (r.c[j >> 1] >> (16 * (j & 1) + 8)) & 0xff);
+	return yuv_chroma(m, (r.c[j >> 2] >> (8 * (j & 3))) & 0xff, (r.c[2 + (j >> 2)] >> (8 * (j & 3))) & 0xff);
+}
+
+// d_dst[f][k] = pixel k (raster order) of frame f, k < npx <= w * h.  Wide a thread's patch is g; byte-wise the wave takes 2048
+// consecutive pixels, 64 at a time.  One frame takes bpf blocks.
+template <int FMT> __global__ __launch_bounds__(256) void k_yuv_to_xrgb(const uint8_t* __restrict__ src, uint32_t w, uint32_t h, size_t frame_bytes, uint32_t npx,
+                                                                        uint32_t bpf, int wide, yuv_rd m, uint32_t* __restrict__ dst)
+{
+	const uint32_t f = blockIdx.x / bpf, g = (blockIdx.x - f * bpf) * 256 + threadIdx.x;
+	const uint8_t* fr = src + (size_t)f * frame_bytes;
+	uint32_t* out = dst + (size_t)f * npx;
+	if (wide) {
+		const uint32_t ppr = w >> 4, py = g / ppr, x0 = (g - py * ppr) * 16;
+		if (2 * py >= h) return;
+		const uint32_t k0 = 2 * py * w + x0;
+		if (2 * py + 1 < h && k0 + w + 16 <= npx) {
+			const yuv_raw r = yuv_load_patch<FMT, true>(fr, w, h, x0, py, true);
+#pragma unroll
+			for (int q = 0; q < 4; q++) {                          // pixels 4q .. 4q + 3 of both rows: chroma samples 2q, 2q + 1
+				const yuv_terms ta = yuv_patch_chroma<FMT>(r, 2 * q, m), tb = yuv_patch_chroma<FMT>(r, 2 * q + 1, m);
+				pf_u32x4 o0, o1;
+#pragma unroll
+				for (int i = 0; i < 4; i++) {
+					o0[i] = yuv_pixel(m, (r.y0[q] >> (8 * i)) & 0xff, i < 2 ? ta : tb);
+					o1[i] = yuv_pixel(m, (r.y1[q] >> (8 * i)) & 0xff, i < 2 ? ta : tb);
+				}
+				*reinterpret_cast<pf_u32x4*>(out + k0 + 4 * q) = o0;
+				*reinterpret_cast<pf_u32x4*>(out + k0 + w + 4 * q) = o1;
+			}
+		} else {                                                   // the odd last row, or the count ends in this patch
+			for (uint32_t r = 0; r < 2 && 2 * py + r < h; r++)
+				for (uint32_t i = 0; i < 16; i++) if (k0 + r * w + i < npx) out[k0 + r * w + i] = yuv_read<FMT>(fr, w, h, x0 + i, 2 * py + r, m);
+		}
+	} else {
+		const uint32_t k0 = (g & ~63u) * 32 + (threadIdx.x & 63);
+		for (int i = 0; i < 32; i++) {
+			const uint32_t k = k0 + 64 * i;
+			if (k < npx) out[k] = yuv_read<FMT>(fr, w, h, k % w, k / w, m);
+		}
+	}
+}
+
+__device__ __forceinline__ uint32_t yuv_luma(const yuv_wr& m, uint32_t x)
+{
+	const int r = (x >> 16) & 0xff, g = (x >> 8) & 0xff, b = x & 0xff;
+	return (uint32_t)yuv_clip8(((m.yr * r + m.yg * g + m.yb * b + 128) >> 8) + m.yo);
+}
+
+// U | V << 8 of the mean colour (sums over cnt = 1 << sh pixels)
+__device__ __forceinline__ uint32_t yuv_uv(const yuv_wr& m, int sr, int sg, int sb, int sh)
+{
+	const int half = (1 << sh) >> 1, r = (sr + half) >> sh, g = (sg + half) >> sh, b = (sb + half) >> sh;
+	return (uint32_t)yuv_clip8(((m.ur * r + m.ug * g + m.ub * b + 128) >> 8) + 128) |
+	       (uint32_t)yuv_clip8(((m.vr * r + m.vg * g + m.vb * b + 128) >> 8) + 128) << 8;
+}
+
+// chroma sample (cx, cy) of a frame from the pixels of its 2 x 2 block that exist, byte by byte
+template <int FMT> __device__ __forceinline__ void yuv_put_chroma(const uint32_t* __restrict__ in, uint8_t* __restrict__ fr, uint32_t w, uint32_t h, uint32_t cx,
+                                                                  uint32_t cy, const yuv_wr& m)
+{
+	const uint32_t x = 2 * cx, y = 2 * cy, nx = x + 1 < w ? 2 : 1, ny = y + 1 < h ? 2 : 1;
+	const size_t cw = (w + 1) >> 1, ch = (h + 1) >> 1, ci = (size_t)cy * cw + cx;
+	int sr = 0, sg = 0, sb = 0;
+	for (uint32_t j = 0; j < ny; j++)
+		for (uint32_t i = 0; i < nx; i++) {
+			const uint32_t p = in[(size_t)(y + j) * w + x + i];
+			sr += (p >> 16) & 0xff; sg += (p >> 8) & 0xff; sb += p & 0xff;
+		}
+	const uint32_t uv = yuv_uv(m, sr, sg, sb, (nx == 2) + (ny == 2));
+	uint8_t* c = fr + (size_t)w * h;
+	if (FMT == PF_NV12) { c[2 * ci] = (uint8_t)uv; c[2 * ci + 1] = (uint8_t)(uv >> 8); }
+	else { c[ci] = (uint8_t)uv; c[cw * ch + ci] = (uint8_t)(uv >> 8); }
+}
+
+// d_dst frame f = src[f][0 .. w * h) written as YUV (whole frames); nothing outside those frames is written
+template <int FMT> __global__ __launch_bounds__(256) void k_yuv_from_xrgb(const uint32_t* __restrict__ src, uint32_t w, uint32_t h, size_t frame_bytes, uint32_t bpf,
+                                                                          int wide, yuv_wr m, uint8_t* __restrict__ dst)
+{
+	const uint32_t f = blockIdx.x / bpf, g = (blockIdx.x - f * bpf) * 256 + threadIdx.x, npx = w * h;
+	const uint32_t* in = src + (size_t)f * npx;
+	uint8_t* fr = dst + (size_t)f * frame_bytes;
+	if (wide) {
+		const uint32_t ppr = w >> 4, py = g / ppr, x0 = (g - py * ppr) * 16;
+		if (2 * py >= h) return;
+		const uint32_t k0 = 2 * py * w + x0;
+		if (2 * py + 1 < h) {
+			pf_u32x4 y0, y1, c;
+#pragma unroll
+			for (int q = 0; q < 4; q++) {
+				const pf_u32x4 a = __builtin_nontemporal_load(reinterpret_cast<const pf_u32x4*>(in + k0 + 4 * q));
+				const pf_u32x4 b = __builtin_nontemporal_load(reinterpret_cast<const pf_u32x4*>(in + k0 + w + 4 * q));
+				uint32_t ya = 0, yb = 0;
+#pragma unroll
+				for (int i = 0; i < 4; i++) { ya |= yuv_luma(m, a[i]) << (8 * i); yb |= yuv_luma(m, b[i]) << (8 * i); }
+				y0[q] = ya; y1[q] = yb;
+				uint32_t uv[2];
+#pragma unroll
+				for (int j = 0; j < 2; j++) {
+					const uint32_t p0 = a[2 * j], p1 = a[2 * j + 1], p2 = b[2 * j], p3 = b[2 * j + 1];
+					uv[j] = yuv_uv(m, (int)(((p0 >> 16) & 0xff) + ((p1 >> 16) & 0xff) + ((p2 >> 16) & 0xff) + ((p3 >> 16) & 0xff)),
+					               (int)(((p0 >> 8) & 0xff) + ((p1 >> 8) & 0xff) + ((p2 >> 8) & 0xff) + ((p3 >> 8) & 0xff)),
+					               (int)((p0 & 0xff) + (p1 & 0xff) + (p2 & 0xff) + (p3 & 0xff)), 2);
+				}
+				if (FMT == PF_NV12) c[q] = uv[0] | uv[1] << 16;        // samples 2q, 2q + 1 as U,V,U,V
+				else {                                             // U of samples 2q, 2q + 1 into byte 2q of the 8 U, V likewise
+					const uint32_t u2 = (uv[0] & 0xff) | (uv[1] & 0xff) << 8, v2 = (uv[0] >> 8) | (uv[1] >> 8) << 8;
+					if (q & 1) { c[q >> 1] |= u2 << 16; c[2 + (q >> 1)] |= v2 << 16; } else { c[q >> 1] = u2; c[2 + (q >> 1)] = v2; }
+				}
+			}
+			*reinterpret_cast<pf_u32x4*>(fr + k0) = y0;
+			*reinterpret_cast<pf_u32x4*>(fr + k0 + w) = y1;
+			if (FMT == PF_NV12) *reinterpret_cast<pf_u32x4*>(fr + (size_t)npx + (size_t)py * w + x0) = c;
+			else {
+				const size_t cw = w >> 1, ch = (h + 1) >> 1;
+				pf_u32x2 u, v;
+				u[0] = c[0]; u[1] = c[1]; v[0] = c[2]; v[1] = c[3];
+				*reinterpret_cast<pf_u32x2*>(fr + (size_t)npx + (size_t)py * cw + (x0 >> 1)) = u;
+				*reinterpret_cast<pf_u32x2*>(fr + (size_t)npx + cw * ch + (size_t)py * cw + (x0 >> 1)) = v;
+			}
+		} else {                                                   // the odd last row: means over two pixels
+			for (uint32_t i = 0; i < 16; i++) fr[k0 + i] = (uint8_t)yuv_luma(m, in[k0 + i]);
+			for (uint32_t j = 0; j < 8; j++) yuv_put_chroma<FMT>(in, fr, w, h, (x0 >> 1) + j, py, m);
+		}
+	} else {                                                       // lanes on consecutive pixels; the pixel at the even corner of a block writes its chroma
+		const uint32_t k0 = (g & ~63u) * 32 + (threadIdx.x & 63);
+		for (int i = 0; i < 32; i++) {
+			const uint32_t k = k0 + 64 * i;
+			if (k >= npx) break;
+			const uint32_t y = k / w, x = k - y * w;
+			fr[k] = (uint8_t)yuv_luma(m, in[k]);
+			if (!((x | y) & 1)) yuv_put_chroma<FMT>(in, fr, w, h, x >> 1, y >> 1, m);
+		}
+	}
+}
+
+// k_gather on a YUV source: only the pixels the table names, and their chroma, are read
+template <int FMT> __global__ __launch_bounds__(256) void k_yuv_gather(const uint8_t* __restrict__ src, uint32_t w, uint32_t h, size_t frame_bytes, uint32_t n_frames,
+                                                                       const uint32_t* __restrict__ index, size_t n_out, yuv_rd m, uint32_t* __restrict__ dst)
+{
+	const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (k >= n_out) return;
+	const uint32_t i = index[k];
+	const bool live = i != 0xFFFFFFFFu && i < w * h;
+	const uint32_t y = live ? i / w : 0, x = live ? i - y * w : 0;
+	for (uint32_t f = 0; f < n_frames; f++) dst[(size_t)f * n_out + k] = live ? yuv_read<FMT>(src + (size_t)f * frame_bytes, w, h, x, y, m) : 0u;
+}
+
+// k_histogram over the first npx pixels (raster order) of each frame of a YUV clip, with the codes and the run-length atomics of
+// k_histogram_fmt.  Wide a wave takes 64 patches: each lane's loads go to LDS at their place (1 KiB of row 0, of row 1 and of
+// chroma per wave) and the wave then walks the 2048 pixels 64 at a time -- 4 patches of one row, lane l on column l & 15 of patch
+// l >> 4 -- so neighbouring lanes hold neighbouring pixels and runs stay long.  Byte-wise a slice of 64 consecutive pixels reads
+// global memory directly.
+template <int FMT> __global__ __launch_bounds__(256) void k_yuv_histogram(const uint8_t* __restrict__ src, uint32_t w, uint32_t h, size_t frame_bytes, uint32_t npx,
+                                                                          uint32_t bpf, int wide, int quality, yuv_rd m, uint32_t* __restrict__ hist)
+{
+	__shared__ pf_u32x4 s_px[4][3][64];
+	const int lane = threadIdx.x & 63;
+	const uint32_t f = blockIdx.x / bpf, g = (blockIdx.x - f * bpf) * 256 + threadIdx.x;
+	const uint8_t* fr = src + (size_t)f * frame_bytes;
+	if (wide) {
+		const uint32_t ppr = w >> 4;
+		{
+			const uint32_t py = g / ppr, x0 = (g - py * ppr) * 16;
+			yuv_raw r;
+			r.y0 = 0; r.y1 = 0; r.c = 0;
+			if (2 * py < h && 2 * py * w + x0 < npx) r = yuv_load_patch<FMT, false>(fr, w, h, x0, py, 2 * py + 1 < h);
+			s_px[threadIdx.x >> 6][0][lane] = r.y0; s_px[threadIdx.x >> 6][1][lane] = r.y1; s_px[threadIdx.x >> 6][2][lane] = r.c;
+		}
+		__syncthreads();
+		const uint8_t* sy = reinterpret_cast<const uint8_t*>(s_px[threadIdx.x >> 6][0]);     // rows 1024 bytes apart, chroma behind them
+		const uint8_t* sc = sy + 2048;
+		uint32_t gp = (g & ~63u) + (lane >> 4), py = gp / ppr, xq = gp - py * ppr;              // this lane's patch of the first four
+		for (int q = 0; q < 16; q++) {
+			const int at = 64 * q + lane, cs = at >> 1;                                        // byte of the wave's row, chroma sample of the wave's 512
+			const int u = FMT == PF_NV12 ? sc[2 * cs] : sc[16 * (cs >> 3) + (cs & 7)], v = FMT == PF_NV12 ? sc[2 * cs + 1] : sc[16 * (cs >> 3) + 8 + (cs & 7)];
+			const yuv_terms t = yuv_chroma(m, u, v);
+			for (uint32_t r = 0; r < 2; r++) {
+				const bool live = 2 * py + r < h && (2 * py + r) * w + xq * 16 + (lane & 15) < npx;
+				hist_add_runs(hist, live ? quantize_color(yuv_pixel(m, sy[1024 * r + at], t), quality) : 0xFFFFFFFFu, live, lane);
+			}
+			xq += 4;
+			while (xq >= ppr) { xq -= ppr; py++; }
+		}
+	} else {
+		const uint32_t k0 = (g & ~63u) * 32 + lane;
+		for (int i = 0; i < 32; i++) {
+			const uint32_t k = k0 + 64 * i;
+			const bool live = k < npx;
+			hist_add_runs(hist, live ? quantize_color(yuv_read<FMT>(fr, w, h, k % w, k / w, m), quality) : 0xFFFFFFFFu, live, lane);
+		}
+	}
+}
+
+// k_similarity on a YUV clip: the same walk through all frames and the same slots.  A lane owns a patch of up to 16 x 2 pixel
+// positions (the grid is ceil(w / 16) x ceil(h / 2) patches): per frame two 16-byte luma loads and the chroma both rows share,
+// the greys of the frame before in eight registers.  Without `wide` the patch is read byte by byte into the same registers.
+// Positions of the patch behind the frame's edge have grey 0 in every frame: they always compare equal and are taken off again.
+template <int FMT> __device__ __forceinline__ yuv_raw sim_yuv_load(const uint8_t* __restrict__ fr, uint32_t w, uint32_t h, uint32_t x0, uint32_t py, uint32_t nx,
+                                                                    bool row1, bool wide)
+{
+	yuv_raw r;
+	r.y0 = 0; r.y1 = 0; r.c = 0;
+	if (nx == 0) return r;
+	if (wide) return yuv_load_patch<FMT, false>(fr, w, h, x0, py, row1);
+	const size_t cw = (w + 1) >> 1, ch = (h + 1) >> 1;
+	const uint8_t *a = fr + (size_t)2 * py * w + x0, *c = fr + (size_t)w * h + (FMT == PF_NV12 ? 2 : 1) * ((size_t)py * cw + (x0 >> 1));
+#pragma unroll
+	for (int i = 0; i < 16; i++) if ((uint32_t)i < nx) {
+		r.y0[i >> 2] |= (uint32_t)a[i] << (8 * (i & 3));
+		if (row1) r.y1[i >> 2] |= (uint32_t)a[w + i] << (8 * (i & 3));
+	}
+#pragma unroll
+	for (int j = 0; j < 8; j++) if ((uint32_t)(2 * j) < nx) {
+		if (FMT == PF_NV12) r.c[j >> 1] |= ((uint32_t)c[2 * j] | (uint32_t)c[2 * j + 1] << 8) << (16 * (j & 1));
+		else { r.c[j >> 2] |= (uint32_t)c[j] << (8 * (j & 3)); r.c[2 + (j >> 2)] |= (uint32_t)c[cw * ch + j] << (8 * (j & 3)); }
+	}
+	return r;
+}
+
+struct yuv_greys { pf_u32x4 a, b; };                               // one grey per byte: row 0, row 1
+
+template <int FMT> __device__ __forceinline__ yuv_greys sim_yuv_greys(const yuv_raw& r, const yuv_rd& m, const pf_u32x4& live, bool row1)
+{
+	yuv_greys g;
+	g.a = 0; g.b = 0;
+#pragma unroll
+	for (int j = 0; j < 8; j++) {
+		const yuv_terms t = yuv_patch_chroma<FMT>(r, j, m);
+#pragma unroll
+		for (int i = 2 * j; i < 2 * j + 2; i++) {
+			g.a[i >> 2] |= sim_grey(yuv_pixel(m, (r.y0[i >> 2] >> (8 * (i & 3))) & 0xff, t)) << (8 * (i & 3));
+			g.b[i >> 2] |= sim_grey(yuv_pixel(m, (r.y1[i >> 2] >> (8 * (i & 3))) & 0xff, t)) << (8 * (i & 3));
+		}
+	}
+	g.a &= live;
+	if (row1) g.b &= live; else g.b = 0;
+	return g;
+}
+
+template <int FMT> __global__ __launch_bounds__(256) void k_yuv_similarity(const uint8_t* __restrict__ pix, uint32_t n_frames, uint32_t w, uint32_t h, size_t frame_bytes,
+                                                                           int wide, yuv_rd m, uint32_t* __restrict__ counts)
+{
+	__shared__ uint32_t s_cnt[SIM_SEG];
+	const uint32_t ppr = (w + 15) >> 4, g = blockIdx.x * 256 + threadIdx.x, py = g / ppr, x0 = (g - py * ppr) * 16;
+	const uint32_t nx = 2 * py < h ? (w - x0 < 16 ? w - x0 : 16) : 0;     // columns of this lane's patch that exist
+	const bool row1 = nx && 2 * py + 1 < h;
+	const uint32_t dead = 32 - nx * (row1 ? 2 : 1);
+	pf_u32x4 live;
+#pragma unroll
+	for (int q = 0; q < 4; q++) live[q] = nx >= 4u * q + 4 ? 0xFFFFFFFFu : (nx > 4u * q ? (1u << (8 * (nx - 4 * q))) - 1 : 0u);
+	const uint32_t n_pairs = n_frames - 1;
+	yuv_greys gp = sim_yuv_greys<FMT>(sim_yuv_load<FMT>(pix, w, h, x0, py, nx, row1, wide), m, live, row1);
+	yuv_raw nxt = sim_yuv_load<FMT>(pix + frame_bytes, w, h, x0, py, nx, row1, wide);
+	for (uint32_t seg = 0; seg < n_pairs; seg += SIM_SEG) {
+		const uint32_t n_seg = n_pairs - seg < SIM_SEG ? n_pairs - seg : SIM_SEG;
+		for (uint32_t k = threadIdx.x; k < n_seg; k += 256) s_cnt[k] = 0;
+		__syncthreads();
+		for (uint32_t k = 0; k < n_seg; k++) {
+			const uint32_t f = seg + k + 1;                    // the later frame of pair seg + k: its patch is in nxt
+			const yuv_raw cur = nxt;
+			if (f + 1 < n_frames) nxt = sim_yuv_load<FMT>(pix + (size_t)(f + 1) * frame_bytes, w, h, x0, py, nx, row1, wide);
+			const yuv_greys gh = sim_yuv_greys<FMT>(cur, m, live, row1);
+			uint32_t c = sim_equal_bytes(gp.a[0], gh.a[0]) + sim_equal_bytes(gp.a[1], gh.a[1]) + sim_equal_bytes(gp.a[2], gh.a[2]) + sim_equal_bytes(gp.a[3], gh.a[3]) +
+			             sim_equal_bytes(gp.b[0], gh.b[0]) + sim_equal_bytes(gp.b[1], gh.b[1]) + sim_equal_bytes(gp.b[2], gh.b[2]) + sim_equal_bytes(gp.b[3], gh.b[3]) - dead;
+			gp = gh;
+			for (int d = 32; d; d >>= 1) c += __shfl_xor(c, d, 64);
+			if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt[k], c);
+		}
+		__syncthreads();
+		for (uint32_t k = threadIdx.x; k < n_seg; k += 256) if (s_cnt[k]) atomicAdd(counts + seg + k, s_cnt[k]);
+		__syncthreads();
+	}
+}
+
 // A spin of k_encode that ran into its bound leaves ctrl[1] != 0 and the kernel carries on with a wrong offset: the bytes of
 // the batch are not to be used.  So that a caller who skips agmv_hip_check cannot take them for good ones, every size of
 // the batch is then overwritten with 0xFFFFFFFF (no frame is that long: agmv_hip_max_usize < 2^32).
@@ -3838,6 +4179,112 @@ extern "C" int agmv_hip_similarity_fmt_dev(agmv_hip_ctx* c, int fmt, const void*
 		hipLaunchKernelGGL(k_similarity_fmt<PF_RGB8P>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_src, n_frames, n_pixels, frame_bytes, vec, d_counts);
 		break;
 	}
+	CK(hipGetLastError());
+	return 0;
+}
+
+// ---- the same on clips in 8-bit YUV 4:2:0: fmt is 16 (NV12) or 17 (I420), | 0x100 for BT.709, | 0x200 for full range ----
+static int yuv_base(int fmt) { return (fmt & ~0x3FF) == 0 && ((fmt & 0xFF) == PF_NV12 || (fmt & 0xFF) == PF_I420) ? fmt & 0xFF : 0; }
+
+// the usual 8-bit fixed-point matrices, indexed by (fmt >> 8) & 3: BT.601 limited, BT.709 limited, BT.601 full, BT.709 full
+static const yuv_rd YUV_RD[4] = { { 298, 16, 409, 100, 208, 516 }, { 298, 16, 459, 55, 136, 541 }, { 256, 0, 359, 88, 183, 454 }, { 256, 0, 403, 48, 120, 475 } };
+static const yuv_wr YUV_WR[4] = { { 66, 129, 25, 16, -38, -74, 112, 112, -94, -18 }, { 47, 157, 16, 16, -26, -86, 112, 112, -102, -10 },
+                                  { 77, 150, 29, 0, -43, -85, 128, 128, -107, -21 }, { 54, 183, 19, 0, -29, -99, 128, 128, -116, -12 } };
+
+extern "C" size_t agmv_hip_yuv_frame_bytes(int fmt, uint32_t w, uint32_t h)
+{
+	if (!yuv_base(fmt)) return 0;
+	return (size_t)w * h + 2 * (size_t)((w + 1) / 2) * ((h + 1) / 2);
+}
+
+static int bad_yuv(int fmt, uint32_t w, uint32_t h)
+{
+	if (!yuv_base(fmt)) { snprintf(g_err, sizeof(g_err), "agmv_hip: unknown pixel format 0x%x (a YUV 4:2:0 format is needed)", (unsigned)fmt); return -1; }
+	if (w == 0 || h == 0 || (unsigned long long)w * h > (1ull << 30)) { snprintf(g_err, sizeof(g_err), "agmv_hip: YUV frames of %u x %u", w, h); return -1; }
+	return 0;
+}
+
+// a clip whose patches of 16 x 2 pixels can be read and written with 16-byte (I420 chroma: 8-byte) accesses
+static int yuv_wide(int fmt, const void* d, uint32_t w, uint32_t h, uint32_t n_frames)
+{
+	return (w & 15) == 0 && ((uintptr_t)d & 15) == 0 && (n_frames == 1 || (agmv_hip_yuv_frame_bytes(fmt, w, h) & 15) == 0);
+}
+
+// the grid of the kernels that give a thread 32 pixels of one frame: wide the patches of the rows that hold the first n_pixels,
+// else runs of 32 pixels
+static int yuv_grid(uint32_t w, size_t n_pixels, int wide, uint32_t n_frames, uint32_t* bpf, unsigned* blocks)
+{
+	const size_t rows = (n_pixels + w - 1) / w;
+	const size_t per = wide ? ((size_t)(w >> 4) * ((rows + 1) / 2) + 255) / 256 : (n_pixels + 8191) / 8192;
+	if (per * n_frames > 0x7FFFFFFFull) { snprintf(g_err, sizeof(g_err), "agmv_hip: clip too large for one launch"); return -1; }
+	*bpf = (uint32_t)per; *blocks = (unsigned)(per * n_frames);
+	return 0;
+}
+
+#define YUV_LAUNCH(kernel, ...) do { \
+	if (yuv_base(fmt) == PF_NV12) hipLaunchKernelGGL(kernel<PF_NV12>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
+	else hipLaunchKernelGGL(kernel<PF_I420>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); } while (0)
+
+extern "C" int agmv_hip_yuv_to_xrgb_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames, size_t n_pixels, uint32_t* d_dst,
+                                        void* stream)
+{
+	if (need_ctx(c, false) || bad_yuv(fmt, w, h)) return -1;
+	if (n_pixels > (size_t)w * h) { snprintf(g_err, sizeof(g_err), "agmv_hip: n_pixels %zu > %u x %u", n_pixels, w, h); return -1; }
+	if (n_frames == 0 || n_pixels == 0) return 0;
+	uint32_t bpf; unsigned blocks;
+	const int wide = yuv_wide(fmt, d_src, w, h, n_frames) && pf_aligned(PF_XRGB32, d_dst, n_pixels, n_frames);
+	if (yuv_grid(w, n_pixels, wide, n_frames, &bpf, &blocks)) return -1;
+	YUV_LAUNCH(k_yuv_to_xrgb, (const uint8_t*)d_src, w, h, agmv_hip_yuv_frame_bytes(fmt, w, h), (uint32_t)n_pixels, bpf, wide, YUV_RD[(fmt >> 8) & 3], d_dst);
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_yuv_from_xrgb_dev(agmv_hip_ctx* c, int fmt, const uint32_t* d_src, uint32_t w, uint32_t h, uint32_t n_frames, void* d_dst, void* stream)
+{
+	if (need_ctx(c, false) || bad_yuv(fmt, w, h)) return -1;
+	if (n_frames == 0) return 0;
+	uint32_t bpf; unsigned blocks;
+	const int wide = yuv_wide(fmt, d_dst, w, h, n_frames) && pf_aligned(PF_XRGB32, d_src, (size_t)w * h, n_frames);
+	if (yuv_grid(w, (size_t)w * h, wide, n_frames, &bpf, &blocks)) return -1;
+	YUV_LAUNCH(k_yuv_from_xrgb, d_src, w, h, agmv_hip_yuv_frame_bytes(fmt, w, h), bpf, wide, YUV_WR[(fmt >> 8) & 3], (uint8_t*)d_dst);
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_yuv_gather_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames, const uint32_t* d_index, size_t n_out,
+                                       uint32_t* d_dst, void* stream)
+{
+	if (need_ctx(c, false) || bad_yuv(fmt, w, h)) return -1;
+	if (n_frames == 0 || n_out == 0) return 0;
+	if (n_out > ((size_t)1 << 39)) { snprintf(g_err, sizeof(g_err), "agmv_hip: gather table too long"); return -1; }
+	const unsigned blocks = (unsigned)((n_out + 255) / 256);
+	YUV_LAUNCH(k_yuv_gather, (const uint8_t*)d_src, w, h, agmv_hip_yuv_frame_bytes(fmt, w, h), n_frames, d_index, n_out, YUV_RD[(fmt >> 8) & 3], d_dst);
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_yuv_histogram_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames, size_t n_pixels, int quality,
+                                          uint32_t* d_hist, void* stream)
+{
+	if (need_ctx(c, false) || bad_yuv(fmt, w, h)) return -1;
+	if (n_pixels > (size_t)w * h) { snprintf(g_err, sizeof(g_err), "agmv_hip: n_pixels %zu > %u x %u", n_pixels, w, h); return -1; }
+	if (n_frames == 0 || n_pixels == 0) return 0;
+	uint32_t bpf; unsigned blocks;
+	const int wide = yuv_wide(fmt, d_src, w, h, n_frames);
+	if (yuv_grid(w, n_pixels, wide, n_frames, &bpf, &blocks)) return -1;
+	YUV_LAUNCH(k_yuv_histogram, (const uint8_t*)d_src, w, h, agmv_hip_yuv_frame_bytes(fmt, w, h), (uint32_t)n_pixels, bpf, wide, quality, YUV_RD[(fmt >> 8) & 3], d_hist);
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_yuv_similarity_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames, uint32_t* d_counts, void* stream)
+{
+	if (need_ctx(c, false) || bad_yuv(fmt, w, h)) return -1;
+	if (n_frames < 2) return 0;                                // no pair
+	const unsigned blocks = (unsigned)(((size_t)((w + 15) >> 4) * ((h + 1) >> 1) + 255) / 256);    // 256 lanes x one patch
+	CK(hipMemsetAsync(d_counts, 0, 4 * (size_t)(n_frames - 1), (hipStream_t)stream));
+	const int wide = yuv_wide(fmt, d_src, w, h, n_frames);
+	YUV_LAUNCH(k_yuv_similarity, (const uint8_t*)d_src, n_frames, w, h, agmv_hip_yuv_frame_bytes(fmt, w, h), wide, YUV_RD[(fmt >> 8) & 3], d_counts);
 	CK(hipGetLastError());
 	return 0;
 }

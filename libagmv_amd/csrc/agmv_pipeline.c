@@ -333,13 +333,17 @@ static void download_rows(eworker* wk, ebatch* b, const uint8_t* d_rows, size_t 
    from the source's layout -- for XRGB32 a copy --, or with a scale gathered through the table) */
 static const void* src_frame(const agmv_seq* s, long idx)
 {
-	return (const u8*)s->src.d_frames + (size_t)(idx - s->src.first) * agmv_hip_pixfmt_frame_bytes(s->src.fmt, (size_t)s->src.src_w * s->src.src_h);
+	return (const u8*)s->src.d_frames + (size_t)(idx - s->src.first) * agmv_fmt_frame_bytes(s->src.fmt, s->src.src_w, s->src.src_h);
 }
 
 static int place_frame(eworker* wk, long idx, uint32_t* dst)
 {
 	agmv_seq* s = wk->s;
 	const size_t fpx = (size_t)s->src.src_w * s->src.src_h;
+	if (AGMV_FMT_IS_YUV(s->src.fmt)) {
+		if (s->d_index) return agmv_hip_yuv_gather_dev(wk->ctx, s->src.fmt, src_frame(s, idx), s->src.src_w, s->src.src_h, 1, s->d_index, s->npx, dst, wk->stream);
+		return agmv_hip_yuv_to_xrgb_dev(wk->ctx, s->src.fmt, src_frame(s, idx), s->src.src_w, s->src.src_h, 1, s->npx, dst, wk->stream);
+	}
 	if (s->d_index) return agmv_hip_gather_fmt_dev(wk->ctx, s->src.fmt, src_frame(s, idx), fpx, 1, s->d_index, s->npx, dst, wk->stream);
 	return agmv_hip_pixels_to_xrgb_dev(wk->ctx, s->src.fmt, src_frame(s, idx), fpx, 1, s->npx, dst, wk->stream);
 }
@@ -698,10 +702,12 @@ void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start,
 	void* stream = agmv_hip_stream_create(ctx);
 	if (src->d_frames) {                                       /* the clip is resident: no parse, no ring, no upload */
 		const size_t fpx = (size_t)src->src_w * src->src_h, px = fpx < size ? fpx : size;
-		const u8* d_first = (const u8*)src->d_frames + (size_t)((long)start - src->first) * agmv_hip_pixfmt_frame_bytes(src->fmt, fpx);
+		const u8* d_first = (const u8*)src->d_frames + (size_t)((long)start - src->first) * agmv_fmt_frame_bytes(src->fmt, src->src_w, src->src_h);
 		if ((long)start < src->first || (long)end >= src->first + (long)src->n_frames) agmv_die("internal: frame outside the device clip");
 		if (!d_hist || !stream || agmv_hip_memset_async(ctx, d_hist, 0, 4u << 19, stream)) agmv_die("histogram");
-		if (agmv_hip_histogram_fmt_dev(ctx, src->fmt, d_first, fpx, n, px, quality, d_hist, stream)) agmv_die("histogram");
+		if (AGMV_FMT_IS_YUV(src->fmt) ? agmv_hip_yuv_histogram_dev(ctx, src->fmt, d_first, src->src_w, src->src_h, n, px, quality, d_hist, stream)
+		                              : agmv_hip_histogram_fmt_dev(ctx, src->fmt, d_first, fpx, n, px, quality, d_hist, stream))
+			agmv_die("histogram");
 		if (agmv_hip_memcpy_async(ctx, hist, d_hist, 4u << 19, 1, stream) || agmv_hip_stream_sync(ctx, stream)) agmv_die("histogram download");
 		agmv_hip_free_on(ctx, d_hist);
 		agmv_hip_stream_destroy(ctx, stream);
@@ -836,9 +842,12 @@ static void* dworker_main(void* p)
 		for (k = 0; k < b->n; k++) if (((b->first + k) & 3u) == 0) last_i = (int)k;
 		if (!have_state && last_i < 0 && agmv_hip_memset_async(d->ctx, d->d_iframe, 0, d->npx * 4, d->stream)) goto fail;
 		if (last_i >= 0 && agmv_hip_memcpy_async(d->ctx, d->d_iframe, out + (size_t)last_i * d->npx, d->npx * 4, 2, d->stream)) goto fail;
-		if (d->d_dst && !direct &&
-		    agmv_hip_pixels_from_xrgb_dev(d->ctx, d->fmt, out, b->n, d->npx, (u8*)d->d_dst + (size_t)b->first * agmv_hip_pixfmt_frame_bytes(d->fmt, d->npx), d->stream))
-			goto fail;
+		if (d->d_dst && !direct) {
+			u8* sink = (u8*)d->d_dst + (size_t)b->first * agmv_fmt_frame_bytes(d->fmt, d->w, d->h);
+			if (AGMV_FMT_IS_YUV(d->fmt) ? agmv_hip_yuv_from_xrgb_dev(d->ctx, d->fmt, out, d->w, d->h, b->n, sink, d->stream)
+			                            : agmv_hip_pixels_from_xrgb_dev(d->ctx, d->fmt, out, b->n, d->npx, sink, d->stream))
+				goto fail;
+		}
 		if ((!d->d_dst && agmv_hip_memcpy_async(d->ctx, b->h_out, out, d->npx * 4 * b->n, 1, d->stream)) || agmv_hip_stream_sync(d->ctx, d->stream)) goto fail;
 		have_state = 1;
 		prev_n = b->n;

@@ -17,8 +17,8 @@ uint32_t* agmv_source_index(uint32_t sw, uint32_t sh, int scale_w, int scale_h, 
 void agmv_load_source(const char* dir, const char* base, long idx, int scale_w, int scale_h, uint32_t w, uint32_t h, uint32_t* dst);
 
 /* where the frames of a sequence encode come from: the numbered BMP files dir/base<idx>.bmp, or (d_frames != NULL) a clip of
-   n_frames frames of src_w x src_h pixels in the layout `fmt` (an AGMV_PIXFMT) in the memory of device `device`, its first
-   frame numbered `first` */
+   n_frames frames of src_w x src_h pixels in the layout `fmt` (an AGMV_PIXFMT, for NV12 / I420 with the AGMV_YUV_ flags) in the
+   memory of device `device`, its first frame numbered `first` */
 typedef struct agmv_source {
 	const char *dir, *base;
 	const void* d_frames;
@@ -27,6 +27,13 @@ typedef struct agmv_source {
 	long first;
 	int device;
 } agmv_source;
+
+/* a YUV 4:2:0 layout (its frames are addressed by w and h, not by a pixel count), and the bytes of one frame of any layout */
+#define AGMV_FMT_IS_YUV(fmt) (((fmt) & 0xFF) >= AGMV_PIXFMT_NV12)
+static inline size_t agmv_fmt_frame_bytes(int fmt, uint32_t w, uint32_t h)
+{
+	return AGMV_FMT_IS_YUV(fmt) ? agmv_hip_yuv_frame_bytes(fmt, w, h) : agmv_hip_pixfmt_frame_bytes(fmt, (size_t)w * h);
+}
 
 /* one open sequence encode: frames are pushed in order (plain, or the PDIFS midpoint of two sources) and leave as AGFC
    (+ AGAC) chunks in `file`, strictly in order; batches of `cap` frames (whole GOPs) go round-robin over two workers per

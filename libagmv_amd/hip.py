@@ -32,6 +32,8 @@ ABI_SYMBOLS = [
     "agmv_hip_event_create", "agmv_hip_event_destroy", "agmv_hip_event_record", "agmv_hip_stream_wait_event",
     "agmv_hip_pixfmt_frame_bytes", "agmv_hip_pixels_to_xrgb_dev", "agmv_hip_pixels_from_xrgb_dev", "agmv_hip_gather_fmt_dev",
     "agmv_hip_histogram_fmt_dev", "agmv_hip_similarity_fmt_dev",
+    "agmv_hip_yuv_frame_bytes", "agmv_hip_yuv_to_xrgb_dev", "agmv_hip_yuv_from_xrgb_dev", "agmv_hip_yuv_gather_dev",
+    "agmv_hip_yuv_histogram_dev", "agmv_hip_yuv_similarity_dev",
 ]
 
 
@@ -147,6 +149,17 @@ def load_library(path=None):
         for f in (L.agmv_hip_pixels_to_xrgb_dev, L.agmv_hip_pixels_from_xrgb_dev, L.agmv_hip_gather_fmt_dev, L.agmv_hip_histogram_fmt_dev,
                   L.agmv_hip_similarity_fmt_dev):
             f.restype = C.c_int
+    if path is None or hasattr(L, "agmv_hip_yuv_to_xrgb_dev"):
+        L.agmv_hip_yuv_frame_bytes.restype = sz
+        L.agmv_hip_yuv_frame_bytes.argtypes = [C.c_int, u32, u32]
+        L.agmv_hip_yuv_to_xrgb_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, sz, vp, vp]
+        L.agmv_hip_yuv_from_xrgb_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, vp, vp]
+        L.agmv_hip_yuv_gather_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, vp, sz, vp, vp]
+        L.agmv_hip_yuv_histogram_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, sz, C.c_int, vp, vp]
+        L.agmv_hip_yuv_similarity_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, vp, vp]
+        for f in (L.agmv_hip_yuv_to_xrgb_dev, L.agmv_hip_yuv_from_xrgb_dev, L.agmv_hip_yuv_gather_dev, L.agmv_hip_yuv_histogram_dev,
+                  L.agmv_hip_yuv_similarity_dev):
+            f.restype = C.c_int
     L.agmv_hip_check.argtypes = [vp, vp]
     L.agmv_hip_enable_timing.argtypes = [vp, C.c_int]
     L.agmv_hip_enable_timing.restype = C.c_int
@@ -174,6 +187,23 @@ def pixfmt(fmt):
     if v not in PIXFMT.values():
         raise ValueError("fmt: one of %s is needed, got %r" % (", ".join(sorted(PIXFMT)), fmt))
     return v
+
+
+# the YUV 4:2:0 formats of include/agmv.h and the flags that are OR-ed into them (PIXFMT and pixfmt() stay the five RGB layouts)
+YUVFMT = {"nv12": 16, "i420": 17}
+YUV_BT709, YUV_FULL_RANGE = 0x100, 0x200
+
+
+def yuvfmt(fmt, yuv=None, full_range=False):
+    """the fmt argument of the agmv_hip_yuv_* functions: a name of YUVFMT with yuv "bt601" (default) / "bt709" and full_range, or
+    such a value itself (then yuv and full_range must be left alone)"""
+    if fmt in YUVFMT:
+        if yuv not in (None, "bt601", "bt709"):
+            raise ValueError("yuv: \"bt601\" or \"bt709\" is needed, got %r" % (yuv,))
+        return YUVFMT[fmt] | (YUV_BT709 if yuv == "bt709" else 0) | (YUV_FULL_RANGE if full_range else 0)
+    if isinstance(fmt, int) and (fmt & 0xFF) in YUVFMT.values() and not fmt & ~0x3FF and yuv is None and not full_range:
+        return fmt
+    raise ValueError("fmt: one of %s (or its value with flags) is needed, got %r" % (", ".join(sorted(YUVFMT)), fmt))
 
 
 def _np_ptr(a):
@@ -698,6 +728,76 @@ class AgmvHip:
             counts = torch.empty(max(n_frames - 1, 0), dtype=torch.int32, device=src.device)
         _check_vec("similarity_fmt_dev: counts", counts, n_frames - 1)
         self._ck(self.L.agmv_hip_similarity_fmt_dev(self.ctx, fmt, src.data_ptr(), n_frames, n_pixels, counts.data_ptr(), self._stream()))
+        return counts
+
+    # ------------------------------------------------------------------ clips in YUV 4:2:0 (NV12 / I420)
+    # A clip is a contiguous CUDA uint8 tensor of any shape holding whole frames back to back (a view at any byte offset will do);
+    # fmt is a name of YUVFMT plus yuv= / full_range=, or the value with its flags.
+    def yuv_frame_bytes(self, fmt, w, h):
+        return self.L.agmv_hip_yuv_frame_bytes(yuvfmt(fmt), w, h)
+
+    def _check_yuv(self, name, fmt, t, w, h, n_frames, yuv, full_range):
+        import torch
+        fmt = yuvfmt(fmt, yuv, full_range)
+        need = n_frames * self.L.agmv_hip_yuv_frame_bytes(fmt, w, h)
+        if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() >= need):
+            raise ValueError("%s: a contiguous CUDA uint8 tensor of >= %d bytes is needed, got %s %s on %s" % (name, need, t.dtype, tuple(t.shape), t.device))
+        return fmt
+
+    def yuv_to_xrgb_dev(self, fmt, src, w, h, n_frames, n_pixels=None, out=None, yuv=None, full_range=False):
+        """src: clip of n_frames frames of w x h -> int32 [n_frames, n_pixels] of 0x00RRGGBB (the first n_pixels of each, raster order)"""
+        import torch
+        n_pixels = w * h if n_pixels is None else n_pixels
+        fmt = self._check_yuv("yuv_to_xrgb_dev: src", fmt, src, w, h, n_frames, yuv, full_range)
+        if out is None:
+            out = torch.empty((n_frames, n_pixels), dtype=torch.int32, device=src.device)
+        _check_vec("yuv_to_xrgb_dev: out", out, n_frames * n_pixels)
+        self._ck(self.L.agmv_hip_yuv_to_xrgb_dev(self.ctx, fmt, src.data_ptr(), w, h, n_frames, n_pixels, out.data_ptr(), self._stream()))
+        return out
+
+    def yuv_from_xrgb_dev(self, fmt, src, w, h, out=None, yuv=None, full_range=False):
+        """src: int32 [n_frames, w * h] -> the clip as uint8 [n_frames, frame bytes]"""
+        import torch
+        if not (src.is_cuda and src.dtype == torch.int32 and src.dim() == 2 and src.is_contiguous() and src.shape[1] == w * h):
+            raise ValueError("yuv_from_xrgb_dev: a contiguous CUDA int32 tensor [n_frames, w * h] is needed")
+        n = src.shape[0]
+        if out is None:
+            out = torch.empty((n, self.L.agmv_hip_yuv_frame_bytes(yuvfmt(fmt, yuv, full_range), w, h)), dtype=torch.uint8, device=src.device)
+        fmt = self._check_yuv("yuv_from_xrgb_dev: out", fmt, out, w, h, n, yuv, full_range)
+        self._ck(self.L.agmv_hip_yuv_from_xrgb_dev(self.ctx, fmt, src.data_ptr(), w, h, n, out.data_ptr(), self._stream()))
+        return out
+
+    def yuv_gather_dev(self, fmt, src, w, h, n_frames, index, out=None, yuv=None, full_range=False):
+        """gather_dev on a YUV clip of n_frames frames of w x h (index: y * w + x); returns int32 [n_frames, n_out]"""
+        import torch
+        fmt = self._check_yuv("yuv_gather_dev: src", fmt, src, w, h, n_frames, yuv, full_range)
+        _check_vec("yuv_gather_dev: index", index, 1)
+        n_out = index.numel()
+        if out is None:
+            out = torch.empty((n_frames, n_out), dtype=torch.int32, device=src.device)
+        _check_vec("yuv_gather_dev: out", out, n_frames * n_out)
+        self._ck(self.L.agmv_hip_yuv_gather_dev(self.ctx, fmt, src.data_ptr(), w, h, n_frames, index.data_ptr(), n_out, out.data_ptr(), self._stream()))
+        return out
+
+    def yuv_histogram_dev(self, fmt, src, w, h, n_frames, n_pixels=None, quality=1, hist=None, yuv=None, full_range=False):
+        """histogram_dev over the first n_pixels of each frame of a YUV clip; `hist` is added to"""
+        import torch
+        n_pixels = w * h if n_pixels is None else n_pixels
+        fmt = self._check_yuv("yuv_histogram_dev: src", fmt, src, w, h, n_frames, yuv, full_range)
+        if hist is None:
+            hist = torch.zeros(1 << 19, dtype=torch.int32, device=src.device)
+        _check_vec("yuv_histogram_dev: hist", hist, 1 << 19)
+        self._ck(self.L.agmv_hip_yuv_histogram_dev(self.ctx, fmt, src.data_ptr(), w, h, n_frames, n_pixels, quality, hist.data_ptr(), self._stream()))
+        return hist
+
+    def yuv_similarity_dev(self, fmt, src, w, h, n_frames, counts=None, yuv=None, full_range=False):
+        """similarity_dev on a YUV clip of n_frames frames of w x h; `counts` [n_frames - 1] is overwritten"""
+        import torch
+        fmt = self._check_yuv("yuv_similarity_dev: src", fmt, src, w, h, n_frames, yuv, full_range)
+        if counts is None:
+            counts = torch.empty(max(n_frames - 1, 0), dtype=torch.int32, device=src.device)
+        _check_vec("yuv_similarity_dev: counts", counts, n_frames - 1)
+        self._ck(self.L.agmv_hip_yuv_similarity_dev(self.ctx, fmt, src.data_ptr(), w, h, n_frames, counts.data_ptr(), self._stream()))
         return counts
 
     # ------------------------------------------------------------------ host-buffer path

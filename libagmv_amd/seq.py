@@ -8,11 +8,15 @@ Pixel layouts (AGMV_PIXFMT) and the tensors that hold n frames of h x w:
   "rgb24"   uint8 [n, h, w, 3]         R, G, B     (video readers)
   "bgr24"   uint8 [n, h, w, 3]         B, G, R     (OpenCV)
   "rgba32"  uint8 [n, h, w, 4]         R, G, B, A  (image decoders; A is ignored on input and 0xFF on output)
-  "rgb8p"   uint8 [n, 3, h, w]         planes R, G, B (models)"""
+  "rgb8p"   uint8 [n, 3, h, w]         planes R, G, B (models)
+  "nv12"    uint8 [n, h * 3 / 2, w]    h rows of Y, then h / 2 rows of U, V pairs      (hardware video decoders and encoders)
+  "i420"    uint8 [n, h * 3 / 2, w]    h rows of Y, then the U plane, then the V plane (software decoders, raw .yuv files)
+The two YUV 4:2:0 layouts (include/agmv.h has their definition) need even h and w here, are never inferred from a tensor, and
+take yuv="bt601" (default) or "bt709" and full_range=False (limited range) or True."""
 import ctypes as C
 import os
 
-from .hip import HERE, PIXFMT, HipUnavailable, pixfmt
+from .hip import HERE, PIXFMT, YUVFMT, HipUnavailable, pixfmt, yuvfmt
 
 SCHEDULE_FULL, SCHEDULE_PDIFS, SCHEDULE_ADAPTIVE = 1, 2, 3
 
@@ -51,10 +55,31 @@ def _device():
     return "cuda:%d" % int(os.environ.get("AGMV_DEVICE", "0"))
 
 
-def _clip_geometry(frames, fmt):
-    """(AGMV_PIXFMT value, n, h, w) of a tensor of frames; fmt None = inferred from dtype and shape.  Raises ValueError naming
-    `fmt` for a tensor that holds no clip of that layout; touches neither the library nor the device."""
+def _fmt_value(who, fmt, yuv, full_range):
+    """the fmt argument of the library for a name (or value) and the two YUV options, which only a YUV layout may carry"""
+    if fmt in YUVFMT:
+        return yuvfmt(fmt, yuv, full_range)
+    if yuv is not None or full_range:
+        raise ValueError("%s: yuv= and full_range= belong to fmt \"nv12\" and \"i420\", not to fmt %r" % (who, fmt))
+    return pixfmt(fmt)
+
+
+def _clip_geometry(frames, fmt, yuv=None, full_range=False):
+    """(fmt value for the library, n, h, w) of a tensor of frames; fmt None = inferred from dtype and shape (never a YUV layout).
+    Raises ValueError naming `fmt` for a tensor that holds no clip of that layout; touches neither the library nor the device."""
     import torch
+    if fmt is None and (yuv is not None or full_range):
+        raise ValueError("encode_frames: yuv= and full_range= need fmt \"nv12\" or \"i420\": a YUV layout is never inferred from a tensor")
+    if fmt in YUVFMT:
+        v, shape = _fmt_value("encode_frames", fmt, yuv, full_range), tuple(frames.shape)
+        if not (frames.dtype == torch.uint8 and len(shape) == 3 and shape[1] % 3 == 0 and shape[2] % 2 == 0 and shape[1] > 0 and shape[2] > 0):
+            raise ValueError("encode_frames: fmt %r does not fit a %s tensor of shape %s: uint8 [n, h * 3 / 2, w] with even h and w is needed"
+                             % (fmt, frames.dtype, shape))
+        if not frames.is_contiguous():
+            raise ValueError("encode_frames: fmt %r needs a contiguous tensor (strides %s of shape %s)" % (fmt, frames.stride(), shape))
+        return v, shape[0], shape[1] // 3 * 2, shape[2]
+    if fmt is not None:
+        _fmt_value("encode_frames", fmt, yuv, full_range)
     shape, packed = tuple(frames.shape), frames.element_size() == 4 and not frames.dtype.is_floating_point and not frames.dtype.is_complex
     if fmt is None:
         fits = []
@@ -77,11 +102,12 @@ def _clip_geometry(frames, fmt):
     return v, n, h, w
 
 
-def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedule=SCHEDULE_PDIFS, fmt=None):
+def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedule=SCHEDULE_PDIFS, fmt=None, yuv=None, full_range=False):
     """frames: contiguous CUDA tensor of n frames on the library's device, in the layout `fmt` (see the module text; None = inferred
-    from the tensor) -> the file at `path`"""
+    from the tensor, which never gives "nv12" or "i420") -> the file at `path`.  yuv ("bt601", the default, or "bt709") and
+    full_range go with the two YUV layouts only."""
     import torch
-    v, n, h, w = _clip_geometry(frames, fmt)
+    v, n, h, w = _clip_geometry(frames, fmt, yuv, full_range)
     if not (frames.is_cuda and frames.device == torch.device(_device())):
         raise ValueError("encode_frames: the frames must be on %s, got %s" % (_device(), frames.device))
     torch.cuda.synchronize(frames.device)          # the library works on streams of its own
@@ -90,18 +116,21 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
         raise ValueError("AGMV_EncodeFramesFmtDev refused its arguments (%d): %d frames of %dx%d, opt %d, schedule %d" % (rc, n, w, h, opt, schedule))
 
 
-def decode_frames(path, fmt="xrgb32"):
+def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False):
     """-> (CUDA tensor of the file's frames on the library's device in the layout `fmt`: int32 [n, h, w] of 0x00RRGGBB for "xrgb32",
-    uint8 [n, h, w, 3] / [n, h, w, 4] / [n, 3, h, w] for the byte formats; AGMV_INFO of the header)"""
+    uint8 [n, h, w, 3] / [n, h, w, 4] / [n, 3, h, w] for the byte formats, uint8 [n, h * 3 / 2, w] for "nv12" and "i420" (a file
+    of even width and height; yuv and full_range as for encode_frames); AGMV_INFO of the header)"""
     import torch
-    v = pixfmt(fmt)
+    v = _fmt_value("decode_frames", fmt, yuv, full_range)
     L = load_library()
     info = AGMV_INFO()
     rc = L.AGMV_DecodeFramesFmtDev(os.fsencode(path), None, v, 0, C.byref(info))
     if rc < 0:
         raise RuntimeError("AGMV_DecodeFramesFmtDev(%s): Error %d" % (path, -rc))
     n, h, w = info.number_of_frames, info.height, info.width
-    shape = {1: (n, h, w), 2: (n, h, w, 3), 3: (n, h, w, 3), 4: (n, h, w, 4), 5: (n, 3, h, w)}[v]
+    if v & 0xFF in YUVFMT.values() and (h % 2 or w % 2):
+        raise ValueError("decode_frames: fmt %r needs a file of even width and height, %s holds %d x %d" % (fmt, path, w, h))
+    shape = {1: (n, h, w), 2: (n, h, w, 3), 3: (n, h, w, 3), 4: (n, h, w, 4), 5: (n, 3, h, w), 16: (n, h * 3 // 2, w), 17: (n, h * 3 // 2, w)}[v & 0xFF]
     out = torch.empty(shape, dtype=torch.int32 if v == 1 else torch.uint8, device=_device())
     rc = L.AGMV_DecodeFramesFmtDev(os.fsencode(path), out.data_ptr(), v, n, None)
     if rc < 0:
