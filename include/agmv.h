@@ -354,6 +354,41 @@ int AGMV_EncodeFramesFmtDev(const char* filename, const void* d_frames, AGMV_PIX
                             AGMV_SCHEDULE schedule);
 int AGMV_DecodeFramesFmtDev(const char* filename, void* d_frames, AGMV_PIXFMT fmt, u32 cap_frames, AGMV_INFO* info);
 
+/* A clip scaled to a target size, then encoded: 1080p or 720p frames of a GPU pipeline to the 320x240, 240x160 or 120x80 files
+   this codec is for.  A source clip of sw x sh pixels per frame (src_width x src_height; need not be multiples of 4) in the layout
+   `fmt` stands for the XRGB32 clip S of that size, by the reading the text above gives for every layout, YUV included.  The scale
+   to dw x dh (width x height) with `filter` gives the XRGB32 clip D defined below, and the file is, byte for byte, the file
+   AGMV_EncodeFramesDev writes for D: the palette (its histogram is that of D), the adaptive schedule's decisions, the PDIFS
+   midpoints, the header and the chunks.  `div` is the integer quotient of non-negative integers.
+     AGMV_SCALE_NEAREST  D(X, Y) = S(((2X + 1) * sw) div (2 * dw), ((2Y + 1) * sh) div (2 * dh)): the source pixel under the target
+                         pixel's centre, in integers (64-bit on the host).  Any non-zero target size, upscales included.
+     AGMV_SCALE_AREA     the exact box filter, downscale only (dw <= sw and dh <= sh).  On an axis source pixel i occupies
+                         [i * dw, (i + 1) * dw) and target pixel X occupies [X * sw, (X + 1) * sw); wx(X, i) is the length of their
+                         overlap, an integer in 0 .. dw, and the wx of one X sum to sw.  wy(Y, j) likewise from sh and dh.  Per
+                         channel  D(X, Y) = (sum over j, i of wy(Y, j) * wx(X, i) * S(i, j) + (sw * sh) div 2) div (sw * sh).
+                         The channels are averaged in RGB, never in YUV.  Hence: a scale to the same size is the identity; a scale by
+                         an integer factor k is the mean of each k x k block, rounded half up; a source pixel contributes to at most
+                         2 target columns and 2 target rows.  sw * sh <= 2^24 is required (3840 x 2160 fits): then
+                         255 * sw * sh + (sw * sh) div 2 < 2^32 and every sum is exact in 32-bit unsigned arithmetic.
+   D is materialised once on the library's device, 4 * width * height * num_of_frames bytes (1080p NV12 to 320x240: 0.3 MB per frame
+   against 3.1 MB of source), freed before the call returns; the source is read once, in its own layout, and nothing of its size is
+   allocated.  Returns 0, or a negative value.  -1, -2 and -3 come before a file is created, before d_frames is read and before a
+   device is opened, and are looked for in this order:
+     -1  NULL pointer; unknown enum value (the filter included); unknown format
+     -3  width or height zero or not a multiple of 4; a zero source size (or one above 2^28 pixels); AGMV_SCALE_AREA with a target
+         larger than the source in either axis, or with src_width * src_height > 2^24; a GBA / NDS opt
+     -2  fewer frames than the schedule's first group reads (as for AGMV_EncodeFramesDev)
+     -4  the scaled clip cannot be allocated: after the device is opened, still before a file is created
+   The GBA / NDS opts bring their own nearest scaler, fixed target sizes and leniency: they stay on AGMV_EncodeFramesDev /
+   AGMV_EncodeFramesFmtDev and are refused here.  AGMV_OPT_I / _II / _III with a 120 x 80 target write files of the same container
+   version and palette mode as AGMV_OPT_GBA_I / _II / _III (AGMV_GetVersionFromOPT depends only on the colour count and the
+   compression), and of the same PDIFS weight for _I and _III; AGMV_OPT_GBA_II is heavy where AGMV_OPT_II is light, its
+   counterpart in weight is AGMV_OPT_ANIM. */
+typedef enum AGMV_SCALE { AGMV_SCALE_NEAREST = 1, AGMV_SCALE_AREA = 2 } AGMV_SCALE;
+int AGMV_EncodeFramesScaledDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height,
+                               u32 width, u32 height, AGMV_SCALE filter, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
+                               AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule);
+
 #ifdef __cplusplus
 }
 #endif

@@ -380,6 +380,19 @@ int agmv_hip_yuv_histogram_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, ui
 int agmv_hip_yuv_similarity_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames,
                                 uint32_t* d_counts, void* stream);
 
+/* -- a clip scaled down with the exact box filter ----------------------------------------------------
+ * AGMV_SCALE_AREA of include/agmv.h, which holds the definition: every channel of a target pixel is the mean of the source
+ * pixels under it, weighted by the overlap, in integers and rounded half up.  `fmt` is any of the seven layouts above (1 .. 5,
+ * or 16 / 17 OR-ed with the YUV flags); the channels are averaged in RGB after the layout's reading rule.  The n_frames source
+ * frames of src_w x src_h lie back to back at the layout's frame stride (agmv_hip_pixfmt_frame_bytes / agmv_hip_yuv_frame_bytes)
+ * and need no alignment beyond the layout's own (frames on 16-byte boundaries are read with 16-byte loads; YUV also needs
+ * src_w % 16 == 0 for that).  d_dst[f][Y][X], dst_w * dst_h words per frame, receives 0x00RRGGBB; nothing else is written.
+ * One kernel, asynchronous on `stream`; each source frame is read once (the rows that lie under two target rows twice), no
+ * temporary is allocated, the result does not depend on the launch.  Any n_frames.  Returns non-zero and launches nothing for
+ * an unknown format, a zero size, dst_w > src_w, dst_h > src_h or src_w * src_h > 2^24 (the bound of the 32-bit sums). */
+int agmv_hip_scale_area_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, uint32_t src_w, uint32_t src_h, uint32_t n_frames,
+                            uint32_t dst_w, uint32_t dst_h, uint32_t* d_dst, void* stream);
+
 /* optional timing: when enabled the library records HIP events on the caller's stream around its three kernel
    groups; agmv_hip_last_kernel_ms(which) returns the last launch's duration in ms (0 = k_encode, 1 = the parser
    kernels, 2 = k_decode + k_fixup, 3 = the whole of agmv_hip_parse_decode_frames_dev / agmv_hip_decode_bitstreams_dev), or a negative value if

@@ -717,6 +717,57 @@ int AGMV_EncodeFramesDev(const char* filename, const unsigned* d_frames, u32 num
 	                               schedule);
 }
 
+/* The clip scaled to width x height first (include/agmv.h has the two rules): the scaled XRGB32 clip D is materialised once on
+   the library's device -- the source is read once in its own layout, where the histogram, the similarity and the encode would
+   each read it -- and AGMV_EncodeFramesDev runs on D.  Nothing of the source's size or layout is allocated. */
+int AGMV_EncodeFramesScaledDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height,
+                               u32 width, u32 height, AGMV_SCALE filter, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
+                               AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+{
+	agmv_hip_ctx* c;
+	void* stream;
+	uint32_t *d_scaled, *d_index = NULL, *index = NULL;
+	const unsigned long long src_px = (unsigned long long)src_width * src_height;
+	size_t npx;
+	int sw, sh, failed, rc;
+	if (!known_pixfmt((int)fmt) || !filename || !d_frames || (filter != AGMV_SCALE_NEAREST && filter != AGMV_SCALE_AREA)) return -1;
+	if (opt < AGMV_OPT_I || opt > AGMV_OPT_NDS || quality < AGMV_HIGH_QUALITY || quality > AGMV_LOW_QUALITY ||
+	    (compression != AGMV_LZSS_COMPRESSION && compression != AGMV_LZ77_COMPRESSION) ||
+	    (schedule != AGMV_SCHEDULE_FULL && schedule != AGMV_SCHEDULE_PDIFS && schedule != AGMV_SCHEDULE_ADAPTIVE))
+		return -1;
+	scaled_size(opt, &sw, &sh);
+	if (sw || bad_geometry((uint32_t)width, (uint32_t)height) || width > 0xFFFFFFFFul || height > 0xFFFFFFFFul) return -3;
+	if (src_width == 0 || src_height == 0 || src_width > 0xFFFFFFFFul || src_height > 0xFFFFFFFFul || src_px > (1ull << 28)) return -3;
+	if (filter == AGMV_SCALE_AREA && (width > src_width || height > src_height || src_px > (1ull << 24))) return -3;
+	if (num_of_frames < (schedule == AGMV_SCHEDULE_FULL ? 1u : (heavy_pdifs(opt) ? 2u : 4u)) || num_of_frames > 0x7FFFFFFFul) return -2;
+
+	c = ctx();
+	npx = (size_t)width * height;
+	d_scaled = (uint32_t*)agmv_hip_malloc_on(c, 4 * npx * num_of_frames);
+	if (!d_scaled) return -4;
+	if (filter == AGMV_SCALE_NEAREST) {
+		index = agmv_scale_index((uint32_t)src_width, (uint32_t)src_height, (uint32_t)width, (uint32_t)height);
+		d_index = (uint32_t*)agmv_hip_malloc_on(c, 4 * npx);
+		if (!index || !d_index) { free(index); agmv_hip_free_on(c, d_index); agmv_hip_free_on(c, d_scaled); return -4; }
+	}
+	stream = agmv_hip_stream_create(c);
+	if (!stream) agmv_die("stream for the scaled clip");
+	if (filter == AGMV_SCALE_AREA)
+		failed = agmv_hip_scale_area_dev(c, (int)fmt, d_frames, (uint32_t)src_width, (uint32_t)src_height, (uint32_t)num_of_frames, (uint32_t)width,
+		                                 (uint32_t)height, d_scaled, stream);
+	else
+		failed = agmv_hip_memcpy_async(c, d_index, index, 4 * npx, 0, stream) ||
+		         (AGMV_FMT_IS_YUV((int)fmt) ? agmv_hip_yuv_gather_dev(c, (int)fmt, d_frames, (uint32_t)src_width, (uint32_t)src_height, (uint32_t)num_of_frames,
+		                                                             d_index, npx, d_scaled, stream)
+		                                    : agmv_hip_gather_fmt_dev(c, (int)fmt, d_frames, (size_t)src_px, (uint32_t)num_of_frames, d_index, npx, d_scaled, stream));
+	if (failed || agmv_hip_stream_sync(c, stream)) agmv_die("frame scale");
+	agmv_hip_stream_destroy(c, stream);
+	free(index); agmv_hip_free_on(c, d_index);
+	rc = AGMV_EncodeFramesDev(filename, d_scaled, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule);
+	agmv_hip_free_on(c, d_scaled);
+	return rc;
+}
+
 /* ------------------------------------------------------------------------------------------
  * sequence decoders (reference src/agmv_decode.c:455-647): host does the chunk scan and the LZ stage
  * frame by frame into ONE persistent buffer (so the stale-tail semantics hold), the GPU parses and

@@ -3055,6 +3055,153 @@ template <int FMT> __global__ __launch_bounds__(256) void k_yuv_similarity(const
 	}
 }
 
+// ---- exact box-filter downscale of a clip in any of the seven layouts (AGMV_SCALE_AREA of include/agmv.h, which defines it) ----
+// On an axis source pixel i covers [i * dw, (i + 1) * dw) and target pixel X covers [X * sw, (X + 1) * sw): a source pixel is dw
+// units long, lies in at most two target columns, and the weights of a target column sum to sw.  A scatter: a workgroup owns one
+// (frame, target row Y, tile of SC_TILE target columns) at a time and walks the source rows that overlap Y.  A lane takes a group
+// of 16 consecutive pixels of one source row -- groups are cut at multiples of 16 of the pixel's index in the FRAME, so that on a
+// clip whose frames (and planes) start on 16-byte boundaries a group that lies inside the row is read with the 16-byte loads of
+// k_pix_to_xrgb / k_yuv_to_xrgb (YUV: 16 luma bytes and the 16 chroma bytes of row j >> 1, which needs sw % 16 == 0); the groups
+// at a row's head and tail, and every group of any other clip, go pixel by pixel through the layout's byte reader.  The lane folds
+// wx * channel of its pixels per target column in registers and adds wy * that into the tile's accumulators in LDS once per
+// column it touches (integer adds: any order gives the same sum).  After the barrier each lane finishes its columns --
+// (sum + area / 2) / area, exact in 32 bits because 255 * sw * sh + sw * sh / 2 < 2^32 for sw * sh <= 2^24 -- clears them for the
+// next item and stores the row.  No float, no global atomic.  Items are walked with a grid stride: any number of frames.
+#define SC_TILE 1024
+
+struct ScaleArgs {
+	const uint8_t* src;
+	uint32_t* dst;
+	size_t frame_bytes;
+	unsigned long long items;                                      // n_frames * dh * tiles
+	uint32_t sw, sh, dw, dh, tiles;
+	int wide, small;                                               // 16-byte loads allowed; sw * dw < 2^32
+	yuv_rd m;
+};
+
+// 16 pixels of one source row as they lie in memory: p0 is their index in the frame (a multiple of 16), j their row
+template <int FMT> struct sc_group {
+	static constexpr bool YUV = FMT >= PF_NV12;
+	static constexpr int NV = YUV ? 2 : (FMT == PF_XRGB32 || FMT == PF_RGBA32 ? 4 : 3);
+	pf_u32x4 v[NV];                                                // YUV: luma, then chroma as yuv_raw::c holds it
+
+	__device__ __forceinline__ void load(const uint8_t* __restrict__ fr, uint32_t w, uint32_t h, uint32_t p0, uint32_t j)
+	{
+		if constexpr (YUV) {
+			const uint32_t x0 = p0 - j * w;
+			const uint8_t* c = fr + (size_t)w * h;
+			v[0] = *reinterpret_cast<const pf_u32x4*>(fr + p0);
+			if constexpr (FMT == PF_NV12) v[1] = *reinterpret_cast<const pf_u32x4*>(c + (size_t)(j >> 1) * w + x0);
+			else {
+				const size_t cw = w >> 1, ch = (h + 1) >> 1, o = (size_t)(j >> 1) * cw + (x0 >> 1);
+				const pf_u32x2 uu = *reinterpret_cast<const pf_u32x2*>(c + o), vv = *reinterpret_cast<const pf_u32x2*>(c + cw * ch + o);
+				v[1][0] = uu[0]; v[1][1] = uu[1]; v[1][2] = vv[0]; v[1][3] = vv[1];
+			}
+		} else if constexpr (NV == 4) {
+#pragma unroll
+			for (int k = 0; k < 4; k++) v[k] = *reinterpret_cast<const pf_u32x4*>(fr + 4 * (size_t)p0 + 16 * k);
+		} else {
+			const pf_raw<FMT> r = pf_load16<FMT, false>(fr, (size_t)w * h, p0);
+#pragma unroll
+			for (int k = 0; k < 3; k++) v[k] = r.v[k];
+		}
+	}
+
+	// pixel i (a constant once the caller's loop is unrolled) as 0x00RRGGBB
+	__device__ __forceinline__ uint32_t pixel(int i, const yuv_rd& m) const
+	{
+		if constexpr (YUV) {
+			yuv_raw r;
+			r.y0 = v[0]; r.y1 = v[0]; r.c = v[1];
+			return yuv_pixel(m, (v[0][i >> 2] >> (8 * (i & 3))) & 0xff, yuv_patch_chroma<FMT>(r, i >> 1, m));
+		} else if constexpr (FMT == PF_XRGB32) {
+			return v[i >> 2][i & 3] & 0xffffffu;
+		} else {
+			pf_raw<FMT> r;
+#pragma unroll
+			for (int k = 0; k < NV; k++) r.v[k] = v[k];
+			return pf_pixel<FMT>(r, i);
+		}
+	}
+};
+
+// pixel (x, j) of a frame as 0x00RRGGBB through the layout's byte reader
+template <int FMT> __device__ __forceinline__ uint32_t sc_read(const uint8_t* __restrict__ fr, uint32_t w, uint32_t h, uint32_t x, uint32_t j, const yuv_rd& m)
+{
+	if constexpr (FMT >= PF_NV12) return yuv_read<FMT>(fr, w, h, x, j, m);
+	else if constexpr (FMT == PF_XRGB32) return reinterpret_cast<const uint32_t*>(fr)[(size_t)j * w + x] & 0xffffffu;
+	else return pf_read(FMT, fr, (size_t)w * h, (size_t)j * w + x);
+}
+
+// a lane's walk along a source row: it stands t units into target column X and holds the sums of wx * channel for that column
+struct sc_run { uint32_t X, t, r, g, b; };
+
+__device__ __forceinline__ void sc_flush(uint32_t (*acc)[SC_TILE], const sc_run& s, uint32_t wy, uint32_t X0, uint32_t X1)
+{
+	if (s.X >= X0 && s.X < X1) {
+		atomicAdd(&acc[0][s.X - X0], s.r * wy); atomicAdd(&acc[1][s.X - X0], s.g * wy); atomicAdd(&acc[2][s.X - X0], s.b * wy);
+	}
+}
+
+// the next source pixel, colour c: min(dw, what is left of column X) units go to X, the rest opens column X + 1
+__device__ __forceinline__ void sc_step(uint32_t (*acc)[SC_TILE], sc_run& s, uint32_t c, uint32_t sw, uint32_t dw, uint32_t wy, uint32_t X0, uint32_t X1)
+{
+	const uint32_t r = (c >> 16) & 0xff, g = (c >> 8) & 0xff, b = c & 0xff, w1 = min(dw, sw - s.t);
+	s.r += w1 * r; s.g += w1 * g; s.b += w1 * b; s.t += w1;
+	if (s.t == sw) {
+		sc_flush(acc, s, wy, X0, X1);
+		s.X++; s.t = dw - w1;
+		s.r = s.t * r; s.g = s.t * g; s.b = s.t * b;
+	}
+}
+
+template <int FMT> __global__ __launch_bounds__(256) void k_scale_area(ScaleArgs A)
+{
+	__shared__ uint32_t s_acc[3][SC_TILE];
+	const uint32_t sw = A.sw, sh = A.sh, dw = A.dw, dh = A.dh, area = sw * sh, per = dh * A.tiles;
+	for (uint32_t k = threadIdx.x; k < 3 * SC_TILE; k += 256) (&s_acc[0][0])[k] = 0;
+	__syncthreads();
+	for (unsigned long long item = blockIdx.x; item < A.items; item += gridDim.x) {
+		const uint32_t f = (uint32_t)(item / per), rem = (uint32_t)(item - (unsigned long long)f * per), Y = rem / A.tiles, tile = rem - Y * A.tiles;
+		const uint32_t X0 = tile * SC_TILE, X1 = min(X0 + SC_TILE, dw);
+		// the source columns that touch the tile, the source rows that touch Y
+		const uint32_t i_lo = (uint32_t)((unsigned long long)X0 * sw / dw), i_hi = (uint32_t)(((unsigned long long)X1 * sw + dw - 1) / dw);
+		const unsigned long long y_lo = (unsigned long long)Y * sh, y_hi = y_lo + sh;
+		const uint32_t j0 = (uint32_t)(y_lo / dh), j1 = (uint32_t)((y_hi + dh - 1) / dh);
+		const uint32_t ng = ((i_hi - i_lo + 15) >> 4) + 1, n_task = (j1 - j0) * ng;
+		const uint8_t* fr = A.src + (size_t)f * A.frame_bytes;
+		for (uint32_t task = threadIdx.x; task < n_task; task += 256) {
+			const uint32_t jr = task / ng, j = j0 + jr, row0 = j * sw, lo = row0 + i_lo, hi = row0 + i_hi;
+			const uint32_t p0 = ((lo >> 4) + (task - jr * ng)) << 4;
+			if (p0 >= hi) continue;
+			const uint32_t a = max(p0, lo), b = min(p0 + 16, hi);      // the group's pixels of this row and tile
+			const unsigned long long r_lo = (unsigned long long)j * dh;
+			const uint32_t wy = (uint32_t)(min(r_lo + dh, y_hi) - max(r_lo, y_lo));
+			sc_run s;
+			if (A.small) { const uint32_t u = (a - row0) * dw; s.X = u / sw; s.t = u - s.X * sw; }
+			else { const unsigned long long u = (unsigned long long)(a - row0) * dw; s.X = (uint32_t)(u / sw); s.t = (uint32_t)(u - (unsigned long long)s.X * sw); }
+			s.r = s.g = s.b = 0;
+			if (A.wide && b - a == 16) {
+				sc_group<FMT> grp;
+				grp.load(fr, sw, sh, p0, j);
+#pragma unroll
+				for (int i = 0; i < 16; i++) sc_step(s_acc, s, grp.pixel(i, A.m), sw, dw, wy, X0, X1);
+			} else {
+				for (uint32_t p = a; p < b; p++) sc_step(s_acc, s, sc_read<FMT>(fr, sw, sh, p - row0, j, A.m), sw, dw, wy, X0, X1);
+			}
+			if (s.t) sc_flush(s_acc, s, wy, X0, X1);
+		}
+		__syncthreads();
+		uint32_t* out = A.dst + ((size_t)f * dh + Y) * dw + X0;
+		for (uint32_t k = threadIdx.x; k < X1 - X0; k += 256) {
+			const uint32_t r = (s_acc[0][k] + area / 2) / area, g = (s_acc[1][k] + area / 2) / area, b = (s_acc[2][k] + area / 2) / area;
+			s_acc[0][k] = 0; s_acc[1][k] = 0; s_acc[2][k] = 0;
+			out[k] = r << 16 | g << 8 | b;
+		}
+		__syncthreads();
+	}
+}
+
 // A spin of k_encode that ran into its bound leaves ctrl[1] != 0 and the kernel carries on with a wrong offset: the bytes of
 // the batch are not to be used.  So that a caller who skips agmv_hip_check cannot take them for good ones, every size of
 // the batch is then overwritten with 0xFFFFFFFF (no frame is that long: agmv_hip_max_usize < 2^32).
@@ -4285,6 +4432,40 @@ extern "C" int agmv_hip_yuv_similarity_dev(agmv_hip_ctx* c, int fmt, const void*
 	CK(hipMemsetAsync(d_counts, 0, 4 * (size_t)(n_frames - 1), (hipStream_t)stream));
 	const int wide = yuv_wide(fmt, d_src, w, h, n_frames);
 	YUV_LAUNCH(k_yuv_similarity, (const uint8_t*)d_src, n_frames, w, h, agmv_hip_yuv_frame_bytes(fmt, w, h), wide, YUV_RD[(fmt >> 8) & 3], d_counts);
+	CK(hipGetLastError());
+	return 0;
+}
+
+// ---- the exact box-filter downscale (AGMV_SCALE_AREA) of a clip in any layout: fmt as above, the YUV formats with their flags ----
+extern "C" int agmv_hip_scale_area_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t src_w, uint32_t src_h, uint32_t n_frames, uint32_t dst_w, uint32_t dst_h,
+                                       uint32_t* d_dst, void* stream)
+{
+	if (need_ctx(c, false)) return -1;
+	const int yuv = yuv_base(fmt);
+	if (!yuv && bad_pixfmt(fmt)) return -1;
+	if (src_w == 0 || src_h == 0 || dst_w == 0 || dst_h == 0 || dst_w > src_w || dst_h > src_h || (unsigned long long)src_w * src_h > (1ull << 24)) {
+		snprintf(g_err, sizeof(g_err), "agmv_hip: area scale of %u x %u to %u x %u (a downscale of at most 2^24 source pixels is needed)", src_w, src_h, dst_w, dst_h);
+		return -1;
+	}
+	if (n_frames == 0) return 0;
+	ScaleArgs A;
+	A.src = (const uint8_t*)d_src; A.dst = d_dst;
+	A.frame_bytes = yuv ? agmv_hip_yuv_frame_bytes(fmt, src_w, src_h) : agmv_hip_pixfmt_frame_bytes(fmt, (size_t)src_w * src_h);
+	A.sw = src_w; A.sh = src_h; A.dw = dst_w; A.dh = dst_h; A.tiles = (dst_w + SC_TILE - 1) / SC_TILE;
+	A.items = (unsigned long long)n_frames * dst_h * A.tiles;
+	A.wide = yuv ? yuv_wide(fmt, d_src, src_w, src_h, n_frames) : pf_aligned(fmt, d_src, (size_t)src_w * src_h, n_frames);
+	A.small = (unsigned long long)src_w * dst_w < (1ull << 32);
+	A.m = YUV_RD[(fmt >> 8) & 3];
+	const dim3 grid((unsigned)(A.items < 65536 ? A.items : 65536)), block(256);
+	switch (yuv ? yuv : fmt) {
+	case PF_XRGB32: hipLaunchKernelGGL(k_scale_area<PF_XRGB32>, grid, block, 0, (hipStream_t)stream, A); break;
+	case PF_RGB24: hipLaunchKernelGGL(k_scale_area<PF_RGB24>, grid, block, 0, (hipStream_t)stream, A); break;
+	case PF_BGR24: hipLaunchKernelGGL(k_scale_area<PF_BGR24>, grid, block, 0, (hipStream_t)stream, A); break;
+	case PF_RGBA32: hipLaunchKernelGGL(k_scale_area<PF_RGBA32>, grid, block, 0, (hipStream_t)stream, A); break;
+	case PF_RGB8P: hipLaunchKernelGGL(k_scale_area<PF_RGB8P>, grid, block, 0, (hipStream_t)stream, A); break;
+	case PF_NV12: hipLaunchKernelGGL(k_scale_area<PF_NV12>, grid, block, 0, (hipStream_t)stream, A); break;
+	default: hipLaunchKernelGGL(k_scale_area<PF_I420>, grid, block, 0, (hipStream_t)stream, A); break;
+	}
 	CK(hipGetLastError());
 	return 0;
 }

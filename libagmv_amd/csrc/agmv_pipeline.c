@@ -149,6 +149,23 @@ uint32_t* agmv_source_index(uint32_t sw, uint32_t sh, int scale_w, int scale_h, 
 	return idx;
 }
 
+/* AGMV_SCALE_NEAREST of include/agmv.h as such a table: target pixel (X, Y) of the dw x dh frame reads the source pixel under
+   its centre, (((2X + 1) * sw) / (2 * dw), ((2Y + 1) * sh) / (2 * dh)) in integers.  NULL without memory. */
+uint32_t* agmv_scale_index(uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh)
+{
+	uint32_t* idx = (uint32_t*)malloc((size_t)dw * dh * sizeof(uint32_t));
+	uint32_t* col = (uint32_t*)malloc((size_t)dw * sizeof(uint32_t));
+	uint32_t x, y;
+	if (!idx || !col) { free(idx); free(col); return NULL; }
+	for (x = 0; x < dw; x++) col[x] = (uint32_t)(((2ull * x + 1) * sw) / (2ull * dw));
+	for (y = 0; y < dh; y++) {
+		const uint32_t row = (uint32_t)(((2ull * y + 1) * sh) / (2ull * dh)) * sw;
+		for (x = 0; x < dw; x++) idx[(size_t)y * dw + x] = row + col[x];
+	}
+	free(col);
+	return idx;
+}
+
 /* source frame `idx` as the encoder sees it: BMP -> 0x00RRGGBB, optional GBA/NDS nearest scale (agmv_source_index) */
 void agmv_load_source(const char* dir, const char* base, long idx, int scale_w, int scale_h, uint32_t w, uint32_t h, uint32_t* dst)
 {

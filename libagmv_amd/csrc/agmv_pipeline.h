@@ -14,6 +14,7 @@ void agmv_pool_stop(agmv_pool* p);                       /* runs what is queued,
 
 void agmv_frame_path(char* out, size_t cap, const char* dir, const char* base, long idx);
 uint32_t* agmv_source_index(uint32_t sw, uint32_t sh, int scale_w, int scale_h, uint32_t w, uint32_t h);
+uint32_t* agmv_scale_index(uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh);
 void agmv_load_source(const char* dir, const char* base, long idx, int scale_w, int scale_h, uint32_t w, uint32_t h, uint32_t* dst);
 
 /* where the frames of a sequence encode come from: the numbered BMP files dir/base<idx>.bmp, or (d_frames != NULL) a clip of

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "agmv_hip_histogram_fmt_dev", "agmv_hip_similarity_fmt_dev",
     "agmv_hip_yuv_frame_bytes", "agmv_hip_yuv_to_xrgb_dev", "agmv_hip_yuv_from_xrgb_dev", "agmv_hip_yuv_gather_dev",
     "agmv_hip_yuv_histogram_dev", "agmv_hip_yuv_similarity_dev",
+    "agmv_hip_scale_area_dev",
 ]
 
 
@@ -160,6 +161,9 @@ def load_library(path=None):
         for f in (L.agmv_hip_yuv_to_xrgb_dev, L.agmv_hip_yuv_from_xrgb_dev, L.agmv_hip_yuv_gather_dev, L.agmv_hip_yuv_histogram_dev,
                   L.agmv_hip_yuv_similarity_dev):
             f.restype = C.c_int
+    if path is None or hasattr(L, "agmv_hip_scale_area_dev"):
+        L.agmv_hip_scale_area_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, u32, u32, vp, vp]
+        L.agmv_hip_scale_area_dev.restype = C.c_int
     L.agmv_hip_check.argtypes = [vp, vp]
     L.agmv_hip_enable_timing.argtypes = [vp, C.c_int]
     L.agmv_hip_enable_timing.restype = C.c_int
@@ -799,6 +803,23 @@ class AgmvHip:
         _check_vec("yuv_similarity_dev: counts", counts, n_frames - 1)
         self._ck(self.L.agmv_hip_yuv_similarity_dev(self.ctx, fmt, src.data_ptr(), w, h, n_frames, counts.data_ptr(), self._stream()))
         return counts
+
+    # ------------------------------------------------------------------ a clip scaled down (AGMV_SCALE_AREA of include/agmv.h)
+    def scale_area_dev(self, fmt, src, w, h, n_frames, dst_w, dst_h, out=None, yuv=None, full_range=False):
+        """src: clip of n_frames frames of w x h in fmt (any name of PIXFMT or YUVFMT, or its value) -> int32 [n_frames, dst_h, dst_w]
+        of 0x00RRGGBB: the exact box filter, dst_w <= w, dst_h <= h, w * h <= 2^24"""
+        import torch
+        if fmt in YUVFMT or (isinstance(fmt, int) and (fmt & 0xFF) in YUVFMT.values()):
+            fmt = self._check_yuv("scale_area_dev: src", fmt, src, w, h, n_frames, yuv, full_range)
+        else:
+            if yuv is not None or full_range:
+                raise ValueError("scale_area_dev: yuv= and full_range= belong to fmt \"nv12\" and \"i420\", not to fmt %r" % (fmt,))
+            fmt = self._check_clip("scale_area_dev: src", fmt, src, n_frames * self.pixfmt_frame_bytes(fmt, w * h))
+        if out is None:
+            out = torch.empty((n_frames, dst_h, dst_w), dtype=torch.int32, device=src.device)
+        _check_vec("scale_area_dev: out", out, n_frames * dst_w * dst_h)
+        self._ck(self.L.agmv_hip_scale_area_dev(self.ctx, fmt, src.data_ptr(), w, h, n_frames, dst_w, dst_h, out.data_ptr(), self._stream()))
+        return out
 
     # ------------------------------------------------------------------ host-buffer path
     def encode_host(self, frames, first_frame_count=0, ientries=None):

@@ -1,5 +1,5 @@
-"""Whole .agmv sequences from and to frames in GPU memory: ctypes calls of AGMV_EncodeFramesFmtDev / AGMV_DecodeFramesFmtDev
-(include/agmv.h, libagmv.so).  No logic here: the schedules, the container, both LZ stages and the reading and writing of the
+"""Whole .agmv sequences from and to frames in GPU memory: ctypes calls of AGMV_EncodeFramesFmtDev / AGMV_EncodeFramesScaledDev /
+AGMV_DecodeFramesFmtDev (include/agmv.h, libagmv.so).  No logic here: the schedules, the container, both LZ stages and the reading and writing of the
 caller's pixel layout are the library's; torch holds the frames.  The frames live on the library's own device (env AGMV_DEVICE,
 default 0).
 
@@ -19,6 +19,7 @@ import os
 from .hip import HERE, PIXFMT, YUVFMT, HipUnavailable, pixfmt, yuvfmt
 
 SCHEDULE_FULL, SCHEDULE_PDIFS, SCHEDULE_ADAPTIVE = 1, 2, 3
+SCALE = {"nearest": 1, "area": 2}          # AGMV_SCALE of include/agmv.h, which defines both filters
 
 
 class AGMV_INFO(C.Structure):
@@ -47,6 +48,8 @@ def load_library():
         L.AGMV_EncodeFramesFmtDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int] + [C.c_ulong] * 4 + [C.c_int] * 4
         L.AGMV_DecodeFramesFmtDev.restype = C.c_int
         L.AGMV_DecodeFramesFmtDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.POINTER(AGMV_INFO)]
+        L.AGMV_EncodeFramesScaledDev.restype = C.c_int
+        L.AGMV_EncodeFramesScaledDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int] + [C.c_ulong] * 5 + [C.c_int, C.c_ulong] + [C.c_int] * 4
         _lib = L
     return _lib
 
@@ -102,18 +105,42 @@ def _clip_geometry(frames, fmt, yuv=None, full_range=False):
     return v, n, h, w
 
 
-def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedule=SCHEDULE_PDIFS, fmt=None, yuv=None, full_range=False):
+def _scale_target(size, scale):
+    """(filter value, h, w) of encode_frames' size= and scale=, or None for size=None; touches neither the library nor the device"""
+    if scale not in SCALE:
+        raise ValueError("encode_frames: scale %r is unknown: one of %s is needed" % (scale, ", ".join("\"%s\"" % k for k in sorted(SCALE))))
+    if size is None:
+        if scale != "area":
+            raise ValueError("encode_frames: scale=%r needs size=(h, w): without a target size nothing is scaled" % (scale,))
+        return None
+    if not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and not isinstance(v, bool) and v > 0 for v in size)):
+        raise ValueError("encode_frames: size must be (h, w), two positive ints, got %r" % (size,))
+    return SCALE[scale], size[0], size[1]
+
+
+def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedule=SCHEDULE_PDIFS, fmt=None, yuv=None, full_range=False,
+                  size=None, scale="area"):
     """frames: contiguous CUDA tensor of n frames on the library's device, in the layout `fmt` (see the module text; None = inferred
     from the tensor, which never gives "nv12" or "i420") -> the file at `path`.  yuv ("bt601", the default, or "bt709") and
-    full_range go with the two YUV layouts only."""
+    full_range go with the two YUV layouts only.  size=(h, w), in tensor order, scales the clip to that size first
+    (AGMV_EncodeFramesScaledDev): scale "area" is the exact box filter (a downscale), "nearest" the pixel under the target
+    pixel's centre; the target must be multiples of 4, the source need not be."""
     import torch
+    target = _scale_target(size, scale)
     v, n, h, w = _clip_geometry(frames, fmt, yuv, full_range)
     if not (frames.is_cuda and frames.device == torch.device(_device())):
         raise ValueError("encode_frames: the frames must be on %s, got %s" % (_device(), frames.device))
     torch.cuda.synchronize(frames.device)          # the library works on streams of its own
-    rc = load_library().AGMV_EncodeFramesFmtDev(os.fsencode(path), frames.data_ptr(), v, n, w, h, fps, opt, quality, compression, schedule)
+    if target is None:
+        rc = load_library().AGMV_EncodeFramesFmtDev(os.fsencode(path), frames.data_ptr(), v, n, w, h, fps, opt, quality, compression, schedule)
+        if rc:
+            raise ValueError("AGMV_EncodeFramesFmtDev refused its arguments (%d): %d frames of %dx%d, opt %d, schedule %d" % (rc, n, w, h, opt, schedule))
+        return
+    filt, th, tw = target
+    rc = load_library().AGMV_EncodeFramesScaledDev(os.fsencode(path), frames.data_ptr(), v, n, w, h, tw, th, filt, fps, opt, quality, compression, schedule)
     if rc:
-        raise ValueError("AGMV_EncodeFramesFmtDev refused its arguments (%d): %d frames of %dx%d, opt %d, schedule %d" % (rc, n, w, h, opt, schedule))
+        raise ValueError("AGMV_EncodeFramesScaledDev refused its arguments (%d): %d frames of %dx%d scaled (%s) to %dx%d, opt %d, schedule %d"
+                         % (rc, n, w, h, scale, tw, th, opt, schedule))
 
 
 def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False):
