@@ -1,7 +1,11 @@
 """libagmv_amd -- MI355X-native hot path of the AGMV codec (libagmv drop-in for that path).
 
 Layout
-  csrc/agmv_hip.hip   hand-written gfx950 kernels + the C-ABI of include/agmv_hip.h
+  csrc/agmv_hip.hip   hand-written gfx950 kernels of the codec (table, encode, parse, decode, pack) + the core of the
+                      C-ABI of include/agmv_hip.h (context, palette, streams, memory)
+  csrc/agmv_clip_hip.hip  the clip front end of that C-ABI: synth, interp, histogram, similarity, gather, the byte and
+                      YUV 4:2:0 layouts, the area scale
+  csrc/agmv_lz*_hip.hip   the LZSS / LZ77 stages of encoder and decoder on the GPU
   csrc/*.c            host C: libagmv-compatible API (include/agmv.h), LZSS/LZ77, container,
                       BMP I/O, palette build, synthetic clip generator
   hip.py              ctypes binding of the C-ABI for tests / bench (torch = device memory only)

@@ -16,7 +16,8 @@
 //   k_fixup         sequential repair of blocks whose value depends on an earlier GOP
 //                   (stale tail after `escape`, src/agmv_decode.c:229-232; last-block FILL
 //                   quirk :264-266)
-// The encoder's LZSS stage (AGMV_LZSS, src/agmv_encode.c:106-177) is in agmv_lz_hip.hip.
+// The encoder's LZSS stage (AGMV_LZSS, src/agmv_encode.c:106-177) is in agmv_lz_hip.hip; the clip front end (synth, interp,
+// histogram, similarity, gather, pixel layouts, area scale) is in agmv_clip_hip.hip.
 // Integer/byte work only: no MFMA. The bound is HBM (4 B/px in, usize out).
 #include <hip/hip_runtime.h>
 
@@ -2295,913 +2296,6 @@ __global__ __launch_bounds__(64) void k_fixup(DecArgs A)
 	if (dep) A.dirty[nwords + 1] = 1u;                         // the batch depends on the decoder state before it
 }
 
-// ----------------------------------------------------------------------------------------------
-// caller-side helpers: synthetic clip, PDIFS midpoint, palette histogram
-// ----------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z)
-{
-	z += 0x9E3779B97F4A7C15ull;
-	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-	return z ^ (z >> 31);
-}
-
-// agmv_synth_v1 (integer-only, also stated in agmv_synth.c and tests/synth.py)
-__host__ __device__ __forceinline__ uint32_t synth_pixel(uint32_t W, uint32_t H, uint32_t x, uint32_t y, uint32_t t, uint64_t seed)
-{
-	const uint64_t te = x < W / 4 ? 0 : t;                     // region A: static
-	if (y >= 3 * H / 4) {                                      // region B: flat 32x32 tiles
-		uint64_t tileid = ((uint64_t)(y / 32) << 40) | ((uint64_t)(x / 32) << 20) | (te / 8);
-		return (uint32_t)(splitmix64(seed ^ tileid) & 0xFFFFFFu);
-	}
-	const uint64_t h = splitmix64(seed ^ (te * 0x9E3779B97F4A7C15ull) ^ (((uint64_t)y << 32) | x));
-	uint32_t r = (uint32_t)(((uint64_t)x * 255 / (W - 1) + 2 * te) & 255);
-	uint32_t g = (uint32_t)(((uint64_t)y * 255 / (H - 1) + te) & 255);
-	uint32_t b = (uint32_t)((((uint64_t)x + y) / 2 + 3 * te) & 255);
-	if ((h & 15) == 0) { r ^= (uint32_t)(h >> 8) & 7; g ^= (uint32_t)(h >> 16) & 7; b ^= (uint32_t)(h >> 24) & 7; }
-	return r << 16 | g << 8 | b;
-}
-
-__global__ __launch_bounds__(256) void k_synth(uint32_t* __restrict__ pix, uint32_t W, uint32_t H, uint32_t t0,
-                                               uint32_t n_frames, uint64_t seed)
-{
-	const size_t npx = (size_t)W * H, total = npx * n_frames;
-	size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-	const size_t stride = (size_t)gridDim.x * 256;
-	for (; i < total; i += stride) {
-		uint32_t f = (uint32_t)(i / npx);
-		uint32_t p = (uint32_t)(i - (size_t)f * npx);
-		pix[i] = synth_pixel(W, H, p % W, p / W, t0 + f, seed);
-	}
-}
-
-// AGMV_InterpFrame, src/agmv_utils.c:949-969: c1 + ((c2 - c1) >> 1) per channel, arithmetic shift
-__global__ __launch_bounds__(256) void k_interp(uint32_t* __restrict__ out, const uint32_t* __restrict__ f1,
-                                                const uint32_t* __restrict__ f2, size_t n)
-{
-	size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-	const size_t stride = (size_t)gridDim.x * 256;
-	for (; i < n; i += stride) {
-		uint32_t a = f1[i], b = f2[i];
-		int r1 = (a >> 16) & 0xff, g1 = (a >> 8) & 0xff, b1 = a & 0xff;
-		int r2 = (b >> 16) & 0xff, g2 = (b >> 8) & 0xff, b2 = b & 0xff;
-		int r = r1 + ((r2 - r1) >> 1), g = g1 + ((g2 - g1) >> 1), bb = b1 + ((b2 - b1) >> 1);
-		out[i] = (uint32_t)(r << 16 | g << 8 | bb);
-	}
-}
-
-// AGMV_QuantizeColor, src/agmv_utils.c:695-742
-__device__ __forceinline__ uint32_t quantize_color(uint32_t c, int quality)
-{
-	uint32_t r = (c >> 16) & 0xff, g = (c >> 8) & 0xff, b = c & 0xff;
-	if (quality == 2) return (r >> 3) << 12 | (g >> 2) << 6 | (b >> 2);     // MID
-	if (quality == 3) return (r >> 3) << 11 | (g >> 2) << 5 | (b >> 3);     // LOW
-	return (r >> 2) << 13 | (g >> 2) << 7 | (b >> 1);                       // HIGH / default
-}
-
-__global__ __launch_bounds__(256) void k_histogram(const uint32_t* __restrict__ pix, size_t n, int quality,
-                                                   uint32_t* __restrict__ hist)
-{
-	// lanes hold consecutive pixels; neighbours mostly fall into the same bin, so each RUN of equal codes inside the
-	// wave adds its length with one atomic (flat or static areas: one atomic per 64 pixels)
-	const int lane = threadIdx.x & 63;
-	const size_t stride = (size_t)gridDim.x * 256;
-	for (size_t i0 = (size_t)blockIdx.x * 256 + (threadIdx.x & ~63); i0 < n; i0 += stride) {
-		const size_t i = i0 + lane;
-		const bool live = i < n;
-		const uint32_t c = live ? quantize_color(pix[i], quality) : 0xFFFFFFFFu;
-		const uint32_t prev = __shfl_up(c, 1, 64);
-		const bool leader = live && (lane == 0 || c != prev);
-		const unsigned long long lead = __ballot(leader), alive = __ballot(live);
-		if (leader) {
-			const unsigned long long rest = lane == 63 ? 0ull : lead >> (lane + 1);
-			const uint32_t end = rest ? (uint32_t)lane + 1u + (uint32_t)__builtin_ctzll(rest) : (uint32_t)__popcll(alive);
-			atomicAdd(hist + c, end - (uint32_t)lane);
-		}
-	}
-}
-
-// The grey-equality count behind AGMV_EncodeVideo's frame skipping, AGMV_CompareFrameSimilarity (src/agmv_utils.c:920-947):
-// counts[f] = number of positions at which frames f and f + 1 have the same grey, grey = (R + G + B) / 3 in integers (equal to
-// the reference's (u8)((r + g + b) / 3.0f) for all 766 sums).  A streaming reduction: a lane owns 8 pixel positions (two
-// 16-byte loads per frame, each coalesced over the wave) and walks them through ALL frames, keeping the greys of the frame
-// before in two registers, so every frame is read once per launch, not once per pair.  The loads of frame f + 1 are issued
-// before frame f is compared.  Per pair the lane's count goes through the wave (__shfl_xor), then one LDS atomic per wave into
-// the block's slot of the pair, and the block flushes its slots with one global atomic per pair every SIM_SEG pairs.
-#define SIM_SEG 1024
-
-__device__ __forceinline__ uint32_t sim_greys(uint4 v)        // the greys of 4 pixels, one per byte; bits >= 24 are ignored
-{
-	const uint32_t a = (((v.x >> 16) & 0xff) + ((v.x >> 8) & 0xff) + (v.x & 0xff)) / 3u;
-	const uint32_t b = (((v.y >> 16) & 0xff) + ((v.y >> 8) & 0xff) + (v.y & 0xff)) / 3u;
-	const uint32_t c = (((v.z >> 16) & 0xff) + ((v.z >> 8) & 0xff) + (v.z & 0xff)) / 3u;
-	const uint32_t d = (((v.w >> 16) & 0xff) + ((v.w >> 8) & 0xff) + (v.w & 0xff)) / 3u;
-	return a | b << 8 | c << 16 | d << 24;
-}
-
-__device__ __forceinline__ uint32_t sim_equal_bytes(uint32_t a, uint32_t b)
-{
-	const uint32_t x = a ^ b;
-	return ((x & 0xffu) == 0) + ((x & 0xff00u) == 0) + ((x & 0xff0000u) == 0) + ((x & 0xff000000u) == 0);
-}
-
-// pixels p .. p + 3 of a frame of npx pixels, 0 where there is none.  vec: npx % 4 == 0 and the clip is 16-byte aligned, so
-// every frame is, and p < npx implies p + 3 < npx
-__device__ __forceinline__ uint4 sim_load(const uint32_t* __restrict__ fr, size_t p, size_t npx, bool vec)
-{
-	if (vec) return p < npx ? *reinterpret_cast<const uint4*>(fr + p) : make_uint4(0, 0, 0, 0);
-	uint4 v;
-	v.x = p < npx ? fr[p] : 0; v.y = p + 1 < npx ? fr[p + 1] : 0; v.z = p + 2 < npx ? fr[p + 2] : 0; v.w = p + 3 < npx ? fr[p + 3] : 0;
-	return v;
-}
-
-__global__ __launch_bounds__(256) void k_similarity(const uint32_t* __restrict__ pix, uint32_t n_frames, size_t npx, int vec,
-                                                    uint32_t* __restrict__ counts)
-{
-	__shared__ uint32_t s_cnt[SIM_SEG];
-	const size_t pa = ((size_t)blockIdx.x * 512 + threadIdx.x) * 4, pb = pa + 1024;
-	// positions of this lane behind the frame's end read as 0 in every frame: they always compare equal and are taken off again
-	const uint32_t dead = (uint32_t)(pa >= npx ? 4 : (pa + 4 > npx ? pa + 4 - npx : 0)) + (uint32_t)(pb >= npx ? 4 : (pb + 4 > npx ? pb + 4 - npx : 0));
-	const uint32_t n_pairs = n_frames - 1;
-	uint32_t ga = sim_greys(sim_load(pix, pa, npx, vec)), gb = sim_greys(sim_load(pix, pb, npx, vec));
-	uint4 na = sim_load(pix + npx, pa, npx, vec), nb = sim_load(pix + npx, pb, npx, vec);
-	for (uint32_t seg = 0; seg < n_pairs; seg += SIM_SEG) {
-		const uint32_t n_seg = n_pairs - seg < SIM_SEG ? n_pairs - seg : SIM_SEG;
-		for (uint32_t k = threadIdx.x; k < n_seg; k += 256) s_cnt[k] = 0;
-		__syncthreads();
-		for (uint32_t k = 0; k < n_seg; k++) {
-			const uint32_t f = seg + k + 1;                    // the later frame of pair seg + k: its pixels are in na, nb
-			const uint4 ca = na, cb = nb;
-			if (f + 1 < n_frames) {
-				const uint32_t* nx = pix + (size_t)(f + 1) * npx;
-				na = sim_load(nx, pa, npx, vec); nb = sim_load(nx, pb, npx, vec);
-			}
-			const uint32_t ha = sim_greys(ca), hb = sim_greys(cb);
-			uint32_t c = sim_equal_bytes(ga, ha) + sim_equal_bytes(gb, hb) - dead;
-			ga = ha; gb = hb;
-			for (int d = 32; d; d >>= 1) c += __shfl_xor(c, d, 64);
-			if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt[k], c);
-		}
-		__syncthreads();
-		for (uint32_t k = threadIdx.x; k < n_seg; k += 256) if (s_cnt[k]) atomicAdd(counts + seg + k, s_cnt[k]);
-		__syncthreads();
-	}
-}
-
-// the GBA / NDS nearest scale as a gather: dst[f][k] = src[f][index[k]], 0 where the table says "no source pixel" (0xFFFFFFFF;
-// an index outside the source frame reads as that too).  The table holds every quirk of the host scaler (agmv_pipeline.c).
-__global__ __launch_bounds__(256) void k_gather(const uint32_t* __restrict__ src, size_t src_px, uint32_t n_frames,
-                                                const uint32_t* __restrict__ index, size_t n_out, uint32_t* __restrict__ dst)
-{
-	const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-	if (k >= n_out) return;
-	const uint32_t i = index[k];
-	const bool live = i != 0xFFFFFFFFu && (size_t)i < src_px;
-	for (uint32_t f = 0; f < n_frames; f++) dst[(size_t)f * n_out + k] = live ? src[(size_t)f * src_px + i] : 0u;
-}
-
-// ---- clips in the caller's pixel layout (AGMV_PIXFMT of include/agmv.h: the values 2 .. 5; XRGB32 = 1 goes to the kernels above) ----
-// A frame of fpx pixels is fr[fpx][3] bytes R,G,B (RGB24) or B,G,R (BGR24), fr[fpx][4] bytes R,G,B,A (RGBA32), or three planes
-// of fpx bytes R, G, B (RGB8P).  The kernels below are HBM streams.  Where every frame (and plane) starts on a 16-byte
-// boundary a lane owns 16 consecutive pixels: three 16-byte loads (four for RGBA32), which the wave issues over one contiguous
-// 3 (4) KiB, and four 16-byte stores.  Otherwise (`wide` / `vec` 0: a clip at an odd byte offset, a frame size that is no multiple
-// of 16) and for the last partial group of 16 of a frame the same kernel goes pixel by pixel through byte loads.
-#define PF_XRGB32 1
-#define PF_RGB24 2
-#define PF_BGR24 3
-#define PF_RGBA32 4
-#define PF_RGB8P 5
-
-typedef uint32_t pf_u32x4 __attribute__((ext_vector_type(4)));
-template <int FMT> struct pf_raw { pf_u32x4 v[FMT == PF_RGBA32 ? 4 : 3]; };      // 16 pixels as they lie in memory
-
-// pixel k of a frame as 0x00RRGGBB, byte by byte (fmt is a constant in the templates)
-__device__ __forceinline__ uint32_t pf_read(int fmt, const uint8_t* __restrict__ fr, size_t fpx, size_t k)
-{
-	if (fmt == PF_RGB8P) return (uint32_t)fr[k] << 16 | (uint32_t)fr[fpx + k] << 8 | fr[2 * fpx + k];
-	const uint8_t* p = fr + (fmt == PF_RGBA32 ? 4 : 3) * k;
-	return fmt == PF_BGR24 ? (uint32_t)p[2] << 16 | (uint32_t)p[1] << 8 | p[0] : (uint32_t)p[0] << 16 | (uint32_t)p[1] << 8 | p[2];
-}
-
-__device__ __forceinline__ void pf_write(int fmt, uint8_t* __restrict__ fr, size_t fpx, size_t k, uint32_t x)
-{
-	const uint8_t r = (uint8_t)(x >> 16), g = (uint8_t)(x >> 8), b = (uint8_t)x;
-	if (fmt == PF_RGB8P) { fr[k] = r; fr[fpx + k] = g; fr[2 * fpx + k] = b; return; }
-	uint8_t* p = fr + (fmt == PF_RGBA32 ? 4 : 3) * k;
-	p[0] = fmt == PF_BGR24 ? b : r; p[1] = g; p[2] = fmt == PF_BGR24 ? r : b;
-	if (fmt == PF_RGBA32) p[3] = 0xFF;
-}
-
-// pixels p .. p + 15 of a frame whose rows of 16 pixels are 16-byte aligned; NT: the bytes are used once
-template <int FMT, bool NT> __device__ __forceinline__ pf_raw<FMT> pf_load16(const uint8_t* __restrict__ fr, size_t fpx, size_t p)
-{
-	pf_raw<FMT> r;
-#pragma unroll
-	for (int j = 0; j < (FMT == PF_RGBA32 ? 4 : 3); j++) {
-		const pf_u32x4* a = reinterpret_cast<const pf_u32x4*>(FMT == PF_RGB8P ? fr + (size_t)j * fpx + p : fr + (FMT == PF_RGBA32 ? 4 : 3) * p + 16 * j);
-		r.v[j] = NT ? __builtin_nontemporal_load(a) : *a;
-	}
-	return r;
-}
-
-// pixel i (a constant once the caller's loop is unrolled) of such a group as 0x00RRGGBB
-template <int FMT> __device__ __forceinline__ uint32_t pf_pixel(const pf_raw<FMT>& r, int i)
-{
-	if (FMT == PF_RGB8P) {
-		const int s = (i & 3) * 8;
-		return ((r.v[0][i >> 2] >> s) & 0xffu) << 16 | ((r.v[1][i >> 2] >> s) & 0xffu) << 8 | ((r.v[2][i >> 2] >> s) & 0xffu);
-	}
-	if (FMT == PF_RGBA32) {
-		const uint32_t w = r.v[i >> 2][i & 3];
-		return (w & 0xffu) << 16 | (w & 0xff00u) | ((w >> 16) & 0xffu);
-	}
-	const int o = 3 * i, w = o >> 2, s = (o & 3) * 8;                  // the pixel's three bytes start at byte o of the 48
-	uint32_t v = r.v[w >> 2][w & 3] >> s;
-	if (s > 8) v |= r.v[(w + 1) >> 2][(w + 1) & 3] << (32 - s);
-	v &= 0xffffffu;                                                  // first byte in bits 0..7: BGR24 is 0x00RRGGBB as it lies
-	return FMT == PF_BGR24 ? v : (v & 0xffu) << 16 | (v & 0xff00u) | v >> 16;
-}
-
-// the inverse: 16 pixels 0x..RRGGBB (x[j] = pixels 4j .. 4j + 3) as they lie in a frame of FMT
-template <int FMT> __device__ __forceinline__ pf_raw<FMT> pf_pack16(const pf_u32x4 x[4])
-{
-	pf_raw<FMT> r;
-#pragma unroll
-	for (int w = 0; w < (FMT == PF_RGBA32 ? 16 : 12); w++) {
-		uint32_t word = 0;
-		if (FMT == PF_RGBA32) {
-			const uint32_t c = x[w >> 2][w & 3];
-			word = ((c >> 16) & 0xffu) | (c & 0xff00u) | (c & 0xffu) << 16 | 0xff000000u;
-		} else {
-#pragma unroll
-			for (int b = 0; b < 4; b++) {
-				const int o = 4 * w + b;                                 // byte o of the 48
-				const int i = FMT == PF_RGB8P ? o & 15 : o / 3, ch = FMT == PF_RGB8P ? o >> 4 : o % 3;    // its pixel and channel (0 = first in memory)
-				const int sh = FMT == PF_BGR24 ? 8 * ch : 16 - 8 * ch;
-				word |= ((x[i >> 2][i & 3] >> sh) & 0xffu) << (8 * b);
-			}
-		}
-		r.v[w >> 2][w & 3] = word;
-	}
-	return r;
-}
-
-// d_dst[f][k] = pixel k of frame f, k < npx <= fpx.  A thread's group of 16 pixels is g; one frame takes bpf blocks.
-template <int FMT> __global__ __launch_bounds__(256) void k_pix_to_xrgb(const uint8_t* __restrict__ src, size_t fpx, size_t frame_bytes, size_t npx,
-                                                                        uint32_t bpf, int wide, uint32_t* __restrict__ dst)
-{
-	const uint32_t f = blockIdx.x / bpf;
-	const size_t g = (size_t)(blockIdx.x - f * bpf) * 256 + threadIdx.x, p = g * 16;
-	const uint8_t* fr = src + (size_t)f * frame_bytes;
-	uint32_t* out = dst + (size_t)f * npx;
-	if (wide && p + 16 <= npx) {
-		const pf_raw<FMT> r = pf_load16<FMT, true>(fr, fpx, p);
-#pragma unroll
-		for (int j = 0; j < 4; j++) {
-			pf_u32x4 o;
-#pragma unroll
-			for (int i = 0; i < 4; i++) o[i] = pf_pixel<FMT>(r, 4 * j + i);
-			*reinterpret_cast<pf_u32x4*>(out + p + 4 * j) = o;
-		}
-	} else if (wide) {                                                 // the last, partial group of the frame
-		for (int i = 0; i < 16; i++) if (p + i < npx) out[p + i] = pf_read(FMT, fr, fpx, p + i);
-	} else {                                                           // lanes on consecutive pixels: the wave's 1024, 64 at a time
-		const size_t w0 = (g & ~(size_t)63) * 16 + (threadIdx.x & 63);
-		for (int i = 0; i < 16; i++) if (w0 + 64 * i < npx) out[w0 + 64 * i] = pf_read(FMT, fr, fpx, w0 + 64 * i);
-	}
-}
-
-// d_dst frame f = src[f][0 .. npx) in FMT (whole frames of npx pixels); nothing outside those frames is written
-template <int FMT> __global__ __launch_bounds__(256) void k_pix_from_xrgb(const uint32_t* __restrict__ src, size_t npx, size_t frame_bytes, uint32_t bpf,
-                                                                          int wide, uint8_t* __restrict__ dst)
-{
-	const uint32_t f = blockIdx.x / bpf;
-	const size_t g = (size_t)(blockIdx.x - f * bpf) * 256 + threadIdx.x, p = g * 16;
-	const uint32_t* in = src + (size_t)f * npx;
-	uint8_t* fr = dst + (size_t)f * frame_bytes;
-	if (wide && p + 16 <= npx) {
-		pf_u32x4 x[4];
-#pragma unroll
-		for (int j = 0; j < 4; j++) x[j] = __builtin_nontemporal_load(reinterpret_cast<const pf_u32x4*>(in + p + 4 * j));
-		const pf_raw<FMT> r = pf_pack16<FMT>(x);
-#pragma unroll
-		for (int j = 0; j < (FMT == PF_RGBA32 ? 4 : 3); j++)
-			*reinterpret_cast<pf_u32x4*>(FMT == PF_RGB8P ? fr + (size_t)j * npx + p : fr + (FMT == PF_RGBA32 ? 4 : 3) * p + 16 * j) = r.v[j];
-	} else if (wide) {
-		for (int i = 0; i < 16; i++) if (p + i < npx) pf_write(FMT, fr, npx, p + i, in[p + i]);
-	} else {
-		const size_t w0 = (g & ~(size_t)63) * 16 + (threadIdx.x & 63);
-		for (int i = 0; i < 16; i++) if (w0 + 64 * i < npx) pf_write(FMT, fr, npx, w0 + 64 * i, in[w0 + 64 * i]);
-	}
-}
-
-// k_gather on a source in fmt: only the pixels the table names are read
-__global__ __launch_bounds__(256) void k_gather_fmt(const uint8_t* __restrict__ src, int fmt, size_t src_px, size_t frame_bytes, uint32_t n_frames,
-                                                    const uint32_t* __restrict__ index, size_t n_out, uint32_t* __restrict__ dst)
-{
-	const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-	if (k >= n_out) return;
-	const uint32_t i = index[k];
-	const bool live = i != 0xFFFFFFFFu && (size_t)i < src_px;
-	for (uint32_t f = 0; f < n_frames; f++) dst[(size_t)f * n_out + k] = live ? pf_read(fmt, src + (size_t)f * frame_bytes, src_px, i) : 0u;
-}
-
-// the run-length atomics of k_histogram for one code per lane: each run of equal codes over the wave's live lanes (a prefix of
-// the wave) adds its length with one atomic.  Every lane of the wave calls it.
-__device__ __forceinline__ void hist_add_runs(uint32_t* __restrict__ hist, uint32_t c, bool live, int lane)
-{
-	const uint32_t prev = __shfl_up(c, 1, 64);
-	const bool leader = live && (lane == 0 || c != prev);
-	const unsigned long long lead = __ballot(leader), alive = __ballot(live);
-	if (leader) {
-		const unsigned long long rest = lane == 63 ? 0ull : lead >> (lane + 1);
-		const uint32_t end = rest ? (uint32_t)lane + 1u + (uint32_t)__builtin_ctzll(rest) : (uint32_t)__popcll(alive);
-		atomicAdd(hist + c, end - (uint32_t)lane);
-	}
-}
-
-// k_histogram over the first npx pixels of each frame of a clip in FMT.  A wave takes 1024 pixels of one frame in 16 slices of
-// 64 consecutive pixels, so that neighbouring lanes hold neighbouring pixels as in k_histogram and runs stay long.  Wide, the
-// wave's 3 (4) KiB go through LDS as they lie in memory (each lane's 16-byte loads stored at their place, the pixels of a
-// partial last group byte by byte) and a slice reads its pixels from there; byte-wise a slice reads global memory directly.
-template <int FMT> __global__ __launch_bounds__(256) void k_histogram_fmt(const uint8_t* __restrict__ src, size_t fpx, size_t frame_bytes, size_t npx,
-                                                                          uint32_t bpf, int wide, int quality, uint32_t* __restrict__ hist)
-{
-	__shared__ pf_u32x4 s_px[4][256];                              // per wave 4 KiB: 1024 pixels (RGB8P: planes 1024 bytes apart)
-	const int lane = threadIdx.x & 63;
-	const uint32_t f = blockIdx.x / bpf;
-	const size_t g = (size_t)(blockIdx.x - f * bpf) * 256 + threadIdx.x, p = g * 16;
-	const size_t w0 = (g & ~(size_t)63) * 16;                      // the wave's first pixel
-	const uint8_t* fr = src + (size_t)f * frame_bytes;
-	if (wide) {
-		uint8_t* sw = reinterpret_cast<uint8_t*>(s_px[threadIdx.x >> 6]);
-		if (p + 16 <= npx) {
-			const pf_raw<FMT> r = pf_load16<FMT, false>(fr, fpx, p);
-#pragma unroll
-			for (int j = 0; j < (FMT == PF_RGBA32 ? 4 : 3); j++)
-				*reinterpret_cast<pf_u32x4*>(FMT == PF_RGB8P ? sw + 1024 * j + 16 * lane : sw + (FMT == PF_RGBA32 ? 64 : 48) * lane + 16 * j) = r.v[j];
-		} else {
-			for (int i = 0; i < 16; i++) if (p + i < npx) pf_write(FMT, sw, 1024, 16 * lane + i, pf_read(FMT, fr, fpx, p + i));
-		}
-		__syncthreads();
-		for (int i = 0; i < 16; i++) {
-			const bool live = w0 + 64 * i + lane < npx;
-			hist_add_runs(hist, live ? quantize_color(pf_read(FMT, sw, 1024, 64 * i + lane), quality) : 0xFFFFFFFFu, live, lane);
-		}
-	} else {
-		for (int i = 0; i < 16; i++) {
-			const size_t k = w0 + 64 * i + lane;
-			const bool live = k < npx;
-			hist_add_runs(hist, live ? quantize_color(pf_read(FMT, fr, fpx, k), quality) : 0xFFFFFFFFu, live, lane);
-		}
-	}
-}
-
-// k_similarity on a clip in FMT (frames npx pixels apart): the same walk through all frames and the same slots, with 16 pixel
-// positions per lane: three (four) 16-byte loads per frame, the greys of the frame before in four registers.  vec: npx % 16 == 0
-// and the clip is 16-byte aligned.  Without it the loads are byte loads and deliver the greys at once (in v[0]).
-__device__ __forceinline__ uint32_t sim_grey(uint32_t x) { return (((x >> 16) & 0xff) + ((x >> 8) & 0xff) + (x & 0xff)) / 3u; }
-
-template <int FMT> __device__ __forceinline__ pf_raw<FMT> sim_load16(const uint8_t* __restrict__ fr, size_t p, size_t npx, bool vec)
-{
-	pf_raw<FMT> r;
-	if (vec && p < npx) return pf_load16<FMT, false>(fr, npx, p);
-#pragma unroll
-	for (int j = 0; j < (FMT == PF_RGBA32 ? 4 : 3); j++) r.v[j] = 0;
-	if (!vec) {
-#pragma unroll
-		for (int i = 0; i < 16; i++) if (p + i < npx) r.v[0][i >> 2] |= sim_grey(pf_read(FMT, fr, npx, p + i)) << (8 * (i & 3));
-	}
-	return r;
-}
-
-template <int FMT> __device__ __forceinline__ pf_u32x4 sim_greys16(const pf_raw<FMT>& r, bool vec)
-{
-	if (!vec) return r.v[0];
-	pf_u32x4 g = 0;
-#pragma unroll
-	for (int i = 0; i < 16; i++) g[i >> 2] |= sim_grey(pf_pixel<FMT>(r, i)) << (8 * (i & 3));
-	return g;
-}
-
-template <int FMT> __global__ __launch_bounds__(256) void k_similarity_fmt(const uint8_t* __restrict__ pix, uint32_t n_frames, size_t npx, size_t frame_bytes,
-                                                                           int vec, uint32_t* __restrict__ counts)
-{
-	__shared__ uint32_t s_cnt[SIM_SEG];
-	const size_t p = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
-	// positions of this lane behind the frame's end read as 0 in every frame: they always compare equal and are taken off again
-	const uint32_t dead = (uint32_t)(p >= npx ? 16 : (p + 16 > npx ? p + 16 - npx : 0));
-	const uint32_t n_pairs = n_frames - 1;
-	pf_u32x4 g = sim_greys16<FMT>(sim_load16<FMT>(pix, p, npx, vec), vec);
-	pf_raw<FMT> nx = sim_load16<FMT>(pix + frame_bytes, p, npx, vec);
-	for (uint32_t seg = 0; seg < n_pairs; seg += SIM_SEG) {
-		const uint32_t n_seg = n_pairs - seg < SIM_SEG ? n_pairs - seg : SIM_SEG;
-		for (uint32_t k = threadIdx.x; k < n_seg; k += 256) s_cnt[k] = 0;
-		__syncthreads();
-		for (uint32_t k = 0; k < n_seg; k++) {
-			const uint32_t f = seg + k + 1;                    // the later frame of pair seg + k: its pixels are in nx
-			const pf_raw<FMT> cur = nx;
-			if (f + 1 < n_frames) nx = sim_load16<FMT>(pix + (size_t)(f + 1) * frame_bytes, p, npx, vec);
-			const pf_u32x4 h = sim_greys16<FMT>(cur, vec);
-			uint32_t c = sim_equal_bytes(g[0], h[0]) + sim_equal_bytes(g[1], h[1]) + sim_equal_bytes(g[2], h[2]) + sim_equal_bytes(g[3], h[3]) - dead;
-			g = h;
-			for (int d = 32; d; d >>= 1) c += __shfl_xor(c, d, 64);
-			if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt[k], c);
-		}
-		__syncthreads();
-		for (uint32_t k = threadIdx.x; k < n_seg; k += 256) if (s_cnt[k]) atomicAdd(counts + seg + k, s_cnt[k]);
-		__syncthreads();
-	}
-}
-
-// ---- clips in 8-bit YUV 4:2:0 (AGMV_PIXFMT_NV12 = 16, AGMV_PIXFMT_I420 = 17 of include/agmv.h, which holds the definition) ----
-// A frame of w x h pixels is [h][w] bytes Y, then with cw = (w + 1) / 2, ch = (h + 1) / 2 either [ch][cw][2] bytes U,V (NV12) or
-// [ch][cw] bytes U and [ch][cw] bytes V (I420).  Pixel (x, y) takes its chroma from (x >> 1, y >> 1).  The matrix is data: six
-// (reading) or ten (writing) integers the host picks from the flags in fmt; the only template axis is the layout.  The kernels are
-// HBM streams.  Wide (w a multiple of 16, every frame on a 16-byte boundary) a lane owns a patch of 16 x 2 pixels: two 16-byte
-// luma loads and the 16 chroma bytes both rows share (I420: 8 + 8), 32 pixels.  Everything else -- another w, a clip at an odd
-// offset, the odd last row, a pixel count that ends inside a patch -- goes pixel by pixel in the same kernel.
-#define PF_NV12 16
-#define PF_I420 17
-
-typedef uint32_t pf_u32x2 __attribute__((ext_vector_type(2)));
-struct yuv_rd { int ky, yo, rv, gu, gv, bu; };
-struct yuv_wr { int yr, yg, yb, yo, ur, ug, ub, vr, vg, vb; };
-struct yuv_terms { int r, g, b; };                                 // what one chroma sample adds to its (up to) 2 x 2 pixels, rounding included
-struct yuv_raw { pf_u32x4 y0, y1, c; };                            // a patch as it lies in memory; c: 8 pairs U,V (NV12), 8 U then 8 V (I420)
-
-__device__ __forceinline__ int yuv_clip8(int v) { return min(max(v, 0), 255); }
-
-__device__ __forceinline__ yuv_terms yuv_chroma(const yuv_rd& m, int u, int v)
-{
-	const int d = u - 128, e = v - 128;
-	yuv_terms t;
-	t.r = m.rv * e + 128; t.g = 128 - m.gu * d - m.gv * e; t.b = m.bu * d + 128;
-	return t;
-}
-
-__device__ __forceinline__ uint32_t yuv_pixel(const yuv_rd& m, int y, const yuv_terms& t)
-{
-	const int c = m.ky * (y - m.yo);
-	return (uint32_t)yuv_clip8((c + t.r) >> 8) << 16 | (uint32_t)yuv_clip8((c + t.g) >> 8) << 8 | (uint32_t)yuv_clip8((c + t.b) >> 8);
-}
-
-// pixel (x, y) of a frame as 0x00RRGGBB, byte by byte
-template <int FMT> __device__ __forceinline__ uint32_t yuv_read(const uint8_t* __restrict__ fr, uint32_t w, uint32_t h, uint32_t x, uint32_t y, const yuv_rd& m)
-{
-	const size_t cw = (w + 1) >> 1, ch = (h + 1) >> 1, ci = (size_t)(y >> 1) * cw + (x >> 1);
-	const uint8_t* c = fr + (size_t)w * h;
-	const int u = FMT == PF_NV12 ? c[2 * ci] : c[ci], v = FMT == PF_NV12 ? c[2 * ci + 1] : c[cw * ch + ci];
-	return yuv_pixel(m, fr[(size_t)y * w + x], yuv_chroma(m, u, v));
-}
-
-// the patch at column x0 (a multiple of 16) of rows 2 * py and (row1) 2 * py + 1, w a multiple of 16 and fr 16-byte aligned
-template <int FMT, bool NT> __device__ __forceinline__ yuv_raw yuv_load_patch(const uint8_t* __restrict__ fr, uint32_t w, uint32_t h, uint32_t x0, uint32_t py, bool row1)
-{
-	yuv_raw r;
-	const size_t cw = w >> 1, ch = (h + 1) >> 1;
-	const pf_u32x4* a = reinterpret_cast<const pf_u32x4*>(fr + (size_t)2 * py * w + x0);
-	const pf_u32x4* b = reinterpret_cast<const pf_u32x4*>(fr + ((size_t)2 * py + 1) * w + x0);
-	r.y0 = NT ? __builtin_nontemporal_load(a) : *a;
-	r.y1 = 0;
-	if (row1) r.y1 = NT ? __builtin_nontemporal_load(b) : *b;
-	if (FMT == PF_NV12) {
-		const pf_u32x4* c = reinterpret_cast<const pf_u32x4*>(fr + (size_t)w * h + (size_t)py * w + x0);
-		r.c = NT ? __builtin_nontemporal_load(c) : *c;
-	} else {
-		const pf_u32x2* u = reinterpret_cast<const pf_u32x2*>(fr + (size_t)w * h + (size_t)py * cw + (x0 >> 1));
-		const pf_u32x2* v = reinterpret_cast<const pf_u32x2*>(fr + (size_t)w * h + cw * ch + (size_t)py * cw + (x0 >> 1));
-		const pf_u32x2 uu = NT ? __builtin_nontemporal_load(u) : *u, vv = NT ? __builtin_nontemporal_load(v) : *v;
-		r.c[0] = uu[0]; r.c[1] = uu[1]; r.c[2] = vv[0]; r.c[3] = vv[1];
-	}
-	return r;
-}
-
-// chroma sample j (a constant once the caller's loop is unrolled) of a patch
-template <int FMT> __device__ __forceinline__ yuv_terms yuv_patch_chroma(const yuv_raw& r, int j, const yuv_rd& m)
-{
-	if (FMT == PF_NV12) return yuv_chroma(m, (r.c[j >> 1] >> (16 * (j & 1))) & 0xff, (r.c[j >> 1] >> (16 * (j & 1) + 8)) & 0xff);
-	return yuv_chroma(m, (r.c[j >> 2] >> (8 * (j & 3))) & 0xff, (r.c[2 + (j >> 2)] >> (8 * (j & 3))) & 0xff);
-}
-
-// d_dst[f][k] = pixel k (raster order) of frame f, k < npx <= w * h.  Wide a thread's patch is g; byte-wise the wave takes 2048
-// consecutive pixels, 64 at a time.  One frame takes bpf blocks.
-template <int FMT> __global__ __launch_bounds__(256) void k_yuv_to_xrgb(const uint8_t* __restrict__ src, uint32_t w, uint32_t h, size_t frame_bytes, uint32_t npx,
-                                                                        uint32_t bpf, int wide, yuv_rd m, uint32_t* __restrict__ dst)
-{
-	const uint32_t f = blockIdx.x / bpf, g = (blockIdx.x - f * bpf) * 256 + threadIdx.x;
-	const uint8_t* fr = src + (size_t)f * frame_bytes;
-	uint32_t* out = dst + (size_t)f * npx;
-	if (wide) {
-		const uint32_t ppr = w >> 4, py = g / ppr, x0 = (g - py * ppr) * 16;
-		if (2 * py >= h) return;
-		const uint32_t k0 = 2 * py * w + x0;
-		if (2 * py + 1 < h && k0 + w + 16 <= npx) {
-			const yuv_raw r = yuv_load_patch<FMT, true>(fr, w, h, x0, py, true);
-#pragma unroll
-			for (int q = 0; q < 4; q++) {                          // pixels 4q .. 4q + 3 of both rows: chroma samples 2q, 2q + 1
-				const yuv_terms ta = yuv_patch_chroma<FMT>(r, 2 * q, m), tb = yuv_patch_chroma<FMT>(r, 2 * q + 1, m);
-				pf_u32x4 o0, o1;
-#pragma unroll
-				for (int i = 0; i < 4; i++) {
-					o0[i] = yuv_pixel(m, (r.y0[q] >> (8 * i)) & 0xff, i < 2 ? ta : tb);
-					o1[i] = yuv_pixel(m, (r.y1[q] >> (8 * i)) & 0xff, i < 2 ? ta : tb);
-				}
-				*reinterpret_cast<pf_u32x4*>(out + k0 + 4 * q) = o0;
-				*reinterpret_cast<pf_u32x4*>(out + k0 + w + 4 * q) = o1;
-			}
-		} else {                                                   // the odd last row, or the count ends in this patch
-			for (uint32_t r = 0; r < 2 && 2 * py + r < h; r++)
-				for (uint32_t i = 0; i < 16; i++) if (k0 + r * w + i < npx) out[k0 + r * w + i] = yuv_read<FMT>(fr, w, h, x0 + i, 2 * py + r, m);
-		}
-	} else {
-		const uint32_t k0 = (g & ~63u) * 32 + (threadIdx.x & 63);
-		for (int i = 0; i < 32; i++) {
-			const uint32_t k = k0 + 64 * i;
-			if (k < npx) out[k] = yuv_read<FMT>(fr, w, h, k % w, k / w, m);
-		}
-	}
-}
-
-__device__ __forceinline__ uint32_t yuv_luma(const yuv_wr& m, uint32_t x)
-{
-	const int r = (x >> 16) & 0xff, g = (x >> 8) & 0xff, b = x & 0xff;
-	return (uint32_t)yuv_clip8(((m.yr * r + m.yg * g + m.yb * b + 128) >> 8) + m.yo);
-}
-
-// U | V << 8 of the mean colour (sums over cnt = 1 << sh pixels)
-__device__ __forceinline__ uint32_t yuv_uv(const yuv_wr& m, int sr, int sg, int sb, int sh)
-{
-	const int half = (1 << sh) >> 1, r = (sr + half) >> sh, g = (sg + half) >> sh, b = (sb + half) >> sh;
-	return (uint32_t)yuv_clip8(((m.ur * r + m.ug * g + m.ub * b + 128) >> 8) + 128) |
-	       (uint32_t)yuv_clip8(((m.vr * r + m.vg * g + m.vb * b + 128) >> 8) + 128) << 8;
-}
-
-// chroma sample (cx, cy) of a frame from the pixels of its 2 x 2 block that exist, byte by byte
-template <int FMT> __device__ __forceinline__ void yuv_put_chroma(const uint32_t* __restrict__ in, uint8_t* __restrict__ fr, uint32_t w, uint32_t h, uint32_t cx,
-                                                                  uint32_t cy, const yuv_wr& m)
-{
-	const uint32_t x = 2 * cx, y = 2 * cy, nx = x + 1 < w ? 2 : 1, ny = y + 1 < h ? 2 : 1;
-	const size_t cw = (w + 1) >> 1, ch = (h + 1) >> 1, ci = (size_t)cy * cw + cx;
-	int sr = 0, sg = 0, sb = 0;
-	for (uint32_t j = 0; j < ny; j++)
-		for (uint32_t i = 0; i < nx; i++) {
-			const uint32_t p = in[(size_t)(y + j) * w + x + i];
-			sr += (p >> 16) & 0xff; sg += (p >> 8) & 0xff; sb += p & 0xff;
-		}
-	const uint32_t uv = yuv_uv(m, sr, sg, sb, (nx == 2) + (ny == 2));
-	uint8_t* c = fr + (size_t)w * h;
-	if (FMT == PF_NV12) { c[2 * ci] = (uint8_t)uv; c[2 * ci + 1] = (uint8_t)(uv >> 8); }
-	else { c[ci] = (uint8_t)uv; c[cw * ch + ci] = (uint8_t)(uv >> 8); }
-}
-
-// d_dst frame f = src[f][0 .. w * h) written as YUV (whole frames); nothing outside those frames is written
-template <int FMT> __global__ __launch_bounds__(256) void k_yuv_from_xrgb(const uint32_t* __restrict__ src, uint32_t w, uint32_t h, size_t frame_bytes, uint32_t bpf,
-                                                                          int wide, yuv_wr m, uint8_t* __restrict__ dst)
-{
-	const uint32_t f = blockIdx.x / bpf, g = (blockIdx.x - f * bpf) * 256 + threadIdx.x, npx = w * h;
-	const uint32_t* in = src + (size_t)f * npx;
-	uint8_t* fr = dst + (size_t)f * frame_bytes;
-	if (wide) {
-		const uint32_t ppr = w >> 4, py = g / ppr, x0 = (g - py * ppr) * 16;
-		if (2 * py >= h) return;
-		const uint32_t k0 = 2 * py * w + x0;
-		if (2 * py + 1 < h) {
-			pf_u32x4 y0, y1, c;
-#pragma unroll
-			for (int q = 0; q < 4; q++) {
-				const pf_u32x4 a = __builtin_nontemporal_load(reinterpret_cast<const pf_u32x4*>(in + k0 + 4 * q));
-				const pf_u32x4 b = __builtin_nontemporal_load(reinterpret_cast<const pf_u32x4*>(in + k0 + w + 4 * q));
-				uint32_t ya = 0, yb = 0;
-#pragma unroll
-				for (int i = 0; i < 4; i++) { ya |= yuv_luma(m, a[i]) << (8 * i); yb |= yuv_luma(m, b[i]) << (8 * i); }
-				y0[q] = ya; y1[q] = yb;
-				uint32_t uv[2];
-#pragma unroll
-				for (int j = 0; j < 2; j++) {
-					const uint32_t p0 = a[2 * j], p1 = a[2 * j + 1], p2 = b[2 * j], p3 = b[2 * j + 1];
-					uv[j] = yuv_uv(m, (int)(((p0 >> 16) & 0xff) + ((p1 >> 16) & 0xff) + ((p2 >> 16) & 0xff) + ((p3 >> 16) & 0xff)),
-					               (int)(((p0 >> 8) & 0xff) + ((p1 >> 8) & 0xff) + ((p2 >> 8) & 0xff) + ((p3 >> 8) & 0xff)),
-					               (int)((p0 & 0xff) + (p1 & 0xff) + (p2 & 0xff) + (p3 & 0xff)), 2);
-				}
-				if (FMT == PF_NV12) c[q] = uv[0] | uv[1] << 16;        // samples 2q, 2q + 1 as U,V,U,V
-				else {                                             // U of samples 2q, 2q + 1 into byte 2q of the 8 U, V likewise
-					const uint32_t u2 = (uv[0] & 0xff) | (uv[1] & 0xff) << 8, v2 = (uv[0] >> 8) | (uv[1] >> 8) << 8;
-					if (q & 1) { c[q >> 1] |= u2 << 16; c[2 + (q >> 1)] |= v2 << 16; } else { c[q >> 1] = u2; c[2 + (q >> 1)] = v2; }
-				}
-			}
-			*reinterpret_cast<pf_u32x4*>(fr + k0) = y0;
-			*reinterpret_cast<pf_u32x4*>(fr + k0 + w) = y1;
-			if (FMT == PF_NV12) *reinterpret_cast<pf_u32x4*>(fr + (size_t)npx + (size_t)py * w + x0) = c;
-			else {
-				const size_t cw = w >> 1, ch = (h + 1) >> 1;
-				pf_u32x2 u, v;
-				u[0] = c[0]; u[1] = c[1]; v[0] = c[2]; v[1] = c[3];
-				*reinterpret_cast<pf_u32x2*>(fr + (size_t)npx + (size_t)py * cw + (x0 >> 1)) = u;
-				*reinterpret_cast<pf_u32x2*>(fr + (size_t)npx + cw * ch + (size_t)py * cw + (x0 >> 1)) = v;
-			}
-		} else {                                                   // the odd last row: means over two pixels
-			for (uint32_t i = 0; i < 16; i++) fr[k0 + i] = (uint8_t)yuv_luma(m, in[k0 + i]);
-			for (uint32_t j = 0; j < 8; j++) yuv_put_chroma<FMT>(in, fr, w, h, (x0 >> 1) + j, py, m);
-		}
-	} else {                                                       // lanes on consecutive pixels; the pixel at the even corner of a block writes its chroma
-		const uint32_t k0 = (g & ~63u) * 32 + (threadIdx.x & 63);
-		for (int i = 0; i < 32; i++) {
-			const uint32_t k = k0 + 64 * i;
-			if (k >= npx) break;
-			const uint32_t y = k / w, x = k - y * w;
-			fr[k] = (uint8_t)yuv_luma(m, in[k]);
-			if (!((x | y) & 1)) yuv_put_chroma<FMT>(in, fr, w, h, x >> 1, y >> 1, m);
-		}
-	}
-}
-
-// k_gather on a YUV source: only the pixels the table names, and their chroma, are read
-template <int FMT> __global__ __launch_bounds__(256) void k_yuv_gather(const uint8_t* __restrict__ src, uint32_t w, uint32_t h, size_t frame_bytes, uint32_t n_frames,
-                                                                       const uint32_t* __restrict__ index, size_t n_out, yuv_rd m, uint32_t* __restrict__ dst)
-{
-	const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-	if (k >= n_out) return;
-	const uint32_t i = index[k];
-	const bool live = i != 0xFFFFFFFFu && i < w * h;
-	const uint32_t y = live ? i / w : 0, x = live ? i - y * w : 0;
-	for (uint32_t f = 0; f < n_frames; f++) dst[(size_t)f * n_out + k] = live ? yuv_read<FMT>(src + (size_t)f * frame_bytes, w, h, x, y, m) : 0u;
-}
-
-// k_histogram over the first npx pixels (raster order) of each frame of a YUV clip, with the codes and the run-length atomics of
-// k_histogram_fmt.  Wide a wave takes 64 patches: each lane's loads go to LDS at their place (1 KiB of row 0, of row 1 and of
-// chroma per wave) and the wave then walks the 2048 pixels 64 at a time -- 4 patches of one row, lane l on column l & 15 of patch
-// l >> 4 -- so neighbouring lanes hold neighbouring pixels and runs stay long.  Byte-wise a slice of 64 consecutive pixels reads
-// global memory directly.
-template <int FMT> __global__ __launch_bounds__(256) void k_yuv_histogram(const uint8_t* __restrict__ src, uint32_t w, uint32_t h, size_t frame_bytes, uint32_t npx,
-                                                                          uint32_t bpf, int wide, int quality, yuv_rd m, uint32_t* __restrict__ hist)
-{
-	__shared__ pf_u32x4 s_px[4][3][64];
-	const int lane = threadIdx.x & 63;
-	const uint32_t f = blockIdx.x / bpf, g = (blockIdx.x - f * bpf) * 256 + threadIdx.x;
-	const uint8_t* fr = src + (size_t)f * frame_bytes;
-	if (wide) {
-		const uint32_t ppr = w >> 4;
-		{
-			const uint32_t py = g / ppr, x0 = (g - py * ppr) * 16;
-			yuv_raw r;
-			r.y0 = 0; r.y1 = 0; r.c = 0;
-			if (2 * py < h && 2 * py * w + x0 < npx) r = yuv_load_patch<FMT, false>(fr, w, h, x0, py, 2 * py + 1 < h);
-			s_px[threadIdx.x >> 6][0][lane] = r.y0; s_px[threadIdx.x >> 6][1][lane] = r.y1; s_px[threadIdx.x >> 6][2][lane] = r.c;
-		}
-		__syncthreads();
-		const uint8_t* sy = reinterpret_cast<const uint8_t*>(s_px[threadIdx.x >> 6][0]);     // rows 1024 bytes apart, chroma behind them
-		const uint8_t* sc = sy + 2048;
-		uint32_t gp = (g & ~63u) + (lane >> 4), py = gp / ppr, xq = gp - py * ppr;              // this lane's patch of the first four
-		for (int q = 0; q < 16; q++) {
-			const int at = 64 * q + lane, cs = at >> 1;                                        // byte of the wave's row, chroma sample of the wave's 512
-			const int u = FMT == PF_NV12 ? sc[2 * cs] : sc[16 * (cs >> 3) + (cs & 7)], v = FMT == PF_NV12 ? sc[2 * cs + 1] : sc[16 * (cs >> 3) + 8 + (cs & 7)];
-			const yuv_terms t = yuv_chroma(m, u, v);
-			for (uint32_t r = 0; r < 2; r++) {
-				const bool live = 2 * py + r < h && (2 * py + r) * w + xq * 16 + (lane & 15) < npx;
-				hist_add_runs(hist, live ? quantize_color(yuv_pixel(m, sy[1024 * r + at], t), quality) : 0xFFFFFFFFu, live, lane);
-			}
-			xq += 4;
-			while (xq >= ppr) { xq -= ppr; py++; }
-		}
-	} else {
-		const uint32_t k0 = (g & ~63u) * 32 + lane;
-		for (int i = 0; i < 32; i++) {
-			const uint32_t k = k0 + 64 * i;
-			const bool live = k < npx;
-			hist_add_runs(hist, live ? quantize_color(yuv_read<FMT>(fr, w, h, k % w, k / w, m), quality) : 0xFFFFFFFFu, live, lane);
-		}
-	}
-}
-
-// k_similarity on a YUV clip: the same walk through all frames and the same slots.  A lane owns a patch of up to 16 x 2 pixel
-// positions (the grid is ceil(w / 16) x ceil(h / 2) patches): per frame two 16-byte luma loads and the chroma both rows share,
-// the greys of the frame before in eight registers.  Without `wide` the patch is read byte by byte into the same registers.
-// Positions of the patch behind the frame's edge have grey 0 in every frame: they always compare equal and are taken off again.
-template <int FMT> __device__ __forceinline__ yuv_raw sim_yuv_load(const uint8_t* __restrict__ fr, uint32_t w, uint32_t h, uint32_t x0, uint32_t py, uint32_t nx,
-                                                                    bool row1, bool wide)
-{
-	yuv_raw r;
-	r.y0 = 0; r.y1 = 0; r.c = 0;
-	if (nx == 0) return r;
-	if (wide) return yuv_load_patch<FMT, false>(fr, w, h, x0, py, row1);
-	const size_t cw = (w + 1) >> 1, ch = (h + 1) >> 1;
-	const uint8_t *a = fr + (size_t)2 * py * w + x0, *c = fr + (size_t)w * h + (FMT == PF_NV12 ? 2 : 1) * ((size_t)py * cw + (x0 >> 1));
-#pragma unroll
-	for (int i = 0; i < 16; i++) if ((uint32_t)i < nx) {
-		r.y0[i >> 2] |= (uint32_t)a[i] << (8 * (i & 3));
-		if (row1) r.y1[i >> 2] |= (uint32_t)a[w + i] << (8 * (i & 3));
-	}
-#pragma unroll
-	for (int j = 0; j < 8; j++) if ((uint32_t)(2 * j) < nx) {
-		if (FMT == PF_NV12) r.c[j >> 1] |= ((uint32_t)c[2 * j] | (uint32_t)c[2 * j + 1] << 8) << (16 * (j & 1));
-		else { r.c[j >> 2] |= (uint32_t)c[j] << (8 * (j & 3)); r.c[2 + (j >> 2)] |= (uint32_t)c[cw * ch + j] << (8 * (j & 3)); }
-	}
-	return r;
-}
-
-struct yuv_greys { pf_u32x4 a, b; };                               // one grey per byte: row 0, row 1
-
-template <int FMT> __device__ __forceinline__ yuv_greys sim_yuv_greys(const yuv_raw& r, const yuv_rd& m, const pf_u32x4& live, bool row1)
-{
-	yuv_greys g;
-	g.a = 0; g.b = 0;
-#pragma unroll
-	for (int j = 0; j < 8; j++) {
-		const yuv_terms t = yuv_patch_chroma<FMT>(r, j, m);
-#pragma unroll
-		for (int i = 2 * j; i < 2 * j + 2; i++) {
-			g.a[i >> 2] |= sim_grey(yuv_pixel(m, (r.y0[i >> 2] >> (8 * (i & 3))) & 0xff, t)) << (8 * (i & 3));
-			g.b[i >> 2] |= sim_grey(yuv_pixel(m, (r.y1[i >> 2] >> (8 * (i & 3))) & 0xff, t)) << (8 * (i & 3));
-		}
-	}
-	g.a &= live;
-	if (row1) g.b &= live; else g.b = 0;
-	return g;
-}
-
-template <int FMT> __global__ __launch_bounds__(256) void k_yuv_similarity(const uint8_t* __restrict__ pix, uint32_t n_frames, uint32_t w, uint32_t h, size_t frame_bytes,
-                                                                           int wide, yuv_rd m, uint32_t* __restrict__ counts)
-{
-	__shared__ uint32_t s_cnt[SIM_SEG];
-	const uint32_t ppr = (w + 15) >> 4, g = blockIdx.x * 256 + threadIdx.x, py = g / ppr, x0 = (g - py * ppr) * 16;
-	const uint32_t nx = 2 * py < h ? (w - x0 < 16 ? w - x0 : 16) : 0;     // columns of this lane's patch that exist
-	const bool row1 = nx && 2 * py + 1 < h;
-	const uint32_t dead = 32 - nx * (row1 ? 2 : 1);
-	pf_u32x4 live;
-#pragma unroll
-	for (int q = 0; q < 4; q++) live[q] = nx >= 4u * q + 4 ? 0xFFFFFFFFu : (nx > 4u * q ? (1u << (8 * (nx - 4 * q))) - 1 : 0u);
-	const uint32_t n_pairs = n_frames - 1;
-	yuv_greys gp = sim_yuv_greys<FMT>(sim_yuv_load<FMT>(pix, w, h, x0, py, nx, row1, wide), m, live, row1);
-	yuv_raw nxt = sim_yuv_load<FMT>(pix + frame_bytes, w, h, x0, py, nx, row1, wide);
-	for (uint32_t seg = 0; seg < n_pairs; seg += SIM_SEG) {
-		const uint32_t n_seg = n_pairs - seg < SIM_SEG ? n_pairs - seg : SIM_SEG;
-		for (uint32_t k = threadIdx.x; k < n_seg; k += 256) s_cnt[k] = 0;
-		__syncthreads();
-		for (uint32_t k = 0; k < n_seg; k++) {
-			const uint32_t f = seg + k + 1;                    // the later frame of pair seg + k: its patch is in nxt
-			const yuv_raw cur = nxt;
-			if (f + 1 < n_frames) nxt = sim_yuv_load<FMT>(pix + (size_t)(f + 1) * frame_bytes, w, h, x0, py, nx, row1, wide);
-			const yuv_greys gh = sim_yuv_greys<FMT>(cur, m, live, row1);
-			uint32_t c = sim_equal_bytes(gp.a[0], gh.a[0]) + sim_equal_bytes(gp.a[1], gh.a[1]) + sim_equal_bytes(gp.a[2], gh.a[2]) + sim_equal_bytes(gp.a[3], gh.a[3]) +
-			             sim_equal_bytes(gp.b[0], gh.b[0]) + sim_equal_bytes(gp.b[1], gh.b[1]) + sim_equal_bytes(gp.b[2], gh.b[2]) + sim_equal_bytes(gp.b[3], gh.b[3]) - dead;
-			gp = gh;
-			for (int d = 32; d; d >>= 1) c += __shfl_xor(c, d, 64);
-			if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt[k], c);
-		}
-		__syncthreads();
-		for (uint32_t k = threadIdx.x; k < n_seg; k += 256) if (s_cnt[k]) atomicAdd(counts + seg + k, s_cnt[k]);
-		__syncthreads();
-	}
-}
-
-// ---- exact box-filter downscale of a clip in any of the seven layouts (AGMV_SCALE_AREA of include/agmv.h, which defines it) ----
-// On an axis source pixel i covers [i * dw, (i + 1) * dw) and target pixel X covers [X * sw, (X + 1) * sw): a source pixel is dw
-// units long, lies in at most two target columns, and the weights of a target column sum to sw.  A scatter: a workgroup owns one
-// (frame, target row Y, tile of SC_TILE target columns) at a time and walks the source rows that overlap Y.  A lane takes a group
-// of 16 consecutive pixels of one source row -- groups are cut at multiples of 16 of the pixel's index in the FRAME, so that on a
-// clip whose frames (and planes) start on 16-byte boundaries a group that lies inside the row is read with the 16-byte loads of
-// k_pix_to_xrgb / k_yuv_to_xrgb (YUV: 16 luma bytes and the 16 chroma bytes of row j >> 1, which needs sw % 16 == 0); the groups
-// at a row's head and tail, and every group of any other clip, go pixel by pixel through the layout's byte reader.  The lane folds
-// wx * channel of its pixels per target column in registers and adds wy * that into the tile's accumulators in LDS once per
-// column it touches (integer adds: any order gives the same sum).  After the barrier each lane finishes its columns --
-// (sum + area / 2) / area, exact in 32 bits because 255 * sw * sh + sw * sh / 2 < 2^32 for sw * sh <= 2^24 -- clears them for the
-// next item and stores the row.  No float, no global atomic.  Items are walked with a grid stride: any number of frames.
-#define SC_TILE 1024
-
-struct ScaleArgs {
-	const uint8_t* src;
-	uint32_t* dst;
-	size_t frame_bytes;
-	unsigned long long items;                                      // n_frames * dh * tiles
-	uint32_t sw, sh, dw, dh, tiles;
-	int wide, small;                                               // 16-byte loads allowed; sw * dw < 2^32
-	yuv_rd m;
-};
-
-// 16 pixels of one source row as they lie in memory: p0 is their index in the frame (a multiple of 16), j their row
-template <int FMT> struct sc_group {
-	static constexpr bool YUV = FMT >= PF_NV12;
-	static constexpr int NV = YUV ? 2 : (FMT == PF_XRGB32 || FMT == PF_RGBA32 ? 4 : 3);
-	pf_u32x4 v[NV];                                                // YUV: luma, then chroma as yuv_raw::c holds it
-
-	__device__ __forceinline__ void load(const uint8_t* __restrict__ fr, uint32_t w, uint32_t h, uint32_t p0, uint32_t j)
-	{
-		if constexpr (YUV) {
-			const uint32_t x0 = p0 - j * w;
-			const uint8_t* c = fr + (size_t)w * h;
-			v[0] = *reinterpret_cast<const pf_u32x4*>(fr + p0);
-			if constexpr (FMT == PF_NV12) v[1] = *reinterpret_cast<const pf_u32x4*>(c + (size_t)(j >> 1) * w + x0);
-			else {
-				const size_t cw = w >> 1, ch = (h + 1) >> 1, o = (size_t)(j >> 1) * cw + (x0 >> 1);
-				const pf_u32x2 uu = *reinterpret_cast<const pf_u32x2*>(c + o), vv = *reinterpret_cast<const pf_u32x2*>(c + cw * ch + o);
-				v[1][0] = uu[0]; v[1][1] = uu[1]; v[1][2] = vv[0]; v[1][3] = vv[1];
-			}
-		} else if constexpr (NV == 4) {
-#pragma unroll
-			for (int k = 0; k < 4; k++) v[k] = *reinterpret_cast<const pf_u32x4*>(fr + 4 * (size_t)p0 + 16 * k);
-		} else {
-			const pf_raw<FMT> r = pf_load16<FMT, false>(fr, (size_t)w * h, p0);
-#pragma unroll
-			for (int k = 0; k < 3; k++) v[k] = r.v[k];
-		}
-	}
-
-	// pixel i (a constant once the caller's loop is unrolled) as 0x00RRGGBB
-	__device__ __forceinline__ uint32_t pixel(int i, const yuv_rd& m) const
-	{
-		if constexpr (YUV) {
-			yuv_raw r;
-			r.y0 = v[0]; r.y1 = v[0]; r.c = v[1];
-			return yuv_pixel(m, (v[0][i >> 2] >> (8 * (i & 3))) & 0xff, yuv_patch_chroma<FMT>(r, i >> 1, m));
-		} else if constexpr (FMT == PF_XRGB32) {
-			return v[i >> 2][i & 3] & 0xffffffu;
-		} else {
-			pf_raw<FMT> r;
-#pragma unroll
-			for (int k = 0; k < NV; k++) r.v[k] = v[k];
-			return pf_pixel<FMT>(r, i);
-		}
-	}
-};
-
-// pixel (x, j) of a frame as 0x00RRGGBB through the layout's byte reader
-template <int FMT> __device__ __forceinline__ uint32_t sc_read(const uint8_t* __restrict__ fr, uint32_t w, uint32_t h, uint32_t x, uint32_t j, const yuv_rd& m)
-{
-	if constexpr (FMT >= PF_NV12) return yuv_read<FMT>(fr, w, h, x, j, m);
-	else if constexpr (FMT == PF_XRGB32) return reinterpret_cast<const uint32_t*>(fr)[(size_t)j * w + x] & 0xffffffu;
-	else return pf_read(FMT, fr, (size_t)w * h, (size_t)j * w + x);
-}
-
-// a lane's walk along a source row: it stands t units into target column X and holds the sums of wx * channel for that column
-struct sc_run { uint32_t X, t, r, g, b; };
-
-__device__ __forceinline__ void sc_flush(uint32_t (*acc)[SC_TILE], const sc_run& s, uint32_t wy, uint32_t X0, uint32_t X1)
-{
-	if (s.X >= X0 && s.X < X1) {
-		atomicAdd(&acc[0][s.X - X0], s.r * wy); atomicAdd(&acc[1][s.X - X0], s.g * wy); atomicAdd(&acc[2][s.X - X0], s.b * wy);
-	}
-}
-
-// the next source pixel, colour c: min(dw, what is left of column X) units go to X, the rest opens column X + 1
-__device__ __forceinline__ void sc_step(uint32_t (*acc)[SC_TILE], sc_run& s, uint32_t c, uint32_t sw, uint32_t dw, uint32_t wy, uint32_t X0, uint32_t X1)
-{
-	const uint32_t r = (c >> 16) & 0xff, g = (c >> 8) & 0xff, b = c & 0xff, w1 = min(dw, sw - s.t);
-	s.r += w1 * r; s.g += w1 * g; s.b += w1 * b; s.t += w1;
-	if (s.t == sw) {
-		sc_flush(acc, s, wy, X0, X1);
-		s.X++; s.t = dw - w1;
-		s.r = s.t * r; s.g = s.t * g; s.b = s.t * b;
-	}
-}
-
-template <int FMT> __global__ __launch_bounds__(256) void k_scale_area(ScaleArgs A)
-{
-	__shared__ uint32_t s_acc[3][SC_TILE];
-	const uint32_t sw = A.sw, sh = A.sh, dw = A.dw, dh = A.dh, area = sw * sh, per = dh * A.tiles;
-	for (uint32_t k = threadIdx.x; k < 3 * SC_TILE; k += 256) (&s_acc[0][0])[k] = 0;
-	__syncthreads();
-	for (unsigned long long item = blockIdx.x; item < A.items; item += gridDim.x) {
-		const uint32_t f = (uint32_t)(item / per), rem = (uint32_t)(item - (unsigned long long)f * per), Y = rem / A.tiles, tile = rem - Y * A.tiles;
-		const uint32_t X0 = tile * SC_TILE, X1 = min(X0 + SC_TILE, dw);
-		// the source columns that touch the tile, the source rows that touch Y
-		const uint32_t i_lo = (uint32_t)((unsigned long long)X0 * sw / dw), i_hi = (uint32_t)(((unsigned long long)X1 * sw + dw - 1) / dw);
-		const unsigned long long y_lo = (unsigned long long)Y * sh, y_hi = y_lo + sh;
-		const uint32_t j0 = (uint32_t)(y_lo / dh), j1 = (uint32_t)((y_hi + dh - 1) / dh);
-		const uint32_t ng = ((i_hi - i_lo + 15) >> 4) + 1, n_task = (j1 - j0) * ng;
-		const uint8_t* fr = A.src + (size_t)f * A.frame_bytes;
-		for (uint32_t task = threadIdx.x; task < n_task; task += 256) {
-			const uint32_t jr = task / ng, j = j0 + jr, row0 = j * sw, lo = row0 + i_lo, hi = row0 + i_hi;
-			const uint32_t p0 = ((lo >> 4) + (task - jr * ng)) << 4;
-			if (p0 >= hi) continue;
-			const uint32_t a = max(p0, lo), b = min(p0 + 16, hi);      // the group's pixels of this row and tile
-			const unsigned long long r_lo = (unsigned long long)j * dh;
-			const uint32_t wy = (uint32_t)(min(r_lo + dh, y_hi) - max(r_lo, y_lo));
-			sc_run s;
-			if (A.small) { const uint32_t u = (a - row0) * dw; s.X = u / sw; s.t = u - s.X * sw; }
-			else { const unsigned long long u = (unsigned long long)(a - row0) * dw; s.X = (uint32_t)(u / sw); s.t = (uint32_t)(u - (unsigned long long)s.X * sw); }
-			s.r = s.g = s.b = 0;
-			if (A.wide && b - a == 16) {
-				sc_group<FMT> grp;
-				grp.load(fr, sw, sh, p0, j);
-#pragma unroll
-				for (int i = 0; i < 16; i++) sc_step(s_acc, s, grp.pixel(i, A.m), sw, dw, wy, X0, X1);
-			} else {
-				for (uint32_t p = a; p < b; p++) sc_step(s_acc, s, sc_read<FMT>(fr, sw, sh, p - row0, j, A.m), sw, dw, wy, X0, X1);
-			}
-			if (s.t) sc_flush(s_acc, s, wy, X0, X1);
-		}
-		__syncthreads();
-		uint32_t* out = A.dst + ((size_t)f * dh + Y) * dw + X0;
-		for (uint32_t k = threadIdx.x; k < X1 - X0; k += 256) {
-			const uint32_t r = (s_acc[0][k] + area / 2) / area, g = (s_acc[1][k] + area / 2) / area, b = (s_acc[2][k] + area / 2) / area;
-			s_acc[0][k] = 0; s_acc[1][k] = 0; s_acc[2][k] = 0;
-			out[k] = r << 16 | g << 8 | b;
-		}
-		__syncthreads();
-	}
-}
-
 // A spin of k_encode that ran into its bound leaves ctrl[1] != 0 and the kernel carries on with a wrong offset: the bytes of
 // the batch are not to be used.  So that a caller who skips agmv_hip_check cannot take them for good ones, every size of
 // the batch is then overwritten with 0xFFFFFFFF (no frame is that long: agmv_hip_max_usize < 2^32).
@@ -4138,336 +3232,6 @@ extern "C" int agmv_hip_unpack_frames_dev(agmv_hip_ctx* c, const uint8_t* d_msg,
 	if (need_ctx(c, false)) return -1;
 	if (n_frames == 0) return 0;
 	return pack_launch(c, true, d_slab, stride, d_sizes, n_frames, (uint8_t*)d_msg, d_offsets, (hipStream_t)stream);
-}
-
-extern "C" int agmv_hip_synth_dev(agmv_hip_ctx* c, uint32_t* d_pix, uint32_t w, uint32_t h, uint32_t t0, uint32_t n_frames,
-                                  uint64_t seed, void* stream)
-{
-	if (need_ctx(c, false)) return -1;
-	if (w < 2 || h < 2 || n_frames == 0) { snprintf(g_err, sizeof(g_err), "agmv_hip: bad synth geometry"); return -1; }
-	hipLaunchKernelGGL(k_synth, dim3(8192), dim3(256), 0, (hipStream_t)stream, d_pix, w, h, t0, n_frames, seed);
-	CK(hipGetLastError());
-	return 0;
-}
-
-extern "C" int agmv_hip_interp_dev(agmv_hip_ctx* c, uint32_t* d_out, const uint32_t* d_f1, const uint32_t* d_f2, size_t n, void* stream)
-{
-	if (need_ctx(c, false)) return -1;
-	if (n == 0) return 0;
-	size_t blocks = (n + 255) / 256;
-	if (blocks > 8192) blocks = 8192;
-	hipLaunchKernelGGL(k_interp, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_out, d_f1, d_f2, n);
-	CK(hipGetLastError());
-	return 0;
-}
-
-extern "C" int agmv_hip_histogram_dev(agmv_hip_ctx* c, const uint32_t* d_pix, size_t n, int quality, uint32_t* d_hist, void* stream)
-{
-	if (need_ctx(c, false)) return -1;
-	if (n == 0) return 0;
-	size_t blocks = (n + 255) / 256;
-	if (blocks > 8192) blocks = 8192;
-	hipLaunchKernelGGL(k_histogram, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_pix, n, quality, d_hist);
-	CK(hipGetLastError());
-	return 0;
-}
-
-extern "C" int agmv_hip_similarity_dev(agmv_hip_ctx* c, const uint32_t* d_pix, uint32_t n_frames, size_t n_pixels, uint32_t* d_counts, void* stream)
-{
-	if (need_ctx(c, false)) return -1;
-	if (n_pixels == 0 || n_pixels > 0xFFFFFFFFu) { snprintf(g_err, sizeof(g_err), "agmv_hip: similarity needs 1 .. 2^32 - 1 pixels per frame"); return -1; }
-	if (n_frames < 2) return 0;                                // no pair
-	const size_t blocks = (n_pixels + 2047) / 2048;            // 256 lanes x 8 pixels
-	CK(hipMemsetAsync(d_counts, 0, 4 * (size_t)(n_frames - 1), (hipStream_t)stream));
-	const int vec = (n_pixels & 3) == 0 && ((uintptr_t)d_pix & 15) == 0;
-	hipLaunchKernelGGL(k_similarity, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_pix, n_frames, n_pixels, vec, d_counts);
-	CK(hipGetLastError());
-	return 0;
-}
-
-extern "C" int agmv_hip_gather_dev(agmv_hip_ctx* c, const uint32_t* d_src, size_t src_frame_pixels, uint32_t n_frames, const uint32_t* d_index,
-                                   size_t n_out, uint32_t* d_dst, void* stream)
-{
-	if (need_ctx(c, false)) return -1;
-	if (n_frames == 0 || n_out == 0) return 0;
-	if (n_out > ((size_t)1 << 39)) { snprintf(g_err, sizeof(g_err), "agmv_hip: gather table too long"); return -1; }
-	hipLaunchKernelGGL(k_gather, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_src, src_frame_pixels, n_frames,
-	                   d_index, n_out, d_dst);
-	CK(hipGetLastError());
-	return 0;
-}
-
-// ---- the same on clips in the caller's pixel layout ----
-extern "C" size_t agmv_hip_pixfmt_frame_bytes(int fmt, size_t n_pixels)
-{
-	switch (fmt) {
-	case PF_XRGB32: case PF_RGBA32: return 4 * n_pixels;
-	case PF_RGB24: case PF_BGR24: case PF_RGB8P: return 3 * n_pixels;
-	default: return 0;
-	}
-}
-
-static int bad_pixfmt(int fmt)
-{
-	if (fmt >= PF_XRGB32 && fmt <= PF_RGB8P) return 0;
-	snprintf(g_err, sizeof(g_err), "agmv_hip: unknown pixel format %d", fmt);
-	return -1;
-}
-
-// the grid of the kernels that give a thread 16 pixels of one frame: blocks per frame, and whether all of them fit
-static int pf_grid(size_t n_pixels, uint32_t n_frames, uint32_t* bpf, unsigned* blocks)
-{
-	const size_t per = (n_pixels + 4095) / 4096;
-	if (per * n_frames > 0x7FFFFFFFull) { snprintf(g_err, sizeof(g_err), "agmv_hip: clip too large for one launch"); return -1; }
-	*bpf = (uint32_t)per; *blocks = (unsigned)(per * n_frames);
-	return 0;
-}
-
-// every frame of the clip (planes frame_pixels apart) starts on a 16-byte boundary
-static int pf_aligned(int fmt, const void* d, size_t frame_pixels, uint32_t n_frames)
-{
-	if ((uintptr_t)d & 15) return 0;
-	if (fmt == PF_RGB8P && (frame_pixels & 15)) return 0;
-	return n_frames == 1 || (agmv_hip_pixfmt_frame_bytes(fmt, frame_pixels) & 15) == 0;
-}
-
-#define PF_LAUNCH(kernel, ...) do { switch (fmt) { \
-	case PF_RGB24: hipLaunchKernelGGL(kernel<PF_RGB24>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-	case PF_BGR24: hipLaunchKernelGGL(kernel<PF_BGR24>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-	case PF_RGBA32: hipLaunchKernelGGL(kernel<PF_RGBA32>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-	default: hipLaunchKernelGGL(kernel<PF_RGB8P>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); break; } } while (0)
-
-extern "C" int agmv_hip_pixels_to_xrgb_dev(agmv_hip_ctx* c, int fmt, const void* d_src, size_t frame_pixels, uint32_t n_frames, size_t n_pixels,
-                                           uint32_t* d_dst, void* stream)
-{
-	if (need_ctx(c, false) || bad_pixfmt(fmt)) return -1;
-	if (n_pixels > frame_pixels) { snprintf(g_err, sizeof(g_err), "agmv_hip: n_pixels %zu > frame_pixels %zu", n_pixels, frame_pixels); return -1; }
-	if (n_frames == 0 || n_pixels == 0) return 0;
-	if (fmt == PF_XRGB32) {
-		if (n_frames == 1 || n_pixels == frame_pixels) CK(hipMemcpyAsync(d_dst, d_src, (size_t)n_frames * n_pixels * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-		else CK(hipMemcpy2DAsync(d_dst, n_pixels * 4, d_src, frame_pixels * 4, n_pixels * 4, n_frames, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-		return 0;
-	}
-	uint32_t bpf; unsigned blocks;
-	if (pf_grid(n_pixels, n_frames, &bpf, &blocks)) return -1;
-	const int wide = pf_aligned(fmt, d_src, frame_pixels, n_frames) && pf_aligned(PF_XRGB32, d_dst, n_pixels, n_frames);
-	PF_LAUNCH(k_pix_to_xrgb, (const uint8_t*)d_src, frame_pixels, agmv_hip_pixfmt_frame_bytes(fmt, frame_pixels), n_pixels, bpf, wide, d_dst);
-	CK(hipGetLastError());
-	return 0;
-}
-
-extern "C" int agmv_hip_pixels_from_xrgb_dev(agmv_hip_ctx* c, int fmt, const uint32_t* d_src, uint32_t n_frames, size_t n_pixels, void* d_dst, void* stream)
-{
-	if (need_ctx(c, false) || bad_pixfmt(fmt)) return -1;
-	if (n_frames == 0 || n_pixels == 0) return 0;
-	if (fmt == PF_XRGB32) {
-		CK(hipMemcpyAsync(d_dst, d_src, (size_t)n_frames * n_pixels * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-		return 0;
-	}
-	uint32_t bpf; unsigned blocks;
-	if (pf_grid(n_pixels, n_frames, &bpf, &blocks)) return -1;
-	const int wide = pf_aligned(fmt, d_dst, n_pixels, n_frames) && pf_aligned(PF_XRGB32, d_src, n_pixels, n_frames);
-	PF_LAUNCH(k_pix_from_xrgb, d_src, n_pixels, agmv_hip_pixfmt_frame_bytes(fmt, n_pixels), bpf, wide, (uint8_t*)d_dst);
-	CK(hipGetLastError());
-	return 0;
-}
-
-extern "C" int agmv_hip_gather_fmt_dev(agmv_hip_ctx* c, int fmt, const void* d_src, size_t src_frame_pixels, uint32_t n_frames, const uint32_t* d_index,
-                                       size_t n_out, uint32_t* d_dst, void* stream)
-{
-	if (need_ctx(c, false) || bad_pixfmt(fmt)) return -1;
-	if (fmt == PF_XRGB32) return agmv_hip_gather_dev(c, (const uint32_t*)d_src, src_frame_pixels, n_frames, d_index, n_out, d_dst, stream);
-	if (n_frames == 0 || n_out == 0) return 0;
-	if (n_out > ((size_t)1 << 39)) { snprintf(g_err, sizeof(g_err), "agmv_hip: gather table too long"); return -1; }
-	hipLaunchKernelGGL(k_gather_fmt, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_src, fmt, src_frame_pixels,
-	                   agmv_hip_pixfmt_frame_bytes(fmt, src_frame_pixels), n_frames, d_index, n_out, d_dst);
-	CK(hipGetLastError());
-	return 0;
-}
-
-extern "C" int agmv_hip_histogram_fmt_dev(agmv_hip_ctx* c, int fmt, const void* d_src, size_t frame_pixels, uint32_t n_frames, size_t n_pixels, int quality,
-                                          uint32_t* d_hist, void* stream)
-{
-	if (need_ctx(c, false) || bad_pixfmt(fmt)) return -1;
-	if (n_pixels > frame_pixels) { snprintf(g_err, sizeof(g_err), "agmv_hip: n_pixels %zu > frame_pixels %zu", n_pixels, frame_pixels); return -1; }
-	if (n_frames == 0 || n_pixels == 0) return 0;
-	if (fmt == PF_XRGB32) {
-		const uint32_t* d_pix = (const uint32_t*)d_src;
-		if (n_pixels == frame_pixels) return agmv_hip_histogram_dev(c, d_pix, (size_t)n_frames * frame_pixels, quality, d_hist, stream);   // one run of pixels
-		for (uint32_t f = 0; f < n_frames; f++) if (agmv_hip_histogram_dev(c, d_pix + (size_t)f * frame_pixels, n_pixels, quality, d_hist, stream)) return -1;
-		return 0;
-	}
-	uint32_t bpf; unsigned blocks;
-	if (pf_grid(n_pixels, n_frames, &bpf, &blocks)) return -1;
-	const int wide = pf_aligned(fmt, d_src, frame_pixels, n_frames);
-	PF_LAUNCH(k_histogram_fmt, (const uint8_t*)d_src, frame_pixels, agmv_hip_pixfmt_frame_bytes(fmt, frame_pixels), n_pixels, bpf, wide, quality, d_hist);
-	CK(hipGetLastError());
-	return 0;
-}
-
-extern "C" int agmv_hip_similarity_fmt_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t n_frames, size_t n_pixels, uint32_t* d_counts, void* stream)
-{
-	if (need_ctx(c, false) || bad_pixfmt(fmt)) return -1;
-	if (fmt == PF_XRGB32) return agmv_hip_similarity_dev(c, (const uint32_t*)d_src, n_frames, n_pixels, d_counts, stream);
-	if (n_pixels == 0 || n_pixels > 0xFFFFFFFFu) { snprintf(g_err, sizeof(g_err), "agmv_hip: similarity needs 1 .. 2^32 - 1 pixels per frame"); return -1; }
-	if (n_frames < 2) return 0;                                // no pair
-	const unsigned blocks = (unsigned)((n_pixels + 4095) / 4096);    // 256 lanes x 16 pixels
-	CK(hipMemsetAsync(d_counts, 0, 4 * (size_t)(n_frames - 1), (hipStream_t)stream));
-	const int vec = (n_pixels & 15) == 0 && ((uintptr_t)d_src & 15) == 0;
-	const size_t frame_bytes = agmv_hip_pixfmt_frame_bytes(fmt, n_pixels);
-	switch (fmt) {                                             // (the grey is a sum: the two 3-byte orders are one kernel)
-	case PF_RGB24: case PF_BGR24:
-		hipLaunchKernelGGL(k_similarity_fmt<PF_RGB24>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_src, n_frames, n_pixels, frame_bytes, vec, d_counts);
-		break;
-	case PF_RGBA32:
-		hipLaunchKernelGGL(k_similarity_fmt<PF_RGBA32>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_src, n_frames, n_pixels, frame_bytes, vec, d_counts);
-		break;
-	default:
-		hipLaunchKernelGGL(k_similarity_fmt<PF_RGB8P>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_src, n_frames, n_pixels, frame_bytes, vec, d_counts);
-		break;
-	}
-	CK(hipGetLastError());
-	return 0;
-}
-
-// ---- the same on clips in 8-bit YUV 4:2:0: fmt is 16 (NV12) or 17 (I420), | 0x100 for BT.709, | 0x200 for full range ----
-static int yuv_base(int fmt) { return (fmt & ~0x3FF) == 0 && ((fmt & 0xFF) == PF_NV12 || (fmt & 0xFF) == PF_I420) ? fmt & 0xFF : 0; }
-
-// the usual 8-bit fixed-point matrices, indexed by (fmt >> 8) & 3: BT.601 limited, BT.709 limited, BT.601 full, BT.709 full
-static const yuv_rd YUV_RD[4] = { { 298, 16, 409, 100, 208, 516 }, { 298, 16, 459, 55, 136, 541 }, { 256, 0, 359, 88, 183, 454 }, { 256, 0, 403, 48, 120, 475 } };
-static const yuv_wr YUV_WR[4] = { { 66, 129, 25, 16, -38, -74, 112, 112, -94, -18 }, { 47, 157, 16, 16, -26, -86, 112, 112, -102, -10 },
-                                  { 77, 150, 29, 0, -43, -85, 128, 128, -107, -21 }, { 54, 183, 19, 0, -29, -99, 128, 128, -116, -12 } };
-
-extern "C" size_t agmv_hip_yuv_frame_bytes(int fmt, uint32_t w, uint32_t h)
-{
-	if (!yuv_base(fmt)) return 0;
-	return (size_t)w * h + 2 * (size_t)((w + 1) / 2) * ((h + 1) / 2);
-}
-
-static int bad_yuv(int fmt, uint32_t w, uint32_t h)
-{
-	if (!yuv_base(fmt)) { snprintf(g_err, sizeof(g_err), "agmv_hip: unknown pixel format 0x%x (a YUV 4:2:0 format is needed)", (unsigned)fmt); return -1; }
-	if (w == 0 || h == 0 || (unsigned long long)w * h > (1ull << 30)) { snprintf(g_err, sizeof(g_err), "agmv_hip: YUV frames of %u x %u", w, h); return -1; }
-	return 0;
-}
-
-// a clip whose patches of 16 x 2 pixels can be read and written with 16-byte (I420 chroma: 8-byte) accesses
-static int yuv_wide(int fmt, const void* d, uint32_t w, uint32_t h, uint32_t n_frames)
-{
-	return (w & 15) == 0 && ((uintptr_t)d & 15) == 0 && (n_frames == 1 || (agmv_hip_yuv_frame_bytes(fmt, w, h) & 15) == 0);
-}
-
-// the grid of the kernels that give a thread 32 pixels of one frame: wide the patches of the rows that hold the first n_pixels,
-// else runs of 32 pixels
-static int yuv_grid(uint32_t w, size_t n_pixels, int wide, uint32_t n_frames, uint32_t* bpf, unsigned* blocks)
-{
-	const size_t rows = (n_pixels + w - 1) / w;
-	const size_t per = wide ? ((size_t)(w >> 4) * ((rows + 1) / 2) + 255) / 256 : (n_pixels + 8191) / 8192;
-	if (per * n_frames > 0x7FFFFFFFull) { snprintf(g_err, sizeof(g_err), "agmv_hip: clip too large for one launch"); return -1; }
-	*bpf = (uint32_t)per; *blocks = (unsigned)(per * n_frames);
-	return 0;
-}
-
-#define YUV_LAUNCH(kernel, ...) do { \
-	if (yuv_base(fmt) == PF_NV12) hipLaunchKernelGGL(kernel<PF_NV12>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
-	else hipLaunchKernelGGL(kernel<PF_I420>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); } while (0)
-
-extern "C" int agmv_hip_yuv_to_xrgb_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames, size_t n_pixels, uint32_t* d_dst,
-                                        void* stream)
-{
-	if (need_ctx(c, false) || bad_yuv(fmt, w, h)) return -1;
-	if (n_pixels > (size_t)w * h) { snprintf(g_err, sizeof(g_err), "agmv_hip: n_pixels %zu > %u x %u", n_pixels, w, h); return -1; }
-	if (n_frames == 0 || n_pixels == 0) return 0;
-	uint32_t bpf; unsigned blocks;
-	const int wide = yuv_wide(fmt, d_src, w, h, n_frames) && pf_aligned(PF_XRGB32, d_dst, n_pixels, n_frames);
-	if (yuv_grid(w, n_pixels, wide, n_frames, &bpf, &blocks)) return -1;
-	YUV_LAUNCH(k_yuv_to_xrgb, (const uint8_t*)d_src, w, h, agmv_hip_yuv_frame_bytes(fmt, w, h), (uint32_t)n_pixels, bpf, wide, YUV_RD[(fmt >> 8) & 3], d_dst);
-	CK(hipGetLastError());
-	return 0;
-}
-
-extern "C" int agmv_hip_yuv_from_xrgb_dev(agmv_hip_ctx* c, int fmt, const uint32_t* d_src, uint32_t w, uint32_t h, uint32_t n_frames, void* d_dst, void* stream)
-{
-	if (need_ctx(c, false) || bad_yuv(fmt, w, h)) return -1;
-	if (n_frames == 0) return 0;
-	uint32_t bpf; unsigned blocks;
-	const int wide = yuv_wide(fmt, d_dst, w, h, n_frames) && pf_aligned(PF_XRGB32, d_src, (size_t)w * h, n_frames);
-	if (yuv_grid(w, (size_t)w * h, wide, n_frames, &bpf, &blocks)) return -1;
-	YUV_LAUNCH(k_yuv_from_xrgb, d_src, w, h, agmv_hip_yuv_frame_bytes(fmt, w, h), bpf, wide, YUV_WR[(fmt >> 8) & 3], (uint8_t*)d_dst);
-	CK(hipGetLastError());
-	return 0;
-}
-
-extern "C" int agmv_hip_yuv_gather_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames, const uint32_t* d_index, size_t n_out,
-                                       uint32_t* d_dst, void* stream)
-{
-	if (need_ctx(c, false) || bad_yuv(fmt, w, h)) return -1;
-	if (n_frames == 0 || n_out == 0) return 0;
-	if (n_out > ((size_t)1 << 39)) { snprintf(g_err, sizeof(g_err), "agmv_hip: gather table too long"); return -1; }
-	const unsigned blocks = (unsigned)((n_out + 255) / 256);
-	YUV_LAUNCH(k_yuv_gather, (const uint8_t*)d_src, w, h, agmv_hip_yuv_frame_bytes(fmt, w, h), n_frames, d_index, n_out, YUV_RD[(fmt >> 8) & 3], d_dst);
-	CK(hipGetLastError());
-	return 0;
-}
-
-extern "C" int agmv_hip_yuv_histogram_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames, size_t n_pixels, int quality,
-                                          uint32_t* d_hist, void* stream)
-{
-	if (need_ctx(c, false) || bad_yuv(fmt, w, h)) return -1;
-	if (n_pixels > (size_t)w * h) { snprintf(g_err, sizeof(g_err), "agmv_hip: n_pixels %zu > %u x %u", n_pixels, w, h); return -1; }
-	if (n_frames == 0 || n_pixels == 0) return 0;
-	uint32_t bpf; unsigned blocks;
-	const int wide = yuv_wide(fmt, d_src, w, h, n_frames);
-	if (yuv_grid(w, n_pixels, wide, n_frames, &bpf, &blocks)) return -1;
-	YUV_LAUNCH(k_yuv_histogram, (const uint8_t*)d_src, w, h, agmv_hip_yuv_frame_bytes(fmt, w, h), (uint32_t)n_pixels, bpf, wide, quality, YUV_RD[(fmt >> 8) & 3], d_hist);
-	CK(hipGetLastError());
-	return 0;
-}
-
-extern "C" int agmv_hip_yuv_similarity_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames, uint32_t* d_counts, void* stream)
-{
-	if (need_ctx(c, false) || bad_yuv(fmt, w, h)) return -1;
-	if (n_frames < 2) return 0;                                // no pair
-	const unsigned blocks = (unsigned)(((size_t)((w + 15) >> 4) * ((h + 1) >> 1) + 255) / 256);    // 256 lanes x one patch
-	CK(hipMemsetAsync(d_counts, 0, 4 * (size_t)(n_frames - 1), (hipStream_t)stream));
-	const int wide = yuv_wide(fmt, d_src, w, h, n_frames);
-	YUV_LAUNCH(k_yuv_similarity, (const uint8_t*)d_src, n_frames, w, h, agmv_hip_yuv_frame_bytes(fmt, w, h), wide, YUV_RD[(fmt >> 8) & 3], d_counts);
-	CK(hipGetLastError());
-	return 0;
-}
-
-// ---- the exact box-filter downscale (AGMV_SCALE_AREA) of a clip in any layout: fmt as above, the YUV formats with their flags ----
-extern "C" int agmv_hip_scale_area_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t src_w, uint32_t src_h, uint32_t n_frames, uint32_t dst_w, uint32_t dst_h,
-                                       uint32_t* d_dst, void* stream)
-{
-	if (need_ctx(c, false)) return -1;
-	const int yuv = yuv_base(fmt);
-	if (!yuv && bad_pixfmt(fmt)) return -1;
-	if (src_w == 0 || src_h == 0 || dst_w == 0 || dst_h == 0 || dst_w > src_w || dst_h > src_h || (unsigned long long)src_w * src_h > (1ull << 24)) {
-		snprintf(g_err, sizeof(g_err), "agmv_hip: area scale of %u x %u to %u x %u (a downscale of at most 2^24 source pixels is needed)", src_w, src_h, dst_w, dst_h);
-		return -1;
-	}
-	if (n_frames == 0) return 0;
-	ScaleArgs A;
-	A.src = (const uint8_t*)d_src; A.dst = d_dst;
-	A.frame_bytes = yuv ? agmv_hip_yuv_frame_bytes(fmt, src_w, src_h) : agmv_hip_pixfmt_frame_bytes(fmt, (size_t)src_w * src_h);
-	A.sw = src_w; A.sh = src_h; A.dw = dst_w; A.dh = dst_h; A.tiles = (dst_w + SC_TILE - 1) / SC_TILE;
-	A.items = (unsigned long long)n_frames * dst_h * A.tiles;
-	A.wide = yuv ? yuv_wide(fmt, d_src, src_w, src_h, n_frames) : pf_aligned(fmt, d_src, (size_t)src_w * src_h, n_frames);
-	A.small = (unsigned long long)src_w * dst_w < (1ull << 32);
-	A.m = YUV_RD[(fmt >> 8) & 3];
-	const dim3 grid((unsigned)(A.items < 65536 ? A.items : 65536)), block(256);
-	switch (yuv ? yuv : fmt) {
-	case PF_XRGB32: hipLaunchKernelGGL(k_scale_area<PF_XRGB32>, grid, block, 0, (hipStream_t)stream, A); break;
-	case PF_RGB24: hipLaunchKernelGGL(k_scale_area<PF_RGB24>, grid, block, 0, (hipStream_t)stream, A); break;
-	case PF_BGR24: hipLaunchKernelGGL(k_scale_area<PF_BGR24>, grid, block, 0, (hipStream_t)stream, A); break;
-	case PF_RGBA32: hipLaunchKernelGGL(k_scale_area<PF_RGBA32>, grid, block, 0, (hipStream_t)stream, A); break;
-	case PF_RGB8P: hipLaunchKernelGGL(k_scale_area<PF_RGB8P>, grid, block, 0, (hipStream_t)stream, A); break;
-	case PF_NV12: hipLaunchKernelGGL(k_scale_area<PF_NV12>, grid, block, 0, (hipStream_t)stream, A); break;
-	default: hipLaunchKernelGGL(k_scale_area<PF_I420>, grid, block, 0, (hipStream_t)stream, A); break;
-	}
-	CK(hipGetLastError());
-	return 0;
 }
 
 // ---- streams, pinned staging and asynchronous copies for C hosts (the pipelined drivers of agmv_pipeline.c) ----

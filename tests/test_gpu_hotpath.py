@@ -751,6 +751,31 @@ def test_synth_interp_histogram(torch, hip):
         assert (got_h == exp_h).all()
 
 
+def test_histogram_runs_and_tails(torch, hip):
+    """k_histogram adds the length of each run of equal codes inside a wave with one atomic.  Noise has runs of length 1 only:
+    here the pixels come in runs of 1 .. 130 equal colours (runs that end inside a wave, at its edge, and span waves), and the
+    pixel counts end inside the first wave, at its edge, behind it, in the second block and in the 17th.  The table is added
+    to, so it starts non-zero, and lies between guard words."""
+    rng = np.random.default_rng(11)
+    lens = np.concatenate(([1, 130, 63, 64, 65], rng.integers(1, 131, size=120)))
+    pix = np.repeat(rng.integers(0, 1 << 24, size=lens.size, dtype=np.uint32), lens)[:4100]
+    assert pix.size == 4100
+    G, NB, mark = 64, 1 << 19, 0xA5A5A5A5
+    base = ((np.arange(NB, dtype=np.uint64) * 2654435761) % 65521 + 1).astype(np.uint32)
+    d_base = dev_u32(torch, base)
+    r, g_, bb = (pix >> 16) & 255, (pix >> 8) & 255, pix & 255
+    for q, shifts in ((1, (2, 2, 1, 13, 7)), (2, (3, 2, 2, 12, 6)), (3, (3, 2, 3, 11, 5))):
+        code = ((r >> shifts[0]) << shifts[3]) | ((g_ >> shifts[1]) << shifts[4]) | (bb >> shifts[2])
+        for n in (1, 63, 64, 65, 257, 4100):
+            buf = torch.full((G + NB + G,), mark - (1 << 32), dtype=torch.int32, device="cuda")
+            buf[G:G + NB] = d_base
+            hip.histogram_dev(dev_u32(torch, pix[:n]), q, hist=buf[G:G + NB])
+            got = to_u32(buf)
+            exp = base + np.bincount(code[:n], minlength=NB).astype(np.uint32)
+            assert (got[G:G + NB] == exp).all(), (q, n, np.argwhere(got[G:G + NB] != exp)[:4])
+            assert (got[:G] == mark).all() and (got[G + NB:] == mark).all(), (q, n, "guard words written")
+
+
 # ------------------------------------------------------------------------------- full size
 def test_full_size_properties(torch, hip):
     """BASELINE-sized frames (1080p), sizes the CPU oracle cannot cover in seconds: check
