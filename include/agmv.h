@@ -7,7 +7,8 @@
  * tools/agmvcli) compile and link unchanged against libagmv_amd/libagmv.so.
  * The per-frame work behind AGMV_EncodeFrame / AGMV_DecodeFrameChunk and the batch drivers
  * runs on the GPU through include/agmv_hip.h; LZSS/LZ77, the container, BMP I/O and the
- * palette build are host C.  There is no CPU fallback for the hot path: without a GPU the
+ * palette build are host C (the opt-in refinement of the palette, AGMV_BuildPaletteRefined,
+ * runs on the GPU).  There is no CPU fallback for the hot path: without a GPU the
  * encode/decode entry points abort with a message (the void encoders have no error channel,
  * reference src/agmv_encode.c:529).
  *
@@ -281,6 +282,35 @@ void AGMV_SynthFrame(unsigned* pix, unsigned w, unsigned h, unsigned t, unsigned
 /* palette build of the encoders (reference src/agmv_encode.c:2364-2656) from a 2^19-bin histogram
    of AGMV_QuantizeColor codes (the +1 initial count is added inside).  pal0/pal1: 256 words each. */
 void AGMV_BuildPalette(const unsigned* hist, AGMV_QUALITY quality, AGMV_OPT opt, u32 pal0[256], u32 pal1[256]);
+
+/* Palette refinement: the colours AGMV_BuildPalette picks, moved by weighted k-means (Lloyd's algorithm) over the histogram.
+   Opt-in; the file format does not change, only the colours in the header's palettes do.  Everything is exact integer work:
+     points     every AGMV_QuantizeColor code of the quality with hist[code] > 0 (the all-ones code included; bins above the
+                quality's largest code are not read).  Its weight is w = hist[code], without the +1 AGMV_BuildPalette adds.  Its
+                colour is the centre of its bin: the channels of AGMV_ReverseQuantizeColor(code) plus half a step,
+                HIGH R +2, G +2, B +1;  MID R +4, G +2, B +2;  LOW R +4, G +2, B +4.
+     centroids  k colours 0x00RRGGBB, c[0 .. k-1].  The first n_free move, the others are pinned.
+     a round    1. every point goes to the j that minimises (r-cr)^2 + (g-cg)^2 + (b-cb)^2, the lowest j on a tie (the metric and
+                   the tie rule of AGMV_FindNearestColor); pinned centroids take part;
+                2. for every j < n_free whose points weigh W_j > 0 each channel of c[j] becomes (sum of w * channel + W_j div 2)
+                   div W_j, in exact 64-bit unsigned sums.  A centroid with W_j = 0 and a pinned one keep their colour.
+     stopping   at most `iterations` rounds, and none after the first round that changes no centroid.  rounds counts those
+                that changed at least one.  sse[0] is the sum of w * (distance to the assigned centroid) over the points before
+                the first round, sse[1] the same for the centroids returned, both modulo 2^64.
+   AGMV_BuildPaletteRefined starts from the pick list of AGMV_BuildPalette (its picks before the slot map, as colours through
+   AGMV_ReverseQuantizeColor): k = n_free = 256 for the 256-colour opts; k = 512, n_free = 511 for the others, with c[511] = 0
+   pinned -- the reference drops pick 511, and palette0[126], which the slot map never fills, is a black the encoder can choose,
+   so the pinned centroid stands for that slot.  The slot map then scatters c[0 .. 510] (c[0 .. 255]) as it scatters the picks.
+   The refinement runs on the library's device (agmv_hip_palette_refine_dev of include/agmv_hip.h).  With iterations == 0 the
+   call IS AGMV_BuildPalette and opens no device.  sse may be NULL.  Returns 0, or -1 for a NULL pointer or an unknown enum value;
+   a GPU failure aborts with a message, as in the encoders.
+   AGMV_SetPaletteRefine sets the rounds the sequence encoders (all three BMP drivers and every AGMV_EncodeFrames*Dev) ask for:
+   0 = not set, then env AGMV_PALETTE_REFINE decides, and without it the refinement is off and every file is what it was
+   without this knob; values above 64 count as 64.  With AGMV_TRACE in the environment the rounds, both distortions and the
+   stage's time are printed. */
+int AGMV_BuildPaletteRefined(const unsigned* hist, AGMV_QUALITY quality, AGMV_OPT opt, u32 pal0[256], u32 pal1[256], unsigned iterations,
+                             unsigned long long sse[2]);
+void AGMV_SetPaletteRefine(unsigned iterations);
 
 /* Sequences from and to frames in GPU memory: the .agmv files of the three BMP drivers without the BMPs.
    d_frames is device memory of the library's own device (env AGMV_DEVICE, default 0; AGMV_DEVICES is not consulted),

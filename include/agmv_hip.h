@@ -393,6 +393,23 @@ int agmv_hip_yuv_similarity_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, u
 int agmv_hip_scale_area_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, uint32_t src_w, uint32_t src_h, uint32_t n_frames,
                             uint32_t dst_w, uint32_t dst_h, uint32_t* d_dst, void* stream);
 
+/* -- the palette refined by weighted k-means ------------------------------------------------------
+ * The refinement of include/agmv.h ("palette refinement"), which holds the definition: Lloyd's algorithm over the points of a
+ * histogram, in exact integers.
+ *   d_hist      2^19 bins as the agmv_hip_histogram*_dev functions fill them; not modified.  Only the bins of the quality's codes
+ *               are read (2^19 HIGH, 2^17 MID, 2^16 LOW).
+ *   d_pal       k colours 0x00RRGGBB, in and out; the first n_free move, the others are pinned.  Bits >= 24 are ignored, and
+ *               cleared in a centroid that moves.
+ *   iterations  rounds at most (<= 4096); 0 only measures.
+ *   d_rounds    one word: the rounds that changed at least one centroid.
+ *   d_sse       two words: the distortion of the centroids given and of the centroids returned.
+ * 1 <= k <= 512, n_free <= k, quality 1 .. 3: anything else returns non-zero with a message, touches no memory and launches
+ * nothing.  Asynchronous on `stream`: 2 * (iterations + 1) small launches and no host synchronisation; after the round that
+ * changes nothing a device flag makes the remaining launches return at once.  The sums of a pass live in a work area of the
+ * context (16 KB): calls on one context must not overlap.  Exact and repeatable: the same outputs from run to run. */
+int agmv_hip_palette_refine_dev(agmv_hip_ctx* ctx, const uint32_t* d_hist, int quality, uint32_t* d_pal, uint32_t k, uint32_t n_free,
+                                uint32_t iterations, uint32_t* d_rounds, uint64_t* d_sse, void* stream);
+
 /* optional timing: when enabled the library records HIP events on the caller's stream around its three kernel
    groups; agmv_hip_last_kernel_ms(which) returns the last launch's duration in ms (0 = k_encode, 1 = the parser
    kernels, 2 = k_decode + k_fixup, 3 = the whole of agmv_hip_parse_decode_frames_dev / agmv_hip_decode_bitstreams_dev), or a negative value if

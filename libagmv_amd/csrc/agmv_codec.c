@@ -18,6 +18,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 #include <unistd.h>
 
 #include "agmv_hip.h"
@@ -28,7 +29,7 @@
 static agmv_hip_ctx* g_ctx = NULL;
 static uint32_t g_pal[512];
 static int g_pal_mode = -1;
-static unsigned g_batch_frames = 0, g_lz_threads = 0, g_devices = 0;
+static unsigned g_batch_frames = 0, g_lz_threads = 0, g_devices = 0, g_palette_refine = 0;
 static unsigned long g_export_count = 0;            /* AGIDL's expcount, extern/agidl/src/agidl_img_export.c:18 */
 
 void agmv_die(const char* what)
@@ -53,6 +54,7 @@ static int bad_geometry(uint32_t w, uint32_t h)
 void AGMV_SetBatchFrames(unsigned n) { g_batch_frames = n; }
 void AGMV_SetLZThreads(unsigned n) { g_lz_threads = n; }
 void AGMV_SetDevices(unsigned n) { g_devices = n; }
+void AGMV_SetPaletteRefine(unsigned n) { g_palette_refine = n; }
 
 /* frames per GPU batch: what the caller asked for, else about 128 MB of source pixels (64 frames at most), whole GOPs */
 static unsigned batch_frames(size_t npx)
@@ -74,6 +76,15 @@ static unsigned devices(void)
 	const char* e = getenv("AGMV_DEVICES");
 	if (!n && e) n = (unsigned)atoi(e);
 	return n ? n : 1;
+}
+
+/* rounds of the palette refinement the sequence encoders run (AGMV_SetPaletteRefine / env AGMV_PALETTE_REFINE; default 0 = off) */
+static unsigned palette_refine(void)
+{
+	unsigned n = g_palette_refine;
+	const char* e = getenv("AGMV_PALETTE_REFINE");
+	if (!n && e && atoi(e) > 0) n = (unsigned)atoi(e);
+	return n > 64 ? 64 : n;
 }
 
 /* host threads of the pipelines (BMP parse, LZ, BMP export): what the caller asked for, else the cores this process may
@@ -452,13 +463,55 @@ static agmv_seq* seq_open(AGMV* a, FILE* file, const agmv_source* src, AGMV_OPT 
 	                     batch_frames((size_t)AGMV_GetWidth(a) * AGMV_GetHeight(a)), devices(), lz_threads(), pal);
 }
 
-/* pass 1 of the palette build on the GPU (histogram), pick on the host */
+/* AGMV_BuildPalette with the picked colours moved by weighted k-means on the GPU between the pick and the slot map
+   (include/agmv.h, "palette refinement").  The 512-colour opts pin centroid 511 at black: the slot map drops pick 511, and
+   palette0[126], which it never fills, is the black the encoder can choose. */
+int AGMV_BuildPaletteRefined(const unsigned* hist, AGMV_QUALITY quality, AGMV_OPT opt, u32 pal0[256], u32 pal1[256], unsigned iterations,
+                             unsigned long long sse[2])
+{
+	u32 pal[512];
+	uint32_t clr[512], rounds = 0, *d_hist, *d_pal, *d_rounds;
+	uint64_t e[2] = { 0, 0 }, *d_sse;
+	const uint32_t k = mode512_of(opt) ? 512 : 256, n_free = mode512_of(opt) ? 511 : 256;
+	struct timespec t0, t1;
+	agmv_hip_ctx* c;
+	u32 n;
+	if (!hist || !pal0 || !pal1 || opt < AGMV_OPT_I || opt > AGMV_OPT_NDS || quality < AGMV_HIGH_QUALITY || quality > AGMV_LOW_QUALITY) return -1;
+	if (iterations == 0) {
+		AGMV_BuildPalette(hist, quality, opt, pal0, pal1);
+		return 0;
+	}
+	clock_gettime(CLOCK_MONOTONIC, &t0);
+	agmv_palette_pick(hist, quality, pal);
+	for (n = 0; n < 512; n++) clr[n] = (uint32_t)AGMV_ReverseQuantizeColor(pal[n], quality);
+	if (k == 512) clr[511] = 0;
+	c = ctx();
+	d_hist = (uint32_t*)agmv_hip_malloc_on(c, 4u << 19); d_pal = (uint32_t*)agmv_hip_malloc_on(c, 4 * 512);
+	d_rounds = (uint32_t*)agmv_hip_malloc_on(c, 4); d_sse = (uint64_t*)agmv_hip_malloc_on(c, 16);
+	if (!d_hist || !d_pal || !d_rounds || !d_sse) agmv_die("device allocation for the palette refinement");
+	if (agmv_hip_memcpy_async(c, d_hist, hist, 4u << 19, 0, NULL) || agmv_hip_memcpy_async(c, d_pal, clr, 4 * k, 0, NULL) ||
+	    agmv_hip_palette_refine_dev(c, d_hist, (int)quality, d_pal, k, n_free, iterations, d_rounds, d_sse, NULL) ||
+	    agmv_hip_memcpy_async(c, clr, d_pal, 4 * k, 1, NULL) || agmv_hip_memcpy_async(c, &rounds, d_rounds, 4, 1, NULL) ||
+	    agmv_hip_memcpy_async(c, e, d_sse, 16, 1, NULL) || agmv_hip_stream_sync(c, NULL))
+		agmv_die("palette refinement");
+	agmv_hip_free_on(c, d_hist); agmv_hip_free_on(c, d_pal); agmv_hip_free_on(c, d_rounds); agmv_hip_free_on(c, d_sse);
+	for (n = 0; n < 512; n++) pal[n] = n < k ? (u32)clr[n] : 0;
+	agmv_palette_slots(pal, opt, pal0, pal1);
+	if (sse) { sse[0] = e[0]; sse[1] = e[1]; }
+	clock_gettime(CLOCK_MONOTONIC, &t1);
+	if (getenv("AGMV_TRACE"))
+		fprintf(stderr, "agmv trace: palette refinement: %u colours, %u of %u rounds moved a colour, distortion %llu -> %llu, %.3f s with the pick\n", (unsigned)k,
+		        (unsigned)rounds, iterations, (unsigned long long)e[0], (unsigned long long)e[1], (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec));
+	return 0;
+}
+
+/* pass 1 of the palette build on the GPU (histogram), pick on the host, refinement (when asked for) on the GPU */
 static void build_palette_from_frames(const agmv_source* src, u32 start, u32 end, u32 size, AGMV_QUALITY quality,
                                       AGMV_OPT opt, u32* p0, u32* p1)
 {
 	uint32_t* hist = (uint32_t*)malloc(4u << 19);
 	agmv_histogram_frames(ctx(), src, start, end, size, (int)quality, lz_threads(), hist);
-	AGMV_BuildPalette(hist, quality, opt, p0, p1);
+	if (AGMV_BuildPaletteRefined(hist, quality, opt, p0, p1, palette_refine(), NULL)) agmv_die("internal: palette build refused its arguments");
 	free(hist);
 }
 

@@ -134,6 +134,7 @@ struct agmv_hip_ctx {
 	void* lz_ws;                    // agmv_hip_lzss_frames_dev: work areas (agmv_lz_hip.hip)
 	void* lzd_ws;                   // agmv_hip_lz_decode_*: work areas (agmv_lz_decode_hip.hip)
 	void* lz77_ws;                  // agmv_hip_lz77_*: work areas (agmv_lz77_hip.hip)
+	void* pal_ws;                   // agmv_hip_palette_refine_dev: sums and flag of a pass, device memory (agmv_palette_hip.hip)
 };
 
 // for agmv_lz_hip.hip, the LZSS stage: the error text, the context's slot for its work areas, the device
@@ -146,6 +147,8 @@ void** agmv_hip_internal_lzd_slot(agmv_hip_ctx* c) { return &c->lzd_ws; }
 void agmv_hip_internal_lzd_free(void* p);
 void** agmv_hip_internal_lz77_slot(agmv_hip_ctx* c) { return &c->lz77_ws; }
 void agmv_hip_internal_lz77_free(void* p);
+void** agmv_hip_internal_pal_slot(agmv_hip_ctx* c) { return &c->pal_ws; }
+void agmv_hip_internal_pal_free(void* p);
 
 extern "C" size_t agmv_hip_max_usize(uint32_t w, uint32_t h, int mode512)
 {
@@ -2432,6 +2435,7 @@ extern "C" void agmv_hip_destroy(agmv_hip_ctx* c)
 	agmv_hip_internal_lz_free(c->lz_ws);
 	agmv_hip_internal_lzd_free(c->lzd_ws);
 	agmv_hip_internal_lz77_free(c->lz77_ws);
+	agmv_hip_internal_pal_free(c->pal_ws);
 	free(c);
 }
 

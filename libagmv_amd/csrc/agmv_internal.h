@@ -25,6 +25,10 @@ int  agmv_bmp_save(const char* path, const uint32_t* pix, uint32_t w, uint32_t h
 #define AGMV_NO_SOURCE 0xFFFFFFFFu
 uint32_t* agmv_scale_nearest_index(uint32_t w, uint32_t h, float sx, float sy, uint32_t* nw, uint32_t* nh);
 
+/* agmv_palette.c: the two halves of AGMV_BuildPalette */
+void agmv_palette_pick(const unsigned* hist, AGMV_QUALITY quality, u32 pal[512]);
+void agmv_palette_slots(const u32 clr[512], AGMV_OPT opt, u32 pal0[256], u32 pal1[256]);
+
 /* agmv_codec.c */
 void agmv_die(const char* what);
 

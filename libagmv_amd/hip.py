@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "agmv_hip_yuv_frame_bytes", "agmv_hip_yuv_to_xrgb_dev", "agmv_hip_yuv_from_xrgb_dev", "agmv_hip_yuv_gather_dev",
     "agmv_hip_yuv_histogram_dev", "agmv_hip_yuv_similarity_dev",
     "agmv_hip_scale_area_dev",
+    "agmv_hip_palette_refine_dev",
 ]
 
 
@@ -164,6 +165,9 @@ def load_library(path=None):
     if path is None or hasattr(L, "agmv_hip_scale_area_dev"):
         L.agmv_hip_scale_area_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, u32, u32, vp, vp]
         L.agmv_hip_scale_area_dev.restype = C.c_int
+    if path is None or hasattr(L, "agmv_hip_palette_refine_dev"):
+        L.agmv_hip_palette_refine_dev.argtypes = [vp, vp, C.c_int, vp, u32, u32, u32, vp, vp, vp]
+        L.agmv_hip_palette_refine_dev.restype = C.c_int
     L.agmv_hip_check.argtypes = [vp, vp]
     L.agmv_hip_enable_timing.argtypes = [vp, C.c_int]
     L.agmv_hip_enable_timing.restype = C.c_int
@@ -820,6 +824,19 @@ class AgmvHip:
         _check_vec("scale_area_dev: out", out, n_frames * dst_w * dst_h)
         self._ck(self.L.agmv_hip_scale_area_dev(self.ctx, fmt, src.data_ptr(), w, h, n_frames, dst_w, dst_h, out.data_ptr(), self._stream()))
         return out
+
+    # ------------------------------------------------------------------ the palette refined by weighted k-means (include/agmv.h)
+    def palette_refine_dev(self, hist, quality, pal, n_free, iterations):
+        """hist: int32 storage of the 2^19 u32 bins (not modified); pal: int32 storage of k colours 0x00RRGGBB, refined in place (the
+        first n_free move).  Returns (rounds int32 [1], sse int64 storage of two u64: before, after), device tensors; nothing waits."""
+        import torch
+        _check_vec("palette_refine_dev: hist", hist, 1 << 19)
+        _check_vec("palette_refine_dev: pal", pal, 1)
+        rounds = torch.empty(1, dtype=torch.int32, device=hist.device)
+        sse = torch.empty(2, dtype=torch.int64, device=hist.device)
+        self._ck(self.L.agmv_hip_palette_refine_dev(self.ctx, hist.data_ptr(), int(quality), pal.data_ptr(), pal.numel(), int(n_free), int(iterations),
+                                                    rounds.data_ptr(), sse.data_ptr(), self._stream()))
+        return rounds, sse
 
     # ------------------------------------------------------------------ host-buffer path
     def encode_host(self, frames, first_frame_count=0, ientries=None):
