@@ -1,8 +1,9 @@
 """libagmv_amd -- MI355X-native hot path of the AGMV codec (libagmv drop-in for that path).
 
 Layout
-  csrc/agmv_hip.hip   hand-written gfx950 kernels of the codec (table, encode, parse, decode, pack) + the core of the
+  csrc/agmv_hip.hip   hand-written gfx950 kernels of the encoder (table, encode, pack) + the core of the
                       C-ABI of include/agmv_hip.h (context, palette, streams, memory)
+  csrc/agmv_decode_hip.hip  the decoder: the parsers, k_decode, k_fixup and the calls of that C-ABI that launch them
   csrc/agmv_clip_hip.hip  the clip front end of that C-ABI: synth, interp, histogram, similarity, gather, the byte and
                       YUV 4:2:0 layouts, the area scale
   csrc/agmv_lz*_hip.hip   the LZSS / LZ77 stages of encoder and decoder on the GPU

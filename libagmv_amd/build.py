@@ -84,7 +84,7 @@ def build(force=False, verbose=False):
 
 
 def _build(force=False, verbose=False):
-    hip_srcs = [os.path.join(CSRC, "agmv_hip.hip"), os.path.join(CSRC, "agmv_lz_hip.hip"), os.path.join(CSRC, "agmv_lz_decode_hip.hip"),
+    hip_srcs = [os.path.join(CSRC, "agmv_hip.hip"), os.path.join(CSRC, "agmv_decode_hip.hip"), os.path.join(CSRC, "agmv_lz_hip.hip"), os.path.join(CSRC, "agmv_lz_decode_hip.hip"),
                 os.path.join(CSRC, "agmv_lz77_hip.hip"), os.path.join(CSRC, "agmv_clip_hip.hip"), os.path.join(CSRC, "agmv_palette_hip.hip")]
     hdrs = glob.glob(os.path.join(ROOT, "include", "*.h"))
     hip_so = os.path.join(HERE, "libagmv_hip.so")
