@@ -107,11 +107,21 @@ int agmv_hip_within2_count(agmv_hip_ctx* ctx, const uint32_t a[16], const uint32
  *    frame, parser workspace <= 15 % of the bitstream slab; LZSS: about 29 bytes per position of the largest chunk of a
  *    batch, at most 2^24 positions, ~460 MiB; LZ77: 5 bytes per input byte of the largest chunk of a batch, at most
  *    2^26 bytes, 320 MiB);
+ *  - agmv_hip_set_palette builds the tables on `stream` (contexts of a device that hold the same palette share one set: a
+ *    context that finds it makes `stream` wait for the build, wherever that runs, and does not wait itself).  It is not
+ *    asynchronous: a call that builds sends the colours up from the caller's memory and waits for `stream` once before
+ *    its kernels; a call that replaces the context's palette waits for the device.  So it MAY wait, and need not.
+ *    The tables are complete for work submitted to THAT stream afterwards; work of the context on another stream must
+ *    be ordered behind it by the caller (an event, or a synchronisation of the stream);
  *  - the encode entry points of ONE context share its look-back status and control words: a second encode is
  *    ordered behind the first (on another stream it waits for it through an event); use one context per
  *    concurrent encoder;
  *  - likewise the parse / decode entry points of ONE context share its parser work areas and repair bitmap: calls on
  *    different streams of one context must not overlap; use one context per concurrent decoder;
+ *  - the LZ-decode entry points of ONE context upload their per-call tables from one pinned staging buffer: a call returns
+ *    without waiting for the stream (agmv_hip_lz_decode_frames_sized_dev: for nothing at all) only when the upload of the
+ *    PREVIOUS call of that context has ended; otherwise it waits on the host for that upload (not for the kernels behind it)
+ *    before it rewrites the buffer.  The results are the same either way;
  *  - a device-side wait that runs into its bound (never observed on a healthy GPU) makes agmv_hip_check fail AND
  *    overwrites every size of that batch with 0xFFFFFFFF, so the bytes cannot be taken for valid ones. */
 

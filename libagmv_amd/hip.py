@@ -173,6 +173,20 @@ def load_library(path=None):
     L.agmv_hip_enable_timing.restype = C.c_int
     L.agmv_hip_last_kernel_ms.argtypes = [vp, C.c_int]
     L.agmv_hip_last_kernel_ms.restype = C.c_float
+    # streams, events, pinned staging and asynchronous copies (pointers: without a restype ctypes would cut them to 32 bits)
+    L.agmv_hip_stream_create.restype, L.agmv_hip_stream_create.argtypes = vp, [vp]
+    L.agmv_hip_stream_destroy.restype, L.agmv_hip_stream_destroy.argtypes = None, [vp, vp]
+    L.agmv_hip_stream_sync.restype, L.agmv_hip_stream_sync.argtypes = C.c_int, [vp, vp]
+    if path is None or hasattr(L, "agmv_hip_event_create"):         # (older builds under tools/variants/ lack them)
+        L.agmv_hip_event_create.restype, L.agmv_hip_event_create.argtypes = vp, [vp]
+        L.agmv_hip_event_destroy.restype, L.agmv_hip_event_destroy.argtypes = None, [vp, vp]
+        L.agmv_hip_event_record.restype, L.agmv_hip_event_record.argtypes = C.c_int, [vp, vp, vp]
+        L.agmv_hip_stream_wait_event.restype, L.agmv_hip_stream_wait_event.argtypes = C.c_int, [vp, vp, vp]
+    L.agmv_hip_host_alloc.restype, L.agmv_hip_host_alloc.argtypes = vp, [sz]
+    L.agmv_hip_host_free.restype, L.agmv_hip_host_free.argtypes = None, [vp]
+    L.agmv_hip_memcpy_async.argtypes = [vp, vp, vp, sz, C.c_int, vp]
+    L.agmv_hip_memset_async.argtypes = [vp, vp, C.c_int, sz, vp]
+    L.agmv_hip_memcpy_async.restype = L.agmv_hip_memset_async.restype = C.c_int
     L.agmv_hip_malloc.restype = vp
     L.agmv_hip_malloc.argtypes = [sz]
     L.agmv_hip_free.argtypes = [vp]
