@@ -312,6 +312,35 @@ int AGMV_BuildPaletteRefined(const unsigned* hist, AGMV_QUALITY quality, AGMV_OP
                              unsigned long long sse[2]);
 void AGMV_SetPaletteRefine(unsigned iterations);
 
+/* Pattern dithering: every pixel of a clip replaced by one of 16 palette colours whose mean approaches it, before the encoder
+   quantises it.  Opt-in; the file format does not change.  The dither is positional (a 4x4 threshold matrix, the size of the
+   codec's blocks), never error diffusion: a pixel's result depends on its colour and on (x & 3, y & 3) alone, so content that
+   does not move stays equal from frame to frame and the P-frames' COPY blocks survive.  Everything is integer work:
+     px        the pixel (R, G, B); bits >= 24 are ignored.  (x, y) is its position inside its own frame.
+     LUT       the exact nearest entry of a colour in the palette, by the rules of AGMV_FindNearestColor (256-colour opts) /
+               AGMV_FindNearestEntry (512-colour opts); an entry is pal_num << 8 | index, col(e) its colour.
+     s         the strength, 1 .. 64.
+       acc = (0, 0, 0)                                   signed, per channel
+       for i = 0 .. 15:
+           a   = clamp(px + ((acc * s) >> 6), 0, 255)    per channel; >> is arithmetic (rounds down)
+           e_i = LUT[a]
+           acc = acc + px - col(e_i)
+       key_i = (299 * R + 587 * G + 114 * B of col(e_i)) * 512 + e_i
+       sort the 16 keys ascending;  t = B4[y & 3][x & 3]
+       out(x, y) = col(entry of the t-th key)            as 0x00RRGGBB
+     B4        has the rows  0 8 2 10 / 12 4 14 6 / 3 11 1 9 / 15 7 13 5.
+   |acc| <= 16 * 255 and the keys stay below 2^27; equal keys are the same entry, so the sort needs no stability rule.  What
+   follows: the output is always a palette colour with a zero high byte; a pixel whose colour is in the palette comes back as
+   it is; the result never depends on the frame number or on a linear index.  agmv_hip_dither_frames_async of
+   include/agmv_hip.h is the kernel.
+   AGMV_SetDither sets the strength for the sequence encoders (all three BMP drivers and every AGMV_EncodeFrames*Dev, from every
+   pixel layout and with a scale): 0 = not set, then env AGMV_DITHER decides (1 .. 64, anything else is off), and without it the
+   dither is off and every file is what it was without this knob; values above 64 count as 64.  The knob is read when a sequence
+   is opened.  What is dithered is exactly what the encoder would have seen, frame by frame, PDIFS midpoints included; the
+   palette's histogram, the palette refinement and the adaptive schedule's similarity counts read the undithered source.
+   AGMV_EncodeFrame (one frame, FILE*) is not affected.  With AGMV_TRACE in the environment the strength is printed. */
+void AGMV_SetDither(unsigned strength);
+
 /* Sequences from and to frames in GPU memory: the .agmv files of the three BMP drivers without the BMPs.
    d_frames is device memory of the library's own device (env AGMV_DEVICE, default 0; AGMV_DEVICES is not consulted),
    [num_of_frames][height][width] pixels of 4 bytes, 0x00RRGGBB (bits >= 24 are ignored).

@@ -57,6 +57,18 @@ int agmv_hip_set_palette(agmv_hip_ctx* ctx, const uint32_t p0[256], const uint32
 int agmv_hip_quantise_dev(agmv_hip_ctx* ctx, const uint32_t* d_pix, size_t n, uint16_t* d_entries,
                           void* stream);
 
+/* -- pattern dithering ----------------------------------------------------------------------
+ * The dither of include/agmv.h ("pattern dithering"), which holds the definition, against the context's palette and its exact
+ * table: every pixel of n_frames packed frames of w x h at d_pix is replaced, in place, by one of 16 palette colours whose mean
+ * approaches it, picked by the 4x4 threshold matrix at (x & 3, y & 3) of the pixel's position inside its own frame.  strength
+ * 1 .. 64.  Any w, h >= 1 (not only multiples of 4); d_pix 4-byte aligned; bits >= 24 are ignored on input and 0 on output;
+ * nothing outside the n_frames frames is written.  Asynchronous on `stream`: one launch, no allocation, no host synchronisation.
+ * Returns non-zero with a message, touches nothing and launches nothing for a NULL pointer, a context without a palette,
+ * strength 0 or above 64, a zero size, or w * h >= 2^31 (the index inside a frame is 32 bits wide; the frames' bases are 64-bit
+ * offsets, so n_frames has no bound of its own).  n_frames == 0 is success and launches nothing. */
+int agmv_hip_dither_frames_async(agmv_hip_ctx* ctx, uint32_t strength, uint32_t* d_pix,
+                                 uint32_t w, uint32_t h, uint32_t n_frames, void* stream);
+
 /* -- encode -------------------------------------------------------------------------------
  * Loops A+B of AGMV_EncodeFrame for n_frames consecutive frames (reference
  * src/agmv_encode.c:552-565 / :589-599, :626-630): quantise, I/P block classification
@@ -122,6 +134,9 @@ int agmv_hip_within2_count(agmv_hip_ctx* ctx, const uint32_t a[16], const uint32
  *    without waiting for the stream (agmv_hip_lz_decode_frames_sized_dev: for nothing at all) only when the upload of the
  *    PREVIOUS call of that context has ended; otherwise it waits on the host for that upload (not for the kernels behind it)
  *    before it rewrites the buffer.  The results are the same either way;
+ *  - agmv_hip_dither_frames_async reads the context's tables and nothing else of it: with respect to agmv_hip_set_palette
+ *    it is ordered like an encode (the tables are complete for work submitted to the palette's stream afterwards), and it
+ *    may run beside the context's encodes and decodes on other streams;
  *  - a device-side wait that runs into its bound (never observed on a healthy GPU) makes agmv_hip_check fail AND
  *    overwrites every size of that batch with 0xFFFFFFFF, so the bytes cannot be taken for valid ones. */
 

@@ -29,7 +29,7 @@
 static agmv_hip_ctx* g_ctx = NULL;
 static uint32_t g_pal[512];
 static int g_pal_mode = -1;
-static unsigned g_batch_frames = 0, g_lz_threads = 0, g_devices = 0, g_palette_refine = 0;
+static unsigned g_batch_frames = 0, g_lz_threads = 0, g_devices = 0, g_palette_refine = 0, g_dither = 0;
 static unsigned long g_export_count = 0;            /* AGIDL's expcount, extern/agidl/src/agidl_img_export.c:18 */
 
 void agmv_die(const char* what)
@@ -55,6 +55,7 @@ void AGMV_SetBatchFrames(unsigned n) { g_batch_frames = n; }
 void AGMV_SetLZThreads(unsigned n) { g_lz_threads = n; }
 void AGMV_SetDevices(unsigned n) { g_devices = n; }
 void AGMV_SetPaletteRefine(unsigned n) { g_palette_refine = n; }
+void AGMV_SetDither(unsigned n) { g_dither = n; }
 
 /* frames per GPU batch: what the caller asked for, else about 128 MB of source pixels (64 frames at most), whole GOPs */
 static unsigned batch_frames(size_t npx)
@@ -85,6 +86,15 @@ static unsigned palette_refine(void)
 	const char* e = getenv("AGMV_PALETTE_REFINE");
 	if (!n && e && atoi(e) > 0) n = (unsigned)atoi(e);
 	return n > 64 ? 64 : n;
+}
+
+/* strength of the pattern dithering a sequence opened now runs before its encodes (AGMV_SetDither / env AGMV_DITHER, 1 .. 64;
+   default 0 = off); agmv_seq_open reads it */
+unsigned agmv_dither_strength(void)
+{
+	const char* e = getenv("AGMV_DITHER");
+	if (g_dither) return g_dither > 64 ? 64 : g_dither;
+	return e && atoi(e) >= 1 && atoi(e) <= 64 ? (unsigned)atoi(e) : 0;
 }
 
 /* host threads of the pipelines (BMP parse, LZ, BMP export): what the caller asked for, else the cores this process may

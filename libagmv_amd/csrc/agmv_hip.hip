@@ -6,6 +6,8 @@
 //                   AGMV_FindNearestColor / AGMV_FindNearestEntry (src/agmv_utils.c:785-895)
 //   k_mtx_build     512x512 bit matrix "palette colours within +-2 on every channel",
 //                   the predicate of CompareI/PFrameBlock (src/agmv_encode.c:293,345)
+//   k_dither        opt-in, no counterpart in the reference: pattern dithering of a clip in place before k_encode sees it
+//                   (include/agmv.h, "pattern dithering"); the other reader of the table and the palette
 //   k_encode        loops A+B of AGMV_EncodeFrame fused (src/agmv_encode.c:552-565, 240-527):
 //                   one lane = one 4x4 block carried through the 4 frames of its GOP, one
 //                   workgroup = 512 consecutive blocks; per-frame byte offsets by a decoupled
@@ -222,6 +224,64 @@ __global__ __launch_bounds__(256) void k_quantise(const uint32_t* __restrict__ p
 	size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
 	size_t stride = (size_t)gridDim.x * 256;
 	for (; i < n; i += stride) out[i] = lut[lut_index(pix[i])];
+}
+
+// K0c: pattern dithering in place (include/agmv.h, "pattern dithering", holds the definition).  One lane = one pixel, neighbouring
+// lanes neighbouring pixels of a row: their colours are close, so their look-ups -- the early ones above all -- fall into the same
+// 128-byte lines (4x4x4 cubes) of the table.  A pixel costs 16 DEPENDENT look-ups (candidate i is found at the pixel plus the error
+// the candidates before it left), so the kernel is bound by their latency and wants every wave the CU can hold: 256 lanes, 4 KB of
+// LDS, no array indexed at run time (the candidate loop and the sort are unrolled over 16 registers).  The palette and the sort keys
+// of its 512 entries sit side by side in LDS: one 8-byte per-lane read per candidate.
+constexpr int DITHER_T = 256;
+constexpr int DITHER_WG_PER_CU = 8;                           // 32 waves per CU, the hardware's limit, when the registers allow it
+constexpr unsigned long long DITHER_B4 = 0x5D7F91B36E4CA280ull;   // nibble (y & 3) * 4 + (x & 3) of the threshold matrix
+
+__global__ __launch_bounds__(DITHER_T) void k_dither(uint32_t* __restrict__ pix, uint32_t w, uint32_t npx, uint32_t n_frames, int strength,
+                                                     const uint16_t* __restrict__ lut, const uint32_t* __restrict__ pal)
+{
+	__shared__ uint2 s_tab[512];                               // .x colour of the entry, .y its key: luma * 512 + entry
+	for (uint32_t e = threadIdx.x; e < 512u; e += DITHER_T) {
+		const uint32_t c = pal[e] & 0xFFFFFFu;
+		s_tab[e] = make_uint2(c, (299u * (c >> 16) + 587u * ((c >> 8) & 255u) + 114u * (c & 255u)) * 512u + e);
+	}
+	__syncthreads();
+	const uint32_t stride = gridDim.x * DITHER_T;
+	for (uint32_t f = blockIdx.y; f < n_frames; f += gridDim.y) {
+		uint32_t* __restrict__ fp = pix + (size_t)f * npx;
+		for (uint32_t p = blockIdx.x * DITHER_T + threadIdx.x; p < npx; p += stride) {   // p < 2^31, stride <= 2^24: no wrap
+			const uint32_t px = fp[p];
+			const int r = (int)((px >> 16) & 255u), g = (int)((px >> 8) & 255u), b = (int)(px & 255u);
+			int ar = 0, ag = 0, ab = 0;                        // the error so far, |.| <= 16 * 255
+			uint32_t k[16];
+#pragma unroll
+			for (int i = 0; i < 16; i++) {
+				const int cr = min(max(r + (__mul24(ar, strength) >> 6), 0), 255);
+				const int cg = min(max(g + (__mul24(ag, strength) >> 6), 0), 255);
+				const int cb = min(max(b + (__mul24(ab, strength) >> 6), 0), 255);
+				const uint32_t e = lut[lut_index((uint32_t)(cr << 16 | cg << 8 | cb))] & 511u;
+				const uint2 t = s_tab[e];
+				ar += r - (int)(t.x >> 16); ag += g - (int)((t.x >> 8) & 255u); ab += b - (int)(t.x & 255u);
+				k[i] = t.y;
+			}
+			// the 16 keys in ascending order: Batcher's odd-even merge sort, 63 compare-exchanges on registers
+#define CE(a, b) { const uint32_t lo_ = min(k[a], k[b]), hi_ = max(k[a], k[b]); k[a] = lo_; k[b] = hi_; }
+			CE(0, 1) CE(2, 3) CE(4, 5) CE(6, 7) CE(8, 9) CE(10, 11) CE(12, 13) CE(14, 15)
+			CE(0, 2) CE(1, 3) CE(4, 6) CE(5, 7) CE(8, 10) CE(9, 11) CE(12, 14) CE(13, 15)
+			CE(1, 2) CE(5, 6) CE(9, 10) CE(13, 14) CE(0, 4) CE(1, 5) CE(2, 6) CE(3, 7)
+			CE(8, 12) CE(9, 13) CE(10, 14) CE(11, 15) CE(2, 4) CE(3, 5) CE(10, 12) CE(11, 13)
+			CE(1, 2) CE(3, 4) CE(5, 6) CE(9, 10) CE(11, 12) CE(13, 14) CE(0, 8) CE(1, 9)
+			CE(2, 10) CE(3, 11) CE(4, 12) CE(5, 13) CE(6, 14) CE(7, 15) CE(4, 8) CE(5, 9)
+			CE(6, 10) CE(7, 11) CE(2, 4) CE(3, 5) CE(6, 8) CE(7, 9) CE(10, 12) CE(11, 13)
+			CE(1, 2) CE(3, 4) CE(5, 6) CE(7, 8) CE(9, 10) CE(11, 12) CE(13, 14)
+#undef CE
+			const uint32_t y = p / w, x = p - y * w;           // the position inside the frame
+			const uint32_t t = (uint32_t)(DITHER_B4 >> (((y & 3u) * 4u + (x & 3u)) * 4u)) & 15u;
+			uint32_t key = k[0];
+#pragma unroll
+			for (int i = 1; i < 16; i++) key = t == (uint32_t)i ? k[i] : key;
+			fp[p] = s_tab[key & 511u].x;
+		}
+	}
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1100,6 +1160,25 @@ extern "C" int agmv_hip_quantise_dev(agmv_hip_ctx* c, const uint32_t* d_pix, siz
 	size_t blocks = (n + 255) / 256;
 	if (blocks > 8192) blocks = 8192;
 	hipLaunchKernelGGL(k_quantise, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_pix, n, c->d_lut, d_entries);
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_dither_frames_async(agmv_hip_ctx* c, uint32_t strength, uint32_t* d_pix, uint32_t w, uint32_t h, uint32_t n_frames,
+                                            void* stream)
+{
+	if (need_ctx(c, true)) return -1;
+	if (!d_pix || ((uintptr_t)d_pix & 3u)) { snprintf(g_err, sizeof(g_err), "agmv_hip: dither: d_pix must be a 4-byte aligned device pointer"); return -1; }
+	if (strength < 1 || strength > 64) { snprintf(g_err, sizeof(g_err), "agmv_hip: dither: strength must be 1 .. 64 (got %u)", strength); return -1; }
+	if (w == 0 || h == 0) { snprintf(g_err, sizeof(g_err), "agmv_hip: dither: width/height must be non-zero (got %ux%u)", w, h); return -1; }
+	// the index inside a frame is 32 bits wide and steps past the end once; the frame's base is a 64-bit offset
+	if ((uint64_t)w * h >= (1ull << 31)) { snprintf(g_err, sizeof(g_err), "agmv_hip: dither: a frame must have fewer than 2^31 pixels (got %ux%u)", w, h); return -1; }
+	if (n_frames == 0) return 0;
+	const uint32_t npx = w * h, cap = (uint32_t)(c->n_cu * DITHER_WG_PER_CU);
+	uint32_t gx = (npx + DITHER_T - 1) / DITHER_T, gy = 1;
+	if (gx > cap) gx = cap;
+	else { gy = cap / gx; if (gy > n_frames) gy = n_frames; if (gy > 65535u) gy = 65535u; }
+	hipLaunchKernelGGL(k_dither, dim3(gx, gy), dim3(DITHER_T), 0, (hipStream_t)stream, d_pix, w, npx, n_frames, (int)strength, c->d_lut, c->d_pal);
 	CK(hipGetLastError());
 	return 0;
 }

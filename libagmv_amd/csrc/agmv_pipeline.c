@@ -5,8 +5,8 @@
  * thread; here the stages of DIFFERENT batches overlap (SURVEY.md section 7 "pipeline shape"):
  *
  *   encode   host cores: BMP parse (+ GBA/NDS nearest scale) of batch b+1 into pinned staging
- *            GPU worker threads (two per device, devices = AGMV_DEVICES): H2D -> PDIFS midpoint -> k_encode -> D2H of
- *              batch b, each worker on its own stream and context; batches are whole GOPs, so they are independent given
+ *            GPU worker threads (two per device, devices = AGMV_DEVICES): H2D -> PDIFS midpoint -> (opt-in, AGMV_SetDither /
+ *              AGMV_DITHER: k_dither, in place) -> k_encode -> D2H of batch b, each worker on its own stream and context; batches are whole GOPs, so they are independent given
  *              the palette and go round-robin over the workers / devices (multi-GPU sharding by GOP range, no exchange)
  *            host cores: exact LZSS / LZ77 of batch b-1, one task per frame -- or, opt-in (AGMV_LZ_DEVICE for LZSS,
  *              AGMV_LZ77_DEVICE for LZ77 on one device), the same stage on the GPU worker's stream behind k_encode: the
@@ -229,6 +229,7 @@ struct agmv_seq {
 	int scale_w, scale_h, audio_chunks, mode512, lz77, use_b;
 	int lz_dev;                            /* the LZ stage runs on the GPU workers (lz77 chooses the form): AGMV_LZ_DEVICE for LZSS,
 	                                          AGMV_LZ77_DEVICE for LZ77 on one device */
+	unsigned dither;                       /* strength of the pattern dithering of every batch before its encode, 0 = off (AGMV_SetDither / AGMV_DITHER) */
 	uint8_t* d_persist;                    /* lz_dev, LZ77: `persist` on the device (persist_len bytes, zero-initialised) */
 	unsigned peek_turn;                    /* lz_dev, LZ77: the batch whose peek call comes next (under mu) */
 	uint32_t w, h;
@@ -413,6 +414,8 @@ static void* eworker_main(void* p)
 				agmv_die("entry plane upload");
 			free(e);
 		}
+		/* the frames are what k_encode would have seen, midpoints included: dithered in place, on the same stream */
+		if (s->dither && agmv_hip_dither_frames_async(wk->ctx, s->dither, wk->d_frames, s->w, s->h, b->n, wk->stream)) agmv_die("batch dither");
 		if (agmv_hip_encode_frames_dev(wk->ctx, wk->d_frames, b->n, s->w, s->h, b->first_fc, wk->d_out, s->stride, wk->d_sizes, wk->d_ient,
 		                               wk->stream) ||
 		    agmv_hip_memcpy_async(wk->ctx, b->sizes, wk->d_sizes, 4 * (size_t)b->n, 1, wk->stream) || agmv_hip_check(wk->ctx, wk->stream))
@@ -566,6 +569,8 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const agmv_source* src, int scale_w
 	   persistent buffer behind the streams then lives on ONE device, so with more than one device its stage stays on the host pool. */
 	s->lz_dev = lz77 ? devices == 1 && env_nonzero("AGMV_LZ77_DEVICE") : env_nonzero("AGMV_LZ_DEVICE");
 	s->lz_stride = (agmv_hip_lzss_max_csize(s->stride) + 255) & ~(size_t)255;
+	s->dither = agmv_dither_strength();
+	if (s->dither) TRACE("seq_open: pattern dithering of every batch before its encode, strength %u\n", s->dither);
 	s->cap = (cap + 3u) & ~3u;
 	s->nworkers = devices * 2;
 	s->nslots = s->nworkers + 2;

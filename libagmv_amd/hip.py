@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "agmv_hip_yuv_histogram_dev", "agmv_hip_yuv_similarity_dev",
     "agmv_hip_scale_area_dev",
     "agmv_hip_palette_refine_dev",
+    "agmv_hip_dither_frames_async",
 ]
 
 
@@ -168,6 +169,9 @@ def load_library(path=None):
     if path is None or hasattr(L, "agmv_hip_palette_refine_dev"):
         L.agmv_hip_palette_refine_dev.argtypes = [vp, vp, C.c_int, vp, u32, u32, u32, vp, vp, vp]
         L.agmv_hip_palette_refine_dev.restype = C.c_int
+    if path is None or hasattr(L, "agmv_hip_dither_frames_async"):
+        L.agmv_hip_dither_frames_async.argtypes = [vp, u32, vp, u32, u32, u32, vp]
+        L.agmv_hip_dither_frames_async.restype = C.c_int
     L.agmv_hip_check.argtypes = [vp, vp]
     L.agmv_hip_enable_timing.argtypes = [vp, C.c_int]
     L.agmv_hip_enable_timing.restype = C.c_int
@@ -851,6 +855,18 @@ class AgmvHip:
         self._ck(self.L.agmv_hip_palette_refine_dev(self.ctx, hist.data_ptr(), int(quality), pal.data_ptr(), pal.numel(), int(n_free), int(iterations),
                                                     rounds.data_ptr(), sse.data_ptr(), self._stream()))
         return rounds, sse
+
+    # ------------------------------------------------------------------ pattern dithering against the context's palette (include/agmv.h)
+    def dither_frames(self, pix, w, h, strength, stream=None):
+        """pix: int32 CUDA tensor of whole frames of w x h pixels 0x00RRGGBB, dithered in place (agmv_hip_dither_frames_async) on
+        `stream` (a torch stream; None = torch's current stream).  strength 1 .. 64.  Returns pix; nothing waits."""
+        _check_vec("dither_frames: pix", pix, 0)
+        w, h = int(w), int(h)
+        if w < 1 or h < 1 or pix.numel() % (w * h):
+            raise ValueError("dither_frames: pix must hold whole frames of %d x %d pixels, got %d words" % (w, h, pix.numel()))
+        s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self._ck(self.L.agmv_hip_dither_frames_async(self.ctx, int(strength), pix.data_ptr(), w, h, pix.numel() // (w * h), s))
+        return pix
 
     # ------------------------------------------------------------------ host-buffer path
     def encode_host(self, frames, first_frame_count=0, ientries=None):

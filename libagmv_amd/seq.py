@@ -52,6 +52,8 @@ def load_library():
         L.AGMV_EncodeFramesScaledDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int] + [C.c_ulong] * 5 + [C.c_int, C.c_ulong] + [C.c_int] * 4
         L.AGMV_SetPaletteRefine.restype = None
         L.AGMV_SetPaletteRefine.argtypes = [C.c_uint]
+        L.AGMV_SetDither.restype = None
+        L.AGMV_SetDither.argtypes = [C.c_uint]
         _lib = L
     return _lib
 
@@ -121,15 +123,19 @@ def _scale_target(size, scale):
 
 
 def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedule=SCHEDULE_PDIFS, fmt=None, yuv=None, full_range=False,
-                  size=None, scale="area", palette_refine=None):
+                  size=None, scale="area", palette_refine=None, dither=None):
     """frames: contiguous CUDA tensor of n frames on the library's device, in the layout `fmt` (see the module text; None = inferred
     from the tensor, which never gives "nv12" or "i420") -> the file at `path`.  yuv ("bt601", the default, or "bt709") and
     full_range go with the two YUV layouts only.  size=(h, w), in tensor order, scales the clip to that size first
     (AGMV_EncodeFramesScaledDev): scale "area" is the exact box filter (a downscale), "nearest" the pixel under the target
     pixel's centre; the target must be multiples of 4, the source need not be.  palette_refine=n, an int from 1 to 64, moves the
     palette's colours by at most n rounds of weighted k-means over the clip's histogram (AGMV_SetPaletteRefine of include/agmv.h,
-    set for this call only); None leaves the library's knob as it is."""
+    set for this call only); None leaves the library's knob as it is.  dither=s, an int from 1 to 64, pattern-dithers the frames
+    against the palette with that strength before they are quantised (AGMV_SetDither of include/agmv.h, which holds the
+    definition; set for this call only); None leaves the library's knob as it is."""
     import torch
+    if dither is not None and not (isinstance(dither, int) and not isinstance(dither, bool) and 1 <= dither <= 64):
+        raise ValueError("encode_frames: dither must be None or an int from 1 to 64, got %r" % (dither,))
     if palette_refine is not None and not (isinstance(palette_refine, int) and not isinstance(palette_refine, bool) and 1 <= palette_refine <= 64):
         raise ValueError("encode_frames: palette_refine must be None or an int from 1 to 64, got %r" % (palette_refine,))
     target = _scale_target(size, scale)
@@ -140,6 +146,8 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
     L = load_library()
     if palette_refine is not None:
         L.AGMV_SetPaletteRefine(palette_refine)
+    if dither is not None:
+        L.AGMV_SetDither(dither)
     try:
         if target is None:
             rc = L.AGMV_EncodeFramesFmtDev(os.fsencode(path), frames.data_ptr(), v, n, w, h, fps, opt, quality, compression, schedule)
@@ -154,6 +162,8 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
     finally:
         if palette_refine is not None:
             L.AGMV_SetPaletteRefine(0)
+        if dither is not None:
+            L.AGMV_SetDither(0)
 
 
 def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False):
