@@ -129,7 +129,7 @@ static int dec_grow(T*& d_buf, size_t& cap, size_t bytes)
 	if (m512) hipLaunchKernelGGL((k<true, ##__VA_ARGS__>), grid, block, 0, s, A); \
 	else      hipLaunchKernelGGL((k<false, ##__VA_ARGS__>), grid, block, 0, s, A); \
 	DCK(hipGetLastError()); } while (0)
-// ... for k_decode / k_fixup: k<mode512, bitmap form>
+// ... for k_fixup (and, spelled out in decode_launch, k_decode): k<mode512, bitmap form>
 #define DEC_LAUNCH_BM(k, m512, bm, grid, block, s, A) do { \
 	if (bm) DEC_LAUNCH(k, m512, grid, block, s, A, true); else DEC_LAUNCH(k, m512, grid, block, s, A, false); } while (0)
 
@@ -1030,7 +1030,8 @@ struct DecArgs {
 	const uint32_t* prev_iframe;
 	uint32_t* dirty;
 	uint32_t n_frames, w, h, bw, nblk, tpf, first_fc, phase, n_groups;
-	uint32_t grp0;          // first GOP of this launch (the grid covers GOPs grp0 .. grp0 + gridDim.x / tpf - 1)
+	uint32_t grp0;          // first GOP of this launch (its items cover GOPs grp0 .. grp0 + n_items / tpf - 1)
+	uint32_t n_items;       // k_decode: (GOP, tile) pairs of this launch
 	// bitmap form (BM kernels): the parser's entry bitmaps, first block number per region, tile entries -- no offsets[]
 	const unsigned long long* vm;
 	const uint32_t* kb;
@@ -1221,8 +1222,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void* p, ui
 #ifndef DEC_WPE
 #define DEC_WPE 5         // waves per SIMD: 87 VGPRs, no spills; 6 spills and is slower
 #endif
-template <bool M512, bool BM>
-__global__ __launch_bounds__(DEC_T, DEC_WPE) void k_decode(DecArgs A)
+template <bool M512, bool BM, bool LOOP>   // (the looping form, a test and tuning aid, would spill at DEC_WPE waves: it gets the registers of one wave fewer)
+__global__ __launch_bounds__(DEC_T, LOOP ? DEC_WPE - 1 : DEC_WPE) void k_decode(DecArgs A)
 {
 	__shared__ uint32_t s_pal[512];
 	__shared__ uint32_t s_nb[DEC_T];        // neighbour exchange for the last-block quirk
@@ -1233,7 +1234,16 @@ __global__ __launch_bounds__(DEC_T, DEC_WPE) void k_decode(DecArgs A)
 	const uint32_t npx = A.w * A.h;
 	for (int i = tid; i < 512; i += DEC_T) s_pal[i] = A.pal[i];
 
-	const uint32_t lgroup = blockIdx.x / A.tpf, tile = blockIdx.x - lgroup * A.tpf, group = lgroup + A.grp0;
+	// items = (GOP, tile) pairs of the launch.  The grid has one workgroup per item (LOOP false: straight-line code) unless
+	// AGMV_DEC_GRID caps it: workgroup g then takes items g, g + gridDim.x, ... one after the other (a static assignment:
+	// nothing to wait for).  Everything below is per item; only the palette copy is the workgroup's.
+	// Items run from the launch's LAST GOP to its first.  The parser in front of this kernel reads the batch's bitstreams
+	// first frame to last and writes their entry bitmaps in that order, and a batch is larger than the memory-side cache
+	// (c3: 446 MB of stream): what the cache still holds when this kernel starts is the END of the batch.  GOPs are
+	// independent here (k_fixup repairs what is not), so the order is free; first GOP first, every window load of c3
+	// missed the cache and k_decode + k_fixup took 1.85 ms instead of 1.69 (profiles/decode_pipeline/).
+	for (uint32_t item = blockIdx.x;;) {
+	const uint32_t lgroup = (A.n_items - 1 - item) / A.tpf, tile = item % A.tpf, group = lgroup + A.grp0;
 	const int f_lo = group == 0 ? 0 : (int)(group * 4 - A.phase);
 	int f_hi = (int)(group * 4 - A.phase) + 4;
 	if (f_hi > (int)A.n_frames) f_hi = (int)A.n_frames;
@@ -1497,6 +1507,11 @@ __global__ __launch_bounds__(DEC_T, DEC_WPE) void k_decode(DecArgs A)
 			A.dirty[(A.nblk + 31) >> 5] = 1u;                   // "anything to repair" word behind the bitmap
 		}
 		if (group == 0 && depstale) A.dirty[((A.nblk + 31) >> 5) + 1] = 1u;   // the batch depends on the decoder state before it
+	}
+	if (!LOOP) break;
+	item += gridDim.x;
+	if (item >= A.n_items) break;
+	__syncthreads();                                           // the next item's ranges, scratch and windows go where this one's are still being read
 	}
 }
 
@@ -1764,8 +1779,19 @@ static int decode_prepare(agmv_hip_ctx* c, DecArgs& A, const uint8_t* d_bits, si
 static int decode_launch(agmv_hip_ctx* c, DecArgs A, uint32_t g0, uint32_t g1, hipStream_t s)   // GOPs [g0, g1) of the batch
 {
 	A.grp0 = g0;
-	const dim3 grid((g1 - g0) * A.tpf);
-	DEC_LAUNCH_BM(k_decode, dec_mode512(c), A.vm, grid, dim3(DEC_T), s, A);
+	A.n_items = (g1 - g0) * A.tpf;
+	uint32_t nwg = A.n_items;
+	if (const char* e = getenv("AGMV_DEC_GRID")) {             // tuning / test aid: at most n workgroups, each looping over its items
+		const long n = atol(e);
+		if (n > 0 && (unsigned long)n < nwg) nwg = (uint32_t)n;
+	}
+	const dim3 grid(nwg);
+	const int m512 = dec_mode512(c);
+	if (nwg < A.n_items) {                                     // k_decode<mode512, bitmap form, looping>
+		if (A.vm) DEC_LAUNCH(k_decode, m512, grid, dim3(DEC_T), s, A, true, true); else DEC_LAUNCH(k_decode, m512, grid, dim3(DEC_T), s, A, false, true);
+	} else {
+		if (A.vm) DEC_LAUNCH(k_decode, m512, grid, dim3(DEC_T), s, A, true, false); else DEC_LAUNCH(k_decode, m512, grid, dim3(DEC_T), s, A, false, false);
+	}
 	return 0;
 }
 
