@@ -13,7 +13,8 @@
  * reference src/agmv_encode.c:529).
  *
  * Out of scope in this build (declared by the reference, not provided here): the ten
- * non-BMP image formats, audio import/export (WAV/AIFF), the Win32 player helpers.
+ * non-BMP image formats, the AIFF / AIFC audio importers (AGMV_AIFFToAudioTrack, AGMV_AIFCToAudioTrack,
+ * AGMV_80BitFloat), the Win32 player helpers.
  */
 #ifndef AGMV_H
 #define AGMV_H
@@ -203,6 +204,10 @@ u16  AGMV_SwapShort(u16 word);
 u32  AGMV_SwapLong(u32 dword);
 void AGMV_CopyImageData(u32* dest, u32* src, u32 size);
 void AGMV_SyncFrameAndImage(AGMV* agmv, u32* img_data);
+void AGMV_SyncAudioTrack(AGMV* agmv, const void* pcm);
+void AGMV_SignedToUnsignedPCM(u8* pcm, u32 size);
+void AGMV_UnsigendToSignedPCM(u8* pcm, u32 size);
+u32  AGMV_CalculateTotalAudioDuration(u32 size, u32 sample_rate, u16 num_of_channels, u16 bits_per_sample);
 int  AGMV_Abs(int a);
 int  AGMV_Min(int a, int b);
 u8   AGMV_GetR(u32 color);
@@ -236,6 +241,7 @@ void AGMV_EncodeHeader(FILE* file, AGMV* agmv);
 void AGMV_EncodeFrame(FILE* file, AGMV* agmv, u32* img_data);
 u32  AGMV_LZSS(FILE* file, AGMV_BITSTREAM* in);
 u32  AGMV_LZ77(FILE* file, AGMV_BITSTREAM* in);
+void AGMV_CompressAudio(AGMV* agmv);
 void AGMV_EncodeAudioChunk(FILE* file, AGMV* agmv);
 int  AGMV_DecodeHeader(FILE* file, AGMV* agmv);
 int  AGMV_DecodeFrameChunk(FILE* file, AGMV* agmv);
@@ -255,6 +261,37 @@ void AGMV_EncodeFullAGMV(AGMV* agmv, const char* filename, const char* dir, cons
                          AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression);
 int AGMV_DecodeVideo(const char* filename, u8 img_type);
 int AGMV_DecodeAGMV(const char* filename, u8 img_type, AGMV_AUDIO_TYPE audio_type);
+
+/* ---- audio tracks (reference include/agmv_encode.h:33, agmv_decode.h:25, agmv_utils.h:101-103, :118, :124-132).  Host C.
+ * The format.  "Has audio" means header.total_audio_duration != 0, and the duration is in whole seconds: a track shorter than
+ * one second is no track.  audio_size counts samples over all channels, in track order (interleaved).  A 16-bit track is u16
+ * words holding the WAV samples' bit patterns (signed samples included); the file stores ONE code byte per sample.  With
+ * k = floor(sqrt(s)) for a sample s in 0 .. 65535, in integers:
+ *     e1 = k even ? k : (k + 1) & 255            r  = (s > k * k + k ? k + 1 : k) & 255
+ *     e2 = r even ? r : (r + 1) & 255            e3 = (s >> 8) | 1
+ *     d1 = |e1 * e1 - s|    d2 = |e2 * e2 - s|    d3 = |(e3 << 8) - s|    d = min(d1, d3)
+ *     code = d == d1 ? e1 : d == d2 ? e2 : e3
+ * (AGMV_CompressAudio, reference src/agmv_encode.c:636-705, with its quirks: the second minimum overwrites the first, rounding up
+ * to even wraps from 255 to 0, a root of 256 is 0.)  A code c expands to c * c when even and to (c << 8) & 0xFFFF when odd
+ * (src/agmv_decode.c:412-453); the worst round-trip error is 256.  An 8-bit track stores its bytes unchanged.
+ * Every frame chunk is followed by 'AGAC', a 4-byte size and `size` codes from a running start_point.  The sequence encoders
+ * write the same size into every chunk, (u32)(audio_size / (f32)d), with the reference's divisors: AGMV_EncodeAGMV (PDIFS) takes
+ * d = its adjusted frame count, (end_frame - start_frame) / 2 for the heavy opts and * 0.75 for the light ones, and leaves the
+ * tail audio_size - size * chunks unwritten; AGMV_EncodeFullAGMV takes d = end_frame - start_frame (src/agmv_encode.c:4024), one
+ * less than the chunks it writes, so its chunks ask for more codes than audio_size holds and end in zeros here.  A decoder
+ * reads each chunk's own size field.
+ * Where the reference reads or leaves memory it never set, this build reads zeros and stays in bounds: AGMV_WavToAudioTrack takes
+ * the RIFF size for the data size like the reference, so audio_size exceeds what the file holds by 18 samples (36 for 8 bits)
+ * and those are 0; the decoders' track is 0 behind the last chunk; AGMV_EncodeAudioChunk writes 0 for samples past audio_size,
+ * AGMV_DecodeAudioChunk drops them (start_point advances all the same).  A file that cannot be opened leaves the object as it
+ * was.  AGMV_ExportAudioType writes the reference's bytes, its constant byte rate 75600 and its swapped form names (AGMV_AUDIO_AIFF
+ * writes an 'AIFC' form, AGMV_AUDIO_AIFC an 'AIFF' form) included.  AGMV_DecodeAudio writes quick_export.wav / quick_export.aiff
+ * into the working directory; AGMV_DecodeAGMV of this build writes no audio file, AGMV_DecodeAudio is the export. */
+void AGMV_WavToAudioTrack(const char* filename, AGMV* agmv);
+void AGMV_RawSignedPCMToAudioTrack(const char* filename, AGMV* agmv, u8 num_of_channels, u32 sample_rate);
+void AGMV_Raw8PCMToAudioTrack(const char* filename, AGMV* agmv);
+void AGMV_ExportAudioType(FILE* audio, AGMV* agmv, AGMV_AUDIO_TYPE audio_type);
+int  AGMV_DecodeAudio(const char* filename, AGMV_AUDIO_TYPE audio_type);
 
 /* ---- playback helpers (reference include/agmv_playback.h:23-31) */
 void AGMV_ResetVideo(FILE* file, AGMV* agmv);
@@ -447,6 +484,32 @@ typedef enum AGMV_SCALE { AGMV_SCALE_NEAREST = 1, AGMV_SCALE_AREA = 2 } AGMV_SCA
 int AGMV_EncodeFramesScaledDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height,
                                u32 width, u32 height, AGMV_SCALE filter, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
                                AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule);
+
+/* Audio tracks from and to GPU memory.  An AGMV_PCMFMT names the layout of PCM in device memory:
+     AGMV_PCM_S16   [samples][channels] 16-bit words, bits unchanged (int16 WAV samples as they are); for 16-bit tracks
+     AGMV_PCM_U8    [samples][channels] unsigned bytes; for 8-bit tracks; a copy
+     AGMV_PCM_F32P  [channels][samples] float, 1 .. 8 channels (torchaudio's planar layout); for 16-bit tracks.  Into the track:
+                    q = (int)rintf(fminf(fmaxf(x, -1), 1) * 32767.0f), rounding half to even, NaN gives 0, and the track's u16 is
+                    the bit pattern of (int16)q.  Out of the track: (float)(int16)u / 32768.0f.
+   AGMV_SetAudioDev attaches a track in the memory of the library's device to the NEXT AGMV_EncodeFrames*Dev call, which consumes
+   it whatever that call returns; NULL clears it.  The memory must stay valid and complete until that call returns.  Returns 0,
+   or a negative value and attaches nothing: -1 unknown format, -2 zero channels, more than 255, or more than 8 planar ones, -3 a sample rate
+   of 0, -4 a length of less than one second (samples_per_channel / sample_rate == 0: no track), -5 more than 2^32 - 1 samples
+   over all channels.  The encode call sets the header as the WAV importer would for that PCM (16 or 8 bits per sample,
+   audio_size = samples_per_channel * channels, duration = samples_per_channel / sample_rate), compands the whole track in one
+   kernel (agmv_hip_audio_compand_async of include/agmv_hip.h) on the library's device, downloads the codes and lets the drivers
+   interleave the chunks: byte for byte the file of the BMP driver on an object that holds the same track.
+   AGMV_SCHEDULE_ADAPTIVE with a pending track returns -5 before any file is created (AGMV_EncodeVideo has no audio).
+   AGMV_DecodeAudioDev mirrors AGMV_DecodeFramesFmtDev: *info (may be NULL) receives the header's AGMV_INFO; with d_pcm NULL
+   nothing else happens.  Otherwise the chunks' payloads are gathered as AGMV_DecodeAudio walks them, uploaded once and expanded
+   by one kernel into the layout `fmt`.  Returns the samples decoded over all channels: the sum of the chunks' sizes, at most
+   audio_size and at most cap_samples, rounded down to whole sample frames; 0 for a file without a track.  F32P planes hold
+   (return value / channels) samples each and lie back to back from d_pcm.  A negative return is an Error, negated; -1 also for
+   an unknown format, a format that does not fit the track's bits per sample, zero channels and more than 8 planar ones.  No
+   video is decoded. */
+typedef enum AGMV_PCMFMT { AGMV_PCM_S16 = 1, AGMV_PCM_U8 = 2, AGMV_PCM_F32P = 3 } AGMV_PCMFMT;
+int AGMV_SetAudioDev(const void* d_pcm, AGMV_PCMFMT fmt, u32 samples_per_channel, u32 sample_rate, u16 channels);
+int AGMV_DecodeAudioDev(const char* filename, void* d_pcm, AGMV_PCMFMT fmt, u32 cap_samples, AGMV_INFO* info);
 
 #ifdef __cplusplus
 }

@@ -435,6 +435,26 @@ int agmv_hip_scale_area_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, uint3
 int agmv_hip_palette_refine_dev(agmv_hip_ctx* ctx, const uint32_t* d_hist, int quality, uint32_t* d_pal, uint32_t k, uint32_t n_free,
                                 uint32_t iterations, uint32_t* d_rounds, uint64_t* d_sse, void* stream);
 
+/* -- audio tracks -----------------------------------------------------------------------------------
+ * The audio codec of include/agmv.h ("audio tracks"), which holds the definitions: a 16-bit track stores one code byte per
+ * sample (compand), an 8-bit track its bytes.  `pcmfmt` is an AGMV_PCMFMT, by value:
+ *   1 S16   [samples_per_channel][channels] 16-bit words, the track's own bit patterns; 2-byte aligned
+ *   2 U8    [samples_per_channel][channels] bytes; both directions are a copy
+ *   3 F32P  [channels][samples_per_channel] float, 1 .. 8 channels; 4-byte aligned.  In: clamp to [-1, 1], x 32767, round half to
+ *           even, NaN = 0, the int16's bit pattern.  Out: the int16 / 32768.
+ * d_codes holds samples_per_channel * channels bytes in track order (interleaved), 1-byte aligned.
+ * agmv_hip_audio_compand_async: d_pcm -> d_codes.   agmv_hip_audio_expand_async: d_codes -> d_pcm.
+ * Asynchronous on `stream`: one launch (U8: one device-to-device copy), no allocation, no host synchronisation, nothing of the
+ * context is used but its device.  Nothing outside the samples_per_channel * channels elements of the destination is written.
+ * The body runs on 16-byte loads and stores where the two pointers can be brought to 16-byte boundaries together (for F32P
+ * also samples_per_channel % 4 == 0, so that every plane can); otherwise sample by sample, with the same result.
+ * Returns non-zero with a message and launches nothing for a NULL pointer, an unknown format, zero channels, more than 8 planar
+ * channels or a PCM pointer that is not aligned to its sample.  samples_per_channel == 0 is success and launches nothing. */
+int agmv_hip_audio_compand_async(agmv_hip_ctx* ctx, int pcmfmt, const void* d_pcm, uint32_t channels, uint64_t samples_per_channel,
+                                 uint8_t* d_codes, void* stream);
+int agmv_hip_audio_expand_async(agmv_hip_ctx* ctx, int pcmfmt, const uint8_t* d_codes, uint32_t channels, uint64_t samples_per_channel,
+                                void* d_pcm, void* stream);
+
 /* optional timing: when enabled the library records HIP events on the caller's stream around its three kernel
    groups; agmv_hip_last_kernel_ms(which) returns the last launch's duration in ms (0 = k_encode, 1 = the parser
    kernels, 2 = k_decode + k_fixup, 3 = the whole of agmv_hip_parse_decode_frames_dev / agmv_hip_decode_bitstreams_dev), or a negative value if

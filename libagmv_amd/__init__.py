@@ -7,6 +7,7 @@ Layout
   csrc/agmv_clip_hip.hip  the clip front end of that C-ABI: synth, interp, histogram, similarity, gather, the byte and
                       YUV 4:2:0 layouts, the area scale
   csrc/agmv_lz*_hip.hip   the LZSS / LZ77 stages of encoder and decoder on the GPU
+  csrc/agmv_audio_hip.hip  audio tracks: the compand / expand kernels (csrc/agmv_audio.h states the codec once, for host and device)
   csrc/*.c            host C: libagmv-compatible API (include/agmv.h), LZSS/LZ77, container,
                       BMP I/O, palette build, synthetic clip generator
   hip.py              ctypes binding of the C-ABI for tests / bench (torch = device memory only)
@@ -16,8 +17,8 @@ Layout
 There is no CPU fallback anywhere in this package: without the built HIP library, or
 without a GPU, the hot-path calls raise.
 """
-from .hip import PIXFMT, YUVFMT, AgmvHip, HipUnavailable, lib_path, load_library  # noqa: F401
-from .seq import SCALE, SCHEDULE_ADAPTIVE, SCHEDULE_FULL, SCHEDULE_PDIFS, decode_frames, encode_frames  # noqa: F401
+from .hip import PCMFMT, PIXFMT, YUVFMT, AgmvHip, HipUnavailable, lib_path, load_library  # noqa: F401
+from .seq import SCALE, SCHEDULE_ADAPTIVE, SCHEDULE_FULL, SCHEDULE_PDIFS, decode_audio, decode_frames, encode_frames  # noqa: F401
 
-__all__ = ["AgmvHip", "HipUnavailable", "lib_path", "load_library", "encode_frames", "decode_frames",
-           "SCHEDULE_FULL", "SCHEDULE_PDIFS", "SCHEDULE_ADAPTIVE", "PIXFMT", "YUVFMT", "SCALE"]
+__all__ = ["AgmvHip", "HipUnavailable", "lib_path", "load_library", "encode_frames", "decode_frames", "decode_audio",
+           "SCHEDULE_FULL", "SCHEDULE_PDIFS", "SCHEDULE_ADAPTIVE", "PIXFMT", "YUVFMT", "PCMFMT", "SCALE"]

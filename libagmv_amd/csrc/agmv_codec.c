@@ -30,6 +30,8 @@ static agmv_hip_ctx* g_ctx = NULL;
 static uint32_t g_pal[512];
 static int g_pal_mode = -1;
 static unsigned g_batch_frames = 0, g_lz_threads = 0, g_devices = 0, g_palette_refine = 0, g_dither = 0;
+/* the device track AGMV_SetAudioDev attached to the next AGMV_EncodeFrames*Dev call (d_pcm NULL: none) */
+static struct { const void* d_pcm; int fmt; u32 samples, rate; u16 channels; } g_audio;
 static unsigned long g_export_count = 0;            /* AGIDL's expcount, extern/agidl/src/agidl_img_export.c:18 */
 
 void agmv_die(const char* what)
@@ -198,28 +200,6 @@ int AGMV_DecodeHeader(FILE* f, AGMV* a)
 			u32 c = a->header.fmt == 2 ? (b << 16 | g << 8 | r) : (r << 16 | g << 8 | b);
 			if (p) a->header.palette1[i] = c; else a->header.palette0[i] = c;
 		}
-	return NO_ERR;
-}
-
-/* zero-length audio chunks are written after every frame by the AGMV drivers (reference
-   src/agmv_encode.c:707-717); audio itself is out of scope: only pass-through of what the object holds */
-void AGMV_EncodeAudioChunk(FILE* f, AGMV* a)
-{
-	u32 size = a->audio_chunk ? a->audio_chunk->size : 0, i;
-	AGMV_WriteFourCC(f, 'A', 'G', 'A', 'C');
-	AGMV_WriteLong(f, size);
-	for (i = 0; i < size; i++)
-		AGMV_WriteByte(f, a->audio_chunk->atsample ? a->audio_chunk->atsample[a->audio_track->start_point++] : 0);
-}
-
-/* audio payloads are skipped, not decoded (out of scope); the chunk framing is honoured so a file
-   with audio decodes its video (reference src/agmv_decode.c:412-453) */
-int AGMV_DecodeAudioChunk(FILE* f, AGMV* a)
-{
-	AGMV_ReadFourCC(f, a->audio_chunk->fourcc);
-	a->audio_chunk->size = AGMV_ReadLong(f);
-	if (!AGMV_IsCorrectFourCC(a->audio_chunk->fourcc, 'A', 'G', 'A', 'C')) return INVALID_HEADER_FORMATTING_ERR;
-	fseek(f, (long)a->audio_chunk->size, SEEK_CUR);
 	return NO_ERR;
 }
 
@@ -660,7 +640,20 @@ static void encode_sequence(AGMV* a, const char* filename, const agmv_source* sr
 
 	build_palette_from_frames(src, start_frame, end_frame, width * height, quality, opt, p0, p1);
 	if (schedule == AGMV_SCHEDULE_PDIFS && a->audio_chunk) a->audio_chunk->size = (u32)(a->header.audio_size / (f32)adjusted);   /* 0 without an audio track */
-	if (schedule == AGMV_SCHEDULE_FULL && a->audio_chunk) a->audio_chunk->size = (u32)(a->header.audio_size / (f32)AGMV_GetNumberOfFrames(a));
+	/* :4024 divides by end_frame - start_frame, one less than the frames (and chunks) it writes: with a track, the chunks of a FULL
+	   file ask for more codes than audio_size holds, and AGMV_EncodeAudioChunk writes zeros where the reference reads on */
+	if (schedule == AGMV_SCHEDULE_FULL && a->audio_chunk)
+		a->audio_chunk->size = (u32)(a->header.audio_size / (f32)(end_frame > start_frame ? end_frame - start_frame : 1));
+
+	if (AGMV_GetTotalAudioDuration(a) != 0 && a->audio_chunk && a->audio_track) {      /* :2661-2667, :4023-4029 */
+		/* an object with a track gets its codes; a track that came from device memory brought them along (attach_audio_dev) */
+		if (!a->audio_chunk->atsample && (AGMV_GetBitsPerSample(a) == 16 ? (void*)a->audio_track->pcm : (void*)a->audio_track->pcm8)) {
+			a->audio_chunk->atsample = (u8*)calloc(AGMV_GetAudioSize(a) ? AGMV_GetAudioSize(a) : 1, 1);
+			if (!a->audio_chunk->atsample) { fprintf(stderr, "libagmv(amd): out of host memory for the audio codes\n"); abort(); }
+			AGMV_CompressAudio(a);
+		}
+		a->audio_track->start_point = 0;
+	}
 
 	file = fopen(filename, "wb");
 	if (!file) { fprintf(stderr, "libagmv(amd): cannot create %s\n", filename); abort(); }
@@ -743,14 +736,51 @@ static int known_pixfmt(int fmt)
 	return flags == 0 && base >= AGMV_PIXFMT_XRGB32 && base <= AGMV_PIXFMT_RGB8P;
 }
 
+int AGMV_SetAudioDev(const void* d_pcm, AGMV_PCMFMT fmt, u32 samples_per_channel, u32 sample_rate, u16 channels)
+{
+	memset(&g_audio, 0, sizeof(g_audio));
+	if (!d_pcm) return 0;
+	if (fmt != AGMV_PCM_S16 && fmt != AGMV_PCM_U8 && fmt != AGMV_PCM_F32P) return -1;
+	if (channels == 0 || channels > 255 || (fmt == AGMV_PCM_F32P && channels > 8)) return -2;      /* the object holds the count in a u8 */
+	if (sample_rate == 0) return -3;
+	if (samples_per_channel / sample_rate == 0) return -4;
+	if (samples_per_channel > 0xFFFFFFFFul / channels) return -5;
+	g_audio.d_pcm = d_pcm; g_audio.fmt = (int)fmt; g_audio.samples = samples_per_channel; g_audio.rate = sample_rate; g_audio.channels = channels;
+	return 0;
+}
+
+/* the pending device track becomes the object's: the header as the WAV importer sets it for that PCM, and the codes of the whole
+   track from one compand kernel on the library's device (the object holds no PCM of its own, encode_sequence finds the codes) */
+static void attach_audio_dev(AGMV* a)
+{
+	agmv_hip_ctx* c = ctx();
+	const size_t n = (size_t)g_audio.samples * g_audio.channels;
+	void* stream = agmv_hip_stream_create(c);
+	uint8_t *d_codes = (uint8_t*)agmv_hip_malloc_on(c, n), *h_codes = (uint8_t*)agmv_hip_host_alloc(n);
+	u8* codes = (u8*)malloc(n);
+	if (!stream || !d_codes || !h_codes || !codes) agmv_die("buffers for the audio track");
+	if (agmv_hip_audio_compand_async(c, g_audio.fmt, g_audio.d_pcm, g_audio.channels, g_audio.samples, d_codes, stream) ||
+	    agmv_hip_memcpy_async(c, h_codes, d_codes, n, 1, stream) || agmv_hip_stream_sync(c, stream))
+		agmv_die("audio compand");
+	memcpy(codes, h_codes, n);
+	agmv_hip_host_free(h_codes); agmv_hip_free_on(c, d_codes); agmv_hip_stream_destroy(c, stream);
+	AGMV_SetBitsPerSample(a, g_audio.fmt == AGMV_PCM_U8 ? 8 : 16);
+	AGMV_SetAudioSize(a, (u32)n);
+	AGMV_SetSampleRate(a, g_audio.rate);
+	AGMV_SetNumberOfChannels(a, (u8)g_audio.channels);
+	AGMV_SetTotalAudioDuration(a, g_audio.samples / g_audio.rate);
+	a->audio_chunk->atsample = codes;
+}
+
 /* The same three files from frames in device memory: num_of_frames frames of width x height pixels in the layout `fmt`, on the
    device of this library's context.  What the BMP drivers write for f1.bmp .. f<n>.bmp holding these frames, byte for byte (for
    AGMV_SCHEDULE_ADAPTIVE with AGMV_EncodeVideo's CreateAGMV(n - 1, ...)); GBA_GEN_AGMV.h is not written.  Returns 0, or a
    negative value -- before any file is created -- for arguments that cannot be encoded. */
-int AGMV_EncodeFramesFmtDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 width, u32 height,
-                            u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+static int encode_frames_dev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 width, u32 height,
+                             u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
 {
 	agmv_source src;
+	AGMV* a;
 	int sw, sh;
 	u32 least;
 	if (!known_pixfmt((int)fmt) || !filename || !d_frames) return -1;
@@ -758,6 +788,7 @@ int AGMV_EncodeFramesFmtDev(const char* filename, const void* d_frames, AGMV_PIX
 	    (compression != AGMV_LZSS_COMPRESSION && compression != AGMV_LZ77_COMPRESSION) ||
 	    (schedule != AGMV_SCHEDULE_FULL && schedule != AGMV_SCHEDULE_PDIFS && schedule != AGMV_SCHEDULE_ADAPTIVE))
 		return -1;
+	if (schedule == AGMV_SCHEDULE_ADAPTIVE && g_audio.d_pcm) return -5;      /* AGMV_EncodeVideo has no audio */
 	/* the first group of the schedule reads this many frames whatever the length of the clip */
 	least = schedule == AGMV_SCHEDULE_FULL ? 1 : (heavy_pdifs(opt) ? 2 : 4);
 	if (num_of_frames < least || num_of_frames > 0x7FFFFFFFul) return -2;
@@ -768,9 +799,18 @@ int AGMV_EncodeFramesFmtDev(const char* filename, const void* d_frames, AGMV_PIX
 	memset(&src, 0, sizeof(src));
 	src.d_frames = d_frames; src.fmt = (int)fmt; src.src_w = (uint32_t)width; src.src_h = (uint32_t)height;
 	src.n_frames = (uint32_t)num_of_frames; src.first = 1; src.device = agmv_hip_ctx_device(ctx());
-	encode_sequence(CreateAGMV(schedule == AGMV_SCHEDULE_ADAPTIVE ? num_of_frames - 1 : num_of_frames, width, height, frames_per_second),
-	                filename, &src, schedule, 1, num_of_frames, width, height, opt, quality, compression);
+	a = CreateAGMV(schedule == AGMV_SCHEDULE_ADAPTIVE ? num_of_frames - 1 : num_of_frames, width, height, frames_per_second);
+	if (g_audio.d_pcm) attach_audio_dev(a);
+	encode_sequence(a, filename, &src, schedule, 1, num_of_frames, width, height, opt, quality, compression);
 	return 0;
+}
+
+int AGMV_EncodeFramesFmtDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 width, u32 height,
+                            u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+{
+	const int rc = encode_frames_dev(filename, d_frames, fmt, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule);
+	memset(&g_audio, 0, sizeof(g_audio));                      /* a pending track is consumed whatever the call returns */
+	return rc;
 }
 
 int AGMV_EncodeFramesDev(const char* filename, const unsigned* d_frames, u32 num_of_frames, u32 width, u32 height,
@@ -783,9 +823,9 @@ int AGMV_EncodeFramesDev(const char* filename, const unsigned* d_frames, u32 num
 /* The clip scaled to width x height first (include/agmv.h has the two rules): the scaled XRGB32 clip D is materialised once on
    the library's device -- the source is read once in its own layout, where the histogram, the similarity and the encode would
    each read it -- and AGMV_EncodeFramesDev runs on D.  Nothing of the source's size or layout is allocated. */
-int AGMV_EncodeFramesScaledDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height,
-                               u32 width, u32 height, AGMV_SCALE filter, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
-                               AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+static int encode_frames_scaled_dev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height,
+                                   u32 width, u32 height, AGMV_SCALE filter, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
+                                   AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
 {
 	agmv_hip_ctx* c;
 	void* stream;
@@ -798,6 +838,7 @@ int AGMV_EncodeFramesScaledDev(const char* filename, const void* d_frames, AGMV_
 	    (compression != AGMV_LZSS_COMPRESSION && compression != AGMV_LZ77_COMPRESSION) ||
 	    (schedule != AGMV_SCHEDULE_FULL && schedule != AGMV_SCHEDULE_PDIFS && schedule != AGMV_SCHEDULE_ADAPTIVE))
 		return -1;
+	if (schedule == AGMV_SCHEDULE_ADAPTIVE && g_audio.d_pcm) return -5;
 	scaled_size(opt, &sw, &sh);
 	if (sw || bad_geometry((uint32_t)width, (uint32_t)height) || width > 0xFFFFFFFFul || height > 0xFFFFFFFFul) return -3;
 	if (src_width == 0 || src_height == 0 || src_width > 0xFFFFFFFFul || src_height > 0xFFFFFFFFul || src_px > (1ull << 28)) return -3;
@@ -826,8 +867,18 @@ int AGMV_EncodeFramesScaledDev(const char* filename, const void* d_frames, AGMV_
 	if (failed || agmv_hip_stream_sync(c, stream)) agmv_die("frame scale");
 	agmv_hip_stream_destroy(c, stream);
 	free(index); agmv_hip_free_on(c, d_index);
-	rc = AGMV_EncodeFramesDev(filename, d_scaled, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule);
+	rc = encode_frames_dev(filename, d_scaled, AGMV_PIXFMT_XRGB32, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule);
 	agmv_hip_free_on(c, d_scaled);
+	return rc;
+}
+
+int AGMV_EncodeFramesScaledDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height,
+                               u32 width, u32 height, AGMV_SCALE filter, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
+                               AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+{
+	const int rc = encode_frames_scaled_dev(filename, d_frames, fmt, num_of_frames, src_width, src_height, width, height, filter, frames_per_second, opt,
+	                                        quality, compression, schedule);
+	memset(&g_audio, 0, sizeof(g_audio));
 	return rc;
 }
 
@@ -906,12 +957,63 @@ int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frame
 	return AGMV_DecodeFramesFmtDev(filename, d_frames, AGMV_PIXFMT_XRGB32, cap_frames, info);
 }
 
-/* audio export (quick_export.wav / .aiff) is out of scope of this build; the video frames are exported
-   exactly like the reference does */
+/* the video frames are exported exactly like the reference does; no quick_export.wav / .aiff is written here (callers of this
+   build never found one in their working directory): AGMV_DecodeAudio(filename, audio_type) is the audio export */
 int AGMV_DecodeAGMV(const char* filename, u8 img_type, AGMV_AUDIO_TYPE audio_type)
 {
 	(void)audio_type;
 	return decode_file(filename, img_type, NULL, AGMV_PIXFMT_XRGB32, 0, 0, NULL, NULL);
+}
+
+/* The file's audio track into device memory in the layout `fmt` (include/agmv.h): the AGAC payloads gathered on the host into
+   one pinned buffer, one upload, one expand kernel.  No video is decoded. */
+int AGMV_DecodeAudioDev(const char* filename, void* d_pcm, AGMV_PCMFMT fmt, u32 cap_samples, AGMV_INFO* info)
+{
+	FILE* f;
+	AGMV hdr_obj;
+	u8* file;
+	uint8_t *h_codes, *d_codes;
+	long flen;
+	size_t pos, got, cap, n;
+	u32 channels;
+	int err, failed;
+	agmv_hip_ctx* c;
+	void* stream;
+	if (fmt != AGMV_PCM_S16 && fmt != AGMV_PCM_U8 && fmt != AGMV_PCM_F32P) return -1;
+	f = filename ? fopen(filename, "rb") : NULL;
+	if (!f) return -FILE_NOT_FOUND_ERR;
+	memset(&hdr_obj, 0, sizeof(hdr_obj.header));
+	err = AGMV_DecodeHeader(f, &hdr_obj);
+	if (err != NO_ERR) { fclose(f); return -err; }
+	if (info) *info = AGMV_GetVideoInfo(&hdr_obj);
+	channels = hdr_obj.header.num_of_channels;
+	if (!d_pcm || hdr_obj.header.total_audio_duration == 0) { fclose(f); return 0; }
+	if ((hdr_obj.header.bits_per_sample == 16) == (fmt == AGMV_PCM_U8) || channels == 0 || (fmt == AGMV_PCM_F32P && channels > 8)) { fclose(f); return -1; }
+	pos = (size_t)ftell(f);
+	fseek(f, 0, SEEK_END); flen = ftell(f); fseek(f, 0, SEEK_SET);
+	file = (u8*)malloc((size_t)flen + 16);
+	if (!file) { fclose(f); return -MEMORY_CORRUPTION_ERR; }
+	got = fread(file, 1, (size_t)flen, f);
+	fclose(f);
+	cap = hdr_obj.header.audio_size < cap_samples ? hdr_obj.header.audio_size : cap_samples;
+	h_codes = (uint8_t*)agmv_hip_host_alloc(cap ? cap : 1);
+	if (!h_codes) { free(file); return -gpu_failed("pinned buffer for the audio codes"); }
+	n = agmv_gather_audio(file, got, pos, (uint32_t)hdr_obj.header.num_of_frames, h_codes, cap);
+	free(file);
+	if (n > 0x7FFFFFFFu) n = 0x7FFFFFFFu;                      /* the return value is an int */
+	n -= n % channels;
+	if (n == 0) { agmv_hip_host_free(h_codes); return 0; }
+	if (!g_ctx) { const char* e = getenv("AGMV_DEVICE"); g_ctx = agmv_hip_create(e ? atoi(e) : 0); }
+	c = g_ctx;
+	if (!c) { agmv_hip_host_free(h_codes); return -gpu_failed("cannot open the GPU"); }
+	stream = agmv_hip_stream_create(c);
+	d_codes = (uint8_t*)agmv_hip_malloc_on(c, n);
+	failed = !stream || !d_codes || agmv_hip_memcpy_async(c, d_codes, h_codes, n, 0, stream) ||
+	         agmv_hip_audio_expand_async(c, (int)fmt, d_codes, channels, n / channels, d_pcm, stream) || agmv_hip_stream_sync(c, stream);
+	if (failed) err = gpu_failed("audio expand");
+	agmv_hip_free_on(c, d_codes); agmv_hip_host_free(h_codes);
+	if (stream) agmv_hip_stream_destroy(c, stream);
+	return failed ? -err : (int)n;
 }
 
 /* ------------------------------------------------------------------------------------------

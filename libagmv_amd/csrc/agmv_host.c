@@ -208,9 +208,11 @@ static void find_chunk(FILE* f, char c0, char c1, char c2, char c3)
 	AGMV_ReadFourCC(f, cc);
 	if (AGMV_IsCorrectFourCC(cc, c0, c1, c2, c3)) { fseek(f, ftell(f) - 4, SEEK_SET); return; }
 	for (;;) {
+		const long at = ftell(f);
 		if (AGMV_EOF(f)) break;
 		AGMV_ReadFourCC(f, cc);
 		if (AGMV_IsCorrectFourCC(cc, c0, c1, c2, c3)) break;
+		if (ftell(f) - at < 4) break;                              /* fewer than 4 bytes were left: the reference's loop never ends here */
 		fseek(f, ftell(f) - 3, SEEK_SET);
 	}
 	fseek(f, ftell(f) - 4, SEEK_SET);

@@ -907,7 +907,7 @@ static size_t scan_fourcc(const u8* d, size_t len, size_t pos, const char* cc)
 static uint32_t le32(const u8* p) { return p[0] | p[1] << 8 | p[2] << 16 | (uint32_t)p[3] << 24; }
 
 /* where the reference's reader stands behind a frame chunk at c whose LZ stage consumed `used` payload bytes (audio: AGMV_FindNextAudioChunk
-   + skip, out of scope) */
+   + the chunk's payload) */
 static size_t behind_chunk(const u8* file, size_t len, size_t c, size_t used, int has_audio)
 {
 	size_t pos = c + 16 + used;
@@ -936,6 +936,34 @@ static unsigned locate_chunks(const u8* file, size_t len, size_t pos, int has_au
 		pos = behind_chunk(file, len, at, c[n].csize < c[n].avail ? c[n].csize : c[n].avail, has_audio);
 	}
 	return n;
+}
+
+/* The AGAC payloads of the first nframes frames, back to back in out[0, cap): the walk of AGMV_DecodeAudio (reference
+   src/agmv_decode.c:725-729), which skips every frame chunk by its csize field -- what locate_chunks assumes of a reader -- and
+   reads each audio chunk's own size field.  Payload bytes the file does not hold are zeros.  Returns the bytes gathered. */
+size_t agmv_gather_audio(const u8* file, size_t len, size_t pos, uint32_t nframes, u8* out, size_t cap)
+{
+	dchunk c[64];
+	size_t total = 0;
+	while (nframes && total < cap) {
+		const unsigned want = nframes < 64 ? (unsigned)nframes : 64u, n = locate_chunks(file, len, pos, 1, c, want);
+		unsigned k;
+		for (k = 0; k < n && total < cap; k++) {
+			const size_t behind = c[k].at + 16 + (c[k].csize < c[k].avail ? c[k].csize : c[k].avail), ac = scan_fourcc(file, len, behind, "AGAC");
+			size_t size, held;
+			if (ac + 8 > len) return total;
+			size = le32(file + ac + 4);
+			if (size > cap - total) size = cap - total;
+			held = size < len - (ac + 8) ? size : len - (ac + 8);
+			memcpy(out + total, file + ac + 8, held);
+			memset(out + total + held, 0, size - held);
+			total += size;
+			pos = ac + 8 + le32(file + ac + 4);
+		}
+		if (n < want) break;
+		nframes -= n;
+	}
+	return total;
 }
 
 /* *pos = the true position behind the last chunk that was where it was assumed; returns the frames up to and including it

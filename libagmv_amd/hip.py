@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "agmv_hip_scale_area_dev",
     "agmv_hip_palette_refine_dev",
     "agmv_hip_dither_frames_async",
+    "agmv_hip_audio_compand_async", "agmv_hip_audio_expand_async",
 ]
 
 
@@ -172,6 +173,10 @@ def load_library(path=None):
     if path is None or hasattr(L, "agmv_hip_dither_frames_async"):
         L.agmv_hip_dither_frames_async.argtypes = [vp, u32, vp, u32, u32, u32, vp]
         L.agmv_hip_dither_frames_async.restype = C.c_int
+    if path is None or hasattr(L, "agmv_hip_audio_compand_async"):
+        L.agmv_hip_audio_compand_async.argtypes = [vp, C.c_int, vp, u32, C.c_uint64, vp, vp]
+        L.agmv_hip_audio_expand_async.argtypes = [vp, C.c_int, vp, u32, C.c_uint64, vp, vp]
+        L.agmv_hip_audio_compand_async.restype = L.agmv_hip_audio_expand_async.restype = C.c_int
     L.agmv_hip_check.argtypes = [vp, vp]
     L.agmv_hip_enable_timing.argtypes = [vp, C.c_int]
     L.agmv_hip_enable_timing.restype = C.c_int
@@ -230,6 +235,18 @@ def yuvfmt(fmt, yuv=None, full_range=False):
     if isinstance(fmt, int) and (fmt & 0xFF) in YUVFMT.values() and not fmt & ~0x3FF and yuv is None and not full_range:
         return fmt
     raise ValueError("fmt: one of %s (or its value with flags) is needed, got %r" % (", ".join(sorted(YUVFMT)), fmt))
+
+
+# AGMV_PCMFMT of include/agmv.h: name -> value
+PCMFMT = {"s16": 1, "u8": 2, "f32p": 3}
+
+
+def pcmfmt(fmt):
+    """the AGMV_PCMFMT value of a name or of a value"""
+    v = PCMFMT.get(fmt, fmt)
+    if v not in PCMFMT.values():
+        raise ValueError("fmt: one of %s is needed, got %r" % (", ".join(sorted(PCMFMT)), fmt))
+    return v
 
 
 def _np_ptr(a):
@@ -867,6 +884,47 @@ class AgmvHip:
         s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
         self._ck(self.L.agmv_hip_dither_frames_async(self.ctx, int(strength), pix.data_ptr(), w, h, pix.numel() // (w * h), s))
         return pix
+
+    # ------------------------------------------------------------------ audio tracks (include/agmv.h, "audio tracks")
+    @staticmethod
+    def _pcm_shape(name, fmt, pcm):
+        """(AGMV_PCMFMT value, channels, samples per channel) of a contiguous CUDA tensor: int16 [n, ch] / uint8 [n, ch] / float32 [ch, n]"""
+        import torch
+        v = pcmfmt(fmt)
+        want = {1: torch.int16, 2: torch.uint8, 3: torch.float32}[v]
+        if not (pcm.is_cuda and pcm.dtype == want and pcm.dim() == 2 and pcm.is_contiguous()):
+            raise ValueError("%s: fmt %r needs a contiguous CUDA %s tensor %s, got %s %s strides %s on %s"
+                             % (name, fmt, want, "[channels, samples]" if v == 3 else "[samples, channels]", pcm.dtype, tuple(pcm.shape), pcm.stride(), pcm.device))
+        return (v, pcm.shape[0], pcm.shape[1]) if v == 3 else (v, pcm.shape[1], pcm.shape[0])
+
+    def audio_compand(self, fmt, pcm, codes=None, stream=None):
+        """pcm in the layout `fmt` ("s16", "u8" or "f32p") -> uint8 [samples, channels], the track's code bytes
+        (agmv_hip_audio_compand_async) on `stream` (a torch stream; None = torch's current one).  Nothing waits."""
+        import torch
+        v, ch, n = self._pcm_shape("audio_compand", fmt, pcm)
+        if codes is None:
+            codes = torch.empty((n, ch), dtype=torch.uint8, device=pcm.device)
+        elif not (codes.is_cuda and codes.dtype == torch.uint8 and codes.is_contiguous() and codes.numel() == n * ch):
+            raise ValueError("audio_compand: codes must be a contiguous CUDA uint8 tensor of %d bytes" % (n * ch))
+        s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self._ck(self.L.agmv_hip_audio_compand_async(self.ctx, v, pcm.data_ptr(), ch, n, codes.data_ptr(), s))
+        return codes
+
+    def audio_expand(self, fmt, codes, pcm=None, stream=None):
+        """codes uint8 [samples, channels] -> the PCM in the layout `fmt` (agmv_hip_audio_expand_async): int16 / uint8
+        [samples, channels] or float32 [channels, samples].  Nothing waits."""
+        import torch
+        v = pcmfmt(fmt)
+        if not (codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2 and codes.is_contiguous()):
+            raise ValueError("audio_expand: codes must be a contiguous CUDA uint8 tensor [samples, channels], got %s %s" % (codes.dtype, tuple(codes.shape)))
+        n, ch = codes.shape
+        if pcm is None:
+            pcm = torch.empty((ch, n) if v == 3 else (n, ch), dtype={1: torch.int16, 2: torch.uint8, 3: torch.float32}[v], device=codes.device)
+        elif self._pcm_shape("audio_expand", fmt, pcm) != (v, ch, n):
+            raise ValueError("audio_expand: pcm of shape %s does not hold %d samples in %d channels as %r" % (tuple(pcm.shape), n, ch, fmt))
+        s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self._ck(self.L.agmv_hip_audio_expand_async(self.ctx, v, codes.data_ptr(), ch, n, pcm.data_ptr(), s))
+        return pcm
 
     # ------------------------------------------------------------------ host-buffer path
     def encode_host(self, frames, first_frame_count=0, ientries=None):

@@ -12,11 +12,16 @@ Pixel layouts (AGMV_PIXFMT) and the tensors that hold n frames of h x w:
   "nv12"    uint8 [n, h * 3 / 2, w]    h rows of Y, then h / 2 rows of U, V pairs      (hardware video decoders and encoders)
   "i420"    uint8 [n, h * 3 / 2, w]    h rows of Y, then the U plane, then the V plane (software decoders, raw .yuv files)
 The two YUV 4:2:0 layouts (include/agmv.h has their definition) need even h and w here, are never inferred from a tensor, and
-take yuv="bt601" (default) or "bt709" and full_range=False (limited range) or True."""
+take yuv="bt601" (default) or "bt709" and full_range=False (limited range) or True.
+
+Audio tracks (AGMV_PCMFMT; include/agmv.h, "audio tracks") and the tensors that hold n samples per channel of ch channels:
+  "s16"   int16 [n, ch]     interleaved, the WAV samples as they are     (16-bit track)
+  "u8"    uint8 [n, ch]     interleaved unsigned bytes                   (8-bit track)
+  "f32p"  float32 [ch, n]   planar, -1 .. 1, at most 8 channels (torchaudio)   (16-bit track)"""
 import ctypes as C
 import os
 
-from .hip import HERE, PIXFMT, YUVFMT, HipUnavailable, pixfmt, yuvfmt
+from .hip import HERE, PIXFMT, YUVFMT, HipUnavailable, pcmfmt, pixfmt, yuvfmt
 
 SCHEDULE_FULL, SCHEDULE_PDIFS, SCHEDULE_ADAPTIVE = 1, 2, 3
 SCALE = {"nearest": 1, "area": 2}          # AGMV_SCALE of include/agmv.h, which defines both filters
@@ -54,6 +59,10 @@ def load_library():
         L.AGMV_SetPaletteRefine.argtypes = [C.c_uint]
         L.AGMV_SetDither.restype = None
         L.AGMV_SetDither.argtypes = [C.c_uint]
+        L.AGMV_SetAudioDev.restype = C.c_int
+        L.AGMV_SetAudioDev.argtypes = [C.c_void_p, C.c_int, C.c_ulong, C.c_ulong, C.c_ushort]
+        L.AGMV_DecodeAudioDev.restype = C.c_int
+        L.AGMV_DecodeAudioDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.POINTER(AGMV_INFO)]
         _lib = L
     return _lib
 
@@ -122,8 +131,23 @@ def _scale_target(size, scale):
     return SCALE[scale], size[0], size[1]
 
 
+def _track_geometry(audio, sample_rate):
+    """(AGMV_PCMFMT value, samples per channel, channels) of encode_frames' audio= tensor; touches neither the library nor the device"""
+    import torch
+    if not (isinstance(sample_rate, int) and not isinstance(sample_rate, bool) and sample_rate > 0):
+        raise ValueError("encode_frames: audio= needs sample_rate=, a positive int, got %r" % (sample_rate,))
+    shape = tuple(audio.shape)
+    v = {torch.int16: 1, torch.uint8: 2, torch.float32: 3}.get(audio.dtype)
+    if v is None or len(shape) != 2:
+        raise ValueError("encode_frames: audio must be int16 [n, ch], uint8 [n, ch] or float32 [ch, n], got %s %s" % (audio.dtype, shape))
+    if not audio.is_contiguous():
+        raise ValueError("encode_frames: audio needs a contiguous tensor (strides %s of shape %s)" % (audio.stride(), shape))
+    n, ch = (shape[1], shape[0]) if v == 3 else shape
+    return v, n, ch
+
+
 def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedule=SCHEDULE_PDIFS, fmt=None, yuv=None, full_range=False,
-                  size=None, scale="area", palette_refine=None, dither=None):
+                  size=None, scale="area", palette_refine=None, dither=None, audio=None, sample_rate=None):
     """frames: contiguous CUDA tensor of n frames on the library's device, in the layout `fmt` (see the module text; None = inferred
     from the tensor, which never gives "nv12" or "i420") -> the file at `path`.  yuv ("bt601", the default, or "bt709") and
     full_range go with the two YUV layouts only.  size=(h, w), in tensor order, scales the clip to that size first
@@ -132,7 +156,10 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
     palette's colours by at most n rounds of weighted k-means over the clip's histogram (AGMV_SetPaletteRefine of include/agmv.h,
     set for this call only); None leaves the library's knob as it is.  dither=s, an int from 1 to 64, pattern-dithers the frames
     against the palette with that strength before they are quantised (AGMV_SetDither of include/agmv.h, which holds the
-    definition; set for this call only); None leaves the library's knob as it is."""
+    definition; set for this call only); None leaves the library's knob as it is.  audio= is the clip's sound, a contiguous CUDA
+    tensor on the same device -- int16 [n, ch], uint8 [n, ch] or float32 [ch, n] (see the module text) -- at sample_rate= samples
+    per second; it is companded on the GPU and interleaved with the frames as AGAC chunks (AGMV_SetAudioDev, for this call only).
+    A track shorter than one second and SCHEDULE_ADAPTIVE with a track are refused."""
     import torch
     if dither is not None and not (isinstance(dither, int) and not isinstance(dither, bool) and 1 <= dither <= 64):
         raise ValueError("encode_frames: dither must be None or an int from 1 to 64, got %r" % (dither,))
@@ -140,10 +167,21 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
         raise ValueError("encode_frames: palette_refine must be None or an int from 1 to 64, got %r" % (palette_refine,))
     target = _scale_target(size, scale)
     v, n, h, w = _clip_geometry(frames, fmt, yuv, full_range)
+    track = None
+    if audio is not None:
+        track = _track_geometry(audio, sample_rate)
+    elif sample_rate is not None:
+        raise ValueError("encode_frames: sample_rate= goes with audio=")
     if not (frames.is_cuda and frames.device == torch.device(_device())):
         raise ValueError("encode_frames: the frames must be on %s, got %s" % (_device(), frames.device))
+    if audio is not None and not (audio.is_cuda and audio.device == torch.device(_device())):
+        raise ValueError("encode_frames: the audio must be on %s, got %s" % (_device(), audio.device))
     torch.cuda.synchronize(frames.device)          # the library works on streams of its own
     L = load_library()
+    if track is not None:
+        rc = L.AGMV_SetAudioDev(audio.data_ptr(), track[0], track[1], sample_rate, track[2])
+        if rc:
+            raise ValueError("AGMV_SetAudioDev refused the track (%d): %d samples in %d channels at %d Hz" % (rc, track[1], track[2], sample_rate))
     if palette_refine is not None:
         L.AGMV_SetPaletteRefine(palette_refine)
     if dither is not None:
@@ -160,6 +198,8 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
             raise ValueError("AGMV_EncodeFramesScaledDev refused its arguments (%d): %d frames of %dx%d scaled (%s) to %dx%d, opt %d, schedule %d"
                              % (rc, n, w, h, scale, tw, th, opt, schedule))
     finally:
+        if track is not None:
+            L.AGMV_SetAudioDev(None, 0, 0, 0, 0)
         if palette_refine is not None:
             L.AGMV_SetPaletteRefine(0)
         if dither is not None:
@@ -186,3 +226,30 @@ def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False):
     if rc < 0:
         raise RuntimeError("AGMV_DecodeFramesFmtDev(%s): Error %d" % (path, -rc))
     return out[:rc], info
+
+
+def decode_audio(path, fmt="s16", cap_samples=None):
+    """-> (CUDA tensor of the file's audio track on the library's device in the layout `fmt`: int16 [n, ch] for "s16" and float32
+    [ch, n] for "f32p" (a 16-bit track), uint8 [n, ch] for "u8" (an 8-bit track); AGMV_INFO of the header).  n is what the file's
+    chunks hold, at most audio_size / ch -- and at most cap_samples / ch where cap_samples, a count over all channels, is given.
+    A file without a track gives n = 0.  No video is decoded."""
+    import torch
+    v = pcmfmt(fmt)
+    L = load_library()
+    info = AGMV_INFO()
+    rc = L.AGMV_DecodeAudioDev(os.fsencode(path), None, v, 0, C.byref(info))
+    if rc < 0:
+        raise RuntimeError("AGMV_DecodeAudioDev(%s): Error %d" % (path, -rc))
+    dtype = {1: torch.int16, 2: torch.uint8, 3: torch.float32}[v]
+    ch = max(int(info.number_of_channels), 1)
+    cap = int(info.audio_size) if info.total_audio_duration else 0
+    if cap_samples is not None:
+        cap = min(cap, int(cap_samples))
+    buf = torch.empty(max(cap, 1), dtype=dtype, device=_device())
+    got = 0
+    if cap:
+        got = L.AGMV_DecodeAudioDev(os.fsencode(path), buf.data_ptr(), v, cap, None)
+        if got < 0:
+            raise RuntimeError("AGMV_DecodeAudioDev(%s, fmt %r): Error %d (a 16-bit track decodes as \"s16\" or \"f32p\", an 8-bit track as \"u8\")"
+                               % (path, fmt, -got))
+    return (buf[:got].view(ch, got // ch) if v == 3 else buf[:got].view(got // ch, ch)), info
