@@ -10,8 +10,8 @@
 //   k_fixup         sequential repair of blocks whose value depends on an earlier GOP
 //                   (stale tail after `escape`, src/agmv_decode.c:229-232; last-block FILL
 //                   quirk :264-266)
-// On the host DEC_LAUNCH is the one place where the palette's mode (and for k_decode / k_fixup the bitmap form) becomes a
-// kernel's template argument.  Integer/byte work only: no MFMA.
+// On the host DEC_LAUNCH is the one place where a run-time flag (the palette's mode; for k_decode / k_fixup the bitmap form;
+// for k_decode the looping form) becomes a kernel's template argument.  Integer/byte work only: no MFMA.
 #include <hip/hip_runtime.h>
 
 #include <stdarg.h>
@@ -19,6 +19,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/agmv_hip.h"
 
@@ -77,10 +78,6 @@ struct dec_ws {
 	size_t fp_ws_cap;               // in bytes
 	uint32_t* d_fp_fstate;          // frame states of the last parse (inside d_fp_ws) and how many
 	uint32_t fp_frames;
-	unsigned long long* fp_vm;      // bitmap form of the last parse (inside d_fp_ws): entry bitmaps, first block per region, tile entries
-	uint32_t* fp_kb;
-	uint32_t* fp_tidx;
-	uint32_t fp_maxR;
 	uint32_t* d_nent_own;           // agmv_hip_decode_bitstreams_dev without a caller's nentered[]
 	size_t nent_cap;                // in bytes
 	hipStream_t aux_stream;         // decode pipeline: the parser's stream (the reconstruction runs on the caller's)
@@ -124,14 +121,15 @@ static int dec_grow(T*& d_buf, size_t& cap, size_t bytes)
 	return 0;
 }
 
-// launch k<mode512 [, more template arguments]> on stream s, then check the launch
-#define DEC_LAUNCH(k, m512, grid, block, s, A, ...) do { \
-	if (m512) hipLaunchKernelGGL((k<true, ##__VA_ARGS__>), grid, block, 0, s, A); \
-	else      hipLaunchKernelGGL((k<false, ##__VA_ARGS__>), grid, block, 0, s, A); \
+// f(std::bool_constant<flag>()...): every run-time flag becomes a compile-time one
+template <class F>
+static void dec_flags(F&& f) { f(); }
+template <class F, class... Rest>
+static void dec_flags(F&& f, bool flag, Rest... rest) { dec_flags([&](auto... r_) { if (flag) f(std::true_type(), r_...); else f(std::false_type(), r_...); }, rest...); }
+// launch k<flags...> on stream s, then check the launch
+#define DEC_LAUNCH(k, grid, block, s, A, ...) do { \
+	dec_flags([&](auto... b_) { hipLaunchKernelGGL((k<decltype(b_)::value...>), grid, block, 0, s, A); }, __VA_ARGS__); \
 	DCK(hipGetLastError()); } while (0)
-// ... for k_fixup (and, spelled out in decode_launch, k_decode): k<mode512, bitmap form>
-#define DEC_LAUNCH_BM(k, m512, bm, grid, block, s, A) do { \
-	if (bm) DEC_LAUNCH(k, m512, grid, block, s, A, true); else DEC_LAUNCH(k, m512, grid, block, s, A, false); } while (0)
 
 static int dec_mode512(agmv_hip_ctx* c) { int m = 0; (void)agmv_hip_internal_palette(c, &m); return m; }
 
@@ -1594,119 +1592,136 @@ __global__ __launch_bounds__(64) void k_fixup(DecArgs A)
 
 static int check_slab(const uint8_t* d_bits, size_t stride)
 {
-	if ((stride & 3u) || stride < 4 || ((uintptr_t)d_bits & 3u)) { dec_err("agmv_hip: bitstream slab and stride must be 4-byte aligned"); return -1; }
+	if ((stride & 3u) || stride < 4 || ((uintptr_t)d_bits & 3u)) return dec_err("agmv_hip: bitstream slab and stride must be 4-byte aligned");
 	return 0;
 }
 
-// the robust parser kernels over n_frames frames on stream s (workspace of the context: launches that share it must be
-// ordered); fstate != NULL: only the frames marked FS_BAD
-static int parse_launch_robust(agmv_hip_ctx* c, const uint8_t* d_bits, size_t stride, const uint32_t* d_bpos, uint32_t n_frames,
-                               uint32_t nblk, uint32_t* d_offsets, uint32_t* d_nentered, size_t ws_frames, const uint32_t* fstate, hipStream_t s,
-                               unsigned long long* vm = nullptr, uint32_t maxR = 0, const uint32_t* nbad = nullptr)
+// these rows of a batch, one frame per row: its bitstream in the slab, bpos[], nentered[] and (two-call form) nblk offsets[]
+struct DecRows {
+	const uint8_t* bits;
+	size_t stride;
+	const uint32_t* bpos;
+	uint32_t *offsets, *nentered;   // offsets == NULL: the bitmap form
+	uint32_t n_frames, nblk;
+};
+static DecRows rows_range(DecRows r, uint32_t f0, uint32_t f1)   // rows [f0, f1)
 {
-	const size_t cpf = (stride + PC) / PC, maxchunks = cpf * ws_frames;
-	if (maxchunks >> 32) { dec_err("agmv_hip: parser batch too large (%zu chunk rows)", maxchunks); return -1; }
-	const size_t need = maxchunks + (maxchunks * 33 + 1) / 2 + 16;   // dwords: centry | summ (u16)
-	dec_ws* d = dec_area(c);
-	if (dec_grow(d->d_parse_ws, d->parse_ws_cap, need * 4)) return -1;
-	ParseArgs A;
-	memset(&A, 0, sizeof(A));
-	A.bits = d_bits; A.stride = stride; A.bpos = d_bpos; A.offsets = d_offsets; A.nentered = d_nentered;
-	A.cpf = (uint32_t)cpf; A.centry = d->d_parse_ws; A.summ = (uint16_t*)(A.centry + maxchunks);
-	A.n_frames = n_frames; A.nblk = nblk; A.fstate = fstate; A.vm = vm; A.maxR = maxR; A.nbad = nbad;
-	// the exception path (fstate): a few rows of workgroups stride over the frames and leave those that are not FS_BAD at
-	// once -- with one row per frame the three gated launches cost 0.03 ms per 1024 frames for zero frames to parse
-	const dim3 gy(1, fstate ? (n_frames < 64u ? n_frames : 64u) : (n_frames < 65535u ? n_frames : 65535u));
-	// one wave per workgroup, each striding over the chunks of one frame: ~512 waves per CU in the grid (measured on
-	// 1024 x 1080p: 8 / 16 / 32 / 64 / 128 / 256 per frame -> 2.85 / 2.30 / 1.96 / 1.87 / 1.83 / 1.84 ms)
+	r.bits += (size_t)f0 * r.stride; r.bpos += f0; r.nentered += f0; r.n_frames = f1 - f0;
+	if (r.offsets) r.offsets += (size_t)f0 * r.nblk;
+	return r;
+}
+// where the rows' pixels go and the decoder state they continue from
+struct DecPix {
+	uint32_t w, h, first_fc;
+	uint32_t* out;
+	const uint32_t *prev, *prev_iframe;
+};
+
+// words of the context's bitmap of positions to repair: the bitmap + the "anything to repair" word + the "depends on the prior state" word
+static uint32_t dirty_words(uint32_t nblk) { return (nblk + 31) / 32 + 2; }
+
+enum ParseMode { PARSE_FAST, PARSE_ROBUST, PARSE_SERIAL };
+static ParseMode parse_mode()                                  // AGMV_HIP_PARSE (include/agmv_hip.h), read by every call
+{
+	const char* m = getenv("AGMV_HIP_PARSE");
+	return !m ? PARSE_FAST : strcmp(m, "robust") == 0 ? PARSE_ROBUST : strcmp(m, "serial") == 0 ? PARSE_SERIAL : PARSE_FAST;
+}
+
+// width of a parser grid whose rows are frames: one wave per workgroup, each striding over the chunks or regions of one
+// frame (at most `cap` of them are worth a workgroup): ~512 waves per CU in the grid (measured on 1024 x 1080p:
+// 8 / 16 / 32 / 64 / 128 / 256 per frame -> 2.85 / 2.30 / 1.96 / 1.87 / 1.83 / 1.84 ms)
+static uint32_t parse_grid_x(agmv_hip_ctx* c, uint32_t n_frames, size_t cap)
+{
 	uint32_t gx = (uint32_t)(((size_t)agmv_hip_internal_n_cu(c) * 512 + n_frames - 1) / n_frames);
 	if (gx < 32) gx = 32;
 	if (gx > 256) gx = 256;
-	if (fstate) gx = 32;                                       // the exception path: most frames leave at once
-	if (getenv("AGMV_PARSE_GX")) gx = (uint32_t)atoi(getenv("AGMV_PARSE_GX"));   // tuning aid
-	if (gx > cpf) gx = (uint32_t)cpf;
-	if (gx < 1) gx = 1;
-	const dim3 grid(gx, gy.y);
+	if (gx > cap) gx = (uint32_t)cap;
+	return gx < 1 ? 1 : gx;
+}
+
+// the robust parser kernels over the rows r on stream s (workspace of the context, sized for ws_frames rows: launches that
+// share it must be ordered); fstate != NULL: only the frames marked FS_BAD (nbad of them); vm != NULL: entry bits, no offsets[]
+static int parse_launch_robust(agmv_hip_ctx* c, const DecRows& r, size_t ws_frames, hipStream_t s,
+                               const uint32_t* fstate, const uint32_t* nbad, unsigned long long* vm, uint32_t maxR)
+{
+	const size_t cpf = (r.stride + PC) / PC, maxchunks = cpf * ws_frames;
+	if (maxchunks >> 32) { dec_err("agmv_hip: parser batch too large (%zu chunk rows)", maxchunks); return -1; }
+	dec_ws* d = dec_area(c);
+	if (dec_grow(d->d_parse_ws, d->parse_ws_cap, (maxchunks + (maxchunks * 33 + 1) / 2 + 16) * 4)) return -1;   // dwords: centry | summ (u16)
+	ParseArgs A;
+	memset(&A, 0, sizeof(A));
+	A.bits = r.bits; A.stride = r.stride; A.bpos = r.bpos; A.offsets = r.offsets; A.nentered = r.nentered;
+	A.cpf = (uint32_t)cpf; A.centry = d->d_parse_ws; A.summ = (uint16_t*)(A.centry + maxchunks);
+	A.n_frames = r.n_frames; A.nblk = r.nblk; A.fstate = fstate; A.vm = vm; A.maxR = maxR; A.nbad = nbad;
+	// the exception path (fstate): a few rows of workgroups, 32 wide, stride over the frames and leave those that are not
+	// FS_BAD at once -- with one row per frame the three gated launches cost 0.03 ms per 1024 frames for zero frames to parse
+	const uint32_t n = r.n_frames;
+	const dim3 grid(parse_grid_x(c, n, fstate && cpf > 32 ? 32 : cpf), fstate ? (n < 64u ? n : 64u) : (n < 65535u ? n : 65535u));
 	const int m512 = dec_mode512(c);
-	DEC_LAUNCH(k_parse_chunks, m512, grid, dim3(64), s, A);
-	hipLaunchKernelGGL(k_parse_stitch, dim3(fstate ? (n_frames < 1024u ? n_frames : 1024u) : n_frames), dim3(64), 0, s, A);
+	DEC_LAUNCH(k_parse_chunks, grid, dim3(64), s, A, m512);
+	hipLaunchKernelGGL(k_parse_stitch, dim3(fstate ? (n < 1024u ? n : 1024u) : n), dim3(64), 0, s, A);
 	DCK(hipGetLastError());
-	DEC_LAUNCH(k_parse_emit, m512, grid, dim3(64), s, A);
+	DEC_LAUNCH(k_parse_emit, grid, dim3(64), s, A, m512);
 	return 0;
 }
 
 // the parser: speculative walks proven per frame (k_fp_*), the robust kernels for the frames that could not be proven.
-// AGMV_HIP_PARSE=robust runs the robust kernels alone.
-static int parse_launch(agmv_hip_ctx* c, const uint8_t* d_bits, size_t stride, const uint32_t* d_bpos, uint32_t n_frames,
-                        uint32_t nblk, uint32_t* d_offsets, uint32_t* d_nentered, size_t ws_frames, hipStream_t s, bool bitmap = false,
-                        uint32_t* dirty = nullptr, uint32_t ndirty = 0)
+// AGMV_HIP_PARSE=robust runs the robust kernels alone.  bm != NULL: the bitmap form (no offsets[]) for these arguments of
+// k_decode -- their bitmap of positions to repair is cleared; entry bitmaps, first block per region, tile entries come back
+static int parse_launch(agmv_hip_ctx* c, const DecRows& r, size_t ws_frames, hipStream_t s, DecArgs* bm)
 {
-	const char* mode = getenv("AGMV_HIP_PARSE");
-	const bool robust_only = mode && strcmp(mode, "robust") == 0;
+	const bool robust_only = parse_mode() == PARSE_ROBUST;
+	const uint32_t n_frames = r.n_frames;
 	dec_ws* d = dec_area(c);
 	d->d_fp_fstate = nullptr; d->fp_frames = 0;
-	if (!bitmap && (n_frames > 65535u || robust_only))
-		return parse_launch_robust(c, d_bits, stride, d_bpos, n_frames, nblk, d_offsets, d_nentered, ws_frames, nullptr, s);
+	if (!bm && (n_frames > 65535u || robust_only)) return parse_launch_robust(c, r, ws_frames, s, nullptr, nullptr, nullptr, 0);
 	if (n_frames > 65535u) { dec_err("agmv_hip: more than 65535 frames in one parser launch"); return -1; }
-	const size_t maxR = (stride + FRB - 1) / FRB + 1;
-	const size_t nreg = maxR * ws_frames;
-	const uint32_t tpfd = (nblk + DEC_T - 1) / DEC_T;
+	const size_t maxR = (r.stride + FRB - 1) / FRB + 1, nreg = maxR * ws_frames;
+	const uint32_t tpfd = (r.nblk + DEC_T - 1) / DEC_T;
 	const size_t b_rec = nreg * sizeof(uint4), b_vm = nreg * FOWN * 8, b_kb = nreg * 4, b_fs = ((ws_frames * 4 + 15) & ~(size_t)15);
-	const size_t b_tx = bitmap ? (((size_t)ws_frames * (tpfd + 1) * 4 + 15) & ~(size_t)15) : 0;
-	const size_t need = b_rec + b_vm + b_kb + b_fs + b_tx + 16;
-	if (dec_grow(d->d_fp_ws, d->fp_ws_cap, need)) return -1;
+	const size_t b_tx = bm ? (((size_t)ws_frames * (tpfd + 1) * 4 + 15) & ~(size_t)15) : 0;
+	if (dec_grow(d->d_fp_ws, d->fp_ws_cap, b_rec + b_vm + b_kb + b_fs + b_tx + 16)) return -1;
 	FpArgs A;
 	memset(&A, 0, sizeof(A));
-	A.bits = d_bits; A.stride = stride; A.bpos = d_bpos; A.offsets = d_offsets; A.nentered = d_nentered;
+	A.bits = r.bits; A.stride = r.stride; A.bpos = r.bpos; A.offsets = r.offsets; A.nentered = r.nentered;
 	uint8_t* w = (uint8_t*)d->d_fp_ws;
 	A.rec = (uint4*)w; A.vm = (unsigned long long*)(w + b_rec); A.kb = (uint32_t*)(w + b_rec + b_vm); A.fstate = (uint32_t*)(w + b_rec + b_vm + b_kb);
-	A.tidx = bitmap ? (uint32_t*)(w + b_rec + b_vm + b_kb + b_fs) : nullptr; A.tpfd = tpfd;
+	A.tidx = bm ? (uint32_t*)(w + b_rec + b_vm + b_kb + b_fs) : nullptr; A.tpfd = tpfd;
 	A.nbad = (uint32_t*)(w + b_rec + b_vm + b_kb + b_fs + b_tx);
-	A.n_frames = n_frames; A.nblk = nblk; A.maxR = (uint32_t)maxR; A.dirty = dirty; A.ndirty = ndirty;
-	uint32_t gx = (uint32_t)(((size_t)agmv_hip_internal_n_cu(c) * 512 + n_frames - 1) / n_frames);
-	if (gx < 32) gx = 32;
-	if (gx > 256) gx = 256;
-	if (getenv("AGMV_PARSE_GX")) gx = (uint32_t)atoi(getenv("AGMV_PARSE_GX"));   // tuning aid
-	if (gx > maxR) gx = (uint32_t)maxR;
-	if (gx < 1) gx = 1;
+	A.n_frames = n_frames; A.nblk = r.nblk; A.maxR = (uint32_t)maxR;
+	if (bm) { A.dirty = bm->dirty; A.ndirty = dirty_words(r.nblk); }
+	uint32_t gx = parse_grid_x(c, n_frames, maxR);
 	// many small frames (8192 x 320x240: 7 regions each): one row of gx workgroups per frame would launch a quarter of a million
 	// one-wave workgroups of which most find nothing to do; the rows stride over the frames instead
 	uint32_t gy = n_frames;
 	if ((size_t)gx * gy > 131072u) {
-		const uint32_t want = (uint32_t)(((size_t)stride / 8 + FRB - 1) / FRB) + 1;   // regions of a frame whose stream is an eighth of the worst case
+		const uint32_t want = (uint32_t)(((size_t)r.stride / 8 + FRB - 1) / FRB) + 1;   // regions of a frame whose stream is an eighth of the worst case
 		if (gx > want) gx = want;
 		if ((size_t)gx * gy > 131072u) gy = 131072u / gx;
 	}
 	const dim3 grid(gx, gy);
 	if (robust_only) {                                         // debugging aid: every frame through the robust kernels (bitmap form)
-		if (bitmap) DCK(hipMemsetAsync(A.tidx, 0xFF, (size_t)n_frames * (tpfd + 1) * 4, s));   // TIDX_NONE (otherwise k_fp_finish's job; nbad: k_fp_walk's)
+		DCK(hipMemsetAsync(A.tidx, 0xFF, (size_t)n_frames * (tpfd + 1) * 4, s));   // TIDX_NONE (otherwise k_fp_finish's job; nbad: k_fp_walk's)
 		// k_parse_chunks clears the entry bitmap words up to a frame's last chunk, k_fp_tiles / k_decode read up to the end of
 		// its last region: without k_fp_walk (which writes every word of a region) the words in between are cleared here
-		if (bitmap) DCK(hipMemsetAsync(A.vm, 0, (size_t)n_frames * maxR * FOWN * 8, s));
+		DCK(hipMemsetAsync(A.vm, 0, (size_t)n_frames * maxR * FOWN * 8, s));
 		DCK(hipMemsetD32Async((hipDeviceptr_t)A.fstate, (int)FS_BAD, n_frames, s));
 		DCK(hipMemsetD32Async((hipDeviceptr_t)A.nbad, (int)n_frames, 1, s));
 	} else {
-		const int m512 = dec_mode512(c);
-		DEC_LAUNCH(k_fp_walk, m512, grid, dim3(64), s, A);
-		DEC_LAUNCH(k_fp_finish, m512, dim3(n_frames), dim3(64), s, A);
+		DEC_LAUNCH(k_fp_walk, grid, dim3(64), s, A, dec_mode512(c));
+		DEC_LAUNCH(k_fp_finish, dim3(n_frames), dim3(64), s, A, dec_mode512(c));
 	}
 	d->d_fp_fstate = A.fstate; d->fp_frames = n_frames;
-	d->fp_vm = A.vm; d->fp_kb = A.kb; d->fp_tidx = A.tidx; d->fp_maxR = A.maxR;
-	if (!bitmap) {
-		uint32_t ge = gx;                                      // (a quarter / an eighth of it: 0.179 / 0.188 against 0.169 ms per 256 frames)
-		if (getenv("AGMV_EXPAND_GX")) ge = (uint32_t)atoi(getenv("AGMV_EXPAND_GX"));   // tuning aid
-		if (ge < 1) ge = 1;
-		hipLaunchKernelGGL(k_fp_expand, dim3(ge, n_frames), dim3(64), 0, s, A);   // (one row per frame)
+	if (!bm) {
+		hipLaunchKernelGGL(k_fp_expand, dim3(gx, n_frames), dim3(64), 0, s, A);   // one row per frame (a quarter / an eighth of gx: 0.179 / 0.188 against 0.169 ms per 256 frames)
 		DCK(hipGetLastError());
-		return parse_launch_robust(c, d_bits, stride, d_bpos, n_frames, nblk, d_offsets, d_nentered, ws_frames, A.fstate, s, nullptr, 0, A.nbad);
+		return parse_launch_robust(c, r, ws_frames, s, A.fstate, A.nbad, nullptr, 0);
 	}
 	// bitmap form: the frames that could not be proven get their entry BITS from the robust kernels, are counted and
 	// numbered by k_fp_tiles, which then looks up every frame's tile entries
-	if (parse_launch_robust(c, d_bits, stride, d_bpos, n_frames, nblk, nullptr, d_nentered, ws_frames, A.fstate, s, A.vm, A.maxR, A.nbad)) return -1;
-	uint32_t gt = gx / 2 ? gx / 2 : 1;
-	if (getenv("AGMV_TILES_GX")) gt = (uint32_t)atoi(getenv("AGMV_TILES_GX"));   // tuning aid
-	if (gt < 1) gt = 1;
-	hipLaunchKernelGGL(k_fp_tiles, dim3(gt, gy), dim3(64), 0, s, A);
+	bm->vm = A.vm; bm->kb = A.kb; bm->tidx = A.tidx; bm->maxR = A.maxR;
+	if (parse_launch_robust(c, r, ws_frames, s, A.fstate, A.nbad, A.vm, A.maxR)) return -1;
+	hipLaunchKernelGGL(k_fp_tiles, dim3(gx / 2 ? gx / 2 : 1, gy), dim3(64), 0, s, A);
 	DCK(hipGetLastError());
 	return 0;
 }
@@ -1718,18 +1733,17 @@ extern "C" int agmv_hip_parse_frames_dev(agmv_hip_ctx* c, const uint8_t* d_bits,
 	if (need_dec_ctx(c, true)) return -1;
 	if (agmv_hip_internal_check_geometry(w, h)) return -1;
 	if (n_frames == 0) return 0;
-	uint32_t nblk = (w / 4) * (h / 4);
+	const DecRows r = {d_bits, stride, d_bpos, d_offsets, d_nentered, n_frames, (w / 4) * (h / 4)};
 	hipStream_t s = (hipStream_t)stream;
-	const char* mode = getenv("AGMV_HIP_PARSE");
-	if (mode && strcmp(mode, "serial") == 0) {                 // debugging aid: one lane per frame
+	if (parse_mode() == PARSE_SERIAL) {                        // debugging aid: one lane per frame
 		hipLaunchKernelGGL(k_parse_serial, dim3((n_frames + 63) / 64), dim3(64), 0, s, d_bits,
-		                   (unsigned long long)stride, d_bpos, n_frames, nblk, dec_mode512(c), d_offsets, d_nentered);
+		                   (unsigned long long)stride, d_bpos, n_frames, r.nblk, dec_mode512(c), d_offsets, d_nentered);
 		DCK(hipGetLastError());
 		return 0;
 	}
 	if (check_slab(d_bits, stride)) return -1;
 	agmv_hip_internal_ev_mark(c, 2, s);
-	if (parse_launch(c, d_bits, stride, d_bpos, n_frames, nblk, d_offsets, d_nentered, n_frames, s)) return -1;
+	if (parse_launch(c, r, n_frames, s, nullptr)) return -1;
 	agmv_hip_internal_ev_mark(c, 3, s);
 	return 0;
 }
@@ -1749,56 +1763,41 @@ extern "C" int agmv_hip_parse_fallback_frames(agmv_hip_ctx* c, void* stream)
 	return n;
 }
 
-// arguments of k_decode / k_fixup for a batch; grows and clears the context's bitmap of positions to repair
-static int decode_prepare(agmv_hip_ctx* c, DecArgs& A, const uint8_t* d_bits, size_t stride, const uint32_t* d_bpos,
-                          const uint32_t* d_offsets, const uint32_t* d_nentered, uint32_t n_frames, uint32_t w, uint32_t h,
-                          uint32_t first_fc, uint32_t* d_out, const uint32_t* d_prev, const uint32_t* d_prev_iframe, hipStream_t s,
-                          uint32_t* ndirty_out = nullptr /* != NULL: the caller has the bitmap cleared (k_fp_tiles) */)
+// arguments of k_decode / k_fixup for the rows r; grows the context's bitmap of positions to repair and, unless the
+// caller has that done (k_fp_tiles), clears it
+static int decode_prepare(agmv_hip_ctx* c, DecArgs& A, const DecRows& r, const DecPix& px, hipStream_t s, bool clear)
 {
-	if (((uintptr_t)d_out & 15u) || ((uintptr_t)d_prev & 15u) || ((uintptr_t)d_prev_iframe & 15u)) {
-		dec_err("agmv_hip: pixel buffers must be 16-byte aligned"); return -1;
-	}
-	if (check_slab(d_bits, stride)) return -1;
+	if (((uintptr_t)px.out & 15u) || ((uintptr_t)px.prev & 15u) || ((uintptr_t)px.prev_iframe & 15u)) return dec_err("agmv_hip: pixel buffers must be 16-byte aligned");
+	if (check_slab(r.bits, r.stride)) return -1;
 	memset(&A, 0, sizeof(A));
-	A.bits = d_bits; A.stride = stride; A.bpos = d_bpos; A.offsets = d_offsets; A.nentered = d_nentered;
-	A.out = d_out; A.pal = agmv_hip_internal_palette(c, nullptr); A.prev = d_prev; A.prev_iframe = d_prev_iframe;
-	A.n_frames = n_frames; A.w = w; A.h = h; A.bw = w / 4; A.nblk = (w / 4) * (h / 4);
+	A.bits = r.bits; A.stride = r.stride; A.bpos = r.bpos; A.offsets = r.offsets; A.nentered = r.nentered;
+	A.out = px.out; A.pal = agmv_hip_internal_palette(c, nullptr); A.prev = px.prev; A.prev_iframe = px.prev_iframe;
+	A.n_frames = r.n_frames; A.w = px.w; A.h = px.h; A.bw = px.w / 4; A.nblk = r.nblk;
 	A.tpf = (A.nblk + DEC_T - 1) / DEC_T;
-	A.first_fc = first_fc; A.phase = first_fc & 3u;
-	A.n_groups = (n_frames + A.phase + 3) / 4;
-	size_t nwords = (A.nblk + 31) / 32 + 2;                    // bitmap + the "anything to repair" word + the "depends on the prior state" word
+	A.first_fc = px.first_fc; A.phase = px.first_fc & 3u; A.n_groups = (r.n_frames + A.phase + 3) / 4;
+	const size_t nwords = dirty_words(A.nblk);
 	dec_ws* d = dec_area(c);                                   // (+ part 0's "depends" word of a call cut into parts: written, never cleared)
 	if (dec_grow(d->d_dirty, d->dirty_cap, (nwords + 1) * 4)) return -1;
-	A.dirty = d->d_dirty;
-	d->dep_split = false;
-	if (ndirty_out) *ndirty_out = (uint32_t)nwords;
-	else DCK(hipMemsetAsync(d->d_dirty, 0, nwords * 4, s));
+	A.dirty = d->d_dirty; d->dep_split = false;
+	if (clear) DCK(hipMemsetAsync(d->d_dirty, 0, nwords * 4, s));
 	return 0;
 }
 
 static int decode_launch(agmv_hip_ctx* c, DecArgs A, uint32_t g0, uint32_t g1, hipStream_t s)   // GOPs [g0, g1) of the batch
 {
-	A.grp0 = g0;
-	A.n_items = (g1 - g0) * A.tpf;
+	A.grp0 = g0; A.n_items = (g1 - g0) * A.tpf;
 	uint32_t nwg = A.n_items;
 	if (const char* e = getenv("AGMV_DEC_GRID")) {             // tuning / test aid: at most n workgroups, each looping over its items
 		const long n = atol(e);
 		if (n > 0 && (unsigned long)n < nwg) nwg = (uint32_t)n;
 	}
-	const dim3 grid(nwg);
-	const int m512 = dec_mode512(c);
-	if (nwg < A.n_items) {                                     // k_decode<mode512, bitmap form, looping>
-		if (A.vm) DEC_LAUNCH(k_decode, m512, grid, dim3(DEC_T), s, A, true, true); else DEC_LAUNCH(k_decode, m512, grid, dim3(DEC_T), s, A, false, true);
-	} else {
-		if (A.vm) DEC_LAUNCH(k_decode, m512, grid, dim3(DEC_T), s, A, true, false); else DEC_LAUNCH(k_decode, m512, grid, dim3(DEC_T), s, A, false, false);
-	}
+	DEC_LAUNCH(k_decode, dim3(nwg), dim3(DEC_T), s, A, dec_mode512(c), A.vm != nullptr, nwg < A.n_items);   // <mode512, bitmap form, looping>
 	return 0;
 }
 
 static int fixup_launch(agmv_hip_ctx* c, const DecArgs& A, hipStream_t s)
 {
-	const dim3 grid((A.nblk + 63) / 64);
-	DEC_LAUNCH_BM(k_fixup, dec_mode512(c), A.vm, grid, dim3(64), s, A);
+	DEC_LAUNCH(k_fixup, dim3((A.nblk + 63) / 64), dim3(64), s, A, dec_mode512(c), A.vm != nullptr);   // <mode512, bitmap form>
 	return 0;
 }
 
@@ -1811,8 +1810,10 @@ extern "C" int agmv_hip_decode_frames_dev(agmv_hip_ctx* c, const uint8_t* d_bits
 	if (agmv_hip_internal_check_geometry(w, h)) return -1;
 	if (n_frames == 0) return 0;
 	hipStream_t s = (hipStream_t)stream;
+	const DecRows r = {d_bits, stride, d_bpos, const_cast<uint32_t*>(d_offsets), const_cast<uint32_t*>(d_nentered), n_frames, (w / 4) * (h / 4)};   // (only read: no parser runs here)
+	const DecPix px = {w, h, first_fc, d_out, d_prev, d_prev_iframe};
 	DecArgs A;
-	if (decode_prepare(c, A, d_bits, stride, d_bpos, d_offsets, d_nentered, n_frames, w, h, first_fc, d_out, d_prev, d_prev_iframe, s)) return -1;
+	if (decode_prepare(c, A, r, px, s, true)) return -1;
 	agmv_hip_internal_ev_mark(c, 4, s);
 	if (decode_launch(c, A, 0, A.n_groups, s)) return -1;
 	if (fixup_launch(c, A, s)) return -1;
@@ -1833,8 +1834,10 @@ extern "C" int agmv_hip_parse_decode_frames_dev(agmv_hip_ctx* c, const uint8_t* 
 	if (agmv_hip_internal_check_geometry(w, h)) return -1;
 	if (n_frames == 0) return 0;
 	hipStream_t s = (hipStream_t)stream;
+	const DecRows r = {d_bits, stride, d_bpos, d_offsets, d_nentered, n_frames, (w / 4) * (h / 4)};
+	const DecPix px = {w, h, first_fc, d_out, d_prev, d_prev_iframe};
 	DecArgs A;
-	if (decode_prepare(c, A, d_bits, stride, d_bpos, d_offsets, d_nentered, n_frames, w, h, first_fc, d_out, d_prev, d_prev_iframe, s)) return -1;
+	if (decode_prepare(c, A, r, px, s, true)) return -1;
 	uint32_t nsl = 1;
 	if (getenv("AGMV_DEC_SLICES")) nsl = (uint32_t)atoi(getenv("AGMV_DEC_SLICES"));
 	if (nsl > A.n_groups) nsl = A.n_groups;
@@ -1845,7 +1848,7 @@ extern "C" int agmv_hip_parse_decode_frames_dev(agmv_hip_ctx* c, const uint8_t* 
 	const size_t ws_frames = (size_t)gps * 4;
 	agmv_hip_internal_ev_mark(c, 6, s);
 	if (nsl == 1) {
-		if (parse_launch(c, d_bits, stride, d_bpos, n_frames, A.nblk, d_offsets, d_nentered, n_frames, s)) return -1;
+		if (parse_launch(c, r, n_frames, s, nullptr)) return -1;
 		if (decode_launch(c, A, 0, A.n_groups, s)) return -1;
 	} else {
 		dec_ws* d = dec_area(c);
@@ -1859,9 +1862,7 @@ extern "C" int agmv_hip_parse_decode_frames_dev(agmv_hip_ctx* c, const uint8_t* 
 		uint32_t k = 0;
 		for (uint32_t g0 = 0; g0 < A.n_groups; g0 += gps, k++) {
 			const uint32_t g1 = g0 + gps < A.n_groups ? g0 + gps : A.n_groups;
-			const uint32_t f0 = first_frame(g0), f1 = first_frame(g1);
-			if (parse_launch(c, d_bits + (size_t)f0 * stride, stride, d_bpos + f0, f1 - f0, A.nblk, d_offsets + (size_t)f0 * A.nblk,
-			                 d_nentered + f0, ws_frames, d->aux_stream)) return -1;
+			if (parse_launch(c, rows_range(r, first_frame(g0), first_frame(g1)), ws_frames, d->aux_stream, nullptr)) return -1;
 			DCK(hipEventRecord(d->ev_slice[k], d->aux_stream));
 			DCK(hipStreamWaitEvent(s, d->ev_slice[k], 0));
 			if (decode_launch(c, A, g0, g1, s)) return -1;
@@ -1890,23 +1891,22 @@ extern "C" int agmv_hip_decode_bitstreams_dev(agmv_hip_ctx* c, const uint8_t* d_
 		if (dec_grow(d->d_nent_own, d->nent_cap, (size_t)n_frames * 4)) return -1;
 		d_nentered = d->d_nent_own;
 	}
+	const DecRows all = {d_bits, stride, d_bpos, nullptr, d_nentered, n_frames, (w / 4) * (h / 4)};
 	const size_t npx = (size_t)w * h;
 	constexpr uint32_t PART = 65532u;                          // a multiple of 4
 	agmv_hip_internal_ev_mark(c, 6, s);
 	for (uint32_t f0 = 0; f0 < n_frames;) {
 		uint32_t f1 = n_frames;
 		if (f1 - f0 > PART) { f1 = f0 + PART; f1 -= (first_fc + f1) & 3u; }   // the next part starts with an I-frame
-		const uint32_t n = f1 - f0, fc = first_fc + f0;
+		const DecRows r = rows_range(all, f0, f1);
 		// state before frame f0: the frame before it, and the snapshot taken at the last I-frame (the decoded I-frame itself, :401-405)
-		const uint32_t* prev = f0 == 0 ? d_prev : d_out + (size_t)(f0 - 1) * npx;
-		const uint32_t* previ = f0 == 0 ? d_prev_iframe : d_out + (size_t)(f0 - 4) * npx;
+		const DecPix px = {w, h, first_fc + f0, d_out + (size_t)f0 * npx, f0 == 0 ? d_prev : d_out + (size_t)(f0 - 1) * npx,
+		                   f0 == 0 ? d_prev_iframe : d_out + (size_t)(f0 - 4) * npx};
 		DecArgs A;
-		uint32_t ndirty = 0;
-		if (decode_prepare(c, A, d_bits + (size_t)f0 * stride, stride, d_bpos + f0, nullptr, d_nentered + f0, n, w, h, fc, d_out + (size_t)f0 * npx, prev, previ, s, &ndirty)) return -1;
+		if (decode_prepare(c, A, r, px, s, false)) return -1;
 		agmv_hip_internal_ev_mark(c, 2, s);
-		if (parse_launch(c, d_bits + (size_t)f0 * stride, stride, d_bpos + f0, n, A.nblk, nullptr, d_nentered + f0, n, s, true, A.dirty, ndirty)) return -1;
+		if (parse_launch(c, r, r.n_frames, s, &A)) return -1;   // fills in A.vm, A.kb, A.tidx, A.maxR
 		agmv_hip_internal_ev_mark(c, 3, s);
-		A.vm = d->fp_vm; A.kb = d->fp_kb; A.tidx = d->fp_tidx; A.maxR = d->fp_maxR;
 		agmv_hip_internal_ev_mark(c, 4, s);
 		if (decode_launch(c, A, 0, A.n_groups, s)) return -1;
 		if (fixup_launch(c, A, s)) return -1;

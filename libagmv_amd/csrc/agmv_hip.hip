@@ -374,7 +374,7 @@ __device__ __forceinline__ uint32_t lookback(unsigned long long* st, int tile, i
 }
 
 constexpr int WBLK = 64;                                       // blocks per wave = slice of the workgroup tile
-constexpr size_t CTRL_BYTES = 1024;                            // dwords: [0] ticket, [1] error, [32..42] phase stamps (ENC_PROF builds), the rest: lab builds
+constexpr size_t CTRL_BYTES = 1024;                            // dwords: [0] ticket, [1] error; the rest is spare here (the experiment builds kept as patches under profiles/ use [32..42])
 
 // K1.  Barrier-free dataflow form.  One workgroup = one tile of ENC_T consecutive 4x4 blocks (ENC_WAVES waves x 64
 // blocks), one lane = one block for classification/emission, carried through the <=4 frames of its GOP.  The stream of
@@ -671,14 +671,6 @@ __global__ __launch_bounds__(ENC_T, ENC_WPE) void k_encode(EncArgs A)
 	int p_f = 0;
 	unsigned long long pre_next = ST_PREFIX;                   // the status window the NEXT item's duty wave will look back through
 
-#ifdef ENC_PROF
-	uint32_t prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-	unsigned long long pt = __builtin_amdgcn_s_memtime();
-#define PSTAMP(k) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); prof[k] += (uint32_t)(n_ - pt); pt = n_; } while (0)
-#else
-#define PSTAMP(k) do { } while (0)
-#endif
-	uint32_t prof_sink = 0; (void)prof_sink;
 	auto body = [&](px4 (&px)[4]) -> bool {                 // one item: consumes px and refills it with the item ENC_PFDEPTH ahead
 		EncGeo& g = cur.g;
 		const int f = cur.f;
@@ -726,7 +718,6 @@ __global__ __launch_bounds__(ENC_T, ENC_WPE) void k_encode(EncArgs A)
 			asm volatile("" ::: "memory");
 			if (p_len == 0) return;
 			const uint32_t base = __builtin_amdgcn_readfirstlane(lds_ld(gb));
-			PSTAMP(6);
 			wave_copy_own_u(s_stage0 + (((it - 1) & 1) * ENC_WAVES + wave) * WSLOT, A.out + (size_t)p_f * A.out_stride + base, p_len, lane);
 		};
 
@@ -759,12 +750,6 @@ __global__ __launch_bounds__(ENC_T, ENC_WPE) void k_encode(EncArgs A)
 			publish_ticket();
 			if (pf.have) { load_frame(pf.g, A.pix + (size_t)pf.f * npx, px); advance(pf, true); }
 		};
-#ifdef ENC_PROF
-		PSTAMP(9);                                             // loop top: bookkeeping, duty status prefetch, I-frame entry plane
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		PSTAMP(8);                                             // wait for this item's pixels
-		prof[10]++;
-#endif
 #if ENC_PRIO
 		__builtin_amdgcn_s_setprio(ENC_PRIO);
 #endif
@@ -780,11 +765,9 @@ __global__ __launch_bounds__(ENC_T, ENC_WPE) void k_encode(EncArgs A)
 			if (ENTRIES) eq[k] = pxv[k] & (M512 ? 0x1FFu : 0xFFu);
 			else eq[k] = (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(lut_rs, lut_offset(pxv[k]), 0, ENC_LUTAUX);
 		}
-		PSTAMP(0);
 #if ENC_PRIO
 		__builtin_amdgcn_s_setprio(0);
 #endif
-		PSTAMP(2);
 		// [block][pixel] u16 table in the wave's scratch; a lane writes its row: 8 bytes at i*512 + lane*8
 #pragma unroll
 		for (int i = 0; i < 4; i++) {
@@ -793,9 +776,7 @@ __global__ __launch_bounds__(ENC_T, ENC_WPE) void k_encode(EncArgs A)
 			q.y = eq[i * 4 + 2] | (eq[i * 4 + 3] << 16);
 			*(uint2*)(scratch + i * 512 + lane * 8) = q;
 		}
-		PSTAMP(1);
 		if (duty) resolve_prev();
-		PSTAMP(3);
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 		__builtin_amdgcn_wave_barrier();
 		// ---- transpose: lane = block reads its 16 entries (32 contiguous bytes), kept PACKED two per register
@@ -855,7 +836,6 @@ __global__ __launch_bounds__(ENC_T, ENC_WPE) void k_encode(EncArgs A)
 				lds_st(&s_ctl[C_TTOTAL + slot], (tag << 16) | total);
 			}
 		}
-		PSTAMP(4);
 		// ---- (E) emit this block's bytes into the wave's stage slot
 		// Codes are built two at a time in packed 16-bit lanes and written as {code, index} byte PAIRS at byte-granular
 		// LDS addresses (gfx950 runs DS in unaligned mode): when an entry has no escape byte its pair's second byte is
@@ -894,10 +874,8 @@ __global__ __launch_bounds__(ENC_T, ENC_WPE) void k_encode(EncArgs A)
 			asm volatile("" ::: "memory");
 			sp[0] = copy ? COPY_FLAG : (fill ? FILL_FLAG : NORMAL_FLAG);
 		}
-		PSTAMP(5);
 		if (have_prev) copy_out_prev();
 		prefetch_next();                                       // LAST in the item: any later wait of the item (the compiler places conservative ones at branch joins) would drain these loads -- requested right behind the entries they measured 0.98 against 0.72 ms per 256 frames
-		PSTAMP(7);
 
 		// ---- next item
 		have_prev = true; p_tile = g.tile; p_f = f; p_len = wtot;
@@ -913,15 +891,7 @@ __global__ __launch_bounds__(ENC_T, ENC_WPE) void k_encode(EncArgs A)
 			if (!body(pxs[d])) goto done;
 	}
 done:;
-#ifdef ENC_PROF
-	if (lane == 0)
-		for (int k = 0; k < 11; k++) atomicAdd(A.ctrl + 32 + k, k == 10 ? prof[k] : prof[k] >> 6);
-#endif
 }
-
-#ifdef AGMV_LAB_ENCODE_W
-#include "lab/k_encode_w.inc"   // the independent-wave form of k_encode (measured slower; profiles/r03/k_encode_experiments.txt)
-#endif
 
 // A spin of k_encode that ran into its bound leaves ctrl[1] != 0 and the kernel carries on with a wrong offset: the bytes of
 // the batch are not to be used.  So that a caller who skips agmv_hip_check cannot take them for good ones, every size of
@@ -1212,13 +1182,7 @@ static int encode_dev(agmv_hip_ctx* c, const uint32_t* d_pix, uint32_t n_frames,
 	A.pix = d_pix; A.out = d_out; A.sizes = d_sizes; A.lut = c->d_lut; A.mtx = c->d_mtx; A.ientries_in = d_ientries; A.ientries_out = d_ientries;
 	A.out_stride = out_stride;
 	A.n_frames = n_frames; A.w = w; A.h = h; A.bw = w / 4; A.nblk = (w / 4) * (h / 4);
-#ifdef AGMV_LAB_ENCODE_W
-	const char* ek = getenv("AGMV_ENC_KERNEL");                // lab build only: the independent-wave form (lab/k_encode_w.inc)
-	const bool wform = ek && strcmp(ek, "w") == 0;
-#else
-	constexpr bool wform = false;
-#endif
-	A.tpf = wform ? (A.nblk + WBLK - 1) / WBLK : (A.nblk + ENC_T - 1) / ENC_T;   // tiles of ENC_T blocks per frame
+	A.tpf = (A.nblk + ENC_T - 1) / ENC_T;   // tiles of ENC_T blocks per frame
 	A.first_fc = first_fc; A.phase = first_fc & 3u;
 	A.n_groups = (n_frames + A.phase + 3) / 4;
 	A.total_tiles = A.n_groups * A.tpf;
@@ -1257,18 +1221,10 @@ static int encode_dev(agmv_hip_ctx* c, const uint32_t* d_pix, uint32_t n_frames,
 	CK(hipMemsetAsync(c->d_status, 0, need * sizeof(unsigned long long), s));
 	CK(hipMemsetAsync(c->d_ctrl, 0, CTRL_BYTES, s));
 	uint32_t grid = (uint32_t)c->enc_grid;
-	const uint32_t work = wform ? (A.total_tiles + ENC_WAVES - 1) / ENC_WAVES : A.total_tiles;
-	if (grid > work) grid = work;
-	size_t lds = (size_t)(c->mode512 ? 512 : 256) * MROW * 4 + ENC_LDS_EXTRA;
+	if (grid > A.total_tiles) grid = A.total_tiles;
+	const size_t lds = (size_t)(c->mode512 ? 512 : 256) * MROW * 4 + ENC_LDS_EXTRA;
 	void (*kern)(EncArgs) = c->mode512 ? (entries ? k_encode<true, true> : k_encode<true, false>)
 	                                   : (entries ? k_encode<false, true> : k_encode<false, false>);
-#ifdef AGMV_LAB_ENCODE_W
-	if (wform) {
-		lds = (size_t)(c->mode512 ? 512 : 256) * MROW * 4 + ENCW_LDS_EXTRA;
-		kern = c->mode512 ? (entries ? k_encode_w<true, true> : k_encode_w<true, false>)
-		                  : (entries ? k_encode_w<false, true> : k_encode_w<false, false>);
-	}
-#endif
 	CK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 	agmv_hip_internal_ev_mark(c, 0, s);
 	hipLaunchKernelGGL(kern, dim3(grid), dim3(ENC_T), lds, s, A);
@@ -1302,19 +1258,6 @@ extern "C" int agmv_hip_check(agmv_hip_ctx* c, void* stream)
 	uint32_t ctrl[4] = {0, 0, 0, 0};
 	CK(hipStreamSynchronize((hipStream_t)stream));
 	CK(hipMemcpy(ctrl, c->d_ctrl, 16, hipMemcpyDeviceToHost));
-#ifdef ENC_PROF
-	{
-		uint32_t pr[12];
-		CK(hipMemcpy(pr, c->d_ctrl + 32, 44, hipMemcpyDeviceToHost));
-		double tot = 0;
-		for (int k = 0; k < 10; k++) tot += pr[k];
-		const double per = 64.0 / (pr[10] ? pr[10] : 1);        // shader cycles per item of ONE wave (the counters hold cycles / 64 summed over the waves)
-		fprintf(stderr, "k_encode phases, cycles per wave-item (%% of wave time): loop top %.0f (%.1f) | pixel wait %.0f (%.1f) | look-up issue %.0f (%.1f) | prefetch issue + ticket %.0f (%.1f) | "
-		        "look-up wait + park %.0f (%.1f) | duty %.0f (%.1f) | transpose + classify + scan %.0f (%.1f) | emit %.0f (%.1f) | wait for gbase %.0f (%.1f) | copy-out %.0f (%.1f) | total %.0f, %u wave-items\n",
-		        pr[9] * per, 100 * pr[9] / tot, pr[8] * per, 100 * pr[8] / tot, pr[0] * per, 100 * pr[0] / tot, pr[2] * per, 100 * pr[2] / tot, pr[1] * per, 100 * pr[1] / tot,
-		        pr[3] * per, 100 * pr[3] / tot, pr[4] * per, 100 * pr[4] / tot, pr[5] * per, 100 * pr[5] / tot, pr[6] * per, 100 * pr[6] / tot, pr[7] * per, 100 * pr[7] / tot, tot * per, pr[10]);
-	}
-#endif
 	if (ctrl[1]) { snprintf(g_err, sizeof(g_err), "agmv_hip: look-back timed out inside k_encode (device error word %u)", ctrl[1]); return -2; }
 	return 0;
 }
