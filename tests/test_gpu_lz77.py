@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import lz77_cases as Z
-from lz77_cases import SEG, bitstream_like, gpu_batch77, host77, orc77, same, tokens77, zeros_closed_form
+from lz77_cases import SEG, bitstream_like, gpu_batch77, host77, orc77, same, token_starting_at, tokens77, zeros_closed_form
 
 pytestmark = pytest.mark.gpu
 
@@ -112,11 +112,7 @@ def test_window_edge_repeat(hip, dist):
     x[dist - 1] = 250                                                # occurs nowhere before: the next byte starts a token
     got = hip.lz77_frames([x])[0]
     assert same(got, host77(x))
-    at, hit = 0, None
-    for t in tokens77(got):
-        if at == dist:
-            hit = t
-        at += t[1] + 1
+    hit = token_starting_at(got, dist)
     assert hit is not None, "position %d is not a token start" % dist
     if dist == 65535:
         assert hit == (65535, 40, 251)
@@ -134,12 +130,7 @@ def test_window_edge_single_byte(hip, dist):
     x[1:dist][x[1:dist] == 222] = 0
     got = hip.lz77_frames([x])[0]
     assert same(got, host77(x))
-    tk = tokens77(got)
-    at, hit = 0, None
-    for t in tk:
-        if at == dist:
-            hit = t
-        at += t[1] + 1
+    hit = token_starting_at(got, dist)
     assert hit is not None, "position %d is not a token start" % dist
     assert hit == ((65535, 1, 251) if dist == 65535 else (0, 0, 222))
 
