@@ -511,6 +511,48 @@ typedef enum AGMV_PCMFMT { AGMV_PCM_S16 = 1, AGMV_PCM_U8 = 2, AGMV_PCM_F32P = 3 
 int AGMV_SetAudioDev(const void* d_pcm, AGMV_PCMFMT fmt, u32 samples_per_channel, u32 sample_rate, u16 channels);
 int AGMV_DecodeAudioDev(const char* filename, void* d_pcm, AGMV_PCMFMT fmt, u32 cap_samples, AGMV_INFO* info);
 
+/* Measuring a decoded clip: what a lossy knob (the quality level, the palette refinement, the dither, a scale) did to the pixels,
+   computed where the frames are.  Two clips of n frames of w x h pixels, w and h multiples of 4: the TEST clip is packed XRGB32
+   (what the decoder produces; bits >= 24 are ignored), the REFERENCE clip is in any AGMV_PIXFMT layout, YUV flags included; a YUV
+   reference is compared as the XRGB32 clip it stands for by the reading rule above.  Per frame and per channel c (0 = R, 1 = G,
+   2 = B), with a the test channel and b the reference channel of a pixel:
+     sse[c]        the sum over the pixels of (a - b)^2
+     block_sse[c]  the sum over the 4x4 blocks of the codec's grid of (sum of a over the block - sum of b over the block)^2: 256
+                   times the squared error of the block means
+     max_err[c]    the largest |a - b|
+     ssim[c]       the sum over the windows of the window's SSIM in Q20, signed
+   A window is 2 x 2 blocks (8 x 8 pixels) at every block position (bx, by) with bx < w/4 - 1 and by < h/4 - 1: overlapping windows at
+   stride 4, (w/4 - 1) * (h/4 - 1) per frame, none when w = 4 or h = 4.  Over the 64 pixels of a window
+     s1 = sum a    s2 = sum b    ss = sum a^2 + sum b^2    s12 = sum a*b
+     vars = 64 * ss - s1^2 - s2^2                cov = 64 * s12 - s1 * s2
+     num = (2 * s1 * s2 + C1) * (2 * cov + C2)     den = (s1^2 + s2^2 + C1) * (vars + C2)
+     C1 = 26634 = floor(0.01^2 * 255^2 * 64^2 + 0.5)       C2 = 235963 = floor(0.03^2 * 255^2 * 64 * 63 + 0.5)
+   and the window's value is floor(num * 2^20 / den), the floor towards minus infinity.  den > 0 and |num| <= den < 2^58, so 20
+   shift-and-subtract steps on 64-bit magnitudes give the quotient, and for a negative num the value is -q - (remainder != 0).
+   Equal windows give exactly 2^20.  Everything is integer: the sums do not depend on the order of accumulation, and the same
+   clips give the same words from run to run.  PSNR and the mean SSIM are the caller's to form: over a set of frames and channels
+   PSNR = 10 * log10(255^2 * pixels * channels / sum of sse), mean SSIM = sum of ssim / 2^20 / (windows * channels).
+   AGMV_MeasureFramesDev measures two clips in the memory of the library's device (agmv_hip_measure_frames_async of
+   include/agmv_hip.h is the kernel) into `quality`, host memory of num_of_frames entries.  Returns 0, or a negative value before a
+   device is opened: -1 NULL pointer or unknown format, -3 width or height zero, not a multiple of 4, more than 2^28 pixels, or more than 2^31 - 1 frames.
+   num_of_frames == 0 is 0 and touches nothing.  A GPU failure aborts with a message, as in the encoders.
+   AGMV_MeasureFileDev decodes the file and measures frame k of it against frame k of the reference clip d_ref (num_of_frames
+   frames of the file's size in the layout ref_fmt), batch by batch, without ever holding the decoded clip: a batch is decoded
+   into the decoder's double buffer, measured there, and its entries are downloaded once at the end.  Returns the number of
+   frames measured; entries behind that number are not written.  *info (may be NULL) receives the header's AGMV_INFO; with
+   `quality` NULL nothing else happens and the return is 0.  Negative returns: -1 unknown format or NULL d_ref, -3 num_of_frames
+   differs from the header's count or the file's size cannot hold the layout (odd width or height for YUV), else an Error,
+   negated.  File and clip correspond frame for frame when the file was written with AGMV_SCHEDULE_FULL; the other schedules
+   drop frames, and the header's count says so. */
+typedef struct AGMV_FRAME_QUALITY {            /* 96 bytes, the same on host and device */
+	unsigned long long sse[3], block_sse[3], max_err[3];
+	long long ssim[3];
+} AGMV_FRAME_QUALITY;
+int AGMV_MeasureFramesDev(const unsigned* d_test, const void* d_ref, AGMV_PIXFMT ref_fmt, u32 num_of_frames, u32 width, u32 height,
+                          AGMV_FRAME_QUALITY* quality /* host, num_of_frames entries */);
+int AGMV_MeasureFileDev(const char* filename, const void* d_ref, AGMV_PIXFMT ref_fmt, u32 num_of_frames,
+                        AGMV_FRAME_QUALITY* quality /* host */, AGMV_INFO* info);
+
 #ifdef __cplusplus
 }
 #endif

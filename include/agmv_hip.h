@@ -455,6 +455,22 @@ int agmv_hip_audio_compand_async(agmv_hip_ctx* ctx, int pcmfmt, const void* d_pc
 int agmv_hip_audio_expand_async(agmv_hip_ctx* ctx, int pcmfmt, const uint8_t* d_codes, uint32_t channels, uint64_t samples_per_channel,
                                 void* d_pcm, void* stream);
 
+/* -- a decoded clip measured against its reference ---------------------------------------------------
+ * AGMV_FRAME_QUALITY of include/agmv.h ("measuring a decoded clip"), which holds the definition: per frame and channel the exact
+ * squared error, the squared error of the 4x4 block sums, the largest error and the sum of the integer SSIM (Q20) of the 8x8
+ * windows at stride 4.  d_test holds n_frames packed frames of w x h (bits >= 24 ignored, 4-byte aligned), d_ref the same frames
+ * in the layout `ref_fmt`: any of the seven above (1 .. 5, or 16 / 17 OR-ed with the YUV flags), at that layout's frame stride and
+ * alignment; a YUV reference is compared as the clip agmv_hip_yuv_to_xrgb_dev makes of it.  w and h are multiples of 4, w * h
+ * <= 2^28.  d_quality (8-byte aligned) receives n_frames entries of 96 bytes: 12 64-bit words sse[3], block_sse[3], max_err[3],
+ * ssim[3] (signed), channel 0 = R.  The call clears them itself on `stream`: what they held before does not matter.
+ * Asynchronous on `stream`: one memset and one launch, no allocation, no host synchronisation, nothing of the context is used
+ * but its device.  Each clip is read once (the one block row and column two tiles share, twice), the test clip and a reference
+ * whose frames start on 16-byte boundaries with 16-byte loads; no converted copy of the reference exists.  Exact and repeatable:
+ * integer sums, the same words from run to run.  Any n_frames; n_frames == 0 is success and touches nothing.  Returns non-zero
+ * with a message and launches nothing for an unknown format, a zero size, a size that is no multiple of 4 or a NULL pointer. */
+int agmv_hip_measure_frames_async(agmv_hip_ctx* ctx, const uint32_t* d_test, int ref_fmt, const void* d_ref,
+                                  uint32_t w, uint32_t h, uint32_t n_frames, void* d_quality /* n_frames * 96 bytes */, void* stream);
+
 /* optional timing: when enabled the library records HIP events on the caller's stream around its three kernel
    groups; agmv_hip_last_kernel_ms(which) returns the last launch's duration in ms (0 = k_encode, 1 = the parser
    kernels, 2 = k_decode + k_fixup, 3 = the whole of agmv_hip_parse_decode_frames_dev / agmv_hip_decode_bitstreams_dev), or a negative value if

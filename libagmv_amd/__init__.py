@@ -11,14 +11,15 @@ Layout
   csrc/*.c            host C: libagmv-compatible API (include/agmv.h), LZSS/LZ77, container,
                       BMP I/O, palette build, synthetic clip generator
   hip.py              ctypes binding of the C-ABI for tests / bench (torch = device memory only)
-  seq.py              ctypes calls of the memory-sequence entry points of include/agmv.h (.agmv file <-> CUDA tensor: five RGB layouts, NV12, I420; a scale to a target size before the encode)
+  seq.py              ctypes calls of the memory-sequence entry points of include/agmv.h (.agmv file <-> CUDA tensor: five RGB layouts, NV12, I420; a scale to a target size before the encode; a decoded clip or file measured against its reference)
   build.py            in-tree build of libagmv_hip.so / libagmv.so (hipcc, gcc)
 
 There is no CPU fallback anywhere in this package: without the built HIP library, or
 without a GPU, the hot-path calls raise.
 """
 from .hip import PCMFMT, PIXFMT, YUVFMT, AgmvHip, HipUnavailable, lib_path, load_library  # noqa: F401
-from .seq import SCALE, SCHEDULE_ADAPTIVE, SCHEDULE_FULL, SCHEDULE_PDIFS, decode_audio, decode_frames, encode_frames  # noqa: F401
+from .seq import SCALE, SCHEDULE_ADAPTIVE, SCHEDULE_FULL, SCHEDULE_PDIFS, Quality, clip_quality, decode_audio, decode_frames, encode_frames, file_quality  # noqa: F401
 
 __all__ = ["AgmvHip", "HipUnavailable", "lib_path", "load_library", "encode_frames", "decode_frames", "decode_audio",
+           "clip_quality", "file_quality", "Quality",
            "SCHEDULE_FULL", "SCHEDULE_PDIFS", "SCHEDULE_ADAPTIVE", "PIXFMT", "YUVFMT", "PCMFMT", "SCALE"]

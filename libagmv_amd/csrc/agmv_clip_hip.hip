@@ -1,5 +1,6 @@
 // libagmv_amd/csrc/agmv_clip_hip.hip -- the clip front end: what a caller does to a clip in GPU memory before it reaches
-// the codec of agmv_hip.hip (include/agmv_hip.h from "helpers on the caller side of the path" to agmv_hip_scale_area_dev).
+// the codec of agmv_hip.hip (include/agmv_hip.h from "helpers on the caller side of the path" to agmv_hip_scale_area_dev), and
+// what it asks about one that came back from it (agmv_hip_measure_frames_async).
 //
 //   k_synth / k_interp        the synthetic test clip, the PDIFS midpoint frame
 //   k_histogram*              palette histogram; hist_add_runs is the one statement of the run-length atomics
@@ -7,9 +8,10 @@
 //   k_gather*                 the nearest scale as a table look-up; gather_frames is the body of the XRGB32 and byte-layout forms
 //   k_pix_* / k_yuv_*         the byte layouts and NV12 / I420 to and from XRGB32
 //   k_scale_area              the exact box-filter downscale of a clip in any of the seven layouts
+//   k_measure                 a decoded XRGB32 clip against its reference in any of the seven layouts: SSE, block-mean SSE, SSIM
 // Each family has an XRGB32 form, one for the byte layouts (PF_RGB24 .. PF_RGB8P) and one templated on the YUV layout; on the
 // host CLIP_LAUNCH is the one place where a format value becomes a kernel's template argument.
-// Integer/byte work only; every kernel is an HBM stream.
+// Integer/byte work only; every kernel is an HBM stream, except k_measure, which its divisions and moments bind.
 #include <hip/hip_runtime.h>
 
 #include <stdarg.h>
@@ -950,6 +952,162 @@ template <int FMT> __global__ __launch_bounds__(256) void k_scale_area(ScaleArgs
 	}
 }
 
+// ---- a decoded clip measured against its reference (AGMV_FRAME_QUALITY of include/agmv.h, which holds the definition) ----
+// The test clip is XRGB32, the reference in any of the seven layouts.  A workgroup owns one (frame, tile of MS_TW x MS_TH blocks) at
+// a time, plus one block row below and one block column to the right of it, which only its windows use.  First a lane takes four
+// neighbouring blocks of one block row (16 x 4 pixels): per pixel row 16 test pixels and 16 reference pixels -- four 16-byte
+// loads of the test clip and the loads of sc_group<FMT> where the clip's frames start on 16-byte boundaries and (for the 3-byte
+// and planar layouts) the 16 pixels start at a multiple of 16 of the frame's pixel index; the tile's one extra column, the tail
+// of a row whose width is no multiple of 16 and every pixel of any other clip go through sc_read<FMT> -- and folds the five
+// moments sum a, sum b, sum a^2, sum b^2, sum ab of each block and channel in registers, then stores the block's 15 dwords in LDS
+// (each block of the tile has one writer).  After the barrier a lane takes owned blocks: a block's moments give its part of sse
+// (sum a^2 + sum b^2 - 2 sum ab) and of block_sse, the moments of the 2 x 2 blocks at (bx, by) give one window, whose value is one
+// Q20 division by 20 shift-and-subtract steps per channel.  The lane's sums go through the wave (__shfl_xor), then one 64-bit LDS
+// atomic per wave and value, and the workgroup issues one 64-bit global atomic per value into the frame's entry.  All integer:
+// any order of the adds gives the same sums.  Items are walked with a grid stride: any number of frames.
+#define MS_TW 32
+#define MS_TH 18
+#define MS_NQ (MS_TW / 4 + 1)                                   // groups of four blocks per block row of a tile, the extra column included
+#define MS_C1 26634ull                                          // floor(0.01^2 * 255^2 * 64^2 + 0.5)
+#define MS_C2 235963ll                                          // floor(0.03^2 * 255^2 * 64 * 63 + 0.5)
+
+struct MeasureArgs {
+	const uint32_t* test;
+	const uint8_t* ref;
+	unsigned long long* out;                                       // [n_frames][12]: sse, block_sse, max_err, ssim, three channels each
+	size_t frame_bytes;                                            // of the reference
+	unsigned long long items;                                      // n_frames * tx * ty
+	uint32_t w, h, tx, ty;
+	int t_vec, wide;                                               // 16-byte loads allowed on the test clip, on the reference
+	yuv_rd m;
+};
+
+// the SSIM of one window of 64 pixels in Q20, floor towards minus infinity: s1 = sum a, s2 = sum b, ss = sum a^2 + sum b^2,
+// s12 = sum ab.  den > 0, |num| <= den < 2^58: the remainder stays below 2^59
+__device__ __forceinline__ long long ms_ssim_q20(uint32_t s1, uint32_t s2, uint32_t ss, uint32_t s12)
+{
+	const unsigned long long p11 = (unsigned long long)s1 * s1, p22 = (unsigned long long)s2 * s2, p12 = (unsigned long long)s1 * s2;
+	const long long vars = (long long)(64ull * ss) - (long long)p11 - (long long)p22, cov = (long long)(64ull * s12) - (long long)p12;
+	const long long t = 2 * cov + MS_C2;                            // carries the sign of num
+	const unsigned long long den = (p11 + p22 + MS_C1) * (unsigned long long)(vars + MS_C2);
+	const unsigned long long mag = (2 * p12 + MS_C1) * (unsigned long long)(t < 0 ? -t : t);
+	unsigned long long q = mag >= den ? 1 : 0, r = mag - (q ? den : 0);
+	for (int k = 0; k < 20; k++) {
+		r <<= 1; q <<= 1;
+		if (r >= den) { r -= den; q |= 1; }
+	}
+	return t < 0 ? -(long long)q - (r != 0) : (long long)q;
+}
+
+__device__ __forceinline__ unsigned long long ms_wave_sum(unsigned long long v)
+{
+	for (int d = 32; d; d >>= 1) {
+		const uint32_t lo = __shfl_xor((uint32_t)v, d, 64), hi = __shfl_xor((uint32_t)(v >> 32), d, 64);
+		v += (unsigned long long)hi << 32 | lo;
+	}
+	return v;
+}
+
+template <int FMT> __global__ __launch_bounds__(256) void k_measure(MeasureArgs A)
+{
+	__shared__ uint32_t s_mom[MS_TH + 1][MS_TW + 1][15];              // per block and channel c: [5c] sum a, sum b, sum a^2, sum b^2, sum ab
+	__shared__ unsigned long long s_red[12];
+	const uint32_t w = A.w, h = A.h, bw = w >> 2, bh = h >> 2, per = A.tx * A.ty;
+	const size_t npx = (size_t)w * h;
+	if (threadIdx.x < 12) s_red[threadIdx.x] = 0;
+	for (unsigned long long item = blockIdx.x; item < A.items; item += gridDim.x) {
+		const uint32_t f = (uint32_t)(item / per), rem = (uint32_t)(item - (unsigned long long)f * per), ty = rem / A.tx, bx0 = (rem - ty * A.tx) * MS_TW, by0 = ty * MS_TH;
+		const uint32_t nbx = min((uint32_t)MS_TW + 1, bw - bx0), nby = min((uint32_t)MS_TH + 1, bh - by0);     // the tile's blocks, the extra ones included
+		const uint32_t* tf = A.test + (size_t)f * npx;
+		const uint8_t* rf = A.ref + (size_t)f * A.frame_bytes;
+		uint32_t mx[3] = { 0, 0, 0 };                              // (the extra blocks are pixels of the frame too: a maximum may count them twice)
+		for (uint32_t task = threadIdx.x; task < nby * MS_NQ; task += 256) {
+			const uint32_t jr = task / MS_NQ, qd = task - jr * MS_NQ;
+			if (4 * qd >= nbx) continue;
+			const uint32_t nb = min(4u, nbx - 4 * qd), x0 = (bx0 + 4 * qd) * 4;
+			uint32_t acc[4][15];
+#pragma unroll
+			for (int q = 0; q < 4; q++)
+#pragma unroll
+				for (int k = 0; k < 15; k++) acc[q][k] = 0;
+			for (uint32_t r = 0; r < 4; r++) {
+				const uint32_t j = (by0 + jr) * 4 + r, p = j * w + x0;
+				uint32_t ta[16], rb[16];                           // blocks the tile does not have read as 0 on both sides
+				if (A.t_vec && nb == 4) {
+					sc_group<PF_XRGB32> g;
+					g.load(reinterpret_cast<const uint8_t*>(tf), w, h, p, j);
+#pragma unroll
+					for (int i = 0; i < 16; i++) ta[i] = g.pixel(i, A.m);
+				} else {
+#pragma unroll
+					for (int i = 0; i < 16; i++) ta[i] = (uint32_t)(i >> 2) < nb ? tf[p + i] & 0xffffffu : 0u;
+				}
+				if (A.wide && nb == 4 && (sc_group<FMT>::NV == 4 || (p & 15) == 0)) {
+					sc_group<FMT> g;
+					g.load(rf, w, h, p, j);
+#pragma unroll
+					for (int i = 0; i < 16; i++) rb[i] = g.pixel(i, A.m);
+				} else {
+#pragma unroll
+					for (int i = 0; i < 16; i++) rb[i] = (uint32_t)(i >> 2) < nb ? sc_read<FMT>(rf, w, h, x0 + i, j, A.m) : 0u;
+				}
+#pragma unroll
+				for (int i = 0; i < 16; i++)
+#pragma unroll
+					for (int c = 0; c < 3; c++) {
+						const uint32_t a = (ta[i] >> (16 - 8 * c)) & 0xff, b = (rb[i] >> (16 - 8 * c)) & 0xff;
+						uint32_t* m = &acc[i >> 2][5 * c];
+						m[0] += a; m[1] += b; m[2] += a * a; m[3] += b * b; m[4] += a * b;
+						mx[c] = max(mx[c], a > b ? a - b : b - a);
+					}
+			}
+#pragma unroll
+			for (int q = 0; q < 4; q++) if ((uint32_t)q < nb) {
+#pragma unroll
+				for (int k = 0; k < 15; k++) s_mom[jr][4 * qd + q][k] = acc[q][k];
+			}
+		}
+		__syncthreads();
+		unsigned long long sse[3] = { 0, 0, 0 }, bsse[3] = { 0, 0, 0 }, ssim[3] = { 0, 0, 0 };
+		const uint32_t own_x = min((uint32_t)MS_TW, bw - bx0), own_y = min((uint32_t)MS_TH, bh - by0);
+		for (uint32_t k = threadIdx.x; k < own_y * MS_TW; k += 256) {
+			const uint32_t ly = k / MS_TW, lx = k - ly * MS_TW;
+			if (lx >= own_x) continue;
+			const bool win = bx0 + lx + 1 < bw && by0 + ly + 1 < bh;
+#pragma unroll
+			for (int c = 0; c < 3; c++) {
+				const uint32_t* m = &s_mom[ly][lx][5 * c];
+				const int d = (int)m[0] - (int)m[1];
+				sse[c] += m[2] + m[3] - 2 * m[4];
+				bsse[c] += (uint32_t)(d * d);
+				if (win) {
+					const uint32_t *m1 = &s_mom[ly][lx + 1][5 * c], *m2 = &s_mom[ly + 1][lx][5 * c], *m3 = &s_mom[ly + 1][lx + 1][5 * c];
+					ssim[c] += (unsigned long long)ms_ssim_q20(m[0] + m1[0] + m2[0] + m3[0], m[1] + m1[1] + m2[1] + m3[1],
+					                                           m[2] + m1[2] + m2[2] + m3[2] + m[3] + m1[3] + m2[3] + m3[3], m[4] + m1[4] + m2[4] + m3[4]);
+				}
+			}
+		}
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			sse[c] = ms_wave_sum(sse[c]); bsse[c] = ms_wave_sum(bsse[c]); ssim[c] = ms_wave_sum(ssim[c]);
+			for (int d = 32; d; d >>= 1) mx[c] = max(mx[c], (uint32_t)__shfl_xor(mx[c], d, 64));
+		}
+		if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+			for (int c = 0; c < 3; c++) {
+				atomicAdd(&s_red[c], sse[c]); atomicAdd(&s_red[3 + c], bsse[c]); atomicMax(&s_red[6 + c], (unsigned long long)mx[c]); atomicAdd(&s_red[9 + c], ssim[c]);
+			}
+		}
+		__syncthreads();
+		if (threadIdx.x < 12) {                                    // one global atomic per value; the signed sums add as their two's complement
+			const unsigned long long v = s_red[threadIdx.x];
+			unsigned long long* o = A.out + (size_t)f * 12 + threadIdx.x;
+			s_red[threadIdx.x] = 0;
+			if (v) { if (threadIdx.x >= 6 && threadIdx.x < 9) atomicMax(o, v); else atomicAdd(o, v); }
+		}
+	}
+}
+
 // ----------------------------------------------------------------------------------------------
 // host side.  fmt is an AGMV_PIXFMT: 1 .. 5 the byte layouts, 16 (NV12) or 17 (I420), | 0x100 for BT.709, | 0x200 for full range
 // ----------------------------------------------------------------------------------------------
@@ -1282,6 +1440,32 @@ extern "C" int agmv_hip_scale_area_dev(agmv_hip_ctx* c, int fmt, const void* d_s
 	A.small = (unsigned long long)src_w * dst_w < (1ull << 32);
 	A.m = YUV_RD[(fmt >> 8) & 3];
 	CLIP_LAUNCH(PF_BYTES | PF_YUV | PF_BIT(PF_XRGB32), k_scale_area, (unsigned)(A.items < 65536 ? A.items : 65536), A);
+	CCK(hipGetLastError());
+	return 0;
+}
+
+// ---- a decoded clip measured against its reference (AGMV_FRAME_QUALITY) ----
+extern "C" int agmv_hip_measure_frames_async(agmv_hip_ctx* c, const uint32_t* d_test, int fmt, const void* d_ref, uint32_t w, uint32_t h, uint32_t n_frames,
+                                             void* d_quality, void* stream)
+{
+	if (need_clip_ctx(c)) return -1;
+	const int yuv = yuv_base(fmt);
+	if (yuv ? bad_yuv(fmt, w, h) : bad_pixfmt(fmt)) return -1;
+	if (w == 0 || h == 0 || (w & 3) || (h & 3) || (unsigned long long)w * h > (1ull << 28))
+		return clip_err("agmv_hip: measuring frames of %u x %u (multiples of 4, at most 2^28 pixels, are needed)", w, h);
+	if (n_frames == 0) return 0;
+	if (!d_test || !d_ref || !d_quality) return clip_err("agmv_hip: NULL clip or result");
+	if ((uintptr_t)d_test & 3 || (uintptr_t)d_quality & 7) return clip_err("agmv_hip: the test clip needs 4-byte, the result 8-byte alignment");
+	CCK(hipMemsetAsync(d_quality, 0, 96 * (size_t)n_frames, (hipStream_t)stream));
+	MeasureArgs A;
+	A.test = d_test; A.ref = (const uint8_t*)d_ref; A.out = (unsigned long long*)d_quality;
+	A.frame_bytes = clip_frame_bytes(fmt, w, h);
+	A.w = w; A.h = h; A.tx = (w / 4 + MS_TW - 1) / MS_TW; A.ty = (h / 4 + MS_TH - 1) / MS_TH;
+	A.items = (unsigned long long)n_frames * A.tx * A.ty;
+	A.t_vec = pf_aligned(PF_XRGB32, d_test, (size_t)w * h, n_frames);
+	A.wide = yuv ? yuv_wide(fmt, d_ref, w, h, n_frames) : pf_aligned(fmt, d_ref, (size_t)w * h, n_frames);
+	A.m = YUV_RD[(fmt >> 8) & 3];
+	CLIP_LAUNCH(PF_BYTES | PF_YUV | PF_BIT(PF_XRGB32), k_measure, (unsigned)(A.items < 4096 ? A.items : 4096), A);
 	CCK(hipGetLastError());
 	return 0;
 }

@@ -887,10 +887,21 @@ int AGMV_EncodeFramesScaledDev(const char* filename, const void* d_frames, AGMV_
  * frame by frame into ONE persistent buffer (so the stale-tail semantics hold), the GPU parses and
  * reconstructs whole batches, frames are exported as quick_export_<n>.bmp in the CWD.
  * ------------------------------------------------------------------------------------------ */
-/* d_dst NULL: AGMV_DecodeAGMV / AGMV_DecodeVideo, every frame to its BMP.  Else AGMV_DecodeFramesFmtDev: up to cap_frames frames
-   in the layout `fmt` into d_dst, their number into *decoded.  *info (may be NULL) = the header's; with info_only nothing else happens. */
-static int decode_file(const char* filename, u8 img_type, void* d_dst, int fmt, u32 cap_frames, int info_only, AGMV_INFO* info, unsigned long* decoded)
+/* the entries of n measured frames from the device array where agmv_hip_measure_frames_async made them, once */
+static void download_quality(agmv_hip_ctx* c, const void* d_q, AGMV_FRAME_QUALITY* quality, size_t n)
 {
+	if (n && (agmv_hip_memcpy_async(c, quality, d_q, n * sizeof(AGMV_FRAME_QUALITY), 1, NULL) || agmv_hip_stream_sync(c, NULL))) agmv_die("quality download");
+}
+
+/* d_dst NULL: AGMV_DecodeAGMV / AGMV_DecodeVideo, every frame to its BMP.  Else AGMV_DecodeFramesFmtDev: up to cap_frames frames
+   in the layout `fmt` into d_dst, their number into *decoded; or, with `quality` (host memory), AGMV_MeasureFileDev: d_dst is the
+   reference clip of exactly cap_frames frames, only read, and the entries of the *decoded frames measured land in quality[] -- made
+   on the device, downloaded once.  *info (may be NULL) = the header's; with info_only nothing else happens.  Returns an Error, or
+   -3 where the reference cannot correspond to the file (before a device is opened). */
+static int decode_file(const char* filename, u8 img_type, void* d_dst, int fmt, AGMV_FRAME_QUALITY* quality, u32 cap_frames, int info_only,
+                       AGMV_INFO* info, unsigned long* decoded)
+{
+	void* d_quality = NULL;
 	FILE* f = fopen(filename, "rb");
 	AGMV hdr_obj;
 	u8* file;
@@ -909,6 +920,10 @@ static int decode_file(const char* filename, u8 img_type, void* d_dst, int fmt, 
 	if (err != NO_ERR) { fclose(f); return err; }
 	if (info) *info = AGMV_GetVideoInfo(&hdr_obj);
 	if (info_only) { fclose(f); return NO_ERR; }
+	if (quality && (hdr_obj.header.num_of_frames != cap_frames || (AGMV_FMT_IS_YUV(fmt) && ((hdr_obj.header.width | hdr_obj.header.height) & 1)))) {
+		fclose(f);
+		return -3;
+	}
 	pos = (size_t)ftell(f);
 	fseek(f, 0, SEEK_END); flen = ftell(f); fseek(f, 0, SEEK_SET);
 	file = (u8*)malloc((size_t)flen + 16);
@@ -932,13 +947,19 @@ static int decode_file(const char* filename, u8 img_type, void* d_dst, int fmt, 
 	cap = batch_frames(npx);
 	nframes = (uint32_t)hdr_obj.header.num_of_frames;
 	if (d_dst && nframes > cap_frames) nframes = (uint32_t)cap_frames;
+	if (quality && nframes) {
+		d_quality = agmv_hip_malloc_on(c, (size_t)nframes * sizeof(AGMV_FRAME_QUALITY));
+		if (!d_quality) { free(file); return gpu_failed("result array for the measurement"); }
+	}
 	err = agmv_decode_stream(c, file, got, pos, w, h, nframes, hdr_obj.header.version, hdr_obj.header.total_audio_duration != 0, cap,
-	                         lz_threads(), d_dst, fmt, d_dst ? decoded : &g_export_count);
+	                         lz_threads(), d_dst, fmt, d_quality, d_dst ? decoded : &g_export_count);
+	if (d_quality && err == NO_ERR) download_quality(c, d_quality, quality, (size_t)*decoded);
+	agmv_hip_free_on(c, d_quality);
 	free(file);
 	return err;
 }
 
-int AGMV_DecodeVideo(const char* filename, u8 img_type) { return decode_file(filename, img_type, NULL, AGMV_PIXFMT_XRGB32, 0, 0, NULL, NULL); }
+int AGMV_DecodeVideo(const char* filename, u8 img_type) { return decode_file(filename, img_type, NULL, AGMV_PIXFMT_XRGB32, NULL, 0, 0, NULL, NULL); }
 
 /* AGMV_DecodeAGMV with another destination: frame k of the file (0-based) as the k-th frame of the layout `fmt` in d_frames
    (device memory of this library's context) instead of in quick_export_<k + 1>.bmp.  At most cap_frames frames; returns the
@@ -948,7 +969,7 @@ int AGMV_DecodeFramesFmtDev(const char* filename, void* d_frames, AGMV_PIXFMT fm
 	unsigned long decoded = 0;
 	int err;
 	if (!known_pixfmt((int)fmt)) return -1;
-	err = filename ? decode_file(filename, AGMV_IMG_BMP, d_frames, (int)fmt, cap_frames, d_frames == NULL, info, &decoded) : FILE_NOT_FOUND_ERR;
+	err = filename ? decode_file(filename, AGMV_IMG_BMP, d_frames, (int)fmt, NULL, cap_frames, d_frames == NULL, info, &decoded) : FILE_NOT_FOUND_ERR;
 	return err == NO_ERR ? (int)decoded : -err;
 }
 
@@ -962,7 +983,7 @@ int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frame
 int AGMV_DecodeAGMV(const char* filename, u8 img_type, AGMV_AUDIO_TYPE audio_type)
 {
 	(void)audio_type;
-	return decode_file(filename, img_type, NULL, AGMV_PIXFMT_XRGB32, 0, 0, NULL, NULL);
+	return decode_file(filename, img_type, NULL, AGMV_PIXFMT_XRGB32, NULL, 0, 0, NULL, NULL);
 }
 
 /* The file's audio track into device memory in the layout `fmt` (include/agmv.h): the AGAC payloads gathered on the host into
@@ -1014,6 +1035,40 @@ int AGMV_DecodeAudioDev(const char* filename, void* d_pcm, AGMV_PCMFMT fmt, u32 
 	agmv_hip_free_on(c, d_codes); agmv_hip_host_free(h_codes);
 	if (stream) agmv_hip_stream_destroy(c, stream);
 	return failed ? -err : (int)n;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * measuring a decoded clip (include/agmv.h, "measuring a decoded clip"): the entries are made on the device by
+ * agmv_hip_measure_frames_async and downloaded once
+ * ------------------------------------------------------------------------------------------ */
+int AGMV_MeasureFramesDev(const unsigned* d_test, const void* d_ref, AGMV_PIXFMT ref_fmt, u32 num_of_frames, u32 width, u32 height,
+                          AGMV_FRAME_QUALITY* quality)
+{
+	agmv_hip_ctx* c;
+	void *stream, *d_q;
+	if (!known_pixfmt((int)ref_fmt) || !d_test || !d_ref || !quality) return -1;
+	if (width > 0xFFFFFFFFul || height > 0xFFFFFFFFul || bad_geometry((uint32_t)width, (uint32_t)height) || num_of_frames > 0x7FFFFFFFul) return -3;
+	if (num_of_frames == 0) return 0;
+	c = ctx();
+	stream = agmv_hip_stream_create(c);
+	d_q = agmv_hip_malloc_on(c, (size_t)num_of_frames * sizeof(AGMV_FRAME_QUALITY));
+	if (!stream || !d_q) agmv_die("stream and result array for the measurement");
+	if (agmv_hip_measure_frames_async(c, d_test, (int)ref_fmt, d_ref, (uint32_t)width, (uint32_t)height, (uint32_t)num_of_frames, d_q, stream) ||
+	    agmv_hip_stream_sync(c, stream))
+		agmv_die("frame measurement");
+	download_quality(c, d_q, quality, (size_t)num_of_frames);
+	agmv_hip_free_on(c, d_q);
+	agmv_hip_stream_destroy(c, stream);
+	return 0;
+}
+
+int AGMV_MeasureFileDev(const char* filename, const void* d_ref, AGMV_PIXFMT ref_fmt, u32 num_of_frames, AGMV_FRAME_QUALITY* quality, AGMV_INFO* info)
+{
+	unsigned long measured = 0;
+	int err;
+	if (!known_pixfmt((int)ref_fmt) || (quality && !d_ref)) return -1;
+	err = filename ? decode_file(filename, AGMV_IMG_BMP, (void*)d_ref, (int)ref_fmt, quality, num_of_frames, quality == NULL, info, &measured) : FILE_NOT_FOUND_ERR;
+	return err == NO_ERR ? (int)measured : err < 0 ? err : -err;
 }
 
 /* ------------------------------------------------------------------------------------------

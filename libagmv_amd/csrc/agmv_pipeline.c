@@ -812,6 +812,7 @@ typedef struct dpipe {
 	uint8_t* d_bits; uint32_t *d_bpos, *d_nent, *d_out[2], *d_iframe;
 	void* d_dst;                           /* the sink: NULL = BMP export through d_out / h_out, else the caller's device frames */
 	int fmt;                               /* ... in this AGMV_PIXFMT: XRGB32 is decoded in place, any other through d_out */
+	void* d_quality;                       /* the measuring sink: d_dst is the reference clip, only read; frame k's AGMV_FRAME_QUALITY lands here */
 } dpipe;
 
 typedef struct savearg { dpipe* d; dbatch* b; unsigned k; } savearg;
@@ -847,8 +848,8 @@ static void* dworker_main(void* p)
 		if (id >= d->nfilled) { pthread_mutex_unlock(&d->mu); break; }
 		pthread_mutex_unlock(&d->mu);
 		/* with a packed sink the batch is decoded straight into its place, and the frame before it is the one before it there;
-		   a sink in another layout takes the batch from the double buffer, where the decoder's state stays */
-		const int direct = d->d_dst && d->fmt == AGMV_PIXFMT_XRGB32;
+		   a sink in another layout, and the measuring sink, take the batch from the double buffer, where the decoder's state stays */
+		const int direct = d->d_dst && !d->d_quality && d->fmt == AGMV_PIXFMT_XRGB32;
 		out = direct ? (uint32_t*)d->d_dst + (size_t)b->first * d->npx : d->d_out[id & 1];
 		prev = !have_state ? NULL : direct ? out - d->npx : d->d_out[(id - 1) & 1] + (size_t)(prev_n - 1) * d->npx;
 		if (b->d_slab) {                       /* the LZ stage left the rows on the device: wait for their commit, on the device */
@@ -866,7 +867,8 @@ static void* dworker_main(void* p)
 		if (last_i >= 0 && agmv_hip_memcpy_async(d->ctx, d->d_iframe, out + (size_t)last_i * d->npx, d->npx * 4, 2, d->stream)) goto fail;
 		if (d->d_dst && !direct) {
 			u8* sink = (u8*)d->d_dst + (size_t)b->first * agmv_fmt_frame_bytes(d->fmt, d->w, d->h);
-			if (AGMV_FMT_IS_YUV(d->fmt) ? agmv_hip_yuv_from_xrgb_dev(d->ctx, d->fmt, out, d->w, d->h, b->n, sink, d->stream)
+			if (d->d_quality ? agmv_hip_measure_frames_async(d->ctx, out, d->fmt, sink, d->w, d->h, b->n, (u8*)d->d_quality + 96 * (size_t)b->first, d->stream) :
+			    AGMV_FMT_IS_YUV(d->fmt) ? agmv_hip_yuv_from_xrgb_dev(d->ctx, d->fmt, out, d->w, d->h, b->n, sink, d->stream)
 			                            : agmv_hip_pixels_from_xrgb_dev(d->ctx, d->fmt, out, b->n, d->npx, sink, d->stream))
 				goto fail;
 		}
@@ -1086,11 +1088,12 @@ static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, dchunk* c, const u8* fil
    those of the reference's ONE persistent buffer: the host stage takes them from `persist` in frame order, which then
    receives the frame.  The frames go to d_dst (device memory of ctx's device, frame k of the file as a frame of the AGMV_PIXFMT
    `fmt` at its place there) or, with d_dst NULL, to quick_export_<*export_count + 1 ...>.bmp; *export_count advances by the
-   frames decoded either way. */
+   frames decoded either way.  With d_quality (device memory, 96 bytes per frame) d_dst is a reference clip in `fmt` that is only
+   read: frame k is measured against frame k of it where the other sink converts, and no decoded frame outlives its batch. */
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
-                       int has_audio, unsigned cap_frames, unsigned threads, void* d_dst, int fmt, unsigned long* export_count)
+                       int has_audio, unsigned cap_frames, unsigned threads, void* d_dst, int fmt, void* d_quality, unsigned long* export_count)
 {
-	const int direct = d_dst && fmt == AGMV_PIXFMT_XRGB32;     /* decoded in place: no double buffer */
+	const int direct = d_dst && !d_quality && fmt == AGMV_PIXFMT_XRGB32;     /* decoded in place: no double buffer */
 	dpipe d;
 	dlz z;
 	const char* lzv = getenv("AGMV_LZ_DECODE_DEVICE");     /* opt-in: the LZ stage on the GPU (read when a decode starts) */
@@ -1105,7 +1108,7 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	memset(&d, 0, sizeof(d));
 	memset(&z, 0, sizeof(z));
 	d.ctx = ctx; d.w = w; d.h = h; d.npx = npx; d.stride = (cap + 255) & ~(size_t)255;
-	d.cap = cap_frames; d.nslots = 3; d.d_dst = d_dst; d.fmt = fmt;
+	d.cap = cap_frames; d.nslots = 3; d.d_dst = d_dst; d.fmt = fmt; d.d_quality = d_quality;
 	pthread_mutex_init(&d.mu, NULL);
 	pthread_cond_init(&d.cv, NULL);
 	d.slot = (dbatch*)calloc(d.nslots, sizeof(dbatch));

@@ -50,7 +50,7 @@ void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start,
                            unsigned threads, uint32_t* hist);
 
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
-                       int has_audio, unsigned cap_frames, unsigned threads, void* d_dst, int fmt, unsigned long* export_count);
+                       int has_audio, unsigned cap_frames, unsigned threads, void* d_dst, int fmt, void* d_quality, unsigned long* export_count);
 
 /* the AGAC payloads of a file image (its first chunk at or behind pos) back to back, at most cap bytes; returns their number */
 size_t agmv_gather_audio(const u8* file, size_t len, size_t pos, uint32_t nframes, u8* out, size_t cap);

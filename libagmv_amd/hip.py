@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "agmv_hip_palette_refine_dev",
     "agmv_hip_dither_frames_async",
     "agmv_hip_audio_compand_async", "agmv_hip_audio_expand_async",
+    "agmv_hip_measure_frames_async",
 ]
 
 
@@ -177,6 +178,9 @@ def load_library(path=None):
         L.agmv_hip_audio_compand_async.argtypes = [vp, C.c_int, vp, u32, C.c_uint64, vp, vp]
         L.agmv_hip_audio_expand_async.argtypes = [vp, C.c_int, vp, u32, C.c_uint64, vp, vp]
         L.agmv_hip_audio_compand_async.restype = L.agmv_hip_audio_expand_async.restype = C.c_int
+    if path is None or hasattr(L, "agmv_hip_measure_frames_async"):
+        L.agmv_hip_measure_frames_async.argtypes = [vp, vp, C.c_int, vp, u32, u32, u32, vp, vp]
+        L.agmv_hip_measure_frames_async.restype = C.c_int
     L.agmv_hip_check.argtypes = [vp, vp]
     L.agmv_hip_enable_timing.argtypes = [vp, C.c_int]
     L.agmv_hip_enable_timing.restype = C.c_int
@@ -884,6 +888,28 @@ class AgmvHip:
         s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
         self._ck(self.L.agmv_hip_dither_frames_async(self.ctx, int(strength), pix.data_ptr(), w, h, pix.numel() // (w * h), s))
         return pix
+
+    # ------------------------------------------------------------------ a decoded clip measured against its reference (include/agmv.h)
+    def measure_frames(self, test, fmt, ref, w, h, n_frames, out=None, yuv=None, full_range=False, stream=None):
+        """test: int32 CUDA tensor of n_frames frames of w x h pixels 0x00RRGGBB; ref: the same frames in fmt (any name of PIXFMT or
+        YUVFMT, or its value) -> int64 [n_frames, 12]: sse, block_sse, max_err and ssim (Q20 sums) of R, G, B per frame
+        (agmv_hip_measure_frames_async) on `stream` (a torch stream; None = torch's current one).  Nothing waits."""
+        import torch
+        w, h, n_frames = int(w), int(h), int(n_frames)
+        _check_vec("measure_frames: test", test, n_frames * w * h)
+        if fmt in YUVFMT or (isinstance(fmt, int) and (fmt & 0xFF) in YUVFMT.values()):
+            fmt = self._check_yuv("measure_frames: ref", fmt, ref, w, h, n_frames, yuv, full_range)
+        else:
+            if yuv is not None or full_range:
+                raise ValueError("measure_frames: yuv= and full_range= belong to fmt \"nv12\" and \"i420\", not to fmt %r" % (fmt,))
+            fmt = self._check_clip("measure_frames: ref", fmt, ref, n_frames * self.pixfmt_frame_bytes(fmt, w * h))
+        if out is None:
+            out = torch.empty((n_frames, 12), dtype=torch.int64, device=test.device)
+        elif not (out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() >= 12 * n_frames):
+            raise ValueError("measure_frames: out must be a contiguous CUDA int64 tensor of >= %d entries" % (12 * n_frames))
+        s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self._ck(self.L.agmv_hip_measure_frames_async(self.ctx, test.data_ptr(), fmt, ref.data_ptr(), w, h, n_frames, out.data_ptr(), s))
+        return out
 
     # ------------------------------------------------------------------ audio tracks (include/agmv.h, "audio tracks")
     @staticmethod

@@ -2,6 +2,9 @@
 AGMV_DecodeFramesFmtDev (include/agmv.h, libagmv.so).  No logic here: the schedules, the container, both LZ stages and the reading and writing of the
 caller's pixel layout are the library's; torch holds the frames.  The frames live on the library's own device (env AGMV_DEVICE,
 default 0).
+clip_quality / file_quality (AGMV_MeasureFramesDev / AGMV_MeasureFileDev) measure a decoded clip, or a file batch by batch, against
+the frames it was made from, in any of the layouts below, and return a Quality: exact integers per frame and channel, and the
+PSNR, block-mean PSNR and mean SSIM formed from them.
 
 Pixel layouts (AGMV_PIXFMT) and the tensors that hold n frames of h x w:
   "xrgb32"  int32 / uint32 [n, h, w]   0x00RRGGBB
@@ -25,6 +28,11 @@ from .hip import HERE, PIXFMT, YUVFMT, HipUnavailable, pcmfmt, pixfmt, yuvfmt
 
 SCHEDULE_FULL, SCHEDULE_PDIFS, SCHEDULE_ADAPTIVE = 1, 2, 3
 SCALE = {"nearest": 1, "area": 2}          # AGMV_SCALE of include/agmv.h, which defines both filters
+
+
+class AGMV_FRAME_QUALITY(C.Structure):
+    # include/agmv.h: 96 bytes, the same on host and device
+    _fields_ = [("sse", C.c_ulonglong * 3), ("block_sse", C.c_ulonglong * 3), ("max_err", C.c_ulonglong * 3), ("ssim", C.c_longlong * 3)]
 
 
 class AGMV_INFO(C.Structure):
@@ -63,6 +71,10 @@ def load_library():
         L.AGMV_SetAudioDev.argtypes = [C.c_void_p, C.c_int, C.c_ulong, C.c_ulong, C.c_ushort]
         L.AGMV_DecodeAudioDev.restype = C.c_int
         L.AGMV_DecodeAudioDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.POINTER(AGMV_INFO)]
+        L.AGMV_MeasureFramesDev.restype = C.c_int
+        L.AGMV_MeasureFramesDev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_ulong, C.c_ulong, C.c_ulong, C.POINTER(AGMV_FRAME_QUALITY)]
+        L.AGMV_MeasureFileDev.restype = C.c_int
+        L.AGMV_MeasureFileDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.POINTER(AGMV_FRAME_QUALITY), C.POINTER(AGMV_INFO)]
         _lib = L
     return _lib
 
@@ -80,22 +92,23 @@ def _fmt_value(who, fmt, yuv, full_range):
     return pixfmt(fmt)
 
 
-def _clip_geometry(frames, fmt, yuv=None, full_range=False):
+def _clip_geometry(frames, fmt, yuv=None, full_range=False, who="encode_frames"):
     """(fmt value for the library, n, h, w) of a tensor of frames; fmt None = inferred from dtype and shape (never a YUV layout).
-    Raises ValueError naming `fmt` for a tensor that holds no clip of that layout; touches neither the library nor the device."""
+    Raises ValueError naming `fmt` for a tensor that holds no clip of that layout, in the name of the caller `who`; touches neither
+    the library nor the device."""
     import torch
     if fmt is None and (yuv is not None or full_range):
-        raise ValueError("encode_frames: yuv= and full_range= need fmt \"nv12\" or \"i420\": a YUV layout is never inferred from a tensor")
+        raise ValueError(who + ": yuv= and full_range= need fmt \"nv12\" or \"i420\": a YUV layout is never inferred from a tensor")
     if fmt in YUVFMT:
-        v, shape = _fmt_value("encode_frames", fmt, yuv, full_range), tuple(frames.shape)
+        v, shape = _fmt_value(who, fmt, yuv, full_range), tuple(frames.shape)
         if not (frames.dtype == torch.uint8 and len(shape) == 3 and shape[1] % 3 == 0 and shape[2] % 2 == 0 and shape[1] > 0 and shape[2] > 0):
-            raise ValueError("encode_frames: fmt %r does not fit a %s tensor of shape %s: uint8 [n, h * 3 / 2, w] with even h and w is needed"
+            raise ValueError(who + ": fmt %r does not fit a %s tensor of shape %s: uint8 [n, h * 3 / 2, w] with even h and w is needed"
                              % (fmt, frames.dtype, shape))
         if not frames.is_contiguous():
-            raise ValueError("encode_frames: fmt %r needs a contiguous tensor (strides %s of shape %s)" % (fmt, frames.stride(), shape))
+            raise ValueError(who + ": fmt %r needs a contiguous tensor (strides %s of shape %s)" % (fmt, frames.stride(), shape))
         return v, shape[0], shape[1] // 3 * 2, shape[2]
     if fmt is not None:
-        _fmt_value("encode_frames", fmt, yuv, full_range)
+        _fmt_value(who, fmt, yuv, full_range)
     shape, packed = tuple(frames.shape), frames.element_size() == 4 and not frames.dtype.is_floating_point and not frames.dtype.is_complex
     if fmt is None:
         fits = []
@@ -104,16 +117,16 @@ def _clip_geometry(frames, fmt, yuv=None, full_range=False):
         if frames.dtype == torch.uint8 and len(shape) == 4:
             fits += [name for name, ok in (("rgb24", shape[3] == 3), ("rgba32", shape[3] == 4), ("rgb8p", shape[1] == 3)) if ok]
         if len(fits) != 1:
-            raise ValueError("encode_frames: fmt cannot be inferred from a %s tensor of shape %s (%s): pass fmt=" %
+            raise ValueError(who + ": fmt cannot be inferred from a %s tensor of shape %s (%s): pass fmt=" %
                              (frames.dtype, shape, "it fits " + " and ".join(fits) if fits else "int32/uint32 [n,h,w], uint8 [n,h,w,3|4] or uint8 [n,3,h,w] is needed"))
         fmt = fits[0]
     v = pixfmt(fmt)
     ok = (packed and len(shape) == 3) if v == 1 else (frames.dtype == torch.uint8 and len(shape) == 4 and
                                                       (shape[1] == 3 if v == 5 else shape[3] == (4 if v == 4 else 3)))
     if not ok:
-        raise ValueError("encode_frames: fmt %r does not fit a %s tensor of shape %s" % (fmt, frames.dtype, shape))
+        raise ValueError(who + ": fmt %r does not fit a %s tensor of shape %s" % (fmt, frames.dtype, shape))
     if not frames.is_contiguous():
-        raise ValueError("encode_frames: fmt %r needs a contiguous tensor (strides %s of shape %s)" % (fmt, frames.stride(), shape))
+        raise ValueError(who + ": fmt %r needs a contiguous tensor (strides %s of shape %s)" % (fmt, frames.stride(), shape))
     n, h, w = (shape[0], shape[2], shape[3]) if v == 5 else shape[:3]
     return v, n, h, w
 
@@ -253,3 +266,88 @@ def decode_audio(path, fmt="s16", cap_samples=None):
             raise RuntimeError("AGMV_DecodeAudioDev(%s, fmt %r): Error %d (a 16-bit track decodes as \"s16\" or \"f32p\", an 8-bit track as \"u8\")"
                                % (path, fmt, -got))
     return (buf[:got].view(ch, got // ch) if v == 3 else buf[:got].view(got // ch, ch)), info
+
+
+class Quality:
+    """What AGMV_MeasureFramesDev / AGMV_MeasureFileDev report for n frames of width x height (include/agmv.h, "measuring a decoded
+    clip"): sse, block_sse, max_err and ssim_sum as numpy int64 [n, 3], channel 0 = R; ssim_sum holds the Q20 sums over each frame's windows.
+    The three figures are formed here, in float64, over all frames and channels."""
+
+    def __init__(self, entries, n, width, height):
+        import numpy as np
+        raw = np.frombuffer(entries, dtype=np.int64, count=12 * n).reshape(n, 4, 3).copy() if n else np.zeros((0, 4, 3), np.int64)
+        self.sse, self.block_sse, self.max_err, self.ssim_sum = (raw[:, k, :] for k in range(4))
+        self.width, self.height = int(width), int(height)
+
+    def __len__(self):
+        return self.sse.shape[0]
+
+    @property
+    def windows(self):
+        """SSIM windows per frame and channel"""
+        return (self.width // 4 - 1) * (self.height // 4 - 1)
+
+    @staticmethod
+    def _psnr(mse):
+        import math
+        return math.inf if mse == 0 else 10.0 * math.log10(255.0 * 255.0 / mse)
+
+    def psnr(self):
+        """10 log10(255^2 / mean squared error) over all frames and channels; inf for zero error, nan for no frame"""
+        count = 3 * len(self) * self.width * self.height
+        return self._psnr(float(int(self.sse.sum())) / count) if count else float("nan")
+
+    def block_psnr(self):
+        """the same for the means of the 4x4 blocks: block_sse is 256 times their squared error"""
+        count = 3 * len(self) * (self.width // 4) * (self.height // 4)
+        return self._psnr(float(int(self.block_sse.sum())) / 256.0 / count) if count else float("nan")
+
+    def ssim(self):
+        """the mean SSIM over windows, frames and channels; nan where a frame has no window"""
+        count = 3 * len(self) * self.windows
+        return float(int(self.ssim_sum.sum())) / float(1 << 20) / count if count else float("nan")
+
+
+def clip_quality(test, ref, fmt=None, yuv=None, full_range=False):
+    """test: the decoded clip, a contiguous CUDA int32 / uint32 tensor [n, h, w] of 0x00RRGGBB on the library's device; ref: the
+    clip it is measured against, n frames of the same size in the layout `fmt` (as for encode_frames: None = inferred from the
+    tensor, never a YUV layout) -> Quality (AGMV_MeasureFramesDev).  Its four integer arrays are sse, block_sse, max_err and
+    ssim_sum (the `ssim` words of AGMV_FRAME_QUALITY: ssim() is the method that forms the mean from them)."""
+    import torch
+    v, n, h, w = _clip_geometry(ref, fmt, yuv, full_range, who="clip_quality")
+    _, tn, th, tw = _clip_geometry(test, "xrgb32", who="clip_quality")
+    if (tn, th, tw) != (n, h, w):
+        raise ValueError("clip_quality: the test clip holds %d frames of %dx%d, the reference %d frames of %dx%d" % (tn, tw, th, n, w, h))
+    for name, t in (("test clip", test), ("reference", ref)):
+        if not (t.is_cuda and t.device == torch.device(_device())):
+            raise ValueError("clip_quality: the %s must be on %s, got %s" % (name, _device(), t.device))
+    torch.cuda.synchronize(test.device)            # the library works on streams of its own
+    entries = (AGMV_FRAME_QUALITY * max(n, 1))()
+    rc = load_library().AGMV_MeasureFramesDev(test.data_ptr(), ref.data_ptr(), v, n, w, h, entries)
+    if rc:
+        raise ValueError("AGMV_MeasureFramesDev refused its arguments (%d): %d frames of %dx%d" % (rc, n, w, h))
+    return Quality(entries, n, w, h)
+
+
+def file_quality(path, ref, fmt=None, yuv=None, full_range=False):
+    """the file at `path`, decoded batch by batch and never held as a clip, against ref: its frames before they were encoded, in
+    the layout `fmt` (as for clip_quality) -> Quality of the frames measured (AGMV_MeasureFileDev).  The reference must hold
+    exactly the header's number of frames, at the file's size."""
+    import torch
+    v, n, h, w = _clip_geometry(ref, fmt, yuv, full_range, who="file_quality")
+    if not (ref.is_cuda and ref.device == torch.device(_device())):
+        raise ValueError("file_quality: the reference must be on %s, got %s" % (_device(), ref.device))
+    L = load_library()
+    info = AGMV_INFO()
+    rc = L.AGMV_MeasureFileDev(os.fsencode(path), None, v, 0, None, C.byref(info))
+    if rc < 0:
+        raise RuntimeError("AGMV_MeasureFileDev(%s): Error %d" % (path, -rc))
+    if (info.number_of_frames, info.height, info.width) != (n, h, w):
+        raise ValueError("file_quality: %s holds %d frames of %dx%d, the reference %d frames of %dx%d"
+                         % (path, info.number_of_frames, info.width, info.height, n, w, h))
+    torch.cuda.synchronize(ref.device)
+    entries = (AGMV_FRAME_QUALITY * max(n, 1))()
+    rc = L.AGMV_MeasureFileDev(os.fsencode(path), ref.data_ptr(), v, n, entries, None)
+    if rc < 0:
+        raise RuntimeError("AGMV_MeasureFileDev(%s): Error %d" % (path, -rc))
+    return Quality(entries, rc, w, h)
