@@ -87,7 +87,7 @@ def _build(force=False, verbose=False):
     hip_srcs = [os.path.join(CSRC, "agmv_hip.hip"), os.path.join(CSRC, "agmv_decode_hip.hip"), os.path.join(CSRC, "agmv_lz_hip.hip"), os.path.join(CSRC, "agmv_lz_decode_hip.hip"),
                 os.path.join(CSRC, "agmv_lz77_hip.hip"), os.path.join(CSRC, "agmv_clip_hip.hip"), os.path.join(CSRC, "agmv_palette_hip.hip"),
                 os.path.join(CSRC, "agmv_audio_hip.hip")]
-    hdrs = glob.glob(os.path.join(ROOT, "include", "*.h")) + [os.path.join(CSRC, "agmv_audio.h")]
+    hdrs = glob.glob(os.path.join(ROOT, "include", "*.h")) + glob.glob(os.path.join(CSRC, "*.h"))
     hip_so = os.path.join(HERE, "libagmv_hip.so")
     if force or _stale(hip_so, hip_srcs + hdrs):
         _compile([HIPCC, "--offload-arch=" + ARCH, "-O3", "-fPIC", "-shared", "-std=c++17"] + hip_srcs + ["-o", hip_so], hip_so, verbose, no_scratch=True)

@@ -10,33 +10,10 @@
 // not start on 16-byte boundaries, samples_per_channel % 4 != 0) make the whole track "head".  The grid is capped and strides.
 #include <hip/hip_runtime.h>
 
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
-#include "../../include/agmv_hip.h"
+#include "agmv_hip_impl.h"
 #include "agmv_audio.h"
-
-// defined in agmv_hip.hip: the library's error text and the context's device
-int agmv_hip_internal_error(const char* msg);
-int agmv_hip_internal_device(agmv_hip_ctx* c);
-
-static int aud_err(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-static int aud_err(const char* fmt, ...)
-{
-	char m[512];
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(m, sizeof(m), fmt, ap);
-	va_end(ap);
-	return agmv_hip_internal_error(m);
-}
-
-static int aud_fail(const char* what, hipError_t e, int line)
-{
-	return aud_err("agmv_hip: %s failed: %s (agmv_audio_hip.hip:%d)", what, hipGetErrorString(e), line);
-}
-#define ACK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return aud_fail(#x, e_, __LINE__); } while (0)
 
 constexpr uint32_t AUD_T = 256;              // lanes of a workgroup
 constexpr uint32_t AUD_MAX_BLOCKS = 2048;    // 256 CUs x 8 workgroups; the rest of a long track is reached by the stride
@@ -177,14 +154,14 @@ static dim3 grid_of(const aud_cut& k, uint32_t per_sample)
 // what both directions refuse; *total = samples over all channels
 static int check_args(const char* who, agmv_hip_ctx* c, int pcmfmt, const void* d_pcm, uint32_t channels, uint64_t n, const void* d_codes, uint64_t* total)
 {
-	if (!c) return aud_err("agmv_hip: NULL context");
-	if (pcmfmt != PCM_S16 && pcmfmt != PCM_U8 && pcmfmt != PCM_F32P) return aud_err("%s: %d is no AGMV_PCMFMT (1 S16, 2 U8, 3 F32P)", who, pcmfmt);
-	if (!d_pcm || !d_codes) return aud_err("%s: NULL pointer", who);
-	if (channels == 0) return aud_err("%s: zero channels", who);
-	if (pcmfmt == PCM_F32P && channels > AUD_MAX_PLANES) return aud_err("%s: %u planar channels, 1 .. %u are possible", who, channels, AUD_MAX_PLANES);
-	if (n > (UINT64_MAX >> 4) / channels) return aud_err("%s: %llu samples in %u channels cannot be addressed", who, (unsigned long long)n, channels);
+	if (!c) return agmv_hip_err("agmv_hip: NULL context");
+	if (pcmfmt != PCM_S16 && pcmfmt != PCM_U8 && pcmfmt != PCM_F32P) return agmv_hip_err("%s: %d is no AGMV_PCMFMT (1 S16, 2 U8, 3 F32P)", who, pcmfmt);
+	if (!d_pcm || !d_codes) return agmv_hip_err("%s: NULL pointer", who);
+	if (channels == 0) return agmv_hip_err("%s: zero channels", who);
+	if (pcmfmt == PCM_F32P && channels > AUD_MAX_PLANES) return agmv_hip_err("%s: %u planar channels, 1 .. %u are possible", who, channels, AUD_MAX_PLANES);
+	if (n > (UINT64_MAX >> 4) / channels) return agmv_hip_err("%s: %llu samples in %u channels cannot be addressed", who, (unsigned long long)n, channels);
 	if ((uintptr_t)d_pcm % (pcmfmt == PCM_S16 ? 2 : pcmfmt == PCM_F32P ? 4 : 1))
-		return aud_err("%s: the PCM pointer is not aligned to its sample size", who);
+		return agmv_hip_err("%s: the PCM pointer is not aligned to its sample size", who);
 	*total = n * channels;
 	return 0;
 }
@@ -207,10 +184,10 @@ extern "C" int agmv_hip_audio_compand_async(agmv_hip_ctx* c, int pcmfmt, const v
 	uint64_t total = 0;
 	if (check_args("agmv_hip_audio_compand_async", c, pcmfmt, d_pcm, channels, samples_per_channel, d_codes, &total)) return -1;
 	if (total == 0) return 0;
-	ACK(hipSetDevice(agmv_hip_internal_device(c)));
+	CK(hipSetDevice(c->device));
 	const hipStream_t s = (hipStream_t)stream;
 	if (pcmfmt == PCM_U8) {
-		ACK(hipMemcpyAsync(d_codes, d_pcm, total, hipMemcpyDeviceToDevice, s));
+		CK(hipMemcpyAsync(d_codes, d_pcm, total, hipMemcpyDeviceToDevice, s));
 		return 0;
 	}
 	if (pcmfmt == PCM_S16) {
@@ -220,7 +197,7 @@ extern "C" int agmv_hip_audio_compand_async(agmv_hip_ctx* c, int pcmfmt, const v
 		const aud_cut k = cut_of(samples_per_channel, (uintptr_t)d_pcm, 4, samples_per_channel * 4, channels, (uintptr_t)d_codes, channels);
 		AUD_PER_CHANNELS(k_aud_compand_f32p, (const float*)d_pcm, d_codes, k)
 	}
-	ACK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
@@ -230,10 +207,10 @@ extern "C" int agmv_hip_audio_expand_async(agmv_hip_ctx* c, int pcmfmt, const ui
 	uint64_t total = 0;
 	if (check_args("agmv_hip_audio_expand_async", c, pcmfmt, d_pcm, channels, samples_per_channel, d_codes, &total)) return -1;
 	if (total == 0) return 0;
-	ACK(hipSetDevice(agmv_hip_internal_device(c)));
+	CK(hipSetDevice(c->device));
 	const hipStream_t s = (hipStream_t)stream;
 	if (pcmfmt == PCM_U8) {
-		ACK(hipMemcpyAsync(d_pcm, d_codes, total, hipMemcpyDeviceToDevice, s));
+		CK(hipMemcpyAsync(d_pcm, d_codes, total, hipMemcpyDeviceToDevice, s));
 		return 0;
 	}
 	if (pcmfmt == PCM_S16) {
@@ -243,6 +220,6 @@ extern "C" int agmv_hip_audio_expand_async(agmv_hip_ctx* c, int pcmfmt, const ui
 		const aud_cut k = cut_of(samples_per_channel, (uintptr_t)d_pcm, 4, samples_per_channel * 4, channels, (uintptr_t)d_codes, channels);
 		AUD_PER_CHANNELS(k_aud_expand_f32p, d_codes, (float*)d_pcm, k)
 	}
-	ACK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }

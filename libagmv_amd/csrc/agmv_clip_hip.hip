@@ -14,41 +14,11 @@
 // Integer/byte work only; every kernel is an HBM stream, except k_measure, which its divisions and moments bind.
 #include <hip/hip_runtime.h>
 
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include <type_traits>
 
-#include "../../include/agmv_hip.h"
-
-// defined in agmv_hip.hip: the library's error text, and the context's device
-int agmv_hip_internal_error(const char* msg);
-int agmv_hip_internal_device(agmv_hip_ctx* c);
-
-static int clip_err(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-static int clip_err(const char* fmt, ...)
-{
-	char m[512];
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(m, sizeof(m), fmt, ap);
-	va_end(ap);
-	return agmv_hip_internal_error(m);
-}
-
-static int clip_fail(const char* what, hipError_t e, int line)
-{
-	return clip_err("agmv_hip: %s failed: %s (agmv_clip_hip.hip:%d)", what, hipGetErrorString(e), line);
-}
-#define CCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return clip_fail(#x, e_, __LINE__); } while (0)
-
-static int need_clip_ctx(agmv_hip_ctx* c)
-{
-	if (!c) return clip_err("agmv_hip: NULL context");
-	CCK(hipSetDevice(agmv_hip_internal_device(c)));
-	return 0;
-}
+#include "agmv_hip_impl.h"
 
 // ----------------------------------------------------------------------------------------------
 // caller-side helpers: synthetic clip, PDIFS midpoint, palette histogram
@@ -1153,24 +1123,24 @@ template <unsigned SET, class L> static void clip_dispatch(int fmt, L launch)
 static int bad_pixfmt(int fmt)
 {
 	if (fmt >= PF_XRGB32 && fmt <= PF_RGB8P) return 0;
-	return clip_err("agmv_hip: unknown pixel format %d", fmt);
+	return agmv_hip_err("agmv_hip: unknown pixel format %d", fmt);
 }
 
 static int bad_yuv(int fmt, uint32_t w, uint32_t h)
 {
-	if (!yuv_base(fmt)) return clip_err("agmv_hip: unknown pixel format 0x%x (a YUV 4:2:0 format is needed)", (unsigned)fmt);
-	if (w == 0 || h == 0 || (unsigned long long)w * h > (1ull << 30)) return clip_err("agmv_hip: YUV frames of %u x %u", w, h);
+	if (!yuv_base(fmt)) return agmv_hip_err("agmv_hip: unknown pixel format 0x%x (a YUV 4:2:0 format is needed)", (unsigned)fmt);
+	if (w == 0 || h == 0 || (unsigned long long)w * h > (1ull << 30)) return agmv_hip_err("agmv_hip: YUV frames of %u x %u", w, h);
 	return 0;
 }
 
 // more pixels asked for than a frame has
-static int pf_bad_count(size_t n, size_t frame_pixels) { return n > frame_pixels ? clip_err("agmv_hip: n_pixels %zu > frame_pixels %zu", n, frame_pixels) : 0; }
-static int yuv_bad_count(size_t n, uint32_t w, uint32_t h) { return n > (size_t)w * h ? clip_err("agmv_hip: n_pixels %zu > %u x %u", n, w, h) : 0; }
+static int pf_bad_count(size_t n, size_t frame_pixels) { return n > frame_pixels ? agmv_hip_err("agmv_hip: n_pixels %zu > frame_pixels %zu", n, frame_pixels) : 0; }
+static int yuv_bad_count(size_t n, uint32_t w, uint32_t h) { return n > (size_t)w * h ? agmv_hip_err("agmv_hip: n_pixels %zu > %u x %u", n, w, h) : 0; }
 
 // the grid of a gather kernel: one thread per entry of the table
 static int gather_grid(size_t n_out, unsigned* blocks)
 {
-	if (n_out > ((size_t)1 << 39)) return clip_err("agmv_hip: gather table too long");
+	if (n_out > ((size_t)1 << 39)) return agmv_hip_err("agmv_hip: gather table too long");
 	*blocks = (unsigned)((n_out + 255) / 256);
 	return 0;
 }
@@ -1178,16 +1148,16 @@ static int gather_grid(size_t n_out, unsigned* blocks)
 // before a similarity launch: 1 = go on (the counts are cleared: the kernels add to them), 0 = no pair, nothing to do, -1 = error
 static int sim_begin(size_t n_pixels, uint32_t n_frames, uint32_t* d_counts, void* stream)
 {
-	if (n_pixels == 0 || n_pixels > 0xFFFFFFFFu) return clip_err("agmv_hip: similarity needs 1 .. 2^32 - 1 pixels per frame");
+	if (n_pixels == 0 || n_pixels > 0xFFFFFFFFu) return agmv_hip_err("agmv_hip: similarity needs 1 .. 2^32 - 1 pixels per frame");
 	if (n_frames < 2) return 0;
-	CCK(hipMemsetAsync(d_counts, 0, 4 * (size_t)(n_frames - 1), (hipStream_t)stream));
+	CK(hipMemsetAsync(d_counts, 0, 4 * (size_t)(n_frames - 1), (hipStream_t)stream));
 	return 1;
 }
 
 // the grid of a kernel whose blocks each lie in one frame, `per` blocks per frame, if all of them fit
 static int clip_grid(size_t per, uint32_t n_frames, uint32_t* bpf, unsigned* blocks)
 {
-	if (per * n_frames > 0x7FFFFFFFull) return clip_err("agmv_hip: clip too large for one launch");
+	if (per * n_frames > 0x7FFFFFFFull) return agmv_hip_err("agmv_hip: clip too large for one launch");
 	*bpf = (uint32_t)per; *blocks = (unsigned)(per * n_frames);
 	return 0;
 }
@@ -1221,44 +1191,44 @@ static int yuv_grid(uint32_t w, size_t n_pixels, int wide, uint32_t n_frames, ui
 extern "C" int agmv_hip_synth_dev(agmv_hip_ctx* c, uint32_t* d_pix, uint32_t w, uint32_t h, uint32_t t0, uint32_t n_frames,
                                   uint64_t seed, void* stream)
 {
-	if (need_clip_ctx(c)) return -1;
-	if (w < 2 || h < 2 || n_frames == 0) return clip_err("agmv_hip: bad synth geometry");
+	if (agmv_hip_enter(c)) return -1;
+	if (w < 2 || h < 2 || n_frames == 0) return agmv_hip_err("agmv_hip: bad synth geometry");
 	hipLaunchKernelGGL(k_synth, dim3(8192), dim3(256), 0, (hipStream_t)stream, d_pix, w, h, t0, n_frames, seed);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
 extern "C" int agmv_hip_interp_dev(agmv_hip_ctx* c, uint32_t* d_out, const uint32_t* d_f1, const uint32_t* d_f2, size_t n, void* stream)
 {
-	if (need_clip_ctx(c)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	if (n == 0) return 0;
 	size_t blocks = (n + 255) / 256;
 	if (blocks > 8192) blocks = 8192;
 	hipLaunchKernelGGL(k_interp, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_out, d_f1, d_f2, n);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
 extern "C" int agmv_hip_histogram_dev(agmv_hip_ctx* c, const uint32_t* d_pix, size_t n, int quality, uint32_t* d_hist, void* stream)
 {
-	if (need_clip_ctx(c)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	if (n == 0) return 0;
 	size_t blocks = (n + 255) / 256;
 	if (blocks > 8192) blocks = 8192;
 	hipLaunchKernelGGL(k_histogram, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_pix, n, quality, d_hist);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
 extern "C" int agmv_hip_similarity_dev(agmv_hip_ctx* c, const uint32_t* d_pix, uint32_t n_frames, size_t n_pixels, uint32_t* d_counts, void* stream)
 {
-	if (need_clip_ctx(c)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	const int go = sim_begin(n_pixels, n_frames, d_counts, stream);
 	if (go <= 0) return go;
 	const size_t blocks = (n_pixels + 2047) / 2048;            // 256 lanes x 8 pixels
 	const int vec = (n_pixels & 3) == 0 && ((uintptr_t)d_pix & 15) == 0;
 	hipLaunchKernelGGL(k_similarity, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_pix, n_frames, n_pixels, vec, d_counts);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
@@ -1266,11 +1236,11 @@ extern "C" int agmv_hip_gather_dev(agmv_hip_ctx* c, const uint32_t* d_src, size_
                                    size_t n_out, uint32_t* d_dst, void* stream)
 {
 	unsigned blocks;
-	if (need_clip_ctx(c)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	if (n_frames == 0 || n_out == 0) return 0;
 	if (gather_grid(n_out, &blocks)) return -1;
 	hipLaunchKernelGGL(k_gather, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_src, src_frame_pixels, n_frames, d_index, n_out, d_dst);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
@@ -1278,34 +1248,34 @@ extern "C" int agmv_hip_gather_dev(agmv_hip_ctx* c, const uint32_t* d_src, size_
 extern "C" int agmv_hip_pixels_to_xrgb_dev(agmv_hip_ctx* c, int fmt, const void* d_src, size_t frame_pixels, uint32_t n_frames, size_t n_pixels,
                                            uint32_t* d_dst, void* stream)
 {
-	if (need_clip_ctx(c) || bad_pixfmt(fmt) || pf_bad_count(n_pixels, frame_pixels)) return -1;
+	if (agmv_hip_enter(c) || bad_pixfmt(fmt) || pf_bad_count(n_pixels, frame_pixels)) return -1;
 	if (n_frames == 0 || n_pixels == 0) return 0;
 	if (fmt == PF_XRGB32) {
-		if (n_frames == 1 || n_pixels == frame_pixels) CCK(hipMemcpyAsync(d_dst, d_src, (size_t)n_frames * n_pixels * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-		else CCK(hipMemcpy2DAsync(d_dst, n_pixels * 4, d_src, frame_pixels * 4, n_pixels * 4, n_frames, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+		if (n_frames == 1 || n_pixels == frame_pixels) CK(hipMemcpyAsync(d_dst, d_src, (size_t)n_frames * n_pixels * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+		else CK(hipMemcpy2DAsync(d_dst, n_pixels * 4, d_src, frame_pixels * 4, n_pixels * 4, n_frames, hipMemcpyDeviceToDevice, (hipStream_t)stream));
 		return 0;
 	}
 	uint32_t bpf; unsigned blocks;
 	if (pf_grid(n_pixels, n_frames, &bpf, &blocks)) return -1;
 	const int wide = pf_aligned(fmt, d_src, frame_pixels, n_frames) && pf_aligned(PF_XRGB32, d_dst, n_pixels, n_frames);
 	CLIP_LAUNCH(PF_BYTES, k_pix_to_xrgb, blocks, (const uint8_t*)d_src, frame_pixels, clip_frame_bytes(fmt, frame_pixels, 1), n_pixels, bpf, wide, d_dst);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
 extern "C" int agmv_hip_pixels_from_xrgb_dev(agmv_hip_ctx* c, int fmt, const uint32_t* d_src, uint32_t n_frames, size_t n_pixels, void* d_dst, void* stream)
 {
-	if (need_clip_ctx(c) || bad_pixfmt(fmt)) return -1;
+	if (agmv_hip_enter(c) || bad_pixfmt(fmt)) return -1;
 	if (n_frames == 0 || n_pixels == 0) return 0;
 	if (fmt == PF_XRGB32) {
-		CCK(hipMemcpyAsync(d_dst, d_src, (size_t)n_frames * n_pixels * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+		CK(hipMemcpyAsync(d_dst, d_src, (size_t)n_frames * n_pixels * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
 		return 0;
 	}
 	uint32_t bpf; unsigned blocks;
 	if (pf_grid(n_pixels, n_frames, &bpf, &blocks)) return -1;
 	const int wide = pf_aligned(fmt, d_dst, n_pixels, n_frames) && pf_aligned(PF_XRGB32, d_src, n_pixels, n_frames);
 	CLIP_LAUNCH(PF_BYTES, k_pix_from_xrgb, blocks, d_src, n_pixels, clip_frame_bytes(fmt, n_pixels, 1), bpf, wide, (uint8_t*)d_dst);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
@@ -1313,20 +1283,20 @@ extern "C" int agmv_hip_gather_fmt_dev(agmv_hip_ctx* c, int fmt, const void* d_s
                                        size_t n_out, uint32_t* d_dst, void* stream)
 {
 	unsigned blocks;
-	if (need_clip_ctx(c) || bad_pixfmt(fmt)) return -1;
+	if (agmv_hip_enter(c) || bad_pixfmt(fmt)) return -1;
 	if (fmt == PF_XRGB32) return agmv_hip_gather_dev(c, (const uint32_t*)d_src, src_frame_pixels, n_frames, d_index, n_out, d_dst, stream);
 	if (n_frames == 0 || n_out == 0) return 0;
 	if (gather_grid(n_out, &blocks)) return -1;
 	hipLaunchKernelGGL(k_gather_fmt, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_src, fmt, src_frame_pixels,
 	                   clip_frame_bytes(fmt, src_frame_pixels, 1), n_frames, d_index, n_out, d_dst);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
 extern "C" int agmv_hip_histogram_fmt_dev(agmv_hip_ctx* c, int fmt, const void* d_src, size_t frame_pixels, uint32_t n_frames, size_t n_pixels, int quality,
                                           uint32_t* d_hist, void* stream)
 {
-	if (need_clip_ctx(c) || bad_pixfmt(fmt) || pf_bad_count(n_pixels, frame_pixels)) return -1;
+	if (agmv_hip_enter(c) || bad_pixfmt(fmt) || pf_bad_count(n_pixels, frame_pixels)) return -1;
 	if (n_frames == 0 || n_pixels == 0) return 0;
 	if (fmt == PF_XRGB32) {
 		const uint32_t* d_pix = (const uint32_t*)d_src;
@@ -1338,13 +1308,13 @@ extern "C" int agmv_hip_histogram_fmt_dev(agmv_hip_ctx* c, int fmt, const void* 
 	if (pf_grid(n_pixels, n_frames, &bpf, &blocks)) return -1;
 	const int wide = pf_aligned(fmt, d_src, frame_pixels, n_frames);
 	CLIP_LAUNCH(PF_BYTES, k_histogram_fmt, blocks, (const uint8_t*)d_src, frame_pixels, clip_frame_bytes(fmt, frame_pixels, 1), n_pixels, bpf, wide, quality, d_hist);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
 extern "C" int agmv_hip_similarity_fmt_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t n_frames, size_t n_pixels, uint32_t* d_counts, void* stream)
 {
-	if (need_clip_ctx(c) || bad_pixfmt(fmt)) return -1;
+	if (agmv_hip_enter(c) || bad_pixfmt(fmt)) return -1;
 	if (fmt == PF_XRGB32) return agmv_hip_similarity_dev(c, (const uint32_t*)d_src, n_frames, n_pixels, d_counts, stream);
 	const int go = sim_begin(n_pixels, n_frames, d_counts, stream);
 	if (go <= 0) return go;
@@ -1353,7 +1323,7 @@ extern "C" int agmv_hip_similarity_fmt_dev(agmv_hip_ctx* c, int fmt, const void*
 	const size_t frame_bytes = clip_frame_bytes(fmt, n_pixels, 1);
 	if (fmt == PF_BGR24) fmt = PF_RGB24;                         // the grey is a sum: the two 3-byte orders are one kernel
 	CLIP_LAUNCH(PF_BYTES & ~PF_BIT(PF_BGR24), k_similarity_fmt, blocks, (const uint8_t*)d_src, n_frames, n_pixels, frame_bytes, vec, d_counts);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
@@ -1361,25 +1331,25 @@ extern "C" int agmv_hip_similarity_fmt_dev(agmv_hip_ctx* c, int fmt, const void*
 extern "C" int agmv_hip_yuv_to_xrgb_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames, size_t n_pixels, uint32_t* d_dst,
                                         void* stream)
 {
-	if (need_clip_ctx(c) || bad_yuv(fmt, w, h) || yuv_bad_count(n_pixels, w, h)) return -1;
+	if (agmv_hip_enter(c) || bad_yuv(fmt, w, h) || yuv_bad_count(n_pixels, w, h)) return -1;
 	if (n_frames == 0 || n_pixels == 0) return 0;
 	uint32_t bpf; unsigned blocks;
 	const int wide = yuv_wide(fmt, d_src, w, h, n_frames) && pf_aligned(PF_XRGB32, d_dst, n_pixels, n_frames);
 	if (yuv_grid(w, n_pixels, wide, n_frames, &bpf, &blocks)) return -1;
 	CLIP_LAUNCH(PF_YUV, k_yuv_to_xrgb, blocks, (const uint8_t*)d_src, w, h, clip_frame_bytes(fmt, w, h), (uint32_t)n_pixels, bpf, wide, YUV_RD[(fmt >> 8) & 3], d_dst);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
 extern "C" int agmv_hip_yuv_from_xrgb_dev(agmv_hip_ctx* c, int fmt, const uint32_t* d_src, uint32_t w, uint32_t h, uint32_t n_frames, void* d_dst, void* stream)
 {
-	if (need_clip_ctx(c) || bad_yuv(fmt, w, h)) return -1;
+	if (agmv_hip_enter(c) || bad_yuv(fmt, w, h)) return -1;
 	if (n_frames == 0) return 0;
 	uint32_t bpf; unsigned blocks;
 	const int wide = yuv_wide(fmt, d_dst, w, h, n_frames) && pf_aligned(PF_XRGB32, d_src, (size_t)w * h, n_frames);
 	if (yuv_grid(w, (size_t)w * h, wide, n_frames, &bpf, &blocks)) return -1;
 	CLIP_LAUNCH(PF_YUV, k_yuv_from_xrgb, blocks, d_src, w, h, clip_frame_bytes(fmt, w, h), bpf, wide, YUV_WR[(fmt >> 8) & 3], (uint8_t*)d_dst);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
@@ -1387,37 +1357,37 @@ extern "C" int agmv_hip_yuv_gather_dev(agmv_hip_ctx* c, int fmt, const void* d_s
                                        uint32_t* d_dst, void* stream)
 {
 	unsigned blocks;
-	if (need_clip_ctx(c) || bad_yuv(fmt, w, h)) return -1;
+	if (agmv_hip_enter(c) || bad_yuv(fmt, w, h)) return -1;
 	if (n_frames == 0 || n_out == 0) return 0;
 	if (gather_grid(n_out, &blocks)) return -1;
 	CLIP_LAUNCH(PF_YUV, k_yuv_gather, blocks, (const uint8_t*)d_src, w, h, clip_frame_bytes(fmt, w, h), n_frames, d_index, n_out, YUV_RD[(fmt >> 8) & 3], d_dst);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
 extern "C" int agmv_hip_yuv_histogram_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames, size_t n_pixels, int quality,
                                           uint32_t* d_hist, void* stream)
 {
-	if (need_clip_ctx(c) || bad_yuv(fmt, w, h) || yuv_bad_count(n_pixels, w, h)) return -1;
+	if (agmv_hip_enter(c) || bad_yuv(fmt, w, h) || yuv_bad_count(n_pixels, w, h)) return -1;
 	if (n_frames == 0 || n_pixels == 0) return 0;
 	uint32_t bpf; unsigned blocks;
 	const int wide = yuv_wide(fmt, d_src, w, h, n_frames);
 	if (yuv_grid(w, n_pixels, wide, n_frames, &bpf, &blocks)) return -1;
 	CLIP_LAUNCH(PF_YUV, k_yuv_histogram, blocks, (const uint8_t*)d_src, w, h, clip_frame_bytes(fmt, w, h), (uint32_t)n_pixels, bpf, wide, quality, YUV_RD[(fmt >> 8) & 3],
 	            d_hist);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
 extern "C" int agmv_hip_yuv_similarity_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t w, uint32_t h, uint32_t n_frames, uint32_t* d_counts, void* stream)
 {
-	if (need_clip_ctx(c) || bad_yuv(fmt, w, h)) return -1;
+	if (agmv_hip_enter(c) || bad_yuv(fmt, w, h)) return -1;
 	const int go = sim_begin((size_t)w * h, n_frames, d_counts, stream);
 	if (go <= 0) return go;
 	const unsigned blocks = (unsigned)(((size_t)((w + 15) >> 4) * ((h + 1) >> 1) + 255) / 256);    // 256 lanes x one patch
 	const int wide = yuv_wide(fmt, d_src, w, h, n_frames);
 	CLIP_LAUNCH(PF_YUV, k_yuv_similarity, blocks, (const uint8_t*)d_src, n_frames, w, h, clip_frame_bytes(fmt, w, h), wide, YUV_RD[(fmt >> 8) & 3], d_counts);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
@@ -1425,11 +1395,11 @@ extern "C" int agmv_hip_yuv_similarity_dev(agmv_hip_ctx* c, int fmt, const void*
 extern "C" int agmv_hip_scale_area_dev(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t src_w, uint32_t src_h, uint32_t n_frames, uint32_t dst_w, uint32_t dst_h,
                                        uint32_t* d_dst, void* stream)
 {
-	if (need_clip_ctx(c)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	const int yuv = yuv_base(fmt);
 	if (!yuv && bad_pixfmt(fmt)) return -1;
 	if (src_w == 0 || src_h == 0 || dst_w == 0 || dst_h == 0 || dst_w > src_w || dst_h > src_h || (unsigned long long)src_w * src_h > (1ull << 24))
-		return clip_err("agmv_hip: area scale of %u x %u to %u x %u (a downscale of at most 2^24 source pixels is needed)", src_w, src_h, dst_w, dst_h);
+		return agmv_hip_err("agmv_hip: area scale of %u x %u to %u x %u (a downscale of at most 2^24 source pixels is needed)", src_w, src_h, dst_w, dst_h);
 	if (n_frames == 0) return 0;
 	ScaleArgs A;
 	A.src = (const uint8_t*)d_src; A.dst = d_dst;
@@ -1440,7 +1410,7 @@ extern "C" int agmv_hip_scale_area_dev(agmv_hip_ctx* c, int fmt, const void* d_s
 	A.small = (unsigned long long)src_w * dst_w < (1ull << 32);
 	A.m = YUV_RD[(fmt >> 8) & 3];
 	CLIP_LAUNCH(PF_BYTES | PF_YUV | PF_BIT(PF_XRGB32), k_scale_area, (unsigned)(A.items < 65536 ? A.items : 65536), A);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
@@ -1448,15 +1418,15 @@ extern "C" int agmv_hip_scale_area_dev(agmv_hip_ctx* c, int fmt, const void* d_s
 extern "C" int agmv_hip_measure_frames_async(agmv_hip_ctx* c, const uint32_t* d_test, int fmt, const void* d_ref, uint32_t w, uint32_t h, uint32_t n_frames,
                                              void* d_quality, void* stream)
 {
-	if (need_clip_ctx(c)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	const int yuv = yuv_base(fmt);
 	if (yuv ? bad_yuv(fmt, w, h) : bad_pixfmt(fmt)) return -1;
 	if (w == 0 || h == 0 || (w & 3) || (h & 3) || (unsigned long long)w * h > (1ull << 28))
-		return clip_err("agmv_hip: measuring frames of %u x %u (multiples of 4, at most 2^28 pixels, are needed)", w, h);
+		return agmv_hip_err("agmv_hip: measuring frames of %u x %u (multiples of 4, at most 2^28 pixels, are needed)", w, h);
 	if (n_frames == 0) return 0;
-	if (!d_test || !d_ref || !d_quality) return clip_err("agmv_hip: NULL clip or result");
-	if ((uintptr_t)d_test & 3 || (uintptr_t)d_quality & 7) return clip_err("agmv_hip: the test clip needs 4-byte, the result 8-byte alignment");
-	CCK(hipMemsetAsync(d_quality, 0, 96 * (size_t)n_frames, (hipStream_t)stream));
+	if (!d_test || !d_ref || !d_quality) return agmv_hip_err("agmv_hip: NULL clip or result");
+	if ((uintptr_t)d_test & 3 || (uintptr_t)d_quality & 7) return agmv_hip_err("agmv_hip: the test clip needs 4-byte, the result 8-byte alignment");
+	CK(hipMemsetAsync(d_quality, 0, 96 * (size_t)n_frames, (hipStream_t)stream));
 	MeasureArgs A;
 	A.test = d_test; A.ref = (const uint8_t*)d_ref; A.out = (unsigned long long*)d_quality;
 	A.frame_bytes = clip_frame_bytes(fmt, w, h);
@@ -1466,6 +1436,6 @@ extern "C" int agmv_hip_measure_frames_async(agmv_hip_ctx* c, const uint32_t* d_
 	A.wide = yuv ? yuv_wide(fmt, d_ref, w, h, n_frames) : pf_aligned(fmt, d_ref, (size_t)w * h, n_frames);
 	A.m = YUV_RD[(fmt >> 8) & 3];
 	CLIP_LAUNCH(PF_BYTES | PF_YUV | PF_BIT(PF_XRGB32), k_measure, (unsigned)(A.items < 4096 ? A.items : 4096), A);
-	CCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }

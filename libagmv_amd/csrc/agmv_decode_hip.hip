@@ -14,47 +14,12 @@
 // for k_decode the looping form) becomes a kernel's template argument.  Integer/byte work only: no MFMA.
 #include <hip/hip_runtime.h>
 
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
 
-#include "../../include/agmv_hip.h"
-
-// defined in agmv_hip.hip: the library's error text, and of the context: the device, the slot for the work area below, the
-// palette (NULL: none set), the CU count, a timing mark (events 2..7 of agmv_hip_last_kernel_ms); the one geometry check
-int agmv_hip_internal_error(const char* msg);
-int agmv_hip_internal_device(agmv_hip_ctx* c);
-void** agmv_hip_internal_dec_slot(agmv_hip_ctx* c);
-const uint32_t* agmv_hip_internal_palette(agmv_hip_ctx* c, int* mode512);
-int agmv_hip_internal_n_cu(agmv_hip_ctx* c);
-void agmv_hip_internal_ev_mark(agmv_hip_ctx* c, int which, hipStream_t s);
-int agmv_hip_internal_check_geometry(uint32_t w, uint32_t h);
-
-#define FILL_FLAG   0x4Eu   /* include/agmv_defines.h:49 */
-#define NORMAL_FLAG 0x2Fu   /* :50 */
-#define COPY_FLAG   0x5Eu   /* :51 */
-#define FILL_COUNT  14u     /* :52 */
-#define COPY_COUNT  13u     /* :53 */
-
-static int dec_err(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-static int dec_err(const char* fmt, ...)
-{
-	char m[512];
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(m, sizeof(m), fmt, ap);
-	va_end(ap);
-	return agmv_hip_internal_error(m);
-}
-
-static int dec_fail(const char* what, hipError_t e, int line)
-{
-	return dec_err("agmv_hip: %s failed: %s (agmv_decode_hip.hip:%d)", what, hipGetErrorString(e), line);
-}
-#define DCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return dec_fail(#x, e_, __LINE__); } while (0)
+#include "agmv_hip_impl.h"
 
 #ifndef DEC_T_OVERRIDE
 #define DEC_T_OVERRIDE 256
@@ -67,7 +32,7 @@ constexpr int DEC_STAGE = DEC_T * DEC_BPB;   // LDS window for a tile's bitstrea
 constexpr int DEC_SR = DEC_STAGE / 4 / DEC_T;   // dwords of the window each lane carries from global memory to LDS
 constexpr int DEC_MAX_SLICES = 32;           // agmv_hip_parse_decode_frames_dev: GOP ranges whose parse overlaps the reconstruction of the range before
 
-// the decoder's part of a context, behind its dec_ws slot: created by the first parse or decode call, freed by agmv_hip_destroy
+// the decoder's work area of a context (AREA_DEC): created by the first parse or decode call, freed by agmv_hip_destroy
 struct dec_ws {
 	uint32_t* d_dirty;              // decode: bitmap of block positions needing the fix-up
 	size_t dirty_cap;               // in bytes
@@ -85,12 +50,11 @@ struct dec_ws {
 	hipEvent_t ev_slice[DEC_MAX_SLICES];   // ... slice parsed
 };
 
-static dec_ws* dec_area(agmv_hip_ctx* c) { return (dec_ws*)*agmv_hip_internal_dec_slot(c); }
+static dec_ws* dec_area(agmv_hip_ctx* c) { return (dec_ws*)c->ws[AREA_DEC]; }
 
-void agmv_hip_internal_dec_free(void* p)                      // (device of the context is current)
+static void dec_free(void* p)                                 // (device of the context is current)
 {
 	dec_ws* d = (dec_ws*)p;
-	if (!d) return;
 	(void)hipFree(d->d_dirty); (void)hipFree(d->d_parse_ws); (void)hipFree(d->d_fp_ws); (void)hipFree(d->d_nent_own);
 	if (d->ev_fork) (void)hipEventDestroy(d->ev_fork);
 	for (int i = 0; i < DEC_MAX_SLICES; i++) if (d->ev_slice[i]) (void)hipEventDestroy(d->ev_slice[i]);
@@ -101,24 +65,8 @@ void agmv_hip_internal_dec_free(void* p)                      // (device of the 
 // palette: the call parses or decodes -- a palette must be set, and the context has its work area afterwards
 static int need_dec_ctx(agmv_hip_ctx* c, bool palette)
 {
-	if (!c) return dec_err("agmv_hip: NULL context");
-	if (palette && !agmv_hip_internal_palette(c, nullptr)) return dec_err("agmv_hip: agmv_hip_set_palette was not called");
-	DCK(hipSetDevice(agmv_hip_internal_device(c)));
-	void** slot = agmv_hip_internal_dec_slot(c);
-	if (palette && !*slot && !(*slot = calloc(1, sizeof(dec_ws)))) return dec_err("agmv_hip: out of host memory");
-	return 0;
-}
-
-// grow a device buffer of the work area to at least `bytes` (the contents are not kept)
-template <class T>
-static int dec_grow(T*& d_buf, size_t& cap, size_t bytes)
-{
-	if (bytes <= cap) return 0;
-	if (d_buf) DCK(hipFree(d_buf));
-	d_buf = nullptr; cap = 0;
-	DCK(hipMalloc(&d_buf, bytes));
-	cap = bytes;
-	return 0;
+	if (agmv_hip_enter(c, palette)) return -1;
+	return palette && !agmv_hip_area(c, AREA_DEC, sizeof(dec_ws), dec_free) ? -1 : 0;
 }
 
 // f(std::bool_constant<flag>()...): every run-time flag becomes a compile-time one
@@ -129,37 +77,7 @@ static void dec_flags(F&& f, bool flag, Rest... rest) { dec_flags([&](auto... r_
 // launch k<flags...> on stream s, then check the launch
 #define DEC_LAUNCH(k, grid, block, s, A, ...) do { \
 	dec_flags([&](auto... b_) { hipLaunchKernelGGL((k<decltype(b_)::value...>), grid, block, 0, s, A); }, __VA_ARGS__); \
-	DCK(hipGetLastError()); } while (0)
-
-static int dec_mode512(agmv_hip_ctx* c) { int m = 0; (void)agmv_hip_internal_palette(c, &m); return m; }
-
-// Workgroup barrier that orders LDS only, and the wave-wide scans on the DPP lanes: as in agmv_hip.hip, which explains them
-__device__ __forceinline__ void lds_barrier()
-{
-	asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_or0(uint32_t x)       // lanes without a source (or masked off) read 0
-{
-	return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROW_MASK, 0xF, false);
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, int)
-{
-	x += dpp_or0<0x111, 0xF>(x);                               // row_shr:1
-	x += dpp_or0<0x112, 0xF>(x);                               // row_shr:2
-	x += dpp_or0<0x114, 0xF>(x);                               // row_shr:4
-	x += dpp_or0<0x118, 0xF>(x);                               // row_shr:8
-	x += dpp_or0<0x142, 0xA>(x);                               // row_bcast:15 -> rows 1 and 3
-	x += dpp_or0<0x143, 0xC>(x);                               // row_bcast:31 -> rows 2 and 3
-	return x;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x)      // the same value in every lane
-{
-	return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(x, 0), 63);
-}
+	CK(hipGetLastError()); } while (0)
 
 // ----------------------------------------------------------------------------------------------
 // decode side
@@ -1592,7 +1510,7 @@ __global__ __launch_bounds__(64) void k_fixup(DecArgs A)
 
 static int check_slab(const uint8_t* d_bits, size_t stride)
 {
-	if ((stride & 3u) || stride < 4 || ((uintptr_t)d_bits & 3u)) return dec_err("agmv_hip: bitstream slab and stride must be 4-byte aligned");
+	if ((stride & 3u) || stride < 4 || ((uintptr_t)d_bits & 3u)) return agmv_hip_err("agmv_hip: bitstream slab and stride must be 4-byte aligned");
 	return 0;
 }
 
@@ -1632,7 +1550,7 @@ static ParseMode parse_mode()                                  // AGMV_HIP_PARSE
 // 8 / 16 / 32 / 64 / 128 / 256 per frame -> 2.85 / 2.30 / 1.96 / 1.87 / 1.83 / 1.84 ms)
 static uint32_t parse_grid_x(agmv_hip_ctx* c, uint32_t n_frames, size_t cap)
 {
-	uint32_t gx = (uint32_t)(((size_t)agmv_hip_internal_n_cu(c) * 512 + n_frames - 1) / n_frames);
+	uint32_t gx = (uint32_t)(((size_t)c->n_cu * 512 + n_frames - 1) / n_frames);
 	if (gx < 32) gx = 32;
 	if (gx > 256) gx = 256;
 	if (gx > cap) gx = (uint32_t)cap;
@@ -1645,9 +1563,9 @@ static int parse_launch_robust(agmv_hip_ctx* c, const DecRows& r, size_t ws_fram
                                const uint32_t* fstate, const uint32_t* nbad, unsigned long long* vm, uint32_t maxR)
 {
 	const size_t cpf = (r.stride + PC) / PC, maxchunks = cpf * ws_frames;
-	if (maxchunks >> 32) { dec_err("agmv_hip: parser batch too large (%zu chunk rows)", maxchunks); return -1; }
+	if (maxchunks >> 32) return agmv_hip_err("agmv_hip: parser batch too large (%zu chunk rows)", maxchunks);
 	dec_ws* d = dec_area(c);
-	if (dec_grow(d->d_parse_ws, d->parse_ws_cap, (maxchunks + (maxchunks * 33 + 1) / 2 + 16) * 4)) return -1;   // dwords: centry | summ (u16)
+	CK(agmv_hip_dev_grow(&d->d_parse_ws, &d->parse_ws_cap, (maxchunks + (maxchunks * 33 + 1) / 2 + 16) * 4, 1));   // dwords: centry | summ (u16)
 	ParseArgs A;
 	memset(&A, 0, sizeof(A));
 	A.bits = r.bits; A.stride = r.stride; A.bpos = r.bpos; A.offsets = r.offsets; A.nentered = r.nentered;
@@ -1657,10 +1575,10 @@ static int parse_launch_robust(agmv_hip_ctx* c, const DecRows& r, size_t ws_fram
 	// FS_BAD at once -- with one row per frame the three gated launches cost 0.03 ms per 1024 frames for zero frames to parse
 	const uint32_t n = r.n_frames;
 	const dim3 grid(parse_grid_x(c, n, fstate && cpf > 32 ? 32 : cpf), fstate ? (n < 64u ? n : 64u) : (n < 65535u ? n : 65535u));
-	const int m512 = dec_mode512(c);
+	const int m512 = c->mode512;
 	DEC_LAUNCH(k_parse_chunks, grid, dim3(64), s, A, m512);
 	hipLaunchKernelGGL(k_parse_stitch, dim3(fstate ? (n < 1024u ? n : 1024u) : n), dim3(64), 0, s, A);
-	DCK(hipGetLastError());
+	CK(hipGetLastError());
 	DEC_LAUNCH(k_parse_emit, grid, dim3(64), s, A, m512);
 	return 0;
 }
@@ -1675,12 +1593,12 @@ static int parse_launch(agmv_hip_ctx* c, const DecRows& r, size_t ws_frames, hip
 	dec_ws* d = dec_area(c);
 	d->d_fp_fstate = nullptr; d->fp_frames = 0;
 	if (!bm && (n_frames > 65535u || robust_only)) return parse_launch_robust(c, r, ws_frames, s, nullptr, nullptr, nullptr, 0);
-	if (n_frames > 65535u) { dec_err("agmv_hip: more than 65535 frames in one parser launch"); return -1; }
+	if (n_frames > 65535u) return agmv_hip_err("agmv_hip: more than 65535 frames in one parser launch");
 	const size_t maxR = (r.stride + FRB - 1) / FRB + 1, nreg = maxR * ws_frames;
 	const uint32_t tpfd = (r.nblk + DEC_T - 1) / DEC_T;
 	const size_t b_rec = nreg * sizeof(uint4), b_vm = nreg * FOWN * 8, b_kb = nreg * 4, b_fs = ((ws_frames * 4 + 15) & ~(size_t)15);
 	const size_t b_tx = bm ? (((size_t)ws_frames * (tpfd + 1) * 4 + 15) & ~(size_t)15) : 0;
-	if (dec_grow(d->d_fp_ws, d->fp_ws_cap, b_rec + b_vm + b_kb + b_fs + b_tx + 16)) return -1;
+	CK(agmv_hip_dev_grow(&d->d_fp_ws, &d->fp_ws_cap, b_rec + b_vm + b_kb + b_fs + b_tx + 16, 1));
 	FpArgs A;
 	memset(&A, 0, sizeof(A));
 	A.bits = r.bits; A.stride = r.stride; A.bpos = r.bpos; A.offsets = r.offsets; A.nentered = r.nentered;
@@ -1701,20 +1619,20 @@ static int parse_launch(agmv_hip_ctx* c, const DecRows& r, size_t ws_frames, hip
 	}
 	const dim3 grid(gx, gy);
 	if (robust_only) {                                         // debugging aid: every frame through the robust kernels (bitmap form)
-		DCK(hipMemsetAsync(A.tidx, 0xFF, (size_t)n_frames * (tpfd + 1) * 4, s));   // TIDX_NONE (otherwise k_fp_finish's job; nbad: k_fp_walk's)
+		CK(hipMemsetAsync(A.tidx, 0xFF, (size_t)n_frames * (tpfd + 1) * 4, s));   // TIDX_NONE (otherwise k_fp_finish's job; nbad: k_fp_walk's)
 		// k_parse_chunks clears the entry bitmap words up to a frame's last chunk, k_fp_tiles / k_decode read up to the end of
 		// its last region: without k_fp_walk (which writes every word of a region) the words in between are cleared here
-		DCK(hipMemsetAsync(A.vm, 0, (size_t)n_frames * maxR * FOWN * 8, s));
-		DCK(hipMemsetD32Async((hipDeviceptr_t)A.fstate, (int)FS_BAD, n_frames, s));
-		DCK(hipMemsetD32Async((hipDeviceptr_t)A.nbad, (int)n_frames, 1, s));
+		CK(hipMemsetAsync(A.vm, 0, (size_t)n_frames * maxR * FOWN * 8, s));
+		CK(hipMemsetD32Async((hipDeviceptr_t)A.fstate, (int)FS_BAD, n_frames, s));
+		CK(hipMemsetD32Async((hipDeviceptr_t)A.nbad, (int)n_frames, 1, s));
 	} else {
-		DEC_LAUNCH(k_fp_walk, grid, dim3(64), s, A, dec_mode512(c));
-		DEC_LAUNCH(k_fp_finish, dim3(n_frames), dim3(64), s, A, dec_mode512(c));
+		DEC_LAUNCH(k_fp_walk, grid, dim3(64), s, A, c->mode512);
+		DEC_LAUNCH(k_fp_finish, dim3(n_frames), dim3(64), s, A, c->mode512);
 	}
 	d->d_fp_fstate = A.fstate; d->fp_frames = n_frames;
 	if (!bm) {
 		hipLaunchKernelGGL(k_fp_expand, dim3(gx, n_frames), dim3(64), 0, s, A);   // one row per frame (a quarter / an eighth of gx: 0.179 / 0.188 against 0.169 ms per 256 frames)
-		DCK(hipGetLastError());
+		CK(hipGetLastError());
 		return parse_launch_robust(c, r, ws_frames, s, A.fstate, A.nbad, nullptr, 0);
 	}
 	// bitmap form: the frames that could not be proven get their entry BITS from the robust kernels, are counted and
@@ -1722,7 +1640,7 @@ static int parse_launch(agmv_hip_ctx* c, const DecRows& r, size_t ws_frames, hip
 	bm->vm = A.vm; bm->kb = A.kb; bm->tidx = A.tidx; bm->maxR = A.maxR;
 	if (parse_launch_robust(c, r, ws_frames, s, A.fstate, A.nbad, A.vm, A.maxR)) return -1;
 	hipLaunchKernelGGL(k_fp_tiles, dim3(gx / 2 ? gx / 2 : 1, gy), dim3(64), 0, s, A);
-	DCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
@@ -1731,20 +1649,20 @@ extern "C" int agmv_hip_parse_frames_dev(agmv_hip_ctx* c, const uint8_t* d_bits,
                                          void* stream)
 {
 	if (need_dec_ctx(c, true)) return -1;
-	if (agmv_hip_internal_check_geometry(w, h)) return -1;
+	if (agmv_hip_check_geometry(w, h)) return -1;
 	if (n_frames == 0) return 0;
 	const DecRows r = {d_bits, stride, d_bpos, d_offsets, d_nentered, n_frames, (w / 4) * (h / 4)};
 	hipStream_t s = (hipStream_t)stream;
 	if (parse_mode() == PARSE_SERIAL) {                        // debugging aid: one lane per frame
 		hipLaunchKernelGGL(k_parse_serial, dim3((n_frames + 63) / 64), dim3(64), 0, s, d_bits,
-		                   (unsigned long long)stride, d_bpos, n_frames, r.nblk, dec_mode512(c), d_offsets, d_nentered);
-		DCK(hipGetLastError());
+		                   (unsigned long long)stride, d_bpos, n_frames, r.nblk, c->mode512, d_offsets, d_nentered);
+		CK(hipGetLastError());
 		return 0;
 	}
 	if (check_slab(d_bits, stride)) return -1;
-	agmv_hip_internal_ev_mark(c, 2, s);
+	agmv_hip_ev_mark(c, 2, s);
 	if (parse_launch(c, r, n_frames, s, nullptr)) return -1;
-	agmv_hip_internal_ev_mark(c, 3, s);
+	agmv_hip_ev_mark(c, 3, s);
 	return 0;
 }
 
@@ -1753,10 +1671,10 @@ extern "C" int agmv_hip_parse_fallback_frames(agmv_hip_ctx* c, void* stream)
 	if (need_dec_ctx(c, false)) return -1;
 	const dec_ws* d = dec_area(c);
 	if (!d || !d->d_fp_fstate || d->fp_frames == 0) return 0;
-	DCK(hipStreamSynchronize((hipStream_t)stream));
+	CK(hipStreamSynchronize((hipStream_t)stream));
 	uint32_t* h = (uint32_t*)malloc((size_t)d->fp_frames * 4);
-	if (!h) { dec_err("agmv_hip: out of host memory"); return -1; }
-	if (hipMemcpy(h, d->d_fp_fstate, (size_t)d->fp_frames * 4, hipMemcpyDeviceToHost) != hipSuccess) { free(h); dec_err("agmv_hip: D2H failed"); return -1; }
+	if (!h) return agmv_hip_err("agmv_hip: out of host memory");
+	if (hipMemcpy(h, d->d_fp_fstate, (size_t)d->fp_frames * 4, hipMemcpyDeviceToHost) != hipSuccess) { free(h); agmv_hip_err("agmv_hip: D2H failed"); return -1; }
 	int n = 0;
 	for (uint32_t i = 0; i < d->fp_frames; i++) n += h[i] != FS_OK;
 	free(h);
@@ -1767,19 +1685,19 @@ extern "C" int agmv_hip_parse_fallback_frames(agmv_hip_ctx* c, void* stream)
 // caller has that done (k_fp_tiles), clears it
 static int decode_prepare(agmv_hip_ctx* c, DecArgs& A, const DecRows& r, const DecPix& px, hipStream_t s, bool clear)
 {
-	if (((uintptr_t)px.out & 15u) || ((uintptr_t)px.prev & 15u) || ((uintptr_t)px.prev_iframe & 15u)) return dec_err("agmv_hip: pixel buffers must be 16-byte aligned");
+	if (((uintptr_t)px.out & 15u) || ((uintptr_t)px.prev & 15u) || ((uintptr_t)px.prev_iframe & 15u)) return agmv_hip_err("agmv_hip: pixel buffers must be 16-byte aligned");
 	if (check_slab(r.bits, r.stride)) return -1;
 	memset(&A, 0, sizeof(A));
 	A.bits = r.bits; A.stride = r.stride; A.bpos = r.bpos; A.offsets = r.offsets; A.nentered = r.nentered;
-	A.out = px.out; A.pal = agmv_hip_internal_palette(c, nullptr); A.prev = px.prev; A.prev_iframe = px.prev_iframe;
+	A.out = px.out; A.pal = c->d_pal; A.prev = px.prev; A.prev_iframe = px.prev_iframe;
 	A.n_frames = r.n_frames; A.w = px.w; A.h = px.h; A.bw = px.w / 4; A.nblk = r.nblk;
 	A.tpf = (A.nblk + DEC_T - 1) / DEC_T;
 	A.first_fc = px.first_fc; A.phase = px.first_fc & 3u; A.n_groups = (r.n_frames + A.phase + 3) / 4;
 	const size_t nwords = dirty_words(A.nblk);
 	dec_ws* d = dec_area(c);                                   // (+ part 0's "depends" word of a call cut into parts: written, never cleared)
-	if (dec_grow(d->d_dirty, d->dirty_cap, (nwords + 1) * 4)) return -1;
+	CK(agmv_hip_dev_grow(&d->d_dirty, &d->dirty_cap, (nwords + 1) * 4, 1));
 	A.dirty = d->d_dirty; d->dep_split = false;
-	if (clear) DCK(hipMemsetAsync(d->d_dirty, 0, nwords * 4, s));
+	if (clear) CK(hipMemsetAsync(d->d_dirty, 0, nwords * 4, s));
 	return 0;
 }
 
@@ -1791,13 +1709,13 @@ static int decode_launch(agmv_hip_ctx* c, DecArgs A, uint32_t g0, uint32_t g1, h
 		const long n = atol(e);
 		if (n > 0 && (unsigned long)n < nwg) nwg = (uint32_t)n;
 	}
-	DEC_LAUNCH(k_decode, dim3(nwg), dim3(DEC_T), s, A, dec_mode512(c), A.vm != nullptr, nwg < A.n_items);   // <mode512, bitmap form, looping>
+	DEC_LAUNCH(k_decode, dim3(nwg), dim3(DEC_T), s, A, c->mode512, A.vm != nullptr, nwg < A.n_items);   // <mode512, bitmap form, looping>
 	return 0;
 }
 
 static int fixup_launch(agmv_hip_ctx* c, const DecArgs& A, hipStream_t s)
 {
-	DEC_LAUNCH(k_fixup, dim3((A.nblk + 63) / 64), dim3(64), s, A, dec_mode512(c), A.vm != nullptr);   // <mode512, bitmap form>
+	DEC_LAUNCH(k_fixup, dim3((A.nblk + 63) / 64), dim3(64), s, A, c->mode512, A.vm != nullptr);   // <mode512, bitmap form>
 	return 0;
 }
 
@@ -1807,17 +1725,17 @@ extern "C" int agmv_hip_decode_frames_dev(agmv_hip_ctx* c, const uint8_t* d_bits
                                           const uint32_t* d_prev, const uint32_t* d_prev_iframe, void* stream)
 {
 	if (need_dec_ctx(c, true)) return -1;
-	if (agmv_hip_internal_check_geometry(w, h)) return -1;
+	if (agmv_hip_check_geometry(w, h)) return -1;
 	if (n_frames == 0) return 0;
 	hipStream_t s = (hipStream_t)stream;
 	const DecRows r = {d_bits, stride, d_bpos, const_cast<uint32_t*>(d_offsets), const_cast<uint32_t*>(d_nentered), n_frames, (w / 4) * (h / 4)};   // (only read: no parser runs here)
 	const DecPix px = {w, h, first_fc, d_out, d_prev, d_prev_iframe};
 	DecArgs A;
 	if (decode_prepare(c, A, r, px, s, true)) return -1;
-	agmv_hip_internal_ev_mark(c, 4, s);
+	agmv_hip_ev_mark(c, 4, s);
 	if (decode_launch(c, A, 0, A.n_groups, s)) return -1;
 	if (fixup_launch(c, A, s)) return -1;
-	agmv_hip_internal_ev_mark(c, 5, s);
+	agmv_hip_ev_mark(c, 5, s);
 	return 0;
 }
 
@@ -1831,7 +1749,7 @@ extern "C" int agmv_hip_parse_decode_frames_dev(agmv_hip_ctx* c, const uint8_t* 
                                                 const uint32_t* d_prev, const uint32_t* d_prev_iframe, void* stream)
 {
 	if (need_dec_ctx(c, true)) return -1;
-	if (agmv_hip_internal_check_geometry(w, h)) return -1;
+	if (agmv_hip_check_geometry(w, h)) return -1;
 	if (n_frames == 0) return 0;
 	hipStream_t s = (hipStream_t)stream;
 	const DecRows r = {d_bits, stride, d_bpos, d_offsets, d_nentered, n_frames, (w / 4) * (h / 4)};
@@ -1846,30 +1764,30 @@ extern "C" int agmv_hip_parse_decode_frames_dev(agmv_hip_ctx* c, const uint8_t* 
 	const uint32_t gps = (A.n_groups + nsl - 1) / nsl;         // GOPs per range
 	auto first_frame = [&](uint32_t g) -> uint32_t { const long f = (long)g * 4 - (long)A.phase; return f < 0 ? 0u : ((uint32_t)f > n_frames ? n_frames : (uint32_t)f); };
 	const size_t ws_frames = (size_t)gps * 4;
-	agmv_hip_internal_ev_mark(c, 6, s);
+	agmv_hip_ev_mark(c, 6, s);
 	if (nsl == 1) {
 		if (parse_launch(c, r, n_frames, s, nullptr)) return -1;
 		if (decode_launch(c, A, 0, A.n_groups, s)) return -1;
 	} else {
 		dec_ws* d = dec_area(c);
 		if (!d->aux_stream) {
-			DCK(hipStreamCreateWithFlags(&d->aux_stream, hipStreamNonBlocking));
-			DCK(hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming));
-			for (int i = 0; i < DEC_MAX_SLICES; i++) DCK(hipEventCreateWithFlags(&d->ev_slice[i], hipEventDisableTiming));
+			CK(hipStreamCreateWithFlags(&d->aux_stream, hipStreamNonBlocking));
+			CK(hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming));
+			for (int i = 0; i < DEC_MAX_SLICES; i++) CK(hipEventCreateWithFlags(&d->ev_slice[i], hipEventDisableTiming));
 		}
-		DCK(hipEventRecord(d->ev_fork, s));                     // the bitstreams are complete on the caller's stream
-		DCK(hipStreamWaitEvent(d->aux_stream, d->ev_fork, 0));
+		CK(hipEventRecord(d->ev_fork, s));                     // the bitstreams are complete on the caller's stream
+		CK(hipStreamWaitEvent(d->aux_stream, d->ev_fork, 0));
 		uint32_t k = 0;
 		for (uint32_t g0 = 0; g0 < A.n_groups; g0 += gps, k++) {
 			const uint32_t g1 = g0 + gps < A.n_groups ? g0 + gps : A.n_groups;
 			if (parse_launch(c, rows_range(r, first_frame(g0), first_frame(g1)), ws_frames, d->aux_stream, nullptr)) return -1;
-			DCK(hipEventRecord(d->ev_slice[k], d->aux_stream));
-			DCK(hipStreamWaitEvent(s, d->ev_slice[k], 0));
+			CK(hipEventRecord(d->ev_slice[k], d->aux_stream));
+			CK(hipStreamWaitEvent(s, d->ev_slice[k], 0));
 			if (decode_launch(c, A, g0, g1, s)) return -1;
 		}
 	}
 	if (fixup_launch(c, A, s)) return -1;
-	agmv_hip_internal_ev_mark(c, 7, s);
+	agmv_hip_ev_mark(c, 7, s);
 	return 0;
 }
 
@@ -1883,18 +1801,18 @@ extern "C" int agmv_hip_decode_bitstreams_dev(agmv_hip_ctx* c, const uint8_t* d_
                                               const uint32_t* d_prev, const uint32_t* d_prev_iframe, void* stream)
 {
 	if (need_dec_ctx(c, true)) return -1;
-	if (agmv_hip_internal_check_geometry(w, h)) return -1;
+	if (agmv_hip_check_geometry(w, h)) return -1;
 	if (n_frames == 0) return 0;
 	hipStream_t s = (hipStream_t)stream;
 	dec_ws* d = dec_area(c);
 	if (!d_nentered) {
-		if (dec_grow(d->d_nent_own, d->nent_cap, (size_t)n_frames * 4)) return -1;
+		CK(agmv_hip_dev_grow(&d->d_nent_own, &d->nent_cap, (size_t)n_frames * 4, 1));
 		d_nentered = d->d_nent_own;
 	}
 	const DecRows all = {d_bits, stride, d_bpos, nullptr, d_nentered, n_frames, (w / 4) * (h / 4)};
 	const size_t npx = (size_t)w * h;
 	constexpr uint32_t PART = 65532u;                          // a multiple of 4
-	agmv_hip_internal_ev_mark(c, 6, s);
+	agmv_hip_ev_mark(c, 6, s);
 	for (uint32_t f0 = 0; f0 < n_frames;) {
 		uint32_t f1 = n_frames;
 		if (f1 - f0 > PART) { f1 = f0 + PART; f1 -= (first_fc + f1) & 3u; }   // the next part starts with an I-frame
@@ -1904,21 +1822,21 @@ extern "C" int agmv_hip_decode_bitstreams_dev(agmv_hip_ctx* c, const uint8_t* d_
 		                   f0 == 0 ? d_prev_iframe : d_out + (size_t)(f0 - 4) * npx};
 		DecArgs A;
 		if (decode_prepare(c, A, r, px, s, false)) return -1;
-		agmv_hip_internal_ev_mark(c, 2, s);
+		agmv_hip_ev_mark(c, 2, s);
 		if (parse_launch(c, r, r.n_frames, s, &A)) return -1;   // fills in A.vm, A.kb, A.tidx, A.maxR
-		agmv_hip_internal_ev_mark(c, 3, s);
-		agmv_hip_internal_ev_mark(c, 4, s);
+		agmv_hip_ev_mark(c, 3, s);
+		agmv_hip_ev_mark(c, 4, s);
 		if (decode_launch(c, A, 0, A.n_groups, s)) return -1;
 		if (fixup_launch(c, A, s)) return -1;
-		agmv_hip_internal_ev_mark(c, 5, s);
+		agmv_hip_ev_mark(c, 5, s);
 		if (f0 == 0 && f1 < n_frames) {                        // later parts depend on the parts before them, not on the caller:
 			const size_t dw = (A.nblk + 31) / 32 + 1;          // the call's prior dependence is part 0's (the next k_fp_tiles clears it)
-			DCK(hipMemcpyAsync(d->d_dirty + dw + 1, d->d_dirty + dw, 4, hipMemcpyDeviceToDevice, s));
+			CK(hipMemcpyAsync(d->d_dirty + dw + 1, d->d_dirty + dw, 4, hipMemcpyDeviceToDevice, s));
 		}
 		f0 = f1;
 	}
 	d->dep_split = n_frames > PART;
-	agmv_hip_internal_ev_mark(c, 7, s);
+	agmv_hip_ev_mark(c, 7, s);
 	return 0;
 }
 
@@ -1926,11 +1844,11 @@ extern "C" int agmv_hip_decode_prior_dependent(agmv_hip_ctx* c, uint32_t w, uint
 {
 	if (need_dec_ctx(c, false)) return -1;
 	const dec_ws* d = dec_area(c);
-	if (!d || !d->d_dirty) { dec_err("agmv_hip: no decode has run on this context"); return -1; }
+	if (!d || !d->d_dirty) return agmv_hip_err("agmv_hip: no decode has run on this context");
 	const size_t nblk = (size_t)(w / 4) * (h / 4);
 	uint32_t v = 0;
-	DCK(hipStreamSynchronize((hipStream_t)stream));
-	DCK(hipMemcpy(&v, d->d_dirty + (nblk + 31) / 32 + (d->dep_split ? 2 : 1), 4, hipMemcpyDeviceToHost));
+	CK(hipStreamSynchronize((hipStream_t)stream));
+	CK(hipMemcpy(&v, d->d_dirty + (nblk + 31) / 32 + (d->dep_split ? 2 : 1), 4, hipMemcpyDeviceToHost));
 	return v ? 1 : 0;
 }
 
@@ -1939,7 +1857,7 @@ extern "C" int agmv_hip_decode_frames(agmv_hip_ctx* c, const uint8_t* h_bits, si
                                       const uint32_t* h_prev, const uint32_t* h_prev_iframe)
 {
 	if (need_dec_ctx(c, true)) return -1;
-	if (agmv_hip_internal_check_geometry(w, h)) return -1;
+	if (agmv_hip_check_geometry(w, h)) return -1;
 	if (n_frames == 0) return 0;
 	const size_t npx = (size_t)w * h, nblk = npx / 16;
 	uint8_t* d_bits = nullptr;
@@ -1950,17 +1868,17 @@ extern "C" int agmv_hip_decode_frames(agmv_hip_ctx* c, const uint8_t* h_bits, si
 		    hipMalloc(&d_off, 4 * nblk * n_frames) != hipSuccess || hipMalloc(&d_ne, 4 * (size_t)n_frames) != hipSuccess ||
 		    hipMalloc(&d_out, 4 * npx * n_frames) != hipSuccess || (h_prev && hipMalloc(&d_prev, 4 * npx) != hipSuccess) ||
 		    (h_prev_iframe && hipMalloc(&d_pi, 4 * npx) != hipSuccess)) {
-			dec_err("agmv_hip: device allocation failed"); break;
+			agmv_hip_err("agmv_hip: device allocation failed"); break;
 		}
 		if (hipMemcpy(d_bits, h_bits, stride * n_frames, hipMemcpyHostToDevice) != hipSuccess ||
 		    hipMemcpy(d_bpos, h_bpos, 4 * (size_t)n_frames, hipMemcpyHostToDevice) != hipSuccess ||
 		    (h_prev && hipMemcpy(d_prev, h_prev, 4 * npx, hipMemcpyHostToDevice) != hipSuccess) ||
 		    (h_prev_iframe && hipMemcpy(d_pi, h_prev_iframe, 4 * npx, hipMemcpyHostToDevice) != hipSuccess)) {
-			dec_err("agmv_hip: H2D failed"); break;
+			agmv_hip_err("agmv_hip: H2D failed"); break;
 		}
 		if (agmv_hip_parse_frames_dev(c, d_bits, stride, d_bpos, n_frames, w, h, d_off, d_ne, nullptr)) break;
 		if (agmv_hip_decode_frames_dev(c, d_bits, stride, d_bpos, d_off, d_ne, n_frames, w, h, first_fc, d_out, d_prev, d_pi, nullptr)) break;
-		if (hipMemcpy(h_out, d_out, 4 * npx * n_frames, hipMemcpyDeviceToHost) != hipSuccess) { dec_err("agmv_hip: D2H failed"); break; }
+		if (hipMemcpy(h_out, d_out, 4 * npx * n_frames, hipMemcpyDeviceToHost) != hipSuccess) { agmv_hip_err("agmv_hip: D2H failed"); break; }
 		rc = 0;
 	} while (0);
 	(void)hipFree(d_bits); (void)hipFree(d_bpos); (void)hipFree(d_off); (void)hipFree(d_ne); (void)hipFree(d_out); (void)hipFree(d_prev); (void)hipFree(d_pi);

@@ -19,32 +19,33 @@
 // Integer/byte work only: no MFMA. The bound is HBM (4 B/px in, usize out).
 #include <hip/hip_runtime.h>
 
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <pthread.h>
 
-#include "../../include/agmv_hip.h"
-
-#define FILL_FLAG   0x4Eu   /* include/agmv_defines.h:49 */
-#define NORMAL_FLAG 0x2Fu   /* :50 */
-#define COPY_FLAG   0x5Eu   /* :51 */
-#define FILL_COUNT  14u     /* :52 */
-#define COPY_COUNT  13u     /* :53 */
+#include "agmv_hip_impl.h"
 
 // ----------------------------------------------------------------------------------------------
 // error plumbing
 // ----------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
 
-static int fail(const char* what, hipError_t e, int line)
+int agmv_hip_err(const char* fmt, ...)
 {
-	snprintf(g_err, sizeof(g_err), "agmv_hip: %s failed: %s (agmv_hip.hip:%d)", what, hipGetErrorString(e), line);
+	va_list ap;
+	va_start(ap, fmt);
+	vsnprintf(g_err, sizeof(g_err), fmt, ap);
+	va_end(ap);
 	return -1;
 }
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(#x, e_, __LINE__); } while (0)
-#define CKP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fail(#x, e_, __LINE__); return nullptr; } } while (0)
+
+int agmv_hip_hip_failed(const char* what, hipError_t e, const char* file, int line)
+{
+	return agmv_hip_err("agmv_hip: %s failed: %s (%s:%d)", what, hipGetErrorString(e), file, line);
+}
 
 extern "C" const char* agmv_hip_last_error(void) { return g_err; }
 
@@ -76,59 +77,6 @@ constexpr uint32_t LUT_ENTRIES = 1u << 28;   // index space of the table (see lu
 
 constexpr unsigned long long ST_AGG = 1ull << 32;     // look-back status tags (high word)
 constexpr unsigned long long ST_PREFIX = 2ull << 32;
-
-struct agmv_hip_ctx {
-	int device;
-	int mode512;
-	int have_palette;
-	uint16_t* d_lut;                // 2^24 entries
-	uint32_t* d_mtx;                // 512 * MROW dwords
-	uint32_t* d_pal;                // 512 colours (p0 | p1)
-	struct lut_share* share;        // owner of the three tables above (shared between the contexts of a device that hold the same palette)
-	unsigned long long* d_status;   // look-back words
-	size_t status_cap;              // in words
-	uint32_t* d_ctrl;               // [0] ticket, [1] error, padded to 16 B
-	uint16_t* d_ient_tmp;           // encode: I-frame entries written by a batch that also READS the caller's plane
-	size_t ient_cap;                // in entries
-	int enc_grid;                   // resident workgroups for the persistent encode kernel
-	int n_cu;
-	int timing;                     // record HIP events around the three hot kernels
-	hipEvent_t ev[8];               // encode, parse, decode, parse||decode pipeline: start/stop
-	hipEvent_t ev_enc;              // end of the last encode launch (encodes of one context share status / control words)
-	hipStream_t enc_stream;         // ... and the stream it went to
-	int have_enc;
-	uint32_t* d_nn_pal;             // agmv_hip_nearest: palette, pixels, entries (grown on demand)
-	uint32_t* d_nn_pix;
-	uint16_t* d_nn_ent;
-	size_t nn_cap;
-	void* dec_ws;                   // the decoder's work areas, its stream and events (agmv_decode_hip.hip)
-	void* lz_ws;                    // agmv_hip_lzss_frames_dev: work areas (agmv_lz_hip.hip)
-	void* lzd_ws;                   // agmv_hip_lz_decode_*: work areas (agmv_lz_decode_hip.hip)
-	void* lz77_ws;                  // agmv_hip_lz77_*: work areas (agmv_lz77_hip.hip)
-	void* pal_ws;                   // agmv_hip_palette_refine_dev: sums and flag of a pass, device memory (agmv_palette_hip.hip)
-};
-
-// for agmv_lz_hip.hip, the LZSS stage: the error text, the context's slot for its work areas, the device
-int agmv_hip_internal_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); return -1; }
-void** agmv_hip_internal_lz_slot(agmv_hip_ctx* c) { return &c->lz_ws; }
-int agmv_hip_internal_device(agmv_hip_ctx* c) { return c->device; }
-void agmv_hip_internal_lz_free(void* p);
-// ... and for agmv_lz_decode_hip.hip, the LZ stage of the decoder
-void** agmv_hip_internal_lzd_slot(agmv_hip_ctx* c) { return &c->lzd_ws; }
-void agmv_hip_internal_lzd_free(void* p);
-void** agmv_hip_internal_lz77_slot(agmv_hip_ctx* c) { return &c->lz77_ws; }
-void agmv_hip_internal_lz77_free(void* p);
-void** agmv_hip_internal_pal_slot(agmv_hip_ctx* c) { return &c->pal_ws; }
-void agmv_hip_internal_pal_free(void* p);
-// ... and for agmv_decode_hip.hip, the decoder: also the palette (NULL: none set), the CU count, ev_mark and check_geometry (below)
-void** agmv_hip_internal_dec_slot(agmv_hip_ctx* c) { return &c->dec_ws; }
-void agmv_hip_internal_dec_free(void* p);
-const uint32_t* agmv_hip_internal_palette(agmv_hip_ctx* c, int* mode512)
-{
-	if (mode512) *mode512 = c->mode512;
-	return c->have_palette ? c->d_pal : nullptr;
-}
-int agmv_hip_internal_n_cu(agmv_hip_ctx* c) { return c->n_cu; }
 
 extern "C" size_t agmv_hip_max_usize(uint32_t w, uint32_t h, int mode512)
 {
@@ -300,37 +248,6 @@ struct EncArgs {
 	unsigned long long out_stride;
 	uint32_t n_frames, w, h, bw, nblk, tpf, first_fc, phase, n_groups, last_iframe, total_tiles;
 };
-
-// Workgroup barrier that orders LDS only.  __syncthreads() also carries a global-memory fence, i.e. an
-// s_waitcnt vmcnt(0): every prefetch and every output store in flight would have to land before the barrier.
-__device__ __forceinline__ void lds_barrier()
-{
-	asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// Wave-wide scans on the VALU's DPP lanes (row shifts inside the 16-lane rows, then the two row broadcasts gfx9 has
-// for exactly this) -- six dependent adds, no LDS round trips (__shfl_up compiles to ds_bpermute + a wait per step).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_or0(uint32_t x)       // lanes without a source (or masked off) read 0
-{
-	return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROW_MASK, 0xF, false);
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, int)
-{
-	x += dpp_or0<0x111, 0xF>(x);                               // row_shr:1
-	x += dpp_or0<0x112, 0xF>(x);                               // row_shr:2
-	x += dpp_or0<0x114, 0xF>(x);                               // row_shr:4
-	x += dpp_or0<0x118, 0xF>(x);                               // row_shr:8
-	x += dpp_or0<0x142, 0xA>(x);                               // row_bcast:15 -> rows 1 and 3
-	x += dpp_or0<0x143, 0xC>(x);                               // row_bcast:31 -> rows 2 and 3
-	return x;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x)      // the same value in every lane
-{
-	return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(x, 0), 63);
-}
 
 // decoupled look-back over the tiles of one frame (run by ONE wave; returns the exclusive
 // prefix of `tile`).  Status words are single 8-byte {tag,value} granules read/written with
@@ -980,17 +897,17 @@ extern "C" agmv_hip_ctx* agmv_hip_create(int device)
 	int n = 0;
 	hipError_t e = hipGetDeviceCount(&n);
 	if (e != hipSuccess || n <= 0) {
-		snprintf(g_err, sizeof(g_err), "agmv_hip: no HIP device available (%s); the AGMV hot path has no CPU fallback",
-		         e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+		agmv_hip_err("agmv_hip: no HIP device available (%s); the AGMV hot path has no CPU fallback",
+		             e == hipSuccess ? "device count 0" : hipGetErrorString(e));
 		return nullptr;
 	}
 	if (device < 0 || device >= n) {
-		snprintf(g_err, sizeof(g_err), "agmv_hip: device %d out of range (0..%d)", device, n - 1);
+		agmv_hip_err("agmv_hip: device %d out of range (0..%d)", device, n - 1);
 		return nullptr;
 	}
 	CKP(hipSetDevice(device));
 	agmv_hip_ctx* c = (agmv_hip_ctx*)calloc(1, sizeof(*c));
-	if (!c) { snprintf(g_err, sizeof(g_err), "agmv_hip: out of host memory"); return nullptr; }
+	if (!c) { agmv_hip_err("agmv_hip: out of host memory"); return nullptr; }
 	c->device = device;
 	hipDeviceProp_t prop;
 	hipError_t e2 = hipMalloc(&c->d_ctrl, CTRL_BYTES);
@@ -999,7 +916,7 @@ extern "C" agmv_hip_ctx* agmv_hip_create(int device)
 	if (e2 == hipSuccess) e2 = hipStreamSynchronize(nullptr);
 	if (e2 == hipSuccess) e2 = hipGetDeviceProperties(&prop, device);
 	if (e2 != hipSuccess) {                                    // nothing half-built is left behind
-		fail("agmv_hip_create", e2, __LINE__);
+		agmv_hip_hip_failed("agmv_hip_create", e2, __FILE_NAME__, __LINE__);
 		agmv_hip_destroy(c);
 		return nullptr;
 	}
@@ -1026,15 +943,20 @@ extern "C" void agmv_hip_destroy(agmv_hip_ctx* c)
 	(void)hipFree(c->d_nn_pal); (void)hipFree(c->d_nn_pix); (void)hipFree(c->d_nn_ent);
 	if (c->ev_enc) (void)hipEventDestroy(c->ev_enc);
 	for (int i = 0; i < 8; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-	agmv_hip_internal_lz_free(c->lz_ws);
-	agmv_hip_internal_lzd_free(c->lzd_ws);
-	agmv_hip_internal_lz77_free(c->lz77_ws);
-	agmv_hip_internal_pal_free(c->pal_ws);
-	agmv_hip_internal_dec_free(c->dec_ws);
+	for (int k = 0; k < AREA_KINDS; k++) if (c->ws[k]) c->ws_free[k](c->ws[k]);
 	free(c);
 }
 
-void agmv_hip_internal_ev_mark(agmv_hip_ctx* c, int which, hipStream_t s)   // encode: 0/1, the decoder: 2..7
+void* agmv_hip_area(agmv_hip_ctx* c, agmv_hip_area_kind kind, size_t bytes, void (*destroy)(void*))
+{
+	if (!c->ws[kind]) {
+		if (!(c->ws[kind] = calloc(1, bytes))) { agmv_hip_err("agmv_hip: out of host memory"); return nullptr; }
+		c->ws_free[kind] = destroy;
+	}
+	return c->ws[kind];
+}
+
+void agmv_hip_ev_mark(agmv_hip_ctx* c, int which, hipStream_t s)
 {
 	if (c->timing) (void)hipEventRecord(c->ev[which], s);
 }
@@ -1059,17 +981,17 @@ extern "C" float agmv_hip_last_kernel_ms(agmv_hip_ctx* c, int which)
 	return ms;
 }
 
-static int need_ctx(agmv_hip_ctx* c, bool palette)
+int agmv_hip_enter(agmv_hip_ctx* c, bool palette)
 {
-	if (!c) { snprintf(g_err, sizeof(g_err), "agmv_hip: NULL context"); return -1; }
-	if (palette && !c->have_palette) { snprintf(g_err, sizeof(g_err), "agmv_hip: agmv_hip_set_palette was not called"); return -1; }
+	if (!c) return agmv_hip_err("agmv_hip: NULL context");
+	if (palette && !c->have_palette) return agmv_hip_err("agmv_hip: agmv_hip_set_palette was not called");
 	CK(hipSetDevice(c->device));
 	return 0;
 }
 
 extern "C" int agmv_hip_set_palette(agmv_hip_ctx* c, const uint32_t p0[256], const uint32_t p1[256], int mode512, void* stream)
 {
-	if (need_ctx(c, false)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	hipStream_t s = (hipStream_t)stream;
 	uint32_t pal[512];
 	memcpy(pal, p0, 1024);
@@ -1100,7 +1022,7 @@ extern "C" int agmv_hip_set_palette(agmv_hip_ctx* c, const uint32_t p0[256], con
 		}
 		if (e == hipSuccess) e = hipEventRecord(sh->built, s);
 		if (e != hipSuccess) {
-			rc = fail("agmv_hip_set_palette", e, __LINE__);
+			rc = agmv_hip_hip_failed("agmv_hip_set_palette", e, __FILE_NAME__, __LINE__);
 			if (sh) { (void)hipFree(sh->d_lut); (void)hipFree(sh->d_mtx); (void)hipFree(sh->d_pal); if (sh->built) (void)hipEventDestroy(sh->built); free(sh); }
 			sh = nullptr;
 		} else {
@@ -1111,7 +1033,7 @@ extern "C" int agmv_hip_set_palette(agmv_hip_ctx* c, const uint32_t p0[256], con
 	}
 	pthread_mutex_unlock(&g_lut_mu);
 	if (rc) return rc;
-	if (hipStreamWaitEvent(s, sh->built, 0) != hipSuccess) { lut_release(sh); return fail("hipStreamWaitEvent", hipErrorUnknown, __LINE__); }   // built on another context's stream?
+	if (hipStreamWaitEvent(s, sh->built, 0) != hipSuccess) { lut_release(sh); return agmv_hip_hip_failed("hipStreamWaitEvent", hipErrorUnknown, __FILE_NAME__, __LINE__); }   // built on another context's stream?
 	lut_share* old_sh = c->share;
 	c->share = sh; c->d_lut = sh->d_lut; c->d_mtx = sh->d_mtx; c->d_pal = sh->d_pal;
 	c->mode512 = mode512;
@@ -1125,7 +1047,7 @@ extern "C" int agmv_hip_set_palette(agmv_hip_ctx* c, const uint32_t p0[256], con
 
 extern "C" int agmv_hip_quantise_dev(agmv_hip_ctx* c, const uint32_t* d_pix, size_t n, uint16_t* d_entries, void* stream)
 {
-	if (need_ctx(c, true)) return -1;
+	if (agmv_hip_enter(c, true)) return -1;
 	if (n == 0) return 0;
 	size_t blocks = (n + 255) / 256;
 	if (blocks > 8192) blocks = 8192;
@@ -1137,12 +1059,12 @@ extern "C" int agmv_hip_quantise_dev(agmv_hip_ctx* c, const uint32_t* d_pix, siz
 extern "C" int agmv_hip_dither_frames_async(agmv_hip_ctx* c, uint32_t strength, uint32_t* d_pix, uint32_t w, uint32_t h, uint32_t n_frames,
                                             void* stream)
 {
-	if (need_ctx(c, true)) return -1;
-	if (!d_pix || ((uintptr_t)d_pix & 3u)) { snprintf(g_err, sizeof(g_err), "agmv_hip: dither: d_pix must be a 4-byte aligned device pointer"); return -1; }
-	if (strength < 1 || strength > 64) { snprintf(g_err, sizeof(g_err), "agmv_hip: dither: strength must be 1 .. 64 (got %u)", strength); return -1; }
-	if (w == 0 || h == 0) { snprintf(g_err, sizeof(g_err), "agmv_hip: dither: width/height must be non-zero (got %ux%u)", w, h); return -1; }
+	if (agmv_hip_enter(c, true)) return -1;
+	if (!d_pix || ((uintptr_t)d_pix & 3u)) return agmv_hip_err("agmv_hip: dither: d_pix must be a 4-byte aligned device pointer");
+	if (strength < 1 || strength > 64) return agmv_hip_err("agmv_hip: dither: strength must be 1 .. 64 (got %u)", strength);
+	if (w == 0 || h == 0) return agmv_hip_err("agmv_hip: dither: width/height must be non-zero (got %ux%u)", w, h);
 	// the index inside a frame is 32 bits wide and steps past the end once; the frame's base is a 64-bit offset
-	if ((uint64_t)w * h >= (1ull << 31)) { snprintf(g_err, sizeof(g_err), "agmv_hip: dither: a frame must have fewer than 2^31 pixels (got %ux%u)", w, h); return -1; }
+	if ((uint64_t)w * h >= (1ull << 31)) return agmv_hip_err("agmv_hip: dither: a frame must have fewer than 2^31 pixels (got %ux%u)", w, h);
 	if (n_frames == 0) return 0;
 	const uint32_t npx = w * h, cap = (uint32_t)(c->n_cu * DITHER_WG_PER_CU);
 	uint32_t gx = (npx + DITHER_T - 1) / DITHER_T, gy = 1;
@@ -1153,14 +1075,12 @@ extern "C" int agmv_hip_dither_frames_async(agmv_hip_ctx* c, uint32_t strength, 
 	return 0;
 }
 
-int agmv_hip_internal_check_geometry(uint32_t w, uint32_t h)
+int agmv_hip_check_geometry(uint32_t w, uint32_t h)
 {
-	if (w == 0 || h == 0 || (w & 3u) || (h & 3u)) {
-		snprintf(g_err, sizeof(g_err), "agmv_hip: width/height must be non-zero multiples of 4 (got %ux%u); "
-		         "the reference's block loops have no edge handling (src/agmv_encode.c:365-366)", w, h);
-		return -1;
-	}
-	if ((uint64_t)w * h >= (1ull << 31)) { snprintf(g_err, sizeof(g_err), "agmv_hip: frame too large"); return -1; }
+	if (w == 0 || h == 0 || (w & 3u) || (h & 3u))
+		return agmv_hip_err("agmv_hip: width/height must be non-zero multiples of 4 (got %ux%u); "
+		                    "the reference's block loops have no edge handling (src/agmv_encode.c:365-366)", w, h);
+	if ((uint64_t)w * h >= (1ull << 31)) return agmv_hip_err("agmv_hip: frame too large");
 	return 0;
 }
 
@@ -1168,14 +1088,12 @@ static int encode_dev(agmv_hip_ctx* c, const uint32_t* d_pix, uint32_t n_frames,
                       uint32_t first_fc, uint8_t* d_out, size_t out_stride, uint32_t* d_sizes,
                       uint16_t* d_ientries, void* stream, bool entries)
 {
-	if (need_ctx(c, true)) return -1;
-	if (agmv_hip_internal_check_geometry(w, h)) return -1;
+	if (agmv_hip_enter(c, true)) return -1;
+	if (agmv_hip_check_geometry(w, h)) return -1;
 	if (n_frames == 0) return 0;
-	if (out_stride < agmv_hip_max_usize(w, h, c->mode512)) {
-		snprintf(g_err, sizeof(g_err), "agmv_hip: out_stride %zu < agmv_hip_max_usize %zu", out_stride, agmv_hip_max_usize(w, h, c->mode512));
-		return -1;
-	}
-	if (((uintptr_t)d_pix & 15u) || ((uintptr_t)d_out & 3u)) { snprintf(g_err, sizeof(g_err), "agmv_hip: d_pix must be 16-byte and d_out 4-byte aligned"); return -1; }
+	if (out_stride < agmv_hip_max_usize(w, h, c->mode512))
+		return agmv_hip_err("agmv_hip: out_stride %zu < agmv_hip_max_usize %zu", out_stride, agmv_hip_max_usize(w, h, c->mode512));
+	if (((uintptr_t)d_pix & 15u) || ((uintptr_t)d_out & 3u)) return agmv_hip_err("agmv_hip: d_pix must be 16-byte and d_out 4-byte aligned");
 	hipStream_t s = (hipStream_t)stream;
 	EncArgs A;
 	memset(&A, 0, sizeof(A));
@@ -1186,20 +1104,13 @@ static int encode_dev(agmv_hip_ctx* c, const uint32_t* d_pix, uint32_t n_frames,
 	A.first_fc = first_fc; A.phase = first_fc & 3u;
 	A.n_groups = (n_frames + A.phase + 3) / 4;
 	A.total_tiles = A.n_groups * A.tpf;
-	if (A.phase != 0 && !d_ientries) {
-		snprintf(g_err, sizeof(g_err), "agmv_hip: batch starts inside a GOP (frame_count %u) but no I-frame entries were supplied", first_fc);
-		return -1;
-	}
+	if (A.phase != 0 && !d_ientries)
+		return agmv_hip_err("agmv_hip: batch starts inside a GOP (frame_count %u) but no I-frame entries were supplied", first_fc);
 	A.last_iframe = 0xffffffffu;
 	for (int64_t f = (int64_t)n_frames - 1; f >= 0; f--)
 		if (((first_fc + (uint32_t)f) & 3u) == 0) { A.last_iframe = (uint32_t)f; break; }
 	size_t need = (size_t)n_frames * A.tpf;
-	if (need > c->status_cap) {
-		if (c->d_status) CK(hipFree(c->d_status));
-		c->d_status = nullptr; c->status_cap = 0;
-		CK(hipMalloc(&c->d_status, need * sizeof(unsigned long long)));
-		c->status_cap = need;
-	}
+	CK(agmv_hip_dev_grow(&c->d_status, &c->status_cap, need));
 	A.status = c->d_status; A.ctrl = c->d_ctrl;
 	// A batch that starts inside a GOP READS the caller's entry plane (its first tiles) and, if it also holds an I-frame,
 	// WRITES the plane (other tiles of the same positions, running at the same time): the new entries go to a scratch
@@ -1207,12 +1118,7 @@ static int encode_dev(agmv_hip_ctx* c, const uint32_t* d_pix, uint32_t n_frames,
 	const bool ient_both = d_ientries && A.phase != 0 && A.last_iframe != 0xffffffffu;
 	const size_t npx_e = (size_t)w * h;
 	if (ient_both) {
-		if (npx_e > c->ient_cap) {
-			if (c->d_ient_tmp) CK(hipFree(c->d_ient_tmp));
-			c->d_ient_tmp = nullptr; c->ient_cap = 0;
-			CK(hipMalloc(&c->d_ient_tmp, npx_e * sizeof(uint16_t)));
-			c->ient_cap = npx_e;
-		}
+		CK(agmv_hip_dev_grow(&c->d_ient_tmp, &c->ient_cap, npx_e));
 		A.ientries_out = c->d_ient_tmp;
 	}
 	// the look-back status and the control words belong to the context: an encode on another stream waits for the previous one
@@ -1226,9 +1132,9 @@ static int encode_dev(agmv_hip_ctx* c, const uint32_t* d_pix, uint32_t n_frames,
 	void (*kern)(EncArgs) = c->mode512 ? (entries ? k_encode<true, true> : k_encode<true, false>)
 	                                   : (entries ? k_encode<false, true> : k_encode<false, false>);
 	CK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-	agmv_hip_internal_ev_mark(c, 0, s);
+	agmv_hip_ev_mark(c, 0, s);
 	hipLaunchKernelGGL(kern, dim3(grid), dim3(ENC_T), lds, s, A);
-	agmv_hip_internal_ev_mark(c, 1, s);
+	agmv_hip_ev_mark(c, 1, s);
 	CK(hipGetLastError());
 	hipLaunchKernelGGL(k_encode_verdict, dim3(1), dim3(64), 0, s, c->d_ctrl, d_sizes, n_frames);
 	CK(hipGetLastError());
@@ -1254,19 +1160,19 @@ extern "C" int agmv_hip_encode_entries_dev(agmv_hip_ctx* c, const uint32_t* d_en
 
 extern "C" int agmv_hip_check(agmv_hip_ctx* c, void* stream)
 {
-	if (need_ctx(c, false)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	uint32_t ctrl[4] = {0, 0, 0, 0};
 	CK(hipStreamSynchronize((hipStream_t)stream));
 	CK(hipMemcpy(ctrl, c->d_ctrl, 16, hipMemcpyDeviceToHost));
-	if (ctrl[1]) { snprintf(g_err, sizeof(g_err), "agmv_hip: look-back timed out inside k_encode (device error word %u)", ctrl[1]); return -2; }
+	if (ctrl[1]) { agmv_hip_err("agmv_hip: look-back timed out inside k_encode (device error word %u)", ctrl[1]); return -2; }
 	return 0;
 }
 
 static int encode_host(agmv_hip_ctx* c, const uint32_t* h_pix, uint32_t n_frames, uint32_t w, uint32_t h,
                        uint32_t first_fc, uint8_t* h_out, size_t out_stride, uint32_t* h_sizes, uint16_t* h_ient, bool entries)
 {
-	if (need_ctx(c, true)) return -1;
-	if (agmv_hip_internal_check_geometry(w, h)) return -1;
+	if (agmv_hip_enter(c, true)) return -1;
+	if (agmv_hip_check_geometry(w, h)) return -1;
 	if (n_frames == 0) return 0;
 	const size_t npx = (size_t)w * h;
 	uint32_t *d_pix = nullptr, *d_sizes = nullptr;
@@ -1276,18 +1182,18 @@ static int encode_host(agmv_hip_ctx* c, const uint32_t* h_pix, uint32_t n_frames
 	do {
 		if (hipMalloc(&d_pix, npx * 4 * n_frames) != hipSuccess || hipMalloc(&d_out, out_stride * n_frames) != hipSuccess ||
 		    hipMalloc(&d_sizes, 4 * (size_t)n_frames) != hipSuccess || (h_ient && hipMalloc(&d_ient, npx * 2) != hipSuccess)) {
-			snprintf(g_err, sizeof(g_err), "agmv_hip: device allocation failed"); break;
+			agmv_hip_err("agmv_hip: device allocation failed"); break;
 		}
-		if (hipMemcpy(d_pix, h_pix, npx * 4 * n_frames, hipMemcpyHostToDevice) != hipSuccess) { snprintf(g_err, sizeof(g_err), "agmv_hip: H2D failed"); break; }
-		if (h_ient && hipMemcpy(d_ient, h_ient, npx * 2, hipMemcpyHostToDevice) != hipSuccess) { snprintf(g_err, sizeof(g_err), "agmv_hip: H2D failed"); break; }
+		if (hipMemcpy(d_pix, h_pix, npx * 4 * n_frames, hipMemcpyHostToDevice) != hipSuccess) { agmv_hip_err("agmv_hip: H2D failed"); break; }
+		if (h_ient && hipMemcpy(d_ient, h_ient, npx * 2, hipMemcpyHostToDevice) != hipSuccess) { agmv_hip_err("agmv_hip: H2D failed"); break; }
 		if (encode_dev(c, d_pix, n_frames, w, h, first_fc, d_out, out_stride, d_sizes, d_ient, nullptr, entries)) break;
 		if (agmv_hip_check(c, nullptr)) break;
-		if (hipMemcpy(h_sizes, d_sizes, 4 * (size_t)n_frames, hipMemcpyDeviceToHost) != hipSuccess) { snprintf(g_err, sizeof(g_err), "agmv_hip: D2H failed"); break; }
+		if (hipMemcpy(h_sizes, d_sizes, 4 * (size_t)n_frames, hipMemcpyDeviceToHost) != hipSuccess) { agmv_hip_err("agmv_hip: D2H failed"); break; }
 		bool ok = true;
 		for (uint32_t f = 0; f < n_frames && ok; f++)
 			ok = hipMemcpy(h_out + (size_t)f * out_stride, d_out + (size_t)f * out_stride, h_sizes[f], hipMemcpyDeviceToHost) == hipSuccess;
-		if (!ok) { snprintf(g_err, sizeof(g_err), "agmv_hip: D2H failed"); break; }
-		if (h_ient && hipMemcpy(h_ient, d_ient, npx * 2, hipMemcpyDeviceToHost) != hipSuccess) { snprintf(g_err, sizeof(g_err), "agmv_hip: D2H failed"); break; }
+		if (!ok) { agmv_hip_err("agmv_hip: D2H failed"); break; }
+		if (h_ient && hipMemcpy(h_ient, d_ient, npx * 2, hipMemcpyDeviceToHost) != hipSuccess) { agmv_hip_err("agmv_hip: D2H failed"); break; }
 		rc = 0;
 	} while (0);
 	(void)hipFree(d_pix); (void)hipFree(d_out); (void)hipFree(d_sizes); (void)hipFree(d_ient);
@@ -1308,7 +1214,7 @@ extern "C" int agmv_hip_encode_entries(agmv_hip_ctx* c, const uint32_t* h_entrie
 
 extern "C" int agmv_hip_within2_count(agmv_hip_ctx* c, const uint32_t a[16], const uint32_t b[16])
 {
-	if (need_ctx(c, false)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	if (!c->d_nn_pal) CK(hipMalloc(&c->d_nn_pal, 512 * sizeof(uint32_t)));
 	uint32_t ab[32], n = 0;
 	memcpy(ab, a, 64); memcpy(ab + 16, b, 64);
@@ -1322,15 +1228,14 @@ extern "C" int agmv_hip_within2_count(agmv_hip_ctx* c, const uint32_t a[16], con
 extern "C" int agmv_hip_nearest(agmv_hip_ctx* c, const uint32_t p0[256], const uint32_t p1[256], int mode512,
                                 const uint32_t* h_pix, size_t n, uint16_t* h_entries)
 {
-	if (need_ctx(c, false)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	if (n == 0) return 0;
 	if (!c->d_nn_pal) CK(hipMalloc(&c->d_nn_pal, 512 * sizeof(uint32_t)));
-	if (n > c->nn_cap) {
-		(void)hipFree(c->d_nn_pix); (void)hipFree(c->d_nn_ent);
-		c->d_nn_pix = nullptr; c->d_nn_ent = nullptr; c->nn_cap = 0;
+	if (n > c->nn_cap) {                                       // pixels and entries share the capacity
 		const size_t cap = n < 256 ? 256 : n;
-		CK(hipMalloc(&c->d_nn_pix, cap * sizeof(uint32_t)));
-		CK(hipMalloc(&c->d_nn_ent, cap * sizeof(uint16_t)));
+		c->nn_cap = 0;
+		CK(agmv_hip_dev_grow(&c->d_nn_pix, nullptr, cap));
+		CK(agmv_hip_dev_grow(&c->d_nn_ent, nullptr, cap));
 		c->nn_cap = cap;
 	}
 	uint32_t pal[512];
@@ -1397,8 +1302,8 @@ __global__ __launch_bounds__(256) void k_pack_copy(uint8_t* __restrict__ slab, u
 static int pack_launch(agmv_hip_ctx* c, bool unpack, uint8_t* d_slab, size_t stride, const uint32_t* d_sizes, uint32_t n_frames,
                        uint8_t* d_msg, unsigned long long* d_offsets, hipStream_t s)
 {
-	if (!d_slab || !d_sizes || !d_msg || !d_offsets) { snprintf(g_err, sizeof(g_err), "agmv_hip: pack/unpack: NULL argument"); return -1; }
-	if (stride & 3u) { snprintf(g_err, sizeof(g_err), "agmv_hip: pack/unpack: the slab stride must be a multiple of 4 (agmv_hip_max_usize is)"); return -1; }
+	if (!d_slab || !d_sizes || !d_msg || !d_offsets) return agmv_hip_err("agmv_hip: pack/unpack: NULL argument");
+	if (stride & 3u) return agmv_hip_err("agmv_hip: pack/unpack: the slab stride must be a multiple of 4 (agmv_hip_max_usize is)");
 	hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(256), 0, s, d_sizes, n_frames, d_offsets);
 	CK(hipGetLastError());
 	uint32_t gx = (uint32_t)((stride / 8 + PACK_CHUNK - 1) / PACK_CHUNK);   // chunks of a frame whose stream is an eighth of the worst case
@@ -1415,7 +1320,7 @@ static int pack_launch(agmv_hip_ctx* c, bool unpack, uint8_t* d_slab, size_t str
 extern "C" int agmv_hip_pack_frames_dev(agmv_hip_ctx* c, const uint8_t* d_slab, size_t stride, const uint32_t* d_sizes, uint32_t n_frames,
                                         uint8_t* d_msg, unsigned long long* d_offsets, void* stream)
 {
-	if (need_ctx(c, false)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	if (n_frames == 0) return 0;
 	return pack_launch(c, false, (uint8_t*)d_slab, stride, d_sizes, n_frames, d_msg, d_offsets, (hipStream_t)stream);
 }
@@ -1423,7 +1328,7 @@ extern "C" int agmv_hip_pack_frames_dev(agmv_hip_ctx* c, const uint8_t* d_slab, 
 extern "C" int agmv_hip_unpack_frames_dev(agmv_hip_ctx* c, const uint8_t* d_msg, const uint32_t* d_sizes, uint32_t n_frames,
                                           uint8_t* d_slab, size_t stride, unsigned long long* d_offsets, void* stream)
 {
-	if (need_ctx(c, false)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	if (n_frames == 0) return 0;
 	return pack_launch(c, true, d_slab, stride, d_sizes, n_frames, (uint8_t*)d_msg, d_offsets, (hipStream_t)stream);
 }
@@ -1431,7 +1336,7 @@ extern "C" int agmv_hip_unpack_frames_dev(agmv_hip_ctx* c, const uint8_t* d_msg,
 // ---- streams, pinned staging and asynchronous copies for C hosts (the pipelined drivers of agmv_pipeline.c) ----
 extern "C" void* agmv_hip_stream_create(agmv_hip_ctx* c)
 {
-	if (need_ctx(c, false)) return nullptr;
+	if (agmv_hip_enter(c)) return nullptr;
 	hipStream_t s = nullptr;
 	CKP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
 	return (void*)s;
@@ -1444,15 +1349,15 @@ extern "C" void agmv_hip_stream_destroy(agmv_hip_ctx* c, void* stream)
 }
 extern "C" int agmv_hip_stream_sync(agmv_hip_ctx* c, void* stream)
 {
-	if (need_ctx(c, false)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	CK(hipStreamSynchronize((hipStream_t)stream));
 	return 0;
 }
 extern "C" void* agmv_hip_event_create(agmv_hip_ctx* c)
 {
-	if (need_ctx(c, false)) return nullptr;
+	if (agmv_hip_enter(c)) return nullptr;
 	hipEvent_t e = nullptr;
-	if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { snprintf(g_err, sizeof(g_err), "agmv_hip: hipEventCreate failed"); return nullptr; }
+	if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { agmv_hip_err("agmv_hip: hipEventCreate failed"); return nullptr; }
 	return (void*)e;
 }
 extern "C" void agmv_hip_event_destroy(agmv_hip_ctx* c, void* ev)
@@ -1463,41 +1368,41 @@ extern "C" void agmv_hip_event_destroy(agmv_hip_ctx* c, void* ev)
 }
 extern "C" int agmv_hip_event_record(agmv_hip_ctx* c, void* ev, void* stream)
 {
-	if (need_ctx(c, false)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	CK(hipEventRecord((hipEvent_t)ev, (hipStream_t)stream));
 	return 0;
 }
 extern "C" int agmv_hip_stream_wait_event(agmv_hip_ctx* c, void* stream, void* ev)
 {
-	if (need_ctx(c, false)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	CK(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)ev, 0));
 	return 0;
 }
 extern "C" void* agmv_hip_host_alloc(size_t bytes)
 {
 	void* p = nullptr;
-	if (hipHostMalloc(&p, bytes, hipHostMallocPortable) != hipSuccess) { snprintf(g_err, sizeof(g_err), "agmv_hip: hipHostMalloc(%zu) failed", bytes); return nullptr; }
+	if (hipHostMalloc(&p, bytes, hipHostMallocPortable) != hipSuccess) { agmv_hip_err("agmv_hip: hipHostMalloc(%zu) failed", bytes); return nullptr; }
 	return p;
 }
 extern "C" void agmv_hip_host_free(void* h) { if (h) (void)hipHostFree(h); }
 extern "C" void* agmv_hip_malloc_on(agmv_hip_ctx* c, size_t bytes)
 {
-	if (need_ctx(c, false)) return nullptr;
+	if (agmv_hip_enter(c)) return nullptr;
 	void* p = nullptr;
-	if (hipMalloc(&p, bytes) != hipSuccess) { snprintf(g_err, sizeof(g_err), "agmv_hip: hipMalloc(%zu) failed on device %d", bytes, c->device); return nullptr; }
+	if (hipMalloc(&p, bytes) != hipSuccess) { agmv_hip_err("agmv_hip: hipMalloc(%zu) failed on device %d", bytes, c->device); return nullptr; }
 	return p;
 }
 extern "C" void agmv_hip_free_on(agmv_hip_ctx* c, void* d) { if (c && d) { (void)hipSetDevice(c->device); (void)hipFree(d); } }
 extern "C" int agmv_hip_memcpy_async(agmv_hip_ctx* c, void* dst, const void* src, size_t n, int kind, void* stream)
 {
-	if (need_ctx(c, false)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	const hipMemcpyKind k = kind == 0 ? hipMemcpyHostToDevice : (kind == 1 ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
 	CK(hipMemcpyAsync(dst, src, n, k, (hipStream_t)stream));
 	return 0;
 }
 extern "C" int agmv_hip_memset_async(agmv_hip_ctx* c, void* d, int v, size_t n, void* stream)
 {
-	if (need_ctx(c, false)) return -1;
+	if (agmv_hip_enter(c)) return -1;
 	CK(hipMemsetAsync(d, v, n, (hipStream_t)stream));
 	return 0;
 }
@@ -1506,7 +1411,7 @@ extern "C" int agmv_hip_ctx_device(agmv_hip_ctx* c) { return c ? c->device : -1;
 extern "C" void* agmv_hip_malloc(size_t bytes)
 {
 	void* p = nullptr;
-	if (hipMalloc(&p, bytes) != hipSuccess) { snprintf(g_err, sizeof(g_err), "agmv_hip: hipMalloc(%zu) failed", bytes); return nullptr; }
+	if (hipMalloc(&p, bytes) != hipSuccess) { agmv_hip_err("agmv_hip: hipMalloc(%zu) failed", bytes); return nullptr; }
 	return p;
 }
 extern "C" void agmv_hip_free(void* d) { if (d) (void)hipFree(d); }

@@ -24,26 +24,11 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include <vector>
 
-#include "../../include/agmv_hip.h"
-
-// defined in agmv_hip.hip: the library's error text, and the context's slot for this stage's work areas
-int agmv_hip_internal_error(const char* msg);
-void** agmv_hip_internal_lz77_slot(agmv_hip_ctx* c);
-int agmv_hip_internal_device(agmv_hip_ctx* c);
-
-static int lz77_fail(const char* what, hipError_t e, int line)
-{
-	char m[512];
-	snprintf(m, sizeof(m), "agmv_hip: %s failed: %s (agmv_lz77_hip.hip:%d)", what, hipGetErrorString(e), line);
-	return agmv_hip_internal_error(m);
-}
-#define LCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return lz77_fail(#x, e_, __LINE__); } while (0)
+#include "agmv_hip_impl.h"
 
 constexpr uint32_t LZ77_WIN = 65535;             // matches start in [i - 65535, i)
 constexpr uint32_t LZ77_MAXLEN = 255;
@@ -419,10 +404,9 @@ struct lz77_ws {
 	uint32_t* reparsed;
 };
 
-extern "C++" void agmv_hip_internal_lz77_free(void* p)
+static void lz77_free(void* p)
 {
 	lz77_ws* w = (lz77_ws*)p;
-	if (!w) return;
 	void* all[] = {w->tokv, w->flag, w->sexit, w->smerge, w->scnt, w->tab, w->sm, w->reparsed};
 	for (void* a : all) if (a) (void)hipFree(a);
 	free(w);
@@ -430,15 +414,11 @@ extern "C++" void agmv_hip_internal_lz77_free(void* p)
 
 static int lz77_get_ws(agmv_hip_ctx* c, lz77_ws** out)
 {
-	void** slot = agmv_hip_internal_lz77_slot(c);
-	if (!*slot) {
-		*slot = calloc(1, sizeof(lz77_ws));
-		if (!*slot) return agmv_hip_internal_error("agmv_hip: out of host memory");
-	}
-	lz77_ws* w = (lz77_ws*)*slot;
+	lz77_ws* w = (lz77_ws*)agmv_hip_area(c, AREA_LZ77, sizeof(lz77_ws), lz77_free);
+	if (!w) return -1;
 	if (!w->reparsed) {
-		LCK(hipMalloc((void**)&w->reparsed, 4));
-		LCK(hipMemset(w->reparsed, 0, 4));
+		CK(hipMalloc((void**)&w->reparsed, 4));
+		CK(hipMemset(w->reparsed, 0, 4));
 	}
 	*out = w;
 	return 0;
@@ -446,27 +426,18 @@ static int lz77_get_ws(agmv_hip_ctx* c, lz77_ws** out)
 
 static int lz77_grow(lz77_ws* w, size_t n, size_t nseg, size_t ntab)
 {
-	if (n > w->cap_n) {
-		if (w->tokv) LCK(hipFree(w->tokv));
-		if (w->flag) LCK(hipFree(w->flag));
-		w->tokv = nullptr; w->flag = nullptr; w->cap_n = 0;
-		LCK(hipMalloc((void**)&w->tokv, n * 4));
-		LCK(hipMalloc((void**)&w->flag, n));
+	if (n > w->cap_n) {                                            // a shared capacity is committed when all its buffers exist
+		w->cap_n = 0;
+		CK(agmv_hip_dev_grow(&w->tokv, nullptr, n));
+		CK(agmv_hip_dev_grow(&w->flag, nullptr, n));
 		w->cap_n = n;
 	}
 	if (nseg > w->cap_seg) {
-		void** bufs[] = {(void**)&w->sexit, (void**)&w->smerge, (void**)&w->scnt};
-		for (void** b : bufs) { if (*b) LCK(hipFree(*b)); *b = nullptr; }
 		w->cap_seg = 0;
-		for (void** b : bufs) LCK(hipMalloc(b, nseg * 4));
+		for (uint32_t** b : {&w->sexit, &w->smerge, &w->scnt}) CK(agmv_hip_dev_grow(b, nullptr, nseg));
 		w->cap_seg = nseg;
 	}
-	if (ntab > w->cap_tab) {
-		if (w->tab) LCK(hipFree(w->tab));
-		w->tab = nullptr; w->cap_tab = 0;
-		LCK(hipMalloc((void**)&w->tab, ntab * 4));
-		w->cap_tab = ntab;
-	}
+	CK(agmv_hip_dev_grow(&w->tab, &w->cap_tab, ntab));
 	return 0;
 }
 
@@ -478,28 +449,22 @@ extern "C" size_t agmv_hip_lz77_max_csize(size_t n)
 extern "C" int agmv_hip_lz77_peek_dev(agmv_hip_ctx* c, const uint8_t* d_bits, size_t bits_stride, const uint32_t* d_sizes,
                                       uint32_t n_frames, uint8_t* d_persist, size_t persist_len, uint8_t* d_peek, void* stream)
 {
-	if (!c) return agmv_hip_internal_error("agmv_hip: NULL context");
-	LCK(hipSetDevice(agmv_hip_internal_device(c)));
+	if (agmv_hip_enter(c)) return -1;
 	if (n_frames == 0) return 0;
 	hipStream_t s = (hipStream_t)stream;
 	lz77_ws* w;
 	if (lz77_get_ws(c, &w)) return -1;
-	if (n_frames > w->cap_sm) {
-		if (w->sm) LCK(hipFree(w->sm));
-		w->sm = nullptr; w->cap_sm = 0;
-		LCK(hipMalloc((void**)&w->sm, (size_t)n_frames * 4));
-		w->cap_sm = n_frames;
-	}
+	CK(agmv_hip_dev_grow(&w->sm, &w->cap_sm, n_frames));
 	hipLaunchKernelGGL(k_lz77_peek, dim3((n_frames + 255) / 256), dim3(256), 0, s, d_bits, (unsigned long long)bits_stride, d_sizes,
 	                   n_frames, d_persist, (unsigned long long)persist_len, d_peek);
-	LCK(hipGetLastError());
+	CK(hipGetLastError());
 	if (persist_len) {
 		const size_t top = persist_len < bits_stride ? persist_len : bits_stride;
 		const uint32_t gx = (uint32_t)((top + 255) / 256 < 4096 ? (top + 255) / 256 : 4096);
 		hipLaunchKernelGGL(k_lz77_sufmax, dim3(1), dim3(1024), 0, s, d_sizes, n_frames, w->sm);
 		hipLaunchKernelGGL(k_lz77_persist, dim3(gx < 1 ? 1 : gx), dim3(256), 0, s, d_bits, (unsigned long long)bits_stride, n_frames,
 		                   w->sm, d_persist, (unsigned long long)persist_len);
-		LCK(hipGetLastError());
+		CK(hipGetLastError());
 	}
 	return 0;
 }
@@ -508,8 +473,7 @@ extern "C" int agmv_hip_lz77_frames_dev(agmv_hip_ctx* c, const uint8_t* d_bits, 
                                         uint32_t n_frames, const uint8_t* d_peek, uint8_t* d_out, size_t out_stride,
                                         uint32_t* d_csize, void* stream)
 {
-	if (!c) return agmv_hip_internal_error("agmv_hip: NULL context");
-	LCK(hipSetDevice(agmv_hip_internal_device(c)));
+	if (agmv_hip_enter(c)) return -1;
 	if (n_frames == 0) return 0;
 	hipStream_t s = (hipStream_t)stream;
 	lz77_ws* w;
@@ -517,15 +481,12 @@ extern "C" int agmv_hip_lz77_frames_dev(agmv_hip_ctx* c, const uint8_t* d_bits, 
 
 	// the sizes decide the chunks: read them once
 	std::vector<uint32_t> sz(n_frames);
-	LCK(hipMemcpyAsync(sz.data(), d_sizes, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s));
-	LCK(hipStreamSynchronize(s));
+	CK(hipMemcpyAsync(sz.data(), d_sizes, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s));
+	CK(hipStreamSynchronize(s));
 	for (uint32_t f = 0; f < n_frames; f++) {
-		char m[256];
-		if (sz[f] > bits_stride || sz[f] >= LZ77_MAXN || agmv_hip_lz77_max_csize(sz[f]) > out_stride) {
-			snprintf(m, sizeof(m), "agmv_hip_lz77_frames_dev: frame %u: %u bytes (bits_stride %zu, out_stride %zu, at most %u bytes per frame)",
-			         f, sz[f], bits_stride, out_stride, LZ77_MAXN - 1);
-			return agmv_hip_internal_error(m);
-		}
+		if (sz[f] > bits_stride || sz[f] >= LZ77_MAXN || agmv_hip_lz77_max_csize(sz[f]) > out_stride)
+			return agmv_hip_err("agmv_hip_lz77_frames_dev: frame %u: %u bytes (bits_stride %zu, out_stride %zu, at most %u bytes per frame)",
+			                    f, sz[f], bits_stride, out_stride, LZ77_MAXN - 1);
 	}
 	// chunks: [f0, f0 + nf) with <= LZ77_CHUNK positions; per chunk the tables fstart[nf + 1] (positions), sb[nf + 1] (first segment)
 	struct chunk { uint32_t f0, nf, n, nseg; size_t tab; };
@@ -550,9 +511,9 @@ extern "C" int agmv_hip_lz77_frames_dev(agmv_hip_ctx* c, const uint8_t* d_bits, 
 		ch.push_back(k);
 	}
 	if (lz77_grow(w, maxn, maxs, tab.size())) return -1;
-	LCK(hipMemcpyAsync(w->tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
-	LCK(hipMemsetAsync(w->reparsed, 0, 4, s));
-	LCK(hipStreamSynchronize(s));                                   // (tab is host memory of this call)
+	CK(hipMemcpyAsync(w->tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+	CK(hipMemsetAsync(w->reparsed, 0, 4, s));
+	CK(hipStreamSynchronize(s));                                   // (tab is host memory of this call)
 
 	for (const chunk& k : ch) {
 		const uint32_t* fs = w->tab + k.tab;
@@ -563,26 +524,25 @@ extern "C" int agmv_hip_lz77_frames_dev(agmv_hip_ctx* c, const uint8_t* d_bits, 
 			hipLaunchKernelGGL(k_lz77_stitch, dim3(k.nf), dim3(LZ77_T), 0, s, d_bits, (unsigned long long)bits_stride, fs, sb, k.f0,
 			                   w->tokv, w->flag, w->sexit, w->smerge, w->reparsed);
 			hipLaunchKernelGGL(k_lz77_count, dim3(k.nseg), dim3(256), 0, s, fs, sb, k.nf, w->flag, w->smerge, w->scnt);
-			LCK(hipGetLastError());
+			CK(hipGetLastError());
 		}
 		hipLaunchKernelGGL(k_lz77_scan, dim3(k.nf), dim3(256), 0, s, sb, k.f0, w->scnt, d_csize);
 		if (k.nseg)
 			hipLaunchKernelGGL(k_lz77_emit, dim3(k.nseg), dim3(256), 0, s, fs, sb, k.f0, k.nf, w->tokv, w->flag, w->smerge, w->scnt,
 			                   d_peek, d_out, (unsigned long long)out_stride);
-		LCK(hipGetLastError());
+		CK(hipGetLastError());
 	}
 	return 0;
 }
 
 extern "C" int agmv_hip_lz77_reparsed_segments(agmv_hip_ctx* c, void* stream)
 {
-	if (!c) return agmv_hip_internal_error("agmv_hip: NULL context");
-	LCK(hipSetDevice(agmv_hip_internal_device(c)));
-	void** slot = agmv_hip_internal_lz77_slot(c);
-	if (!*slot || !((lz77_ws*)*slot)->reparsed) return 0;
+	if (agmv_hip_enter(c)) return -1;
+	const lz77_ws* w = (const lz77_ws*)c->ws[AREA_LZ77];
+	if (!w || !w->reparsed) return 0;
 	uint32_t v = 0;
-	LCK(hipStreamSynchronize((hipStream_t)stream));
-	LCK(hipMemcpy(&v, ((lz77_ws*)*slot)->reparsed, 4, hipMemcpyDeviceToHost));
+	CK(hipStreamSynchronize((hipStream_t)stream));
+	CK(hipMemcpy(&v, w->reparsed, 4, hipMemcpyDeviceToHost));
 	return (int)v;
 }
 
@@ -590,8 +550,7 @@ extern "C" int agmv_hip_lz77_frames(agmv_hip_ctx* c, const uint8_t* h_bits, size
                                     uint32_t n_frames, uint8_t* h_persist, size_t persist_len, uint8_t* h_out, size_t out_stride,
                                     uint32_t* h_csize)
 {
-	if (!c) return agmv_hip_internal_error("agmv_hip: NULL context");
-	LCK(hipSetDevice(agmv_hip_internal_device(c)));
+	if (agmv_hip_enter(c)) return -1;
 	if (n_frames == 0) return 0;
 	uint8_t *db = nullptr, *dout = nullptr, *dp = nullptr, *dpeek = nullptr;
 	uint32_t *ds = nullptr, *dc = nullptr;
@@ -606,7 +565,7 @@ extern "C" int agmv_hip_lz77_frames(agmv_hip_ctx* c, const uint8_t* h_bits, size
 	    (e = hipMemcpy(db, h_bits, (size_t)n_frames * bits_stride, hipMemcpyHostToDevice)) != hipSuccess ||
 	    (e = hipMemcpy(ds, h_sizes, (size_t)n_frames * 4, hipMemcpyHostToDevice)) != hipSuccess ||
 	    (e = h_persist ? hipMemcpy(dp, h_persist, persist_len, hipMemcpyHostToDevice) : hipMemset(dp, 0, persist_len + 1)) != hipSuccess) {
-		lz77_fail("agmv_hip_lz77_frames", e, __LINE__);
+		agmv_hip_hip_failed("agmv_hip_lz77_frames", e, __FILE_NAME__, __LINE__);
 		goto done;
 	}
 	if (agmv_hip_lz77_peek_dev(c, db, bits_stride, ds, n_frames, dp, persist_len, dpeek, nullptr)) goto done;
@@ -614,12 +573,12 @@ extern "C" int agmv_hip_lz77_frames(agmv_hip_ctx* c, const uint8_t* h_bits, size
 	if ((e = hipDeviceSynchronize()) != hipSuccess ||
 	    (e = hipMemcpy(h_csize, dc, (size_t)n_frames * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
 	    (e = h_persist && persist_len ? hipMemcpy(h_persist, dp, persist_len, hipMemcpyDeviceToHost) : hipSuccess) != hipSuccess) {
-		lz77_fail("agmv_hip_lz77_frames", e, __LINE__);
+		agmv_hip_hip_failed("agmv_hip_lz77_frames", e, __FILE_NAME__, __LINE__);
 		goto done;
 	}
 	for (uint32_t f = 0; f < n_frames; f++)                        // rows: only the payload bytes are defined
 		if (h_csize[f] && (e = hipMemcpy(h_out + (size_t)f * out_stride, dout + (size_t)f * out_stride, h_csize[f], hipMemcpyDeviceToHost)) != hipSuccess) {
-			lz77_fail("agmv_hip_lz77_frames", e, __LINE__);
+			agmv_hip_hip_failed("agmv_hip_lz77_frames", e, __FILE_NAME__, __LINE__);
 			goto done;
 		}
 	rc = 0;

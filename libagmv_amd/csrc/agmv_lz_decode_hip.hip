@@ -36,26 +36,12 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <vector>
 
-#include "../../include/agmv_hip.h"
-
-// defined in agmv_hip.hip: the library's error text, the context's slot for this stage's work areas, the device
-int agmv_hip_internal_error(const char* msg);
-void** agmv_hip_internal_lzd_slot(agmv_hip_ctx* c);
-int agmv_hip_internal_device(agmv_hip_ctx* c);
-
-static int lzd_fail(const char* what, hipError_t e, int line)
-{
-	char m[512];
-	snprintf(m, sizeof(m), "agmv_hip: %s failed: %s (agmv_lz_decode_hip.hip:%d)", what, hipGetErrorString(e), line);
-	return agmv_hip_internal_error(m);
-}
-#define DCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return lzd_fail(#x, e_, __LINE__); } while (0)
+#include "agmv_hip_impl.h"
 
 constexpr uint32_t LZD_PB = 2048;              // LZSS: bits per piece
 constexpr uint32_t LZD_PW = LZD_PB / 32 + 2;   // LDS words of a piece: its bits and the <= 20 a token may run past it
@@ -461,10 +447,9 @@ struct lzd_ws {
 	uint32_t* ctl;                                  // [0] fallback frames of the last call, [1 ..] round flags
 };
 
-extern "C++" void agmv_hip_internal_lzd_free(void* p)
+static void lzd_free(void* p)
 {
 	lzd_ws* w = (lzd_ws*)p;
-	if (!w) return;
 	void* all[] = {w->words, w->pexit, w->psum, w->pentry, w->ppos, w->fd, w->fs, w->pbase, w->tab, w->ctl};
 	for (void* a : all) if (a) (void)hipFree(a);
 	if (w->ev_done) { (void)hipEventSynchronize(w->ev_done); (void)hipEventDestroy(w->ev_done); }
@@ -473,37 +458,22 @@ extern "C++" void agmv_hip_internal_lzd_free(void* p)
 	free(w);
 }
 
-template <class T>
-static int grow(T** p, size_t* cap, size_t n)
-{
-	if (n <= *cap) return 0;
-	if (*p) DCK(hipFree(*p));
-	*p = nullptr; *cap = 0;
-	DCK(hipMalloc((void**)p, n * sizeof(T)));
-	*cap = n;
-	return 0;
-}
-
 static lzd_ws* lzd_get(agmv_hip_ctx* c)
 {
-	void** slot = agmv_hip_internal_lzd_slot(c);
-	if (!*slot) {
-		lzd_ws* w = (lzd_ws*)calloc(1, sizeof(lzd_ws));
-		if (!w) { agmv_hip_internal_error("agmv_hip: out of host memory"); return nullptr; }
-		if (hipMalloc((void**)&w->ctl, (1 + LZD_ROUNDS) * 4) != hipSuccess || hipMemset(w->ctl, 0, (1 + LZD_ROUNDS) * 4) != hipSuccess) {
-			free(w);
-			agmv_hip_internal_error("agmv_hip: LZ decode work area: hipMalloc failed");
-			return nullptr;
-		}
-		*slot = w;
+	lzd_ws* w = (lzd_ws*)agmv_hip_area(c, AREA_LZ_DECODE, sizeof(lzd_ws), lzd_free);
+	if (w && !w->ctl && (hipMalloc((void**)&w->ctl, (1 + LZD_ROUNDS) * 4) != hipSuccess || hipMemset(w->ctl, 0, (1 + LZD_ROUNDS) * 4) != hipSuccess)) {
+		(void)hipFree(w->ctl);
+		w->ctl = nullptr;
+		agmv_hip_err("agmv_hip: LZ decode work area: hipMalloc failed");
+		return nullptr;
 	}
-	return (lzd_ws*)*slot;
+	return w;
 }
 
 static int lzd_mark_done(lzd_ws* w, hipStream_t s)
 {
-	if (!w->ev_done) DCK(hipEventCreateWithFlags(&w->ev_done, hipEventDisableTiming));
-	DCK(hipEventRecord(w->ev_done, s));
+	if (!w->ev_done) CK(hipEventCreateWithFlags(&w->ev_done, hipEventDisableTiming));
+	CK(hipEventRecord(w->ev_done, s));
 	return 0;
 }
 
@@ -517,7 +487,7 @@ static int lzd_frames(agmv_hip_ctx* c, int version, const uint8_t* d_src, const 
 	if (!w) return -1;
 	const bool lzss = version == 1 || version == 2;
 	const unsigned long long lim = cap > 16 ? cap - 16 : 0;
-	DCK(hipMemsetAsync(w->ctl, 0, 4, s));
+	CK(hipMemsetAsync(w->ctl, 0, 4, s));
 	// per frame: readable bytes, the walk's extent, word positions; chunks of frames
 	struct chunk { uint32_t f0, nf, npieces, nwords, maxw; };
 	std::vector<lzd_fd> fd(n_frames);
@@ -552,11 +522,8 @@ static int lzd_frames(agmv_hip_ctx* c, int version, const uint8_t* d_src, const 
 			if (W > lim) W = lim;
 			d.W = (uint32_t)W;
 			if (k.nf && ((unsigned long long)k.nwords + W > LZD_WORDS || (unsigned long long)k.npieces + np > LZD_PIECES)) break;
-			if ((unsigned long long)k.nwords + W >= (1ull << 31) || (unsigned long long)k.npieces + np >= (1ull << 31)) {
-				char m[256];
-				snprintf(m, sizeof(m), "agmv_hip_lz_decode_frames_dev: frame %u is too large (%llu output words, %llu pieces)", f, W, np);
-				return agmv_hip_internal_error(m);
-			}
+			if ((unsigned long long)k.nwords + W >= (1ull << 31) || (unsigned long long)k.npieces + np >= (1ull << 31))
+				return agmv_hip_err("agmv_hip_lz_decode_frames_dev: frame %u is too large (%llu output words, %llu pieces)", f, W, np);
 			d.wbase = k.nwords;
 			pb.push_back(k.npieces);
 			k.nwords += (uint32_t)W;
@@ -573,43 +540,39 @@ static int lzd_frames(agmv_hip_ctx* c, int version, const uint8_t* d_src, const 
 	}
 	const size_t nfd = n_frames, npb = pb.size();     // fd and fs: one entry per frame of the call; pbase: per frame and chunk
 	if ((maxwords > w->cap_words || maxp > w->cap_pieces || nfd > w->cap_fd || npb > w->cap_pb) && w->ev_done)
-		DCK(hipEventSynchronize(w->ev_done));           // the areas about to be replaced may still be in use by the last call
-	if (grow(&w->words, &w->cap_words, maxwords)) return -1;
-	if (maxp > w->cap_pieces) {
-		void* old[] = {w->pexit, w->psum, w->pentry, w->ppos};
-		for (void* a : old) if (a) DCK(hipFree(a));
-		w->pexit = nullptr; w->psum = nullptr; w->pentry = nullptr; w->ppos = nullptr; w->cap_pieces = 0;
-		DCK(hipMalloc((void**)&w->pexit, maxp * LZD_NE * 2));
-		DCK(hipMalloc((void**)&w->psum, maxp * LZD_NE * 4));
-		DCK(hipMalloc((void**)&w->pentry, maxp));
-		DCK(hipMalloc((void**)&w->ppos, maxp * 8));
+		CK(hipEventSynchronize(w->ev_done));           // the areas about to be replaced may still be in use by the last call
+	CK(agmv_hip_dev_grow(&w->words, &w->cap_words, maxwords));
+	if (maxp > w->cap_pieces) {                                    // a shared capacity is committed when all its buffers exist
+		w->cap_pieces = 0;
+		CK(agmv_hip_dev_grow(&w->pexit, nullptr, maxp * LZD_NE));
+		CK(agmv_hip_dev_grow(&w->psum, nullptr, maxp * LZD_NE));
+		CK(agmv_hip_dev_grow(&w->pentry, nullptr, maxp));
+		CK(agmv_hip_dev_grow(&w->ppos, nullptr, maxp));
 		w->cap_pieces = maxp;
 	}
 	if (nfd > w->cap_fd) {
-		if (w->fd) DCK(hipFree(w->fd));
-		if (w->fs) DCK(hipFree(w->fs));
-		w->fd = nullptr; w->fs = nullptr; w->cap_fd = 0;
-		DCK(hipMalloc((void**)&w->fd, nfd * sizeof(lzd_fd)));
-		DCK(hipMalloc((void**)&w->fs, nfd * sizeof(lzd_fs)));
+		w->cap_fd = 0;
+		CK(agmv_hip_dev_grow(&w->fd, nullptr, nfd));
+		CK(agmv_hip_dev_grow(&w->fs, nullptr, nfd));
 		w->cap_fd = nfd;
 	}
-	if (grow(&w->pbase, &w->cap_pb, npb)) return -1;
+	CK(agmv_hip_dev_grow(&w->pbase, &w->cap_pb, npb));
 	// the tables go up from pinned staging, without a stream synchronisation: the staging is rewritten only once the
 	// upload of the previous call has ended
 	const size_t fdb = nfd * sizeof(lzd_fd), stage = fdb + npb * 4;
-	if (!w->ev_up) DCK(hipEventCreateWithFlags(&w->ev_up, hipEventDisableTiming));
-	else DCK(hipEventSynchronize(w->ev_up));
+	if (!w->ev_up) CK(hipEventCreateWithFlags(&w->ev_up, hipEventDisableTiming));
+	else CK(hipEventSynchronize(w->ev_up));
 	if (stage > w->cap_stage) {
-		if (w->h_stage) DCK(hipHostFree(w->h_stage));
+		if (w->h_stage) CK(hipHostFree(w->h_stage));
 		w->h_stage = nullptr; w->cap_stage = 0;
-		DCK(hipHostMalloc((void**)&w->h_stage, stage, hipHostMallocDefault));
+		CK(hipHostMalloc((void**)&w->h_stage, stage, hipHostMallocDefault));
 		w->cap_stage = stage;
 	}
 	memcpy(w->h_stage, fd.data(), fdb);
 	memcpy(w->h_stage + fdb, pb.data(), npb * 4);
-	DCK(hipMemcpyAsync(w->fd, w->h_stage, fdb, hipMemcpyHostToDevice, s));
-	DCK(hipMemcpyAsync(w->pbase, w->h_stage + fdb, npb * 4, hipMemcpyHostToDevice, s));
-	DCK(hipEventRecord(w->ev_up, s));
+	CK(hipMemcpyAsync(w->fd, w->h_stage, fdb, hipMemcpyHostToDevice, s));
+	CK(hipMemcpyAsync(w->pbase, w->h_stage + fdb, npb * 4, hipMemcpyHostToDevice, s));
+	CK(hipEventRecord(w->ev_up, s));
 
 	size_t pbo = 0;
 	for (const chunk& k : ch) {
@@ -618,8 +581,8 @@ static int lzd_frames(agmv_hip_ctx* c, int version, const uint8_t* d_src, const 
 		lzd_fs* fsk = w->fs + k.f0;
 		pbo += k.nf + 1;
 		const uint32_t rounds = ceil_log2(k.maxw) + 1;
-		DCK(hipMemsetD32Async((hipDeviceptr_t)w->words, (int)LZD_RES, k.nwords ? k.nwords : 1, s));
-		DCK(hipMemsetAsync(w->ctl + 1, 0, LZD_ROUNDS * 4, s));
+		CK(hipMemsetD32Async((hipDeviceptr_t)w->words, (int)LZD_RES, k.nwords ? k.nwords : 1, s));
+		CK(hipMemsetAsync(w->ctl + 1, 0, LZD_ROUNDS * 4, s));
 		if (lzss) {
 			if (k.npieces)
 				hipLaunchKernelGGL(k_lzd_spiece, dim3((k.npieces + LZD_PPB - 1) / LZD_PPB), dim3(256), 0, s, k.npieces, pbk, k.nf, fdk,
@@ -643,31 +606,27 @@ static int lzd_frames(agmv_hip_ctx* c, int version, const uint8_t* d_src, const 
 			hipLaunchKernelGGL(k_lzd_final<false>, dim3((k.nf + 63) / 64), dim3(64), 0, s, k.nf, k.f0, fdk, (uint32_t)lim, fsk, d_bpos,
 			                   d_used, w->ctl);
 		}
-		DCK(hipGetLastError());
+		CK(hipGetLastError());
 		if (k.nwords) {
 			const uint32_t g = (k.nwords + 1023) / 1024;
 			for (uint32_t r = 0; r < rounds; r++)
 				hipLaunchKernelGGL(k_lzd_jump, dim3(g < 8192 ? g : 8192), dim3(256), 0, s, k.nwords, r, w->ctl + 1, w->words);
-			DCK(hipGetLastError());
+			CK(hipGetLastError());
 		}
 		hipLaunchKernelGGL(k_lzd_serial, dim3((k.nf + 63) / 64), dim3(64), 0, s, k.nf, k.f0, lzss ? 1 : 0, fdk, d_src, d_off,
 		                   (uint32_t)lim, d_bits, (unsigned long long)bits_stride, fsk, d_bpos, d_used);
 		const unsigned long long gx = (lim + 4095) / 4096;
 		hipLaunchKernelGGL(k_lzd_out, dim3(gx < 1 ? 1 : (gx > 1024 ? 1024 : (uint32_t)gx), k.nf), dim3(256), 0, s, k.f0, fdk, fsk,
 		                   w->words, d_bpos, d_bits, (unsigned long long)bits_stride);
-		DCK(hipGetLastError());
+		CK(hipGetLastError());
 	}
 	return lzd_mark_done(w, s);
 }
 
 static int check_args(agmv_hip_ctx* c, size_t bits_stride, size_t cap, const char* who)
 {
-	char m[256];
-	if (!c) return agmv_hip_internal_error("agmv_hip: NULL context");
-	if (cap > bits_stride || cap >= (1ull << 31)) {
-		snprintf(m, sizeof(m), "%s: cap %zu must be <= bits_stride %zu and < 2^31", who, cap, bits_stride);
-		return agmv_hip_internal_error(m);
-	}
+	if (!c) return agmv_hip_err("agmv_hip: NULL context");
+	if (cap > bits_stride || cap >= (1ull << 31)) return agmv_hip_err("%s: cap %zu must be <= bits_stride %zu and < 2^31", who, cap, bits_stride);
 	return 0;
 }
 
@@ -677,19 +636,19 @@ extern "C" int agmv_hip_lz_decode_frames_dev(agmv_hip_ctx* c, int version, const
                                              void* stream)
 {
 	if (check_args(c, bits_stride, cap, "agmv_hip_lz_decode_frames_dev")) return -1;
-	DCK(hipSetDevice(agmv_hip_internal_device(c)));
+	CK(hipSetDevice(c->device));
 	hipStream_t s = (hipStream_t)stream;
 	if (n_frames == 0) {
 		lzd_ws* w = lzd_get(c);
 		if (!w) return -1;
-		DCK(hipMemsetAsync(w->ctl, 0, 4, s));
+		CK(hipMemsetAsync(w->ctl, 0, 4, s));
 		return 0;
 	}
 	std::vector<uint32_t> h((size_t)3 * n_frames);     // the sizes decide the chunks: read them once
-	DCK(hipMemcpyAsync(h.data(), d_avail, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s));
-	DCK(hipMemcpyAsync(h.data() + n_frames, d_usize, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s));
-	DCK(hipMemcpyAsync(h.data() + 2 * (size_t)n_frames, d_csize, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s));
-	DCK(hipStreamSynchronize(s));
+	CK(hipMemcpyAsync(h.data(), d_avail, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s));
+	CK(hipMemcpyAsync(h.data() + n_frames, d_usize, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s));
+	CK(hipMemcpyAsync(h.data() + 2 * (size_t)n_frames, d_csize, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s));
+	CK(hipStreamSynchronize(s));
 	return lzd_frames(c, version, d_src, d_off, h.data(), h.data() + n_frames, h.data() + 2 * (size_t)n_frames, n_frames, d_bits,
 	                  bits_stride, cap, d_bpos, d_used, s);
 }
@@ -700,12 +659,12 @@ extern "C" int agmv_hip_lz_decode_frames_sized_dev(agmv_hip_ctx* c, int version,
                                                    uint32_t* d_used, void* stream)
 {
 	if (check_args(c, bits_stride, cap, "agmv_hip_lz_decode_frames_sized_dev")) return -1;
-	DCK(hipSetDevice(agmv_hip_internal_device(c)));
+	CK(hipSetDevice(c->device));
 	hipStream_t s = (hipStream_t)stream;
 	if (n_frames == 0) {
 		lzd_ws* w = lzd_get(c);
 		if (!w) return -1;
-		DCK(hipMemsetAsync(w->ctl, 0, 4, s));
+		CK(hipMemsetAsync(w->ctl, 0, 4, s));
 		return 0;
 	}
 	return lzd_frames(c, version, d_src, d_off, h_avail, h_usize, h_csize, n_frames, d_bits, bits_stride, cap, d_bpos, d_used, s);
@@ -714,16 +673,15 @@ extern "C" int agmv_hip_lz_decode_frames_sized_dev(agmv_hip_ctx* c, int version,
 extern "C" int agmv_hip_lz_decode_commit_dev(agmv_hip_ctx* c, uint8_t* d_bits, size_t bits_stride, const uint32_t* d_bpos,
                                              uint32_t n_frames, uint8_t* d_persist, size_t cap, void* stream)
 {
-	if (!c) return agmv_hip_internal_error("agmv_hip: NULL context");
-	DCK(hipSetDevice(agmv_hip_internal_device(c)));
+	if (agmv_hip_enter(c)) return -1;
 	if (n_frames == 0 || cap == 0) return 0;
 	hipStream_t s = (hipStream_t)stream;
 	lzd_ws* w = lzd_get(c);
 	if (!w) return -1;
 	const uint32_t levels = ceil_log2(n_frames) + 1, n = n_frames;
-	if ((size_t)levels * n > w->cap_tab && w->ev_done) DCK(hipEventSynchronize(w->ev_done));
-	if (grow(&w->tab, &w->cap_tab, (size_t)levels * n)) return -1;
-	DCK(hipMemcpyAsync(w->tab, d_bpos, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+	if ((size_t)levels * n > w->cap_tab && w->ev_done) CK(hipEventSynchronize(w->ev_done));
+	CK(agmv_hip_dev_grow(&w->tab, &w->cap_tab, (size_t)levels * n));
+	CK(hipMemcpyAsync(w->tab, d_bpos, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
 	for (uint32_t L = 1; L < levels; L++)
 		hipLaunchKernelGGL(k_lzc_level, dim3((n + 255) / 256), dim3(256), 0, s, n, 1u << (L - 1), w->tab + (size_t)(L - 1) * n,
 		                   w->tab + (size_t)L * n);
@@ -732,19 +690,18 @@ extern "C" int agmv_hip_lz_decode_commit_dev(agmv_hip_ctx* c, uint8_t* d_bits, s
 	const unsigned long long g = (cap + 1023) / 1024;
 	hipLaunchKernelGGL(k_lzc_persist, dim3(g > 4096 ? 4096 : (uint32_t)g), dim3(256), 0, s, n, levels, w->tab, d_bits,
 	                   (unsigned long long)bits_stride, (unsigned long long)cap, d_persist);
-	DCK(hipGetLastError());
+	CK(hipGetLastError());
 	return lzd_mark_done(w, s);
 }
 
 extern "C" int agmv_hip_lz_decode_fallback_frames(agmv_hip_ctx* c, void* stream)
 {
-	if (!c) return agmv_hip_internal_error("agmv_hip: NULL context");
-	DCK(hipSetDevice(agmv_hip_internal_device(c)));
-	void** slot = agmv_hip_internal_lzd_slot(c);
-	if (!*slot) return 0;
+	if (agmv_hip_enter(c)) return -1;
+	const lzd_ws* w = (const lzd_ws*)c->ws[AREA_LZ_DECODE];
+	if (!w || !w->ctl) return 0;
 	uint32_t v = 0;
-	DCK(hipStreamSynchronize((hipStream_t)stream));
-	DCK(hipMemcpy(&v, ((lzd_ws*)*slot)->ctl, 4, hipMemcpyDeviceToHost));
+	CK(hipStreamSynchronize((hipStream_t)stream));
+	CK(hipMemcpy(&v, w->ctl, 4, hipMemcpyDeviceToHost));
 	return (int)v;
 }
 
@@ -754,15 +711,12 @@ extern "C" int agmv_hip_lz_decode_frames(agmv_hip_ctx* c, int version, const uin
                                          uint32_t* h_bpos, uint32_t* h_used, uint8_t* h_persist)
 {
 	if (check_args(c, bits_stride, cap, "agmv_hip_lz_decode_frames")) return -1;
-	DCK(hipSetDevice(agmv_hip_internal_device(c)));
+	CK(hipSetDevice(c->device));
 	if (n_frames == 0) return 0;
 	for (uint32_t f = 0; f < n_frames; f++) {
 		const unsigned long long r = h_avail[f] < (unsigned long long)h_csize[f] + 3 ? h_avail[f] : (unsigned long long)h_csize[f] + 3;
-		if (h_off[f] > src_len || r > src_len - h_off[f]) {
-			char m[256];
-			snprintf(m, sizeof(m), "agmv_hip_lz_decode_frames: frame %u reads %llu bytes at %llu of a %zu-byte source", f, r, h_off[f], src_len);
-			return agmv_hip_internal_error(m);
-		}
+		if (h_off[f] > src_len || r > src_len - h_off[f])
+			return agmv_hip_err("agmv_hip_lz_decode_frames: frame %u reads %llu bytes at %llu of a %zu-byte source", f, r, h_off[f], src_len);
 	}
 	uint8_t *dsrc = nullptr, *dbits = nullptr, *dper = nullptr;
 	unsigned long long* doff = nullptr;
@@ -779,7 +733,7 @@ extern "C" int agmv_hip_lz_decode_frames(agmv_hip_ctx* c, int version, const uin
 	    (e = hipMemcpy(doff, h_off, (size_t)n_frames * 8, hipMemcpyHostToDevice)) != hipSuccess ||
 	    (e = hipMemcpy(dbits, h_bits, (size_t)n_frames * bits_stride, hipMemcpyHostToDevice)) != hipSuccess ||
 	    (h_persist ? (e = hipMemcpy(dper, h_persist, cap, hipMemcpyHostToDevice)) : (e = hipMemset(dper, 0, cap))) != hipSuccess) {
-		lzd_fail("agmv_hip_lz_decode_frames", e, __LINE__);
+		agmv_hip_hip_failed("agmv_hip_lz_decode_frames", e, __FILE_NAME__, __LINE__);
 		goto done;
 	}
 	if (lzd_frames(c, version, dsrc, doff, h_avail, h_usize, h_csize, n_frames, dbits, bits_stride, cap, dbp, dused, nullptr) ||
@@ -790,7 +744,7 @@ extern "C" int agmv_hip_lz_decode_frames(agmv_hip_ctx* c, int version, const uin
 	    (e = hipMemcpy(h_used, dused, (size_t)n_frames * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
 	    (e = hipMemcpy(h_bits, dbits, (size_t)n_frames * bits_stride, hipMemcpyDeviceToHost)) != hipSuccess ||
 	    (h_persist && (e = hipMemcpy(h_persist, dper, cap, hipMemcpyDeviceToHost)) != hipSuccess)) {
-		lzd_fail("agmv_hip_lz_decode_frames", e, __LINE__);
+		agmv_hip_hip_failed("agmv_hip_lz_decode_frames", e, __FILE_NAME__, __LINE__);
 		goto done;
 	}
 	rc = 0;

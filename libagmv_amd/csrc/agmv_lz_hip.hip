@@ -23,26 +23,11 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include <vector>
 
-#include "../../include/agmv_hip.h"
-
-// defined in agmv_hip.hip: the library's error text, and the context's slot for this stage's work areas
-int agmv_hip_internal_error(const char* msg);
-void** agmv_hip_internal_lz_slot(agmv_hip_ctx* c);
-int agmv_hip_internal_device(agmv_hip_ctx* c);
-
-static int lz_fail(const char* what, hipError_t e, int line)
-{
-	char m[512];
-	snprintf(m, sizeof(m), "agmv_hip: %s failed: %s (agmv_lz_hip.hip:%d)", what, hipGetErrorString(e), line);
-	return agmv_hip_internal_error(m);
-}
-#define LCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return lz_fail(#x, e_, __LINE__); } while (0)
+#include "agmv_hip_impl.h"
 
 constexpr uint32_t LZ_WIN = 65535;            // matches start in [i - 65535, i)
 constexpr uint32_t LZ_MAXLEN = 15;
@@ -340,7 +325,7 @@ __global__ void __launch_bounds__(256) k_lz_copy(uint32_t f0, const uint32_t* __
 // work areas (per context, grown on demand)
 // ---------------------------------------------------------------------------------------------------------------------
 struct lz_ws {
-	uint32_t cap_n;             // positions of a chunk
+	size_t cap_n;               // positions of a chunk
 	uint8_t* cat;               // cap_n + LZ_PAD
 	uint32_t *kA, *kB, *vA, *vB, *grp, *res, *fend;
 	uint32_t* hist;             // 256 per radix tile, then the scan's block sums
@@ -356,10 +341,9 @@ struct lz_ws {
 	uint32_t* tab;
 };
 
-extern "C++" void agmv_hip_internal_lz_free(void* p)
+static void lz_free(void* p)
 {
 	lz_ws* w = (lz_ws*)p;
-	if (!w) return;
 	void* all[] = {w->cat, w->kA, w->kB, w->vA, w->vB, w->grp, w->res, w->fend, w->hist, w->part, w->pexit, w->pbits, w->pentry, w->poff, w->words, w->tab};
 	for (void* a : all) if (a) (void)hipFree(a);
 	free(w);
@@ -367,42 +351,24 @@ extern "C++" void agmv_hip_internal_lz_free(void* p)
 
 static int lz_grow(lz_ws* w, uint32_t n, size_t pieces, size_t nwords, size_t ntab)
 {
-	if (n > w->cap_n) {
-		void** bufs[] = {(void**)&w->kA, (void**)&w->kB, (void**)&w->vA, (void**)&w->vB, (void**)&w->grp, (void**)&w->res, (void**)&w->fend};
-		for (void** b : bufs) { if (*b) LCK(hipFree(*b)); *b = nullptr; }
-		if (w->cat) LCK(hipFree(w->cat));
-		if (w->hist) LCK(hipFree(w->hist));
-		if (w->part) LCK(hipFree(w->part));
-		w->cat = nullptr; w->hist = nullptr; w->part = nullptr; w->cap_n = 0;
-		for (void** b : bufs) LCK(hipMalloc(b, (size_t)n * 4));
-		LCK(hipMalloc((void**)&w->cat, (size_t)n + LZ_PAD));
-		const size_t ntiles = (n + RS_TILE - 1) / RS_TILE;
-		LCK(hipMalloc((void**)&w->hist, ntiles * 256 * 4));
-		LCK(hipMalloc((void**)&w->part, ((size_t)n / SC_BLOCK + 2) * 4));
+	if (n > w->cap_n) {                                            // one capacity for all of these: committed when all exist
+		w->cap_n = 0;
+		for (uint32_t** b : {&w->kA, &w->kB, &w->vA, &w->vB, &w->grp, &w->res, &w->fend}) CK(agmv_hip_dev_grow(b, nullptr, n));
+		CK(agmv_hip_dev_grow(&w->cat, nullptr, (size_t)n + LZ_PAD));
+		CK(agmv_hip_dev_grow(&w->hist, nullptr, ((size_t)n + RS_TILE - 1) / RS_TILE * 256));
+		CK(agmv_hip_dev_grow(&w->part, nullptr, (size_t)n / SC_BLOCK + 2));
 		w->cap_n = n;
 	}
 	if (pieces > w->cap_pieces) {
-		void** bufs[] = {(void**)&w->pexit, (void**)&w->pbits, (void**)&w->pentry, (void**)&w->poff};
-		for (void** b : bufs) { if (*b) LCK(hipFree(*b)); *b = nullptr; }
 		w->cap_pieces = 0;
-		LCK(hipMalloc((void**)&w->pexit, pieces * LZ_MAXLEN));
-		LCK(hipMalloc((void**)&w->pbits, pieces * LZ_MAXLEN * 4));
-		LCK(hipMalloc((void**)&w->pentry, pieces));
-		LCK(hipMalloc((void**)&w->poff, pieces * 4));
+		CK(agmv_hip_dev_grow(&w->pexit, nullptr, pieces * LZ_MAXLEN));
+		CK(agmv_hip_dev_grow(&w->pbits, nullptr, pieces * LZ_MAXLEN));
+		CK(agmv_hip_dev_grow(&w->pentry, nullptr, pieces));
+		CK(agmv_hip_dev_grow(&w->poff, nullptr, pieces));
 		w->cap_pieces = pieces;
 	}
-	if (nwords > w->cap_words) {
-		if (w->words) LCK(hipFree(w->words));
-		w->words = nullptr; w->cap_words = 0;
-		LCK(hipMalloc((void**)&w->words, nwords * 4));
-		w->cap_words = nwords;
-	}
-	if (ntab > w->cap_tab) {
-		if (w->tab) LCK(hipFree(w->tab));
-		w->tab = nullptr; w->cap_tab = 0;
-		LCK(hipMalloc((void**)&w->tab, ntab * 4));
-		w->cap_tab = ntab;
-	}
+	CK(agmv_hip_dev_grow(&w->words, &w->cap_words, nwords));
+	CK(agmv_hip_dev_grow(&w->tab, &w->cap_tab, ntab));
 	return 0;
 }
 
@@ -413,7 +379,7 @@ static int scan_u32(lz_ws* w, uint32_t* a, uint32_t n, bool inclusive, hipStream
 	hipLaunchKernelGGL(k_scan_part, dim3(1), dim3(256), 0, s, w->part, nb);
 	if (inclusive) hipLaunchKernelGGL(k_scan_down<true>, dim3(nb), dim3(256), 0, s, a, n, w->part);
 	else           hipLaunchKernelGGL(k_scan_down<false>, dim3(nb), dim3(256), 0, s, a, n, w->part);
-	LCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }
 
@@ -426,10 +392,10 @@ static int radix_sort(lz_ws* w, uint32_t n, uint32_t nbits, bool* in_b, hipStrea
 		uint32_t* ki = b ? w->kB : w->kA; uint32_t* vi = b ? w->vB : w->vA;
 		uint32_t* ko = b ? w->kA : w->kB; uint32_t* vo = b ? w->vA : w->vB;
 		hipLaunchKernelGGL(k_rs_hist, dim3(ntiles), dim3(64), 0, s, n, ki, shift, w->hist, ntiles);
-		LCK(hipGetLastError());
+		CK(hipGetLastError());
 		if (scan_u32(w, w->hist, ntiles * 256, false, s)) return -1;
 		hipLaunchKernelGGL(k_rs_scatter, dim3(ntiles), dim3(64), 0, s, n, ki, vi, ko, vo, shift, w->hist, ntiles);
-		LCK(hipGetLastError());
+		CK(hipGetLastError());
 		b = !b;
 	}
 	*in_b = b;
@@ -446,28 +412,20 @@ extern "C" size_t agmv_hip_lzss_max_csize(size_t n)
 extern "C" int agmv_hip_lzss_frames_dev(agmv_hip_ctx* c, const uint8_t* d_bits, size_t bits_stride, const uint32_t* d_sizes,
                                         uint32_t n_frames, uint8_t* d_out, size_t out_stride, uint32_t* d_csize, void* stream)
 {
-	if (!c) return agmv_hip_internal_error("agmv_hip: NULL context");
-	LCK(hipSetDevice(agmv_hip_internal_device(c)));
+	if (agmv_hip_enter(c)) return -1;
 	if (n_frames == 0) return 0;
 	hipStream_t s = (hipStream_t)stream;
-	void** slot = agmv_hip_internal_lz_slot(c);
-	if (!*slot) {
-		*slot = calloc(1, sizeof(lz_ws));
-		if (!*slot) return agmv_hip_internal_error("agmv_hip: out of host memory");
-	}
-	lz_ws* w = (lz_ws*)*slot;
+	lz_ws* w = (lz_ws*)agmv_hip_area(c, AREA_LZSS, sizeof(lz_ws), lz_free);
+	if (!w) return -1;
 
 	// the sizes decide the chunks: read them once
 	std::vector<uint32_t> sz(n_frames);
-	LCK(hipMemcpyAsync(sz.data(), d_sizes, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s));
-	LCK(hipStreamSynchronize(s));
+	CK(hipMemcpyAsync(sz.data(), d_sizes, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s));
+	CK(hipStreamSynchronize(s));
 	for (uint32_t f = 0; f < n_frames; f++) {
-		char m[256];
-		if (sz[f] > bits_stride || sz[f] >= LZ_CHUNK || agmv_hip_lzss_max_csize(sz[f]) > out_stride) {
-			snprintf(m, sizeof(m), "agmv_hip_lzss_frames_dev: frame %u: %u bytes (bits_stride %zu, out_stride %zu, at most %u bytes per frame)",
-			         f, sz[f], bits_stride, out_stride, LZ_CHUNK - 1);
-			return agmv_hip_internal_error(m);
-		}
+		if (sz[f] > bits_stride || sz[f] >= LZ_CHUNK || agmv_hip_lzss_max_csize(sz[f]) > out_stride)
+			return agmv_hip_err("agmv_hip_lzss_frames_dev: frame %u: %u bytes (bits_stride %zu, out_stride %zu, at most %u bytes per frame)",
+			                    f, sz[f], bits_stride, out_stride, LZ_CHUNK - 1);
 	}
 	// chunks: [f0, f1) with <= LZ_CHUNK positions and <= LZ_CHUNK_FRAMES frames; per chunk the tables
 	//   fstart[nf + 1] (chunk positions), pb[nf + 1] (first piece), wb[nf + 1] (first output word)
@@ -495,8 +453,8 @@ extern "C" int agmv_hip_lzss_frames_dev(agmv_hip_ctx* c, const uint8_t* d_bits, 
 		ch.push_back(k);
 	}
 	if (lz_grow(w, maxn < RS_TILE ? RS_TILE : maxn, maxp < 1 ? 1 : maxp, maxw < 1 ? 1 : maxw, tab.size())) return -1;
-	LCK(hipMemcpyAsync(w->tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
-	LCK(hipStreamSynchronize(s));                                   // (tab is host memory of this call)
+	CK(hipMemcpyAsync(w->tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+	CK(hipStreamSynchronize(s));                                   // (tab is host memory of this call)
 
 	for (const chunk& k : ch) {
 		const uint32_t* fs = w->tab + k.tab;
@@ -507,43 +465,43 @@ extern "C" int agmv_hip_lzss_frames_dev(agmv_hip_ctx* c, const uint8_t* d_bits, 
 			hipLaunchKernelGGL(k_lz_gather, dim3((N + LZ_PAD + 255) / 256), dim3(256), 0, s, d_bits, (unsigned long long)bits_stride,
 			                   fs, k.f0, k.nf, N, w->cat, w->fend);
 			hipLaunchKernelGGL(k_lz_key3, dim3(gN), dim3(256), 0, s, fs, k.nf, N, w->cat, w->kA, w->vA, w->res);
-			LCK(hipGetLastError());
+			CK(hipGetLastError());
 			const uint32_t rank_bits = bit_len(N - 1) > 1 ? bit_len(N - 1) : 1;
 			for (uint32_t L = 3; L <= LZ_MAXLEN; L++) {
 				bool in_b = false;
 				if (radix_sort(w, N, L == 3 ? 24 + bit_len(k.nf - 1) : 8 + rank_bits, &in_b, s)) return -1;
 				uint32_t* ks = in_b ? w->kB : w->kA; uint32_t* vs = in_b ? w->vB : w->vA;
 				hipLaunchKernelGGL(k_lz_query, dim3(gN), dim3(256), 0, s, N, L, ks, vs, w->fend, w->res);
-				LCK(hipGetLastError());
+				CK(hipGetLastError());
 				if (L == LZ_MAXLEN) break;
 				hipLaunchKernelGGL(k_lz_heads, dim3(gN), dim3(256), 0, s, N, ks, w->grp);
-				LCK(hipGetLastError());
+				CK(hipGetLastError());
 				if (scan_u32(w, w->grp, N, true, s)) return -1;
 				// the next level's keys go to the A buffers: its sort starts there
-				if (in_b) LCK(hipMemcpyAsync(w->vA, w->vB, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
+				if (in_b) CK(hipMemcpyAsync(w->vA, w->vB, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
 				hipLaunchKernelGGL(k_lz_key, dim3(gN), dim3(256), 0, s, N, L + 1, w->cat, w->grp, w->vA, w->kA);
-				LCK(hipGetLastError());
+				CK(hipGetLastError());
 			}
 		}
 		if (k.npieces) {
 			hipLaunchKernelGGL(k_lz_piece, dim3((k.npieces * 16 + 255) / 256), dim3(256), 0, s, k.npieces, pb, fs, k.nf, w->res,
 			                   w->pexit, w->pbits);
-			LCK(hipGetLastError());
+			CK(hipGetLastError());
 		}
 		hipLaunchKernelGGL(k_lz_fscan, dim3((k.nf + 63) / 64), dim3(64), 0, s, k.nf, pb, w->pexit, w->pbits, w->pentry, w->poff,
 		                   d_csize + k.f0);
-		LCK(hipGetLastError());
+		CK(hipGetLastError());
 		if (k.npieces) {
-			LCK(hipMemsetAsync(w->words, 0, (size_t)k.nwords * 4, s));
+			CK(hipMemsetAsync(w->words, 0, (size_t)k.nwords * 4, s));
 			hipLaunchKernelGGL(k_lz_emit, dim3((k.npieces + 255) / 256), dim3(256), 0, s, k.npieces, pb, fs, k.nf, wb, w->cat, w->res,
 			                   w->pentry, w->poff, w->words);
-			LCK(hipGetLastError());
+			CK(hipGetLastError());
 			uint32_t maxf = 0;
 			for (uint32_t j = 0; j < k.nf; j++) if (sz[k.f0 + j] > maxf) maxf = sz[k.f0 + j];
 			const uint32_t gx = (uint32_t)((agmv_hip_lzss_max_csize(maxf) + 4095) / 4096);
 			hipLaunchKernelGGL(k_lz_copy, dim3(gx < 1 ? 1 : gx, k.nf), dim3(256), 0, s, k.f0, wb, w->words, d_csize, d_out,
 			                   (unsigned long long)out_stride);
-			LCK(hipGetLastError());
+			CK(hipGetLastError());
 		}
 	}
 	return 0;
@@ -552,8 +510,7 @@ extern "C" int agmv_hip_lzss_frames_dev(agmv_hip_ctx* c, const uint8_t* d_bits, 
 extern "C" int agmv_hip_lzss_frames(agmv_hip_ctx* c, const uint8_t* h_bits, size_t bits_stride, const uint32_t* h_sizes,
                                     uint32_t n_frames, uint8_t* h_out, size_t out_stride, uint32_t* h_csize)
 {
-	if (!c) return agmv_hip_internal_error("agmv_hip: NULL context");
-	LCK(hipSetDevice(agmv_hip_internal_device(c)));
+	if (agmv_hip_enter(c)) return -1;
 	if (n_frames == 0) return 0;
 	uint8_t *db = nullptr, *dout = nullptr;
 	uint32_t *ds = nullptr, *dc = nullptr;
@@ -565,18 +522,18 @@ extern "C" int agmv_hip_lzss_frames(agmv_hip_ctx* c, const uint8_t* h_bits, size
 	    (e = hipMalloc((void**)&dc, (size_t)n_frames * 4)) != hipSuccess ||
 	    (e = hipMemcpy(db, h_bits, (size_t)n_frames * bits_stride, hipMemcpyHostToDevice)) != hipSuccess ||
 	    (e = hipMemcpy(ds, h_sizes, (size_t)n_frames * 4, hipMemcpyHostToDevice)) != hipSuccess) {
-		lz_fail("agmv_hip_lzss_frames", e, __LINE__);
+		agmv_hip_hip_failed("agmv_hip_lzss_frames", e, __FILE_NAME__, __LINE__);
 		goto done;
 	}
 	if (agmv_hip_lzss_frames_dev(c, db, bits_stride, ds, n_frames, dout, out_stride, dc, nullptr)) goto done;
 	if ((e = hipDeviceSynchronize()) != hipSuccess ||
 	    (e = hipMemcpy(h_csize, dc, (size_t)n_frames * 4, hipMemcpyDeviceToHost)) != hipSuccess) {
-		lz_fail("agmv_hip_lzss_frames", e, __LINE__);
+		agmv_hip_hip_failed("agmv_hip_lzss_frames", e, __FILE_NAME__, __LINE__);
 		goto done;
 	}
 	for (uint32_t f = 0; f < n_frames; f++)                        // rows: only the payload bytes are defined
 		if (h_csize[f] && (e = hipMemcpy(h_out + (size_t)f * out_stride, dout + (size_t)f * out_stride, h_csize[f], hipMemcpyDeviceToHost)) != hipSuccess) {
-			lz_fail("agmv_hip_lzss_frames", e, __LINE__);
+			agmv_hip_hip_failed("agmv_hip_lzss_frames", e, __FILE_NAME__, __LINE__);
 			goto done;
 		}
 	rc = 0;

@@ -14,33 +14,10 @@
 // Pass p measures the distortion of the centroids of round p's start, so the last pass (update with `last`) only measures.
 #include <hip/hip_runtime.h>
 
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
+#include <stdlib.h>
 
-#include "../../include/agmv_hip.h"
-
-// defined in agmv_hip.hip: the library's error text, the context's device and its slot for the work area of this file
-int agmv_hip_internal_error(const char* msg);
-int agmv_hip_internal_device(agmv_hip_ctx* c);
-void** agmv_hip_internal_pal_slot(agmv_hip_ctx* c);
-
-static int pal_err(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-static int pal_err(const char* fmt, ...)
-{
-	char m[512];
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(m, sizeof(m), fmt, ap);
-	va_end(ap);
-	return agmv_hip_internal_error(m);
-}
-
-static int pal_fail(const char* what, hipError_t e, int line)
-{
-	return pal_err("agmv_hip: %s failed: %s (agmv_palette_hip.hip:%d)", what, hipGetErrorString(e), line);
-}
-#define PCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return pal_fail(#x, e_, __LINE__); } while (0)
+#include "agmv_hip_impl.h"
 
 constexpr uint32_t PAL_MAX_K = 512;
 constexpr uint32_t PAL_T = 256;                // lanes, and bins, of a k_pal_assign workgroup
@@ -133,32 +110,37 @@ __global__ __launch_bounds__(PAL_MAX_K) void k_pal_update(uint32_t* __restrict__
 	}
 }
 
-extern "C++" void agmv_hip_internal_pal_free(void* p)
+// the context's area of this stage holds the device memory of a pass
+struct pal_area { pal_ws* d; };
+
+static void pal_area_free(void* p)
 {
-	if (p) (void)hipFree(p);
+	(void)hipFree(((pal_area*)p)->d);
+	free(p);
 }
 
 extern "C" int agmv_hip_palette_refine_dev(agmv_hip_ctx* c, const uint32_t* d_hist, int quality, uint32_t* d_pal, uint32_t k, uint32_t n_free,
                                            uint32_t iterations, uint32_t* d_rounds, uint64_t* d_sse, void* stream)
 {
-	if (!c) return pal_err("agmv_hip: NULL context");
-	if (!d_hist || !d_pal || !d_rounds || !d_sse) return pal_err("agmv_hip_palette_refine_dev: NULL pointer");
-	if (quality < 1 || quality > 3) return pal_err("agmv_hip_palette_refine_dev: quality %d is not 1 (HIGH), 2 (MID) or 3 (LOW)", quality);
-	if (k < 1 || k > PAL_MAX_K) return pal_err("agmv_hip_palette_refine_dev: k = %u centroids, 1 .. %u are possible", k, PAL_MAX_K);
-	if (n_free > k) return pal_err("agmv_hip_palette_refine_dev: n_free = %u exceeds k = %u", n_free, k);
-	if (iterations > PAL_MAX_ITERATIONS) return pal_err("agmv_hip_palette_refine_dev: %u iterations, at most %u are possible", iterations, PAL_MAX_ITERATIONS);
-	PCK(hipSetDevice(agmv_hip_internal_device(c)));
-	void** slot = agmv_hip_internal_pal_slot(c);
-	if (!*slot) PCK(hipMalloc(slot, sizeof(pal_ws)));
-	pal_ws* ws = (pal_ws*)*slot;
+	if (!c) return agmv_hip_err("agmv_hip: NULL context");
+	if (!d_hist || !d_pal || !d_rounds || !d_sse) return agmv_hip_err("agmv_hip_palette_refine_dev: NULL pointer");
+	if (quality < 1 || quality > 3) return agmv_hip_err("agmv_hip_palette_refine_dev: quality %d is not 1 (HIGH), 2 (MID) or 3 (LOW)", quality);
+	if (k < 1 || k > PAL_MAX_K) return agmv_hip_err("agmv_hip_palette_refine_dev: k = %u centroids, 1 .. %u are possible", k, PAL_MAX_K);
+	if (n_free > k) return agmv_hip_err("agmv_hip_palette_refine_dev: n_free = %u exceeds k = %u", n_free, k);
+	if (iterations > PAL_MAX_ITERATIONS) return agmv_hip_err("agmv_hip_palette_refine_dev: %u iterations, at most %u are possible", iterations, PAL_MAX_ITERATIONS);
+	CK(hipSetDevice(c->device));
+	pal_area* area = (pal_area*)agmv_hip_area(c, AREA_PALETTE, sizeof(pal_area), pal_area_free);
+	if (!area) return -1;
+	if (!area->d) CK(hipMalloc(&area->d, sizeof(pal_ws)));
+	pal_ws* ws = area->d;
 	const hipStream_t s = (hipStream_t)stream;
 	const uint32_t n_codes = quality == 2 ? 1u << 17 : (quality == 3 ? 1u << 16 : 1u << 19);
-	PCK(hipMemsetAsync(ws, 0, sizeof(pal_ws), s));
-	PCK(hipMemsetAsync(d_rounds, 0, sizeof(uint32_t), s));
+	CK(hipMemsetAsync(ws, 0, sizeof(pal_ws), s));
+	CK(hipMemsetAsync(d_rounds, 0, sizeof(uint32_t), s));
 	for (uint32_t p = 0; p <= iterations; p++) {
 		hipLaunchKernelGGL(k_pal_assign, dim3(n_codes / PAL_T), dim3(PAL_T), 0, s, d_hist, quality, (const uint32_t*)d_pal, k, ws);
 		hipLaunchKernelGGL(k_pal_update, dim3(1), dim3(PAL_MAX_K), 0, s, d_pal, k, n_free, ws, d_rounds, (unsigned long long*)d_sse, p == 0, p == iterations);
 	}
-	PCK(hipGetLastError());
+	CK(hipGetLastError());
 	return 0;
 }

@@ -1,4 +1,4 @@
-"""The decoder's part of a context (agmv_decode_hip.hip: struct dec_ws behind one slot of agmv_hip_ctx) is created by the
+"""The decoder's part of a context (agmv_decode_hip.hip: struct dec_ws, one of the work areas of agmv_hip_ctx) is created by the
 first parse or decode call and freed by agmv_hip_destroy: contexts that never decode, two contexts side by side, a work area
 that shrinks and grows again, and the timing groups the decoder marks in the core's events.  Expected pixels: the CPU oracle."""
 import math
