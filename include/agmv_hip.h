@@ -165,8 +165,8 @@ int agmv_hip_decode_frames_dev(agmv_hip_ctx* ctx, const uint8_t* d_bits, size_t 
                                uint32_t h, uint32_t first_frame_count, uint32_t* d_pix_out,
                                const uint32_t* d_prev_frame, const uint32_t* d_prev_iframe,
                                void* stream);
-/* How many frames of the last agmv_hip_parse_frames_dev call (of the last range, for agmv_hip_parse_decode_frames_dev)
-   the speculative parser could not prove and left to the robust kernels (0 for streams the encoder emits unless a
+/* How many frames of the last agmv_hip_parse_frames_dev call (of the last range, for agmv_hip_parse_decode_frames_dev; of
+   the whole call, whatever its ranges, for agmv_hip_decode_bitstreams_dev) the speculative parser could not prove and left to the robust kernels (0 for streams the encoder emits unless a
    long run of FILL blocks carries a flag-valued index; damaged streams typically land here).  A statistic: the
    outputs are the same either way.  Synchronises the stream; negative on error. */
 int agmv_hip_parse_fallback_frames(agmv_hip_ctx* ctx, void* stream);
@@ -185,7 +185,14 @@ int agmv_hip_parse_decode_frames_dev(agmv_hip_ctx* ctx, const uint8_t* d_bits, s
    the robust kernels.  This is the form the sequence drivers and bench.py use: it saves the 4 bytes per block that
    agmv_hip_parse_frames_dev writes and agmv_hip_decode_frames_dev reads back (reference: the block loop of
    AGMV_DecodeFrameChunk, src/agmv_decode.c:224-407, has no such table either -- it walks).  d_nentered may be NULL.
-   Any number of frames (more than 65532 are cut at GOP boundaries internally). */
+   Any number of frames.  A long batch is cut at GOP boundaries into ranges that run one after the other on `stream`, each
+   one parser -> reconstruction -> repair from the pixels the range before it left: a range is as many whole GOPs as decode
+   to at most 512 frames' worth of 1920x1080 pixels (4.2 GB: 512 frames of 1080p, 1152 of 720p, 13824 of 320x240), and never
+   more than 65532 frames.  That keeps the streams the parser has just read in the memory-side cache for the reconstruction
+   that follows (MI355X: 256 MiB) and the parser's work areas one range long.  A batch no longer than a range runs as one.
+   AGMV_DEC_RANGE_FRAMES=n in the environment (read per call; a test and tuning aid) forces ranges of n frames, rounded up to
+   whole GOPs; 0 cuts at 65532 frames only.  The outputs, agmv_hip_decode_prior_dependent and
+   agmv_hip_parse_fallback_frames answer for the whole call whatever the ranges. */
 int agmv_hip_decode_bitstreams_dev(agmv_hip_ctx* ctx, const uint8_t* d_bits, size_t bits_stride,
                                    const uint32_t* d_bpos, uint32_t n_frames, uint32_t w, uint32_t h,
                                    uint32_t first_frame_count, uint32_t* d_nentered, uint32_t* d_pix_out,
@@ -198,8 +205,9 @@ int agmv_hip_decode_bitstreams_dev(agmv_hip_ctx* ctx, const uint8_t* d_bits, siz
    the prior state.  What a GOP-sharded decode needs to know before it trusts a range decoded from the fresh state.  Never 1 for a
    stream the encoder emits that starts at a GOP boundary, with one exception: at width 4 (one block per row) a FILL as the
    last block of the first frame stores the block's own pixel (3,0) of d_prev_frame (the reference's x-1 wraps, :264-266).
-   A decode_bitstreams call cut into parts (more than 65532 frames) reports its dependence on the caller's state, i.e. that
-   of its first part: later parts continue from the output of the part before them.  Synchronises the stream. */
+   A decode_bitstreams call cut into ranges reports its dependence on the caller's state, i.e. that of its first range:
+   later ranges continue from the output of the range before them (the first range always holds the batch's first
+   I-frame, the last frame that can read d_prev_iframe).  Synchronises the stream. */
 int agmv_hip_decode_prior_dependent(agmv_hip_ctx* ctx, uint32_t w, uint32_t h, void* stream);
 /* host-memory convenience: parse on the GPU, reconstruct, copy back (synchronous) */
 int agmv_hip_decode_frames(agmv_hip_ctx* ctx, const uint8_t* h_bits, size_t bits_stride,
@@ -474,7 +482,8 @@ int agmv_hip_measure_frames_async(agmv_hip_ctx* ctx, const uint32_t* d_test, int
 /* optional timing: when enabled the library records HIP events on the caller's stream around its three kernel
    groups; agmv_hip_last_kernel_ms(which) returns the last launch's duration in ms (0 = k_encode, 1 = the parser
    kernels, 2 = k_decode + k_fixup, 3 = the whole of agmv_hip_parse_decode_frames_dev / agmv_hip_decode_bitstreams_dev), or a negative value if
-   unavailable */
+   unavailable.  An agmv_hip_decode_bitstreams_dev call cut into ranges runs groups 1 and 2 once per range: 1 and 2 are then the
+   sums over the ranges of that call (disjoint intervals inside 3) */
 int   agmv_hip_enable_timing(agmv_hip_ctx* ctx, int on);
 float agmv_hip_last_kernel_ms(agmv_hip_ctx* ctx, int which);
 

@@ -36,13 +36,15 @@ constexpr int DEC_MAX_SLICES = 32;           // agmv_hip_parse_decode_frames_dev
 struct dec_ws {
 	uint32_t* d_dirty;              // decode: bitmap of block positions needing the fix-up
 	size_t dirty_cap;               // in bytes
-	bool dep_split;                 // the last decode call was cut into parts: its prior dependence is part 0's, saved behind the bitmap
+	bool dep_split;                 // the last decode call was cut into ranges: its prior dependence is range 0's, saved behind the bitmap
 	uint32_t* d_parse_ws;           // parser workspace: cum | centry | summ
 	size_t parse_ws_cap;            // in bytes
 	uint32_t* d_fp_ws;              // fast parser workspace: rec | vm | kb | fstate
 	size_t fp_ws_cap;               // in bytes
-	uint32_t* d_fp_fstate;          // frame states of the last parse (inside d_fp_ws) and how many
+	uint32_t* d_fp_fstate;          // frame states of the last parse (inside d_fp_ws, or d_fstate_call) and how many
 	uint32_t fp_frames;
+	uint32_t* d_fstate_call;        // agmv_hip_decode_bitstreams_dev cut into ranges: the frame states of the whole call
+	size_t fstate_call_cap;         // in bytes
 	uint32_t* d_nent_own;           // agmv_hip_decode_bitstreams_dev without a caller's nentered[]
 	size_t nent_cap;                // in bytes
 	hipStream_t aux_stream;         // decode pipeline: the parser's stream (the reconstruction runs on the caller's)
@@ -56,6 +58,7 @@ static void dec_free(void* p)                                 // (device of the 
 {
 	dec_ws* d = (dec_ws*)p;
 	(void)hipFree(d->d_dirty); (void)hipFree(d->d_parse_ws); (void)hipFree(d->d_fp_ws); (void)hipFree(d->d_nent_own);
+	(void)hipFree(d->d_fstate_call);
 	if (d->ev_fork) (void)hipEventDestroy(d->ev_fork);
 	for (int i = 0; i < DEC_MAX_SLICES; i++) if (d->ev_slice[i]) (void)hipEventDestroy(d->ev_slice[i]);
 	if (d->aux_stream) (void)hipStreamDestroy(d->aux_stream);
@@ -1585,8 +1588,9 @@ static int parse_launch_robust(agmv_hip_ctx* c, const DecRows& r, size_t ws_fram
 
 // the parser: speculative walks proven per frame (k_fp_*), the robust kernels for the frames that could not be proven.
 // AGMV_HIP_PARSE=robust runs the robust kernels alone.  bm != NULL: the bitmap form (no offsets[]) for these arguments of
-// k_decode -- their bitmap of positions to repair is cleared; entry bitmaps, first block per region, tile entries come back
-static int parse_launch(agmv_hip_ctx* c, const DecRows& r, size_t ws_frames, hipStream_t s, DecArgs* bm)
+// k_decode -- their bitmap of positions to repair is cleared; entry bitmaps, first block per region, tile entries come back.
+// fstate != NULL: the frame states go there (n_frames words of the caller's) and not into the workspace
+static int parse_launch(agmv_hip_ctx* c, const DecRows& r, size_t ws_frames, hipStream_t s, DecArgs* bm, uint32_t* fstate = nullptr)
 {
 	const bool robust_only = parse_mode() == PARSE_ROBUST;
 	const uint32_t n_frames = r.n_frames;
@@ -1604,6 +1608,7 @@ static int parse_launch(agmv_hip_ctx* c, const DecRows& r, size_t ws_frames, hip
 	A.bits = r.bits; A.stride = r.stride; A.bpos = r.bpos; A.offsets = r.offsets; A.nentered = r.nentered;
 	uint8_t* w = (uint8_t*)d->d_fp_ws;
 	A.rec = (uint4*)w; A.vm = (unsigned long long*)(w + b_rec); A.kb = (uint32_t*)(w + b_rec + b_vm); A.fstate = (uint32_t*)(w + b_rec + b_vm + b_kb);
+	if (fstate) A.fstate = fstate;
 	A.tidx = bm ? (uint32_t*)(w + b_rec + b_vm + b_kb + b_fs) : nullptr; A.tpfd = tpfd;
 	A.nbad = (uint32_t*)(w + b_rec + b_vm + b_kb + b_fs + b_tx);
 	A.n_frames = n_frames; A.nblk = r.nblk; A.maxR = (uint32_t)maxR;
@@ -1791,10 +1796,36 @@ extern "C" int agmv_hip_parse_decode_frames_dev(agmv_hip_ctx* c, const uint8_t* 
 	return 0;
 }
 
+// Frames per range of agmv_hip_decode_bitstreams_dev: as many whole GOPs as decode to at most DEC_RANGE_PIXEL_BYTES of
+// pixels, at least one; 0 = cut only where the parser's grid makes it (65532 frames).  Derived from what the host knows: the
+// stream sizes live on the device.  AGMV_DEC_RANGE_FRAMES=n (read per call, a test and tuning aid) forces n frames, rounded
+// up to whole GOPs; 0 = never cut below 65532.
+// The constant is 512 frames of 1920x1080: on the 1024 x 1080p clip (profiles/decode_ranges/sweep.txt, row "synth ... range
+// 512") parser + k_decode + k_fixup take 1.870 ms against 2.093 ms uncut, 1.932 / 1.990 ms with 256 / 340 frames and 1.932 with
+// 768 -- k_decode is as fast as with 256 (1.49 ms: a range's streams, 223 MB, are still in the 256 MiB memory-side cache behind
+// its parser) and the parser pays for one extra set of launches, not three.  In bytes of pixels, not frames, so that other
+// frame sizes are cut at the same footprint (rows "range -1"): a fixed frame count costs small frames a parser round each.
+constexpr uint32_t DEC_PART_MAX = 65532u;                      // a multiple of 4: the parser's grid has one row per frame
+constexpr size_t DEC_RANGE_PIXEL_BYTES = (size_t)512 * 1920 * 1080 * 4;
+static uint32_t dec_range_frames(uint32_t w, uint32_t h)
+{
+	size_t n = DEC_PART_MAX;
+	if (const char* e = getenv("AGMV_DEC_RANGE_FRAMES")) {
+		const long v = atol(e);
+		if (v > 0) n = ((size_t)v + 3) & ~(size_t)3;
+	} else if (DEC_RANGE_PIXEL_BYTES) {
+		const size_t gops = DEC_RANGE_PIXEL_BYTES / ((size_t)w * h * 16);
+		n = (gops ? gops : 1) * 4;
+	}
+	return n < DEC_PART_MAX ? (uint32_t)n : DEC_PART_MAX;
+}
+
 // Parse + reconstruct without offsets[]: the parser's entry bitmaps go straight to k_decode, which ranks its own blocks in
 // them (k_fp_tiles tells every tile where it starts).  Against agmv_hip_parse_decode_frames_dev this drops k_fp_expand and
-// the 4 bytes per block it writes and k_decode reads back.  Batches of more than 65532 frames are cut at GOP boundaries
-// (the parser's grid has one row per frame); each part continues from the decoder state the part before it left.
+// the 4 bytes per block it writes and k_decode reads back.  A batch longer than dec_range_frames() is cut at GOP
+// boundaries into ranges that run one after the other on the caller's stream -- parser, k_decode, k_fixup -- so that
+// k_decode finds the streams its parser has just read still in the memory-side cache, and the parser's work areas are one
+// range long; each range continues from the decoder state the range before it left.
 extern "C" int agmv_hip_decode_bitstreams_dev(agmv_hip_ctx* c, const uint8_t* d_bits, size_t stride, const uint32_t* d_bpos,
                                               uint32_t n_frames, uint32_t w, uint32_t h, uint32_t first_fc,
                                               uint32_t* d_nentered, uint32_t* d_out,
@@ -1811,31 +1842,46 @@ extern "C" int agmv_hip_decode_bitstreams_dev(agmv_hip_ctx* c, const uint8_t* d_
 	}
 	const DecRows all = {d_bits, stride, d_bpos, nullptr, d_nentered, n_frames, (w / 4) * (h / 4)};
 	const size_t npx = (size_t)w * h;
-	constexpr uint32_t PART = 65532u;                          // a multiple of 4
+	const uint32_t range = dec_range_frames(w, h);
+	const bool cut = n_frames > range;
+	const size_t ws_frames = (size_t)range + 3;                // the longest range: a first one with the frames of a GOP cut short in front
+	uint32_t* fstate = nullptr;                                // cut: the frame states of every range, for agmv_hip_parse_fallback_frames
+	if (cut) {
+		CK(agmv_hip_dev_grow(&d->d_fstate_call, &d->fstate_call_cap, (size_t)n_frames * 4, 1));
+		fstate = d->d_fstate_call;
+	}
 	agmv_hip_ev_mark(c, 6, s);
-	for (uint32_t f0 = 0; f0 < n_frames;) {
+	int k = 0;
+	for (uint32_t f0 = 0; f0 < n_frames; k++) {
 		uint32_t f1 = n_frames;
-		if (f1 - f0 > PART) { f1 = f0 + PART; f1 -= (first_fc + f1) & 3u; }   // the next part starts with an I-frame
+		if (f1 - f0 > range) {
+			f1 = f0 + range; f1 -= (first_fc + f1) & 3u;           // the next range starts with an I-frame
+			// ... and never with the batch's first one (a range of one GOP, a batch that starts inside a GOP): it would take the
+			// caller's I-frame snapshot, and the call's prior dependence is range 0's alone -- that GOP rides with range 0
+			if (f1 < 4) f1 = f1 + 4 < n_frames ? f1 + 4 : n_frames;
+		}
 		const DecRows r = rows_range(all, f0, f1);
 		// state before frame f0: the frame before it, and the snapshot taken at the last I-frame (the decoded I-frame itself, :401-405)
 		const DecPix px = {w, h, first_fc + f0, d_out + (size_t)f0 * npx, f0 == 0 ? d_prev : d_out + (size_t)(f0 - 1) * npx,
 		                   f0 == 0 ? d_prev_iframe : d_out + (size_t)(f0 - 4) * npx};
 		DecArgs A;
 		if (decode_prepare(c, A, r, px, s, false)) return -1;
-		agmv_hip_ev_mark(c, 2, s);
-		if (parse_launch(c, r, r.n_frames, s, &A)) return -1;   // fills in A.vm, A.kb, A.tidx, A.maxR
-		agmv_hip_ev_mark(c, 3, s);
-		agmv_hip_ev_mark(c, 4, s);
+		if (agmv_hip_ev_mark_range(c, 2, k, s)) return -1;
+		// work areas sized for the longest range, not for this one: growing them in mid-call would wait for the device
+		if (parse_launch(c, r, cut ? ws_frames : r.n_frames, s, &A, fstate ? fstate + f0 : nullptr)) return -1;   // fills in A.vm, A.kb, A.tidx, A.maxR
+		if (agmv_hip_ev_mark_range(c, 3, k, s)) return -1;
+		if (agmv_hip_ev_mark_range(c, 4, k, s)) return -1;
 		if (decode_launch(c, A, 0, A.n_groups, s)) return -1;
 		if (fixup_launch(c, A, s)) return -1;
-		agmv_hip_ev_mark(c, 5, s);
-		if (f0 == 0 && f1 < n_frames) {                        // later parts depend on the parts before them, not on the caller:
-			const size_t dw = (A.nblk + 31) / 32 + 1;          // the call's prior dependence is part 0's (the next k_fp_tiles clears it)
+		if (agmv_hip_ev_mark_range(c, 5, k, s)) return -1;
+		if (f0 == 0 && cut) {                                      // later ranges depend on the ranges before them, not on the caller:
+			const size_t dw = (A.nblk + 31) / 32 + 1;          // the call's prior dependence is range 0's (the next k_fp_tiles clears it)
 			CK(hipMemcpyAsync(d->d_dirty + dw + 1, d->d_dirty + dw, 4, hipMemcpyDeviceToDevice, s));
 		}
 		f0 = f1;
 	}
-	d->dep_split = n_frames > PART;
+	d->dep_split = cut;
+	if (cut) { d->d_fp_fstate = fstate; d->fp_frames = n_frames; }
 	agmv_hip_ev_mark(c, 7, s);
 	return 0;
 }

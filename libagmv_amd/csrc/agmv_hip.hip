@@ -943,6 +943,8 @@ extern "C" void agmv_hip_destroy(agmv_hip_ctx* c)
 	(void)hipFree(c->d_nn_pal); (void)hipFree(c->d_nn_pix); (void)hipFree(c->d_nn_ent);
 	if (c->ev_enc) (void)hipEventDestroy(c->ev_enc);
 	for (int i = 0; i < 8; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
+	for (int i = 0; i < 4 * c->ev_rng_cap; i++) (void)hipEventDestroy(c->ev_rng[i]);
+	free(c->ev_rng);
 	for (int k = 0; k < AREA_KINDS; k++) if (c->ws[k]) c->ws_free[k](c->ws[k]);
 	free(c);
 }
@@ -958,7 +960,26 @@ void* agmv_hip_area(agmv_hip_ctx* c, agmv_hip_area_kind kind, size_t bytes, void
 
 void agmv_hip_ev_mark(agmv_hip_ctx* c, int which, hipStream_t s)
 {
-	if (c->timing) (void)hipEventRecord(c->ev[which], s);
+	if (!c->timing) return;
+	if (which == 2 || which == 4) c->ev_rng_n[which / 2 - 1] = 0;   // a start mark: one interval so far
+	(void)hipEventRecord(c->ev[which], s);
+}
+
+int agmv_hip_ev_mark_range(agmv_hip_ctx* c, int which, int range, hipStream_t s)
+{
+	if (!c->timing) return 0;
+	if (range == 0) { agmv_hip_ev_mark(c, which, s); return 0; }
+	if (range > c->ev_rng_cap) {
+		const int cap = range > 2 * c->ev_rng_cap ? range : 2 * c->ev_rng_cap;
+		hipEvent_t* p = (hipEvent_t*)realloc(c->ev_rng, (size_t)cap * 4 * sizeof(hipEvent_t));
+		if (!p) return agmv_hip_err("agmv_hip: out of host memory");
+		c->ev_rng = p;
+		for (; c->ev_rng_cap < cap; c->ev_rng_cap++)
+			for (int i = 0; i < 4; i++) CK(hipEventCreate(&p[4 * c->ev_rng_cap + i]));
+	}
+	CK(hipEventRecord(c->ev_rng[4 * (range - 1) + which - 2], s));
+	if (which == 2 || which == 4) c->ev_rng_n[which / 2 - 1] = range;
+	return 0;
 }
 
 extern "C" int agmv_hip_enable_timing(agmv_hip_ctx* c, int on)
@@ -971,13 +992,21 @@ extern "C" int agmv_hip_enable_timing(agmv_hip_ctx* c, int on)
 }
 
 /* duration in ms of the last launch of kernel group `which` (0 = k_encode, 1 = the parser kernels,
-   2 = k_decode + k_fixup, 3 = the whole of agmv_hip_parse_decode_frames_dev), measured with HIP events on the stream it ran on; synchronises on the stop event */
+   2 = k_decode + k_fixup, 3 = the whole of agmv_hip_parse_decode_frames_dev), measured with HIP events on the stream it ran on; synchronises on the stop event.
+   A decode cut into GOP ranges ran groups 1 and 2 once per range: the sum over the ranges of that call */
 extern "C" float agmv_hip_last_kernel_ms(agmv_hip_ctx* c, int which)
 {
 	float ms = -1.0f;
 	if (!c || !c->timing || which < 0 || which > 3) return -1.0f;
 	if (hipEventSynchronize(c->ev[2 * which + 1]) != hipSuccess) return -1.0f;
 	if (hipEventElapsedTime(&ms, c->ev[2 * which], c->ev[2 * which + 1]) != hipSuccess) return -1.0f;
+	if (which == 1 || which == 2)
+		for (int k = 0; k < c->ev_rng_n[which - 1]; k++) {     // the later ranges, in stream order behind the first
+			hipEvent_t* e = c->ev_rng + 4 * k + 2 * (which - 1);
+			float part = 0.0f;
+			if (hipEventSynchronize(e[1]) != hipSuccess || hipEventElapsedTime(&part, e[0], e[1]) != hipSuccess) return -1.0f;
+			ms += part;
+		}
 	return ms;
 }
 

@@ -31,6 +31,9 @@ struct agmv_hip_ctx {
 	int n_cu;
 	int timing;                     // record HIP events around the three hot kernels
 	hipEvent_t ev[8];               // encode, parse, decode, parse||decode pipeline: start/stop
+	hipEvent_t* ev_rng;             // a decode cut into GOP ranges: marks 2..5 of range k >= 1 at [4 * (k - 1) + mark - 2], grown on demand
+	int ev_rng_cap;                 // ... ranges the pool has events for
+	int ev_rng_n[2];                // ... ranges behind the first that the last parse / the last decode marked
 	hipEvent_t ev_enc;              // end of the last encode launch (encodes of one context share status / control words)
 	hipStream_t enc_stream;         // ... and the stream it went to
 	int have_enc;
@@ -57,6 +60,8 @@ int agmv_hip_enter(agmv_hip_ctx* c, bool palette = false);
 void* agmv_hip_area(agmv_hip_ctx* c, agmv_hip_area_kind kind, size_t bytes, void (*destroy)(void*));
 
 void agmv_hip_ev_mark(agmv_hip_ctx* c, int which, hipStream_t s);   // a timing mark: encode 0/1, the decoder 2..7
+// marks 2..5 of range `range` of a call cut into ranges (range 0: agmv_hip_ev_mark): agmv_hip_last_kernel_ms adds the ranges up
+int agmv_hip_ev_mark_range(agmv_hip_ctx* c, int which, int range, hipStream_t s);
 int agmv_hip_check_geometry(uint32_t w, uint32_t h);
 
 // Grow the device buffer *p of *cap units (of `unit` bytes) to at least `need` units.  The contents are not kept; on failure
