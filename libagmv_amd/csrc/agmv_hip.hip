@@ -1157,6 +1157,11 @@ static int encode_dev(agmv_hip_ctx* c, const uint32_t* d_pix, uint32_t n_frames,
 	CK(hipMemsetAsync(c->d_ctrl, 0, CTRL_BYTES, s));
 	uint32_t grid = (uint32_t)c->enc_grid;
 	if (grid > A.total_tiles) grid = A.total_tiles;
+	if (const char* e = getenv("AGMV_ENC_GRID")) {             // tuning / test aid: at most n workgroups, each running more tiles.  Never more than are resident (the ticket order's forward progress)
+		const long n = atol(e);
+		if (n > 0 && (unsigned long)n < grid) grid = (uint32_t)n;
+	}
+	if (getenv("AGMV_HIP_DEBUG")) fprintf(stderr, "agmv_hip: k_encode: grid of %u workgroup(s) for %u tile(s)\n", grid, A.total_tiles);
 	const size_t lds = (size_t)(c->mode512 ? 512 : 256) * MROW * 4 + ENC_LDS_EXTRA;
 	void (*kern)(EncArgs) = c->mode512 ? (entries ? k_encode<true, true> : k_encode<true, false>)
 	                                   : (entries ? k_encode<false, true> : k_encode<false, false>);
