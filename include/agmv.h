@@ -480,10 +480,42 @@ int AGMV_DecodeFramesFmtDev(const char* filename, void* d_frames, AGMV_PIXFMT fm
    version and palette mode as AGMV_OPT_GBA_I / _II / _III (AGMV_GetVersionFromOPT depends only on the colour count and the
    compression), and of the same PDIFS weight for _I and _III; AGMV_OPT_GBA_II is heavy where AGMV_OPT_II is light, its
    counterpart in weight is AGMV_OPT_ANIM. */
-typedef enum AGMV_SCALE { AGMV_SCALE_NEAREST = 1, AGMV_SCALE_AREA = 2 } AGMV_SCALE;
+typedef enum AGMV_SCALE { AGMV_SCALE_NEAREST = 1, AGMV_SCALE_AREA = 2, AGMV_SCALE_BILINEAR = 3 } AGMV_SCALE;
 int AGMV_EncodeFramesScaledDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height,
                                u32 width, u32 height, AGMV_SCALE filter, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
                                AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule);
+
+/* A file decoded at a target size: the 120x80 .. 320x240 frames of this codec as the 1080p NV12 a video encoder takes, a model's
+   input size, or thumbnails.  The file of sw x sh decodes to the XRGB32 clip S, which is what AGMV_DecodeFramesDev gives; a target
+   size dw x dh (width x height) and `filter` give the XRGB32 clip D defined below, and d_frames receives D in the layout `fmt` by
+   the writing rule the text above states for that layout -- NV12 / I420: luma per pixel of D, chroma from the pixels of D's 2 x 2
+   block that exist.  Frame k lands k * (frame bytes of fmt at dw x dh) bytes into d_frames; frames behind cap_frames are not
+   touched.  All integer: the same bytes from every run.  `div` and `mod` are the integer quotient and remainder of non-negative integers.
+     AGMV_SCALE_NEAREST   the rule above.  Any non-zero target size.
+     AGMV_SCALE_AREA      the rule above, under its conditions: dw <= sw, dh <= sh, sw * sh <= 2^24.
+     AGMV_SCALE_BILINEAR  pixel centres aligned, edges clamped, 8-bit weights, one rounding.  Any non-zero target size in either
+                          direction; a downscale reads four source pixels per target pixel whatever the ratio, so it aliases (use
+                          AGMV_SCALE_AREA for that).  On an axis with source length s and target length d the taps of target
+                          index X are: p = (2X + 1) * s - d, signed; if p < 0 then i0 = 0 and f = 0, otherwise i0 = p div 2d,
+                          r = p mod 2d, f = (256 * r + d) div 2d, which lies in 0 .. 256; i1 = min(i0 + 1, s - 1).  With
+                          (x0, x1, fx) from (sw, dw) and (y0, y1, fy) from (sh, dh), per channel
+                            D(X, Y) = ((256 - fy) * ((256 - fx) * S(x0, y0) + fx * S(x1, y0))
+                                       + fy * ((256 - fx) * S(x0, y1) + fx * S(x1, y1)) + 32768) >> 16
+                          Every term fits 32-bit unsigned arithmetic: 255 * 65536 + 32768 < 2^32.  Hence: a scale to the same size
+                          is the identity; a flat frame stays flat; every output lies between the smallest and the largest of its
+                          four taps; the channels are interpolated in RGB, never in YUV.  AGMV_EncodeFramesScaledDev refuses
+                          this filter (-1).
+   The batches are decoded at the file's size; the decoder's state never leaves that size, and no XRGB32 copy of D exists for
+   NEAREST and BILINEAR (AREA into a layout other than XRGB32 goes through one batch of D).  Returns the number of frames decoded, or
+   a negative value; *info (may be NULL) receives the header's AGMV_INFO, with the file's own size.  The checks, in this order, all
+   before a device is opened:
+     -1        NULL filename; unknown format; unknown filter
+     -4        width or height zero, or more than 2^28 target pixels
+     -Error    the file cannot be opened or its header is bad (as AGMV_DecodeFramesFmtDev)
+      0        d_frames NULL: only *info is filled
+     -4        AGMV_SCALE_AREA with a target larger than the file's frame in either axis, or a file frame above 2^24 pixels */
+int AGMV_DecodeFramesScaledDev(const char* filename, void* d_frames, AGMV_PIXFMT fmt, u32 width, u32 height, AGMV_SCALE filter, u32 cap_frames,
+                               AGMV_INFO* info);
 
 /* Audio tracks from and to GPU memory.  An AGMV_PCMFMT names the layout of PCM in device memory:
      AGMV_PCM_S16   [samples][channels] 16-bit words, bits unchanged (int16 WAV samples as they are); for 16-bit tracks

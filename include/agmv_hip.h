@@ -426,6 +426,21 @@ int agmv_hip_yuv_similarity_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, u
 int agmv_hip_scale_area_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, uint32_t src_w, uint32_t src_h, uint32_t n_frames,
                             uint32_t dst_w, uint32_t dst_h, uint32_t* d_dst, void* stream);
 
+/* -- a decoded clip written at a target size -------------------------------------------------------
+ * AGMV_SCALE_NEAREST (1) and AGMV_SCALE_BILINEAR (3) of include/agmv.h, which holds both definitions, as the decoder's sink:
+ * d_src holds n_frames packed XRGB32 frames of src_w x src_h (bits >= 24 ignored, 4-byte aligned); frame k of the scaled clip lands
+ * k * (frame bytes of `fmt` at dst_w x dst_h) bytes into d_dst, written in `fmt` by that layout's writing rule -- any of the seven
+ * layouts (1 .. 5, or 16 / 17 OR-ed with the YUV flags; NV12 / I420 take luma per target pixel and chroma from the 2 x 2 block of
+ * target pixels that exist).  Any non-zero sizes of at most 2^28 pixels, in either direction.  One launch, asynchronous on
+ * `stream`: no allocation, no host synchronisation, nothing of the context is used but its device, and no XRGB32 copy of the
+ * scaled clip exists.  Where dst_w % 16 == 0 and every target frame (and plane) starts on a 16-byte boundary (YUV: and dst_h is
+ * even) the pixels leave in 16-byte stores; any other target is written pixel by pixel, to the same bytes.  Nothing outside the n_frames target frames is
+ * written.  n_frames == 0 is success and launches nothing.  Returns non-zero with a message and launches nothing for a NULL
+ * pointer, an unknown format or filter, AGMV_SCALE_AREA (2: that filter is agmv_hip_scale_area_dev's), a zero size or a size
+ * above 2^28 pixels. */
+int agmv_hip_scale_frames_async(agmv_hip_ctx* ctx, int filter, const uint32_t* d_src, uint32_t src_w, uint32_t src_h,
+                                uint32_t n_frames, int fmt, uint32_t dst_w, uint32_t dst_h, void* d_dst, void* stream);
+
 /* -- the palette refined by weighted k-means ------------------------------------------------------
  * The refinement of include/agmv.h ("palette refinement"), which holds the definition: Lloyd's algorithm over the points of a
  * histogram, in exact integers.

@@ -1,6 +1,6 @@
 // libagmv_amd/csrc/agmv_clip_hip.hip -- the clip front end: what a caller does to a clip in GPU memory before it reaches
 // the codec of agmv_hip.hip (include/agmv_hip.h from "helpers on the caller side of the path" to agmv_hip_scale_area_dev), and
-// what it asks about one that came back from it (agmv_hip_measure_frames_async).
+// what it asks of one that came back from it (agmv_hip_scale_frames_async, agmv_hip_measure_frames_async).
 //
 //   k_synth / k_interp        the synthetic test clip, the PDIFS midpoint frame
 //   k_histogram*              palette histogram; hist_add_runs is the one statement of the run-length atomics
@@ -8,6 +8,7 @@
 //   k_gather*                 the nearest scale as a table look-up; gather_frames is the body of the XRGB32 and byte-layout forms
 //   k_pix_* / k_yuv_*         the byte layouts and NV12 / I420 to and from XRGB32
 //   k_scale_area              the exact box-filter downscale of a clip in any of the seven layouts
+//   k_scale_up*               a decoded XRGB32 clip written at a target size, nearest or bilinear, in any of the seven layouts
 //   k_measure                 a decoded XRGB32 clip against its reference in any of the seven layouts: SSE, block-mean SSE, SSIM
 // Each family has an XRGB32 form, one for the byte layouts (PF_RGB24 .. PF_RGB8P) and one templated on the YUV layout; on the
 // host CLIP_LAUNCH is the one place where a format value becomes a kernel's template argument.
@@ -574,6 +575,54 @@ template <int FMT> __device__ __forceinline__ void yuv_put_chroma(const uint32_t
 	else { c[ci] = (uint8_t)uv; c[cw * ch + ci] = (uint8_t)(uv >> 8); }
 }
 
+// quarter q (a constant once the caller's loop is unrolled) of a patch of 16 x 2 pixels as it lies in a frame of FMT: a, b = the
+// pixels 4q .. 4q + 3 of its two rows as 0x..RRGGBB.  The quarters of a patch are packed in order, 0 first.
+template <int FMT> __device__ __forceinline__ void yuv_pack_quarter(yuv_raw& r, int q, const pf_u32x4& a, const pf_u32x4& b, const yuv_wr& m)
+{
+	uint32_t ya = 0, yb = 0;
+#pragma unroll
+	for (int i = 0; i < 4; i++) { ya |= yuv_luma(m, a[i]) << (8 * i); yb |= yuv_luma(m, b[i]) << (8 * i); }
+	r.y0[q] = ya; r.y1[q] = yb;
+	uint32_t uv[2];
+#pragma unroll
+	for (int j = 0; j < 2; j++) {
+		const uint32_t p0 = a[2 * j], p1 = a[2 * j + 1], p2 = b[2 * j], p3 = b[2 * j + 1];
+		uv[j] = yuv_uv(m, (int)(((p0 >> 16) & 0xff) + ((p1 >> 16) & 0xff) + ((p2 >> 16) & 0xff) + ((p3 >> 16) & 0xff)),
+		               (int)(((p0 >> 8) & 0xff) + ((p1 >> 8) & 0xff) + ((p2 >> 8) & 0xff) + ((p3 >> 8) & 0xff)),
+		               (int)((p0 & 0xff) + (p1 & 0xff) + (p2 & 0xff) + (p3 & 0xff)), 2);
+	}
+	if (FMT == PF_NV12) r.c[q] = uv[0] | uv[1] << 16;              // samples 2q, 2q + 1 as U,V,U,V
+	else {                                                     // U of samples 2q, 2q + 1 into byte 2q of the 8 U, V likewise
+		const uint32_t u2 = (uv[0] & 0xff) | (uv[1] & 0xff) << 8, v2 = (uv[0] >> 8) | (uv[1] >> 8) << 8;
+		if (q & 1) { r.c[q >> 1] |= u2 << 16; r.c[2 + (q >> 1)] |= v2 << 16; } else { r.c[q >> 1] = u2; r.c[2 + (q >> 1)] = v2; }
+	}
+}
+
+// the whole patch from registers: a[j], b[j] = pixels 4j .. 4j + 3 of its two rows
+template <int FMT> __device__ __forceinline__ yuv_raw yuv_pack_patch(const pf_u32x4 a[4], const pf_u32x4 b[4], const yuv_wr& m)
+{
+	yuv_raw r;
+#pragma unroll
+	for (int q = 0; q < 4; q++) yuv_pack_quarter<FMT>(r, q, a[q], b[q], m);
+	return r;
+}
+
+// ... stored at column x0 (a multiple of 16) of rows 2 * py and 2 * py + 1, w a multiple of 16 and fr 16-byte aligned
+template <int FMT> __device__ __forceinline__ void yuv_store_patch(uint8_t* __restrict__ fr, uint32_t w, uint32_t h, uint32_t x0, uint32_t py, const yuv_raw& r)
+{
+	const size_t npx = (size_t)w * h, k0 = (size_t)2 * py * w + x0;
+	*reinterpret_cast<pf_u32x4*>(fr + k0) = r.y0;
+	*reinterpret_cast<pf_u32x4*>(fr + k0 + w) = r.y1;
+	if (FMT == PF_NV12) *reinterpret_cast<pf_u32x4*>(fr + npx + (size_t)py * w + x0) = r.c;
+	else {
+		const size_t cw = w >> 1, ch = (h + 1) >> 1;
+		pf_u32x2 u, v;
+		u[0] = r.c[0]; u[1] = r.c[1]; v[0] = r.c[2]; v[1] = r.c[3];
+		*reinterpret_cast<pf_u32x2*>(fr + npx + (size_t)py * cw + (x0 >> 1)) = u;
+		*reinterpret_cast<pf_u32x2*>(fr + npx + cw * ch + (size_t)py * cw + (x0 >> 1)) = v;
+	}
+}
+
 // d_dst frame f = src[f][0 .. w * h) written as YUV (whole frames); nothing outside those frames is written
 template <int FMT> __global__ __launch_bounds__(256) void k_yuv_from_xrgb(const uint32_t* __restrict__ src, uint32_t w, uint32_t h, size_t frame_bytes, uint32_t bpf,
                                                                           int wide, yuv_wr m, uint8_t* __restrict__ dst)
@@ -586,39 +635,14 @@ template <int FMT> __global__ __launch_bounds__(256) void k_yuv_from_xrgb(const 
 		if (2 * py >= h) return;
 		const uint32_t k0 = 2 * py * w + x0;
 		if (2 * py + 1 < h) {
-			pf_u32x4 y0, y1, c;
+			yuv_raw r;
 #pragma unroll
 			for (int q = 0; q < 4; q++) {
 				const pf_u32x4 a = __builtin_nontemporal_load(reinterpret_cast<const pf_u32x4*>(in + k0 + 4 * q));
 				const pf_u32x4 b = __builtin_nontemporal_load(reinterpret_cast<const pf_u32x4*>(in + k0 + w + 4 * q));
-				uint32_t ya = 0, yb = 0;
-#pragma unroll
-				for (int i = 0; i < 4; i++) { ya |= yuv_luma(m, a[i]) << (8 * i); yb |= yuv_luma(m, b[i]) << (8 * i); }
-				y0[q] = ya; y1[q] = yb;
-				uint32_t uv[2];
-#pragma unroll
-				for (int j = 0; j < 2; j++) {
-					const uint32_t p0 = a[2 * j], p1 = a[2 * j + 1], p2 = b[2 * j], p3 = b[2 * j + 1];
-					uv[j] = yuv_uv(m, (int)(((p0 >> 16) & 0xff) + ((p1 >> 16) & 0xff) + ((p2 >> 16) & 0xff) + ((p3 >> 16) & 0xff)),
-					               (int)(((p0 >> 8) & 0xff) + ((p1 >> 8) & 0xff) + ((p2 >> 8) & 0xff) + ((p3 >> 8) & 0xff)),
-					               (int)((p0 & 0xff) + (p1 & 0xff) + (p2 & 0xff) + (p3 & 0xff)), 2);
-				}
-				if (FMT == PF_NV12) c[q] = uv[0] | uv[1] << 16;        // samples 2q, 2q + 1 as U,V,U,V
-				else {                                             // U of samples 2q, 2q + 1 into byte 2q of the 8 U, V likewise
-					const uint32_t u2 = (uv[0] & 0xff) | (uv[1] & 0xff) << 8, v2 = (uv[0] >> 8) | (uv[1] >> 8) << 8;
-					if (q & 1) { c[q >> 1] |= u2 << 16; c[2 + (q >> 1)] |= v2 << 16; } else { c[q >> 1] = u2; c[2 + (q >> 1)] = v2; }
-				}
+				yuv_pack_quarter<FMT>(r, q, a, b, m);
 			}
-			*reinterpret_cast<pf_u32x4*>(fr + k0) = y0;
-			*reinterpret_cast<pf_u32x4*>(fr + k0 + w) = y1;
-			if (FMT == PF_NV12) *reinterpret_cast<pf_u32x4*>(fr + (size_t)npx + (size_t)py * w + x0) = c;
-			else {
-				const size_t cw = w >> 1, ch = (h + 1) >> 1;
-				pf_u32x2 u, v;
-				u[0] = c[0]; u[1] = c[1]; v[0] = c[2]; v[1] = c[3];
-				*reinterpret_cast<pf_u32x2*>(fr + (size_t)npx + (size_t)py * cw + (x0 >> 1)) = u;
-				*reinterpret_cast<pf_u32x2*>(fr + (size_t)npx + cw * ch + (size_t)py * cw + (x0 >> 1)) = v;
-			}
+			yuv_store_patch<FMT>(fr, w, h, x0, py, r);
 		} else {                                                   // the odd last row: means over two pixels
 			for (uint32_t i = 0; i < 16; i++) fr[k0 + i] = (uint8_t)yuv_luma(m, in[k0 + i]);
 			for (uint32_t j = 0; j < 8; j++) yuv_put_chroma<FMT>(in, fr, w, h, (x0 >> 1) + j, py, m);
@@ -919,6 +943,215 @@ template <int FMT> __global__ __launch_bounds__(256) void k_scale_area(ScaleArgs
 			out[k] = r << 16 | g << 8 | b;
 		}
 		__syncthreads();
+	}
+}
+
+// ---- a decoded XRGB32 clip written at a target size in any of the seven layouts (AGMV_SCALE_NEAREST / _BILINEAR of include/agmv.h) ----
+// 1080p XRGB32 is 8.3 MB out per frame from 0.3 MB in, and the source batch stays in L2, so the taps are plain gathers.  A lane
+// forms 16 consecutive target pixels of a row (YUV: 16 x 2, the patch of k_yuv_from_xrgb) in registers; where the target's rows of
+// 16 lie on 16-byte boundaries they leave through pf_pack16 / yuv_pack_patch with 16-byte stores (k_scale_up_wide), so no XRGB32
+// copy of the scaled clip exists.  Every other target -- a width that is no multiple of 16, a clip at an odd offset, a YUV frame
+// with an odd last row -- goes pixel by pixel through the layout's byte writer (k_scale_up), to the same bytes.
+// The taps of an axis: with p = (2X + 1) * s - d the floor quotient i = p div 2d (-1 where p < 0) and r = p mod 2d give the
+// bilinear taps (i0 = max(i, 0), f = (256 r + d) div 2d, 0 where p < 0) and the nearest index i + (r >= d), since
+// (2X + 1) * s = p + d.  A lane divides once per axis (in 32 bits where `small` says that every term fits) and then steps:
+// p grows by 2s = 2d * (s div d) + 2 * (s mod d) per pixel, 256 r + d by 512 * (s mod d), both kept as quotient and remainder.
+struct up_axis { uint32_t s, d, d2, q, m2, fq, fr; };              // d2 = 2d, q = s div d, m2 = 2 (s mod d), (fq, fr) = 512 (s mod d) divmod 2d
+struct up_tap { int32_t i; uint32_t r, f, e; };                    // p = 2d i + r, 256 r + d = 2d f + e
+struct up_idx { uint32_t i0, i1, f; };
+
+struct UpArgs {
+	const uint32_t* src;
+	uint8_t* dst;
+	size_t frame_bytes;                                            // of a target frame
+	uint32_t bpf, gpr, rows;                                       // blocks per frame, groups of 16 per row, rows (YUV: row pairs; wide: bands) per frame
+	int small;
+	up_axis x, y;
+	yuv_wr m;
+};
+
+template <bool BIL> __device__ __forceinline__ up_tap up_tap_at(const up_axis& a, uint32_t X, int small)
+{
+	up_tap t;
+	if (small) {                                                   // p + 2d = (2X + 1) s + d > 0
+		const uint32_t p2 = (2 * X + 1) * a.s + a.d, q = p2 / a.d2;
+		t.i = (int32_t)q - 1; t.r = p2 - q * a.d2;
+		if (BIL) { const uint32_t v = 256 * t.r + a.d; t.f = v / a.d2; t.e = v - t.f * a.d2; }
+	} else {
+		const unsigned long long p2 = (2ull * X + 1) * a.s + a.d, q = p2 / a.d2;
+		t.i = (int32_t)q - 1; t.r = (uint32_t)(p2 - q * a.d2);
+		if (BIL) { const unsigned long long v = 256ull * t.r + a.d; t.f = (uint32_t)(v / a.d2); t.e = (uint32_t)(v - (unsigned long long)t.f * a.d2); }
+	}
+	if (!BIL) { t.f = 0; t.e = 0; }
+	return t;
+}
+
+template <bool BIL> __device__ __forceinline__ void up_tap_step(const up_axis& a, up_tap& t)
+{
+	t.i += (int32_t)a.q; t.r += a.m2;
+	const bool wrap = t.r >= a.d2;
+	if (wrap) { t.r -= a.d2; t.i++; }
+	if (BIL) {
+		t.f += a.fq; t.e += a.fr;
+		if (t.e >= a.d2) { t.e -= a.d2; t.f++; }
+		if (wrap) t.f -= 256;
+	}
+}
+
+template <bool BIL> __device__ __forceinline__ up_idx up_resolve(const up_axis& a, const up_tap& t)
+{
+	up_idx x;
+	if (BIL) {
+		x.i0 = t.i < 0 ? 0u : (uint32_t)t.i; x.f = t.i < 0 ? 0u : t.f;
+		x.i1 = min(x.i0 + 1, a.s - 1);
+	} else {
+		x.i0 = x.i1 = (uint32_t)(t.i + (t.r >= a.d ? 1 : 0)); x.f = 0;
+	}
+	return x;
+}
+
+// target pixel at column taps x of the row whose taps are source rows r0, r1 and fy
+template <bool BIL> __device__ __forceinline__ uint32_t up_sample(const uint32_t* __restrict__ r0, const uint32_t* __restrict__ r1, const up_idx& x, uint32_t fy)
+{
+	if (!BIL) return r0[x.i0] & 0xffffffu;
+	const uint32_t a = r0[x.i0], b = r0[x.i1], c = r1[x.i0], d = r1[x.i1], gx = 256 - x.f, gy = 256 - fy;
+	uint32_t o = 0;
+#pragma unroll
+	for (int sh = 16; sh >= 0; sh -= 8) {
+		const uint32_t top = gx * ((a >> sh) & 0xff) + x.f * ((b >> sh) & 0xff), bot = gx * ((c >> sh) & 0xff) + x.f * ((d >> sh) & 0xff);
+		o |= ((gy * top + fy * bot + 32768u) >> 16) << sh;
+	}
+	return o;
+}
+
+// The wide kernel: a lane owns 16 columns of a band of UP_BAND target rows.  An upscale reads the same two source rows for several
+// target rows (4.5 on average from 240 to 1080), so the lane keeps the horizontal pass of its 16 columns -- per column
+// (256 - fx) * S(x0, y) + fx * S(x1, y) for both rows, exact in 16 bits per channel, R and B sharing a word -- in registers and forms
+// them again only when the row's (y0, y1) change; a target row then costs the vertical pass and the stores.  NEAREST keeps the 16
+// source pixels of the row.  A YUV lane keeps the 16 pixels of a pair's even row until the odd row is there (dh is even here).
+#define UP_BAND 8
+
+template <int FMT, bool BIL> __global__ __launch_bounds__(256) void k_scale_up_wide(UpArgs A)
+{
+	constexpr bool YUV = FMT >= PF_NV12;
+	const uint32_t f = blockIdx.x / A.bpf, g = (blockIdx.x - f * A.bpf) * 256 + threadIdx.x, band = g / A.gpr;
+	if (band >= A.rows) return;
+	const uint32_t dw = A.x.d, dh = A.y.d, sw = A.x.s, X0 = (g - band * A.gpr) * 16, Y0 = band * UP_BAND, Y1 = min(Y0 + UP_BAND, dh);
+	const uint32_t* sf = A.src + (size_t)f * sw * A.y.s;
+	uint8_t* fr = A.dst + (size_t)f * A.frame_bytes;
+	const up_tap tx0 = up_tap_at<BIL>(A.x, X0, A.small);
+	up_tap ty = up_tap_at<BIL>(A.y, Y0, A.small);
+	uint32_t cy0 = 0xFFFFFFFFu, cy1 = 0xFFFFFFFFu;                 // the source rows the registers below were made from
+	uint32_t h_rb0[16], h_rb1[16], h_g[16];                        // R << 16 | B of row y0, of row y1; G of y0 | G of y1 << 16 (NEAREST: h_rb0 = the pixels)
+	// the 16 pixels of the target row ty stands at; ty moves on to the next row
+	auto row = [&](pf_u32x4 out[4]) __attribute__((always_inline)) {
+		const up_idx y = up_resolve<BIL>(A.y, ty);
+		if (y.i0 != cy0 || y.i1 != cy1) {
+			const uint32_t *r0 = sf + (size_t)y.i0 * sw, *r1 = sf + (size_t)y.i1 * sw;
+			up_tap tx = tx0;
+			// (opaque, so that the 16 columns' taps are stepped again at every refill, which is rare: hoisted out of the row loop
+			// they take 100 registers more and halve the occupancy)
+			asm volatile("" : "+v"(tx.i), "+v"(tx.r), "+v"(tx.f), "+v"(tx.e));
+#pragma unroll
+			for (int i = 0; i < 16; i++) {
+				const up_idx x = up_resolve<BIL>(A.x, tx);
+				if (BIL) {
+					const uint32_t a = r0[x.i0], b = r0[x.i1], c = r1[x.i0], d = r1[x.i1], gx = 256 - x.f;
+					h_rb0[i] = gx * (a & 0xff00ffu) + x.f * (b & 0xff00ffu);
+					h_rb1[i] = gx * (c & 0xff00ffu) + x.f * (d & 0xff00ffu);
+					h_g[i] = (gx * ((a >> 8) & 0xff) + x.f * ((b >> 8) & 0xff)) | (gx * ((c >> 8) & 0xff) + x.f * ((d >> 8) & 0xff)) << 16;
+				} else {
+					h_rb0[i] = r0[x.i0] & 0xffffffu;
+				}
+				up_tap_step<BIL>(A.x, tx);
+			}
+			cy0 = y.i0; cy1 = y.i1;
+		}
+		const uint32_t fy = y.f, gy = 256 - fy;
+#pragma unroll
+		for (int i = 0; i < 16; i++) {
+			if (BIL) {
+				const uint32_t r = (gy * (h_rb0[i] >> 16) + fy * (h_rb1[i] >> 16) + 32768u) >> 16;
+				const uint32_t gg = (gy * (h_g[i] & 0xffffu) + fy * (h_g[i] >> 16) + 32768u) >> 16;
+				const uint32_t b = (gy * (h_rb0[i] & 0xffffu) + fy * (h_rb1[i] & 0xffffu) + 32768u) >> 16;
+				out[i >> 2][i & 3] = r << 16 | gg << 8 | b;
+			} else {
+				out[i >> 2][i & 3] = h_rb0[i];
+			}
+		}
+		up_tap_step<BIL>(A.y, ty);
+	};
+	pf_u32x4 pa[4];                                                // YUV: the even row of the pair, kept until the odd row is there
+	for (uint32_t Y = Y0; Y < Y1; Y++) {
+		pf_u32x4 px[4];
+		row(px);
+		if constexpr (YUV) {                                       // (one copy of `row` in the loop, not two: its refill is what costs registers)
+			if (!(Y & 1)) {
+#pragma unroll
+				for (int j = 0; j < 4; j++) pa[j] = px[j];
+			} else {
+				yuv_store_patch<FMT>(fr, dw, dh, X0, Y >> 1, yuv_pack_patch<FMT>(pa, px, A.m));
+			}
+		} else if constexpr (FMT == PF_XRGB32) {
+#pragma unroll
+			for (int j = 0; j < 4; j++) *reinterpret_cast<pf_u32x4*>(fr + 4 * ((size_t)Y * dw + X0) + 16 * j) = px[j];
+		} else {
+			const size_t npx = (size_t)dw * dh, p = (size_t)Y * dw + X0;
+			const pf_raw<FMT> r = pf_pack16<FMT>(px);
+#pragma unroll
+			for (int j = 0; j < (FMT == PF_RGBA32 ? 4 : 3); j++)
+				*reinterpret_cast<pf_u32x4*>(FMT == PF_RGB8P ? fr + (size_t)j * npx + p : fr + (FMT == PF_RGBA32 ? 4 : 3) * p + 16 * j) = r.v[j];
+		}
+	}
+}
+
+// Every other target, pixel by pixel: a lane owns 16 consecutive target pixels of one row (YUV: of a row pair, column pair by
+// column pair, each with the chroma sample of the up to 2 x 2 pixels that exist).
+template <int FMT, bool BIL> __global__ __launch_bounds__(256) void k_scale_up(UpArgs A)
+{
+	constexpr bool YUV = FMT >= PF_NV12;
+	const uint32_t f = blockIdx.x / A.bpf, g = (blockIdx.x - f * A.bpf) * 256 + threadIdx.x, ry = g / A.gpr;
+	if (ry >= A.rows) return;
+	const uint32_t dw = A.x.d, dh = A.y.d, sw = A.x.s, X0 = (g - ry * A.gpr) * 16, Y0 = YUV ? 2 * ry : ry;
+	const uint32_t* sf = A.src + (size_t)f * sw * A.y.s;
+	uint8_t* fr = A.dst + (size_t)f * A.frame_bytes;
+	up_tap ty = up_tap_at<BIL>(A.y, Y0, A.small);
+	const up_idx ya = up_resolve<BIL>(A.y, ty);
+	const bool row1 = YUV && Y0 + 1 < dh;
+	if (row1) up_tap_step<BIL>(A.y, ty);
+	const up_idx yb = up_resolve<BIL>(A.y, ty);                   // (the row's own taps again where there is no second row)
+	const uint32_t *a0 = sf + (size_t)ya.i0 * sw, *a1 = sf + (size_t)ya.i1 * sw, *b0 = sf + (size_t)yb.i0 * sw, *b1 = sf + (size_t)yb.i1 * sw;
+	up_tap tx = up_tap_at<BIL>(A.x, X0, A.small);
+	const size_t npx = (size_t)dw * dh;
+	if constexpr (YUV) {
+		const size_t cw = (dw + 1) >> 1, ch = (dh + 1) >> 1;
+		for (uint32_t X = X0; X < X0 + 16 && X < dw; X += 2) {
+			const bool two = X + 1 < dw;
+			up_idx xi = up_resolve<BIL>(A.x, tx);
+			const uint32_t p00 = up_sample<BIL>(a0, a1, xi, ya.f), p10 = row1 ? up_sample<BIL>(b0, b1, xi, yb.f) : 0u;
+			up_tap_step<BIL>(A.x, tx);
+			xi = up_resolve<BIL>(A.x, tx);
+			const uint32_t p01 = two ? up_sample<BIL>(a0, a1, xi, ya.f) : 0u, p11 = two && row1 ? up_sample<BIL>(b0, b1, xi, yb.f) : 0u;
+			up_tap_step<BIL>(A.x, tx);
+			uint8_t* l = fr + (size_t)Y0 * dw + X;
+			l[0] = (uint8_t)yuv_luma(A.m, p00);
+			if (two) l[1] = (uint8_t)yuv_luma(A.m, p01);
+			if (row1) { l[dw] = (uint8_t)yuv_luma(A.m, p10); if (two) l[dw + 1] = (uint8_t)yuv_luma(A.m, p11); }
+			const uint32_t uv = yuv_uv(A.m, (int)(((p00 >> 16) & 0xff) + ((p01 >> 16) & 0xff) + ((p10 >> 16) & 0xff) + ((p11 >> 16) & 0xff)),
+			                           (int)(((p00 >> 8) & 0xff) + ((p01 >> 8) & 0xff) + ((p10 >> 8) & 0xff) + ((p11 >> 8) & 0xff)),
+			                           (int)((p00 & 0xff) + (p01 & 0xff) + (p10 & 0xff) + (p11 & 0xff)), (int)two + (int)row1);
+			const size_t ci = (size_t)ry * cw + (X >> 1);
+			uint8_t* c = fr + npx;
+			if (FMT == PF_NV12) { c[2 * ci] = (uint8_t)uv; c[2 * ci + 1] = (uint8_t)(uv >> 8); }
+			else { c[ci] = (uint8_t)uv; c[cw * ch + ci] = (uint8_t)(uv >> 8); }
+		}
+	} else {
+		for (uint32_t X = X0; X < X0 + 16 && X < dw; X++) {
+			const uint32_t c = up_sample<BIL>(a0, a1, up_resolve<BIL>(A.x, tx), ya.f);
+			up_tap_step<BIL>(A.x, tx);
+			if constexpr (FMT == PF_XRGB32) reinterpret_cast<uint32_t*>(fr)[(size_t)Y0 * dw + X] = c;
+			else pf_write(FMT, fr, npx, (size_t)Y0 * dw + X, c);
+		}
 	}
 }
 
@@ -1410,6 +1643,51 @@ extern "C" int agmv_hip_scale_area_dev(agmv_hip_ctx* c, int fmt, const void* d_s
 	A.small = (unsigned long long)src_w * dst_w < (1ull << 32);
 	A.m = YUV_RD[(fmt >> 8) & 3];
 	CLIP_LAUNCH(PF_BYTES | PF_YUV | PF_BIT(PF_XRGB32), k_scale_area, (unsigned)(A.items < 65536 ? A.items : 65536), A);
+	CK(hipGetLastError());
+	return 0;
+}
+
+// ---- a decoded XRGB32 clip at a target size in any layout (AGMV_SCALE_NEAREST / AGMV_SCALE_BILINEAR) ----
+static up_axis up_axis_of(uint32_t s, uint32_t d)
+{
+	up_axis a;
+	const unsigned long long k = 512ull * (s % d);
+	a.s = s; a.d = d; a.d2 = 2 * d; a.q = s / d; a.m2 = 2 * (s % d); a.fq = (uint32_t)(k / a.d2); a.fr = (uint32_t)(k % a.d2);
+	return a;
+}
+
+// (2X + 1) * s + d for every X < d, and 256 * r + d for every r < 2d, fit 32 bits
+static int up_small(uint32_t s, uint32_t d) { return (2ull * d - 1) * s + d < (1ull << 32) && 513ull * d < (1ull << 32); }
+
+extern "C" int agmv_hip_scale_frames_async(agmv_hip_ctx* c, int filter, const uint32_t* d_src, uint32_t src_w, uint32_t src_h, uint32_t n_frames, int fmt,
+                                           uint32_t dst_w, uint32_t dst_h, void* d_dst, void* stream)
+{
+	if (agmv_hip_enter(c)) return -1;
+	const int yuv = yuv_base(fmt);
+	if (!yuv && bad_pixfmt(fmt)) return -1;
+	if (filter == 2) return agmv_hip_err("agmv_hip: the area filter is agmv_hip_scale_area_dev's, not agmv_hip_scale_frames_async's");
+	if (filter != 1 && filter != 3) return agmv_hip_err("agmv_hip: unknown scale filter %d", filter);
+	if (src_w == 0 || src_h == 0 || dst_w == 0 || dst_h == 0 || (unsigned long long)src_w * src_h > (1ull << 28) || (unsigned long long)dst_w * dst_h > (1ull << 28))
+		return agmv_hip_err("agmv_hip: scaling frames of %u x %u to %u x %u (non-zero sizes of at most 2^28 pixels are needed)", src_w, src_h, dst_w, dst_h);
+	if (!d_src || !d_dst) return agmv_hip_err("agmv_hip: NULL clip");
+	if ((uintptr_t)d_src & 3 || (fmt == PF_XRGB32 && ((uintptr_t)d_dst & 3))) return agmv_hip_err("agmv_hip: an XRGB32 clip needs 4-byte alignment");
+	if (n_frames == 0) return 0;
+	UpArgs A;
+	A.src = d_src; A.dst = (uint8_t*)d_dst;
+	A.frame_bytes = clip_frame_bytes(fmt, dst_w, dst_h);
+	const int wide = yuv ? (dst_h & 1) == 0 && yuv_wide(fmt, d_dst, dst_w, dst_h, n_frames)
+	                     : (dst_w & 15) == 0 && pf_aligned(fmt, d_dst, (size_t)dst_w * dst_h, n_frames);
+	A.gpr = (dst_w + 15) >> 4; A.rows = wide ? (dst_h + UP_BAND - 1) / UP_BAND : yuv ? (dst_h + 1) >> 1 : dst_h;
+	A.small = up_small(src_w, dst_w) && up_small(src_h, dst_h);
+	A.x = up_axis_of(src_w, dst_w); A.y = up_axis_of(src_h, dst_h);
+	A.m = YUV_WR[(fmt >> 8) & 3];
+	unsigned blocks;
+	if (clip_grid(((size_t)A.gpr * A.rows + 255) / 256, n_frames, &A.bpf, &blocks)) return -1;
+	clip_dispatch<PF_BYTES | PF_YUV | PF_BIT(PF_XRGB32)>(fmt, [&](auto F) {
+		constexpr int L = decltype(F)::value;
+		auto k = wide ? (filter == 3 ? k_scale_up_wide<L, true> : k_scale_up_wide<L, false>) : (filter == 3 ? k_scale_up<L, true> : k_scale_up<L, false>);
+		hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, A);
+	});
 	CK(hipGetLastError());
 	return 0;
 }

@@ -896,10 +896,11 @@ static void download_quality(agmv_hip_ctx* c, const void* d_q, AGMV_FRAME_QUALIT
 /* d_dst NULL: AGMV_DecodeAGMV / AGMV_DecodeVideo, every frame to its BMP.  Else AGMV_DecodeFramesFmtDev: up to cap_frames frames
    in the layout `fmt` into d_dst, their number into *decoded; or, with `quality` (host memory), AGMV_MeasureFileDev: d_dst is the
    reference clip of exactly cap_frames frames, only read, and the entries of the *decoded frames measured land in quality[] -- made
-   on the device, downloaded once.  *info (may be NULL) = the header's; with info_only nothing else happens.  Returns an Error, or
-   -3 where the reference cannot correspond to the file (before a device is opened). */
-static int decode_file(const char* filename, u8 img_type, void* d_dst, int fmt, AGMV_FRAME_QUALITY* quality, u32 cap_frames, int info_only,
-                       AGMV_INFO* info, unsigned long* decoded)
+   on the device, downloaded once.  With `scale` (AGMV_DecodeFramesScaledDev) the frames of d_dst have its size.  *info (may be NULL)
+   = the header's; with info_only nothing else happens.  Returns an Error, or -3 where the reference cannot correspond to the file,
+   or -4 where the box filter cannot scale the file's frames to the target (both before a device is opened). */
+static int decode_file(const char* filename, u8 img_type, void* d_dst, int fmt, const agmv_scale* scale, AGMV_FRAME_QUALITY* quality, u32 cap_frames,
+                       int info_only, AGMV_INFO* info, unsigned long* decoded)
 {
 	void* d_quality = NULL;
 	FILE* f = fopen(filename, "rb");
@@ -923,6 +924,11 @@ static int decode_file(const char* filename, u8 img_type, void* d_dst, int fmt, 
 	if (quality && (hdr_obj.header.num_of_frames != cap_frames || (AGMV_FMT_IS_YUV(fmt) && ((hdr_obj.header.width | hdr_obj.header.height) & 1)))) {
 		fclose(f);
 		return -3;
+	}
+	if (scale && scale->filter == AGMV_SCALE_AREA && (scale->w > hdr_obj.header.width || scale->h > hdr_obj.header.height ||
+	                                                   (unsigned long long)hdr_obj.header.width * hdr_obj.header.height > (1ull << 24))) {
+		fclose(f);
+		return -4;
 	}
 	pos = (size_t)ftell(f);
 	fseek(f, 0, SEEK_END); flen = ftell(f); fseek(f, 0, SEEK_SET);
@@ -952,14 +958,14 @@ static int decode_file(const char* filename, u8 img_type, void* d_dst, int fmt, 
 		if (!d_quality) { free(file); return gpu_failed("result array for the measurement"); }
 	}
 	err = agmv_decode_stream(c, file, got, pos, w, h, nframes, hdr_obj.header.version, hdr_obj.header.total_audio_duration != 0, cap,
-	                         lz_threads(), d_dst, fmt, d_quality, d_dst ? decoded : &g_export_count);
+	                         lz_threads(), d_dst, fmt, scale, d_quality, d_dst ? decoded : &g_export_count);
 	if (d_quality && err == NO_ERR) download_quality(c, d_quality, quality, (size_t)*decoded);
 	agmv_hip_free_on(c, d_quality);
 	free(file);
 	return err;
 }
 
-int AGMV_DecodeVideo(const char* filename, u8 img_type) { return decode_file(filename, img_type, NULL, AGMV_PIXFMT_XRGB32, NULL, 0, 0, NULL, NULL); }
+int AGMV_DecodeVideo(const char* filename, u8 img_type) { return decode_file(filename, img_type, NULL, AGMV_PIXFMT_XRGB32, NULL, NULL, 0, 0, NULL, NULL); }
 
 /* AGMV_DecodeAGMV with another destination: frame k of the file (0-based) as the k-th frame of the layout `fmt` in d_frames
    (device memory of this library's context) instead of in quick_export_<k + 1>.bmp.  At most cap_frames frames; returns the
@@ -969,8 +975,23 @@ int AGMV_DecodeFramesFmtDev(const char* filename, void* d_frames, AGMV_PIXFMT fm
 	unsigned long decoded = 0;
 	int err;
 	if (!known_pixfmt((int)fmt)) return -1;
-	err = filename ? decode_file(filename, AGMV_IMG_BMP, d_frames, (int)fmt, NULL, cap_frames, d_frames == NULL, info, &decoded) : FILE_NOT_FOUND_ERR;
+	err = filename ? decode_file(filename, AGMV_IMG_BMP, d_frames, (int)fmt, NULL, NULL, cap_frames, d_frames == NULL, info, &decoded) : FILE_NOT_FOUND_ERR;
 	return err == NO_ERR ? (int)decoded : -err;
+}
+
+/* AGMV_DecodeFramesFmtDev with a target size (include/agmv.h has the rules): the batches are decoded at the file's size and the
+   sink scales each into its place in d_frames, in the layout `fmt`.  The checks that need no device come first, in the header's order. */
+int AGMV_DecodeFramesScaledDev(const char* filename, void* d_frames, AGMV_PIXFMT fmt, u32 width, u32 height, AGMV_SCALE filter, u32 cap_frames,
+                               AGMV_INFO* info)
+{
+	unsigned long decoded = 0;
+	agmv_scale sc;
+	int err;
+	if (!filename || !known_pixfmt((int)fmt) || (filter != AGMV_SCALE_NEAREST && filter != AGMV_SCALE_AREA && filter != AGMV_SCALE_BILINEAR)) return -1;
+	if (width == 0 || height == 0 || width > (1ul << 28) || height > (1ul << 28) || (unsigned long long)width * height > (1ull << 28)) return -4;
+	sc.w = (uint32_t)width; sc.h = (uint32_t)height; sc.filter = (int)filter;
+	err = decode_file(filename, AGMV_IMG_BMP, d_frames, (int)fmt, &sc, NULL, cap_frames, d_frames == NULL, info, &decoded);
+	return err == NO_ERR ? (int)decoded : err < 0 ? err : -err;
 }
 
 int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frames, AGMV_INFO* info)
@@ -983,7 +1004,7 @@ int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frame
 int AGMV_DecodeAGMV(const char* filename, u8 img_type, AGMV_AUDIO_TYPE audio_type)
 {
 	(void)audio_type;
-	return decode_file(filename, img_type, NULL, AGMV_PIXFMT_XRGB32, NULL, 0, 0, NULL, NULL);
+	return decode_file(filename, img_type, NULL, AGMV_PIXFMT_XRGB32, NULL, NULL, 0, 0, NULL, NULL);
 }
 
 /* The file's audio track into device memory in the layout `fmt` (include/agmv.h): the AGAC payloads gathered on the host into
@@ -1067,7 +1088,7 @@ int AGMV_MeasureFileDev(const char* filename, const void* d_ref, AGMV_PIXFMT ref
 	unsigned long measured = 0;
 	int err;
 	if (!known_pixfmt((int)ref_fmt) || (quality && !d_ref)) return -1;
-	err = filename ? decode_file(filename, AGMV_IMG_BMP, (void*)d_ref, (int)ref_fmt, quality, num_of_frames, quality == NULL, info, &measured) : FILE_NOT_FOUND_ERR;
+	err = filename ? decode_file(filename, AGMV_IMG_BMP, (void*)d_ref, (int)ref_fmt, NULL, quality, num_of_frames, quality == NULL, info, &measured) : FILE_NOT_FOUND_ERR;
 	return err == NO_ERR ? (int)measured : err < 0 ? err : -err;
 }
 

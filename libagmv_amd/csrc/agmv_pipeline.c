@@ -813,6 +813,8 @@ typedef struct dpipe {
 	void* d_dst;                           /* the sink: NULL = BMP export through d_out / h_out, else the caller's device frames */
 	int fmt;                               /* ... in this AGMV_PIXFMT: XRGB32 is decoded in place, any other through d_out */
 	void* d_quality;                       /* the measuring sink: d_dst is the reference clip, only read; frame k's AGMV_FRAME_QUALITY lands here */
+	agmv_scale scale;                      /* filter != 0: the sink holds frames of scale.w x scale.h; the batch always goes through d_out */
+	uint32_t* d_scaled;                    /* AGMV_SCALE_AREA into another layout than XRGB32: one batch of scaled XRGB32 frames */
 } dpipe;
 
 typedef struct savearg { dpipe* d; dbatch* b; unsigned k; } savearg;
@@ -848,8 +850,9 @@ static void* dworker_main(void* p)
 		if (id >= d->nfilled) { pthread_mutex_unlock(&d->mu); break; }
 		pthread_mutex_unlock(&d->mu);
 		/* with a packed sink the batch is decoded straight into its place, and the frame before it is the one before it there;
-		   a sink in another layout, and the measuring sink, take the batch from the double buffer, where the decoder's state stays */
-		const int direct = d->d_dst && !d->d_quality && d->fmt == AGMV_PIXFMT_XRGB32;
+		   a sink in another layout or at another size, and the measuring sink, take the batch from the double buffer, where the
+		   decoder's state stays (at the file's size) */
+		const int direct = d->d_dst && !d->d_quality && !d->scale.filter && d->fmt == AGMV_PIXFMT_XRGB32;
 		out = direct ? (uint32_t*)d->d_dst + (size_t)b->first * d->npx : d->d_out[id & 1];
 		prev = !have_state ? NULL : direct ? out - d->npx : d->d_out[(id - 1) & 1] + (size_t)(prev_n - 1) * d->npx;
 		if (b->d_slab) {                       /* the LZ stage left the rows on the device: wait for their commit, on the device */
@@ -865,7 +868,20 @@ static void* dworker_main(void* p)
 		for (k = 0; k < b->n; k++) if (((b->first + k) & 3u) == 0) last_i = (int)k;
 		if (!have_state && last_i < 0 && agmv_hip_memset_async(d->ctx, d->d_iframe, 0, d->npx * 4, d->stream)) goto fail;
 		if (last_i >= 0 && agmv_hip_memcpy_async(d->ctx, d->d_iframe, out + (size_t)last_i * d->npx, d->npx * 4, 2, d->stream)) goto fail;
-		if (d->d_dst && !direct) {
+		if (d->d_dst && d->scale.filter) {
+			const uint32_t tw = d->scale.w, th = d->scale.h;
+			u8* sink = (u8*)d->d_dst + (size_t)b->first * agmv_fmt_frame_bytes(d->fmt, tw, th);
+			if (d->scale.filter != AGMV_SCALE_AREA) {
+				if (agmv_hip_scale_frames_async(d->ctx, d->scale.filter, out, d->w, d->h, b->n, d->fmt, tw, th, sink, d->stream)) goto fail;
+			} else {                                           /* the box filter makes XRGB32: in place for that sink, else converted from d_scaled */
+				uint32_t* scaled = d->fmt == AGMV_PIXFMT_XRGB32 ? (uint32_t*)sink : d->d_scaled;
+				if (agmv_hip_scale_area_dev(d->ctx, AGMV_PIXFMT_XRGB32, out, d->w, d->h, b->n, tw, th, scaled, d->stream)) goto fail;
+				if (d->fmt != AGMV_PIXFMT_XRGB32 &&
+				    (AGMV_FMT_IS_YUV(d->fmt) ? agmv_hip_yuv_from_xrgb_dev(d->ctx, d->fmt, scaled, tw, th, b->n, sink, d->stream)
+				                             : agmv_hip_pixels_from_xrgb_dev(d->ctx, d->fmt, scaled, b->n, (size_t)tw * th, sink, d->stream)))
+					goto fail;
+			}
+		} else if (d->d_dst && !direct) {
 			u8* sink = (u8*)d->d_dst + (size_t)b->first * agmv_fmt_frame_bytes(d->fmt, d->w, d->h);
 			if (d->d_quality ? agmv_hip_measure_frames_async(d->ctx, out, d->fmt, sink, d->w, d->h, b->n, (u8*)d->d_quality + 96 * (size_t)b->first, d->stream) :
 			    AGMV_FMT_IS_YUV(d->fmt) ? agmv_hip_yuv_from_xrgb_dev(d->ctx, d->fmt, out, d->w, d->h, b->n, sink, d->stream)
@@ -1089,11 +1105,15 @@ static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, dchunk* c, const u8* fil
    receives the frame.  The frames go to d_dst (device memory of ctx's device, frame k of the file as a frame of the AGMV_PIXFMT
    `fmt` at its place there) or, with d_dst NULL, to quick_export_<*export_count + 1 ...>.bmp; *export_count advances by the
    frames decoded either way.  With d_quality (device memory, 96 bytes per frame) d_dst is a reference clip in `fmt` that is only
-   read: frame k is measured against frame k of it where the other sink converts, and no decoded frame outlives its batch. */
+   read: frame k is measured against frame k of it where the other sink converts, and no decoded frame outlives its batch.
+   With `scale` (d_dst set, no d_quality) the frames of d_dst are scale->w x scale->h: the batch is decoded at the file's size into
+   the double buffer, never in place, and the sink step scales it into its place (AGMV_DecodeFramesScaledDev of include/agmv.h). */
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
-                       int has_audio, unsigned cap_frames, unsigned threads, void* d_dst, int fmt, void* d_quality, unsigned long* export_count)
+                       int has_audio, unsigned cap_frames, unsigned threads, void* d_dst, int fmt, const agmv_scale* scale, void* d_quality,
+                       unsigned long* export_count)
 {
-	const int direct = d_dst && !d_quality && fmt == AGMV_PIXFMT_XRGB32;     /* decoded in place: no double buffer */
+	const int scaled = scale && scale->filter && d_dst && !d_quality;
+	const int direct = d_dst && !d_quality && !scaled && fmt == AGMV_PIXFMT_XRGB32;     /* decoded in place: no double buffer */
 	dpipe d;
 	dlz z;
 	const char* lzv = getenv("AGMV_LZ_DECODE_DEVICE");     /* opt-in: the LZ stage on the GPU (read when a decode starts) */
@@ -1109,6 +1129,7 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	memset(&z, 0, sizeof(z));
 	d.ctx = ctx; d.w = w; d.h = h; d.npx = npx; d.stride = (cap + 255) & ~(size_t)255;
 	d.cap = cap_frames; d.nslots = 3; d.d_dst = d_dst; d.fmt = fmt; d.d_quality = d_quality;
+	if (scaled) d.scale = *scale;
 	pthread_mutex_init(&d.mu, NULL);
 	pthread_cond_init(&d.cv, NULL);
 	d.slot = (dbatch*)calloc(d.nslots, sizeof(dbatch));
@@ -1120,6 +1141,10 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	d.d_out[0] = direct ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
 	d.d_out[1] = direct ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
 	d.d_iframe = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4);
+	if (scaled && scale->filter == AGMV_SCALE_AREA && fmt != AGMV_PIXFMT_XRGB32) {
+		d.d_scaled = (uint32_t*)agmv_hip_malloc_on(ctx, (size_t)scale->w * scale->h * 4 * d.cap);
+		if (!d.d_scaled) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+	}
 	if (!persist || !chunks || (!lz_dev && !jobs) || !d.stream || (!lz_dev && (!d.d_bits || !d.d_bpos)) || !d.d_nent || (!direct && (!d.d_out[0] || !d.d_out[1])) || !d.d_iframe) { rc = MEMORY_CORRUPTION_ERR; goto out; }
 	if (lz_dev && dlz_open(&z, ctx, d.cap, cap)) { rc = MEMORY_CORRUPTION_ERR; goto out; }
 	for (i = 0; i < d.nslots; i++) {
@@ -1207,7 +1232,7 @@ out:
 	}
 	dlz_close(&z);
 	agmv_hip_free_on(ctx, d.d_bits); agmv_hip_free_on(ctx, d.d_bpos); agmv_hip_free_on(ctx, d.d_nent);
-	agmv_hip_free_on(ctx, d.d_out[0]); agmv_hip_free_on(ctx, d.d_out[1]); agmv_hip_free_on(ctx, d.d_iframe);
+	agmv_hip_free_on(ctx, d.d_out[0]); agmv_hip_free_on(ctx, d.d_out[1]); agmv_hip_free_on(ctx, d.d_iframe); agmv_hip_free_on(ctx, d.d_scaled);
 	agmv_hip_stream_destroy(ctx, d.stream);
 	free(d.slot); free(persist); free(chunks); free(jobs);
 	pthread_mutex_destroy(&d.mu);

@@ -34,7 +34,7 @@ ABI_SYMBOLS = [
     "agmv_hip_histogram_fmt_dev", "agmv_hip_similarity_fmt_dev",
     "agmv_hip_yuv_frame_bytes", "agmv_hip_yuv_to_xrgb_dev", "agmv_hip_yuv_from_xrgb_dev", "agmv_hip_yuv_gather_dev",
     "agmv_hip_yuv_histogram_dev", "agmv_hip_yuv_similarity_dev",
-    "agmv_hip_scale_area_dev",
+    "agmv_hip_scale_area_dev", "agmv_hip_scale_frames_async",
     "agmv_hip_palette_refine_dev",
     "agmv_hip_dither_frames_async",
     "agmv_hip_audio_compand_async", "agmv_hip_audio_expand_async",
@@ -168,6 +168,9 @@ def load_library(path=None):
     if path is None or hasattr(L, "agmv_hip_scale_area_dev"):
         L.agmv_hip_scale_area_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, u32, u32, vp, vp]
         L.agmv_hip_scale_area_dev.restype = C.c_int
+    if path is None or hasattr(L, "agmv_hip_scale_frames_async"):
+        L.agmv_hip_scale_frames_async.argtypes = [vp, C.c_int, vp, u32, u32, u32, C.c_int, u32, u32, vp, vp]
+        L.agmv_hip_scale_frames_async.restype = C.c_int
     if path is None or hasattr(L, "agmv_hip_palette_refine_dev"):
         L.agmv_hip_palette_refine_dev.argtypes = [vp, vp, C.c_int, vp, u32, u32, u32, vp, vp, vp]
         L.agmv_hip_palette_refine_dev.restype = C.c_int
@@ -862,6 +865,31 @@ class AgmvHip:
             out = torch.empty((n_frames, dst_h, dst_w), dtype=torch.int32, device=src.device)
         _check_vec("scale_area_dev: out", out, n_frames * dst_w * dst_h)
         self._ck(self.L.agmv_hip_scale_area_dev(self.ctx, fmt, src.data_ptr(), w, h, n_frames, dst_w, dst_h, out.data_ptr(), self._stream()))
+        return out
+
+    # ------------------------------------------------------------------ a decoded clip at a target size (AGMV_SCALE_NEAREST / _BILINEAR of include/agmv.h)
+    def scale_frames_async(self, filt, src, w, h, n_frames, fmt, dst_w, dst_h, out=None, yuv=None, full_range=False, stream=None):
+        """src: int32 CUDA tensor of n_frames frames of w x h pixels 0x00RRGGBB -> the clip scaled to dst_w x dst_h with `filt`
+        (1 nearest, 3 bilinear) in fmt (any name of PIXFMT or YUVFMT, or its value): uint8 [n_frames, frame bytes], or `out`, a
+        contiguous CUDA tensor of at least that many bytes (agmv_hip_scale_frames_async) on `stream` (a torch stream; None =
+        torch's current one).  Nothing waits."""
+        import torch
+        w, h, n_frames, dst_w, dst_h = int(w), int(h), int(n_frames), int(dst_w), int(dst_h)
+        _check_vec("scale_frames_async: src", src, n_frames * w * h)
+        if fmt in YUVFMT or (isinstance(fmt, int) and (fmt & 0xFF) in YUVFMT.values()):
+            fmt = yuvfmt(fmt, yuv, full_range)
+            fb = self.L.agmv_hip_yuv_frame_bytes(fmt, dst_w, dst_h)
+        else:
+            if yuv is not None or full_range:
+                raise ValueError("scale_frames_async: yuv= and full_range= belong to fmt \"nv12\" and \"i420\", not to fmt %r" % (fmt,))
+            fmt = pixfmt(fmt)
+            fb = self.pixfmt_frame_bytes(fmt, dst_w * dst_h)
+        if out is None:
+            out = torch.empty((n_frames, fb), dtype=torch.uint8, device=src.device)
+        elif not (out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= n_frames * fb):
+            raise ValueError("scale_frames_async: out must be a contiguous CUDA tensor of >= %d bytes" % (n_frames * fb))
+        s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self._ck(self.L.agmv_hip_scale_frames_async(self.ctx, int(filt), src.data_ptr(), w, h, n_frames, fmt, dst_w, dst_h, out.data_ptr(), s))
         return out
 
     # ------------------------------------------------------------------ the palette refined by weighted k-means (include/agmv.h)

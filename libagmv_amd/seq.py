@@ -1,5 +1,5 @@
 """Whole .agmv sequences from and to frames in GPU memory: ctypes calls of AGMV_EncodeFramesFmtDev / AGMV_EncodeFramesScaledDev /
-AGMV_DecodeFramesFmtDev (include/agmv.h, libagmv.so).  No logic here: the schedules, the container, both LZ stages and the reading and writing of the
+AGMV_DecodeFramesFmtDev / AGMV_DecodeFramesScaledDev (include/agmv.h, libagmv.so).  No logic here: the schedules, the container, both LZ stages and the reading and writing of the
 caller's pixel layout are the library's; torch holds the frames.  The frames live on the library's own device (env AGMV_DEVICE,
 default 0).
 clip_quality / file_quality (AGMV_MeasureFramesDev / AGMV_MeasureFileDev) measure a decoded clip, or a file batch by batch, against
@@ -28,6 +28,7 @@ from .hip import HERE, PIXFMT, YUVFMT, HipUnavailable, pcmfmt, pixfmt, yuvfmt
 
 SCHEDULE_FULL, SCHEDULE_PDIFS, SCHEDULE_ADAPTIVE = 1, 2, 3
 SCALE = {"nearest": 1, "area": 2}          # AGMV_SCALE of include/agmv.h, which defines both filters
+DECODE_SCALE = {"nearest": 1, "area": 2, "bilinear": 3}      # ... and the filters of decode_frames(size=): AGMV_DecodeFramesScaledDev
 
 
 class AGMV_FRAME_QUALITY(C.Structure):
@@ -61,6 +62,8 @@ def load_library():
         L.AGMV_EncodeFramesFmtDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int] + [C.c_ulong] * 4 + [C.c_int] * 4
         L.AGMV_DecodeFramesFmtDev.restype = C.c_int
         L.AGMV_DecodeFramesFmtDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.POINTER(AGMV_INFO)]
+        L.AGMV_DecodeFramesScaledDev.restype = C.c_int
+        L.AGMV_DecodeFramesScaledDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.c_ulong, C.c_int, C.c_ulong, C.POINTER(AGMV_INFO)]
         L.AGMV_EncodeFramesScaledDev.restype = C.c_int
         L.AGMV_EncodeFramesScaledDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int] + [C.c_ulong] * 5 + [C.c_int, C.c_ulong] + [C.c_int] * 4
         L.AGMV_SetPaletteRefine.restype = None
@@ -219,11 +222,29 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
             L.AGMV_SetDither(0)
 
 
-def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False):
+def _decode_target(size, scale):
+    """(filter value, h, w) of decode_frames' size= and scale=, or None for size=None; touches neither the library nor the device"""
+    if not isinstance(scale, str) or scale not in DECODE_SCALE:
+        raise ValueError("decode_frames: scale %r is unknown: one of %s is needed" % (scale, ", ".join("\"%s\"" % k for k in sorted(DECODE_SCALE))))
+    if size is None:
+        if scale != "bilinear":
+            raise ValueError("decode_frames: scale=%r needs size=(h, w): without a target size nothing is scaled" % (scale,))
+        return None
+    if not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and not isinstance(v, bool) and v > 0 for v in size)):
+        raise ValueError("decode_frames: size must be (h, w), two positive ints, got %r" % (size,))
+    return DECODE_SCALE[scale], size[0], size[1]
+
+
+def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False, size=None, scale="bilinear"):
     """-> (CUDA tensor of the file's frames on the library's device in the layout `fmt`: int32 [n, h, w] of 0x00RRGGBB for "xrgb32",
     uint8 [n, h, w, 3] / [n, h, w, 4] / [n, 3, h, w] for the byte formats, uint8 [n, h * 3 / 2, w] for "nv12" and "i420" (a file
-    of even width and height; yuv and full_range as for encode_frames); AGMV_INFO of the header)"""
+    of even width and height; yuv and full_range as for encode_frames); AGMV_INFO of the header).  size=(h, w), in tensor order,
+    delivers the frames at that size instead of the file's (AGMV_DecodeFramesScaledDev of include/agmv.h, which defines the
+    filters): scale "bilinear" (the default) and "nearest" take any size in either direction, "area" is the exact box filter and
+    only scales down.  The tensor then has the layout's shape at (h, w) -- even h and w for the two YUV layouts, whatever the
+    file's size -- and the AGMV_INFO still carries the file's own size."""
     import torch
+    target = _decode_target(size, scale)
     v = _fmt_value("decode_frames", fmt, yuv, full_range)
     L = load_library()
     info = AGMV_INFO()
@@ -231,13 +252,24 @@ def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False):
     if rc < 0:
         raise RuntimeError("AGMV_DecodeFramesFmtDev(%s): Error %d" % (path, -rc))
     n, h, w = info.number_of_frames, info.height, info.width
+    if target is not None:
+        filt, th, tw = target
+        if filt == DECODE_SCALE["area"] and (th > h or tw > w):
+            raise ValueError("decode_frames: scale=\"area\" only scales down, %s holds %d x %d and size= asks for %d x %d" % (path, w, h, tw, th))
+        h, w = th, tw
     if v & 0xFF in YUVFMT.values() and (h % 2 or w % 2):
-        raise ValueError("decode_frames: fmt %r needs a file of even width and height, %s holds %d x %d" % (fmt, path, w, h))
+        raise ValueError("decode_frames: fmt %r needs %s of even width and height, %s %d x %d"
+                         % (fmt, "a file" if target is None else "a target", ("%s holds" % path) if target is None else "size= asks for", w, h))
     shape = {1: (n, h, w), 2: (n, h, w, 3), 3: (n, h, w, 3), 4: (n, h, w, 4), 5: (n, 3, h, w), 16: (n, h * 3 // 2, w), 17: (n, h * 3 // 2, w)}[v & 0xFF]
     out = torch.empty(shape, dtype=torch.int32 if v == 1 else torch.uint8, device=_device())
-    rc = L.AGMV_DecodeFramesFmtDev(os.fsencode(path), out.data_ptr(), v, n, None)
+    if target is None:
+        rc = L.AGMV_DecodeFramesFmtDev(os.fsencode(path), out.data_ptr(), v, n, None)
+        if rc < 0:
+            raise RuntimeError("AGMV_DecodeFramesFmtDev(%s): Error %d" % (path, -rc))
+        return out[:rc], info
+    rc = L.AGMV_DecodeFramesScaledDev(os.fsencode(path), out.data_ptr(), v, w, h, filt, n, None)
     if rc < 0:
-        raise RuntimeError("AGMV_DecodeFramesFmtDev(%s): Error %d" % (path, -rc))
+        raise RuntimeError("AGMV_DecodeFramesScaledDev(%s, %d x %d, scale %r): Error %d" % (path, w, h, scale, -rc))
     return out[:rc], info
 
 
