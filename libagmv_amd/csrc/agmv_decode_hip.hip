@@ -36,7 +36,7 @@ constexpr int DEC_MAX_SLICES = 32;           // agmv_hip_parse_decode_frames_dev
 struct dec_ws {
 	uint32_t* d_dirty;              // decode: bitmap of block positions needing the fix-up
 	size_t dirty_cap;               // in bytes
-	bool dep_split;                 // the last decode call was cut into ranges: its prior dependence is range 0's, saved behind the bitmap
+	bool dep_split;                 // the last decode call was cut into ranges: its prior dependence is range 0's, whose words are the second set
 	uint32_t* d_parse_ws;           // parser workspace: cum | centry | summ
 	size_t parse_ws_cap;            // in bytes
 	uint32_t* d_fp_ws;              // fast parser workspace: rec | vm | kb | fstate
@@ -527,6 +527,15 @@ struct FpArgs {
 };
 constexpr uint32_t TIDX_NONE = 0xFFFFFFFFu;
 
+// buffer descriptor from wave-uniform inputs, made PROVABLY uniform (readfirstlane on both pointer halves and the size): otherwise
+// hipcc wraps every buffer op in a waterfall loop
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void* p, uint32_t bytes)
+{
+	const uint64_t a = (uint64_t)p;
+	const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
+	return __builtin_amdgcn_make_buffer_rsrc((void*)((uint64_t)hi << 32 | lo), 0, __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
+}
+
 __device__ __forceinline__ uint32_t ctz64(unsigned long long m) { return (uint32_t)__builtin_ctzll(m); }       // m != 0
 __device__ __forceinline__ unsigned long long above(uint32_t q) { return (~0ull << q) << 1; }     // bits > q (q <= 63)
 
@@ -539,11 +548,19 @@ __device__ __forceinline__ void fp_walk_region(const FpArgs& A, uint32_t* s_b, u
 	// ---- stage the 64 pieces (run-in, own, one behind); bytes before the frame or past the slab read as 0
 	const long sb = (long)r * FRB - FH * FC;
 	uint32_t raw[16];
-	const long pos0 = sb + 4 * lane;
+	{
+		// The range check is the buffer descriptor's, not the lanes': the resource is the frame's row, cap bytes of it (a multiple
+		// of 4, and so is every offset: a dword in range lies wholly inside).  A dword at or past cap reads 0 and fetches nothing;
+		// a row never sees its neighbour's bytes.  Only region 0 has bytes in front of the row (sb = -FH * FC: exactly the 64
+		// dwords of k = 0): their offsets, 0xFFFFFF00 .. 0xFFFFFFFC, are >= the resource's size for any stride below 4 GB - 256,
+		// so they read 0.  No offset relies on wrapping around 2^32: o1 < stride + 2 FRB and o1 + 3584 stay far below it,
+		// whether or not the compiler folds the constant 256 (k - 1) into the instruction.
+		const __amdgpu_buffer_rsrc_t rs = uniform_rsrc(fbits, cap & ~3u);
+		const uint32_t o0 = (sb < 0 ? 0xFFFFFF00u : (uint32_t)sb) + 4u * (uint32_t)lane;   // (sb is uniform: a scalar select)
+		const uint32_t o1 = (uint32_t)(sb + FH * FC) + 4u * (uint32_t)lane;
+		raw[0] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, o0, 0, 0);
 #pragma unroll
-	for (int k = 0; k < 16; k++) {
-		const long pos = pos0 + 256 * k;
-		raw[k] = (pos >= 0 && pos + 4 <= (long)cap) ? *(const uint32_t*)(fbits + pos) : 0u;
+		for (int k = 1; k < 16; k++) raw[k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, o1 + 256u * (uint32_t)(k - 1), 0, 0);
 	}
 	{
 		// dword i = 64 k + lane of the span is dword j = lane & 15 of piece 4 k + (lane >> 4): one base address + constants
@@ -1117,15 +1134,6 @@ __device__ __forceinline__ void store_block(uint32_t* frame, uint32_t poff, uint
 	}
 }
 
-// buffer descriptor from wave-uniform inputs, made PROVABLY uniform (readfirstlane on both pointer halves and the size): otherwise
-// hipcc wraps every buffer op in a waterfall loop
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void* p, uint32_t bytes)
-{
-	const uint64_t a = (uint64_t)p;
-	const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
-	return __builtin_amdgcn_make_buffer_rsrc((void*)((uint64_t)hi << 32 | lo), 0, __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-}
-
 // K3: one lane = one 4x4 block carried through the <=4 frames of its GOP (img_data and
 // iframe->img_data of the block live in registers).  A block whose value depends on a frame
 // outside the GOP (not rewritten since the GOP started) is flagged in `dirty` and repaired by
@@ -1621,6 +1629,17 @@ static int parse_launch(agmv_hip_ctx* c, const DecRows& r, size_t ws_frames, hip
 		const uint32_t want = (uint32_t)(((size_t)r.stride / 8 + FRB - 1) / FRB) + 1;   // regions of a frame whose stream is an eighth of the worst case
 		if (gx > want) gx = want;
 		if ((size_t)gx * gy > 131072u) gy = 131072u / gx;
+	} else if (bm) {
+		// A long range of large frames (bitmap form; k_fp_expand was not measured): as wide as a frame whose stream is an
+		// eighth of the geometry's worst case (agmv_hip_max_usize; not the caller's stride, which changes with the slab's
+		// padding) has regions -- 143 columns for 1080p, 512 colours, where parse_grid_x gives 256 -- wherever that grid
+		// still holds four waves for every wave slot of the device, so that its tail stays short.  Measured at 512 x 1080p
+		// (profiles/parser_staging/): k_fp_walk 142 -> 131 us and k_fp_tiles 24.8 -> 21.4 us on the synthetic clip (117 regions
+		// a frame: one turn per workgroup as before), 396 -> 386 and 48.3 -> 45.2 on NORMAL-heavy content (356 regions: three
+		// turns instead of two).  Frames of more regions than that (up to 1133 at 1080p: eight turns instead of five) were not measured.
+		const size_t worst = (size_t)r.nblk * (c->mode512 ? 33 : 17) + 64;
+		const uint32_t want = (uint32_t)((worst / 8 + FRB - 1) / FRB) + 1;
+		if (gx > want && (size_t)want * gy >= (size_t)c->n_cu * 32 * 4) gx = want;
 	}
 	const dim3 grid(gx, gy);
 	if (robust_only) {                                         // debugging aid: every frame through the robust kernels (bitmap form)
@@ -1687,8 +1706,10 @@ extern "C" int agmv_hip_parse_fallback_frames(agmv_hip_ctx* c, void* stream)
 }
 
 // arguments of k_decode / k_fixup for the rows r; grows the context's bitmap of positions to repair and, unless the
-// caller has that done (k_fp_tiles), clears it
-static int decode_prepare(agmv_hip_ctx* c, DecArgs& A, const DecRows& r, const DecPix& px, hipStream_t s, bool clear)
+// caller has that done (k_fp_tiles), clears it.  The context holds TWO sets of those words.  Range 0 of a call cut into ranges
+// takes the second (`second`): its "depends on the prior state" word is the call's, and the later ranges, which depend on
+// the ranges before them and not on the caller, clear and write the first set only
+static int decode_prepare(agmv_hip_ctx* c, DecArgs& A, const DecRows& r, const DecPix& px, hipStream_t s, bool clear, bool second = false)
 {
 	if (((uintptr_t)px.out & 15u) || ((uintptr_t)px.prev & 15u) || ((uintptr_t)px.prev_iframe & 15u)) return agmv_hip_err("agmv_hip: pixel buffers must be 16-byte aligned");
 	if (check_slab(r.bits, r.stride)) return -1;
@@ -1699,10 +1720,10 @@ static int decode_prepare(agmv_hip_ctx* c, DecArgs& A, const DecRows& r, const D
 	A.tpf = (A.nblk + DEC_T - 1) / DEC_T;
 	A.first_fc = px.first_fc; A.phase = px.first_fc & 3u; A.n_groups = (r.n_frames + A.phase + 3) / 4;
 	const size_t nwords = dirty_words(A.nblk);
-	dec_ws* d = dec_area(c);                                   // (+ part 0's "depends" word of a call cut into parts: written, never cleared)
-	CK(agmv_hip_dev_grow(&d->d_dirty, &d->dirty_cap, (nwords + 1) * 4, 1));
-	A.dirty = d->d_dirty; d->dep_split = false;
-	if (clear) CK(hipMemsetAsync(d->d_dirty, 0, nwords * 4, s));
+	dec_ws* d = dec_area(c);
+	CK(agmv_hip_dev_grow(&d->d_dirty, &d->dirty_cap, 2 * nwords * 4, 1));
+	A.dirty = d->d_dirty + (second ? nwords : 0); d->dep_split = false;
+	if (clear) CK(hipMemsetAsync(A.dirty, 0, nwords * 4, s));
 	return 0;
 }
 
@@ -1850,7 +1871,8 @@ extern "C" int agmv_hip_decode_bitstreams_dev(agmv_hip_ctx* c, const uint8_t* d_
 		CK(agmv_hip_dev_grow(&d->d_fstate_call, &d->fstate_call_cap, (size_t)n_frames * 4, 1));
 		fstate = d->d_fstate_call;
 	}
-	agmv_hip_ev_mark(c, 6, s);
+	// timing marks: one per boundary (the end of a parser is the start of its k_decode, the end of a range the start of the
+	// next, the first and the last are the call's)
 	int k = 0;
 	for (uint32_t f0 = 0; f0 < n_frames; k++) {
 		uint32_t f1 = n_frames;
@@ -1865,24 +1887,18 @@ extern "C" int agmv_hip_decode_bitstreams_dev(agmv_hip_ctx* c, const uint8_t* d_
 		const DecPix px = {w, h, first_fc + f0, d_out + (size_t)f0 * npx, f0 == 0 ? d_prev : d_out + (size_t)(f0 - 1) * npx,
 		                   f0 == 0 ? d_prev_iframe : d_out + (size_t)(f0 - 4) * npx};
 		DecArgs A;
-		if (decode_prepare(c, A, r, px, s, false)) return -1;
-		if (agmv_hip_ev_mark_range(c, 2, k, s)) return -1;
+		if (decode_prepare(c, A, r, px, s, false, cut && f0 == 0)) return -1;
+		if (agmv_hip_ev_mark_seq(c, 2 * k, s)) return -1;     // (k > 0: also the end of the range before)
 		// work areas sized for the longest range, not for this one: growing them in mid-call would wait for the device
 		if (parse_launch(c, r, cut ? ws_frames : r.n_frames, s, &A, fstate ? fstate + f0 : nullptr)) return -1;   // fills in A.vm, A.kb, A.tidx, A.maxR
-		if (agmv_hip_ev_mark_range(c, 3, k, s)) return -1;
-		if (agmv_hip_ev_mark_range(c, 4, k, s)) return -1;
+		if (agmv_hip_ev_mark_seq(c, 2 * k + 1, s)) return -1;
 		if (decode_launch(c, A, 0, A.n_groups, s)) return -1;
 		if (fixup_launch(c, A, s)) return -1;
-		if (agmv_hip_ev_mark_range(c, 5, k, s)) return -1;
-		if (f0 == 0 && cut) {                                      // later ranges depend on the ranges before them, not on the caller:
-			const size_t dw = (A.nblk + 31) / 32 + 1;          // the call's prior dependence is range 0's (the next k_fp_tiles clears it)
-			CK(hipMemcpyAsync(d->d_dirty + dw + 1, d->d_dirty + dw, 4, hipMemcpyDeviceToDevice, s));
-		}
 		f0 = f1;
 	}
+	if (agmv_hip_ev_mark_seq(c, 2 * k, s)) return -1;
 	d->dep_split = cut;
 	if (cut) { d->d_fp_fstate = fstate; d->fp_frames = n_frames; }
-	agmv_hip_ev_mark(c, 7, s);
 	return 0;
 }
 
@@ -1894,7 +1910,7 @@ extern "C" int agmv_hip_decode_prior_dependent(agmv_hip_ctx* c, uint32_t w, uint
 	const size_t nblk = (size_t)(w / 4) * (h / 4);
 	uint32_t v = 0;
 	CK(hipStreamSynchronize((hipStream_t)stream));
-	CK(hipMemcpy(&v, d->d_dirty + (nblk + 31) / 32 + (d->dep_split ? 2 : 1), 4, hipMemcpyDeviceToHost));
+	CK(hipMemcpy(&v, d->d_dirty + (d->dep_split ? dirty_words((uint32_t)nblk) : 0u) + (nblk + 31) / 32 + 1, 4, hipMemcpyDeviceToHost));
 	return v ? 1 : 0;
 }
 

@@ -19,6 +19,7 @@
 // Integer/byte work only: no MFMA. The bound is HBM (4 B/px in, usize out).
 #include <hip/hip_runtime.h>
 
+#include <math.h>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -943,8 +944,8 @@ extern "C" void agmv_hip_destroy(agmv_hip_ctx* c)
 	(void)hipFree(c->d_nn_pal); (void)hipFree(c->d_nn_pix); (void)hipFree(c->d_nn_ent);
 	if (c->ev_enc) (void)hipEventDestroy(c->ev_enc);
 	for (int i = 0; i < 8; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-	for (int i = 0; i < 4 * c->ev_rng_cap; i++) (void)hipEventDestroy(c->ev_rng[i]);
-	free(c->ev_rng);
+	for (int i = 0; i < c->ev_seq_cap; i++) (void)hipEventDestroy(c->ev_seq[i]);
+	free(c->ev_seq);
 	for (int k = 0; k < AREA_KINDS; k++) if (c->ws[k]) c->ws_free[k](c->ws[k]);
 	free(c);
 }
@@ -961,24 +962,22 @@ void* agmv_hip_area(agmv_hip_ctx* c, agmv_hip_area_kind kind, size_t bytes, void
 void agmv_hip_ev_mark(agmv_hip_ctx* c, int which, hipStream_t s)
 {
 	if (!c->timing) return;
-	if (which == 2 || which == 4) c->ev_rng_n[which / 2 - 1] = 0;   // a start mark: one interval so far
+	if (which >= 2 && !(which & 1)) c->ev_seq_n[which / 2 - 1] = 0;   // a start mark: this interval is ev[which], ev[which + 1] again
 	(void)hipEventRecord(c->ev[which], s);
 }
 
-int agmv_hip_ev_mark_range(agmv_hip_ctx* c, int which, int range, hipStream_t s)
+int agmv_hip_ev_mark_seq(agmv_hip_ctx* c, int i, hipStream_t s)
 {
 	if (!c->timing) return 0;
-	if (range == 0) { agmv_hip_ev_mark(c, which, s); return 0; }
-	if (range > c->ev_rng_cap) {
-		const int cap = range > 2 * c->ev_rng_cap ? range : 2 * c->ev_rng_cap;
-		hipEvent_t* p = (hipEvent_t*)realloc(c->ev_rng, (size_t)cap * 4 * sizeof(hipEvent_t));
+	if (i >= c->ev_seq_cap) {
+		const int cap = i + 1 > 2 * c->ev_seq_cap ? i + 1 : 2 * c->ev_seq_cap;
+		hipEvent_t* p = (hipEvent_t*)realloc(c->ev_seq, (size_t)cap * sizeof(hipEvent_t));
 		if (!p) return agmv_hip_err("agmv_hip: out of host memory");
-		c->ev_rng = p;
-		for (; c->ev_rng_cap < cap; c->ev_rng_cap++)
-			for (int i = 0; i < 4; i++) CK(hipEventCreate(&p[4 * c->ev_rng_cap + i]));
+		c->ev_seq = p;
+		for (; c->ev_seq_cap < cap; c->ev_seq_cap++) CK(hipEventCreate(&p[c->ev_seq_cap]));
 	}
-	CK(hipEventRecord(c->ev_rng[4 * (range - 1) + which - 2], s));
-	if (which == 2 || which == 4) c->ev_rng_n[which / 2 - 1] = range;
+	CK(hipEventRecord(c->ev_seq[i], s));
+	if (i > 0 && !(i & 1)) c->ev_seq_n[0] = c->ev_seq_n[1] = c->ev_seq_n[2] = i / 2;   // behind a range's k_fixup: i / 2 whole ranges
 	return 0;
 }
 
@@ -992,21 +991,31 @@ extern "C" int agmv_hip_enable_timing(agmv_hip_ctx* c, int on)
 }
 
 /* duration in ms of the last launch of kernel group `which` (0 = k_encode, 1 = the parser kernels,
-   2 = k_decode + k_fixup, 3 = the whole of agmv_hip_parse_decode_frames_dev), measured with HIP events on the stream it ran on; synchronises on the stop event.
-   A decode cut into GOP ranges ran groups 1 and 2 once per range: the sum over the ranges of that call */
+   2 = k_decode + k_fixup, 3 = the whole of agmv_hip_parse_decode_frames_dev / agmv_hip_decode_bitstreams_dev), measured with HIP events on the
+   stream it ran on; synchronises on the stop event.  agmv_hip_decode_bitstreams_dev ran groups 1 and 2 once per range, with one mark
+   per boundary: 1 and 2 are the sums over the ranges of that call, 3 is the sum of both (no time lies between its intervals) */
 extern "C" float agmv_hip_last_kernel_ms(agmv_hip_ctx* c, int which)
 {
 	float ms = -1.0f;
 	if (!c || !c->timing || which < 0 || which > 3) return -1.0f;
+	if (const int n = which ? c->ev_seq_n[which - 1] : 0) {    // agmv_hip_decode_bitstreams_dev: n ranges, a mark per boundary
+		const hipEvent_t* e = c->ev_seq;
+		if (hipEventSynchronize(e[2 * n]) != hipSuccess) return -1.0f;
+		double sum[2] = {0.0, 0.0};                             // parser: [2k] -> [2k + 1]; k_decode + k_fixup: [2k + 1] -> [2k + 2]
+		for (int i = 0; i < 2 * n; i++) {
+			float part = 0.0f;
+			if (hipEventElapsedTime(&part, e[i], e[i + 1]) != hipSuccess) return -1.0f;
+			sum[i & 1] += part;
+		}
+		if (which < 3) return (float)sum[which - 1];
+		// the intervals share their marks, so the call is exactly their sum: rounded UP, so that groups 1 and 2 as returned
+		// never add up to more than group 3
+		const double whole = (double)(float)sum[0] + (double)(float)sum[1];
+		ms = (float)whole;
+		return (double)ms < whole ? nextafterf(ms, INFINITY) : ms;
+	}
 	if (hipEventSynchronize(c->ev[2 * which + 1]) != hipSuccess) return -1.0f;
 	if (hipEventElapsedTime(&ms, c->ev[2 * which], c->ev[2 * which + 1]) != hipSuccess) return -1.0f;
-	if (which == 1 || which == 2)
-		for (int k = 0; k < c->ev_rng_n[which - 1]; k++) {     // the later ranges, in stream order behind the first
-			hipEvent_t* e = c->ev_rng + 4 * k + 2 * (which - 1);
-			float part = 0.0f;
-			if (hipEventSynchronize(e[1]) != hipSuccess || hipEventElapsedTime(&part, e[0], e[1]) != hipSuccess) return -1.0f;
-			ms += part;
-		}
 	return ms;
 }
 

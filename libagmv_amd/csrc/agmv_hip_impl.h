@@ -31,9 +31,10 @@ struct agmv_hip_ctx {
 	int n_cu;
 	int timing;                     // record HIP events around the three hot kernels
 	hipEvent_t ev[8];               // encode, parse, decode, parse||decode pipeline: start/stop
-	hipEvent_t* ev_rng;             // a decode cut into GOP ranges: marks 2..5 of range k >= 1 at [4 * (k - 1) + mark - 2], grown on demand
-	int ev_rng_cap;                 // ... ranges the pool has events for
-	int ev_rng_n[2];                // ... ranges behind the first that the last parse / the last decode marked
+	hipEvent_t* ev_seq;             // agmv_hip_decode_bitstreams_dev: one mark per boundary -- [2k] in front of range k's parser, [2k + 1] between
+	                                // it and the range's k_decode, [2n] behind the last k_fixup; grown on demand
+	int ev_seq_cap;                 // ... events in the pool
+	int ev_seq_n[3];                // ... ranges n whose marks hold the last parse / decode / whole-call times (0: ev[2..7] do)
 	hipEvent_t ev_enc;              // end of the last encode launch (encodes of one context share status / control words)
 	hipStream_t enc_stream;         // ... and the stream it went to
 	int have_enc;
@@ -60,8 +61,9 @@ int agmv_hip_enter(agmv_hip_ctx* c, bool palette = false);
 void* agmv_hip_area(agmv_hip_ctx* c, agmv_hip_area_kind kind, size_t bytes, void (*destroy)(void*));
 
 void agmv_hip_ev_mark(agmv_hip_ctx* c, int which, hipStream_t s);   // a timing mark: encode 0/1, the decoder 2..7
-// marks 2..5 of range `range` of a call cut into ranges (range 0: agmv_hip_ev_mark): agmv_hip_last_kernel_ms adds the ranges up
-int agmv_hip_ev_mark_range(agmv_hip_ctx* c, int which, int range, hipStream_t s);
+// boundary `i` of a decode that runs parser, k_decode + k_fixup, parser, ... back to back (see ev_seq): ONE mark where an
+// interval ends and the next begins.  Behind mark 2n, agmv_hip_last_kernel_ms(1..3) are the sums over the n ranges
+int agmv_hip_ev_mark_seq(agmv_hip_ctx* c, int i, hipStream_t s);
 int agmv_hip_check_geometry(uint32_t w, uint32_t h);
 
 // Grow the device buffer *p of *cap units (of `unit` bytes) to at least `need` units.  The contents are not kept; on failure
