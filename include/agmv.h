@@ -517,6 +517,50 @@ int AGMV_EncodeFramesScaledDev(const char* filename, const void* d_frames, AGMV_
 int AGMV_DecodeFramesScaledDev(const char* filename, void* d_frames, AGMV_PIXFMT fmt, u32 width, u32 height, AGMV_SCALE filter, u32 cap_frames,
                                AGMV_INFO* info);
 
+/* Normalised float tensors: what a model takes and gives.  A tensor clip is n frames of [3][h][w] elements -- planes R, G, B,
+   back to back (NCHW) -- of the type an AGMV_TENSORFMT names, aligned to its element:
+     AGMV_TENSOR_F32   IEEE binary32
+     AGMV_TENSOR_F16   IEEE binary16
+     AGMV_TENSOR_BF16  the upper 16 bits of a binary32
+   It carries a normalisation mean[3], std[3] (float, channel 0 = R), and a byte v of channel c stands for
+   (v / 255 - mean[c]) / std[c].  Bounds: 2^-32 <= |std[c]| <= 2^32 and |mean[c]| <= 2^32, both finite; anything else (and an
+   unknown type) is -1 before a device is opened.  Inside these bounds no outcome depends on whether the device flushes subnormals:
+   the table below is made on the host and only copied by the device, and where an input, the product or the sum of the reading
+   rule is a float32 subnormal, t lies so close to 0 that the byte is 0 with and without the flush.
+
+   Writing (the decoder's sink) is exact by construction, because it is a table.  T[c][v], 3 x 256 entries, is the float32
+   nearest to the double ((double)v / 255.0 - (double)mean[c]) / (double)std[c]; for F16 / BF16 that float32 is rounded to
+   nearest-even into the type, overflow giving an infinity of its sign.  The host builds the table in integers where it narrows
+   (agmv_hip_tensor_table of include/agmv_hip.h) and the kernel only looks it up:
+     out[k][c][y][x] = T[c][channel c of D(x, y)]
+   where D is the XRGB32 decode, or with a target size the clip AGMV_DecodeFramesScaledDev defines for the filter.
+
+   Reading (the encoder's source).  With a[c] = (float)(255.0 * (double)std[c]) and b[c] = (float)(255.0 * (double)mean[c]) an
+   element x of channel c, converted exactly to float32, gives
+     t = fl32(fl32(x * a[c]) + b[c])          two separately rounded float32 operations, never a fused one
+     v = 0 for a NaN, else (int)rintf(fminf(fmaxf(t, 0), 255)), rounding half to even
+   so -inf and everything below 0 give 0, +inf and everything above 255 give 255.  A tensor clip stands for the XRGB32 clip this
+   reading gives: the palette, the schedules' decisions and the file are those of that clip, byte for byte.  For the usual
+   normalisations reading what was written returns every v (tests/test_tensor_cpu.py).
+
+   AGMV_DecodeFramesTensorDev is AGMV_DecodeFramesScaledDev into a tensor clip: width == height == 0 means the file's size, and
+   `filter` is then ignored.  The batches are decoded at the file's size, the table is uploaded once per call, and the sink is
+   one launch per batch (AGMV_SCALE_AREA goes through one batch of D).  Frame k lands k * 3 * width * height elements into
+   d_tensor.  Returns and the order of the checks are AGMV_DecodeFramesScaledDev's, with -1 also for an unknown type or a refused
+   normalisation; with d_tensor NULL only *info is filled.
+   AGMV_EncodeFramesTensorDev materialises the XRGB32 clip of the reading rule on the library's device with one launch
+   (agmv_hip_tensor_to_xrgb_async; 4 * width * height * num_of_frames bytes, a third to two thirds of the source), takes the path
+   of AGMV_EncodeFramesDev on it and frees it before it returns.  It returns what AGMV_EncodeFramesDev returns for that clip
+   (-1, also for an unknown type or a refused normalisation, -5, -2, -3), all before a device is opened, and -4 when the clip
+   cannot be allocated.  A pending AGMV_SetAudioDev track, the dither and the palette refinement apply as for the other
+   AGMV_EncodeFrames*Dev; the track is consumed whatever the call returns. */
+typedef enum AGMV_TENSORFMT { AGMV_TENSOR_F32 = 1, AGMV_TENSOR_F16 = 2, AGMV_TENSOR_BF16 = 3 } AGMV_TENSORFMT;
+int AGMV_DecodeFramesTensorDev(const char* filename, void* d_tensor, AGMV_TENSORFMT type, const float mean[3], const float std[3], u32 width,
+                               u32 height, AGMV_SCALE filter, u32 cap_frames, AGMV_INFO* info);
+int AGMV_EncodeFramesTensorDev(const char* filename, const void* d_tensor, AGMV_TENSORFMT type, const float mean[3], const float std[3],
+                               u32 num_of_frames, u32 width, u32 height, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
+                               AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule);
+
 /* Audio tracks from and to GPU memory.  An AGMV_PCMFMT names the layout of PCM in device memory:
      AGMV_PCM_S16   [samples][channels] 16-bit words, bits unchanged (int16 WAV samples as they are); for 16-bit tracks
      AGMV_PCM_U8    [samples][channels] unsigned bytes; for 8-bit tracks; a copy

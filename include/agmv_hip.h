@@ -441,6 +441,41 @@ int agmv_hip_scale_area_dev(agmv_hip_ctx* ctx, int fmt, const void* d_src, uint3
 int agmv_hip_scale_frames_async(agmv_hip_ctx* ctx, int filter, const uint32_t* d_src, uint32_t src_w, uint32_t src_h,
                                 uint32_t n_frames, int fmt, uint32_t dst_w, uint32_t dst_h, void* d_dst, void* stream);
 
+/* -- normalised float tensor clips ---------------------------------------------------------------
+ * AGMV_TENSORFMT of include/agmv.h ("normalised float tensors"), which holds the definitions: `type` is 1 F32, 2 F16 (IEEE
+ * binary16) or 3 BF16, by value; a tensor clip is n frames of [3][h][w] elements, planes R, G, B, aligned to its element.
+ * agmv_hip_tensor_frame_bytes:  3 * (4, 2, 2) * n_pixels; 0 for an unknown type.  Host only: needs no context and no GPU.
+ * agmv_hip_tensor_table:        the writing rule as a table: table[256 * c + v] = the bit pattern, in `type`, of the float32
+ *                               nearest to the double ((double)v / 255.0 - (double)mean[c]) / (double)std[c], rounded to
+ *                               nearest-even into F16 / BF16 (overflow is an infinity) by integer code.  768 elements of the
+ *                               type in host memory.  Host only.  Returns non-zero for an unknown type, a NULL pointer or a
+ *                               normalisation outside the bounds of include/agmv.h (NaN and infinities are outside).
+ * agmv_hip_tensor_from_xrgb_async (the decoder's sink): d_src holds n_frames packed XRGB32 frames of src_w x src_h (bits >= 24
+ *   ignored, 4-byte aligned); target frame k, 3 * dst_w * dst_h elements, receives out[c][Y][X] = table[256 * c + channel c of
+ *   D(X, Y)], where D is the source (`filter` 0: the sizes are equal) or the clip agmv_hip_scale_frames_async defines for `filter`
+ *   1 (nearest) or 3 (bilinear); 2 is refused: the box filter is agmv_hip_scale_area_dev's.  d_table is agmv_hip_tensor_table's
+ *   768 elements in device memory; the kernel keeps them in LDS and only looks them up, so the elements are the table's bit
+ *   patterns whatever they are.  One launch, asynchronous on `stream`: no allocation, no host synchronisation, nothing of the
+ *   context is used but its device, no XRGB32 copy of the scaled clip exists.  Where dst_w % 16 == 0 and every plane starts on
+ *   a 16-byte boundary a lane forms 16 target pixels of a row and stores them per plane with 16-byte stores; any other target
+ *   is written element by element, to the same bytes.  Nothing outside the n_frames target frames is written.
+ * agmv_hip_tensor_to_xrgb_async (the encoder's source): d_src holds n_frames tensor frames of frame_pixels pixels; d_dst
+ *   receives frame_pixels words 0x00RRGGBB per frame by the reading rule of include/agmv.h: an element x, converted exactly to
+ *   float32, gives t = fl32(fl32(x * a[c]) + b[c]) -- two separately rounded operations, never fused -- and the byte 0 for a
+ *   NaN, else (int)rintf(fminf(fmaxf(t, 0), 255)), rounding half to even.  `ab` is host memory, a[3] then b[3], read before
+ *   the call returns.  One launch, asynchronous on `stream`, 16-byte loads and stores where every plane and every target
+ *   frame starts on a 16-byte boundary, element by element otherwise, with the same result.
+ * The two asynchronous calls: n_frames == 0 is success and launches nothing; a NULL pointer, an unknown type or filter, a zero
+ * or oversize shape (more than 2^28 pixels) or a pointer that is not aligned to its element returns non-zero with a message and
+ * launches nothing. */
+size_t agmv_hip_tensor_frame_bytes(int type, size_t n_pixels);
+int agmv_hip_tensor_table(int type, const float* mean /* [3] */, const float* std /* [3] */, void* table /* host, 768 elements */);
+int agmv_hip_tensor_from_xrgb_async(agmv_hip_ctx* ctx, int type, const uint32_t* d_src, uint32_t src_w, uint32_t src_h,
+                                    uint32_t n_frames, int filter, uint32_t dst_w, uint32_t dst_h, const void* d_table, void* d_dst,
+                                    void* stream);
+int agmv_hip_tensor_to_xrgb_async(agmv_hip_ctx* ctx, int type, const void* d_src, size_t frame_pixels, uint32_t n_frames,
+                                  const float* ab /* host: a[3] then b[3] */, uint32_t* d_dst, void* stream);
+
 /* -- the palette refined by weighted k-means ------------------------------------------------------
  * The refinement of include/agmv.h ("palette refinement"), which holds the definition: Lloyd's algorithm over the points of a
  * histogram, in exact integers.

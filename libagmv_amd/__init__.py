@@ -5,21 +5,21 @@ Layout
                       C-ABI of include/agmv_hip.h (context, palette, streams, memory)
   csrc/agmv_decode_hip.hip  the decoder: the parsers, k_decode, k_fixup and the calls of that C-ABI that launch them
   csrc/agmv_clip_hip.hip  the clip front end of that C-ABI: synth, interp, histogram, similarity, gather, the byte and
-                      YUV 4:2:0 layouts, the area scale, the decoder's scaling sink
+                      YUV 4:2:0 layouts, the area scale, the decoder's scaling sink, normalised float tensors
   csrc/agmv_lz*_hip.hip   the LZSS / LZ77 stages of encoder and decoder on the GPU
   csrc/agmv_audio_hip.hip  audio tracks: the compand / expand kernels (csrc/agmv_audio.h states the codec once, for host and device)
   csrc/*.c            host C: libagmv-compatible API (include/agmv.h), LZSS/LZ77, container,
                       BMP I/O, palette build, synthetic clip generator
   hip.py              ctypes binding of the C-ABI for tests / bench (torch = device memory only)
-  seq.py              ctypes calls of the memory-sequence entry points of include/agmv.h (.agmv file <-> CUDA tensor: five RGB layouts, NV12, I420; a scale to a target size before the encode and behind the decode; a decoded clip or file measured against its reference)
+  seq.py              ctypes calls of the memory-sequence entry points of include/agmv.h (.agmv file <-> CUDA tensor: five RGB layouts, NV12, I420; normalised float tensors; a scale to a target size before the encode and behind the decode; a decoded clip or file measured against its reference)
   build.py            in-tree build of libagmv_hip.so / libagmv.so (hipcc, gcc)
 
 There is no CPU fallback anywhere in this package: without the built HIP library, or
 without a GPU, the hot-path calls raise.
 """
-from .hip import PCMFMT, PIXFMT, YUVFMT, AgmvHip, HipUnavailable, lib_path, load_library  # noqa: F401
+from .hip import PCMFMT, PIXFMT, TENSORFMT, YUVFMT, AgmvHip, HipUnavailable, lib_path, load_library  # noqa: F401
 from .seq import DECODE_SCALE, SCALE, SCHEDULE_ADAPTIVE, SCHEDULE_FULL, SCHEDULE_PDIFS, Quality, clip_quality, decode_audio, decode_frames, encode_frames, file_quality  # noqa: F401
 
 __all__ = ["AgmvHip", "HipUnavailable", "lib_path", "load_library", "encode_frames", "decode_frames", "decode_audio",
            "clip_quality", "file_quality", "Quality",
-           "SCHEDULE_FULL", "SCHEDULE_PDIFS", "SCHEDULE_ADAPTIVE", "PIXFMT", "YUVFMT", "PCMFMT", "SCALE", "DECODE_SCALE"]
+           "SCHEDULE_FULL", "SCHEDULE_PDIFS", "SCHEDULE_ADAPTIVE", "PIXFMT", "YUVFMT", "PCMFMT", "TENSORFMT", "SCALE", "DECODE_SCALE"]

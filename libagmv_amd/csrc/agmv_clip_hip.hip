@@ -10,12 +10,15 @@
 //   k_scale_area              the exact box-filter downscale of a clip in any of the seven layouts
 //   k_scale_up*               a decoded XRGB32 clip written at a target size, nearest or bilinear, in any of the seven layouts
 //   k_measure                 a decoded XRGB32 clip against its reference in any of the seven layouts: SSE, block-mean SSE, SSIM
+//   k_scale_up* <PF_T32/16>   ... or as a normalised float tensor clip (a table look-up per channel);  k_tensor_to_xrgb  the way back
 // Each family has an XRGB32 form, one for the byte layouts (PF_RGB24 .. PF_RGB8P) and one templated on the YUV layout; on the
 // host CLIP_LAUNCH is the one place where a format value becomes a kernel's template argument.
-// Integer/byte work only; every kernel is an HBM stream, except k_measure, which its divisions and moments bind.
+// Integer/byte work only (k_tensor_to_xrgb: two float32 operations per element); every kernel is an HBM stream, except k_measure,
+// which its divisions and moments bind.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
+#include <string.h>
 
 #include <type_traits>
 
@@ -968,7 +971,23 @@ struct UpArgs {
 	int small;
 	up_axis x, y;
 	yuv_wr m;
+	const void* table;                                             // PF_T32 / PF_T16: the 3 x 256 elements of agmv_hip_tensor_table, device memory
 };
+
+// ---- the target as a normalised float tensor clip (AGMV_TENSORFMT of include/agmv.h, which holds the definition) ----
+// A frame is three planes [h][w] of elements R, G, B.  The writer computes nothing: element = T[c][channel c of the pixel], and the
+// table holds the element type's bit patterns, so the only template axis is the element's size -- PF_T32 (AGMV_TENSOR_F32) or
+// PF_T16 (AGMV_TENSOR_F16 and _BF16).  Every workgroup copies the 768 elements to LDS first.
+#define PF_T32 32
+#define PF_T16 33
+template <int FMT> using ten_elem = std::conditional_t<FMT == PF_T16, uint16_t, uint32_t>;
+
+// (every thread of the workgroup calls it, before any of them returns)
+template <int FMT> __device__ __forceinline__ void ten_table_to_lds(ten_elem<FMT>* __restrict__ s_tab, const void* __restrict__ table)
+{
+	for (uint32_t k = threadIdx.x; k < 768; k += 256) s_tab[k] = static_cast<const ten_elem<FMT>*>(table)[k];
+	__syncthreads();
+}
 
 template <bool BIL> __device__ __forceinline__ up_tap up_tap_at(const up_axis& a, uint32_t X, int small)
 {
@@ -1033,7 +1052,9 @@ template <bool BIL> __device__ __forceinline__ uint32_t up_sample(const uint32_t
 
 template <int FMT, bool BIL> __global__ __launch_bounds__(256) void k_scale_up_wide(UpArgs A)
 {
-	constexpr bool YUV = FMT >= PF_NV12;
+	constexpr bool YUV = FMT == PF_NV12 || FMT == PF_I420, TEN = FMT >= PF_T32;
+	__shared__ ten_elem<FMT> s_tab[TEN ? 768 : 1];
+	if constexpr (TEN) ten_table_to_lds<FMT>(s_tab, A.table);
 	const uint32_t f = blockIdx.x / A.bpf, g = (blockIdx.x - f * A.bpf) * 256 + threadIdx.x, band = g / A.gpr;
 	if (band >= A.rows) return;
 	const uint32_t dw = A.x.d, dh = A.y.d, sw = A.x.s, X0 = (g - band * A.gpr) * 16, Y0 = band * UP_BAND, Y1 = min(Y0 + UP_BAND, dh);
@@ -1095,6 +1116,24 @@ template <int FMT, bool BIL> __global__ __launch_bounds__(256) void k_scale_up_w
 		} else if constexpr (FMT == PF_XRGB32) {
 #pragma unroll
 			for (int j = 0; j < 4; j++) *reinterpret_cast<pf_u32x4*>(fr + 4 * ((size_t)Y * dw + X0) + 16 * j) = px[j];
+		} else if constexpr (TEN) {                                // plane by plane: 16 elements are 64 (32) bytes, four (two) stores
+			const size_t npx = (size_t)dw * dh;
+			ten_elem<FMT>* o = reinterpret_cast<ten_elem<FMT>*>(fr) + (size_t)Y * dw + X0;
+#pragma unroll
+			for (int c = 0; c < 3; c++) {
+				const ten_elem<FMT>* t = s_tab + 256 * c;
+				const int sh = 16 - 8 * c;
+#pragma unroll
+				for (int j = 0; j < (FMT == PF_T32 ? 4 : 2); j++) {
+					pf_u32x4 v;
+#pragma unroll
+					for (int i = 0; i < 4; i++) {
+						if constexpr (FMT == PF_T32) v[i] = t[(px[j][i] >> sh) & 0xffu];
+						else v[i] = (uint32_t)t[(px[2 * j + (i >> 1)][2 * (i & 1)] >> sh) & 0xffu] | (uint32_t)t[(px[2 * j + (i >> 1)][2 * (i & 1) + 1] >> sh) & 0xffu] << 16;
+					}
+					*reinterpret_cast<pf_u32x4*>(reinterpret_cast<uint8_t*>(o + (size_t)c * npx) + 16 * j) = v;
+				}
+			}
 		} else {
 			const size_t npx = (size_t)dw * dh, p = (size_t)Y * dw + X0;
 			const pf_raw<FMT> r = pf_pack16<FMT>(px);
@@ -1109,7 +1148,9 @@ template <int FMT, bool BIL> __global__ __launch_bounds__(256) void k_scale_up_w
 // column pair, each with the chroma sample of the up to 2 x 2 pixels that exist).
 template <int FMT, bool BIL> __global__ __launch_bounds__(256) void k_scale_up(UpArgs A)
 {
-	constexpr bool YUV = FMT >= PF_NV12;
+	constexpr bool YUV = FMT == PF_NV12 || FMT == PF_I420, TEN = FMT >= PF_T32;
+	__shared__ ten_elem<FMT> s_tab[TEN ? 768 : 1];
+	if constexpr (TEN) ten_table_to_lds<FMT>(s_tab, A.table);
 	const uint32_t f = blockIdx.x / A.bpf, g = (blockIdx.x - f * A.bpf) * 256 + threadIdx.x, ry = g / A.gpr;
 	if (ry >= A.rows) return;
 	const uint32_t dw = A.x.d, dh = A.y.d, sw = A.x.s, X0 = (g - ry * A.gpr) * 16, Y0 = YUV ? 2 * ry : ry;
@@ -1150,8 +1191,86 @@ template <int FMT, bool BIL> __global__ __launch_bounds__(256) void k_scale_up(U
 			const uint32_t c = up_sample<BIL>(a0, a1, up_resolve<BIL>(A.x, tx), ya.f);
 			up_tap_step<BIL>(A.x, tx);
 			if constexpr (FMT == PF_XRGB32) reinterpret_cast<uint32_t*>(fr)[(size_t)Y0 * dw + X] = c;
-			else pf_write(FMT, fr, npx, (size_t)Y0 * dw + X, c);
+			else if constexpr (TEN) {
+				ten_elem<FMT>* o = reinterpret_cast<ten_elem<FMT>*>(fr) + (size_t)Y0 * dw + X;
+				o[0] = s_tab[(c >> 16) & 0xffu]; o[npx] = s_tab[256 + ((c >> 8) & 0xffu)]; o[2 * npx] = s_tab[512 + (c & 0xffu)];
+			} else pf_write(FMT, fr, npx, (size_t)Y0 * dw + X, c);
 		}
+	}
+}
+
+// ---- a normalised float tensor clip read as XRGB32 (the reading rule of include/agmv.h: AGMV_TENSORFMT) ----
+// An HBM stream: 12 (6) bytes in, 4 out per pixel.  A lane owns 8 consecutive pixels: per plane two (one) 16-byte loads, then two
+// 16-byte stores, where every plane and every target frame starts on a 16-byte boundary (`vec`; that makes frame_pixels a
+// multiple of 4 resp. 8); the frame's last partial group, and every pixel of any other clip, goes element by element.
+#define TEN_F32 1
+#define TEN_F16 2
+#define TEN_BF16 3
+struct ten_ab { float a[3], b[3]; };
+
+// the element's bit pattern as the float32 of the same value, in integers: no conversion mode can touch it
+template <int TYPE> __device__ __forceinline__ float ten_f32(uint32_t u)
+{
+	if (TYPE == TEN_F32) return __uint_as_float(u);
+	if (TYPE == TEN_BF16) return __uint_as_float(u << 16);
+	const uint32_t s = (u & 0x8000u) << 16, e = (u >> 10) & 31u, m = u & 0x3ffu;
+	if (e == 0) return __uint_as_float(s | __float_as_uint((float)m * 0x1p-24f));      // m * 2^-24 is exact and a normal float32
+	return __uint_as_float(s | (e == 31 ? 0x7f800000u : (e + 112) << 23) | m << 13);
+}
+
+// two separately rounded operations (never an fma), NaN = 0, round half to even
+__device__ __forceinline__ uint32_t ten_byte(float x, float a, float b)
+{
+	const float t = __fadd_rn(__fmul_rn(x, a), b);
+	return t != t ? 0u : (uint32_t)(int)rintf(fminf(fmaxf(t, 0.0f), 255.0f));
+}
+
+template <int TYPE> __device__ __forceinline__ uint32_t ten_read(const uint8_t* __restrict__ fr, size_t npx, size_t k, const ten_ab& ab)
+{
+	uint32_t x = 0;
+#pragma unroll
+	for (int c = 0; c < 3; c++) {
+		const size_t i = (size_t)c * npx + k;
+		const uint32_t u = TYPE == TEN_F32 ? reinterpret_cast<const uint32_t*>(fr)[i] : reinterpret_cast<const uint16_t*>(fr)[i];
+		x = x << 8 | ten_byte(ten_f32<TYPE>(u), ab.a[c], ab.b[c]);
+	}
+	return x;
+}
+
+template <int TYPE> __global__ __launch_bounds__(256) void k_tensor_to_xrgb(const uint8_t* __restrict__ src, size_t npx, uint32_t bpf, int vec, ten_ab ab,
+                                                                           uint32_t* __restrict__ dst)
+{
+	constexpr int ES = TYPE == TEN_F32 ? 4 : 2;
+	const uint32_t f = blockIdx.x / bpf;
+	const size_t g = (size_t)(blockIdx.x - f * bpf) * 256 + threadIdx.x, p = g * 8;
+	const uint8_t* fr = src + (size_t)f * 3 * ES * npx;
+	uint32_t* out = dst + (size_t)f * npx;
+	if (vec && p + 8 <= npx) {
+		uint32_t x[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			const pf_u32x4* a = reinterpret_cast<const pf_u32x4*>(fr + ((size_t)c * npx + p) * ES);
+			const pf_u32x4 lo = __builtin_nontemporal_load(a);
+			pf_u32x4 hi = 0;
+			if (TYPE == TEN_F32) hi = __builtin_nontemporal_load(a + 1);
+#pragma unroll
+			for (int i = 0; i < 8; i++) {
+				const uint32_t u = TYPE == TEN_F32 ? (i < 4 ? lo[i & 3] : hi[i & 3]) : (lo[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+				x[i] = x[i] << 8 | ten_byte(ten_f32<TYPE>(u), ab.a[c], ab.b[c]);
+			}
+		}
+#pragma unroll
+		for (int j = 0; j < 2; j++) {
+			pf_u32x4 o;
+#pragma unroll
+			for (int i = 0; i < 4; i++) o[i] = x[4 * j + i];
+			*reinterpret_cast<pf_u32x4*>(out + p + 4 * j) = o;
+		}
+	} else if (vec) {                                                  // the last, partial group of the frame
+		for (int i = 0; i < 8; i++) if (p + i < npx) out[p + i] = ten_read<TYPE>(fr, npx, p + i, ab);
+	} else {                                                           // lanes on consecutive pixels: the wave's 512, 64 at a time
+		const size_t w0 = (g & ~(size_t)63) * 8 + (threadIdx.x & 63);
+		for (int i = 0; i < 8; i++) if (w0 + 64 * i < npx) out[w0 + 64 * i] = ten_read<TYPE>(fr, npx, w0 + 64 * i, ab);
 	}
 }
 
@@ -1659,6 +1778,21 @@ static up_axis up_axis_of(uint32_t s, uint32_t d)
 // (2X + 1) * s + d for every X < d, and 256 * r + d for every r < 2d, fit 32 bits
 static int up_small(uint32_t s, uint32_t d) { return (2ull * d - 1) * s + d < (1ull << 32) && 513ull * d < (1ull << 32); }
 
+// what the four scaling kernels share: the grid (wide: bands of 16 columns; else rows, or YUV row pairs) and the taps of both axes
+static int up_geometry(UpArgs& A, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, uint32_t n_frames, int wide, int yuv, unsigned* blocks)
+{
+	A.gpr = (dst_w + 15) >> 4; A.rows = wide ? (dst_h + UP_BAND - 1) / UP_BAND : yuv ? (dst_h + 1) >> 1 : dst_h;
+	A.small = up_small(src_w, dst_w) && up_small(src_h, dst_h);
+	A.x = up_axis_of(src_w, dst_w); A.y = up_axis_of(src_h, dst_h);
+	return clip_grid(((size_t)A.gpr * A.rows + 255) / 256, n_frames, &A.bpf, blocks);
+}
+
+template <int L> static void up_launch(int wide, bool bilinear, unsigned blocks, const UpArgs& A, void* stream)
+{
+	auto k = wide ? (bilinear ? k_scale_up_wide<L, true> : k_scale_up_wide<L, false>) : (bilinear ? k_scale_up<L, true> : k_scale_up<L, false>);
+	hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, A);
+}
+
 extern "C" int agmv_hip_scale_frames_async(agmv_hip_ctx* c, int filter, const uint32_t* d_src, uint32_t src_w, uint32_t src_h, uint32_t n_frames, int fmt,
                                            uint32_t dst_w, uint32_t dst_h, void* d_dst, void* stream)
 {
@@ -1673,21 +1807,105 @@ extern "C" int agmv_hip_scale_frames_async(agmv_hip_ctx* c, int filter, const ui
 	if ((uintptr_t)d_src & 3 || (fmt == PF_XRGB32 && ((uintptr_t)d_dst & 3))) return agmv_hip_err("agmv_hip: an XRGB32 clip needs 4-byte alignment");
 	if (n_frames == 0) return 0;
 	UpArgs A;
-	A.src = d_src; A.dst = (uint8_t*)d_dst;
+	A.src = d_src; A.dst = (uint8_t*)d_dst; A.table = nullptr;
 	A.frame_bytes = clip_frame_bytes(fmt, dst_w, dst_h);
 	const int wide = yuv ? (dst_h & 1) == 0 && yuv_wide(fmt, d_dst, dst_w, dst_h, n_frames)
 	                     : (dst_w & 15) == 0 && pf_aligned(fmt, d_dst, (size_t)dst_w * dst_h, n_frames);
-	A.gpr = (dst_w + 15) >> 4; A.rows = wide ? (dst_h + UP_BAND - 1) / UP_BAND : yuv ? (dst_h + 1) >> 1 : dst_h;
-	A.small = up_small(src_w, dst_w) && up_small(src_h, dst_h);
-	A.x = up_axis_of(src_w, dst_w); A.y = up_axis_of(src_h, dst_h);
 	A.m = YUV_WR[(fmt >> 8) & 3];
 	unsigned blocks;
-	if (clip_grid(((size_t)A.gpr * A.rows + 255) / 256, n_frames, &A.bpf, &blocks)) return -1;
-	clip_dispatch<PF_BYTES | PF_YUV | PF_BIT(PF_XRGB32)>(fmt, [&](auto F) {
-		constexpr int L = decltype(F)::value;
-		auto k = wide ? (filter == 3 ? k_scale_up_wide<L, true> : k_scale_up_wide<L, false>) : (filter == 3 ? k_scale_up<L, true> : k_scale_up<L, false>);
-		hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, A);
-	});
+	if (up_geometry(A, src_w, src_h, dst_w, dst_h, n_frames, wide, yuv, &blocks)) return -1;
+	clip_dispatch<PF_BYTES | PF_YUV | PF_BIT(PF_XRGB32)>(fmt, [&](auto F) { up_launch<decltype(F)::value>(wide, filter == 3, blocks, A, stream); });
+	CK(hipGetLastError());
+	return 0;
+}
+
+// ---- normalised float tensor clips (AGMV_TENSORFMT of include/agmv.h): the table, the decoder's sink, the encoder's source ----
+static int ten_elem_bytes(int type) { return type == TEN_F32 ? 4 : type == TEN_F16 || type == TEN_BF16 ? 2 : 0; }
+
+extern "C" size_t agmv_hip_tensor_frame_bytes(int type, size_t n_pixels) { return 3 * (size_t)ten_elem_bytes(type) * n_pixels; }
+
+// a float32's bit pattern rounded to nearest-even into binary16, overflow = infinity; integers only
+static uint16_t ten_f16_bits(uint32_t u)
+{
+	const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;
+	if (a > 0x7F800000u) return (uint16_t)(sign | 0x7E00u);                      // NaN (no table entry is one)
+	if (a >= 0x38800000u) {                                                     // 2^-14 and above: a normal binary16, or infinity
+		const uint32_t r = a - 0x38000000u, h = (r + 0xFFFu + ((r >> 13) & 1u)) >> 13;
+		return (uint16_t)(sign | (h < 0x7C00u ? h : 0x7C00u));
+	}
+	if (a < 0x33000000u) return (uint16_t)sign;                                 // below 2^-25: 0
+	const uint32_t m = (a & 0x7FFFFFu) | 0x800000u, shift = 126u - (a >> 23);      // the value is m * 2^-24 >> shift, shift 14 .. 24
+	const uint32_t h = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+	return (uint16_t)(sign | (h + (rem > half || (rem == half && (h & 1u)) ? 1u : 0u)));
+}
+
+static uint16_t ten_bf16_bits(uint32_t u) { return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); }
+
+extern "C" int agmv_hip_tensor_table(int type, const float mean[3], const float std[3], void* table)
+{
+	if (!ten_elem_bytes(type)) return agmv_hip_err("agmv_hip: unknown tensor type %d", type);
+	if (!mean || !std || !table) return agmv_hip_err("agmv_hip: NULL normalisation or table");
+	for (int c = 0; c < 3; c++) {                                               // (a NaN fails every comparison)
+		const double m = mean[c] < 0 ? -(double)mean[c] : (double)mean[c], s = std[c] < 0 ? -(double)std[c] : (double)std[c];
+		if (!(s >= 0x1p-32 && s <= 0x1p32 && m <= 0x1p32))
+			return agmv_hip_err("agmv_hip: normalisation of channel %d outside the bounds (2^-32 <= |std| <= 2^32, |mean| <= 2^32)", c);
+	}
+	for (int c = 0; c < 3; c++)
+		for (int v = 0; v < 256; v++) {
+			const float f = (float)(((double)v / 255.0 - (double)mean[c]) / (double)std[c]);
+			uint32_t u;
+			memcpy(&u, &f, 4);
+			if (type == TEN_F32) static_cast<uint32_t*>(table)[256 * c + v] = u;
+			else static_cast<uint16_t*>(table)[256 * c + v] = type == TEN_F16 ? ten_f16_bits(u) : ten_bf16_bits(u);
+		}
+	return 0;
+}
+
+extern "C" int agmv_hip_tensor_from_xrgb_async(agmv_hip_ctx* c, int type, const uint32_t* d_src, uint32_t src_w, uint32_t src_h, uint32_t n_frames, int filter,
+                                               uint32_t dst_w, uint32_t dst_h, const void* d_table, void* d_dst, void* stream)
+{
+	if (agmv_hip_enter(c)) return -1;
+	const int es = ten_elem_bytes(type);
+	if (!es) return agmv_hip_err("agmv_hip: unknown tensor type %d", type);
+	if (filter == 2) return agmv_hip_err("agmv_hip: the area filter is agmv_hip_scale_area_dev's, not agmv_hip_tensor_from_xrgb_async's");
+	if (filter != 0 && filter != 1 && filter != 3) return agmv_hip_err("agmv_hip: unknown scale filter %d", filter);
+	if (src_w == 0 || src_h == 0 || dst_w == 0 || dst_h == 0 || (unsigned long long)src_w * src_h > (1ull << 28) || (unsigned long long)dst_w * dst_h > (1ull << 28))
+		return agmv_hip_err("agmv_hip: a tensor clip of %u x %u from frames of %u x %u (non-zero sizes of at most 2^28 pixels are needed)", dst_w, dst_h, src_w, src_h);
+	if (filter == 0 && (src_w != dst_w || src_h != dst_h)) return agmv_hip_err("agmv_hip: filter 0 does not scale: %u x %u to %u x %u", src_w, src_h, dst_w, dst_h);
+	if (!d_src || !d_table || !d_dst) return agmv_hip_err("agmv_hip: NULL clip or table");
+	if ((uintptr_t)d_src & 3 || ((uintptr_t)d_table | (uintptr_t)d_dst) & (uintptr_t)(es - 1))
+		return agmv_hip_err("agmv_hip: an XRGB32 clip needs 4-byte alignment, a tensor clip and its table that of their element");
+	if (n_frames == 0) return 0;
+	UpArgs A;
+	A.src = d_src; A.dst = (uint8_t*)d_dst; A.table = d_table;
+	A.frame_bytes = 3 * (size_t)es * dst_w * dst_h;
+	A.m = YUV_WR[0];
+	const int wide = (dst_w & 15) == 0 && ((uintptr_t)d_dst & 15) == 0;            // then every plane is a multiple of 32 bytes
+	unsigned blocks;
+	if (up_geometry(A, src_w, src_h, dst_w, dst_h, n_frames, wide, 0, &blocks)) return -1;
+	if (es == 4) up_launch<PF_T32>(wide, filter == 3, blocks, A, stream);       // (filter 0 is the nearest scale to the same size: the identity)
+	else up_launch<PF_T16>(wide, filter == 3, blocks, A, stream);
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_tensor_to_xrgb_async(agmv_hip_ctx* c, int type, const void* d_src, size_t frame_pixels, uint32_t n_frames, const float* ab, uint32_t* d_dst,
+                                             void* stream)
+{
+	if (agmv_hip_enter(c)) return -1;
+	const int es = ten_elem_bytes(type);
+	if (!es) return agmv_hip_err("agmv_hip: unknown tensor type %d", type);
+	if (frame_pixels == 0 || frame_pixels > ((size_t)1 << 28)) return agmv_hip_err("agmv_hip: tensor frames of %zu pixels (1 .. 2^28 are needed)", frame_pixels);
+	if (!d_src || !ab || !d_dst) return agmv_hip_err("agmv_hip: NULL clip or coefficients");
+	if ((uintptr_t)d_src & (uintptr_t)(es - 1) || (uintptr_t)d_dst & 3) return agmv_hip_err("agmv_hip: a tensor clip needs the alignment of its element, an XRGB32 clip 4 bytes");
+	if (n_frames == 0) return 0;
+	uint32_t bpf; unsigned blocks;
+	if (clip_grid((frame_pixels + 2047) / 2048, n_frames, &bpf, &blocks)) return -1;
+	const int vec = (((uintptr_t)d_src | (uintptr_t)d_dst) & 15) == 0 && (frame_pixels * es & 15) == 0;
+	ten_ab k;
+	for (int i = 0; i < 3; i++) { k.a[i] = ab[i]; k.b[i] = ab[3 + i]; }
+	auto kernel = type == TEN_F32 ? k_tensor_to_xrgb<TEN_F32> : type == TEN_F16 ? k_tensor_to_xrgb<TEN_F16> : k_tensor_to_xrgb<TEN_BF16>;
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_src, frame_pixels, bpf, vec, k, d_dst);
 	CK(hipGetLastError());
 	return 0;
 }

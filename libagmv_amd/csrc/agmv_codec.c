@@ -776,14 +776,13 @@ static void attach_audio_dev(AGMV* a)
    device of this library's context.  What the BMP drivers write for f1.bmp .. f<n>.bmp holding these frames, byte for byte (for
    AGMV_SCHEDULE_ADAPTIVE with AGMV_EncodeVideo's CreateAGMV(n - 1, ...)); GBA_GEN_AGMV.h is not written.  Returns 0, or a
    negative value -- before any file is created -- for arguments that cannot be encoded. */
-static int encode_frames_dev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 width, u32 height,
-                             u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+/* what AGMV_EncodeFramesDev refuses, in its order: 0, or the negative value; needs no device */
+static int encode_frames_refused(const char* filename, const void* d_frames, u32 num_of_frames, u32 width, u32 height, AGMV_OPT opt, AGMV_QUALITY quality,
+                                 AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
 {
-	agmv_source src;
-	AGMV* a;
 	int sw, sh;
 	u32 least;
-	if (!known_pixfmt((int)fmt) || !filename || !d_frames) return -1;
+	if (!filename || !d_frames) return -1;
 	if (opt < AGMV_OPT_I || opt > AGMV_OPT_NDS || quality < AGMV_HIGH_QUALITY || quality > AGMV_LOW_QUALITY ||
 	    (compression != AGMV_LZSS_COMPRESSION && compression != AGMV_LZ77_COMPRESSION) ||
 	    (schedule != AGMV_SCHEDULE_FULL && schedule != AGMV_SCHEDULE_PDIFS && schedule != AGMV_SCHEDULE_ADAPTIVE))
@@ -796,6 +795,16 @@ static int encode_frames_dev(const char* filename, const void* d_frames, AGMV_PI
 	if (width == 0 || height == 0 || (unsigned long long)width * height > (1ull << 28)) return -3;
 	if (!sw && bad_geometry((uint32_t)width, (uint32_t)height)) return -3;
 	if (sw && (width < 2 || height < 2)) return -3;
+	return 0;
+}
+
+static int encode_frames_dev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 width, u32 height,
+                             u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+{
+	agmv_source src;
+	AGMV* a;
+	const int refused = known_pixfmt((int)fmt) ? encode_frames_refused(filename, d_frames, num_of_frames, width, height, opt, quality, compression, schedule) : -1;
+	if (refused) return refused;
 	memset(&src, 0, sizeof(src));
 	src.d_frames = d_frames; src.fmt = (int)fmt; src.src_w = (uint32_t)width; src.src_h = (uint32_t)height;
 	src.n_frames = (uint32_t)num_of_frames; src.first = 1; src.device = agmv_hip_ctx_device(ctx());
@@ -878,6 +887,52 @@ int AGMV_EncodeFramesScaledDev(const char* filename, const void* d_frames, AGMV_
 {
 	const int rc = encode_frames_scaled_dev(filename, d_frames, fmt, num_of_frames, src_width, src_height, width, height, filter, frames_per_second, opt,
 	                                        quality, compression, schedule);
+	memset(&g_audio, 0, sizeof(g_audio));
+	return rc;
+}
+
+/* a normalisation the tensor entry points take: agmv_hip_tensor_table holds the bounds (and needs no device) */
+static int known_tensor(AGMV_TENSORFMT type, const float mean[3], const float std[3], void* table)
+{
+	return mean && std && agmv_hip_tensor_table((int)type, mean, std, table) == 0;
+}
+
+/* A tensor clip (include/agmv.h, "normalised float tensors"): the XRGB32 clip its reading rule gives is materialised once on the
+   library's device, as encode_frames_scaled_dev materialises D, and AGMV_EncodeFramesDev runs on it. */
+static int encode_frames_tensor_dev(const char* filename, const void* d_tensor, AGMV_TENSORFMT type, const float mean[3], const float std[3], u32 num_of_frames,
+                                    u32 width, u32 height, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression,
+                                    AGMV_SCHEDULE schedule)
+{
+	agmv_hip_ctx* c;
+	void* stream;
+	uint32_t table[768], *d_clip;
+	float ab[6];
+	size_t npx;
+	int i, rc;
+	if (!known_tensor(type, mean, std, table)) return -1;
+	rc = encode_frames_refused(filename, d_tensor, num_of_frames, width, height, opt, quality, compression, schedule);
+	if (rc) return rc;
+	for (i = 0; i < 3; i++) { ab[i] = (float)(255.0 * (double)std[i]); ab[3 + i] = (float)(255.0 * (double)mean[i]); }
+	c = ctx();
+	npx = (size_t)width * height;
+	d_clip = (uint32_t*)agmv_hip_malloc_on(c, 4 * npx * num_of_frames);
+	if (!d_clip) return -4;
+	stream = agmv_hip_stream_create(c);
+	if (!stream) agmv_die("stream for the tensor clip");
+	if (agmv_hip_tensor_to_xrgb_async(c, (int)type, d_tensor, npx, (uint32_t)num_of_frames, ab, d_clip, stream) || agmv_hip_stream_sync(c, stream))
+		agmv_die("tensor clip");
+	agmv_hip_stream_destroy(c, stream);
+	rc = encode_frames_dev(filename, d_clip, AGMV_PIXFMT_XRGB32, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule);
+	agmv_hip_free_on(c, d_clip);
+	return rc;
+}
+
+int AGMV_EncodeFramesTensorDev(const char* filename, const void* d_tensor, AGMV_TENSORFMT type, const float mean[3], const float std[3], u32 num_of_frames,
+                               u32 width, u32 height, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression,
+                               AGMV_SCHEDULE schedule)
+{
+	const int rc = encode_frames_tensor_dev(filename, d_tensor, type, mean, std, num_of_frames, width, height, frames_per_second, opt, quality, compression,
+	                                        schedule);
 	memset(&g_audio, 0, sizeof(g_audio));
 	return rc;
 }
@@ -989,8 +1044,26 @@ int AGMV_DecodeFramesScaledDev(const char* filename, void* d_frames, AGMV_PIXFMT
 	int err;
 	if (!filename || !known_pixfmt((int)fmt) || (filter != AGMV_SCALE_NEAREST && filter != AGMV_SCALE_AREA && filter != AGMV_SCALE_BILINEAR)) return -1;
 	if (width == 0 || height == 0 || width > (1ul << 28) || height > (1ul << 28) || (unsigned long long)width * height > (1ull << 28)) return -4;
-	sc.w = (uint32_t)width; sc.h = (uint32_t)height; sc.filter = (int)filter;
+	sc.w = (uint32_t)width; sc.h = (uint32_t)height; sc.filter = (int)filter; sc.tensor = 0; sc.table = NULL;
 	err = decode_file(filename, AGMV_IMG_BMP, d_frames, (int)fmt, &sc, NULL, cap_frames, d_frames == NULL, info, &decoded);
+	return err == NO_ERR ? (int)decoded : err < 0 ? err : -err;
+}
+
+/* AGMV_DecodeFramesScaledDev into a tensor clip (include/agmv.h, "normalised float tensors"): the same checks in the same order,
+   the table built here and uploaded once by the sink; width == height == 0 is the file's size, without a filter. */
+int AGMV_DecodeFramesTensorDev(const char* filename, void* d_tensor, AGMV_TENSORFMT type, const float mean[3], const float std[3], u32 width, u32 height,
+                               AGMV_SCALE filter, u32 cap_frames, AGMV_INFO* info)
+{
+	unsigned long decoded = 0;
+	uint32_t table[768];
+	agmv_scale sc;
+	const int sized = width != 0 || height != 0;
+	int err;
+	if (!filename || !known_tensor(type, mean, std, table)) return -1;
+	if (sized && filter != AGMV_SCALE_NEAREST && filter != AGMV_SCALE_AREA && filter != AGMV_SCALE_BILINEAR) return -1;
+	if (sized && (width == 0 || height == 0 || width > (1ul << 28) || height > (1ul << 28) || (unsigned long long)width * height > (1ull << 28))) return -4;
+	sc.w = (uint32_t)width; sc.h = (uint32_t)height; sc.filter = sized ? (int)filter : 0; sc.tensor = (int)type; sc.table = table;
+	err = decode_file(filename, AGMV_IMG_BMP, d_tensor, AGMV_PIXFMT_XRGB32, &sc, NULL, cap_frames, d_tensor == NULL, info, &decoded);
 	return err == NO_ERR ? (int)decoded : err < 0 ? err : -err;
 }
 

@@ -814,7 +814,9 @@ typedef struct dpipe {
 	int fmt;                               /* ... in this AGMV_PIXFMT: XRGB32 is decoded in place, any other through d_out */
 	void* d_quality;                       /* the measuring sink: d_dst is the reference clip, only read; frame k's AGMV_FRAME_QUALITY lands here */
 	agmv_scale scale;                      /* filter != 0: the sink holds frames of scale.w x scale.h; the batch always goes through d_out */
+	                                       /* tensor != 0: ... as a tensor clip of that type (filter 0: at the file's size, which w, h then hold) */
 	uint32_t* d_scaled;                    /* AGMV_SCALE_AREA into another layout than XRGB32: one batch of scaled XRGB32 frames */
+	void* d_table;                         /* the tensor sink's table on the device, uploaded once per call */
 } dpipe;
 
 typedef struct savearg { dpipe* d; dbatch* b; unsigned k; } savearg;
@@ -852,7 +854,7 @@ static void* dworker_main(void* p)
 		/* with a packed sink the batch is decoded straight into its place, and the frame before it is the one before it there;
 		   a sink in another layout or at another size, and the measuring sink, take the batch from the double buffer, where the
 		   decoder's state stays (at the file's size) */
-		const int direct = d->d_dst && !d->d_quality && !d->scale.filter && d->fmt == AGMV_PIXFMT_XRGB32;
+		const int direct = d->d_dst && !d->d_quality && !d->scale.filter && !d->scale.tensor && d->fmt == AGMV_PIXFMT_XRGB32;
 		out = direct ? (uint32_t*)d->d_dst + (size_t)b->first * d->npx : d->d_out[id & 1];
 		prev = !have_state ? NULL : direct ? out - d->npx : d->d_out[(id - 1) & 1] + (size_t)(prev_n - 1) * d->npx;
 		if (b->d_slab) {                       /* the LZ stage left the rows on the device: wait for their commit, on the device */
@@ -868,7 +870,15 @@ static void* dworker_main(void* p)
 		for (k = 0; k < b->n; k++) if (((b->first + k) & 3u) == 0) last_i = (int)k;
 		if (!have_state && last_i < 0 && agmv_hip_memset_async(d->ctx, d->d_iframe, 0, d->npx * 4, d->stream)) goto fail;
 		if (last_i >= 0 && agmv_hip_memcpy_async(d->ctx, d->d_iframe, out + (size_t)last_i * d->npx, d->npx * 4, 2, d->stream)) goto fail;
-		if (d->d_dst && d->scale.filter) {
+		if (d->d_dst && d->scale.tensor) {                     /* one launch per batch; the box filter first makes its batch of D */
+			const uint32_t tw = d->scale.w, th = d->scale.h;
+			const int area = d->scale.filter == AGMV_SCALE_AREA;
+			u8* sink = (u8*)d->d_dst + (size_t)b->first * agmv_hip_tensor_frame_bytes(d->scale.tensor, (size_t)tw * th);
+			if (area && agmv_hip_scale_area_dev(d->ctx, AGMV_PIXFMT_XRGB32, out, d->w, d->h, b->n, tw, th, d->d_scaled, d->stream)) goto fail;
+			if (agmv_hip_tensor_from_xrgb_async(d->ctx, d->scale.tensor, area ? d->d_scaled : out, area ? tw : d->w, area ? th : d->h, b->n,
+			                                    area ? 0 : d->scale.filter, tw, th, d->d_table, sink, d->stream))
+				goto fail;
+		} else if (d->d_dst && d->scale.filter) {
 			const uint32_t tw = d->scale.w, th = d->scale.h;
 			u8* sink = (u8*)d->d_dst + (size_t)b->first * agmv_fmt_frame_bytes(d->fmt, tw, th);
 			if (d->scale.filter != AGMV_SCALE_AREA) {
@@ -1107,12 +1117,13 @@ static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, dchunk* c, const u8* fil
    frames decoded either way.  With d_quality (device memory, 96 bytes per frame) d_dst is a reference clip in `fmt` that is only
    read: frame k is measured against frame k of it where the other sink converts, and no decoded frame outlives its batch.
    With `scale` (d_dst set, no d_quality) the frames of d_dst are scale->w x scale->h: the batch is decoded at the file's size into
-   the double buffer, never in place, and the sink step scales it into its place (AGMV_DecodeFramesScaledDev of include/agmv.h). */
+   the double buffer, never in place, and the sink step scales it into its place (AGMV_DecodeFramesScaledDev of include/agmv.h).
+   With scale->tensor d_dst is a tensor clip (AGMV_DecodeFramesTensorDev), `fmt` is not read, and scale->filter may be 0. */
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
                        int has_audio, unsigned cap_frames, unsigned threads, void* d_dst, int fmt, const agmv_scale* scale, void* d_quality,
                        unsigned long* export_count)
 {
-	const int scaled = scale && scale->filter && d_dst && !d_quality;
+	const int scaled = scale && (scale->filter || scale->tensor) && d_dst && !d_quality;
 	const int direct = d_dst && !d_quality && !scaled && fmt == AGMV_PIXFMT_XRGB32;     /* decoded in place: no double buffer */
 	dpipe d;
 	dlz z;
@@ -1130,6 +1141,7 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	d.ctx = ctx; d.w = w; d.h = h; d.npx = npx; d.stride = (cap + 255) & ~(size_t)255;
 	d.cap = cap_frames; d.nslots = 3; d.d_dst = d_dst; d.fmt = fmt; d.d_quality = d_quality;
 	if (scaled) d.scale = *scale;
+	if (scaled && scale->tensor && !scale->filter) { d.scale.w = w; d.scale.h = h; }
 	pthread_mutex_init(&d.mu, NULL);
 	pthread_cond_init(&d.cv, NULL);
 	d.slot = (dbatch*)calloc(d.nslots, sizeof(dbatch));
@@ -1141,9 +1153,17 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	d.d_out[0] = direct ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
 	d.d_out[1] = direct ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
 	d.d_iframe = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4);
-	if (scaled && scale->filter == AGMV_SCALE_AREA && fmt != AGMV_PIXFMT_XRGB32) {
+	if (scaled && scale->filter == AGMV_SCALE_AREA && (fmt != AGMV_PIXFMT_XRGB32 || scale->tensor)) {
 		d.d_scaled = (uint32_t*)agmv_hip_malloc_on(ctx, (size_t)scale->w * scale->h * 4 * d.cap);
 		if (!d.d_scaled) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+	}
+	if (scaled && scale->tensor) {                         /* 3 x 256 elements, once per call */
+		const size_t bytes = agmv_hip_tensor_frame_bytes(scale->tensor, 256);
+		d.d_table = agmv_hip_malloc_on(ctx, bytes);
+		if (!d.d_table || !d.stream || agmv_hip_memcpy_async(ctx, d.d_table, scale->table, bytes, 0, d.stream) || agmv_hip_stream_sync(ctx, d.stream)) {
+			rc = MEMORY_CORRUPTION_ERR;
+			goto out;
+		}
 	}
 	if (!persist || !chunks || (!lz_dev && !jobs) || !d.stream || (!lz_dev && (!d.d_bits || !d.d_bpos)) || !d.d_nent || (!direct && (!d.d_out[0] || !d.d_out[1])) || !d.d_iframe) { rc = MEMORY_CORRUPTION_ERR; goto out; }
 	if (lz_dev && dlz_open(&z, ctx, d.cap, cap)) { rc = MEMORY_CORRUPTION_ERR; goto out; }
@@ -1233,6 +1253,7 @@ out:
 	dlz_close(&z);
 	agmv_hip_free_on(ctx, d.d_bits); agmv_hip_free_on(ctx, d.d_bpos); agmv_hip_free_on(ctx, d.d_nent);
 	agmv_hip_free_on(ctx, d.d_out[0]); agmv_hip_free_on(ctx, d.d_out[1]); agmv_hip_free_on(ctx, d.d_iframe); agmv_hip_free_on(ctx, d.d_scaled);
+	agmv_hip_free_on(ctx, d.d_table);
 	agmv_hip_stream_destroy(ctx, d.stream);
 	free(d.slot); free(persist); free(chunks); free(jobs);
 	pthread_mutex_destroy(&d.mu);

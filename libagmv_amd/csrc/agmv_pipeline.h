@@ -49,8 +49,10 @@ u32  agmv_seq_close(agmv_seq* s);
 void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start, u32 end, u32 size, int quality,
                            unsigned threads, uint32_t* hist);
 
-/* a target size for the decoder's sink: the frames land in d_dst at w x h, scaled with `filter` (an AGMV_SCALE of include/agmv.h) */
-typedef struct agmv_scale { uint32_t w, h; int filter; } agmv_scale;
+/* a target for the decoder's sink: the frames land in d_dst at w x h, scaled with `filter` (an AGMV_SCALE of include/agmv.h).
+   tensor != 0 (an AGMV_TENSORFMT): d_dst is a tensor clip of that type instead of a clip in `fmt`, written through `table` (host
+   memory, the 768 elements of agmv_hip_tensor_table); filter 0 then means the file's size, and w, h are not read */
+typedef struct agmv_scale { uint32_t w, h; int filter, tensor; const void* table; } agmv_scale;
 
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
                        int has_audio, unsigned cap_frames, unsigned threads, void* d_dst, int fmt, const agmv_scale* scale, void* d_quality,

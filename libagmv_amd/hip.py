@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "agmv_hip_dither_frames_async",
     "agmv_hip_audio_compand_async", "agmv_hip_audio_expand_async",
     "agmv_hip_measure_frames_async",
+    "agmv_hip_tensor_frame_bytes", "agmv_hip_tensor_table", "agmv_hip_tensor_from_xrgb_async", "agmv_hip_tensor_to_xrgb_async",
 ]
 
 
@@ -184,6 +185,13 @@ def load_library(path=None):
     if path is None or hasattr(L, "agmv_hip_measure_frames_async"):
         L.agmv_hip_measure_frames_async.argtypes = [vp, vp, C.c_int, vp, u32, u32, u32, vp, vp]
         L.agmv_hip_measure_frames_async.restype = C.c_int
+    if path is None or hasattr(L, "agmv_hip_tensor_table"):
+        L.agmv_hip_tensor_frame_bytes.restype = sz
+        L.agmv_hip_tensor_frame_bytes.argtypes = [C.c_int, sz]
+        L.agmv_hip_tensor_table.argtypes = [C.c_int, vp, vp, vp]
+        L.agmv_hip_tensor_from_xrgb_async.argtypes = [vp, C.c_int, vp, u32, u32, u32, C.c_int, u32, u32, vp, vp, vp]
+        L.agmv_hip_tensor_to_xrgb_async.argtypes = [vp, C.c_int, vp, sz, u32, vp, vp, vp]
+        L.agmv_hip_tensor_table.restype = L.agmv_hip_tensor_from_xrgb_async.restype = L.agmv_hip_tensor_to_xrgb_async.restype = C.c_int
     L.agmv_hip_check.argtypes = [vp, vp]
     L.agmv_hip_enable_timing.argtypes = [vp, C.c_int]
     L.agmv_hip_enable_timing.restype = C.c_int
@@ -254,6 +262,43 @@ def pcmfmt(fmt):
     if v not in PCMFMT.values():
         raise ValueError("fmt: one of %s is needed, got %r" % (", ".join(sorted(PCMFMT)), fmt))
     return v
+
+
+# AGMV_TENSORFMT of include/agmv.h: name -> value; the numpy storage of one element's bit pattern
+TENSORFMT = {"f32": 1, "f16": 2, "bf16": 3}
+TENSOR_BITS = {1: np.uint32, 2: np.uint16, 3: np.uint16}
+
+
+def tensorfmt(fmt):
+    """the AGMV_TENSORFMT value of a name or of a value"""
+    v = TENSORFMT.get(fmt, fmt) if isinstance(fmt, (str, int)) and not isinstance(fmt, bool) else None
+    if v not in TENSORFMT.values():
+        raise ValueError("fmt: one of %s is needed, got %r" % (", ".join(sorted(TENSORFMT)), fmt))
+    return v
+
+
+def tensor_normalisation(who, mean, std):
+    """(mean, std) as two ctypes float[3]; a number stands for all three channels.  Raises ValueError for anything else; the
+    bounds are the library's to check"""
+    out = []
+    for name, v in (("mean", mean), ("std", std)):
+        if isinstance(v, (int, float)) and not isinstance(v, bool):
+            v = (v, v, v)
+        if not (isinstance(v, (tuple, list)) and len(v) == 3 and all(isinstance(x, (int, float)) and not isinstance(x, bool) for x in v)):
+            raise ValueError("%s: %s must be a number or three numbers, got %r" % (who, name, v))
+        out.append((C.c_float * 3)(*[float(np.float32(x)) for x in v]))
+    return out
+
+
+def tensor_table(fmt, mean=0.0, std=1.0):
+    """agmv_hip_tensor_table: the 3 x 256 bit patterns of the writing rule as a numpy array [3, 256] of uint32 ("f32") or uint16;
+    host only, no GPU.  ValueError for a normalisation the library refuses."""
+    v = tensorfmt(fmt)
+    m, s = tensor_normalisation("tensor_table", mean, std)
+    table = np.zeros((3, 256), dtype=TENSOR_BITS[v])
+    if load_library().agmv_hip_tensor_table(v, m, s, _np_ptr(table)):
+        raise ValueError("tensor_table: mean %r / std %r: %s" % (mean, std, load_library().agmv_hip_last_error().decode()))
+    return table
 
 
 def _np_ptr(a):
@@ -890,6 +935,44 @@ class AgmvHip:
             raise ValueError("scale_frames_async: out must be a contiguous CUDA tensor of >= %d bytes" % (n_frames * fb))
         s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
         self._ck(self.L.agmv_hip_scale_frames_async(self.ctx, int(filt), src.data_ptr(), w, h, n_frames, fmt, dst_w, dst_h, out.data_ptr(), s))
+        return out
+
+    # ------------------------------------------------------------------ normalised float tensor clips (AGMV_TENSORFMT of include/agmv.h)
+    def tensor_from_xrgb_async(self, fmt, src, w, h, n_frames, table, out, filt=0, dst_w=None, dst_h=None, stream=None):
+        """src: int32 CUDA tensor of n_frames frames of w x h pixels 0x00RRGGBB -> out, a contiguous CUDA tensor (or view at any
+        element offset) of n_frames * 3 * dst_h * dst_w elements of fmt ("f32", "f16", "bf16" or its value), through `table`, the
+        768 elements of tensor_table() on the device (agmv_hip_tensor_from_xrgb_async).  filt 0 = no scale, 1 nearest, 3 bilinear.
+        On `stream` (a torch stream; None = torch's current one).  Nothing waits."""
+        v = tensorfmt(fmt)
+        w, h, n_frames = int(w), int(h), int(n_frames)
+        dst_w, dst_h = (w if dst_w is None else int(dst_w)), (h if dst_h is None else int(dst_h))
+        _check_vec("tensor_from_xrgb_async: src", src, n_frames * w * h)
+        need = n_frames * self.L.agmv_hip_tensor_frame_bytes(v, dst_w * dst_h)
+        if not (out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= need):
+            raise ValueError("tensor_from_xrgb_async: out must be a contiguous CUDA tensor of >= %d bytes" % need)
+        if not (table.is_cuda and table.is_contiguous() and table.numel() * table.element_size() >= 768 * (4 if v == 1 else 2)):
+            raise ValueError("tensor_from_xrgb_async: table must be a contiguous CUDA tensor of 768 elements")
+        s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self._ck(self.L.agmv_hip_tensor_from_xrgb_async(self.ctx, v, src.data_ptr(), w, h, n_frames, int(filt), dst_w, dst_h, table.data_ptr(),
+                                                        out.data_ptr(), s))
+        return out
+
+    def tensor_to_xrgb_async(self, fmt, src, frame_pixels, n_frames, ab, out=None, stream=None):
+        """src: contiguous CUDA tensor (or view) of n_frames frames of 3 * frame_pixels elements of fmt -> int32 [n_frames,
+        frame_pixels] of 0x00RRGGBB by the reading rule (agmv_hip_tensor_to_xrgb_async); ab: six numbers, a[3] then b[3], taken as
+        float32.  On `stream` (a torch stream; None = torch's current one).  Nothing waits."""
+        import torch
+        v = tensorfmt(fmt)
+        frame_pixels, n_frames = int(frame_pixels), int(n_frames)
+        need = n_frames * self.L.agmv_hip_tensor_frame_bytes(v, frame_pixels)
+        if not (src.is_cuda and src.is_contiguous() and src.numel() * src.element_size() >= need):
+            raise ValueError("tensor_to_xrgb_async: src must be a contiguous CUDA tensor of >= %d bytes" % need)
+        if out is None:
+            out = torch.empty((n_frames, frame_pixels), dtype=torch.int32, device=src.device)
+        _check_vec("tensor_to_xrgb_async: out", out, n_frames * frame_pixels)
+        k = (C.c_float * 6)(*[float(x) for x in ab])
+        s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self._ck(self.L.agmv_hip_tensor_to_xrgb_async(self.ctx, v, src.data_ptr(), frame_pixels, n_frames, k, out.data_ptr(), s))
         return out
 
     # ------------------------------------------------------------------ the palette refined by weighted k-means (include/agmv.h)

@@ -1,5 +1,5 @@
 """Whole .agmv sequences from and to frames in GPU memory: ctypes calls of AGMV_EncodeFramesFmtDev / AGMV_EncodeFramesScaledDev /
-AGMV_DecodeFramesFmtDev / AGMV_DecodeFramesScaledDev (include/agmv.h, libagmv.so).  No logic here: the schedules, the container, both LZ stages and the reading and writing of the
+AGMV_DecodeFramesFmtDev / AGMV_DecodeFramesScaledDev / AGMV_EncodeFramesTensorDev / AGMV_DecodeFramesTensorDev (include/agmv.h, libagmv.so).  No logic here: the schedules, the container, both LZ stages and the reading and writing of the
 caller's pixel layout are the library's; torch holds the frames.  The frames live on the library's own device (env AGMV_DEVICE,
 default 0).
 clip_quality / file_quality (AGMV_MeasureFramesDev / AGMV_MeasureFileDev) measure a decoded clip, or a file batch by batch, against
@@ -17,6 +17,11 @@ Pixel layouts (AGMV_PIXFMT) and the tensors that hold n frames of h x w:
 The two YUV 4:2:0 layouts (include/agmv.h has their definition) need even h and w here, are never inferred from a tensor, and
 take yuv="bt601" (default) or "bt709" and full_range=False (limited range) or True.
 
+Normalised float tensors (AGMV_TENSORFMT; include/agmv.h, "normalised float tensors"), what a model takes and gives:
+  "f32" / "f16" / "bf16"   float32 / float16 / bfloat16 [n, 3, h, w]   planes R, G, B; a byte v stands for (v / 255 - mean[c]) / std[c]
+with mean= and std= (a number or three; defaults 0 and 1).  decode_frames writes them through a table, encode_frames reads them by
+the header's rule: both are exact, bit for bit.  A floating [n, 3, h, w] tensor is inferred as a tensor clip from its dtype.
+
 Audio tracks (AGMV_PCMFMT; include/agmv.h, "audio tracks") and the tensors that hold n samples per channel of ch channels:
   "s16"   int16 [n, ch]     interleaved, the WAV samples as they are     (16-bit track)
   "u8"    uint8 [n, ch]     interleaved unsigned bytes                   (8-bit track)
@@ -24,7 +29,7 @@ Audio tracks (AGMV_PCMFMT; include/agmv.h, "audio tracks") and the tensors that 
 import ctypes as C
 import os
 
-from .hip import HERE, PIXFMT, YUVFMT, HipUnavailable, pcmfmt, pixfmt, yuvfmt
+from .hip import HERE, PIXFMT, TENSORFMT, YUVFMT, HipUnavailable, pcmfmt, pixfmt, tensor_normalisation, yuvfmt
 
 SCHEDULE_FULL, SCHEDULE_PDIFS, SCHEDULE_ADAPTIVE = 1, 2, 3
 SCALE = {"nearest": 1, "area": 2}          # AGMV_SCALE of include/agmv.h, which defines both filters
@@ -66,6 +71,11 @@ def load_library():
         L.AGMV_DecodeFramesScaledDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.c_ulong, C.c_int, C.c_ulong, C.POINTER(AGMV_INFO)]
         L.AGMV_EncodeFramesScaledDev.restype = C.c_int
         L.AGMV_EncodeFramesScaledDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int] + [C.c_ulong] * 5 + [C.c_int, C.c_ulong] + [C.c_int] * 4
+        L.AGMV_EncodeFramesTensorDev.restype = C.c_int
+        L.AGMV_EncodeFramesTensorDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_ulong] * 4 + [C.c_int] * 4
+        L.AGMV_DecodeFramesTensorDev.restype = C.c_int
+        L.AGMV_DecodeFramesTensorDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_ulong, C.c_ulong, C.c_int, C.c_ulong,
+                                                 C.POINTER(AGMV_INFO)]
         L.AGMV_SetPaletteRefine.restype = None
         L.AGMV_SetPaletteRefine.argtypes = [C.c_uint]
         L.AGMV_SetDither.restype = None
@@ -134,6 +144,33 @@ def _clip_geometry(frames, fmt, yuv=None, full_range=False, who="encode_frames")
     return v, n, h, w
 
 
+def _tensor_dtypes():
+    import torch
+    return {1: torch.float32, 2: torch.float16, 3: torch.bfloat16}
+
+
+def _tensor_clip(frames, fmt, mean, std, who):
+    """(AGMV_TENSORFMT value, n, h, w, mean, std as ctypes float[3]) where the arguments name a tensor clip -- fmt one of TENSORFMT,
+    or fmt None and a floating [n, 3, h, w] tensor -- else None, after refusing mean= / std= on any other layout.  Touches neither
+    the library nor the device."""
+    named = isinstance(fmt, str) and fmt in TENSORFMT
+    shape = tuple(frames.shape) if frames is not None else None
+    if not (named or (fmt is None and frames is not None and frames.dtype.is_floating_point and len(shape) == 4 and shape[1] == 3)):
+        if mean is not None or std is not None:
+            raise ValueError("%s: mean= and std= belong to the tensor layouts %s, not to fmt %r" % (who, ", ".join("\"%s\"" % k for k in sorted(TENSORFMT)), fmt))
+        return None
+    m, s = tensor_normalisation(who, 0.0 if mean is None else mean, 1.0 if std is None else std)
+    if frames is None:
+        return TENSORFMT[fmt], None, None, None, m, s
+    v = {d: k for k, d in _tensor_dtypes().items()}.get(frames.dtype)
+    if v is None or (named and v != TENSORFMT[fmt]) or len(shape) != 4 or shape[1] != 3:
+        raise ValueError("%s: fmt %r does not fit a %s tensor of shape %s: float32, float16 or bfloat16 [n, 3, h, w] of the named type is needed"
+                         % (who, fmt, frames.dtype, shape))
+    if not frames.is_contiguous():
+        raise ValueError("%s: fmt %r needs a contiguous tensor (strides %s of shape %s)" % (who, fmt, frames.stride(), shape))
+    return v, shape[0], shape[2], shape[3], m, s
+
+
 def _scale_target(size, scale):
     """(filter value, h, w) of encode_frames' size= and scale=, or None for size=None; touches neither the library nor the device"""
     if scale not in SCALE:
@@ -163,7 +200,7 @@ def _track_geometry(audio, sample_rate):
 
 
 def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedule=SCHEDULE_PDIFS, fmt=None, yuv=None, full_range=False,
-                  size=None, scale="area", palette_refine=None, dither=None, audio=None, sample_rate=None):
+                  size=None, scale="area", palette_refine=None, dither=None, audio=None, sample_rate=None, mean=None, std=None):
     """frames: contiguous CUDA tensor of n frames on the library's device, in the layout `fmt` (see the module text; None = inferred
     from the tensor, which never gives "nv12" or "i420") -> the file at `path`.  yuv ("bt601", the default, or "bt709") and
     full_range go with the two YUV layouts only.  size=(h, w), in tensor order, scales the clip to that size first
@@ -175,14 +212,24 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
     definition; set for this call only); None leaves the library's knob as it is.  audio= is the clip's sound, a contiguous CUDA
     tensor on the same device -- int16 [n, ch], uint8 [n, ch] or float32 [ch, n] (see the module text) -- at sample_rate= samples
     per second; it is companded on the GPU and interleaved with the frames as AGAC chunks (AGMV_SetAudioDev, for this call only).
-    A track shorter than one second and SCHEDULE_ADAPTIVE with a track are refused."""
+    A track shorter than one second and SCHEDULE_ADAPTIVE with a track are refused.
+    A float32 / float16 / bfloat16 [n, 3, h, w] tensor (fmt "f32" / "f16" / "bf16", or inferred from the dtype) is a normalised
+    tensor clip, model output as it is: mean= and std= (a number or three per channel; defaults 0 and 1) say what its values
+    stand for, and the file is that of the XRGB32 clip the reading rule of include/agmv.h gives (AGMV_EncodeFramesTensorDev).
+    yuv=, full_range= and size= do not go with a tensor clip; mean= and std= go with nothing else."""
     import torch
     if dither is not None and not (isinstance(dither, int) and not isinstance(dither, bool) and 1 <= dither <= 64):
         raise ValueError("encode_frames: dither must be None or an int from 1 to 64, got %r" % (dither,))
     if palette_refine is not None and not (isinstance(palette_refine, int) and not isinstance(palette_refine, bool) and 1 <= palette_refine <= 64):
         raise ValueError("encode_frames: palette_refine must be None or an int from 1 to 64, got %r" % (palette_refine,))
     target = _scale_target(size, scale)
-    v, n, h, w = _clip_geometry(frames, fmt, yuv, full_range)
+    tensor = _tensor_clip(frames, fmt, mean, std, "encode_frames")
+    if tensor is not None:
+        if yuv is not None or full_range or target is not None:
+            raise ValueError("encode_frames: yuv=, full_range= and size= do not go with a tensor clip (fmt %r)" % (fmt,))
+        v, n, h, w = tensor[:4]
+    else:
+        v, n, h, w = _clip_geometry(frames, fmt, yuv, full_range)
     track = None
     if audio is not None:
         track = _track_geometry(audio, sample_rate)
@@ -203,6 +250,12 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
     if dither is not None:
         L.AGMV_SetDither(dither)
     try:
+        if tensor is not None:
+            rc = L.AGMV_EncodeFramesTensorDev(os.fsencode(path), frames.data_ptr(), v, tensor[4], tensor[5], n, w, h, fps, opt, quality, compression, schedule)
+            if rc:
+                raise ValueError("AGMV_EncodeFramesTensorDev refused its arguments (%d): %d frames of %dx%d, mean %r, std %r, opt %d, schedule %d"
+                                 % (rc, n, w, h, mean, std, opt, schedule))
+            return
         if target is None:
             rc = L.AGMV_EncodeFramesFmtDev(os.fsencode(path), frames.data_ptr(), v, n, w, h, fps, opt, quality, compression, schedule)
             if rc:
@@ -235,16 +288,24 @@ def _decode_target(size, scale):
     return DECODE_SCALE[scale], size[0], size[1]
 
 
-def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False, size=None, scale="bilinear"):
+def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False, size=None, scale="bilinear", mean=None, std=None):
     """-> (CUDA tensor of the file's frames on the library's device in the layout `fmt`: int32 [n, h, w] of 0x00RRGGBB for "xrgb32",
     uint8 [n, h, w, 3] / [n, h, w, 4] / [n, 3, h, w] for the byte formats, uint8 [n, h * 3 / 2, w] for "nv12" and "i420" (a file
     of even width and height; yuv and full_range as for encode_frames); AGMV_INFO of the header).  size=(h, w), in tensor order,
     delivers the frames at that size instead of the file's (AGMV_DecodeFramesScaledDev of include/agmv.h, which defines the
     filters): scale "bilinear" (the default) and "nearest" take any size in either direction, "area" is the exact box filter and
     only scales down.  The tensor then has the layout's shape at (h, w) -- even h and w for the two YUV layouts, whatever the
-    file's size -- and the AGMV_INFO still carries the file's own size."""
+    file's size -- and the AGMV_INFO still carries the file's own size.
+    fmt "f32" / "f16" / "bf16" gives a model's input: a float32 / float16 / bfloat16 [n, 3, h, w] tensor, every byte v of channel
+    c as (v / 255 - mean[c]) / std[c] (mean= and std=: a number or three; defaults 0 and 1), written by the sink in the same
+    launch that scales (AGMV_DecodeFramesTensorDev of include/agmv.h: exact, through a table)."""
     import torch
     target = _decode_target(size, scale)
+    tensor = _tensor_clip(None, fmt, mean, std, "decode_frames")
+    if tensor is not None:
+        if yuv is not None or full_range:
+            raise ValueError("decode_frames: yuv= and full_range= belong to fmt \"nv12\" and \"i420\", not to fmt %r" % (fmt,))
+        return _decode_tensor(path, tensor, target, scale)
     v = _fmt_value("decode_frames", fmt, yuv, full_range)
     L = load_library()
     info = AGMV_INFO()
@@ -270,6 +331,29 @@ def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False, size=None, sca
     rc = L.AGMV_DecodeFramesScaledDev(os.fsencode(path), out.data_ptr(), v, w, h, filt, n, None)
     if rc < 0:
         raise RuntimeError("AGMV_DecodeFramesScaledDev(%s, %d x %d, scale %r): Error %d" % (path, w, h, scale, -rc))
+    return out[:rc], info
+
+
+def _decode_tensor(path, tensor, target, scale):
+    """decode_frames for a tensor clip: (AGMV_TENSORFMT value, -, -, -, mean, std) of _tensor_clip, target of _decode_target"""
+    import torch
+    v, m, s = tensor[0], tensor[4], tensor[5]
+    L = load_library()
+    info = AGMV_INFO()
+    rc = L.AGMV_DecodeFramesTensorDev(os.fsencode(path), None, v, m, s, 0, 0, 0, 0, C.byref(info))
+    if rc < 0:
+        raise (ValueError if rc == -1 else RuntimeError)("AGMV_DecodeFramesTensorDev(%s): %s" % (path, "the normalisation is refused" if rc == -1 else "Error %d" % -rc))
+    n, h, w = info.number_of_frames, info.height, info.width
+    filt, tw, th = 0, 0, 0
+    if target is not None:
+        filt, th, tw = target
+        if filt == DECODE_SCALE["area"] and (th > h or tw > w):
+            raise ValueError("decode_frames: scale=\"area\" only scales down, %s holds %d x %d and size= asks for %d x %d" % (path, w, h, tw, th))
+        h, w = th, tw
+    out = torch.empty((n, 3, h, w), dtype=_tensor_dtypes()[v], device=_device())
+    rc = L.AGMV_DecodeFramesTensorDev(os.fsencode(path), out.data_ptr(), v, m, s, tw, th, filt, n, None)
+    if rc < 0:
+        raise RuntimeError("AGMV_DecodeFramesTensorDev(%s, %d x %d, scale %r): Error %d" % (path, w, h, scale, -rc))
     return out[:rc], info
 
 
