@@ -122,13 +122,18 @@ static unsigned lz_threads(void)
 	return n > 64 ? 64 : n;
 }
 
+/* the library's context, opened on first use: NULL where the device cannot be opened, for the callers with an error channel
+   (the decoders, gpu_failed); ctx() is for the others, which abort */
+static agmv_hip_ctx* open_ctx(void)
+{
+	const char* e = getenv("AGMV_DEVICE");
+	if (!g_ctx) g_ctx = agmv_hip_create(e ? atoi(e) : 0);
+	return g_ctx;
+}
+
 static agmv_hip_ctx* ctx(void)
 {
-	if (!g_ctx) {
-		const char* e = getenv("AGMV_DEVICE");
-		g_ctx = agmv_hip_create(e ? atoi(e) : 0);
-		if (!g_ctx) agmv_die("cannot open the GPU");
-	}
+	if (!open_ctx()) agmv_die("cannot open the GPU");
 	return g_ctx;
 }
 
@@ -529,13 +534,6 @@ static void dump_gba_header(const char* filename)
 
 static int heavy_pdifs(AGMV_OPT o) { return o == AGMV_OPT_I || o == AGMV_OPT_ANIM || o == AGMV_OPT_GBA_I || o == AGMV_OPT_GBA_II; }
 
-static void resize_for_target(AGMV* a, AGMV_OPT opt)
-{
-	int sw, sh;
-	scaled_size(opt, &sw, &sh);
-	if (sw) { AGMV_SetWidth(a, (u32)sw); AGMV_SetHeight(a, (u32)sh); }
-}
-
 static void require_bmp(u8 img_type)
 {
 	if (img_type != AGMV_IMG_BMP) {
@@ -572,7 +570,6 @@ static void similarity_open(similarity* m, const agmv_source* src, AGMV* a, AGMV
 	{	/* the whole clip at once; with a scale, of the scaled frames (the same gather the workers run) */
 		agmv_hip_ctx* c = ctx();
 		const uint32_t n = src->n_frames;
-		const uint32_t* d_clip = NULL;                         /* the packed clip today's similarity reads, where one exists */
 		uint32_t *d_scaled = NULL, *d_index = NULL, *d_counts = (uint32_t*)agmv_hip_malloc_on(c, 4 * (size_t)n);
 		m->counts = (uint32_t*)calloc(n, 4);
 		if (!d_counts || !m->counts) agmv_die("device allocation");
@@ -581,15 +578,12 @@ static void similarity_open(similarity* m, const agmv_source* src, AGMV* a, AGMV
 			d_index = (uint32_t*)agmv_hip_malloc_on(c, npx * 4);
 			d_scaled = (uint32_t*)agmv_hip_malloc_on(c, npx * 4 * n);
 			if (!d_index || !d_scaled || agmv_hip_memcpy_async(c, d_index, index, npx * 4, 0, NULL) ||
-			    (AGMV_FMT_IS_YUV(src->fmt) ? agmv_hip_yuv_gather_dev(c, src->fmt, src->d_frames, src->src_w, src->src_h, n, d_index, npx, d_scaled, NULL)
-			                               : agmv_hip_gather_fmt_dev(c, src->fmt, src->d_frames, (size_t)src->src_w * src->src_h, n, d_index, npx, d_scaled, NULL)))
+			    agmv_fmt_gather(c, src->fmt, src->src_w, src->src_h, src->d_frames, n, d_index, npx, d_scaled, NULL))
 				agmv_die("frame gather");
-			d_clip = d_scaled;
 			m->tmp = index;                                    /* (freed by similarity_close, behind the synchronisation below) */
 		}
-		if ((d_clip ? agmv_hip_similarity_dev(c, d_clip, n, npx, d_counts, NULL) :
-		     AGMV_FMT_IS_YUV(src->fmt) ? agmv_hip_yuv_similarity_dev(c, src->fmt, src->d_frames, src->src_w, src->src_h, n, d_counts, NULL) :
-		                                 agmv_hip_similarity_fmt_dev(c, src->fmt, src->d_frames, n, npx, d_counts, NULL)) ||
+		if ((d_scaled ? agmv_hip_similarity_dev(c, d_scaled, n, npx, d_counts, NULL)
+		            : agmv_fmt_similarity(c, src->fmt, src->src_w, src->src_h, src->d_frames, n, d_counts, NULL)) ||
 		    (n > 1 && agmv_hip_memcpy_async(c, m->counts, d_counts, 4 * (size_t)(n - 1), 1, NULL)) || agmv_hip_stream_sync(c, NULL))
 			agmv_die("frame similarity");
 		agmv_hip_free_on(c, d_counts); agmv_hip_free_on(c, d_scaled); agmv_hip_free_on(c, d_index);
@@ -616,6 +610,7 @@ static void encode_sequence(AGMV* a, const char* filename, const agmv_source* sr
                             u32 end_frame, u32 width, u32 height, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression)
 {
 	u32 p0[256], p1[256], adjusted = end_frame - start_frame, i;
+	int sw, sh;
 	FILE* file;
 	agmv_seq* s;
 	u32 written;
@@ -636,7 +631,8 @@ static void encode_sequence(AGMV* a, const char* filename, const agmv_source* sr
 		}
 		AGMV_SetLeniency(a, len);
 	}
-	resize_for_target(a, opt);
+	scaled_size(opt, &sw, &sh);
+	if (sw) { AGMV_SetWidth(a, (u32)sw); AGMV_SetHeight(a, (u32)sh); }     /* the GBA / NDS opts encode at their own size */
 
 	build_palette_from_frames(src, start_frame, end_frame, width * height, quality, opt, p0, p1);
 	if (schedule == AGMV_SCHEDULE_PDIFS && a->audio_chunk) a->audio_chunk->size = (u32)(a->header.audio_size / (f32)adjusted);   /* 0 without an audio track */
@@ -695,10 +691,8 @@ static void encode_sequence(AGMV* a, const char* filename, const agmv_source* sr
 
 static agmv_source bmp_source(const char* dir, const char* basename, u8 img_type)
 {
-	agmv_source src;
+	const agmv_source src = {.dir = dir, .base = basename};
 	require_bmp(img_type);
-	memset(&src, 0, sizeof(src));
-	src.dir = dir; src.base = basename;
 	return src;
 }
 
@@ -772,42 +766,46 @@ static void attach_audio_dev(AGMV* a)
 	a->audio_chunk->atsample = codes;
 }
 
-/* The same three files from frames in device memory: num_of_frames frames of width x height pixels in the layout `fmt`, on the
-   device of this library's context.  What the BMP drivers write for f1.bmp .. f<n>.bmp holding these frames, byte for byte (for
-   AGMV_SCHEDULE_ADAPTIVE with AGMV_EncodeVideo's CreateAGMV(n - 1, ...)); GBA_GEN_AGMV.h is not written.  Returns 0, or a
-   negative value -- before any file is created -- for arguments that cannot be encoded. */
-/* what AGMV_EncodeFramesDev refuses, in its order: 0, or the negative value; needs no device */
-static int encode_frames_refused(const char* filename, const void* d_frames, u32 num_of_frames, u32 width, u32 height, AGMV_OPT opt, AGMV_QUALITY quality,
-                                 AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+/* a pending AGMV_SetAudioDev track is consumed by every AGMV_EncodeFrames*Dev call, whatever it returns: each of them returns through here */
+static int audio_consumed(int rc) { memset(&g_audio, 0, sizeof(g_audio)); return rc; }
+
+/* what every AGMV_EncodeFrames*Dev refuses of its enums (-1), of a pending track (-5) and of the number of frames (-2), in this
+   order; 0 where it has nothing to object to.  Needs no device. */
+static int encode_args_refused(u32 num_of_frames, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
 {
-	int sw, sh;
-	u32 least;
-	if (!filename || !d_frames) return -1;
 	if (opt < AGMV_OPT_I || opt > AGMV_OPT_NDS || quality < AGMV_HIGH_QUALITY || quality > AGMV_LOW_QUALITY ||
 	    (compression != AGMV_LZSS_COMPRESSION && compression != AGMV_LZ77_COMPRESSION) ||
 	    (schedule != AGMV_SCHEDULE_FULL && schedule != AGMV_SCHEDULE_PDIFS && schedule != AGMV_SCHEDULE_ADAPTIVE))
 		return -1;
 	if (schedule == AGMV_SCHEDULE_ADAPTIVE && g_audio.d_pcm) return -5;      /* AGMV_EncodeVideo has no audio */
 	/* the first group of the schedule reads this many frames whatever the length of the clip */
-	least = schedule == AGMV_SCHEDULE_FULL ? 1 : (heavy_pdifs(opt) ? 2 : 4);
-	if (num_of_frames < least || num_of_frames > 0x7FFFFFFFul) return -2;
-	scaled_size(opt, &sw, &sh);
-	if (width == 0 || height == 0 || (unsigned long long)width * height > (1ull << 28)) return -3;
-	if (!sw && bad_geometry((uint32_t)width, (uint32_t)height)) return -3;
-	if (sw && (width < 2 || height < 2)) return -3;
+	if (num_of_frames < (schedule == AGMV_SCHEDULE_FULL ? 1u : (heavy_pdifs(opt) ? 2u : 4u)) || num_of_frames > 0x7FFFFFFFul) return -2;
 	return 0;
 }
 
+/* what AGMV_EncodeFramesDev refuses, in its order (-1, -5, -2, -3): 0, or the negative value; needs no device */
+static int encode_frames_refused(const char* filename, const void* d_frames, u32 num_of_frames, u32 width, u32 height, AGMV_OPT opt, AGMV_QUALITY quality,
+                                 AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+{
+	int sw, sh;
+	const int rc = filename && d_frames ? encode_args_refused(num_of_frames, opt, quality, compression, schedule) : -1;
+	if (rc) return rc;
+	scaled_size(opt, &sw, &sh);
+	if (width == 0 || height == 0 || (unsigned long long)width * height > (1ull << 28)) return -3;
+	return (sw ? width < 2 || height < 2 : bad_geometry((uint32_t)width, (uint32_t)height)) ? -3 : 0;
+}
+
+/* The same three files from frames in device memory (include/agmv.h): what the BMP drivers write for f1.bmp .. f<n>.bmp holding these
+   frames, byte for byte (for AGMV_SCHEDULE_ADAPTIVE with AGMV_EncodeVideo's CreateAGMV(n - 1, ...)); GBA_GEN_AGMV.h is not written.
+   Returns 0, or a negative value -- before any file is created -- for arguments that cannot be encoded. */
 static int encode_frames_dev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 width, u32 height,
                              u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
 {
-	agmv_source src;
+	agmv_source src = {.d_frames = d_frames, .fmt = (int)fmt, .src_w = (uint32_t)width, .src_h = (uint32_t)height, .n_frames = (uint32_t)num_of_frames, .first = 1};
 	AGMV* a;
 	const int refused = known_pixfmt((int)fmt) ? encode_frames_refused(filename, d_frames, num_of_frames, width, height, opt, quality, compression, schedule) : -1;
 	if (refused) return refused;
-	memset(&src, 0, sizeof(src));
-	src.d_frames = d_frames; src.fmt = (int)fmt; src.src_w = (uint32_t)width; src.src_h = (uint32_t)height;
-	src.n_frames = (uint32_t)num_of_frames; src.first = 1; src.device = agmv_hip_ctx_device(ctx());
+	src.device = agmv_hip_ctx_device(ctx());
 	a = CreateAGMV(schedule == AGMV_SCHEDULE_ADAPTIVE ? num_of_frames - 1 : num_of_frames, width, height, frames_per_second);
 	if (g_audio.d_pcm) attach_audio_dev(a);
 	encode_sequence(a, filename, &src, schedule, 1, num_of_frames, width, height, opt, quality, compression);
@@ -817,67 +815,71 @@ static int encode_frames_dev(const char* filename, const void* d_frames, AGMV_PI
 int AGMV_EncodeFramesFmtDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 width, u32 height,
                             u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
 {
-	const int rc = encode_frames_dev(filename, d_frames, fmt, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule);
-	memset(&g_audio, 0, sizeof(g_audio));                      /* a pending track is consumed whatever the call returns */
-	return rc;
+	return audio_consumed(encode_frames_dev(filename, d_frames, fmt, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule));
 }
 
 int AGMV_EncodeFramesDev(const char* filename, const unsigned* d_frames, u32 num_of_frames, u32 width, u32 height,
                          u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
 {
-	return AGMV_EncodeFramesFmtDev(filename, d_frames, AGMV_PIXFMT_XRGB32, num_of_frames, width, height, frames_per_second, opt, quality, compression,
-	                               schedule);
+	return AGMV_EncodeFramesFmtDev(filename, d_frames, AGMV_PIXFMT_XRGB32, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule);
 }
 
-/* The clip scaled to width x height first (include/agmv.h has the two rules): the scaled XRGB32 clip D is materialised once on
-   the library's device -- the source is read once in its own layout, where the histogram, the similarity and the encode would
-   each read it -- and AGMV_EncodeFramesDev runs on D.  Nothing of the source's size or layout is allocated. */
-static int encode_frames_scaled_dev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height,
-                                   u32 width, u32 height, AGMV_SCALE filter, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
-                                   AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+/* A clip that is not encoded as it lies there (a target size, a tensor; include/agmv.h has the rules): the XRGB32 clip it stands for
+   is materialised once on the library's device -- the source is read once in its own layout, where the histogram, the similarity
+   and the encode would each read it -- and AGMV_EncodeFramesDev runs on that.  Nothing of the source's size or layout is allocated.
+   How the clip is filled: the box filter, a gather through agmv_scale_index, or agmv_hip_tensor_to_xrgb_async. */
+typedef struct clip_fill {
+	enum { FILL_AREA, FILL_NEAREST, FILL_TENSOR } how;
+	const void* d_src;
+	int fmt;                               /* the AGMV_PIXFMT of d_src; FILL_TENSOR: its AGMV_TENSORFMT */
+	uint32_t src_w, src_h;                 /* of a source frame (FILL_TENSOR: not read, the clip has the tensor's size) */
+	const float* ab;                       /* FILL_TENSOR: a[3] then b[3] of the reading rule */
+} clip_fill;
+
+/* -4 where the clip (or the index of FILL_NEAREST) cannot be allocated, else what encode_frames_dev returns for the clip */
+static int encode_materialised(const char* filename, const clip_fill* f, u32 num_of_frames, u32 width, u32 height, u32 frames_per_second, AGMV_OPT opt,
+                               AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
 {
-	agmv_hip_ctx* c;
+	agmv_hip_ctx* c = ctx();
+	const uint32_t n = (uint32_t)num_of_frames, w = (uint32_t)width, h = (uint32_t)height;
+	const size_t npx = (size_t)w * h;
+	const int tensor = f->how == FILL_TENSOR;
+	uint32_t *d_clip = (uint32_t*)agmv_hip_malloc_on(c, 4 * npx * num_of_frames), *d_index = NULL, *index = NULL;
 	void* stream;
-	uint32_t *d_scaled, *d_index = NULL, *index = NULL;
+	int failed, rc;
+	if (!d_clip) return -4;
+	if (f->how == FILL_NEAREST) {
+		index = agmv_scale_index(f->src_w, f->src_h, w, h);
+		d_index = (uint32_t*)agmv_hip_malloc_on(c, 4 * npx);
+		if (!index || !d_index) { free(index); agmv_hip_free_on(c, d_index); agmv_hip_free_on(c, d_clip); return -4; }
+	}
+	stream = agmv_hip_stream_create(c);
+	if (!stream) agmv_die(tensor ? "stream for the tensor clip" : "stream for the scaled clip");
+	if (tensor) failed = agmv_hip_tensor_to_xrgb_async(c, f->fmt, f->d_src, npx, n, f->ab, d_clip, stream);
+	else if (f->how == FILL_AREA) failed = agmv_hip_scale_area_dev(c, f->fmt, f->d_src, f->src_w, f->src_h, n, w, h, d_clip, stream);
+	else failed = agmv_hip_memcpy_async(c, d_index, index, 4 * npx, 0, stream) ||
+	              agmv_fmt_gather(c, f->fmt, f->src_w, f->src_h, f->d_src, n, d_index, npx, d_clip, stream);
+	if (failed || agmv_hip_stream_sync(c, stream)) agmv_die(tensor ? "tensor clip" : "frame scale");
+	agmv_hip_stream_destroy(c, stream);
+	free(index); agmv_hip_free_on(c, d_index);
+	rc = encode_frames_dev(filename, d_clip, AGMV_PIXFMT_XRGB32, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule);
+	agmv_hip_free_on(c, d_clip);
+	return rc;
+}
+
+/* what AGMV_EncodeFramesScaledDev refuses before a device is opened, in its order: -1, -5, -3 and only then -2 */
+static int encode_scaled_refused(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height, u32 width,
+                                 u32 height, AGMV_SCALE filter, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+{
 	const unsigned long long src_px = (unsigned long long)src_width * src_height;
-	size_t npx;
-	int sw, sh, failed, rc;
+	int sw, sh, rc;
 	if (!known_pixfmt((int)fmt) || !filename || !d_frames || (filter != AGMV_SCALE_NEAREST && filter != AGMV_SCALE_AREA)) return -1;
-	if (opt < AGMV_OPT_I || opt > AGMV_OPT_NDS || quality < AGMV_HIGH_QUALITY || quality > AGMV_LOW_QUALITY ||
-	    (compression != AGMV_LZSS_COMPRESSION && compression != AGMV_LZ77_COMPRESSION) ||
-	    (schedule != AGMV_SCHEDULE_FULL && schedule != AGMV_SCHEDULE_PDIFS && schedule != AGMV_SCHEDULE_ADAPTIVE))
-		return -1;
-	if (schedule == AGMV_SCHEDULE_ADAPTIVE && g_audio.d_pcm) return -5;
+	rc = encode_args_refused(num_of_frames, opt, quality, compression, schedule);
+	if (rc == -1 || rc == -5) return rc;
 	scaled_size(opt, &sw, &sh);
 	if (sw || bad_geometry((uint32_t)width, (uint32_t)height) || width > 0xFFFFFFFFul || height > 0xFFFFFFFFul) return -3;
 	if (src_width == 0 || src_height == 0 || src_width > 0xFFFFFFFFul || src_height > 0xFFFFFFFFul || src_px > (1ull << 28)) return -3;
 	if (filter == AGMV_SCALE_AREA && (width > src_width || height > src_height || src_px > (1ull << 24))) return -3;
-	if (num_of_frames < (schedule == AGMV_SCHEDULE_FULL ? 1u : (heavy_pdifs(opt) ? 2u : 4u)) || num_of_frames > 0x7FFFFFFFul) return -2;
-
-	c = ctx();
-	npx = (size_t)width * height;
-	d_scaled = (uint32_t*)agmv_hip_malloc_on(c, 4 * npx * num_of_frames);
-	if (!d_scaled) return -4;
-	if (filter == AGMV_SCALE_NEAREST) {
-		index = agmv_scale_index((uint32_t)src_width, (uint32_t)src_height, (uint32_t)width, (uint32_t)height);
-		d_index = (uint32_t*)agmv_hip_malloc_on(c, 4 * npx);
-		if (!index || !d_index) { free(index); agmv_hip_free_on(c, d_index); agmv_hip_free_on(c, d_scaled); return -4; }
-	}
-	stream = agmv_hip_stream_create(c);
-	if (!stream) agmv_die("stream for the scaled clip");
-	if (filter == AGMV_SCALE_AREA)
-		failed = agmv_hip_scale_area_dev(c, (int)fmt, d_frames, (uint32_t)src_width, (uint32_t)src_height, (uint32_t)num_of_frames, (uint32_t)width,
-		                                 (uint32_t)height, d_scaled, stream);
-	else
-		failed = agmv_hip_memcpy_async(c, d_index, index, 4 * npx, 0, stream) ||
-		         (AGMV_FMT_IS_YUV((int)fmt) ? agmv_hip_yuv_gather_dev(c, (int)fmt, d_frames, (uint32_t)src_width, (uint32_t)src_height, (uint32_t)num_of_frames,
-		                                                             d_index, npx, d_scaled, stream)
-		                                    : agmv_hip_gather_fmt_dev(c, (int)fmt, d_frames, (size_t)src_px, (uint32_t)num_of_frames, d_index, npx, d_scaled, stream));
-	if (failed || agmv_hip_stream_sync(c, stream)) agmv_die("frame scale");
-	agmv_hip_stream_destroy(c, stream);
-	free(index); agmv_hip_free_on(c, d_index);
-	rc = encode_frames_dev(filename, d_scaled, AGMV_PIXFMT_XRGB32, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule);
-	agmv_hip_free_on(c, d_scaled);
 	return rc;
 }
 
@@ -885,56 +887,24 @@ int AGMV_EncodeFramesScaledDev(const char* filename, const void* d_frames, AGMV_
                                u32 width, u32 height, AGMV_SCALE filter, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
                                AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
 {
-	const int rc = encode_frames_scaled_dev(filename, d_frames, fmt, num_of_frames, src_width, src_height, width, height, filter, frames_per_second, opt,
-	                                        quality, compression, schedule);
-	memset(&g_audio, 0, sizeof(g_audio));
-	return rc;
+	const clip_fill f = {filter == AGMV_SCALE_AREA ? FILL_AREA : FILL_NEAREST, d_frames, (int)fmt, (uint32_t)src_width, (uint32_t)src_height, NULL};
+	const int rc = encode_scaled_refused(filename, d_frames, fmt, num_of_frames, src_width, src_height, width, height, filter, opt, quality, compression, schedule);
+	return audio_consumed(rc ? rc : encode_materialised(filename, &f, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule));
 }
 
 /* a normalisation the tensor entry points take: agmv_hip_tensor_table holds the bounds (and needs no device) */
-static int known_tensor(AGMV_TENSORFMT type, const float mean[3], const float std[3], void* table)
-{
-	return mean && std && agmv_hip_tensor_table((int)type, mean, std, table) == 0;
-}
-
-/* A tensor clip (include/agmv.h, "normalised float tensors"): the XRGB32 clip its reading rule gives is materialised once on the
-   library's device, as encode_frames_scaled_dev materialises D, and AGMV_EncodeFramesDev runs on it. */
-static int encode_frames_tensor_dev(const char* filename, const void* d_tensor, AGMV_TENSORFMT type, const float mean[3], const float std[3], u32 num_of_frames,
-                                    u32 width, u32 height, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression,
-                                    AGMV_SCHEDULE schedule)
-{
-	agmv_hip_ctx* c;
-	void* stream;
-	uint32_t table[768], *d_clip;
-	float ab[6];
-	size_t npx;
-	int i, rc;
-	if (!known_tensor(type, mean, std, table)) return -1;
-	rc = encode_frames_refused(filename, d_tensor, num_of_frames, width, height, opt, quality, compression, schedule);
-	if (rc) return rc;
-	for (i = 0; i < 3; i++) { ab[i] = (float)(255.0 * (double)std[i]); ab[3 + i] = (float)(255.0 * (double)mean[i]); }
-	c = ctx();
-	npx = (size_t)width * height;
-	d_clip = (uint32_t*)agmv_hip_malloc_on(c, 4 * npx * num_of_frames);
-	if (!d_clip) return -4;
-	stream = agmv_hip_stream_create(c);
-	if (!stream) agmv_die("stream for the tensor clip");
-	if (agmv_hip_tensor_to_xrgb_async(c, (int)type, d_tensor, npx, (uint32_t)num_of_frames, ab, d_clip, stream) || agmv_hip_stream_sync(c, stream))
-		agmv_die("tensor clip");
-	agmv_hip_stream_destroy(c, stream);
-	rc = encode_frames_dev(filename, d_clip, AGMV_PIXFMT_XRGB32, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule);
-	agmv_hip_free_on(c, d_clip);
-	return rc;
-}
+static int known_tensor(AGMV_TENSORFMT type, const float* mean, const float* std, void* table) { return mean && std && agmv_hip_tensor_table((int)type, mean, std, table) == 0; }
 
 int AGMV_EncodeFramesTensorDev(const char* filename, const void* d_tensor, AGMV_TENSORFMT type, const float mean[3], const float std[3], u32 num_of_frames,
                                u32 width, u32 height, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression,
                                AGMV_SCHEDULE schedule)
 {
-	const int rc = encode_frames_tensor_dev(filename, d_tensor, type, mean, std, num_of_frames, width, height, frames_per_second, opt, quality, compression,
-	                                        schedule);
-	memset(&g_audio, 0, sizeof(g_audio));
-	return rc;
+	uint32_t table[768];
+	float ab[6];
+	const clip_fill f = {FILL_TENSOR, d_tensor, (int)type, 0, 0, ab};
+	int i, rc = known_tensor(type, mean, std, table) ? encode_frames_refused(filename, d_tensor, num_of_frames, width, height, opt, quality, compression, schedule) : -1;
+	for (i = 0; i < 3 && !rc; i++) { ab[i] = (float)(255.0 * (double)std[i]); ab[3 + i] = (float)(255.0 * (double)mean[i]); }
+	return audio_consumed(rc ? rc : encode_materialised(filename, &f, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule));
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -948,128 +918,88 @@ static void download_quality(agmv_hip_ctx* c, const void* d_q, AGMV_FRAME_QUALIT
 	if (n && (agmv_hip_memcpy_async(c, quality, d_q, n * sizeof(AGMV_FRAME_QUALITY), 1, NULL) || agmv_hip_stream_sync(c, NULL))) agmv_die("quality download");
 }
 
-/* d_dst NULL: AGMV_DecodeAGMV / AGMV_DecodeVideo, every frame to its BMP.  Else AGMV_DecodeFramesFmtDev: up to cap_frames frames
-   in the layout `fmt` into d_dst, their number into *decoded; or, with `quality` (host memory), AGMV_MeasureFileDev: d_dst is the
-   reference clip of exactly cap_frames frames, only read, and the entries of the *decoded frames measured land in quality[] -- made
-   on the device, downloaded once.  With `scale` (AGMV_DecodeFramesScaledDev) the frames of d_dst have its size.  *info (may be NULL)
-   = the header's; with info_only nothing else happens.  Returns an Error, or -3 where the reference cannot correspond to the file,
-   or -4 where the box filter cannot scale the file's frames to the target (both before a device is opened). */
-static int decode_file(const char* filename, u8 img_type, void* d_dst, int fmt, const agmv_scale* scale, AGMV_FRAME_QUALITY* quality, u32 cap_frames,
-                       int info_only, AGMV_INFO* info, unsigned long* decoded)
+/* An .agmv file the decoders read: agmv_file_open reads the header (and fills *info, which may be NULL), agmv_file_slurp then holds the whole file
+   in memory, `len` bytes with 16 zero bytes behind them, `pos` the first byte behind the header.  Both return an Error; agmv_file_close after either. */
+typedef struct agmv_file { FILE* f; AGMV hdr; u8* image; size_t len, pos; } agmv_file;
+
+static int agmv_file_open(agmv_file* af, const char* filename, AGMV_INFO* info)
 {
-	void* d_quality = NULL;
-	FILE* f = fopen(filename, "rb");
-	AGMV hdr_obj;
-	u8* file;
-	long flen;
-	size_t pos, got, npx;
-	uint32_t w, h, nframes;
-	unsigned cap;
-	int err, m512;
-	agmv_hip_ctx* c;
-	uint32_t pal[512];
-	int i;
-	if (!f) return FILE_NOT_FOUND_ERR;
-	if (img_type != AGMV_IMG_BMP) { fclose(f); require_bmp(img_type); }
-	memset(&hdr_obj, 0, sizeof(hdr_obj.header));
-	err = AGMV_DecodeHeader(f, &hdr_obj);
-	if (err != NO_ERR) { fclose(f); return err; }
-	if (info) *info = AGMV_GetVideoInfo(&hdr_obj);
-	if (info_only) { fclose(f); return NO_ERR; }
-	if (quality && (hdr_obj.header.num_of_frames != cap_frames || (AGMV_FMT_IS_YUV(fmt) && ((hdr_obj.header.width | hdr_obj.header.height) & 1)))) {
-		fclose(f);
-		return -3;
-	}
-	if (scale && scale->filter == AGMV_SCALE_AREA && (scale->w > hdr_obj.header.width || scale->h > hdr_obj.header.height ||
-	                                                   (unsigned long long)hdr_obj.header.width * hdr_obj.header.height > (1ull << 24))) {
-		fclose(f);
-		return -4;
-	}
-	pos = (size_t)ftell(f);
-	fseek(f, 0, SEEK_END); flen = ftell(f); fseek(f, 0, SEEK_SET);
-	file = (u8*)malloc((size_t)flen + 16);
-	if (!file) { fclose(f); return MEMORY_CORRUPTION_ERR; }
-	got = fread(file, 1, (size_t)flen, f);
-	fclose(f);
-	memset(file + got, 0, 16);
-	w = (uint32_t)hdr_obj.header.width; h = (uint32_t)hdr_obj.header.height;
-	if (bad_geometry(w, h)) { free(file); return INVALID_HEADER_FORMATTING_ERR; }
-	npx = (size_t)w * h;
-	m512 = hdr_obj.header.version == 1 || hdr_obj.header.version == 3;
-	if (!g_ctx) { const char* e = getenv("AGMV_DEVICE"); g_ctx = agmv_hip_create(e ? atoi(e) : 0); }
-	c = g_ctx;
-	if (!c) { free(file); return gpu_failed("cannot open the GPU"); }
-	for (i = 0; i < 256; i++) { pal[i] = (uint32_t)hdr_obj.header.palette0[i]; pal[256 + i] = m512 ? (uint32_t)hdr_obj.header.palette1[i] : 0; }
-	if (!(g_pal_mode == m512 && memcmp(pal, g_pal, sizeof(pal)) == 0)) {
-		if (agmv_hip_set_palette(c, pal, pal + 256, m512, NULL) || agmv_hip_sync()) { free(file); return gpu_failed("palette upload"); }
-		memcpy(g_pal, pal, sizeof(pal));
-		g_pal_mode = m512;
-	}
-	cap = batch_frames(npx);
-	nframes = (uint32_t)hdr_obj.header.num_of_frames;
-	if (d_dst && nframes > cap_frames) nframes = (uint32_t)cap_frames;
-	if (quality && nframes) {
-		d_quality = agmv_hip_malloc_on(c, (size_t)nframes * sizeof(AGMV_FRAME_QUALITY));
-		if (!d_quality) { free(file); return gpu_failed("result array for the measurement"); }
-	}
-	err = agmv_decode_stream(c, file, got, pos, w, h, nframes, hdr_obj.header.version, hdr_obj.header.total_audio_duration != 0, cap,
-	                         lz_threads(), d_dst, fmt, scale, d_quality, d_dst ? decoded : &g_export_count);
-	if (d_quality && err == NO_ERR) download_quality(c, d_quality, quality, (size_t)*decoded);
-	agmv_hip_free_on(c, d_quality);
-	free(file);
+	int err;
+	af->image = NULL;
+	if (!(af->f = filename ? fopen(filename, "rb") : NULL)) return FILE_NOT_FOUND_ERR;
+	memset(&af->hdr, 0, sizeof(af->hdr.header));
+	err = AGMV_DecodeHeader(af->f, &af->hdr);
+	if (err == NO_ERR && info) *info = AGMV_GetVideoInfo(&af->hdr);
 	return err;
 }
 
-int AGMV_DecodeVideo(const char* filename, u8 img_type) { return decode_file(filename, img_type, NULL, AGMV_PIXFMT_XRGB32, NULL, NULL, 0, 0, NULL, NULL); }
-
-/* AGMV_DecodeAGMV with another destination: frame k of the file (0-based) as the k-th frame of the layout `fmt` in d_frames
-   (device memory of this library's context) instead of in quick_export_<k + 1>.bmp.  At most cap_frames frames; returns the
-   number decoded or a negative Error.  With d_frames NULL nothing is decoded and only *info is filled. */
-int AGMV_DecodeFramesFmtDev(const char* filename, void* d_frames, AGMV_PIXFMT fmt, u32 cap_frames, AGMV_INFO* info)
+static int agmv_file_slurp(agmv_file* af)
 {
-	unsigned long decoded = 0;
-	int err;
-	if (!known_pixfmt((int)fmt)) return -1;
-	err = filename ? decode_file(filename, AGMV_IMG_BMP, d_frames, (int)fmt, NULL, NULL, cap_frames, d_frames == NULL, info, &decoded) : FILE_NOT_FOUND_ERR;
-	return err == NO_ERR ? (int)decoded : -err;
+	long flen;
+	af->pos = (size_t)ftell(af->f);
+	fseek(af->f, 0, SEEK_END); flen = ftell(af->f); fseek(af->f, 0, SEEK_SET);
+	af->image = (u8*)malloc((size_t)flen + 16);
+	if (!af->image) return MEMORY_CORRUPTION_ERR;
+	af->len = fread(af->image, 1, (size_t)flen, af->f);
+	memset(af->image + af->len, 0, 16);
+	return NO_ERR;
 }
 
-/* AGMV_DecodeFramesFmtDev with a target size (include/agmv.h has the rules): the batches are decoded at the file's size and the
-   sink scales each into its place in d_frames, in the layout `fmt`.  The checks that need no device come first, in the header's order. */
-int AGMV_DecodeFramesScaledDev(const char* filename, void* d_frames, AGMV_PIXFMT fmt, u32 width, u32 height, AGMV_SCALE filter, u32 cap_frames,
-                               AGMV_INFO* info)
+static void agmv_file_close(agmv_file* af) { if (af->f) fclose(af->f); free(af->image); }
+
+/* the public return value of a decoder: the frames (samples) it made, or its Error negated; -3 and -4 of decode_file are negative already.
+   (The count by address: it is read here, behind the decode that the caller's expression holds as the other argument.) */
+static int decode_result(int err, const unsigned long* count) { return err == NO_ERR ? (int)*count : err < 0 ? err : -err; }
+
+/* The file's frames into `sink`: every frame for EXPORT (AGMV_DecodeAGMV / AGMV_DecodeVideo), up to cap_frames frames for the other
+   kinds, their number added to *sink->count.  For MEASURE (AGMV_MeasureFileDev) the reference clip holds exactly cap_frames frames,
+   the device array sink->measure.d_quality is made here, and the entries of the frames measured land in quality[] (host memory),
+   downloaded once.  *info (may be NULL) = the header's; with info_only nothing else happens.  Returns an Error, or before a device is opened
+   -3 where the reference cannot correspond to the file, -4 where the box filter cannot scale the file's frames to the sink's target. */
+static int decode_file(const char* filename, u8 img_type, agmv_sink* sink, AGMV_FRAME_QUALITY* quality, u32 cap_frames, int info_only, AGMV_INFO* info)
 {
-	unsigned long decoded = 0;
-	agmv_scale sc;
-	int err;
-	if (!filename || !known_pixfmt((int)fmt) || (filter != AGMV_SCALE_NEAREST && filter != AGMV_SCALE_AREA && filter != AGMV_SCALE_BILINEAR)) return -1;
-	if (width == 0 || height == 0 || width > (1ul << 28) || height > (1ul << 28) || (unsigned long long)width * height > (1ull << 28)) return -4;
-	sc.w = (uint32_t)width; sc.h = (uint32_t)height; sc.filter = (int)filter; sc.tensor = 0; sc.table = NULL;
-	err = decode_file(filename, AGMV_IMG_BMP, d_frames, (int)fmt, &sc, NULL, cap_frames, d_frames == NULL, info, &decoded);
-	return err == NO_ERR ? (int)decoded : err < 0 ? err : -err;
+	const agmv_target* to = agmv_sink_target(sink);
+	const int measure = sink->kind == AGMV_SINK_MEASURE;
+	agmv_file af;
+	const AGMV_MAIN_HEADER* hd = &af.hdr.header;
+	uint32_t nframes, pal[512];
+	int err = agmv_file_open(&af, filename, info), m512, i;
+	agmv_hip_ctx* c;
+	if (err != FILE_NOT_FOUND_ERR) require_bmp(img_type);        /* (the file exists) */
+	if (err == NO_ERR && !info_only) {
+		/* (a rule of the API, not a dispatch: 4:2:0 chroma cannot lie over an odd frame) */
+		if (measure && (hd->num_of_frames != cap_frames || (AGMV_FMT_IS_YUV(sink->measure.fmt) && ((hd->width | hd->height) & 1)))) err = -3;
+		else if (to && to->filter == AGMV_SCALE_AREA && (to->w > hd->width || to->h > hd->height || (unsigned long long)hd->width * hd->height > (1ull << 24))) err = -4;
+		else if ((err = agmv_file_slurp(&af)) == NO_ERR && bad_geometry((uint32_t)hd->width, (uint32_t)hd->height)) err = INVALID_HEADER_FORMATTING_ERR;
+	}
+	if (err != NO_ERR || info_only) { agmv_file_close(&af); return err; }
+	m512 = hd->version == 1 || hd->version == 3;
+	c = open_ctx();
+	if (!c) { agmv_file_close(&af); return gpu_failed("cannot open the GPU"); }
+	for (i = 0; i < 256; i++) { pal[i] = (uint32_t)hd->palette0[i]; pal[256 + i] = m512 ? (uint32_t)hd->palette1[i] : 0; }
+	if (!(g_pal_mode == m512 && memcmp(pal, g_pal, sizeof(pal)) == 0)) {
+		if (agmv_hip_set_palette(c, pal, pal + 256, m512, NULL) || agmv_hip_sync()) { agmv_file_close(&af); return gpu_failed("palette upload"); }
+		memcpy(g_pal, pal, sizeof(pal));
+		g_pal_mode = m512;
+	}
+	nframes = (uint32_t)hd->num_of_frames;
+	if (sink->kind != AGMV_SINK_EXPORT && nframes > cap_frames) nframes = (uint32_t)cap_frames;
+	if (measure && nframes) {
+		sink->measure.d_quality = agmv_hip_malloc_on(c, (size_t)nframes * sizeof(AGMV_FRAME_QUALITY));
+		if (!sink->measure.d_quality) { agmv_file_close(&af); return gpu_failed("result array for the measurement"); }
+	}
+	err = agmv_decode_stream(c, af.image, af.len, af.pos, (uint32_t)hd->width, (uint32_t)hd->height, nframes, hd->version, hd->total_audio_duration != 0,
+	                         batch_frames((size_t)hd->width * hd->height), lz_threads(), sink);
+	if (measure && err == NO_ERR) download_quality(c, sink->measure.d_quality, quality, (size_t)*sink->count);
+	if (measure) agmv_hip_free_on(c, sink->measure.d_quality);
+	agmv_file_close(&af);
+	return err;
 }
 
-/* AGMV_DecodeFramesScaledDev into a tensor clip (include/agmv.h, "normalised float tensors"): the same checks in the same order,
-   the table built here and uploaded once by the sink; width == height == 0 is the file's size, without a filter. */
-int AGMV_DecodeFramesTensorDev(const char* filename, void* d_tensor, AGMV_TENSORFMT type, const float mean[3], const float std[3], u32 width, u32 height,
-                               AGMV_SCALE filter, u32 cap_frames, AGMV_INFO* info)
+int AGMV_DecodeVideo(const char* filename, u8 img_type)
 {
-	unsigned long decoded = 0;
-	uint32_t table[768];
-	agmv_scale sc;
-	const int sized = width != 0 || height != 0;
-	int err;
-	if (!filename || !known_tensor(type, mean, std, table)) return -1;
-	if (sized && filter != AGMV_SCALE_NEAREST && filter != AGMV_SCALE_AREA && filter != AGMV_SCALE_BILINEAR) return -1;
-	if (sized && (width == 0 || height == 0 || width > (1ul << 28) || height > (1ul << 28) || (unsigned long long)width * height > (1ull << 28))) return -4;
-	sc.w = (uint32_t)width; sc.h = (uint32_t)height; sc.filter = sized ? (int)filter : 0; sc.tensor = (int)type; sc.table = table;
-	err = decode_file(filename, AGMV_IMG_BMP, d_tensor, AGMV_PIXFMT_XRGB32, &sc, NULL, cap_frames, d_tensor == NULL, info, &decoded);
-	return err == NO_ERR ? (int)decoded : err < 0 ? err : -err;
-}
-
-int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frames, AGMV_INFO* info)
-{
-	return AGMV_DecodeFramesFmtDev(filename, d_frames, AGMV_PIXFMT_XRGB32, cap_frames, info);
+	agmv_sink sink = {AGMV_SINK_EXPORT, &g_export_count, {{0}}};
+	return decode_file(filename, img_type, &sink, NULL, 0, 0, NULL);
 }
 
 /* the video frames are exported exactly like the reference does; no quick_export.wav / .aiff is written here (callers of this
@@ -1077,58 +1007,92 @@ int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frame
 int AGMV_DecodeAGMV(const char* filename, u8 img_type, AGMV_AUDIO_TYPE audio_type)
 {
 	(void)audio_type;
-	return decode_file(filename, img_type, NULL, AGMV_PIXFMT_XRGB32, NULL, NULL, 0, 0, NULL, NULL);
+	return AGMV_DecodeVideo(filename, img_type);
+}
+
+/* AGMV_DecodeAGMV with another destination (include/agmv.h): at most cap_frames frames into d_frames in the layout `fmt`, at the target
+   `to` of AGMV_DecodeFramesScaledDev or, with NULL, at the file's size.  With d_frames NULL nothing is decoded and only *info is filled. */
+static int decode_frames(const char* filename, void* d_frames, AGMV_PIXFMT fmt, const agmv_target* to, u32 cap_frames, AGMV_INFO* info)
+{
+	unsigned long decoded = 0;
+	agmv_sink sink = {AGMV_SINK_FRAMES, &decoded, .frames = {d_frames, (int)fmt, to ? *to : (agmv_target){0, 0, 0}}};
+	return decode_result(decode_file(filename, AGMV_IMG_BMP, &sink, NULL, cap_frames, d_frames == NULL, info), &decoded);
+}
+
+int AGMV_DecodeFramesFmtDev(const char* filename, void* d_frames, AGMV_PIXFMT fmt, u32 cap_frames, AGMV_INFO* info)
+{
+	return known_pixfmt((int)fmt) ? decode_frames(filename, d_frames, fmt, NULL, cap_frames, info) : -1;
+}
+
+int AGMV_DecodeFramesDev(const char* filename, unsigned* d_frames, u32 cap_frames, AGMV_INFO* info)
+{
+	return AGMV_DecodeFramesFmtDev(filename, d_frames, AGMV_PIXFMT_XRGB32, cap_frames, info);
+}
+
+/* a target the sized decoders take: -1 for an unknown filter, then -4 for a width or height of zero or more than 2^28 target pixels */
+static int target_refused(u32 width, u32 height, AGMV_SCALE filter)
+{
+	if (filter != AGMV_SCALE_NEAREST && filter != AGMV_SCALE_AREA && filter != AGMV_SCALE_BILINEAR) return -1;
+	if (width == 0 || height == 0 || width > (1ul << 28) || height > (1ul << 28) || (unsigned long long)width * height > (1ull << 28)) return -4;
+	return 0;
+}
+
+/* AGMV_DecodeFramesFmtDev with a target size (include/agmv.h has the rules); the checks that need no device come first, in the header's order */
+int AGMV_DecodeFramesScaledDev(const char* filename, void* d_frames, AGMV_PIXFMT fmt, u32 width, u32 height, AGMV_SCALE filter, u32 cap_frames,
+                               AGMV_INFO* info)
+{
+	const agmv_target to = {(uint32_t)width, (uint32_t)height, (int)filter};
+	const int refused = filename && known_pixfmt((int)fmt) ? target_refused(width, height, filter) : -1;
+	return refused ? refused : decode_frames(filename, d_frames, fmt, &to, cap_frames, info);
+}
+
+/* AGMV_DecodeFramesScaledDev into a tensor clip: the same checks in the same order, the table built here; width == height == 0 is the file's size */
+int AGMV_DecodeFramesTensorDev(const char* filename, void* d_tensor, AGMV_TENSORFMT type, const float mean[3], const float std[3], u32 width, u32 height,
+                               AGMV_SCALE filter, u32 cap_frames, AGMV_INFO* info)
+{
+	unsigned long decoded = 0;
+	uint32_t table[768];
+	const int sized = width != 0 || height != 0;
+	agmv_sink sink = {AGMV_SINK_TENSOR, &decoded, .tensor = {d_tensor, (int)type, table, {(uint32_t)width, (uint32_t)height, sized ? (int)filter : 0}}};
+	const int refused = filename && known_tensor(type, mean, std, table) ? (sized ? target_refused(width, height, filter) : 0) : -1;
+	return refused ? refused : decode_result(decode_file(filename, AGMV_IMG_BMP, &sink, NULL, cap_frames, d_tensor == NULL, info), &decoded);
 }
 
 /* The file's audio track into device memory in the layout `fmt` (include/agmv.h): the AGAC payloads gathered on the host into
    one pinned buffer, one upload, one expand kernel.  No video is decoded. */
 int AGMV_DecodeAudioDev(const char* filename, void* d_pcm, AGMV_PCMFMT fmt, u32 cap_samples, AGMV_INFO* info)
 {
-	FILE* f;
-	AGMV hdr_obj;
-	u8* file;
-	uint8_t *h_codes, *d_codes;
-	long flen;
-	size_t pos, got, cap, n;
-	u32 channels;
-	int err, failed;
+	agmv_file af;
+	const AGMV_MAIN_HEADER* hd = &af.hdr.header;
+	uint8_t *h_codes = NULL, *d_codes;
+	unsigned long n = 0;
+	u32 channels = 0;
+	int err;
 	agmv_hip_ctx* c;
 	void* stream;
 	if (fmt != AGMV_PCM_S16 && fmt != AGMV_PCM_U8 && fmt != AGMV_PCM_F32P) return -1;
-	f = filename ? fopen(filename, "rb") : NULL;
-	if (!f) return -FILE_NOT_FOUND_ERR;
-	memset(&hdr_obj, 0, sizeof(hdr_obj.header));
-	err = AGMV_DecodeHeader(f, &hdr_obj);
-	if (err != NO_ERR) { fclose(f); return -err; }
-	if (info) *info = AGMV_GetVideoInfo(&hdr_obj);
-	channels = hdr_obj.header.num_of_channels;
-	if (!d_pcm || hdr_obj.header.total_audio_duration == 0) { fclose(f); return 0; }
-	if ((hdr_obj.header.bits_per_sample == 16) == (fmt == AGMV_PCM_U8) || channels == 0 || (fmt == AGMV_PCM_F32P && channels > 8)) { fclose(f); return -1; }
-	pos = (size_t)ftell(f);
-	fseek(f, 0, SEEK_END); flen = ftell(f); fseek(f, 0, SEEK_SET);
-	file = (u8*)malloc((size_t)flen + 16);
-	if (!file) { fclose(f); return -MEMORY_CORRUPTION_ERR; }
-	got = fread(file, 1, (size_t)flen, f);
-	fclose(f);
-	cap = hdr_obj.header.audio_size < cap_samples ? hdr_obj.header.audio_size : cap_samples;
-	h_codes = (uint8_t*)agmv_hip_host_alloc(cap ? cap : 1);
-	if (!h_codes) { free(file); return -gpu_failed("pinned buffer for the audio codes"); }
-	n = agmv_gather_audio(file, got, pos, (uint32_t)hdr_obj.header.num_of_frames, h_codes, cap);
-	free(file);
-	if (n > 0x7FFFFFFFu) n = 0x7FFFFFFFu;                      /* the return value is an int */
-	n -= n % channels;
-	if (n == 0) { agmv_hip_host_free(h_codes); return 0; }
-	if (!g_ctx) { const char* e = getenv("AGMV_DEVICE"); g_ctx = agmv_hip_create(e ? atoi(e) : 0); }
-	c = g_ctx;
-	if (!c) { agmv_hip_host_free(h_codes); return -gpu_failed("cannot open the GPU"); }
+	err = agmv_file_open(&af, filename, info);
+	if (err == NO_ERR && d_pcm && hd->total_audio_duration != 0) {
+		const size_t cap = hd->audio_size < cap_samples ? hd->audio_size : cap_samples;
+		channels = hd->num_of_channels;
+		if ((hd->bits_per_sample == 16) == (fmt == AGMV_PCM_U8) || channels == 0 || (fmt == AGMV_PCM_F32P && channels > 8)) err = -1;
+		else if ((err = agmv_file_slurp(&af)) == NO_ERR && !(h_codes = (uint8_t*)agmv_hip_host_alloc(cap ? cap : 1))) err = gpu_failed("pinned buffer for the audio codes");
+		if (err == NO_ERR) n = agmv_gather_audio(af.image, af.len, af.pos, (uint32_t)hd->num_of_frames, h_codes, cap);
+		if (n > 0x7FFFFFFFu) n = 0x7FFFFFFFu;                  /* the return value is an int */
+		if (n) n -= n % channels;
+	}
+	agmv_file_close(&af);
+	if (err != NO_ERR || n == 0) { agmv_hip_host_free(h_codes); return decode_result(err, &n); }
+	c = open_ctx();
+	if (!c) { agmv_hip_host_free(h_codes); return decode_result(gpu_failed("cannot open the GPU"), &n); }
 	stream = agmv_hip_stream_create(c);
 	d_codes = (uint8_t*)agmv_hip_malloc_on(c, n);
-	failed = !stream || !d_codes || agmv_hip_memcpy_async(c, d_codes, h_codes, n, 0, stream) ||
-	         agmv_hip_audio_expand_async(c, (int)fmt, d_codes, channels, n / channels, d_pcm, stream) || agmv_hip_stream_sync(c, stream);
-	if (failed) err = gpu_failed("audio expand");
+	if (!stream || !d_codes || agmv_hip_memcpy_async(c, d_codes, h_codes, n, 0, stream) ||
+	    agmv_hip_audio_expand_async(c, (int)fmt, d_codes, channels, n / channels, d_pcm, stream) || agmv_hip_stream_sync(c, stream))
+		err = gpu_failed("audio expand");
 	agmv_hip_free_on(c, d_codes); agmv_hip_host_free(h_codes);
 	if (stream) agmv_hip_stream_destroy(c, stream);
-	return failed ? -err : (int)n;
+	return decode_result(err, &n);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -1147,8 +1111,7 @@ int AGMV_MeasureFramesDev(const unsigned* d_test, const void* d_ref, AGMV_PIXFMT
 	stream = agmv_hip_stream_create(c);
 	d_q = agmv_hip_malloc_on(c, (size_t)num_of_frames * sizeof(AGMV_FRAME_QUALITY));
 	if (!stream || !d_q) agmv_die("stream and result array for the measurement");
-	if (agmv_hip_measure_frames_async(c, d_test, (int)ref_fmt, d_ref, (uint32_t)width, (uint32_t)height, (uint32_t)num_of_frames, d_q, stream) ||
-	    agmv_hip_stream_sync(c, stream))
+	if (agmv_hip_measure_frames_async(c, d_test, (int)ref_fmt, d_ref, (uint32_t)width, (uint32_t)height, (uint32_t)num_of_frames, d_q, stream) || agmv_hip_stream_sync(c, stream))
 		agmv_die("frame measurement");
 	download_quality(c, d_q, quality, (size_t)num_of_frames);
 	agmv_hip_free_on(c, d_q);
@@ -1159,10 +1122,9 @@ int AGMV_MeasureFramesDev(const unsigned* d_test, const void* d_ref, AGMV_PIXFMT
 int AGMV_MeasureFileDev(const char* filename, const void* d_ref, AGMV_PIXFMT ref_fmt, u32 num_of_frames, AGMV_FRAME_QUALITY* quality, AGMV_INFO* info)
 {
 	unsigned long measured = 0;
-	int err;
+	agmv_sink sink = {AGMV_SINK_MEASURE, &measured, .measure = {d_ref, (int)ref_fmt, NULL}};
 	if (!known_pixfmt((int)ref_fmt) || (quality && !d_ref)) return -1;
-	err = filename ? decode_file(filename, AGMV_IMG_BMP, (void*)d_ref, (int)ref_fmt, NULL, quality, num_of_frames, quality == NULL, info, &measured) : FILE_NOT_FOUND_ERR;
-	return err == NO_ERR ? (int)measured : err < 0 ? err : -err;
+	return decode_result(decode_file(filename, AGMV_IMG_BMP, &sink, quality, num_of_frames, quality == NULL, info), &measured);
 }
 
 /* ------------------------------------------------------------------------------------------

@@ -357,13 +357,8 @@ static const void* src_frame(const agmv_seq* s, long idx)
 static int place_frame(eworker* wk, long idx, uint32_t* dst)
 {
 	agmv_seq* s = wk->s;
-	const size_t fpx = (size_t)s->src.src_w * s->src.src_h;
-	if (AGMV_FMT_IS_YUV(s->src.fmt)) {
-		if (s->d_index) return agmv_hip_yuv_gather_dev(wk->ctx, s->src.fmt, src_frame(s, idx), s->src.src_w, s->src.src_h, 1, s->d_index, s->npx, dst, wk->stream);
-		return agmv_hip_yuv_to_xrgb_dev(wk->ctx, s->src.fmt, src_frame(s, idx), s->src.src_w, s->src.src_h, 1, s->npx, dst, wk->stream);
-	}
-	if (s->d_index) return agmv_hip_gather_fmt_dev(wk->ctx, s->src.fmt, src_frame(s, idx), fpx, 1, s->d_index, s->npx, dst, wk->stream);
-	return agmv_hip_pixels_to_xrgb_dev(wk->ctx, s->src.fmt, src_frame(s, idx), fpx, 1, s->npx, dst, wk->stream);
+	if (s->d_index) return agmv_fmt_gather(wk->ctx, s->src.fmt, s->src.src_w, s->src.src_h, src_frame(s, idx), 1, s->d_index, s->npx, dst, wk->stream);
+	return agmv_fmt_to_xrgb(wk->ctx, s->src.fmt, s->src.src_w, s->src.src_h, src_frame(s, idx), 1, s->npx, dst, wk->stream);
 }
 
 /* one GPU worker: its batches are id = idx, idx + nworkers, ... in order */
@@ -727,9 +722,7 @@ void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start,
 		const u8* d_first = (const u8*)src->d_frames + (size_t)((long)start - src->first) * agmv_fmt_frame_bytes(src->fmt, src->src_w, src->src_h);
 		if ((long)start < src->first || (long)end >= src->first + (long)src->n_frames) agmv_die("internal: frame outside the device clip");
 		if (!d_hist || !stream || agmv_hip_memset_async(ctx, d_hist, 0, 4u << 19, stream)) agmv_die("histogram");
-		if (AGMV_FMT_IS_YUV(src->fmt) ? agmv_hip_yuv_histogram_dev(ctx, src->fmt, d_first, src->src_w, src->src_h, n, px, quality, d_hist, stream)
-		                              : agmv_hip_histogram_fmt_dev(ctx, src->fmt, d_first, fpx, n, px, quality, d_hist, stream))
-			agmv_die("histogram");
+		if (agmv_fmt_histogram(ctx, src->fmt, src->src_w, src->src_h, d_first, n, px, quality, d_hist, stream)) agmv_die("histogram");
 		if (agmv_hip_memcpy_async(ctx, hist, d_hist, 4u << 19, 1, stream) || agmv_hip_stream_sync(ctx, stream)) agmv_die("histogram download");
 		agmv_hip_free_on(ctx, d_hist);
 		agmv_hip_stream_destroy(ctx, stream);
@@ -810,14 +803,30 @@ typedef struct dpipe {
 	agmv_pool* pool;
 	pthread_t th;
 	uint8_t* d_bits; uint32_t *d_bpos, *d_nent, *d_out[2], *d_iframe;
-	void* d_dst;                           /* the sink: NULL = BMP export through d_out / h_out, else the caller's device frames */
-	int fmt;                               /* ... in this AGMV_PIXFMT: XRGB32 is decoded in place, any other through d_out */
-	void* d_quality;                       /* the measuring sink: d_dst is the reference clip, only read; frame k's AGMV_FRAME_QUALITY lands here */
-	agmv_scale scale;                      /* filter != 0: the sink holds frames of scale.w x scale.h; the batch always goes through d_out */
-	                                       /* tensor != 0: ... as a tensor clip of that type (filter 0: at the file's size, which w, h then hold) */
-	uint32_t* d_scaled;                    /* AGMV_SCALE_AREA into another layout than XRGB32: one batch of scaled XRGB32 frames */
+	agmv_sink sink;                        /* where the batches go (agmv_pipeline.h); the four facts below are all that is derived from it */
+	uint32_t* d_scaled;                    /* sink_needs_scaled: one batch of scaled XRGB32 frames */
 	void* d_table;                         /* the tensor sink's table on the device, uploaded once per call */
 } dpipe;
+
+/* A packed XRGB32 clip at the file's size is decoded straight into its place, and the frame before a batch is the one before it there.
+   Every other sink takes the batch from the double buffer d_out, which exists for them alone and where the decoder's state stays. */
+static int sink_in_place(const agmv_sink* s) { return s->kind == AGMV_SINK_FRAMES && s->frames.fmt == AGMV_PIXFMT_XRGB32 && !agmv_sink_target(s); }
+
+/* the box filter makes XRGB32: straight into an XRGB32 clip, through one batch of scaled frames (d_scaled) for any other layout and a tensor */
+static int sink_needs_scaled(const agmv_sink* s)
+{
+	const agmv_target* t = agmv_sink_target(s);
+	return t && t->filter == AGMV_SCALE_AREA && !(s->kind == AGMV_SINK_FRAMES && s->frames.fmt == AGMV_PIXFMT_XRGB32);
+}
+
+/* the bytes of one frame of the destination (MEASURE: of the reference clip); w x h is the file's size */
+static size_t sink_frame_bytes(const agmv_sink* s, uint32_t w, uint32_t h)
+{
+	const agmv_target* t = agmv_sink_target(s);
+	if (t) { w = t->w; h = t->h; }
+	if (s->kind == AGMV_SINK_TENSOR) return agmv_hip_tensor_frame_bytes(s->tensor.type, (size_t)w * h);
+	return agmv_fmt_frame_bytes(s->kind == AGMV_SINK_FRAMES ? s->frames.fmt : s->kind == AGMV_SINK_MEASURE ? s->measure.fmt : AGMV_PIXFMT_XRGB32, w, h);
+}
 
 typedef struct savearg { dpipe* d; dbatch* b; unsigned k; } savearg;
 
@@ -834,9 +843,41 @@ static void save_task(void* p)
 	free(sa);
 }
 
+/* batch b, decoded at `out`, to the sink on the worker's stream: one launch, behind the box filter's where that goes through d_scaled;
+   for EXPORT the download to the slot's pinned frames; nothing for a batch decoded in place */
+static int sink_batch(dpipe* d, const dbatch* b, const uint32_t* out)
+{
+	const agmv_sink* s = &d->sink;
+	const agmv_target* t = agmv_sink_target(s);
+	uint32_t sw = d->w, sh = d->h;                             /* the size of the frames at `out`, the filter still to apply, the target size */
+	int filter = t ? t->filter : 0;
+	const uint32_t tw = t ? t->w : sw, th = t ? t->h : sh;
+	const size_t at = (size_t)b->first * sink_frame_bytes(s, d->w, d->h);
+	if (sink_needs_scaled(s)) {
+		if (agmv_hip_scale_area_dev(d->ctx, AGMV_PIXFMT_XRGB32, out, sw, sh, b->n, tw, th, d->d_scaled, d->stream)) return -1;
+		out = d->d_scaled; sw = tw; sh = th; filter = 0;
+	}
+	switch (s->kind) {
+	case AGMV_SINK_EXPORT:
+		return agmv_hip_memcpy_async(d->ctx, b->h_out, out, d->npx * 4 * b->n, 1, d->stream);
+	case AGMV_SINK_MEASURE:
+		return agmv_hip_measure_frames_async(d->ctx, out, s->measure.fmt, (const u8*)s->measure.d_ref + at, sw, sh, b->n,
+		                                     (u8*)s->measure.d_quality + sizeof(AGMV_FRAME_QUALITY) * (size_t)b->first, d->stream);
+	case AGMV_SINK_TENSOR:
+		return agmv_hip_tensor_from_xrgb_async(d->ctx, s->tensor.type, out, sw, sh, b->n, filter, tw, th, d->d_table, (u8*)s->tensor.d_dst + at, d->stream);
+	default: {
+		void* dst = (u8*)s->frames.d_dst + at;
+		if (filter == AGMV_SCALE_AREA) return agmv_hip_scale_area_dev(d->ctx, AGMV_PIXFMT_XRGB32, out, sw, sh, b->n, tw, th, (uint32_t*)dst, d->stream);
+		if (filter) return agmv_hip_scale_frames_async(d->ctx, filter, out, sw, sh, b->n, s->frames.fmt, tw, th, dst, d->stream);
+		return sink_in_place(s) ? 0 : agmv_fmt_from_xrgb(d->ctx, s->frames.fmt, tw, th, out, b->n, dst, d->stream);      /* XRGB32 to the caller's layout */
+	}
+	}
+}
+
 static void* dworker_main(void* p)
 {
 	dpipe* d = (dpipe*)p;
+	const int direct = sink_in_place(&d->sink), to_bmp = d->sink.kind == AGMV_SINK_EXPORT;
 	unsigned id, prev_n = 0;
 	int have_state = 0;
 	for (id = 0;; id++) {
@@ -851,11 +892,7 @@ static void* dworker_main(void* p)
 		while (!(id < d->nfilled) && !d->closing) pthread_cond_wait(&d->cv, &d->mu);
 		if (id >= d->nfilled) { pthread_mutex_unlock(&d->mu); break; }
 		pthread_mutex_unlock(&d->mu);
-		/* with a packed sink the batch is decoded straight into its place, and the frame before it is the one before it there;
-		   a sink in another layout or at another size, and the measuring sink, take the batch from the double buffer, where the
-		   decoder's state stays (at the file's size) */
-		const int direct = d->d_dst && !d->d_quality && !d->scale.filter && !d->scale.tensor && d->fmt == AGMV_PIXFMT_XRGB32;
-		out = direct ? (uint32_t*)d->d_dst + (size_t)b->first * d->npx : d->d_out[id & 1];
+		out = direct ? (uint32_t*)d->sink.frames.d_dst + (size_t)b->first * d->npx : d->d_out[id & 1];
 		prev = !have_state ? NULL : direct ? out - d->npx : d->d_out[(id - 1) & 1] + (size_t)(prev_n - 1) * d->npx;
 		if (b->d_slab) {                       /* the LZ stage left the rows on the device: wait for their commit, on the device */
 			if (agmv_hip_stream_wait_event(d->ctx, d->stream, b->ready)) goto fail;
@@ -870,43 +907,15 @@ static void* dworker_main(void* p)
 		for (k = 0; k < b->n; k++) if (((b->first + k) & 3u) == 0) last_i = (int)k;
 		if (!have_state && last_i < 0 && agmv_hip_memset_async(d->ctx, d->d_iframe, 0, d->npx * 4, d->stream)) goto fail;
 		if (last_i >= 0 && agmv_hip_memcpy_async(d->ctx, d->d_iframe, out + (size_t)last_i * d->npx, d->npx * 4, 2, d->stream)) goto fail;
-		if (d->d_dst && d->scale.tensor) {                     /* one launch per batch; the box filter first makes its batch of D */
-			const uint32_t tw = d->scale.w, th = d->scale.h;
-			const int area = d->scale.filter == AGMV_SCALE_AREA;
-			u8* sink = (u8*)d->d_dst + (size_t)b->first * agmv_hip_tensor_frame_bytes(d->scale.tensor, (size_t)tw * th);
-			if (area && agmv_hip_scale_area_dev(d->ctx, AGMV_PIXFMT_XRGB32, out, d->w, d->h, b->n, tw, th, d->d_scaled, d->stream)) goto fail;
-			if (agmv_hip_tensor_from_xrgb_async(d->ctx, d->scale.tensor, area ? d->d_scaled : out, area ? tw : d->w, area ? th : d->h, b->n,
-			                                    area ? 0 : d->scale.filter, tw, th, d->d_table, sink, d->stream))
-				goto fail;
-		} else if (d->d_dst && d->scale.filter) {
-			const uint32_t tw = d->scale.w, th = d->scale.h;
-			u8* sink = (u8*)d->d_dst + (size_t)b->first * agmv_fmt_frame_bytes(d->fmt, tw, th);
-			if (d->scale.filter != AGMV_SCALE_AREA) {
-				if (agmv_hip_scale_frames_async(d->ctx, d->scale.filter, out, d->w, d->h, b->n, d->fmt, tw, th, sink, d->stream)) goto fail;
-			} else {                                           /* the box filter makes XRGB32: in place for that sink, else converted from d_scaled */
-				uint32_t* scaled = d->fmt == AGMV_PIXFMT_XRGB32 ? (uint32_t*)sink : d->d_scaled;
-				if (agmv_hip_scale_area_dev(d->ctx, AGMV_PIXFMT_XRGB32, out, d->w, d->h, b->n, tw, th, scaled, d->stream)) goto fail;
-				if (d->fmt != AGMV_PIXFMT_XRGB32 &&
-				    (AGMV_FMT_IS_YUV(d->fmt) ? agmv_hip_yuv_from_xrgb_dev(d->ctx, d->fmt, scaled, tw, th, b->n, sink, d->stream)
-				                             : agmv_hip_pixels_from_xrgb_dev(d->ctx, d->fmt, scaled, b->n, (size_t)tw * th, sink, d->stream)))
-					goto fail;
-			}
-		} else if (d->d_dst && !direct) {
-			u8* sink = (u8*)d->d_dst + (size_t)b->first * agmv_fmt_frame_bytes(d->fmt, d->w, d->h);
-			if (d->d_quality ? agmv_hip_measure_frames_async(d->ctx, out, d->fmt, sink, d->w, d->h, b->n, (u8*)d->d_quality + 96 * (size_t)b->first, d->stream) :
-			    AGMV_FMT_IS_YUV(d->fmt) ? agmv_hip_yuv_from_xrgb_dev(d->ctx, d->fmt, out, d->w, d->h, b->n, sink, d->stream)
-			                            : agmv_hip_pixels_from_xrgb_dev(d->ctx, d->fmt, out, b->n, d->npx, sink, d->stream))
-				goto fail;
-		}
-		if ((!d->d_dst && agmv_hip_memcpy_async(d->ctx, b->h_out, out, d->npx * 4 * b->n, 1, d->stream)) || agmv_hip_stream_sync(d->ctx, d->stream)) goto fail;
+		if (sink_batch(d, b, out) || agmv_hip_stream_sync(d->ctx, d->stream)) goto fail;
 		have_state = 1;
 		prev_n = b->n;
 		pthread_mutex_lock(&d->mu);
-		if (d->d_dst) b->filled = 0;                       /* the frames are where they belong: the slot is free again */
+		if (!to_bmp) b->filled = 0;                        /* the frames are where they belong: the slot is free again */
 		else { b->decoded = 1; b->saves_left = b->n; }
 		pthread_cond_broadcast(&d->cv);
 		pthread_mutex_unlock(&d->mu);
-		for (k = 0; !d->d_dst && k < b->n; k++) {
+		for (k = 0; to_bmp && k < b->n; k++) {
 			savearg* sa = (savearg*)xmalloc(sizeof(*sa));
 			sa->d = d; sa->b = b; sa->k = k;
 			agmv_pool_submit(d->pool, save_task, sa);
@@ -1112,19 +1121,13 @@ static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, dchunk* c, const u8* fil
    The LZ stage of a batch (between locate_chunks and cut_batch) runs on the pool, one frame per task, or with
    AGMV_LZ_DECODE_DEVICE=1 on the GPU (dlz_batch).  The bytes behind bpos that the block parser may read on an over-run are
    those of the reference's ONE persistent buffer: the host stage takes them from `persist` in frame order, which then
-   receives the frame.  The frames go to d_dst (device memory of ctx's device, frame k of the file as a frame of the AGMV_PIXFMT
-   `fmt` at its place there) or, with d_dst NULL, to quick_export_<*export_count + 1 ...>.bmp; *export_count advances by the
-   frames decoded either way.  With d_quality (device memory, 96 bytes per frame) d_dst is a reference clip in `fmt` that is only
-   read: frame k is measured against frame k of it where the other sink converts, and no decoded frame outlives its batch.
-   With `scale` (d_dst set, no d_quality) the frames of d_dst are scale->w x scale->h: the batch is decoded at the file's size into
-   the double buffer, never in place, and the sink step scales it into its place (AGMV_DecodeFramesScaledDev of include/agmv.h).
-   With scale->tensor d_dst is a tensor clip (AGMV_DecodeFramesTensorDev), `fmt` is not read, and scale->filter may be 0. */
+   receives the frame.  The frames go to `sink` (agmv_pipeline.h), whose count advances by the frames decoded.  Whatever the sink, a
+   batch is decoded at the file's size; only a packed XRGB32 clip of that size receives it in place (sink_in_place), every other
+   sink -- another layout, a target size, a tensor, the BMP export, the measurement -- gets it from the double buffer by sink_batch. */
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
-                       int has_audio, unsigned cap_frames, unsigned threads, void* d_dst, int fmt, const agmv_scale* scale, void* d_quality,
-                       unsigned long* export_count)
+                       int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink)
 {
-	const int scaled = scale && (scale->filter || scale->tensor) && d_dst && !d_quality;
-	const int direct = d_dst && !d_quality && !scaled && fmt == AGMV_PIXFMT_XRGB32;     /* decoded in place: no double buffer */
+	const int buffered = !sink_in_place(sink), to_bmp = sink->kind == AGMV_SINK_EXPORT;
 	dpipe d;
 	dlz z;
 	const char* lzv = getenv("AGMV_LZ_DECODE_DEVICE");     /* opt-in: the LZ stage on the GPU (read when a decode starts) */
@@ -1135,58 +1138,49 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	unlz* jobs = lz_dev ? NULL : (unlz*)calloc(cap_frames, sizeof(unlz));
 	uint32_t done = 0;
 	unsigned id = 0, i;
-	int rc = NO_ERR;
+	int rc = MEMORY_CORRUPTION_ERR;                        /* until everything is set up: what any failure on the way there returns */
 	memset(&d, 0, sizeof(d));
 	memset(&z, 0, sizeof(z));
 	d.ctx = ctx; d.w = w; d.h = h; d.npx = npx; d.stride = (cap + 255) & ~(size_t)255;
-	d.cap = cap_frames; d.nslots = 3; d.d_dst = d_dst; d.fmt = fmt; d.d_quality = d_quality;
-	if (scaled) d.scale = *scale;
-	if (scaled && scale->tensor && !scale->filter) { d.scale.w = w; d.scale.h = h; }
+	d.cap = cap_frames; d.nslots = 3; d.sink = *sink;
 	pthread_mutex_init(&d.mu, NULL);
 	pthread_cond_init(&d.cv, NULL);
 	d.slot = (dbatch*)calloc(d.nslots, sizeof(dbatch));
-	if (!d.slot) { d.nslots = 0; rc = MEMORY_CORRUPTION_ERR; goto out; }
+	if (!d.slot) { d.nslots = 0; goto out; }
 	d.stream = agmv_hip_stream_create(ctx);
 	d.d_bits = lz_dev ? NULL : (uint8_t*)agmv_hip_malloc_on(ctx, d.stride * d.cap);      /* (the host LZ stage's upload slab) */
 	d.d_bpos = lz_dev ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
 	d.d_nent = (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
-	d.d_out[0] = direct ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
-	d.d_out[1] = direct ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap);
+	d.d_out[0] = buffered ? (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap) : NULL;
+	d.d_out[1] = buffered ? (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap) : NULL;
 	d.d_iframe = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4);
-	if (scaled && scale->filter == AGMV_SCALE_AREA && (fmt != AGMV_PIXFMT_XRGB32 || scale->tensor)) {
-		d.d_scaled = (uint32_t*)agmv_hip_malloc_on(ctx, (size_t)scale->w * scale->h * 4 * d.cap);
-		if (!d.d_scaled) { rc = MEMORY_CORRUPTION_ERR; goto out; }
-	}
-	if (scaled && scale->tensor) {                         /* 3 x 256 elements, once per call */
-		const size_t bytes = agmv_hip_tensor_frame_bytes(scale->tensor, 256);
+	if (sink_needs_scaled(sink) && !(d.d_scaled = (uint32_t*)agmv_hip_malloc_on(ctx, (size_t)agmv_sink_target(sink)->w * agmv_sink_target(sink)->h * 4 * d.cap))) goto out;
+	if (sink->kind == AGMV_SINK_TENSOR) {                  /* 3 x 256 elements, once per call */
+		const size_t bytes = agmv_hip_tensor_frame_bytes(sink->tensor.type, 256);
 		d.d_table = agmv_hip_malloc_on(ctx, bytes);
-		if (!d.d_table || !d.stream || agmv_hip_memcpy_async(ctx, d.d_table, scale->table, bytes, 0, d.stream) || agmv_hip_stream_sync(ctx, d.stream)) {
-			rc = MEMORY_CORRUPTION_ERR;
-			goto out;
-		}
+		if (!d.d_table || !d.stream || agmv_hip_memcpy_async(ctx, d.d_table, sink->tensor.table, bytes, 0, d.stream) || agmv_hip_stream_sync(ctx, d.stream)) goto out;
 	}
-	if (!persist || !chunks || (!lz_dev && !jobs) || !d.stream || (!lz_dev && (!d.d_bits || !d.d_bpos)) || !d.d_nent || (!direct && (!d.d_out[0] || !d.d_out[1])) || !d.d_iframe) { rc = MEMORY_CORRUPTION_ERR; goto out; }
-	if (lz_dev && dlz_open(&z, ctx, d.cap, cap)) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+	if (!persist || !chunks || (!lz_dev && !jobs) || !d.stream || (!lz_dev && (!d.d_bits || !d.d_bpos)) || !d.d_nent || (buffered && (!d.d_out[0] || !d.d_out[1])) || !d.d_iframe) goto out;
+	if (lz_dev && dlz_open(&z, ctx, d.cap, cap)) goto out;
 	for (i = 0; i < d.nslots; i++) {
 		if (lz_dev) {                                          /* the rows live on the device only */
 			d.slot[i].d_slab = (uint8_t*)agmv_hip_malloc_on(ctx, d.stride * d.cap);
 			d.slot[i].d_bpos = (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
 			d.slot[i].ready = agmv_hip_event_create(ctx);
-			if (!d.slot[i].d_slab || !d.slot[i].d_bpos || !d.slot[i].ready) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+			if (!d.slot[i].d_slab || !d.slot[i].d_bpos || !d.slot[i].ready) goto out;
 		} else {
 			d.slot[i].h_slab = (u8*)agmv_hip_host_alloc(d.stride * d.cap);
 			d.slot[i].h_bpos = (uint32_t*)agmv_hip_host_alloc(4 * (size_t)d.cap + 64);
-			if (!d.slot[i].h_slab || !d.slot[i].h_bpos) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+			if (!d.slot[i].h_slab || !d.slot[i].h_bpos) goto out;
 		}
-		d.slot[i].h_out = d_dst ? NULL : (uint32_t*)agmv_hip_host_alloc(npx * 4 * d.cap);
-		if (!d_dst && !d.slot[i].h_out) { rc = MEMORY_CORRUPTION_ERR; goto out; }
+		if (to_bmp && !(d.slot[i].h_out = (uint32_t*)agmv_hip_host_alloc(npx * 4 * d.cap))) goto out;
 	}
 	d.pool = agmv_pool_start(threads);
 	if (pthread_create(&d.th, NULL, dworker_main, &d)) {       /* no worker: nothing to join, nothing would ever consume a batch */
 		agmv_pool_stop(d.pool);
-		rc = MEMORY_CORRUPTION_ERR;
 		goto out;
 	}
+	rc = NO_ERR;
 	while (done < nframes) {
 		dbatch* b = &d.slot[id % d.nslots];
 		const unsigned want = d.cap < nframes - done ? d.cap : nframes - done;
@@ -1225,8 +1219,8 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 			}
 		}
 		if (!n) break;
-		b->n = n; b->first = done; b->name0 = *export_count + 1;
-		*export_count += n;
+		b->n = n; b->first = done; b->name0 = *sink->count + 1;
+		*sink->count += n;
 		pthread_mutex_lock(&d.mu);
 		b->filled = 1;
 		d.nfilled = ++id;

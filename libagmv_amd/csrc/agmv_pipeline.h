@@ -29,11 +29,37 @@ typedef struct agmv_source {
 	int device;
 } agmv_source;
 
-/* a YUV 4:2:0 layout (its frames are addressed by w and h, not by a pixel count), and the bytes of one frame of any layout */
+/* The one place that knows the two families of layouts: a YUV 4:2:0 clip is addressed by w and h, a byte layout by a pixel count.
+   The bytes of one frame, and the device calls that read or write a clip of w x h frames in the layout `fmt`. */
 #define AGMV_FMT_IS_YUV(fmt) (((fmt) & 0xFF) >= AGMV_PIXFMT_NV12)
 static inline size_t agmv_fmt_frame_bytes(int fmt, uint32_t w, uint32_t h)
 {
 	return AGMV_FMT_IS_YUV(fmt) ? agmv_hip_yuv_frame_bytes(fmt, w, h) : agmv_hip_pixfmt_frame_bytes(fmt, (size_t)w * h);
+}
+static inline int agmv_fmt_to_xrgb(agmv_hip_ctx* c, int fmt, uint32_t w, uint32_t h, const void* d_src, uint32_t n, size_t n_pixels, uint32_t* d_dst, void* stream)
+{
+	return AGMV_FMT_IS_YUV(fmt) ? agmv_hip_yuv_to_xrgb_dev(c, fmt, d_src, w, h, n, n_pixels, d_dst, stream)
+	                            : agmv_hip_pixels_to_xrgb_dev(c, fmt, d_src, (size_t)w * h, n, n_pixels, d_dst, stream);
+}
+static inline int agmv_fmt_from_xrgb(agmv_hip_ctx* c, int fmt, uint32_t w, uint32_t h, const uint32_t* d_src, uint32_t n, void* d_dst, void* stream)
+{
+	return AGMV_FMT_IS_YUV(fmt) ? agmv_hip_yuv_from_xrgb_dev(c, fmt, d_src, w, h, n, d_dst, stream)
+	                            : agmv_hip_pixels_from_xrgb_dev(c, fmt, d_src, n, (size_t)w * h, d_dst, stream);
+}
+static inline int agmv_fmt_gather(agmv_hip_ctx* c, int fmt, uint32_t w, uint32_t h, const void* d_src, uint32_t n, const uint32_t* d_index, size_t n_out, uint32_t* d_dst, void* stream)
+{
+	return AGMV_FMT_IS_YUV(fmt) ? agmv_hip_yuv_gather_dev(c, fmt, d_src, w, h, n, d_index, n_out, d_dst, stream)
+	                            : agmv_hip_gather_fmt_dev(c, fmt, d_src, (size_t)w * h, n, d_index, n_out, d_dst, stream);
+}
+static inline int agmv_fmt_histogram(agmv_hip_ctx* c, int fmt, uint32_t w, uint32_t h, const void* d_src, uint32_t n, size_t n_pixels, int quality, uint32_t* d_hist, void* stream)
+{
+	return AGMV_FMT_IS_YUV(fmt) ? agmv_hip_yuv_histogram_dev(c, fmt, d_src, w, h, n, n_pixels, quality, d_hist, stream)
+	                            : agmv_hip_histogram_fmt_dev(c, fmt, d_src, (size_t)w * h, n, n_pixels, quality, d_hist, stream);
+}
+static inline int agmv_fmt_similarity(agmv_hip_ctx* c, int fmt, uint32_t w, uint32_t h, const void* d_src, uint32_t n, uint32_t* d_counts, void* stream)
+{
+	return AGMV_FMT_IS_YUV(fmt) ? agmv_hip_yuv_similarity_dev(c, fmt, d_src, w, h, n, d_counts, stream)
+	                            : agmv_hip_similarity_fmt_dev(c, fmt, d_src, n, (size_t)w * h, d_counts, stream);
 }
 
 /* one open sequence encode: frames are pushed in order (plain, or the PDIFS midpoint of two sources) and leave as AGFC
@@ -49,14 +75,31 @@ u32  agmv_seq_close(agmv_seq* s);
 void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start, u32 end, u32 size, int quality,
                            unsigned threads, uint32_t* hist);
 
-/* a target for the decoder's sink: the frames land in d_dst at w x h, scaled with `filter` (an AGMV_SCALE of include/agmv.h).
-   tensor != 0 (an AGMV_TENSORFMT): d_dst is a tensor clip of that type instead of a clip in `fmt`, written through `table` (host
-   memory, the 768 elements of agmv_hip_tensor_table); filter 0 then means the file's size, and w, h are not read */
-typedef struct agmv_scale { uint32_t w, h; int filter, tensor; const void* table; } agmv_scale;
+/* Where the decoder's frames go, frame k of the file to its place in device memory of the decoder's device; *count advances by the
+   frames decoded.  EXPORT: quick_export_<*count + 1 ...>.bmp, *count being the running export counter.  FRAMES: a clip in the AGMV_PIXFMT fmt.
+   TENSOR: a tensor clip of the AGMV_TENSORFMT type, written through `table` (host, the 768 elements of agmv_hip_tensor_table).  MEASURE:
+   nowhere; frame k is measured against frame k of the clip d_ref in fmt, which is only read, and its AGMV_FRAME_QUALITY lands in d_quality[k].
+   A target with a filter (an AGMV_SCALE) scales every frame to w x h on its way; filter 0 is the file's size, and w, h are not read. */
+typedef struct agmv_target { uint32_t w, h; int filter; } agmv_target;
+typedef struct agmv_sink {
+	enum { AGMV_SINK_EXPORT, AGMV_SINK_FRAMES, AGMV_SINK_TENSOR, AGMV_SINK_MEASURE } kind;
+	unsigned long* count;
+	union {
+		struct { void* d_dst; int fmt; agmv_target to; } frames;
+		struct { void* d_dst; int type; const void* table; agmv_target to; } tensor;
+		struct { const void* d_ref; int fmt; void* d_quality; } measure;
+	};
+} agmv_sink;
+
+/* the target of a sink that scales, else NULL */
+static inline const agmv_target* agmv_sink_target(const agmv_sink* s)
+{
+	const agmv_target* t = s->kind == AGMV_SINK_FRAMES ? &s->frames.to : s->kind == AGMV_SINK_TENSOR ? &s->tensor.to : NULL;
+	return t && t->filter ? t : NULL;
+}
 
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
-                       int has_audio, unsigned cap_frames, unsigned threads, void* d_dst, int fmt, const agmv_scale* scale, void* d_quality,
-                       unsigned long* export_count);
+                       int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink);
 
 /* the AGAC payloads of a file image (its first chunk at or behind pos) back to back, at most cap bytes; returns their number */
 size_t agmv_gather_audio(const u8* file, size_t len, size_t pos, uint32_t nframes, u8* out, size_t cap);

@@ -4,8 +4,9 @@ torch tensors.
 A 21-frame 64 x 48 clip is written with AGMV_SCHEDULE_FULL, LZSS and LZ77.  Measuring the file -- decoded in three batches of 8
 with the decoder's state carried across them, never held as a clip -- must give, entry for entry, what clip_quality gives for
 decode_frames(path) and what the numpy statement (tests/quality_cases.py) gives for those pixels, with the host LZ stage and with
-AGMV_LZ_DECODE_DEVICE=1, for a reference in XRGB32, RGB24 and NV12.  One child process does all of it (the drivers keep
-process-wide state and read their knobs from the environment); the tests read its answer.  Needs an MI355X."""
+AGMV_LZ_DECODE_DEVICE=1, for a reference in XRGB32, RGB24 and NV12; ten frames of 36 x 20 repeat it at a width that is no
+multiple of 16.  One child process does all of it (the drivers keep process-wide state and read their knobs from the
+environment); the tests read its answer.  Needs an MI355X."""
 import functools
 import json
 import os
@@ -95,6 +96,19 @@ CHILD = textwrap.dedent("""
         res["file_mismatch"] = "accepted"
     except ValueError as ex:
         res["file_mismatch"] = "ValueError"
+    # the measuring sink at a width that is no multiple of 16: 10 frames of 36 x 20 (two batches), an RGB24 reference
+    n2, h2, w2 = 10, 20, 36
+    small = np.ascontiguousarray(src[:n2, :h2, :w2])
+    raw, stands_for = Q.reference_clip(2, small)
+    tens = torch.from_numpy(raw).reshape(n2, h2, w2, 3).cuda()
+    seq.encode_frames("small.agmv", torch.from_numpy(small.view(np.int32)).cuda(), opt=3, quality=3, compression=1, schedule=seq.SCHEDULE_FULL)
+    decoded, _ = seq.decode_frames("small.agmv")
+    e = (seq.AGMV_FRAME_QUALITY * n2)()
+    rc = L.AGMV_MeasureFileDev(b"small.agmv", tens.data_ptr(), 2, n2, e, None)
+    a = seq.clip_quality(decoded, tens, fmt="rgb24")
+    want = Q.entries(Q.measure(decoded.cpu().numpy().view(np.uint32), stands_for))
+    res["small"] = {"rc": rc, "decoded": list(decoded.shape), "file_is_clip": bool((words(e, n2) == of(a)).all()),
+                    "clip_is_statement": bool((of(a) == want).all())}
     print(json.dumps(res))
 """)
 
@@ -122,6 +136,14 @@ def test_file_measure_is_the_clip_measure_of_its_decode(compression, lz_stage, r
     assert c["seq_file_is_file"], "file_quality differs from AGMV_MeasureFileDev"
     assert c["lossy"] and c["dims"] == [W, HT, W, HT]
     assert c["psnr"][0] == c["psnr"][1] and 10.0 < c["psnr"][0] < 100.0 and c["block_psnr"] > c["psnr"][0] and 0.0 < c["ssim"] < 1.0
+
+
+def test_file_measure_at_a_width_that_is_no_multiple_of_16():
+    """36 x 20, ten frames in two batches: the reference's frames of the second batch lie 8 * 36 * 20 * 3 bytes into the clip"""
+    c = answer()["small"]
+    assert c["rc"] == 10 and c["decoded"] == [10, 20, 36]
+    assert c["clip_is_statement"], "AGMV_MeasureFramesDev differs from the numpy statement on the decoded clip"
+    assert c["file_is_clip"], "AGMV_MeasureFileDev differs from AGMV_MeasureFramesDev on the decoded clip"
 
 
 def test_refusals_and_the_info_only_call():
