@@ -70,6 +70,34 @@ def scale_area(pix, dw, dh):
     return out
 
 
+def _area_axis(c, d):
+    """int64 [..., s] -> int64 [..., d]: target X = F((X + 1) * s) - F(X * s), where every source pixel is d units long and
+    F(t) = d * (the sum of the pixels before pixel t div d) + (t mod d) * pixel t div d is the integral of the row up to unit t"""
+    s = c.shape[-1]
+    cum = np.zeros(c.shape[:-1] + (s + 1,), np.int64)
+    np.cumsum(c, axis=-1, out=cum[..., 1:])
+    t = np.arange(d + 1, dtype=np.int64) * s
+    i, r = t // d, t % d
+    assert i[-1] == s and r[-1] == 0                              # F(s * d) takes nothing of a pixel behind the row
+    F = d * cum[..., i] + r * c[..., np.minimum(i, s - 1)]
+    return F[..., 1:] - F[..., :-1]
+
+
+def scale_area_streamed(pix, dw, dh):
+    """scale_area without the weight matrices, for shapes whose [dw, sw] matrix cannot be held: prefix sums along x, then along y,
+    in int64, then the same rounding.  tests/test_scale_cpu.py proves it equal to scale_area on every shape of STARRED and MORE"""
+    pix = np.asarray(pix, np.uint32)
+    n, sh, sw = pix.shape
+    assert 0 < dw <= sw and 0 < dh <= sh and sw * sh <= AREA_MAX_SOURCE
+    out = np.zeros((n, dh, dw), np.uint32)
+    for s in (16, 8, 0):
+        c = ((pix >> s) & 255).astype(np.int64)
+        acc = _area_axis(_area_axis(c, dw).swapaxes(1, 2), dh).swapaxes(1, 2)     # int64 [n, dh, dw]
+        assert acc.shape == (n, dh, dw) and int(acc.max()) <= 255 * sw * sh
+        out |= ((acc + (sw * sh) // 2) // (sw * sh)).astype(np.uint32) << s
+    return out
+
+
 def scale_nearest(pix, dw, dh):
     """uint32 [n, sh, sw] -> uint32 [n, dh, dw]: D(X, Y) = S(((2X + 1) * sw) div (2 * dw), ((2Y + 1) * sh) div (2 * dh))"""
     pix = np.asarray(pix, np.uint32)
@@ -99,6 +127,18 @@ MORE = [(5, 7, 5, 3),                # one axis identity
         (1000, 16, 999, 15),         # weights 1 and dw - 1
         (5000, 2, 2499, 1),          # a target wider than one accumulator tile: three tiles, their edges inside source pixels
         (2064, 4, 1040, 2)]          # tiles again, with 16-byte loads (2064 = 16 * 129) and a tile edge inside a source pixel's reach
+
+
+def area_small(shape):
+    """whether a lane's position u = (source column) * dw, at most (sw - 1) * dw, is formed in 32 bits: the library asks sw * dw < 2^32"""
+    return shape[0] * shape[2] < 1 << 32
+
+
+# (shape, area_small): scale_area_streamed states these, the weight matrices of scale_area would hold up to 2^32 elements
+WIDE_U = [((65536, 2, 65536, 1), False),      # sw * dw = 2^32 exactly: the identity in x, 64 tiles
+          ((65536, 2, 65535, 1), True)]       # the largest 32-bit u, weights 1 and dw - 1
+WIDE_TILES = ((131072, 1, 40000, 1), False)   # 40 accumulator tiles
+WIDE_BOUND = ((1 << 22, 4, 4099, 3), False)   # sw * sh = 2^24, the accumulator bound, with the 64-bit u: five tiles, target rows astride source rows
 
 
 def shape_id(s):

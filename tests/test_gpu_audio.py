@@ -1,7 +1,7 @@
 """agmv_hip_audio_compand_async / agmv_hip_audio_expand_async against the numpy statement of tests/audio_cases.py: every sample
 value and every code, the three layouts at sample counts around the kernels' 16-sample unit, 1 to 6 channels, pointers one element
-off their 16-byte boundary (the scalar head), canary bytes on both sides of every output, the float rule's edge values, the round
-trip and the refusals.  Expected values never come from the GPU.  Needs an MI355X."""
+off their 16-byte boundary (the scalar head), tracks longer than one pass of the capped grid (both loops of every kernel go round a
+second time), canary bytes on both sides of every output, the float rule's edge values, the round trip and the refusals.  Expected values never come from the GPU.  Needs an MI355X."""
 import itertools
 
 import numpy as np
@@ -120,6 +120,76 @@ def test_planar_head_and_body_with_several_channels(hip, channels, plane_off, co
         rc, got, intact = launch(hip, True, A.PCM_F32P, c.reshape(-1), channels, n, code_off, plane_off)
         want = A.to_f32(A.expand(c)).T.copy().reshape(-1).view(np.uint32)
         assert rc == 0 and intact and (got == want).all(), (n, np.flatnonzero(got != want)[:8])
+
+
+# ---- tracks longer than one pass of the capped grid: the second trip of the unit loop and of the edge loop ----
+AUD_MAX_BLOCKS, AUD_T = 2048, 256                  # the kernels' grid cap and workgroup size, restated
+CAP = AUD_MAX_BLOCKS * AUD_T                       # lanes of the largest grid: a loop of more iterations goes round a second time
+LONG = 16 * CAP + 16 * 300 + 5                     # samples: 300 units past the cap, and a tail
+
+
+def cut(n, pcm_off, pcm_step, plane_bytes, planes, code_off, code_step):
+    """(head, units) of a track of n samples per channel by the kernels' rule, restated: the smallest head below 16 that brings the
+    codes and every plane to a 16-byte boundary (offsets in bytes from one), else the whole track is head"""
+    for h in range(16):
+        if h + 16 <= n and (code_off + h * code_step) % 16 == 0 and all((pcm_off + c * plane_bytes + h * pcm_step) % 16 == 0 for c in range(planes)):
+            return h, (n - h) // 16
+    return n, 0
+
+
+def every_code(track):
+    """A.compand through its table over all 65536 sample values"""
+    return A.compand(np.arange(65536, dtype=np.uint16))[track]
+
+
+def both_ways(hip, fmt, channels, n, pcm_off, code_off, seed):
+    """a compand and an expand of n samples per channel with the PCM pointer pcm_off elements and the codes code_off bytes off a
+    16-byte boundary, against the statement, canaries included"""
+    src, track = pcm_of(fmt, n, channels, seed)
+    rc, got, intact = launch(hip, False, fmt, src, channels, n, pcm_off, code_off)
+    want = every_code(track).reshape(-1)
+    assert rc == 0 and intact, "compand wrote outside its output" if rc == 0 else hip.L.agmv_hip_last_error()
+    assert (got == want).all(), np.flatnonzero(got != want)[:8]
+    c = np.random.default_rng(seed + 1).integers(0, 256, (n, channels)).astype(np.uint8)
+    rc, got, intact = launch(hip, True, fmt, c.reshape(-1), channels, n, code_off, pcm_off)
+    samples = A.expand(np.arange(256, dtype=np.uint8))                              # A.expand through its table over all 256 codes
+    want = samples[c].reshape(-1) if fmt == A.PCM_S16 else A.to_f32(samples)[c].T.copy().reshape(-1).view(np.uint32)
+    assert rc == 0 and intact, "expand wrote outside its output" if rc == 0 else hip.L.agmv_hip_last_error()
+    assert (got == want).all(), np.flatnonzero(got != want)[:8]
+
+
+def test_the_edge_loop_goes_round_twice_s16(hip):
+    """600 001 mono samples, the PCM pointer one sample off its boundary and the codes on theirs: no head serves both, so the whole
+    track goes one sample per lane, more samples than the capped grid has lanes"""
+    n = 600001
+    assert cut(n, 2, 2, 0, 1, 0, 1) == (n, 0) and n > CAP
+    both_ways(hip, A.PCM_S16, 1, n, 1, 0, 41)
+
+
+def test_the_edge_loop_goes_round_twice_f32p(hip):
+    """3 planes of 200 001 samples: n % 4 != 0, the planes cannot all lie on 16-byte boundaries, the whole track is head"""
+    n, ch = 200001, 3
+    assert cut(n, 0, 4, 4 * n, ch, 0, ch) == (n, 0) and n * ch > CAP
+    both_ways(hip, A.PCM_F32P, ch, n, 0, 0, 43)
+
+
+@pytest.mark.parametrize("off,head", ((0, 0), (1, 15)))
+def test_the_unit_loop_goes_round_twice_s16(hip, off, head):
+    """mono, both pointers `off` elements off their boundaries: a head of 0 or of 15 samples, more units than the grid has lanes, a tail"""
+    h, units = cut(LONG, 2 * off, 2, 0, 1, off, 1)
+    assert h == head and units > CAP and 0 < LONG - h - 16 * units < 16
+    both_ways(hip, A.PCM_S16, 1, LONG, off, off, 45 + off)
+
+
+def test_the_unit_loop_goes_round_twice_f32p(hip):
+    """2 planes in the first phase of PHASES: head 7, more units than the grid has lanes, a tail of 5.  The planes keep one phase
+    only where n % 4 == 0, so the count is LONG + 7"""
+    channels, plane_off, code_off, head = PHASES[0]
+    n = LONG + 7
+    assert (channels, head) == (2, 7) and n % 4 == 0
+    h, units = cut(n, 4 * plane_off, 4, 4 * n, channels, code_off, channels)
+    assert h == head and units > CAP and n - h - 16 * units == 5
+    both_ways(hip, A.PCM_F32P, channels, n, plane_off, code_off, 47)
 
 
 def test_float_rule(hip):

@@ -1019,3 +1019,70 @@ def test_pack_unpack_frames(torch, hip):
         back = hip.unpack_frames_dev(packed, sizes, stride)
         keep = torch.arange(stride, device="cuda")[None, :] < sizes[:, None]
         assert torch.equal(back, slab * keep)
+
+
+# ------------------------------------------------------------------------------- grids that go round a second time
+PAST_THE_CAP = (1 << 21) + (1 << 20) + 3           # pixels: k_interp and k_histogram launch at most 8192 workgroups of 256 lanes, 2^21 pixels a trip
+
+
+def test_interp_past_the_grid_cap(torch, hip):
+    """3 * 2^20 + 3 pixels: every lane goes round a second time, half of them only; three lanes a third time"""
+    n = PAST_THE_CAP
+    assert n > 8192 * 256
+    rng = np.random.default_rng(21)
+    a = rng.integers(0, 1 << 24, size=n, dtype=np.uint32)
+    b = rng.integers(0, 1 << 24, size=n, dtype=np.uint32)
+    exp = np.zeros_like(a)
+    O.oracle().orc_interp_frame(exp, a, b, n)
+    got = to_u32(hip.interp_dev(dev_u32(torch, a), dev_u32(torch, b)))
+    assert (got == exp).all(), np.flatnonzero(got != exp)[:4]
+
+
+def test_histogram_past_the_grid_cap(torch, hip):
+    """the same count of random pixels, for the three qualities.  The table is added to, so it starts non-zero, between guard words"""
+    n = PAST_THE_CAP
+    assert n > 8192 * 256
+    b = np.random.default_rng(22).integers(0, 1 << 24, size=n, dtype=np.uint32)
+    d_b = dev_u32(torch, b)
+    G, NB, mark = 64, 1 << 19, 0xA5A5A5A5
+    base = ((np.arange(NB, dtype=np.uint64) * 2654435761) % 65521 + 1).astype(np.uint32)
+    d_base = dev_u32(torch, base)
+    r, g_, bb = (b >> 16) & 255, (b >> 8) & 255, b & 255
+    for q, shifts in ((1, (2, 2, 1, 13, 7)), (2, (3, 2, 2, 12, 6)), (3, (3, 2, 3, 11, 5))):
+        code = ((r >> shifts[0]) << shifts[3]) | ((g_ >> shifts[1]) << shifts[4]) | (bb >> shifts[2])
+        buf = torch.full((G + NB + G,), mark - (1 << 32), dtype=torch.int32, device="cuda")
+        buf[G:G + NB] = d_base
+        hip.histogram_dev(d_b, q, hist=buf[G:G + NB])
+        got_h = to_u32(buf)
+        exp_h = base + np.bincount(code, minlength=NB).astype(np.uint32)
+        assert (got_h[G:G + NB] == exp_h).all(), (q, np.argwhere(got_h[G:G + NB] != exp_h)[:4])
+        assert (got_h[:G] == mark).all() and (got_h[G + NB:] == mark).all(), (q, "guard words written")
+
+
+def ragged_rows(torch):
+    """70 001 frames in rows of 256 bytes, sizes in [0, 256], a fifth of them 0: one workgroup column, and 65 536 grid rows that
+    stride over the frames.  -> (slab, sz, sizes, keep, the message: each row's first sz[f] bytes, row by row)"""
+    n, stride = 70001, 256
+    assert (stride // 8 + 16383) // 16384 == 1 and n > 65536               # gx = 1, so gy is capped at 65536 / gx < n
+    rng = np.random.default_rng(12)
+    slab = torch.from_numpy(rng.integers(0, 256, (n, stride), dtype=np.uint8)).cuda()
+    sz = rng.integers(0, stride + 1, n)
+    sz[rng.integers(0, n, n // 5)] = 0
+    assert sz[65536:].any() and sz.max() == stride and (sz == 0).sum() > n // 8
+    sizes = torch.from_numpy(sz.astype(np.int32)).cuda()
+    keep = torch.arange(stride, device="cuda")[None, :] < sizes[:, None]
+    return slab, sz, sizes, keep, slab[keep]
+
+
+def test_pack_more_frames_than_the_grid_has_rows(torch, hip):
+    slab, sz, sizes, keep, exp = ragged_rows(torch)
+    packed, offs = hip.pack_frames_dev(slab, sizes)
+    assert torch.equal(packed, exp)
+    assert offs.cpu().tolist() == [0] + np.cumsum(sz).tolist()
+
+
+def test_unpack_more_frames_than_the_grid_has_rows(torch, hip):
+    """from the message stated by the mask, so that the way back does not lean on the way there"""
+    slab, sz, sizes, keep, exp = ragged_rows(torch)
+    back = hip.unpack_frames_dev(exp, sizes, slab.shape[1])
+    assert torch.equal(back, slab * keep)

@@ -3,7 +3,8 @@ through AgmvHip against the numpy statement of the rule (tests/scale_cases.py). 
 A lane takes 16 consecutive pixels of a source row, with 16-byte loads where the clip's frames lie on 16-byte boundaries (YUV:
 and the width is a multiple of 16) and byte by byte otherwise and at a row's head and tail; 1024 target columns share one
 accumulator tile; the work items are walked with a grid stride.  The shapes hold each of these paths and their edges, the byte
-offset 1 takes an aligned clip to the byte-wise path.  Needs an MI355X."""
+offset 1 takes an aligned clip to the byte-wise path.  Where sw * dw leaves 32 bits a lane forms its position in 64: shapes on either
+side of that, stated by prefix sums (SC.scale_area_streamed).  Needs an MI355X."""
 import ctypes as C
 
 import numpy as np
@@ -60,8 +61,8 @@ def run(torch, hip, fmt, raw, sw, sh, dw, dh, off=0):
     return host[GUARD:-GUARD].view(np.uint32).reshape(n, dh, dw), bool((host[:GUARD] == 0x5A5A5A5A).all() and (host[-GUARD:] == 0x5A5A5A5A).all())
 
 
-def check(torch, hip, fmt, raw, sw, sh, dw, dh, offsets=(0,)):
-    exp = SC.scale_area(SC.to_packed(fmt, raw, sw, sh), dw, dh)
+def check(torch, hip, fmt, raw, sw, sh, dw, dh, offsets=(0,), statement=SC.scale_area):
+    exp = statement(SC.to_packed(fmt, raw, sw, sh), dw, dh)
     for off in offsets:
         got, guards = run(torch, hip, fmt, raw, sw, sh, dw, dh, off)
         assert (got >> 24 == 0).all(), (sw, sh, dw, dh, off, "top byte")
@@ -115,6 +116,38 @@ def test_the_accumulator_bound(torch, hip):
     sums = raw.reshape(3, 4, 1024, 4, 1024).sum(axis=(2, 4), dtype=np.int64)
     mean = ((sums + (1 << 19)) >> 20).astype(np.uint32)
     assert (got[0] == (mean[0] << 16 | mean[1] << 8 | mean[2])).all() and guards
+
+
+# ---- a lane's position u = column * dw past 32 bits (SC.scale_area_streamed states these shapes; tests/test_scale_cpu.py proves it) ----
+@pytest.mark.parametrize("shape,small", SC.WIDE_U, ids=[SC.shape_id(s) for s, _ in SC.WIDE_U])
+@pytest.mark.parametrize("fmt", ALL_FORMATS, ids=IDS)
+def test_either_side_of_the_largest_32_bit_position(torch, hip, fmt, shape, small):
+    """2 frames of 65536 x 2 -> 65536 x 1 (sw * dw = 2^32, the 64-bit form) and -> 65535 x 1 (the largest 32-bit u); the byte
+    layouts also at byte offset 1, so that the 16-byte loads and the byte reader both walk each form"""
+    sw, sh, dw, dh = shape
+    assert SC.area_small(shape) == small and abs(sw * dw - (1 << 32)) <= 65536
+    raw = np.random.default_rng(fmt * 1000 + dw).integers(0, 256, (2, SC.frame_bytes(fmt, sw, sh)), dtype=np.uint8)
+    offsets = (0, 1) if fmt in SC.BYTE_LAYOUTS and fmt != P.XRGB32 else (0,)
+    check(torch, hip, fmt, raw, sw, sh, dw, dh, offsets=offsets, statement=SC.scale_area_streamed)
+
+
+@pytest.mark.parametrize("fmt", SC.LAYOUTS, ids=[SC.fmt_name(f) for f in SC.LAYOUTS])
+def test_forty_tiles_with_the_64_bit_position(torch, hip, fmt):
+    (sw, sh, dw, dh), small = SC.WIDE_TILES
+    assert SC.area_small((sw, sh, dw, dh)) == small and not small and (dw + 1023) // 1024 == 40
+    raw = np.random.default_rng(fmt * 1000 + dw).integers(0, 256, (2, SC.frame_bytes(fmt, sw, sh)), dtype=np.uint8)
+    check(torch, hip, fmt, raw, sw, sh, dw, dh, statement=SC.scale_area_streamed)
+
+
+def test_the_accumulator_bound_with_the_64_bit_position(torch, hip):
+    """sw * sh = 2^24 and sw * dw >= 2^32 in one frame of 4194304 x 4 -> 4099 x 3: five tiles, target rows astride source rows"""
+    (sw, sh, dw, dh), small = SC.WIDE_BOUND
+    assert SC.area_small((sw, sh, dw, dh)) == small and not small and sw * sh == SC.AREA_MAX_SOURCE and (dw + 1023) // 1024 == 5 and sh % dh
+    white = np.full((1, 4 * sw * sh), 0xFF, np.uint8)                                           # bits >= 24 set: they are no pixels
+    got, guards = run(torch, hip, P.XRGB32, white, sw, sh, dw, dh)
+    assert (got == 0xFFFFFF).all() and guards
+    raw = np.random.default_rng(17).integers(0, 256, (1, 3 * sw * sh), dtype=np.uint8)
+    check(torch, hip, P.RGB24, raw, sw, sh, dw, dh, statement=SC.scale_area_streamed)
 
 
 def test_more_frames_than_a_grid_holds(torch, hip):

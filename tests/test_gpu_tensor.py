@@ -117,6 +117,22 @@ def test_the_scaled_sink_is_the_table_applied_to_the_scaled_clip(torch, hip, sha
         assert guards, (shape, off, "guard bytes written")
 
 
+# the taps divided in 64 bits (U.WIDE_INDEX): the band kernel with 4-byte and 2-byte elements, and the per-pixel one
+WIDE_INDEX = [((70001, 1, 40000, 2), U.BILINEAR, TC.F32), ((70001, 1, 40000, 2), U.BILINEAR, TC.F16), ((70001, 1, 40001, 3), U.NEAREST, TC.BF16)]
+
+
+@pytest.mark.parametrize("shape,filt,t", WIDE_INDEX, ids=["%s-%s-%s" % (U.shape_id(s), U.FILTER_NAMES[f], TC.NAMES[t]) for s, f, t in WIDE_INDEX])
+def test_the_scaled_sink_with_taps_divided_in_64_bits(torch, hip, shape, filt, t):
+    sw, sh, dw, dh = shape
+    assert U.axes_small(shape) == (False, True) and dict(U.WIDE_INDEX)[shape] == (False, True)
+    pix = source(sw, sh, 1000 * t + dw + dh)
+    tab = TC.table(t, *IMAGENET)
+    exp = TC.from_packed(tab, U.scale(filt, pix, dw, dh))
+    got, guards = sink(torch, hip, t, pix, tab, filt, dw, dh)
+    assert (got == exp).all(), (shape, np.argwhere(got != exp)[:4])
+    assert guards, (shape, "guard bytes written")
+
+
 def test_the_sink_wrapper_on_many_blocks(torch, hip):
     """AgmvHip.tensor_from_xrgb_async on 2 frames of 320 x 240 -> 224 x 224 F16 and 640 x 360 BF16: many blocks per frame"""
     pix = source(320, 240, 5, n=2)

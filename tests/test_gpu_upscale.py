@@ -4,6 +4,7 @@ layouts' writing rules (tests/upscale_cases.py, tests/scale_cases.py).  Everythi
 row (YUV: 16 x 2) and stores them with 16-byte stores where the target's width is a multiple of 16 and its frames lie on 16-byte
 boundaries, walking a band of 8 rows; every other target, and a YUV frame with an odd last row, is written pixel by pixel.  The shapes hold both paths and
 their edges; a target base off a 16-byte boundary takes an aligned shape to the per-pixel path, which must give the same bytes.
+Where a term of the taps leaves 32 bits on either axis the kernels divide in 64: shapes on either side of that (U.up_small).
 Needs an MI355X."""
 import ctypes as C
 
@@ -91,6 +92,70 @@ def test_bands_of_rows_equal_numpy(torch, hip, filt, fmt, shape):
     got, guards = run(torch, hip, filt, pix, fmt, dw, dh)
     assert (got == exp).all(), (shape, np.argwhere(got != exp)[:4], got[got != exp][:4], exp[got != exp][:4])
     assert guards, (shape, "guard bytes written")
+
+
+# ---- the 64-bit form of the taps, the column stepper on a downscale, degenerate targets (tests/upscale_cases.py) ----
+_scaled = {}
+
+
+def scaled(filt, shape, n):
+    """(the source, its scaled XRGB32 clip by the numpy statement), made once per filter and shape and left unchanged: every layout
+    of a shape is written from the same pixels"""
+    key = (filt, shape, n)
+    if key not in _scaled:
+        sw, sh, dw, dh = shape
+        pix = source(sw, sh, sw + 7 * dw + 13 * dh, n=n)
+        exp = U.scale(filt, pix, dw, dh)
+        exp.setflags(write=False)                                 # (the source stays writable: torch.from_numpy warns otherwise)
+        _scaled[key] = pix, exp
+    return _scaled[key]
+
+
+def check_shape(torch, hip, filt, fmt, shape, small, n=N):
+    assert U.axes_small(shape) == small, (shape, "the shape is on the wrong side of up_small")
+    sw, sh, dw, dh = shape
+    pix, xrgb = scaled(filt, shape, n)
+    exp = np.asarray(SC.from_packed(fmt, xrgb)).view(np.uint8).reshape(n, -1)
+    got, guards = run(torch, hip, filt, pix, fmt, dw, dh)
+    assert got.shape == exp.shape
+    assert (got == exp).all(), (shape, np.argwhere(got != exp)[:4], got[got != exp][:4], exp[got != exp][:4])
+    assert guards, (shape, "guard bytes written")
+
+
+@pytest.mark.parametrize("shape,small", U.WIDE_INDEX, ids=[U.shape_id(s) for s, _ in U.WIDE_INDEX])
+@pytest.mark.parametrize("fmt", FORMATS, ids=[SC.fmt_name(f) for f in FORMATS])
+@pytest.mark.parametrize("filt", FILTERS, ids=[U.FILTER_NAMES[f] for f in FILTERS])
+def test_taps_divided_in_64_bits_equal_numpy(torch, hip, filt, fmt, shape, small):
+    """(2X + 1) * s + d leaves 32 bits on one axis, so both axes divide in 64: through x and through y, on the band kernel and pixel by pixel"""
+    assert small != (True, True)
+    check_shape(torch, hip, filt, fmt, shape, small)
+
+
+@pytest.mark.parametrize("shape,small", U.BOUNDARY_P, ids=[U.shape_id(s) for s, _ in U.BOUNDARY_P])
+@pytest.mark.parametrize("fmt", (P.XRGB32, P.RGB24), ids=("xrgb32", "rgb24"))
+@pytest.mark.parametrize("filt", FILTERS, ids=[U.FILTER_NAMES[f] for f in FILTERS])
+def test_either_side_of_the_largest_32_bit_numerator(torch, hip, filt, fmt, shape, small):
+    sw, sh, dw, dh = shape
+    assert ((2 * dw - 1) * sw + dw < 1 << 32) == small[0] and abs((2 * dw - 1) * sw + dw - (1 << 32)) <= 32768
+    check_shape(torch, hip, filt, fmt, shape, small)
+
+
+@pytest.mark.parametrize("shape,small", U.BOUNDARY_F, ids=[U.shape_id(s) for s, _ in U.BOUNDARY_F])
+@pytest.mark.parametrize("fmt", (P.XRGB32, P.RGB24), ids=("xrgb32", "rgb24"))
+def test_either_side_of_the_largest_32_bit_weight_numerator(torch, hip, fmt, shape, small):
+    """one frame of 3 x 1 -> 8.4 million columns, bilinear: 513 * d on either side of 2^32"""
+    sw, sh, dw, dh = shape
+    assert (513 * dw < 1 << 32) == small[0] and abs(513 * dw - (1 << 32)) < 16 * 513 and (2 * dw - 1) * sw + dw < 1 << 32
+    check_shape(torch, hip, U.BILINEAR, fmt, shape, small, n=1)
+
+
+@pytest.mark.parametrize("shape,small", U.DOWN_X, ids=[U.shape_id(s) for s, _ in U.DOWN_X])
+@pytest.mark.parametrize("fmt", FORMATS, ids=[SC.fmt_name(f) for f in FORMATS])
+@pytest.mark.parametrize("filt", FILTERS, ids=[U.FILTER_NAMES[f] for f in FILTERS])
+def test_down_in_x_with_a_remainder_and_targets_of_one_pixel(torch, hip, filt, fmt, shape, small):
+    sw, sh, dw, dh = shape
+    assert sw > dw and (sw % dw or (dw, dh) == (1, 1))                             # the column stepper moves by q >= 1 and a remainder
+    check_shape(torch, hip, filt, fmt, shape, small)
 
 
 def test_the_flags_reach_the_writer(torch, hip):

@@ -65,6 +65,31 @@ def test_known_answers_of_the_area_rule():
     assert SC.scale_area(np.array([[[0xFF0000, 0x00FF00], [0x0000FF, 0x000000]]], np.uint32), 1, 1).tolist() == [[[0x404040]]]
 
 
+@pytest.mark.parametrize("shape", SC.STARRED + SC.MORE, ids=[SC.shape_id(s) for s in SC.STARRED + SC.MORE])
+def test_the_streamed_statement_equals_the_dense_one(shape):
+    """scale_area_streamed (prefix sums) against scale_area (weight matrices), before a GPU test relies on the former"""
+    sw, sh, dw, dh = shape
+    rng = np.random.default_rng(sw * 31 + dw)
+    for pix in (rng.integers(0, 1 << 32, (2, sh, sw), dtype=np.uint32), np.full((2, sh, sw), 0xFFFFFFFF, np.uint32)):
+        got, exp = SC.scale_area_streamed(pix, dw, dh), SC.scale_area(pix, dw, dh)
+        assert got.dtype == exp.dtype and got.shape == exp.shape and (got == exp).all(), np.argwhere(got != exp)[:4]
+    assert (SC.scale_area_streamed(np.full((1, sh, sw), 0xFFFFFFFF, np.uint32), dw, dh) == 0xFFFFFF).all()
+
+
+def test_the_streamed_statement_by_hand_and_the_wide_shapes():
+    assert SC.scale_area_streamed(chan([[1, 2], [3, 5]]), 1, 1).tolist() == chan([[3]]).tolist()
+    assert SC.scale_area_streamed(chan([[10, 40, 100]]), 2, 1).tolist() == chan([[20, 80]]).tolist()
+    assert SC._area_axis(np.array([10, 40, 100], np.int64), 2).tolist() == [60, 240]                  # 2 * 10 + 1 * 40, 1 * 40 + 2 * 100
+    for shape, small in SC.WIDE_U + [SC.WIDE_TILES, SC.WIDE_BOUND]:
+        sw, sh, dw, dh = shape
+        assert SC.area_small(shape) == small and dw <= sw and dh <= sh and sw * sh <= SC.AREA_MAX_SOURCE
+    assert 65536 * 65536 == 1 << 32 and 65536 * 65535 == (1 << 32) - 65536 and SC.WIDE_BOUND[0][0] * SC.WIDE_BOUND[0][1] == SC.AREA_MAX_SOURCE
+    # 65536 -> 65535 columns on one row: target X takes 65535 - X units of pixel X and X + 1 of pixel X + 1
+    row = np.random.default_rng(6).integers(0, 256, 65536).astype(np.int64)
+    X = np.arange(65535, dtype=np.int64)
+    assert (SC._area_axis(row, 65535) == (65535 - X) * row[:-1] + (X + 1) * row[1:]).all()
+
+
 def test_known_answers_of_the_nearest_rule():
     row = np.arange(4, dtype=np.uint32)[None, None, :] + 0x100
     assert SC.scale_nearest(row, 2, 1).tolist() == [[[0x101, 0x103]]]                                 # ((2X + 1) * 4) div 4 = 2X + 1

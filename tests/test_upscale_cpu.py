@@ -76,6 +76,36 @@ def test_the_taps():
         assert 0 <= f.min() and f.max() <= 256 and i0.min() >= 0 and i1.max() <= s - 1 and ((i1 == i0 + 1) | (i1 == s - 1)).all()
 
 
+def test_the_32_bit_predicate_on_its_boundaries():
+    """U.up_small restates the rule under which the kernels divide in 32 bits; the four boundary shapes lie where the GPU tests say"""
+    assert (2 * 32768 - 1) * 65536 + 32768 == (1 << 32) - 32768 and U.up_small(65536, 32768)
+    assert (2 * 32768 - 1) * 65537 + 32768 == (1 << 32) + 32767 and not U.up_small(65537, 32768)
+    assert 513 * 8372240 == (1 << 32) - 8176 and U.up_small(3, 8372240)
+    assert 513 * 8372256 == (1 << 32) + 32 and not U.up_small(3, 8372256)
+    assert 8372240 % 16 == 0 and 8372256 - 8372240 == 16                                           # neighbours among the widths the band kernel takes
+    assert [U.axes_small(s) for s, _ in U.BOUNDARY_P + U.BOUNDARY_F] == [(True, True), (False, True), (True, True), (False, True)]
+    # the terms the 32-bit form computes, at their largest, on the small side of both pairs
+    for s, d in ((65536, 32768), (3, 8372240)):
+        p = (2 * np.arange(d, dtype=np.int64) + 1) * s + d
+        assert int(p.max()) < 1 << 32 and int((256 * (p % (2 * d)) + d).max()) < 1 << 32
+    for s, d in ((1, 1), (320, 1920), (4096, 4096), (1 << 28, 1), (1, 1 << 22)):
+        assert U.up_small(s, d)
+    assert not U.up_small(1 << 28, 9) and not U.up_small(1, 1 << 24)
+
+
+@pytest.mark.parametrize("shape,small", U.NEW_SHAPES, ids=[U.shape_id(s) for s, _ in U.NEW_SHAPES])
+def test_the_taps_of_the_wide_and_degenerate_shapes(shape, small):
+    """every shape is on the side of the predicate it was chosen for, and its taps stay inside the source with f <= 256"""
+    assert U.axes_small(shape) == small
+    sw, sh, dw, dh = shape
+    for s, d in ((sw, dw), (sh, dh)):
+        i0, i1, f = U.taps(s, d)
+        assert len(i0) == d and i0.min() >= 0 and i1.max() <= s - 1 and (i0 <= i1).all() and ((i1 == i0 + 1) | (i1 == s - 1)).all()
+        assert 0 <= f.min() and f.max() <= 256
+        near = ((2 * np.arange(d, dtype=np.int64) + 1) * s) // (2 * d)
+        assert near.min() >= 0 and near.max() <= s - 1
+
+
 @pytest.mark.parametrize("shape", U.SHAPES, ids=[U.shape_id(s) for s in U.SHAPES])
 def test_properties_on_random_frames(shape):
     sw, sh, dw, dh = shape

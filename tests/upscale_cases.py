@@ -8,6 +8,7 @@ from scale_cases import from_packed, scale_area, scale_nearest  # noqa: F401  (t
 
 NEAREST, AREA, BILINEAR = SC.NEAREST, SC.AREA, 3
 FILTER_NAMES = {NEAREST: "nearest", AREA: "area", BILINEAR: "bilinear"}
+COLUMNS = 1 << 16                                # target columns scale_bilinear forms at a time
 
 # agmv_hip_scale_frames_async: (sw, sh, dw, dh).  A lane owns 16 target pixels of a row (YUV: 16 x 2).
 SHAPES = [(8, 8, 8, 8),              # identity
@@ -21,6 +22,37 @@ SHAPES = [(8, 8, 8, 8),              # identity
 
 def shape_id(s):
     return "%dx%d-to-%dx%d" % s
+
+
+def up_small(s, d):
+    """whether the kernels divide an axis of source length s and target length d in 32 bits: (2X + 1) * s + d for every X < d and
+    256 * r + d for every r < 2d fit 32 bits.  The first is largest at X = d - 1; the second stays below 513 * d, which is the
+    bound the library takes"""
+    return (2 * d - 1) * s + d < 1 << 32 and 513 * d < 1 << 32
+
+
+def axes_small(shape):
+    """(x, y): a launch takes the 64-bit form on both axes where either is False"""
+    sw, sh, dw, dh = shape
+    return up_small(sw, dw), up_small(sh, dh)
+
+
+# Shapes whose products leave 32 bits, each with the side of up_small its axes must fall on (x, y); extreme aspect ratios keep
+# them small: 3 frames of the largest are 0.5 MB.
+WIDE_INDEX = [((70001, 1, 40000, 2), (False, True)),     # through x; dw a multiple of 16 and dh even: every layout stores 16 bytes at a time
+              ((70001, 1, 40001, 3), (False, True)),     # through x, pixel by pixel, with odd YUV edges
+              ((1, 70001, 16, 40000), (True, False)),    # through y only: 5000 bands of 8 rows, each dividing on y
+              ((2, 70001, 17, 40001), (True, False))]    # through y only, pixel by pixel
+# either side of the first term: (2d - 1) * s + d = 2^32 - 32768, the largest a 32-bit p + 2d takes, and 2^32 + 32767
+BOUNDARY_P = [((65536, 1, 32768, 2), (True, True)), ((65537, 1, 32768, 2), (False, True))]
+# either side of the second term: 513 * d = 2^32 - 8176, where 256 * r + d is the largest 32 bits hold, and 2^32 + 32
+BOUNDARY_F = [((3, 1, 8372240, 1), (True, True)), ((3, 1, 8372256, 1), (False, True))]
+# down in x with a remainder (the column stepper's q >= 1 and m2 > 0), and targets of one row and of one pixel
+DOWN_X = [((37, 5, 16, 8), (True, True)),                # q = 2, 16-byte stores
+          ((100, 7, 48, 10), (True, True)),              # q = 2, three groups, bands of 8 and 2 rows
+          ((50, 3, 17, 1), (True, True)),                # a single odd YUV row
+          ((33, 33, 1, 1), (True, True))]
+NEW_SHAPES = WIDE_INDEX + BOUNDARY_P + BOUNDARY_F + DOWN_X
 
 
 def taps(s, d):
@@ -40,16 +72,23 @@ def scale_bilinear(pix, dw, dh, sums=None):
     assert dw > 0 and dh > 0
     x0, x1, fx = taps(sw, dw)
     y0, y1, fy = taps(sh, dh)
-    fx, fy = fx[None, None, :], fy[None, :, None]
+    fy = fy[None, :, None]
     out = np.zeros((n, dh, dw), np.uint32)
     for s in (16, 8, 0):
         c = ((pix >> s) & 255).astype(np.int64)
-        top = (256 - fx) * c[:, y0][:, :, x0] + fx * c[:, y0][:, :, x1]
-        bot = (256 - fx) * c[:, y1][:, :, x0] + fx * c[:, y1][:, :, x1]
-        acc = (256 - fy) * top + fy * bot + 32768
+        r0, r1 = c[:, y0], c[:, y1]
+        most = 0
+        for a in range(0, dw, COLUMNS):                           # (slices that stay in cache: a target of 8 million columns in half the time)
+            b = min(a + COLUMNS, dw)
+            f, xa, xb = fx[None, None, a:b], x0[a:b], x1[a:b]
+            top = (256 - f) * r0[:, :, xa] + f * r0[:, :, xb]
+            bot = (256 - f) * r1[:, :, xa] + f * r1[:, :, xb]
+            acc = (256 - fy) * top + fy * bot + 32768
+            if sums is not None:
+                most = max(most, int(acc.max()))
+            out[:, :, a:b] |= (acc >> 16).astype(np.uint32) << s
         if sums is not None:
-            sums.append(int(acc.max()))
-        out |= (acc >> 16).astype(np.uint32) << s
+            sums.append(most)
     return out
 
 
