@@ -55,6 +55,14 @@ def oracle():
         L.orc_encoder_free.argtypes = [C.c_void_p]
         L.orc_encode_frame.restype = C.c_size_t
         L.orc_encode_frame.argtypes = [C.c_void_p, u32p, u8p, C.c_void_p]
+        L.orc_compare_iframe_block.restype = C.c_uint8
+        L.orc_compare_iframe_block.argtypes = [u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u16p]
+        L.orc_compare_pframe_block.restype = C.c_uint8
+        L.orc_compare_pframe_block.argtypes = [u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u16p, u16p]
+        L.orc_assemble_iframe.restype = C.c_size_t
+        L.orc_assemble_iframe.argtypes = [u32p, u32p, C.c_int, C.c_uint32, C.c_uint32, u16p, u8p]
+        L.orc_assemble_pframe.restype = C.c_size_t
+        L.orc_assemble_pframe.argtypes = [u32p, u32p, C.c_int, C.c_uint32, C.c_uint32, u16p, u16p, u8p]
         for f in (L.orc_lzss_compress, L.orc_lz77_compress):
             f.restype = C.c_size_t
             f.argtypes = [u8p, C.c_size_t, u8p, C.POINTER(C.c_uint32)]
@@ -120,6 +128,41 @@ LZSS, LZ77 = 1, 2
 
 def max_usize(w, h):
     return 33 * (w * h // 16) + 64
+
+
+def _plane(entries, w, h):
+    e = np.ascontiguousarray(entries, np.uint16).reshape(-1)
+    assert e.size == w * h
+    return e
+
+
+def assemble_iframe(p0, p1, mode512, w, h, entries):
+    """E7 on a given entry plane (u16 [h*w] of pal_num << 8 | index): the frame's bytes"""
+    out = np.zeros(33 * (w * h // 16), np.uint8)
+    n = oracle().orc_assemble_iframe(np.ascontiguousarray(p0, np.uint32), np.ascontiguousarray(p1, np.uint32), int(mode512), w, h,
+                                     _plane(entries, w, h), out)
+    return out[:n].copy()
+
+
+def assemble_pframe(p0, p1, mode512, w, h, entries, iframe_entries):
+    """E8 on a given entry plane and the plane of the GOP's I-frame"""
+    out = np.zeros(33 * (w * h // 16), np.uint8)
+    n = oracle().orc_assemble_pframe(np.ascontiguousarray(p0, np.uint32), np.ascontiguousarray(p1, np.uint32), int(mode512), w, h,
+                                     _plane(entries, w, h), _plane(iframe_entries, w, h), out)
+    return out[:n].copy()
+
+
+def compare_iframe_block(p0, p1, w, x, y, color, entries):
+    """E5: how many of the block's 16 entry colours are within +-2 of `color` on every channel"""
+    return int(oracle().orc_compare_iframe_block(np.ascontiguousarray(p0, np.uint32), np.ascontiguousarray(p1, np.uint32), w, x, y,
+                                                 int(color), np.ascontiguousarray(entries, np.uint16).reshape(-1)))
+
+
+def compare_pframe_block(p0, p1, w, x, y, entries, iframe_entries):
+    """E6: how many of the block's 16 entry colours are within +-2 of the I-frame's at the same pixel"""
+    return int(oracle().orc_compare_pframe_block(np.ascontiguousarray(p0, np.uint32), np.ascontiguousarray(p1, np.uint32), w, x, y,
+                                                 np.ascontiguousarray(entries, np.uint16).reshape(-1),
+                                                 np.ascontiguousarray(iframe_entries, np.uint16).reshape(-1)))
 
 
 class OracleEncoder:
