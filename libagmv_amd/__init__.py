@@ -10,6 +10,7 @@ Layout
   csrc/agmv_audio_hip.hip  audio tracks: the compand / expand kernels (csrc/agmv_audio.h states the codec once, for host and device)
   csrc/*.c            host C: libagmv-compatible API (include/agmv.h), LZSS/LZ77, container,
                       BMP I/O, palette build, synthetic clip generator
+  abi.py              the public C signatures, stated once: both libraries' ctypes tables and the structures (tests/test_abi.py holds them to the headers)
   hip.py              ctypes binding of the C-ABI for tests / bench (torch = device memory only)
   seq.py              ctypes calls of the memory-sequence entry points of include/agmv.h (.agmv file <-> CUDA tensor: five RGB layouts, NV12, I420; normalised float tensors; a scale to a target size before the encode and behind the decode; a decoded clip or file measured against its reference)
   build.py            in-tree build of libagmv_hip.so / libagmv.so (hipcc, gcc)

@@ -1,4 +1,4 @@
-"""ctypes binding of include/agmv_hip.h.
+"""ctypes binding of include/agmv_hip.h (the signatures are abi.HIP).
 
 The product is the shared library; this module only marshals pointers.  torch is used for
 device memory and streams (plumbing).  Every failure is loud: a missing library raises
@@ -9,38 +9,12 @@ import os
 
 import numpy as np
 
+from . import abi
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 # every symbol include/agmv_hip.h declares (tests check the built library exports them all)
-ABI_SYMBOLS = [
-    "agmv_hip_max_usize", "agmv_hip_device_count", "agmv_hip_create", "agmv_hip_destroy",
-    "agmv_hip_last_error", "agmv_hip_set_palette", "agmv_hip_quantise_dev",
-    "agmv_hip_encode_frames_dev", "agmv_hip_encode_frames", "agmv_hip_encode_entries_dev",
-    "agmv_hip_encode_entries", "agmv_hip_nearest", "agmv_hip_within2_count", "agmv_hip_parse_frames_dev",
-    "agmv_hip_decode_frames_dev", "agmv_hip_parse_decode_frames_dev", "agmv_hip_decode_bitstreams_dev", "agmv_hip_pack_frames_dev", "agmv_hip_unpack_frames_dev", "agmv_hip_parse_fallback_frames", "agmv_hip_decode_frames", "agmv_hip_decode_prior_dependent", "agmv_hip_synth_dev",
-    "agmv_hip_interp_dev", "agmv_hip_histogram_dev", "agmv_hip_similarity_dev", "agmv_hip_gather_dev", "agmv_hip_check", "agmv_hip_malloc",
-    "agmv_hip_free", "agmv_hip_memcpy_h2d", "agmv_hip_memcpy_d2h", "agmv_hip_memset",
-    "agmv_hip_sync", "agmv_hip_enable_timing", "agmv_hip_last_kernel_ms",
-    "agmv_hip_stream_create", "agmv_hip_stream_destroy", "agmv_hip_stream_sync", "agmv_hip_host_alloc",
-    "agmv_hip_host_free", "agmv_hip_malloc_on", "agmv_hip_free_on", "agmv_hip_memcpy_async",
-    "agmv_hip_memset_async", "agmv_hip_ctx_device",
-    "agmv_hip_lzss_max_csize", "agmv_hip_lzss_frames_dev", "agmv_hip_lzss_frames",
-    "agmv_hip_lz77_max_csize", "agmv_hip_lz77_peek_dev", "agmv_hip_lz77_frames_dev", "agmv_hip_lz77_frames",
-    "agmv_hip_lz77_reparsed_segments",
-    "agmv_hip_lz_decode_frames_dev", "agmv_hip_lz_decode_commit_dev", "agmv_hip_lz_decode_fallback_frames",
-    "agmv_hip_lz_decode_frames", "agmv_hip_lz_decode_frames_sized_dev",
-    "agmv_hip_event_create", "agmv_hip_event_destroy", "agmv_hip_event_record", "agmv_hip_stream_wait_event",
-    "agmv_hip_pixfmt_frame_bytes", "agmv_hip_pixels_to_xrgb_dev", "agmv_hip_pixels_from_xrgb_dev", "agmv_hip_gather_fmt_dev",
-    "agmv_hip_histogram_fmt_dev", "agmv_hip_similarity_fmt_dev",
-    "agmv_hip_yuv_frame_bytes", "agmv_hip_yuv_to_xrgb_dev", "agmv_hip_yuv_from_xrgb_dev", "agmv_hip_yuv_gather_dev",
-    "agmv_hip_yuv_histogram_dev", "agmv_hip_yuv_similarity_dev",
-    "agmv_hip_scale_area_dev", "agmv_hip_scale_frames_async",
-    "agmv_hip_palette_refine_dev",
-    "agmv_hip_dither_frames_async",
-    "agmv_hip_audio_compand_async", "agmv_hip_audio_expand_async",
-    "agmv_hip_measure_frames_async",
-    "agmv_hip_tensor_frame_bytes", "agmv_hip_tensor_table", "agmv_hip_tensor_from_xrgb_async", "agmv_hip_tensor_to_xrgb_async",
-]
+ABI_SYMBOLS = list(abi.HIP)
 
 
 class HipUnavailable(RuntimeError):
@@ -75,150 +49,8 @@ def load_library(path=None):
         L = C.CDLL(p)
     except OSError as e:
         raise HipUnavailable("cannot load %s: %s" % (p, e))
-    vp, sz, u32 = C.c_void_p, C.c_size_t, C.c_uint32
-    L.agmv_hip_max_usize.restype = sz
-    L.agmv_hip_max_usize.argtypes = [u32, u32, C.c_int]
-    L.agmv_hip_device_count.restype = C.c_int
-    L.agmv_hip_create.restype = vp
-    L.agmv_hip_create.argtypes = [C.c_int]
-    L.agmv_hip_destroy.argtypes = [vp]
-    L.agmv_hip_last_error.restype = C.c_char_p
-    L.agmv_hip_set_palette.argtypes = [vp, vp, vp, C.c_int, vp]
-    L.agmv_hip_quantise_dev.argtypes = [vp, vp, sz, vp, vp]
-    L.agmv_hip_encode_frames_dev.argtypes = [vp, vp, u32, u32, u32, u32, vp, sz, vp, vp, vp]
-    L.agmv_hip_encode_frames.argtypes = [vp, vp, u32, u32, u32, u32, vp, sz, vp, vp]
-    L.agmv_hip_encode_entries_dev.argtypes = [vp, vp, u32, u32, u32, u32, vp, sz, vp, vp, vp]
-    L.agmv_hip_encode_entries.argtypes = [vp, vp, u32, u32, u32, u32, vp, sz, vp, vp]
-    L.agmv_hip_nearest.argtypes = [vp, vp, vp, C.c_int, vp, sz, vp]
-    L.agmv_hip_within2_count.argtypes = [vp, vp, vp]
-    L.agmv_hip_within2_count.restype = C.c_int
-    L.agmv_hip_parse_frames_dev.argtypes = [vp, vp, sz, vp, u32, u32, u32, vp, vp, vp]
-    L.agmv_hip_decode_frames_dev.argtypes = [vp, vp, sz, vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]
-    L.agmv_hip_decode_frames.argtypes = [vp, vp, sz, vp, u32, u32, u32, u32, vp, vp, vp]
-    L.agmv_hip_parse_decode_frames_dev.argtypes = [vp, vp, sz, vp, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp]
-    if path is None or hasattr(L, "agmv_hip_decode_bitstreams_dev"):    # (an explicit `path` may be an older build kept for A/B timing, tools/variants/)
-        L.agmv_hip_decode_bitstreams_dev.argtypes = [vp, vp, sz, vp, u32, u32, u32, u32, vp, vp, vp, vp, vp]
-        L.agmv_hip_decode_bitstreams_dev.restype = C.c_int
-    L.agmv_hip_decode_prior_dependent.argtypes = [vp, u32, u32, vp]
-    L.agmv_hip_parse_fallback_frames.argtypes = [vp, vp]
-    if path is None or hasattr(L, "agmv_hip_pack_frames_dev"):      # (older builds under tools/variants/ lack it)
-        L.agmv_hip_pack_frames_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp]
-        L.agmv_hip_pack_frames_dev.restype = C.c_int
-        L.agmv_hip_unpack_frames_dev.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp]
-        L.agmv_hip_unpack_frames_dev.restype = C.c_int
-    L.agmv_hip_parse_fallback_frames.restype = C.c_int
-    if path is None or hasattr(L, "agmv_hip_lzss_frames_dev"):      # (older builds under tools/variants/ lack it)
-        L.agmv_hip_lzss_max_csize.restype = sz
-        L.agmv_hip_lzss_max_csize.argtypes = [sz]
-        L.agmv_hip_lzss_frames_dev.argtypes = [vp, vp, sz, vp, u32, vp, sz, vp, vp]
-        L.agmv_hip_lzss_frames_dev.restype = C.c_int
-        L.agmv_hip_lzss_frames.argtypes = [vp, vp, sz, vp, u32, vp, sz, vp]
-        L.agmv_hip_lzss_frames.restype = C.c_int
-    if path is None or hasattr(L, "agmv_hip_lz77_frames_dev"):
-        L.agmv_hip_lz77_max_csize.restype = sz
-        L.agmv_hip_lz77_max_csize.argtypes = [sz]
-        L.agmv_hip_lz77_peek_dev.argtypes = [vp, vp, sz, vp, u32, vp, sz, vp, vp]
-        L.agmv_hip_lz77_peek_dev.restype = C.c_int
-        L.agmv_hip_lz77_frames_dev.argtypes = [vp, vp, sz, vp, u32, vp, vp, sz, vp, vp]
-        L.agmv_hip_lz77_frames_dev.restype = C.c_int
-        L.agmv_hip_lz77_frames.argtypes = [vp, vp, sz, vp, u32, vp, sz, vp, sz, vp]
-        L.agmv_hip_lz77_frames.restype = C.c_int
-        L.agmv_hip_lz77_reparsed_segments.argtypes = [vp, vp]
-        L.agmv_hip_lz77_reparsed_segments.restype = C.c_int
-    if path is None or hasattr(L, "agmv_hip_lz_decode_frames_dev"):
-        L.agmv_hip_lz_decode_frames_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, u32, vp, sz, sz, vp, vp, vp]
-        L.agmv_hip_lz_decode_frames_dev.restype = C.c_int
-        L.agmv_hip_lz_decode_frames_sized_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, u32, vp, sz, sz, vp, vp, vp]
-        L.agmv_hip_lz_decode_frames_sized_dev.restype = C.c_int
-        L.agmv_hip_lz_decode_commit_dev.argtypes = [vp, vp, sz, vp, u32, vp, sz, vp]
-        L.agmv_hip_lz_decode_commit_dev.restype = C.c_int
-        L.agmv_hip_lz_decode_fallback_frames.argtypes = [vp, vp]
-        L.agmv_hip_lz_decode_fallback_frames.restype = C.c_int
-        L.agmv_hip_lz_decode_frames.argtypes = [vp, C.c_int, vp, sz, vp, vp, vp, vp, u32, vp, sz, sz, vp, vp, vp]
-        L.agmv_hip_lz_decode_frames.restype = C.c_int
-    L.agmv_hip_decode_prior_dependent.restype = C.c_int
-    L.agmv_hip_synth_dev.argtypes = [vp, vp, u32, u32, u32, u32, C.c_uint64, vp]
-    L.agmv_hip_interp_dev.argtypes = [vp, vp, vp, vp, sz, vp]
-    L.agmv_hip_histogram_dev.argtypes = [vp, vp, sz, C.c_int, vp, vp]
-    L.agmv_hip_similarity_dev.argtypes = [vp, vp, u32, sz, vp, vp]
-    L.agmv_hip_similarity_dev.restype = C.c_int
-    L.agmv_hip_gather_dev.argtypes = [vp, vp, sz, u32, vp, sz, vp, vp]
-    L.agmv_hip_gather_dev.restype = C.c_int
-    if path is None or hasattr(L, "agmv_hip_pixels_to_xrgb_dev"):     # (older builds under tools/variants/ lack them)
-        L.agmv_hip_pixfmt_frame_bytes.restype = sz
-        L.agmv_hip_pixfmt_frame_bytes.argtypes = [C.c_int, sz]
-        L.agmv_hip_pixels_to_xrgb_dev.argtypes = [vp, C.c_int, vp, sz, u32, sz, vp, vp]
-        L.agmv_hip_pixels_from_xrgb_dev.argtypes = [vp, C.c_int, vp, u32, sz, vp, vp]
-        L.agmv_hip_gather_fmt_dev.argtypes = [vp, C.c_int, vp, sz, u32, vp, sz, vp, vp]
-        L.agmv_hip_histogram_fmt_dev.argtypes = [vp, C.c_int, vp, sz, u32, sz, C.c_int, vp, vp]
-        L.agmv_hip_similarity_fmt_dev.argtypes = [vp, C.c_int, vp, u32, sz, vp, vp]
-        for f in (L.agmv_hip_pixels_to_xrgb_dev, L.agmv_hip_pixels_from_xrgb_dev, L.agmv_hip_gather_fmt_dev, L.agmv_hip_histogram_fmt_dev,
-                  L.agmv_hip_similarity_fmt_dev):
-            f.restype = C.c_int
-    if path is None or hasattr(L, "agmv_hip_yuv_to_xrgb_dev"):
-        L.agmv_hip_yuv_frame_bytes.restype = sz
-        L.agmv_hip_yuv_frame_bytes.argtypes = [C.c_int, u32, u32]
-        L.agmv_hip_yuv_to_xrgb_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, sz, vp, vp]
-        L.agmv_hip_yuv_from_xrgb_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, vp, vp]
-        L.agmv_hip_yuv_gather_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, vp, sz, vp, vp]
-        L.agmv_hip_yuv_histogram_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, sz, C.c_int, vp, vp]
-        L.agmv_hip_yuv_similarity_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, vp, vp]
-        for f in (L.agmv_hip_yuv_to_xrgb_dev, L.agmv_hip_yuv_from_xrgb_dev, L.agmv_hip_yuv_gather_dev, L.agmv_hip_yuv_histogram_dev,
-                  L.agmv_hip_yuv_similarity_dev):
-            f.restype = C.c_int
-    if path is None or hasattr(L, "agmv_hip_scale_area_dev"):
-        L.agmv_hip_scale_area_dev.argtypes = [vp, C.c_int, vp, u32, u32, u32, u32, u32, vp, vp]
-        L.agmv_hip_scale_area_dev.restype = C.c_int
-    if path is None or hasattr(L, "agmv_hip_scale_frames_async"):
-        L.agmv_hip_scale_frames_async.argtypes = [vp, C.c_int, vp, u32, u32, u32, C.c_int, u32, u32, vp, vp]
-        L.agmv_hip_scale_frames_async.restype = C.c_int
-    if path is None or hasattr(L, "agmv_hip_palette_refine_dev"):
-        L.agmv_hip_palette_refine_dev.argtypes = [vp, vp, C.c_int, vp, u32, u32, u32, vp, vp, vp]
-        L.agmv_hip_palette_refine_dev.restype = C.c_int
-    if path is None or hasattr(L, "agmv_hip_dither_frames_async"):
-        L.agmv_hip_dither_frames_async.argtypes = [vp, u32, vp, u32, u32, u32, vp]
-        L.agmv_hip_dither_frames_async.restype = C.c_int
-    if path is None or hasattr(L, "agmv_hip_audio_compand_async"):
-        L.agmv_hip_audio_compand_async.argtypes = [vp, C.c_int, vp, u32, C.c_uint64, vp, vp]
-        L.agmv_hip_audio_expand_async.argtypes = [vp, C.c_int, vp, u32, C.c_uint64, vp, vp]
-        L.agmv_hip_audio_compand_async.restype = L.agmv_hip_audio_expand_async.restype = C.c_int
-    if path is None or hasattr(L, "agmv_hip_measure_frames_async"):
-        L.agmv_hip_measure_frames_async.argtypes = [vp, vp, C.c_int, vp, u32, u32, u32, vp, vp]
-        L.agmv_hip_measure_frames_async.restype = C.c_int
-    if path is None or hasattr(L, "agmv_hip_tensor_table"):
-        L.agmv_hip_tensor_frame_bytes.restype = sz
-        L.agmv_hip_tensor_frame_bytes.argtypes = [C.c_int, sz]
-        L.agmv_hip_tensor_table.argtypes = [C.c_int, vp, vp, vp]
-        L.agmv_hip_tensor_from_xrgb_async.argtypes = [vp, C.c_int, vp, u32, u32, u32, C.c_int, u32, u32, vp, vp, vp]
-        L.agmv_hip_tensor_to_xrgb_async.argtypes = [vp, C.c_int, vp, sz, u32, vp, vp, vp]
-        L.agmv_hip_tensor_table.restype = L.agmv_hip_tensor_from_xrgb_async.restype = L.agmv_hip_tensor_to_xrgb_async.restype = C.c_int
-    L.agmv_hip_check.argtypes = [vp, vp]
-    L.agmv_hip_enable_timing.argtypes = [vp, C.c_int]
-    L.agmv_hip_enable_timing.restype = C.c_int
-    L.agmv_hip_last_kernel_ms.argtypes = [vp, C.c_int]
-    L.agmv_hip_last_kernel_ms.restype = C.c_float
-    # streams, events, pinned staging and asynchronous copies (pointers: without a restype ctypes would cut them to 32 bits)
-    L.agmv_hip_stream_create.restype, L.agmv_hip_stream_create.argtypes = vp, [vp]
-    L.agmv_hip_stream_destroy.restype, L.agmv_hip_stream_destroy.argtypes = None, [vp, vp]
-    L.agmv_hip_stream_sync.restype, L.agmv_hip_stream_sync.argtypes = C.c_int, [vp, vp]
-    if path is None or hasattr(L, "agmv_hip_event_create"):         # (older builds under tools/variants/ lack them)
-        L.agmv_hip_event_create.restype, L.agmv_hip_event_create.argtypes = vp, [vp]
-        L.agmv_hip_event_destroy.restype, L.agmv_hip_event_destroy.argtypes = None, [vp, vp]
-        L.agmv_hip_event_record.restype, L.agmv_hip_event_record.argtypes = C.c_int, [vp, vp, vp]
-        L.agmv_hip_stream_wait_event.restype, L.agmv_hip_stream_wait_event.argtypes = C.c_int, [vp, vp, vp]
-    L.agmv_hip_host_alloc.restype, L.agmv_hip_host_alloc.argtypes = vp, [sz]
-    L.agmv_hip_host_free.restype, L.agmv_hip_host_free.argtypes = None, [vp]
-    L.agmv_hip_memcpy_async.argtypes = [vp, vp, vp, sz, C.c_int, vp]
-    L.agmv_hip_memset_async.argtypes = [vp, vp, C.c_int, sz, vp]
-    L.agmv_hip_memcpy_async.restype = L.agmv_hip_memset_async.restype = C.c_int
-    L.agmv_hip_malloc.restype = vp
-    L.agmv_hip_malloc.argtypes = [sz]
-    L.agmv_hip_free.argtypes = [vp]
-    for f in (L.agmv_hip_set_palette, L.agmv_hip_quantise_dev, L.agmv_hip_encode_frames_dev,
-              L.agmv_hip_encode_frames, L.agmv_hip_encode_entries_dev, L.agmv_hip_encode_entries, L.agmv_hip_nearest, L.agmv_hip_parse_frames_dev, L.agmv_hip_decode_frames_dev,
-              L.agmv_hip_decode_frames, L.agmv_hip_parse_decode_frames_dev, L.agmv_hip_synth_dev, L.agmv_hip_interp_dev,
-              L.agmv_hip_histogram_dev, L.agmv_hip_check):
-        f.restype = C.c_int
+    # only an explicitly named other build of the same source may lack symbols; the default library has them all
+    abi.bind(L, abi.HIP, missing_ok=path is not None)
     _libs[p] = L
     return L
 

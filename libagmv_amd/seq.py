@@ -29,23 +29,13 @@ Audio tracks (AGMV_PCMFMT; include/agmv.h, "audio tracks") and the tensors that 
 import ctypes as C
 import os
 
+from . import abi
+from .abi import AGMV_FRAME_QUALITY, AGMV_INFO  # noqa: F401  (importable from here as before)
 from .hip import HERE, PIXFMT, TENSORFMT, YUVFMT, HipUnavailable, pcmfmt, pixfmt, tensor_normalisation, yuvfmt
 
 SCHEDULE_FULL, SCHEDULE_PDIFS, SCHEDULE_ADAPTIVE = 1, 2, 3
 SCALE = {"nearest": 1, "area": 2}          # AGMV_SCALE of include/agmv.h, which defines both filters
 DECODE_SCALE = {"nearest": 1, "area": 2, "bilinear": 3}      # ... and the filters of decode_frames(size=): AGMV_DecodeFramesScaledDev
-
-
-class AGMV_FRAME_QUALITY(C.Structure):
-    # include/agmv.h: 96 bytes, the same on host and device
-    _fields_ = [("sse", C.c_ulonglong * 3), ("block_sse", C.c_ulonglong * 3), ("max_err", C.c_ulonglong * 3), ("ssim", C.c_longlong * 3)]
-
-
-class AGMV_INFO(C.Structure):
-    # include/agmv.h (u32 is `unsigned long` there)
-    _fields_ = [("width", C.c_ulong), ("height", C.c_ulong), ("number_of_frames", C.c_ulong), ("version", C.c_ubyte),
-                ("total_audio_duration", C.c_ulong), ("sample_rate", C.c_ulong), ("audio_size", C.c_ulong),
-                ("number_of_channels", C.c_ushort), ("bits_per_sample", C.c_ushort)]
 
 
 _lib = None
@@ -58,37 +48,7 @@ def load_library():
         p = os.path.join(HERE, "libagmv.so")
         if not os.path.exists(p):
             raise HipUnavailable("%s is missing: run `python -m libagmv_amd.build`; the AGMV hot path has no CPU fallback" % p)
-        L = C.CDLL(p)
-        L.AGMV_EncodeFramesDev.restype = C.c_int
-        L.AGMV_EncodeFramesDev.argtypes = [C.c_char_p, C.c_void_p] + [C.c_ulong] * 4 + [C.c_int] * 4
-        L.AGMV_DecodeFramesDev.restype = C.c_int
-        L.AGMV_DecodeFramesDev.argtypes = [C.c_char_p, C.c_void_p, C.c_ulong, C.POINTER(AGMV_INFO)]
-        L.AGMV_EncodeFramesFmtDev.restype = C.c_int
-        L.AGMV_EncodeFramesFmtDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int] + [C.c_ulong] * 4 + [C.c_int] * 4
-        L.AGMV_DecodeFramesFmtDev.restype = C.c_int
-        L.AGMV_DecodeFramesFmtDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.POINTER(AGMV_INFO)]
-        L.AGMV_DecodeFramesScaledDev.restype = C.c_int
-        L.AGMV_DecodeFramesScaledDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.c_ulong, C.c_int, C.c_ulong, C.POINTER(AGMV_INFO)]
-        L.AGMV_EncodeFramesScaledDev.restype = C.c_int
-        L.AGMV_EncodeFramesScaledDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int] + [C.c_ulong] * 5 + [C.c_int, C.c_ulong] + [C.c_int] * 4
-        L.AGMV_EncodeFramesTensorDev.restype = C.c_int
-        L.AGMV_EncodeFramesTensorDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_ulong] * 4 + [C.c_int] * 4
-        L.AGMV_DecodeFramesTensorDev.restype = C.c_int
-        L.AGMV_DecodeFramesTensorDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_ulong, C.c_ulong, C.c_int, C.c_ulong,
-                                                 C.POINTER(AGMV_INFO)]
-        L.AGMV_SetPaletteRefine.restype = None
-        L.AGMV_SetPaletteRefine.argtypes = [C.c_uint]
-        L.AGMV_SetDither.restype = None
-        L.AGMV_SetDither.argtypes = [C.c_uint]
-        L.AGMV_SetAudioDev.restype = C.c_int
-        L.AGMV_SetAudioDev.argtypes = [C.c_void_p, C.c_int, C.c_ulong, C.c_ulong, C.c_ushort]
-        L.AGMV_DecodeAudioDev.restype = C.c_int
-        L.AGMV_DecodeAudioDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.POINTER(AGMV_INFO)]
-        L.AGMV_MeasureFramesDev.restype = C.c_int
-        L.AGMV_MeasureFramesDev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_ulong, C.c_ulong, C.c_ulong, C.POINTER(AGMV_FRAME_QUALITY)]
-        L.AGMV_MeasureFileDev.restype = C.c_int
-        L.AGMV_MeasureFileDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.POINTER(AGMV_FRAME_QUALITY), C.POINTER(AGMV_INFO)]
-        _lib = L
+        _lib = abi.bind(C.CDLL(p), abi.AGMV)
     return _lib
 
 

@@ -133,30 +133,9 @@ def libc():
 
 
 def bind(L):
-    """argument types of the audio part of the reference API, on either library"""
-    ul = C.c_ulong
-    L.CreateAGMV.restype = vp
-    L.CreateAGMV.argtypes = [ul] * 4
-    L.DestroyAGMV.argtypes = [vp]
-    L.AGMV_DecodeHeader.restype = C.c_int
-    L.AGMV_DecodeHeader.argtypes = [vp, vp]
-    for name, args in (("AGMV_SetTotalAudioDuration", [vp, ul]), ("AGMV_SetSampleRate", [vp, ul]), ("AGMV_SetNumberOfChannels", [vp, C.c_ubyte]),
-                       ("AGMV_SetAudioSize", [vp, ul]), ("AGMV_SetBitsPerSample", [vp, C.c_ushort]), ("AGMV_SyncAudioTrack", [vp, vp]),
-                       ("AGMV_CompressAudio", [vp]), ("AGMV_WavToAudioTrack", [C.c_char_p, vp]), ("AGMV_ExportAudioType", [vp, vp, C.c_int]),
-                       ("AGMV_FindNextFrameChunk", [vp]), ("AGMV_SkipFrameChunk", [vp]), ("AGMV_FindNextAudioChunk", [vp])):
-        getattr(L, name).restype = None
-        getattr(L, name).argtypes = args
-    for name in ("AGMV_GetTotalAudioDuration", "AGMV_GetSampleRate", "AGMV_GetAudioSize", "AGMV_GetNumberOfFrames"):
-        getattr(L, name).restype = ul
-        getattr(L, name).argtypes = [vp]
-    for name in ("AGMV_GetNumberOfChannels", "AGMV_GetBitsPerSample"):
-        getattr(L, name).restype = C.c_ushort
-        getattr(L, name).argtypes = [vp]
-    L.AGMV_DecodeAudioChunk.restype = C.c_int
-    L.AGMV_DecodeAudioChunk.argtypes = [vp, vp]
-    L.AGMV_DecodeAudio.restype = C.c_int
-    L.AGMV_DecodeAudio.argtypes = [C.c_char_p, C.c_int]
-    return L
+    """the API of include/agmv.h on either library"""
+    import hostlib
+    return hostlib.bind(L, missing_ok=True)
 
 
 class Track:

@@ -34,10 +34,7 @@ HEAVY = {3: False, 1: True, 2: False}
 def main():
     O.build_oracles()
     assert O.have_ref(), "reference build missing"
-    R = C.CDLL(O.REF_SO)
-    u64p = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
-    R.AGMV_CompareFrameSimilarity.restype = C.c_float
-    R.AGMV_CompareFrameSimilarity.argtypes = [u64p, u64p, C.c_ulong, C.c_ulong]
+    R = Hh.bind(C.CDLL(O.REF_SO), missing_ok=True)
     clip = MC.mixed_clip()
     T, H, W = clip.shape
     wide = [np.ascontiguousarray(f.reshape(-1)).astype(np.uint64) for f in clip]

@@ -4,6 +4,8 @@ import os
 
 import numpy as np
 
+from libagmv_amd import abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO = os.path.join(ROOT, "libagmv_amd", "libagmv.so")
 
@@ -11,7 +13,36 @@ u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
 u64p = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
 
+# exports of libagmv.so that exist for the tests alone and stand in no public header
+TEST_ONLY = {
+    "agmv_lzss_mem": (C.c_ulong, (u8p, C.c_size_t, u8p)),
+    "agmv_lz77_mem": (C.c_ulong, (u8p, C.c_size_t, u8p)),
+    "agmv_lz_decode_mem": (C.c_ulong, (C.c_int, u8p, C.c_size_t, C.c_ulong, C.c_ulong, u8p, C.c_size_t, C.POINTER(C.c_size_t))),
+    "agmv_bmp_save": (C.c_int, (C.c_char_p, u32p, C.c_uint32, C.c_uint32)),
+    "agmv_bmp_load": (C.c_int, (C.c_char_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))),
+    "agmv_source_index": (C.POINTER(C.c_uint32), (C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32)),
+}
+# pointer slots of abi.AGMV that the tests fill with numpy arrays (the header's u32 has 8 bytes)
+ARRAYS = {"AGMV_SetICP0": {1: u64p}, "AGMV_SetICP1": {1: u64p}, "AGMV_EncodeFrame": {2: u64p}, "AGMV_BuildPalette": {0: u32p, 3: u64p, 4: u64p},
+          "AGMV_SynthFrame": {0: u32p}, "AGMV_BubbleSort": {0: u64p, 1: u64p}, "AGMV_FindNearestColor": {0: u64p},
+          "AGMV_FindNearestEntry": {0: u64p, 1: u64p}, "AGMV_CompareFrameSimilarity": {0: u64p, 1: u64p}}
+
 _lib = None
+
+
+def bind(L, missing_ok=False):
+    """a loaded libagmv.so (or, with missing_ok, the compiled reference, which shares the API) bound from the tables"""
+    abi.bind(L, abi.AGMV, missing_ok)
+    abi.bind(L, TEST_ONLY, missing_ok)
+    for name, slots in ARRAYS.items():
+        f = getattr(L, name, None)
+        if f is not None:
+            args = list(f.argtypes)
+            for i, t in slots.items():
+                assert args[i] is C.c_void_p, (name, i)
+                args[i] = t
+            f.argtypes = args
+    return L
 
 
 def lib():
@@ -19,42 +50,7 @@ def lib():
     if _lib is None:
         from libagmv_amd import build
         build.build()
-        L = C.CDLL(SO)
-        L.agmv_lzss_mem.restype = C.c_ulong
-        L.agmv_lzss_mem.argtypes = [u8p, C.c_size_t, u8p]
-        L.agmv_lz77_mem.restype = C.c_ulong
-        L.agmv_lz77_mem.argtypes = [u8p, C.c_size_t, u8p]
-        L.agmv_lz_decode_mem.restype = C.c_ulong
-        L.agmv_lz_decode_mem.argtypes = [C.c_int, u8p, C.c_size_t, C.c_ulong, C.c_ulong, u8p, C.c_size_t, C.POINTER(C.c_size_t)]
-        L.AGMV_BuildPalette.restype = None
-        L.AGMV_BuildPalette.argtypes = [u32p, C.c_int, C.c_int, u64p, u64p]
-        L.AGMV_SynthFrame.restype = None
-        L.AGMV_SynthFrame.argtypes = [u32p, C.c_uint, C.c_uint, C.c_uint, C.c_ulonglong]
-        L.AGMV_BubbleSort.restype = None
-        L.AGMV_BubbleSort.argtypes = [u64p, u64p, C.c_ulong]
-        L.agmv_bmp_save.argtypes = [C.c_char_p, u32p, C.c_uint32, C.c_uint32]
-        L.agmv_bmp_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.CreateAGMV.restype = C.c_void_p
-        L.CreateAGMV.argtypes = [C.c_ulong] * 4
-        L.DestroyAGMV.argtypes = [C.c_void_p]
-        for f in ("AGMV_EncodeAGMV", "AGMV_EncodeFullAGMV"):
-            getattr(L, f).restype = None
-            getattr(L, f).argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ubyte] + [C.c_ulong] * 5 + [C.c_int] * 3
-        L.AGMV_EncodeVideo.restype = None
-        L.AGMV_EncodeVideo.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_ubyte] + [C.c_ulong] * 5 + [C.c_int] * 3
-        L.AGMV_DecodeAGMV.restype = C.c_int
-        L.AGMV_DecodeAGMV.argtypes = [C.c_char_p, C.c_ubyte, C.c_int]
-        L.AGMV_DecodeVideo.restype = C.c_int
-        L.AGMV_DecodeVideo.argtypes = [C.c_char_p, C.c_ubyte]
-        L.AGMV_QuantizeColor.restype = C.c_ulong
-        L.AGMV_QuantizeColor.argtypes = [C.c_ulong, C.c_int]
-        L.AGMV_ReverseQuantizeColor.restype = C.c_ulong
-        L.AGMV_ReverseQuantizeColor.argtypes = [C.c_ulong, C.c_int]
-        L.AGMV_GetVersionFromOPT.restype = C.c_ubyte
-        L.AGMV_GetVersionFromOPT.argtypes = [C.c_int, C.c_int]
-        L.AGMV_SetBatchFrames.argtypes = [C.c_uint]
-        L.AGMV_SetLZThreads.argtypes = [C.c_uint]
-        _lib = L
+        _lib = bind(C.CDLL(SO))
     return _lib
 
 

@@ -128,7 +128,6 @@ def test_decode_chunk_without_a_buffer_seeks_over_the_payload(tmp_path):
 
 def test_encode_chunk_writes_zeros_past_audio_size(tmp_path):
     L, libc = ours(), A.libc()
-    L.AGMV_EncodeAudioChunk.restype, L.AGMV_EncodeAudioChunk.argtypes = None, [vp, vp]
     a = L.CreateAGMV(1, 4, 4, 1)
     L.AGMV_SetAudioSize(a, 10)
     L.AGMV_SetTotalAudioDuration(a, 1)
@@ -331,8 +330,6 @@ def test_signed_unsigned_and_raw_importers(tmp_path):
     L.AGMV_UnsigendToSignedPCM(buf.ctypes.data_as(vp), C.c_ulong(len(buf)))
     assert (buf == raw).all()
     (tmp_path / "s8.raw").write_bytes(raw.tobytes())
-    L.AGMV_RawSignedPCMToAudioTrack.argtypes = [C.c_char_p, vp, C.c_ubyte, C.c_ulong]
-    L.AGMV_Raw8PCMToAudioTrack.argtypes = [C.c_char_p, vp]
     a = L.CreateAGMV(1, 4, 4, 1)
     L.AGMV_RawSignedPCMToAudioTrack(str(tmp_path / "s8.raw").encode(), a, 2, 500)
     assert (L.AGMV_GetTotalAudioDuration(a), L.AGMV_GetSampleRate(a), L.AGMV_GetAudioSize(a), L.AGMV_GetNumberOfChannels(a), L.AGMV_GetBitsPerSample(a)) == (2, 500, 2100, 2, 8)
@@ -351,8 +348,6 @@ def test_signed_unsigned_and_raw_importers(tmp_path):
 def test_set_audio_dev_refusals():
     """AGMV_SetAudioDev stores its arguments: nothing is read and no device is opened, so the refusals need no GPU"""
     L = H.lib()
-    L.AGMV_SetAudioDev.restype = C.c_int
-    L.AGMV_SetAudioDev.argtypes = [vp, C.c_int, C.c_ulong, C.c_ulong, C.c_ushort]
     p = 0x10000
     try:
         assert L.AGMV_SetAudioDev(p, 0, 48000, 48000, 2) == -1 and L.AGMV_SetAudioDev(p, 4, 48000, 48000, 2) == -1      # a bad format

@@ -19,14 +19,14 @@ import pytest
 
 import hostlib as H
 import oracles as O
+from libagmv_amd import abi
 
 needs_ref = pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (needs /root/reference at build time)")
 vp = C.c_void_p
 SPLASH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "agmv_splash.agmv")
 
 
-class Entry(C.Structure):                       # AGMV_ENTRY, include/agmv.h (reference include/agmv_defines.h:122-126)
-    _fields_ = [("pal_num", C.c_ubyte), ("index", C.c_ubyte), ("occurence", C.c_ulong)]
+Entry = abi.AGMV_ENTRY
 
 
 def _libc():
@@ -41,21 +41,9 @@ def _libc():
     return libc
 
 
-def _bind_playback(L):
-    L.CreateAGMV.restype = vp
-    L.CreateAGMV.argtypes = [C.c_ulong] * 4
-    L.DestroyAGMV.argtypes = [vp]
-    L.AGMV_DecodeHeader.restype = C.c_int
-    L.AGMV_DecodeHeader.argtypes = [vp, vp]
-    for f in ("AGMV_ParseAGMV", "AGMV_ResetVideo", "AGMV_PlayAGMV"):
-        getattr(L, f).restype = None
-        getattr(L, f).argtypes = [vp, vp]
-    for f in ("AGMV_SkipForwards", "AGMV_SkipBackwards", "AGMV_SkipTo", "AGMV_SkipForwardsAndDecodeAudio"):
-        getattr(L, f).restype = None
-        getattr(L, f).argtypes = [vp, vp, C.c_int]
-    L.AGMV_IsVideoDone.restype = C.c_int
-    L.AGMV_IsVideoDone.argtypes = [vp]
-    return L
+def _ref_lib():
+    """the compiled reference: it shares the API of include/agmv.h"""
+    return H.bind(O.ref(), missing_ok=True)
 
 
 def _ref_accessors():
@@ -72,14 +60,12 @@ class Player:
     """one library's view of the splash file: an AGMV object + an open FILE*, driven step by step"""
 
     def __init__(self, L, R, libc):
-        self.L, self.R, self.libc = _bind_playback(L), R, libc
+        self.L, self.R, self.libc = L, R, libc
         self.a = self.L.CreateAGMV(119, 320, 240, 12)
         self.f = libc.fopen(SPLASH.encode(), b"rb")
         assert self.L.AGMV_DecodeHeader(self.f, self.a) == 0
         # the file carries audio: give the object the sample buffer a player allocates (reference src/agmv_decode.c:575), the
         # reference's chunk walk writes the decoded samples there; DestroyAGMV frees it
-        self.L.AGMV_GetAudioSize.restype = C.c_ulong
-        self.L.AGMV_GetAudioSize.argtypes = [vp]
         track = C.c_void_p.from_address(self.a + 4216).value                  # agmv->audio_track
         C.c_void_p.from_address(track + 16).value = libc.calloc(2 * self.L.AGMV_GetAudioSize(self.a) + 64, 2)   # ->pcm (room for the chunks the script decodes twice)
         C.c_void_p.from_address(track + 24).value = None                      # ->pcm8
@@ -117,7 +103,7 @@ class Player:
 def test_parse_and_seek_helpers_match_reference():
     """no decode involved: chunk walk, offset_table bookkeeping and the seek arithmetic (also the version-1-only reset)"""
     libc, R = _libc(), _ref_accessors()
-    ours, ref = Player(H.lib(), R, libc), Player(O.ref(), R, libc)
+    ours, ref = Player(H.lib(), R, libc), Player(_ref_lib(), R, libc)
     steps = [("AGMV_ParseAGMV", None), ("AGMV_ResetVideo", None), ("AGMV_SkipForwards", 1), ("AGMV_SkipForwards", 6),
              ("AGMV_SkipBackwards", 3), ("AGMV_SkipForwards", 4), ("AGMV_SkipTo", 37), ("AGMV_SkipBackwards", 8),
              ("AGMV_SkipTo", 118), ("AGMV_SkipTo", 400), ("AGMV_SkipForwardsAndDecodeAudio", 2), ("AGMV_SkipBackwards", 1),
@@ -131,7 +117,7 @@ def test_parse_and_seek_helpers_match_reference():
     assert ours.table(119) == ref.table(119)
     # a fresh object that is never parsed: the skips fill offset_table as they go (reference src/agmv_playback.c:35-60)
     ours.close(); ref.close()
-    ours, ref = Player(H.lib(), R, libc), Player(O.ref(), R, libc)
+    ours, ref = Player(H.lib(), R, libc), Player(_ref_lib(), R, libc)
     for n in (2, 5, 1):
         for p in (ours, ref):
             p.L.AGMV_SkipForwards(p.f, p.a, n)
@@ -150,7 +136,7 @@ def test_play_and_seek_like_a_player():
     """AGMV_PlayAGMV + skips in a player loop WITHOUT AGMV_ParseAGMV (tools/agmvp's pattern): file position, frame_count,
     offset_table and the decoded frame after every step equal the reference's"""
     libc, R = _libc(), _ref_accessors()
-    ours, ref = Player(H.lib(), R, libc), Player(O.ref(), R, libc)
+    ours, ref = Player(H.lib(), R, libc), Player(_ref_lib(), R, libc)
     script = [("play", 6), ("fwd", 3), ("play", 3), ("back", 4), ("play", 5), ("fwd", 1), ("play", 2), ("reset", 0), ("play", 2)]
     for what, n in script:
         for k in range(n if what == "play" else 1):
@@ -188,10 +174,6 @@ def _dup_palettes(seed=5):
 @pytest.mark.gpu
 def test_exported_find_nearest_matches_reference():
     L = H.lib()
-    L.AGMV_FindNearestColor.restype = C.c_ubyte
-    L.AGMV_FindNearestColor.argtypes = [H.u64p, C.c_ulong]
-    L.AGMV_FindNearestEntry.restype = Entry
-    L.AGMV_FindNearestEntry.argtypes = [H.u64p, H.u64p, C.c_ulong]
     rng = np.random.default_rng(11)
     for seed in (5, 6):
         p0, p1 = _dup_palettes(seed)
@@ -224,22 +206,6 @@ def _entry_plane(rng, W, Hh, p0, p1):
     return ent
 
 
-def _bind_assemble(L):
-    L.CreateAGMV.restype = vp
-    L.CreateAGMV.argtypes = [C.c_ulong] * 4
-    L.DestroyAGMV.argtypes = [vp]
-    L.AGMV_SetOPT.argtypes = [vp, C.c_int]
-    L.AGMV_SetICP0.argtypes = [vp, H.u64p]
-    L.AGMV_SetICP1.argtypes = [vp, H.u64p]
-    for f in ("AGMV_AssembleIFrameBitstream", "AGMV_AssemblePFrameBitstream"):
-        getattr(L, f).restype = None
-        getattr(L, f).argtypes = [vp, C.POINTER(Entry)]
-    L.AGMV_CompareIFrameBlock.restype = C.c_ubyte
-    L.AGMV_CompareIFrameBlock.argtypes = [vp, C.c_ulong, C.c_ulong, C.c_ulong, C.POINTER(Entry)]
-    L.AGMV_ComparePFrameBlock.restype = C.c_ubyte
-    L.AGMV_ComparePFrameBlock.argtypes = [vp, C.c_ulong, C.c_ulong, C.POINTER(Entry)]
-
-
 def _entries_c(ent):
     arr = (Entry * ent.size)()
     flat = ent.reshape(-1)
@@ -255,7 +221,6 @@ def _entries_c(ent):
 def test_exported_assemble_and_compare_match_reference(opt):
     """the reference's own AGMV_Assemble{I,P}FrameBitstream / AGMV_Compare{I,P}FrameBlock on the same AGMV_ENTRY planes"""
     L, R = H.lib(), _ref_accessors()
-    _bind_assemble(L)
     R.refshim_assemble.restype = C.c_size_t
     R.refshim_assemble.argtypes = [vp, O.u16p, C.c_int, O.u8p]
     R.refshim_set_iframe_entries.argtypes = [vp, O.u16p]

@@ -32,20 +32,11 @@ PROTOS = _prototypes()
 CTX_INT = [(n, p) for r, n, p in PROTOS if r == "int" and p and p[0][0].replace(" ", "") == "agmv_hip_ctx*"]
 
 
-def _ctype(t):
-    if "*" in t:
-        return C.c_void_p
-    return {"size_t": C.c_size_t, "uint64_t": C.c_uint64, "uint32_t": C.c_uint32, "int": C.c_int,
-            "unsigned long long": C.c_ulonglong}[t.replace("const ", "")]
-
-
 @pytest.fixture(scope="module")
 def lib():
-    from libagmv_amd import hip
+    from libagmv_amd import abi, hip
     hip.load_library()                                           # builds nothing, raises when the library is missing
-    L = C.CDLL(hip.lib_path())                                   # a handle of its own: the argument types come from the header
-    L.agmv_hip_last_error.restype = C.c_char_p
-    return L
+    return abi.bind(C.CDLL(hip.lib_path()), abi.HIP)             # a handle of its own
 
 
 def test_the_header_parses():
@@ -60,8 +51,6 @@ def test_the_header_parses():
 @pytest.mark.parametrize("name,params", CTX_INT, ids=[n for n, _ in CTX_INT])
 def test_null_context_is_refused(lib, name, params):
     f = getattr(lib, name)
-    f.restype = C.c_int
-    f.argtypes = [_ctype(t) for t, _ in params]
     bufs = [C.create_string_buffer(4096) for _ in params]
     args = [None]
     for (t, pname), b in zip(params[1:], bufs):

@@ -17,10 +17,7 @@ files are recorded, not written next to this library's: its drivers read memory 
 does not clear, behind the longest frame so far; the recorder zeroes it), and run live beside this test on another machine they
 wrote other bytes than on the machine that built them.  LOW quality: its palette build sorts the whole histogram.  Needs an MI355X."""
 import functools
-import json
 import os
-import subprocess
-import sys
 import tempfile
 import textwrap
 
@@ -28,6 +25,7 @@ import numpy as np
 import pytest
 
 import audio_cases as A
+import children as K
 import dither_cases as D
 import hostlib as H
 
@@ -51,9 +49,6 @@ DRIVE = textwrap.dedent("""
 
     def drive(L, name, schedule, opt, comp, pcm, rate):
         A.bind(L)
-        sig = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ubyte] + [C.c_ulong] * 5 + [C.c_int] * 3
-        L.AGMV_EncodeAGMV.restype = L.AGMV_EncodeFullAGMV.restype = None
-        L.AGMV_EncodeAGMV.argtypes = L.AGMV_EncodeFullAGMV.argtypes = sig
         a = L.CreateAGMV(job["T"], job["W"], job["H"], 24)
         t = A.Track(a)
         t.atsample(None); t.satsample(None)
@@ -158,19 +153,14 @@ def files():
     H.lib()
     frames = clip()
     long_, short, pcm8, x = tracks()
-    tests = os.path.dirname(os.path.abspath(__file__))
-    job = {"T": T, "W": W, "H": HH, "cases": CASES, "long_rate": LONG[1], "short_rate": SHORT[1], "root": H.ROOT, "tests": tests,
-           "fox": A.FOXLOGO, "splash": A.SPLASH}
+    job = {"T": T, "W": W, "H": HH, "cases": CASES, "long_rate": LONG[1], "short_rate": SHORT[1], "fox": A.FOXLOGO, "splash": A.SPLASH}
     with tempfile.TemporaryDirectory() as d:
         os.mkdir(os.path.join(d, "fr"))
         for t in range(1, T + 1):
             H.write_bmp(os.path.join(d, "fr", "f%d.bmp" % t), frames[t - 1])
         for name, a in (("frames", frames), ("long", long_), ("short", short), ("pcm8", pcm8), ("float", x)):
             np.save(os.path.join(d, name + ".npy"), a)
-        env = {k: v for k, v in os.environ.items() if k not in ("AGMV_DITHER", "AGMV_PALETTE_REFINE", "AGMV_TRACE")}
-        r = subprocess.run([sys.executable, "-c", OURS_CHILD, json.dumps(job)], cwd=d, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-        assert r.returncode == 0, r.stderr.decode()[-2000:]
-        res = json.loads(r.stdout.decode().strip().splitlines()[-1])
+        res = K.run_child(d, OURS_CHILD, job, {"AGMV_DITHER": None, "AGMV_PALETTE_REFINE": None, "AGMV_TRACE": None}, prelude="")
         data = {f: open(os.path.join(d, f), "rb").read() for f in os.listdir(d) if f.endswith(".agmv")}
         data.update({f: open(os.path.join(GOLDEN, f), "rb").read() for f in os.listdir(GOLDEN) if f.endswith(".agmv")})
         dec = {f[4:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d) if f.startswith("dec_")}

@@ -10,11 +10,10 @@ for the whole golden clip; they are recorded, not asserted.  Needs an MI355X."""
 import functools
 import json
 import os
-import subprocess
-import sys
 import tempfile
 import textwrap
 
+import children as K
 import numpy as np
 import pytest
 
@@ -37,11 +36,6 @@ SMALL_CHILD = textwrap.dedent("""
     import libagmv_amd
     from libagmv_amd import seq
     L = seq.load_library()
-    ul = C.c_ulong
-    L.CreateAGMV.restype = C.c_void_p
-    L.CreateAGMV.argtypes = [ul] * 4
-    L.AGMV_EncodeFullAGMV.restype = None
-    L.AGMV_EncodeFullAGMV.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ubyte] + [ul] * 5 + [C.c_int] * 3
     T, W, Hh, quality = job["T"], job["W"], job["H"], job["quality"]
     packed = torch.from_numpy(np.load("frames.npy").view(np.int32)).cuda()
 
@@ -117,10 +111,7 @@ def host_lib():
 
 def run_child(cwd, script, job, env_extra=None):
     host_lib()
-    env = {k: v for k, v in os.environ.items() if k not in ("AGMV_DITHER", "AGMV_PALETTE_REFINE", "AGMV_TRACE")}
-    env.update(env_extra or {})
-    r = subprocess.run([sys.executable, "-c", script, json.dumps(dict(job, root=H.ROOT, tests=os.path.dirname(os.path.abspath(__file__))))],
-                       cwd=str(cwd), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    r = K.start_child(cwd, script, job, dict({"AGMV_DITHER": None, "AGMV_PALETTE_REFINE": None, "AGMV_TRACE": None}, **(env_extra or {})), prelude="")
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     return json.loads(r.stdout.decode().strip().splitlines()[-1]), r.stderr.decode()
 

@@ -6,34 +6,14 @@ like the reference's, free the caller's AGMV object.  Needs an MI355X."""
 import hashlib
 import os
 import subprocess
-import sys
-import textwrap
 
 import pytest
 
+import children as K
 import hostlib as H
 import synth as S
 
 pytestmark = pytest.mark.gpu
-
-DRIVER = textwrap.dedent("""
-    import ctypes as C, sys
-    L = C.CDLL(%r)
-    L.CreateAGMV.restype = C.c_void_p; L.CreateAGMV.argtypes = [C.c_ulong] * 4
-    sig = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ubyte] + [C.c_ulong] * 5 + [C.c_int] * 3
-    L.AGMV_EncodeAGMV.argtypes = sig; L.AGMV_EncodeFullAGMV.argtypes = sig
-    L.AGMV_EncodeVideo.argtypes = sig[1:]
-    L.AGMV_DecodeAGMV.argtypes = [C.c_char_p, C.c_ubyte, C.c_int]
-    L.AGMV_SetBatchFrames.argtypes = [C.c_uint]
-    drv, T, W, H, opt, q, comp, batch = sys.argv[1], *[int(x) for x in sys.argv[2:]]
-    L.AGMV_SetBatchFrames(batch)
-    if drv == "video":
-        L.AGMV_EncodeVideo(b"out.agmv", b"fr", b"f", 1, 1, T, W, H, 24, opt, q, comp)
-    else:
-        a = L.CreateAGMV(T, W, H, 24)
-        (L.AGMV_EncodeAGMV if drv == "agmv" else L.AGMV_EncodeFullAGMV)(a, b"out.agmv", b"fr", b"f", 1, 1, T, W, H, 24, opt, q, comp)
-    sys.exit(L.AGMV_DecodeAGMV(b"out.agmv", 1, 1))
-""")
 
 CASES = ["agmv_opt3_low_lzss_160x128", "agmv_opt1_mid_lzss_160x128", "agmv_opt2_low_lz77_160x128", "full_opt3_high_lzss_160x128",
          "agmv_gba1_low_lzss_320x240", "agmv_nds_low_lzss_320x240", "video_opt3_low_lzss_160x128",
@@ -61,9 +41,7 @@ def test_file_roundtrip_matches_reference(golden, tmp_path, name):
     for t in range(1, T + 1):
         H.write_bmp(str(tmp_path / "fr" / ("f%d.bmp" % t)), S.synth_frame(W, Hh, t))
     batch = 8 if T < 100 else 64          # small batches: several GPU batches + decoder state hand-over per file
-    r = subprocess.run([sys.executable, "-c", DRIVER % H.SO, g["driver"], str(T), str(W), str(Hh), str(g["opt"]),
-                        str(g["quality"]), str(g["compression"]), str(batch)], cwd=str(tmp_path),
-                       stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=1200)
+    r = K.drive_child(tmp_path, g["driver"], T, W, Hh, g["opt"], g["quality"], g["compression"], batch, decode=True)
     # (the reference itself crashes in DestroyAGMV after exporting the last frame when driven this way -- its decoder
     #  frees the uninitialised agmv->iframe_entries, src/agmv_decode.c:532,644 -- so golden decode_rc is not compared)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
@@ -91,10 +69,8 @@ def test_two_devices_write_the_same_file(golden, tmp_path):
     (tmp_path / "fr").mkdir()
     for t in range(1, T + 1):
         H.write_bmp(str(tmp_path / "fr" / ("f%d.bmp" % t)), S.synth_frame(W, Hh, t))
-    env = dict(os.environ, AGMV_DEVICES="2", AGMV_DEVICES_OVERSUBSCRIBE="1", AGMV_TRACE="1")
-    r = subprocess.run([sys.executable, "-c", DRIVER % H.SO, g["driver"], str(T), str(W), str(Hh), str(g["opt"]),
-                        str(g["quality"]), str(g["compression"]), "8"], cwd=str(tmp_path), env=env,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=1200)
+    env = dict(AGMV_DEVICES="2", AGMV_DEVICES_OVERSUBSCRIBE="1", AGMV_TRACE="1")
+    r = K.drive_child(tmp_path, g["driver"], T, W, Hh, g["opt"], g["quality"], g["compression"], 8, decode=True, env=env)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     assert b"4 GPU workers" in r.stderr, r.stderr.decode()[-2000:]      # two worker pairs were really opened
     data = open(tmp_path / "out.agmv", "rb").read()
@@ -115,8 +91,7 @@ def test_foxlogo_212_through_encodevideo(golden_dir, tmp_path):
     (tmp_path / "fr").mkdir()
     for k in range(212):
         H.write_bmp(str(tmp_path / "fr" / ("f%d.bmp" % (k + 1))), frames[k])
-    r = subprocess.run([sys.executable, "-c", DRIVER % H.SO, "video", "212", "320", "240", "3", "3", "1", "64"], cwd=str(tmp_path),
-                       stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=1200)
+    r = K.drive_child(tmp_path, "video", 212, 320, 240, 3, 3, 1, 64, decode=True)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     data = open(tmp_path / "out.agmv", "rb").read()
     assert len(data) == g["file_len"] and int.from_bytes(data[4:8], "little") == g["frames"] == 156
@@ -136,8 +111,7 @@ def test_foxlogo_through_the_readme_flow(golden_fox, foxlogo, tmp_path):
     (tmp_path / "fr").mkdir()
     for k, f in enumerate(foxlogo["frames"]):
         H.write_bmp(str(tmp_path / "fr" / ("f%d.bmp" % (k + 1))), f)
-    r = subprocess.run([sys.executable, "-c", DRIVER % H.SO, "agmv", "24", "320", "240", str(g["opt"]), str(g["quality"]),
-                        str(g["compression"]), "8"], cwd=str(tmp_path), stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=1200)
+    r = K.drive_child(tmp_path, "agmv", 24, 320, 240, g["opt"], g["quality"], g["compression"], 8, decode=True)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     data = open(tmp_path / "out.agmv", "rb").read()
     assert (int.from_bytes(data[4:8], "little"), int.from_bytes(data[18:22], "little"), len(data)) == (g["frames"], g["fps_field"], g["file_len"])
@@ -153,10 +127,7 @@ def test_decode_sample_with_audio_chunks_via_c_api(golden_fox, golden_dir, tmp_p
     """AGMV_DecodeAGMV on a stream with AGAC chunks between the frames (audio itself is out of scope: the chunks are skipped)"""
     import numpy as np
     g = golden_fox[which]
-    code = "import ctypes as C,sys; L=C.CDLL(%r); L.AGMV_DecodeAGMV.argtypes=[C.c_char_p,C.c_ubyte,C.c_int]; sys.exit(L.AGMV_DecodeAGMV(%r,1,1))" % (
-        H.SO, os.path.join(golden_dir, which + ".agmv").encode())
-    H.lib()
-    r = subprocess.run([sys.executable, "-c", code], cwd=str(tmp_path), stderr=subprocess.PIPE, timeout=300)
+    r = K.decode_child(tmp_path, os.path.join(golden_dir, which + ".agmv"))
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     for k in (1, 2, 40, 64, g["n"]):
         raw = open(tmp_path / ("quick_export_%d.bmp" % k), "rb").read()
@@ -169,10 +140,7 @@ def test_decode_reference_sample_file_via_c_api(golden, golden_dir, tmp_path):
     """config 1 through the drop-in API: AGMV_DecodeAGMV(agmv_splash.agmv) -> 119 BMPs whose pixels are the golden ones"""
     import numpy as np
     g = golden["agmv_splash"]
-    code = "import ctypes as C,sys; L=C.CDLL(%r); L.AGMV_DecodeAGMV.argtypes=[C.c_char_p,C.c_ubyte,C.c_int]; sys.exit(L.AGMV_DecodeAGMV(%r,1,1))" % (
-        H.SO, os.path.join(golden_dir, "agmv_splash.agmv").encode())
-    H.lib()
-    r = subprocess.run([sys.executable, "-c", code], cwd=str(tmp_path), stderr=subprocess.PIPE, timeout=300)
+    r = K.decode_child(tmp_path, os.path.join(golden_dir, "agmv_splash.agmv"))
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     for k in (1, 2, 37, 60, 119):
         raw = open(tmp_path / ("quick_export_%d.bmp" % k), "rb").read()
@@ -206,10 +174,7 @@ def test_decode_batches_cut_where_a_chunk_is_not_where_it_was_assumed(golden_dir
     for batch in (1, 8):
         d = tmp_path / ("b%d" % batch)
         d.mkdir()
-        code = ("import ctypes as C,sys; L=C.CDLL(%r); L.AGMV_DecodeAGMV.argtypes=[C.c_char_p,C.c_ubyte,C.c_int]; "
-                "L.AGMV_SetBatchFrames.argtypes=[C.c_uint]; L.AGMV_SetBatchFrames(%d); sys.exit(L.AGMV_DecodeAGMV(%r,1,1))"
-                % (H.SO, batch, str(tmp_path / "patched.agmv").encode()))
-        r = subprocess.run([sys.executable, "-c", code], cwd=str(d), stderr=subprocess.PIPE, timeout=300)
+        r = K.decode_child(d, tmp_path / "patched.agmv", batch)
         assert r.returncode == 0, r.stderr.decode()[-2000:]
         h = hashlib.sha256()
         names = sorted(f for f in os.listdir(d) if f.startswith("quick_export_"))
@@ -247,18 +212,6 @@ def test_per_frame_file_api_matches_reference(golden, tmp_path):
     libc.fopen.restype = C.c_void_p
     libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
     libc.fclose.argtypes = [C.c_void_p]
-    vp = C.c_void_p
-    L.AGMV_SetICP0.argtypes = [vp, H.u64p]
-    L.AGMV_SetICP1.argtypes = [vp, H.u64p]
-    L.AGMV_SetOPT.argtypes = [vp, C.c_int]
-    L.AGMV_SetCompression.argtypes = [vp, C.c_int]
-    L.AGMV_EncodeHeader.argtypes = [vp, vp]
-    L.AGMV_EncodeFrame.argtypes = [vp, vp, H.u64p]
-    L.AGMV_DecodeHeader.argtypes = [vp, vp]
-    L.AGMV_DecodeHeader.restype = C.c_int
-    L.AGMV_FindNextFrameChunk.argtypes = [vp]
-    L.AGMV_DecodeFrameChunk.argtypes = [vp, vp]
-    L.AGMV_DecodeFrameChunk.restype = C.c_int
     for key, g in golden["per_frame_api"].items():
         opt, comp = int(key[3]), int(key[-1])
         W, Hh, T = g["W"], g["H"], g["T"]

@@ -4,32 +4,16 @@ and sequences over more than one device are unaffected by the knob."""
 import hashlib
 import json
 import os
-import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
 
+import children as K
 import hostlib as H
 import oracles as O
 import synth as S
 
 pytestmark = pytest.mark.gpu
-
-DRIVER = textwrap.dedent("""
-    import ctypes as C, sys
-    L = C.CDLL(%r)
-    L.CreateAGMV.restype = C.c_void_p; L.CreateAGMV.argtypes = [C.c_ulong] * 4
-    L.AGMV_EncodeAGMV.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ubyte] + [C.c_ulong] * 5 + [C.c_int] * 3
-    T, W, H, opt, q, comp, batch = [int(x) for x in sys.argv[1:]]
-    if hasattr(L, "AGMV_SetBatchFrames"):                            # (the compiled reference has no batches)
-        L.AGMV_SetBatchFrames.argtypes = [C.c_uint]
-        L.AGMV_SetBatchFrames(batch)
-    a = L.CreateAGMV(T, W, H, 24)
-    L.AGMV_EncodeAGMV(a, b"out.agmv", b"fr", b"f", 1, 1, T, W, H, 24, opt, q, comp)
-""")
-
 
 def encode(tmp_path, sub, so, T, W, Hh, opt, q, comp, batch, frame=S.synth_frame, **env):
     """the clip frame(W, Hh, t), t = 1..T, through the drop-in API in a child process: (bytes of the .agmv file, stderr)"""
@@ -41,10 +25,8 @@ def encode(tmp_path, sub, so, T, W, Hh, opt, q, comp, batch, frame=S.synth_frame
     d = tmp_path / sub
     d.mkdir()
     os.symlink(str(fr), str(d / "fr"))
-    e = {k: v for k, v in os.environ.items() if k not in ("AGMV_LZ77_DEVICE", "AGMV_LZ_DEVICE", "AGMV_DEVICES", "AGMV_DEVICES_OVERSUBSCRIBE")}
-    e.update(env, AGMV_TRACE="1")
-    r = subprocess.run([sys.executable, "-c", DRIVER % so, str(T), str(W), str(Hh), str(opt), str(q), str(comp), str(batch)],
-                       cwd=str(d), env=e, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=1200)
+    e = dict(dict.fromkeys(("AGMV_LZ77_DEVICE", "AGMV_LZ_DEVICE", "AGMV_DEVICES", "AGMV_DEVICES_OVERSUBSCRIBE")), **env, AGMV_TRACE="1")
+    r = K.drive_child(d, "agmv", T, W, Hh, opt, q, comp, batch, so=None if so == H.SO else so, env=e)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     return open(d / "out.agmv", "rb").read(), r.stderr
 

@@ -4,45 +4,20 @@ it, and the reference's where golden hashes exist: LZSS and LZ77 files written b
 decode runs in a child process (the drivers write into the CWD)."""
 import hashlib
 import os
-import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
 
+import children as K
 import hostlib as H
 import synth as S
 
 pytestmark = pytest.mark.gpu
 
-ENCODE = textwrap.dedent("""
-    import ctypes as C, sys
-    L = C.CDLL(%r)
-    L.CreateAGMV.restype = C.c_void_p; L.CreateAGMV.argtypes = [C.c_ulong] * 4
-    sig = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ubyte] + [C.c_ulong] * 5 + [C.c_int] * 3
-    L.AGMV_EncodeAGMV.argtypes = sig; L.AGMV_EncodeFullAGMV.argtypes = sig
-    drv, T, W, H, opt, q, comp = sys.argv[1], *[int(x) for x in sys.argv[2:]]
-    a = L.CreateAGMV(T, W, H, 24)
-    (L.AGMV_EncodeAGMV if drv == "agmv" else L.AGMV_EncodeFullAGMV)(a, b"out.agmv", b"fr", b"f", 1, 1, T, W, H, 24, opt, q, comp)
-""")
-
-DECODE = ("import ctypes as C,sys; L=C.CDLL(%r); L.AGMV_DecodeAGMV.argtypes=[C.c_char_p,C.c_ubyte,C.c_int]; "
-          "L.AGMV_SetBatchFrames.argtypes=[C.c_uint]; L.AGMV_SetBatchFrames(%d); sys.exit(L.AGMV_DecodeAGMV(%r,1,1))")
-
-
 def decode(path, where, batch, device, trace=False):
     """AGMV_DecodeAGMV in a child; returns (number of BMPs, sha256 over their names and bytes, stderr)"""
     os.makedirs(where, exist_ok=True)
-    env = dict(os.environ)
-    env.pop("AGMV_LZ_DECODE_DEVICE", None)
-    env.pop("AGMV_TRACE", None)
-    if device:
-        env["AGMV_LZ_DECODE_DEVICE"] = "1"
-    if trace:
-        env["AGMV_TRACE"] = "1"
-    r = subprocess.run([sys.executable, "-c", DECODE % (H.SO, batch, str(path).encode())], cwd=str(where), env=env,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=600)
+    r = K.decode_child(where, path, batch, {"AGMV_LZ_DECODE_DEVICE": "1" if device else None, "AGMV_TRACE": "1" if trace else None})
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     names = sorted((f for f in os.listdir(where) if f.startswith("quick_export_")), key=lambda f: int(f[13:-4]))
     h = hashlib.sha256()
@@ -63,8 +38,7 @@ def encode(tmp_path, drv, T, W, Hh, opt, q, comp):
     (tmp_path / "fr").mkdir()
     for t in range(1, T + 1):
         H.write_bmp(str(tmp_path / "fr" / ("f%d.bmp" % t)), S.synth_frame(W, Hh, t))
-    r = subprocess.run([sys.executable, "-c", ENCODE % H.SO, drv, str(T), str(W), str(Hh), str(opt), str(q), str(comp)],
-                       cwd=str(tmp_path), stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=600)
+    r = K.drive_child(tmp_path, drv, T, W, Hh, opt, q, comp, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     return tmp_path / "out.agmv"
 

@@ -8,13 +8,11 @@ References: the brute-force restatement (orc_lzss_compress) for frames up to a f
 against the brute force by the CPU suite) for larger ones, and the same frames through the GPU one call each.  Every check
 compares csize and every payload byte."""
 import hashlib
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import children as K
 import hostlib as H
 import lzss_cases as Z
 from lzss_cases import gpu_batch, orc
@@ -537,7 +535,6 @@ def test_pipeline_with_multi_chunk_batches(tmp_path):
     """28 source frames of 1080p noise through AGMV_EncodeAGMV (OPT_III, LZSS) in batches of 8: NORMAL-heavy frames of > 3 MB
     pre-LZ, so every batch of 8 is more than 2^24 positions.  LZSS on the GPU (one device, and two contexts on one card)
     must write the file the host stage writes."""
-    import test_gpu_files as F
     H.lib()
     T, W, Hh = 28, 1920, 1080
     rng = np.random.default_rng(10)
@@ -547,13 +544,11 @@ def test_pipeline_with_multi_chunk_batches(tmp_path):
     files = {}
     for name, extra in [("host", {}), ("device", {"AGMV_LZ_DEVICE": "1"}),
                         ("device2", {"AGMV_LZ_DEVICE": "1", "AGMV_DEVICES": "2", "AGMV_DEVICES_OVERSUBSCRIBE": "1"})]:
-        env = {k: v for k, v in os.environ.items() if k not in ("AGMV_LZ_DEVICE", "AGMV_DEVICES", "AGMV_DEVICES_OVERSUBSCRIBE")}
-        env.update(AGMV_TRACE="1", **extra)
+        env = dict(dict.fromkeys(("AGMV_LZ_DEVICE", "AGMV_DEVICES", "AGMV_DEVICES_OVERSUBSCRIBE")), AGMV_TRACE="1", **extra)
         d = tmp_path / name
         d.mkdir()
         (d / "fr").symlink_to(tmp_path / "fr")
-        r = subprocess.run([sys.executable, "-c", F.DRIVER % H.SO, "agmv", str(T), str(W), str(Hh), "3", "3", "1", "8"],
-                           cwd=str(d), env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=1200)
+        r = K.drive_child(d, "agmv", T, W, Hh, 3, 3, 1, 8, decode=True, env=env)
         assert r.returncode == 0, r.stderr.decode()[-2000:]
         assert (b"LZ (host)" if name == "host" else b"LZ (device)") in r.stderr, r.stderr.decode()[-2000:]
         if name == "device2":

@@ -1,12 +1,10 @@
 """File level with AGMV_LZ_DEVICE=1 (agmv_pipeline.c: the LZSS stage on the GPU workers): every file golden of
 tests/test_gpu_files.py must come out byte-identical, on one device and on two; LZ77 files are unaffected by the knob."""
 import hashlib
-import os
-import subprocess
-import sys
 
 import pytest
 
+import children as K
 import hostlib as H
 import synth as S
 import test_gpu_files as F
@@ -38,10 +36,8 @@ def test_knob_takes_the_device_path_for_lzss_only(golden, tmp_path, name):
     (tmp_path / "fr").mkdir()
     for t in range(1, T + 1):
         H.write_bmp(str(tmp_path / "fr" / ("f%d.bmp" % t)), S.synth_frame(W, Hh, t))
-    env = dict(os.environ, AGMV_LZ_DEVICE="1", AGMV_TRACE="1")
-    r = subprocess.run([sys.executable, "-c", F.DRIVER % H.SO, g["driver"], str(T), str(W), str(Hh), str(g["opt"]),
-                        str(g["quality"]), str(g["compression"]), "8"], cwd=str(tmp_path), env=env,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=1200)
+    r = K.drive_child(tmp_path, g["driver"], T, W, Hh, g["opt"], g["quality"], g["compression"], 8, decode=True,
+                      env=dict(AGMV_LZ_DEVICE="1", AGMV_TRACE="1"))
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lz77 = g["compression"] != 1
     assert (b"LZ (host)" if lz77 else b"LZ (device)") in r.stderr, r.stderr.decode()[-2000:]

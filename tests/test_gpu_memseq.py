@@ -10,14 +10,13 @@ import hashlib
 import json
 import os
 import struct
-import subprocess
-import sys
 import tempfile
 import textwrap
 
 import numpy as np
 import pytest
 
+import children as K
 import hostlib as H
 import memseq_cases as MC
 import synth as S
@@ -25,37 +24,11 @@ import synth as S
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-HIP_SO = os.path.join(H.ROOT, "libagmv_amd", "libagmv_hip.so")
 SCHEDULE = {"full": 1, "agmv": 2, "video": 3}
 
-# one job per child, as JSON in argv[1]; the answer is one JSON line on stdout
 CHILD = textwrap.dedent("""
-    import ctypes as C, json, sys
-    import numpy as np
-    job = json.loads(sys.argv[1])
-    L, G = C.CDLL(job["so"]), C.CDLL(job["hip_so"])
-    vp, ul = C.c_void_p, C.c_ulong
-    class INFO(C.Structure):
-        _fields_ = [("width", ul), ("height", ul), ("number_of_frames", ul), ("version", C.c_ubyte), ("total_audio_duration", ul),
-                    ("sample_rate", ul), ("audio_size", ul), ("number_of_channels", C.c_ushort), ("bits_per_sample", C.c_ushort)]
-    G.agmv_hip_malloc.restype = vp; G.agmv_hip_malloc.argtypes = [C.c_size_t]
-    G.agmv_hip_free.argtypes = [vp]
-    G.agmv_hip_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]; G.agmv_hip_memcpy_d2h.argtypes = [vp, vp, C.c_size_t]
-    G.agmv_hip_memset.argtypes = [vp, C.c_int, C.c_size_t]
-    L.AGMV_EncodeFramesDev.restype = C.c_int
-    L.AGMV_EncodeFramesDev.argtypes = [C.c_char_p, vp] + [ul] * 4 + [C.c_int] * 4
-    L.AGMV_DecodeFramesDev.restype = C.c_int
-    L.AGMV_DecodeFramesDev.argtypes = [C.c_char_p, vp, ul, C.POINTER(INFO)]
-    L.AGMV_EncodeVideo.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_ubyte] + [ul] * 5 + [C.c_int] * 3
-    L.AGMV_DecodeAGMV.argtypes = [C.c_char_p, C.c_ubyte, C.c_int]
-    L.AGMV_SetBatchFrames.argtypes = [C.c_uint]
     L.AGMV_SetBatchFrames(job["batch"])
     res = {}
-
-    def upload(fr):
-        d = G.agmv_hip_malloc(fr.nbytes)
-        assert d and G.agmv_hip_memcpy_h2d(d, fr.ctypes.data, fr.nbytes) == 0
-        return d
 
     if "enc" in job:
         e = job["enc"]
@@ -63,7 +36,7 @@ CHILD = textwrap.dedent("""
         n, h, w = fr.shape
         d = upload(fr)
         res["enc_rc"] = L.AGMV_EncodeFramesDev(b"out.agmv", d, n, w, h, 24, e["opt"], e["quality"], e["compression"], e["schedule"])
-        G.agmv_hip_free(d)
+        free(d)
     if "bmp_video" in job:                 # the existing BMP driver over fr/f<t>.bmp of the same frames
         e = job["bmp_video"]
         L.AGMV_EncodeVideo(b"bmp.agmv", b"fr", b"f", 1, 1, e["T"], e["W"], e["H"], 24, e["opt"], e["quality"], e["compression"])
@@ -71,7 +44,7 @@ CHILD = textwrap.dedent("""
         fr = np.zeros((8, 16, 16), np.uint32)
         d = upload(fr)
         res["bad_rc"] = [L.AGMV_EncodeFramesDev(a[0].encode() if a[0] else None, None if a[1] else d, *a[2:5], 24, *a[5:]) for a in job["bad_args"]]
-        G.agmv_hip_free(d)
+        free(d)
     if "dec" in job:
         e = job["dec"]
         path = e["path"].encode()
@@ -79,13 +52,10 @@ CHILD = textwrap.dedent("""
         res["info_rc"] = L.AGMV_DecodeFramesDev(path, None, 0, C.byref(info))
         n, w, h = info.number_of_frames, info.width, info.height
         res["info"] = [n, w, h, info.version]
-        buf = np.empty((n, h, w), np.uint32)
-        d = G.agmv_hip_malloc(buf.nbytes)
-        assert d and G.agmv_hip_memset(d, 0xA5, buf.nbytes) == 0        # what a frame that is not decoded keeps
+        d = poisoned(4 * n * h * w)                                     # what a frame that is not decoded keeps
         res["dec_rc"] = L.AGMV_DecodeFramesDev(path, d, e.get("cap", n), None)
-        assert G.agmv_hip_memcpy_d2h(buf.ctypes.data, d, buf.nbytes) == 0
-        G.agmv_hip_free(d)
-        np.save("dec.npy", buf)
+        np.save("dec.npy", download(d, 4 * n * h * w).view(np.uint32).reshape(n, h, w))
+        free(d)
         if e.get("bmps"):
             res["bmp_rc"] = L.AGMV_DecodeAGMV(path, 1, 1)
     print(json.dumps(res))
@@ -93,12 +63,7 @@ CHILD = textwrap.dedent("""
 
 
 def run_child(cwd, job, env=None):
-    H.lib()
-    job = dict(job, so=H.SO, hip_so=HIP_SO)
-    r = subprocess.run([sys.executable, "-c", CHILD, json.dumps(job)], cwd=str(cwd), env=dict(os.environ, **(env or {})),
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    return json.loads(r.stdout.decode().strip().splitlines()[-1])
+    return K.run_child(cwd, CHILD, job, env)
 
 
 @functools.lru_cache(maxsize=None)

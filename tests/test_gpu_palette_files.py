@@ -6,13 +6,11 @@ refinement, and with the refinement off the file must be the one AGMV_EncodeFram
 through the BMP driver and through the rgb24 and nv12 device sources must give one and the same refined file.  The drivers keep
 process-wide state, so each group runs in a child process, once.  Needs an MI355X."""
 import functools
-import json
 import os
-import subprocess
-import sys
 import tempfile
 import textwrap
 
+import children as K
 import numpy as np
 import pytest
 
@@ -68,11 +66,6 @@ SMALL_CHILD = textwrap.dedent("""
     import libagmv_amd
     from libagmv_amd import seq
     L = seq.load_library()
-    ul = C.c_ulong
-    L.CreateAGMV.restype = C.c_void_p
-    L.CreateAGMV.argtypes = [ul] * 4
-    L.AGMV_EncodeFullAGMV.restype = None
-    L.AGMV_EncodeFullAGMV.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ubyte] + [ul] * 5 + [C.c_int] * 3
     T, W, Hh, opt, quality = job["T"], job["W"], job["H"], job["opt"], job["quality"]
 
     def bmp(path, rounds):
@@ -95,12 +88,7 @@ SMALL_CHILD = textwrap.dedent("""
 
 
 def run_child(cwd, script, job):
-    H.lib()
-    env = {k: v for k, v in os.environ.items() if k not in ("AGMV_PALETTE_REFINE", "AGMV_TRACE")}
-    r = subprocess.run([sys.executable, "-c", script, json.dumps(dict(job, root=H.ROOT))], cwd=str(cwd), env=env, stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=600)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    return json.loads(r.stdout.decode().strip().splitlines()[-1])
+    return K.run_child(cwd, script, job, {"AGMV_PALETTE_REFINE": None, "AGMV_TRACE": None}, prelude="")
 
 
 @functools.lru_cache(maxsize=None)

@@ -11,14 +11,13 @@ import functools
 import hashlib
 import json
 import os
-import subprocess
-import sys
 import tempfile
 import textwrap
 
 import numpy as np
 import pytest
 
+import children as K
 import hostlib as H
 import memseq_cases as MC
 import pixfmt_cases as P
@@ -28,40 +27,13 @@ pytestmark = pytest.mark.gpu
 
 TESTS = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(TESTS, "golden")
-HIP_SO = os.path.join(H.ROOT, "libagmv_amd", "libagmv_hip.so")
 SCHEDULE = {"full": 1, "agmv": 2, "video": 3}
 FIRST = "agmv_opt3_low_lzss_160x128"
 
-# one job per child, as JSON in argv[1]; the answer is one JSON line on stdout
 CHILD = textwrap.dedent("""
-    import ctypes as C, json, sys
-    import numpy as np
-    job = json.loads(sys.argv[1])
-    sys.path.insert(0, job["tests"])
     import pixfmt_cases as P
-    L, G = C.CDLL(job["so"]), C.CDLL(job["hip_so"])
-    vp, ul = C.c_void_p, C.c_ulong
-    class INFO(C.Structure):
-        _fields_ = [("width", ul), ("height", ul), ("number_of_frames", ul), ("version", C.c_ubyte), ("total_audio_duration", ul),
-                    ("sample_rate", ul), ("audio_size", ul), ("number_of_channels", C.c_ushort), ("bits_per_sample", C.c_ushort)]
-    G.agmv_hip_malloc.restype = vp; G.agmv_hip_malloc.argtypes = [C.c_size_t]
-    G.agmv_hip_free.argtypes = [vp]
-    G.agmv_hip_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]; G.agmv_hip_memcpy_d2h.argtypes = [vp, vp, C.c_size_t]
-    G.agmv_hip_memset.argtypes = [vp, C.c_int, C.c_size_t]
-    L.AGMV_EncodeFramesFmtDev.restype = C.c_int
-    L.AGMV_EncodeFramesFmtDev.argtypes = [C.c_char_p, vp, C.c_int] + [ul] * 4 + [C.c_int] * 4
-    L.AGMV_DecodeFramesFmtDev.restype = C.c_int
-    L.AGMV_DecodeFramesFmtDev.argtypes = [C.c_char_p, vp, C.c_int, ul, C.POINTER(INFO)]
-    L.AGMV_DecodeFramesDev.restype = C.c_int
-    L.AGMV_DecodeFramesDev.argtypes = [C.c_char_p, vp, ul, C.POINTER(INFO)]
-    L.AGMV_SetBatchFrames.argtypes = [C.c_uint]
     L.AGMV_SetBatchFrames(job["batch"])
     res = {"enc_rc": [], "dec": [], "bad_rc": []}
-
-    def upload(a):
-        d = G.agmv_hip_malloc(a.nbytes)
-        assert d and G.agmv_hip_memcpy_h2d(d, a.ctypes.data, a.nbytes) == 0
-        return d
 
     for e in job.get("enc", []):
         fr = np.load("frames.npy")
@@ -70,24 +42,22 @@ CHILD = textwrap.dedent("""
         raw = np.ascontiguousarray(P.from_packed(e["fmt"], fr.reshape(n, h * w), alpha=alpha))
         d = upload(raw)
         res["enc_rc"].append(L.AGMV_EncodeFramesFmtDev(e["out"].encode(), d, e["fmt"], n, w, h, 24, e["opt"], e["quality"], e["compression"], e["schedule"]))
-        G.agmv_hip_free(d)
+        free(d)
     for a in job.get("bad", []):             # [filename, fmt, n, w, h, opt, quality, compression, schedule] on a real clip
         d = upload(np.zeros(8 * 16 * 16 * 4, np.uint8))
         res["bad_rc"].append(L.AGMV_EncodeFramesFmtDev(a[0].encode(), d, a[1], *a[2:5], 24, *a[5:]))
-        G.agmv_hip_free(d)
+        free(d)
     for e in job.get("dec", []):             # fmt 0: AGMV_DecodeFramesDev
         path = e["path"].encode()
         info = INFO()
         rc_info = L.AGMV_DecodeFramesFmtDev(path, None, e["fmt"] or 1, 0, C.byref(info))
         n, w, h = info.number_of_frames, info.width, info.height
-        buf = np.empty(n * P.frame_bytes(e["fmt"] or 1, w * h), np.uint8)
-        d = G.agmv_hip_malloc(buf.nbytes)
-        assert d and G.agmv_hip_memset(d, 0xA5, buf.nbytes) == 0        # what a frame that is not decoded keeps
+        nbytes = n * P.frame_bytes(e["fmt"] or 1, w * h)
+        d = poisoned(nbytes)                                            # what a frame that is not decoded keeps
         cap = e.get("cap", n)
         rc = L.AGMV_DecodeFramesFmtDev(path, d, e["fmt"], cap, None) if e["fmt"] else L.AGMV_DecodeFramesDev(path, d, cap, None)
-        assert G.agmv_hip_memcpy_d2h(buf.ctypes.data, d, buf.nbytes) == 0
-        G.agmv_hip_free(d)
-        np.save(e["out"], buf)
+        np.save(e["out"], download(d, nbytes))
+        free(d)
         res["dec"].append({"info_rc": rc_info, "rc": rc, "n": n, "w": w, "h": h})
     print(json.dumps(res))
 """)
@@ -118,12 +88,7 @@ SEQ_CHILD = textwrap.dedent("""
 
 
 def run_child(cwd, job, env=None, script=CHILD):
-    H.lib()
-    job = dict(job, so=H.SO, hip_so=HIP_SO, tests=TESTS, root=H.ROOT)
-    r = subprocess.run([sys.executable, "-c", script, json.dumps(job)], cwd=str(cwd), env=dict(os.environ, **(env or {})),
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    return json.loads(r.stdout.decode().strip().splitlines()[-1])
+    return K.run_child(cwd, script, job, env, prelude="" if script is SEQ_CHILD else K.PRELUDE)
 
 
 @functools.lru_cache(maxsize=None)

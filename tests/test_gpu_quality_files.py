@@ -8,16 +8,13 @@ AGMV_LZ_DECODE_DEVICE=1, for a reference in XRGB32, RGB24 and NV12; ten frames o
 multiple of 16.  One child process does all of it (the drivers keep process-wide state and read their knobs from the
 environment); the tests read its answer.  Needs an MI355X."""
 import functools
-import json
 import os
-import subprocess
-import sys
 import tempfile
 import textwrap
 
 import pytest
 
-import hostlib as H
+import children as K
 
 pytestmark = pytest.mark.gpu
 
@@ -115,14 +112,9 @@ CHILD = textwrap.dedent("""
 
 @functools.lru_cache(maxsize=None)
 def answer():
-    H.lib()
-    job = {"root": H.ROOT, "tests": TESTS, "n": N, "w": W, "h": HT}
-    env = {k: v for k, v in os.environ.items() if k not in ("AGMV_DITHER", "AGMV_PALETTE_REFINE", "AGMV_TRACE", "AGMV_LZ_DECODE_DEVICE")}
-    env["AGMV_BATCH_FRAMES"] = "8"
+    env = dict(dict.fromkeys(("AGMV_DITHER", "AGMV_PALETTE_REFINE", "AGMV_TRACE", "AGMV_LZ_DECODE_DEVICE")), AGMV_BATCH_FRAMES="8")
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([sys.executable, "-c", CHILD, json.dumps(job)], cwd=d, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-    assert r.returncode == 0, r.stderr.decode()[-3000:]
-    return json.loads(r.stdout.decode().strip().splitlines()[-1])
+        return K.run_child(d, CHILD, {"n": N, "w": W, "h": HT}, env, prelude="")
 
 
 @pytest.mark.parametrize("ref", REFS)

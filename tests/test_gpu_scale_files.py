@@ -10,14 +10,12 @@ import functools
 import hashlib
 import json
 import os
-import subprocess
-import sys
 import textwrap
 
+import children as K
 import numpy as np
 import pytest
 
-import hostlib as H
 import memseq_cases as MC
 import pixfmt_cases as P
 import scale_cases as SC
@@ -27,35 +25,13 @@ pytestmark = pytest.mark.gpu
 
 TESTS = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(TESTS, "golden")
-HIP_SO = os.path.join(H.ROOT, "libagmv_amd", "libagmv_hip.so")
 FULL, PDIFS, ADAPTIVE = 1, 2, 3
 I420_709F = Y.I420 | Y.BT709 | Y.FULL_RANGE
 FORMATS = SC.BYTE_LAYOUTS + (Y.NV12, I420_709F)
 
-# one job per child, as JSON in argv[1]; the answer is one JSON line on stdout
 CHILD = textwrap.dedent("""
-    import ctypes as C, json, sys
-    import numpy as np
-    job = json.loads(sys.argv[1])
-    L, G = C.CDLL(job["so"]), C.CDLL(job["hip_so"])
-    vp, ul = C.c_void_p, C.c_ulong
-    G.agmv_hip_malloc.restype = vp; G.agmv_hip_malloc.argtypes = [C.c_size_t]
-    G.agmv_hip_free.argtypes = [vp]
-    G.agmv_hip_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]
-    L.AGMV_EncodeFramesScaledDev.restype = C.c_int
-    L.AGMV_EncodeFramesScaledDev.argtypes = [C.c_char_p, vp, C.c_int] + [ul] * 5 + [C.c_int, ul] + [C.c_int] * 4
-    L.AGMV_EncodeFramesFmtDev.restype = C.c_int
-    L.AGMV_EncodeFramesFmtDev.argtypes = [C.c_char_p, vp, C.c_int] + [ul] * 4 + [C.c_int] * 4
-    L.AGMV_EncodeFramesDev.restype = C.c_int
-    L.AGMV_EncodeFramesDev.argtypes = [C.c_char_p, vp] + [ul] * 4 + [C.c_int] * 4
-    L.AGMV_SetBatchFrames.argtypes = [C.c_uint]
     L.AGMV_SetBatchFrames(job["batch"])
     rcs = []
-
-    def upload(a):
-        d = G.agmv_hip_malloc(a.nbytes)
-        assert d and G.agmv_hip_memcpy_h2d(d, a.ctypes.data, a.nbytes) == 0
-        return d
 
     for e in job["enc"]:
         tail = [24, e["opt"], e["quality"], e["compression"], e["schedule"]]
@@ -71,7 +47,7 @@ CHILD = textwrap.dedent("""
             n, h, w = packed.shape
             d = upload(packed)
             rcs.append(L.AGMV_EncodeFramesDev(e["out"].encode(), d, n, w, h, *tail))
-        G.agmv_hip_free(d)
+        free(d)
     print(json.dumps({"rc": rcs}))
 """)
 
@@ -106,11 +82,7 @@ SEQ_CHILD = textwrap.dedent("""
 
 
 def run_child(cwd, job, script=CHILD):
-    H.lib()
-    job = dict(job, so=H.SO, hip_so=HIP_SO, root=H.ROOT)
-    r = subprocess.run([sys.executable, "-c", script, json.dumps(job)], cwd=str(cwd), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    return json.loads(r.stdout.decode().strip().splitlines()[-1])
+    return K.run_child(cwd, script, job, prelude="" if script is SEQ_CHILD else K.PRELUDE)
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,7 +1,6 @@
 """The two per-pixel jobs of the memory sequences, through AgmvHip: agmv_hip_similarity_dev (the integer behind
 AGMV_CompareFrameSimilarity, for every adjacent pair of a clip) and agmv_hip_gather_dev (the GBA / NDS nearest scale as a
 gather).  Exact integers against numpy; the counts also against the host library's AGMV_CompareFrameSimilarity.  Needs an MI355X."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -50,8 +49,6 @@ def host_counts(frames):
     """count = ratio * npx from the host library's AGMV_CompareFrameSimilarity (8-byte pixels): exact below 2^23 pixels, where the
     float ratio is off by less than half a pixel"""
     L = H.lib()
-    L.AGMV_CompareFrameSimilarity.restype = C.c_float
-    L.AGMV_CompareFrameSimilarity.argtypes = [H.u64p, H.u64p, C.c_ulong, C.c_ulong]
     fl = [np.ascontiguousarray(f.reshape(-1)).astype(np.uint64) for f in frames]
     npx = fl[0].size
     assert npx < 1 << 23

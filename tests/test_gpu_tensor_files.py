@@ -8,16 +8,12 @@ the clamp) must give, byte for byte, the file that encode_frames writes for the 
 numpy first where a size is given (tests/upscale_cases.py); a decode without the new arguments is what it was.  The library rounds
 AGMV_BATCH_FRAMES=3 up to whole GOPs of 4, so the 8-frame clip takes two batches and the table uploaded once per call serves both.
 Child processes as in tests/test_gpu_upscale_files.py (the drivers keep process-wide state).  Needs an MI355X."""
-import json
-import os
-import subprocess
-import sys
 import textwrap
 
+import children as K
 import numpy as np
 import pytest
 
-import hostlib as H
 import memseq_cases as MC
 import tensor_cases as TC
 import upscale_cases as U
@@ -66,15 +62,8 @@ CHILD = textwrap.dedent("""
 
 def run_child(cwd, job, env=None):
     import torch  # noqa: F401  (torch's HIP runtime first, should this be the process's first use of the libraries)
-    H.lib()
-    e = dict(os.environ)
-    for k in ("AGMV_BATCH_FRAMES", "AGMV_LZ_DECODE_DEVICE", "AGMV_DITHER", "AGMV_PALETTE_REFINE"):
-        e.pop(k, None)
-    e.update(env or {})
-    r = subprocess.run([sys.executable, "-c", CHILD, json.dumps(dict(job, root=H.ROOT))], cwd=str(cwd), env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       timeout=600)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    return json.loads(r.stdout.decode().strip().splitlines()[-1])
+    return K.run_child(cwd, CHILD, job, dict(dict.fromkeys(("AGMV_BATCH_FRAMES", "AGMV_LZ_DECODE_DEVICE", "AGMV_DITHER", "AGMV_PALETTE_REFINE")), **(env or {})),
+                       prelude="")
 
 
 def model_output(t, pix, mean, std, seed):

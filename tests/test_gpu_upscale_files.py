@@ -7,12 +7,10 @@ rule; the scaled decode must deliver exactly those bytes, for the three filters 
 AGMV_BATCH_FRAMES=3 up to whole GOPs of 4, so the 8-frame clip takes two batches and the decoder's state (the last frame, the
 I-frame snapshot) has to survive in the double buffer at the file's size while the sink writes another size.  Child processes as
 in tests/test_gpu_scale_files.py (the drivers keep process-wide state).  Needs an MI355X."""
-import json
 import os
-import subprocess
-import sys
 import textwrap
 
+import children as K
 import numpy as np
 import pytest
 
@@ -66,15 +64,7 @@ CHILD = textwrap.dedent("""
 
 
 def run_child(cwd, job, env=None):
-    H.lib()
-    e = dict(os.environ)
-    for k in ("AGMV_BATCH_FRAMES", "AGMV_LZ_DECODE_DEVICE"):
-        e.pop(k, None)
-    e.update(env or {})
-    r = subprocess.run([sys.executable, "-c", CHILD, json.dumps(dict(job, root=H.ROOT))], cwd=str(cwd), env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       timeout=600)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    return json.loads(r.stdout.decode().strip().splitlines()[-1])
+    return K.run_child(cwd, CHILD, job, dict({"AGMV_BATCH_FRAMES": None, "AGMV_LZ_DECODE_DEVICE": None}, **(env or {})), prelude="")
 
 
 def dec(fmt, size, scale, yuv=None, full=False):

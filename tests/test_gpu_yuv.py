@@ -171,8 +171,6 @@ def test_every_colour_is_written_as_the_definition_says(torch, hip, flags):
 # ------------------------------------------------------------------ gather
 def source_index(sw, sh, tw, th):
     L = H.lib()
-    L.agmv_source_index.restype = C.POINTER(C.c_uint32)
-    L.agmv_source_index.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32]
     p = L.agmv_source_index(sw, sh, tw, th, tw, th)
     out = np.ctypeslib.as_array(p, (tw * th,)).copy()
     libc = C.CDLL(None)

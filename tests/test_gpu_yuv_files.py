@@ -10,14 +10,12 @@ a YUV sink must be numpy's writing of the XRGB32 decode.  Child processes as in 
 import functools
 import json
 import os
-import subprocess
-import sys
 import textwrap
 
 import numpy as np
 import pytest
 
-import hostlib as H
+import children as K
 import memseq_cases as MC
 import yuv_cases as Y
 
@@ -25,41 +23,14 @@ pytestmark = pytest.mark.gpu
 
 TESTS = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(TESTS, "golden")
-HIP_SO = os.path.join(H.ROOT, "libagmv_amd", "libagmv_hip.so")
 FULL, PDIFS, ADAPTIVE = 1, 2, 3
 NV12_601, I420_601 = Y.NV12, Y.I420
 NV12_709F, I420_709F = Y.NV12 | Y.BT709 | Y.FULL_RANGE, Y.I420 | Y.BT709 | Y.FULL_RANGE
 LENIENCY = {3: 0.2282, 1: 0.2282}                  # AGMV_OPT_III, AGMV_OPT_I (heavy PDIFS)
 
-# one job per child, as JSON in argv[1]; the answer is one JSON line on stdout
 CHILD = textwrap.dedent("""
-    import ctypes as C, json, sys
-    import numpy as np
-    job = json.loads(sys.argv[1])
-    L, G = C.CDLL(job["so"]), C.CDLL(job["hip_so"])
-    vp, ul = C.c_void_p, C.c_ulong
-    class INFO(C.Structure):
-        _fields_ = [("width", ul), ("height", ul), ("number_of_frames", ul), ("version", C.c_ubyte), ("total_audio_duration", ul),
-                    ("sample_rate", ul), ("audio_size", ul), ("number_of_channels", C.c_ushort), ("bits_per_sample", C.c_ushort)]
-    G.agmv_hip_malloc.restype = vp; G.agmv_hip_malloc.argtypes = [C.c_size_t]
-    G.agmv_hip_free.argtypes = [vp]
-    G.agmv_hip_memcpy_h2d.argtypes = [vp, vp, C.c_size_t]; G.agmv_hip_memcpy_d2h.argtypes = [vp, vp, C.c_size_t]
-    G.agmv_hip_memset.argtypes = [vp, C.c_int, C.c_size_t]
-    G.agmv_hip_yuv_frame_bytes.restype = C.c_size_t; G.agmv_hip_yuv_frame_bytes.argtypes = [C.c_int, C.c_uint32, C.c_uint32]
-    L.AGMV_EncodeFramesFmtDev.restype = C.c_int
-    L.AGMV_EncodeFramesFmtDev.argtypes = [C.c_char_p, vp, C.c_int] + [ul] * 4 + [C.c_int] * 4
-    L.AGMV_EncodeFramesDev.restype = C.c_int
-    L.AGMV_EncodeFramesDev.argtypes = [C.c_char_p, vp] + [ul] * 4 + [C.c_int] * 4
-    L.AGMV_DecodeFramesFmtDev.restype = C.c_int
-    L.AGMV_DecodeFramesFmtDev.argtypes = [C.c_char_p, vp, C.c_int, ul, C.POINTER(INFO)]
-    L.AGMV_SetBatchFrames.argtypes = [C.c_uint]
     L.AGMV_SetBatchFrames(job["batch"])
     res = {"enc_rc": [], "dec": []}
-
-    def upload(a):
-        d = G.agmv_hip_malloc(a.nbytes)
-        assert d and G.agmv_hip_memcpy_h2d(d, a.ctypes.data, a.nbytes) == 0
-        return d
 
     for e in job.get("enc", []):             # the YUV clip through FmtDev, then the comparator clip through AGMV_EncodeFramesDev
         raw, packed = np.load(e["yuv"]), np.load(e["packed"])
@@ -67,10 +38,10 @@ CHILD = textwrap.dedent("""
         args = [n, w, h, 24, e["opt"], e["quality"], e["compression"], e["schedule"]]
         d = upload(raw)
         rc = [L.AGMV_EncodeFramesFmtDev(e["out"].encode(), d, e["fmt"], *args)]
-        G.agmv_hip_free(d)
+        free(d)
         d = upload(packed)
         rc.append(L.AGMV_EncodeFramesDev((e["out"] + ".packed").encode(), d, *args))
-        G.agmv_hip_free(d)
+        free(d)
         res["enc_rc"].append(rc)
     for e in job.get("dec", []):             # fmt 1: the XRGB32 decode
         path = e["path"].encode()
@@ -78,13 +49,10 @@ CHILD = textwrap.dedent("""
         rc_info = L.AGMV_DecodeFramesFmtDev(path, None, e["fmt"], 0, C.byref(info))
         n, w, h = info.number_of_frames, info.width, info.height
         fb = 4 * w * h if e["fmt"] == 1 else G.agmv_hip_yuv_frame_bytes(e["fmt"], w, h)
-        buf = np.empty(n * fb, np.uint8)
-        d = G.agmv_hip_malloc(buf.nbytes)
-        assert d and G.agmv_hip_memset(d, 0xA5, buf.nbytes) == 0        # what a frame that is not decoded keeps
+        d = poisoned(n * fb)                                            # what a frame that is not decoded keeps
         rc = L.AGMV_DecodeFramesFmtDev(path, d, e["fmt"], e.get("cap", n), None)
-        assert G.agmv_hip_memcpy_d2h(buf.ctypes.data, d, buf.nbytes) == 0
-        G.agmv_hip_free(d)
-        np.save(e["out"], buf)
+        np.save(e["out"], download(d, n * fb))
+        free(d)
         res["dec"].append({"info_rc": rc_info, "rc": rc, "n": n, "w": w, "h": h, "fb": fb})
     print(json.dumps(res))
 """)
@@ -116,12 +84,7 @@ SEQ_CHILD = textwrap.dedent("""
 
 
 def run_child(cwd, job, env=None, script=CHILD):
-    H.lib()
-    job = dict(job, so=H.SO, hip_so=HIP_SO, tests=TESTS, root=H.ROOT)
-    r = subprocess.run([sys.executable, "-c", script, json.dumps(job)], cwd=str(cwd), env=dict(os.environ, **(env or {})),
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    return json.loads(r.stdout.decode().strip().splitlines()[-1])
+    return K.run_child(cwd, script, job, env, prelude="" if script is SEQ_CHILD else K.PRELUDE)
 
 
 @functools.lru_cache(maxsize=None)

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import children as K
 import hostlib as H
 import oracles as O
 import synth as S
@@ -142,7 +143,6 @@ def test_bmp_roundtrip(tmp_path):
 def test_palette_build_matches_reference_file(tmp_path):
     """the palette the reference's AGMV_EncodeAGMV writes into the header for a small synthetic clip
     (its real histogram + bubble sort + greedy pick + slot map) against AGMV_BuildPalette."""
-    import subprocess, sys, textwrap
     W, H_, T = 64, 48, 12
     d = tmp_path / "fr"
     d.mkdir()
@@ -150,16 +150,8 @@ def test_palette_build_matches_reference_file(tmp_path):
     for t, f in enumerate(frames, 1):
         H.write_bmp(str(d / ("f%d.bmp" % t)), f)
     # run the reference driver in a child process (it frees its AGMV and writes into CWD)
-    code = textwrap.dedent("""
-        import ctypes as C, sys
-        L = C.CDLL(%r)
-        L.CreateAGMV.restype = C.c_void_p; L.CreateAGMV.argtypes = [C.c_ulong] * 4
-        L.AGMV_EncodeAGMV.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ubyte] + [C.c_ulong] * 5 + [C.c_int] * 3
-        a = L.CreateAGMV(%d, %d, %d, 24)
-        L.AGMV_EncodeAGMV(a, b"ref.agmv", b"fr", b"f", 1, 1, %d, %d, %d, 24, int(sys.argv[1]), int(sys.argv[2]), 1)
-    """ % (O.REF_SO, T, W, H_, T, W, H_))
     for opt, quality in ((3, 3), (2, 2)):
-        subprocess.run([sys.executable, "-c", code, str(opt), str(quality)], cwd=str(tmp_path), check=True, stdout=subprocess.DEVNULL)
+        assert K.drive_child(tmp_path, "agmv", T, W, H_, opt, quality, 1, out="ref.agmv", so=O.REF_SO).returncode == 0
         hdr = open(tmp_path / "ref.agmv", "rb").read()
         npal = 2 if opt == 3 else 1
         ref_pal = np.frombuffer(hdr[38:38 + 768 * npal], np.uint8).reshape(-1, 3).astype(np.uint32)
@@ -176,10 +168,6 @@ def test_palette_build_matches_reference_file(tmp_path):
         assert (mine == ref_pal).all(), (opt, quality, int((mine != ref_pal).sum()))
 
 
-class _Entry(C.Structure):
-    _fields_ = [("pal_num", C.c_uint8), ("index", C.c_uint8), ("occurence", C.c_ulong)]
-
-
 def test_find_smallest_helpers_match_reference():
     """AGMV_FindSmallestColor / AGMV_FindSmallestEntry (reference src/agmv_utils.c:818-849, :897-914; unused by the
     library, part of its API): first 200 slots only, entry chosen by the smaller index."""
@@ -188,12 +176,7 @@ def test_find_smallest_helpers_match_reference():
     p1 = rng.integers(0, 1 << 24, 256).astype(np.uint64)
     p1[7] = p0[3]
     cols = [int(c) for c in rng.integers(0, 1 << 24, 200)] + [int(p0[3]), int(p0[250]), 0, 0xFFFFFF]
-    libs = [C.CDLL(H.SO)] + ([C.CDLL(O.REF_SO)] if O.have_ref() else [])
-    for L in libs:
-        L.AGMV_FindSmallestColor.restype = C.c_uint8
-        L.AGMV_FindSmallestColor.argtypes = [C.c_void_p, C.c_ulong]
-        L.AGMV_FindSmallestEntry.restype = _Entry
-        L.AGMV_FindSmallestEntry.argtypes = [C.c_void_p, C.c_void_p, C.c_ulong]
+    libs = [H.lib()] + ([H.bind(C.CDLL(O.REF_SO), missing_ok=True)] if O.have_ref() else [])
 
     def smallest(pal, c):
         ch = lambda v, s: (v >> s) & 255
@@ -210,7 +193,7 @@ def test_find_smallest_helpers_match_reference():
 
 
 def test_display_frame_and_header_export(tmp_path):
-    L = C.CDLL(H.SO)
+    L = H.lib()
     # AGMV_ExportAGMVToHeader: ./agmv.h, byte-identical to the reference's when it is built here
     src = tmp_path / "clip.agmv"
     src.write_bytes(bytes(range(256)) * 5 + b"tail")
@@ -225,7 +208,6 @@ def test_display_frame_and_header_export(tmp_path):
     assert outs[0].count(b"\n") == 6 + 2 + 1 and outs[0].endswith(b"116,97,105,108,};\n#endif")
     assert all(o == outs[0] for o in outs)
     # PlotPixel clips; AGMV_DisplayFrame copies the frame into the top-left of a larger (or smaller) target
-    L.PlotPixel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulong]
     vram = np.zeros(6 * 4, np.uint64)
     for (x, y) in ((-1, 0), (0, -1), (6, 0), (0, 4), (5, 3), (2, 1)):
         L.PlotPixel(vram.ctypes.data, x, y, 6, 4, 0xABCDEF)

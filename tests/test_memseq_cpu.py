@@ -14,10 +14,6 @@ ROOT = H.ROOT
 def entry_points():
     L = H.lib()
     from libagmv_amd.seq import AGMV_INFO
-    L.AGMV_EncodeFramesDev.restype = C.c_int
-    L.AGMV_EncodeFramesDev.argtypes = [C.c_char_p, C.c_void_p] + [C.c_ulong] * 4 + [C.c_int] * 4
-    L.AGMV_DecodeFramesDev.restype = C.c_int
-    L.AGMV_DecodeFramesDev.argtypes = [C.c_char_p, C.c_void_p, C.c_ulong, C.POINTER(AGMV_INFO)]
     return L, AGMV_INFO
 
 
@@ -58,8 +54,6 @@ def test_null_destination_reads_the_header_only(golden, golden_dir):
 
 def source_index(sw, sh, scale_w, scale_h, w, h):
     L = H.lib()
-    L.agmv_source_index.restype = C.POINTER(C.c_uint32)
-    L.agmv_source_index.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32]
     p = L.agmv_source_index(sw, sh, scale_w, scale_h, w, h)
     out = np.ctypeslib.as_array(p, (w * h,)).copy()
     libc = C.CDLL(None)

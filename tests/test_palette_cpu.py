@@ -1,7 +1,6 @@
 """The palette refinement without a GPU: AGMV_BuildPaletteRefined with no rounds is AGMV_BuildPalette and opens no device, the numpy
 statement of the refinement (tests/palette_cases.py) behaves like Lloyd's algorithm on the golden clip's histograms, and
 encode_frames checks palette_refine before anything else."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -14,10 +13,6 @@ QUALITIES = (PC.HIGH, PC.MID, PC.LOW)
 
 def refined_lib():
     L = H.lib()
-    L.AGMV_BuildPaletteRefined.restype = C.c_int
-    L.AGMV_BuildPaletteRefined.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]
-    L.AGMV_SetPaletteRefine.restype = None
-    L.AGMV_SetPaletteRefine.argtypes = [C.c_uint]
     return L
 
 

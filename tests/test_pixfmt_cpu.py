@@ -9,6 +9,7 @@ import re
 import pytest
 
 import hostlib as H
+from libagmv_amd import abi
 import pixfmt_cases as P
 
 ROOT = H.ROOT
@@ -20,16 +21,12 @@ HOST_FUNCS = ["AGMV_EncodeFramesFmtDev", "AGMV_DecodeFramesFmtDev"]
 def host():
     L = H.lib()
     from libagmv_amd.seq import AGMV_INFO
-    L.AGMV_EncodeFramesFmtDev.restype = C.c_int
-    L.AGMV_EncodeFramesFmtDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int] + [C.c_ulong] * 4 + [C.c_int] * 4
-    L.AGMV_DecodeFramesFmtDev.restype = C.c_int
-    L.AGMV_DecodeFramesFmtDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.POINTER(AGMV_INFO)]
     return L, AGMV_INFO
 
 
 def hip_lib():
     H.lib()
-    return C.CDLL(os.path.join(ROOT, "libagmv_amd", "libagmv_hip.so"))
+    return abi.bind(C.CDLL(os.path.join(ROOT, "libagmv_amd", "libagmv_hip.so")), abi.HIP)
 
 
 def test_headers_declare_the_enum_and_the_functions():
@@ -60,8 +57,6 @@ def test_both_libraries_export_the_functions():
 
 def test_frame_bytes_needs_no_device():
     G = hip_lib()
-    G.agmv_hip_pixfmt_frame_bytes.restype = C.c_size_t
-    G.agmv_hip_pixfmt_frame_bytes.argtypes = [C.c_int, C.c_size_t]
     for n in (0, 1, 7, 160 * 128, 1920 * 1080, (1 << 33) + 5):
         assert [G.agmv_hip_pixfmt_frame_bytes(f, n) for f in range(0, 7)] == [0, 4 * n, 3 * n, 3 * n, 4 * n, 3 * n, 0], n
     assert [P.frame_bytes(f, 10) for f in (1, 2, 3, 4, 5)] == [G.agmv_hip_pixfmt_frame_bytes(f, 10) for f in (1, 2, 3, 4, 5)]

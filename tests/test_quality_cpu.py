@@ -101,17 +101,9 @@ def test_float64_ssim_agrees_to_one_q20_step():
 
 
 # ---- the public calls refuse before a device is opened (this host has none)
-class QUALITY(C.Structure):
-    _fields_ = [("sse", C.c_ulonglong * 3), ("block_sse", C.c_ulonglong * 3), ("max_err", C.c_ulonglong * 3), ("ssim", C.c_longlong * 3)]
+from libagmv_amd.abi import AGMV_FRAME_QUALITY as QUALITY, AGMV_INFO as INFO  # noqa: E402
 
-
-def lib():
-    L = H.lib()
-    L.AGMV_MeasureFramesDev.restype = C.c_int
-    L.AGMV_MeasureFramesDev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_ulong, C.c_ulong, C.c_ulong, C.POINTER(QUALITY)]
-    L.AGMV_MeasureFileDev.restype = C.c_int
-    L.AGMV_MeasureFileDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.POINTER(QUALITY), C.c_void_p]
-    return L
+lib = H.lib
 
 
 def test_entry_is_96_bytes():
@@ -148,11 +140,6 @@ def test_measure_file_reads_the_header_and_refuses_what_cannot_correspond(tmp_pa
     """on a file of the goldens: the info-only call, a frame count that is not the header's, and -- with the header's width made odd
     by hand -- a YUV reference that such a size cannot hold; all before a device is opened"""
     import os
-
-    class INFO(C.Structure):
-        _fields_ = [("width", C.c_ulong), ("height", C.c_ulong), ("number_of_frames", C.c_ulong), ("version", C.c_ubyte),
-                    ("total_audio_duration", C.c_ulong), ("sample_rate", C.c_ulong), ("audio_size", C.c_ulong),
-                    ("number_of_channels", C.c_ushort), ("bits_per_sample", C.c_ushort)]
     L = lib()
     q = (QUALITY * 1)()
     fake = C.c_void_p(0x1000)

@@ -18,8 +18,6 @@ ROOT = H.ROOT
 
 def host():
     L = H.lib()
-    L.AGMV_EncodeFramesScaledDev.restype = C.c_int
-    L.AGMV_EncodeFramesScaledDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int] + [C.c_ulong] * 5 + [C.c_int, C.c_ulong] + [C.c_int] * 4
     return L
 
 

@@ -15,28 +15,27 @@ import hostlib as H
 GOLDEN = os.path.join(H.ROOT, "tests", "golden")
 FIXTURE = os.path.join(GOLDEN, "seq_refusals.json")
 FAKE = 4096                                                      # never dereferenced
-U, I, P, S, F3 = C.c_ulong, C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_float)
 UNIT = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))                        # mean, std
 
-# ---- the entry points: (argument, ctypes type, baseline value) in the order of the C signature
-ENC = [("fps", U, 24), ("opt", I, 3), ("quality", I, 3), ("compression", I, 1), ("schedule", I, 2)]
-CLIP = [("n", U, 8), ("w", U, 16), ("h", U, 16)]
-TENSOR = [("type", I, 1), ("mean", F3, UNIT[0]), ("std", F3, UNIT[1])]
+# ---- the entry points: (argument, baseline value) in the order of the C signature (libagmv_amd/abi.py has the types)
+ENC = [("fps", 24), ("opt", 3), ("quality", 3), ("compression", 1), ("schedule", 2)]
+CLIP = [("n", 8), ("w", 16), ("h", 16)]
+TENSOR = [("type", 1), ("mean", UNIT[0]), ("std", UNIT[1])]
 ENTRY = {
-    "AGMV_EncodeFramesDev": [("filename", S, "out"), ("frames", P, FAKE)] + CLIP + ENC,
-    "AGMV_EncodeFramesFmtDev": [("filename", S, "out"), ("frames", P, FAKE), ("fmt", I, 2)] + CLIP + ENC,
-    "AGMV_EncodeFramesScaledDev": [("filename", S, "out"), ("frames", P, FAKE), ("fmt", I, 2), ("n", U, 8), ("sw", U, 32), ("sh", U, 32), ("w", U, 16),
-                                   ("h", U, 16), ("filt", I, 2)] + ENC,
-    "AGMV_EncodeFramesTensorDev": [("filename", S, "out"), ("frames", P, FAKE)] + TENSOR + CLIP + ENC,
-    "AGMV_DecodeFramesDev": [("filename", S, "good"), ("frames", P, FAKE), ("cap", U, 4), ("info", P, None)],
-    "AGMV_DecodeFramesFmtDev": [("filename", S, "good"), ("frames", P, FAKE), ("fmt", I, 2), ("cap", U, 4), ("info", P, None)],
-    "AGMV_DecodeFramesScaledDev": [("filename", S, "good"), ("frames", P, FAKE), ("fmt", I, 2), ("w", U, 16), ("h", U, 16), ("filt", I, 1), ("cap", U, 4),
-                                   ("info", P, None)],
-    "AGMV_DecodeFramesTensorDev": [("filename", S, "good"), ("frames", P, FAKE)] + TENSOR + [("w", U, 16), ("h", U, 16), ("filt", I, 1), ("cap", U, 4),
-                                                                                              ("info", P, None)],
-    "AGMV_MeasureFramesDev": [("test", P, FAKE), ("ref", P, FAKE), ("fmt", I, 2), ("n", U, 2), ("w", U, 8), ("h", U, 8), ("quality", P, FAKE)],
-    "AGMV_MeasureFileDev": [("filename", S, "good"), ("ref", P, FAKE), ("fmt", I, 2), ("n", U, "frames-of-good"), ("quality", P, FAKE), ("info", P, None)],
-    "AGMV_DecodeAudioDev": [("filename", S, "good"), ("pcm", P, FAKE), ("fmt", I, 1), ("cap", U, 1 << 20), ("info", P, None)],
+    "AGMV_EncodeFramesDev": [("filename", "out"), ("frames", FAKE)] + CLIP + ENC,
+    "AGMV_EncodeFramesFmtDev": [("filename", "out"), ("frames", FAKE), ("fmt", 2)] + CLIP + ENC,
+    "AGMV_EncodeFramesScaledDev": [("filename", "out"), ("frames", FAKE), ("fmt", 2), ("n", 8), ("sw", 32), ("sh", 32), ("w", 16),
+                                   ("h", 16), ("filt", 2)] + ENC,
+    "AGMV_EncodeFramesTensorDev": [("filename", "out"), ("frames", FAKE)] + TENSOR + CLIP + ENC,
+    "AGMV_DecodeFramesDev": [("filename", "good"), ("frames", FAKE), ("cap", 4), ("info", None)],
+    "AGMV_DecodeFramesFmtDev": [("filename", "good"), ("frames", FAKE), ("fmt", 2), ("cap", 4), ("info", None)],
+    "AGMV_DecodeFramesScaledDev": [("filename", "good"), ("frames", FAKE), ("fmt", 2), ("w", 16), ("h", 16), ("filt", 1), ("cap", 4),
+                                   ("info", None)],
+    "AGMV_DecodeFramesTensorDev": [("filename", "good"), ("frames", FAKE)] + TENSOR + [("w", 16), ("h", 16), ("filt", 1), ("cap", 4),
+                                                                                              ("info", None)],
+    "AGMV_MeasureFramesDev": [("test", FAKE), ("ref", FAKE), ("fmt", 2), ("n", 2), ("w", 8), ("h", 8), ("quality", FAKE)],
+    "AGMV_MeasureFileDev": [("filename", "good"), ("ref", FAKE), ("fmt", 2), ("n", "frames-of-good"), ("quality", FAKE), ("info", None)],
+    "AGMV_DecodeAudioDev": [("filename", "good"), ("pcm", FAKE), ("fmt", 1), ("cap", 1 << 20), ("info", None)],
 }
 
 # ---- the violations: (return-code class, changes to the baseline).  Two of different classes whose changes do not touch the same
@@ -118,23 +117,22 @@ def files(tmp):
 def replay(tmp, verbose=False):
     """{entry point: {case name: return value}}; a case with a pending track is [its return value, that of the second refused call]"""
     L = H.lib()
-    L.AGMV_SetAudioDev.restype = C.c_int
-    L.AGMV_SetAudioDev.argtypes = [P, I, U, U, C.c_ushort]
     paths, nframes = files(tmp)
     got = {}
     for entry, name, changes in cases():
         f = getattr(L, entry)
-        f.restype = C.c_int
-        f.argtypes = [t for _, t, _ in ENTRY[entry]]
+        assert len(f.argtypes) == len(ENTRY[entry])
 
         def call(changes):
             args = []
-            for arg, t, base in ENTRY[entry]:
+            for (arg, base), t in zip(ENTRY[entry], f.argtypes):
                 v = changes.get(arg, base)
                 if arg == "filename":
                     v = paths[v]
-                elif t is F3 and v is not None:
+                elif arg in ("mean", "std") and v is not None:
                     v = (C.c_float * 3)(*v)
+                elif v == FAKE and issubclass(t, C._Pointer):       # (a structure pointer takes no plain address)
+                    v = C.cast(v, t)
                 elif v == "frames-of-good":
                     v = nframes
                 args.append(v)

@@ -31,13 +31,6 @@ def host():
     import torch  # noqa: F401
     from libagmv_amd.seq import AGMV_INFO
     L = H.lib()
-    L.AGMV_DecodeFramesTensorDev.restype = C.c_int
-    L.AGMV_DecodeFramesTensorDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_ulong, C.c_ulong, C.c_int, C.c_ulong,
-                                             C.POINTER(AGMV_INFO)]
-    L.AGMV_EncodeFramesTensorDev.restype = C.c_int
-    L.AGMV_EncodeFramesTensorDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_ulong] * 4 + [C.c_int] * 4
-    L.AGMV_EncodeFramesDev.restype = C.c_int
-    L.AGMV_EncodeFramesDev.argtypes = [C.c_char_p, C.c_void_p] + [C.c_ulong] * 4 + [C.c_int] * 4
     return L
 
 

@@ -21,8 +21,6 @@ SPLASH = os.path.join(ROOT, "tests", "golden", "agmv_splash.agmv")         # 119
 def host():
     from libagmv_amd.seq import AGMV_INFO
     L = H.lib()
-    L.AGMV_DecodeFramesScaledDev.restype = C.c_int
-    L.AGMV_DecodeFramesScaledDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.c_ulong, C.c_int, C.c_ulong, C.POINTER(AGMV_INFO)]
     return L
 
 

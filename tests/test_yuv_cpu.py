@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import hostlib as H
+from libagmv_amd import abi
 import yuv_cases as Y
 
 ROOT = H.ROOT
@@ -21,21 +22,12 @@ HIP_FUNCS = ["agmv_hip_yuv_frame_bytes", "agmv_hip_yuv_to_xrgb_dev", "agmv_hip_y
 def host():
     L = H.lib()
     from libagmv_amd.seq import AGMV_INFO
-    L.AGMV_EncodeFramesFmtDev.restype = C.c_int
-    L.AGMV_EncodeFramesFmtDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int] + [C.c_ulong] * 4 + [C.c_int] * 4
-    L.AGMV_DecodeFramesFmtDev.restype = C.c_int
-    L.AGMV_DecodeFramesFmtDev.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_ulong, C.POINTER(AGMV_INFO)]
     return L, AGMV_INFO
 
 
 def hip_lib():
     H.lib()
-    G = C.CDLL(os.path.join(ROOT, "libagmv_amd", "libagmv_hip.so"))
-    G.agmv_hip_yuv_frame_bytes.restype = C.c_size_t
-    G.agmv_hip_yuv_frame_bytes.argtypes = [C.c_int, C.c_uint32, C.c_uint32]
-    G.agmv_hip_pixfmt_frame_bytes.restype = C.c_size_t
-    G.agmv_hip_pixfmt_frame_bytes.argtypes = [C.c_int, C.c_size_t]
-    return G
+    return abi.bind(C.CDLL(os.path.join(ROOT, "libagmv_amd", "libagmv_hip.so")), abi.HIP)
 
 
 def test_headers_and_libraries_hold_the_formats_and_the_functions():

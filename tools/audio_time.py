@@ -64,10 +64,6 @@ def main():
     pinned = torch.empty((n, CH), dtype=torch.int16).pin_memory()
     med, lo, hi = timed(lambda: pinned.copy_(s16, non_blocking=True))
     say("S16  download of the PCM to pinned host memory %.2f ms (min %.2f .. max %.2f), %.1f GB/s" % (med, lo, hi, total * 2 / (med * 1e-3) / 1e9))
-    L.CreateAGMV.restype = C.c_void_p
-    L.CreateAGMV.argtypes = [C.c_ulong] * 4
-    L.AGMV_CompressAudio.argtypes = [C.c_void_p]
-    L.AGMV_SetAudioSize.argtypes = [C.c_void_p, C.c_ulong]
     a = L.CreateAGMV(1, 4, 4, 1)
     L.AGMV_SetAudioSize(a, total)
     host = pinned.numpy().view(np.uint16)

@@ -10,6 +10,7 @@ R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import numpy as np
 import hostlib as H
+from libagmv_amd import abi
 W, Hh, T = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
 batch = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 devices = int(sys.argv[5]) if len(sys.argv) > 5 else 1
@@ -17,23 +18,8 @@ comp = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 flow = sys.argv[7] if len(sys.argv) > 7 else "bmp"
 reps = int(sys.argv[8]) if len(sys.argv) > 8 else 1
 assert flow in ("bmp", "dev", "both")
-L = C.CDLL(H.SO)
-G = C.CDLL(os.path.join(R, "libagmv_amd", "libagmv_hip.so"))
-vp, ul = C.c_void_p, C.c_ulong
-L.CreateAGMV.restype = vp; L.CreateAGMV.argtypes = [ul] * 4
-sig = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ubyte] + [ul] * 5 + [C.c_int] * 3
-L.AGMV_EncodeFullAGMV.argtypes = sig
-L.AGMV_DecodeAGMV.argtypes = [C.c_char_p, C.c_ubyte, C.c_int]
-L.AGMV_EncodeFramesDev.argtypes = [C.c_char_p, vp] + [ul] * 4 + [C.c_int] * 4
-L.AGMV_DecodeFramesDev.argtypes = [C.c_char_p, vp, ul, vp]
-L.AGMV_SetBatchFrames.argtypes = [C.c_uint]
-L.AGMV_SetDevices.argtypes = [C.c_uint]
-L.AGMV_SynthFrame.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_ulonglong]
-G.agmv_hip_create.restype = vp; G.agmv_hip_create.argtypes = [C.c_int]
-G.agmv_hip_malloc.restype = vp; G.agmv_hip_malloc.argtypes = [C.c_size_t]
-G.agmv_hip_free.argtypes = [vp]
-G.agmv_hip_synth_dev.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, vp]
-G.agmv_hip_last_error.restype = C.c_char_p
+L = abi.bind(C.CDLL(H.SO), abi.AGMV)
+G = abi.bind(C.CDLL(os.path.join(R, "libagmv_amd", "libagmv_hip.so")), abi.HIP)
 label = "%dx%d x %d frames (batch %d, %d GPU(s), %s)" % (W, Hh, T, batch, devices, "LZSS" if comp == 1 else "LZ77")
 
 

@@ -7,7 +7,6 @@ and palette size (512 colours with 511 free, 256 colours):
   3  AGMV_BuildPaletteRefined, 16 rounds: pick, upload of the histogram, refinement, download, slot map (wall time)
 There is no target: the stage runs once per file.  What is printed is also written to profiles/palette/refine_time.txt (or argv[3]).
 usage: palette_time.py [T=32] [reps=5] [out]"""
-import ctypes as C
 import os
 import sys
 import time
@@ -41,10 +40,6 @@ def start_of(p0, p1, mode512):
 def main():
     hip = AgmvHip(0)
     L = seq.load_library()
-    L.AGMV_BuildPalette.restype = None
-    L.AGMV_BuildPalette.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.AGMV_BuildPaletteRefined.restype = C.c_int
-    L.AGMV_BuildPaletteRefined.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]
     rgb = np.load(os.path.join(R, "tests", "golden", "foxlogo212.npz"))["rgb"].astype(np.uint32)
     fox = torch.from_numpy((rgb[..., 0] << 16 | rgb[..., 1] << 8 | rgb[..., 2]).view(np.int32)).cuda()
     clips = (("foxlogo, 212 x 320x240", fox), ("agmv_synth_v1, %d x 1920x1080" % T, hip.synth_dev(1920, 1080, 1, T)))

@@ -3,7 +3,6 @@ agmv_synth_v1 frames resident on the GPU: HIP events, median of REPS after a war
 frame is read once) over that time as a share of the 8 TB/s HBM peak.  Beside it the host library's AGMV_CompareFrameSimilarity
 over the same T - 1 pairs on one core, and the check that both give the same counts.
 usage: similarity_time.py [T=256] [reps=7]"""
-import ctypes as C
 import os
 import sys
 import time
@@ -42,8 +41,6 @@ def main():
           "%.2f GB read once = %.2f TB/s = %.0f %% of the 8 TB/s HBM peak" % (T, W, Hh, REPS, ms, min(ts), max(ts), nbytes / 1e9,
                                                                           nbytes / ms / 1e9, 100 * nbytes / (ms * 1e-3) / HBM_PEAK), flush=True)
     L = H.lib()
-    L.AGMV_CompareFrameSimilarity.restype = C.c_float
-    L.AGMV_CompareFrameSimilarity.argtypes = [H.u64p, H.u64p, C.c_ulong, C.c_ulong]
     gpu = counts.cpu().numpy().view(np.uint32)
     prev = frames[0].cpu().numpy().view(np.uint32).reshape(-1).astype(np.uint64)
     host_s, same = 0.0, True
