@@ -561,6 +561,52 @@ int AGMV_EncodeFramesTensorDev(const char* filename, const void* d_tensor, AGMV_
                                u32 num_of_frames, u32 width, u32 height, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
                                AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule);
 
+/* A view of a file: 16 frames at stride 4 from somewhere inside it, a 224 x 224 window of them, as a model takes them -- without
+   a tensor that holds the whole file.  A view selects the frames first, first + step, first + 2 * step, ... of the file and of
+   each the window [x, x + width) x [y, y + height) of its pixels.  The contract, for every file, damaged ones included:
+     frame j of a view is the window of frame first + j * step of the full decode (AGMV_DecodeFramesDev).
+   Everything behind the selection applies to the window as to a file of that size: the layout `fmt`, a target size and its
+   filter (AGMV_DecodeFramesScaledDev), the normalisation of a tensor clip (AGMV_DecodeFramesTensorDev).  The fields are plain
+   32-bit `unsigned` (u32 is `unsigned long` here):
+     view == NULL            the whole file
+     step                    >= 1
+     count                   0 means "to the end of the file"; a selection that runs past the file's last frame is cut there;
+                             `first` at or behind the end delivers 0 frames and writes nothing
+     width == height == 0    the full frame; x and y must then be 0.  Otherwise the window must lie inside the file's frame
+   A target width == height == 0 means no scaling, and `filter` is not read, as in AGMV_DecodeFramesTensorDev.  cap_frames counts
+   frames of the view; frame j lands j * (frame bytes of the layout at the target's, else the window's, size) bytes into the
+   destination, and frames behind cap_frames are not touched.  Returns the number of view frames delivered, or a negative value;
+   *info (may be NULL) receives the header's AGMV_INFO as always.  The checks, in this order, all before a device is opened:
+     -1        NULL filename; unknown format, type or normalisation; unknown filter when a target is given; step == 0; exactly one
+               of view->width, view->height zero; x or y not zero with a zero window
+     -4        a target with a width or height of zero, or more than 2^28 target pixels
+     -Error    the file cannot be opened or its header is bad (as AGMV_DecodeFramesFmtDev)
+      0        the destination is NULL: only *info is filled
+     -4        the window does not lie inside the frame; AGMV_SCALE_AREA with a target larger than the window in either axis, or a
+               file frame above 2^24 pixels; NV12 / I420 without a target size over a window of odd width or height
+   How it runs.  The view that selects everything (first 0, step 1, the full frame) is the decode without a view, launch for
+   launch, of as many frames as it delivers.  Any other view ends behind the last frame it needs.  The LZ stage runs for every
+   frame from 0 up to there, in order: bytes [bpos, bpos + 16) of a frame's row come from the ONE persistent buffer of the
+   reference's decoder, which only the LZ output of all earlier frames makes right.  The GPU stage -- parse, reconstruct, I-frame
+   snapshot, sink -- starts at the GOP that holds `first`, frame g0 = first & ~3, from the state of a fresh decoder.  When g0 > 0 the
+   decoder is asked once, behind the first batch it decoded, whether a pixel of that batch derives from the state before it
+   (agmv_hip_decode_prior_dependent of include/agmv_hip.h: exact, per pixel); if so -- a COPY in the I-frame, a stream that ends
+   early, a file of width 4 -- the call is run again with the GPU stage from frame 0 and writes the same destinations.  Every later
+   batch follows from the first by the decoder's own state hand-over.  The selected windows of a batch are packed by one copy
+   launch (agmv_hip_view_frames_async of include/agmv_hip_view.h) into a buffer of one batch of windows, which the sink reads as it reads a batch of a file of
+   the window's size; a packed XRGB32 destination without a target receives that copy directly, and consecutive full frames go to
+   the sink from where they were decoded.  A batch without a selected frame runs no sink launch.
+   AGMV_GetViewStats reports what the last AGMV_DecodeViewDev / AGMV_DecodeViewTensorDev of this process did -- of a restarted
+   call, what the run that delivered did: lz_frames = frames through the LZ stage, gpu_frames = frames through the GPU stage,
+   delivered = the call's return value (0 for a negative one), restarts = 0 or 1.  All zero behind a call that did not reach the decode. */
+typedef struct AGMV_VIEW { unsigned first, count, step; unsigned x, y, width, height; } AGMV_VIEW;
+typedef struct AGMV_VIEW_STATS { unsigned lz_frames, gpu_frames, delivered, restarts; } AGMV_VIEW_STATS;
+int AGMV_DecodeViewDev(const char* filename, void* d_frames, AGMV_PIXFMT fmt, u32 width, u32 height, AGMV_SCALE filter, const AGMV_VIEW* view,
+                       u32 cap_frames, AGMV_INFO* info);
+int AGMV_DecodeViewTensorDev(const char* filename, void* d_tensor, AGMV_TENSORFMT type, const float mean[3], const float std[3], u32 width,
+                             u32 height, AGMV_SCALE filter, const AGMV_VIEW* view, u32 cap_frames, AGMV_INFO* info);
+void AGMV_GetViewStats(AGMV_VIEW_STATS* out);
+
 /* Audio tracks from and to GPU memory.  An AGMV_PCMFMT names the layout of PCM in device memory:
      AGMV_PCM_S16   [samples][channels] 16-bit words, bits unchanged (int16 WAV samples as they are); for 16-bit tracks
      AGMV_PCM_U8    [samples][channels] unsigned bytes; for 8-bit tracks; a copy

@@ -1,5 +1,5 @@
 """The public C signatures, stated once: the structures of include/agmv.h that Python passes, every function of
-include/agmv_hip.h (HIP) and every function of include/agmv.h that Python calls on libagmv.so (AGMV), as
+include/agmv_hip.h (HIP) and of include/agmv_hip_view.h (HIP_VIEW) and every function of include/agmv.h that Python calls on libagmv.so (AGMV), as
 name -> (restype, (argtypes...)).  bind() sets them on a loaded library.  tests/test_abi.py checks both tables and the
 structures against the headers.  ctypes only, and no library is loaded here: the test children import this module the
 way a C host would include the headers."""
@@ -23,9 +23,19 @@ class AGMV_FRAME_QUALITY(Structure):
     _fields_ = [("sse", c_ulonglong * 3), ("block_sse", c_ulonglong * 3), ("max_err", c_ulonglong * 3), ("ssim", c_longlong * 3)]
 
 
-# vp: any pointer but the three below and `const char*`; ul: the header's u32; the enums and Bool are c_int
+class AGMV_VIEW(Structure):
+    # plain 32-bit unsigned, not the header's u32
+    _fields_ = [("first", c_uint), ("count", c_uint), ("step", c_uint), ("x", c_uint), ("y", c_uint), ("width", c_uint), ("height", c_uint)]
+
+
+class AGMV_VIEW_STATS(Structure):
+    _fields_ = [("lz_frames", c_uint), ("gpu_frames", c_uint), ("delivered", c_uint), ("restarts", c_uint)]
+
+
+# vp: any pointer but the five below and `const char*`; ul: the header's u32; the enums and Bool are c_int
 vp, sz, u32, u64, ul = c_void_p, c_size_t, c_uint32, c_uint64, c_ulong
 INFO_P, QUALITY_P, ENTRY_P = POINTER(AGMV_INFO), POINTER(AGMV_FRAME_QUALITY), POINTER(AGMV_ENTRY)
+VIEW_P, VIEW_STATS_P = POINTER(AGMV_VIEW), POINTER(AGMV_VIEW_STATS)
 
 HIP = {
     "agmv_hip_max_usize": (sz, (u32, u32, c_int)),
@@ -116,6 +126,11 @@ HIP = {
     "agmv_hip_sync": (c_int, ()),
 }
 
+# include/agmv_hip_view.h, exported by the same library
+HIP_VIEW = {
+    "agmv_hip_view_frames_async": (c_int, (vp, vp, u32, u32, u32, u32, u32, u32, u32, u32, u32, vp, vp)),
+}
+
 _SEQ = (c_char_p, c_char_p, c_char_p, c_ubyte, ul, ul, ul, ul, ul, c_int, c_int, c_int)     # the three BMP drivers, behind `agmv`
 _CLIP = (ul, ul, ul, ul, c_int, c_int, c_int, c_int)                 # frames, width, height, fps, opt, quality, compression, schedule
 
@@ -201,6 +216,9 @@ AGMV = {
     "AGMV_DecodeFramesScaledDev": (c_int, (c_char_p, vp, c_int, ul, ul, c_int, ul, INFO_P)),
     "AGMV_EncodeFramesTensorDev": (c_int, (c_char_p, vp, c_int, vp, vp) + _CLIP),
     "AGMV_DecodeFramesTensorDev": (c_int, (c_char_p, vp, c_int, vp, vp, ul, ul, c_int, ul, INFO_P)),
+    "AGMV_DecodeViewDev": (c_int, (c_char_p, vp, c_int, ul, ul, c_int, VIEW_P, ul, INFO_P)),
+    "AGMV_DecodeViewTensorDev": (c_int, (c_char_p, vp, c_int, vp, vp, ul, ul, c_int, VIEW_P, ul, INFO_P)),
+    "AGMV_GetViewStats": (None, (VIEW_STATS_P,)),
     "AGMV_SetAudioDev": (c_int, (vp, c_int, ul, ul, c_ushort)),
     "AGMV_DecodeAudioDev": (c_int, (c_char_p, vp, c_int, ul, INFO_P)),
     "AGMV_MeasureFramesDev": (c_int, (vp, vp, c_int, ul, ul, ul, QUALITY_P)),

@@ -6,6 +6,7 @@
 //   k_histogram*              palette histogram; hist_add_runs is the one statement of the run-length atomics
 //   k_similarity*             grey-equality counts of consecutive frames
 //   k_gather*                 the nearest scale as a table look-up; gather_frames is the body of the XRGB32 and byte-layout forms
+//   k_view                    every step-th frame of an XRGB32 clip and a window of each, copied into a packed clip
 //   k_pix_* / k_yuv_*         the byte layouts and NV12 / I420 to and from XRGB32
 //   k_scale_area              the exact box-filter downscale of a clip in any of the seven layouts
 //   k_scale_up*               a decoded XRGB32 clip written at a target size, nearest or bilinear, in any of the seven layouts
@@ -23,6 +24,7 @@
 #include <type_traits>
 
 #include "agmv_hip_impl.h"
+#include "../../include/agmv_hip_view.h"
 
 // ----------------------------------------------------------------------------------------------
 // caller-side helpers: synthetic clip, PDIFS midpoint, palette histogram
@@ -199,6 +201,41 @@ __global__ __launch_bounds__(256) void k_gather(const uint32_t* __restrict__ src
                                                 const uint32_t* __restrict__ index, size_t n_out, uint32_t* __restrict__ dst)
 {
 	gather_frames(index, n_out, n_frames, src_px, dst, [&](uint32_t f, uint32_t i) { return src[(size_t)f * src_px + i]; });
+}
+
+// A view of an XRGB32 clip (agmv_hip_view_frames_async): dst[j][r][c] = src[first + j * step][y + r][x + c], whole words.  A
+// streaming copy: a lane owns the 4 consecutive pixels c0 .. c0 + 3 of one output row, blockIdx.x runs over the gpr groups of the h
+// rows of a frame, blockIdx.y strides over the frames.  LD4: x, src_w and the source's address are multiples of 4 pixels, so the
+// group is one 16-byte load that stays inside its source row (x + c0 + 4 <= src_w); ST4: w and the destination's address are, so
+// every group is whole and one 16-byte store.  Every other group goes word by word over its `live` pixels.
+template <bool LD4, bool ST4>
+__global__ __launch_bounds__(256) void k_view(const uint32_t* __restrict__ src, uint32_t src_w, size_t src_px, uint32_t first, uint32_t step, uint32_t count,
+                                              uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t gpr, uint32_t* __restrict__ dst)
+{
+	const size_t item = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (item >= (size_t)h * gpr) return;
+	const uint32_t r = (uint32_t)(item / gpr), c0 = (uint32_t)(item - (size_t)r * gpr) * 4u;
+	const uint32_t live = w - c0 < 4u ? w - c0 : 4u;
+	const size_t in_frame = (size_t)(y + r) * src_w + x + c0, out_frame = (size_t)r * w + c0, dst_px = (size_t)w * h;
+	for (uint32_t j = blockIdx.y; j < count; j += gridDim.y) {
+		const uint32_t* s = src + ((size_t)first + (size_t)j * step) * src_px + in_frame;
+		uint32_t* d = dst + (size_t)j * dst_px + out_frame;
+		uint4 v = make_uint4(0, 0, 0, 0);
+		if (LD4) v = *(const uint4*)s;
+		else {
+			v.x = s[0];
+			if (live > 1) v.y = s[1];
+			if (live > 2) v.z = s[2];
+			if (live > 3) v.w = s[3];
+		}
+		if (ST4) *(uint4*)d = v;
+		else {
+			d[0] = v.x;
+			if (live > 1) d[1] = v.y;
+			if (live > 2) d[2] = v.z;
+			if (live > 3) d[3] = v.w;
+		}
+	}
 }
 
 // ---- clips in the caller's pixel layout (AGMV_PIXFMT of include/agmv.h: the values 2 .. 5; XRGB32 = 1 goes to the kernels above) ----
@@ -1592,6 +1629,33 @@ extern "C" int agmv_hip_gather_dev(agmv_hip_ctx* c, const uint32_t* d_src, size_
 	if (n_frames == 0 || n_out == 0) return 0;
 	if (gather_grid(n_out, &blocks)) return -1;
 	hipLaunchKernelGGL(k_gather, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_src, src_frame_pixels, n_frames, d_index, n_out, d_dst);
+	CK(hipGetLastError());
+	return 0;
+}
+
+// the frames a launch of k_view spreads over blockIdx.y; a longer view takes further trips round the kernel's frame loop
+#define VIEW_GRID_FRAMES 65535u
+
+extern "C" int agmv_hip_view_frames_async(agmv_hip_ctx* c, const uint32_t* d_src, uint32_t src_w, uint32_t src_h, uint32_t first, uint32_t step, uint32_t count,
+                                          uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t* d_dst, void* stream)
+{
+	if (agmv_hip_enter(c)) return -1;
+	if (!d_src || !d_dst || src_w == 0 || src_h == 0 || w == 0 || h == 0 || step == 0) return agmv_hip_err("agmv_hip: view needs clips, sizes and a step that are not zero");
+	if (x > src_w || w > src_w - x || y > src_h || h > src_h - y)
+		return agmv_hip_err("agmv_hip: the window %u x %u at (%u, %u) does not lie inside the %u x %u frame", w, h, x, y, src_w, src_h);
+	if (count == 0) return 0;
+	const uint32_t gpr = w / 4 + ((w & 3) != 0);               // groups of 4 pixels per output row
+	const size_t items = (size_t)h * gpr;
+	if (items > 0xFFFFFFFFull) return agmv_hip_err("agmv_hip: window too large for one launch");
+	const dim3 grid((unsigned)((items + 255) / 256), count < VIEW_GRID_FRAMES ? count : VIEW_GRID_FRAMES);
+	const size_t src_px = (size_t)src_w * src_h;
+	const bool ld4 = (x & 3) == 0 && (src_w & 3) == 0 && ((uintptr_t)d_src & 15) == 0, st4 = (w & 3) == 0 && ((uintptr_t)d_dst & 15) == 0;
+#define VIEW_LAUNCH(L, S) hipLaunchKernelGGL((k_view<L, S>), grid, dim3(256), 0, (hipStream_t)stream, d_src, src_w, src_px, first, step, count, x, y, w, h, gpr, d_dst)
+	if (ld4 && st4) VIEW_LAUNCH(true, true);
+	else if (ld4) VIEW_LAUNCH(true, false);
+	else if (st4) VIEW_LAUNCH(false, true);
+	else VIEW_LAUNCH(false, false);
+#undef VIEW_LAUNCH
 	CK(hipGetLastError());
 	return 0;
 }

@@ -956,10 +956,33 @@ static int decode_result(int err, const unsigned long* count) { return err == NO
    the device array sink->measure.d_quality is made here, and the entries of the frames measured land in quality[] (host memory),
    downloaded once.  *info (may be NULL) = the header's; with info_only nothing else happens.  Returns an Error, or before a device is opened
    -3 where the reference cannot correspond to the file, -4 where the box filter cannot scale the file's frames to the sink's target. */
+static AGMV_VIEW_STATS g_view_stats;                 /* of the last AGMV_DecodeViewDev / AGMV_DecodeViewTensorDev */
+
+void AGMV_GetViewStats(AGMV_VIEW_STATS* out) { if (out) *out = g_view_stats; }
+
+/* The view of a sink as the caller gave it (include/agmv.h) against the file's header: the window's own size, the number of frames it
+   delivers in count, and `viewed` cleared for the view that selects everything, which is the decode without a view of that many
+   frames.  -4 where the file refuses the view, else NO_ERR. */
+static int resolve_view(agmv_sink* sink, const AGMV_MAIN_HEADER* hd, u32 cap_frames)
+{
+	const agmv_target* to = agmv_sink_target(sink);
+	AGMV_VIEW* v = &sink->view;
+	const u32 fw = hd->width, fh = hd->height;
+	uint32_t n;
+	if (v->width == 0) { v->width = (unsigned)fw; v->height = (unsigned)fh; }
+	else if (v->x > fw || v->width > fw - v->x || v->y > fh || v->height > fh - v->y) return -4;
+	if (to && to->filter == AGMV_SCALE_AREA && (to->w > v->width || to->h > v->height || (unsigned long long)fw * fh > (1ull << 24))) return -4;
+	if (!to && sink->kind == AGMV_SINK_FRAMES && AGMV_FMT_IS_YUV(sink->frames.fmt) && ((v->width | v->height) & 1)) return -4;
+	n = agmv_view_length(v->first, v->step, v->count, hd->num_of_frames > 0xFFFFFFFFul ? 0xFFFFFFFFu : (uint32_t)hd->num_of_frames);
+	v->count = n > cap_frames ? (unsigned)cap_frames : n;
+	if (v->first == 0 && v->step == 1 && v->width == fw && v->height == fh) sink->viewed = 0;
+	return NO_ERR;
+}
+
 static int decode_file(const char* filename, u8 img_type, agmv_sink* sink, AGMV_FRAME_QUALITY* quality, u32 cap_frames, int info_only, AGMV_INFO* info)
 {
 	const agmv_target* to = agmv_sink_target(sink);
-	const int measure = sink->kind == AGMV_SINK_MEASURE;
+	const int measure = sink->kind == AGMV_SINK_MEASURE, view = sink->viewed;
 	agmv_file af;
 	const AGMV_MAIN_HEADER* hd = &af.hdr.header;
 	uint32_t nframes, pal[512];
@@ -969,10 +992,11 @@ static int decode_file(const char* filename, u8 img_type, agmv_sink* sink, AGMV_
 	if (err == NO_ERR && !info_only) {
 		/* (a rule of the API, not a dispatch: 4:2:0 chroma cannot lie over an odd frame) */
 		if (measure && (hd->num_of_frames != cap_frames || (AGMV_FMT_IS_YUV(sink->measure.fmt) && ((hd->width | hd->height) & 1)))) err = -3;
-		else if (to && to->filter == AGMV_SCALE_AREA && (to->w > hd->width || to->h > hd->height || (unsigned long long)hd->width * hd->height > (1ull << 24))) err = -4;
+		else if (view && resolve_view(sink, hd, cap_frames) != NO_ERR) err = -4;
+		else if (!view && to && to->filter == AGMV_SCALE_AREA && (to->w > hd->width || to->h > hd->height || (unsigned long long)hd->width * hd->height > (1ull << 24))) err = -4;
 		else if ((err = agmv_file_slurp(&af)) == NO_ERR && bad_geometry((uint32_t)hd->width, (uint32_t)hd->height)) err = INVALID_HEADER_FORMATTING_ERR;
 	}
-	if (err != NO_ERR || info_only) { agmv_file_close(&af); return err; }
+	if (err != NO_ERR || info_only || (sink->viewed && sink->view.count == 0)) { agmv_file_close(&af); return err; }      /* (a view without a frame: nothing to do) */
 	m512 = hd->version == 1 || hd->version == 3;
 	c = open_ctx();
 	if (!c) { agmv_file_close(&af); return gpu_failed("cannot open the GPU"); }
@@ -984,12 +1008,13 @@ static int decode_file(const char* filename, u8 img_type, agmv_sink* sink, AGMV_
 	}
 	nframes = (uint32_t)hd->num_of_frames;
 	if (sink->kind != AGMV_SINK_EXPORT && nframes > cap_frames) nframes = (uint32_t)cap_frames;
+	if (view) nframes = sink->viewed ? sink->view.first + (sink->view.count - 1) * sink->view.step + 1 : sink->view.count;      /* behind the last frame it needs */
 	if (measure && nframes) {
 		sink->measure.d_quality = agmv_hip_malloc_on(c, (size_t)nframes * sizeof(AGMV_FRAME_QUALITY));
 		if (!sink->measure.d_quality) { agmv_file_close(&af); return gpu_failed("result array for the measurement"); }
 	}
 	err = agmv_decode_stream(c, af.image, af.len, af.pos, (uint32_t)hd->width, (uint32_t)hd->height, nframes, hd->version, hd->total_audio_duration != 0,
-	                         batch_frames((size_t)hd->width * hd->height), lz_threads(), sink);
+	                         batch_frames((size_t)hd->width * hd->height), lz_threads(), sink, view ? &g_view_stats : NULL);
 	if (measure && err == NO_ERR) download_quality(c, sink->measure.d_quality, quality, (size_t)*sink->count);
 	if (measure) agmv_hip_free_on(c, sink->measure.d_quality);
 	agmv_file_close(&af);
@@ -1055,6 +1080,40 @@ int AGMV_DecodeFramesTensorDev(const char* filename, void* d_tensor, AGMV_TENSOR
 	const int sized = width != 0 || height != 0;
 	agmv_sink sink = {AGMV_SINK_TENSOR, &decoded, .tensor = {d_tensor, (int)type, table, {(uint32_t)width, (uint32_t)height, sized ? (int)filter : 0}}};
 	const int refused = filename && known_tensor(type, mean, std, table) ? (sized ? target_refused(width, height, filter) : 0) : -1;
+	return refused ? refused : decode_result(decode_file(filename, AGMV_IMG_BMP, &sink, NULL, cap_frames, d_tensor == NULL, info), &decoded);
+}
+
+/* A view of a file (include/agmv.h): the sized decoders with a selection of frames and a window in front of the sink.  view_refused is
+   the -1 class of the view's own fields; NULL is the whole file. */
+static const AGMV_VIEW WHOLE_FILE = {0, 0, 1, 0, 0, 0, 0};
+
+static int view_refused(const AGMV_VIEW* v)
+{
+	return v && (v->step == 0 || (v->width == 0) != (v->height == 0) || (v->width == 0 && (v->x || v->y)));
+}
+
+int AGMV_DecodeViewDev(const char* filename, void* d_frames, AGMV_PIXFMT fmt, u32 width, u32 height, AGMV_SCALE filter, const AGMV_VIEW* view,
+                       u32 cap_frames, AGMV_INFO* info)
+{
+	unsigned long decoded = 0;
+	const int sized = width != 0 || height != 0;
+	agmv_sink sink = {AGMV_SINK_FRAMES, &decoded, .frames = {d_frames, (int)fmt, {(uint32_t)width, (uint32_t)height, sized ? (int)filter : 0}},
+	                  .viewed = 1, .view = view ? *view : WHOLE_FILE};
+	const int refused = filename && known_pixfmt((int)fmt) && !view_refused(view) ? (sized ? target_refused(width, height, filter) : 0) : -1;
+	memset(&g_view_stats, 0, sizeof(g_view_stats));
+	return refused ? refused : decode_result(decode_file(filename, AGMV_IMG_BMP, &sink, NULL, cap_frames, d_frames == NULL, info), &decoded);
+}
+
+int AGMV_DecodeViewTensorDev(const char* filename, void* d_tensor, AGMV_TENSORFMT type, const float mean[3], const float std[3], u32 width, u32 height,
+                             AGMV_SCALE filter, const AGMV_VIEW* view, u32 cap_frames, AGMV_INFO* info)
+{
+	unsigned long decoded = 0;
+	uint32_t table[768];
+	const int sized = width != 0 || height != 0;
+	agmv_sink sink = {AGMV_SINK_TENSOR, &decoded, .tensor = {d_tensor, (int)type, table, {(uint32_t)width, (uint32_t)height, sized ? (int)filter : 0}},
+	                  .viewed = 1, .view = view ? *view : WHOLE_FILE};
+	const int refused = filename && known_tensor(type, mean, std, table) && !view_refused(view) ? (sized ? target_refused(width, height, filter) : 0) : -1;
+	memset(&g_view_stats, 0, sizeof(g_view_stats));
 	return refused ? refused : decode_result(decode_file(filename, AGMV_IMG_BMP, &sink, NULL, cap_frames, d_tensor == NULL, info), &decoded);
 }
 

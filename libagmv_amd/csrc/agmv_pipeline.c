@@ -779,7 +779,8 @@ void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start,
 typedef struct dbatch {
 	unsigned n;
 	uint32_t first;                        /* frame_count of its first frame */
-	u8* h_slab;                            /* pinned [cap][stride] (host LZ stage) */
+	unsigned skip;                         /* a view: its first rows, the frames before g0, do not enter the GPU stage */
+	u8* h_slab;                           /* pinned [cap][stride] (host LZ stage) */
 	uint32_t *h_bpos, *h_out;              /* pinned [cap], [cap][npx] */
 	uint8_t* d_slab;                       /* AGMV_LZ_DECODE_DEVICE: the batch's rows [cap][stride] on the device, their bpos, and */
 	uint32_t* d_bpos;
@@ -806,6 +807,10 @@ typedef struct dpipe {
 	agmv_sink sink;                        /* where the batches go (agmv_pipeline.h); the four facts below are all that is derived from it */
 	uint32_t* d_scaled;                    /* sink_needs_scaled: one batch of scaled XRGB32 frames */
 	void* d_table;                         /* the tensor sink's table on the device, uploaded once per call */
+	uint32_t g0;                           /* a view: the GOP start at which the GPU stage begins, from the fresh state */
+	uint32_t* d_view;                      /* ... one batch of packed windows (sink_view), where the sink does not receive them directly */
+	int restart;                           /* ... the first decoded batch derives from the state before g0: the call runs again from frame 0 */
+	unsigned gpu_frames;                   /* frames through the GPU stage */
 } dpipe;
 
 /* A packed XRGB32 clip at the file's size is decoded straight into its place, and the frame before a batch is the one before it there.
@@ -843,73 +848,128 @@ static void save_task(void* p)
 	free(sa);
 }
 
-/* batch b, decoded at `out`, to the sink on the worker's stream: one launch, behind the box filter's where that goes through d_scaled;
+/* n frames of sw x sh at `out` -- batch b as it was decoded, or the frames and windows of it that a view selects -- to the sink as
+   its frames `at_frame` onwards, on the worker's stream: one launch, behind the box filter's where that goes through d_scaled;
    for EXPORT the download to the slot's pinned frames; nothing for a batch decoded in place */
-static int sink_batch(dpipe* d, const dbatch* b, const uint32_t* out)
+static int sink_batch(dpipe* d, const dbatch* b, const uint32_t* out, uint32_t sw, uint32_t sh, unsigned n, uint32_t at_frame)
 {
 	const agmv_sink* s = &d->sink;
 	const agmv_target* t = agmv_sink_target(s);
-	uint32_t sw = d->w, sh = d->h;                             /* the size of the frames at `out`, the filter still to apply, the target size */
-	int filter = t ? t->filter : 0;
+	int filter = t ? t->filter : 0;                            /* (sw x sh: the size of the frames at `out`) the filter still to apply, the target size */
 	const uint32_t tw = t ? t->w : sw, th = t ? t->h : sh;
-	const size_t at = (size_t)b->first * sink_frame_bytes(s, d->w, d->h);
+	const size_t at = (size_t)at_frame * sink_frame_bytes(s, sw, sh);
 	if (sink_needs_scaled(s)) {
-		if (agmv_hip_scale_area_dev(d->ctx, AGMV_PIXFMT_XRGB32, out, sw, sh, b->n, tw, th, d->d_scaled, d->stream)) return -1;
+		if (agmv_hip_scale_area_dev(d->ctx, AGMV_PIXFMT_XRGB32, out, sw, sh, n, tw, th, d->d_scaled, d->stream)) return -1;
 		out = d->d_scaled; sw = tw; sh = th; filter = 0;
 	}
 	switch (s->kind) {
 	case AGMV_SINK_EXPORT:
-		return agmv_hip_memcpy_async(d->ctx, b->h_out, out, d->npx * 4 * b->n, 1, d->stream);
+		return agmv_hip_memcpy_async(d->ctx, b->h_out, out, d->npx * 4 * n, 1, d->stream);
 	case AGMV_SINK_MEASURE:
-		return agmv_hip_measure_frames_async(d->ctx, out, s->measure.fmt, (const u8*)s->measure.d_ref + at, sw, sh, b->n,
-		                                     (u8*)s->measure.d_quality + sizeof(AGMV_FRAME_QUALITY) * (size_t)b->first, d->stream);
+		return agmv_hip_measure_frames_async(d->ctx, out, s->measure.fmt, (const u8*)s->measure.d_ref + at, sw, sh, n,
+		                                     (u8*)s->measure.d_quality + sizeof(AGMV_FRAME_QUALITY) * (size_t)at_frame, d->stream);
 	case AGMV_SINK_TENSOR:
-		return agmv_hip_tensor_from_xrgb_async(d->ctx, s->tensor.type, out, sw, sh, b->n, filter, tw, th, d->d_table, (u8*)s->tensor.d_dst + at, d->stream);
+		return agmv_hip_tensor_from_xrgb_async(d->ctx, s->tensor.type, out, sw, sh, n, filter, tw, th, d->d_table, (u8*)s->tensor.d_dst + at, d->stream);
 	default: {
 		void* dst = (u8*)s->frames.d_dst + at;
-		if (filter == AGMV_SCALE_AREA) return agmv_hip_scale_area_dev(d->ctx, AGMV_PIXFMT_XRGB32, out, sw, sh, b->n, tw, th, (uint32_t*)dst, d->stream);
-		if (filter) return agmv_hip_scale_frames_async(d->ctx, filter, out, sw, sh, b->n, s->frames.fmt, tw, th, dst, d->stream);
-		return sink_in_place(s) ? 0 : agmv_fmt_from_xrgb(d->ctx, s->frames.fmt, tw, th, out, b->n, dst, d->stream);      /* XRGB32 to the caller's layout */
+		if (filter == AGMV_SCALE_AREA) return agmv_hip_scale_area_dev(d->ctx, AGMV_PIXFMT_XRGB32, out, sw, sh, n, tw, th, (uint32_t*)dst, d->stream);
+		if (filter) return agmv_hip_scale_frames_async(d->ctx, filter, out, sw, sh, n, s->frames.fmt, tw, th, dst, d->stream);
+		return sink_in_place(s) ? 0 : agmv_fmt_from_xrgb(d->ctx, s->frames.fmt, tw, th, out, n, dst, d->stream);      /* XRGB32 to the caller's layout */
 	}
 	}
+}
+
+uint32_t agmv_view_length(uint32_t first, uint32_t step, uint32_t count, uint32_t nframes)
+{
+	const uint32_t n = first < nframes ? (nframes - first - 1) / step + 1 : 0;
+	return count && count < n ? count : n;
+}
+
+uint32_t agmv_view_in_batch(uint32_t first, uint32_t step, uint32_t count, uint32_t batch_first, uint32_t batch_n, uint32_t* row, uint32_t* index)
+{
+	const uint64_t end = (uint64_t)batch_first + batch_n;       /* the view's frame j is frame first + j * step of the file */
+	const uint64_t j0 = batch_first > first ? ((uint64_t)(batch_first - first) + step - 1) / step : 0, f0 = first + j0 * step;
+	uint64_t j1;
+	if (batch_n == 0 || f0 >= end || (count && j0 >= count)) return 0;
+	j1 = (end - 1 - first) / step;                              /* the last j of the batch, then of the view */
+	if (count && j1 >= count) j1 = count - 1;
+	*row = (uint32_t)(f0 - batch_first); *index = (uint32_t)j0;
+	return (uint32_t)(j1 - j0 + 1);
+}
+
+/* the nd frames decoded at `out`, the first of them frame f0 of the file, to the sink of a view: the frames the view selects,
+   packed with their windows by one launch, then sunk as a batch of a file of the window's size.  Two shortcuts: consecutive full
+   frames are sunk from where they lie, and a packed XRGB32 destination at the window's size receives the copy itself. */
+static int sink_view(dpipe* d, const dbatch* b, const uint32_t* out, uint32_t f0, unsigned nd)
+{
+	const AGMV_VIEW* v = &d->sink.view;
+	const int packed = sink_in_place(&d->sink), whole = v->width == d->w && v->height == d->h;
+	const size_t wpx = (size_t)v->width * v->height;
+	uint32_t row, index, *win;
+	const uint32_t len = agmv_view_in_batch(v->first, v->step, v->count, f0, nd, &row, &index);
+	if (!len) return 0;
+	*d->sink.count += len;                                     /* (this thread alone writes it during a view; it is read behind the join) */
+	win = packed ? (uint32_t*)d->sink.frames.d_dst + index * wpx : d->d_view;
+	if (whole && (v->step == 1 || len == 1)) {
+		const uint32_t* src = out + (size_t)row * d->npx;
+		return packed ? agmv_hip_memcpy_async(d->ctx, win, src, wpx * 4 * len, 2, d->stream) : sink_batch(d, b, src, d->w, d->h, len, index);
+	}
+	if (agmv_hip_view_frames_async(d->ctx, out, d->w, d->h, row, v->step, len, v->x, v->y, v->width, v->height, win, d->stream)) return -1;
+	return packed ? 0 : sink_batch(d, b, win, v->width, v->height, len, index);
 }
 
 static void* dworker_main(void* p)
 {
 	dpipe* d = (dpipe*)p;
-	const int direct = sink_in_place(&d->sink), to_bmp = d->sink.kind == AGMV_SINK_EXPORT;
+	const int viewed = d->sink.viewed, direct = sink_in_place(&d->sink) && !viewed, to_bmp = d->sink.kind == AGMV_SINK_EXPORT;
 	unsigned id, prev_n = 0;
 	int have_state = 0;
 	for (id = 0;; id++) {
 		dbatch* b = &d->slot[id % d->nslots];
 		uint32_t* out;
 		const uint32_t* prev;
-		const uint8_t* bits = b->d_slab ? b->d_slab : d->d_bits;
-		const uint32_t* bpos = b->d_slab ? b->d_bpos : d->d_bpos;
-		unsigned k;
+		const uint8_t* bits;
+		const uint32_t* bpos;
+		unsigned k, skip, n;
+		uint32_t first;
 		int last_i = -1;
 		pthread_mutex_lock(&d->mu);
 		while (!(id < d->nfilled) && !d->closing) pthread_cond_wait(&d->cv, &d->mu);
 		if (id >= d->nfilled) { pthread_mutex_unlock(&d->mu); break; }
 		pthread_mutex_unlock(&d->mu);
-		out = direct ? (uint32_t*)d->sink.frames.d_dst + (size_t)b->first * d->npx : d->d_out[id & 1];
+		skip = b->skip; n = b->n - skip; first = b->first + skip;    /* (a view's first batch: from the GOP start g0 on; else the whole batch) */
+		bits = b->d_slab ? b->d_slab + (size_t)skip * d->stride : d->d_bits;
+		bpos = b->d_slab ? b->d_bpos + skip : d->d_bpos;
+		out = direct ? (uint32_t*)d->sink.frames.d_dst + (size_t)first * d->npx : d->d_out[id & 1];
 		prev = !have_state ? NULL : direct ? out - d->npx : d->d_out[(id - 1) & 1] + (size_t)(prev_n - 1) * d->npx;
 		if (b->d_slab) {                       /* the LZ stage left the rows on the device: wait for their commit, on the device */
 			if (agmv_hip_stream_wait_event(d->ctx, d->stream, b->ready)) goto fail;
-		} else if (agmv_hip_memcpy_async(d->ctx, d->d_bits, b->h_slab, d->stride * b->n, 0, d->stream) ||
-		           agmv_hip_memcpy_async(d->ctx, d->d_bpos, b->h_bpos, 4 * (size_t)b->n, 0, d->stream))
+		} else if (agmv_hip_memcpy_async(d->ctx, d->d_bits, b->h_slab + (size_t)skip * d->stride, d->stride * n, 0, d->stream) ||
+		           agmv_hip_memcpy_async(d->ctx, d->d_bpos, b->h_bpos + skip, 4 * (size_t)n, 0, d->stream))
 			goto fail;
-		if (agmv_hip_decode_bitstreams_dev(d->ctx, bits, d->stride, bpos, b->n, d->w, d->h, b->first, d->d_nent, out, prev,
+		if (agmv_hip_decode_bitstreams_dev(d->ctx, bits, d->stride, bpos, n, d->w, d->h, first, d->d_nent, out, prev,
 		                                   have_state ? d->d_iframe : NULL, d->stream))
 			goto fail;
+		d->gpu_frames += n;
+		if (!have_state && d->g0) {            /* a view that starts inside the file: is this batch a function of its own streams alone? */
+			const int dependent = agmv_hip_decode_prior_dependent(d->ctx, d->w, d->h, d->stream);
+			if (dependent < 0) goto fail;
+			if (dependent) {
+				pthread_mutex_lock(&d->mu);
+				d->restart = d->failed = 1;        /* (failed: what stops the batch loop) */
+				pthread_cond_broadcast(&d->cv);
+				pthread_mutex_unlock(&d->mu);
+				break;
+			}
+		}
 		/* decoder state for the next batch stays on the device: img_data = the last frame (read in place from this batch's
 		   output), iframe = the last I-frame of the batch (src/agmv_decode.c:401-405) */
-		for (k = 0; k < b->n; k++) if (((b->first + k) & 3u) == 0) last_i = (int)k;
+		for (k = 0; k < n; k++) if (((first + k) & 3u) == 0) last_i = (int)k;
 		if (!have_state && last_i < 0 && agmv_hip_memset_async(d->ctx, d->d_iframe, 0, d->npx * 4, d->stream)) goto fail;
 		if (last_i >= 0 && agmv_hip_memcpy_async(d->ctx, d->d_iframe, out + (size_t)last_i * d->npx, d->npx * 4, 2, d->stream)) goto fail;
-		if (sink_batch(d, b, out) || agmv_hip_stream_sync(d->ctx, d->stream)) goto fail;
+		if ((viewed ? sink_view(d, b, out, first, n) : sink_batch(d, b, out, d->w, d->h, n, first)) || agmv_hip_stream_sync(d->ctx, d->stream)) goto fail;
 		have_state = 1;
-		prev_n = b->n;
+		prev_n = n;
 		pthread_mutex_lock(&d->mu);
 		if (!to_bmp) b->filled = 0;                        /* the frames are where they belong: the slot is free again */
 		else { b->decoded = 1; b->saves_left = b->n; }
@@ -1123,11 +1183,17 @@ static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, dchunk* c, const u8* fil
    those of the reference's ONE persistent buffer: the host stage takes them from `persist` in frame order, which then
    receives the frame.  The frames go to `sink` (agmv_pipeline.h), whose count advances by the frames decoded.  Whatever the sink, a
    batch is decoded at the file's size; only a packed XRGB32 clip of that size receives it in place (sink_in_place), every other
-   sink -- another layout, a target size, a tensor, the BMP export, the measurement -- gets it from the double buffer by sink_batch. */
-int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
-                       int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink)
+   sink -- another layout, a target size, a tensor, the BMP export, the measurement -- gets it from the double buffer by sink_batch.
+   A view (sink->viewed; nframes then ends behind the last frame it needs) is always decoded into the double buffer and leaves it
+   through sink_view.  Its LZ stage runs from frame 0 like any other, because only that keeps the persistent buffer right; its GPU
+   stage starts at the GOP start g0 from the fresh state: a batch wholly before g0 is not handed to the worker and its slot is
+   filled again, the batch that holds g0 is decoded from row g0 - first on.  *restart = 1 (and NO_ERR) when the worker found that
+   the first decoded batch derives from the state before it: nothing that run delivered counts, and the caller runs g0 = 0. */
+static int decode_run(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
+                      int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink, uint32_t g0, AGMV_VIEW_STATS* stats, int* restart)
 {
-	const int buffered = !sink_in_place(sink), to_bmp = sink->kind == AGMV_SINK_EXPORT;
+	const int viewed = sink->viewed, buffered = !sink_in_place(sink) || viewed, to_bmp = sink->kind == AGMV_SINK_EXPORT;
+	const int view_packs = viewed && !sink_in_place(sink) && !(sink->view.step == 1 && sink->view.width == w && sink->view.height == h);
 	dpipe d;
 	dlz z;
 	const char* lzv = getenv("AGMV_LZ_DECODE_DEVICE");     /* opt-in: the LZ stage on the GPU (read when a decode starts) */
@@ -1142,7 +1208,7 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	memset(&d, 0, sizeof(d));
 	memset(&z, 0, sizeof(z));
 	d.ctx = ctx; d.w = w; d.h = h; d.npx = npx; d.stride = (cap + 255) & ~(size_t)255;
-	d.cap = cap_frames; d.nslots = 3; d.sink = *sink;
+	d.cap = cap_frames; d.nslots = 3; d.sink = *sink; d.g0 = g0;
 	pthread_mutex_init(&d.mu, NULL);
 	pthread_cond_init(&d.cv, NULL);
 	d.slot = (dbatch*)calloc(d.nslots, sizeof(dbatch));
@@ -1155,6 +1221,7 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	d.d_out[1] = buffered ? (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap) : NULL;
 	d.d_iframe = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4);
 	if (sink_needs_scaled(sink) && !(d.d_scaled = (uint32_t*)agmv_hip_malloc_on(ctx, (size_t)agmv_sink_target(sink)->w * agmv_sink_target(sink)->h * 4 * d.cap))) goto out;
+	if (view_packs && !(d.d_view = (uint32_t*)agmv_hip_malloc_on(ctx, (size_t)sink->view.width * sink->view.height * 4 * d.cap))) goto out;
 	if (sink->kind == AGMV_SINK_TENSOR) {                  /* 3 x 256 elements, once per call */
 		const size_t bytes = agmv_hip_tensor_frame_bytes(sink->tensor.type, 256);
 		d.d_table = agmv_hip_malloc_on(ctx, bytes);
@@ -1219,8 +1286,10 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 			}
 		}
 		if (!n) break;
+		if (viewed && done + n <= g0) { done += n; continue; }     /* wholly before the view's GOP: the LZ stage was all it needed */
 		b->n = n; b->first = done; b->name0 = *sink->count + 1;
-		*sink->count += n;
+		b->skip = viewed && g0 > done ? g0 - done : 0;
+		if (!viewed) *sink->count += n;                            /* (a view's frames are counted where they are selected: sink_view) */
 		pthread_mutex_lock(&d.mu);
 		b->filled = 1;
 		d.nfilled = ++id;
@@ -1237,8 +1306,12 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
 	for (i = 0; i < d.nslots; i++) while (d.slot[i].decoded && !d.failed) pthread_cond_wait(&d.cv, &d.mu);
 	pthread_mutex_unlock(&d.mu);
 	agmv_pool_stop(d.pool);
-	if (d.failed) rc = MEMORY_CORRUPTION_ERR;
+	if (d.restart) *restart = 1;
+	else if (d.failed) rc = MEMORY_CORRUPTION_ERR;
 	if (lz_dev) TRACE("decode: LZ stage device, %u frames in %u batches, %.3f s\n", (unsigned)done, z.batches, z.secs);
+	if (viewed) TRACE("decode: view from GOP start %u, %u frames through the LZ stage, %u through the GPU stage%s\n", (unsigned)g0, (unsigned)done, d.gpu_frames,
+	                  d.restart ? ", which depend on the state before them: again from frame 0" : "");
+	if (stats) { stats->lz_frames += done; stats->gpu_frames += d.gpu_frames; }
 out:
 	for (i = 0; i < d.nslots; i++) {
 		agmv_hip_host_free(d.slot[i].h_slab); agmv_hip_host_free(d.slot[i].h_bpos); agmv_hip_host_free(d.slot[i].h_out);
@@ -1247,10 +1320,28 @@ out:
 	dlz_close(&z);
 	agmv_hip_free_on(ctx, d.d_bits); agmv_hip_free_on(ctx, d.d_bpos); agmv_hip_free_on(ctx, d.d_nent);
 	agmv_hip_free_on(ctx, d.d_out[0]); agmv_hip_free_on(ctx, d.d_out[1]); agmv_hip_free_on(ctx, d.d_iframe); agmv_hip_free_on(ctx, d.d_scaled);
-	agmv_hip_free_on(ctx, d.d_table);
+	agmv_hip_free_on(ctx, d.d_table); agmv_hip_free_on(ctx, d.d_view);
 	agmv_hip_stream_destroy(ctx, d.stream);
 	free(d.slot); free(persist); free(chunks); free(jobs);
 	pthread_mutex_destroy(&d.mu);
 	pthread_cond_destroy(&d.cv);
+	return rc;
+}
+
+/* decode_run, and for a view that starts inside the file and cannot be trusted from the fresh state the same call again from
+   frame 0, which writes the same destinations.  *stats (may be NULL) receives what the run that delivered did. */
+int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
+                       int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink, AGMV_VIEW_STATS* stats)
+{
+	const unsigned long count0 = *sink->count;
+	int restart = 0, rc;
+	if (stats) memset(stats, 0, sizeof(*stats));
+	rc = decode_run(ctx, file, len, pos, w, h, nframes, ver, has_audio, cap_frames, threads, sink, sink->viewed ? sink->view.first & ~3u : 0, stats, &restart);
+	if (rc == NO_ERR && restart) {
+		*sink->count = count0;
+		if (stats) memset(stats, 0, sizeof(*stats));               /* (how far the LZ stage of the run given up had come is a matter of timing) */
+		rc = decode_run(ctx, file, len, pos, w, h, nframes, ver, has_audio, cap_frames, threads, sink, 0, stats, &restart);
+	}
+	if (stats) { stats->restarts = (unsigned)restart; stats->delivered = rc == NO_ERR ? (unsigned)(*sink->count - count0) : 0; }
 	return rc;
 }

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "agmv_hip.h"
+#include "agmv_hip_view.h"
 #include "agmv_internal.h"
 
 typedef struct agmv_pool agmv_pool;
@@ -81,6 +82,10 @@ void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start,
    nowhere; frame k is measured against frame k of the clip d_ref in fmt, which is only read, and its AGMV_FRAME_QUALITY lands in d_quality[k].
    A target with a filter (an AGMV_SCALE) scales every frame to w x h on its way; filter 0 is the file's size, and w, h are not read. */
 typedef struct agmv_target { uint32_t w, h; int filter; } agmv_target;
+/* A FRAMES or TENSOR sink with `viewed` set takes a view of the file (AGMV_VIEW of include/agmv.h), resolved against the header:
+   view.count >= 1 is the number of frames it delivers, view.width x view.height the window's own size.  Frame j of the view goes
+   where frame j of a file goes; target, layout and normalisation apply to the window as to a file of that size; *count advances by
+   the frames delivered.  Without `viewed` nothing of `view` is read and the sink is what it was before views existed. */
 typedef struct agmv_sink {
 	enum { AGMV_SINK_EXPORT, AGMV_SINK_FRAMES, AGMV_SINK_TENSOR, AGMV_SINK_MEASURE } kind;
 	unsigned long* count;
@@ -89,7 +94,16 @@ typedef struct agmv_sink {
 		struct { void* d_dst; int type; const void* table; agmv_target to; } tensor;
 		struct { const void* d_ref; int fmt; void* d_quality; } measure;
 	};
+	int viewed;
+	AGMV_VIEW view;
 } agmv_sink;
+
+/* The frames of a view in a file of nframes frames: first, first + step, ... below nframes, at most `count` of them (0: no bound). */
+uint32_t agmv_view_length(uint32_t first, uint32_t step, uint32_t count, uint32_t nframes);
+/* The one statement of which frames of a batch belong to a view.  The frames [batch_first, batch_first + batch_n) of the file that
+   are frames first + j * step of the view, j < count (count 0: no bound), are an arithmetic progression of difference `step`:
+   returns its length, and for a length above 0 *row = the index in the batch of its first frame and *index = that frame's j. */
+uint32_t agmv_view_in_batch(uint32_t first, uint32_t step, uint32_t count, uint32_t batch_first, uint32_t batch_n, uint32_t* row, uint32_t* index);
 
 /* the target of a sink that scales, else NULL */
 static inline const agmv_target* agmv_sink_target(const agmv_sink* s)
@@ -99,7 +113,7 @@ static inline const agmv_target* agmv_sink_target(const agmv_sink* s)
 }
 
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
-                       int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink);
+                       int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink, AGMV_VIEW_STATS* stats);
 
 /* the AGAC payloads of a file image (its first chunk at or behind pos) back to back, at most cap bytes; returns their number */
 size_t agmv_gather_audio(const u8* file, size_t len, size_t pos, uint32_t nframes, u8* out, size_t cap);

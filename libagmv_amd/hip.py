@@ -1,4 +1,4 @@
-"""ctypes binding of include/agmv_hip.h (the signatures are abi.HIP).
+"""ctypes binding of include/agmv_hip.h (the signatures are abi.HIP) and include/agmv_hip_view.h (abi.HIP_VIEW).
 
 The product is the shared library; this module only marshals pointers.  torch is used for
 device memory and streams (plumbing).  Every failure is loud: a missing library raises
@@ -51,6 +51,7 @@ def load_library(path=None):
         raise HipUnavailable("cannot load %s: %s" % (p, e))
     # only an explicitly named other build of the same source may lack symbols; the default library has them all
     abi.bind(L, abi.HIP, missing_ok=path is not None)
+    abi.bind(L, abi.HIP_VIEW, missing_ok=path is not None)
     _libs[p] = L
     return L
 
@@ -767,6 +768,24 @@ class AgmvHip:
             raise ValueError("scale_frames_async: out must be a contiguous CUDA tensor of >= %d bytes" % (n_frames * fb))
         s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
         self._ck(self.L.agmv_hip_scale_frames_async(self.ctx, int(filt), src.data_ptr(), w, h, n_frames, fmt, dst_w, dst_h, out.data_ptr(), s))
+        return out
+
+    # ------------------------------------------------------------------ a view of a decoded clip (agmv_hip_view_frames_async of include/agmv_hip_view.h)
+    def view_frames_async(self, src, w, h, first, step, count, x, y, win_w, win_h, out=None, stream=None):
+        """src: int32 CUDA tensor of whole frames of w x h pixels -> int32 [count, win_h, win_w]: the window win_w x win_h at (x, y) of
+        the frames first, first + step, ... (count of them, all inside src), whole words copied as they are, or `out`, a contiguous
+        CUDA int32 tensor (or view at any element offset) of at least that many words (agmv_hip_view_frames_async) on `stream` (a
+        torch stream; None = torch's current one).  Nothing waits."""
+        import torch
+        w, h, first, step, count, x, y, win_w, win_h = (int(v) for v in (w, h, first, step, count, x, y, win_w, win_h))
+        if step < 1 or count < 0 or first < 0:
+            raise ValueError("view_frames_async: first >= 0, step >= 1 and count >= 0 are needed, got %d, %d, %d" % (first, step, count))
+        _check_vec("view_frames_async: src", src, (first + (count - 1) * step + 1) * w * h if count else 0)
+        if out is None:
+            out = torch.empty((count, win_h, win_w), dtype=torch.int32, device=src.device)
+        _check_vec("view_frames_async: out", out, count * win_w * win_h)
+        s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self._ck(self.L.agmv_hip_view_frames_async(self.ctx, src.data_ptr(), w, h, first, step, count, x, y, win_w, win_h, out.data_ptr(), s))
         return out
 
     # ------------------------------------------------------------------ normalised float tensor clips (AGMV_TENSORFMT of include/agmv.h)

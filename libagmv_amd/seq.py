@@ -248,7 +248,76 @@ def _decode_target(size, scale):
     return DECODE_SCALE[scale], size[0], size[1]
 
 
-def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False, size=None, scale="bilinear", mean=None, std=None):
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _decode_selection(frames, crop):
+    """decode_frames' frames= and crop= checked -> (a range or a slice or None, crop); touches neither the library nor the device"""
+    if isinstance(frames, tuple):
+        if not (len(frames) == 3 and all(_is_int(v) for v in frames) and frames[2] >= 1):
+            raise ValueError("decode_frames: frames as a tuple must be (start, stop, step), three ints with step >= 1, got %r" % (frames,))
+        frames = range(*frames)
+    if isinstance(frames, range):
+        if frames.step < 1 or frames.start < 0:
+            raise ValueError("decode_frames: frames must start at 0 or later and step forwards, got %r" % (frames,))
+    elif isinstance(frames, slice):
+        if not (all(v is None or _is_int(v) for v in (frames.start, frames.stop, frames.step)) and (frames.step is None or frames.step >= 1)):
+            raise ValueError("decode_frames: frames as a slice needs ints and a step >= 1, got %r" % (frames,))
+    elif frames is not None:
+        raise ValueError("decode_frames: frames must be a range, a slice or a tuple (start, stop, step), got %r" % (frames,))
+    if crop is not None and not (isinstance(crop, (tuple, list)) and len(crop) == 4 and all(_is_int(v) for v in crop)
+                                 and crop[0] >= 0 and crop[1] >= 0 and crop[2] > 0 and crop[3] > 0):
+        raise ValueError("decode_frames: crop must be (top, left, height, width), four ints with a height and a width above 0, got %r" % (crop,))
+    return frames, crop
+
+
+def _decode_view(path, v, tensor, target, scale, frames, crop, fmt):
+    """decode_frames with frames= or crop=: AGMV_DecodeViewDev, or for a tensor clip (`tensor` of _tensor_clip) AGMV_DecodeViewTensorDev"""
+    import torch
+    L = load_library()
+    info = AGMV_INFO()
+    if tensor is not None:
+        v, m, s = tensor[0], tensor[4], tensor[5]
+        call, head = "AGMV_DecodeViewTensorDev", lambda dst, *rest: L.AGMV_DecodeViewTensorDev(os.fsencode(path), dst, v, m, s, *rest)
+    else:
+        call, head = "AGMV_DecodeViewDev", lambda dst, *rest: L.AGMV_DecodeViewDev(os.fsencode(path), dst, v, *rest)
+    rc = head(None, 0, 0, 0, None, 0, C.byref(info))
+    if rc < 0:
+        raise (ValueError if rc == -1 else RuntimeError)("%s(%s): %s" % (call, path, "the normalisation is refused" if rc == -1 else "Error %d" % -rc))
+    n, h, w = info.number_of_frames, info.height, info.width
+    sel = range(n) if frames is None else range(*frames.indices(n)) if isinstance(frames, slice) else range(frames.start, min(frames.stop, n), frames.step)
+    view = abi.AGMV_VIEW(sel.start if len(sel) else 0, len(sel), sel.step, 0, 0, 0, 0)
+    if crop is not None:
+        top, left, ch, cw = crop
+        if top + ch > h or left + cw > w:
+            raise ValueError("decode_frames: crop %r does not lie inside the %d x %d frames of %s" % (tuple(crop), w, h, path))
+        view.x, view.y, view.width, view.height = left, top, cw, ch
+        h, w = ch, cw
+    filt, tw, th = 0, 0, 0
+    if target is not None:
+        filt, th, tw = target
+        if filt == DECODE_SCALE["area"] and (th > h or tw > w):
+            raise ValueError("decode_frames: scale=\"area\" only scales down, the frames taken from %s are %d x %d and size= asks for %d x %d" % (path, w, h, tw, th))
+        h, w = th, tw
+    if tensor is not None:
+        shape, dtype = (len(sel), 3, h, w), _tensor_dtypes()[v]
+    else:
+        if v & 0xFF in YUVFMT.values() and (h % 2 or w % 2):
+            raise ValueError("decode_frames: fmt %r needs frames of even width and height, got %d x %d" % (fmt, w, h))
+        k = len(sel)
+        shape = {1: (k, h, w), 2: (k, h, w, 3), 3: (k, h, w, 3), 4: (k, h, w, 4), 5: (k, 3, h, w), 16: (k, h * 3 // 2, w), 17: (k, h * 3 // 2, w)}[v & 0xFF]
+        dtype = torch.int32 if v == 1 else torch.uint8
+    out = torch.empty(shape, dtype=dtype, device=_device())
+    if len(sel) == 0:
+        return out, info
+    rc = head(out.data_ptr(), tw, th, filt, C.byref(view), len(sel), None)
+    if rc < 0:
+        raise RuntimeError("%s(%s, frames %r, crop %r, %d x %d, scale %r): Error %d" % (call, path, sel, crop, w, h, scale, -rc))
+    return out[:rc], info
+
+
+def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False, size=None, scale="bilinear", mean=None, std=None, frames=None, crop=None):
     """-> (CUDA tensor of the file's frames on the library's device in the layout `fmt`: int32 [n, h, w] of 0x00RRGGBB for "xrgb32",
     uint8 [n, h, w, 3] / [n, h, w, 4] / [n, 3, h, w] for the byte formats, uint8 [n, h * 3 / 2, w] for "nv12" and "i420" (a file
     of even width and height; yuv and full_range as for encode_frames); AGMV_INFO of the header).  size=(h, w), in tensor order,
@@ -258,15 +327,25 @@ def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False, size=None, sca
     file's size -- and the AGMV_INFO still carries the file's own size.
     fmt "f32" / "f16" / "bf16" gives a model's input: a float32 / float16 / bfloat16 [n, 3, h, w] tensor, every byte v of channel
     c as (v / 255 - mean[c]) / std[c] (mean= and std=: a number or three; defaults 0 and 1), written by the sink in the same
-    launch that scales (AGMV_DecodeFramesTensorDev of include/agmv.h: exact, through a table)."""
+    launch that scales (AGMV_DecodeFramesTensorDev of include/agmv.h: exact, through a table).
+    frames= and crop= decode a view of the file (AGMV_DecodeViewDev / AGMV_DecodeViewTensorDev of include/agmv.h): frames is a range,
+    a slice (resolved against the file's frame count) or a tuple (start, stop, step), steps >= 1 only; crop=(top, left, height, width),
+    in tensor order, is a window of every frame, which must lie inside it.  Frame j of the result is the window of frame
+    frames[j] of the full decode; layout, size=, scale= and the normalisation apply to the window as to a file of that size, and the
+    tensor holds as many frames as the selection has inside the file -- none, without a decode, for an empty one."""
     import torch
     target = _decode_target(size, scale)
     tensor = _tensor_clip(None, fmt, mean, std, "decode_frames")
+    frames, crop = _decode_selection(frames, crop)
     if tensor is not None:
         if yuv is not None or full_range:
             raise ValueError("decode_frames: yuv= and full_range= belong to fmt \"nv12\" and \"i420\", not to fmt %r" % (fmt,))
+        if frames is not None or crop is not None:
+            return _decode_view(path, None, tensor, target, scale, frames, crop, fmt)
         return _decode_tensor(path, tensor, target, scale)
     v = _fmt_value("decode_frames", fmt, yuv, full_range)
+    if frames is not None or crop is not None:
+        return _decode_view(path, v, None, target, scale, frames, crop, fmt)
     L = load_library()
     info = AGMV_INFO()
     rc = L.AGMV_DecodeFramesFmtDev(os.fsencode(path), None, v, 0, C.byref(info))
