@@ -378,6 +378,39 @@ void AGMV_SetPaletteRefine(unsigned iterations);
    AGMV_EncodeFrame (one frame, FILE*) is not affected.  With AGMV_TRACE in the environment the strength is printed. */
 void AGMV_SetDither(unsigned strength);
 
+/* Temporal stabilisation: blocks of a P-frame that differ from their GOP's I-frame by no more than the source's own noise receive
+   the I-frame's pixels, before the encoder quantises them.  Opt-in; the file format does not change.  The encoder makes a block a
+   one-byte COPY only when 13 of its 16 palette colours lie within +-2 of the I-frame's at the same pixel; a source whose pixels
+   move by two or three levels from frame to frame (a camera, temporal dither, model output) loses that, and this gives it back.
+   The rule acts on a batch of XRGB32 frames with frame counts fc = first_fc + k, in place, in integers only:
+     anchor    of frame k is frame k - (fc & 3) of the same batch: the I-frame of its GOP, by the encoder's own frame_count % 4
+               rule.  Frames with fc & 3 == 0 are never changed; frames whose anchor lies before the batch are never changed.
+     block     4x4 pixels, aligned to the frame; w and h are multiples of 4.
+     d         the 48 absolute channel differences between a block and the anchor's block at the same place, over bits 0 .. 23
+               only.
+     s         the strength, 1 .. 64.
+       still     = max(d) <= s  and  sum(d) <= 12 * s          (a mean difference of at most s / 4)
+       a still block receives the anchor's 16 pixels & 0x00FFFFFF;
+       any other block keeps every bit it had, bits 24 .. 31 included.
+   What follows: the result is idempotent (a replaced block differs by 0 and is replaced by the same words again); a replaced
+   block is a COPY block whatever the palette; I-frames, and with them everything the palette is built from, are untouched; a GOP
+   depends on nothing outside itself, so batches and devices need no exchange.  agmv_hip_stabilise_frames_async of
+   include/agmv_hip_stabilise.h is the kernel.
+   AGMV_SetStabilise sets the strength for the sequence encoders (all three BMP drivers and every AGMV_EncodeFrames*Dev, from every
+   pixel layout and with a scale): 0 = not set, then env AGMV_STABILISE decides (1 .. 64, anything else is off), and without it the
+   stabilisation is off and every file is what it was without this knob, launch for launch; values above 64 count as 64.  The knob
+   is read when a sequence is opened.  What is stabilised is exactly what the encoder would have seen, frame by frame, PDIFS
+   midpoints included, and BEFORE the dither: the dither is positional, so equal blocks stay equal and COPY survives both.  The
+   palette's histogram, the palette refinement and the adaptive schedule's similarity counts read the source as it is.
+   AGMV_EncodeFrame (one frame, FILE*) is not affected.
+   AGMV_GetStabiliseStats reports the last sequence encode of this process: examined = the blocks of the P-frames that had
+   their anchor in their batch, replaced = those that were replaced, summed over the GPU workers and devices (each worker owns one
+   device counter, downloaded once when the sequence closes).  Both are zero when the knob was off.  With AGMV_TRACE in the
+   environment the strength and the two counts are printed. */
+typedef struct AGMV_STABILISE_STATS { unsigned long long examined, replaced; } AGMV_STABILISE_STATS;
+void AGMV_SetStabilise(unsigned strength);
+void AGMV_GetStabiliseStats(AGMV_STABILISE_STATS* out);
+
 /* Sequences from and to frames in GPU memory: the .agmv files of the three BMP drivers without the BMPs.
    d_frames is device memory of the library's own device (env AGMV_DEVICE, default 0; AGMV_DEVICES is not consulted),
    [num_of_frames][height][width] pixels of 4 bytes, 0x00RRGGBB (bits >= 24 are ignored).
@@ -633,7 +666,7 @@ typedef enum AGMV_PCMFMT { AGMV_PCM_S16 = 1, AGMV_PCM_U8 = 2, AGMV_PCM_F32P = 3 
 int AGMV_SetAudioDev(const void* d_pcm, AGMV_PCMFMT fmt, u32 samples_per_channel, u32 sample_rate, u16 channels);
 int AGMV_DecodeAudioDev(const char* filename, void* d_pcm, AGMV_PCMFMT fmt, u32 cap_samples, AGMV_INFO* info);
 
-/* Measuring a decoded clip: what a lossy knob (the quality level, the palette refinement, the dither, a scale) did to the pixels,
+/* Measuring a decoded clip: what a lossy knob (the quality level, the palette refinement, the dither, the stabilisation, a scale) did to the pixels,
    computed where the frames are.  Two clips of n frames of w x h pixels, w and h multiples of 4: the TEST clip is packed XRGB32
    (what the decoder produces; bits >= 24 are ignored), the REFERENCE clip is in any AGMV_PIXFMT layout, YUV flags included; a YUV
    reference is compared as the XRGB32 clip it stands for by the reading rule above.  Per frame and per channel c (0 = R, 1 = G,

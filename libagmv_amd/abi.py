@@ -1,5 +1,5 @@
 """The public C signatures, stated once: the structures of include/agmv.h that Python passes, every function of
-include/agmv_hip.h (HIP) and of include/agmv_hip_view.h (HIP_VIEW) and every function of include/agmv.h that Python calls on libagmv.so (AGMV), as
+include/agmv_hip.h (HIP), of include/agmv_hip_view.h (HIP_VIEW) and of include/agmv_hip_stabilise.h (HIP_STABILISE) and every function of include/agmv.h that Python calls on libagmv.so (AGMV), as
 name -> (restype, (argtypes...)).  bind() sets them on a loaded library.  tests/test_abi.py checks both tables and the
 structures against the headers.  ctypes only, and no library is loaded here: the test children import this module the
 way a C host would include the headers."""
@@ -32,10 +32,14 @@ class AGMV_VIEW_STATS(Structure):
     _fields_ = [("lz_frames", c_uint), ("gpu_frames", c_uint), ("delivered", c_uint), ("restarts", c_uint)]
 
 
+class AGMV_STABILISE_STATS(Structure):
+    _fields_ = [("examined", c_ulonglong), ("replaced", c_ulonglong)]
+
+
 # vp: any pointer but the five below and `const char*`; ul: the header's u32; the enums and Bool are c_int
 vp, sz, u32, u64, ul = c_void_p, c_size_t, c_uint32, c_uint64, c_ulong
 INFO_P, QUALITY_P, ENTRY_P = POINTER(AGMV_INFO), POINTER(AGMV_FRAME_QUALITY), POINTER(AGMV_ENTRY)
-VIEW_P, VIEW_STATS_P = POINTER(AGMV_VIEW), POINTER(AGMV_VIEW_STATS)
+VIEW_P, VIEW_STATS_P, STABILISE_STATS_P = POINTER(AGMV_VIEW), POINTER(AGMV_VIEW_STATS), POINTER(AGMV_STABILISE_STATS)
 
 HIP = {
     "agmv_hip_max_usize": (sz, (u32, u32, c_int)),
@@ -131,6 +135,11 @@ HIP_VIEW = {
     "agmv_hip_view_frames_async": (c_int, (vp, vp, u32, u32, u32, u32, u32, u32, u32, u32, u32, vp, vp)),
 }
 
+# include/agmv_hip_stabilise.h, exported by the same library
+HIP_STABILISE = {
+    "agmv_hip_stabilise_frames_async": (c_int, (vp, u32, vp, u32, u32, u32, u32, vp, vp)),
+}
+
 _SEQ = (c_char_p, c_char_p, c_char_p, c_ubyte, ul, ul, ul, ul, ul, c_int, c_int, c_int)     # the three BMP drivers, behind `agmv`
 _CLIP = (ul, ul, ul, ul, c_int, c_int, c_int, c_int)                 # frames, width, height, fps, opt, quality, compression, schedule
 
@@ -208,6 +217,8 @@ AGMV = {
     "AGMV_BuildPaletteRefined": (c_int, (vp, c_int, c_int, vp, vp, c_uint, vp)),
     "AGMV_SetPaletteRefine": (None, (c_uint,)),
     "AGMV_SetDither": (None, (c_uint,)),
+    "AGMV_SetStabilise": (None, (c_uint,)),
+    "AGMV_GetStabiliseStats": (None, (STABILISE_STATS_P,)),
     "AGMV_EncodeFramesDev": (c_int, (c_char_p, vp) + _CLIP),
     "AGMV_DecodeFramesDev": (c_int, (c_char_p, vp, ul, INFO_P)),
     "AGMV_EncodeFramesFmtDev": (c_int, (c_char_p, vp, c_int) + _CLIP),

@@ -7,6 +7,7 @@
 //   k_similarity*             grey-equality counts of consecutive frames
 //   k_gather*                 the nearest scale as a table look-up; gather_frames is the body of the XRGB32 and byte-layout forms
 //   k_view                    every step-th frame of an XRGB32 clip and a window of each, copied into a packed clip
+//   k_stabilise               opt-in: still blocks of the P-frames of a batch replaced by their GOP's I-frame's, in place
 //   k_pix_* / k_yuv_*         the byte layouts and NV12 / I420 to and from XRGB32
 //   k_scale_area              the exact box-filter downscale of a clip in any of the seven layouts
 //   k_scale_up*               a decoded XRGB32 clip written at a target size, nearest or bilinear, in any of the seven layouts
@@ -24,6 +25,7 @@
 #include <type_traits>
 
 #include "agmv_hip_impl.h"
+#include "../../include/agmv_hip_stabilise.h"
 #include "../../include/agmv_hip_view.h"
 
 // ----------------------------------------------------------------------------------------------
@@ -235,6 +237,139 @@ __global__ __launch_bounds__(256) void k_view(const uint32_t* __restrict__ src, 
 			if (live > 2) d[2] = v.z;
 			if (live > 3) d[3] = v.w;
 		}
+	}
+}
+
+// Temporal stabilisation in place (agmv_hip_stabilise_frames_async; include/agmv.h, "temporal stabilisation", holds the rule).  One
+// lane owns one 4x4 block of one GOP: blockIdx.x runs over the frame's blocks in row-major order, so a wave's row load is 64
+// consecutive blocks = 1 KiB wherever a block row is that long, and a narrow frame still fills its waves; blockIdx.y strides over the
+// GOPs whose I-frame the batch holds.  stab_gop<NP> is the straight-line body for a GOP with NP P-frames in the batch: the four
+// 16-byte row loads of the anchor and the 4 * NP of the P-frames are all issued before the first use, then the decisions, then four
+// 16-byte stores per still block.  The decision works on two kinds of masked words, R and B of a pixel (p & 0x00FF00FF) and the
+// G of two neighbours in the same two byte places: the sum of the 48 differences is 24 byte SADs, and the max test keeps two
+// 16-bit fields per word, u = 0x8000 + s + a - p and v = 0x8000 + s - a + p (0 < u, v < 2^16: no borrow crosses a field, and
+// u + v is a constant word, so v costs one subtraction), whose bits 15 are all set exactly when every |a - p| <= s.
+constexpr int STAB_T = 256;
+#define STAB_GRID_GOPS 65535u     // the GOPs a launch spreads over blockIdx.y; a longer batch takes further trips round the GOP loop
+
+typedef uint32_t stab_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t stab_u32x8 __attribute__((ext_vector_type(8)));     // two rows of a block
+
+template <bool VEC> __device__ __forceinline__ stab_u32x4 stab_load(const uint32_t* p)
+{
+	if (VEC) return *reinterpret_cast<const stab_u32x4*>(p);
+	return stab_u32x4{p[0], p[1], p[2], p[3]};
+}
+
+template <bool VEC> __device__ __forceinline__ void stab_store(uint32_t* p, stab_u32x4 v)
+{
+	if (VEC) *reinterpret_cast<stab_u32x4*>(p) = v;
+	else { p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w; }
+}
+
+// rows r and r + 1 of a block, two 16-byte loads
+template <bool VEC> __device__ __forceinline__ stab_u32x8 stab_load2(const uint32_t* p, uint32_t w)
+{
+	return __builtin_shufflevector(stab_load<VEC>(p), stab_load<VEC>(p + w), 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// 4 pixels of a row as their 6 masked words: R.B of each pixel, then G of pixels 0|1 and 2|3
+__device__ __forceinline__ void stab_split(uint32_t x, uint32_t y, uint32_t z, uint32_t w, uint32_t m[6])
+{
+	m[0] = x & 0x00FF00FFu; m[1] = y & 0x00FF00FFu; m[2] = z & 0x00FF00FFu; m[3] = w & 0x00FF00FFu;
+	m[4] = ((x >> 8) & 0xFFu) | ((y << 8) & 0x00FF0000u);
+	m[5] = ((z >> 8) & 0xFFu) | ((w << 8) & 0x00FF0000u);
+}
+
+__device__ __forceinline__ void stab_split2(stab_u32x8 v, uint32_t m[2][6])
+{
+	stab_split(v[0], v[1], v[2], v[3], m[0]);
+	stab_split(v[4], v[5], v[6], v[7], m[1]);
+}
+
+// frames fa (the anchor) and fa + (j + 1) * npx, j < NP, at this lane's block; returns bit j set where P-frame j was replaced.
+// F[f][i] holds rows 2i and 2i + 1 of frame f of the GOP.  The empty asm statement takes every loaded register as an operand:
+// whatever reads a pixel comes behind it, and every load in front of it (left alone, hipcc holds the last frame's loads back
+// until the first frame is decided).
+template <bool VEC, int NP>
+__device__ __forceinline__ uint32_t stab_gop(uint32_t* fa, size_t npx, uint32_t w, uint32_t s)
+{
+	stab_u32x8 F[NP + 1][2];
+#pragma unroll
+	for (int f = 0; f <= NP; f++) {
+		F[f][0] = stab_load2<VEC>(fa + (size_t)f * npx, w);
+		F[f][1] = stab_load2<VEC>(fa + (size_t)f * npx + (size_t)2 * w, w);
+	}
+	if constexpr (NP == 1) asm volatile("" : "+v"(F[0][0]), "+v"(F[0][1]), "+v"(F[1][0]), "+v"(F[1][1]));
+	if constexpr (NP == 2) asm volatile("" : "+v"(F[0][0]), "+v"(F[0][1]), "+v"(F[1][0]), "+v"(F[1][1]), "+v"(F[2][0]), "+v"(F[2][1]));
+	if constexpr (NP == 3)
+		asm volatile("" : "+v"(F[0][0]), "+v"(F[0][1]), "+v"(F[1][0]), "+v"(F[1][1]), "+v"(F[2][0]), "+v"(F[2][1]), "+v"(F[3][0]), "+v"(F[3][1]));
+	const uint32_t K = 0x80008000u + s * 0x00010001u, C = 2u * K;     // (C modulo 2^32: u + v of a word, whose top carry v never has)
+	uint32_t am[2][2][6], out = 0;
+	stab_split2(F[0][0], am[0]);
+	stab_split2(F[0][1], am[1]);
+#pragma unroll
+	for (int j = 0; j < NP; j++) {
+		uint32_t sum = 0, ok = 0x80008000u;
+#pragma unroll
+		for (int i = 0; i < 2; i++) {
+			uint32_t pm[2][6];
+			stab_split2(F[j + 1][i], pm);
+#pragma unroll
+			for (int k = 0; k < 12; k++) {
+				const uint32_t a = am[i][k / 6][k % 6], p = pm[k / 6][k % 6], u = a + K - p;
+				sum = __builtin_amdgcn_sad_u8(a, p, sum);
+				ok &= u & (C - u);
+			}
+		}
+		if ((ok & 0x80008000u) == 0x80008000u && sum <= 12u * s) out |= 1u << j;
+	}
+	F[0][0] &= 0x00FFFFFFu;
+	F[0][1] &= 0x00FFFFFFu;
+#pragma unroll
+	for (int j = 0; j < NP; j++)
+		if (out & (1u << j)) {
+#pragma unroll
+			for (int i = 0; i < 2; i++) {
+				uint32_t* d = fa + (size_t)(j + 1) * npx + (size_t)(2 * i) * w;
+				stab_store<VEC>(d, __builtin_shufflevector(F[0][i], F[0][i], 0, 1, 2, 3));
+				stab_store<VEC>(d + w, __builtin_shufflevector(F[0][i], F[0][i], 4, 5, 6, 7));
+			}
+		}
+	return out;
+}
+
+// lead: the frames in front of the batch's first I-frame; n_gops: the GOPs of the batch that have a P-frame in it.  The count
+// of replaced blocks: ballot and popcount per wave and P-frame, the waves' sums through LDS, one 64-bit atomic per workgroup.
+// Three waves per SIMD: the 16 loaded rows are 64 registers and the anchor's masked words 24 more; a bound of four waves spills.
+template <bool VEC>
+__global__ __launch_bounds__(STAB_T, 3) void k_stabilise(uint32_t* __restrict__ pix, uint32_t w, uint32_t bw, uint32_t nblk, size_t npx, uint32_t n_frames,
+                                                      uint32_t lead, uint32_t n_gops, uint32_t s, unsigned long long* __restrict__ replaced)
+{
+	__shared__ uint32_t s_cnt[STAB_T / 64];
+	const uint32_t b = blockIdx.x * STAB_T + threadIdx.x;
+	const bool live = b < nblk;
+	const uint32_t by = b / bw, bx = b - by * bw;
+	const size_t in_frame = (size_t)by * 4u * w + (size_t)bx * 4u;
+	uint32_t count = 0;                                        // of this wave, the same in all its lanes
+	for (uint32_t g = blockIdx.y; g < n_gops; g += gridDim.y) {
+		const uint32_t a = lead + 4u * g, after = n_frames - 1u - a;      // the anchor; the batch's frames behind it, >= 1
+		uint32_t got = 0;
+		if (live) {
+			uint32_t* fa = pix + (size_t)a * npx + in_frame;
+			if (after >= 3u) got = stab_gop<VEC, 3>(fa, npx, w, s);
+			else if (after == 2u) got = stab_gop<VEC, 2>(fa, npx, w, s);
+			else got = stab_gop<VEC, 1>(fa, npx, w, s);
+		}
+		count += (uint32_t)__popcll(__ballot(got & 1u)) + (uint32_t)__popcll(__ballot(got & 2u)) + (uint32_t)__popcll(__ballot(got & 4u));
+	}
+	if (!replaced) return;
+	if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = count;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		unsigned long long total = 0;
+		for (int i = 0; i < STAB_T / 64; i++) total += s_cnt[i];
+		if (total) atomicAdd(replaced, total);
 	}
 }
 
@@ -1656,6 +1791,25 @@ extern "C" int agmv_hip_view_frames_async(agmv_hip_ctx* c, const uint32_t* d_src
 	else if (st4) VIEW_LAUNCH(false, true);
 	else VIEW_LAUNCH(false, false);
 #undef VIEW_LAUNCH
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_stabilise_frames_async(agmv_hip_ctx* c, uint32_t strength, uint32_t* d_pix, uint32_t w, uint32_t h, uint32_t n_frames,
+                                               uint32_t first_fc, unsigned long long* d_replaced, void* stream)
+{
+	if (agmv_hip_enter(c)) return -1;
+	if (!d_pix || ((uintptr_t)d_pix & 3u)) return agmv_hip_err("agmv_hip: stabilise: d_pix must be a 4-byte aligned device pointer");
+	if (agmv_hip_check_geometry(w, h)) return -1;
+	if (strength < 1 || strength > 64) return agmv_hip_err("agmv_hip: stabilise: strength must be 1 .. 64 (got %u)", strength);
+	const uint32_t lead = (4u - (first_fc & 3u)) & 3u;         // frames whose I-frame lies before the batch
+	if (n_frames < lead + 2u) return 0;                        // no P-frame with its I-frame in the batch
+	const uint32_t n_gops = (n_frames - lead - 2u) / 4u + 1u, bw = w / 4u, nblk = bw * (h / 4u);
+	const dim3 grid((nblk + STAB_T - 1) / STAB_T, n_gops < STAB_GRID_GOPS ? n_gops : STAB_GRID_GOPS);
+#define STAB_LAUNCH(V) hipLaunchKernelGGL((k_stabilise<V>), grid, dim3(STAB_T), 0, (hipStream_t)stream, d_pix, w, bw, nblk, (size_t)w * h, n_frames, lead, n_gops, strength, d_replaced)
+	if (((uintptr_t)d_pix & 15u) == 0) STAB_LAUNCH(true);
+	else STAB_LAUNCH(false);
+#undef STAB_LAUNCH
 	CK(hipGetLastError());
 	return 0;
 }

@@ -29,7 +29,7 @@
 static agmv_hip_ctx* g_ctx = NULL;
 static uint32_t g_pal[512];
 static int g_pal_mode = -1;
-static unsigned g_batch_frames = 0, g_lz_threads = 0, g_devices = 0, g_palette_refine = 0, g_dither = 0;
+static unsigned g_batch_frames = 0, g_lz_threads = 0, g_devices = 0, g_palette_refine = 0, g_dither = 0, g_stabilise = 0;
 /* the device track AGMV_SetAudioDev attached to the next AGMV_EncodeFrames*Dev call (d_pcm NULL: none) */
 static struct { const void* d_pcm; int fmt; u32 samples, rate; u16 channels; } g_audio;
 static unsigned long g_export_count = 0;            /* AGIDL's expcount, extern/agidl/src/agidl_img_export.c:18 */
@@ -58,6 +58,7 @@ void AGMV_SetLZThreads(unsigned n) { g_lz_threads = n; }
 void AGMV_SetDevices(unsigned n) { g_devices = n; }
 void AGMV_SetPaletteRefine(unsigned n) { g_palette_refine = n; }
 void AGMV_SetDither(unsigned n) { g_dither = n; }
+void AGMV_SetStabilise(unsigned n) { g_stabilise = n; }
 
 /* frames per GPU batch: what the caller asked for, else about 128 MB of source pixels (64 frames at most), whole GOPs */
 static unsigned batch_frames(size_t npx)
@@ -96,6 +97,15 @@ unsigned agmv_dither_strength(void)
 {
 	const char* e = getenv("AGMV_DITHER");
 	if (g_dither) return g_dither > 64 ? 64 : g_dither;
+	return e && atoi(e) >= 1 && atoi(e) <= 64 ? (unsigned)atoi(e) : 0;
+}
+
+/* strength of the temporal stabilisation a sequence opened now runs before its encodes (AGMV_SetStabilise / env AGMV_STABILISE,
+   1 .. 64; default 0 = off); agmv_seq_open reads it */
+unsigned agmv_stabilise_strength(void)
+{
+	const char* e = getenv("AGMV_STABILISE");
+	if (g_stabilise) return g_stabilise > 64 ? 64 : g_stabilise;
 	return e && atoi(e) >= 1 && atoi(e) <= 64 ? (unsigned)atoi(e) : 0;
 }
 

@@ -5,7 +5,8 @@
  * thread; here the stages of DIFFERENT batches overlap (SURVEY.md section 7 "pipeline shape"):
  *
  *   encode   host cores: BMP parse (+ GBA/NDS nearest scale) of batch b+1 into pinned staging
- *            GPU worker threads (two per device, devices = AGMV_DEVICES): H2D -> PDIFS midpoint -> (opt-in, AGMV_SetDither /
+ *            GPU worker threads (two per device, devices = AGMV_DEVICES): H2D -> PDIFS midpoint -> (opt-in, AGMV_SetStabilise /
+ *              AGMV_STABILISE: k_stabilise, in place) -> (opt-in, AGMV_SetDither /
  *              AGMV_DITHER: k_dither, in place) -> k_encode -> D2H of batch b, each worker on its own stream and context; batches are whole GOPs, so they are independent given
  *              the palette and go round-robin over the workers / devices (multi-GPU sharding by GOP range, no exchange)
  *            host cores: exact LZSS / LZ77 of batch b-1, one task per frame -- or, opt-in (AGMV_LZ_DEVICE for LZSS,
@@ -219,6 +220,8 @@ typedef struct eworker {
 	uint32_t* d_csize;
 	size_t lz77_stride;                    /* lz_dev, LZ77: stride of the rows d_lz holds now (grown on demand) */
 	uint8_t* d_peek;                       /* lz_dev, LZ77: [cap] the byte behind each stream */
+	unsigned long long* d_replaced;        /* stabilise: this worker's count of replaced blocks on its device, downloaded by agmv_seq_close */
+	unsigned long long examined;           /* stabilise: P-frame blocks of this worker's batches that had their anchor in the batch */
 } eworker;
 
 struct agmv_seq {
@@ -229,6 +232,7 @@ struct agmv_seq {
 	int scale_w, scale_h, audio_chunks, mode512, lz77, use_b;
 	int lz_dev;                            /* the LZ stage runs on the GPU workers (lz77 chooses the form): AGMV_LZ_DEVICE for LZSS,
 	                                          AGMV_LZ77_DEVICE for LZ77 on one device */
+	unsigned stabilise;                    /* strength of the temporal stabilisation of every batch before its dither and encode, 0 = off (AGMV_SetStabilise / AGMV_STABILISE) */
 	unsigned dither;                       /* strength of the pattern dithering of every batch before its encode, 0 = off (AGMV_SetDither / AGMV_DITHER) */
 	uint8_t* d_persist;                    /* lz_dev, LZ77: `persist` on the device (persist_len bytes, zero-initialised) */
 	unsigned peek_turn;                    /* lz_dev, LZ77: the batch whose peek call comes next (under mu) */
@@ -361,6 +365,18 @@ static int place_frame(eworker* wk, long idx, uint32_t* dst)
 	return agmv_fmt_to_xrgb(wk->ctx, s->src.fmt, s->src.src_w, s->src.src_h, src_frame(s, idx), 1, s->npx, dst, wk->stream);
 }
 
+/* the P-frames of a batch of n frames from frame count first_fc on whose I-frame (frame_count % 4 == 0) lies in the batch */
+static unsigned stabilise_examined_frames(unsigned n, u32 first_fc)
+{
+	const unsigned lead = (4u - (unsigned)(first_fc & 3u)) & 3u;
+	return n > lead ? (n - lead) - (n - lead + 3u) / 4u : 0;
+}
+
+/* the last sequence encode's AGMV_STABILISE_STATS: zeroed by agmv_seq_open, set by agmv_seq_close */
+static AGMV_STABILISE_STATS g_stabilise_stats;
+
+void AGMV_GetStabiliseStats(AGMV_STABILISE_STATS* out) { if (out) *out = g_stabilise_stats; }
+
 /* one GPU worker: its batches are id = idx, idx + nworkers, ... in order */
 static void* eworker_main(void* p)
 {
@@ -409,7 +425,13 @@ static void* eworker_main(void* p)
 				agmv_die("entry plane upload");
 			free(e);
 		}
-		/* the frames are what k_encode would have seen, midpoints included: dithered in place, on the same stream */
+		/* the frames are what k_encode would have seen, midpoints included: stabilised against the batch's own I-frames, then
+		   dithered, in place, on the same stream */
+		if (s->stabilise) {
+			if (agmv_hip_stabilise_frames_async(wk->ctx, s->stabilise, wk->d_frames, s->w, s->h, b->n, b->first_fc, wk->d_replaced, wk->stream))
+				agmv_die("batch stabilisation");
+			wk->examined += (unsigned long long)stabilise_examined_frames(b->n, b->first_fc) * (s->npx / 16);
+		}
 		if (s->dither && agmv_hip_dither_frames_async(wk->ctx, s->dither, wk->d_frames, s->w, s->h, b->n, wk->stream)) agmv_die("batch dither");
 		if (agmv_hip_encode_frames_dev(wk->ctx, wk->d_frames, b->n, s->w, s->h, b->first_fc, wk->d_out, s->stride, wk->d_sizes, wk->d_ient,
 		                               wk->stream) ||
@@ -564,6 +586,9 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const agmv_source* src, int scale_w
 	   persistent buffer behind the streams then lives on ONE device, so with more than one device its stage stays on the host pool. */
 	s->lz_dev = lz77 ? devices == 1 && env_nonzero("AGMV_LZ77_DEVICE") : env_nonzero("AGMV_LZ_DEVICE");
 	s->lz_stride = (agmv_hip_lzss_max_csize(s->stride) + 255) & ~(size_t)255;
+	s->stabilise = agmv_stabilise_strength();
+	memset(&g_stabilise_stats, 0, sizeof(g_stabilise_stats));
+	if (s->stabilise) TRACE("seq_open: temporal stabilisation of every batch before its dither and encode, strength %u\n", s->stabilise);
 	s->dither = agmv_dither_strength();
 	if (s->dither) TRACE("seq_open: pattern dithering of every batch before its encode, strength %u\n", s->dither);
 	s->cap = (cap + 3u) & ~3u;
@@ -613,6 +638,12 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const agmv_source* src, int scale_w
 		wk->d_lz = s->lz_dev && !lz77 ? (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->lz_stride * s->cap) : NULL;   /* (LZ77: lz77_rows) */
 		wk->d_csize = s->lz_dev ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, 4 * (size_t)s->cap) : NULL;
 		wk->d_peek = s->lz_dev && lz77 ? (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->cap) : NULL;
+		if (s->stabilise) {
+			wk->d_replaced = (unsigned long long*)agmv_hip_malloc_on(wk->ctx, sizeof(unsigned long long));
+			if (!wk->d_replaced || agmv_hip_memset_async(wk->ctx, wk->d_replaced, 0, sizeof(unsigned long long), wk->stream) ||
+			    agmv_hip_stream_sync(wk->ctx, wk->stream))
+				agmv_die("device allocation");
+		}
 		if (s->lz_dev && lz77 && i == 0) {
 			s->d_persist = (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->persist_len);
 			if (!s->d_persist || agmv_hip_memset_async(wk->ctx, s->d_persist, 0, s->persist_len, wk->stream) || agmv_hip_stream_sync(wk->ctx, wk->stream))
@@ -658,6 +689,14 @@ u32 agmv_seq_close(agmv_seq* s)
 	for (i = 0; i < s->nworkers; i++) {
 		eworker* wk = &s->wk[i];
 		pthread_join(wk->th, NULL);
+		if (s->stabilise) {                                /* (the worker synchronised its stream behind its last batch) */
+			unsigned long long replaced = 0;
+			if (agmv_hip_memcpy_async(wk->ctx, &replaced, wk->d_replaced, sizeof(replaced), 1, wk->stream) || agmv_hip_stream_sync(wk->ctx, wk->stream))
+				agmv_die("stabilisation count download");
+			g_stabilise_stats.examined += wk->examined;
+			g_stabilise_stats.replaced += replaced;
+			agmv_hip_free_on(wk->ctx, wk->d_replaced);
+		}
 		agmv_hip_free_on(wk->ctx, wk->d_frames); agmv_hip_free_on(wk->ctx, wk->d_out); agmv_hip_free_on(wk->ctx, wk->d_sizes);
 		agmv_hip_free_on(wk->ctx, wk->d_ient); agmv_hip_free_on(wk->ctx, wk->d_tmp[0]); agmv_hip_free_on(wk->ctx, wk->d_tmp[1]);
 		agmv_hip_free_on(wk->ctx, wk->d_lz); agmv_hip_free_on(wk->ctx, wk->d_csize); agmv_hip_free_on(wk->ctx, wk->d_peek);
@@ -672,6 +711,9 @@ u32 agmv_seq_close(agmv_seq* s)
 		agmv_hip_host_free(b->h_pix); agmv_hip_host_free(b->sizes); agmv_hip_host_free(b->csizes); agmv_hip_host_free(b->h_bits);
 	}
 	written = s->frames_written;
+	if (s->stabilise)
+		TRACE("seq_close: temporal stabilisation, strength %u: %llu of %llu P-frame blocks with their I-frame in the batch replaced\n", s->stabilise,
+		      g_stabilise_stats.replaced, g_stabilise_stats.examined);
 	TRACE("seq_close: teardown %.3f s\n", now_s() - t0);
 	free(s->slot); free(s->wk); free(s->persist);
 	pthread_mutex_destroy(&s->mu);

@@ -1,4 +1,5 @@
-"""ctypes binding of include/agmv_hip.h (the signatures are abi.HIP) and include/agmv_hip_view.h (abi.HIP_VIEW).
+"""ctypes binding of include/agmv_hip.h (the signatures are abi.HIP), include/agmv_hip_view.h (abi.HIP_VIEW) and
+include/agmv_hip_stabilise.h (abi.HIP_STABILISE).
 
 The product is the shared library; this module only marshals pointers.  torch is used for
 device memory and streams (plumbing).  Every failure is loud: a missing library raises
@@ -52,6 +53,7 @@ def load_library(path=None):
     # only an explicitly named other build of the same source may lack symbols; the default library has them all
     abi.bind(L, abi.HIP, missing_ok=path is not None)
     abi.bind(L, abi.HIP_VIEW, missing_ok=path is not None)
+    abi.bind(L, abi.HIP_STABILISE, missing_ok=path is not None)
     _libs[p] = L
     return L
 
@@ -838,6 +840,24 @@ class AgmvHip:
         self._ck(self.L.agmv_hip_palette_refine_dev(self.ctx, hist.data_ptr(), int(quality), pal.data_ptr(), pal.numel(), int(n_free), int(iterations),
                                                     rounds.data_ptr(), sse.data_ptr(), self._stream()))
         return rounds, sse
+
+    # ------------------------------------------------------------------ temporal stabilisation of a batch (include/agmv.h; agmv_hip_stabilise_frames_async of include/agmv_hip_stabilise.h)
+    def stabilise_frames(self, pix, w, h, strength, first_fc=0, count=None, stream=None):
+        """pix: int32 CUDA tensor (or view at any element offset) of whole frames of w x h pixels with frame counts first_fc,
+        first_fc + 1, ..., stabilised in place (agmv_hip_stabilise_frames_async) on `stream` (a torch stream; None = torch's current
+        stream).  strength 1 .. 64.  count: None, or an int64 CUDA tensor of one element on the same device, to which the number of
+        replaced blocks is added (the caller sets it to zero).  Returns pix; nothing waits."""
+        import torch
+        _check_vec("stabilise_frames: pix", pix, 0)
+        w, h = int(w), int(h)
+        if w < 1 or h < 1 or pix.numel() % (w * h):
+            raise ValueError("stabilise_frames: pix must hold whole frames of %d x %d pixels, got %d words" % (w, h, pix.numel()))
+        if count is not None and not (count.is_cuda and count.dtype == torch.int64 and count.numel() == 1 and count.device == pix.device):
+            raise ValueError("stabilise_frames: count must be an int64 CUDA tensor of one element on the device of pix")
+        s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self._ck(self.L.agmv_hip_stabilise_frames_async(self.ctx, int(strength), pix.data_ptr(), w, h, pix.numel() // (w * h), int(first_fc),
+                                                        count.data_ptr() if count is not None else None, s))
+        return pix
 
     # ------------------------------------------------------------------ pattern dithering against the context's palette (include/agmv.h)
     def dither_frames(self, pix, w, h, strength, stream=None):

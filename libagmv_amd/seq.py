@@ -160,7 +160,7 @@ def _track_geometry(audio, sample_rate):
 
 
 def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedule=SCHEDULE_PDIFS, fmt=None, yuv=None, full_range=False,
-                  size=None, scale="area", palette_refine=None, dither=None, audio=None, sample_rate=None, mean=None, std=None):
+                  size=None, scale="area", palette_refine=None, dither=None, audio=None, sample_rate=None, mean=None, std=None, stabilise=None):
     """frames: contiguous CUDA tensor of n frames on the library's device, in the layout `fmt` (see the module text; None = inferred
     from the tensor, which never gives "nv12" or "i420") -> the file at `path`.  yuv ("bt601", the default, or "bt709") and
     full_range go with the two YUV layouts only.  size=(h, w), in tensor order, scales the clip to that size first
@@ -169,7 +169,10 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
     palette's colours by at most n rounds of weighted k-means over the clip's histogram (AGMV_SetPaletteRefine of include/agmv.h,
     set for this call only); None leaves the library's knob as it is.  dither=s, an int from 1 to 64, pattern-dithers the frames
     against the palette with that strength before they are quantised (AGMV_SetDither of include/agmv.h, which holds the
-    definition; set for this call only); None leaves the library's knob as it is.  audio= is the clip's sound, a contiguous CUDA
+    definition; set for this call only); None leaves the library's knob as it is.  stabilise=s, an int from 1 to 64, gives the
+    blocks of a P-frame that differ from their GOP's I-frame by no more than that strength allows the I-frame's pixels, before the
+    dither (AGMV_SetStabilise of include/agmv.h, which holds the rule; set for this call only; stabilise_stats() says what it did);
+    None leaves the library's knob as it is.  audio= is the clip's sound, a contiguous CUDA
     tensor on the same device -- int16 [n, ch], uint8 [n, ch] or float32 [ch, n] (see the module text) -- at sample_rate= samples
     per second; it is companded on the GPU and interleaved with the frames as AGAC chunks (AGMV_SetAudioDev, for this call only).
     A track shorter than one second and SCHEDULE_ADAPTIVE with a track are refused.
@@ -180,6 +183,8 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
     import torch
     if dither is not None and not (isinstance(dither, int) and not isinstance(dither, bool) and 1 <= dither <= 64):
         raise ValueError("encode_frames: dither must be None or an int from 1 to 64, got %r" % (dither,))
+    if stabilise is not None and not (isinstance(stabilise, int) and not isinstance(stabilise, bool) and 1 <= stabilise <= 64):
+        raise ValueError("encode_frames: stabilise must be None or an int from 1 to 64, got %r" % (stabilise,))
     if palette_refine is not None and not (isinstance(palette_refine, int) and not isinstance(palette_refine, bool) and 1 <= palette_refine <= 64):
         raise ValueError("encode_frames: palette_refine must be None or an int from 1 to 64, got %r" % (palette_refine,))
     target = _scale_target(size, scale)
@@ -209,6 +214,8 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
         L.AGMV_SetPaletteRefine(palette_refine)
     if dither is not None:
         L.AGMV_SetDither(dither)
+    if stabilise is not None:
+        L.AGMV_SetStabilise(stabilise)
     try:
         if tensor is not None:
             rc = L.AGMV_EncodeFramesTensorDev(os.fsencode(path), frames.data_ptr(), v, tensor[4], tensor[5], n, w, h, fps, opt, quality, compression, schedule)
@@ -233,6 +240,16 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
             L.AGMV_SetPaletteRefine(0)
         if dither is not None:
             L.AGMV_SetDither(0)
+        if stabilise is not None:
+            L.AGMV_SetStabilise(0)
+
+
+def stabilise_stats():
+    """(examined, replaced) of the last sequence encode of this process (AGMV_GetStabiliseStats of include/agmv.h): the blocks of the
+    P-frames that had their GOP's I-frame in their batch, and those the temporal stabilisation replaced; (0, 0) when it was off"""
+    st = abi.AGMV_STABILISE_STATS()
+    load_library().AGMV_GetStabiliseStats(C.byref(st))
+    return int(st.examined), int(st.replaced)
 
 
 def _decode_target(size, scale):
