@@ -640,6 +640,50 @@ int AGMV_DecodeViewTensorDev(const char* filename, void* d_tensor, AGMV_TENSORFM
                              u32 height, AGMV_SCALE filter, const AGMV_VIEW* view, u32 cap_frames, AGMV_INFO* info);
 void AGMV_GetViewStats(AGMV_VIEW_STATS* out);
 
+/* A view of a clip encoded: 1080p60 NV12 from a capture as the 240 x 160, 15 fps file of this codec -- every 4th frame, the centred
+   1440 x 1080 window of each, scaled -- without a copy of the selection.  The view is the AGMV_VIEW above with the same field rules,
+   now resolved against the clip of num_of_frames frames of src_width x src_height in the layout `fmt`: view == NULL is the whole
+   clip, count == 0 means "to the end", a selection that runs past the last frame is cut there, width == height == 0 is the full
+   frame.  Let S be the XRGB32 clip the source stands for by its reading rule and V the XRGB32 clip of the selected windows,
+     V[j][r][c] = S[first + j * step][y + r][x + c]
+   (an NV12 / I420 pixel keeps the chroma sample of its 2 x 2 cell of the source frame, so a window may start and end anywhere).
+     width == height == 0   the file is, byte for byte, what AGMV_EncodeFramesDev writes for V; `filter` is not read
+     otherwise              the file is, byte for byte, what AGMV_EncodeFramesScaledDev writes for V as an XRGB32 source with this
+                            target and filter; only AGMV_SCALE_NEAREST and AGMV_SCALE_AREA are accepted
+   The palette, the schedule's decisions, the PDIFS midpoints, the header and the chunks are those of V.  frames_per_second is
+   written as given (divide by step to keep the clip's speed).  The dither, the stabilisation, the palette refinement and a pending
+   AGMV_SetAudioDev track apply as for the other AGMV_EncodeFrames*Dev; the track is consumed whatever the call returns.
+   Returns 0, or a negative value; the checks, in this order, all before a device is opened and before a file is created:
+     -1  NULL filename or frames; unknown format or enum value; with a target a filter other than NEAREST and AREA; step == 0;
+         exactly one of view->width, view->height zero; x or y not zero with a zero window
+     -5  AGMV_SCHEDULE_ADAPTIVE with a pending track
+     -3  a source size AGMV_EncodeFramesScaledDev refuses (zero, or above 2^28 pixels); a window that does not lie inside the frame;
+         an NV12 / I420 source of odd width or height, unless the view is consecutive full frames; without a target a window
+         (or full frame) whose size AGMV_EncodeFramesDev refuses for this opt; with a target everything
+         AGMV_EncodeFramesScaledDev refuses for a source of the window's size: a target that is zero or no multiple of 4, a GBA /
+         NDS opt, AGMV_SCALE_AREA with a target above the window in either axis or with a window above 2^24 pixels
+     -2  the view's length -- the frames first, first + step, ... below num_of_frames, at most count of them; 0 for a `first` at or
+         behind the end -- is below what the schedule's first group reads
+     -4  the clip or the staging batch cannot be allocated: after the device is opened, still before a file is created
+   How it runs.  The selection that takes everything is AGMV_EncodeFramesFmtDev / AGMV_EncodeFramesScaledDev, launch for launch.
+   Consecutive full frames (step == 1, no window) are the same call on d_frames + first * frame bytes: nothing is copied.  Any
+   other view without a target materialises V once on the library's device, 4 * window width * window height * length bytes, with
+   one launch (agmv_hip_view_source_async of include/agmv_hip_view_source.h), and takes the path of AGMV_EncodeFramesDev on it.
+   With a target only D, the clip at the target's size, is materialised: V exists one staging batch at a time -- as many windows
+   as fit 256 MiB, and at least one -- which agmv_hip_view_source_async writes and the box filter / the nearest gather then reads as
+   an XRGB32 source into that batch's frames of D; every frame of D is a function of its own window alone, so D is what the scale
+   of the whole of V gives.  256 MiB is the size of the memory-side cache and bounds the memory; it is not a tuned value.
+   AGMV_VIEW_STAGE_FRAMES=n in the environment (read per call, a test aid) forces batches of n windows.  The source is read once,
+   in its own layout, and nothing of its size is allocated; everything is freed before the call returns.
+   AGMV_GetEncodeViewStats reports what the last AGMV_EncodeViewDev of this process did: frames = the frames encoded (the view's
+   length), clip_bytes = the bytes of the XRGB32 clip it materialised (V, with a target D; 0 where the source was encoded in place),
+   staging_bytes = the bytes of the staging batch (0 without one).  All zero behind a call that returned a negative value. */
+typedef struct AGMV_ENCODE_VIEW_STATS { unsigned frames; unsigned long long clip_bytes, staging_bytes; } AGMV_ENCODE_VIEW_STATS;
+int AGMV_EncodeViewDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height,
+                       const AGMV_VIEW* view, u32 width, u32 height, AGMV_SCALE filter, u32 frames_per_second, AGMV_OPT opt,
+                       AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule);
+void AGMV_GetEncodeViewStats(AGMV_ENCODE_VIEW_STATS* out);
+
 /* Audio tracks from and to GPU memory.  An AGMV_PCMFMT names the layout of PCM in device memory:
      AGMV_PCM_S16   [samples][channels] 16-bit words, bits unchanged (int16 WAV samples as they are); for 16-bit tracks
      AGMV_PCM_U8    [samples][channels] unsigned bytes; for 8-bit tracks; a copy

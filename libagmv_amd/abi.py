@@ -1,5 +1,6 @@
 """The public C signatures, stated once: the structures of include/agmv.h that Python passes, every function of
-include/agmv_hip.h (HIP), of include/agmv_hip_view.h (HIP_VIEW) and of include/agmv_hip_stabilise.h (HIP_STABILISE) and every function of include/agmv.h that Python calls on libagmv.so (AGMV), as
+include/agmv_hip.h (HIP), of include/agmv_hip_view.h (HIP_VIEW), of include/agmv_hip_view_source.h (HIP_VIEW_SOURCE) and of
+include/agmv_hip_stabilise.h (HIP_STABILISE) and every function of include/agmv.h that Python calls on libagmv.so (AGMV), as
 name -> (restype, (argtypes...)).  bind() sets them on a loaded library.  tests/test_abi.py checks both tables and the
 structures against the headers.  ctypes only, and no library is loaded here: the test children import this module the
 way a C host would include the headers."""
@@ -32,6 +33,10 @@ class AGMV_VIEW_STATS(Structure):
     _fields_ = [("lz_frames", c_uint), ("gpu_frames", c_uint), ("delivered", c_uint), ("restarts", c_uint)]
 
 
+class AGMV_ENCODE_VIEW_STATS(Structure):
+    _fields_ = [("frames", c_uint), ("clip_bytes", c_ulonglong), ("staging_bytes", c_ulonglong)]
+
+
 class AGMV_STABILISE_STATS(Structure):
     _fields_ = [("examined", c_ulonglong), ("replaced", c_ulonglong)]
 
@@ -40,6 +45,7 @@ class AGMV_STABILISE_STATS(Structure):
 vp, sz, u32, u64, ul = c_void_p, c_size_t, c_uint32, c_uint64, c_ulong
 INFO_P, QUALITY_P, ENTRY_P = POINTER(AGMV_INFO), POINTER(AGMV_FRAME_QUALITY), POINTER(AGMV_ENTRY)
 VIEW_P, VIEW_STATS_P, STABILISE_STATS_P = POINTER(AGMV_VIEW), POINTER(AGMV_VIEW_STATS), POINTER(AGMV_STABILISE_STATS)
+ENCODE_VIEW_STATS_P = POINTER(AGMV_ENCODE_VIEW_STATS)
 
 HIP = {
     "agmv_hip_max_usize": (sz, (u32, u32, c_int)),
@@ -133,6 +139,11 @@ HIP = {
 # include/agmv_hip_view.h, exported by the same library
 HIP_VIEW = {
     "agmv_hip_view_frames_async": (c_int, (vp, vp, u32, u32, u32, u32, u32, u32, u32, u32, u32, vp, vp)),
+}
+
+# include/agmv_hip_view_source.h, exported by the same library
+HIP_VIEW_SOURCE = {
+    "agmv_hip_view_source_async": (c_int, (vp, c_int, vp, u32, u32, u32, u32, u32, u32, u32, u32, u32, vp, vp)),
 }
 
 # include/agmv_hip_stabilise.h, exported by the same library
@@ -230,6 +241,8 @@ AGMV = {
     "AGMV_DecodeViewDev": (c_int, (c_char_p, vp, c_int, ul, ul, c_int, VIEW_P, ul, INFO_P)),
     "AGMV_DecodeViewTensorDev": (c_int, (c_char_p, vp, c_int, vp, vp, ul, ul, c_int, VIEW_P, ul, INFO_P)),
     "AGMV_GetViewStats": (None, (VIEW_STATS_P,)),
+    "AGMV_EncodeViewDev": (c_int, (c_char_p, vp, c_int, ul, ul, ul, VIEW_P, ul, ul, c_int, ul, c_int, c_int, c_int, c_int)),
+    "AGMV_GetEncodeViewStats": (None, (ENCODE_VIEW_STATS_P,)),
     "AGMV_SetAudioDev": (c_int, (vp, c_int, ul, ul, c_ushort)),
     "AGMV_DecodeAudioDev": (c_int, (c_char_p, vp, c_int, ul, INFO_P)),
     "AGMV_MeasureFramesDev": (c_int, (vp, vp, c_int, ul, ul, ul, QUALITY_P)),

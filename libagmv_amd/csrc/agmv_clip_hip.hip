@@ -7,6 +7,7 @@
 //   k_similarity*             grey-equality counts of consecutive frames
 //   k_gather*                 the nearest scale as a table look-up; gather_frames is the body of the XRGB32 and byte-layout forms
 //   k_view                    every step-th frame of an XRGB32 clip and a window of each, copied into a packed clip
+//   k_view_src                the same of a clip in any other layout, converted on the way: the encoder's view of its source
 //   k_stabilise               opt-in: still blocks of the P-frames of a batch replaced by their GOP's I-frame's, in place
 //   k_pix_* / k_yuv_*         the byte layouts and NV12 / I420 to and from XRGB32
 //   k_scale_area              the exact box-filter downscale of a clip in any of the seven layouts
@@ -27,6 +28,7 @@
 #include "agmv_hip_impl.h"
 #include "../../include/agmv_hip_stabilise.h"
 #include "../../include/agmv_hip_view.h"
+#include "../../include/agmv_hip_view_source.h"
 
 // ----------------------------------------------------------------------------------------------
 // caller-side helpers: synthetic clip, PDIFS midpoint, palette histogram
@@ -1121,6 +1123,87 @@ template <int FMT> __global__ __launch_bounds__(256) void k_scale_area(ScaleArgs
 	}
 }
 
+// ---- a view of a clip in the caller's layout (agmv_hip_view_source_async of include/agmv_hip_view_source.h) ----
+// dst[j][r][c] = P(first + j * step)[y + r][x + c], P(k) being frame k as k_pix_to_xrgb / k_yuv_to_xrgb give it.  A streaming
+// convert-copy: a lane owns the 16 consecutive pixels c0 .. c0 + 15 of one output row (YUV: of the rows 2i and 2i + 1 of the window,
+// the patch of yuv_load_patch), blockIdx.x runs over the gpr groups of the rows (row pairs) of a window, blockIdx.y strides over
+// the frames.  ld: the groups of the window's rows start on 16-byte boundaries of the source (YUV: and y is even, so both rows of
+// a patch share a chroma row): a group whose 16 source pixels lie inside its source row is read through pf_load16 /
+// yuv_load_patch, non-temporal.  st: w is a multiple of 4 and dst is 16-byte aligned: a group is 1 .. 4 whole 16-byte stores per row.
+// A group that was loaded whole is converted whole and then stored; the pixel-by-pixel form makes and stores four pixels at a time.
+// Every other group goes pixel by pixel over its `live` pixels through sc_read, to the same words.
+struct ViewSrcArgs {
+	const uint8_t* src;
+	uint32_t* dst;
+	size_t frame_bytes;                                            // of a source frame
+	uint32_t sw, sh, first, step, count, x, y, w, h, gpr;
+	int ld, st;
+	yuv_rd m;
+};
+
+// pixels 4q .. 4q + 3 of a lane's group, those below `live`, to d: one 16-byte store (st: all four are live), else word by word
+__device__ __forceinline__ void view_src_store4(uint32_t* __restrict__ d, int q, const pf_u32x4& o, uint32_t live, int st)
+{
+	if (st) *reinterpret_cast<pf_u32x4*>(d + 4 * q) = o;
+	else {
+#pragma unroll
+		for (int i = 0; i < 4; i++) if (4u * q + i < live) d[4 * q + i] = o[i];
+	}
+}
+
+template <int FMT> __global__ __launch_bounds__(256) void k_view_src(ViewSrcArgs A)
+{
+	constexpr bool YUV = FMT >= PF_NV12;
+	const size_t item = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (item >= (size_t)(YUV ? (A.h + 1) >> 1 : A.h) * A.gpr) return;
+	const uint32_t ri = (uint32_t)(item / A.gpr), c0 = (uint32_t)(item - (size_t)ri * A.gpr) * 16u, r = YUV ? 2 * ri : ri;
+	const uint32_t live = A.w - c0 < 16u ? A.w - c0 : 16u, sx = A.x + c0, sy = A.y + r;
+	const bool row1 = YUV && r + 1 < A.h, ld = A.ld && sx + 16 <= A.sw;
+	for (uint32_t j = blockIdx.y; j < A.count; j += gridDim.y) {
+		const uint8_t* fr = A.src + ((size_t)A.first + (size_t)j * A.step) * A.frame_bytes;
+		uint32_t* d = A.dst + ((size_t)j * A.h + r) * A.w + c0;
+		if (ld) {
+			if constexpr (YUV) {
+				const yuv_raw p = yuv_load_patch<FMT, true>(fr, A.sw, A.sh, sx, sy >> 1, row1);
+				pf_u32x4 o0[4], o1[4];
+#pragma unroll
+				for (int q = 0; q < 4; q++) {                          // pixels 4q .. 4q + 3 of both rows: chroma samples 2q, 2q + 1
+					const yuv_terms ta = yuv_patch_chroma<FMT>(p, 2 * q, A.m), tb = yuv_patch_chroma<FMT>(p, 2 * q + 1, A.m);
+#pragma unroll
+					for (int i = 0; i < 4; i++) {
+						o0[q][i] = yuv_pixel(A.m, (p.y0[q] >> (8 * i)) & 0xff, i < 2 ? ta : tb);
+						o1[q][i] = yuv_pixel(A.m, (p.y1[q] >> (8 * i)) & 0xff, i < 2 ? ta : tb);
+					}
+				}
+#pragma unroll
+				for (int q = 0; q < 4; q++) if (4u * q < live) view_src_store4(d, q, o0[q], live, A.st);
+				if (row1) {
+#pragma unroll
+					for (int q = 0; q < 4; q++) if (4u * q < live) view_src_store4(d + A.w, q, o1[q], live, A.st);
+				}
+			} else {
+				const pf_raw<FMT> p = pf_load16<FMT, true>(fr, (size_t)A.sw * A.sh, (size_t)sy * A.sw + sx);
+				pf_u32x4 o[4];
+#pragma unroll
+				for (int i = 0; i < 16; i++) o[i >> 2][i & 3] = pf_pixel<FMT>(p, i);
+#pragma unroll
+				for (int q = 0; q < 4; q++) if (4u * q < live) view_src_store4(d, q, o[q], live, A.st);
+			}
+		} else {
+			for (uint32_t rr = 0; rr < (row1 ? 2u : 1u); rr++) {
+#pragma unroll
+				for (int q = 0; q < 4; q++) {
+					if (4u * q >= live) break;
+					pf_u32x4 o;
+#pragma unroll
+					for (int i = 0; i < 4; i++) o[i] = 4u * q + i < live ? sc_read<FMT>(fr, A.sw, A.sh, sx + 4 * q + i, sy + rr, A.m) : 0u;
+					view_src_store4(d + (size_t)rr * A.w, q, o, live, A.st);
+				}
+			}
+		}
+	}
+}
+
 // ---- a decoded XRGB32 clip written at a target size in any of the seven layouts (AGMV_SCALE_NEAREST / _BILINEAR of include/agmv.h) ----
 // 1080p XRGB32 is 8.3 MB out per frame from 0.3 MB in, and the source batch stays in L2, so the taps are plain gathers.  A lane
 // forms 16 consecutive target pixels of a row (YUV: 16 x 2, the patch of k_yuv_from_xrgb) in registers; where the target's rows of
@@ -1791,6 +1874,35 @@ extern "C" int agmv_hip_view_frames_async(agmv_hip_ctx* c, const uint32_t* d_src
 	else if (st4) VIEW_LAUNCH(false, true);
 	else VIEW_LAUNCH(false, false);
 #undef VIEW_LAUNCH
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_view_source_async(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t src_w, uint32_t src_h, uint32_t first, uint32_t step, uint32_t count,
+                                          uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t* d_dst, void* stream)
+{
+	if (fmt == PF_XRGB32) return agmv_hip_view_frames_async(c, (const uint32_t*)d_src, src_w, src_h, first, step, count, x, y, w, h, d_dst, stream);
+	if (agmv_hip_enter(c)) return -1;
+	if (!d_src || !d_dst || src_w == 0 || src_h == 0 || w == 0 || h == 0 || step == 0) return agmv_hip_err("agmv_hip: view needs clips, sizes and a step that are not zero");
+	if (x > src_w || w > src_w - x || y > src_h || h > src_h - y)
+		return agmv_hip_err("agmv_hip: the window %u x %u at (%u, %u) does not lie inside the %u x %u frame", w, h, x, y, src_w, src_h);
+	const int yuv = yuv_base(fmt);
+	if (yuv ? bad_yuv(fmt, src_w, src_h) : bad_pixfmt(fmt)) return -1;
+	if (yuv && ((src_w | src_h) & 1)) return agmv_hip_err("agmv_hip: a view of a YUV 4:2:0 source needs an even frame size, got %u x %u", src_w, src_h);
+	if (count == 0) return 0;
+	ViewSrcArgs A;
+	A.src = (const uint8_t*)d_src; A.dst = d_dst; A.frame_bytes = clip_frame_bytes(fmt, src_w, src_h);
+	A.sw = src_w; A.sh = src_h; A.first = first; A.step = step; A.count = count; A.x = x; A.y = y; A.w = w; A.h = h;
+	A.gpr = w / 16 + ((w & 15) != 0);                          // groups of 16 pixels per output row
+	A.m = YUV_RD[(fmt >> 8) & 3];
+	// the source groups of the window's rows on 16-byte boundaries: RGBA32 needs multiples of 4 pixels, the byte-per-sample layouts of 16
+	const uint32_t px = fmt == PF_RGBA32 ? 3u : 15u;
+	A.ld = ((x | src_w) & px) == 0 && ((uintptr_t)d_src & 15) == 0 && !(yuv && (y & 1));
+	A.st = (w & 3) == 0 && ((uintptr_t)d_dst & 15) == 0;
+	const size_t items = (size_t)(yuv ? (h + 1) / 2 : h) * A.gpr;
+	if (items > 0xFFFFFFFFull) return agmv_hip_err("agmv_hip: window too large for one launch");
+	const dim3 grid((unsigned)((items + 255) / 256), count < VIEW_GRID_FRAMES ? count : VIEW_GRID_FRAMES);
+	clip_dispatch<PF_BYTES | PF_YUV>(fmt, [&](auto F) { hipLaunchKernelGGL(k_view_src<decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, A); });
 	CK(hipGetLastError());
 	return 0;
 }

@@ -834,44 +834,93 @@ int AGMV_EncodeFramesDev(const char* filename, const unsigned* d_frames, u32 num
 	return AGMV_EncodeFramesFmtDev(filename, d_frames, AGMV_PIXFMT_XRGB32, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule);
 }
 
-/* A clip that is not encoded as it lies there (a target size, a tensor; include/agmv.h has the rules): the XRGB32 clip it stands for
-   is materialised once on the library's device -- the source is read once in its own layout, where the histogram, the similarity
-   and the encode would each read it -- and AGMV_EncodeFramesDev runs on that.  Nothing of the source's size or layout is allocated.
-   How the clip is filled: the box filter, a gather through agmv_scale_index, or agmv_hip_tensor_to_xrgb_async. */
+/* A clip that is not encoded as it lies there (a target size, a tensor, a view; include/agmv.h has the rules): the XRGB32 clip it
+   stands for is materialised once on the library's device -- the source is read once in its own layout, where the histogram, the
+   similarity and the encode would each read it -- and AGMV_EncodeFramesDev runs on that.  Nothing of the source's size or layout is
+   allocated.  How the clip is filled: the box filter, a gather through agmv_scale_index, agmv_hip_tensor_to_xrgb_async, or the
+   windows of selected frames by agmv_hip_view_source_async.  FILL_AREA / FILL_NEAREST with a view scale those windows: they exist one
+   staging batch at a time, which the scaler reads as an XRGB32 source. */
+static AGMV_ENCODE_VIEW_STATS g_encode_view_stats;  /* of the last AGMV_EncodeViewDev */
+
+void AGMV_GetEncodeViewStats(AGMV_ENCODE_VIEW_STATS* out) { if (out) *out = g_encode_view_stats; }
+
 typedef struct clip_fill {
-	enum { FILL_AREA, FILL_NEAREST, FILL_TENSOR } how;
+	enum { FILL_AREA, FILL_NEAREST, FILL_TENSOR, FILL_VIEW } how;
 	const void* d_src;
 	int fmt;                               /* the AGMV_PIXFMT of d_src; FILL_TENSOR: its AGMV_TENSORFMT */
 	uint32_t src_w, src_h;                 /* of a source frame (FILL_TENSOR: not read, the clip has the tensor's size) */
 	const float* ab;                       /* FILL_TENSOR: a[3] then b[3] of the reading rule */
+	const AGMV_VIEW* view;                 /* FILL_VIEW, or a scale of a view: first, step and the window, resolved; clip frame j is source frame first + j * step */
+	AGMV_ENCODE_VIEW_STATS* stats;         /* where a view reports the clip it materialised; else NULL */
 } clip_fill;
 
-/* -4 where the clip (or the index of FILL_NEAREST) cannot be allocated, else what encode_frames_dev returns for the clip */
+/* A staging batch of a scaled view: as many windows as fit 256 MiB -- the size of the memory-side cache, taken as a bound
+   on memory, not as a tuned value -- and at least one; AGMV_VIEW_STAGE_FRAMES=n (read per call, a test aid) forces n. */
+#define VIEW_STAGE_BYTES ((size_t)256 << 20)
+
+static uint32_t view_stage_frames(size_t window_px, uint32_t length)
+{
+	const char* e = getenv("AGMV_VIEW_STAGE_FRAMES");
+	size_t n = e && atol(e) > 0 ? (size_t)atol(e) : VIEW_STAGE_BYTES / (4 * window_px);
+	if (n < 1) n = 1;
+	return n < length ? (uint32_t)n : length;
+}
+
+/* the windows of a view scaled into d_clip: batch by batch through d_stage, every launch on `stream` and in its order */
+static int fill_scaled_view(agmv_hip_ctx* c, const clip_fill* f, uint32_t n, uint32_t w, uint32_t h, uint32_t stage, uint32_t* d_stage, const uint32_t* d_index,
+                            uint32_t* d_clip, void* stream)
+{
+	const AGMV_VIEW* v = f->view;
+	const size_t npx = (size_t)w * h;
+	uint32_t j, nb;
+	for (j = 0; j < n; j += nb) {
+		nb = n - j < stage ? n - j : stage;
+		if (agmv_hip_view_source_async(c, f->fmt, f->d_src, f->src_w, f->src_h, v->first + j * v->step, v->step, nb, v->x, v->y, v->width, v->height, d_stage, stream))
+			return -1;
+		if (f->how == FILL_AREA ? agmv_hip_scale_area_dev(c, AGMV_PIXFMT_XRGB32, d_stage, v->width, v->height, nb, w, h, d_clip + j * npx, stream)
+		                        : agmv_fmt_gather(c, AGMV_PIXFMT_XRGB32, v->width, v->height, d_stage, nb, d_index, npx, d_clip + j * npx, stream))
+			return -1;
+	}
+	return 0;
+}
+
+/* -4 where the clip (or the index of FILL_NEAREST, or the staging batch of a scaled view) cannot be allocated, else what
+   encode_frames_dev returns for the clip */
 static int encode_materialised(const char* filename, const clip_fill* f, u32 num_of_frames, u32 width, u32 height, u32 frames_per_second, AGMV_OPT opt,
                                AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
 {
 	agmv_hip_ctx* c = ctx();
 	const uint32_t n = (uint32_t)num_of_frames, w = (uint32_t)width, h = (uint32_t)height;
 	const size_t npx = (size_t)w * h;
-	const int tensor = f->how == FILL_TENSOR;
-	uint32_t *d_clip = (uint32_t*)agmv_hip_malloc_on(c, 4 * npx * num_of_frames), *d_index = NULL, *index = NULL;
+	const int tensor = f->how == FILL_TENSOR, staged = f->view && f->how != FILL_VIEW;
+	const uint32_t from_w = staged ? f->view->width : f->src_w, from_h = staged ? f->view->height : f->src_h;      /* what the scaler reads */
+	const uint32_t stage = staged ? view_stage_frames((size_t)from_w * from_h, n) : 0;
+	uint32_t *d_clip = (uint32_t*)agmv_hip_malloc_on(c, 4 * npx * num_of_frames), *d_index = NULL, *index = NULL, *d_stage = NULL;
 	void* stream;
 	int failed, rc;
 	if (!d_clip) return -4;
 	if (f->how == FILL_NEAREST) {
-		index = agmv_scale_index(f->src_w, f->src_h, w, h);
+		index = agmv_scale_index(from_w, from_h, w, h);
 		d_index = (uint32_t*)agmv_hip_malloc_on(c, 4 * npx);
-		if (!index || !d_index) { free(index); agmv_hip_free_on(c, d_index); agmv_hip_free_on(c, d_clip); return -4; }
+	}
+	if (staged) d_stage = (uint32_t*)agmv_hip_malloc_on(c, 4 * (size_t)from_w * from_h * stage);
+	if ((f->how == FILL_NEAREST && (!index || !d_index)) || (staged && !d_stage)) {
+		free(index); agmv_hip_free_on(c, d_index); agmv_hip_free_on(c, d_stage); agmv_hip_free_on(c, d_clip);
+		return -4;
 	}
 	stream = agmv_hip_stream_create(c);
-	if (!stream) agmv_die(tensor ? "stream for the tensor clip" : "stream for the scaled clip");
-	if (tensor) failed = agmv_hip_tensor_to_xrgb_async(c, f->fmt, f->d_src, npx, n, f->ab, d_clip, stream);
+	if (!stream) agmv_die(tensor ? "stream for the tensor clip" : f->view ? "stream for the view" : "stream for the scaled clip");
+	if (f->how == FILL_NEAREST && agmv_hip_memcpy_async(c, d_index, index, 4 * npx, 0, stream)) failed = -1;
+	else if (tensor) failed = agmv_hip_tensor_to_xrgb_async(c, f->fmt, f->d_src, npx, n, f->ab, d_clip, stream);
+	else if (f->how == FILL_VIEW)
+		failed = agmv_hip_view_source_async(c, f->fmt, f->d_src, f->src_w, f->src_h, f->view->first, f->view->step, n, f->view->x, f->view->y, w, h, d_clip, stream);
+	else if (staged) failed = fill_scaled_view(c, f, n, w, h, stage, d_stage, d_index, d_clip, stream);
 	else if (f->how == FILL_AREA) failed = agmv_hip_scale_area_dev(c, f->fmt, f->d_src, f->src_w, f->src_h, n, w, h, d_clip, stream);
-	else failed = agmv_hip_memcpy_async(c, d_index, index, 4 * npx, 0, stream) ||
-	              agmv_fmt_gather(c, f->fmt, f->src_w, f->src_h, f->d_src, n, d_index, npx, d_clip, stream);
-	if (failed || agmv_hip_stream_sync(c, stream)) agmv_die(tensor ? "tensor clip" : "frame scale");
+	else failed = agmv_fmt_gather(c, f->fmt, f->src_w, f->src_h, f->d_src, n, d_index, npx, d_clip, stream);
+	if (failed || agmv_hip_stream_sync(c, stream)) agmv_die(tensor ? "tensor clip" : f->view ? "view of the source" : "frame scale");
 	agmv_hip_stream_destroy(c, stream);
-	free(index); agmv_hip_free_on(c, d_index);
+	free(index); agmv_hip_free_on(c, d_index); agmv_hip_free_on(c, d_stage);
+	if (f->stats) { f->stats->clip_bytes = 4ull * npx * n; f->stats->staging_bytes = 4ull * from_w * from_h * stage; }
 	rc = encode_frames_dev(filename, d_clip, AGMV_PIXFMT_XRGB32, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule);
 	agmv_hip_free_on(c, d_clip);
 	return rc;
@@ -1125,6 +1174,57 @@ int AGMV_DecodeViewTensorDev(const char* filename, void* d_tensor, AGMV_TENSORFM
 	const int refused = filename && known_tensor(type, mean, std, table) && !view_refused(view) ? (sized ? target_refused(width, height, filter) : 0) : -1;
 	memset(&g_view_stats, 0, sizeof(g_view_stats));
 	return refused ? refused : decode_result(decode_file(filename, AGMV_IMG_BMP, &sink, NULL, cap_frames, d_tensor == NULL, info), &decoded);
+}
+
+/* A view of a clip encoded (include/agmv.h has the rules).  encode_view_refused is everything that needs no device, in the header's
+   order; *r receives the view resolved against the clip: count = its length, width x height = the window's own size. */
+static int encode_view_refused(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height, const AGMV_VIEW* view,
+                               u32 width, u32 height, AGMV_SCALE filter, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule,
+                               AGMV_VIEW* r)
+{
+	const int sized = width != 0 || height != 0;
+	const unsigned long long src_px = (unsigned long long)src_width * src_height;
+	int sw, sh, rc;
+	if (!known_pixfmt((int)fmt) || !filename || !d_frames || (sized && filter != AGMV_SCALE_NEAREST && filter != AGMV_SCALE_AREA) || view_refused(view)) return -1;
+	*r = view ? *view : WHOLE_FILE;
+	r->count = agmv_view_length(r->first, r->step, r->count, num_of_frames > 0xFFFFFFFFul ? 0xFFFFFFFFu : (uint32_t)num_of_frames);
+	rc = encode_args_refused(r->count, opt, quality, compression, schedule);
+	if (rc == -1 || rc == -5) return rc;
+	if (src_width == 0 || src_height == 0 || src_width > 0xFFFFFFFFul || src_height > 0xFFFFFFFFul || src_px > (1ull << 28)) return -3;
+	if (r->width == 0) { r->width = (unsigned)src_width; r->height = (unsigned)src_height; }
+	if (r->x > src_width || r->width > src_width - r->x || r->y > src_height || r->height > src_height - r->y) return -3;
+	/* an NV12 / I420 window is cut out of the 2 x 2 cells of an even frame (agmv_hip_view_source_async); consecutive full frames are not cut */
+	if (AGMV_FMT_IS_YUV((int)fmt) && ((src_width | src_height) & 1) && !(r->step == 1 && r->width == src_width && r->height == src_height)) return -3;
+	scaled_size(opt, &sw, &sh);
+	if (!sized) {
+		if (sw ? r->width < 2 || r->height < 2 : bad_geometry(r->width, r->height)) return -3;
+	} else {
+		if (sw || width > 0xFFFFFFFFul || height > 0xFFFFFFFFul || bad_geometry((uint32_t)width, (uint32_t)height)) return -3;
+		if (filter == AGMV_SCALE_AREA && (width > r->width || height > r->height || (unsigned long long)r->width * r->height > (1ull << 24))) return -3;
+	}
+	return rc;
+}
+
+int AGMV_EncodeViewDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height, const AGMV_VIEW* view,
+                       u32 width, u32 height, AGMV_SCALE filter, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression,
+                       AGMV_SCHEDULE schedule)
+{
+	const int sized = width != 0 || height != 0;
+	AGMV_VIEW v;
+	clip_fill f = {sized ? (filter == AGMV_SCALE_AREA ? FILL_AREA : FILL_NEAREST) : FILL_VIEW, d_frames, (int)fmt, (uint32_t)src_width, (uint32_t)src_height, NULL, NULL,
+	               &g_encode_view_stats};
+	int rc, whole_frames;
+	memset(&g_encode_view_stats, 0, sizeof(g_encode_view_stats));
+	rc = encode_view_refused(filename, d_frames, fmt, num_of_frames, src_width, src_height, view, width, height, filter, opt, quality, compression, schedule, &v);
+	if (rc) return audio_consumed(rc);
+	whole_frames = v.step == 1 && v.width == src_width && v.height == src_height;
+	if (whole_frames) f.d_src = (const u8*)d_frames + (size_t)v.first * agmv_fmt_frame_bytes((int)fmt, f.src_w, f.src_h);     /* consecutive full frames: read in place */
+	else f.view = &v;
+	if (whole_frames && !sized) rc = encode_frames_dev(filename, f.d_src, fmt, v.count, src_width, src_height, frames_per_second, opt, quality, compression, schedule);
+	else rc = encode_materialised(filename, &f, v.count, sized ? width : v.width, sized ? height : v.height, frames_per_second, opt, quality, compression, schedule);
+	if (rc) memset(&g_encode_view_stats, 0, sizeof(g_encode_view_stats));
+	else g_encode_view_stats.frames = v.count;
+	return audio_consumed(rc);
 }
 
 /* The file's audio track into device memory in the layout `fmt` (include/agmv.h): the AGAC payloads gathered on the host into

@@ -7,6 +7,7 @@
 #include "agmv_hip.h"
 #include "agmv_hip_stabilise.h"
 #include "agmv_hip_view.h"
+#include "agmv_hip_view_source.h"
 #include "agmv_internal.h"
 
 typedef struct agmv_pool agmv_pool;

@@ -1,5 +1,5 @@
-"""ctypes binding of include/agmv_hip.h (the signatures are abi.HIP), include/agmv_hip_view.h (abi.HIP_VIEW) and
-include/agmv_hip_stabilise.h (abi.HIP_STABILISE).
+"""ctypes binding of include/agmv_hip.h (the signatures are abi.HIP), include/agmv_hip_view.h (abi.HIP_VIEW),
+include/agmv_hip_view_source.h (abi.HIP_VIEW_SOURCE) and include/agmv_hip_stabilise.h (abi.HIP_STABILISE).
 
 The product is the shared library; this module only marshals pointers.  torch is used for
 device memory and streams (plumbing).  Every failure is loud: a missing library raises
@@ -53,6 +53,7 @@ def load_library(path=None):
     # only an explicitly named other build of the same source may lack symbols; the default library has them all
     abi.bind(L, abi.HIP, missing_ok=path is not None)
     abi.bind(L, abi.HIP_VIEW, missing_ok=path is not None)
+    abi.bind(L, abi.HIP_VIEW_SOURCE, missing_ok=path is not None)
     abi.bind(L, abi.HIP_STABILISE, missing_ok=path is not None)
     _libs[p] = L
     return L
@@ -788,6 +789,31 @@ class AgmvHip:
         _check_vec("view_frames_async: out", out, count * win_w * win_h)
         s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
         self._ck(self.L.agmv_hip_view_frames_async(self.ctx, src.data_ptr(), w, h, first, step, count, x, y, win_w, win_h, out.data_ptr(), s))
+        return out
+
+    # ------------------------------------------------------------------ a view of a clip in any layout (agmv_hip_view_source_async of include/agmv_hip_view_source.h)
+    def view_source(self, fmt, src, w, h, first, step, count, x, y, win_w, win_h, out=None, yuv=None, full_range=False, stream=None):
+        """src: clip of whole frames of w x h pixels in fmt (any name of PIXFMT or YUVFMT, or its value) -> int32 [count, win_h, win_w]
+        of 0x00RRGGBB: the window win_w x win_h at (x, y) of the frames first, first + step, ... (count of them, all inside src) as
+        pixels_to_xrgb_dev / yuv_to_xrgb_dev give them ("xrgb32": whole words as they are), or `out`, a contiguous CUDA int32 tensor
+        (or view at any element offset) of at least that many words (agmv_hip_view_source_async) on `stream` (a torch stream;
+        None = torch's current one).  Nothing waits."""
+        import torch
+        w, h, first, step, count, x, y, win_w, win_h = (int(v) for v in (w, h, first, step, count, x, y, win_w, win_h))
+        if step < 1 or count < 0 or first < 0:
+            raise ValueError("view_source: first >= 0, step >= 1 and count >= 0 are needed, got %d, %d, %d" % (first, step, count))
+        n = first + (count - 1) * step + 1 if count else 0
+        if fmt in YUVFMT or (isinstance(fmt, int) and (fmt & 0xFF) in YUVFMT.values()):
+            fmt = self._check_yuv("view_source: src", fmt, src, w, h, n, yuv, full_range)
+        else:
+            if yuv is not None or full_range:
+                raise ValueError("view_source: yuv= and full_range= belong to fmt \"nv12\" and \"i420\", not to fmt %r" % (fmt,))
+            fmt = self._check_clip("view_source: src", fmt, src, n * self.pixfmt_frame_bytes(fmt, w * h))
+        if out is None:
+            out = torch.empty((count, win_h, win_w), dtype=torch.int32, device=src.device)
+        _check_vec("view_source: out", out, count * win_w * win_h)
+        s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self._ck(self.L.agmv_hip_view_source_async(self.ctx, fmt, src.data_ptr(), w, h, first, step, count, x, y, win_w, win_h, out.data_ptr(), s))
         return out
 
     # ------------------------------------------------------------------ normalised float tensor clips (AGMV_TENSORFMT of include/agmv.h)

@@ -1,5 +1,5 @@
 """Whole .agmv sequences from and to frames in GPU memory: ctypes calls of AGMV_EncodeFramesFmtDev / AGMV_EncodeFramesScaledDev /
-AGMV_DecodeFramesFmtDev / AGMV_DecodeFramesScaledDev / AGMV_EncodeFramesTensorDev / AGMV_DecodeFramesTensorDev (include/agmv.h, libagmv.so).  No logic here: the schedules, the container, both LZ stages and the reading and writing of the
+AGMV_EncodeViewDev / AGMV_DecodeFramesFmtDev / AGMV_DecodeFramesScaledDev / AGMV_EncodeFramesTensorDev / AGMV_DecodeFramesTensorDev (include/agmv.h, libagmv.so).  No logic here: the schedules, the container, both LZ stages and the reading and writing of the
 caller's pixel layout are the library's; torch holds the frames.  The frames live on the library's own device (env AGMV_DEVICE,
 default 0).
 clip_quality / file_quality (AGMV_MeasureFramesDev / AGMV_MeasureFileDev) measure a decoded clip, or a file batch by batch, against
@@ -160,7 +160,8 @@ def _track_geometry(audio, sample_rate):
 
 
 def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedule=SCHEDULE_PDIFS, fmt=None, yuv=None, full_range=False,
-                  size=None, scale="area", palette_refine=None, dither=None, audio=None, sample_rate=None, mean=None, std=None, stabilise=None):
+                  size=None, scale="area", palette_refine=None, dither=None, audio=None, sample_rate=None, mean=None, std=None, stabilise=None,
+                  select=None, crop=None, fit=None):
     """frames: contiguous CUDA tensor of n frames on the library's device, in the layout `fmt` (see the module text; None = inferred
     from the tensor, which never gives "nv12" or "i420") -> the file at `path`.  yuv ("bt601", the default, or "bt709") and
     full_range go with the two YUV layouts only.  size=(h, w), in tensor order, scales the clip to that size first
@@ -179,8 +180,18 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
     A float32 / float16 / bfloat16 [n, 3, h, w] tensor (fmt "f32" / "f16" / "bf16", or inferred from the dtype) is a normalised
     tensor clip, model output as it is: mean= and std= (a number or three per channel; defaults 0 and 1) say what its values
     stand for, and the file is that of the XRGB32 clip the reading rule of include/agmv.h gives (AGMV_EncodeFramesTensorDev).
-    yuv=, full_range= and size= do not go with a tensor clip; mean= and std= go with nothing else."""
+    yuv=, full_range= and size= do not go with a tensor clip; mean= and std= go with nothing else.
+    select=, crop= and fit= encode a view of the clip (AGMV_EncodeViewDev of include/agmv.h) without a copy of the selection: select is
+    a range, a slice (resolved against the clip's length) or a tuple (start, stop, step), steps >= 1 only, as decode_frames(frames=)
+    takes them; crop=(top, left, height, width), in tensor order, is a window of every frame, which must lie inside it -- anywhere,
+    odd offsets and sizes included, for "nv12" and "i420" too; fit="crop" needs size= and no crop= and takes fit_window() of the
+    frame and the target, the largest centred window of the target's aspect.  The file is that of the contiguous XRGB32 clip of the
+    selected windows, scaled to size= where that is given; fps is written as given.  An empty selection is refused, and none of
+    the three goes with a tensor clip.  encode_view_stats() says what the call materialised."""
     import torch
+    select, crop = _decode_selection(select, crop, who="encode_frames", name="select")
+    if fit is not None and not (fit == "crop" and size is not None and crop is None):
+        raise ValueError("encode_frames: fit must be None or \"crop\", which needs size=(h, w) and no crop=, got fit=%r, size=%r, crop=%r" % (fit, size, crop))
     if dither is not None and not (isinstance(dither, int) and not isinstance(dither, bool) and 1 <= dither <= 64):
         raise ValueError("encode_frames: dither must be None or an int from 1 to 64, got %r" % (dither,))
     if stabilise is not None and not (isinstance(stabilise, int) and not isinstance(stabilise, bool) and 1 <= stabilise <= 64):
@@ -192,9 +203,24 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
     if tensor is not None:
         if yuv is not None or full_range or target is not None:
             raise ValueError("encode_frames: yuv=, full_range= and size= do not go with a tensor clip (fmt %r)" % (fmt,))
+        if select is not None or crop is not None or fit is not None:
+            raise ValueError("encode_frames: select=, crop= and fit= do not go with a tensor clip (fmt %r)" % (fmt,))
         v, n, h, w = tensor[:4]
     else:
         v, n, h, w = _clip_geometry(frames, fmt, yuv, full_range)
+    view = None
+    if select is not None or crop is not None or fit is not None:
+        sel = _resolve_selection(select, n)
+        if len(sel) == 0:
+            raise ValueError("encode_frames: select=%r takes no frame of a clip of %d" % (select, n))
+        if fit is not None:
+            crop = fit_window(h, w, target[1], target[2])
+        view = abi.AGMV_VIEW(sel.start, len(sel), sel.step, 0, 0, 0, 0)
+        if crop is not None:
+            top, left, ch, cw = crop
+            if top + ch > h or left + cw > w:
+                raise ValueError("encode_frames: crop %r does not lie inside the %d x %d frames of the clip" % (tuple(crop), w, h))
+            view.x, view.y, view.width, view.height = left, top, cw, ch
     track = None
     if audio is not None:
         track = _track_geometry(audio, sample_rate)
@@ -222,6 +248,13 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
             if rc:
                 raise ValueError("AGMV_EncodeFramesTensorDev refused its arguments (%d): %d frames of %dx%d, mean %r, std %r, opt %d, schedule %d"
                                  % (rc, n, w, h, mean, std, opt, schedule))
+            return
+        if view is not None:
+            filt, th, tw = target if target is not None else (0, 0, 0)
+            rc = L.AGMV_EncodeViewDev(os.fsencode(path), frames.data_ptr(), v, n, w, h, C.byref(view), tw, th, filt, fps, opt, quality, compression, schedule)
+            if rc:
+                raise ValueError("AGMV_EncodeViewDev refused its arguments (%d): %d frames of %dx%d, select %r, crop %r, size %r (%s), opt %d, schedule %d"
+                                 % (rc, n, w, h, sel, crop, size, scale, opt, schedule))
             return
         if target is None:
             rc = L.AGMV_EncodeFramesFmtDev(os.fsencode(path), frames.data_ptr(), v, n, w, h, fps, opt, quality, compression, schedule)
@@ -252,6 +285,15 @@ def stabilise_stats():
     return int(st.examined), int(st.replaced)
 
 
+def encode_view_stats():
+    """(frames, clip_bytes, staging_bytes) of the last encode_frames(select= / crop= / fit=) of this process (AGMV_GetEncodeViewStats of
+    include/agmv.h): the frames encoded, the bytes of the XRGB32 clip the call materialised (0 where the source was encoded in
+    place) and of its staging batch (0 without one); all 0 behind a refused call"""
+    st = abi.AGMV_ENCODE_VIEW_STATS()
+    load_library().AGMV_GetEncodeViewStats(C.byref(st))
+    return int(st.frames), int(st.clip_bytes), int(st.staging_bytes)
+
+
 def _decode_target(size, scale):
     """(filter value, h, w) of decode_frames' size= and scale=, or None for size=None; touches neither the library nor the device"""
     if not isinstance(scale, str) or scale not in DECODE_SCALE:
@@ -269,24 +311,45 @@ def _is_int(v):
     return isinstance(v, int) and not isinstance(v, bool)
 
 
-def _decode_selection(frames, crop):
-    """decode_frames' frames= and crop= checked -> (a range or a slice or None, crop); touches neither the library nor the device"""
+def _decode_selection(frames, crop, who="decode_frames", name="frames"):
+    """decode_frames' frames= (encode_frames' select=) and crop= checked, in the name of the caller `who` -> (a range or a slice or None,
+    crop); touches neither the library nor the device"""
     if isinstance(frames, tuple):
         if not (len(frames) == 3 and all(_is_int(v) for v in frames) and frames[2] >= 1):
-            raise ValueError("decode_frames: frames as a tuple must be (start, stop, step), three ints with step >= 1, got %r" % (frames,))
+            raise ValueError("%s: %s as a tuple must be (start, stop, step), three ints with step >= 1, got %r" % (who, name, frames))
         frames = range(*frames)
     if isinstance(frames, range):
         if frames.step < 1 or frames.start < 0:
-            raise ValueError("decode_frames: frames must start at 0 or later and step forwards, got %r" % (frames,))
+            raise ValueError("%s: %s must start at 0 or later and step forwards, got %r" % (who, name, frames))
     elif isinstance(frames, slice):
         if not (all(v is None or _is_int(v) for v in (frames.start, frames.stop, frames.step)) and (frames.step is None or frames.step >= 1)):
-            raise ValueError("decode_frames: frames as a slice needs ints and a step >= 1, got %r" % (frames,))
+            raise ValueError("%s: %s as a slice needs ints and a step >= 1, got %r" % (who, name, frames))
     elif frames is not None:
-        raise ValueError("decode_frames: frames must be a range, a slice or a tuple (start, stop, step), got %r" % (frames,))
+        raise ValueError("%s: %s must be a range, a slice or a tuple (start, stop, step), got %r" % (who, name, frames))
     if crop is not None and not (isinstance(crop, (tuple, list)) and len(crop) == 4 and all(_is_int(v) for v in crop)
                                  and crop[0] >= 0 and crop[1] >= 0 and crop[2] > 0 and crop[3] > 0):
-        raise ValueError("decode_frames: crop must be (top, left, height, width), four ints with a height and a width above 0, got %r" % (crop,))
+        raise ValueError("%s: crop must be (top, left, height, width), four ints with a height and a width above 0, got %r" % (who, crop))
     return frames, crop
+
+
+def _resolve_selection(sel, n):
+    """a checked selection against a clip or file of n frames -> the range of the frames it takes"""
+    return range(n) if sel is None else range(*sel.indices(n)) if isinstance(sel, slice) else range(sel.start, min(sel.stop, n), sel.step)
+
+
+def fit_window(src_h, src_w, h, w):
+    """(top, left, height, width) of the largest centred window of a src_h x src_w frame that has the aspect of an h x w target, in
+    integers (`//` on non-negative ints): the full height where the source is the wider of the two, else the full width.  What
+    encode_frames(fit="crop") takes; touches neither the library nor the device."""
+    if not all(_is_int(v) and v > 0 for v in (src_h, src_w, h, w)):
+        raise ValueError("fit_window: four positive ints are needed, got %r" % ((src_h, src_w, h, w),))
+    if src_w * h >= src_h * w:
+        ch, cw = src_h, src_h * w // h
+    else:
+        cw, ch = src_w, src_w * h // w
+    if ch == 0 or cw == 0:
+        raise ValueError("fit_window: a %d x %d frame holds no window of the aspect of %d x %d" % (src_w, src_h, w, h))
+    return (src_h - ch) // 2, (src_w - cw) // 2, ch, cw
 
 
 def _decode_view(path, v, tensor, target, scale, frames, crop, fmt):
@@ -303,7 +366,7 @@ def _decode_view(path, v, tensor, target, scale, frames, crop, fmt):
     if rc < 0:
         raise (ValueError if rc == -1 else RuntimeError)("%s(%s): %s" % (call, path, "the normalisation is refused" if rc == -1 else "Error %d" % -rc))
     n, h, w = info.number_of_frames, info.height, info.width
-    sel = range(n) if frames is None else range(*frames.indices(n)) if isinstance(frames, slice) else range(frames.start, min(frames.stop, n), frames.step)
+    sel = _resolve_selection(frames, n)
     view = abi.AGMV_VIEW(sel.start if len(sel) else 0, len(sel), sel.step, 0, 0, 0, 0)
     if crop is not None:
         top, left, ch, cw = crop
