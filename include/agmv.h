@@ -640,6 +640,44 @@ int AGMV_DecodeViewTensorDev(const char* filename, void* d_tensor, AGMV_TENSORFM
                              u32 height, AGMV_SCALE filter, const AGMV_VIEW* view, u32 cap_frames, AGMV_INFO* info);
 void AGMV_GetViewStats(AGMV_VIEW_STATS* out);
 
+/* Deblocking: the edges of the 4x4 block grid of a decoded clip smoothed between reconstruction and the sink.  Opt-in; the decoder's
+   own state is never filtered.  What a file decodes to is dominated by flat FILL blocks, a gradient comes back as a staircase of
+   squares, and a scaling sink magnifies every step; this is the decoder's counterpart of the encoder's dither.  The rule, in
+   integers only, which tests/deblock_cases.py states in numpy:
+     frames    w x h packed XRGB32 pixels, w and h multiples of 4.  Channels are the three low bytes; bits 24 .. 31 of every pixel
+               are copied from the source.
+     s         the strength, 1 .. 64.
+     stage 1   vertical edges: for every row y and every x = 4, 8, ..., w - 4 the line p1 p0 | q0 q1 = columns x-2, x-1, x, x+1 of
+               the decoded frame.
+     stage 2   horizontal edges: for every column x and every y = 4, 8, ..., h - 4 the line p1 p0 | q0 q1 = rows y-2, y-1, y, y+1 of
+               stage 1's result.  Each stage is a function of its input only.
+     decision  per line, over R, G and B together:  step = max_c |p0_c - q0_c|,  side = max_c max(|p1_c - p0_c|, |q1_c - q0_c|).
+               A line with step = 0 or step > s is left as it is; any other line is STRONG when side <= s >> 2, else WEAK.
+     weak      per channel  p0' = (p1 + 2 p0 + q0 + 2) >> 2,  q0' = (p0 + 2 q0 + q1 + 2) >> 2;  p1 and q1 are kept.
+     strong    per channel, with a = p1 + p0 and b = q0 + q1:
+               p1' = (7a + b + 8) >> 4,  p0' = (5a + 3b + 8) >> 4,  q0' = (3a + 5b + 8) >> 4,  q1' = (a + 7b + 8) >> 4
+               (two flat blocks A | B become the ramp 7:1, 5:3, 3:5, 1:7).
+     counters  the weak and the strong lines of both stages, two 64-bit counts; the same clip gives the same counts on every run.
+   What follows: every result lies in 0 .. 255; a frame without a step across a block edge comes back unchanged; every pixel
+   belongs to exactly one line per stage, so the 4x4 cell around a block corner (pixels 4i-2 .. 4i+1 x 4j-2 .. 4j+1, clipped at
+   the rim) depends on its own 16 pixels alone and the rule needs no halo.  agmv_hip_deblock_frames_async of
+   include/agmv_hip_deblock.h is the kernel.
+   AGMV_SetDeblock sets the strength for the sequence decoders -- AGMV_DecodeFramesDev, ...FmtDev, ...ScaledDev, ...TensorDev,
+   AGMV_DecodeViewDev, ...ViewTensorDev, AGMV_MeasureFileDev and the BMP export of AGMV_DecodeAGMV / AGMV_DecodeVideo: 0 = not set,
+   then env AGMV_DEBLOCK decides (a decimal number 1 .. 64 and nothing else in the value; anything else is off), and without it the filter is off and every decode is what it was
+   without this knob, launch for launch; values above 64 count as 64.  The knob is read when a decode is opened.  Each batch is
+   filtered once, whole frames at the file's size, behind the decoder's I-frame snapshot and in front of the sink: before a view's
+   window and stride and before any scaling, so frame j of a deblocked view is the window of frame first + j * step of the
+   deblocked full decode.  The last frame and the I-frame snapshot that the next batch decodes from stay unfiltered.
+   AGMV_DecodeFrameChunk (one frame, FILE*, state in the AGMV object) is NOT covered.
+   AGMV_GetDeblockStats reports the last sequence decode of this process (zeroed when it opens, set when it closes): the
+   strength, the frames filtered (for a view: those from the GOP it starts at), lines = frames * ((w/4 - 1) * h + (h/4 - 1) * w)
+   examined, and the weak and strong counts.  All zero when the knob was off.  With AGMV_TRACE in the environment the strength is
+   printed at open and the counts at close. */
+typedef struct AGMV_DEBLOCK_STATS { unsigned strength, frames; unsigned long long lines, weak, strong; } AGMV_DEBLOCK_STATS;
+void AGMV_SetDeblock(unsigned strength);
+void AGMV_GetDeblockStats(AGMV_DEBLOCK_STATS* out);
+
 /* A view of a clip encoded: 1080p60 NV12 from a capture as the 240 x 160, 15 fps file of this codec -- every 4th frame, the centred
    1440 x 1080 window of each, scaled -- without a copy of the selection.  The view is the AGMV_VIEW above with the same field rules,
    now resolved against the clip of num_of_frames frames of src_width x src_height in the layout `fmt`: view == NULL is the whole

@@ -1,6 +1,6 @@
 """The public C signatures, stated once: the structures of include/agmv.h that Python passes, every function of
-include/agmv_hip.h (HIP), of include/agmv_hip_view.h (HIP_VIEW), of include/agmv_hip_view_source.h (HIP_VIEW_SOURCE) and of
-include/agmv_hip_stabilise.h (HIP_STABILISE) and every function of include/agmv.h that Python calls on libagmv.so (AGMV), as
+include/agmv_hip.h (HIP), of include/agmv_hip_view.h (HIP_VIEW), of include/agmv_hip_view_source.h (HIP_VIEW_SOURCE), of
+include/agmv_hip_stabilise.h (HIP_STABILISE) and of include/agmv_hip_deblock.h (HIP_DEBLOCK) and every function of include/agmv.h that Python calls on libagmv.so (AGMV), as
 name -> (restype, (argtypes...)).  bind() sets them on a loaded library.  tests/test_abi.py checks both tables and the
 structures against the headers.  ctypes only, and no library is loaded here: the test children import this module the
 way a C host would include the headers."""
@@ -41,10 +41,15 @@ class AGMV_STABILISE_STATS(Structure):
     _fields_ = [("examined", c_ulonglong), ("replaced", c_ulonglong)]
 
 
+class AGMV_DEBLOCK_STATS(Structure):
+    _fields_ = [("strength", c_uint), ("frames", c_uint), ("lines", c_ulonglong), ("weak", c_ulonglong), ("strong", c_ulonglong)]
+
+
 # vp: any pointer but the five below and `const char*`; ul: the header's u32; the enums and Bool are c_int
 vp, sz, u32, u64, ul = c_void_p, c_size_t, c_uint32, c_uint64, c_ulong
 INFO_P, QUALITY_P, ENTRY_P = POINTER(AGMV_INFO), POINTER(AGMV_FRAME_QUALITY), POINTER(AGMV_ENTRY)
 VIEW_P, VIEW_STATS_P, STABILISE_STATS_P = POINTER(AGMV_VIEW), POINTER(AGMV_VIEW_STATS), POINTER(AGMV_STABILISE_STATS)
+DEBLOCK_STATS_P = POINTER(AGMV_DEBLOCK_STATS)
 ENCODE_VIEW_STATS_P = POINTER(AGMV_ENCODE_VIEW_STATS)
 
 HIP = {
@@ -151,6 +156,11 @@ HIP_STABILISE = {
     "agmv_hip_stabilise_frames_async": (c_int, (vp, u32, vp, u32, u32, u32, u32, vp, vp)),
 }
 
+# include/agmv_hip_deblock.h, exported by the same library
+HIP_DEBLOCK = {
+    "agmv_hip_deblock_frames_async": (c_int, (vp, u32, vp, u32, u32, u32, vp, vp, vp)),
+}
+
 _SEQ = (c_char_p, c_char_p, c_char_p, c_ubyte, ul, ul, ul, ul, ul, c_int, c_int, c_int)     # the three BMP drivers, behind `agmv`
 _CLIP = (ul, ul, ul, ul, c_int, c_int, c_int, c_int)                 # frames, width, height, fps, opt, quality, compression, schedule
 
@@ -230,6 +240,8 @@ AGMV = {
     "AGMV_SetDither": (None, (c_uint,)),
     "AGMV_SetStabilise": (None, (c_uint,)),
     "AGMV_GetStabiliseStats": (None, (STABILISE_STATS_P,)),
+    "AGMV_SetDeblock": (None, (c_uint,)),
+    "AGMV_GetDeblockStats": (None, (DEBLOCK_STATS_P,)),
     "AGMV_EncodeFramesDev": (c_int, (c_char_p, vp) + _CLIP),
     "AGMV_DecodeFramesDev": (c_int, (c_char_p, vp, ul, INFO_P)),
     "AGMV_EncodeFramesFmtDev": (c_int, (c_char_p, vp, c_int) + _CLIP),

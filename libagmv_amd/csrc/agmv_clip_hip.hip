@@ -9,6 +9,7 @@
 //   k_view                    every step-th frame of an XRGB32 clip and a window of each, copied into a packed clip
 //   k_view_src                the same of a clip in any other layout, converted on the way: the encoder's view of its source
 //   k_stabilise               opt-in: still blocks of the P-frames of a batch replaced by their GOP's I-frame's, in place
+//   k_deblock                 opt-in: the block edges of a decoded clip smoothed, one lane per 4x4 cell around a block corner
 //   k_pix_* / k_yuv_*         the byte layouts and NV12 / I420 to and from XRGB32
 //   k_scale_area              the exact box-filter downscale of a clip in any of the seven layouts
 //   k_scale_up*               a decoded XRGB32 clip written at a target size, nearest or bilinear, in any of the seven layouts
@@ -26,6 +27,7 @@
 #include <type_traits>
 
 #include "agmv_hip_impl.h"
+#include "../../include/agmv_hip_deblock.h"
 #include "../../include/agmv_hip_stabilise.h"
 #include "../../include/agmv_hip_view.h"
 #include "../../include/agmv_hip_view_source.h"
@@ -372,6 +374,154 @@ __global__ __launch_bounds__(STAB_T, 3) void k_stabilise(uint32_t* __restrict__ 
 		unsigned long long total = 0;
 		for (int i = 0; i < STAB_T / 64; i++) total += s_cnt[i];
 		if (total) atomicAdd(replaced, total);
+	}
+}
+
+// Deblocking a decoded clip (agmv_hip_deblock_frames_async; include/agmv.h, "deblocking", holds the rule).  The 4x4 cell offset by
+// (2, 2) around a block corner -- pixels 4i-2 .. 4i+1 x 4j-2 .. 4j+1, clipped at the frame's rim -- holds every pixel of the lines
+// that cross it in either stage, so its 16 output pixels are a function of its 16 input pixels, and the (w/4 + 1) x (h/4 + 1) cells
+// partition the frame.  One lane owns one cell of one frame: blockIdx.x runs over the frame's cells in row-major order, blockIdx.y
+// strides over the frames, so a workgroup adds its counts once for all its frames.  Four unconditional row loads are issued before the
+// first use (a rim cell clamps its rows into the frame and loads the frame's first or last four columns, so no load hangs on a
+// branch), both stages run in registers, four row stores.  An interior cell's row starts 8 bytes off a 16-byte boundary of the clip: it
+// is ONE 16-byte access at 8-byte alignment (half the memory instructions of two 8-byte ones, and a wave's 64 rows are one
+// contiguous KiB either way); a rim cell in x stores the 8-byte half that exists.  A clip that is only 4-byte aligned takes word
+// accesses to the same words, as written; hipcc is free to merge them, and does.  The pixels see no LDS and no barrier; the counts are summed per wave by shuffles, per workgroup
+// through 32 bytes of LDS behind the last frame, and added with one 64-bit atomic per counter and workgroup.
+constexpr int DBK_T = 256;
+#define DBK_GRID_BLOCKS 16384u    // the workgroups a launch aims at: blockIdx.y spreads the frames over at most this many / gridDim.x rows ...
+#define DBK_GRID_FRAMES 65535u    // ... and never more than the axis holds; a longer clip takes further trips round the frame loop
+
+typedef uint32_t dbk_u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t dbk_u32x4 __attribute__((ext_vector_type(4)));
+
+template <bool VEC> __device__ __forceinline__ void dbk_load4(const uint32_t* p, uint32_t* c)
+{
+	if (VEC) {
+		dbk_u32x4 v;                                           // 16 bytes at 8-byte alignment: one global_load_dwordx4
+		__builtin_memcpy(&v, __builtin_assume_aligned(p, 8), 16);
+		c[0] = v.x; c[1] = v.y; c[2] = v.z; c[3] = v.w;
+	} else { c[0] = p[0]; c[1] = p[1]; c[2] = p[2]; c[3] = p[3]; }
+}
+
+template <bool VEC> __device__ __forceinline__ void dbk_store2(uint32_t* p, const uint32_t* c)
+{
+	if (VEC) *reinterpret_cast<dbk_u32x2*>(p) = dbk_u32x2{c[0], c[1]};
+	else { p[0] = c[0]; p[1] = c[1]; }
+}
+
+template <bool VEC> __device__ __forceinline__ void dbk_store4(uint32_t* p, const uint32_t* c)
+{
+	if (VEC) {
+		const dbk_u32x4 v = {c[0], c[1], c[2], c[3]};
+		__builtin_memcpy(__builtin_assume_aligned(p, 8), &v, 16);
+	} else { p[0] = c[0]; p[1] = c[1]; p[2] = c[2]; p[3] = c[3]; }
+}
+
+// bits 15 and 31 of the result are set where the 16-bit fields of a and b (each 0 .. 255) differ by at most t; K = 0x80008000 + t * 0x00010001.
+// u = K + a - b and v = K - a + b stay inside (0, 2^16) per field, so no borrow crosses a field, and v = 2K - u modulo 2^32.
+__device__ __forceinline__ uint32_t dbk_near(uint32_t a, uint32_t b, uint32_t K)
+{
+	const uint32_t u = a + K - b;
+	return u & (2u * K - u);
+}
+
+// one line p1 p0 | q0 q1 of one stage, in place.  R and B are worked on in the two 16-bit fields of x & 0x00FF00FF, G in the low
+// field of a word of its own: the largest intermediate, 7 * 510 + 510 + 8, fits a field.
+__device__ __forceinline__ void dbk_line(uint32_t& P1, uint32_t& P0, uint32_t& Q0, uint32_t& Q1, bool on, uint32_t Ks, uint32_t Kq, uint32_t& weak, uint32_t& strong)
+{
+	const uint32_t M = 0x00FF00FFu, TOP = 0x80008000u;
+	const uint32_t p1r = P1 & M, p0r = P0 & M, q0r = Q0 & M, q1r = Q1 & M;
+	const uint32_t p1g = (P1 >> 8) & 0xFFu, p0g = (P0 >> 8) & 0xFFu, q0g = (Q0 >> 8) & 0xFFu, q1g = (Q1 >> 8) & 0xFFu;
+	const uint32_t step = dbk_near(p0r, q0r, Ks) & dbk_near(p0g, q0g, Ks);
+	const uint32_t side = dbk_near(p1r, p0r, Kq) & dbk_near(p1g, p0g, Kq) & dbk_near(q1r, q0r, Kq) & dbk_near(q1g, q0g, Kq);
+	const bool filt = on && ((P0 ^ Q0) & 0x00FFFFFFu) != 0 && (step & TOP) == TOP;
+	const bool st = filt && (side & TOP) == TOP, wk = filt && !st;
+	const uint32_t ar = p1r + p0r, br = q0r + q1r, ag = p1g + p0g, bg = q0g + q1g;
+	const uint32_t r8 = 0x00080008u, r2 = 0x00020002u;
+	uint32_t n1r = p1r, n0r = p0r, m0r = q0r, m1r = q1r, n1g = p1g, n0g = p0g, m0g = q0g, m1g = q1g;
+	if (st) {
+		n1r = ((7u * ar + br + r8) >> 4) & M; n1g = (7u * ag + bg + 8u) >> 4;
+		n0r = ((5u * ar + 3u * br + r8) >> 4) & M; n0g = (5u * ag + 3u * bg + 8u) >> 4;
+		m0r = ((3u * ar + 5u * br + r8) >> 4) & M; m0g = (3u * ag + 5u * bg + 8u) >> 4;
+		m1r = ((ar + 7u * br + r8) >> 4) & M; m1g = (ag + 7u * bg + 8u) >> 4;
+	} else if (wk) {
+		n0r = ((ar + p0r + q0r + r2) >> 2) & M; n0g = (ag + p0g + q0g + 2u) >> 2;
+		m0r = ((br + q0r + p0r + r2) >> 2) & M; m0g = (bg + q0g + p0g + 2u) >> 2;
+	}
+	P1 = (P1 & 0xFF000000u) | n1r | (n1g << 8);
+	P0 = (P0 & 0xFF000000u) | n0r | (n0g << 8);
+	Q0 = (Q0 & 0xFF000000u) | m0r | (m0g << 8);
+	Q1 = (Q1 & 0xFF000000u) | m1r | (m1g << 8);
+	weak += wk;
+	strong += st;
+}
+
+// the cell: stage 1 on its rows, stage 2 on its columns.  top / bottom: rows 0, 1 / 2, 3 lie in the frame; left / right: columns 0, 1 / 2, 3.
+// A rim cell has only the edges that exist, and its pixels outside the frame are never looked at.
+__device__ __forceinline__ void dbk_cell(uint32_t c[4][4], bool top, bool bottom, bool left, bool right, uint32_t Ks, uint32_t Kq, uint32_t& weak, uint32_t& strong)
+{
+#pragma unroll
+	for (int r = 0; r < 4; r++) dbk_line(c[r][0], c[r][1], c[r][2], c[r][3], left && right && (r < 2 ? top : bottom), Ks, Kq, weak, strong);
+#pragma unroll
+	for (int k = 0; k < 4; k++) dbk_line(c[0][k], c[1][k], c[2][k], c[3][k], top && bottom && (k < 2 ? left : right), Ks, Kq, weak, strong);
+}
+
+// cw = w/4 + 1 cells per cell row, ncell of them in a frame; bw = w/4 and bh = h/4 are the last cell column and row.  src == dst is
+// allowed (a lane reads its cell before it writes it, and no other lane touches it), so neither is __restrict__.
+template <bool VEC>
+__global__ __launch_bounds__(DBK_T) void k_deblock(const uint32_t* src, uint32_t* dst, uint32_t w, uint32_t cw, uint32_t bh, uint32_t ncell, size_t npx,
+                                                   uint32_t n_frames, uint32_t s, unsigned long long* counts)
+{
+	__shared__ uint32_t s_cnt[DBK_T / 64][2];
+	const uint32_t b = blockIdx.x * DBK_T + threadIdx.x;
+	const bool live = b < ncell;
+	const uint32_t cy = b / cw, cx = b - cy * cw;
+	const bool top = cy > 0, bottom = cy < bh, left = cx > 0, right = cx < cw - 1u;
+	// the cell's first pixel, (4 cx - 2, 4 cy - 2): outside the frame for a rim cell, whose rows and halves there are never touched
+	const ptrdiff_t in_frame = ((ptrdiff_t)cy * 4 - 2) * (ptrdiff_t)w + ((ptrdiff_t)cx * 4 - 2);
+	// where the loads go: rows 4 cy - 2 + r clamped to 0 .. h - 1, columns from 4 cx - 2, or 0 / w - 4 for the left / right rim
+	uint32_t row[4];
+#pragma unroll
+	for (int r = 0; r < 4; r++) { const int y = (int)cy * 4 - 2 + r; row[r] = y < 0 ? 0u : (uint32_t)y > bh * 4u - 1u ? bh * 4u - 1u : (uint32_t)y; }
+	const uint32_t col = !left ? 0u : right ? cx * 4u - 2u : w - 4u;
+	const uint32_t Ks = 0x80008000u + s * 0x00010001u, Kq = 0x80008000u + (s >> 2) * 0x00010001u;
+	uint32_t weak = 0, strong = 0;
+	if (live)
+		for (uint32_t f = blockIdx.y; f < n_frames; f += gridDim.y) {
+			uint32_t* out = dst + (size_t)f * npx + in_frame;
+			// four unconditional row loads, back to back: a row outside the frame is clamped into it (loaded, never looked at), and
+			// a rim cell in x loads the frame's first or last four columns, which hold its half
+			uint32_t v[4][4], c[4][4];
+#pragma unroll
+			for (int r = 0; r < 4; r++) dbk_load4<VEC>(src + (size_t)f * npx + (size_t)row[r] * w + col, v[r]);
+			// every loaded register is an operand: what reads a pixel comes behind this, every load in front of it
+			asm volatile("" : "+v"(v[0][0]), "+v"(v[0][1]), "+v"(v[0][2]), "+v"(v[0][3]), "+v"(v[1][0]), "+v"(v[1][1]), "+v"(v[1][2]), "+v"(v[1][3]),
+			             "+v"(v[2][0]), "+v"(v[2][1]), "+v"(v[2][2]), "+v"(v[2][3]), "+v"(v[3][0]), "+v"(v[3][1]), "+v"(v[3][2]), "+v"(v[3][3]));
+#pragma unroll
+			for (int r = 0; r < 4; r++) {
+				c[r][0] = right ? v[r][0] : v[r][2]; c[r][1] = right ? v[r][1] : v[r][3];
+				c[r][2] = left ? v[r][2] : v[r][0]; c[r][3] = left ? v[r][3] : v[r][1];
+			}
+			dbk_cell(c, top, bottom, left, right, Ks, Kq, weak, strong);
+#pragma unroll
+			for (int r = 0; r < 4; r++)
+				if (r < 2 ? top : bottom) {
+					uint32_t* p = out + (ptrdiff_t)r * w;
+					if (left && right) dbk_store4<VEC>(p, c[r]);
+					else if (left) dbk_store2<VEC>(p, c[r]);
+					else dbk_store2<VEC>(p + 2, c[r] + 2);
+				}
+		}
+	if (!counts) return;
+#pragma unroll
+	for (int d = 32; d; d >>= 1) { weak += __shfl_xor(weak, d); strong += __shfl_xor(strong, d); }
+	if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6][0] = weak; s_cnt[threadIdx.x >> 6][1] = strong; }
+	__syncthreads();
+	if (threadIdx.x < 2) {                                     // lane 0: the weak lines, lane 1: the strong ones
+		unsigned long long total = 0;
+		for (int i = 0; i < DBK_T / 64; i++) total += s_cnt[i][threadIdx.x];
+		if (total) atomicAdd(counts + threadIdx.x, total);
 	}
 }
 
@@ -1922,6 +2072,29 @@ extern "C" int agmv_hip_stabilise_frames_async(agmv_hip_ctx* c, uint32_t strengt
 	if (((uintptr_t)d_pix & 15u) == 0) STAB_LAUNCH(true);
 	else STAB_LAUNCH(false);
 #undef STAB_LAUNCH
+	CK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int agmv_hip_deblock_frames_async(agmv_hip_ctx* c, uint32_t strength, const uint32_t* d_src, uint32_t w, uint32_t h, uint32_t n_frames,
+                                             uint32_t* d_dst, unsigned long long* d_counts, void* stream)
+{
+	if (agmv_hip_enter(c)) return -1;
+	if (!d_src || ((uintptr_t)d_src & 3u) || !d_dst || ((uintptr_t)d_dst & 3u))
+		return agmv_hip_err("agmv_hip: deblock: d_src and d_dst must be 4-byte aligned device pointers");
+	if (agmv_hip_check_geometry(w, h)) return -1;
+	if (strength < 1 || strength > 64) return agmv_hip_err("agmv_hip: deblock: strength must be 1 .. 64 (got %u)", strength);
+	if (n_frames == 0) return 0;
+	const uint32_t cw = w / 4u + 1u, bh = h / 4u, ncell = cw * (bh + 1u), gx = (ncell + DBK_T - 1) / DBK_T;
+	uint32_t gy = DBK_GRID_BLOCKS / gx;
+	if (gy < 1u) gy = 1u;
+	if (gy > DBK_GRID_FRAMES) gy = DBK_GRID_FRAMES;
+	if (gy > n_frames) gy = n_frames;
+	const dim3 grid(gx, gy);
+#define DBK_LAUNCH(V) hipLaunchKernelGGL((k_deblock<V>), grid, dim3(DBK_T), 0, (hipStream_t)stream, d_src, d_dst, w, cw, bh, ncell, (size_t)w * h, n_frames, strength, d_counts)
+	if ((((uintptr_t)d_src | (uintptr_t)d_dst) & 7u) == 0) DBK_LAUNCH(true);
+	else DBK_LAUNCH(false);
+#undef DBK_LAUNCH
 	CK(hipGetLastError());
 	return 0;
 }

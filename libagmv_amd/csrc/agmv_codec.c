@@ -29,7 +29,7 @@
 static agmv_hip_ctx* g_ctx = NULL;
 static uint32_t g_pal[512];
 static int g_pal_mode = -1;
-static unsigned g_batch_frames = 0, g_lz_threads = 0, g_devices = 0, g_palette_refine = 0, g_dither = 0, g_stabilise = 0;
+static unsigned g_batch_frames = 0, g_lz_threads = 0, g_devices = 0, g_palette_refine = 0, g_dither = 0, g_stabilise = 0, g_deblock = 0;
 /* the device track AGMV_SetAudioDev attached to the next AGMV_EncodeFrames*Dev call (d_pcm NULL: none) */
 static struct { const void* d_pcm; int fmt; u32 samples, rate; u16 channels; } g_audio;
 static unsigned long g_export_count = 0;            /* AGIDL's expcount, extern/agidl/src/agidl_img_export.c:18 */
@@ -59,6 +59,7 @@ void AGMV_SetDevices(unsigned n) { g_devices = n; }
 void AGMV_SetPaletteRefine(unsigned n) { g_palette_refine = n; }
 void AGMV_SetDither(unsigned n) { g_dither = n; }
 void AGMV_SetStabilise(unsigned n) { g_stabilise = n; }
+void AGMV_SetDeblock(unsigned n) { g_deblock = n; }
 
 /* frames per GPU batch: what the caller asked for, else about 128 MB of source pixels (64 frames at most), whole GOPs */
 static unsigned batch_frames(size_t npx)
@@ -107,6 +108,19 @@ unsigned agmv_stabilise_strength(void)
 	const char* e = getenv("AGMV_STABILISE");
 	if (g_stabilise) return g_stabilise > 64 ? 64 : g_stabilise;
 	return e && atoi(e) >= 1 && atoi(e) <= 64 ? (unsigned)atoi(e) : 0;
+}
+
+/* strength of the deblocking a sequence decode opened now runs between reconstruction and its sink (AGMV_SetDeblock / env
+   AGMV_DEBLOCK, 1 .. 64; default 0 = off); agmv_decode_stream reads it */
+unsigned agmv_deblock_strength(void)
+{
+	const char* e = getenv("AGMV_DEBLOCK");
+	char* end;
+	unsigned long v;
+	if (g_deblock) return g_deblock > 64 ? 64 : g_deblock;
+	if (!e || *e < '0' || *e > '9') return 0;                  /* (no sign, no leading blank: a decimal number and nothing else) */
+	v = strtoul(e, &end, 10);
+	return *end == 0 && v >= 1 && v <= 64 ? (unsigned)v : 0;
 }
 
 /* host threads of the pipelines (BMP parse, LZ, BMP export): what the caller asked for, else the cores this process may

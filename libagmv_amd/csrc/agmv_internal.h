@@ -33,5 +33,6 @@ void agmv_palette_slots(const u32 clr[512], AGMV_OPT opt, u32 pal0[256], u32 pal
 void agmv_die(const char* what);
 unsigned agmv_dither_strength(void);
 unsigned agmv_stabilise_strength(void);
+unsigned agmv_deblock_strength(void);
 
 #endif

@@ -15,8 +15,9 @@
  *            calling thread: chunks written strictly in frame order
  *   decode   calling thread: chunks located, LZ stage on the host cores into pinned batch slabs, with ONE persistent buffer
  *            for the stale-tail semantics -- or, opt-in (AGMV_LZ_DECODE_DEVICE), on the GPU into device rows, the buffer
- *            on the device; GPU worker: (H2D ->) parse -> reconstruct -> D2H with the decoder state (last frame, I-frame
- *            snapshot) kept on the device; host cores: BMP export, one task per frame
+ *            on the device; GPU worker: (H2D ->) parse -> reconstruct -> (opt-in, AGMV_SetDeblock / AGMV_DEBLOCK: k_deblock,
+ *            into a copy) -> D2H with the decoder state (last frame, I-frame snapshot) kept on the device, unfiltered;
+ *            host cores: BMP export, one task per frame
  *
  * Both pipelines have a second end for frames that live in GPU memory (AGMV_EncodeFramesDev / AGMV_DecodeFramesDev): a device
  * SOURCE of the encoder (agmv_source: no BMP parse, no pinned staging, no upload -- the workers copy, gather or interpolate
@@ -832,6 +833,11 @@ typedef struct dbatch {
 	unsigned saves_left;
 } dbatch;
 
+/* the last sequence decode's AGMV_DEBLOCK_STATS: zeroed when agmv_decode_stream opens, set when the run that delivered closes */
+static AGMV_DEBLOCK_STATS g_deblock_stats;
+
+void AGMV_GetDeblockStats(AGMV_DEBLOCK_STATS* out) { if (out) *out = g_deblock_stats; }
+
 typedef struct dpipe {
 	agmv_hip_ctx* ctx;
 	void* stream;
@@ -853,10 +859,14 @@ typedef struct dpipe {
 	uint32_t* d_view;                      /* ... one batch of packed windows (sink_view), where the sink does not receive them directly */
 	int restart;                           /* ... the first decoded batch derives from the state before g0: the call runs again from frame 0 */
 	unsigned gpu_frames;                   /* frames through the GPU stage */
+	unsigned deblock;                      /* strength of the deblocking of every batch in front of its sink, 0 = off (AGMV_SetDeblock / AGMV_DEBLOCK) */
+	uint32_t* d_deblock;                   /* ... one batch of deblocked frames, where the sink does not receive them directly */
+	unsigned long long* d_dbcounts;        /* ... [2] the weak and the strong lines of this run, downloaded behind the worker's join */
 } dpipe;
 
 /* A packed XRGB32 clip at the file's size is decoded straight into its place, and the frame before a batch is the one before it there.
-   Every other sink takes the batch from the double buffer d_out, which exists for them alone and where the decoder's state stays. */
+   Every other sink takes the batch from the double buffer d_out, which exists for them alone and where the decoder's state stays.
+   With the deblocking on no sink is in place: the state stays unfiltered in d_out, and that clip receives the filter's output. */
 static int sink_in_place(const agmv_sink* s) { return s->kind == AGMV_SINK_FRAMES && s->frames.fmt == AGMV_PIXFMT_XRGB32 && !agmv_sink_target(s); }
 
 /* the box filter makes XRGB32: straight into an XRGB32 clip, through one batch of scaled frames (d_scaled) for any other layout and a tensor */
@@ -963,13 +973,13 @@ static int sink_view(dpipe* d, const dbatch* b, const uint32_t* out, uint32_t f0
 static void* dworker_main(void* p)
 {
 	dpipe* d = (dpipe*)p;
-	const int viewed = d->sink.viewed, direct = sink_in_place(&d->sink) && !viewed, to_bmp = d->sink.kind == AGMV_SINK_EXPORT;
+	const int viewed = d->sink.viewed, in_place = sink_in_place(&d->sink) && !viewed, direct = in_place && !d->deblock, to_bmp = d->sink.kind == AGMV_SINK_EXPORT;
 	unsigned id, prev_n = 0;
 	int have_state = 0;
 	for (id = 0;; id++) {
 		dbatch* b = &d->slot[id % d->nslots];
 		uint32_t* out;
-		const uint32_t* prev;
+		const uint32_t *prev, *sunk;
 		const uint8_t* bits;
 		const uint32_t* bpos;
 		unsigned k, skip, n;
@@ -1009,7 +1019,15 @@ static void* dworker_main(void* p)
 		for (k = 0; k < n; k++) if (((first + k) & 3u) == 0) last_i = (int)k;
 		if (!have_state && last_i < 0 && agmv_hip_memset_async(d->ctx, d->d_iframe, 0, d->npx * 4, d->stream)) goto fail;
 		if (last_i >= 0 && agmv_hip_memcpy_async(d->ctx, d->d_iframe, out + (size_t)last_i * d->npx, d->npx * 4, 2, d->stream)) goto fail;
-		if ((viewed ? sink_view(d, b, out, first, n) : sink_batch(d, b, out, d->w, d->h, n, first)) || agmv_hip_stream_sync(d->ctx, d->stream)) goto fail;
+		/* the sinks' frames: the batch as it was decoded, or, behind the snapshot, its deblocked copy (whole frames at the file's size,
+		   before a view's window and stride and before any scaling) -- in the caller's clip where that is packed XRGB32 of this size */
+		sunk = out;
+		if (d->deblock) {
+			uint32_t* to = in_place ? (uint32_t*)d->sink.frames.d_dst + (size_t)first * d->npx : d->d_deblock;
+			if (agmv_hip_deblock_frames_async(d->ctx, d->deblock, out, d->w, d->h, n, to, d->d_dbcounts, d->stream)) goto fail;
+			sunk = to;
+		}
+		if ((viewed ? sink_view(d, b, sunk, first, n) : sink_batch(d, b, sunk, d->w, d->h, n, first)) || agmv_hip_stream_sync(d->ctx, d->stream)) goto fail;
 		have_state = 1;
 		prev_n = n;
 		pthread_mutex_lock(&d->mu);
@@ -1232,9 +1250,10 @@ static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, dchunk* c, const u8* fil
    filled again, the batch that holds g0 is decoded from row g0 - first on.  *restart = 1 (and NO_ERR) when the worker found that
    the first decoded batch derives from the state before it: nothing that run delivered counts, and the caller runs g0 = 0. */
 static int decode_run(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
-                      int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink, uint32_t g0, AGMV_VIEW_STATS* stats, int* restart)
+                      int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink, uint32_t g0, unsigned deblock, AGMV_VIEW_STATS* stats,
+                      int* restart)
 {
-	const int viewed = sink->viewed, buffered = !sink_in_place(sink) || viewed, to_bmp = sink->kind == AGMV_SINK_EXPORT;
+	const int viewed = sink->viewed, buffered = !sink_in_place(sink) || viewed || deblock, to_bmp = sink->kind == AGMV_SINK_EXPORT;
 	const int view_packs = viewed && !sink_in_place(sink) && !(sink->view.step == 1 && sink->view.width == w && sink->view.height == h);
 	dpipe d;
 	dlz z;
@@ -1250,7 +1269,7 @@ static int decode_run(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos,
 	memset(&d, 0, sizeof(d));
 	memset(&z, 0, sizeof(z));
 	d.ctx = ctx; d.w = w; d.h = h; d.npx = npx; d.stride = (cap + 255) & ~(size_t)255;
-	d.cap = cap_frames; d.nslots = 3; d.sink = *sink; d.g0 = g0;
+	d.cap = cap_frames; d.nslots = 3; d.sink = *sink; d.g0 = g0; d.deblock = deblock;
 	pthread_mutex_init(&d.mu, NULL);
 	pthread_cond_init(&d.cv, NULL);
 	d.slot = (dbatch*)calloc(d.nslots, sizeof(dbatch));
@@ -1264,6 +1283,11 @@ static int decode_run(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos,
 	d.d_iframe = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4);
 	if (sink_needs_scaled(sink) && !(d.d_scaled = (uint32_t*)agmv_hip_malloc_on(ctx, (size_t)agmv_sink_target(sink)->w * agmv_sink_target(sink)->h * 4 * d.cap))) goto out;
 	if (view_packs && !(d.d_view = (uint32_t*)agmv_hip_malloc_on(ctx, (size_t)sink->view.width * sink->view.height * 4 * d.cap))) goto out;
+	if (deblock) {                                         /* the counters, and a batch of filtered frames for every sink but the packed clip */
+		if ((!sink_in_place(sink) || viewed) && !(d.d_deblock = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap))) goto out;
+		d.d_dbcounts = (unsigned long long*)agmv_hip_malloc_on(ctx, 2 * sizeof(unsigned long long));
+		if (!d.d_dbcounts || !d.stream || agmv_hip_memset_async(ctx, d.d_dbcounts, 0, 2 * sizeof(unsigned long long), d.stream) || agmv_hip_stream_sync(ctx, d.stream)) goto out;
+	}
 	if (sink->kind == AGMV_SINK_TENSOR) {                  /* 3 x 256 elements, once per call */
 		const size_t bytes = agmv_hip_tensor_frame_bytes(sink->tensor.type, 256);
 		d.d_table = agmv_hip_malloc_on(ctx, bytes);
@@ -1354,6 +1378,17 @@ static int decode_run(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos,
 	if (viewed) TRACE("decode: view from GOP start %u, %u frames through the LZ stage, %u through the GPU stage%s\n", (unsigned)g0, (unsigned)done, d.gpu_frames,
 	                  d.restart ? ", which depend on the state before them: again from frame 0" : "");
 	if (stats) { stats->lz_frames += done; stats->gpu_frames += d.gpu_frames; }
+	if (deblock && rc == NO_ERR && !d.restart) {           /* (the worker synchronised its stream behind its last batch) */
+		unsigned long long counts[2] = {0, 0};
+		if (agmv_hip_memcpy_async(ctx, counts, d.d_dbcounts, sizeof(counts), 1, d.stream) || agmv_hip_stream_sync(ctx, d.stream)) rc = MEMORY_CORRUPTION_ERR;
+		g_deblock_stats.strength = deblock;
+		g_deblock_stats.frames = d.gpu_frames;
+		g_deblock_stats.lines = (unsigned long long)d.gpu_frames * ((unsigned long long)(w / 4 - 1) * h + (unsigned long long)(h / 4 - 1) * w);
+		g_deblock_stats.weak = counts[0];
+		g_deblock_stats.strong = counts[1];
+		TRACE("decode: deblocking, strength %u: %u frames, %llu weak and %llu strong of %llu lines\n", deblock, g_deblock_stats.frames, counts[0], counts[1],
+		      g_deblock_stats.lines);
+	}
 out:
 	for (i = 0; i < d.nslots; i++) {
 		agmv_hip_host_free(d.slot[i].h_slab); agmv_hip_host_free(d.slot[i].h_bpos); agmv_hip_host_free(d.slot[i].h_out);
@@ -1362,7 +1397,7 @@ out:
 	dlz_close(&z);
 	agmv_hip_free_on(ctx, d.d_bits); agmv_hip_free_on(ctx, d.d_bpos); agmv_hip_free_on(ctx, d.d_nent);
 	agmv_hip_free_on(ctx, d.d_out[0]); agmv_hip_free_on(ctx, d.d_out[1]); agmv_hip_free_on(ctx, d.d_iframe); agmv_hip_free_on(ctx, d.d_scaled);
-	agmv_hip_free_on(ctx, d.d_table); agmv_hip_free_on(ctx, d.d_view);
+	agmv_hip_free_on(ctx, d.d_table); agmv_hip_free_on(ctx, d.d_view); agmv_hip_free_on(ctx, d.d_deblock); agmv_hip_free_on(ctx, d.d_dbcounts);
 	agmv_hip_stream_destroy(ctx, d.stream);
 	free(d.slot); free(persist); free(chunks); free(jobs);
 	pthread_mutex_destroy(&d.mu);
@@ -1376,13 +1411,16 @@ int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos
                        int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink, AGMV_VIEW_STATS* stats)
 {
 	const unsigned long count0 = *sink->count;
+	const unsigned deblock = agmv_deblock_strength();
 	int restart = 0, rc;
 	if (stats) memset(stats, 0, sizeof(*stats));
-	rc = decode_run(ctx, file, len, pos, w, h, nframes, ver, has_audio, cap_frames, threads, sink, sink->viewed ? sink->view.first & ~3u : 0, stats, &restart);
+	memset(&g_deblock_stats, 0, sizeof(g_deblock_stats));
+	if (deblock) TRACE("decode: deblocking of every batch in front of its sink, strength %u\n", deblock);
+	rc = decode_run(ctx, file, len, pos, w, h, nframes, ver, has_audio, cap_frames, threads, sink, sink->viewed ? sink->view.first & ~3u : 0, deblock, stats, &restart);
 	if (rc == NO_ERR && restart) {
 		*sink->count = count0;
 		if (stats) memset(stats, 0, sizeof(*stats));               /* (how far the LZ stage of the run given up had come is a matter of timing) */
-		rc = decode_run(ctx, file, len, pos, w, h, nframes, ver, has_audio, cap_frames, threads, sink, 0, stats, &restart);
+		rc = decode_run(ctx, file, len, pos, w, h, nframes, ver, has_audio, cap_frames, threads, sink, 0, deblock, stats, &restart);
 	}
 	if (stats) { stats->restarts = (unsigned)restart; stats->delivered = rc == NO_ERR ? (unsigned)(*sink->count - count0) : 0; }
 	return rc;

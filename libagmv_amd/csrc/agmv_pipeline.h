@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "agmv_hip.h"
+#include "agmv_hip_deblock.h"
 #include "agmv_hip_stabilise.h"
 #include "agmv_hip_view.h"
 #include "agmv_hip_view_source.h"

@@ -1,5 +1,6 @@
 """ctypes binding of include/agmv_hip.h (the signatures are abi.HIP), include/agmv_hip_view.h (abi.HIP_VIEW),
-include/agmv_hip_view_source.h (abi.HIP_VIEW_SOURCE) and include/agmv_hip_stabilise.h (abi.HIP_STABILISE).
+include/agmv_hip_view_source.h (abi.HIP_VIEW_SOURCE), include/agmv_hip_stabilise.h (abi.HIP_STABILISE) and
+include/agmv_hip_deblock.h (abi.HIP_DEBLOCK).
 
 The product is the shared library; this module only marshals pointers.  torch is used for
 device memory and streams (plumbing).  Every failure is loud: a missing library raises
@@ -55,6 +56,7 @@ def load_library(path=None):
     abi.bind(L, abi.HIP_VIEW, missing_ok=path is not None)
     abi.bind(L, abi.HIP_VIEW_SOURCE, missing_ok=path is not None)
     abi.bind(L, abi.HIP_STABILISE, missing_ok=path is not None)
+    abi.bind(L, abi.HIP_DEBLOCK, missing_ok=path is not None)
     _libs[p] = L
     return L
 
@@ -884,6 +886,31 @@ class AgmvHip:
         self._ck(self.L.agmv_hip_stabilise_frames_async(self.ctx, int(strength), pix.data_ptr(), w, h, pix.numel() // (w * h), int(first_fc),
                                                         count.data_ptr() if count is not None else None, s))
         return pix
+
+    # ------------------------------------------------------------------ deblocking of a decoded clip (include/agmv.h; agmv_hip_deblock_frames_async of include/agmv_hip_deblock.h)
+    def deblock_frames(self, pix, w, h, strength, out=None, counts=None, stream=None):
+        """pix: int32 CUDA tensor (or view at any element offset) of whole frames of w x h pixels, deblocked (agmv_hip_deblock_frames_async)
+        into out -- None = a new tensor of the same shape; pix itself is allowed, any other overlap is the caller's error -- on `stream`
+        (a torch stream; None = torch's current stream).  strength 1 .. 64.  counts: None, or an int64 CUDA tensor of two elements on
+        the same device, to which the weak and the strong lines are added (the caller sets them to zero).  Returns out; nothing waits."""
+        import torch
+        _check_vec("deblock_frames: pix", pix, 0)
+        w, h = int(w), int(h)
+        if w < 1 or h < 1 or pix.numel() % (w * h):
+            raise ValueError("deblock_frames: pix must hold whole frames of %d x %d pixels, got %d words" % (w, h, pix.numel()))
+        if out is None:
+            out = torch.empty_like(pix)
+        else:
+            _check_vec("deblock_frames: out", out, 0)
+            if out.numel() != pix.numel() or out.device != pix.device:
+                raise ValueError("deblock_frames: out must hold as many words as pix, on its device")
+        if counts is not None and not (counts.is_cuda and counts.dtype == torch.int64 and counts.numel() == 2 and counts.is_contiguous()
+                                       and counts.device == pix.device):
+            raise ValueError("deblock_frames: counts must be a contiguous int64 CUDA tensor of two elements on the device of pix")
+        s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self._ck(self.L.agmv_hip_deblock_frames_async(self.ctx, int(strength), pix.data_ptr(), w, h, pix.numel() // (w * h), out.data_ptr(),
+                                                      counts.data_ptr() if counts is not None else None, s))
+        return out
 
     # ------------------------------------------------------------------ pattern dithering against the context's palette (include/agmv.h)
     def dither_frames(self, pix, w, h, strength, stream=None):

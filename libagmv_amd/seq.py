@@ -26,6 +26,7 @@ Audio tracks (AGMV_PCMFMT; include/agmv.h, "audio tracks") and the tensors that 
   "s16"   int16 [n, ch]     interleaved, the WAV samples as they are     (16-bit track)
   "u8"    uint8 [n, ch]     interleaved unsigned bytes                   (8-bit track)
   "f32p"  float32 [ch, n]   planar, -1 .. 1, at most 8 channels (torchaudio)   (16-bit track)"""
+import contextlib
 import ctypes as C
 import os
 
@@ -397,7 +398,32 @@ def _decode_view(path, v, tensor, target, scale, frames, crop, fmt):
     return out[:rc], info
 
 
-def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False, size=None, scale="bilinear", mean=None, std=None, frames=None, crop=None):
+@contextlib.contextmanager
+def _deblock_for_this_call(who, deblock):
+    """AGMV_SetDeblock(deblock) around one decode, reset in a finally; anything but None or an int from 1 to 64 raises before the
+    library is touched"""
+    if deblock is not None and not (isinstance(deblock, int) and not isinstance(deblock, bool) and 1 <= deblock <= 64):
+        raise ValueError("%s: deblock must be None or an int from 1 to 64, got %r" % (who, deblock))
+    if deblock is None:
+        yield
+        return
+    L = load_library()
+    L.AGMV_SetDeblock(deblock)
+    try:
+        yield
+    finally:
+        L.AGMV_SetDeblock(0)
+
+
+def deblock_stats():
+    """what the deblocking did in the last sequence decode of this process (AGMV_GetDeblockStats of include/agmv.h) as a dict:
+    strength, frames filtered, lines examined, weak and strong lines; all zero when it was off"""
+    st = abi.AGMV_DEBLOCK_STATS()
+    load_library().AGMV_GetDeblockStats(C.byref(st))
+    return {"strength": int(st.strength), "frames": int(st.frames), "lines": int(st.lines), "weak": int(st.weak), "strong": int(st.strong)}
+
+
+def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False, size=None, scale="bilinear", mean=None, std=None, frames=None, crop=None, deblock=None):
     """-> (CUDA tensor of the file's frames on the library's device in the layout `fmt`: int32 [n, h, w] of 0x00RRGGBB for "xrgb32",
     uint8 [n, h, w, 3] / [n, h, w, 4] / [n, 3, h, w] for the byte formats, uint8 [n, h * 3 / 2, w] for "nv12" and "i420" (a file
     of even width and height; yuv and full_range as for encode_frames); AGMV_INFO of the header).  size=(h, w), in tensor order,
@@ -412,7 +438,15 @@ def decode_frames(path, fmt="xrgb32", yuv=None, full_range=False, size=None, sca
     a slice (resolved against the file's frame count) or a tuple (start, stop, step), steps >= 1 only; crop=(top, left, height, width),
     in tensor order, is a window of every frame, which must lie inside it.  Frame j of the result is the window of frame
     frames[j] of the full decode; layout, size=, scale= and the normalisation apply to the window as to a file of that size, and the
-    tensor holds as many frames as the selection has inside the file -- none, without a decode, for an empty one."""
+    tensor holds as many frames as the selection has inside the file -- none, without a decode, for an empty one.
+    deblock=s, an int from 1 to 64, smooths the edges of the 4x4 block grid of every decoded frame with that strength before the
+    layout, the view and the scaling see it (AGMV_SetDeblock of include/agmv.h, which holds the rule; set for this call only;
+    deblock_stats() says what it did); None leaves the library's knob as it is."""
+    with _deblock_for_this_call("decode_frames", deblock):
+        return _decode_frames(path, fmt, yuv, full_range, size, scale, mean, std, frames, crop)
+
+
+def _decode_frames(path, fmt, yuv, full_range, size, scale, mean, std, frames, crop):
     import torch
     target = _decode_target(size, scale)
     tensor = _tensor_clip(None, fmt, mean, std, "decode_frames")
@@ -564,10 +598,16 @@ def clip_quality(test, ref, fmt=None, yuv=None, full_range=False):
     return Quality(entries, n, w, h)
 
 
-def file_quality(path, ref, fmt=None, yuv=None, full_range=False):
+def file_quality(path, ref, fmt=None, yuv=None, full_range=False, deblock=None):
     """the file at `path`, decoded batch by batch and never held as a clip, against ref: its frames before they were encoded, in
     the layout `fmt` (as for clip_quality) -> Quality of the frames measured (AGMV_MeasureFileDev).  The reference must hold
-    exactly the header's number of frames, at the file's size."""
+    exactly the header's number of frames, at the file's size.  deblock=s measures the frames as decode_frames(deblock=s)
+    delivers them."""
+    with _deblock_for_this_call("file_quality", deblock):
+        return _file_quality(path, ref, fmt, yuv, full_range)
+
+
+def _file_quality(path, ref, fmt, yuv, full_range):
     import torch
     v, n, h, w = _clip_geometry(ref, fmt, yuv, full_range, who="file_quality")
     if not (ref.is_cuda and ref.device == torch.device(_device())):
