@@ -1052,8 +1052,13 @@ static void* dworker_main(void* p)
 	return NULL;
 }
 
+/* AGMV_FindNextFrameChunk / AGMV_FindNextAudioChunk (reference src/agmv_utils.c:140-194) from pos: the four bytes at pos are compared
+   once, the loop behind them reads its first four from pos + 4 and only then steps by one byte, so a FourCC that starts 1, 2 or 3
+   bytes behind pos is not found.  Returns len where the reference would never return. */
 static size_t scan_fourcc(const u8* d, size_t len, size_t pos, const char* cc)
 {
+	if (pos + 4 <= len && memcmp(d + pos, cc, 4) == 0) return pos;
+	pos += 4;
 	while (pos + 4 <= len) {
 		if (memcmp(d + pos, cc, 4) == 0) return pos;
 		pos++;

@@ -483,9 +483,12 @@ int orc_parse_header(const uint8_t* f, size_t len, orc_file_info* info, uint32_t
 	return 0;
 }
 
-/* src/agmv_utils.c:140-166: compare 4 bytes, step 1 byte */
+/* src/agmv_utils.c:140-166: the four bytes at pos are compared once (:145-152); the loop behind them reads its first four from
+   pos + 4 and only then steps by one byte (:154-162), so an 'AGFC' that starts 1, 2 or 3 bytes behind pos is never seen */
 size_t orc_find_next_frame_chunk(const uint8_t* f, size_t len, size_t pos)
 {
+	if (pos + 4 <= len && f[pos] == 'A' && f[pos + 1] == 'G' && f[pos + 2] == 'F' && f[pos + 3] == 'C') return pos;
+	pos += 4;
 	while (pos + 4 <= len) {
 		if (f[pos] == 'A' && f[pos + 1] == 'G' && f[pos + 2] == 'F' && f[pos + 3] == 'C') return pos;
 		pos++;
