@@ -820,17 +820,14 @@ void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start,
  * decode pipeline
  * ------------------------------------------------------------------------------------------ */
 typedef struct dbatch {
-	unsigned n;
-	uint32_t first;                        /* frame_count of its first frame */
-	unsigned skip;                         /* a view: its first rows, the frames before g0, do not enter the GPU stage */
+	unsigned n; uint32_t first;            /* the frames for the GPU stage, and the frame_count of the first of them */
+	unsigned skip;                         /* a view: the slot's rows in front of them, the frames before g0, which do not enter the GPU stage */
 	u8* h_slab;                           /* pinned [cap][stride] (host LZ stage) */
 	uint32_t *h_bpos, *h_out;              /* pinned [cap], [cap][npx] */
-	uint8_t* d_slab;                       /* AGMV_LZ_DECODE_DEVICE: the batch's rows [cap][stride] on the device, their bpos, and */
-	uint32_t* d_bpos;
+	uint8_t* d_slab; uint32_t* d_bpos;     /* AGMV_LZ_DECODE_DEVICE: the batch's rows [cap][stride] on the device, their bpos, and */
 	void* ready;                           /* the event behind their commit on the LZ stage's stream */
 	unsigned long name0;                   /* quick_export_<name0 + k>.bmp */
-	int filled, decoded;
-	unsigned saves_left;
+	int filled, decoded; unsigned saves_left;
 } dbatch;
 
 /* the last sequence decode's AGMV_DEBLOCK_STATS: zeroed when agmv_decode_stream opens, set when the run that delivered closes */
@@ -838,42 +835,47 @@ static AGMV_DEBLOCK_STATS g_deblock_stats;
 
 void AGMV_GetDeblockStats(AGMV_DEBLOCK_STATS* out) { if (out) *out = g_deblock_stats; }
 
+typedef struct dplan { int viewed, packed, in_place, direct, buffered, needs_scaled, view_whole, view_packs, deblock_buffered, to_bmp, lz_dev; } dplan;
+
 typedef struct dpipe {
-	agmv_hip_ctx* ctx;
-	void* stream;
-	uint32_t w, h;
-	size_t npx, stride;
-	unsigned cap, nslots;
-	dbatch* slot;
-	pthread_mutex_t mu;
-	pthread_cond_t cv;
-	unsigned nfilled;                      /* batches handed to the GPU worker */
-	int closing, failed;
-	agmv_pool* pool;
-	pthread_t th;
+	agmv_hip_ctx* ctx; void* stream;
+	uint32_t w, h; size_t npx, stride;
+	unsigned cap, nslots; dbatch* slot;
+	pthread_mutex_t mu; pthread_cond_t cv;
+	unsigned nfilled; int closing, failed; /* nfilled: batches handed to the GPU worker */
+	agmv_pool* pool; pthread_t th;
 	uint8_t* d_bits; uint32_t *d_bpos, *d_nent, *d_out[2], *d_iframe;
-	agmv_sink sink;                        /* where the batches go (agmv_pipeline.h); the four facts below are all that is derived from it */
-	uint32_t* d_scaled;                    /* sink_needs_scaled: one batch of scaled XRGB32 frames */
+	agmv_sink sink;                        /* where the batches go (agmv_pipeline.h) */
+	dplan plan;                            /* ... and everything that is derived from it (dplan_of); each calls for one batch of: */
+	uint32_t *d_scaled, *d_view, *d_deblock;               /* needs_scaled: scaled XRGB32 frames; view_packs: packed windows (sink_view); deblock_buffered: deblocked frames */
 	void* d_table;                         /* the tensor sink's table on the device, uploaded once per call */
 	uint32_t g0;                           /* a view: the GOP start at which the GPU stage begins, from the fresh state */
-	uint32_t* d_view;                      /* ... one batch of packed windows (sink_view), where the sink does not receive them directly */
 	int restart;                           /* ... the first decoded batch derives from the state before g0: the call runs again from frame 0 */
 	unsigned gpu_frames;                   /* frames through the GPU stage */
 	unsigned deblock;                      /* strength of the deblocking of every batch in front of its sink, 0 = off (AGMV_SetDeblock / AGMV_DEBLOCK) */
-	uint32_t* d_deblock;                   /* ... one batch of deblocked frames, where the sink does not receive them directly */
-	unsigned long long* d_dbcounts;        /* ... [2] the weak and the strong lines of this run, downloaded behind the worker's join */
+	unsigned long long* d_dbcounts;        /* deblock: [2] the weak and the strong lines of this run, downloaded behind the worker's join */
+	size_t lz_cap; u8* persist;            /* the reference's ONE decompression buffer, zero-initialised, and its bytes (device LZ stage: dlz.d_persist) */
+	struct dchunk* chunks; struct unlz* jobs;              /* [cap] the chunks of a batch, and the host LZ stage's jobs */
 } dpipe;
 
-/* A packed XRGB32 clip at the file's size is decoded straight into its place, and the frame before a batch is the one before it there.
-   Every other sink takes the batch from the double buffer d_out, which exists for them alone and where the decoder's state stays.
-   With the deblocking on no sink is in place: the state stays unfiltered in d_out, and that clip receives the filter's output. */
-static int sink_in_place(const agmv_sink* s) { return s->kind == AGMV_SINK_FRAMES && s->frames.fmt == AGMV_PIXFMT_XRGB32 && !agmv_sink_target(s); }
-
-/* the box filter makes XRGB32: straight into an XRGB32 clip, through one batch of scaled frames (d_scaled) for any other layout and a tensor */
-static int sink_needs_scaled(const agmv_sink* s)
+/* The plan of a run over a w x h file: what the driver branches on, derived here alone.  Whatever the sink, a batch is decoded at the file's size.
+   packed: a packed XRGB32 destination without a target size -- a clip of the file's size or, for a view, of its window's.
+   in_place: that and no view: the clip holds every frame where the decoder puts it, and no converter runs.
+   direct: in place and no deblocking: a batch is decoded straight into the caller's clip, and the frame before a batch is the one before it there.
+   buffered: every other run decodes into the double buffer d_out, which exists for them alone; the decoder's state stays there, unfiltered, and the sink takes the batch from it.
+   needs_scaled: the box filter makes XRGB32: straight into an XRGB32 clip, through d_scaled for any other layout and a tensor.
+   view_whole: the view's window is the whole frame.  view_packs: the frames a view selects are packed into d_view first: not for a packed
+   destination, which receives the windows itself, and not for consecutive whole frames, which are sunk from where they lie.
+   deblock_buffered: the filter writes d_deblock, from where the sink takes the batch; only the clip in place receives the filter's output itself. */
+static dplan dplan_of(const agmv_sink* s, uint32_t w, uint32_t h, unsigned deblock, int lz_dev)
 {
 	const agmv_target* t = agmv_sink_target(s);
-	return t && t->filter == AGMV_SCALE_AREA && !(s->kind == AGMV_SINK_FRAMES && s->frames.fmt == AGMV_PIXFMT_XRGB32);
+	const int xrgb = s->kind == AGMV_SINK_FRAMES && s->frames.fmt == AGMV_PIXFMT_XRGB32;
+	dplan p = {.viewed = s->viewed, .packed = xrgb && !t, .needs_scaled = t && t->filter == AGMV_SCALE_AREA && !xrgb, .to_bmp = s->kind == AGMV_SINK_EXPORT, .lz_dev = lz_dev};
+	p.in_place = p.packed && !p.viewed; p.direct = p.in_place && !deblock; p.buffered = !p.direct; p.deblock_buffered = deblock && !p.in_place;
+	p.view_whole = p.viewed && s->view.width == w && s->view.height == h;
+	p.view_packs = p.viewed && !p.packed && !(s->view.step == 1 && p.view_whole);
+	return p;
 }
 
 /* the bytes of one frame of the destination (MEASURE: of the reference clip); w x h is the file's size */
@@ -910,7 +912,7 @@ static int sink_batch(dpipe* d, const dbatch* b, const uint32_t* out, uint32_t s
 	int filter = t ? t->filter : 0;                            /* (sw x sh: the size of the frames at `out`) the filter still to apply, the target size */
 	const uint32_t tw = t ? t->w : sw, th = t ? t->h : sh;
 	const size_t at = (size_t)at_frame * sink_frame_bytes(s, sw, sh);
-	if (sink_needs_scaled(s)) {
+	if (d->plan.needs_scaled) {
 		if (agmv_hip_scale_area_dev(d->ctx, AGMV_PIXFMT_XRGB32, out, sw, sh, n, tw, th, d->d_scaled, d->stream)) return -1;
 		out = d->d_scaled; sw = tw; sh = th; filter = 0;
 	}
@@ -926,7 +928,7 @@ static int sink_batch(dpipe* d, const dbatch* b, const uint32_t* out, uint32_t s
 		void* dst = (u8*)s->frames.d_dst + at;
 		if (filter == AGMV_SCALE_AREA) return agmv_hip_scale_area_dev(d->ctx, AGMV_PIXFMT_XRGB32, out, sw, sh, n, tw, th, (uint32_t*)dst, d->stream);
 		if (filter) return agmv_hip_scale_frames_async(d->ctx, filter, out, sw, sh, n, s->frames.fmt, tw, th, dst, d->stream);
-		return sink_in_place(s) ? 0 : agmv_fmt_from_xrgb(d->ctx, s->frames.fmt, tw, th, out, n, dst, d->stream);      /* XRGB32 to the caller's layout */
+		return d->plan.in_place ? 0 : agmv_fmt_from_xrgb(d->ctx, s->frames.fmt, tw, th, out, n, dst, d->stream);      /* XRGB32 to the caller's layout */
 	}
 	}
 }
@@ -955,14 +957,14 @@ uint32_t agmv_view_in_batch(uint32_t first, uint32_t step, uint32_t count, uint3
 static int sink_view(dpipe* d, const dbatch* b, const uint32_t* out, uint32_t f0, unsigned nd)
 {
 	const AGMV_VIEW* v = &d->sink.view;
-	const int packed = sink_in_place(&d->sink), whole = v->width == d->w && v->height == d->h;
+	const int packed = d->plan.packed;
 	const size_t wpx = (size_t)v->width * v->height;
 	uint32_t row, index, *win;
 	const uint32_t len = agmv_view_in_batch(v->first, v->step, v->count, f0, nd, &row, &index);
 	if (!len) return 0;
 	*d->sink.count += len;                                     /* (this thread alone writes it during a view; it is read behind the join) */
 	win = packed ? (uint32_t*)d->sink.frames.d_dst + index * wpx : d->d_view;
-	if (whole && (v->step == 1 || len == 1)) {
+	if (d->plan.view_whole && (v->step == 1 || len == 1)) {
 		const uint32_t* src = out + (size_t)row * d->npx;
 		return packed ? agmv_hip_memcpy_async(d->ctx, win, src, wpx * 4 * len, 2, d->stream) : sink_batch(d, b, src, d->w, d->h, len, index);
 	}
@@ -970,84 +972,92 @@ static int sink_view(dpipe* d, const dbatch* b, const uint32_t* out, uint32_t f0
 	return packed ? 0 : sink_batch(d, b, win, v->width, v->height, len, index);
 }
 
+/* The worker, by step.  Take: batch id once the calling thread has handed it over; NULL when the pipe closes with none left. */
+static dbatch* dworker_take(dpipe* d, unsigned id)
+{
+	int handed;
+	pthread_mutex_lock(&d->mu);
+	while (!(id < d->nfilled) && !d->closing) pthread_cond_wait(&d->cv, &d->mu);
+	handed = id < d->nfilled;
+	pthread_mutex_unlock(&d->mu);
+	return handed ? &d->slot[id % d->nslots] : NULL;
+}
+
+/* Decode: the frames of batch id to *at on the worker's stream, behind the upload of their rows or, on the device, the LZ stage's commit; then
+   the state for the next batch.  prev_n: the frames of the batch before, 0 = the fresh state.  Returns 0, negative on error, 1 for the restart. */
+static int dworker_decode(dpipe* d, const dbatch* b, unsigned id, unsigned prev_n, uint32_t** at)
+{
+	const int direct = d->plan.direct;
+	const uint32_t skip = b->skip, n = b->n, first = b->first;
+	const uint8_t* bits = b->d_slab ? b->d_slab + (size_t)skip * d->stride : d->d_bits;
+	const uint32_t* bpos = b->d_slab ? b->d_bpos + skip : d->d_bpos;
+	uint32_t* out = *at = direct ? (uint32_t*)d->sink.frames.d_dst + (size_t)first * d->npx : d->d_out[id & 1];
+	const uint32_t* prev = !prev_n ? NULL : direct ? out - d->npx : d->d_out[(id - 1) & 1] + (size_t)(prev_n - 1) * d->npx;
+	unsigned k; int last_i = -1, dependent;
+	if (b->d_slab) {                       /* the LZ stage left the rows on the device: wait for their commit, on the device */
+		if (agmv_hip_stream_wait_event(d->ctx, d->stream, b->ready)) return -1;
+	} else if (agmv_hip_memcpy_async(d->ctx, d->d_bits, b->h_slab + (size_t)skip * d->stride, d->stride * n, 0, d->stream) ||
+	           agmv_hip_memcpy_async(d->ctx, d->d_bpos, b->h_bpos + skip, 4 * (size_t)n, 0, d->stream))
+		return -1;
+	if (agmv_hip_decode_bitstreams_dev(d->ctx, bits, d->stride, bpos, n, d->w, d->h, first, d->d_nent, out, prev, prev_n ? d->d_iframe : NULL, d->stream)) return -1;
+	d->gpu_frames += n;
+	/* a view that starts inside the file: is this batch a function of its own streams alone? */
+	dependent = !prev_n && d->g0 ? agmv_hip_decode_prior_dependent(d->ctx, d->w, d->h, d->stream) : 0;
+	if (dependent) return dependent < 0 ? -1 : 1;
+	/* the state stays on the device: img_data = the last frame (read in place from this batch's output), iframe = the last I-frame of the batch (src/agmv_decode.c:401-405) */
+	for (k = 0; k < n; k++) if (((first + k) & 3u) == 0) last_i = (int)k;
+	if (!prev_n && last_i < 0 && agmv_hip_memset_async(d->ctx, d->d_iframe, 0, d->npx * 4, d->stream)) return -1;
+	if (last_i >= 0 && agmv_hip_memcpy_async(d->ctx, d->d_iframe, out + (size_t)last_i * d->npx, d->npx * 4, 2, d->stream)) return -1;
+	return 0;
+}
+
+/* Deliver: the sinks' frames are the batch as it was decoded, or, behind the snapshot, its deblocked copy (whole frames at the file's size, before a
+   view's window and stride and before any scaling) -- in the caller's clip where that is in place.  On return the frames are where they belong. */
+static int dworker_deliver(dpipe* d, const dbatch* b, const uint32_t* out)
+{
+	if (d->deblock) {
+		uint32_t* to = d->plan.deblock_buffered ? d->d_deblock : (uint32_t*)d->sink.frames.d_dst + (size_t)b->first * d->npx;
+		if (agmv_hip_deblock_frames_async(d->ctx, d->deblock, out, d->w, d->h, b->n, to, d->d_dbcounts, d->stream)) return -1;
+		out = to;
+	}
+	if (d->plan.viewed ? sink_view(d, b, out, b->first, b->n) : sink_batch(d, b, out, d->w, d->h, b->n, b->first)) return -1;
+	return agmv_hip_stream_sync(d->ctx, d->stream) ? -1 : 0;
+}
+
+/* Release: the slot is free again, for the BMP export once the pool has saved its frames */
+static void dworker_release(dpipe* d, dbatch* b)
+{
+	const unsigned saves = d->plan.to_bmp ? b->n : 0; unsigned k;
+	pthread_mutex_lock(&d->mu);
+	if (!saves) b->filled = 0;                         /* the frames are where they belong */
+	else { b->decoded = 1; b->saves_left = saves; }
+	pthread_cond_broadcast(&d->cv);
+	pthread_mutex_unlock(&d->mu);
+	for (k = 0; k < saves; k++) {
+		savearg* sa = (savearg*)xmalloc(sizeof(*sa));
+		sa->d = d; sa->b = b; sa->k = k;
+		agmv_pool_submit(d->pool, save_task, sa);
+	}
+}
+
 static void* dworker_main(void* p)
 {
 	dpipe* d = (dpipe*)p;
-	const int viewed = d->sink.viewed, in_place = sink_in_place(&d->sink) && !viewed, direct = in_place && !d->deblock, to_bmp = d->sink.kind == AGMV_SINK_EXPORT;
 	unsigned id, prev_n = 0;
-	int have_state = 0;
-	for (id = 0;; id++) {
-		dbatch* b = &d->slot[id % d->nslots];
-		uint32_t* out;
-		const uint32_t *prev, *sunk;
-		const uint8_t* bits;
-		const uint32_t* bpos;
-		unsigned k, skip, n;
-		uint32_t first;
-		int last_i = -1;
-		pthread_mutex_lock(&d->mu);
-		while (!(id < d->nfilled) && !d->closing) pthread_cond_wait(&d->cv, &d->mu);
-		if (id >= d->nfilled) { pthread_mutex_unlock(&d->mu); break; }
-		pthread_mutex_unlock(&d->mu);
-		skip = b->skip; n = b->n - skip; first = b->first + skip;    /* (a view's first batch: from the GOP start g0 on; else the whole batch) */
-		bits = b->d_slab ? b->d_slab + (size_t)skip * d->stride : d->d_bits;
-		bpos = b->d_slab ? b->d_bpos + skip : d->d_bpos;
-		out = direct ? (uint32_t*)d->sink.frames.d_dst + (size_t)first * d->npx : d->d_out[id & 1];
-		prev = !have_state ? NULL : direct ? out - d->npx : d->d_out[(id - 1) & 1] + (size_t)(prev_n - 1) * d->npx;
-		if (b->d_slab) {                       /* the LZ stage left the rows on the device: wait for their commit, on the device */
-			if (agmv_hip_stream_wait_event(d->ctx, d->stream, b->ready)) goto fail;
-		} else if (agmv_hip_memcpy_async(d->ctx, d->d_bits, b->h_slab + (size_t)skip * d->stride, d->stride * n, 0, d->stream) ||
-		           agmv_hip_memcpy_async(d->ctx, d->d_bpos, b->h_bpos + skip, 4 * (size_t)n, 0, d->stream))
-			goto fail;
-		if (agmv_hip_decode_bitstreams_dev(d->ctx, bits, d->stride, bpos, n, d->w, d->h, first, d->d_nent, out, prev,
-		                                   have_state ? d->d_iframe : NULL, d->stream))
-			goto fail;
-		d->gpu_frames += n;
-		if (!have_state && d->g0) {            /* a view that starts inside the file: is this batch a function of its own streams alone? */
-			const int dependent = agmv_hip_decode_prior_dependent(d->ctx, d->w, d->h, d->stream);
-			if (dependent < 0) goto fail;
-			if (dependent) {
-				pthread_mutex_lock(&d->mu);
-				d->restart = d->failed = 1;        /* (failed: what stops the batch loop) */
-				pthread_cond_broadcast(&d->cv);
-				pthread_mutex_unlock(&d->mu);
-				break;
-			}
+	dbatch* b; uint32_t* out;
+	for (id = 0; (b = dworker_take(d, id)) != NULL; id++) {
+		int rc = dworker_decode(d, b, id, prev_n, &out);
+		if (!rc) rc = dworker_deliver(d, b, out);
+		if (rc) {                              /* (failed: what stops the batch loop, for the restart too) */
+			if (rc < 0) fprintf(stderr, "libagmv(amd): batch decode: %s (the AGMV hot path runs on the GPU only -- no CPU fallback)\n", agmv_hip_last_error());
+			pthread_mutex_lock(&d->mu);
+			d->failed = 1; d->restart = rc > 0;
+			pthread_cond_broadcast(&d->cv);
+			pthread_mutex_unlock(&d->mu);
+			break;
 		}
-		/* decoder state for the next batch stays on the device: img_data = the last frame (read in place from this batch's
-		   output), iframe = the last I-frame of the batch (src/agmv_decode.c:401-405) */
-		for (k = 0; k < n; k++) if (((first + k) & 3u) == 0) last_i = (int)k;
-		if (!have_state && last_i < 0 && agmv_hip_memset_async(d->ctx, d->d_iframe, 0, d->npx * 4, d->stream)) goto fail;
-		if (last_i >= 0 && agmv_hip_memcpy_async(d->ctx, d->d_iframe, out + (size_t)last_i * d->npx, d->npx * 4, 2, d->stream)) goto fail;
-		/* the sinks' frames: the batch as it was decoded, or, behind the snapshot, its deblocked copy (whole frames at the file's size,
-		   before a view's window and stride and before any scaling) -- in the caller's clip where that is packed XRGB32 of this size */
-		sunk = out;
-		if (d->deblock) {
-			uint32_t* to = in_place ? (uint32_t*)d->sink.frames.d_dst + (size_t)first * d->npx : d->d_deblock;
-			if (agmv_hip_deblock_frames_async(d->ctx, d->deblock, out, d->w, d->h, n, to, d->d_dbcounts, d->stream)) goto fail;
-			sunk = to;
-		}
-		if ((viewed ? sink_view(d, b, sunk, first, n) : sink_batch(d, b, sunk, d->w, d->h, n, first)) || agmv_hip_stream_sync(d->ctx, d->stream)) goto fail;
-		have_state = 1;
-		prev_n = n;
-		pthread_mutex_lock(&d->mu);
-		if (!to_bmp) b->filled = 0;                        /* the frames are where they belong: the slot is free again */
-		else { b->decoded = 1; b->saves_left = b->n; }
-		pthread_cond_broadcast(&d->cv);
-		pthread_mutex_unlock(&d->mu);
-		for (k = 0; to_bmp && k < b->n; k++) {
-			savearg* sa = (savearg*)xmalloc(sizeof(*sa));
-			sa->d = d; sa->b = b; sa->k = k;
-			agmv_pool_submit(d->pool, save_task, sa);
-		}
-		continue;
-	fail:
-		fprintf(stderr, "libagmv(amd): batch decode: %s (the AGMV hot path runs on the GPU only -- no CPU fallback)\n", agmv_hip_last_error());
-		pthread_mutex_lock(&d->mu);
-		d->failed = 1;
-		pthread_cond_broadcast(&d->cv);
-		pthread_mutex_unlock(&d->mu);
-		break;
+		prev_n = b->n;
+		dworker_release(d, b);
 	}
 	return NULL;
 }
@@ -1084,9 +1094,10 @@ static size_t behind_chunk(const u8* file, size_t len, size_t c, size_t used, in
    the guard, src/agmv_decode.c:171-198).  So the chunks of a batch are first located as if every reader stopped right
    behind its payload (locate_chunks), the LZ stage decompresses them all at once and reports what each reader consumed,
    and the true positions are then checked in order (cut_batch): at the first chunk that was not where it was assumed the
-   batch is cut, and the next one starts from the true position.  A chunk: its "AGFC" at `at`, its header fields, `avail` bytes
-   of file behind its 16-byte header, and the `used` payload bytes that its LZ stage reports. */
+   batch is cut, and the next one starts from the true position.  A chunk: its "AGFC" at `at`, the usize and csize fields of its 16-byte header, the
+   `avail` bytes of file behind that header, the `used` payload bytes that its LZ stage reports; chunk_payload: the payload bytes that the file holds. */
 typedef struct dchunk { size_t at; uint32_t usize, csize; size_t avail, used; } dchunk;
+static size_t chunk_payload(const dchunk* c) { return c->csize < c->avail ? c->csize : c->avail; }
 
 static unsigned locate_chunks(const u8* file, size_t len, size_t pos, int has_audio, dchunk* c, unsigned want)
 {
@@ -1095,7 +1106,7 @@ static unsigned locate_chunks(const u8* file, size_t len, size_t pos, int has_au
 		const size_t at = scan_fourcc(file, len, pos, "AGFC");
 		if (at + 16 > len) break;
 		c[n].at = at; c[n].usize = le32(file + at + 8); c[n].csize = le32(file + at + 12); c[n].avail = len - (at + 16);
-		pos = behind_chunk(file, len, at, c[n].csize < c[n].avail ? c[n].csize : c[n].avail, has_audio);
+		pos = behind_chunk(file, len, at, chunk_payload(&c[n]), has_audio);
 	}
 	return n;
 }
@@ -1111,7 +1122,7 @@ size_t agmv_gather_audio(const u8* file, size_t len, size_t pos, uint32_t nframe
 		const unsigned want = nframes < 64 ? (unsigned)nframes : 64u, n = locate_chunks(file, len, pos, 1, c, want);
 		unsigned k;
 		for (k = 0; k < n && total < cap; k++) {
-			const size_t behind = c[k].at + 16 + (c[k].csize < c[k].avail ? c[k].csize : c[k].avail), ac = scan_fourcc(file, len, behind, "AGAC");
+			const size_t ac = scan_fourcc(file, len, c[k].at + 16 + chunk_payload(&c[k]), "AGAC");
 			size_t size, held;
 			if (ac + 8 > len) return total;
 			size = le32(file + ac + 4);
@@ -1242,128 +1253,131 @@ static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, dchunk* c, const u8* fil
 	return (int)n;
 }
 
-/* the frame loop of AGMV_DecodeAGMV / AGMV_DecodeVideo on a file image: `pos` = first byte behind the header.
-   The LZ stage of a batch (between locate_chunks and cut_batch) runs on the pool, one frame per task, or with
-   AGMV_LZ_DECODE_DEVICE=1 on the GPU (dlz_batch).  The bytes behind bpos that the block parser may read on an over-run are
-   those of the reference's ONE persistent buffer: the host stage takes them from `persist` in frame order, which then
-   receives the frame.  The frames go to `sink` (agmv_pipeline.h), whose count advances by the frames decoded.  Whatever the sink, a
-   batch is decoded at the file's size; only a packed XRGB32 clip of that size receives it in place (sink_in_place), every other
-   sink -- another layout, a target size, a tensor, the BMP export, the measurement -- gets it from the double buffer by sink_batch.
-   A view (sink->viewed; nframes then ends behind the last frame it needs) is always decoded into the double buffer and leaves it
-   through sink_view.  Its LZ stage runs from frame 0 like any other, because only that keeps the persistent buffer right; its GPU
-   stage starts at the GOP start g0 from the fresh state: a batch wholly before g0 is not handed to the worker and its slot is
-   filled again, the batch that holds g0 is decoded from row g0 - first on.  *restart = 1 (and NO_ERR) when the worker found that
-   the first decoded batch derives from the state before it: nothing that run delivered counts, and the caller runs g0 = 0. */
-static int decode_run(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
-                      int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink, uint32_t g0, unsigned deblock, AGMV_VIEW_STATS* stats,
-                      int* restart)
+/* The host LZ stage of a batch, dlz_batch's counterpart: locate up to `want` chunks from *pos, decompress them on the pool, one frame per task, into
+   the rows of b's pinned slab, cut the batch, and then, in frame order and for the frames before the cut, a row takes its stale tail from the
+   persistent buffer and the buffer takes the row.  Returns the frames of the batch (0: none left); nothing in this stage can fail. */
+static int host_lz_batch(dpipe* d, dbatch* b, dchunk* c, const u8* file, size_t len, size_t* pos, unsigned want, int ver, int has_audio, size_t cap)
 {
-	const int viewed = sink->viewed, buffered = !sink_in_place(sink) || viewed || deblock, to_bmp = sink->kind == AGMV_SINK_EXPORT;
-	const int view_packs = viewed && !sink_in_place(sink) && !(sink->view.step == 1 && sink->view.width == w && sink->view.height == h);
-	dpipe d;
-	dlz z;
+	unsigned left, k, n = left = locate_chunks(file, len, *pos, has_audio, c, want);
+	for (k = 0; k < n; k++) {
+		unlz* j = &d->jobs[k];
+		j->d = d; j->ver = ver; j->c = &c[k]; j->left = &left; j->cap = cap;
+		j->payload = file + c[k].at + 16; j->row = b->h_slab + (size_t)k * d->stride;
+		agmv_pool_submit(d->pool, unlz_task, j);
+	}
+	pthread_mutex_lock(&d->mu);
+	while (left) pthread_cond_wait(&d->cv, &d->mu);
+	pthread_mutex_unlock(&d->mu);
+	n = cut_batch(file, len, has_audio, c, n, pos);
+	for (k = 0; k < n; k++) {                              /* in order: stale bytes, persistent buffer */
+		const unlz* j = &d->jobs[k];
+		const size_t bp = j->bpos, tail = bp + 16 < d->stride ? 16 : (bp < d->stride ? d->stride - bp : 0);
+		if (tail) memcpy(j->row + bp, d->persist + bp, tail);
+		memcpy(d->persist, j->row, bp < cap ? bp : cap);
+		b->h_bpos[k] = j->bpos;
+	}
+	return (int)n;
+}
+
+/* Everything a run holds, from the plan: a buffer the plan does not call for stays NULL, one it calls for is checked where it is
+   made.  The pool and the worker start last.  Returns 0, or -1 with the pipe half-opened: dpipe_close takes it as it is. */
+static int dpipe_open(dpipe* d, dlz* z, agmv_hip_ctx* ctx, uint32_t w, uint32_t h, unsigned cap_frames, unsigned threads, const agmv_sink* sink, uint32_t g0, unsigned deblock)
+{
 	const char* lzv = getenv("AGMV_LZ_DECODE_DEVICE");     /* opt-in: the LZ stage on the GPU (read when a decode starts) */
-	const int lz_dev = lzv && atoi(lzv) == 1;
-	const size_t npx = (size_t)w * h, cap = npx * 33 / 16 + 4096;
-	u8* persist = (u8*)calloc(cap, 1);                     /* the reference's ONE decompression buffer, zero-initialised */
-	dchunk* chunks = (dchunk*)calloc(cap_frames, sizeof(dchunk));           /* the chunks of a batch, and the host LZ stage's jobs */
-	unlz* jobs = lz_dev ? NULL : (unlz*)calloc(cap_frames, sizeof(unlz));
-	uint32_t done = 0;
-	unsigned id = 0, i;
-	int rc = MEMORY_CORRUPTION_ERR;                        /* until everything is set up: what any failure on the way there returns */
-	memset(&d, 0, sizeof(d));
-	memset(&z, 0, sizeof(z));
-	d.ctx = ctx; d.w = w; d.h = h; d.npx = npx; d.stride = (cap + 255) & ~(size_t)255;
-	d.cap = cap_frames; d.nslots = 3; d.sink = *sink; d.g0 = g0; d.deblock = deblock;
-	pthread_mutex_init(&d.mu, NULL);
-	pthread_cond_init(&d.cv, NULL);
-	d.slot = (dbatch*)calloc(d.nslots, sizeof(dbatch));
-	if (!d.slot) { d.nslots = 0; goto out; }
-	d.stream = agmv_hip_stream_create(ctx);
-	d.d_bits = lz_dev ? NULL : (uint8_t*)agmv_hip_malloc_on(ctx, d.stride * d.cap);      /* (the host LZ stage's upload slab) */
-	d.d_bpos = lz_dev ? NULL : (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
-	d.d_nent = (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
-	d.d_out[0] = buffered ? (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap) : NULL;
-	d.d_out[1] = buffered ? (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap) : NULL;
-	d.d_iframe = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4);
-	if (sink_needs_scaled(sink) && !(d.d_scaled = (uint32_t*)agmv_hip_malloc_on(ctx, (size_t)agmv_sink_target(sink)->w * agmv_sink_target(sink)->h * 4 * d.cap))) goto out;
-	if (view_packs && !(d.d_view = (uint32_t*)agmv_hip_malloc_on(ctx, (size_t)sink->view.width * sink->view.height * 4 * d.cap))) goto out;
-	if (deblock) {                                         /* the counters, and a batch of filtered frames for every sink but the packed clip */
-		if ((!sink_in_place(sink) || viewed) && !(d.d_deblock = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4 * d.cap))) goto out;
-		d.d_dbcounts = (unsigned long long*)agmv_hip_malloc_on(ctx, 2 * sizeof(unsigned long long));
-		if (!d.d_dbcounts || !d.stream || agmv_hip_memset_async(ctx, d.d_dbcounts, 0, 2 * sizeof(unsigned long long), d.stream) || agmv_hip_stream_sync(ctx, d.stream)) goto out;
+	const dplan* p = &d->plan;
+	const agmv_target* t = agmv_sink_target(sink);
+	const size_t table = sink->kind == AGMV_SINK_TENSOR ? agmv_hip_tensor_frame_bytes(sink->tensor.type, 256) : 0;       /* 3 x 256 elements, uploaded once per call */
+	const size_t npx = (size_t)w * h, lz_cap = npx * 33 / 16 + 4096, stride = (lz_cap + 255) & ~(size_t)255;
+	const size_t batch = npx * 4 * cap_frames, rows = stride * cap_frames;     /* a batch of XRGB32 frames at the file's size; of LZ stage rows */
+	unsigned i;
+	memset(d, 0, sizeof(*d)); memset(z, 0, sizeof(*z));
+	pthread_mutex_init(&d->mu, NULL); pthread_cond_init(&d->cv, NULL);
+	d->ctx = ctx; d->w = w; d->h = h; d->npx = npx; d->lz_cap = lz_cap; d->stride = stride; d->cap = cap_frames;
+	d->sink = *sink; d->g0 = g0; d->deblock = deblock; d->plan = dplan_of(sink, w, h, deblock, lzv && atoi(lzv) == 1);
+	d->persist = (u8*)calloc(lz_cap, 1); d->chunks = (dchunk*)calloc(d->cap, sizeof(dchunk)); d->slot = (dbatch*)calloc(3, sizeof(dbatch));
+	if (!d->persist || !d->chunks || !d->slot || (!p->lz_dev && !(d->jobs = (unlz*)calloc(d->cap, sizeof(unlz))))) return -1;
+	d->nslots = 3;
+	if (!(d->stream = agmv_hip_stream_create(ctx))) return -1;
+	if (!p->lz_dev && (!(d->d_bits = (uint8_t*)agmv_hip_malloc_on(ctx, rows)) || !(d->d_bpos = (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d->cap)))) return -1;
+	if (!(d->d_nent = (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d->cap))) return -1;         /* (d_bits: the host LZ stage's upload slab) */
+	if (p->buffered && (!(d->d_out[0] = (uint32_t*)agmv_hip_malloc_on(ctx, batch)) || !(d->d_out[1] = (uint32_t*)agmv_hip_malloc_on(ctx, batch)))) return -1;
+	if (!(d->d_iframe = (uint32_t*)agmv_hip_malloc_on(ctx, npx * 4))) return -1;
+	if (p->needs_scaled && !(d->d_scaled = (uint32_t*)agmv_hip_malloc_on(ctx, (size_t)t->w * t->h * 4 * d->cap))) return -1;
+	if (p->view_packs && !(d->d_view = (uint32_t*)agmv_hip_malloc_on(ctx, (size_t)sink->view.width * sink->view.height * 4 * d->cap))) return -1;
+	if (p->deblock_buffered && !(d->d_deblock = (uint32_t*)agmv_hip_malloc_on(ctx, batch))) return -1;
+	if (deblock && (!(d->d_dbcounts = (unsigned long long*)agmv_hip_malloc_on(ctx, 2 * sizeof(unsigned long long))) ||       /* the counters of this run */
+	                agmv_hip_memset_async(ctx, d->d_dbcounts, 0, 2 * sizeof(unsigned long long), d->stream) || agmv_hip_stream_sync(ctx, d->stream)))
+		return -1;
+	if (table && (!(d->d_table = agmv_hip_malloc_on(ctx, table)) || agmv_hip_memcpy_async(ctx, d->d_table, sink->tensor.table, table, 0, d->stream) ||
+	              agmv_hip_stream_sync(ctx, d->stream)))
+		return -1;
+	if (p->lz_dev && dlz_open(z, ctx, d->cap, d->lz_cap)) return -1;
+	for (i = 0; i < d->nslots; i++) {                      /* a slot's rows: with the LZ stage on the device they live there only */
+		dbatch* b = &d->slot[i];
+		if (p->lz_dev && (!(b->d_slab = (uint8_t*)agmv_hip_malloc_on(ctx, rows)) || !(b->d_bpos = (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d->cap)) ||
+		                  !(b->ready = agmv_hip_event_create(ctx))))
+			return -1;
+		if (!p->lz_dev && (!(b->h_slab = (u8*)agmv_hip_host_alloc(rows)) || !(b->h_bpos = (uint32_t*)agmv_hip_host_alloc(4 * (size_t)d->cap + 64)))) return -1;
+		if (p->to_bmp && !(b->h_out = (uint32_t*)agmv_hip_host_alloc(batch))) return -1;
 	}
-	if (sink->kind == AGMV_SINK_TENSOR) {                  /* 3 x 256 elements, once per call */
-		const size_t bytes = agmv_hip_tensor_frame_bytes(sink->tensor.type, 256);
-		d.d_table = agmv_hip_malloc_on(ctx, bytes);
-		if (!d.d_table || !d.stream || agmv_hip_memcpy_async(ctx, d.d_table, sink->tensor.table, bytes, 0, d.stream) || agmv_hip_stream_sync(ctx, d.stream)) goto out;
+	d->pool = agmv_pool_start(threads);
+	if (!pthread_create(&d->th, NULL, dworker_main, d)) return 0;
+	agmv_pool_stop(d->pool);                               /* no worker: nothing to join, nothing would ever consume a batch */
+	return -1;
+}
+
+/* frees what dpipe_open made, however far it came; the worker is joined and the pool stopped before */
+static void dpipe_close(dpipe* d, dlz* z)
+{
+	agmv_hip_ctx* ctx = d->ctx; unsigned i;
+	for (i = 0; i < d->nslots; i++) {
+		const dbatch* b = &d->slot[i];
+		agmv_hip_host_free(b->h_slab); agmv_hip_host_free(b->h_bpos); agmv_hip_host_free(b->h_out);
+		agmv_hip_free_on(ctx, b->d_slab); agmv_hip_free_on(ctx, b->d_bpos); agmv_hip_event_destroy(ctx, b->ready);
 	}
-	if (!persist || !chunks || (!lz_dev && !jobs) || !d.stream || (!lz_dev && (!d.d_bits || !d.d_bpos)) || !d.d_nent || (buffered && (!d.d_out[0] || !d.d_out[1])) || !d.d_iframe) goto out;
-	if (lz_dev && dlz_open(&z, ctx, d.cap, cap)) goto out;
-	for (i = 0; i < d.nslots; i++) {
-		if (lz_dev) {                                          /* the rows live on the device only */
-			d.slot[i].d_slab = (uint8_t*)agmv_hip_malloc_on(ctx, d.stride * d.cap);
-			d.slot[i].d_bpos = (uint32_t*)agmv_hip_malloc_on(ctx, 4 * (size_t)d.cap);
-			d.slot[i].ready = agmv_hip_event_create(ctx);
-			if (!d.slot[i].d_slab || !d.slot[i].d_bpos || !d.slot[i].ready) goto out;
-		} else {
-			d.slot[i].h_slab = (u8*)agmv_hip_host_alloc(d.stride * d.cap);
-			d.slot[i].h_bpos = (uint32_t*)agmv_hip_host_alloc(4 * (size_t)d.cap + 64);
-			if (!d.slot[i].h_slab || !d.slot[i].h_bpos) goto out;
-		}
-		if (to_bmp && !(d.slot[i].h_out = (uint32_t*)agmv_hip_host_alloc(npx * 4 * d.cap))) goto out;
-	}
-	d.pool = agmv_pool_start(threads);
-	if (pthread_create(&d.th, NULL, dworker_main, &d)) {       /* no worker: nothing to join, nothing would ever consume a batch */
-		agmv_pool_stop(d.pool);
-		goto out;
-	}
-	rc = NO_ERR;
+	dlz_close(z);
+	agmv_hip_free_on(ctx, d->d_bits); agmv_hip_free_on(ctx, d->d_bpos); agmv_hip_free_on(ctx, d->d_nent);
+	agmv_hip_free_on(ctx, d->d_out[0]); agmv_hip_free_on(ctx, d->d_out[1]); agmv_hip_free_on(ctx, d->d_iframe); agmv_hip_free_on(ctx, d->d_scaled);
+	agmv_hip_free_on(ctx, d->d_table); agmv_hip_free_on(ctx, d->d_view); agmv_hip_free_on(ctx, d->d_deblock); agmv_hip_free_on(ctx, d->d_dbcounts);
+	agmv_hip_stream_destroy(ctx, d->stream);
+	free(d->slot); free(d->persist); free(d->chunks); free(d->jobs);
+	pthread_mutex_destroy(&d->mu); pthread_cond_destroy(&d->cv);
+}
+
+/* The frame loop of AGMV_DecodeAGMV / AGMV_DecodeVideo on a file image, `pos` = first byte behind the header: open, loop, close.  The LZ stage of a
+   batch runs on the pool (host_lz_batch) or on the GPU (dlz_batch).  The frames go to `sink` (agmv_pipeline.h), whose count advances by the frames
+   decoded; how they get there is the plan's matter (dplan_of).  A view (sink->viewed; nframes then ends behind the last frame it needs) runs its LZ
+   stage from frame 0 like any other, because only that keeps the persistent buffer right; its GPU stage starts at the GOP start g0 from the fresh
+   state: a batch wholly before g0 is not handed to the worker and its slot is filled again, the batch that holds g0 is decoded from row g0 - first
+   on.  *restart = 1 (and NO_ERR) when the worker found that the first decoded batch derives from the state before it: nothing that run delivered
+   counts, and the caller runs g0 = 0. */
+static int decode_run(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
+                      int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink, uint32_t g0, unsigned deblock, AGMV_VIEW_STATS* stats, int* restart)
+{
+	const int viewed = sink->viewed;
+	dpipe d; dlz z;
+	uint32_t done = 0; unsigned id = 0, i;
+	int rc = dpipe_open(&d, &z, ctx, w, h, cap_frames, threads, sink, g0, deblock) ? MEMORY_CORRUPTION_ERR : NO_ERR;
+	if (rc != NO_ERR) { dpipe_close(&d, &z); return rc; }
 	while (done < nframes) {
 		dbatch* b = &d.slot[id % d.nslots];
 		const unsigned want = d.cap < nframes - done ? d.cap : nframes - done;
-		unsigned n;
+		unsigned n; int got;
 		pthread_mutex_lock(&d.mu);
 		while (b->filled && !d.failed) pthread_cond_wait(&d.cv, &d.mu);      /* the slot's frames of batch id - nslots are all exported */
 		pthread_mutex_unlock(&d.mu);
 		if (d.failed) break;
-		if (lz_dev) {
-			const int got = dlz_batch(&z, &d, b, chunks, file, len, &pos, want, ver, has_audio, cap);
-			if (got < 0) {
-				fprintf(stderr, "libagmv(amd): batch LZ stage: %s (the AGMV hot path runs on the GPU only -- no CPU fallback)\n", agmv_hip_last_error());
-				rc = MEMORY_CORRUPTION_ERR;
-				break;
-			}
-			n = (unsigned)got;
-		} else {
-			unsigned left, k;
-			n = left = locate_chunks(file, len, pos, has_audio, chunks, want);
-			for (k = 0; k < n; k++) {
-				unlz* j = &jobs[k];
-				j->d = &d; j->ver = ver; j->c = &chunks[k]; j->left = &left; j->cap = cap;
-				j->payload = file + chunks[k].at + 16; j->row = b->h_slab + (size_t)k * d.stride;
-				agmv_pool_submit(d.pool, unlz_task, j);
-			}
-			pthread_mutex_lock(&d.mu);
-			while (left) pthread_cond_wait(&d.cv, &d.mu);
-			pthread_mutex_unlock(&d.mu);
-			n = cut_batch(file, len, has_audio, chunks, n, &pos);
-			for (k = 0; k < n; k++) {                          /* in order: stale bytes, persistent buffer */
-				unlz* j = &jobs[k];
-				const size_t bp = j->bpos, tail = bp + 16 < d.stride ? 16 : (bp < d.stride ? d.stride - bp : 0);
-				if (tail) memcpy(j->row + bp, persist + bp, tail);
-				memcpy(persist, j->row, bp < cap ? bp : cap);
-				b->h_bpos[k] = j->bpos;
-			}
-		}
-		if (!n) break;
+		got = d.plan.lz_dev ? dlz_batch(&z, &d, b, d.chunks, file, len, &pos, want, ver, has_audio, d.lz_cap)
+		                    : host_lz_batch(&d, b, d.chunks, file, len, &pos, want, ver, has_audio, d.lz_cap);
+		if (got < 0) fprintf(stderr, "libagmv(amd): batch LZ stage: %s (the AGMV hot path runs on the GPU only -- no CPU fallback)\n", agmv_hip_last_error());
+		if (got <= 0) { if (got < 0) rc = MEMORY_CORRUPTION_ERR; break; }
+		n = (unsigned)got;
 		if (viewed && done + n <= g0) { done += n; continue; }     /* wholly before the view's GOP: the LZ stage was all it needed */
-		b->n = n; b->first = done; b->name0 = *sink->count + 1;
-		b->skip = viewed && g0 > done ? g0 - done : 0;
+		b->skip = viewed && g0 > done ? g0 - done : 0;             /* (the batch that holds g0: from row g0 - done on) */
+		b->n = n - b->skip; b->first = done + b->skip; b->name0 = *sink->count + 1;
 		if (!viewed) *sink->count += n;                            /* (a view's frames are counted where they are selected: sink_view) */
 		pthread_mutex_lock(&d.mu);
-		b->filled = 1;
-		d.nfilled = ++id;
+		b->filled = 1; d.nfilled = ++id;
 		pthread_cond_broadcast(&d.cv);
 		pthread_mutex_unlock(&d.mu);
 		done += n;
@@ -1379,34 +1393,19 @@ static int decode_run(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos,
 	agmv_pool_stop(d.pool);
 	if (d.restart) *restart = 1;
 	else if (d.failed) rc = MEMORY_CORRUPTION_ERR;
-	if (lz_dev) TRACE("decode: LZ stage device, %u frames in %u batches, %.3f s\n", (unsigned)done, z.batches, z.secs);
+	if (d.plan.lz_dev) TRACE("decode: LZ stage device, %u frames in %u batches, %.3f s\n", (unsigned)done, z.batches, z.secs);
 	if (viewed) TRACE("decode: view from GOP start %u, %u frames through the LZ stage, %u through the GPU stage%s\n", (unsigned)g0, (unsigned)done, d.gpu_frames,
 	                  d.restart ? ", which depend on the state before them: again from frame 0" : "");
 	if (stats) { stats->lz_frames += done; stats->gpu_frames += d.gpu_frames; }
 	if (deblock && rc == NO_ERR && !d.restart) {           /* (the worker synchronised its stream behind its last batch) */
 		unsigned long long counts[2] = {0, 0};
 		if (agmv_hip_memcpy_async(ctx, counts, d.d_dbcounts, sizeof(counts), 1, d.stream) || agmv_hip_stream_sync(ctx, d.stream)) rc = MEMORY_CORRUPTION_ERR;
-		g_deblock_stats.strength = deblock;
-		g_deblock_stats.frames = d.gpu_frames;
+		g_deblock_stats.strength = deblock; g_deblock_stats.frames = d.gpu_frames; g_deblock_stats.weak = counts[0]; g_deblock_stats.strong = counts[1];
 		g_deblock_stats.lines = (unsigned long long)d.gpu_frames * ((unsigned long long)(w / 4 - 1) * h + (unsigned long long)(h / 4 - 1) * w);
-		g_deblock_stats.weak = counts[0];
-		g_deblock_stats.strong = counts[1];
 		TRACE("decode: deblocking, strength %u: %u frames, %llu weak and %llu strong of %llu lines\n", deblock, g_deblock_stats.frames, counts[0], counts[1],
 		      g_deblock_stats.lines);
 	}
-out:
-	for (i = 0; i < d.nslots; i++) {
-		agmv_hip_host_free(d.slot[i].h_slab); agmv_hip_host_free(d.slot[i].h_bpos); agmv_hip_host_free(d.slot[i].h_out);
-		agmv_hip_free_on(ctx, d.slot[i].d_slab); agmv_hip_free_on(ctx, d.slot[i].d_bpos); agmv_hip_event_destroy(ctx, d.slot[i].ready);
-	}
-	dlz_close(&z);
-	agmv_hip_free_on(ctx, d.d_bits); agmv_hip_free_on(ctx, d.d_bpos); agmv_hip_free_on(ctx, d.d_nent);
-	agmv_hip_free_on(ctx, d.d_out[0]); agmv_hip_free_on(ctx, d.d_out[1]); agmv_hip_free_on(ctx, d.d_iframe); agmv_hip_free_on(ctx, d.d_scaled);
-	agmv_hip_free_on(ctx, d.d_table); agmv_hip_free_on(ctx, d.d_view); agmv_hip_free_on(ctx, d.d_deblock); agmv_hip_free_on(ctx, d.d_dbcounts);
-	agmv_hip_stream_destroy(ctx, d.stream);
-	free(d.slot); free(persist); free(chunks); free(jobs);
-	pthread_mutex_destroy(&d.mu);
-	pthread_cond_destroy(&d.cv);
+	dpipe_close(&d, &z);
 	return rc;
 }
 

@@ -13,6 +13,7 @@ import children as K
 import numpy as np
 import pytest
 
+import deblock_cases as DK
 import memseq_cases as MC
 import pixfmt_cases as P
 import scale_cases as SC
@@ -31,7 +32,8 @@ WHOLE = [0, 0, 1, 0, 0, 0, 0]
 
 # job: clip (npy of the XRGB32 clip to encode, or none), compression, craft ([a, b]: chunk a replaced by the bytes of chunk b), path,
 # views: [{fmt, value (the C call's fmt or type), size, scale, filt, mean, std, view ([first, count, step, x, y, w, h] or none), cap, frames
-# ([start, stop, step] for decode_frames, or none), crop, py, frame_bytes, buf_frames}].  Answers one JSON line.
+# ([start, stop, step] for decode_frames, or none), crop, py, frame_bytes, buf_frames, deblock (a strength: decode_frames once more with
+# deblock= it and once with deblock=None, the restarts and libagmv_amd.deblock_stats() of each)}].  Answers one JSON line.
 CHILD = textwrap.dedent("""
     import ctypes as C, json, sys
     import numpy as np
@@ -76,6 +78,10 @@ CHILD = textwrap.dedent("""
             assert (info2.width, info2.height, info2.number_of_frames) == (info.width, info.height, info.number_of_frames)
             r["py_shape"], r["py_stats"] = list(got.shape), view_stats()
             np.save("py_%d.npy" % k, got.contiguous().view(torch.uint8).cpu().numpy().reshape(-1))
+            for name, knob in (("on", d["deblock"]), ("off", None)) if d.get("deblock") else ():
+                got, _ = libagmv_amd.decode_frames(path, deblock=knob, **kw)
+                r[name + "_restarts"], r[name + "_stats"] = view_stats()[3], libagmv_amd.deblock_stats()
+                np.save("%s_%d.npy" % (name, k), got.contiguous().view(torch.uint8).cpu().numpy().reshape(-1))
         buf = torch.full((d["buf_frames"], d["frame_bytes"]), 0xA5, dtype=torch.uint8, device="cuda")
         view = abi.AGMV_VIEW(*d["view"]) if d["view"] is not None else None
         th, tw = d["size"] if d.get("size") else (0, 0)
@@ -222,6 +228,32 @@ def test_a_file_that_depends_on_the_frames_before_a_gop_start_is_decoded_again_f
         assert res["views"][k]["c_stats"][3] == 1 and res["views"][k]["py_stats"][3] == 1, (k, res["views"][k])
     assert res["views"][0]["c_stats"] == [24, 24, 8, 1]                                            # the run that delivered: the GPU stage from frame 0
     assert res["views"][2]["c_stats"] == [21, 9, 8, 0]                                             # GOP 3 on stands on its own again
+
+
+@pytest.mark.parametrize("lz", ["host", "device"])
+def test_a_view_that_is_decoded_again_with_the_deblocking_on_counts_the_delivering_run_alone(tmp_path, clip, lz):
+    """the crafted file of the test above, its views from frame 9 with deblock=16 and then with deblock=None.  The first run of each is given
+    up; what the deblocked call delivers is the numpy view of the statement's deblocked full decode of that file, and its statistics are
+    those of the run from frame 0 alone: the frames 0 .. the last one the view needs, and the statement's counts over exactly those."""
+    s = 16
+    views = [dict(case("xrgb32", [9, 0, 2, 0, 0, 0, 0], frames=[9, None, 2]), deblock=s),
+             dict(case("rgb24", [9, 5, 1, 4, 4, 24, 16], frames=[9, 14, 1], crop=[4, 4, 16, 24]), deblock=s)]
+    res = run_child(tmp_path, {"clip": clip, "path": "clip.agmv", "craft": [8, 9], "views": views}, {"AGMV_LZ_DECODE_DEVICE": "1"} if lz == "device" else None)
+    native = check(tmp_path, views, res)
+    deblocked = DK.deblock(native, s)[0]
+    assert (deblocked != native).any()
+    for k, (d, r) in enumerate(zip(views, res["views"])):
+        for name, full in (("on", deblocked), ("off", native)):
+            exp = expected(full, d)
+            got = np.load(tmp_path / ("%s_%d.npy" % (name, k)))
+            assert got.size == exp.size and (got.reshape(exp.shape) == exp).all(), (k, name, np.argwhere(got.reshape(exp.shape) != exp)[:4])
+            assert r[name + "_restarts"] == 1, (k, name, r)
+        through = d["view"][0] + d["view"][2] * (len(exp) - 1) + 1                                # the GPU stage of the delivering run: frames 0 .. through - 1
+        _, weak, strong = DK.deblock(native[:through], s)
+        assert weak + strong
+        assert r["on_stats"] == {"strength": s, "frames": through, "lines": DK.lines_examined(through, H0, W), "weak": weak, "strong": strong}, (k, r)
+        assert r["off_stats"] == {"strength": 0, "frames": 0, "lines": 0, "weak": 0, "strong": 0}, (k, r)
+    assert [d["view"][0] + d["view"][2] * (r["py_shape"][0] - 1) + 1 for d, r in zip(views, res["views"])] == [T, 14]
 
 
 def test_the_frame_13_view_with_the_lz_stage_on_the_device(tmp_path, clip):
