@@ -474,12 +474,12 @@ static void scaled_size(AGMV_OPT opt, int* sw, int* sh)
 static agmv_seq* seq_open(AGMV* a, FILE* file, const agmv_source* src, AGMV_OPT opt, int audio_chunks, int use_interp)
 {
 	uint32_t pal[512];
-	int i, sw, sh;
-	const int m512 = mode512_of(opt);
-	scaled_size(opt, &sw, &sh);
-	for (i = 0; i < 256; i++) { pal[i] = (uint32_t)a->header.palette0[i]; pal[256 + i] = m512 ? (uint32_t)a->header.palette1[i] : 0; }
-	return agmv_seq_open(a, file, src, sw, sh, m512, AGMV_GetCompression(a) != AGMV_LZSS_COMPRESSION, audio_chunks, use_interp,
-	                     batch_frames((size_t)AGMV_GetWidth(a) * AGMV_GetHeight(a)), devices(), lz_threads(), pal);
+	agmv_seq_opts o = {.mode512 = mode512_of(opt), .lz77 = AGMV_GetCompression(a) != AGMV_LZSS_COMPRESSION, .audio_chunks = audio_chunks, .use_interp = use_interp,
+	                   .cap = batch_frames((size_t)AGMV_GetWidth(a) * AGMV_GetHeight(a)), .devices = devices(), .threads = lz_threads(), .pal = pal};
+	int i;
+	scaled_size(opt, &o.scale_w, &o.scale_h);
+	for (i = 0; i < 256; i++) { pal[i] = (uint32_t)a->header.palette0[i]; pal[256 + i] = o.mode512 ? (uint32_t)a->header.palette1[i] : 0; }
+	return agmv_seq_open(a, file, src, &o);
 }
 
 /* AGMV_BuildPalette with the picked colours moved by weighted k-means on the GPU between the pick and the slot map
@@ -594,22 +594,20 @@ static void similarity_open(similarity* m, const agmv_source* src, AGMV* a, AGMV
 	{	/* the whole clip at once; with a scale, of the scaled frames (the same gather the workers run) */
 		agmv_hip_ctx* c = ctx();
 		const uint32_t n = src->n_frames;
-		uint32_t *d_scaled = NULL, *d_index = NULL, *d_counts = (uint32_t*)agmv_hip_malloc_on(c, 4 * (size_t)n);
+		uint32_t *d_scaled = NULL, *d_index = NULL, *index = NULL, *d_counts = (uint32_t*)agmv_hip_malloc_on(c, 4 * (size_t)n);
 		m->counts = (uint32_t*)calloc(n, 4);
 		if (!d_counts || !m->counts) agmv_die("device allocation");
 		if (m->scale_w) {
-			uint32_t* index = agmv_source_index(src->src_w, src->src_h, m->scale_w, m->scale_h, m->w, m->h);
-			d_index = (uint32_t*)agmv_hip_malloc_on(c, npx * 4);
+			d_index = agmv_source_index_dev(c, NULL, src, m->scale_w, m->scale_h, m->w, m->h, &index);
 			d_scaled = (uint32_t*)agmv_hip_malloc_on(c, npx * 4 * n);
-			if (!d_index || !d_scaled || agmv_hip_memcpy_async(c, d_index, index, npx * 4, 0, NULL) ||
-			    agmv_fmt_gather(c, src->fmt, src->src_w, src->src_h, src->d_frames, n, d_index, npx, d_scaled, NULL))
+			if (!d_index || !d_scaled || agmv_fmt_gather(c, src->fmt, src->src_w, src->src_h, src->d_frames, n, d_index, npx, d_scaled, NULL))
 				agmv_die("frame gather");
-			m->tmp = index;                                    /* (freed by similarity_close, behind the synchronisation below) */
 		}
 		if ((d_scaled ? agmv_hip_similarity_dev(c, d_scaled, n, npx, d_counts, NULL)
 		            : agmv_fmt_similarity(c, src->fmt, src->src_w, src->src_h, src->d_frames, n, d_counts, NULL)) ||
 		    (n > 1 && agmv_hip_memcpy_async(c, m->counts, d_counts, 4 * (size_t)(n - 1), 1, NULL)) || agmv_hip_stream_sync(c, NULL))
 			agmv_die("frame similarity");
+		free(index);                                           /* (the upload has read it) */
 		agmv_hip_free_on(c, d_counts); agmv_hip_free_on(c, d_scaled); agmv_hip_free_on(c, d_index);
 	}
 }

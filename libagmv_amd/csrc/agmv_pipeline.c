@@ -44,6 +44,15 @@ static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t
    allocation ends the process with a message instead of a NULL dereference in some pool thread */
 static void* xmalloc(size_t n) { void* p = malloc(n ? n : 1); if (!p) agmv_die("out of host memory"); return p; }
 static void* xcalloc(size_t n, size_t m) { void* p = calloc(n ? n : 1, m ? m : 1); if (!p) agmv_die("out of host memory"); return p; }
+/* ... and their pinned and device allocations likewise */
+static void* pinned(size_t n) { void* p = agmv_hip_host_alloc(n); if (!p) agmv_die("pinned allocation"); return p; }
+static void* on_device(agmv_hip_ctx* c, size_t n) { void* p = agmv_hip_malloc_on(c, n); if (!p) agmv_die("device allocation"); return p; }
+static void* zeroed_on_device(agmv_hip_ctx* c, size_t n, void* stream)       /* (complete on return) */
+{
+	void* p = on_device(c, n);
+	if (agmv_hip_memset_async(c, p, 0, n, stream) || agmv_hip_stream_sync(c, stream)) agmv_die("device allocation");
+	return p;
+}
 
 static int tracing(void) { static int v = -1; if (v < 0) v = getenv("AGMV_TRACE") != NULL; return v; }
 #define TRACE(...) do { if (tracing()) fprintf(stderr, "agmv trace: " __VA_ARGS__); } while (0)
@@ -151,6 +160,17 @@ uint32_t* agmv_source_index(uint32_t sw, uint32_t sh, int scale_w, int scale_h, 
 	return idx;
 }
 
+/* that table for the clip of a device source, on the device of context c: allocated there and uploaded on `stream`.  *h_index is the host's table, which
+   the copy reads: the caller frees it behind its next synchronisation of the stream.  NULL without device memory or when the copy is refused. */
+uint32_t* agmv_source_index_dev(agmv_hip_ctx* c, void* stream, const agmv_source* src, int scale_w, int scale_h, uint32_t w, uint32_t h, uint32_t** h_index)
+{
+	const size_t bytes = (size_t)w * h * sizeof(uint32_t);
+	uint32_t* d_index = (uint32_t*)agmv_hip_malloc_on(c, bytes);
+	*h_index = agmv_source_index(src->src_w, src->src_h, scale_w, scale_h, w, h);
+	if (d_index && agmv_hip_memcpy_async(c, d_index, *h_index, bytes, 0, stream)) { agmv_hip_free_on(c, d_index); d_index = NULL; }
+	return d_index;
+}
+
 /* AGMV_SCALE_NEAREST of include/agmv.h as such a table: target pixel (X, Y) of the dw x dh frame reads the source pixel under
    its centre, (((2X + 1) * sw) / (2 * dw), ((2Y + 1) * sh) / (2 * dh)) in integers.  NULL without memory. */
 uint32_t* agmv_scale_index(uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh)
@@ -194,65 +214,65 @@ void agmv_load_source(const char* dir, const char* base, long idx, int scale_w, 
 typedef struct lzjob { const u8* in; uint32_t n; u8* out; u32 csize; } lzjob;
 
 typedef struct ebatch {
-	unsigned id, n;
+	unsigned id, n; u32 first_fc;
 	long *srcA, *srcB;                     /* source frame numbers; srcB < 0: plain frame, else PDIFS midpoint of A and B */
-	u32 first_fc;
 	uint32_t* h_pix;                       /* BMP source, pinned: frame k at [k * per], its second source at [k * per + npx] */
-	unsigned loads_left, lz_left;
-	int loaded, bits_ready;
-	uint32_t* sizes;                       /* pinned [cap] */
-	u8* h_bits; size_t h_bits_cap;         /* pinned, rows packed back to back by download_rows */
-	size_t* boff;
-	lzjob* jobs;
-	u8* comp; size_t comp_cap;
-	uint32_t* csizes;                      /* pinned [cap]: lz_dev, the csize of each frame */
+	unsigned loads_left, lz_left; int loaded, bits_ready;
+	uint32_t *sizes, *csizes;              /* pinned [cap]: the usize of each frame and, lz_dev, its csize */
+	u8* h_bits; size_t h_bits_cap, *boff;  /* pinned, rows packed back to back by download_rows, row k at boff[k] */
+	lzjob* jobs; u8* comp; size_t comp_cap;
 } ebatch;
 
 typedef struct eworker {
-	struct agmv_seq* s;
-	unsigned idx;
-	pthread_t th;
-	agmv_hip_ctx* ctx;
-	void* stream;
-	uint32_t *d_frames, *d_sizes, *d_tmp[2];
-	uint8_t* d_out;
-	uint16_t* d_ient;
-	uint8_t* d_lz;                         /* lz_dev: payload rows [cap][LZSS: lz_stride, LZ77: lz77_stride] and their csize */
-	uint32_t* d_csize;
-	size_t lz77_stride;                    /* lz_dev, LZ77: stride of the rows d_lz holds now (grown on demand) */
-	uint8_t* d_peek;                       /* lz_dev, LZ77: [cap] the byte behind each stream */
-	unsigned long long* d_replaced;        /* stabilise: this worker's count of replaced blocks on its device, downloaded by agmv_seq_close */
+	struct agmv_seq* s; unsigned idx; pthread_t th;
+	agmv_hip_ctx* ctx; void* stream;
+	uint32_t *d_frames, *d_sizes, *d_tmp[2]; uint8_t* d_out; uint16_t* d_ient;
+	uint8_t* d_lz; uint32_t* d_csize;      /* lz_dev: payload rows [cap][LZSS: lz_stride, LZ77: lz77_stride] and their csize */
+	size_t lz77_stride; uint8_t* d_peek;   /* lz_dev, LZ77: stride of the rows d_lz holds now (grown on demand); [cap] the byte behind each stream */
+	unsigned long long* d_replaced;        /* stabilise: this worker's count of replaced blocks on its device, downloaded by eworker_close */
 	unsigned long long examined;           /* stabilise: P-frame blocks of this worker's batches that had their anchor in the batch */
 } eworker;
 
+typedef struct eplan { int device_src, scaled, packs, direct, midpoints, lz_dev, lz77; unsigned devices; } eplan;
+
 struct agmv_seq {
-	AGMV* a;
-	FILE* file;
-	agmv_source src;
-	uint32_t* d_index;                     /* device source with a scale: the table of agmv_source_index on the device */
-	int scale_w, scale_h, audio_chunks, mode512, lz77, use_b;
-	int lz_dev;                            /* the LZ stage runs on the GPU workers (lz77 chooses the form): AGMV_LZ_DEVICE for LZSS,
-	                                          AGMV_LZ77_DEVICE for LZ77 on one device */
-	unsigned stabilise;                    /* strength of the temporal stabilisation of every batch before its dither and encode, 0 = off (AGMV_SetStabilise / AGMV_STABILISE) */
-	unsigned dither;                       /* strength of the pattern dithering of every batch before its encode, 0 = off (AGMV_SetDither / AGMV_DITHER) */
+	AGMV* a; FILE* file; agmv_source src;
+	eplan plan;                            /* what the engine branches on (eplan_of) */
+	int scale_w, scale_h, audio_chunks;
+	unsigned stabilise, dither;            /* strengths, 0 = off, of the temporal stabilisation of every batch (AGMV_SetStabilise / AGMV_STABILISE) and, behind it, of
+	                                          its pattern dithering (AGMV_SetDither / AGMV_DITHER), both before its encode */
+	uint32_t* d_index;                     /* plan.scaled: the table of agmv_source_index on the device; this and d_persist are shared by the workers (eshared_open) */
 	uint8_t* d_persist;                    /* lz_dev, LZ77: `persist` on the device (persist_len bytes, zero-initialised) */
 	unsigned peek_turn;                    /* lz_dev, LZ77: the batch whose peek call comes next (under mu) */
-	uint32_t w, h;
-	size_t npx, per, stride, lz_stride;
-	unsigned cap, nslots, nworkers;
-	ebatch* slot;
-	eworker* wk;
-	agmv_pool* pool;
-	pthread_mutex_t mu;
-	pthread_cond_t cv;
-	unsigned nsubmitted, next_prep, next_write;
-	int closing;
+	uint32_t w, h; size_t npx, per, stride, lz_stride;
+	unsigned cap, nslots, nworkers; ebatch* slot; eworker* wk; agmv_pool* pool;
+	pthread_mutex_t mu; pthread_cond_t cv;
+	unsigned nsubmitted, next_prep, next_write; int closing;
 	ebatch* cur;                           /* batch being described by agmv_seq_push */
 	u32 fc0, frames_written;
 	u8* persist; size_t persist_len;       /* emulation of agmv->bitstream->data for LZ77's one-past-the-end read */
-	char err[256];
 	double t_open, t_load, t_lz, t_gpu, t_write;          /* AGMV_TRACE: summed task times */
 };
+
+/* The plan of a sequence encode: what open, the worker, submit, push and close branch on, derived here alone (the environment is read here, once per open).
+   device_src: the frames are resident in device memory: no pinned h_pix, no load tasks, and one device, the clip's own.
+   devices: the devices the batches go round, as asked for (at most the cards there are, or oversubscribed); 1 for a device source.
+   scaled: a device source under a GBA / NDS opt: its frames are gathered through d_index, which exists for them alone (a BMP source is scaled on the host).
+   direct: a device source of XRGB32 frames without a scale: a midpoint interpolates straight from the clip.
+   packs: every other source: a midpoint's two sources are put into the worker's two temporaries as packed pixels first.
+   midpoints: the sequence was opened with interpolation: frames may be PDIFS midpoints, h_pix has room for two sources per frame and the temporaries exist.
+   lz77: the file's compression is LZ77, not LZSS.  lz_dev: the LZ stage runs on the GPU workers, in the form lz77 chooses (d_csize; LZSS: d_lz up front; LZ77: d_peek,
+   d_persist and the turn-taking), opt-in: AGMV_LZ_DEVICE for LZSS sequences only, AGMV_LZ77_DEVICE for LZ77 ones on ONE device, where their persistent buffer then lives. */
+static eplan eplan_of(const agmv_source* src, int scale_w, int use_interp, int lz77, unsigned devices)
+{
+	eplan p = {.device_src = src->d_frames != NULL, .midpoints = use_interp, .lz77 = lz77};
+	p.devices = p.device_src ? 1 : devices;
+	p.scaled = p.device_src && scale_w;
+	p.direct = p.device_src && !p.scaled && src->fmt == AGMV_PIXFMT_XRGB32;
+	p.packs = !p.direct;
+	p.lz_dev = lz77 ? p.devices == 1 && env_nonzero("AGMV_LZ77_DEVICE") : env_nonzero("AGMV_LZ_DEVICE");
+	return p;
+}
 
 typedef struct loadarg { agmv_seq* s; ebatch* b; unsigned k; int which; } loadarg;
 typedef struct lzarg { agmv_seq* s; ebatch* b; unsigned k; } lzarg;
@@ -278,7 +298,7 @@ static void lz_task(void* p)
 	agmv_seq* s = za->s;
 	lzjob* j = &za->b->jobs[za->k];
 	const double t0 = now_s();
-	j->csize = s->lz77 ? agmv_lz77_mem(j->in, j->n, j->out) : agmv_lzss_mem(j->in, j->n, j->out);
+	j->csize = s->plan.lz77 ? agmv_lz77_mem(j->in, j->n, j->out) : agmv_lzss_mem(j->in, j->n, j->out);
 	pthread_mutex_lock(&s->mu);
 	s->t_lz += now_s() - t0;
 	if (--za->b->lz_left == 0) pthread_cond_broadcast(&s->cv);
@@ -309,9 +329,9 @@ static size_t lz77_rows(eworker* wk, const ebatch* b)
 static size_t lz_stage_dev(eworker* wk, ebatch* b)
 {
 	agmv_seq* s = wk->s;
-	const size_t lz_stride = s->lz77 ? lz77_rows(wk, b) : s->lz_stride;
+	const size_t lz_stride = s->plan.lz77 ? lz77_rows(wk, b) : s->lz_stride;
 	int rc;
-	if (s->lz77) {
+	if (s->plan.lz77) {
 		/* the persistent buffer is shared by the two workers and has to see the batches in order: the peek calls take
 		   turns, and the turn is passed on once this one's writes are complete on the device */
 		pthread_mutex_lock(&s->mu);
@@ -328,7 +348,7 @@ static size_t lz_stage_dev(eworker* wk, ebatch* b)
 	} else
 		rc = agmv_hip_lzss_frames_dev(wk->ctx, wk->d_out, s->stride, wk->d_sizes, b->n, wk->d_lz, lz_stride, wk->d_csize, wk->stream);
 	if (rc || agmv_hip_memcpy_async(wk->ctx, b->csizes, wk->d_csize, 4 * (size_t)b->n, 1, wk->stream) || agmv_hip_stream_sync(wk->ctx, wk->stream))
-		agmv_die(s->lz77 ? "batch LZ77" : "batch LZSS");
+		agmv_die(s->plan.lz77 ? "batch LZ77" : "batch LZSS");
 	return lz_stride;
 }
 
@@ -352,18 +372,22 @@ static void download_rows(eworker* wk, ebatch* b, const uint8_t* d_rows, size_t 
 	if (agmv_hip_stream_sync(wk->ctx, wk->stream)) agmv_die("row download");
 }
 
-/* a device source: where its frame `idx` is, and that frame as the encoder sees it into dst on the worker's stream (converted
-   from the source's layout -- for XRGB32 a copy --, or with a scale gathered through the table) */
+/* a device source: where its frame `idx` is */
 static const void* src_frame(const agmv_seq* s, long idx)
 {
 	return (const u8*)s->src.d_frames + (size_t)(idx - s->src.first) * agmv_fmt_frame_bytes(s->src.fmt, s->src.src_w, s->src.src_h);
 }
 
-static int place_frame(eworker* wk, long idx, uint32_t* dst)
+/* The one put: the source of batch b's slot k (which = 1: its second source) into dst as packed XRGB32, as the encoder sees it, on the worker's stream.
+   A BMP source: the upload of what the load task left in h_pix.  A device source: converted from the clip's layout (XRGB32: a copy), or gathered through the scale's table. */
+static int put_frame(eworker* wk, const ebatch* b, unsigned k, int which, uint32_t* dst)
 {
 	agmv_seq* s = wk->s;
-	if (s->d_index) return agmv_fmt_gather(wk->ctx, s->src.fmt, s->src.src_w, s->src.src_h, src_frame(s, idx), 1, s->d_index, s->npx, dst, wk->stream);
-	return agmv_fmt_to_xrgb(wk->ctx, s->src.fmt, s->src.src_w, s->src.src_h, src_frame(s, idx), 1, s->npx, dst, wk->stream);
+	const void* at;
+	if (!s->plan.device_src) return agmv_hip_memcpy_async(wk->ctx, dst, b->h_pix + (size_t)k * s->per + (which ? s->npx : 0), s->npx * 4, 0, wk->stream);
+	at = src_frame(s, which ? b->srcB[k] : b->srcA[k]);
+	if (s->plan.scaled) return agmv_fmt_gather(wk->ctx, s->src.fmt, s->src.src_w, s->src.src_h, at, 1, s->d_index, s->npx, dst, wk->stream);
+	return agmv_fmt_to_xrgb(wk->ctx, s->src.fmt, s->src.src_w, s->src.src_h, at, 1, s->npx, dst, wk->stream);
 }
 
 /* the P-frames of a batch of n frames from frame count first_fc on whose I-frame (frame_count % 4 == 0) lies in the batch */
@@ -375,81 +399,97 @@ static unsigned stabilise_examined_frames(unsigned n, u32 first_fc)
 
 /* the last sequence encode's AGMV_STABILISE_STATS: zeroed by agmv_seq_open, set by agmv_seq_close */
 static AGMV_STABILISE_STATS g_stabilise_stats;
-
 void AGMV_GetStabiliseStats(AGMV_STABILISE_STATS* out) { if (out) *out = g_stabilise_stats; }
+
+/* The worker, by step.  Take: batch id once it is submitted and loaded; NULL when the sequence closes with none left. */
+static ebatch* eworker_take(agmv_seq* s, unsigned id)
+{
+	ebatch* b = &s->slot[id % s->nslots];
+	pthread_mutex_lock(&s->mu);
+	while (!(id < s->nsubmitted && b->id == id && b->loaded) && !(s->closing && id >= s->nsubmitted)) pthread_cond_wait(&s->cv, &s->mu);
+	if (id >= s->nsubmitted) b = NULL;
+	pthread_mutex_unlock(&s->mu);
+	return b;
+}
+
+/* Fill: the batch's frames into d_frames.  A plain frame is put; a midpoint (AGMV_InterpFrame on the GPU, src/agmv_utils.c:949-969) interpolates
+   straight from the clip where the plan says `direct`, else from its two sources put into the temporaries. */
+static void eworker_fill(eworker* wk, const ebatch* b)
+{
+	agmv_seq* s = wk->s;
+	const int dev = s->plan.device_src;
+	unsigned k;
+	for (k = 0; k < b->n; k++) {
+		uint32_t* dst = wk->d_frames + (size_t)k * s->npx;
+		if (b->srcB[k] < 0) {
+			if (put_frame(wk, b, k, 0, dst)) agmv_die(dev ? "frame copy" : "frame upload");
+		} else if (s->plan.direct) {
+			if (agmv_hip_interp_dev(wk->ctx, dst, (const uint32_t*)src_frame(s, b->srcA[k]), (const uint32_t*)src_frame(s, b->srcB[k]), s->npx, wk->stream))
+				agmv_die("frame interp");
+		} else if (put_frame(wk, b, k, 0, wk->d_tmp[0]) || put_frame(wk, b, k, 1, wk->d_tmp[1]) ||
+		           agmv_hip_interp_dev(wk->ctx, dst, wk->d_tmp[0], wk->d_tmp[1], s->npx, wk->stream))
+			agmv_die(dev ? "frame gather / interp" : "frame upload / interp");
+	}
+}
+
+/* The caller's entry plane, for a first batch that completes a GOP the caller began (first_fc & 3): its I-frame entries to d_ient, behind the fill */
+static void eworker_entry_plane(eworker* wk)
+{
+	agmv_seq* s = wk->s;
+	uint16_t* e = (uint16_t*)xmalloc(s->npx * 2); size_t i;
+	for (i = 0; i < s->npx; i++) e[i] = (uint16_t)((s->a->iframe_entries[i].pal_num & 1u) << 8 | s->a->iframe_entries[i].index);
+	if (agmv_hip_stream_sync(wk->ctx, wk->stream) || agmv_hip_memcpy_async(wk->ctx, wk->d_ient, e, s->npx * 2, 0, wk->stream) ||
+	    agmv_hip_stream_sync(wk->ctx, wk->stream))
+		agmv_die("entry plane upload");
+	free(e);
+}
+
+/* Encode: the frames are what k_encode would have seen, midpoints included: stabilised against the batch's own I-frames, then dithered, in place,
+   on the same stream; then the bitstreams into d_out and their sizes to the host, complete on return */
+static void eworker_encode(eworker* wk, ebatch* b)
+{
+	agmv_seq* s = wk->s;
+	if (s->stabilise) {
+		if (agmv_hip_stabilise_frames_async(wk->ctx, s->stabilise, wk->d_frames, s->w, s->h, b->n, b->first_fc, wk->d_replaced, wk->stream))
+			agmv_die("batch stabilisation");
+		wk->examined += (unsigned long long)stabilise_examined_frames(b->n, b->first_fc) * (s->npx / 16);
+	}
+	if (s->dither && agmv_hip_dither_frames_async(wk->ctx, s->dither, wk->d_frames, s->w, s->h, b->n, wk->stream)) agmv_die("batch dither");
+	if (agmv_hip_encode_frames_dev(wk->ctx, wk->d_frames, b->n, s->w, s->h, b->first_fc, wk->d_out, s->stride, wk->d_sizes, wk->d_ient, wk->stream) ||
+	    agmv_hip_memcpy_async(wk->ctx, b->sizes, wk->d_sizes, 4 * (size_t)b->n, 1, wk->stream) || agmv_hip_check(wk->ctx, wk->stream))
+		agmv_die("batch encode");
+}
+
+/* Hand over: the rows to the host and the batch to the calling thread.  With the LZ stage on the GPU the payloads travel instead of the bitstreams and the time
+   from here on is the trace's LZ slot; else the bitstreams, +1 byte each: prepare_batch sets the byte behind each stream.  t_taken: when the worker took the batch. */
+static void eworker_hand_over(eworker* wk, ebatch* b, double t_taken)
+{
+	agmv_seq* s = wk->s;
+	const double t_lz = now_s(); unsigned k;
+	if (s->plan.lz_dev) {
+		const size_t lz_stride = lz_stage_dev(wk, b);
+		download_rows(wk, b, wk->d_lz, lz_stride, b->csizes, 0);
+		for (k = 0; k < b->n; k++) { b->jobs[k].out = b->h_bits + b->boff[k]; b->jobs[k].csize = b->csizes[k]; }
+	} else download_rows(wk, b, wk->d_out, s->stride, b->sizes, 1);
+	pthread_mutex_lock(&s->mu);
+	s->t_gpu += now_s() - t_taken;
+	if (s->plan.lz_dev) s->t_lz += now_s() - t_lz;
+	b->bits_ready = 1;
+	pthread_cond_broadcast(&s->cv);
+	pthread_mutex_unlock(&s->mu);
+}
 
 /* one GPU worker: its batches are id = idx, idx + nworkers, ... in order */
 static void* eworker_main(void* p)
 {
 	eworker* wk = (eworker*)p;
-	agmv_seq* s = wk->s;
-	unsigned id;
-	for (id = wk->idx;; id += s->nworkers) {
-		ebatch* b;
-		unsigned k;
-		pthread_mutex_lock(&s->mu);
-		while (!(id < s->nsubmitted && s->slot[id % s->nslots].id == id && s->slot[id % s->nslots].loaded) &&
-		       !(s->closing && id >= s->nsubmitted))
-			pthread_cond_wait(&s->cv, &s->mu);
-		if (id >= s->nsubmitted) { pthread_mutex_unlock(&s->mu); break; }
-		pthread_mutex_unlock(&s->mu);
-		b = &s->slot[id % s->nslots];
-		const double tw0 = now_s();
-		for (k = 0; k < b->n; k++) {
-			const uint32_t* src = b->h_pix ? b->h_pix + (size_t)k * s->per : NULL;
-			uint32_t* dst = wk->d_frames + (size_t)k * s->npx;
-			if (s->src.d_frames) {                             /* the frames are on this device already: no upload */
-				if (b->srcB[k] < 0) {
-					if (place_frame(wk, b->srcA[k], dst)) agmv_die("frame copy");
-				} else if (s->d_index || s->src.fmt != AGMV_PIXFMT_XRGB32) {        /* the two sources as packed frames first */
-					if (place_frame(wk, b->srcA[k], wk->d_tmp[0]) || place_frame(wk, b->srcB[k], wk->d_tmp[1]) ||
-					    agmv_hip_interp_dev(wk->ctx, dst, wk->d_tmp[0], wk->d_tmp[1], s->npx, wk->stream))
-						agmv_die("frame gather / interp");
-				} else if (agmv_hip_interp_dev(wk->ctx, dst, (const uint32_t*)src_frame(s, b->srcA[k]), (const uint32_t*)src_frame(s, b->srcB[k]), s->npx,
-				                               wk->stream))
-					agmv_die("frame interp");
-			} else if (b->srcB[k] < 0) {
-				if (agmv_hip_memcpy_async(wk->ctx, dst, src, s->npx * 4, 0, wk->stream)) agmv_die("frame upload");
-			} else {                                       /* AGMV_InterpFrame on the GPU, src/agmv_utils.c:949-969 */
-				if (agmv_hip_memcpy_async(wk->ctx, wk->d_tmp[0], src, s->npx * 4, 0, wk->stream) ||
-				    agmv_hip_memcpy_async(wk->ctx, wk->d_tmp[1], src + s->npx, s->npx * 4, 0, wk->stream) ||
-				    agmv_hip_interp_dev(wk->ctx, dst, wk->d_tmp[0], wk->d_tmp[1], s->npx, wk->stream))
-					agmv_die("frame upload / interp");
-			}
-		}
-		if (b->first_fc & 3u) {                            /* the batch completes a GOP the caller began: its I-frame entries */
-			uint16_t* e = (uint16_t*)xmalloc(s->npx * 2);
-			size_t i;
-			for (i = 0; i < s->npx; i++) e[i] = (uint16_t)((s->a->iframe_entries[i].pal_num & 1u) << 8 | s->a->iframe_entries[i].index);
-			if (agmv_hip_stream_sync(wk->ctx, wk->stream) || agmv_hip_memcpy_async(wk->ctx, wk->d_ient, e, s->npx * 2, 0, wk->stream) ||
-			    agmv_hip_stream_sync(wk->ctx, wk->stream))
-				agmv_die("entry plane upload");
-			free(e);
-		}
-		/* the frames are what k_encode would have seen, midpoints included: stabilised against the batch's own I-frames, then
-		   dithered, in place, on the same stream */
-		if (s->stabilise) {
-			if (agmv_hip_stabilise_frames_async(wk->ctx, s->stabilise, wk->d_frames, s->w, s->h, b->n, b->first_fc, wk->d_replaced, wk->stream))
-				agmv_die("batch stabilisation");
-			wk->examined += (unsigned long long)stabilise_examined_frames(b->n, b->first_fc) * (s->npx / 16);
-		}
-		if (s->dither && agmv_hip_dither_frames_async(wk->ctx, s->dither, wk->d_frames, s->w, s->h, b->n, wk->stream)) agmv_die("batch dither");
-		if (agmv_hip_encode_frames_dev(wk->ctx, wk->d_frames, b->n, s->w, s->h, b->first_fc, wk->d_out, s->stride, wk->d_sizes, wk->d_ient,
-		                               wk->stream) ||
-		    agmv_hip_memcpy_async(wk->ctx, b->sizes, wk->d_sizes, 4 * (size_t)b->n, 1, wk->stream) || agmv_hip_check(wk->ctx, wk->stream))
-			agmv_die("batch encode");
-		const double tl0 = now_s();                        /* (the LZ slot of the trace when the stage runs here) */
-		if (s->lz_dev) {                                   /* LZ on the GPU: the payloads travel instead of the bitstreams */
-			const size_t lz_stride = lz_stage_dev(wk, b);
-			download_rows(wk, b, wk->d_lz, lz_stride, b->csizes, 0);
-			for (k = 0; k < b->n; k++) { b->jobs[k].out = b->h_bits + b->boff[k]; b->jobs[k].csize = b->csizes[k]; }
-		} else download_rows(wk, b, wk->d_out, s->stride, b->sizes, 1);      /* (+1: prepare_batch sets the byte behind each stream) */
-		pthread_mutex_lock(&s->mu);
-		s->t_gpu += now_s() - tw0;
-		if (s->lz_dev) s->t_lz += now_s() - tl0;
-		b->bits_ready = 1;
-		pthread_cond_broadcast(&s->cv);
-		pthread_mutex_unlock(&s->mu);
+	unsigned id; ebatch* b;
+	for (id = wk->idx; (b = eworker_take(wk->s, id)) != NULL; id += wk->s->nworkers) {
+		const double t_taken = now_s();
+		eworker_fill(wk, b);
+		if (b->first_fc & 3u) eworker_entry_plane(wk);
+		eworker_encode(wk, b);
+		eworker_hand_over(wk, b, t_taken);
 	}
 	return NULL;
 }
@@ -460,8 +500,8 @@ static void prepare_batch(agmv_seq* s, ebatch* b)
 {
 	size_t need = 0, coff = 0;
 	unsigned k;
-	if (s->lz_dev) return;     /* the GPU worker left the payloads (LZ77 with the byte past the end from d_persist); lz_left is 0 since begin_batch */
-	for (k = 0; k < b->n; k++) need += (size_t)b->sizes[k] * (s->lz77 ? 4 : 2) + 64;
+	if (s->plan.lz_dev) return;     /* the GPU worker left the payloads (LZ77 with the byte past the end from d_persist); lz_left is 0 since begin_batch */
+	for (k = 0; k < b->n; k++) need += (size_t)b->sizes[k] * (s->plan.lz77 ? 4 : 2) + 64;
 	if (need > b->comp_cap) { free(b->comp); b->comp_cap = need + need / 4; b->comp = (u8*)xmalloc(b->comp_cap); }
 	for (k = 0; k < b->n; k++) {
 		u8* raw = b->h_bits + b->boff[k];
@@ -469,7 +509,7 @@ static void prepare_batch(agmv_seq* s, ebatch* b)
 		raw[n] = n < s->persist_len ? s->persist[n] : 0;
 		memcpy(s->persist, raw, n < s->persist_len ? n : s->persist_len);
 		b->jobs[k].in = raw; b->jobs[k].n = (uint32_t)n; b->jobs[k].out = b->comp + coff;
-		coff += n * (s->lz77 ? 4 : 2) + 64;
+		coff += n * (s->plan.lz77 ? 4 : 2) + 64;
 	}
 	pthread_mutex_lock(&s->mu);
 	b->lz_left = b->n;
@@ -548,7 +588,7 @@ static void submit_batch(agmv_seq* s)
 	ebatch* b = s->cur;
 	unsigned k, tasks = 0;
 	if (!b || !b->n) return;
-	if (!s->src.d_frames) for (k = 0; k < b->n; k++) tasks += b->srcB[k] < 0 ? 1 : 2;
+	if (!s->plan.device_src) for (k = 0; k < b->n; k++) tasks += b->srcB[k] < 0 ? 1 : 2;
 	pthread_mutex_lock(&s->mu);
 	b->loads_left = tasks;
 	if (!tasks) b->loaded = 1;                             /* a device source: nothing to load, the batch is the worker's at once */
@@ -566,95 +606,97 @@ static void submit_batch(agmv_seq* s)
 	s->cur = NULL;
 }
 
-agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const agmv_source* src, int scale_w, int scale_h, int mode512, int lz77,
-                        int audio_chunks, int use_interp, unsigned cap, unsigned devices, unsigned threads, const uint32_t pal[512])
+/* Open and close, in pairs.  Every allocation is checked where it is made (xmalloc, pinned, on_device), what the plan does not call for stays NULL,
+   and the closes free whatever is there.  One batch slot: h_pix only for a BMP source. */
+static void eslot_open(const agmv_seq* s, ebatch* b)
+{
+	b->id = ~0u;
+	b->srcA = (long*)xmalloc(sizeof(long) * s->cap); b->srcB = (long*)xmalloc(sizeof(long) * s->cap);
+	b->boff = (size_t*)xmalloc(sizeof(size_t) * s->cap); b->jobs = (lzjob*)xcalloc(s->cap, sizeof(lzjob));
+	if (!s->plan.device_src) b->h_pix = (uint32_t*)pinned(s->per * 4 * s->cap);
+	b->sizes = (uint32_t*)pinned(4 * (size_t)s->cap + 64); b->csizes = (uint32_t*)pinned(4 * (size_t)s->cap + 64);
+}
+
+static void eslot_close(ebatch* b)
+{
+	free(b->srcA); free(b->srcB); free(b->boff); free(b->jobs); free(b->comp);
+	agmv_hip_host_free(b->h_pix); agmv_hip_host_free(b->sizes); agmv_hip_host_free(b->csizes); agmv_hip_host_free(b->h_bits);
+}
+
+/* One worker: its context on `device` with the palette's tables, its stream and its buffers, sized by the plan (LZ77's payload rows: lz77_rows) */
+static void eworker_open(agmv_seq* s, unsigned i, int device, const agmv_seq_opts* o)
+{
+	eworker* wk = &s->wk[i]; const eplan* p = &s->plan;
+	agmv_hip_ctx* c = wk->ctx = agmv_hip_create(device);
+	wk->s = s; wk->idx = i;
+	if (!c) agmv_die("cannot open the GPU");
+	if (agmv_hip_set_palette(c, o->pal, o->pal + 256, o->mode512, NULL) || agmv_hip_sync()) agmv_die("palette upload");
+	if (!(wk->stream = agmv_hip_stream_create(c))) agmv_die("device allocation");
+	wk->d_frames = (uint32_t*)on_device(c, s->npx * 4 * s->cap); wk->d_out = (uint8_t*)on_device(c, s->stride * s->cap);
+	wk->d_sizes = (uint32_t*)on_device(c, 4 * (size_t)s->cap); wk->d_ient = (uint16_t*)on_device(c, s->npx * 2);
+	if (p->midpoints && p->packs) { wk->d_tmp[0] = (uint32_t*)on_device(c, s->npx * 4); wk->d_tmp[1] = (uint32_t*)on_device(c, s->npx * 4); }
+	if (p->lz_dev) wk->d_csize = (uint32_t*)on_device(c, 4 * (size_t)s->cap);
+	if (p->lz_dev && !p->lz77) wk->d_lz = (uint8_t*)on_device(c, s->lz_stride * s->cap);
+	if (p->lz_dev && p->lz77) wk->d_peek = (uint8_t*)on_device(c, s->cap);
+	if (s->stabilise) wk->d_replaced = (unsigned long long*)zeroed_on_device(c, sizeof(unsigned long long), wk->stream);
+}
+
+/* ... behind its thread's join: the stabilisation's count joins the statistics (the worker synchronised its stream behind its last batch) */
+static void eworker_close(eworker* wk)
+{
+	agmv_hip_ctx* c = wk->ctx; unsigned long long replaced = 0;
+	if (wk->s->stabilise) {
+		if (agmv_hip_memcpy_async(c, &replaced, wk->d_replaced, sizeof(replaced), 1, wk->stream) || agmv_hip_stream_sync(c, wk->stream)) agmv_die("stabilisation count download");
+		g_stabilise_stats.examined += wk->examined; g_stabilise_stats.replaced += replaced;
+	}
+	agmv_hip_free_on(c, wk->d_replaced); agmv_hip_free_on(c, wk->d_frames); agmv_hip_free_on(c, wk->d_out); agmv_hip_free_on(c, wk->d_sizes); agmv_hip_free_on(c, wk->d_ient);
+	agmv_hip_free_on(c, wk->d_tmp[0]); agmv_hip_free_on(c, wk->d_tmp[1]); agmv_hip_free_on(c, wk->d_lz); agmv_hip_free_on(c, wk->d_csize); agmv_hip_free_on(c, wk->d_peek);
+	agmv_hip_stream_destroy(c, wk->stream); agmv_hip_destroy(c);
+}
+
+/* What all workers share, once, on worker 0's context and stream: a scaled device source's table, LZ77's persistent buffer (agmv_seq_close frees both) */
+static void eshared_open(agmv_seq* s)
+{
+	eworker* wk = &s->wk[0]; uint32_t* index = NULL;
+	if (s->plan.scaled) {
+		s->d_index = agmv_source_index_dev(wk->ctx, wk->stream, &s->src, s->scale_w, s->scale_h, s->w, s->h, &index);
+		if (!s->d_index || agmv_hip_stream_sync(wk->ctx, wk->stream)) agmv_die("scale table upload");
+		free(index);
+	}
+	if (s->plan.lz_dev && s->plan.lz77) s->d_persist = (uint8_t*)zeroed_on_device(wk->ctx, s->persist_len, wk->stream);
+}
+
+agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const agmv_source* src, const agmv_seq_opts* o)
 {
 	agmv_seq* s = (agmv_seq*)xcalloc(1, sizeof(*s));
-	unsigned i, ndev = (unsigned)agmv_hip_device_count();
-	const double t0 = now_s();
-	double t1;
+	unsigned i, devices = o->devices < 1 ? 1 : o->devices;
+	const unsigned ndev = (unsigned)agmv_hip_device_count();
+	const double t0 = now_s(); double t1;
 	if (ndev < 1) agmv_die("cannot open the GPU");
-	if (devices < 1 || src->d_frames) devices = 1;             /* a device source is encoded where it lives */
-	{	/* AGMV_DEVICES_OVERSUBSCRIBE=1: more "devices" than cards -- worker pair d runs on card d % ndev.  The round-robin of
-		   batches over devices, the in-order chunk writer and the per-device tables are then exercised on a one-GPU box. */
-		if (devices > ndev && !env_nonzero("AGMV_DEVICES_OVERSUBSCRIBE")) devices = ndev;
-	}
-	s->a = a; s->file = file; s->src = *src; s->scale_w = scale_w; s->scale_h = scale_h;
-	s->audio_chunks = audio_chunks; s->mode512 = mode512; s->lz77 = lz77; s->use_b = use_interp;
-	s->w = (uint32_t)AGMV_GetWidth(a); s->h = (uint32_t)AGMV_GetHeight(a);
-	s->npx = (size_t)s->w * s->h; s->per = s->npx * (use_interp ? 2 : 1); s->stride = agmv_hip_max_usize(s->w, s->h, 1);
-	/* the LZ stage on the GPU workers, opt-in: AGMV_LZ_DEVICE acts on LZSS sequences only, AGMV_LZ77_DEVICE on LZ77 ones.  LZ77's
-	   persistent buffer behind the streams then lives on ONE device, so with more than one device its stage stays on the host pool. */
-	s->lz_dev = lz77 ? devices == 1 && env_nonzero("AGMV_LZ77_DEVICE") : env_nonzero("AGMV_LZ_DEVICE");
+	/* AGMV_DEVICES_OVERSUBSCRIBE=1: more "devices" than cards -- worker pair d runs on card d % ndev.  The round-robin of batches over
+	   devices, the in-order chunk writer and the per-device tables are then exercised on a one-GPU box. */
+	if (devices > ndev && !env_nonzero("AGMV_DEVICES_OVERSUBSCRIBE")) devices = ndev;
+	s->plan = eplan_of(src, o->scale_w, o->use_interp, o->lz77, devices);
+	s->a = a; s->file = file; s->src = *src; s->scale_w = o->scale_w; s->scale_h = o->scale_h; s->audio_chunks = o->audio_chunks;
+	s->w = (uint32_t)AGMV_GetWidth(a); s->h = (uint32_t)AGMV_GetHeight(a); s->fc0 = (u32)a->frame_count;
+	s->npx = (size_t)s->w * s->h; s->per = s->npx * (s->plan.midpoints ? 2 : 1); s->stride = agmv_hip_max_usize(s->w, s->h, 1);
 	s->lz_stride = (agmv_hip_lzss_max_csize(s->stride) + 255) & ~(size_t)255;
-	s->stabilise = agmv_stabilise_strength();
+	s->stabilise = agmv_stabilise_strength(); s->dither = agmv_dither_strength();
 	memset(&g_stabilise_stats, 0, sizeof(g_stabilise_stats));
 	if (s->stabilise) TRACE("seq_open: temporal stabilisation of every batch before its dither and encode, strength %u\n", s->stabilise);
-	s->dither = agmv_dither_strength();
 	if (s->dither) TRACE("seq_open: pattern dithering of every batch before its encode, strength %u\n", s->dither);
-	s->cap = (cap + 3u) & ~3u;
-	s->nworkers = devices * 2;
-	s->nslots = s->nworkers + 2;
-	s->fc0 = (u32)a->frame_count;
-	pthread_mutex_init(&s->mu, NULL);
-	pthread_cond_init(&s->cv, NULL);
-	s->pool = agmv_pool_start(threads);
-	s->persist_len = s->stride + 64;
-	s->persist = (u8*)xcalloc(s->persist_len, 1);
-	s->slot = (ebatch*)xcalloc(s->nslots, sizeof(ebatch));
-	for (i = 0; i < s->nslots; i++) {
-		ebatch* b = &s->slot[i];
-		b->id = ~0u;
-		b->srcA = (long*)xmalloc(sizeof(long) * s->cap); b->srcB = (long*)xmalloc(sizeof(long) * s->cap);
-		b->boff = (size_t*)xmalloc(sizeof(size_t) * s->cap);
-		b->jobs = (lzjob*)xcalloc(s->cap, sizeof(lzjob));
-		b->h_pix = src->d_frames ? NULL : (uint32_t*)agmv_hip_host_alloc(s->per * 4 * s->cap);
-		b->sizes = (uint32_t*)agmv_hip_host_alloc(4 * (size_t)s->cap + 64);
-		b->csizes = (uint32_t*)agmv_hip_host_alloc(4 * (size_t)s->cap + 64);
-		if ((!src->d_frames && !b->h_pix) || !b->sizes || !b->csizes) agmv_die("pinned allocation");
-	}
+	s->cap = (o->cap + 3u) & ~3u; s->nworkers = s->plan.devices * 2; s->nslots = s->nworkers + 2;
+	pthread_mutex_init(&s->mu, NULL); pthread_cond_init(&s->cv, NULL);
+	s->pool = agmv_pool_start(o->threads); s->persist_len = s->stride + 64; s->persist = (u8*)xcalloc(s->persist_len, 1);
+	s->slot = (ebatch*)xcalloc(s->nslots, sizeof(ebatch)); s->wk = (eworker*)xcalloc(s->nworkers, sizeof(eworker));
+	for (i = 0; i < s->nslots; i++) eslot_open(s, &s->slot[i]);
 	t1 = now_s();
-	TRACE("seq_open: pool + %u pinned slots of %.1f MB in %.3f s\n", s->nslots, src->d_frames ? 0.0 : s->per * 4.0 * s->cap / 1e6, t1 - t0);
-	s->wk = (eworker*)xcalloc(s->nworkers, sizeof(eworker));
-	for (i = 0; i < s->nworkers; i++) {
-		eworker* wk = &s->wk[i];
-		wk->s = s; wk->idx = i;
-		wk->ctx = agmv_hip_create(src->d_frames ? src->device : (int)((i % devices) % ndev));
-		if (!wk->ctx) agmv_die("cannot open the GPU");
-		if (agmv_hip_set_palette(wk->ctx, pal, pal + 256, mode512, NULL) || agmv_hip_sync()) agmv_die("palette upload");
-		wk->stream = agmv_hip_stream_create(wk->ctx);
-		wk->d_frames = (uint32_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 4 * s->cap);
-		wk->d_out = (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->stride * s->cap);
-		wk->d_sizes = (uint32_t*)agmv_hip_malloc_on(wk->ctx, 4 * (size_t)s->cap);
-		wk->d_ient = (uint16_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 2);
-		wk->d_tmp[0] = use_interp ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 4) : NULL;
-		wk->d_tmp[1] = use_interp ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 4) : NULL;
-		if (src->d_frames && scale_w && i == 0) {              /* the scale of a device source: its table, once, for all workers */
-			uint32_t* index = agmv_source_index(src->src_w, src->src_h, scale_w, scale_h, s->w, s->h);
-			s->d_index = (uint32_t*)agmv_hip_malloc_on(wk->ctx, s->npx * 4);
-			if (!s->d_index || agmv_hip_memcpy_async(wk->ctx, s->d_index, index, s->npx * 4, 0, wk->stream) || agmv_hip_stream_sync(wk->ctx, wk->stream))
-				agmv_die("scale table upload");
-			free(index);
-		}
-		wk->d_lz = s->lz_dev && !lz77 ? (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->lz_stride * s->cap) : NULL;   /* (LZ77: lz77_rows) */
-		wk->d_csize = s->lz_dev ? (uint32_t*)agmv_hip_malloc_on(wk->ctx, 4 * (size_t)s->cap) : NULL;
-		wk->d_peek = s->lz_dev && lz77 ? (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->cap) : NULL;
-		if (s->stabilise) {
-			wk->d_replaced = (unsigned long long*)agmv_hip_malloc_on(wk->ctx, sizeof(unsigned long long));
-			if (!wk->d_replaced || agmv_hip_memset_async(wk->ctx, wk->d_replaced, 0, sizeof(unsigned long long), wk->stream) ||
-			    agmv_hip_stream_sync(wk->ctx, wk->stream))
-				agmv_die("device allocation");
-		}
-		if (s->lz_dev && lz77 && i == 0) {
-			s->d_persist = (uint8_t*)agmv_hip_malloc_on(wk->ctx, s->persist_len);
-			if (!s->d_persist || agmv_hip_memset_async(wk->ctx, s->d_persist, 0, s->persist_len, wk->stream) || agmv_hip_stream_sync(wk->ctx, wk->stream))
-				agmv_die("device allocation");
-		}
-		if (!wk->stream || !wk->d_frames || !wk->d_out || !wk->d_sizes || !wk->d_ient || (use_interp && (!wk->d_tmp[0] || !wk->d_tmp[1])) ||
-		    (s->lz_dev && (!wk->d_csize || (lz77 ? !wk->d_peek : !wk->d_lz))))
-			agmv_die("device allocation");
-		if (pthread_create(&wk->th, NULL, eworker_main, wk)) agmv_die("cannot start a GPU worker thread");
-	}
+	TRACE("seq_open: pool + %u pinned slots of %.1f MB in %.3f s\n", s->nslots, s->plan.device_src ? 0.0 : s->per * 4.0 * s->cap / 1e6, t1 - t0);
+	for (i = 0; i < s->nworkers; i++)                          /* a device source is encoded where it lives */
+		eworker_open(s, i, s->plan.device_src ? src->device : (int)((i % s->plan.devices) % ndev), o);
+	eshared_open(s);
+	for (i = 0; i < s->nworkers; i++)
+		if (pthread_create(&s->wk[i].th, NULL, eworker_main, &s->wk[i])) agmv_die("cannot start a GPU worker thread");
 	TRACE("seq_open: %u GPU workers (context + table + buffers) in %.3f s\n", s->nworkers, now_s() - t1);
 	s->t_open = now_s();
 	return s;
@@ -663,20 +705,17 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const agmv_source* src, int scale_w
 /* append one encoded frame: source `a`, or the PDIFS midpoint of sources a and b (b >= 0) */
 void agmv_seq_push(agmv_seq* s, long a, long b)
 {
+	const long first = s->src.first, end = first + (long)s->src.n_frames;
 	if (!s->cur) begin_batch(s);
-	if (b >= 0 && !s->use_b) agmv_die("internal: midpoint frame on a sequence opened without interpolation");
-	if (s->src.d_frames && (a < s->src.first || a >= s->src.first + (long)s->src.n_frames || b >= s->src.first + (long)s->src.n_frames ||
-	                        (b >= 0 && b < s->src.first)))
-		agmv_die("internal: frame outside the device clip");
+	if (b >= 0 && !s->plan.midpoints) agmv_die("internal: midpoint frame on a sequence opened without interpolation");
+	if (s->plan.device_src && (a < first || a >= end || b >= end || (b >= 0 && b < first))) agmv_die("internal: frame outside the device clip");
 	s->cur->srcA[s->cur->n] = a; s->cur->srcB[s->cur->n] = b;
 	if (++s->cur->n == batch_limit(s, s->cur)) submit_batch(s);
 }
 
 u32 agmv_seq_close(agmv_seq* s)
 {
-	unsigned i;
-	u32 written;
-	double t0;
+	unsigned i; u32 written; double t0;
 	submit_batch(s);
 	pthread_mutex_lock(&s->mu);
 	s->closing = 1;
@@ -685,40 +724,20 @@ u32 agmv_seq_close(agmv_seq* s)
 	seq_progress(s, 0, 1);
 	TRACE("pipeline: %u frames in %u batches, %.3f s from open to last chunk written; summed over the threads: BMP parse %.3f s, GPU workers "
 	      "(upload + kernels + download) %.3f s, LZ (%s) %.3f s, chunk writes %.3f s\n", (unsigned)s->frames_written, s->nsubmitted, now_s() - s->t_open,
-	      s->t_load, s->t_gpu, s->lz_dev ? "device" : "host", s->t_lz, s->t_write);
+	      s->t_load, s->t_gpu, s->plan.lz_dev ? "device" : "host", s->t_lz, s->t_write);
 	t0 = now_s();
-	for (i = 0; i < s->nworkers; i++) {
-		eworker* wk = &s->wk[i];
-		pthread_join(wk->th, NULL);
-		if (s->stabilise) {                                /* (the worker synchronised its stream behind its last batch) */
-			unsigned long long replaced = 0;
-			if (agmv_hip_memcpy_async(wk->ctx, &replaced, wk->d_replaced, sizeof(replaced), 1, wk->stream) || agmv_hip_stream_sync(wk->ctx, wk->stream))
-				agmv_die("stabilisation count download");
-			g_stabilise_stats.examined += wk->examined;
-			g_stabilise_stats.replaced += replaced;
-			agmv_hip_free_on(wk->ctx, wk->d_replaced);
-		}
-		agmv_hip_free_on(wk->ctx, wk->d_frames); agmv_hip_free_on(wk->ctx, wk->d_out); agmv_hip_free_on(wk->ctx, wk->d_sizes);
-		agmv_hip_free_on(wk->ctx, wk->d_ient); agmv_hip_free_on(wk->ctx, wk->d_tmp[0]); agmv_hip_free_on(wk->ctx, wk->d_tmp[1]);
-		agmv_hip_free_on(wk->ctx, wk->d_lz); agmv_hip_free_on(wk->ctx, wk->d_csize); agmv_hip_free_on(wk->ctx, wk->d_peek);
-		if (i == s->nworkers - 1) { agmv_hip_free_on(wk->ctx, s->d_persist); agmv_hip_free_on(wk->ctx, s->d_index); }   /* (every worker has been joined) */
-		agmv_hip_stream_destroy(wk->ctx, wk->stream);
-		agmv_hip_destroy(wk->ctx);
-	}
+	for (i = 0; i < s->nworkers; i++) pthread_join(s->wk[i].th, NULL);
+	agmv_hip_free_on(s->wk[0].ctx, s->d_index); agmv_hip_free_on(s->wk[0].ctx, s->d_persist);       /* (eshared_open; every worker has been joined) */
+	for (i = 0; i < s->nworkers; i++) eworker_close(&s->wk[i]);
 	agmv_pool_stop(s->pool);
-	for (i = 0; i < s->nslots; i++) {
-		ebatch* b = &s->slot[i];
-		free(b->srcA); free(b->srcB); free(b->boff); free(b->jobs); free(b->comp);
-		agmv_hip_host_free(b->h_pix); agmv_hip_host_free(b->sizes); agmv_hip_host_free(b->csizes); agmv_hip_host_free(b->h_bits);
-	}
+	for (i = 0; i < s->nslots; i++) eslot_close(&s->slot[i]);
 	written = s->frames_written;
 	if (s->stabilise)
 		TRACE("seq_close: temporal stabilisation, strength %u: %llu of %llu P-frame blocks with their I-frame in the batch replaced\n", s->stabilise,
 		      g_stabilise_stats.replaced, g_stabilise_stats.examined);
 	TRACE("seq_close: teardown %.3f s\n", now_s() - t0);
 	free(s->slot); free(s->wk); free(s->persist);
-	pthread_mutex_destroy(&s->mu);
-	pthread_cond_destroy(&s->cv);
+	pthread_mutex_destroy(&s->mu); pthread_cond_destroy(&s->cv);
 	free(s);
 	return written;
 }
@@ -747,48 +766,27 @@ static void hist_load_task(void* p)
 	free(ha);
 }
 
-void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start, u32 end, u32 size, int quality,
-                           unsigned threads, uint32_t* hist /* 2^19 bins */)
+/* the clip is resident: no parse, no ring, no upload, one call over the n frames from `start` */
+static void hist_resident(agmv_hip_ctx* ctx, const agmv_source* src, u32 start, u32 n, u32 size, int quality, uint32_t* d_hist, void* stream)
 {
-	const char *dir = src->dir, *base = src->base;
-	const u32 n = end >= start ? end - start + 1 : 0;
-	const double t0 = now_s();
-	uint32_t *d_hist, *d_pix;
-	if (n == 0) {                                              /* the reference's `for (i = start; i <= end; i++)` does not run (src/agmv_encode.c:2371-2397) */
-		memset(hist, 0, 4u << 19);
-		return;
-	}
-	d_hist = (uint32_t*)agmv_hip_malloc_on(ctx, 4u << 19);
-	void* stream = agmv_hip_stream_create(ctx);
-	if (src->d_frames) {                                       /* the clip is resident: no parse, no ring, no upload */
-		const size_t fpx = (size_t)src->src_w * src->src_h, px = fpx < size ? fpx : size;
-		const u8* d_first = (const u8*)src->d_frames + (size_t)((long)start - src->first) * agmv_fmt_frame_bytes(src->fmt, src->src_w, src->src_h);
-		if ((long)start < src->first || (long)end >= src->first + (long)src->n_frames) agmv_die("internal: frame outside the device clip");
-		if (!d_hist || !stream || agmv_hip_memset_async(ctx, d_hist, 0, 4u << 19, stream)) agmv_die("histogram");
-		if (agmv_fmt_histogram(ctx, src->fmt, src->src_w, src->src_h, d_first, n, px, quality, d_hist, stream)) agmv_die("histogram");
-		if (agmv_hip_memcpy_async(ctx, hist, d_hist, 4u << 19, 1, stream) || agmv_hip_stream_sync(ctx, stream)) agmv_die("histogram download");
-		agmv_hip_free_on(ctx, d_hist);
-		agmv_hip_stream_destroy(ctx, stream);
-		TRACE("palette pass 1: %u resident frames histogrammed in %.3f s\n", (unsigned)n, now_s() - t0);
-		return;
-	}
+	const size_t fpx = (size_t)src->src_w * src->src_h, px = fpx < size ? fpx : size;
+	const u8* d_first = (const u8*)src->d_frames + (size_t)((long)start - src->first) * agmv_fmt_frame_bytes(src->fmt, src->src_w, src->src_h);
+	if ((long)start < src->first || (long)start + (long)n > src->first + (long)src->n_frames) agmv_die("internal: frame outside the device clip");
+	if (agmv_fmt_histogram(ctx, src->fmt, src->src_w, src->src_h, d_first, n, px, quality, d_hist, stream)) agmv_die("histogram");
+}
+
+/* BMP files: a ring of pinned frames, parsed ahead of the GPU by the host cores; only the first `size` pixels of a frame count
+   (the reference histograms img[0 .. width*height) of the size it was told, src/agmv_encode.c:2390-2394) */
+static void hist_bmp_ring(agmv_hip_ctx* ctx, const agmv_source* src, u32 start, u32 n, u32 size, int quality, unsigned threads, uint32_t* d_hist, void* stream)
+{
 	agmv_pool* pool = agmv_pool_start(threads);
-	hctx c;
+	hctx c = {.fr = (hframe*)xcalloc(n, sizeof(hframe)), .dir = src->dir, .base = src->base, .start = start, .ring_px = size, .window = threads + 2 < n ? threads + 2 : n};
+	uint32_t* d_pix = (uint32_t*)on_device(ctx, c.ring_px * 4);
 	u32 i, issued = 0;
-	memset(&c, 0, sizeof(c));
 	pthread_mutex_init(&c.mu, NULL);
 	pthread_cond_init(&c.cv, NULL);
-	c.fr = (hframe*)xcalloc(n, sizeof(hframe)); c.dir = dir; c.base = base; c.start = start;
-	/* a ring of pinned frames, parsed ahead of the GPU by the host cores; only the first `size` pixels of a frame count
-	   (the reference histograms img[0 .. width*height) of the size it was told, src/agmv_encode.c:2390-2394) */
-	c.window = threads + 2;
-	if (c.window > n) c.window = n;
-	c.ring_px = size;
 	c.ring = (uint32_t**)xcalloc(c.window, sizeof(uint32_t*));
-	for (i = 0; i < c.window; i++) { c.ring[i] = (uint32_t*)agmv_hip_host_alloc(c.ring_px * 4); if (!c.ring[i]) agmv_die("pinned allocation"); }
-	d_pix = (uint32_t*)agmv_hip_malloc_on(ctx, c.ring_px * 4);
-	if (!d_hist || !d_pix || !stream) agmv_die("device allocation");
-	if (agmv_hip_memset_async(ctx, d_hist, 0, 4u << 19, stream)) agmv_die("histogram");
+	for (i = 0; i < c.window; i++) c.ring[i] = (uint32_t*)pinned(c.ring_px * 4);
 	for (i = 0; i < n; i++) {
 		hframe* f = &c.fr[i];
 		size_t px;
@@ -805,16 +803,38 @@ void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start,
 		    agmv_hip_stream_sync(ctx, stream))
 			agmv_die("histogram");
 	}
-	if (agmv_hip_memcpy_async(ctx, hist, d_hist, 4u << 19, 1, stream) || agmv_hip_stream_sync(ctx, stream)) agmv_die("histogram download");
 	agmv_pool_stop(pool);
 	for (i = 0; i < c.window; i++) agmv_hip_host_free(c.ring[i]);
-	agmv_hip_free_on(ctx, d_hist); agmv_hip_free_on(ctx, d_pix);
-	agmv_hip_stream_destroy(ctx, stream);
-	TRACE("palette pass 1: %u frames histogrammed in %.3f s\n", (unsigned)n, now_s() - t0);
+	agmv_hip_free_on(ctx, d_pix);
 	free(c.ring); free(c.fr);
 	pthread_mutex_destroy(&c.mu);
 	pthread_cond_destroy(&c.cv);
 }
+
+void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start, u32 end, u32 size, int quality,
+                           unsigned threads, uint32_t* hist /* 2^19 bins */)
+{
+	const u32 n = end >= start ? end - start + 1 : 0;
+	const int resident = src->d_frames != NULL;
+	const double t0 = now_s();
+	uint32_t* d_hist;
+	void* stream;
+	if (n == 0) {                                              /* the reference's `for (i = start; i <= end; i++)` does not run (src/agmv_encode.c:2371-2397) */
+		memset(hist, 0, 4u << 19);
+		return;
+	}
+	d_hist = (uint32_t*)agmv_hip_malloc_on(ctx, 4u << 19);
+	stream = agmv_hip_stream_create(ctx);
+	if (!d_hist || !stream) agmv_die(resident ? "histogram" : "device allocation");
+	if (agmv_hip_memset_async(ctx, d_hist, 0, 4u << 19, stream)) agmv_die("histogram");
+	if (resident) hist_resident(ctx, src, start, n, size, quality, d_hist, stream);
+	else hist_bmp_ring(ctx, src, start, n, size, quality, threads, d_hist, stream);
+	if (agmv_hip_memcpy_async(ctx, hist, d_hist, 4u << 19, 1, stream) || agmv_hip_stream_sync(ctx, stream)) agmv_die("histogram download");
+	agmv_hip_free_on(ctx, d_hist);
+	agmv_hip_stream_destroy(ctx, stream);
+	TRACE("palette pass 1: %u %sframes histogrammed in %.3f s\n", (unsigned)n, resident ? "resident " : "", now_s() - t0);
+}
+
 
 /* ------------------------------------------------------------------------------------------
  * decode pipeline

@@ -32,6 +32,9 @@ typedef struct agmv_source {
 	long first;
 	int device;
 } agmv_source;
+/* the table of agmv_source_index for such a clip on the device of context c, uploaded on `stream`; *h_index: the host's table, the caller's to free
+   behind its next synchronisation of that stream.  NULL on failure. */
+uint32_t* agmv_source_index_dev(agmv_hip_ctx* c, void* stream, const agmv_source* src, int scale_w, int scale_h, uint32_t w, uint32_t h, uint32_t** h_index);
 
 /* The one place that knows the two families of layouts: a YUV 4:2:0 clip is addressed by w and h, a byte layout by a pixel count.
    The bytes of one frame, and the device calls that read or write a clip of w x h frames in the layout `fmt`. */
@@ -69,10 +72,16 @@ static inline int agmv_fmt_similarity(agmv_hip_ctx* c, int fmt, uint32_t w, uint
 /* one open sequence encode: frames are pushed in order (plain, or the PDIFS midpoint of two sources) and leave as AGFC
    (+ AGAC) chunks in `file`, strictly in order; batches of `cap` frames (whole GOPs) go round-robin over two workers per
    device; a device source is encoded by two workers on its own device, which read it in place (no load tasks, no pinned
-   staging).  `pal` = palette0 | palette1.  agmv_seq_close returns the number of frames written. */
+   staging).  agmv_seq_close returns the number of frames written. */
 typedef struct agmv_seq agmv_seq;
-agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const agmv_source* src, int scale_w, int scale_h, int mode512, int lz77,
-                        int audio_chunks, int use_interp, unsigned cap, unsigned devices, unsigned threads, const uint32_t pal[512]);
+typedef struct agmv_seq_opts {
+	int scale_w, scale_h;                  /* the size a GBA / NDS opt scales every source frame to, 0 x 0: the frames as they are */
+	int mode512, lz77;                     /* two palettes; LZ77 instead of LZSS */
+	int audio_chunks, use_interp;          /* an AGAC chunk behind every frame chunk; frames may be PDIFS midpoints */
+	unsigned cap, devices, threads;        /* frames per batch (rounded up to whole GOPs), devices asked for, host pool threads */
+	const uint32_t* pal;                   /* [512] palette0 | palette1 */
+} agmv_seq_opts;
+agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const agmv_source* src, const agmv_seq_opts* opts);
 void agmv_seq_push(agmv_seq* s, long a, long b);
 u32  agmv_seq_close(agmv_seq* s);
 
