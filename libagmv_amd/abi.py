@@ -1,6 +1,7 @@
 """The public C signatures, stated once: the structures of include/agmv.h that Python passes, every function of
 include/agmv_hip.h (HIP), of include/agmv_hip_view.h (HIP_VIEW), of include/agmv_hip_view_source.h (HIP_VIEW_SOURCE), of
-include/agmv_hip_stabilise.h (HIP_STABILISE) and of include/agmv_hip_deblock.h (HIP_DEBLOCK) and every function of include/agmv.h that Python calls on libagmv.so (AGMV), as
+include/agmv_hip_stabilise.h (HIP_STABILISE) and of include/agmv_hip_deblock.h (HIP_DEBLOCK), every function of include/agmv.h that Python calls on libagmv.so (AGMV)
+and every function of include/agmv_reader.h, which the same library exports (READER), as
 name -> (restype, (argtypes...)).  bind() sets them on a loaded library.  tests/test_abi.py checks both tables and the
 structures against the headers.  ctypes only, and no library is loaded here: the test children import this module the
 way a C host would include the headers."""
@@ -43,6 +44,18 @@ class AGMV_STABILISE_STATS(Structure):
 
 class AGMV_DEBLOCK_STATS(Structure):
     _fields_ = [("strength", c_uint), ("frames", c_uint), ("lines", c_ulonglong), ("weak", c_ulonglong), ("strong", c_ulonglong)]
+
+
+class AGMV_READER_DESC(Structure):
+    # include/agmv_reader.h; the enums are c_int
+    _fields_ = [("tensor", c_int), ("fmt", c_int), ("yuv_flags", c_int), ("type", c_int), ("mean", c_float * 3), ("std", c_float * 3),
+                ("width", c_uint), ("height", c_uint), ("filter", c_int), ("step", c_uint), ("x", c_uint), ("y", c_uint),
+                ("win_width", c_uint), ("win_height", c_uint), ("deblock", c_uint), ("index_bytes", c_size_t)]
+
+
+class AGMV_READER_STATS(Structure):
+    _fields_ = [("lz_frames", c_ulonglong), ("gpu_frames", c_ulonglong), ("delivered", c_ulonglong), ("reads", c_uint), ("seeks", c_uint),
+                ("restarts", c_uint), ("checkpoints", c_uint), ("interval", c_uint)]
 
 
 # vp: any pointer but the five below and `const char*`; ul: the header's u32; the enums and Bool are c_int
@@ -259,6 +272,16 @@ AGMV = {
     "AGMV_DecodeAudioDev": (c_int, (c_char_p, vp, c_int, ul, INFO_P)),
     "AGMV_MeasureFramesDev": (c_int, (vp, vp, c_int, ul, ul, ul, QUALITY_P)),
     "AGMV_MeasureFileDev": (c_int, (c_char_p, vp, c_int, ul, QUALITY_P, INFO_P)),
+}
+
+# include/agmv_reader.h, exported by libagmv.so
+READER = {
+    "AGMV_OpenReaderDev": (vp, (c_char_p, POINTER(AGMV_READER_DESC), INFO_P, POINTER(c_int))),
+    "AGMV_ReaderReadDev": (c_int, (vp, vp, ul)),
+    "AGMV_ReaderSeek": (c_int, (vp, ul)),
+    "AGMV_ReaderTell": (ul, (vp,)),
+    "AGMV_GetReaderStats": (None, (vp, POINTER(AGMV_READER_STATS))),
+    "AGMV_CloseReader": (None, (vp,)),
 }
 
 

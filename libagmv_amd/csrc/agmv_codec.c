@@ -1050,6 +1050,24 @@ static int resolve_view(agmv_sink* sink, const AGMV_MAIN_HEADER* hd, u32 cap_fra
 	return NO_ERR;
 }
 
+/* the palette of a file's header as the device takes it, and whether it is two palettes */
+static void header_palette(const AGMV_MAIN_HEADER* hd, uint32_t pal[512], int* m512)
+{
+	int i;
+	*m512 = hd->version == 1 || hd->version == 3;
+	for (i = 0; i < 256; i++) { pal[i] = (uint32_t)hd->palette0[i]; pal[256 + i] = *m512 ? (uint32_t)hd->palette1[i] : 0; }
+}
+
+/* ... on the device, uploaded when it differs from the one that is there */
+static int device_palette(agmv_hip_ctx* c, const uint32_t pal[512], int m512)
+{
+	if (g_pal_mode == m512 && memcmp(pal, g_pal, sizeof(g_pal)) == 0) return 0;
+	if (agmv_hip_set_palette(c, pal, pal + 256, m512, NULL) || agmv_hip_sync()) return -1;
+	memcpy(g_pal, pal, sizeof(g_pal));
+	g_pal_mode = m512;
+	return 0;
+}
+
 static int decode_file(const char* filename, u8 img_type, agmv_sink* sink, AGMV_FRAME_QUALITY* quality, u32 cap_frames, int info_only, AGMV_INFO* info)
 {
 	const agmv_target* to = agmv_sink_target(sink);
@@ -1057,7 +1075,7 @@ static int decode_file(const char* filename, u8 img_type, agmv_sink* sink, AGMV_
 	agmv_file af;
 	const AGMV_MAIN_HEADER* hd = &af.hdr.header;
 	uint32_t nframes, pal[512];
-	int err = agmv_file_open(&af, filename, info), m512, i;
+	int err = agmv_file_open(&af, filename, info), m512;
 	agmv_hip_ctx* c;
 	if (err != FILE_NOT_FOUND_ERR) require_bmp(img_type);        /* (the file exists) */
 	if (err == NO_ERR && !info_only) {
@@ -1068,15 +1086,10 @@ static int decode_file(const char* filename, u8 img_type, agmv_sink* sink, AGMV_
 		else if ((err = agmv_file_slurp(&af)) == NO_ERR && bad_geometry((uint32_t)hd->width, (uint32_t)hd->height)) err = INVALID_HEADER_FORMATTING_ERR;
 	}
 	if (err != NO_ERR || info_only || (sink->viewed && sink->view.count == 0)) { agmv_file_close(&af); return err; }      /* (a view without a frame: nothing to do) */
-	m512 = hd->version == 1 || hd->version == 3;
 	c = open_ctx();
 	if (!c) { agmv_file_close(&af); return gpu_failed("cannot open the GPU"); }
-	for (i = 0; i < 256; i++) { pal[i] = (uint32_t)hd->palette0[i]; pal[256 + i] = m512 ? (uint32_t)hd->palette1[i] : 0; }
-	if (!(g_pal_mode == m512 && memcmp(pal, g_pal, sizeof(pal)) == 0)) {
-		if (agmv_hip_set_palette(c, pal, pal + 256, m512, NULL) || agmv_hip_sync()) { agmv_file_close(&af); return gpu_failed("palette upload"); }
-		memcpy(g_pal, pal, sizeof(pal));
-		g_pal_mode = m512;
-	}
+	header_palette(hd, pal, &m512);
+	if (device_palette(c, pal, m512)) { agmv_file_close(&af); return gpu_failed("palette upload"); }
 	nframes = (uint32_t)hd->num_of_frames;
 	if (sink->kind != AGMV_SINK_EXPORT && nframes > cap_frames) nframes = (uint32_t)cap_frames;
 	if (view) nframes = sink->viewed ? sink->view.first + (sink->view.count - 1) * sink->view.step + 1 : sink->view.count;      /* behind the last frame it needs */
@@ -1186,6 +1199,81 @@ int AGMV_DecodeViewTensorDev(const char* filename, void* d_tensor, AGMV_TENSORFM
 	const int refused = filename && known_tensor(type, mean, std, table) && !view_refused(view) ? (sized ? target_refused(width, height, filter) : 0) : -1;
 	memset(&g_view_stats, 0, sizeof(g_view_stats));
 	return refused ? refused : decode_result(decode_file(filename, AGMV_IMG_BMP, &sink, NULL, cap_frames, d_tensor == NULL, info), &decoded);
+}
+
+/* Reader sessions (include/agmv_reader.h): the checks of the two view decoders in their order, the file image and its palette kept, and
+   agmv_dreader of agmv_pipeline.h behind them.  The library's context has one palette: a read puts its file's there first when another
+   file's decode has replaced it. */
+struct AGMV_READER { agmv_file af; agmv_dreader* r; uint32_t pal[512]; int m512; };
+
+AGMV_READER* AGMV_OpenReaderDev(const char* filename, const AGMV_READER_DESC* desc, AGMV_INFO* info, int* error)
+{
+	static const AGMV_READER_DESC none;
+	const AGMV_READER_DESC* q = desc ? desc : &none;
+	const AGMV_VIEW view = {0, 0, q->step ? q->step : 1, q->x, q->y, q->win_width, q->win_height};
+	const int sized = q->width != 0 || q->height != 0, fmt = (int)q->fmt | q->yuv_flags;
+	const agmv_target to = {(uint32_t)q->width, (uint32_t)q->height, sized ? (int)q->filter : 0};
+	uint32_t table[768];
+	unsigned long unused = 0;
+	agmv_sink sink = {AGMV_SINK_FRAMES, &unused, .frames = {NULL, fmt, to}, .viewed = 1, .view = view};
+	const int known = q->tensor ? known_tensor(q->type, q->mean, q->std, table) : known_pixfmt(fmt);
+	int err = desc && filename && known && !view_refused(&view) ? (sized ? target_refused(q->width, q->height, q->filter) : 0) : -1;
+	AGMV_READER* rd = NULL;
+	const AGMV_MAIN_HEADER* hd;
+	agmv_hip_ctx* c = NULL;
+	if (q->tensor) { sink.kind = AGMV_SINK_TENSOR; sink.tensor.d_dst = NULL; sink.tensor.type = (int)q->type; sink.tensor.table = table; sink.tensor.to = to; }
+	if (!err && !(rd = (AGMV_READER*)calloc(1, sizeof(*rd)))) err = -MEMORY_CORRUPTION_ERR;
+	if (!err) {
+		hd = &rd->af.hdr.header;
+		err = agmv_file_open(&rd->af, filename, info);
+		if (err == NO_ERR && resolve_view(&sink, hd, 0xFFFFFFFFu) != NO_ERR) err = -4;
+		else if (err == NO_ERR && (err = agmv_file_slurp(&rd->af)) == NO_ERR && bad_geometry((uint32_t)hd->width, (uint32_t)hd->height)) err = INVALID_HEADER_FORMATTING_ERR;
+		if (err == NO_ERR && !(c = open_ctx())) err = gpu_failed("cannot open the GPU");
+		if (err == NO_ERR) {
+			const agmv_dfile f = {rd->af.image, rd->af.len, rd->af.pos, (uint32_t)hd->width, (uint32_t)hd->height,
+			                      hd->num_of_frames > 0xFFFFFFFFul ? 0xFFFFFFFFu : (uint32_t)hd->num_of_frames, hd->version, hd->total_audio_duration != 0};
+			const unsigned deblock = q->deblock ? (q->deblock > 64 ? 64 : q->deblock) : agmv_deblock_strength();
+			header_palette(hd, rd->pal, &rd->m512);
+			if (device_palette(c, rd->pal, rd->m512)) err = gpu_failed("palette upload");
+			else if (!(rd->r = agmv_dreader_open(c, &f, batch_frames((size_t)f.w * f.h), lz_threads(), &sink, deblock, q->index_bytes ? q->index_bytes : (size_t)64 << 20)))
+				err = gpu_failed("cannot open the reader");
+		}
+		if (err != NO_ERR) { agmv_file_close(&rd->af); free(rd); rd = NULL; err = err < 0 ? err : -err; }
+	}
+	if (error) *error = err;
+	return rd;
+}
+
+int AGMV_ReaderReadDev(AGMV_READER* rd, void* d_dst, u32 n)
+{
+	if (!rd || (!d_dst && n)) return -1;
+	if (!n) return 0;
+	if (device_palette(g_ctx, rd->pal, rd->m512)) return -gpu_failed("palette upload");
+	return agmv_dreader_read(rd->r, d_dst, n > 0xFFFFFFFFul ? 0xFFFFFFFFu : (uint32_t)n);
+}
+
+int AGMV_ReaderSeek(AGMV_READER* rd, u32 frame)
+{
+	if (!rd) return -1;
+	agmv_dreader_seek(rd->r, frame > 0xFFFFFFFFul ? 0xFFFFFFFFu : (uint32_t)frame);
+	return 0;
+}
+
+u32 AGMV_ReaderTell(const AGMV_READER* rd) { return rd ? agmv_dreader_tell(rd->r) : 0; }
+
+void AGMV_GetReaderStats(const AGMV_READER* rd, AGMV_READER_STATS* stats)
+{
+	if (!stats) return;
+	memset(stats, 0, sizeof(*stats));
+	if (rd) agmv_dreader_stats(rd->r, stats);
+}
+
+void AGMV_CloseReader(AGMV_READER* rd)
+{
+	if (!rd) return;
+	agmv_dreader_close(rd->r);
+	agmv_file_close(&rd->af);
+	free(rd);
 }
 
 /* A view of a clip encoded (include/agmv.h has the rules).  encode_view_refused is everything that needs no device, in the header's

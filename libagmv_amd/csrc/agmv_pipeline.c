@@ -842,6 +842,7 @@ void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start,
 typedef struct dbatch {
 	unsigned n; uint32_t first;            /* the frames for the GPU stage, and the frame_count of the first of them */
 	unsigned skip;                         /* a view: the slot's rows in front of them, the frames before g0, which do not enter the GPU stage */
+	int fresh;                             /* the GPU stage takes this batch from the state of a fresh decoder (the first batch of a run, of a reader's seek) */
 	u8* h_slab;                           /* pinned [cap][stride] (host LZ stage) */
 	uint32_t *h_bpos, *h_out;              /* pinned [cap], [cap][npx] */
 	uint8_t* d_slab; uint32_t* d_bpos;     /* AGMV_LZ_DECODE_DEVICE: the batch's rows [cap][stride] on the device, their bpos, and */
@@ -876,6 +877,17 @@ typedef struct dpipe {
 	unsigned long long* d_dbcounts;        /* deblock: [2] the weak and the strong lines of this run, downloaded behind the worker's join */
 	size_t lz_cap; u8* persist;            /* the reference's ONE decompression buffer, zero-initialised, and its bytes (device LZ stage: dlz.d_persist) */
 	struct dchunk* chunks; struct unlz* jobs;              /* [cap] the chunks of a batch, and the host LZ stage's jobs */
+	agmv_dfile f;                          /* the file image the LZ stage reads ... */
+	size_t pos; uint32_t done;             /* ... where it stands there, and the frames before that place: the next frame of the LZ stage */
+	int fresh;                             /* the next batch handed over starts the GPU stage anew, at g0 */
+	unsigned ndone;                        /* batches the worker has released (under mu) */
+	unsigned long long lz_frames;          /* frames through the LZ stage, over all runs of this pipe */
+	int keep;                              /* a reader's pipe: the worker outlives a restart, which the calling thread answers (dreader_read) */
+	/* a reader's seek index (include/agmv_reader.h): checkpoint k > 0 is the persistent buffer as it stood before frame k * interval, in slot k - 1 of
+	   ckpt (host LZ stage) or d_ckpt (device LZ stage, on the LZ context), with the place of that frame's chunk; checkpoint 0 is the zero buffer at the
+	   first chunk and is not stored.  interval 0: no index (the one-shot drivers) */
+	uint32_t interval, nckpt, *recorded; unsigned checkpoints;
+	u8* ckpt; uint8_t* d_ckpt; size_t* ckpt_pos;
 } dpipe;
 
 /* The plan of a run over a w x h file: what the driver branches on, derived here alone.  Whatever the sink, a batch is decoded at the file's size.
@@ -1051,6 +1063,7 @@ static void dworker_release(dpipe* d, dbatch* b)
 	pthread_mutex_lock(&d->mu);
 	if (!saves) b->filled = 0;                         /* the frames are where they belong */
 	else { b->decoded = 1; b->saves_left = saves; }
+	d->ndone++;
 	pthread_cond_broadcast(&d->cv);
 	pthread_mutex_unlock(&d->mu);
 	for (k = 0; k < saves; k++) {
@@ -1066,8 +1079,18 @@ static void* dworker_main(void* p)
 	unsigned id, prev_n = 0;
 	dbatch* b; uint32_t* out;
 	for (id = 0; (b = dworker_take(d, id)) != NULL; id++) {
-		int rc = dworker_decode(d, b, id, prev_n, &out);
+		int rc;
+		if (b->fresh) prev_n = 0;
+		if (d->keep && d->restart) { dworker_release(d, b); continue; }      /* (a reader's run that is given up: its later batches are dropped) */
+		rc = dworker_decode(d, b, id, prev_n, &out);
 		if (!rc) rc = dworker_deliver(d, b, out);
+		if (rc > 0 && d->keep) {               /* a reader: the calling thread finds `restart` behind this batch and runs again from frame 0 */
+			pthread_mutex_lock(&d->mu);
+			d->restart = 1;
+			pthread_mutex_unlock(&d->mu);
+			dworker_release(d, b);
+			continue;
+		}
 		if (rc) {                              /* (failed: what stops the batch loop, for the restart too) */
 			if (rc < 0) fprintf(stderr, "libagmv(amd): batch decode: %s (the AGMV hot path runs on the GPU only -- no CPU fallback)\n", agmv_hip_last_error());
 			pthread_mutex_lock(&d->mu);
@@ -1171,6 +1194,31 @@ static unsigned cut_batch(const u8* file, size_t len, int has_audio, const dchun
 	return n;
 }
 
+uint32_t agmv_reader_checkpoint(uint32_t nframes, size_t lz_cap, size_t index_bytes, uint32_t f, const uint32_t* recorded, uint32_t* interval)
+{
+	const uint64_t n = nframes ? nframes : 1, slots = lz_cap ? index_bytes / lz_cap : n;          /* the checkpoints the budget holds */
+	uint64_t iv = slots ? (n + slots - 1) / slots : n;                                             /* the least interval with ceil(n / iv) <= slots */
+	uint32_t k;
+	iv = iv < 4 ? 4 : (iv + 3) & ~(uint64_t)3;
+	if (iv > 0xFFFFFFFCu) iv = 0xFFFFFFFCu;
+	if (interval) *interval = (uint32_t)iv;
+	k = (uint32_t)(((uint64_t)(f & ~3u) < n ? (f & ~3u) : n - 1) / iv);                            /* (a frame behind the file: the last checkpoint the file has) */
+	while (k > 0 && !(recorded && (recorded[k >> 5] >> (k & 31) & 1u))) k--;
+	return k * (uint32_t)iv;
+}
+
+/* a reader's LZ stage stands in front of frame f: is that a checkpoint it has not recorded yet?  Then the caller copies the buffer and says so */
+static int checkpoint_due(const dpipe* d, uint32_t f)
+{
+	return d->interval && f && f % d->interval == 0 && f / d->interval < d->nckpt && !(d->recorded[f / d->interval >> 5] >> (f / d->interval & 31) & 1u);
+}
+
+static void checkpoint_recorded(dpipe* d, uint32_t f, size_t at)
+{
+	const uint32_t k = f / d->interval;
+	d->recorded[k >> 5] |= 1u << (k & 31); d->ckpt_pos[k] = at; d->checkpoints++;
+}
+
 /* the host LZ stage of one frame on a pool thread: straight into the frame's row of the batch slab (the decoder copies only
    from bytes it has written itself, src < bpos, so the row's old content does not matter) */
 typedef struct unlz { dpipe* d; int ver; const u8* payload; dchunk* c; size_t cap; uint32_t bpos; u8* row; unsigned* left; } unlz;
@@ -1232,11 +1280,12 @@ static void dlz_close(dlz* z)
    device rows, read back used (the one synchronisation a batch needs), cut the batch, commit the frames before the cut to
    the persistent buffer and record b->ready behind the commit: the worker's stream waits for that event, not the host.
    Returns the frames of the batch (0: none left), negative on error. */
-static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, dchunk* c, const u8* file, size_t len, size_t* pos, unsigned want, int ver,
-                     int has_audio, size_t cap)
+static int dlz_batch(dlz* z, dpipe* d, dbatch* b, unsigned want)
 {
+	const u8* file = d->f.image; const size_t len = d->f.len, cap = d->lz_cap; const int has_audio = d->f.has_audio;
+	dchunk* c = d->chunks;
 	const double t0 = now_s();
-	unsigned n = locate_chunks(file, len, *pos, has_audio, c, want), k;
+	unsigned n = locate_chunks(file, len, d->pos, has_audio, c, want), k, k1;
 	size_t lo, hi = 0;
 	if (!n) return 0;
 	lo = c[0].at + 16;
@@ -1258,16 +1307,23 @@ static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, dchunk* c, const u8* fil
 	/* (the staging and h_off of the batch before are free again: the read of its `used` waited for its uploads) */
 	if (agmv_hip_memcpy_async(z->ctx, z->d_src, z->h_stage, hi - lo, 0, z->stream) ||
 	    agmv_hip_memcpy_async(z->ctx, z->d_off, z->h_off, 8 * (size_t)n, 0, z->stream) ||
-	    agmv_hip_lz_decode_frames_sized_dev(z->ctx, ver, z->d_src, z->d_off, z->h_avail, z->h_usize, z->h_csize, n, b->d_slab, d->stride,
+	    agmv_hip_lz_decode_frames_sized_dev(z->ctx, d->f.ver, z->d_src, z->d_off, z->h_avail, z->h_usize, z->h_csize, n, b->d_slab, d->stride,
 	                                        cap, b->d_bpos, z->d_used, z->stream) ||
 	    agmv_hip_memcpy_async(z->ctx, z->h_used, z->d_used, 4 * (size_t)n, 1, z->stream) ||
 	    agmv_hip_stream_sync(z->ctx, z->stream))
 		return -1;
 	for (k = 0; k < n; k++) c[k].used = z->h_used[k];
-	n = cut_batch(file, len, has_audio, c, n, pos);
-	if (agmv_hip_lz_decode_commit_dev(z->ctx, b->d_slab, d->stride, b->d_bpos, n, z->d_persist, cap, z->stream) ||
-	    agmv_hip_event_record(z->ctx, b->ready, z->stream))
-		return -1;
+	n = cut_batch(file, len, has_audio, c, n, &d->pos);
+	/* one commit -- or, for a reader, one per stretch between the checkpoints the batch passes, each taken from the buffer in front of its frame */
+	for (k = 0; k < n; k = k1) {
+		if (checkpoint_due(d, d->done + k)) {
+			if (agmv_hip_memcpy_async(z->ctx, d->d_ckpt + (size_t)((d->done + k) / d->interval - 1) * cap, z->d_persist, cap, 2, z->stream)) return -1;
+			checkpoint_recorded(d, d->done + k, c[k].at);
+		}
+		k1 = d->interval && d->interval - (d->done + k) % d->interval < n - k ? k + d->interval - (d->done + k) % d->interval : n;
+		if (agmv_hip_lz_decode_commit_dev(z->ctx, b->d_slab + (size_t)k * d->stride, d->stride, b->d_bpos + k, k1 - k, z->d_persist, cap, z->stream)) return -1;
+	}
+	if (agmv_hip_event_record(z->ctx, b->ready, z->stream)) return -1;
 	z->batches++;
 	z->secs += now_s() - t0;
 	return (int)n;
@@ -1276,22 +1332,28 @@ static int dlz_batch(dlz* z, const dpipe* d, dbatch* b, dchunk* c, const u8* fil
 /* The host LZ stage of a batch, dlz_batch's counterpart: locate up to `want` chunks from *pos, decompress them on the pool, one frame per task, into
    the rows of b's pinned slab, cut the batch, and then, in frame order and for the frames before the cut, a row takes its stale tail from the
    persistent buffer and the buffer takes the row.  Returns the frames of the batch (0: none left); nothing in this stage can fail. */
-static int host_lz_batch(dpipe* d, dbatch* b, dchunk* c, const u8* file, size_t len, size_t* pos, unsigned want, int ver, int has_audio, size_t cap)
+static int host_lz_batch(dpipe* d, dbatch* b, unsigned want)
 {
-	unsigned left, k, n = left = locate_chunks(file, len, *pos, has_audio, c, want);
+	const u8* file = d->f.image; const size_t len = d->f.len, cap = d->lz_cap; const int has_audio = d->f.has_audio;
+	dchunk* c = d->chunks;
+	unsigned left, k, n = left = locate_chunks(file, len, d->pos, has_audio, c, want);
 	for (k = 0; k < n; k++) {
 		unlz* j = &d->jobs[k];
-		j->d = d; j->ver = ver; j->c = &c[k]; j->left = &left; j->cap = cap;
+		j->d = d; j->ver = d->f.ver; j->c = &c[k]; j->left = &left; j->cap = cap;
 		j->payload = file + c[k].at + 16; j->row = b->h_slab + (size_t)k * d->stride;
 		agmv_pool_submit(d->pool, unlz_task, j);
 	}
 	pthread_mutex_lock(&d->mu);
 	while (left) pthread_cond_wait(&d->cv, &d->mu);
 	pthread_mutex_unlock(&d->mu);
-	n = cut_batch(file, len, has_audio, c, n, pos);
-	for (k = 0; k < n; k++) {                              /* in order: stale bytes, persistent buffer */
+	n = cut_batch(file, len, has_audio, c, n, &d->pos);
+	for (k = 0; k < n; k++) {                              /* in order: (a reader's checkpoint in front of the frame,) stale bytes, persistent buffer */
 		const unlz* j = &d->jobs[k];
 		const size_t bp = j->bpos, tail = bp + 16 < d->stride ? 16 : (bp < d->stride ? d->stride - bp : 0);
+		if (checkpoint_due(d, d->done + k)) {
+			memcpy(d->ckpt + (size_t)((d->done + k) / d->interval - 1) * cap, d->persist, cap);
+			checkpoint_recorded(d, d->done + k, c[k].at);
+		}
 		if (tail) memcpy(j->row + bp, d->persist + bp, tail);
 		memcpy(d->persist, j->row, bp < cap ? bp : cap);
 		b->h_bpos[k] = j->bpos;
@@ -1301,8 +1363,9 @@ static int host_lz_batch(dpipe* d, dbatch* b, dchunk* c, const u8* file, size_t 
 
 /* Everything a run holds, from the plan: a buffer the plan does not call for stays NULL, one it calls for is checked where it is
    made.  The pool and the worker start last.  Returns 0, or -1 with the pipe half-opened: dpipe_close takes it as it is. */
-static int dpipe_open(dpipe* d, dlz* z, agmv_hip_ctx* ctx, uint32_t w, uint32_t h, unsigned cap_frames, unsigned threads, const agmv_sink* sink, uint32_t g0, unsigned deblock)
+static int dpipe_open(dpipe* d, dlz* z, agmv_hip_ctx* ctx, const agmv_dfile* f, unsigned cap_frames, unsigned threads, const agmv_sink* sink, uint32_t g0, unsigned deblock)
 {
+	const uint32_t w = f->w, h = f->h;
 	const char* lzv = getenv("AGMV_LZ_DECODE_DEVICE");     /* opt-in: the LZ stage on the GPU (read when a decode starts) */
 	const dplan* p = &d->plan;
 	const agmv_target* t = agmv_sink_target(sink);
@@ -1314,6 +1377,7 @@ static int dpipe_open(dpipe* d, dlz* z, agmv_hip_ctx* ctx, uint32_t w, uint32_t 
 	pthread_mutex_init(&d->mu, NULL); pthread_cond_init(&d->cv, NULL);
 	d->ctx = ctx; d->w = w; d->h = h; d->npx = npx; d->lz_cap = lz_cap; d->stride = stride; d->cap = cap_frames;
 	d->sink = *sink; d->g0 = g0; d->deblock = deblock; d->plan = dplan_of(sink, w, h, deblock, lzv && atoi(lzv) == 1);
+	d->f = *f; d->pos = f->pos; d->fresh = 1;
 	d->persist = (u8*)calloc(lz_cap, 1); d->chunks = (dchunk*)calloc(d->cap, sizeof(dchunk)); d->slot = (dbatch*)calloc(3, sizeof(dbatch));
 	if (!d->persist || !d->chunks || !d->slot || (!p->lz_dev && !(d->jobs = (unlz*)calloc(d->cap, sizeof(unlz))))) return -1;
 	d->nslots = 3;
@@ -1355,6 +1419,8 @@ static void dpipe_close(dpipe* d, dlz* z)
 		agmv_hip_host_free(b->h_slab); agmv_hip_host_free(b->h_bpos); agmv_hip_host_free(b->h_out);
 		agmv_hip_free_on(ctx, b->d_slab); agmv_hip_free_on(ctx, b->d_bpos); agmv_hip_event_destroy(ctx, b->ready);
 	}
+	if (z->ctx) agmv_hip_free_on(z->ctx, d->d_ckpt);
+	free(d->ckpt); free(d->ckpt_pos); free(d->recorded);
 	dlz_close(z);
 	agmv_hip_free_on(ctx, d->d_bits); agmv_hip_free_on(ctx, d->d_bpos); agmv_hip_free_on(ctx, d->d_nent);
 	agmv_hip_free_on(ctx, d->d_out[0]); agmv_hip_free_on(ctx, d->d_out[1]); agmv_hip_free_on(ctx, d->d_iframe); agmv_hip_free_on(ctx, d->d_scaled);
@@ -1364,53 +1430,75 @@ static void dpipe_close(dpipe* d, dlz* z)
 	pthread_mutex_destroy(&d->mu); pthread_cond_destroy(&d->cv);
 }
 
-/* The frame loop of AGMV_DecodeAGMV / AGMV_DecodeVideo on a file image, `pos` = first byte behind the header: open, loop, close.  The LZ stage of a
+/* Step: the one batch loop.  From where the LZ stage stands (d->pos, d->done) batch by batch -- LZ stage, then the hand-over to the worker -- until `upto` frames have been
+   through the LZ stage, the file holds no further chunk, the worker has failed or (a reader) asks for the restart.  A batch wholly before g0 is not handed over and its
+   slot is filled again; the batch that holds g0 is decoded from row g0 - first on.  Returns an Error. */
+static int dpipe_run(dpipe* d, dlz* z, uint32_t upto)
+{
+	const int viewed = d->sink.viewed;
+	while (d->done < upto) {
+		dbatch* b = &d->slot[d->nfilled % d->nslots];      /* (nfilled is written by this thread alone) */
+		const unsigned want = d->cap < upto - d->done ? d->cap : upto - d->done;
+		unsigned n; int got, stop;
+		pthread_mutex_lock(&d->mu);
+		while (b->filled && !d->failed) pthread_cond_wait(&d->cv, &d->mu);   /* the slot's frames of batch id - nslots are all exported */
+		stop = d->failed || d->restart;
+		pthread_mutex_unlock(&d->mu);
+		if (stop) break;
+		got = d->plan.lz_dev ? dlz_batch(z, d, b, want) : host_lz_batch(d, b, want);
+		if (got < 0) fprintf(stderr, "libagmv(amd): batch LZ stage: %s (the AGMV hot path runs on the GPU only -- no CPU fallback)\n", agmv_hip_last_error());
+		if (got < 0) return MEMORY_CORRUPTION_ERR;
+		if (got == 0) break;
+		n = (unsigned)got;
+		d->lz_frames += n;
+		if (d->done + n <= d->g0) { d->done += n; continue; }      /* wholly before the view's GOP: the LZ stage was all it needed */
+		b->skip = d->g0 > d->done ? d->g0 - d->done : 0;           /* (the batch that holds g0: from row g0 - done on) */
+		b->n = n - b->skip; b->first = d->done + b->skip; b->name0 = *d->sink.count + 1;
+		b->fresh = d->fresh; d->fresh = 0;
+		if (!viewed) *d->sink.count += n;                          /* (a view's frames are counted where they are selected: sink_view) */
+		pthread_mutex_lock(&d->mu);
+		b->filled = 1; d->nfilled++;
+		pthread_cond_broadcast(&d->cv);
+		pthread_mutex_unlock(&d->mu);
+		d->done += n;
+	}
+	return NO_ERR;
+}
+
+/* ... and the end of the worker and the pool, before dpipe_close: what was handed over is decoded, delivered and, for the BMP export, on disk */
+static void dpipe_finish(dpipe* d)
+{
+	unsigned i;
+	pthread_mutex_lock(&d->mu);
+	d->closing = 1;
+	pthread_cond_broadcast(&d->cv);
+	pthread_mutex_unlock(&d->mu);
+	pthread_join(d->th, NULL);
+	pthread_mutex_lock(&d->mu);                            /* every frame that was decoded is on disk before the call returns */
+	for (i = 0; i < d->nslots; i++) while (d->slot[i].decoded && !d->failed) pthread_cond_wait(&d->cv, &d->mu);
+	pthread_mutex_unlock(&d->mu);
+	agmv_pool_stop(d->pool);
+}
+
+/* The frame loop of AGMV_DecodeAGMV / AGMV_DecodeVideo on a file image, `pos` = first byte behind the header: open (dpipe_open), loop (dpipe_run), close (dpipe_finish, dpipe_close): the three steps a reader session (agmv_dreader, below) takes apart.  The LZ stage of a
    batch runs on the pool (host_lz_batch) or on the GPU (dlz_batch).  The frames go to `sink` (agmv_pipeline.h), whose count advances by the frames
    decoded; how they get there is the plan's matter (dplan_of).  A view (sink->viewed; nframes then ends behind the last frame it needs) runs its LZ
    stage from frame 0 like any other, because only that keeps the persistent buffer right; its GPU stage starts at the GOP start g0 from the fresh
    state: a batch wholly before g0 is not handed to the worker and its slot is filled again, the batch that holds g0 is decoded from row g0 - first
    on.  *restart = 1 (and NO_ERR) when the worker found that the first decoded batch derives from the state before it: nothing that run delivered
    counts, and the caller runs g0 = 0. */
-static int decode_run(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
-                      int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink, uint32_t g0, unsigned deblock, AGMV_VIEW_STATS* stats, int* restart)
+static int decode_run(agmv_hip_ctx* ctx, const agmv_dfile* f, unsigned cap_frames, unsigned threads, const agmv_sink* sink, uint32_t g0, unsigned deblock,
+                      AGMV_VIEW_STATS* stats, int* restart)
 {
 	const int viewed = sink->viewed;
+	const uint32_t w = f->w, h = f->h;
+	uint32_t done;
 	dpipe d; dlz z;
-	uint32_t done = 0; unsigned id = 0, i;
-	int rc = dpipe_open(&d, &z, ctx, w, h, cap_frames, threads, sink, g0, deblock) ? MEMORY_CORRUPTION_ERR : NO_ERR;
+	int rc = dpipe_open(&d, &z, ctx, f, cap_frames, threads, sink, g0, deblock) ? MEMORY_CORRUPTION_ERR : NO_ERR;
 	if (rc != NO_ERR) { dpipe_close(&d, &z); return rc; }
-	while (done < nframes) {
-		dbatch* b = &d.slot[id % d.nslots];
-		const unsigned want = d.cap < nframes - done ? d.cap : nframes - done;
-		unsigned n; int got;
-		pthread_mutex_lock(&d.mu);
-		while (b->filled && !d.failed) pthread_cond_wait(&d.cv, &d.mu);      /* the slot's frames of batch id - nslots are all exported */
-		pthread_mutex_unlock(&d.mu);
-		if (d.failed) break;
-		got = d.plan.lz_dev ? dlz_batch(&z, &d, b, d.chunks, file, len, &pos, want, ver, has_audio, d.lz_cap)
-		                    : host_lz_batch(&d, b, d.chunks, file, len, &pos, want, ver, has_audio, d.lz_cap);
-		if (got < 0) fprintf(stderr, "libagmv(amd): batch LZ stage: %s (the AGMV hot path runs on the GPU only -- no CPU fallback)\n", agmv_hip_last_error());
-		if (got <= 0) { if (got < 0) rc = MEMORY_CORRUPTION_ERR; break; }
-		n = (unsigned)got;
-		if (viewed && done + n <= g0) { done += n; continue; }     /* wholly before the view's GOP: the LZ stage was all it needed */
-		b->skip = viewed && g0 > done ? g0 - done : 0;             /* (the batch that holds g0: from row g0 - done on) */
-		b->n = n - b->skip; b->first = done + b->skip; b->name0 = *sink->count + 1;
-		if (!viewed) *sink->count += n;                            /* (a view's frames are counted where they are selected: sink_view) */
-		pthread_mutex_lock(&d.mu);
-		b->filled = 1; d.nfilled = ++id;
-		pthread_cond_broadcast(&d.cv);
-		pthread_mutex_unlock(&d.mu);
-		done += n;
-	}
-	pthread_mutex_lock(&d.mu);
-	d.closing = 1;
-	pthread_cond_broadcast(&d.cv);
-	pthread_mutex_unlock(&d.mu);
-	pthread_join(d.th, NULL);
-	pthread_mutex_lock(&d.mu);                             /* every frame that was decoded is on disk before the call returns */
-	for (i = 0; i < d.nslots; i++) while (d.slot[i].decoded && !d.failed) pthread_cond_wait(&d.cv, &d.mu);
-	pthread_mutex_unlock(&d.mu);
-	agmv_pool_stop(d.pool);
+	rc = dpipe_run(&d, &z, f->nframes);
+	dpipe_finish(&d);
+	done = d.done;
 	if (d.restart) *restart = 1;
 	else if (d.failed) rc = MEMORY_CORRUPTION_ERR;
 	if (d.plan.lz_dev) TRACE("decode: LZ stage device, %u frames in %u batches, %.3f s\n", (unsigned)done, z.batches, z.secs);
@@ -1434,18 +1522,141 @@ static int decode_run(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos,
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
                        int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink, AGMV_VIEW_STATS* stats)
 {
+	const agmv_dfile f = {file, len, pos, w, h, nframes, ver, has_audio};
 	const unsigned long count0 = *sink->count;
 	const unsigned deblock = agmv_deblock_strength();
 	int restart = 0, rc;
 	if (stats) memset(stats, 0, sizeof(*stats));
 	memset(&g_deblock_stats, 0, sizeof(g_deblock_stats));
 	if (deblock) TRACE("decode: deblocking of every batch in front of its sink, strength %u\n", deblock);
-	rc = decode_run(ctx, file, len, pos, w, h, nframes, ver, has_audio, cap_frames, threads, sink, sink->viewed ? sink->view.first & ~3u : 0, deblock, stats, &restart);
+	rc = decode_run(ctx, &f, cap_frames, threads, sink, sink->viewed ? sink->view.first & ~3u : 0, deblock, stats, &restart);
 	if (rc == NO_ERR && restart) {
 		*sink->count = count0;
 		if (stats) memset(stats, 0, sizeof(*stats));               /* (how far the LZ stage of the run given up had come is a matter of timing) */
-		rc = decode_run(ctx, file, len, pos, w, h, nframes, ver, has_audio, cap_frames, threads, sink, 0, deblock, stats, &restart);
+		rc = decode_run(ctx, &f, cap_frames, threads, sink, 0, deblock, stats, &restart);
 	}
 	if (stats) { stats->restarts = (unsigned)restart; stats->delivered = rc == NO_ERR ? (unsigned)(*sink->count - count0) : 0; }
 	return rc;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * reader sessions (include/agmv_reader.h): the pipe of decode_run, kept open between calls
+ * ------------------------------------------------------------------------------------------ */
+struct agmv_dreader {
+	dpipe d; dlz z;
+	uint32_t position, end;                /* the file frame the next read starts at; the frames the file is known to hold (the header's, fewer once a read found its end) */
+	int moved, dead;                       /* a seek left the position somewhere else: the next read starts from a checkpoint; the GPU failed: every read fails */
+	size_t index_bytes;
+	unsigned long count;                   /* the frames the running read has delivered (the sink's count) */
+	unsigned long long delivered; unsigned reads, seeks, restarts;
+};
+
+/* Open: dpipe_open, with the sink of a view of every frame, and the seek index, whose slots are all made here */
+agmv_dreader* agmv_dreader_open(agmv_hip_ctx* ctx, const agmv_dfile* f, unsigned cap_frames, unsigned threads, const agmv_sink* sink, unsigned deblock, size_t index_bytes)
+{
+	agmv_dreader* r = (agmv_dreader*)calloc(1, sizeof(*r));
+	agmv_sink s = *sink;
+	dpipe* d;
+	if (!r) return NULL;
+	d = &r->d;
+	s.viewed = 1; s.count = &r->count;                     /* (a view, whatever it selects: no read decodes into the caller's clip or takes a frame from it) */
+	r->end = f->nframes; r->index_bytes = index_bytes;
+	if (dpipe_open(d, &r->z, ctx, f, cap_frames, threads, &s, 0, deblock)) goto fail;
+	d->keep = 1;                                           /* (the worker reads it behind its first batch at the earliest, which a read hands over) */
+	agmv_reader_checkpoint(f->nframes, d->lz_cap, index_bytes, 0, NULL, &d->interval);
+	d->nckpt = (f->nframes + d->interval - 1) / d->interval;
+	if (d->nckpt < 1) d->nckpt = 1;
+	d->recorded = (uint32_t*)calloc(d->nckpt / 32 + 1, 4); d->ckpt_pos = (size_t*)calloc(d->nckpt, sizeof(size_t));
+	if (!d->recorded || !d->ckpt_pos) goto fail_open;
+	d->recorded[0] = 1; d->ckpt_pos[0] = f->pos;
+	if (d->nckpt > 1) {
+		const size_t bytes = (size_t)(d->nckpt - 1) * d->lz_cap;
+		if (d->plan.lz_dev ? !(d->d_ckpt = (uint8_t*)agmv_hip_malloc_on(r->z.ctx, bytes)) : !(d->ckpt = (u8*)malloc(bytes))) goto fail_open;
+	}
+	TRACE("reader: open, batches of %u frames, seek index of %u checkpoints every %u frames (%.1f MB, %s)\n", d->cap, (unsigned)d->nckpt - 1, (unsigned)d->interval,
+	      (d->nckpt - 1) * (double)d->lz_cap / 1e6, d->plan.lz_dev ? "device" : "host");
+	return r;
+fail_open:
+	dpipe_finish(d);
+fail:
+	dpipe_close(d, &r->z);
+	free(r);
+	return NULL;
+}
+
+/* the worker has released every batch handed over (or has failed) */
+static void dreader_wait(dpipe* d)
+{
+	pthread_mutex_lock(&d->mu);
+	while (d->ndone < d->nfilled && !d->failed) pthread_cond_wait(&d->cv, &d->mu);
+	pthread_mutex_unlock(&d->mu);
+}
+
+/* The LZ stage to the greatest recorded checkpoint <= g0 -- its buffer, its place in the file -- and the GPU stage to start at g0 from the fresh state.  The worker is idle. */
+static int dreader_start_at(agmv_dreader* r, uint32_t g0)
+{
+	dpipe* d = &r->d; dlz* z = &r->z;
+	const uint32_t c = agmv_reader_checkpoint(d->f.nframes, d->lz_cap, r->index_bytes, g0, d->recorded, NULL), k = c / d->interval;
+	if (d->plan.lz_dev) {
+		if (k ? agmv_hip_memcpy_async(z->ctx, z->d_persist, d->d_ckpt + (size_t)(k - 1) * d->lz_cap, d->lz_cap, 2, z->stream)
+		      : agmv_hip_memset_async(z->ctx, z->d_persist, 0, d->lz_cap, z->stream))
+			return -1;
+	} else if (k) memcpy(d->persist, d->ckpt + (size_t)(k - 1) * d->lz_cap, d->lz_cap);
+	else memset(d->persist, 0, d->lz_cap);
+	d->pos = d->ckpt_pos[k]; d->done = c; d->g0 = g0; d->fresh = 1;
+	TRACE("reader: LZ stage from checkpoint %u, GPU stage from frame %u\n", (unsigned)c, (unsigned)g0);
+	return 0;
+}
+
+int agmv_dreader_read(agmv_dreader* r, void* d_dst, uint32_t n)
+{
+	dpipe* d = &r->d;
+	const AGMV_VIEW* v = &d->sink.view;
+	const uint32_t p = r->position, len = agmv_view_length(p, v->step, n, r->end);
+	uint32_t upto, g0 = p & ~3u;
+	int rc;
+	if (r->dead) return -MEMORY_CORRUPTION_ERR;
+	r->reads++;
+	if (!len) return 0;
+	upto = p + (len - 1) * v->step + 1;                    /* behind the last frame the read needs */
+	d->sink.view.first = p; d->sink.view.count = len;      /* (the worker is idle: it reads the sink behind the next hand-over) */
+	if (d->sink.kind == AGMV_SINK_TENSOR) d->sink.tensor.d_dst = d_dst; else d->sink.frames.d_dst = d_dst;
+	for (;;) {
+		r->count = 0;
+		rc = r->moved && dreader_start_at(r, g0) ? MEMORY_CORRUPTION_ERR : NO_ERR;
+		r->moved = 0;
+		if (rc == NO_ERR) rc = dpipe_run(d, &r->z, upto);
+		dreader_wait(d);
+		if (rc != NO_ERR || d->failed) { r->dead = 1; return -MEMORY_CORRUPTION_ERR; }
+		if (!d->restart) break;
+		/* the first batch from the fresh state derives from the state before it: the same read again, both stages from frame 0 */
+		d->restart = 0; r->restarts++; r->moved = 1; g0 = 0;
+	}
+	if (r->count < len) r->end = d->done;                  /* the file holds no further chunk */
+	r->delivered += r->count;
+	r->position = p + (uint32_t)r->count * v->step;
+	if (d->sink.kind == AGMV_SINK_TENSOR) d->sink.tensor.d_dst = NULL; else d->sink.frames.d_dst = NULL;      /* nothing of the caller's is held */
+	return (int)r->count;
+}
+
+void agmv_dreader_seek(agmv_dreader* r, uint32_t frame)
+{
+	r->seeks++;
+	if (frame == r->position) return;
+	r->position = frame; r->moved = 1;
+}
+
+uint32_t agmv_dreader_tell(const agmv_dreader* r) { return r->position; }
+
+void agmv_dreader_stats(const agmv_dreader* r, AGMV_READER_STATS* out)
+{
+	const AGMV_READER_STATS s = {r->d.lz_frames, r->d.gpu_frames, r->delivered, r->reads, r->seeks, r->restarts, r->d.checkpoints, r->d.interval};
+	*out = s;
+}
+
+void agmv_dreader_close(agmv_dreader* r)
+{
+	dpipe_finish(&r->d);
+	dpipe_close(&r->d, &r->z);
+	free(r);
 }

@@ -10,6 +10,7 @@
 #include "agmv_hip_view.h"
 #include "agmv_hip_view_source.h"
 #include "agmv_internal.h"
+#include "agmv_reader.h"
 
 typedef struct agmv_pool agmv_pool;
 agmv_pool* agmv_pool_start(unsigned threads);
@@ -126,6 +127,29 @@ static inline const agmv_target* agmv_sink_target(const agmv_sink* s)
 
 int agmv_decode_stream(agmv_hip_ctx* ctx, const u8* file, size_t len, size_t pos, uint32_t w, uint32_t h, uint32_t nframes, int ver,
                        int has_audio, unsigned cap_frames, unsigned threads, const agmv_sink* sink, AGMV_VIEW_STATS* stats);
+
+/* A file image as the decode drivers read it: len bytes with 16 zero bytes behind them, pos = the first byte behind the header, w x h frames,
+   nframes of them at most, the header's version, whether an AGAC chunk follows every frame chunk. */
+typedef struct agmv_dfile { const u8* image; size_t len, pos; uint32_t w, h, nframes; int ver, has_audio; } agmv_dfile;
+
+/* A reader session (include/agmv_reader.h has the contract): what agmv_decode_stream opens, kept open.  The image must outlive the reader.  `sink` is a
+   FRAMES or TENSOR sink with `viewed` set and the view resolved against the header (step, window; first and count are each read's own), its destination
+   and count are not read; deblock is the strength, 0 = off; index_bytes the budget of the seek index.  agmv_dreader_read returns the frames delivered
+   or a negative Error. */
+typedef struct agmv_dreader agmv_dreader;
+agmv_dreader* agmv_dreader_open(agmv_hip_ctx* ctx, const agmv_dfile* f, unsigned cap_frames, unsigned threads, const agmv_sink* sink, unsigned deblock, size_t index_bytes);
+int agmv_dreader_read(agmv_dreader* r, void* d_dst, uint32_t n);
+void agmv_dreader_seek(agmv_dreader* r, uint32_t frame);
+uint32_t agmv_dreader_tell(const agmv_dreader* r);
+void agmv_dreader_stats(const agmv_dreader* r, AGMV_READER_STATS* out);
+void agmv_dreader_close(agmv_dreader* r);
+
+/* The arithmetic of a reader's seek index, stated once.  *interval (may be NULL) = the distance of its checkpoints in a file of nframes frames whose
+   persistent buffer has lz_cap bytes, under a budget of index_bytes: the smallest multiple of 4, at least 4, with ceil(nframes / interval) * lz_cap <=
+   index_bytes -- and for a budget below one lz_cap the smallest multiple of 4 that is >= nframes: checkpoint 0 alone, the zero buffer, which costs
+   nothing.  Returns the frame the LZ stage starts at for a seek to frame f: the greatest recorded checkpoint <= f & ~3, where bit k of `recorded`
+   (32 per word; NULL: none) says that checkpoint k * interval is recorded; checkpoint 0 always is. */
+uint32_t agmv_reader_checkpoint(uint32_t nframes, size_t lz_cap, size_t index_bytes, uint32_t f, const uint32_t* recorded, uint32_t* interval);
 
 /* the AGAC payloads of a file image (its first chunk at or behind pos) back to back, at most cap bytes; returns their number */
 size_t agmv_gather_audio(const u8* file, size_t len, size_t pos, uint32_t nframes, u8* out, size_t cap);

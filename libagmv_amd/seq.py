@@ -2,6 +2,8 @@
 AGMV_EncodeViewDev / AGMV_DecodeFramesFmtDev / AGMV_DecodeFramesScaledDev / AGMV_EncodeFramesTensorDev / AGMV_DecodeFramesTensorDev (include/agmv.h, libagmv.so).  No logic here: the schedules, the container, both LZ stages and the reading and writing of the
 caller's pixel layout are the library's; torch holds the frames.  The frames live on the library's own device (env AGMV_DEVICE,
 default 0).
+Reader (AGMV_OpenReaderDev ... of include/agmv_reader.h) is a file opened once and read in pieces with the decoder's state kept: what
+decode_frames(frames=, crop=) returns chunk by chunk, without the call's fixed cost and without the LZ stage from frame 0 each time.
 clip_quality / file_quality (AGMV_MeasureFramesDev / AGMV_MeasureFileDev) measure a decoded clip, or a file batch by batch, against
 the frames it was made from, in any of the layouts below, and return a Quality: exact integers per frame and channel, and the
 PSNR, block-mean PSNR and mean SSIM formed from them.
@@ -49,7 +51,7 @@ def load_library():
         p = os.path.join(HERE, "libagmv.so")
         if not os.path.exists(p):
             raise HipUnavailable("%s is missing: run `python -m libagmv_amd.build`; the AGMV hot path has no CPU fallback" % p)
-        _lib = abi.bind(C.CDLL(p), abi.AGMV)
+        _lib = abi.bind(abi.bind(C.CDLL(p), abi.AGMV), abi.READER)
     return _lib
 
 
@@ -508,6 +510,134 @@ def _decode_tensor(path, tensor, target, scale):
     if rc < 0:
         raise RuntimeError("AGMV_DecodeFramesTensorDev(%s, %d x %d, scale %r): Error %d" % (path, w, h, scale, -rc))
     return out[:rc], info
+
+
+class Reader:
+    """A file opened once and read in pieces with the decoder's state kept (include/agmv_reader.h, which holds the contract): what
+    decode_frames(path, ..., frames=range(p, p + n * step, step), crop=crop) returns for every read of n frames at position p, without
+    the call's fixed cost and without the LZ stage from frame 0 each time.  fmt, yuv, full_range, size, scale, mean, std, crop and
+    deblock are decode_frames' and are checked by the same code; step is the stride of the frames a read takes; index_bytes is the
+    budget of the seek index (None: 64 MiB).  Everything the reader holds on the device is allocated here; a read allocates its
+    result, or nothing with out=.
+        with Reader(path, fmt="f16", crop=(0, 0, 224, 224)) as r:
+            for batch in r.batches(16):
+                ...
+    len() is the file's frame count, .info its AGMV_INFO, .tell() the file frame the next read starts at, .seek(f) moves there,
+    .stats() is AGMV_READER_STATS as a dict.  A closed reader raises ValueError."""
+
+    def __init__(self, path, fmt="xrgb32", yuv=None, full_range=False, size=None, scale="bilinear", mean=None, std=None, step=1, crop=None,
+                 deblock=None, index_bytes=None):
+        self._h = None
+        target = _decode_target(size, scale)
+        tensor = _tensor_clip(None, fmt, mean, std, "Reader")
+        _, crop = _decode_selection(None, crop, who="Reader")
+        if not (_is_int(step) and step >= 1):
+            raise ValueError("Reader: step must be an int >= 1, got %r" % (step,))
+        if index_bytes is not None and not (_is_int(index_bytes) and index_bytes >= 1):
+            raise ValueError("Reader: index_bytes must be None or an int >= 1, got %r" % (index_bytes,))
+        d = abi.AGMV_READER_DESC(step=step, index_bytes=index_bytes or 0)
+        if tensor is not None:
+            if yuv is not None or full_range:
+                raise ValueError("Reader: yuv= and full_range= belong to fmt \"nv12\" and \"i420\", not to fmt %r" % (fmt,))
+            d.tensor, d.type, d.mean, d.std = 1, tensor[0], tensor[4], tensor[5]
+        else:
+            v = _fmt_value("Reader", fmt, yuv, full_range)
+            d.fmt, d.yuv_flags = v & 0xFF, v & ~0xFF
+        with _deblock_for_this_call("Reader", deblock):          # (the argument check; the strength itself travels in the description)
+            pass
+        d.deblock = deblock or 0
+        if target is not None:
+            d.filter, d.height, d.width = target
+        if crop is not None:
+            d.y, d.x, d.win_height, d.win_width = crop
+        info, err = AGMV_INFO(), C.c_int(0)
+        L = load_library()
+        h = L.AGMV_OpenReaderDev(os.fsencode(path), C.byref(d), C.byref(info), C.byref(err))
+        if not h:
+            raise (ValueError if err.value in (-1, -4) else RuntimeError)(
+                "AGMV_OpenReaderDev(%s, fmt %r, size %r (%s), step %d, crop %r): %s" % (path, fmt, size, scale, step, crop, {
+                    -1: "the arguments are refused", -4: "the file's frames refuse the window or the target"}.get(err.value, "Error %d" % -err.value)))
+        self._L, self._h, self.info, self.path = L, h, info, path
+        fh, fw = (crop[2], crop[3]) if crop is not None else (info.height, info.width)
+        if target is not None:
+            fh, fw = target[1], target[2]
+        if tensor is not None:
+            self._frame, self._dtype = (3, fh, fw), _tensor_dtypes()[tensor[0]]
+        else:
+            import torch
+            k = d.fmt
+            self._frame = {1: (fh, fw), 2: (fh, fw, 3), 3: (fh, fw, 3), 4: (fh, fw, 4), 5: (3, fh, fw), 16: (fh * 3 // 2, fw), 17: (fh * 3 // 2, fw)}[k]
+            self._dtype = torch.int32 if k == 1 else torch.uint8
+        self.step = step
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("Reader: the reader is closed")
+        return self._h
+
+    def __len__(self):
+        return int(self.info.number_of_frames)
+
+    def tell(self):
+        return int(self._L.AGMV_ReaderTell(self._handle()))
+
+    def seek(self, frame):
+        if not (_is_int(frame) and frame >= 0):
+            raise ValueError("Reader.seek: a frame index, an int >= 0, is needed, got %r" % (frame,))
+        self._L.AGMV_ReaderSeek(self._handle(), min(frame, 0xFFFFFFFF))
+
+    def read(self, n, out=None):
+        """the next (at most) n frames as a tensor of exactly the frames delivered, none at the file's end; out=, a contiguous tensor
+        of the reader's dtype on the library's device whose frames have the reader's shape, receives them instead, and the slice
+        of it that holds them is returned"""
+        import torch
+        h = self._handle()
+        if not (_is_int(n) and n >= 0):
+            raise ValueError("Reader.read: n must be an int >= 0, got %r" % (n,))
+        left = len(range(min(self.tell(), len(self)), len(self), self.step))
+        if out is None:
+            n = min(n, left)
+            out = torch.empty((n,) + self._frame, dtype=self._dtype, device=_device())
+        else:
+            if not (out.is_cuda and out.device == torch.device(_device()) and out.dtype == self._dtype and tuple(out.shape[1:]) == self._frame
+                    and out.is_contiguous()):
+                raise ValueError("Reader.read: out must be a contiguous %s tensor [n, %s] on %s, got %s %s on %s"
+                                 % (self._dtype, ", ".join(map(str, self._frame)), _device(), out.dtype, tuple(out.shape), out.device))
+            n = min(n, out.shape[0])
+            torch.cuda.synchronize(out.device)         # the library works on streams of its own
+        if n == 0:
+            return out[:0]
+        rc = self._L.AGMV_ReaderReadDev(h, out.data_ptr(), n)
+        if rc < 0:
+            raise RuntimeError("AGMV_ReaderReadDev(%s, %d frames at %d): Error %d" % (self.path, n, self.tell(), -rc))
+        return out[:rc]
+
+    def batches(self, n):
+        """the reads of n frames from the current position to the file's end, one after the other"""
+        while True:
+            got = self.read(n)
+            if got.shape[0] == 0:
+                return
+            yield got
+
+    def stats(self):
+        st = abi.AGMV_READER_STATS()
+        self._L.AGMV_GetReaderStats(self._handle(), C.byref(st))
+        return {k: int(getattr(st, k)) for k, _ in abi.AGMV_READER_STATS._fields_}
+
+    def close(self):
+        if self._h is not None:
+            self._L.AGMV_CloseReader(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
 
 
 def decode_audio(path, fmt="s16", cap_samples=None):
