@@ -12,15 +12,15 @@ Layout
                       BMP I/O, palette build, synthetic clip generator
   abi.py              the public C signatures, stated once: both libraries' ctypes tables and the structures (tests/test_abi.py holds them to the headers)
   hip.py              ctypes binding of the C-ABI for tests / bench (torch = device memory only)
-  seq.py              ctypes calls of the memory-sequence entry points of include/agmv.h (.agmv file <-> CUDA tensor: five RGB layouts, NV12, I420; normalised float tensors; a scale to a target size before the encode and behind the decode; views of a file and of a clip; reader sessions, a file read in pieces with the decoder's state kept; a decoded clip or file measured against its reference)
+  seq.py              ctypes calls of the memory-sequence entry points of include/agmv.h (.agmv file <-> CUDA tensor: five RGB layouts, NV12, I420; normalised float tensors; a scale to a target size before the encode and behind the decode; views of a file and of a clip; reader sessions, a file read in pieces with the decoder's state kept; writer sessions, a clip encoded in pieces into the one-shot call's file; a decoded clip or file measured against its reference)
   build.py            in-tree build of libagmv_hip.so / libagmv.so (hipcc, gcc)
 
 There is no CPU fallback anywhere in this package: without the built HIP library, or
 without a GPU, the hot-path calls raise.
 """
 from .hip import PCMFMT, PIXFMT, TENSORFMT, YUVFMT, AgmvHip, HipUnavailable, lib_path, load_library  # noqa: F401
-from .seq import DECODE_SCALE, SCALE, SCHEDULE_ADAPTIVE, SCHEDULE_FULL, SCHEDULE_PDIFS, Quality, Reader, clip_quality, deblock_stats, decode_audio, decode_frames, encode_frames, encode_view_stats, file_quality, fit_window, stabilise_stats  # noqa: F401
+from .seq import DECODE_SCALE, SCALE, SCHEDULE_ADAPTIVE, SCHEDULE_FULL, SCHEDULE_PDIFS, Quality, Reader, Writer, clip_quality, deblock_stats, decode_audio, decode_frames, encode_frames, encode_view_stats, file_quality, fit_window, stabilise_stats  # noqa: F401
 
-__all__ = ["AgmvHip", "HipUnavailable", "lib_path", "load_library", "encode_frames", "decode_frames", "Reader", "decode_audio",
+__all__ = ["AgmvHip", "HipUnavailable", "lib_path", "load_library", "encode_frames", "decode_frames", "Reader", "Writer", "decode_audio",
            "clip_quality", "file_quality", "Quality", "stabilise_stats", "deblock_stats", "encode_view_stats", "fit_window",
            "SCHEDULE_FULL", "SCHEDULE_PDIFS", "SCHEDULE_ADAPTIVE", "PIXFMT", "YUVFMT", "PCMFMT", "TENSORFMT", "SCALE", "DECODE_SCALE"]

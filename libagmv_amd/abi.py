@@ -1,7 +1,7 @@
 """The public C signatures, stated once: the structures of include/agmv.h that Python passes, every function of
 include/agmv_hip.h (HIP), of include/agmv_hip_view.h (HIP_VIEW), of include/agmv_hip_view_source.h (HIP_VIEW_SOURCE), of
 include/agmv_hip_stabilise.h (HIP_STABILISE) and of include/agmv_hip_deblock.h (HIP_DEBLOCK), every function of include/agmv.h that Python calls on libagmv.so (AGMV)
-and every function of include/agmv_reader.h, which the same library exports (READER), as
+and every function of include/agmv_reader.h and include/agmv_writer.h, which the same library exports (READER, WRITER), as
 name -> (restype, (argtypes...)).  bind() sets them on a loaded library.  tests/test_abi.py checks both tables and the
 structures against the headers.  ctypes only, and no library is loaded here: the test children import this module the
 way a C host would include the headers."""
@@ -56,6 +56,19 @@ class AGMV_READER_DESC(Structure):
 class AGMV_READER_STATS(Structure):
     _fields_ = [("lz_frames", c_ulonglong), ("gpu_frames", c_ulonglong), ("delivered", c_ulonglong), ("reads", c_uint), ("seeks", c_uint),
                 ("restarts", c_uint), ("checkpoints", c_uint), ("interval", c_uint)]
+
+
+class AGMV_WRITER_DESC(Structure):
+    # include/agmv_writer.h; the enums are c_int
+    _fields_ = [("tensor", c_int), ("fmt", c_int), ("yuv_flags", c_int), ("type", c_int), ("mean", c_float * 3), ("std", c_float * 3),
+                ("src_width", c_uint), ("src_height", c_uint), ("width", c_uint), ("height", c_uint), ("filter", c_int),
+                ("frames_per_second", c_uint), ("opt", c_int), ("quality", c_int), ("compression", c_int), ("schedule", c_int),
+                ("ring_frames", c_uint)]
+
+
+class AGMV_WRITER_STATS(Structure):
+    _fields_ = [("analysed", c_ulonglong), ("taken", c_ulonglong), ("written", c_ulonglong), ("writes", c_uint), ("batches", c_uint),
+                ("waits", c_uint), ("ring_frames", c_uint)]
 
 
 # vp: any pointer but the five below and `const char*`; ul: the header's u32; the enums and Bool are c_int
@@ -282,6 +295,15 @@ READER = {
     "AGMV_ReaderTell": (ul, (vp,)),
     "AGMV_GetReaderStats": (None, (vp, POINTER(AGMV_READER_STATS))),
     "AGMV_CloseReader": (None, (vp,)),
+}
+
+# include/agmv_writer.h, exported by libagmv.so
+WRITER = {
+    "AGMV_OpenWriterDev": (vp, (c_char_p, POINTER(AGMV_WRITER_DESC), POINTER(c_int))),
+    "AGMV_WriterAnalyseDev": (c_int, (vp, vp, ul)),
+    "AGMV_WriterWriteDev": (c_int, (vp, vp, ul)),
+    "AGMV_CloseWriter": (c_int, (vp, POINTER(c_ulong))),
+    "AGMV_GetWriterStats": (None, (vp, POINTER(AGMV_WRITER_STATS))),
 }
 
 

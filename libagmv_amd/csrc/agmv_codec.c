@@ -24,6 +24,7 @@
 #include "agmv_hip.h"
 #include "agmv_internal.h"
 #include "agmv_pipeline.h"
+#include "agmv_writer.h"
 
 /* ------------------------------------------------------------------------------------------ */
 static agmv_hip_ctx* g_ctx = NULL;
@@ -477,9 +478,20 @@ static agmv_seq* seq_open(AGMV* a, FILE* file, const agmv_source* src, AGMV_OPT 
 	agmv_seq_opts o = {.mode512 = mode512_of(opt), .lz77 = AGMV_GetCompression(a) != AGMV_LZSS_COMPRESSION, .audio_chunks = audio_chunks, .use_interp = use_interp,
 	                   .cap = batch_frames((size_t)AGMV_GetWidth(a) * AGMV_GetHeight(a)), .devices = devices(), .threads = lz_threads(), .pal = pal};
 	int i;
-	scaled_size(opt, &o.scale_w, &o.scale_h);
+	if (!src->ring_frames) scaled_size(opt, &o.scale_w, &o.scale_h);      /* (a writer's ring holds the frames at the encode size) */
 	for (i = 0; i < 256; i++) { pal[i] = (uint32_t)a->header.palette0[i]; pal[256 + i] = o.mode512 ? (uint32_t)a->header.palette1[i] : 0; }
+	if (!file) o.pal = NULL;                                  /* a writer session: palette and file follow (seq_start) */
 	return agmv_seq_open(a, file, src, &o);
+}
+
+/* ... for a sequence opened without a file: the object's palette, as seq_open reads it, and the file */
+static void seq_start(agmv_seq* s, AGMV* a, FILE* file, AGMV_OPT opt)
+{
+	uint32_t pal[512];
+	const int m512 = mode512_of(opt);
+	int i;
+	for (i = 0; i < 256; i++) { pal[i] = (uint32_t)a->header.palette0[i]; pal[256 + i] = m512 ? (uint32_t)a->header.palette1[i] : 0; }
+	agmv_seq_start(s, file, pal, m512);
 }
 
 /* AGMV_BuildPalette with the picked colours moved by weighted k-means on the GPU between the pick and the slot map
@@ -524,14 +536,39 @@ int AGMV_BuildPaletteRefined(const unsigned* hist, AGMV_QUALITY quality, AGMV_OP
 	return 0;
 }
 
-/* pass 1 of the palette build on the GPU (histogram), pick on the host, refinement (when asked for) on the GPU */
-static void build_palette_from_frames(const agmv_source* src, u32 start, u32 end, u32 size, AGMV_QUALITY quality,
-                                      AGMV_OPT opt, u32* p0, u32* p1)
+/* Histogram -> palette -> header, the step the sequence encoders and a writer session share: the pick on the host, `refine` rounds of the
+   refinement (0: none) on the GPU, then the file created with the header that carries the palette.  Aborts where the file cannot be created. */
+static FILE* create_with_palette(AGMV* a, const char* filename, const uint32_t* hist, AGMV_QUALITY quality, AGMV_OPT opt, unsigned refine)
 {
-	uint32_t* hist = (uint32_t*)malloc(4u << 19);
-	agmv_histogram_frames(ctx(), src, start, end, size, (int)quality, lz_threads(), hist);
-	if (AGMV_BuildPaletteRefined(hist, quality, opt, p0, p1, palette_refine(), NULL)) agmv_die("internal: palette build refused its arguments");
-	free(hist);
+	u32 p0[256], p1[256];
+	FILE* file;
+	if (AGMV_BuildPaletteRefined(hist, quality, opt, p0, p1, refine, NULL)) agmv_die("internal: palette build refused its arguments");
+	file = fopen(filename, "wb");
+	if (!file) { fprintf(stderr, "libagmv(amd): cannot create %s\n", filename); abort(); }
+	AGMV_SetICP0(a, p0);
+	AGMV_SetICP1(a, p1);
+	AGMV_EncodeHeader(file, a);
+	return file;
+}
+
+/* the frame span a PDIFS file's rate and audio chunks are formed from (reference src/agmv_encode.c:2296-2353): integer halves for the heavy
+   modes, x0.75 in double (float for GBA_III) for the light ones */
+static int heavy_pdifs(AGMV_OPT o) { return o == AGMV_OPT_I || o == AGMV_OPT_ANIM || o == AGMV_OPT_GBA_I || o == AGMV_OPT_GBA_II; }
+
+static u32 pdifs_adjusted(AGMV_OPT opt, u32 span)
+{
+	if (heavy_pdifs(opt)) return span / 2;
+	return opt == AGMV_OPT_GBA_III ? (u32)(span * 0.75f) : (u32)(span * 0.75);
+}
+
+/* the header fields that depend on what was written, patched behind the last chunk (:3615-3620, :2225-2231): the frame count at
+   offset 4 and the frames per second, times `rate`, at offset 18 */
+static void patch_header(FILE* file, AGMV* a, u32 written, f32 rate)
+{
+	fseek(file, 4, SEEK_SET);
+	AGMV_WriteLong(file, written);
+	fseek(file, 18, SEEK_SET);
+	AGMV_WriteLong(file, (u32)round(AGMV_GetFramesPerSecond(a) * rate));
 }
 
 static void dump_gba_header(const char* filename)
@@ -555,8 +592,6 @@ static void dump_gba_header(const char* filename)
 	fclose(out);
 	free(data);
 }
-
-static int heavy_pdifs(AGMV_OPT o) { return o == AGMV_OPT_I || o == AGMV_OPT_ANIM || o == AGMV_OPT_GBA_I || o == AGMV_OPT_GBA_II; }
 
 static void require_bmp(u8 img_type)
 {
@@ -631,19 +666,18 @@ static void similarity_close(similarity* m) { free(m->fa); free(m->fb); free(m->
 static void encode_sequence(AGMV* a, const char* filename, const agmv_source* src, AGMV_SCHEDULE schedule, u32 start_frame,
                             u32 end_frame, u32 width, u32 height, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression)
 {
-	u32 p0[256], p1[256], adjusted = end_frame - start_frame, i;
+	u32 adjusted = end_frame - start_frame, i;
 	int sw, sh;
 	FILE* file;
 	agmv_seq* s;
 	u32 written;
+	uint32_t* hist = (uint32_t*)malloc(4u << 19);
+	if (!hist) agmv_die("out of host memory");
 	AGMV_SetOPT(a, opt);
 	AGMV_SetCompression(a, compression);
 	if (schedule == AGMV_SCHEDULE_PDIFS) {
 		AGMV_SetLeniency(a, 0);
-		/* :2296-2353: integer halves for the heavy modes, x0.75 in double (float for GBA_III) for the light ones */
-		if (heavy_pdifs(opt)) adjusted /= 2;
-		else if (opt == AGMV_OPT_GBA_III) adjusted = (u32)(adjusted * 0.75f);
-		else adjusted = (u32)(adjusted * 0.75);
+		adjusted = pdifs_adjusted(opt, adjusted);
 	} else if (schedule == AGMV_SCHEDULE_ADAPTIVE) {
 		f32 len;
 		switch (opt) {                                        /* :744-790 */
@@ -656,7 +690,8 @@ static void encode_sequence(AGMV* a, const char* filename, const agmv_source* sr
 	scaled_size(opt, &sw, &sh);
 	if (sw) { AGMV_SetWidth(a, (u32)sw); AGMV_SetHeight(a, (u32)sh); }     /* the GBA / NDS opts encode at their own size */
 
-	build_palette_from_frames(src, start_frame, end_frame, width * height, quality, opt, p0, p1);
+	/* pass 1 of the palette build on the GPU (histogram) */
+	agmv_histogram_frames(ctx(), src, start_frame, end_frame, width * height, (int)quality, lz_threads(), hist);
 	if (schedule == AGMV_SCHEDULE_PDIFS && a->audio_chunk) a->audio_chunk->size = (u32)(a->header.audio_size / (f32)adjusted);   /* 0 without an audio track */
 	/* :4024 divides by end_frame - start_frame, one less than the frames (and chunks) it writes: with a track, the chunks of a FULL
 	   file ask for more codes than audio_size holds, and AGMV_EncodeAudioChunk writes zeros where the reference reads on */
@@ -673,11 +708,8 @@ static void encode_sequence(AGMV* a, const char* filename, const agmv_source* sr
 		a->audio_track->start_point = 0;
 	}
 
-	file = fopen(filename, "wb");
-	if (!file) { fprintf(stderr, "libagmv(amd): cannot create %s\n", filename); abort(); }
-	AGMV_SetICP0(a, p0);
-	AGMV_SetICP1(a, p1);
-	AGMV_EncodeHeader(file, a);
+	file = create_with_palette(a, filename, hist, quality, opt, palette_refine());
+	free(hist);
 
 	if (schedule == AGMV_SCHEDULE_FULL) {                     /* every input frame, no PDIFS, no header patch */
 		s = seq_open(a, file, src, opt, AGMV_GetTotalAudioDuration(a) != 0, 0);
@@ -688,7 +720,6 @@ static void encode_sequence(AGMV* a, const char* filename, const agmv_source* sr
 		   middle frames of a light group, the two frames of a heavy one) is not similar -- the one frame alone.
 		   NDS is "light" only for BMP input (:2727 vs :2810), and the frames of both sources are what BMP input gives */
 		similarity m;
-		f32 rate;
 		s = seq_open(a, file, src, opt, schedule == AGMV_SCHEDULE_PDIFS, 1);
 		if (schedule == AGMV_SCHEDULE_ADAPTIVE) similarity_open(&m, src, a, opt);
 		for (i = start_frame; i <= end_frame;) {
@@ -700,11 +731,7 @@ static void encode_sequence(AGMV* a, const char* filename, const agmv_source* sr
 		if (schedule == AGMV_SCHEDULE_ADAPTIVE) similarity_close(&m);
 		written = agmv_seq_close(s);
 
-		fseek(file, 4, SEEK_SET);                             /* :3615-3620, :2225-2231 */
-		AGMV_WriteLong(file, written);
-		fseek(file, 18, SEEK_SET);
-		rate = schedule == AGMV_SCHEDULE_PDIFS ? (f32)adjusted / (AGMV_GetNumberOfFrames(a) + 1) : (f32)written / AGMV_GetNumberOfFrames(a);
-		AGMV_WriteLong(file, (u32)round(AGMV_GetFramesPerSecond(a) * rate));
+		patch_header(file, a, written, schedule == AGMV_SCHEDULE_PDIFS ? (f32)adjusted / (AGMV_GetNumberOfFrames(a) + 1) : (f32)written / AGMV_GetNumberOfFrames(a));
 	}
 	fclose(file);
 	DestroyAGMV(a);                                           /* the callee frees the caller's object, :3625 */
@@ -976,6 +1003,229 @@ int AGMV_EncodeFramesTensorDev(const char* filename, const void* d_tensor, AGMV_
 	int i, rc = known_tensor(type, mean, std, table) ? encode_frames_refused(filename, d_tensor, num_of_frames, width, height, opt, quality, compression, schedule) : -1;
 	for (i = 0; i < 3 && !rc; i++) { ab[i] = (float)(255.0 * (double)std[i]); ab[3 + i] = (float)(255.0 * (double)mean[i]); }
 	return audio_consumed(rc ? rc : encode_materialised(filename, &f, num_of_frames, width, height, frames_per_second, opt, quality, compression, schedule));
+}
+
+/* Writer sessions (include/agmv_writer.h has the contract): the checks of the one-shot call of the same layout, one persistent histogram for pass 1,
+   and for pass 2 a ring of XRGB32 frames at the encode size that is the source of an agmv_seq opened here and started at the first write.  How a
+   stretch of frames reaches the ring: a conversion (STAGE_COPY), the box filter (STAGE_AREA), a gather through d_index (STAGE_GATHER: the nearest
+   filter of a target size, or the scale of a GBA / NDS opt), or the tensor's reading rule (STAGE_TENSOR; under a GBA / NDS opt into d_xrgb first,
+   at the source's size, and gathered from there). */
+struct AGMV_WRITER {
+	AGMV_WRITER_DESC d; char* filename; AGMV* a; FILE* file; agmv_seq* s;
+	agmv_hip_ctx* c; void* stream;
+	enum { STAGE_COPY, STAGE_AREA, STAGE_GATHER, STAGE_TENSOR } how;
+	int fmt;                               /* of the frames handed in: the AGMV_PIXFMT with its flags, or the AGMV_TENSORFMT */
+	int hist_as_handed_in;                 /* the palette's histogram is of the frames before the scale (no target size: the one-shot call's rule) */
+	uint32_t src_w, src_h, w, h;           /* of the frames handed in, of the frames encoded */
+	size_t src_px, src_bytes, npx;
+	float ab[6];
+	uint32_t *d_hist, *d_ring, *d_index, *d_xrgb, ring, xrgb_frames;
+	unsigned refine; int pdifs, heavy;
+	unsigned long long analysed, taken;
+	uint32_t groups;                       /* PDIFS: groups pushed */
+	unsigned writes, waits;
+};
+
+/* what the one-shot call of the description's layout refuses before it opens a device, with a clip that is never read and a frame count that passes
+   (the count's check waits for the close) */
+static int writer_refused(const char* filename, const AGMV_WRITER_DESC* q)
+{
+	const u32 any = 0x7FFFFFFFul;
+	const int sized = q->width != 0 || q->height != 0, fmt = (int)q->fmt | q->yuv_flags;
+	uint32_t table[768];
+	int rc;
+	if (q->schedule == AGMV_SCHEDULE_ADAPTIVE) return -1;
+	if (q->tensor) {
+		rc = known_tensor(q->type, q->mean, q->std, table) ? encode_frames_refused(filename, q, any, q->src_width, q->src_height, q->opt, q->quality, q->compression, q->schedule) : -1;
+		return rc ? rc : sized ? -3 : 0;
+	}
+	if (sized)
+		return encode_scaled_refused(filename, q, (AGMV_PIXFMT)fmt, any, q->src_width, q->src_height, q->width, q->height, q->filter, q->opt, q->quality, q->compression, q->schedule);
+	return known_pixfmt(fmt) ? encode_frames_refused(filename, q, any, q->src_width, q->src_height, q->opt, q->quality, q->compression, q->schedule) : -1;
+}
+
+static void writer_free(AGMV_WRITER* w)
+{
+	agmv_hip_free_on(w->c, w->d_hist); agmv_hip_free_on(w->c, w->d_ring); agmv_hip_free_on(w->c, w->d_index); agmv_hip_free_on(w->c, w->d_xrgb);
+	if (w->stream) agmv_hip_stream_destroy(w->c, w->stream);
+	DestroyAGMV(w->a);
+	free(w->filename);
+	free(w);
+}
+
+AGMV_WRITER* AGMV_OpenWriterDev(const char* filename, const AGMV_WRITER_DESC* q, int* error)
+{
+	int err = q ? writer_refused(filename, q) : -1, sw, sh, i;
+	AGMV_WRITER* w = NULL;
+	if (!err && !(w = (AGMV_WRITER*)calloc(1, sizeof(*w)))) agmv_die("out of host memory");
+	if (w) {
+		const int sized = q->width != 0 || q->height != 0;
+		uint32_t* index = NULL;
+		unsigned cap, batch_sources;
+		scaled_size(q->opt, &sw, &sh);
+		w->d = *q; w->c = ctx(); w->pdifs = q->schedule == AGMV_SCHEDULE_PDIFS; w->heavy = heavy_pdifs(q->opt); w->refine = palette_refine();
+		w->src_w = (uint32_t)q->src_width; w->src_h = (uint32_t)q->src_height; w->src_px = (size_t)w->src_w * w->src_h;
+		w->w = sw ? (uint32_t)sw : sized ? (uint32_t)q->width : w->src_w; w->h = sw ? (uint32_t)sh : sized ? (uint32_t)q->height : w->src_h; w->npx = (size_t)w->w * w->h;
+		w->fmt = q->tensor ? (int)q->type : (int)q->fmt | q->yuv_flags;
+		w->src_bytes = q->tensor ? agmv_hip_tensor_frame_bytes(w->fmt, w->src_px) : agmv_fmt_frame_bytes(w->fmt, w->src_w, w->src_h);
+		w->how = q->tensor ? STAGE_TENSOR : sized ? (q->filter == AGMV_SCALE_AREA ? STAGE_AREA : STAGE_GATHER) : sw ? STAGE_GATHER : STAGE_COPY;
+		w->hist_as_handed_in = !q->tensor && !sized;
+		for (i = 0; i < 3 && q->tensor; i++) { w->ab[i] = (float)(255.0 * (double)q->std[i]); w->ab[3 + i] = (float)(255.0 * (double)q->mean[i]); }
+		cap = batch_frames(w->npx); batch_sources = w->pdifs ? 2 * cap : cap;
+		w->ring = 4 * batch_sources + (w->pdifs ? 6 : 0);
+		if (q->ring_frames) w->ring = q->ring_frames < batch_sources + (w->pdifs ? 6 : 0) ? batch_sources + (w->pdifs ? 6 : 0) : q->ring_frames;
+		w->filename = (char*)malloc(strlen(filename) + 1);
+		if (!w->filename) agmv_die("out of host memory");
+		strcpy(w->filename, filename);
+		if (sw) index = agmv_source_index(w->src_w, w->src_h, sw, sh, w->w, w->h);
+		else if (w->how == STAGE_GATHER && !(index = agmv_scale_index(w->src_w, w->src_h, w->w, w->h))) agmv_die("out of host memory");
+		w->d_hist = (uint32_t*)agmv_hip_malloc_on(w->c, 4u << 19); w->d_ring = (uint32_t*)agmv_hip_malloc_on(w->c, 4 * w->npx * w->ring);
+		if (index) w->d_index = (uint32_t*)agmv_hip_malloc_on(w->c, 4 * w->npx);
+		if (index && q->tensor) { w->xrgb_frames = cap; w->d_xrgb = (uint32_t*)agmv_hip_malloc_on(w->c, 4 * w->src_px * cap); }
+		if (!w->d_hist || !w->d_ring || (index && !w->d_index) || (w->xrgb_frames && !w->d_xrgb)) {      /* as the one-shot calls answer a clip they cannot hold */
+			free(index); writer_free(w);
+			w = NULL; err = -4;
+		} else {
+			const agmv_source src = {.d_frames = w->d_ring, .fmt = AGMV_PIXFMT_XRGB32, .src_w = w->w, .src_h = w->h, .first = 1, .device = agmv_hip_ctx_device(w->c), .ring_frames = w->ring};
+			if (!(w->stream = agmv_hip_stream_create(w->c))) agmv_die("stream for the writer");
+			if (agmv_hip_memset_async(w->c, w->d_hist, 0, 4u << 19, w->stream) || (index && agmv_hip_memcpy_async(w->c, w->d_index, index, 4 * w->npx, 0, w->stream)) ||
+			    agmv_hip_stream_sync(w->c, w->stream))
+				agmv_die("writer set-up");
+			free(index);
+			w->a = CreateAGMV(0, w->w, w->h, q->frames_per_second);
+			AGMV_SetOPT(w->a, q->opt); AGMV_SetCompression(w->a, q->compression);
+			if (w->pdifs) AGMV_SetLeniency(w->a, 0);
+			w->s = seq_open(w->a, NULL, &src, q->opt, w->pdifs, w->pdifs);      /* (a PDIFS file carries an AGAC chunk header behind every frame, empty without a track) */
+		}
+	}
+	if (error) *error = err;
+	return w;
+}
+
+/* n frames at `at`, as handed in, to n XRGB32 frames of the encode size at dst, on the writer's stream */
+static int writer_stage(AGMV_WRITER* w, const u8* at, uint32_t n, uint32_t* dst)
+{
+	uint32_t nb;
+	switch (w->how) {
+	case STAGE_AREA: return agmv_hip_scale_area_dev(w->c, w->fmt, at, w->src_w, w->src_h, n, w->w, w->h, dst, w->stream);
+	case STAGE_GATHER: return agmv_fmt_gather(w->c, w->fmt, w->src_w, w->src_h, at, n, w->d_index, w->npx, dst, w->stream);
+	case STAGE_TENSOR:
+		if (!w->d_xrgb) return agmv_hip_tensor_to_xrgb_async(w->c, w->fmt, at, w->npx, n, w->ab, dst, w->stream);
+		for (; n; n -= nb, at += nb * w->src_bytes, dst += nb * w->npx) {
+			nb = n < w->xrgb_frames ? n : w->xrgb_frames;
+			if (agmv_hip_tensor_to_xrgb_async(w->c, w->fmt, at, w->src_px, nb, w->ab, w->d_xrgb, w->stream) ||
+			    agmv_fmt_gather(w->c, AGMV_PIXFMT_XRGB32, w->src_w, w->src_h, w->d_xrgb, nb, w->d_index, w->npx, dst, w->stream))
+				return -1;
+		}
+		return 0;
+	default: return agmv_fmt_to_xrgb(w->c, w->fmt, w->src_w, w->src_h, at, n, w->npx, dst, w->stream);
+	}
+}
+
+/* Pass 1: the frames join d_hist in the layout the one-shot call histograms -- as handed in, or, for a target size and a tensor, as XRGB32 frames made
+   piece by piece in the ring, which is empty until the first write (a tensor under a GBA / NDS opt: in d_xrgb, before the scale) */
+int AGMV_WriterAnalyseDev(AGMV_WRITER* w, const void* d_frames, u32 n)
+{
+	const u8* at = (const u8*)d_frames;
+	uint32_t left = (uint32_t)n, nb;
+	int failed = 0;
+	if (!w || (!d_frames && n)) return -1;
+	if (!n) return 0;
+	if (w->file) return -6;
+	if (n > 0x7FFFFFFFul || w->analysed + n > 0x7FFFFFFFul) return -2;
+	if (w->hist_as_handed_in) failed = agmv_fmt_histogram(w->c, w->fmt, w->src_w, w->src_h, at, left, w->src_px, (int)w->d.quality, w->d_hist, w->stream);
+	else for (; left && !failed; left -= nb, at += nb * w->src_bytes) {
+		if (w->d_xrgb) {
+			nb = left < w->xrgb_frames ? left : w->xrgb_frames;
+			failed = agmv_hip_tensor_to_xrgb_async(w->c, w->fmt, at, w->src_px, nb, w->ab, w->d_xrgb, w->stream) ||
+			         agmv_fmt_histogram(w->c, AGMV_PIXFMT_XRGB32, w->src_w, w->src_h, w->d_xrgb, nb, w->src_px, (int)w->d.quality, w->d_hist, w->stream);
+		} else {
+			nb = left < w->ring ? left : w->ring;
+			failed = writer_stage(w, at, nb, w->d_ring) || agmv_fmt_histogram(w->c, AGMV_PIXFMT_XRGB32, w->w, w->h, w->d_ring, nb, w->npx, (int)w->d.quality, w->d_hist, w->stream);
+		}
+	}
+	if (failed || agmv_hip_stream_sync(w->c, w->stream)) agmv_die("writer histogram");
+	w->analysed += n;
+	return 0;
+}
+
+/* the schedule's frames that the arrivals so far decide, pushed: sources are numbered from 1, as the one-shot calls number theirs */
+static void writer_push(AGMV_WRITER* w, unsigned long long before)
+{
+	if (!w->pdifs) {
+		for (; before < w->taken; before++) agmv_seq_push(w->s, (long)before + 1, -1);
+		return;
+	}
+	for (; w->groups < agmv_writer_groups((uint32_t)w->taken, w->heavy, 0); w->groups++) {
+		const long i = (long)w->groups * (w->heavy ? 2 : 4) + 1;
+		if (w->heavy) agmv_seq_push(w->s, i, i + 1);
+		else { agmv_seq_push(w->s, i, -1); agmv_seq_push(w->s, i + 1, i + 2); agmv_seq_push(w->s, i + 3, -1); }
+	}
+}
+
+/* Pass 2.  The first write freezes the palette: histogram -> palette -> header, then the workers receive the palette and the file.  The frames go into the
+   ring stretch by stretch -- as far as it is free and does not wrap -- and are pushed once they are complete there. */
+int AGMV_WriterWriteDev(AGMV_WRITER* w, const void* d_frames, u32 n)
+{
+	const u8* at = (const u8*)d_frames;
+	uint32_t left = (uint32_t)n;
+	if (!w || (!d_frames && n)) return -1;
+	if (!n) return 0;
+	if (!w->analysed) return -6;
+	if (n > 0x7FFFFFFFul || w->taken + n > 0x7FFFFFFFul) return -2;
+	if (!w->file) {
+		uint32_t* hist = (uint32_t*)malloc(4u << 19);
+		if (!hist) agmv_die("out of host memory");
+		if (agmv_hip_memcpy_async(w->c, hist, w->d_hist, 4u << 19, 1, w->stream) || agmv_hip_stream_sync(w->c, w->stream)) agmv_die("histogram download");
+		w->file = create_with_palette(w->a, w->filename, hist, w->d.quality, w->d.opt, w->refine);
+		free(hist);
+		seq_start(w->s, w->a, w->file, w->d.opt);
+	}
+	w->writes++;
+	while (left) {
+		const unsigned long long before = w->taken;
+		unsigned long freed = agmv_seq_sources_free(w->s);
+		const uint32_t pos = (uint32_t)(w->taken % w->ring);
+		uint32_t nb;
+		if (w->taken - freed >= w->ring) {             /* the ring is full: until the batch that holds its oldest frame has left */
+			w->waits++;
+			freed = agmv_seq_wait_sources_free(w->s, (unsigned long)(w->taken - w->ring + 1));
+		}
+		nb = w->ring - (uint32_t)(w->taken - freed);
+		if (nb > w->ring - pos) nb = w->ring - pos;
+		if (nb > left) nb = left;
+		if (writer_stage(w, at, nb, w->d_ring + (size_t)pos * w->npx) || agmv_hip_stream_sync(w->c, w->stream)) agmv_die("writer staging");
+		w->taken += nb; left -= nb; at += (size_t)nb * w->src_bytes;
+		writer_push(w, before);
+	}
+	return 0;
+}
+
+int AGMV_CloseWriter(AGMV_WRITER* w, u32* frames_written)
+{
+	u32 written;
+	int too_few;
+	if (!w) return 0;
+	too_few = w->taken < (w->pdifs ? (w->heavy ? 2u : 4u) : 1u);
+	written = agmv_seq_close(w->s);
+	if (w->file) {
+		const u32 n = (u32)w->taken;
+		if (!too_few) patch_header(w->file, w->a, written, w->pdifs ? (f32)pdifs_adjusted(w->d.opt, n - 1) / (n + 1) : 1.0f);
+		fclose(w->file);
+		if (too_few) remove(w->filename);
+	}
+	if (frames_written) *frames_written = too_few ? 0 : written;
+	writer_free(w);
+	return too_few ? -2 : 0;
+}
+
+void AGMV_GetWriterStats(const AGMV_WRITER* w, AGMV_WRITER_STATS* stats)
+{
+	if (!stats) return;
+	memset(stats, 0, sizeof(*stats));
+	if (!w) return;
+	stats->analysed = w->analysed; stats->taken = w->taken; stats->writes = w->writes; stats->waits = w->waits; stats->ring_frames = w->ring;
+	agmv_seq_counts(w->s, &stats->batches, &stats->written);
 }
 
 /* ------------------------------------------------------------------------------------------

@@ -215,6 +215,7 @@ typedef struct lzjob { const u8* in; uint32_t n; u8* out; u32 csize; } lzjob;
 
 typedef struct ebatch {
 	unsigned id, n; u32 first_fc;
+	unsigned long src_end;                 /* the sources of this batch lie before source src_end of the clip, counted from its first (submit_batch) */
 	long *srcA, *srcB;                     /* source frame numbers; srcB < 0: plain frame, else PDIFS midpoint of A and B */
 	uint32_t* h_pix;                       /* BMP source, pinned: frame k at [k * per], its second source at [k * per + npx] */
 	unsigned loads_left, lz_left; int loaded, bits_ready;
@@ -248,6 +249,7 @@ struct agmv_seq {
 	unsigned cap, nslots, nworkers; ebatch* slot; eworker* wk; agmv_pool* pool;
 	pthread_mutex_t mu; pthread_cond_t cv;
 	unsigned nsubmitted, next_prep, next_write; int closing;
+	unsigned next_free; unsigned long src_free;           /* a ring source: the batches before next_free have handed over, in order, and read nothing before source src_free any more */
 	ebatch* cur;                           /* batch being described by agmv_seq_push */
 	u32 fc0, frames_written;
 	u8* persist; size_t persist_len;       /* emulation of agmv->bitstream->data for LZ77's one-past-the-end read */
@@ -372,10 +374,13 @@ static void download_rows(eworker* wk, ebatch* b, const uint8_t* d_rows, size_t 
 	if (agmv_hip_stream_sync(wk->ctx, wk->stream)) agmv_die("row download");
 }
 
-/* a device source: where its frame `idx` is */
+/* a device source: where its frame `idx` is -- in a flat clip at its index, in a ring of ring_frames frames at its index modulo the ring's length.
+   The one place that knows the two forms. */
 static const void* src_frame(const agmv_seq* s, long idx)
 {
-	return (const u8*)s->src.d_frames + (size_t)(idx - s->src.first) * agmv_fmt_frame_bytes(s->src.fmt, s->src.src_w, s->src.src_h);
+	size_t k = (size_t)(idx - s->src.first);
+	if (s->src.ring_frames) k %= s->src.ring_frames;
+	return (const u8*)s->src.d_frames + k * agmv_fmt_frame_bytes(s->src.fmt, s->src.src_w, s->src.src_h);
 }
 
 /* The one put: the source of batch b's slot k (which = 1: its second source) into dst as packed XRGB32, as the encoder sees it, on the worker's stream.
@@ -475,6 +480,9 @@ static void eworker_hand_over(eworker* wk, ebatch* b, double t_taken)
 	s->t_gpu += now_s() - t_taken;
 	if (s->plan.lz_dev) s->t_lz += now_s() - t_lz;
 	b->bits_ready = 1;
+	/* the stream is synchronised: nothing reads this batch's sources any more.  Batches hand over in any order, a ring is given back in theirs */
+	while (s->next_free < s->nsubmitted && s->slot[s->next_free % s->nslots].id == s->next_free && s->slot[s->next_free % s->nslots].bits_ready)
+		s->src_free = s->slot[s->next_free++ % s->nslots].src_end;
 	pthread_cond_broadcast(&s->cv);
 	pthread_mutex_unlock(&s->mu);
 }
@@ -535,8 +543,10 @@ static void write_batch(agmv_seq* s, ebatch* b)
 }
 
 /* the calling thread's share: prepare and write finished batches in order.  Returns when batch slot `want` is free
-   (want = the id about to be described) or, with drain, when everything submitted has been written. */
-static void seq_progress(agmv_seq* s, unsigned want, int drain)
+   (UNTIL_SLOT, want = the id about to be described), when everything submitted has been written (UNTIL_DRAINED) or when the
+   batches that read a source before `want` have handed over (UNTIL_FREED, a ring source). */
+enum { UNTIL_SLOT, UNTIL_DRAINED, UNTIL_FREED };
+static void seq_progress(agmv_seq* s, unsigned long want, int until)
 {
 	pthread_mutex_lock(&s->mu);
 	for (;;) {
@@ -561,7 +571,7 @@ static void seq_progress(agmv_seq* s, unsigned want, int drain)
 				continue;
 			}
 		}
-		if (drain ? s->next_write >= s->nsubmitted : want < s->next_write + s->nslots) break;
+		if (until == UNTIL_DRAINED ? s->next_write >= s->nsubmitted : until == UNTIL_SLOT ? want < s->next_write + s->nslots : s->src_free >= want) break;
 		pthread_cond_wait(&s->cv, &s->mu);
 	}
 	pthread_mutex_unlock(&s->mu);
@@ -571,7 +581,7 @@ static void begin_batch(agmv_seq* s)
 {
 	const unsigned id = s->nsubmitted;
 	ebatch* b;
-	seq_progress(s, id, 0);                                /* until the slot of batch id - nslots has been written */
+	seq_progress(s, id, UNTIL_SLOT);                       /* until the slot of batch id - nslots has been written */
 	b = &s->slot[id % s->nslots];
 	b->id = id; b->n = 0; b->loaded = 0; b->bits_ready = 0; b->lz_left = 0;
 	b->first_fc = s->fc0 + (id ? ((s->fc0 & 3u) ? (4u - (s->fc0 & 3u)) + (id - 1) * s->cap : id * s->cap) : 0);
@@ -589,6 +599,7 @@ static void submit_batch(agmv_seq* s)
 	unsigned k, tasks = 0;
 	if (!b || !b->n) return;
 	if (!s->plan.device_src) for (k = 0; k < b->n; k++) tasks += b->srcB[k] < 0 ? 1 : 2;
+	b->src_end = (unsigned long)((b->srcB[b->n - 1] < 0 ? b->srcA[b->n - 1] : b->srcB[b->n - 1]) + 1 - s->src.first);     /* (the schedules push their sources in ascending order) */
 	pthread_mutex_lock(&s->mu);
 	b->loads_left = tasks;
 	if (!tasks) b->loaded = 1;                             /* a device source: nothing to load, the batch is the worker's at once */
@@ -630,7 +641,7 @@ static void eworker_open(agmv_seq* s, unsigned i, int device, const agmv_seq_opt
 	agmv_hip_ctx* c = wk->ctx = agmv_hip_create(device);
 	wk->s = s; wk->idx = i;
 	if (!c) agmv_die("cannot open the GPU");
-	if (agmv_hip_set_palette(c, o->pal, o->pal + 256, o->mode512, NULL) || agmv_hip_sync()) agmv_die("palette upload");
+	if (o->pal && (agmv_hip_set_palette(c, o->pal, o->pal + 256, o->mode512, NULL) || agmv_hip_sync())) agmv_die("palette upload");
 	if (!(wk->stream = agmv_hip_stream_create(c))) agmv_die("device allocation");
 	wk->d_frames = (uint32_t*)on_device(c, s->npx * 4 * s->cap); wk->d_out = (uint8_t*)on_device(c, s->stride * s->cap);
 	wk->d_sizes = (uint32_t*)on_device(c, 4 * (size_t)s->cap); wk->d_ient = (uint16_t*)on_device(c, s->npx * 2);
@@ -702,10 +713,39 @@ agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const agmv_source* src, const agmv_
 	return s;
 }
 
+/* a sequence opened without a palette and a file (opts.pal NULL, file NULL) receives both here, before its first push: the workers exist and wait */
+void agmv_seq_start(agmv_seq* s, FILE* file, const uint32_t* pal, int mode512)
+{
+	unsigned i;
+	for (i = 0; i < s->nworkers; i++)
+		if (agmv_hip_set_palette(s->wk[i].ctx, pal, pal + 256, mode512, NULL) || agmv_hip_sync()) agmv_die("palette upload");
+	s->file = file;
+}
+
+/* a ring source: the sources before this one (counted from the clip's first) are read by no batch any more: their places in the ring are free */
+unsigned long agmv_seq_sources_free(agmv_seq* s)
+{
+	unsigned long v;
+	pthread_mutex_lock(&s->mu);
+	v = s->src_free;
+	pthread_mutex_unlock(&s->mu);
+	return v;
+}
+
+/* ... the same once it has reached `want`, which a submitted batch must cover; the calling thread prepares and writes batches meanwhile */
+unsigned long agmv_seq_wait_sources_free(agmv_seq* s, unsigned long want)
+{
+	seq_progress(s, want, UNTIL_FREED);
+	return agmv_seq_sources_free(s);
+}
+
+void agmv_seq_counts(agmv_seq* s, unsigned* batches, unsigned long long* frames_written) { *batches = s->nsubmitted; *frames_written = s->frames_written; }
+
 /* append one encoded frame: source `a`, or the PDIFS midpoint of sources a and b (b >= 0) */
 void agmv_seq_push(agmv_seq* s, long a, long b)
 {
-	const long first = s->src.first, end = first + (long)s->src.n_frames;
+	const long first = s->src.ring_frames ? s->src.first + (long)agmv_seq_sources_free(s) : s->src.first;    /* a ring holds ring_frames sources from the first that is not free */
+	const long end = first + (long)(s->src.ring_frames ? s->src.ring_frames : s->src.n_frames);
 	if (!s->cur) begin_batch(s);
 	if (b >= 0 && !s->plan.midpoints) agmv_die("internal: midpoint frame on a sequence opened without interpolation");
 	if (s->plan.device_src && (a < first || a >= end || b >= end || (b >= 0 && b < first))) agmv_die("internal: frame outside the device clip");
@@ -721,7 +761,7 @@ u32 agmv_seq_close(agmv_seq* s)
 	s->closing = 1;
 	pthread_cond_broadcast(&s->cv);
 	pthread_mutex_unlock(&s->mu);
-	seq_progress(s, 0, 1);
+	seq_progress(s, 0, UNTIL_DRAINED);
 	TRACE("pipeline: %u frames in %u batches, %.3f s from open to last chunk written; summed over the threads: BMP parse %.3f s, GPU workers "
 	      "(upload + kernels + download) %.3f s, LZ (%s) %.3f s, chunk writes %.3f s\n", (unsigned)s->frames_written, s->nsubmitted, now_s() - s->t_open,
 	      s->t_load, s->t_gpu, s->plan.lz_dev ? "device" : "host", s->t_lz, s->t_write);
@@ -740,6 +780,14 @@ u32 agmv_seq_close(agmv_seq* s)
 	pthread_mutex_destroy(&s->mu); pthread_cond_destroy(&s->cv);
 	free(s);
 	return written;
+}
+
+uint32_t agmv_writer_groups(uint32_t n, int heavy, int closed)
+{
+	const uint32_t step = heavy ? 2u : 4u;
+	(void)closed;
+	if (n < step) return 0;                                    /* (the first group reads `step` sources) */
+	return n < 6 ? 1 : 1 + (n - 6) / step;                     /* group k >= 1 starts at k * step and needs k * step + 5 < n */
 }
 
 /* ------------------------------------------------------------------------------------------

@@ -24,7 +24,9 @@ void agmv_load_source(const char* dir, const char* base, long idx, int scale_w, 
 
 /* where the frames of a sequence encode come from: the numbered BMP files dir/base<idx>.bmp, or (d_frames != NULL) a clip of
    n_frames frames of src_w x src_h pixels in the layout `fmt` (an AGMV_PIXFMT, for NV12 / I420 with the AGMV_YUV_ flags) in the
-   memory of device `device`, its first frame numbered `first` */
+   memory of device `device`, its first frame numbered `first`.  ring_frames != 0 is the ring form of such a clip (a writer session's staging): d_frames holds
+   ring_frames frames, frame idx of the clip lies at (idx - first) % ring_frames, n_frames is not read, and whoever fills the ring waits for
+   agmv_seq_sources_free before it overwrites a frame */
 typedef struct agmv_source {
 	const char *dir, *base;
 	const void* d_frames;
@@ -32,6 +34,7 @@ typedef struct agmv_source {
 	uint32_t src_w, src_h, n_frames;
 	long first;
 	int device;
+	uint32_t ring_frames;
 } agmv_source;
 /* the table of agmv_source_index for such a clip on the device of context c, uploaded on `stream`; *h_index: the host's table, the caller's to free
    behind its next synchronisation of that stream.  NULL on failure. */
@@ -85,6 +88,22 @@ typedef struct agmv_seq_opts {
 agmv_seq* agmv_seq_open(AGMV* a, FILE* file, const agmv_source* src, const agmv_seq_opts* opts);
 void agmv_seq_push(agmv_seq* s, long a, long b);
 u32  agmv_seq_close(agmv_seq* s);
+/* A sequence may be opened before its palette and file exist (opts->pal NULL, file NULL: a writer session allocates everything at its open):
+   agmv_seq_start hands both over before the first push.  A ring source is given back in batch order, when a batch's bitstreams are ready
+   (`bits_ready`: the worker has synchronised its stream behind the batch, so nothing reads its sources any more): agmv_seq_sources_free is the number
+   of sources, counted from the clip's first, that no batch reads any more; agmv_seq_wait_sources_free returns once it is at least `want`, which the
+   batches submitted so far must cover.  agmv_seq_counts: the batches submitted and the frames whose chunks are in the file. */
+void agmv_seq_start(agmv_seq* s, FILE* file, const uint32_t* pal, int mode512);
+unsigned long agmv_seq_sources_free(agmv_seq* s);
+unsigned long agmv_seq_wait_sources_free(agmv_seq* s, unsigned long want);
+void agmv_seq_counts(agmv_seq* s, unsigned* batches, unsigned long long* frames_written);
+
+/* The PDIFS schedule of a clip whose end is not known (a writer session), stated once.  encode_sequence's loop over n frames emits its first group
+   whatever n is (it reads 4 sources for a light opt, 2 for a heavy one: fewer frames are refused) and a later group, starting at 0-based source
+   j = 4k (light) or 2k (heavy), exactly when its `i + 4 >= end_frame` did not break before it: when frame j + 5 exists.  Returns the groups that are
+   decided once n frames have arrived.  Frames that arrive later only add groups, so closing decides nothing more: the sources behind the last decided
+   group are the ones the loop never encodes, and `closed` changes nothing (the test holds both values to the loop). */
+uint32_t agmv_writer_groups(uint32_t n, int heavy, int closed);
 
 void agmv_histogram_frames(agmv_hip_ctx* ctx, const agmv_source* src, u32 start, u32 end, u32 size, int quality,
                            unsigned threads, uint32_t* hist);

@@ -4,6 +4,8 @@ caller's pixel layout are the library's; torch holds the frames.  The frames liv
 default 0).
 Reader (AGMV_OpenReaderDev ... of include/agmv_reader.h) is a file opened once and read in pieces with the decoder's state kept: what
 decode_frames(frames=, crop=) returns chunk by chunk, without the call's fixed cost and without the LZ stage from frame 0 each time.
+Writer (AGMV_OpenWriterDev ... of include/agmv_writer.h) is the encoder's counterpart: a clip analysed and written in pieces, from
+buffers that may be reused, into the file encode_frames writes for the whole of it, with memory bounded by its staging ring.
 clip_quality / file_quality (AGMV_MeasureFramesDev / AGMV_MeasureFileDev) measure a decoded clip, or a file batch by batch, against
 the frames it was made from, in any of the layouts below, and return a Quality: exact integers per frame and channel, and the
 PSNR, block-mean PSNR and mean SSIM formed from them.
@@ -51,7 +53,7 @@ def load_library():
         p = os.path.join(HERE, "libagmv.so")
         if not os.path.exists(p):
             raise HipUnavailable("%s is missing: run `python -m libagmv_amd.build`; the AGMV hot path has no CPU fallback" % p)
-        _lib = abi.bind(abi.bind(C.CDLL(p), abi.AGMV), abi.READER)
+        _lib = abi.bind(abi.bind(abi.bind(C.CDLL(p), abi.AGMV), abi.READER), abi.WRITER)
     return _lib
 
 
@@ -638,6 +640,131 @@ class Reader:
 
     def __del__(self):
         self.close()
+
+
+class Writer:
+    """A clip encoded in pieces into the file encode_frames writes for the whole of it (include/agmv_writer.h, which holds the contract):
+    every frame is handed in twice, first to .analyse(frames), which counts it towards the palette, then to .write(frames), which
+    encodes it; the pieces may have any sizes, may come from one reused buffer, and nothing of them is held after a call returns.
+    height and width are those of the frames handed in; fps, opt, quality, compression, fmt, yuv, full_range, size, scale, mean and
+    std are encode_frames' and are checked the same way (fmt is named, not inferred: there is no tensor to look at yet); schedule is
+    SCHEDULE_FULL or SCHEDULE_PDIFS.  palette_refine, dither and stabilise are set for the open, where the writer reads them, and
+    restored after it.  ring_frames is the staging capacity in frames (None: the library's choice; a request below the minimum is
+    raised to it).  Analysing only a sample is legal: the palette is then the sample's.
+        with Writer(path, 1080, 1920, fmt="nv12") as w:
+            for chunk in source(): w.analyse(chunk)
+            for chunk in source(): w.write(chunk)
+    .close() finishes the file and returns the frames written (a with block closes); .stats() is AGMV_WRITER_STATS as a dict.  A closed
+    writer raises ValueError."""
+
+    def __init__(self, path, height, width, fps=24, opt=3, quality=3, compression=1, schedule=SCHEDULE_FULL, fmt="xrgb32", yuv=None, full_range=False,
+                 size=None, scale="area", mean=None, std=None, palette_refine=None, dither=None, stabilise=None, ring_frames=None):
+        self._h = None
+        for name, v in (("palette_refine", palette_refine), ("dither", dither), ("stabilise", stabilise)):
+            if v is not None and not (_is_int(v) and 1 <= v <= 64):
+                raise ValueError("Writer: %s must be None or an int from 1 to 64, got %r" % (name, v))
+        if not (_is_int(height) and _is_int(width) and height > 0 and width > 0):
+            raise ValueError("Writer: height and width must be positive ints, got %r and %r" % (height, width))
+        if ring_frames is not None and not (_is_int(ring_frames) and ring_frames >= 1):
+            raise ValueError("Writer: ring_frames must be None or an int >= 1, got %r" % (ring_frames,))
+        if schedule not in (SCHEDULE_FULL, SCHEDULE_PDIFS):
+            raise ValueError("Writer: schedule must be SCHEDULE_FULL or SCHEDULE_PDIFS (SCHEDULE_ADAPTIVE compares frames a writer has not seen together), got %r" % (schedule,))
+        target = _scale_target(size, scale)
+        tensor = _tensor_clip(None, fmt, mean, std, "Writer")
+        d = abi.AGMV_WRITER_DESC(src_width=width, src_height=height, frames_per_second=fps, opt=opt, quality=quality, compression=compression,
+                                 schedule=schedule, ring_frames=ring_frames or 0)
+        if tensor is not None:
+            if yuv is not None or full_range or target is not None:
+                raise ValueError("Writer: yuv=, full_range= and size= do not go with a tensor clip (fmt %r)" % (fmt,))
+            d.tensor, d.type, d.mean, d.std = 1, tensor[0], tensor[4], tensor[5]
+        else:
+            v = _fmt_value("Writer", fmt, yuv, full_range)
+            d.fmt, d.yuv_flags = v & 0xFF, v & ~0xFF
+        if target is not None:
+            d.filter, d.height, d.width = target
+        self._fmt, self._yuv, self._full_range, self._mean, self._std, self._tensor = fmt, yuv, full_range, mean, std, tensor
+        self._value, self._hw, self.path = (tensor[0] if tensor is not None else d.fmt | d.yuv_flags), (height, width), path
+        L = load_library()
+        err = C.c_int(0)
+        knobs = ((L.AGMV_SetPaletteRefine, palette_refine), (L.AGMV_SetDither, dither), (L.AGMV_SetStabilise, stabilise))
+        for call, v in knobs:
+            if v is not None:
+                call(v)
+        try:
+            h = L.AGMV_OpenWriterDev(os.fsencode(path), C.byref(d), C.byref(err))
+        finally:
+            for call, v in knobs:
+                if v is not None:
+                    call(0)
+        if not h:
+            raise ValueError("AGMV_OpenWriterDev refused its arguments (%d): frames of %dx%d, fmt %r, size %r (%s), opt %d, schedule %d"
+                             % (err.value, width, height, fmt, size, scale, opt, schedule))
+        self._L, self._h = L, h
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("Writer: the writer is closed")
+        return self._h
+
+    def _frames(self, who, frames):
+        """the number of frames of a piece, checked against the writer's layout and size; the piece must be complete when called"""
+        import torch
+        h = self._handle()
+        if self._tensor is not None:
+            v, n, fh, fw = _tensor_clip(frames, self._fmt, self._mean, self._std, who)[:4]
+        else:
+            v, n, fh, fw = _clip_geometry(frames, self._fmt, self._yuv, self._full_range, who=who)
+        if (v, fh, fw) != (self._value,) + self._hw:
+            raise ValueError("%s: the writer takes frames of %dx%d in fmt %r, got %dx%d" % (who, self._hw[1], self._hw[0], self._fmt, fw, fh))
+        if not (frames.is_cuda and frames.device == torch.device(_device())):
+            raise ValueError("%s: the frames must be on %s, got %s" % (who, _device(), frames.device))
+        torch.cuda.synchronize(frames.device)          # the library works on streams of its own
+        return h, n
+
+    def analyse(self, frames):
+        """pass 1: these frames count towards the palette; refused once a write has frozen it"""
+        h, n = self._frames("Writer.analyse", frames)
+        rc = self._L.AGMV_WriterAnalyseDev(h, frames.data_ptr(), n)
+        if rc:
+            raise ValueError("AGMV_WriterAnalyseDev(%s, %d frames): %s" % (self.path, n, {-6: "the first write has frozen the palette"}.get(rc, "refused (%d)" % rc)))
+
+    def write(self, frames):
+        """pass 2: these frames are the next of the clip; returns once they are in the writer's staging"""
+        h, n = self._frames("Writer.write", frames)
+        rc = self._L.AGMV_WriterWriteDev(h, frames.data_ptr(), n)
+        if rc:
+            raise ValueError("AGMV_WriterWriteDev(%s, %d frames): %s" % (self.path, n, {-6: "nothing has been analysed: there is no palette"}.get(rc, "refused (%d)" % rc)))
+
+    def stats(self):
+        st = abi.AGMV_WRITER_STATS()
+        self._L.AGMV_GetWriterStats(self._handle(), C.byref(st))
+        return {k: int(getattr(st, k)) for k, _ in abi.AGMV_WRITER_STATS._fields_}
+
+    def close(self):
+        """finishes the file and returns the frames written; a clip shorter than the schedule's first group (AGMV_CloseWriter's -2) leaves
+        no file and raises ValueError.  A second close returns None."""
+        if self._h is None:
+            return None
+        h, self._h = self._h, None
+        written = C.c_ulong(0)
+        rc = self._L.AGMV_CloseWriter(h, C.byref(written))
+        if rc:
+            raise ValueError("AGMV_CloseWriter(%s) refused the clip (%d): fewer frames were written than the schedule's first group reads; no file is left" % (self.path, rc))
+        return int(written.value)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, *exc):
+        if exc_type is None:
+            self.close()
+            return
+        with contextlib.suppress(ValueError):          # (the block's own exception is the one to report)
+            self.close()
+
+    def __del__(self):
+        with contextlib.suppress(Exception):
+            self.close()
 
 
 def decode_audio(path, fmt="s16", cap_samples=None):
