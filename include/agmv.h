@@ -722,6 +722,52 @@ int AGMV_EncodeViewDev(const char* filename, const void* d_frames, AGMV_PIXFMT f
                        AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule);
 void AGMV_GetEncodeViewStats(AGMV_ENCODE_VIEW_STATS* out);
 
+/* A view of a clip encoded at another frame rate: 60 -> 24, 30 -> 24, 25 -> 15, 50 -> 12, with an exact box filter in time, where
+   the view's step can only drop frames and only at integer ratios.  Integers only; div is the quotient of non-negative integers.
+   Let V be the XRGB32 clip of the view exactly as AGMV_EncodeViewDev defines it above, nv its length (view == NULL: the whole
+   clip).  A rate src : dst reads "src frames of V become dst frames of the result"; both are divided by their gcd first, giving
+   sn : dn, which must both be <= 65535.  The result R has m = (nv * dn) div sn frames (64-bit): the target intervals that lie
+   entirely inside V.
+     AGMV_TIME_AREA     needs dn <= sn.  Frame k of V occupies [k * dn, (k + 1) * dn), frame j of R occupies [j * sn, (j + 1) * sn);
+                        wt(j, k) is the length of their overlap, 0 .. dn, and the wt of one j sum to sn.  Per channel and pixel
+                          R[j] = (sum over k of wt(j, k) * V[k] + sn div 2) div sn
+                        255 * 65535 + 32767 < 2^32, so every sum is exact in 32-bit unsigned arithmetic.  The channels are averaged
+                        in RGB, after the layout's reading rule, never in YUV (as for AGMV_SCALE_AREA).
+     AGMV_TIME_NEAREST  any ratio, duplication (dn > sn) included: R[j] = V[((2j + 1) * sn) div (2 * dn)], the frame under the
+                        target interval's centre.
+   Bits 24 .. 31 of every pixel of R are 0, under either filter.  What follows from the rule: 1 : 1 is the identity; k : 1 AREA is the
+   mean of each group of k frames, rounded half up; k : 1 NEAREST is frame j * k + k div 2; under AREA a frame of V has weight in
+   at most two frames of R, a pixel that does not change over the taps keeps its value, and under either filter every output lies
+   between the smallest and the largest of its taps.
+   AGMV_EncodeViewRateDev writes, byte for byte, the file AGMV_EncodeFramesDev writes for R when no target is given
+   (width == height == 0), and with a target the file AGMV_EncodeFramesScaledDev writes for R as an XRGB32 source with that target
+   and filter.  The palette, the schedule's decisions (AGMV_SCHEDULE_ADAPTIVE's skipping included), the PDIFS midpoints, the header
+   and the chunks are those of R; frames_per_second is written as given; the dither, the stabilisation, the palette refinement and a
+   pending AGMV_SetAudioDev track apply as for every other AGMV_EncodeFrames*Dev.  rate == NULL, or a rate that reduces to 1 : 1
+   (its filter must still be known), is AGMV_EncodeViewDev, launch for launch and byte for byte.
+   Returns 0, or a negative value: the refusals of AGMV_EncodeViewDev, in its order, all before a device is opened and before a
+   file is created, with these additions:
+     -1  also: rate->src or rate->dst zero; an unknown time filter; a reduced src or dst above 65535; AGMV_TIME_AREA with dst > src
+     -3  also: for a rate other than 1 : 1 an NV12 / I420 source of odd width or height, consecutive full frames included (nothing
+         is encoded in place then)
+     -2  is judged on m, not on nv: an m of 0 is -2
+   How it runs.  Without a target R is materialised once, 4 * window width * window height * m bytes, with one launch
+   (agmv_hip_time_frames_async of include/agmv_hip_time.h), and takes the path of AGMV_EncodeFramesDev.  With a target R exists one
+   staging batch at a time, of the size AGMV_EncodeViewDev gives its batches of V (AGMV_VIEW_STAGE_FRAMES still forces it): the
+   same entry point writes the batch, the box filter / the nearest gather read it as an XRGB32 source, and every frame of D is a
+   function of its own frame of R.  The source is read in its own layout and nothing of its size is allocated.
+   AGMV_GetEncodeRateStats reports the last AGMV_EncodeViewRateDev of this process: frames_in = nv, frames_out = m, frame_reads =
+   the sum over j of the taps with a weight above 0 (under AREA at most nv + m - 1), counted on the host.  All zero behind a call
+   that returned a negative value.  AGMV_GetEncodeViewStats reports the same call too, with frames = m.
+   The writer sessions of include/agmv_writer.h take no rate: a group of taps may straddle two pieces. */
+typedef enum AGMV_TIME { AGMV_TIME_NEAREST = 1, AGMV_TIME_AREA = 2 } AGMV_TIME;
+typedef struct AGMV_RATE { unsigned src, dst, filter; } AGMV_RATE;
+typedef struct AGMV_ENCODE_RATE_STATS { unsigned frames_in, frames_out; unsigned long long frame_reads; } AGMV_ENCODE_RATE_STATS;
+int AGMV_EncodeViewRateDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height,
+                           const AGMV_VIEW* view, const AGMV_RATE* rate, u32 width, u32 height, AGMV_SCALE filter, u32 frames_per_second,
+                           AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule);
+void AGMV_GetEncodeRateStats(AGMV_ENCODE_RATE_STATS* out);
+
 /* Audio tracks from and to GPU memory.  An AGMV_PCMFMT names the layout of PCM in device memory:
      AGMV_PCM_S16   [samples][channels] 16-bit words, bits unchanged (int16 WAV samples as they are); for 16-bit tracks
      AGMV_PCM_U8    [samples][channels] unsigned bytes; for 8-bit tracks; a copy

@@ -60,7 +60,8 @@
  *
  * 7. No audio track: a writer writes none, and a pending AGMV_SetAudioDev track is neither consumed nor cleared (a PDIFS file
  *    carries an AGAC chunk header behind every frame chunk; it is written empty, as the one-shot call writes it without a track).
- *    Crop windows and frame strides (AGMV_EncodeViewDev) are out of scope.
+ *    Crop windows and frame strides (AGMV_EncodeViewDev) are out of scope.  So is another frame rate (AGMV_EncodeViewRateDev): the
+ *    taps of one output frame may straddle two write pieces, and a writer keeps no frames between its calls.
  *
  * AGMV_WRITER_STATS, all since the open: frames analysed, frames taken by writes, frames whose chunks are in the file so far,
  * write calls that ran (n > 0), batches handed to the workers, waits for ring space, and the ring's length.  Writers are

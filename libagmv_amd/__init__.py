@@ -19,8 +19,8 @@ There is no CPU fallback anywhere in this package: without the built HIP library
 without a GPU, the hot-path calls raise.
 """
 from .hip import PCMFMT, PIXFMT, TENSORFMT, YUVFMT, AgmvHip, HipUnavailable, lib_path, load_library  # noqa: F401
-from .seq import DECODE_SCALE, SCALE, SCHEDULE_ADAPTIVE, SCHEDULE_FULL, SCHEDULE_PDIFS, Quality, Reader, Writer, clip_quality, deblock_stats, decode_audio, decode_frames, encode_frames, encode_view_stats, file_quality, fit_window, stabilise_stats  # noqa: F401
+from .seq import DECODE_SCALE, SCALE, SCHEDULE_ADAPTIVE, SCHEDULE_FULL, SCHEDULE_PDIFS, Quality, Reader, Writer, clip_quality, deblock_stats, decode_audio, decode_frames, encode_frames, encode_rate_stats, encode_view_stats, file_quality, fit_window, stabilise_stats  # noqa: F401
 
 __all__ = ["AgmvHip", "HipUnavailable", "lib_path", "load_library", "encode_frames", "decode_frames", "Reader", "Writer", "decode_audio",
-           "clip_quality", "file_quality", "Quality", "stabilise_stats", "deblock_stats", "encode_view_stats", "fit_window",
+           "clip_quality", "file_quality", "Quality", "stabilise_stats", "deblock_stats", "encode_view_stats", "encode_rate_stats", "fit_window",
            "SCHEDULE_FULL", "SCHEDULE_PDIFS", "SCHEDULE_ADAPTIVE", "PIXFMT", "YUVFMT", "PCMFMT", "TENSORFMT", "SCALE", "DECODE_SCALE"]

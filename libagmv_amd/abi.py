@@ -1,6 +1,6 @@
 """The public C signatures, stated once: the structures of include/agmv.h that Python passes, every function of
 include/agmv_hip.h (HIP), of include/agmv_hip_view.h (HIP_VIEW), of include/agmv_hip_view_source.h (HIP_VIEW_SOURCE), of
-include/agmv_hip_stabilise.h (HIP_STABILISE) and of include/agmv_hip_deblock.h (HIP_DEBLOCK), every function of include/agmv.h that Python calls on libagmv.so (AGMV)
+include/agmv_hip_stabilise.h (HIP_STABILISE), of include/agmv_hip_deblock.h (HIP_DEBLOCK) and of include/agmv_hip_time.h (HIP_TIME), every function of include/agmv.h that Python calls on libagmv.so (AGMV)
 and every function of include/agmv_reader.h and include/agmv_writer.h, which the same library exports (READER, WRITER), as
 name -> (restype, (argtypes...)).  bind() sets them on a loaded library.  tests/test_abi.py checks both tables and the
 structures against the headers.  ctypes only, and no library is loaded here: the test children import this module the
@@ -36,6 +36,14 @@ class AGMV_VIEW_STATS(Structure):
 
 class AGMV_ENCODE_VIEW_STATS(Structure):
     _fields_ = [("frames", c_uint), ("clip_bytes", c_ulonglong), ("staging_bytes", c_ulonglong)]
+
+
+class AGMV_RATE(Structure):
+    _fields_ = [("src", c_uint), ("dst", c_uint), ("filter", c_uint)]
+
+
+class AGMV_ENCODE_RATE_STATS(Structure):
+    _fields_ = [("frames_in", c_uint), ("frames_out", c_uint), ("frame_reads", c_ulonglong)]
 
 
 class AGMV_STABILISE_STATS(Structure):
@@ -77,6 +85,7 @@ INFO_P, QUALITY_P, ENTRY_P = POINTER(AGMV_INFO), POINTER(AGMV_FRAME_QUALITY), PO
 VIEW_P, VIEW_STATS_P, STABILISE_STATS_P = POINTER(AGMV_VIEW), POINTER(AGMV_VIEW_STATS), POINTER(AGMV_STABILISE_STATS)
 DEBLOCK_STATS_P = POINTER(AGMV_DEBLOCK_STATS)
 ENCODE_VIEW_STATS_P = POINTER(AGMV_ENCODE_VIEW_STATS)
+RATE_P, ENCODE_RATE_STATS_P = POINTER(AGMV_RATE), POINTER(AGMV_ENCODE_RATE_STATS)
 
 HIP = {
     "agmv_hip_max_usize": (sz, (u32, u32, c_int)),
@@ -187,6 +196,11 @@ HIP_DEBLOCK = {
     "agmv_hip_deblock_frames_async": (c_int, (vp, u32, vp, u32, u32, u32, vp, vp, vp)),
 }
 
+# include/agmv_hip_time.h, exported by the same library
+HIP_TIME = {
+    "agmv_hip_time_frames_async": (c_int, (vp, c_int, vp, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, c_int, u32, u32, vp, vp)),
+}
+
 _SEQ = (c_char_p, c_char_p, c_char_p, c_ubyte, ul, ul, ul, ul, ul, c_int, c_int, c_int)     # the three BMP drivers, behind `agmv`
 _CLIP = (ul, ul, ul, ul, c_int, c_int, c_int, c_int)                 # frames, width, height, fps, opt, quality, compression, schedule
 
@@ -281,6 +295,8 @@ AGMV = {
     "AGMV_GetViewStats": (None, (VIEW_STATS_P,)),
     "AGMV_EncodeViewDev": (c_int, (c_char_p, vp, c_int, ul, ul, ul, VIEW_P, ul, ul, c_int, ul, c_int, c_int, c_int, c_int)),
     "AGMV_GetEncodeViewStats": (None, (ENCODE_VIEW_STATS_P,)),
+    "AGMV_EncodeViewRateDev": (c_int, (c_char_p, vp, c_int, ul, ul, ul, VIEW_P, RATE_P, ul, ul, c_int, ul, c_int, c_int, c_int, c_int)),
+    "AGMV_GetEncodeRateStats": (None, (ENCODE_RATE_STATS_P,)),
     "AGMV_SetAudioDev": (c_int, (vp, c_int, ul, ul, c_ushort)),
     "AGMV_DecodeAudioDev": (c_int, (c_char_p, vp, c_int, ul, INFO_P)),
     "AGMV_MeasureFramesDev": (c_int, (vp, vp, c_int, ul, ul, ul, QUALITY_P)),

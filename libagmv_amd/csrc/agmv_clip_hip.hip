@@ -8,6 +8,7 @@
 //   k_gather*                 the nearest scale as a table look-up; gather_frames is the body of the XRGB32 and byte-layout forms
 //   k_view                    every step-th frame of an XRGB32 clip and a window of each, copied into a packed clip
 //   k_view_src                the same of a clip in any other layout, converted on the way: the encoder's view of its source
+//   k_time                    such a view at another frame rate: the exact box filter in time, or the frame under the centre
 //   k_stabilise               opt-in: still blocks of the P-frames of a batch replaced by their GOP's I-frame's, in place
 //   k_deblock                 opt-in: the block edges of a decoded clip smoothed, one lane per 4x4 cell around a block corner
 //   k_pix_* / k_yuv_*         the byte layouts and NV12 / I420 to and from XRGB32
@@ -29,6 +30,7 @@
 #include "agmv_hip_impl.h"
 #include "../../include/agmv_hip_deblock.h"
 #include "../../include/agmv_hip_stabilise.h"
+#include "../../include/agmv_hip_time.h"
 #include "../../include/agmv_hip_view.h"
 #include "../../include/agmv_hip_view_source.h"
 
@@ -1354,6 +1356,128 @@ template <int FMT> __global__ __launch_bounds__(256) void k_view_src(ViewSrcArgs
 	}
 }
 
+// ---- a view of a clip at another frame rate (agmv_hip_time_frames_async of include/agmv_hip_time.h; AGMV_RATE of include/agmv.h has the rule) ----
+// dst[jj] = frame j = j0 + jj of R, the view V (k_view_src's dst) resampled in time sn : dn.  k_view_src's ownership: a lane owns 16
+// consecutive pixels of one output row, blockIdx.x runs over the groups of a window's rows, blockIdx.y strides over the output
+// frames.  For YUV a lane owns a patch of 8 x 2: the 96 sums of 16 x 2 pixels beside two taps' bytes and the conversion's
+// temporaries took every register a lane can have (256 VGPRs and 86 AGPRs, one wave per SIMD), the 48 of 8 x 2 leave room for three.
+// Per output frame the taps k0 .. k1 of V and their weights are uniform over the workgroup: AREA
+// k0 = (j sn) div dn .. k1 = ((j + 1) sn - 1) div dn with the overlap of [k dn, (k + 1) dn) and [j sn, (j + 1) sn) as weight, NEAREST
+// the one tap ((2j + 1) sn) div (2 dn) at weight sn -- the same loop.  Per tap a lane whose source pixels lie inside their row on
+// a 16-byte boundary (YUV: 8-byte; ld says the frames allow it; the lane checks its own offset, which is the same in every frame)
+// reads them through pf_load16, or as the halves of yuv_load_patch's vectors, non-temporal: a frame has weight in at most two
+// outputs.  The next tap's loads are issued before the current tap is accumulated.  Every other lane goes pixel by pixel through
+// sc_read.  Three 32-bit sums per pixel take weight * channel in RGB, after the layout's reading rule: 255 * sn + sn / 2 < 2^32 for
+// sn <= 65535.  Then (sum + sn / 2) / sn by the uniform divisor, packed, bits 24 .. 31 zero, stored as k_view_src stores.
+struct TimeArgs {
+	const uint8_t* src;
+	uint32_t* dst;
+	size_t frame_bytes;                                            // of a source frame
+	uint32_t sw, sh, first, step, x, y, w, h, gpr, sn, dn, j0, count;
+	int nearest, ld, st;
+	yuv_rd m;
+};
+
+struct yuv_half { pf_u32x2 y0, y1, c; };                           // a patch of 8 x 2 as it lies in memory; c: 4 pairs U,V (NV12), 4 U then 4 V (I420)
+
+// a lane's pixels of one tap as they lie in memory: 16 of a row (XRGB32 lies as RGBA32 does, four words to a vector), YUV 8 x 2
+template <int FMT> struct time_raw {
+	static constexpr bool YUV = FMT >= PF_NV12;
+	std::conditional_t<YUV, yuv_half, pf_raw<FMT == PF_XRGB32 ? PF_RGBA32 : FMT>> v;
+
+	// YUV: sx a multiple of 8, sy even, sw a multiple of 8 and the frame 16-byte aligned; else the conditions of pf_load16
+	__device__ __forceinline__ void load(const uint8_t* __restrict__ fr, uint32_t sw, uint32_t sh, uint32_t sx, uint32_t sy, bool row1)
+	{
+		if constexpr (YUV) {
+			const size_t cw = sw >> 1, ch = (sh + 1) >> 1, py = sy >> 1;
+			const uint8_t* c = fr + (size_t)sw * sh;
+			v.y0 = __builtin_nontemporal_load(reinterpret_cast<const pf_u32x2*>(fr + (size_t)sy * sw + sx));
+			v.y1 = 0;
+			if (row1) v.y1 = __builtin_nontemporal_load(reinterpret_cast<const pf_u32x2*>(fr + ((size_t)sy + 1) * sw + sx));
+			if constexpr (FMT == PF_NV12) v.c = __builtin_nontemporal_load(reinterpret_cast<const pf_u32x2*>(c + py * sw + sx));
+			else {
+				v.c[0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(c + py * cw + (sx >> 1)));
+				v.c[1] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(c + cw * ch + py * cw + (sx >> 1)));
+			}
+		} else v = pf_load16<FMT == PF_XRGB32 ? PF_RGBA32 : FMT, true>(fr, (size_t)sw * sh, (size_t)sy * sw + sx);
+	}
+
+	// pixel i of row rr (constants once the caller's loops are unrolled) as 0x00RRGGBB
+	__device__ __forceinline__ uint32_t pixel(int rr, int i, const yuv_rd& m) const
+	{
+		if constexpr (YUV) {
+			const int j = i >> 1;                                  // the chroma sample
+			const uint32_t u = FMT == PF_NV12 ? v.c[j >> 1] >> (16 * (j & 1)) : v.c[0] >> (8 * j), w = FMT == PF_NV12 ? v.c[j >> 1] >> (16 * (j & 1) + 8) : v.c[1] >> (8 * j);
+			return yuv_pixel(m, ((rr ? v.y1 : v.y0)[i >> 2] >> (8 * (i & 3))) & 0xff, yuv_chroma(m, u & 0xff, w & 0xff));
+		} else if constexpr (FMT == PF_XRGB32) return v.v[i >> 2][i & 3] & 0xffffffu;
+		else return pf_pixel<FMT>(v, i);
+	}
+};
+
+template <int FMT> __global__ __launch_bounds__(256) void k_time(TimeArgs A)
+{
+	constexpr bool YUV = FMT >= PF_NV12;
+	constexpr int ROWS = YUV ? 2 : 1, PX = YUV ? 8 : 16;           // a lane's pixels: PX of each of ROWS rows
+	const size_t item = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (item >= (size_t)(YUV ? (A.h + 1) >> 1 : A.h) * A.gpr) return;
+	const uint32_t ri = (uint32_t)(item / A.gpr), c0 = (uint32_t)(item - (size_t)ri * A.gpr) * PX, r = YUV ? 2 * ri : ri;
+	const uint32_t live = A.w - c0 < (uint32_t)PX ? A.w - c0 : (uint32_t)PX, sx = A.x + c0, sy = A.y + r;
+	const bool row1 = YUV && r + 1 < A.h;
+	const size_t p = (size_t)sy * A.sw + sx;                       // YUV: ld holds the conditions on x, y and sw
+	const bool ld = A.ld && sx + PX <= A.sw && (YUV || (p & (FMT == PF_XRGB32 || FMT == PF_RGBA32 ? 3 : 15)) == 0);
+	const unsigned long long sn = A.sn, dn = A.dn;
+	for (uint32_t jj = blockIdx.y; jj < A.count; jj += gridDim.y) {
+		const unsigned long long j = (unsigned long long)A.j0 + jj, lo = j * sn, hi = lo + sn;
+		const uint32_t k0 = (uint32_t)(A.nearest ? (lo + hi) / (2 * dn) : lo / dn), k1 = A.nearest ? k0 : (uint32_t)((hi - 1) / dn);
+		uint32_t acc[ROWS][PX][3];
+#pragma unroll
+		for (int rr = 0; rr < ROWS; rr++)
+#pragma unroll
+			for (int i = 0; i < PX; i++) acc[rr][i][0] = acc[rr][i][1] = acc[rr][i][2] = 0;
+		time_raw<FMT> cur;
+		if (ld) cur.load(A.src + ((size_t)A.first + (size_t)k0 * A.step) * A.frame_bytes, A.sw, A.sh, sx, sy, row1);
+		for (uint32_t k = k0; k <= k1; k++) {
+			const unsigned long long a = (unsigned long long)k * dn;
+			const uint32_t wt = A.nearest ? A.sn : (uint32_t)(min(a + dn, hi) - max(a, lo));
+			if (ld) {
+				time_raw<FMT> nxt = cur;
+				if (k < k1) nxt.load(A.src + ((size_t)A.first + (size_t)(k + 1) * A.step) * A.frame_bytes, A.sw, A.sh, sx, sy, row1);
+#pragma unroll
+				for (int rr = 0; rr < ROWS; rr++)
+#pragma unroll
+					for (int i = 0; i < PX; i++) {
+						const uint32_t c = cur.pixel(rr, i, A.m);
+						acc[rr][i][0] += wt * (c >> 16); acc[rr][i][1] += wt * ((c >> 8) & 0xffu); acc[rr][i][2] += wt * (c & 0xffu);
+					}
+				cur = nxt;
+			} else {
+				const uint8_t* fr = A.src + ((size_t)A.first + (size_t)k * A.step) * A.frame_bytes;
+#pragma unroll
+				for (int rr = 0; rr < ROWS; rr++)
+#pragma unroll
+					for (int i = 0; i < PX; i++) if ((uint32_t)i < live && (rr == 0 || row1)) {
+						const uint32_t c = sc_read<FMT>(fr, A.sw, A.sh, sx + i, sy + rr, A.m);
+						acc[rr][i][0] += wt * (c >> 16); acc[rr][i][1] += wt * ((c >> 8) & 0xffu); acc[rr][i][2] += wt * (c & 0xffu);
+					}
+			}
+		}
+		const uint32_t div = A.sn, half = div / 2;
+		uint32_t* d = A.dst + ((size_t)jj * A.h + r) * A.w + c0;
+#pragma unroll
+		for (int rr = 0; rr < ROWS; rr++) {
+			if (rr && !row1) break;
+#pragma unroll
+			for (int q = 0; q < PX / 4; q++) {
+				if (4u * q >= live) break;
+				pf_u32x4 o;
+#pragma unroll
+				for (int i = 0; i < 4; i++) o[i] = (acc[rr][4 * q + i][0] + half) / div << 16 | (acc[rr][4 * q + i][1] + half) / div << 8 | (acc[rr][4 * q + i][2] + half) / div;
+				view_src_store4(d + (size_t)rr * A.w, q, o, live, A.st);
+			}
+		}
+	}
+}
+
 // ---- a decoded XRGB32 clip written at a target size in any of the seven layouts (AGMV_SCALE_NEAREST / _BILINEAR of include/agmv.h) ----
 // 1080p XRGB32 is 8.3 MB out per frame from 0.3 MB in, and the source batch stays in L2, so the taps are plain gathers.  A lane
 // forms 16 consecutive target pixels of a row (YUV: 16 x 2, the patch of k_yuv_from_xrgb) in registers; where the target's rows of
@@ -2053,6 +2177,47 @@ extern "C" int agmv_hip_view_source_async(agmv_hip_ctx* c, int fmt, const void* 
 	if (items > 0xFFFFFFFFull) return agmv_hip_err("agmv_hip: window too large for one launch");
 	const dim3 grid((unsigned)((items + 255) / 256), count < VIEW_GRID_FRAMES ? count : VIEW_GRID_FRAMES);
 	clip_dispatch<PF_BYTES | PF_YUV>(fmt, [&](auto F) { hipLaunchKernelGGL(k_view_src<decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, A); });
+	CK(hipGetLastError());
+	return 0;
+}
+
+static uint32_t time_gcd(uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; }
+
+extern "C" int agmv_hip_time_frames_async(agmv_hip_ctx* c, int fmt, const void* d_src, uint32_t src_w, uint32_t src_h, uint32_t n_frames, uint32_t first, uint32_t step,
+                                          uint32_t view_len, uint32_t x, uint32_t y, uint32_t win_w, uint32_t win_h, uint32_t rate_src, uint32_t rate_dst, int time_filter,
+                                          uint32_t j0, uint32_t count, uint32_t* d_dst, void* stream)
+{
+	if (agmv_hip_enter(c)) return -1;
+	if (!d_src || !d_dst || src_w == 0 || src_h == 0 || win_w == 0 || win_h == 0 || step == 0) return agmv_hip_err("agmv_hip: time needs clips, sizes and a step that are not zero");
+	if (x > src_w || win_w > src_w - x || y > src_h || win_h > src_h - y)
+		return agmv_hip_err("agmv_hip: the window %u x %u at (%u, %u) does not lie inside the %u x %u frame", win_w, win_h, x, y, src_w, src_h);
+	const int yuv = yuv_base(fmt);
+	if (yuv ? bad_yuv(fmt, src_w, src_h) : bad_pixfmt(fmt)) return -1;
+	if (yuv && ((src_w | src_h) & 1)) return agmv_hip_err("agmv_hip: a view of a YUV 4:2:0 source needs an even frame size, got %u x %u", src_w, src_h);
+	if (time_filter != 1 && time_filter != 2) return agmv_hip_err("agmv_hip: unknown time filter %d", time_filter);
+	if (rate_src == 0 || rate_dst == 0 || rate_src > 65535u || rate_dst > 65535u || time_gcd(rate_src, rate_dst) != 1)
+		return agmv_hip_err("agmv_hip: the rate %u : %u is not a reduced pair of 1 .. 65535", rate_src, rate_dst);
+	if (time_filter == 2 && rate_dst > rate_src) return agmv_hip_err("agmv_hip: the box filter in time does not raise the rate (%u : %u)", rate_src, rate_dst);
+	const unsigned long long m = (unsigned long long)view_len * rate_dst / rate_src;
+	if ((unsigned long long)j0 + count > m) return agmv_hip_err("agmv_hip: frames %u .. %llu of a result of %llu", j0, (unsigned long long)j0 + count, m);
+	if (view_len && (unsigned long long)first + (unsigned long long)(view_len - 1) * step >= n_frames)
+		return agmv_hip_err("agmv_hip: a tap of the view (first %u, step %u, %u frames) lies outside the clip of %u frames", first, step, view_len, n_frames);
+	if (count == 0) return 0;
+	TimeArgs A;
+	A.src = (const uint8_t*)d_src; A.dst = d_dst; A.frame_bytes = clip_frame_bytes(fmt, src_w, src_h);
+	A.sw = src_w; A.sh = src_h; A.first = first; A.step = step; A.x = x; A.y = y; A.w = win_w; A.h = win_h;
+	A.gpr = yuv ? win_w / 8 + ((win_w & 7) != 0) : win_w / 16 + ((win_w & 15) != 0);      // groups of 16 (YUV: 8) pixels per output row
+	A.sn = rate_src; A.dn = rate_dst; A.j0 = j0; A.count = count; A.nearest = time_filter == 1;
+	A.m = YUV_RD[(fmt >> 8) & 3];
+	// every frame (and plane) on a 16-byte boundary; YUV: and the window's patches of 8 x 2 on 8-byte boundaries of rows that share
+	// a chroma row (I420: its chroma on 4-byte ones).  The byte layouts leave the group's own offset to the lane.
+	A.ld = ((uintptr_t)d_src & 15) == 0 && (A.frame_bytes & 15) == 0 &&
+	       (yuv ? ((x | src_w) & 7) == 0 && !(y & 1) : fmt != PF_RGB8P || ((size_t)src_w * src_h & 15) == 0);
+	A.st = (win_w & 3) == 0 && ((uintptr_t)d_dst & 15) == 0;
+	const size_t items = (size_t)(yuv ? (win_h + 1) / 2 : win_h) * A.gpr;
+	if (items > 0xFFFFFFFFull) return agmv_hip_err("agmv_hip: window too large for one launch");
+	const dim3 grid((unsigned)((items + 255) / 256), count < VIEW_GRID_FRAMES ? count : VIEW_GRID_FRAMES);
+	clip_dispatch<PF_BIT(PF_XRGB32) | PF_BYTES | PF_YUV>(fmt, [&](auto F) { hipLaunchKernelGGL(k_time<decltype(F)::value>, grid, dim3(256), 0, (hipStream_t)stream, A); });
 	CK(hipGetLastError());
 	return 0;
 }

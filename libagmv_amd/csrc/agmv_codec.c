@@ -878,7 +878,8 @@ int AGMV_EncodeFramesDev(const char* filename, const unsigned* d_frames, u32 num
    similarity and the encode would each read it -- and AGMV_EncodeFramesDev runs on that.  Nothing of the source's size or layout is
    allocated.  How the clip is filled: the box filter, a gather through agmv_scale_index, agmv_hip_tensor_to_xrgb_async, or the
    windows of selected frames by agmv_hip_view_source_async.  FILL_AREA / FILL_NEAREST with a view scale those windows: they exist one
-   staging batch at a time, which the scaler reads as an XRGB32 source. */
+   staging batch at a time, which the scaler reads as an XRGB32 source.  A view at another frame rate is the same with R in the place
+   of V: agmv_hip_time_frames_async writes what agmv_hip_view_source_async would. */
 static AGMV_ENCODE_VIEW_STATS g_encode_view_stats;  /* of the last AGMV_EncodeViewDev */
 
 void AGMV_GetEncodeViewStats(AGMV_ENCODE_VIEW_STATS* out) { if (out) *out = g_encode_view_stats; }
@@ -891,7 +892,19 @@ typedef struct clip_fill {
 	const float* ab;                       /* FILL_TENSOR: a[3] then b[3] of the reading rule */
 	const AGMV_VIEW* view;                 /* FILL_VIEW, or a scale of a view: first, step and the window, resolved; clip frame j is source frame first + j * step */
 	AGMV_ENCODE_VIEW_STATS* stats;         /* where a view reports the clip it materialised; else NULL */
+	const AGMV_RATE* rate;                 /* a view at another frame rate (reduced, not 1 : 1): the clip is R, made by agmv_hip_time_frames_async; else NULL */
+	uint32_t view_len, src_frames;         /* with a rate: the length of V and the frames of the source clip */
 } clip_fill;
+
+/* frames j0 .. j0 + n - 1 of a view (with a rate: of R) as packed XRGB32 at d_dst: one launch */
+static int fill_view_frames(agmv_hip_ctx* c, const clip_fill* f, uint32_t j0, uint32_t n, uint32_t* d_dst, void* stream)
+{
+	const AGMV_VIEW* v = f->view;
+	if (f->rate)
+		return agmv_hip_time_frames_async(c, f->fmt, f->d_src, f->src_w, f->src_h, f->src_frames, v->first, v->step, f->view_len, v->x, v->y, v->width, v->height,
+		                                  f->rate->src, f->rate->dst, (int)f->rate->filter, j0, n, d_dst, stream);
+	return agmv_hip_view_source_async(c, f->fmt, f->d_src, f->src_w, f->src_h, v->first + j0 * v->step, v->step, n, v->x, v->y, v->width, v->height, d_dst, stream);
+}
 
 /* A staging batch of a scaled view: as many windows as fit 256 MiB -- the size of the memory-side cache, taken as a bound
    on memory, not as a tuned value -- and at least one; AGMV_VIEW_STAGE_FRAMES=n (read per call, a test aid) forces n. */
@@ -914,8 +927,7 @@ static int fill_scaled_view(agmv_hip_ctx* c, const clip_fill* f, uint32_t n, uin
 	uint32_t j, nb;
 	for (j = 0; j < n; j += nb) {
 		nb = n - j < stage ? n - j : stage;
-		if (agmv_hip_view_source_async(c, f->fmt, f->d_src, f->src_w, f->src_h, v->first + j * v->step, v->step, nb, v->x, v->y, v->width, v->height, d_stage, stream))
-			return -1;
+		if (fill_view_frames(c, f, j, nb, d_stage, stream)) return -1;
 		if (f->how == FILL_AREA ? agmv_hip_scale_area_dev(c, AGMV_PIXFMT_XRGB32, d_stage, v->width, v->height, nb, w, h, d_clip + j * npx, stream)
 		                        : agmv_fmt_gather(c, AGMV_PIXFMT_XRGB32, v->width, v->height, d_stage, nb, d_index, npx, d_clip + j * npx, stream))
 			return -1;
@@ -952,7 +964,7 @@ static int encode_materialised(const char* filename, const clip_fill* f, u32 num
 	if (f->how == FILL_NEAREST && agmv_hip_memcpy_async(c, d_index, index, 4 * npx, 0, stream)) failed = -1;
 	else if (tensor) failed = agmv_hip_tensor_to_xrgb_async(c, f->fmt, f->d_src, npx, n, f->ab, d_clip, stream);
 	else if (f->how == FILL_VIEW)
-		failed = agmv_hip_view_source_async(c, f->fmt, f->d_src, f->src_w, f->src_h, f->view->first, f->view->step, n, f->view->x, f->view->y, w, h, d_clip, stream);
+		failed = fill_view_frames(c, f, 0, n, d_clip, stream);
 	else if (staged) failed = fill_scaled_view(c, f, n, w, h, stage, d_stage, d_index, d_clip, stream);
 	else if (f->how == FILL_AREA) failed = agmv_hip_scale_area_dev(c, f->fmt, f->d_src, f->src_w, f->src_h, n, w, h, d_clip, stream);
 	else failed = agmv_fmt_gather(c, f->fmt, f->src_w, f->src_h, f->d_src, n, d_index, npx, d_clip, stream);
@@ -1526,25 +1538,39 @@ void AGMV_CloseReader(AGMV_READER* rd)
 	free(rd);
 }
 
-/* A view of a clip encoded (include/agmv.h has the rules).  encode_view_refused is everything that needs no device, in the header's
-   order; *r receives the view resolved against the clip: count = its length, width x height = the window's own size. */
-static int encode_view_refused(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height, const AGMV_VIEW* view,
-                               u32 width, u32 height, AGMV_SCALE filter, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule,
-                               AGMV_VIEW* r)
+/* a rate as AGMV_EncodeViewRateDev takes it, reduced into *q (NULL: 1 : 1); non-zero for one the header refuses with -1 */
+static int rate_refused(const AGMV_RATE* rate, AGMV_RATE* q)
 {
+	unsigned a, b;
+	q->src = q->dst = 1; q->filter = AGMV_TIME_AREA;
+	if (!rate) return 0;
+	if (rate->src == 0 || rate->dst == 0 || (rate->filter != AGMV_TIME_NEAREST && rate->filter != AGMV_TIME_AREA)) return 1;
+	for (a = rate->src, b = rate->dst; b; ) { const unsigned t = a % b; a = b; b = t; }
+	q->src = rate->src / a; q->dst = rate->dst / a; q->filter = rate->filter;
+	return q->src > 65535u || q->dst > 65535u || (q->filter == AGMV_TIME_AREA && q->dst > q->src);
+}
+
+/* A view of a clip encoded (include/agmv.h has the rules).  encode_view_refused is everything that needs no device, in the header's
+   order; *r receives the view resolved against the clip: count = its length, width x height = the window's own size.  With a rate
+   (reduced; {1, 1} for none) the schedule is asked about the length of R, and a YUV source of odd size is never encoded in place. */
+static int encode_view_refused(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height, const AGMV_VIEW* view,
+                               const AGMV_RATE* q, u32 width, u32 height, AGMV_SCALE filter, AGMV_OPT opt, AGMV_QUALITY quality, AGMV_COMPRESSION compression,
+                               AGMV_SCHEDULE schedule, AGMV_VIEW* r)
+{
+	const int rated = q->src != 1 || q->dst != 1;
 	const int sized = width != 0 || height != 0;
 	const unsigned long long src_px = (unsigned long long)src_width * src_height;
 	int sw, sh, rc;
 	if (!known_pixfmt((int)fmt) || !filename || !d_frames || (sized && filter != AGMV_SCALE_NEAREST && filter != AGMV_SCALE_AREA) || view_refused(view)) return -1;
 	*r = view ? *view : WHOLE_FILE;
 	r->count = agmv_view_length(r->first, r->step, r->count, num_of_frames > 0xFFFFFFFFul ? 0xFFFFFFFFu : (uint32_t)num_of_frames);
-	rc = encode_args_refused(r->count, opt, quality, compression, schedule);
+	rc = encode_args_refused((u32)((unsigned long long)r->count * q->dst / q->src), opt, quality, compression, schedule);
 	if (rc == -1 || rc == -5) return rc;
 	if (src_width == 0 || src_height == 0 || src_width > 0xFFFFFFFFul || src_height > 0xFFFFFFFFul || src_px > (1ull << 28)) return -3;
 	if (r->width == 0) { r->width = (unsigned)src_width; r->height = (unsigned)src_height; }
 	if (r->x > src_width || r->width > src_width - r->x || r->y > src_height || r->height > src_height - r->y) return -3;
 	/* an NV12 / I420 window is cut out of the 2 x 2 cells of an even frame (agmv_hip_view_source_async); consecutive full frames are not cut */
-	if (AGMV_FMT_IS_YUV((int)fmt) && ((src_width | src_height) & 1) && !(r->step == 1 && r->width == src_width && r->height == src_height)) return -3;
+	if (AGMV_FMT_IS_YUV((int)fmt) && ((src_width | src_height) & 1) && (rated || !(r->step == 1 && r->width == src_width && r->height == src_height))) return -3;
 	scaled_size(opt, &sw, &sh);
 	if (!sized) {
 		if (sw ? r->width < 2 || r->height < 2 : bad_geometry(r->width, r->height)) return -3;
@@ -1560,12 +1586,13 @@ int AGMV_EncodeViewDev(const char* filename, const void* d_frames, AGMV_PIXFMT f
                        AGMV_SCHEDULE schedule)
 {
 	const int sized = width != 0 || height != 0;
+	static const AGMV_RATE same = {1, 1, AGMV_TIME_AREA};
 	AGMV_VIEW v;
 	clip_fill f = {sized ? (filter == AGMV_SCALE_AREA ? FILL_AREA : FILL_NEAREST) : FILL_VIEW, d_frames, (int)fmt, (uint32_t)src_width, (uint32_t)src_height, NULL, NULL,
 	               &g_encode_view_stats};
 	int rc, whole_frames;
 	memset(&g_encode_view_stats, 0, sizeof(g_encode_view_stats));
-	rc = encode_view_refused(filename, d_frames, fmt, num_of_frames, src_width, src_height, view, width, height, filter, opt, quality, compression, schedule, &v);
+	rc = encode_view_refused(filename, d_frames, fmt, num_of_frames, src_width, src_height, view, &same, width, height, filter, opt, quality, compression, schedule, &v);
 	if (rc) return audio_consumed(rc);
 	whole_frames = v.step == 1 && v.width == src_width && v.height == src_height;
 	if (whole_frames) f.d_src = (const u8*)d_frames + (size_t)v.first * agmv_fmt_frame_bytes((int)fmt, f.src_w, f.src_h);     /* consecutive full frames: read in place */
@@ -1574,6 +1601,54 @@ int AGMV_EncodeViewDev(const char* filename, const void* d_frames, AGMV_PIXFMT f
 	else rc = encode_materialised(filename, &f, v.count, sized ? width : v.width, sized ? height : v.height, frames_per_second, opt, quality, compression, schedule);
 	if (rc) memset(&g_encode_view_stats, 0, sizeof(g_encode_view_stats));
 	else g_encode_view_stats.frames = v.count;
+	return audio_consumed(rc);
+}
+
+/* The same at another frame rate (include/agmv.h has the rule): the clip that is materialised is R.  1 : 1 is the call above. */
+static AGMV_ENCODE_RATE_STATS g_encode_rate_stats;  /* of the last AGMV_EncodeViewRateDev */
+
+void AGMV_GetEncodeRateStats(AGMV_ENCODE_RATE_STATS* out) { if (out) *out = g_encode_rate_stats; }
+
+int AGMV_EncodeViewRateDev(const char* filename, const void* d_frames, AGMV_PIXFMT fmt, u32 num_of_frames, u32 src_width, u32 src_height, const AGMV_VIEW* view,
+                           const AGMV_RATE* rate, u32 width, u32 height, AGMV_SCALE filter, u32 frames_per_second, AGMV_OPT opt, AGMV_QUALITY quality,
+                           AGMV_COMPRESSION compression, AGMV_SCHEDULE schedule)
+{
+	const int sized = width != 0 || height != 0;
+	AGMV_RATE q;
+	AGMV_VIEW v;
+	clip_fill f = {sized ? (filter == AGMV_SCALE_AREA ? FILL_AREA : FILL_NEAREST) : FILL_VIEW, d_frames, (int)fmt, (uint32_t)src_width, (uint32_t)src_height, NULL, &v,
+	               &g_encode_view_stats, &q};
+	unsigned long long m;
+	int rc;
+	memset(&g_encode_rate_stats, 0, sizeof(g_encode_rate_stats));
+	if (rate_refused(rate, &q)) {
+		memset(&g_encode_view_stats, 0, sizeof(g_encode_view_stats));
+		return audio_consumed(-1);
+	}
+	if (q.src == 1 && q.dst == 1) {
+		rc = AGMV_EncodeViewDev(filename, d_frames, fmt, num_of_frames, src_width, src_height, view, width, height, filter, frames_per_second, opt, quality, compression,
+		                        schedule);
+		if (!rc) {
+			g_encode_rate_stats.frames_in = g_encode_rate_stats.frames_out = g_encode_view_stats.frames;
+			g_encode_rate_stats.frame_reads = g_encode_view_stats.frames;
+		}
+		return rc;
+	}
+	memset(&g_encode_view_stats, 0, sizeof(g_encode_view_stats));
+	rc = encode_view_refused(filename, d_frames, fmt, num_of_frames, src_width, src_height, view, &q, width, height, filter, opt, quality, compression, schedule, &v);
+	if (rc) return audio_consumed(rc);
+	m = (unsigned long long)v.count * q.dst / q.src;
+	f.view_len = v.count;
+	f.src_frames = num_of_frames > 0xFFFFFFFFul ? 0xFFFFFFFFu : (uint32_t)num_of_frames;
+	rc = encode_materialised(filename, &f, (u32)m, sized ? width : v.width, sized ? height : v.height, frames_per_second, opt, quality, compression, schedule);
+	if (rc) memset(&g_encode_view_stats, 0, sizeof(g_encode_view_stats));
+	else {
+		g_encode_view_stats.frames = (unsigned)m;
+		g_encode_rate_stats.frames_in = v.count;
+		g_encode_rate_stats.frames_out = (unsigned)m;
+		/* AREA: output j reads taps (j sn) div dn .. ((j + 1) sn - 1) div dn, which is one more than the step of (j sn) div dn unless dn divides j + 1 */
+		g_encode_rate_stats.frame_reads = q.filter == AGMV_TIME_NEAREST ? m : m * q.src / q.dst + m - m / q.dst;
+	}
 	return audio_consumed(rc);
 }
 

@@ -9,6 +9,7 @@
 #include "agmv_hip_stabilise.h"
 #include "agmv_hip_view.h"
 #include "agmv_hip_view_source.h"
+#include "agmv_hip_time.h"
 #include "agmv_internal.h"
 #include "agmv_reader.h"
 

@@ -1,6 +1,6 @@
 """ctypes binding of include/agmv_hip.h (the signatures are abi.HIP), include/agmv_hip_view.h (abi.HIP_VIEW),
-include/agmv_hip_view_source.h (abi.HIP_VIEW_SOURCE), include/agmv_hip_stabilise.h (abi.HIP_STABILISE) and
-include/agmv_hip_deblock.h (abi.HIP_DEBLOCK).
+include/agmv_hip_view_source.h (abi.HIP_VIEW_SOURCE), include/agmv_hip_stabilise.h (abi.HIP_STABILISE),
+include/agmv_hip_deblock.h (abi.HIP_DEBLOCK) and include/agmv_hip_time.h (abi.HIP_TIME).
 
 The product is the shared library; this module only marshals pointers.  torch is used for
 device memory and streams (plumbing).  Every failure is loud: a missing library raises
@@ -57,6 +57,7 @@ def load_library(path=None):
     abi.bind(L, abi.HIP_VIEW_SOURCE, missing_ok=path is not None)
     abi.bind(L, abi.HIP_STABILISE, missing_ok=path is not None)
     abi.bind(L, abi.HIP_DEBLOCK, missing_ok=path is not None)
+    abi.bind(L, abi.HIP_TIME, missing_ok=path is not None)
     _libs[p] = L
     return L
 
@@ -89,6 +90,9 @@ def yuvfmt(fmt, yuv=None, full_range=False):
         return fmt
     raise ValueError("fmt: one of %s (or its value with flags) is needed, got %r" % (", ".join(sorted(YUVFMT)), fmt))
 
+
+# AGMV_TIME of include/agmv.h: name -> value
+TIME = {"nearest": 1, "area": 2}
 
 # AGMV_PCMFMT of include/agmv.h: name -> value
 PCMFMT = {"s16": 1, "u8": 2, "f32p": 3}
@@ -816,6 +820,41 @@ class AgmvHip:
         _check_vec("view_source: out", out, count * win_w * win_h)
         s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
         self._ck(self.L.agmv_hip_view_source_async(self.ctx, fmt, src.data_ptr(), w, h, first, step, count, x, y, win_w, win_h, out.data_ptr(), s))
+        return out
+
+    # ------------------------------------------------------------------ such a view at another frame rate (agmv_hip_time_frames_async of include/agmv_hip_time.h)
+    def time_frames(self, fmt, src, w, h, n_frames, first, step, view_len, x, y, win_w, win_h, rate, time="area", j0=0, count=None, out=None,
+                    yuv=None, full_range=False, stream=None):
+        """src: clip of n_frames whole frames of w x h pixels in fmt (any name of PIXFMT or YUVFMT, or its value) -> int32
+        [count, win_h, win_w] of 0x00RRGGBB: frames j0 .. j0 + count - 1 (count None: to the last) of the view view_source gives for
+        first, step, count=view_len and the window, resampled in time at rate = (src, dst), a reduced pair, with the filter
+        time = "area" or "nearest" (AGMV_RATE of include/agmv.h holds the rule), or `out`, a contiguous CUDA int32 tensor (or view at
+        any element offset) of at least that many words (agmv_hip_time_frames_async) on `stream` (a torch stream; None = torch's
+        current one).  Nothing waits."""
+        import torch
+        w, h, n_frames, first, step, view_len, x, y, win_w, win_h, j0 = (int(v) for v in (w, h, n_frames, first, step, view_len, x, y, win_w, win_h, j0))
+        if time not in TIME:
+            raise ValueError("time_frames: time %r is unknown: one of %s is needed" % (time, ", ".join("\"%s\"" % k for k in sorted(TIME))))
+        rs, rd = (int(v) for v in rate)
+        if rs < 1 or rd < 1:
+            raise ValueError("time_frames: rate must be a pair of ints above 0, got %r" % (rate,))
+        if step < 1 or view_len < 0 or first < 0 or n_frames < 0 or j0 < 0:
+            raise ValueError("time_frames: first >= 0, step >= 1, view_len >= 0 and j0 >= 0 are needed, got %d, %d, %d, %d" % (first, step, view_len, j0))
+        if count is None:
+            count = max(view_len * rd // rs - j0, 0)
+        count = int(count)
+        if fmt in YUVFMT or (isinstance(fmt, int) and (fmt & 0xFF) in YUVFMT.values()):
+            fmt = self._check_yuv("time_frames: src", fmt, src, w, h, n_frames, yuv, full_range)
+        else:
+            if yuv is not None or full_range:
+                raise ValueError("time_frames: yuv= and full_range= belong to fmt \"nv12\" and \"i420\", not to fmt %r" % (fmt,))
+            fmt = self._check_clip("time_frames: src", fmt, src, n_frames * self.pixfmt_frame_bytes(fmt, w * h))
+        if out is None:
+            out = torch.empty((count, win_h, win_w), dtype=torch.int32, device=src.device)
+        _check_vec("time_frames: out", out, count * win_w * win_h)
+        s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        self._ck(self.L.agmv_hip_time_frames_async(self.ctx, fmt, src.data_ptr(), w, h, n_frames, first, step, view_len, x, y, win_w, win_h, rs, rd, TIME[time], j0,
+                                                   count, out.data_ptr(), s))
         return out
 
     # ------------------------------------------------------------------ normalised float tensor clips (AGMV_TENSORFMT of include/agmv.h)

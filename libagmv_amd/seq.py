@@ -1,5 +1,5 @@
 """Whole .agmv sequences from and to frames in GPU memory: ctypes calls of AGMV_EncodeFramesFmtDev / AGMV_EncodeFramesScaledDev /
-AGMV_EncodeViewDev / AGMV_DecodeFramesFmtDev / AGMV_DecodeFramesScaledDev / AGMV_EncodeFramesTensorDev / AGMV_DecodeFramesTensorDev (include/agmv.h, libagmv.so).  No logic here: the schedules, the container, both LZ stages and the reading and writing of the
+AGMV_EncodeViewDev / AGMV_EncodeViewRateDev / AGMV_DecodeFramesFmtDev / AGMV_DecodeFramesScaledDev / AGMV_EncodeFramesTensorDev / AGMV_DecodeFramesTensorDev (include/agmv.h, libagmv.so).  No logic here: the schedules, the container, both LZ stages and the reading and writing of the
 caller's pixel layout are the library's; torch holds the frames.  The frames live on the library's own device (env AGMV_DEVICE,
 default 0).
 Reader (AGMV_OpenReaderDev ... of include/agmv_reader.h) is a file opened once and read in pieces with the decoder's state kept: what
@@ -36,7 +36,7 @@ import os
 
 from . import abi
 from .abi import AGMV_FRAME_QUALITY, AGMV_INFO  # noqa: F401  (importable from here as before)
-from .hip import HERE, PIXFMT, TENSORFMT, YUVFMT, HipUnavailable, pcmfmt, pixfmt, tensor_normalisation, yuvfmt
+from .hip import HERE, PIXFMT, TENSORFMT, TIME, YUVFMT, HipUnavailable, pcmfmt, pixfmt, tensor_normalisation, yuvfmt
 
 SCHEDULE_FULL, SCHEDULE_PDIFS, SCHEDULE_ADAPTIVE = 1, 2, 3
 SCALE = {"nearest": 1, "area": 2}          # AGMV_SCALE of include/agmv.h, which defines both filters
@@ -149,6 +149,26 @@ def _scale_target(size, scale):
     return SCALE[scale], size[0], size[1]
 
 
+def _time_rate(rate, time):
+    """the AGMV_RATE of encode_frames' rate= and time=, or None for rate=None; touches neither the library nor the device"""
+    import math
+    if not isinstance(time, str) or time not in TIME:
+        raise ValueError("encode_frames: time %r is unknown: one of %s is needed" % (time, ", ".join("\"%s\"" % k for k in sorted(TIME))))
+    if rate is None:
+        if time != "area":
+            raise ValueError("encode_frames: time=%r needs rate=(src, dst): without a rate nothing is resampled" % (time,))
+        return None
+    if not (isinstance(rate, (tuple, list)) and len(rate) == 2 and all(_is_int(v) and v >= 1 for v in rate)):
+        raise ValueError("encode_frames: rate must be (src, dst), two ints of 1 or more, got %r" % (rate,))
+    g = math.gcd(*rate)
+    src, dst = rate[0] // g, rate[1] // g
+    if src > 65535 or dst > 65535:
+        raise ValueError("encode_frames: rate %r reduces to %d : %d, above 65535" % (tuple(rate), src, dst))
+    if time == "area" and dst > src:
+        raise ValueError("encode_frames: rate %r raises the frame rate, which time=\"area\" does not do: time=\"nearest\" duplicates frames" % (tuple(rate),))
+    return abi.AGMV_RATE(rate[0], rate[1], TIME[time])
+
+
 def _track_geometry(audio, sample_rate):
     """(AGMV_PCMFMT value, samples per channel, channels) of encode_frames' audio= tensor; touches neither the library nor the device"""
     import torch
@@ -166,7 +186,7 @@ def _track_geometry(audio, sample_rate):
 
 def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedule=SCHEDULE_PDIFS, fmt=None, yuv=None, full_range=False,
                   size=None, scale="area", palette_refine=None, dither=None, audio=None, sample_rate=None, mean=None, std=None, stabilise=None,
-                  select=None, crop=None, fit=None):
+                  select=None, crop=None, fit=None, rate=None, time="area"):
     """frames: contiguous CUDA tensor of n frames on the library's device, in the layout `fmt` (see the module text; None = inferred
     from the tensor, which never gives "nv12" or "i420") -> the file at `path`.  yuv ("bt601", the default, or "bt709") and
     full_range go with the two YUV layouts only.  size=(h, w), in tensor order, scales the clip to that size first
@@ -192,7 +212,13 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
     odd offsets and sizes included, for "nv12" and "i420" too; fit="crop" needs size= and no crop= and takes fit_window() of the
     frame and the target, the largest centred window of the target's aspect.  The file is that of the contiguous XRGB32 clip of the
     selected windows, scaled to size= where that is given; fps is written as given.  An empty selection is refused, and none of
-    the three goes with a tensor clip.  encode_view_stats() says what the call materialised."""
+    the three goes with a tensor clip.  encode_view_stats() says what the call materialised.
+    rate=(src, dst) encodes the clip -- or the view select=, crop=, fit= and size= describe -- at another frame rate
+    (AGMV_EncodeViewRateDev of include/agmv.h, which holds the rule): src frames become dst frames, 60 fps to 24 is rate=(5, 2).
+    time "area", the default, is the exact box filter in time and only lowers the rate; "nearest" takes the frame under each
+    target interval's centre and may also duplicate frames.  The two values are reduced by their gcd and must then be at most 65535.
+    The file is that of the resampled XRGB32 clip; fps is written as given.  time= needs rate=, and rate= does not go with a tensor
+    clip.  encode_rate_stats() says how many frames went in and came out."""
     import torch
     select, crop = _decode_selection(select, crop, who="encode_frames", name="select")
     if fit is not None and not (fit == "crop" and size is not None and crop is None):
@@ -204,8 +230,11 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
     if palette_refine is not None and not (isinstance(palette_refine, int) and not isinstance(palette_refine, bool) and 1 <= palette_refine <= 64):
         raise ValueError("encode_frames: palette_refine must be None or an int from 1 to 64, got %r" % (palette_refine,))
     target = _scale_target(size, scale)
+    rated = _time_rate(rate, time)
     tensor = _tensor_clip(frames, fmt, mean, std, "encode_frames")
     if tensor is not None:
+        if rated is not None:
+            raise ValueError("encode_frames: rate= does not go with a tensor clip (fmt %r)" % (fmt,))
         if yuv is not None or full_range or target is not None:
             raise ValueError("encode_frames: yuv=, full_range= and size= do not go with a tensor clip (fmt %r)" % (fmt,))
         if select is not None or crop is not None or fit is not None:
@@ -254,6 +283,14 @@ def encode_frames(path, frames, fps=24, opt=3, quality=3, compression=1, schedul
                 raise ValueError("AGMV_EncodeFramesTensorDev refused its arguments (%d): %d frames of %dx%d, mean %r, std %r, opt %d, schedule %d"
                                  % (rc, n, w, h, mean, std, opt, schedule))
             return
+        if rated is not None:
+            filt, th, tw = target if target is not None else (0, 0, 0)
+            rc = L.AGMV_EncodeViewRateDev(os.fsencode(path), frames.data_ptr(), v, n, w, h, C.byref(view) if view is not None else None, C.byref(rated), tw, th, filt,
+                                          fps, opt, quality, compression, schedule)
+            if rc:
+                raise ValueError("AGMV_EncodeViewRateDev refused its arguments (%d): %d frames of %dx%d, rate %r (%s), select %r, crop %r, size %r (%s), opt %d, schedule %d"
+                                 % (rc, n, w, h, tuple(rate), time, select, crop, size, scale, opt, schedule))
+            return
         if view is not None:
             filt, th, tw = target if target is not None else (0, 0, 0)
             rc = L.AGMV_EncodeViewDev(os.fsencode(path), frames.data_ptr(), v, n, w, h, C.byref(view), tw, th, filt, fps, opt, quality, compression, schedule)
@@ -297,6 +334,15 @@ def encode_view_stats():
     st = abi.AGMV_ENCODE_VIEW_STATS()
     load_library().AGMV_GetEncodeViewStats(C.byref(st))
     return int(st.frames), int(st.clip_bytes), int(st.staging_bytes)
+
+
+def encode_rate_stats():
+    """(frames_in, frames_out, frame_reads) of the last encode_frames(rate=) of this process (AGMV_GetEncodeRateStats of include/agmv.h):
+    the length of the view, the frames of the file, and the source frames read, one per tap with a weight above 0; all 0 behind a
+    refused call"""
+    st = abi.AGMV_ENCODE_RATE_STATS()
+    load_library().AGMV_GetEncodeRateStats(C.byref(st))
+    return int(st.frames_in), int(st.frames_out), int(st.frame_reads)
 
 
 def _decode_target(size, scale):
